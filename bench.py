@@ -14,6 +14,10 @@ process and passes its output and exit code through) the reads are sharded acros
 ranks and the DB is replicated: there is no data-path collective (weak scaling);
 torch.distributed is used for the barriers and the max-over-ranks time only.
 
+--dump-outputs DIR (rank 0): after the timed steps, what the last timed step handed its caller, as DIR/<name>.npy
+(dump_outputs).  The workload is seeded: the same arguments give the same inputs on every run, so that two builds
+can be compared output for output.
+
 Rank 0 prints ONE JSON line.  Extra objects (rank 0, N=1 where they cost time):
   roofline              -- achieved algorithmic GB/s of the placement kernel (HIP events on the
                            launch stream, inside the timed region) against the HBM peak; `bound`
@@ -112,6 +116,9 @@ def parse_args():
                          "kmer-shard (BASELINE configs[4]: --leaves 5000 --reads-per-step 4096): rank g builds and "
                          "holds only the lists of the codes with code %% G == g, every rank accumulates ALL reads of "
                          "the step, one all-to-all + sum of the per-read branch vectors, then each rank finishes its reads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the row count of every read; "
+                         "the rows of a fixed, seeded sample of reads) as DIR/<name>.npy, float32/float64 (rank 0)")
     args = ap.parse_args()
     if args.reads_per_step is None:
         args.reads_per_step = 65536 if args.mode == "kmer-shard" else 1_000_000
@@ -200,6 +207,46 @@ def cpu_baseline(db, data, offs, target_seconds: float):
                       "(node-chained map key -> vector of postings), `variants.direct_index` = CSR lookup"}
     orc.use_hash_map(False)
     return out["all"], out["one"]
+
+
+DUMP_SAMPLE_READS = 65536       # reads whose rows --dump-outputs writes (all of them when a step has no more)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, d_rows, d_nrows, n_out: int, keep: int) -> list:
+    """What the last timed step handed its caller (include/epik_amd.h: rows[n * keep_at_most] of {branch, score, lwr},
+    n_rows[n]), as .npy files in `out_dir`:
+      n_rows        float32 [n_out]            the row count of every read the step placed;
+      sample_reads  float64 [s]                the reads whose rows follow: all of them if n_out <= DUMP_SAMPLE_READS,
+                                               else a fixed seeded sample, ascending;
+      branch        float64 [s, keep_at_most]  -1 past a read's row count;
+      score         float32 [s, keep_at_most]  0 past a read's row count;
+      lwr           float64 [s, keep_at_most]  0 past a read's row count.
+    Returns the names written."""
+    import torch
+
+    from epik_amd import capi
+    n_rows = d_nrows[:n_out].cpu().numpy().view(np.uint32)
+    if n_out <= DUMP_SAMPLE_READS:
+        sample = np.arange(n_out, dtype=np.int64)
+    else:
+        sample = np.sort(np.random.default_rng(2024).choice(n_out, size=DUMP_SAMPLE_READS, replace=False))
+    index = torch.from_numpy(sample).to(d_rows.device)
+    raw = d_rows.view(torch.uint8)[:n_out * keep * capi.PLACEMENT.itemsize].view(n_out, -1).index_select(0, index)
+    rows = np.ascontiguousarray(raw.cpu().numpy()).view(capi.PLACEMENT).reshape(len(sample), keep)
+    valid = np.arange(keep)[None, :] < n_rows[sample].astype(np.int64)[:, None]
+    arrays = {"n_rows": n_rows.astype(np.float32),
+              "sample_reads": sample.astype(np.float64),
+              "branch": np.where(valid, rows["branch"].astype(np.float64), -1.0),
+              "score": np.where(valid, rows["score"], np.float32(0)).astype(np.float32),
+              "lwr": np.where(valid, rows["lwr"], 0.0).astype(np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes for {n_out} reads, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sorted(arrays)
 
 
 def end_to_end(db, tree, data, read_length: int, n_reads: int, jobs: int):
@@ -693,6 +740,10 @@ def main():
         # (a pipelined step: the halves of consecutive batches run side by side on two streams -- the events around a
         # step on the launch stream see one of them; the step's share of the timed region is the launch time)
         kernel_ms = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # (before anything else launches into d_rows / d_nrows: the last timed step's rows, the reads this rank finished)
+        names = dump_outputs(args.dump_outputs, d_rows, d_nrows, (end - begin) if kmer_shard else n, keep)
+        log(f"outputs of the last timed step: {', '.join(names)} in {args.dump_outputs}")
     # ---- what a reader of the line needs to see that N ranks on N devices really took part -------------------
     evidence = {"rank": rank, "local_rank": local_rank, "device": int(torch.cuda.current_device()),
                 "pci_bus_id": pci_bus_id(int(torch.cuda.current_device())), "host": socket.gethostname(),

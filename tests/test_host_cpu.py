@@ -63,25 +63,27 @@ def test_launcher_builds_reference_argv():
         assert flag in out.stdout
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/epik.py"), reason="the reference is not present on this machine")
+def _reference_records():
+    """What the reference's own launcher and comparison function gave on these tests' inputs, recorded where the
+    reference is present (tests/golden/make_reference_records_golden.py)."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_records.json")) as fh:
+        return json.load(fh)
+
+
 @pytest.mark.parametrize("states,max_ram", [("nucl", None), ("amino", "4G")])
-def test_launcher_argv_equals_the_reference_launcher(monkeypatch, capsys, states, max_ram):
-    """The reference's own `place_queries` (epik.py:73-98) with subprocess.call intercepted,
-    beside ours: same flags, same order, same values; ours only picks its own binary."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("reference_epik", "/root/reference/epik.py")
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    seen = []
-    monkeypatch.setattr(ref.subprocess, "call", lambda command: seen.append(list(command)) or 0)
-    ref.place_queries("db.ipk", states, 1.5, 0.8, "out", 3, max_ram, "q.fasta")
-    capsys.readouterr()
+def test_launcher_argv_equals_the_reference_launcher(states, max_ram):
+    """The argv the reference's own `place_queries` (epik.py:73-98) hands to subprocess.call, beside ours: same
+    flags, same order, same values; ours only picks its own binary."""
+    launcher = _reference_records()["launcher"]
+    call = launcher["call"]
+    (seen,) = [c["argv"] for c in launcher["cases"] if c["states"] == states and c["max_ram"] == max_ram]
     sys.path.insert(0, ROOT)
     import epik
-    ours = epik.driver_command(database="db.ipk", states=states, omega=1.5, mu=0.8, outputdir="out", threads=3,
-                               max_ram=max_ram, gpus=1, input_file="q.fasta")   # one GPU: no extra flag
-    assert os.path.basename(ours[0]) == os.path.basename(seen[0][0])      # epik-dna / epik-aa
-    assert ours[1:] == seen[0][1:]
+    ours = epik.driver_command(database=call["database"], states=states, omega=call["omega"], mu=call["mu"],
+                               outputdir=call["outputdir"], threads=call["threads"], max_ram=max_ram, gpus=1,
+                               input_file=call["input_file"])   # one GPU: no extra flag
+    assert os.path.basename(ours[0]) == seen[0]      # epik-dna / epik-aa
+    assert ours[1:] == seen[1:]
 
 
 def test_dbfile_roundtrip_and_filters(tmp_path):
@@ -225,40 +227,14 @@ def test_jplace_write_read_and_diff(tmp_path):
     assert "q1" in jplace_diff.diff_legacy(parsed, leg)
 
 
-REFERENCE_DIFFER = "/root/reference/scripts/jplace_diff.py"
-
-
-@pytest.mark.skipif(not os.path.exists(REFERENCE_DIFFER), reason="the reference is not present on this machine")
-def test_legacy_differ_agrees_with_the_reference_script(tmp_path, capsys):
+def test_legacy_differ_agrees_with_the_reference_script(tmp_path):
     """`--legacy` against the reference's own comparison function (its CLI wrapper is broken, the
-    function behind it is callable), on jplace pairs with every kind of disagreement."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("reference_jplace_diff", REFERENCE_DIFFER)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    rng = np.random.default_rng(7)
-    names = [f"s{i}" for i in range(60)]
-
-    def rows(n):
-        edges = rng.choice(40, size=n, replace=False)
-        return [dict(edge_num=int(e), likelihood=float(-rng.uniform(0.5, 6.0)), like_weight_ratio=float(rng.random()),
-                     distal_length=0.1, pendant_length=0.2) for e in edges]
-
-    first = {name: rows(int(rng.integers(0, 6))) for name in names}
-    second = json.loads(json.dumps(first))
-    for i, name in enumerate(names):
-        r = second[name]
-        kind = i % 6
-        if kind == 1 and r:
-            r[0]["likelihood"] += 5e-5           # inside the 1e-4 window
-        elif kind == 2 and r:
-            r[0]["likelihood"] -= 0.5            # outside: compared edge by edge on 10**likelihood
-        elif kind == 3 and r:
-            r[0]["edge_num"] = 99                # another edge with the same likelihood: still a "match" there
-        elif kind == 4 and r:
-            r.pop()                              # a row missing
-        elif kind == 5:
-            r.append(dict(edge_num=77, likelihood=-9.0, like_weight_ratio=0.0, distal_length=0.0, pendant_length=0.0))
+    function behind it is callable), on jplace pairs with every kind of disagreement: the pairs and the
+    reference's verdicts on them as recorded (tests/golden/make_reference_records_golden.py)."""
+    record = _reference_records()["legacy_differ"]
+    first, second = record["first"], record["second"]
+    names = list(first)
+    assert len(names) == record["names"] == 60
 
     def write(path, placed):
         doc = {"fields": jplace.FIELDS, "version": 3, "tree": "(A:1{0},B:2{1}):0{2};", "metadata": {},
@@ -271,10 +247,7 @@ def test_legacy_differ_agrees_with_the_reference_script(tmp_path, capsys):
     write(a, first)
     write(b, second)
     for only_best in (False, True):
-        capsys.readouterr()
-        ref.jplace_diff.callback(a, b, only_best)
-        out = capsys.readouterr().out
-        matched = int(out.strip().splitlines()[-1].split("/")[0])
+        matched = record["reference_matched"][str(only_best).lower()]
         ours = jplace_diff.diff_legacy(jplace.read_jplace(a), jplace.read_jplace(b), only_best)
         assert matched == len(names) - len(ours), (only_best, matched, ours)
 
