@@ -6,8 +6,9 @@ command taking -i/--database, -s/--states {nucl,amino}, --omega (1.5), --mu (1.0
 -o/--outputdir, --threads (1), --max-ram and one FASTA file.  Like the reference
 (epik.py:73-98) it only selects the native driver -- `epik-dna` for nucl, `epik-aa` for
 amino -- translates the options into that driver's flags (-d -q -j --omega --mu -o
-[--max-ram]) and runs it.  One option is new: --gpus, the number of MI355X devices the
-reads are sharded across.
+[--max-ram]) and runs it.  New options: --gpus, the number of MI355X devices the reads are
+sharded across; --db-shard; and --strand, which strand of each nucleotide read is placed
+(forward as given, its reverse complement, or both and the better one per read).
 """
 from __future__ import annotations
 
@@ -41,6 +42,9 @@ PLACE_OPTIONS = [
     (("--db-shard",), dict(type=int, default=1, show_default=True,
                            help="Cut the database in this many shards by k-mer code, one per device (a database "
                                 "larger than one device's memory); 1 = the whole database on every device.")),
+    (("--strand",), dict(type=click.Choice(["forward", "reverse", "both"]), default="forward", show_default=True,
+                         help="Strand of each nucleotide read to place: as given, its reverse complement, or both and "
+                              "the better one per read (then also strands_<input>.tsv, one name<TAB>+|- per read).")),
 ]
 
 
@@ -54,7 +58,8 @@ def driver_path(states: str) -> str:
     return os.path.join(HERE, "epik_amd", "bin", name)
 
 
-def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpus, input_file, db_shard=1):
+def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpus, input_file, db_shard=1,
+                   strand="forward"):
     argv = [driver_path(states), "-d", str(database), "-q", str(input_file), "-j", str(threads),
             "--omega", str(omega), "--mu", str(mu), "-o", str(outputdir)]
     if max_ram:
@@ -63,6 +68,8 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--gpus", str(gpus)]
     if db_shard != 1:
         argv += ["--db-shard", str(db_shard)]
+    if strand != "forward":
+        argv += ["--strand", str(strand)]
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 

@@ -51,6 +51,9 @@ EXPORTS = (
     "epik_amd_placer_launch_info",
     "epik_amd_placer_set_timing",
     "epik_amd_placer_last_kernel_ms",
+    "epik_amd_placer_strand_workspace_bytes",
+    "epik_amd_placer_place_strands_device",
+    "epik_amd_placer_place_strands",
 )
 
 
@@ -122,6 +125,10 @@ MAX_SHARDS = 16
 #: count of a partial list that found no room in d_entries
 LIST_OVERFLOW = 0xFFFFFFFF
 PATH_WAVE, PATH_TEAM_ONE_KERNEL, PATH_TEAM_STREAMED = 0, 1, 2
+
+#: strand modes of epik_amd_placer_place_strands[_device], and their names in Placer / epik.py / epik-dna --strand
+STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
+STRANDS = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
 
 #: n_rows of a read with more k-mers than the counts of a device-pointer launch hold
 ROWS_COUNTS_TOO_NARROW = 0xFFFFFFFF
@@ -234,6 +241,12 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_placer_set_timing.argtypes = [vp, i32]
     lib.epik_amd_placer_last_kernel_ms.restype = i32
     lib.epik_amd_placer_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    lib.epik_amd_placer_strand_workspace_bytes.restype = i32
+    lib.epik_amd_placer_strand_workspace_bytes.argtypes = [vp, u64, u64, ctypes.c_uint32, ctypes.POINTER(u64)]
+    lib.epik_amd_placer_place_strands_device.restype = i32
+    lib.epik_amd_placer_place_strands_device.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, u64, vp, vp, vp, vp, vp]
+    lib.epik_amd_placer_place_strands.restype = i32
+    lib.epik_amd_placer_place_strands.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, vp, vp, vp]
     _lib = lib
     return lib
 

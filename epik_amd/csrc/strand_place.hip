@@ -1,0 +1,383 @@
+// strand_place.hip -- nucleotide reads placed on either strand: epik_amd_placer_strand_workspace_bytes,
+// epik_amd_placer_place_strands_device, epik_amd_placer_place_strands (include/epik_amd.h).
+//
+// No reference counterpart: the reference places a read in the orientation it arrives in (place.cpp:294,
+// to_kmers over the read as given).  Short reads of a shotgun sample come from either strand, and a read of the
+// opposite strand finds almost none of its k-mers in the database.
+//
+// Semantics:
+//   * The complement is defined on character CLASSES: state s <-> 3 - s in the A C G T order of
+//     epik_amd/alphabet.py -- the same unverified i2l state order everything else here rests on.  On a class
+//     bitmask that is a 4-bit bit reversal: R (AG) <-> Y (CT), K <-> M, B <-> V, D <-> H; S, W and N map to
+//     themselves; U complements to A; a character of class 0 (invalid) stays invalid.
+//   * The reverse strand of read r is the read whose character j has class bitrev4(char_class[r[len-1-j]]).  Its
+//     rows are exactly those of the host-side reverse complement of r, the ambiguous-k-mer path included (whose order
+//     is the k-mer position in that reversed read).
+//   * `both`: F = the forward result, R = the reverse one.  R is chosen when R has rows and either F has none or
+//     R[0].score > F[0].score (float32, strict); else F -- a tie goes to forward (palindromic reads, reads without
+//     hits on either strand).  Both strands have the same number of k-mers, so n_rows == 0 (shorter than k) and
+//     EPIK_AMD_ROWS_COUNTS_TOO_NARROW always agree and report forward.  Rows, n_rows and k-mer counts are those of
+//     the chosen strand, unchanged: LWRs are not renormalised across strands.  The scores compare because both
+//     strands divide by the same n_kmers in the correction.
+//   * Strand byte per read: 0 forward (+), 1 reverse (-).
+//   * Nucleotide handles only (alphabet_size 4), whole databases only (no k-mer-space shard).
+//
+// Device side: the placement itself is epik_amd_placer_place_device, unchanged (every kernel and path it takes);
+// here only two kernels around it:
+//   revcomp_kernel        the reverse-complemented bytes of the batch into the workspace, at the caller's offsets
+//                         (reversal stays inside each read's range, so d_seq_offsets serves both strands);
+//   strand_select_kernel  forward placed into the caller's buffers, reverse into the workspace: overwrites the reads
+//                         where reverse wins and writes the strand byte of every read.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "placer_impl.hpp"
+
+namespace {
+
+using epik_amd::fail_with;
+
+#define STRAND_TRY(expr)                                                                                 \
+    do {                                                                                                 \
+        const hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return fail_with(EPIK_AMD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+constexpr uint32_t kWave = 64;
+constexpr uint32_t kBlockWaves = 4;
+constexpr uint32_t kBlock = kWave * kBlockWaves;
+constexpr uint64_t kMaxBlocks = 8192;  // (grid-stride beyond: a million reads is 256 K waves of work either way)
+constexpr uint64_t kAlign = 256;
+// the host entry's device budget per chunk (EPIK_AMD_STRAND_CHUNK_READS: fewer reads per chunk, for tests)
+constexpr uint64_t kChunkReads = 1u << 18, kChunkBytes = 64u << 20;
+
+inline uint64_t align_up(uint64_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
+inline uint32_t bitrev4(uint32_t c) { return (c & 1u) << 3 | (c & 2u) << 1 | (c & 4u) >> 1 | (c & 8u) >> 3; }
+__host__ __device__ inline bool has_rows(uint32_t n_rows) { return n_rows != 0 && n_rows != EPIK_AMD_ROWS_COUNTS_TOO_NARROW; }
+
+// For every byte, a byte of the complemented class (by value in the kernel's arguments: no allocation)
+struct ComplementMap {
+    uint8_t byte[256];
+};
+
+__global__ __launch_bounds__(kBlock) void revcomp_kernel(const uint8_t *__restrict__ seqs,
+                                                         const uint64_t *__restrict__ seq_offsets, uint64_t n,
+                                                         uint8_t *__restrict__ out, uint64_t out_cap, ComplementMap map)
+{
+    __shared__ uint8_t lut[256];
+    lut[threadIdx.x] = map.byte[threadIdx.x];  // (kBlock == 256)
+    __syncthreads();
+    const uint32_t lane = threadIdx.x % kWave;
+    const uint64_t waves = (uint64_t)gridDim.x * kBlockWaves;
+    // A wave takes 64 reads at a time -- their offsets in one load -- and reverses them one after the other, in
+    // tiles of 64 bytes, four tiles' loads in flight before their stores; reads of any length.
+    for (uint64_t r0 = ((uint64_t)blockIdx.x * kBlockWaves + threadIdx.x / kWave) * kWave; r0 < n; r0 += waves * kWave) {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(kWave, n - r0);
+        const uint64_t my_b = lane < cnt ? seq_offsets[r0 + lane] : 0, my_e = lane < cnt ? seq_offsets[r0 + lane + 1] : 0;
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const uint64_t b = __shfl(my_b, (int)j), e = __shfl(my_e, (int)j);
+            if (e < b || e > out_cap) continue;  // (outside the workspace the caller sized: nothing is written)
+            const uint64_t len = e - b;
+            for (uint64_t t0 = lane; t0 < len; t0 += 4 * kWave) {
+                uint32_t c[4];
+#pragma unroll
+                for (uint32_t u = 0; u < 4; ++u) {
+                    const uint64_t t = t0 + u * kWave;
+                    c[u] = t < len ? seqs[e - 1 - t] : 0u;
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < 4; ++u) {
+                    const uint64_t t = t0 + u * kWave;
+                    if (t < len) out[b + t] = lut[c[u]];
+                }
+            }
+        }
+    }
+}
+
+// One wavefront per 64 reads: lane l decides for read 64 g + l, then the wave copies the rows of the reads where
+// reverse won, 64 row slots at a time.  Every decision of the wave is loaded before any of its stores, and no other
+// wave touches these reads: the forward rows a decision reads are never overwritten under it.
+__global__ __launch_bounds__(kBlock) void strand_select_kernel(uint64_t n, uint32_t keep,
+                                                               epik_amd_placement *__restrict__ rows,
+                                                               uint32_t *__restrict__ n_rows,
+                                                               uint32_t *__restrict__ counts,
+                                                               const epik_amd_placement *__restrict__ rev_rows,
+                                                               const uint32_t *__restrict__ rev_n_rows,
+                                                               const uint32_t *__restrict__ rev_counts,
+                                                               uint8_t *__restrict__ strand)
+{
+    const uint32_t lane = threadIdx.x % kWave;
+    const uint64_t groups = (n + kWave - 1) / kWave, waves = (uint64_t)gridDim.x * kBlockWaves;
+    for (uint64_t g = (uint64_t)blockIdx.x * kBlockWaves + threadIdx.x / kWave; g < groups; g += waves) {
+        const uint64_t first = g * kWave, i = first + lane;
+        bool take = false;
+        uint32_t nr = 0;
+        if (i < n) {
+            const uint32_t nf = n_rows[i];
+            nr = rev_n_rows[i];
+            if (has_rows(nr)) take = !has_rows(nf) || rev_rows[i * keep].score > rows[i * keep].score;
+        }
+        const unsigned long long mask = __ballot(take);
+        if (i < n) {
+            if (strand) strand[i] = take ? 1 : 0;
+            if (take) n_rows[i] = nr;
+        }
+        if (mask == 0) continue;
+        const uint64_t slots = std::min<uint64_t>(kWave, n - first) * keep;
+        for (uint64_t s = lane; s < slots; s += kWave) {
+            if (!((mask >> (s / keep)) & 1ull)) continue;
+            const uint64_t at = first * keep + s;
+            rows[at] = rev_rows[at];
+            if (counts) counts[at] = rev_counts[at];
+        }
+    }
+}
+
+// what the workspace of a `both` placement holds ahead of the reversed bytes: the reverse strand's rows
+struct WorkspaceLayout {
+    uint64_t rows = 0, n_rows = 0, counts = 0, seqs = 0;  // byte offsets
+    uint64_t per_read_bytes = 0;                          // = seqs
+};
+WorkspaceLayout layout_of(uint64_t n, uint32_t keep, uint32_t mode)
+{
+    WorkspaceLayout l;
+    if (mode == EPIK_AMD_STRAND_BOTH) {
+        l.rows = 0;
+        l.n_rows = align_up(n * keep * sizeof(epik_amd_placement));
+        l.counts = l.n_rows + align_up(n * sizeof(uint32_t));
+        l.seqs = l.counts + align_up(n * keep * sizeof(uint32_t));
+    }
+    l.per_read_bytes = l.seqs;
+    return l;
+}
+
+int check_handle(const epik_amd_placer *p, uint32_t mode)
+{
+    if (!p) return fail_with(EPIK_AMD_ERR_INVALID, "null placer");
+    if (mode > EPIK_AMD_STRAND_BOTH) return fail_with(EPIK_AMD_ERR_INVALID, "strand mode must be FORWARD, REVERSE or BOTH");
+    if (p->params.alphabet_size != 4)
+        return fail_with(EPIK_AMD_ERR_UNSUPPORTED, "strand placement needs a nucleotide placer (alphabet_size 4)");
+    if (p->plan.shard_count > 1)
+        return fail_with(EPIK_AMD_ERR_UNSUPPORTED, "strand placement needs a whole database, not a k-mer-space shard");
+    return EPIK_AMD_OK;
+}
+
+// For every byte c, a byte whose class is bitrev4(char_class[c]) -- from the handle's own table
+int complement_map(const epik_amd_placer *p, ComplementMap &map)
+{
+    if (p->h_char_class.size() != 256) return fail_with(EPIK_AMD_ERR_INVALID, "placer has no character table");
+    int rep[16];
+    std::fill(rep, rep + 16, -1);
+    for (int c = 255; c >= 0; --c) {  // (the smallest byte of each class)
+        const uint32_t cls = p->h_char_class[c];
+        if (cls > 15) return fail_with(EPIK_AMD_ERR_UNSUPPORTED, "character class outside the four nucleotide states");
+        rep[cls] = c;
+    }
+    for (int c = 0; c < 256; ++c) {
+        const uint32_t comp = bitrev4(p->h_char_class[c]);
+        if (rep[comp] < 0)
+            return fail_with(EPIK_AMD_ERR_UNSUPPORTED, "the character table has no character of class " + std::to_string(comp) +
+                                                           ", the complement of byte " + std::to_string(c) + "'s");
+        map.byte[c] = (uint8_t)rep[comp];
+    }
+    return EPIK_AMD_OK;
+}
+
+uint32_t grid_for(uint64_t units)
+{
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((units + kBlockWaves - 1) / kBlockWaves, kMaxBlocks));
+}
+
+int place_strands_device_impl(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offsets, uint64_t n,
+                              uint32_t mode, void *d_workspace, uint64_t workspace_bytes, void *d_rows, void *d_n_rows,
+                              void *d_kmer_counts, void *d_strand, hipStream_t stream)
+{
+    if (const int rc = check_handle(p, mode); rc != EPIK_AMD_OK) return rc;
+    if (n == 0) return EPIK_AMD_OK;
+    if (!d_seqs || !d_seq_offsets || !d_rows || !d_n_rows) return fail_with(EPIK_AMD_ERR_INVALID, "null device buffer");
+    const uint32_t keep = p->params.keep_at_most;
+    const WorkspaceLayout l = layout_of(n, keep, mode);
+    if (mode != EPIK_AMD_STRAND_FORWARD && (!d_workspace || workspace_bytes <= l.per_read_bytes))
+        return fail_with(EPIK_AMD_ERR_INVALID, "workspace smaller than epik_amd_placer_strand_workspace_bytes");
+    ComplementMap map{};
+    if (mode != EPIK_AMD_STRAND_FORWARD)
+        if (const int rc = complement_map(p, map); rc != EPIK_AMD_OK) return rc;
+    STRAND_TRY(hipSetDevice(p->device));
+    const auto *offs = static_cast<const uint64_t *>(d_seq_offsets);
+    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
+    uint8_t *strand = static_cast<uint8_t *>(d_strand);
+
+    if (mode != EPIK_AMD_STRAND_REVERSE) {  // forward: straight into the caller's buffers
+        if (const int rc = epik_amd_placer_place_device(p, d_seqs, d_seq_offsets, n, d_rows, d_n_rows, d_kmer_counts, stream);
+            rc != EPIK_AMD_OK)
+            return rc;
+        if (mode == EPIK_AMD_STRAND_FORWARD) {
+            if (strand) STRAND_TRY(hipMemsetAsync(strand, 0, n, stream));
+            return EPIK_AMD_OK;
+        }
+    }
+    uint8_t *rc_seqs = ws + l.seqs;
+    hipLaunchKernelGGL(revcomp_kernel, dim3(grid_for((n + kWave - 1) / kWave)), dim3(kBlock), 0, stream, static_cast<const uint8_t *>(d_seqs),
+                       offs, n, rc_seqs, workspace_bytes - l.seqs, map);
+    STRAND_TRY(hipGetLastError());
+    if (mode == EPIK_AMD_STRAND_REVERSE) {
+        if (const int rc = epik_amd_placer_place_device(p, rc_seqs, d_seq_offsets, n, d_rows, d_n_rows, d_kmer_counts, stream);
+            rc != EPIK_AMD_OK)
+            return rc;
+        if (strand) STRAND_TRY(hipMemsetAsync(strand, 1, n, stream));
+        return EPIK_AMD_OK;
+    }
+    auto *rev_rows = reinterpret_cast<epik_amd_placement *>(ws + l.rows);
+    auto *rev_n_rows = reinterpret_cast<uint32_t *>(ws + l.n_rows);
+    auto *rev_counts = d_kmer_counts ? reinterpret_cast<uint32_t *>(ws + l.counts) : nullptr;
+    if (const int rc = epik_amd_placer_place_device(p, rc_seqs, d_seq_offsets, n, rev_rows, rev_n_rows, rev_counts, stream);
+        rc != EPIK_AMD_OK)
+        return rc;
+    hipLaunchKernelGGL(strand_select_kernel, dim3(grid_for((n + kWave - 1) / kWave)), dim3(kBlock), 0, stream, n, keep,
+                       static_cast<epik_amd_placement *>(d_rows), static_cast<uint32_t *>(d_n_rows),
+                       static_cast<uint32_t *>(d_kmer_counts), rev_rows, rev_n_rows, rev_counts, strand);
+    STRAND_TRY(hipGetLastError());
+    return EPIK_AMD_OK;
+}
+
+// device memory of one host-entry call, freed however the call ends (after its stream has drained)
+struct ChunkBuffers {
+    void *base = nullptr;
+    hipStream_t stream = nullptr;
+    ~ChunkBuffers()
+    {
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (base) (void)hipFree(base);
+    }
+};
+
+int place_strands_impl(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n, uint32_t mode,
+                       epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts, uint8_t *strand)
+{
+    if (const int rc = check_handle(p, mode); rc != EPIK_AMD_OK) return rc;
+    if (n == 0) return EPIK_AMD_OK;
+    if (!seqs || !seq_offsets || !rows || !n_rows) return fail_with(EPIK_AMD_ERR_INVALID, "null host buffer");
+    if (seq_offsets[0] != 0) return fail_with(EPIK_AMD_ERR_INVALID, "seq_offsets[0] must be 0");
+    uint64_t longest = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (seq_offsets[i + 1] < seq_offsets[i] || seq_offsets[i + 1] - seq_offsets[i] > 0xffffffffull)
+            return fail_with(EPIK_AMD_ERR_INVALID, "seq_offsets not monotone, or a read of 2^32 characters or more");
+        longest = std::max<uint64_t>(longest, seq_offsets[i + 1] - seq_offsets[i]);
+    }
+    STRAND_TRY(hipSetDevice(p->device));
+    // The count width as epik_amd_placer_place chooses it from the batch's longest read, and the handle's count
+    // state as that call leaves it: restored on return.
+    struct restore_counts {
+        epik_amd_placer *p;
+        int counts;
+        uint64_t hint;
+        ~restore_counts() { p->counts = counts, p->longest_read_hint = hint; }
+    } restore{p, p->counts, p->longest_read_hint};
+    if (!p->counts_forced) {
+        if (const int rc = epik_amd_placer_choose_counts(p, longest); rc != EPIK_AMD_OK) return rc;
+    } else {
+        // (a forced width is kept unless it cannot hold the longest read's k-mers: no read comes back
+        // EPIK_AMD_ROWS_COUNTS_TOO_NARROW from a host entry point)
+        const uint64_t k = p->params.kmer_size, kmers = longest >= k ? longest - k + 1 : 0;
+        const uint64_t cap = p->counts == epik_amd::kCounts8 ? 255u : p->counts == epik_amd::kCounts16 ? 32767u : 0x7fffffffull;
+        if (kmers > cap) p->counts = kmers > 32767u ? epik_amd::kCounts32 : epik_amd::kCounts16;
+        p->longest_read_hint = longest;
+    }
+
+    // chunks of at most kChunkReads reads and kChunkBytes characters (a longer read: a chunk of its own)
+    uint64_t chunk_reads = kChunkReads;
+    if (const char *e = std::getenv("EPIK_AMD_STRAND_CHUNK_READS")) chunk_reads = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+    std::vector<uint64_t> starts{0};
+    uint64_t max_reads = 0, max_bytes = 0;
+    for (uint64_t r0 = 0; r0 < n;) {
+        uint64_t r1 = r0 + 1;
+        while (r1 < n && r1 - r0 < chunk_reads && seq_offsets[r1 + 1] - seq_offsets[r0] <= kChunkBytes) ++r1;
+        max_reads = std::max(max_reads, r1 - r0);
+        max_bytes = std::max(max_bytes, seq_offsets[r1] - seq_offsets[r0]);
+        starts.push_back(r0 = r1);
+    }
+    const uint64_t keep = p->params.keep_at_most;
+    const WorkspaceLayout wl = layout_of(max_reads, (uint32_t)keep, mode);
+    const uint64_t ws_bytes = mode == EPIK_AMD_STRAND_FORWARD ? 0 : wl.seqs + align_up(max_bytes + 1);
+    // one allocation: seqs | offsets | rows | n_rows | counts | strand | workspace
+    const uint64_t o_offs = align_up(max_bytes + 1), o_rows = o_offs + align_up((max_reads + 1) * sizeof(uint64_t));
+    const uint64_t o_nrows = o_rows + align_up(max_reads * keep * sizeof(epik_amd_placement));
+    const uint64_t o_counts = o_nrows + align_up(max_reads * sizeof(uint32_t));
+    const uint64_t o_strand = o_counts + align_up(max_reads * keep * sizeof(uint32_t));
+    const uint64_t o_ws = o_strand + align_up(max_reads);
+    ChunkBuffers buf;
+    STRAND_TRY(hipMalloc(&buf.base, o_ws + ws_bytes));
+    buf.stream = p->stream;
+    uint8_t *d = static_cast<uint8_t *>(buf.base);
+    auto *d_offs = reinterpret_cast<uint64_t *>(d + o_offs);
+    auto *d_rows = reinterpret_cast<epik_amd_placement *>(d + o_rows);
+    auto *d_nrows = reinterpret_cast<uint32_t *>(d + o_nrows);
+    auto *d_counts = reinterpret_cast<uint32_t *>(d + o_counts);
+    uint8_t *d_strand = d + o_strand, *d_ws = ws_bytes ? d + o_ws : nullptr;
+    std::vector<uint64_t> offs(max_reads + 1);
+    for (size_t c = 0; c + 1 < starts.size(); ++c) {
+        const uint64_t r0 = starts[c], cnt = starts[c + 1] - r0, b0 = seq_offsets[r0], bytes = seq_offsets[r0 + cnt] - b0;
+        for (uint64_t i = 0; i <= cnt; ++i) offs[i] = seq_offsets[r0 + i] - b0;
+        if (bytes) STRAND_TRY(hipMemcpyAsync(d, seqs + b0, bytes, hipMemcpyHostToDevice, p->stream));
+        STRAND_TRY(hipMemcpyAsync(d_offs, offs.data(), (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+        // rows beyond n_rows[i] are never written by the kernels: zero, as epik_amd_placer_place leaves them
+        STRAND_TRY(hipMemsetAsync(d_rows, 0, cnt * keep * sizeof(epik_amd_placement), p->stream));
+        STRAND_TRY(hipMemsetAsync(d_counts, 0, cnt * keep * sizeof(uint32_t), p->stream));
+        if (mode == EPIK_AMD_STRAND_BOTH) STRAND_TRY(hipMemsetAsync(d_ws, 0, layout_of(cnt, (uint32_t)keep, mode).per_read_bytes, p->stream));
+        const uint64_t chunk_ws = mode == EPIK_AMD_STRAND_FORWARD ? 0 : layout_of(cnt, (uint32_t)keep, mode).seqs + align_up(bytes + 1);
+        if (const int rc = place_strands_device_impl(p, d, d_offs, cnt, mode, d_ws, chunk_ws, d_rows, d_nrows, d_counts,
+                                                     d_strand, p->stream);
+            rc != EPIK_AMD_OK)
+            return rc;
+        STRAND_TRY(hipMemcpyAsync(rows + r0 * keep, d_rows, cnt * keep * sizeof(epik_amd_placement), hipMemcpyDeviceToHost, p->stream));
+        STRAND_TRY(hipMemcpyAsync(n_rows + r0, d_nrows, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+        if (kmer_counts)
+            STRAND_TRY(hipMemcpyAsync(kmer_counts + r0 * keep, d_counts, cnt * keep * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+        if (strand) STRAND_TRY(hipMemcpyAsync(strand + r0, d_strand, cnt, hipMemcpyDeviceToHost, p->stream));
+        STRAND_TRY(hipStreamSynchronize(p->stream));
+    }
+    return EPIK_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int epik_amd_placer_strand_workspace_bytes(const epik_amd_placer *p, uint64_t n, uint64_t seq_bytes, uint32_t mode,
+                                           uint64_t *bytes)
+{
+    if (!bytes) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    *bytes = 0;
+    if (const int rc = check_handle(p, mode); rc != EPIK_AMD_OK) return rc;
+    if (mode == EPIK_AMD_STRAND_FORWARD || n == 0) return EPIK_AMD_OK;
+    // (+1: a batch of empty reads still has a workspace of more than its per-read part)
+    *bytes = layout_of(n, p->params.keep_at_most, mode).seqs + align_up(seq_bytes + 1);
+    return EPIK_AMD_OK;
+}
+
+int epik_amd_placer_place_strands_device(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offsets, uint64_t n,
+                                         uint32_t mode, void *d_workspace, uint64_t workspace_bytes, void *d_rows,
+                                         void *d_n_rows, void *d_kmer_counts, void *d_strand, void *stream)
+{
+    return place_strands_device_impl(p, d_seqs, d_seq_offsets, n, mode, d_workspace, workspace_bytes, d_rows, d_n_rows,
+                                     d_kmer_counts, d_strand, static_cast<hipStream_t>(stream));
+}
+
+int epik_amd_placer_place_strands(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                                  uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                                  uint8_t *strand)
+{
+    try {  // std::vector: nothing may leave through the C ABI
+        return place_strands_impl(p, seqs, seq_offsets, n, mode, rows, n_rows, kmer_counts, strand);
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("place_strands: ") + e.what());
+    }
+}
+
+}  // extern "C"

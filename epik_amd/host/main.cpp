@@ -17,6 +17,7 @@
 #include <condition_variable>
 #include <deque>
 #include <exception>
+#include <fstream>
 #include <mutex>
 #include <thread>
 #include <cstdlib>
@@ -132,6 +133,16 @@ std::string make_output_filename(const std::string& input_file, const std::strin
     return dir + "placements_" + base + ".jplace";
 }
 
+/// --strand reverse|both: <output_dir>/strands_<basename(query)>.tsv beside the jplace
+std::string make_strands_filename(const std::string& input_file, const std::string& output_dir)
+{
+    const auto slash = input_file.find_last_of('/');
+    const std::string base = slash == std::string::npos ? input_file : input_file.substr(slash + 1);
+    std::string dir = output_dir;
+    if (!dir.empty() && dir.back() != '/') dir.push_back('/');
+    return dir + "strands_" + base + ".tsv";
+}
+
 }  // namespace
 #endif  // EPIK_AMD_NO_MAIN
 
@@ -157,6 +168,7 @@ const char* kHelp =
     "      --devices arg       Comma-separated HIP device ordinals (overrides --gpus)\n"
     "      --db-shard arg      Cut the database in so many shards by k-mer code, one per device\n"
     "                          (a database larger than one device; default: 1 = replicate it)\n"
+    "      --strand arg        forward | reverse (reverse complement) | both (the better per read) (default: forward)\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -224,6 +236,22 @@ int main(int argc, char** argv)
         if (parsed.has("help")) {
             std::cout << kHelp << std::endl;
             return 0;
+        }
+        // --strand: checked before anything is opened or any device touched
+        const auto strand_name = parsed.get("strand", "forward");
+        epik_amd::strand_mode strand = epik_amd::strand_mode::forward;
+        if (strand_name == "reverse")
+            strand = epik_amd::strand_mode::reverse;
+        else if (strand_name == "both")
+            strand = epik_amd::strand_mode::both;
+        else if (strand_name != "forward")
+            throw std::runtime_error("--strand must be forward, reverse or both, not '" + strand_name + "'");
+        if (strand != epik_amd::strand_mode::forward) {
+#ifdef EPIK_AMD_AA
+            throw std::runtime_error("--strand " + strand_name + " places nucleotide reads only (epik-dna)");
+#endif
+            if (std::stoul(parsed.get("db-shard", "1")) > 1)
+                throw std::runtime_error("--strand " + strand_name + " does not work with --db-shard > 1");
         }
         const auto db_file = parsed.require("database");
         const auto query_file = parsed.require("query");
@@ -295,6 +323,7 @@ int main(int argc, char** argv)
             return part;
         };
         epik_amd::placer placer(db, tree, keep_at_most, keep_factor, num_threads, devices, db_shards, load_shard);
+        placer.set_strand(strand);
         db.drop_lists();  // the lists are on the devices now; tree, k and omega stay for the output
         const auto tree_as_newick = epik_amd::io::to_newick(tree, true);
         const auto jplace_filename = make_output_filename(query_file, output_dir);
@@ -303,6 +332,12 @@ int main(int argc, char** argv)
         epik_amd::io::jplace_writer jplace(jplace_filename, invocation, tree_as_newick);
         jplace.set_branch_lengths(placer.distal_lengths(), placer.pendant_lengths());
         jplace.start();
+        // --strand reverse|both: one "name<TAB>+|-" line per input record, input order
+        std::ofstream strands_out;
+        if (strand != epik_amd::strand_mode::forward) {
+            strands_out.open(make_strands_filename(query_file, output_dir));
+            if (!strands_out) throw std::runtime_error("Could not open " + make_strands_filename(query_file, output_dir));
+        }
 
         std::cout << "Instruction set: gfx950 (" << placer.handle_count()
                   << (db_shards > 1 ? " shard(s) of the database, one handle each)" : " device(s))") << std::endl;
@@ -366,6 +401,13 @@ int main(int argc, char** argv)
                     if (group.empty()) continue;
                     write_clock.start();
                     jplace.write(group, num_threads);
+                    if (strands_out.is_open()) {
+                        for (const auto& item : ready)
+                            for (size_t i = 0; i < item.batch.size(); ++i)
+                                strands_out << item.batch[i].header() << '\t'
+                                            << (item.placed.strands[item.placed.unique_of[i]] ? '-' : '+') << '\n';
+                        if (!strands_out) throw std::runtime_error("Could not write the strands file");
+                    }
                     write_clock.stop();
                 }
             } catch (...) {
@@ -431,6 +473,11 @@ int main(int argc, char** argv)
                   << "Placed " << num_seq_placed << " sequences.\nAverage speed: " << epik_amd::human_count(average_speed, false)
                   << " seq/s.\n";
         std::cout << "Output: " << jplace_filename << std::endl;
+        if (strands_out.is_open()) {
+            strands_out.close();
+            if (!strands_out) throw std::runtime_error("Could not write " + make_strands_filename(query_file, output_dir));
+            std::cout << "Strands: " << make_strands_filename(query_file, output_dir) << std::endl;
+        }
         const auto placement_end = std::chrono::steady_clock::now();
         const auto placement_time = (size_t)std::chrono::duration_cast<std::chrono::milliseconds>(placement_end - begin).count();
         if (std::getenv("EPIK_AMD_STAGE_TIMES"))  // (the reference's line below is in whole milliseconds)

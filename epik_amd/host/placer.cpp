@@ -8,6 +8,10 @@
 
 #include "parallel.hpp"
 
+// The driver is also linked against the test-only stub of the C ABI (Makefile: sanitize, stub), which places one
+// strand only: its strand entry is a weak reference here, and a library without it is an error when asked for.
+#pragma weak epik_amd_placer_place_strands
+
 namespace epik_amd {
 
 using impl::placed_collection;
@@ -105,6 +109,18 @@ std::vector<double> placer::distal_lengths() const
     return out;
 }
 
+void placer::set_strand(strand_mode mode)
+{
+    if (mode != strand_mode::forward) {
+        if (_sharded) throw std::runtime_error("GPU placer: --strand reverse|both does not work with --db-shard > 1");
+        if (alphabet_size(_db.sequence_type()) != 4)
+            throw std::runtime_error("GPU placer: --strand reverse|both needs a nucleotide database");
+        if (!&epik_amd_placer_place_strands)
+            throw std::runtime_error("GPU placer: this libepik_amd has no strand placement");
+    }
+    _strand = mode;
+}
+
 placer::~placer() noexcept
 {
     for (auto* h : _handles) epik_amd_placer_destroy(h);
@@ -188,6 +204,7 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         pb.names.resize(batch.size());
         std::vector<uint32_t> at(pb.name_begin.begin(), pb.name_begin.end() - 1);
         for (size_t i = 0; i < batch.size(); ++i) pb.names[at[unique_of[i]]++] = batch[i].header();
+        if (_strand != strand_mode::forward) pb.unique_of = std::move(unique_of);  // (the strand of each record)
         first_unique[b + 1] = n_unique;
         first_byte[b + 1] = bytes;
         out[b] = std::move(pb);
@@ -214,10 +231,18 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
     });
     std::unique_ptr<epik_amd_placement[]> rows(new epik_amd_placement[n * _keep_at_most]);
     std::unique_ptr<uint32_t[]> n_rows(new uint32_t[n]), counts(new uint32_t[n * _keep_at_most]);
-    const int rc = _sharded ? epik_amd_placer_place_sharded(_handles.data(), (uint32_t)_handles.size(), bytes.get(),
-                                                            offsets.get(), n, rows.get(), n_rows.get(), counts.get())
-                            : epik_amd_placer_place(_handles[device_index], bytes.get(), offsets.get(), n, rows.get(),
-                                                    n_rows.get(), counts.get());
+    std::unique_ptr<uint8_t[]> strands;  // (reverse / both only: forward goes through epik_amd_placer_place as ever)
+    int rc;
+    if (_strand != strand_mode::forward) {
+        strands.reset(new uint8_t[n]);
+        rc = epik_amd_placer_place_strands(_handles[device_index], bytes.get(), offsets.get(), n, (uint32_t)_strand,
+                                           rows.get(), n_rows.get(), counts.get(), strands.get());
+    } else {
+        rc = _sharded ? epik_amd_placer_place_sharded(_handles.data(), (uint32_t)_handles.size(), bytes.get(),
+                                                      offsets.get(), n, rows.get(), n_rows.get(), counts.get())
+                      : epik_amd_placer_place(_handles[device_index], bytes.get(), offsets.get(), n, rows.get(),
+                                              n_rows.get(), counts.get());
+    }
     if (rc != EPIK_AMD_OK) throw std::runtime_error(std::string("GPU placer: ") + epik_amd_last_error());
     parallel_for(batches.size(), num_threads, [&](size_t b) {
         auto& pb = out[b];
@@ -234,6 +259,9 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
             pb.row_begin[u + 1] = pb.row_begin[u] + n_rows[i];
         }
         pb.rows.resize(pb.row_begin[n_unique]);
+        if (strands) {
+            pb.strands.assign(strands.get() + first_unique[b], strands.get() + first_unique[b] + n_unique);
+        }
         for (size_t u = 0; u < n_unique; ++u) {
             const size_t i = first_unique[b] + u;
             for (uint32_t r = 0; r < n_rows[i]; ++r) {

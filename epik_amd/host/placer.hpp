@@ -59,12 +59,19 @@ struct placed_batch {
     std::vector<placement> rows;
     std::vector<uint32_t> name_begin;         // [n_unique + 1]: ... its headers names[name_begin[u] .. name_begin[u + 1]), input order
     std::vector<std::string_view> names;
+    // strand modes other than forward (placer::set_strand) only, else empty:
+    std::vector<uint8_t> strands;             // [n_unique]: 0 = the sequence was placed as given (+), 1 = its reverse complement (-)
+    std::vector<uint32_t> unique_of;          // [batch size]: the unique sequence of each record, input order
     size_t size() const noexcept { return sequences.size(); }
 };
 
 }  // namespace epik_amd::impl
 
 namespace epik_amd {
+
+/// Which strand of a nucleotide read is placed (epik_amd_placer_place_strands): the read as given (the reference's
+/// contract, place.cpp:294), its reverse complement, or per read the better of the two.
+enum class strand_mode : uint32_t { forward = EPIK_AMD_STRAND_FORWARD, reverse = EPIK_AMD_STRAND_REVERSE, both = EPIK_AMD_STRAND_BOTH };
 
 class placer {
 public:
@@ -105,6 +112,11 @@ public:
     /// database, ONE for a sharded one (all its handles work on every batch).
     size_t device_count() const noexcept { return _sharded ? 1 : _handles.size(); }
     size_t handle_count() const noexcept { return _handles.size(); }
+    /// forward (the default) places through epik_amd_placer_place as ever; reverse / both through
+    /// epik_amd_placer_place_strands, and the placed batches say per sequence which strand won.  Nucleotide
+    /// databases, replicated (not --db-shard) only.
+    void set_strand(strand_mode mode);
+    strand_mode strand() const noexcept { return _strand; }
     /// distal_length / pendant_length of a placement on branch b (place.cpp:110-123, 435-437)
     std::vector<double> distal_lengths() const;
     const std::vector<double>& pendant_lengths() const noexcept { return _pendant_lengths; }
@@ -119,6 +131,7 @@ private:
     std::vector<double> _pendant_lengths;
     std::vector<epik_amd_placer*> _handles;  // one per device (replicated) or per shard (sharded)
     bool _sharded = false;
+    strand_mode _strand = strand_mode::forward;
 };
 
 }  // namespace epik_amd

@@ -44,6 +44,7 @@ class PlacedSequence:
 
     sequence: str
     placements: List[Placement]
+    strand: str = "+"     # the strand placed: "-" when the reverse complement won (Placer.place(strand=...))
 
 
 @dataclass
@@ -274,6 +275,46 @@ class Placer:
             self._handle, d_seqs, d_seq_offsets, int(n), d_rows, d_n_rows, d_kmer_counts or None,
             stream or None))
 
+    @staticmethod
+    def _strand_mode(mode) -> int:
+        if isinstance(mode, str):
+            if mode not in capi.STRANDS:
+                raise ValueError(f"unknown strand {mode!r}: expected one of {sorted(capi.STRANDS)}")
+            return capi.STRANDS[mode]
+        return int(mode)
+
+    def strand_workspace_bytes(self, n: int, seq_bytes: int, mode="both") -> int:
+        """Device workspace `place_strands_device` needs for n reads of seq_bytes characters
+        (`epik_amd_placer_strand_workspace_bytes`)."""
+        out = ctypes.c_uint64(0)
+        capi.check(self._lib.epik_amd_placer_strand_workspace_bytes(self._handle, int(n), int(seq_bytes),
+                                                                    self._strand_mode(mode), ctypes.byref(out)))
+        return int(out.value)
+
+    def place_strands(self, seqs: np.ndarray, seq_offsets: np.ndarray, mode="both"):
+        """`place_packed` on the strand(s) `mode` ("forward" / "reverse" / "both", or capi.STRAND_*) asks for
+        (`epik_amd_placer_place_strands`).  Returns (rows, n_rows, kmer_counts, strand[n] uint8: 0 = +, 1 = -)."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+        n = int(seq_offsets.shape[0] - 1)
+        rows = np.zeros((n, self.keep_at_most), dtype=capi.PLACEMENT)
+        n_rows = np.zeros(n, dtype=np.uint32)
+        counts = np.zeros((n, self.keep_at_most), dtype=np.uint32)
+        strand = np.zeros(n, dtype=np.uint8)
+        capi.check(self._lib.epik_amd_placer_place_strands(
+            self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n, self._strand_mode(mode), rows.ctypes.data,
+            n_rows.ctypes.data, counts.ctypes.data, strand.ctypes.data))
+        return rows, n_rows, counts, strand
+
+    def place_strands_device(self, d_seqs: int, d_seq_offsets: int, n: int, mode, d_workspace: int, workspace_bytes: int,
+                             d_rows: int, d_n_rows: int, d_kmer_counts: int = 0, d_strand: int = 0,
+                             stream: int = 0) -> None:
+        """`place_device` on the strand(s) `mode` asks for, asynchronous on `stream`; the caller's workspace of
+        `strand_workspace_bytes(n, seq_bytes, mode)` (`epik_amd_placer_place_strands_device`)."""
+        capi.check(self._lib.epik_amd_placer_place_strands_device(
+            self._handle, d_seqs, d_seq_offsets, int(n), self._strand_mode(mode), d_workspace or None,
+            int(workspace_bytes), d_rows, d_n_rows, d_kmer_counts or None, d_strand or None, stream or None))
+
     def accumulate_device(self, d_seqs: int, d_seq_offsets: int, n: int, d_scores: int, d_counts: int,
                           stream: int = 0, d_amb_slot: int = 0, d_amb_order: int = 0, d_amb_avg: int = 0) -> None:
         """First half of a k-mer-space-sharded placement: raw float32 score sums and uint16 k-mer counts
@@ -384,10 +425,14 @@ class Placer:
         return float(ms.value)
 
     # -- epik::placer::place ---------------------------------------------------------
-    def place(self, seq_records: Iterable[Tuple[str, str]], num_threads: int = 1) -> PlacedCollection:
+    def place(self, seq_records: Iterable[Tuple[str, str]], num_threads: int = 1,
+              strand: str = "forward") -> PlacedCollection:
         """`seq_records` = (header, sequence) pairs (i2l::seq_record).  `num_threads`
-        is accepted for signature parity and ignored, as the parallelism is the GPU's."""
+        is accepted for signature parity and ignored, as the parallelism is the GPU's.
+        `strand`: "forward" (the reference's contract: each read as given), "reverse" (its reverse
+        complement) or "both" (per read the better of the two; PlacedSequence.strand says which)."""
         del num_threads
+        mode = self._strand_mode(strand)
         sequence_map: dict = {}
         for header, sequence in seq_records:          # place.cpp:73-81
             sequence_map.setdefault(sequence, []).append(header)
@@ -397,7 +442,11 @@ class Placer:
         if bufs:
             offsets[1:] = np.cumsum([len(b) for b in bufs], dtype=np.uint64)
         data = np.frombuffer(b"".join(bufs), dtype=np.uint8) if bufs else np.zeros(0, np.uint8)
-        rows, n_rows, counts = self.place_packed(data, offsets)
+        if mode == capi.STRAND_FORWARD:
+            rows, n_rows, counts = self.place_packed(data, offsets)
+            strands = None
+        else:
+            rows, n_rows, counts, strands = self.place_strands(data, offsets, mode)
         if len(n_rows) and int(n_rows.max()) > self.keep_at_most:
             # (never from place_packed, which widens the counts by itself: a row count, not the
             # EPIK_AMD_ROWS_COUNTS_TOO_NARROW mark of the device entry points)
@@ -414,5 +463,6 @@ class Placer:
                     # rows fabricated for a read without hits carry 0.0 lengths (place.cpp:150)
                     distal_length=float(self.distal[b]) if in_tree and counts[i, r] else 0.0,
                     pendant_length=float(self.pendant[b]) if in_tree and counts[i, r] else 0.0))
-            placed.append(PlacedSequence(sequence=seq, placements=pl))
+            placed.append(PlacedSequence(sequence=seq, placements=pl,
+                                         strand="-" if strands is not None and strands[i] else "+"))
         return PlacedCollection(sequence_map=sequence_map, placed_seqs=placed)

@@ -322,6 +322,44 @@ int epik_amd_placer_place_sharded(epik_amd_placer *const *shards, uint32_t n_sha
                                   const uint64_t *seq_offsets, uint64_t n, epik_amd_placement *rows,
                                   uint32_t *n_rows, uint32_t *kmer_counts);
 
+/*
+ * Nucleotide reads placed on either strand.  No reference counterpart: the reference places a read in the
+ * orientation it arrives in (place.cpp:294, to_kmers over the read as given).
+ *   FORWARD  the read as given: the rows of place / place_device, strand 0 everywhere;
+ *   REVERSE  its reverse complement, strand 1 everywhere;
+ *   BOTH     both orientations, per read the better one: reverse when it has rows and either forward has none or
+ *            its first score is strictly greater (float32) than forward's; else forward (a tie goes to forward).
+ *            Rows, n_rows and k-mer counts are those of the chosen strand, LWRs not renormalised across strands.
+ * The complement is taken on character classes: state s <-> 3 - s in the order A C G T, a 4-bit reversal of the
+ * class bitmask (R <-> Y, K <-> M, B <-> V, D <-> H; S, W, N themselves; U -> A; invalid stays invalid).  The
+ * reverse strand of read r has at position j the class bitrev4(char_class[r[len-1-j]]): its rows are those
+ * place() gives for the host-side reverse complement of r.  strand[i]: 0 forward (+), 1 reverse (-).
+ * Nucleotide handles of a whole database only: EPIK_AMD_ERR_UNSUPPORTED for alphabet_size != 4 or a k-mer-space
+ * shard.  Deduplication stays the caller's, by exact string (place.cpp:73-81).
+ *
+ * place_strands_device: asynchronous on `stream`, count width as the caller chose it (as place_device); keeps no
+ *   state of its own and never allocates: the caller provides d_workspace of at least the bytes
+ *   strand_workspace_bytes gives for n reads and seq_bytes = d_seq_offsets[n] (the characters of the batch when
+ *   its offsets start at 0): the reversed reads are written there at the caller's offsets.  FORWARD needs none.
+ *   d_kmer_counts and d_strand (uint8 [n]) may be NULL.
+ * place_strands: synchronous, host buffers; count width chosen from the batch's longest read as place() does,
+ *   the handle's count state left as place() leaves it; the batch goes through the device in chunks of bounded
+ *   size, allocated and freed inside the call.  kmer_counts and strand may be NULL.
+ */
+#define EPIK_AMD_STRAND_FORWARD 0u
+#define EPIK_AMD_STRAND_REVERSE 1u
+#define EPIK_AMD_STRAND_BOTH    2u
+/* bytes of device workspace place_strands_device needs for n reads of seq_bytes characters in total */
+int epik_amd_placer_strand_workspace_bytes(const epik_amd_placer *p, uint64_t n, uint64_t seq_bytes,
+                                           uint32_t mode, uint64_t *bytes);
+int epik_amd_placer_place_strands_device(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offsets,
+                                         uint64_t n, uint32_t mode, void *d_workspace, uint64_t workspace_bytes,
+                                         void *d_rows, void *d_n_rows, void *d_kmer_counts, void *d_strand,
+                                         void *stream);
+int epik_amd_placer_place_strands(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                                  uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows,
+                                  uint32_t *kmer_counts, uint8_t *strand);
+
 /* Which kernels the last launch of this handle ran (reports; a large-tree handle falls back from the three-kernel
  * placement to the one-kernel one when the device has no room for the scratch of a launch). */
 #define EPIK_AMD_PATH_WAVE 0u            /* place_reads_kernel: one wavefront per read */
