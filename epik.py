@@ -7,8 +7,9 @@ command taking -i/--database, -s/--states {nucl,amino}, --omega (1.5), --mu (1.0
 (epik.py:73-98) it only selects the native driver -- `epik-dna` for nucl, `epik-aa` for
 amino -- translates the options into that driver's flags (-d -q -j --omega --mu -o
 [--max-ram]) and runs it.  New options: --gpus, the number of MI355X devices the reads are
-sharded across; --db-shard; and --strand, which strand of each nucleotide read is placed
-(forward as given, its reverse complement, or both and the better one per read).
+sharded across; --db-shard; --strand, which strand of each nucleotide read is placed
+(forward as given, its reverse complement, or both and the better one per read); and --translate, with
+-s amino: nucleotide reads translated into their frames, per read the best frame.
 """
 from __future__ import annotations
 
@@ -45,6 +46,10 @@ PLACE_OPTIONS = [
     (("--strand",), dict(type=click.Choice(["forward", "reverse", "both"]), default="forward", show_default=True,
                          help="Strand of each nucleotide read to place: as given, its reverse complement, or both and "
                               "the better one per read (then also strands_<input>.tsv, one name<TAB>+|- per read).")),
+    (("--translate",), dict(type=click.Choice(["forward", "reverse", "both"]), default=None,
+                            help="With -s amino: the reads are nucleotide reads; place their frames +1 +2 +3 (forward), "
+                                 "-1 -2 -3 (reverse) or all six (both), the best frame per read (then also "
+                                 "frames_<input>.tsv, one name<TAB>+1..-3 per read).")),
 ]
 
 
@@ -59,7 +64,7 @@ def driver_path(states: str) -> str:
 
 
 def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpus, input_file, db_shard=1,
-                   strand="forward"):
+                   strand="forward", translate=None):
     argv = [driver_path(states), "-d", str(database), "-q", str(input_file), "-j", str(threads),
             "--omega", str(omega), "--mu", str(mu), "-o", str(outputdir)]
     if max_ram:
@@ -70,6 +75,8 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--db-shard", str(db_shard)]
     if strand != "forward":
         argv += ["--strand", str(strand)]
+    if translate is not None:
+        argv += ["--translate", str(translate)]
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 

@@ -54,6 +54,10 @@ EXPORTS = (
     "epik_amd_placer_strand_workspace_bytes",
     "epik_amd_placer_place_strands_device",
     "epik_amd_placer_place_strands",
+    "epik_amd_codon_table",
+    "epik_amd_placer_frame_workspace_bytes",
+    "epik_amd_placer_place_frames_device",
+    "epik_amd_placer_place_frames",
 )
 
 
@@ -129,6 +133,12 @@ PATH_WAVE, PATH_TEAM_ONE_KERNEL, PATH_TEAM_STREAMED = 0, 1, 2
 #: strand modes of epik_amd_placer_place_strands[_device], and their names in Placer / epik.py / epik-dna --strand
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
 STRANDS = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
+
+#: frame modes of epik_amd_placer_place_frames[_device] (+1 +2 +3 / -1 -2 -3 / all six), their names in Placer /
+#: epik.py / epik-aa --translate, and the names of the frame bytes 0..5
+FRAMES_FORWARD, FRAMES_REVERSE, FRAMES_BOTH = 0, 1, 2
+FRAME_MODES = {"forward": FRAMES_FORWARD, "reverse": FRAMES_REVERSE, "both": FRAMES_BOTH}
+FRAME_NAMES = ("+1", "+2", "+3", "-1", "-2", "-3")
 
 #: n_rows of a read with more k-mers than the counts of a device-pointer launch hold
 ROWS_COUNTS_TOO_NARROW = 0xFFFFFFFF
@@ -247,6 +257,14 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_placer_place_strands_device.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, u64, vp, vp, vp, vp, vp]
     lib.epik_amd_placer_place_strands.restype = i32
     lib.epik_amd_placer_place_strands.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, vp, vp, vp]
+    lib.epik_amd_codon_table.restype = i32
+    lib.epik_amd_codon_table.argtypes = [vp]
+    lib.epik_amd_placer_frame_workspace_bytes.restype = i32
+    lib.epik_amd_placer_frame_workspace_bytes.argtypes = [vp, u64, u64, ctypes.c_uint32, ctypes.POINTER(u64)]
+    lib.epik_amd_placer_place_frames_device.restype = i32
+    lib.epik_amd_placer_place_frames_device.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, u64, vp, vp, vp, vp, vp]
+    lib.epik_amd_placer_place_frames.restype = i32
+    lib.epik_amd_placer_place_frames.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, vp, vp, vp]
     _lib = lib
     return lib
 

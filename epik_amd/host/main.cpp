@@ -143,6 +143,16 @@ std::string make_strands_filename(const std::string& input_file, const std::stri
     return dir + "strands_" + base + ".tsv";
 }
 
+/// --translate: <output_dir>/frames_<basename(query)>.tsv beside the jplace
+std::string make_frames_filename(const std::string& input_file, const std::string& output_dir)
+{
+    const auto slash = input_file.find_last_of('/');
+    const std::string base = slash == std::string::npos ? input_file : input_file.substr(slash + 1);
+    std::string dir = output_dir;
+    if (!dir.empty() && dir.back() != '/') dir.push_back('/');
+    return dir + "frames_" + base + ".tsv";
+}
+
 }  // namespace
 #endif  // EPIK_AMD_NO_MAIN
 
@@ -169,6 +179,8 @@ const char* kHelp =
     "      --db-shard arg      Cut the database in so many shards by k-mer code, one per device\n"
     "                          (a database larger than one device; default: 1 = replicate it)\n"
     "      --strand arg        forward | reverse (reverse complement) | both (the better per read) (default: forward)\n"
+    "      --translate arg     Nucleotide reads on this amino-acid database: forward (frames +1 +2 +3) | reverse\n"
+    "                          (-1 -2 -3) | both (all six); the best frame per read (epik-aa; default: off)\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -253,6 +265,23 @@ int main(int argc, char** argv)
             if (std::stoul(parsed.get("db-shard", "1")) > 1)
                 throw std::runtime_error("--strand " + strand_name + " does not work with --db-shard > 1");
         }
+        // --translate: checked before anything is opened or any device touched
+        const bool translate = parsed.has("translate");
+        epik_amd::translate_mode frames = epik_amd::translate_mode::both;
+        if (translate) {
+            const auto name = parsed.get("translate", "");
+            if (name == "forward")
+                frames = epik_amd::translate_mode::forward;
+            else if (name == "reverse")
+                frames = epik_amd::translate_mode::reverse;
+            else if (name != "both")
+                throw std::runtime_error("--translate must be forward, reverse or both, not '" + name + "'");
+#ifndef EPIK_AMD_AA
+            throw std::runtime_error("--translate " + name + " places nucleotide reads on amino-acid databases only (epik-aa)");
+#endif
+            if (std::stoul(parsed.get("db-shard", "1")) > 1)
+                throw std::runtime_error("--translate " + name + " does not work with --db-shard > 1");
+        }
         const auto db_file = parsed.require("database");
         const auto query_file = parsed.require("query");
         const auto num_threads = (size_t)std::stoul(parsed.get("jobs", "1"));
@@ -324,6 +353,7 @@ int main(int argc, char** argv)
         };
         epik_amd::placer placer(db, tree, keep_at_most, keep_factor, num_threads, devices, db_shards, load_shard);
         placer.set_strand(strand);
+        if (translate) placer.set_translate(frames);
         db.drop_lists();  // the lists are on the devices now; tree, k and omega stay for the output
         const auto tree_as_newick = epik_amd::io::to_newick(tree, true);
         const auto jplace_filename = make_output_filename(query_file, output_dir);
@@ -337,6 +367,12 @@ int main(int argc, char** argv)
         if (strand != epik_amd::strand_mode::forward) {
             strands_out.open(make_strands_filename(query_file, output_dir));
             if (!strands_out) throw std::runtime_error("Could not open " + make_strands_filename(query_file, output_dir));
+        }
+        // --translate: one "name<TAB>+1..-3" line per input record, input order
+        std::ofstream frames_out;
+        if (translate) {
+            frames_out.open(make_frames_filename(query_file, output_dir));
+            if (!frames_out) throw std::runtime_error("Could not open " + make_frames_filename(query_file, output_dir));
         }
 
         std::cout << "Instruction set: gfx950 (" << placer.handle_count()
@@ -408,6 +444,14 @@ int main(int argc, char** argv)
                                             << (item.placed.strands[item.placed.unique_of[i]] ? '-' : '+') << '\n';
                         if (!strands_out) throw std::runtime_error("Could not write the strands file");
                     }
+                    if (frames_out.is_open()) {
+                        static const char* const names[6] = {"+1", "+2", "+3", "-1", "-2", "-3"};
+                        for (const auto& item : ready)
+                            for (size_t i = 0; i < item.batch.size(); ++i)
+                                frames_out << item.batch[i].header() << '\t'
+                                           << names[item.placed.frames[item.placed.unique_of[i]] % 6] << '\n';
+                        if (!frames_out) throw std::runtime_error("Could not write the frames file");
+                    }
                     write_clock.stop();
                 }
             } catch (...) {
@@ -477,6 +521,11 @@ int main(int argc, char** argv)
             strands_out.close();
             if (!strands_out) throw std::runtime_error("Could not write " + make_strands_filename(query_file, output_dir));
             std::cout << "Strands: " << make_strands_filename(query_file, output_dir) << std::endl;
+        }
+        if (frames_out.is_open()) {
+            frames_out.close();
+            if (!frames_out) throw std::runtime_error("Could not write " + make_frames_filename(query_file, output_dir));
+            std::cout << "Frames: " << make_frames_filename(query_file, output_dir) << std::endl;
         }
         const auto placement_end = std::chrono::steady_clock::now();
         const auto placement_time = (size_t)std::chrono::duration_cast<std::chrono::milliseconds>(placement_end - begin).count();

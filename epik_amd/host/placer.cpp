@@ -9,8 +9,9 @@
 #include "parallel.hpp"
 
 // The driver is also linked against the test-only stub of the C ABI (Makefile: sanitize, stub), which places one
-// strand only: its strand entry is a weak reference here, and a library without it is an error when asked for.
+// strand only: its strand and frame entries are weak references here, and a library without it is an error when asked for.
 #pragma weak epik_amd_placer_place_strands
+#pragma weak epik_amd_placer_place_frames
 
 namespace epik_amd {
 
@@ -121,6 +122,16 @@ void placer::set_strand(strand_mode mode)
     _strand = mode;
 }
 
+void placer::set_translate(translate_mode mode)
+{
+    if (_sharded) throw std::runtime_error("GPU placer: --translate does not work with --db-shard > 1");
+    if (alphabet_size(_db.sequence_type()) != 20)
+        throw std::runtime_error("GPU placer: --translate needs an amino-acid database");
+    if (!&epik_amd_placer_place_frames) throw std::runtime_error("GPU placer: this libepik_amd has no translated placement");
+    _translate = true;
+    _frames = mode;
+}
+
 placer::~placer() noexcept
 {
     for (auto* h : _handles) epik_amd_placer_destroy(h);
@@ -204,7 +215,7 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         pb.names.resize(batch.size());
         std::vector<uint32_t> at(pb.name_begin.begin(), pb.name_begin.end() - 1);
         for (size_t i = 0; i < batch.size(); ++i) pb.names[at[unique_of[i]]++] = batch[i].header();
-        if (_strand != strand_mode::forward) pb.unique_of = std::move(unique_of);  // (the strand of each record)
+        if (_strand != strand_mode::forward || _translate) pb.unique_of = std::move(unique_of);  // (the strand / frame of each record)
         first_unique[b + 1] = n_unique;
         first_byte[b + 1] = bytes;
         out[b] = std::move(pb);
@@ -232,8 +243,13 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
     std::unique_ptr<epik_amd_placement[]> rows(new epik_amd_placement[n * _keep_at_most]);
     std::unique_ptr<uint32_t[]> n_rows(new uint32_t[n]), counts(new uint32_t[n * _keep_at_most]);
     std::unique_ptr<uint8_t[]> strands;  // (reverse / both only: forward goes through epik_amd_placer_place as ever)
+    std::unique_ptr<uint8_t[]> frames;   // (translated placement only)
     int rc;
-    if (_strand != strand_mode::forward) {
+    if (_translate) {
+        frames.reset(new uint8_t[n]);
+        rc = epik_amd_placer_place_frames(_handles[device_index], bytes.get(), offsets.get(), n, (uint32_t)_frames,
+                                          rows.get(), n_rows.get(), counts.get(), frames.get());
+    } else if (_strand != strand_mode::forward) {
         strands.reset(new uint8_t[n]);
         rc = epik_amd_placer_place_strands(_handles[device_index], bytes.get(), offsets.get(), n, (uint32_t)_strand,
                                            rows.get(), n_rows.get(), counts.get(), strands.get());
@@ -262,6 +278,7 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         if (strands) {
             pb.strands.assign(strands.get() + first_unique[b], strands.get() + first_unique[b] + n_unique);
         }
+        if (frames) pb.frames.assign(frames.get() + first_unique[b], frames.get() + first_unique[b] + n_unique);
         for (size_t u = 0; u < n_unique; ++u) {
             const size_t i = first_unique[b] + u;
             for (uint32_t r = 0; r < n_rows[i]; ++r) {

@@ -62,6 +62,8 @@ struct placed_batch {
     // strand modes other than forward (placer::set_strand) only, else empty:
     std::vector<uint8_t> strands;             // [n_unique]: 0 = the sequence was placed as given (+), 1 = its reverse complement (-)
     std::vector<uint32_t> unique_of;          // [batch size]: the unique sequence of each record, input order
+    // translated placement (placer::set_translate) only, else empty:
+    std::vector<uint8_t> frames;              // [n_unique]: the frame placed, 0..5 = +1 +2 +3 -1 -2 -3
     size_t size() const noexcept { return sequences.size(); }
 };
 
@@ -72,6 +74,10 @@ namespace epik_amd {
 /// Which strand of a nucleotide read is placed (epik_amd_placer_place_strands): the read as given (the reference's
 /// contract, place.cpp:294), its reverse complement, or per read the better of the two.
 enum class strand_mode : uint32_t { forward = EPIK_AMD_STRAND_FORWARD, reverse = EPIK_AMD_STRAND_REVERSE, both = EPIK_AMD_STRAND_BOTH };
+
+/// Which frames of a nucleotide read are placed on an amino-acid database (epik_amd_placer_place_frames): +1 +2 +3,
+/// -1 -2 -3, or all six; per read the best one.
+enum class translate_mode : uint32_t { forward = EPIK_AMD_FRAMES_FORWARD, reverse = EPIK_AMD_FRAMES_REVERSE, both = EPIK_AMD_FRAMES_BOTH };
 
 class placer {
 public:
@@ -117,6 +123,10 @@ public:
     /// databases, replicated (not --db-shard) only.
     void set_strand(strand_mode mode);
     strand_mode strand() const noexcept { return _strand; }
+    /// The reads are nucleotide reads, translated on the device and placed through epik_amd_placer_place_frames;
+    /// the placed batches say per sequence which frame won.  Amino-acid databases, replicated (not --db-shard) only.
+    void set_translate(translate_mode mode);
+    bool translating() const noexcept { return _translate; }
     /// distal_length / pendant_length of a placement on branch b (place.cpp:110-123, 435-437)
     std::vector<double> distal_lengths() const;
     const std::vector<double>& pendant_lengths() const noexcept { return _pendant_lengths; }
@@ -132,6 +142,8 @@ private:
     std::vector<epik_amd_placer*> _handles;  // one per device (replicated) or per shard (sharded)
     bool _sharded = false;
     strand_mode _strand = strand_mode::forward;
+    bool _translate = false;
+    translate_mode _frames = translate_mode::both;
 };
 
 }  // namespace epik_amd

@@ -45,6 +45,7 @@ class PlacedSequence:
     sequence: str
     placements: List[Placement]
     strand: str = "+"     # the strand placed: "-" when the reverse complement won (Placer.place(strand=...))
+    frame: str = ""       # the frame placed, "+1" ... "-3" (Placer.place(translate=...)); "" when not translated
 
 
 @dataclass
@@ -315,6 +316,56 @@ class Placer:
             self._handle, d_seqs, d_seq_offsets, int(n), self._strand_mode(mode), d_workspace or None,
             int(workspace_bytes), d_rows, d_n_rows, d_kmer_counts or None, d_strand or None, stream or None))
 
+    @staticmethod
+    def _frame_mode(mode) -> int:
+        if isinstance(mode, str):
+            if mode not in capi.FRAME_MODES:
+                raise ValueError(f"unknown translation {mode!r}: expected one of {sorted(capi.FRAME_MODES)}")
+            return capi.FRAME_MODES[mode]
+        return int(mode)
+
+    @staticmethod
+    def codon_table() -> np.ndarray:
+        """The library's codon -> residue table: uint8[4096] indexed by the three nucleotide class masks, 4 bits each,
+        first nucleotide most significant (`epik_amd_codon_table`; needs no device)."""
+        out = np.zeros(4096, dtype=np.uint8)
+        capi.check(capi.load().epik_amd_codon_table(out.ctypes.data))
+        return out
+
+    def frame_workspace_bytes(self, n: int, seq_bytes: int, mode="both") -> int:
+        """Device workspace `place_frames_device` needs for n nucleotide reads of seq_bytes characters
+        (`epik_amd_placer_frame_workspace_bytes`)."""
+        out = ctypes.c_uint64(0)
+        capi.check(self._lib.epik_amd_placer_frame_workspace_bytes(self._handle, int(n), int(seq_bytes),
+                                                                   self._frame_mode(mode), ctypes.byref(out)))
+        return int(out.value)
+
+    def place_frames(self, seqs: np.ndarray, seq_offsets: np.ndarray, mode="both"):
+        """`place_packed` for nucleotide reads on this amino-acid database, through the frames `mode` ("forward" /
+        "reverse" / "both", or capi.FRAMES_*) asks for; per read the best frame (`epik_amd_placer_place_frames`).
+        Returns (rows, n_rows, kmer_counts, frame[n] uint8: 0..5 = +1 +2 +3 -1 -2 -3)."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+        n = int(seq_offsets.shape[0] - 1)
+        rows = np.zeros((n, self.keep_at_most), dtype=capi.PLACEMENT)
+        n_rows = np.zeros(n, dtype=np.uint32)
+        counts = np.zeros((n, self.keep_at_most), dtype=np.uint32)
+        frame = np.zeros(n, dtype=np.uint8)
+        capi.check(self._lib.epik_amd_placer_place_frames(
+            self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n, self._frame_mode(mode), rows.ctypes.data,
+            n_rows.ctypes.data, counts.ctypes.data, frame.ctypes.data))
+        return rows, n_rows, counts, frame
+
+    def place_frames_device(self, d_seqs: int, d_seq_offsets: int, n: int, mode, d_workspace: int,
+                            workspace_bytes: int, d_rows: int, d_n_rows: int, d_kmer_counts: int = 0,
+                            d_frame: int = 0, stream: int = 0) -> None:
+        """`place_frames` on device buffers, asynchronous on `stream`; the caller's workspace of
+        `frame_workspace_bytes(n, seq_bytes, mode)` and count width (`choose_counts` with the longest frame,
+        L // 3) (`epik_amd_placer_place_frames_device`)."""
+        capi.check(self._lib.epik_amd_placer_place_frames_device(
+            self._handle, d_seqs, d_seq_offsets, int(n), self._frame_mode(mode), d_workspace or None,
+            int(workspace_bytes), d_rows, d_n_rows, d_kmer_counts or None, d_frame or None, stream or None))
+
     def accumulate_device(self, d_seqs: int, d_seq_offsets: int, n: int, d_scores: int, d_counts: int,
                           stream: int = 0, d_amb_slot: int = 0, d_amb_order: int = 0, d_amb_avg: int = 0) -> None:
         """First half of a k-mer-space-sharded placement: raw float32 score sums and uint16 k-mer counts
@@ -426,13 +477,19 @@ class Placer:
 
     # -- epik::placer::place ---------------------------------------------------------
     def place(self, seq_records: Iterable[Tuple[str, str]], num_threads: int = 1,
-              strand: str = "forward") -> PlacedCollection:
+              strand: str = "forward", translate=None) -> PlacedCollection:
         """`seq_records` = (header, sequence) pairs (i2l::seq_record).  `num_threads`
         is accepted for signature parity and ignored, as the parallelism is the GPU's.
         `strand`: "forward" (the reference's contract: each read as given), "reverse" (its reverse
-        complement) or "both" (per read the better of the two; PlacedSequence.strand says which)."""
+        complement) or "both" (per read the better of the two; PlacedSequence.strand says which).
+        `translate` (amino-acid databases): None places the reads as given; "forward" / "reverse" / "both" takes
+        them as nucleotide reads and places their frames +1 +2 +3 / -1 -2 -3 / all six, per read the best one
+        (PlacedSequence.frame says which).  Duplicates are merged on the nucleotide string."""
         del num_threads
         mode = self._strand_mode(strand)
+        frame_mode = None if translate is None else self._frame_mode(translate)
+        if frame_mode is not None and mode != capi.STRAND_FORWARD:
+            raise ValueError("strand and translate do not combine: translate=both already covers both strands")
         sequence_map: dict = {}
         for header, sequence in seq_records:          # place.cpp:73-81
             sequence_map.setdefault(sequence, []).append(header)
@@ -442,9 +499,11 @@ class Placer:
         if bufs:
             offsets[1:] = np.cumsum([len(b) for b in bufs], dtype=np.uint64)
         data = np.frombuffer(b"".join(bufs), dtype=np.uint8) if bufs else np.zeros(0, np.uint8)
-        if mode == capi.STRAND_FORWARD:
+        strands = frames = None
+        if frame_mode is not None:
+            rows, n_rows, counts, frames = self.place_frames(data, offsets, frame_mode)
+        elif mode == capi.STRAND_FORWARD:
             rows, n_rows, counts = self.place_packed(data, offsets)
-            strands = None
         else:
             rows, n_rows, counts, strands = self.place_strands(data, offsets, mode)
         if len(n_rows) and int(n_rows.max()) > self.keep_at_most:
@@ -464,5 +523,6 @@ class Placer:
                     distal_length=float(self.distal[b]) if in_tree and counts[i, r] else 0.0,
                     pendant_length=float(self.pendant[b]) if in_tree and counts[i, r] else 0.0))
             placed.append(PlacedSequence(sequence=seq, placements=pl,
-                                         strand="-" if strands is not None and strands[i] else "+"))
+                                         strand="-" if strands is not None and strands[i] else "+",
+                                         frame=capi.FRAME_NAMES[int(frames[i])] if frames is not None else ""))
         return PlacedCollection(sequence_map=sequence_map, placed_seqs=placed)

@@ -360,6 +360,57 @@ int epik_amd_placer_place_strands(epik_amd_placer *p, const char *seqs, const ui
                                   uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows,
                                   uint32_t *kmer_counts, uint8_t *strand);
 
+/*
+ * Nucleotide reads placed on an amino-acid database through their translated frames.  No reference counterpart: the
+ * reference places a read in the alphabet of its database (place.cpp:294).
+ *   FORWARD  frames +1 +2 +3;  REVERSE  frames -1 -2 -3;  BOTH  all six.
+ * Frames.  Frame +f (f = 1, 2, 3) translates the codons that start at offset f-1 of the read; frame -f does the same
+ *   on the reverse complement.  An incomplete trailing codon is dropped: a read of length L gives frames of
+ *   floor((L - f + 1) / 3) residues (none when that is negative).  The reverse complement is the strand placement's:
+ *   the class bitmask reversed, in A C G T order.
+ * Codon -> residue: one 4096-entry byte table indexed by the three nucleotide class masks (4 bits each, the first
+ *   nucleotide most significant), built in the library from the standard genetic code (NCBI table 1, which also
+ *   serves table 11).  A codon with any class-0 (invalid) character becomes '*'.  Otherwise every combination of the
+ *   codon's ambiguous characters (at most 64) is expanded: one amino acid -> that letter; only stops -> '*'; the
+ *   amino-acid sets {D,N}, {E,Q} and {I,L} -> B, Z and J; any other set, a mix of stops and amino acids included,
+ *   -> X.  U is T, and lower case is upper case.  '*' must be class 0 in the handle's class table (as in
+ *   alphabet.py), so k-mers across a stop or a gap are skipped exactly as for invalid characters:
+ *   EPIK_AMD_ERR_UNSUPPORTED otherwise.
+ * Choosing a frame.  A frame has rows when its n_rows is neither 0 nor EPIK_AMD_ROWS_COUNTS_TOO_NARROW.  Its key is
+ *   score[0] / (float)(len_f - k + 1), a float32 division rounded to nearest: the per-k-mer score (the raw score is
+ *   not used: frames of one read differ by one residue, and the correction adds one log_threshold term per k-mer).
+ *   The frame with rows and the strictly greatest key wins; ties go to the earlier frame in the order +1 +2 +3 -1 -2
+ *   -3.  If no frame has rows, the read reports the first frame of the mode with that frame's n_rows (0).  If any
+ *   frame of a read is TOO_NARROW, the read is TOO_NARROW.  Rows, counts and LWRs are the winning frame's and are not
+ *   renormalised.  frame[i]: 0..5 for +1 +2 +3 -1 -2 -3.
+ * Amino-acid handles of a whole database only: EPIK_AMD_ERR_UNSUPPORTED for alphabet_size != 20 or a k-mer-space
+ * shard.  Deduplication stays the caller's, on the nucleotide string.
+ *
+ * place_frames_device: asynchronous on `stream`; never allocates: the caller provides d_workspace of at least the
+ *   bytes frame_workspace_bytes gives for n reads and seq_bytes = d_seq_offsets[n] (the characters of the batch when
+ *   its offsets start at 0).  All frames of the batch are placed in ONE call of epik_amd_placer_place_device, with
+ *   the count width the caller chose (epik_amd_placer_choose_counts with the longest FRAME, floor(L / 3)).
+ *   d_kmer_counts and d_frame (uint8 [n]) may be NULL.
+ * place_frames: synchronous, host buffers; count width chosen from the batch's longest frame, the handle's count
+ *   state left as place() leaves it; the batch goes through the device in chunks of bounded size, allocated and
+ *   freed inside the call.  kmer_counts and frame may be NULL.
+ * codon_table: the 4096-entry table above (needs no device).
+ */
+#define EPIK_AMD_FRAMES_FORWARD 0u
+#define EPIK_AMD_FRAMES_REVERSE 1u
+#define EPIK_AMD_FRAMES_BOTH    2u
+int epik_amd_codon_table(uint8_t *out);  /* out: 4096 bytes */
+/* bytes of device workspace place_frames_device needs for n reads of seq_bytes characters in total */
+int epik_amd_placer_frame_workspace_bytes(const epik_amd_placer *p, uint64_t n, uint64_t seq_bytes,
+                                          uint32_t mode, uint64_t *bytes);
+int epik_amd_placer_place_frames_device(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offsets,
+                                        uint64_t n, uint32_t mode, void *d_workspace, uint64_t workspace_bytes,
+                                        void *d_rows, void *d_n_rows, void *d_kmer_counts, void *d_frame,
+                                        void *stream);
+int epik_amd_placer_place_frames(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                                 uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows,
+                                 uint32_t *kmer_counts, uint8_t *frame);
+
 /* Which kernels the last launch of this handle ran (reports; a large-tree handle falls back from the three-kernel
  * placement to the one-kernel one when the device has no room for the scratch of a launch). */
 #define EPIK_AMD_PATH_WAVE 0u            /* place_reads_kernel: one wavefront per read */
