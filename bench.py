@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- reads placed / second on the BASELINE.json workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the hot path (`epik::placer::place`'s per-read loop,
 reference place.cpp:201-440) over one batch of synthetic reads that is already
@@ -18,7 +18,8 @@ torch.distributed is used for the barriers and the max-over-ranks time only.
 (dump_outputs).  The workload is seeded: the same arguments give the same inputs on every run, so that two builds
 can be compared output for output.
 
-Rank 0 prints ONE JSON line.  Extra objects (rank 0, N=1 where they cost time):
+Rank 0 prints ONE JSON line.  A plain run does only what that line needs: it sets up, warms up, times the K steps,
+writes --dump-outputs and prints the line, whose objects beside the headline are
   roofline              -- achieved algorithmic GB/s of the placement kernel (HIP events on the
                            launch stream, inside the timed region) against the HBM peak; `bound`
                            is "hbm+mall" when the device image of the database (`working_set_bytes`)
@@ -26,6 +27,8 @@ Rank 0 prints ONE JSON line.  Extra objects (rank 0, N=1 where they cost time):
                            mostly served from it), "hbm" otherwise;
                            `traffic` = HBM bytes of the committed PMC pass, null unless that pass
                            was taken on exactly these kernel sources (profiles/traffic.json);
+  build                 -- compiler, kernel-source hash and ISA-lint record of the library (epik_amd/provenance.py).
+--full adds, after the timed steps, what takes runs of its own (rank 0, N=1; without it `cpu_baseline` is null):
   roofline_hbm_resident -- the same kernel, reads and tree on a database that does NOT fit the
                            Infinity Cache (k = 11: 148 M postings, 1.2 GB), a short second pass;
   cpu_baseline          -- the CPU oracle (a restatement of the reference loop; the reference itself
@@ -48,8 +51,7 @@ Rank 0 prints ONE JSON line.  Extra objects (rank 0, N=1 where they cost time):
                         -- the two halves of the k-mer-space-sharded placement of that tree on this one GPU
                            (65 536 reads per step, a process of its own): the whole database as one shard;
                            shard 0 of 8 alone with ALL reads finished from that one source; and the same shard as one
-                           rank of eight works -- all reads accumulated, an eighth finished from eight sources;
-  build                 -- compiler, kernel-source hash and ISA-lint record of the library (epik_amd/provenance.py).
+                           rank of eight works -- all reads accumulated, an eighth finished from eight sources.
 config.world_size is what the process group reports; config.ranks lists every rank's device ordinal, PCI bus id,
 host and own ms_per_step (the k-mer-space shard: the bytes it sent per step) -- a SCALE record says by itself
 whether N ranks on N devices took part.
@@ -89,10 +91,13 @@ def parse_args():
     ap.add_argument("--read-length", type=int, default=150)
     ap.add_argument("--leaves", type=int, default=500, help="tree leaves; N = 2*leaves - 1")
     ap.add_argument("--kmer-size", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the measurements that take runs of their own (rank 0, one GPU, reads "
+                         "mode): host entry point, second passes, k-mer-shard lines, CPU baseline, end-to-end driver run")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=20.0,
-                    help="target CPU time of the bounded cpu_baseline sample (0 = skip the CPU legs)")
+                    help="with --full: target CPU time of the bounded cpu_baseline sample (0 = skip the CPU legs)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the HBM-resident second pass and the end-to-end driver run")
+                    help="with --full: skip all but the CPU baseline")
     ap.add_argument("--scattered", action="store_true",
                     help="non-contiguous branch sets in the synthetic posting lists")
     ap.add_argument("--clades", action="store_true",
@@ -820,7 +825,7 @@ def main():
             # lint of the streaming loop passed on both (epik_amd/provenance.py)
             "build": provenance.summary(),
         }
-    extras = rank == 0 and world == 1 and not kmer_shard
+    extras = args.full and rank == 0 and world == 1 and not kmer_shard
     if extras and not args.no_extras:
         # ---- the boundary's own rate (PCIe-inclusive), beside the device-resident `value` and the FASTA -> jplace `e2e`
         log("host entry point (epik_amd_placer_place) ...")

@@ -17,7 +17,7 @@ log() { echo "[profile_round] $*"; }
 PART=${PART:-1234}
 if [[ $PART == *1* ]]; then
 log "full default bench line"
-python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err || log "bench failed"
+python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || log "bench failed"
 
 trace() { # name args...
   local name=$1; shift
