@@ -32,6 +32,8 @@ EXPORTS = (
     "epik_amd_placer_plan",
     "epik_amd_placer_plan_sizes",
     "epik_amd_placer_build_image",
+    "epik_amd_placer_plan_run_counts",
+    "epik_amd_placer_run_counts",
     "epik_amd_placer_destroy",
     "epik_amd_placer_place",
     "epik_amd_placer_place_device",
@@ -231,6 +233,11 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_placer_build_image.restype = i32
     lib.epik_amd_placer_build_image.argtypes = [ctypes.POINTER(PlacerDesc), ctypes.c_uint32, ctypes.c_uint32, u64,
                                                 vp, vp, vp]
+    lib.epik_amd_placer_plan_run_counts.restype = i32
+    lib.epik_amd_placer_plan_run_counts.argtypes = [ctypes.POINTER(PlacerDesc), ctypes.c_uint32, ctypes.c_uint32, u64,
+                                                    ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+    lib.epik_amd_placer_run_counts.restype = i32
+    lib.epik_amd_placer_run_counts.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     lib.epik_amd_placer_destroy.restype = None
     lib.epik_amd_placer_destroy.argtypes = [vp]
     lib.epik_amd_placer_place.restype = i32

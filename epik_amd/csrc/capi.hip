@@ -322,6 +322,8 @@ int create_impl(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t sh
     }
     p->layout = plan.layout;
     p->team = plan.layout == epik_amd::DbLayout::kTeam;
+    const bool run_lists = image::run_counts_apply(plan, std::getenv("EPIK_AMD_RUN_COUNTS"));
+    p->runs = run_lists ? epik_amd::kRunLists : plan.runs ? epik_amd::kRunsMixed : 0;
     p->db_bytes = plan.posting_bytes;
     CREATE_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     CREATE_TRY(hipStreamCreateWithFlags(&p->stream_in, hipStreamNonBlocking));
@@ -490,9 +492,9 @@ int create_impl(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t sh
             for (uint32_t wpb = 4; wpb >= 1; wpb >>= 1) {
                 const uint32_t block_bytes = wpb * g.lds_wave_bytes;
                 if (block_bytes > kMaxLdsPerBlock) continue;
-                CREATE_TRY(epik_amd::set_place_reads_lds_limit(p->layout, p->plan.runs, counts, block_bytes));
+                CREATE_TRY(epik_amd::set_place_reads_lds_limit(p->layout, p->runs, counts, block_bytes));
                 int per_cu = 0;
-                CREATE_TRY(epik_amd::place_reads_occupancy(p->layout, p->plan.runs, counts, (int)(wpb * 64u), block_bytes, &per_cu));
+                CREATE_TRY(epik_amd::place_reads_occupancy(p->layout, p->runs, counts, (int)(wpb * 64u), block_bytes, &per_cu));
                 const uint32_t lds_units = (block_bytes + epik_amd::kLdsGranule - 1u) / epik_amd::kLdsGranule;
                 per_cu = std::min<int>(per_cu, (int)(128u / std::max(lds_units, 1u)));
                 if (per_cu < 1) per_cu = 1;
@@ -504,7 +506,7 @@ int create_impl(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t sh
                 }
             }
             g.resident_waves = best_waves;
-            CREATE_TRY(epik_amd::set_place_reads_lds_limit(p->layout, p->plan.runs, counts, g.lds_block_bytes));
+            CREATE_TRY(epik_amd::set_place_reads_lds_limit(p->layout, p->runs, counts, g.lds_block_bytes));
             CREATE_TRY(epik_amd::set_finish_reads_lds_limit(counts, g.lds_block_bytes));
         }
     }
@@ -624,6 +626,29 @@ int epik_amd_placer_plan(const epik_amd_placer_desc *d, uint32_t shard_index, ui
         return EPIK_AMD_OK;
     } catch (const std::exception &e) {
         return fail(EPIK_AMD_ERR_INVALID, std::string("plan: ") + e.what());
+    }
+}
+
+int epik_amd_placer_plan_run_counts(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t shard_count,
+                                    uint64_t free_bytes, uint32_t counts, uint32_t *lists)
+{
+    namespace image = epik_amd::image;
+    if (!lists) return fail(EPIK_AMD_ERR_INVALID, "null argument");
+    if (counts > (uint32_t)epik_amd::kCounts32) return fail(EPIK_AMD_ERR_INVALID, "counts must be 0, 1 or 2");
+    try {
+        std::string err;
+        if (const int rc = image::resolve_shard(d, shard_index, shard_count, err); rc != EPIK_AMD_OK) return fail(rc, err);
+        if (const int rc = image::validate(d, shard_index, shard_count, err); rc != EPIK_AMD_OK) return fail(rc, err);
+        image::Plan plan;
+        if (const int rc = image::make_plan(image::Source{d, shard_index, shard_count}, (size_t)free_bytes,
+                                            std::getenv("EPIK_AMD_LAYOUT"), std::getenv("EPIK_AMD_KERNEL"), plan, err);
+            rc != EPIK_AMD_OK)
+            return fail(rc, err);
+        *lists = counts != (uint32_t)epik_amd::kCounts8 &&
+                 image::run_counts_apply(plan, std::getenv("EPIK_AMD_RUN_COUNTS"));
+        return EPIK_AMD_OK;
+    } catch (const std::exception &e) {
+        return fail(EPIK_AMD_ERR_INVALID, std::string("plan_run_counts: ") + e.what());
     }
 }
 
@@ -945,7 +970,7 @@ static int launch(epik_amd_placer *p, launch_mode mode, const void *d_seqs, cons
         HIP_TRY(epik_amd::launch_finish_reads(pp, p->counts, dim3((unsigned)blocks), dim3(g.waves_per_block * 64u),
                                               g.lds_block_bytes, stream));
     } else {
-        HIP_TRY(epik_amd::launch_place_reads(pp, p->layout, p->plan.runs, p->counts, dim3((unsigned)blocks),
+        HIP_TRY(epik_amd::launch_place_reads(pp, p->layout, p->runs, p->counts, dim3((unsigned)blocks),
                                              dim3(g.waves_per_block * 64u), g.lds_block_bytes, stream));
     }
     if (timed) {
@@ -1081,6 +1106,14 @@ int epik_amd_placer_last_path(const epik_amd_placer *p, uint32_t *path)
 {
     if (!p || !path) return fail(EPIK_AMD_ERR_INVALID, "null argument");
     *path = !p->team ? EPIK_AMD_PATH_WAVE : p->last_streamed ? EPIK_AMD_PATH_TEAM_STREAMED : EPIK_AMD_PATH_TEAM_ONE_KERNEL;
+    return EPIK_AMD_OK;
+}
+
+int epik_amd_placer_run_counts(const epik_amd_placer *p, uint32_t counts, uint32_t *lists)
+{
+    if (!p || !lists) return fail(EPIK_AMD_ERR_INVALID, "null argument");
+    if (counts > (uint32_t)epik_amd::kCounts32) return fail(EPIK_AMD_ERR_INVALID, "counts must be 0, 1 or 2");
+    *lists = !p->team && p->runs == epik_amd::kRunLists && counts != (uint32_t)epik_amd::kCounts8;
     return EPIK_AMD_OK;
 }
 

@@ -449,7 +449,7 @@ int make_plan(const Source &src, size_t free_mem, const char *forced_layout, con
     if (plan.n_pad > 65536u) return fail(EPIK_AMD_ERR_UNSUPPORTED, "num_branches too large for the packed layouts");
     const uint64_t table_bytes = d->num_keys * (paired ? 16u : 8u) + 8u;
     {   // how large the image is with every list explicit, and run-coded, decides whether the lists are run-coded
-        uint64_t explicit_lines = 0, coded_lines = 0, in_runs = 0;
+        uint64_t explicit_lines = 0, coded_lines = 0, in_runs = 0, not_runs = 0;
         Cursor walk(src);
         for (uint64_t key = 0; key < d->num_keys; ++key) {
             uint64_t first = 0;
@@ -458,7 +458,9 @@ int make_plan(const Source &src, size_t free_mem, const char *forced_layout, con
             const bool run = is_run(d->values + first, len);
             coded_lines += ((run ? len * 4u : len * 6u) + 127u) / 128u;
             if (run) in_runs += len;
+            not_runs += len != 0 && !run;
         }
+        plan.run_lists = not_runs == 0;
         plan.runs = choose_runs(explicit_lines * 128u + table_bytes, coded_lines * 128u + table_bytes, plan.kept_entries, in_runs,
                                 plan.wave_resident[kCounts8] >= kWaveKernelWavesPerCu);
     }
@@ -546,11 +548,13 @@ int plan_sizes(const SizeDesc &z, size_t free_mem, const char *forced_layout, co
     plan.layout = w.paired ? DbLayout::kPaired : w.filtered ? DbLayout::kFiltered : DbLayout::kPacked;
     if (plan.n_pad > 65536u) return fail(EPIK_AMD_ERR_UNSUPPORTED, "num_branches too large for the packed layouts");
     uint64_t explicit_lines = 0, coded_lines = 0;
+    plan.run_lists = true;
     for (uint64_t i = 0; i < z.n_bins; ++i) {
         const epik_amd_list_bin &b = z.bins[i];
         if (b.length == 0 || b.lists == 0) continue;
         explicit_lines += b.lists * ((b.length * 6u + 127u) / 128u);
         const uint64_t as_runs = b.length < 65536u ? b.lists_in_runs : 0;
+        if (as_runs != b.lists) plan.run_lists = false;
         coded_lines += (b.lists - as_runs) * ((b.length * 6u + 127u) / 128u) + as_runs * ((b.length * 4u + 127u) / 128u);
     }
     const uint64_t packed_table = num_keys * (w.paired ? 16u : 8u) + 8u;

@@ -102,6 +102,7 @@ struct Plan {
     uint32_t filter_rec_bytes = 8;  // bytes of a presence record of the filtered layout: 8, or 5 (the 2 x 20 bits of a protein database, packed)
     uint64_t kept_entries = 0, present_codes = 0;
     bool runs = false;  // packed layouts: run-coded lists (place_device.hpp, kRuns)
+    bool run_lists = false;  // packed layouts: EVERY kept list is a run (of fewer than 65536 postings)
     uint64_t quarter_lines[4] = {0, 0, 0, 0};  // paired table: posting lines in front of each quarter of the key space
     uint32_t wave_resident[3] = {0, 0, 0};     // resident waves per CU by count width (what chose the kernel)
     // k-mer-space shard (include/epik_amd.h): the placer keeps the lists of the codes with code % shard_count ==
@@ -111,6 +112,20 @@ struct Plan {
     uint32_t shard_index = 0, shard_count = 1;
     uint64_t table_keys = 0;  // sliced layout: entries per pass
 };
+
+// The one-wavefront kernel with counts kept per list (place_device.hpp, RunListLayout) places a run-coded image whose
+// lists are all runs, with 16- or 32-bit counts (the 8-bit kernel keeps the run ring) -- in the packed and paired
+// layouts.  The filtered layout (sparse databases: a read finds a few lists) keeps the run ring: there the pass that
+// turns the differences into counts costs more than the count stages it removes (amino k = 7, N = 999: 3.18 ms with
+// the ring, 3.23-3.25 with list counts).  forced: EPIK_AMD_RUN_COUNTS, "ring" keeps the run ring
+// everywhere, "lists" takes list counts wherever the lists allow it (the filtered layout included).
+inline bool run_counts_apply(const Plan &plan, const char *forced)
+{
+    if (!plan.runs || !plan.run_lists || plan.layout == DbLayout::kTeam) return false;
+    if (forced && forced[0] == 'r') return false;
+    if (forced && forced[0] == 'l') return true;
+    return plan.layout != DbLayout::kFiltered;
+}
 
 // codes of [0, num_keys) with code % count == index
 inline uint64_t shard_keys(uint64_t num_keys, uint32_t index, uint32_t count)

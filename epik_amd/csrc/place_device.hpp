@@ -414,6 +414,58 @@ struct PackedLayout {
     }
 };
 
+// The run-coded packed layouts when EVERY list the placer keeps is a run (the image builder's plan says so,
+// db_image.cpp: Plan::run_lists) and the counts are 16 or 32 bits: the one-wavefront kernel with LIST counts.
+// A list adds 1 to the count of every row of its run [r0, r0 + len): the kernel records that once per list, as +1 at
+// r0 and -1 at r0 + len in a difference array that takes the count array's place (add_run_count), and turns it back
+// into counts when the read's exact k-mers are streamed (materialize_counts) -- integer adds commute, only the float32
+// score adds need the k-mer order.  The ring then carries scores only (stream_round_lists): no cells to fetch, no
+// explicit-cell arm, one load per chunk, and a stage is an LDS read, an add and an LDS write.
+// Descriptor: the chunk's 128-byte line relative to p.postings (the region has fewer than 2^32 lines,
+// db_image.cpp) | (postings in the chunk | its first row << 7) << 32.
+template <int kTable>
+struct RunListLayout : PackedLayout<kTable, true> {
+    static constexpr bool kListCounts = true;
+    static constexpr int kWaitLoads = 1;
+    static constexpr int kFields = 2;
+    __device__ static __forceinline__ uint64_t descriptor(const PlaceParams &p, uint64_t addr, uint32_t w, uint32_t c, uint64_t cnt)
+    {
+        // (a run's chunk c is 64 scores, two lines, from the list's first; its rows ascend from the list's first row)
+        const uint32_t line = (uint32_t)(addr >> 7) + 2u * c;
+        const uint32_t row = p.n_pad - 1u - (w >> 16) + (c << 6);
+        return (uint64_t)line | ((uint64_t)((uint32_t)cnt | (row << 7)) << 32);
+    }
+    // (no postings: every lane loads the +0.0 of an empty buffer, added to rows 0..63 or the dummy row)
+    __device__ static __forceinline__ uint64_t null_descriptor(const PlaceParams &) { return 0ull; }
+    __device__ static __forceinline__ void prepare(const PlaceParams &, uint64_t d, uint32_t (&f)[kFields])
+    {
+        f[0] = (uint32_t)d;
+        f[1] = (uint32_t)(d >> 32);
+    }
+    // The refill of a slot: the chunk's scores, and the LDS address of the lane's row, min(row0 + lane, dummy row).
+    // f[] sits in scalar registers (v_readlane): the buffer resource and the row's address are scalar instructions.
+    template <bool kSettled = false>
+    __device__ static __forceinline__ void issue(const PlaceParams &p, const uint32_t (&f)[kFields], uint32_t lane4,
+                                                 uint32_t score_row0, uint32_t score_top, uint32_t &addr, uint32_t &score)
+    {
+        const uint64_t a = (uint64_t)p.postings + ((uint64_t)f[0] << 7);
+        const uint32_t cnt = f[1] & 127u;
+        const uint32_t base = score_row0 + ((f[1] >> 7) << 2);
+        const v4i srd = {(int)(uint32_t)a, (int)((uint32_t)(a >> 32) & 0xffffu), (int)(cnt * 4u), kRawBufferFormat};
+        asm volatile(".if %6 == 0\n\ts_nop 4\n\t.endif\n\t"
+                     "buffer_load_dword %0, %2, %3, 0 offen\n\t"
+                     "v_add_u32 %1, %4, %2\n\t"
+                     "v_min_u32 %1, %5, %1"
+                     : "=&v"(score), "=&v"(addr)
+                     : "v"(lane4), "s"(srd), "s"(base), "s"(score_top), "n"(kSettled ? 1 : 0)
+                     : "memory");
+    }
+};
+template <typename Layout, typename = void>
+struct ListCounts : std::false_type {};
+template <typename Layout>
+struct ListCounts<Layout, std::void_t<decltype(Layout::kListCounts)>> : std::bool_constant<Layout::kListCounts> {};
+
 // absolute address of chunk c (64 postings each) of the list at byte offset `addr`
 template <typename Layout>
 __device__ __forceinline__ uint64_t chunk_address(const PlaceParams &p, uint64_t addr, uint32_t c)
@@ -758,6 +810,146 @@ __device__ __forceinline__ void stream_round(const PlaceParams &p, const typenam
         // that the copy stands HERE: a plain read of a slot register the compiler may place ahead of the drain)
 #pragma unroll
         for (int i = 0; i < kDepth; ++i) asm volatile("v_mov_b32 %0, %1" : "=v"(cells_out[i]) : "v"(ring_c[i]));
+    }
+}
+
+// The ring of RunListLayout (scores only; the counts are kept per list, add_run_count).  A slot is the chunk's
+// scores, in flight, and the LDS address of the lane's row, computed when the slot is refilled -- it needs no load.
+// A stage: LDS read of the row, the refill's descriptor words out of the lanes, the wait for the slot (the oldest
+// of the kDepth in flight), the add, the LDS write, the refill.
+// Lanes past the chunk's end load +0.0 (the buffer's range check) and add it to row row0 + lane, clamped to the dummy
+// row: a real row, another branch's, keeps its bits, because a row cleared to +0.0 never holds -0.0 under
+// round-to-nearest adds (x + y is -0.0 only if both are -0.0, or x + -x rounded downwards), and x + +0.0 == x for
+// every x that is not -0.0.  The rows of one instruction are distinct but for the dummy row, where every lane
+// writes the same +0.0 sum.
+template <typename Layout, int kDepth = kRing>
+__device__ __forceinline__ void stream_round_lists(const PlaceParams &p, const typename WaveLds<uint32_t>::u64_t *chunks,
+                                                   uint32_t n_padded, uint32_t score_top, uint32_t n_real)
+{
+    typedef __attribute__((address_space(3))) float lds_f32;
+    const int lane = lane_id();
+    const uint32_t lane4 = (uint32_t)lane * 4u;
+    const uint32_t score_row0 = __builtin_amdgcn_readfirstlane(score_top - (p.n_pad - 1u) * 4u);
+    uint32_t ring_a[kDepth], ring_s[kDepth];
+    auto stage = [&](int i, auto wait_count, auto &&meanwhile, auto &&refill) {
+        lds_f32 *cell = (lds_f32 *)(uintptr_t)ring_a[i];
+        const float old_score = *cell;
+        meanwhile();
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(wait_count)::value) : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        float new_score;
+        asm volatile("v_add_f32 %0, %1, %2" : "=v"(new_score) : "v"(old_score), "v"(ring_s[i]) : "memory");
+        *cell = new_score;
+        refill();
+    };
+    if (n_padded == 0) return;
+    uint64_t d_next = chunks[lane & (kDepth - 1)];  // descriptors of the first trip, lane i <-> stage i
+    {
+        // the ring is empty: the first trip only puts its chunks in flight
+        uint32_t field[Layout::kFields];
+        Layout::prepare(p, d_next, field);
+        d_next = chunks[kDepth + (lane & (kDepth - 1))];
+#pragma unroll
+        for (int i = 0; i < kDepth; ++i) {
+            uint32_t f[Layout::kFields];
+#pragma unroll
+            for (int q = 0; q < Layout::kFields; ++q) f[q] = __builtin_amdgcn_readlane(field[q], i);
+            Layout::issue(p, f, lane4, score_row0, score_top, ring_a[i], ring_s[i]);
+        }
+    }
+    for (uint32_t c0 = (uint32_t)kDepth; c0 < n_padded; c0 += kDepth) {
+        uint32_t field[Layout::kFields];
+        Layout::prepare(p, d_next, field);
+        d_next = chunks[c0 + kDepth + (lane & (kDepth - 1))];  // next trip (spare entries behind the end)
+#pragma unroll
+        for (int i = 0; i < kDepth; ++i) {
+            uint32_t f[Layout::kFields];
+            stage(
+                i, std::integral_constant<int, kDepth - 1>{},
+                [&]() {
+                    // (the words leave the lanes here: the wait, the add and the LDS write lie between them and the
+                    // refill's buffer load -- the five wait states a VALU-written SGPR needs, without an s_nop)
+#pragma unroll
+                    for (int q = 0; q < Layout::kFields; ++q)
+                        asm volatile("v_readlane_b32 %0, %1, %2" : "=s"(f[q]) : "v"(field[q]), "i"(i));
+                },
+                [&]() { Layout::template issue<true>(p, f, lane4, score_row0, score_top, ring_a[i], ring_s[i]); });
+        }
+    }
+    // tail: retire the real chunks of the last trip; the first stage drains the ring (padding slots included), so
+    // that nothing is in flight when the function returns
+    const uint32_t last_real = n_real ? n_real - (n_padded - (uint32_t)kDepth) : (uint32_t)kDepth;
+#pragma unroll
+    for (int i = 0; i < kDepth; ++i)
+        if (i == 0 || (uint32_t)i < last_real) stage(i, std::integral_constant<int, 0>{}, []() {}, []() {});
+}
+
+// RunListLayout: the read's list with table word w (a run, len | first cell << 16) adds 1 to the counts of its rows
+// [r0, r0 + len): +1 at r0 and -1 at r0 + len (<= num_branches <= n_pad - 1) in the difference array that lies in the
+// count array's place.  16-bit counts: two 16-bit differences per dword, changed by LDS atomic adds of +-1 or
+// +-1 << 16 -- a borrow out of the low half lands in the high one, and materialize_counts undoes it.
+template <typename CountT>
+__device__ __forceinline__ void add_run_count(WaveLds<CountT> lds, uint32_t n_pad, uint32_t w)
+{
+    static_assert(sizeof(CountT) != 1, "8-bit counts keep the per-chunk count ring");
+    typedef __attribute__((address_space(3))) uint32_t lds_u32;
+    const uint32_t r0 = n_pad - 1u - (w >> 16), r1 = r0 + (w & 0xffffu);
+    if constexpr (sizeof(CountT) == 2) {
+        lds_u32 *words = (lds_u32 *)lds.count;
+        __atomic_fetch_add(words + (r0 >> 1), 1u << ((r0 & 1u) << 4), __ATOMIC_RELAXED);
+        __atomic_fetch_sub(words + (r1 >> 1), 1u << ((r1 & 1u) << 4), __ATOMIC_RELAXED);
+    } else {
+        __atomic_fetch_add((lds_u32 *)lds.count + r0, 1u, __ATOMIC_RELAXED);
+        __atomic_fetch_sub((lds_u32 *)lds.count + r1, 1u, __ATOMIC_RELAXED);
+    }
+}
+// ... and the counts from the differences, in one sweep: each lane takes 16 consecutive rows (a block of 1 024 rows
+// per trip), sums them up in order, and one wave-wide scan of the lane totals gives each lane what the rows in front
+// of its own add up to.  16-bit: a dword V holding the differences d_lo, d_hi of two rows is d_lo + d_hi * 65536
+// modulo 2^32, and |d| <= the read's k-mers <= 32 767, so d_lo = sext16(V) and d_hi = (V - d_lo) >> 16 (arithmetic)
+// exactly.
+template <typename CountT>
+__device__ __forceinline__ void materialize_counts(WaveLds<CountT> lds, uint32_t n_pad)
+{
+    static_assert(sizeof(CountT) != 1, "8-bit counts keep the per-chunk count ring");
+    typedef __attribute__((address_space(3))) v4u lds_u32x4;
+    constexpr uint32_t kRows = 16, kWords = kRows * (uint32_t)sizeof(CountT) / 4u, kVecs = kWords / 4u;
+    const uint32_t lane = (uint32_t)lane_id();
+    uint32_t carry = 0;  // the counts' sum over the blocks in front (wave-uniform)
+    for (uint32_t b0 = 0; b0 < n_pad; b0 += kRows * (uint32_t)kWave) {
+        const uint32_t r0 = b0 + lane * kRows;
+        const bool mine = r0 < n_pad;  // (n_pad is a multiple of 64: a lane's rows are all there or none)
+        lds_u32x4 *at = (lds_u32x4 *)(lds.count + (mine ? r0 : 0u));
+        uint32_t v[kWords];
+#pragma unroll
+        for (uint32_t q = 0; q < kVecs; ++q) {
+            const v4u x = mine ? at[q] : v4u{0u, 0u, 0u, 0u};
+            v[4 * q] = x.x, v[4 * q + 1] = x.y, v[4 * q + 2] = x.z, v[4 * q + 3] = x.w;
+        }
+        int32_t s = 0;  // the lane's running sum, then the counts relative to what lies in front of the lane
+#pragma unroll
+        for (uint32_t q = 0; q < kWords; ++q) {
+            if constexpr (sizeof(CountT) == 2) {
+                const int32_t lo = (int32_t)(v[q] << 16) >> 16;
+                const int32_t hi = (int32_t)(v[q] - (uint32_t)lo) >> 16;
+                const int32_t c_lo = s + lo;
+                s = c_lo + hi;
+                v[q] = ((uint32_t)s << 16) + (uint32_t)c_lo;  // both halves relative, modulo 2^32
+            } else {
+                s += (int32_t)v[q];
+                v[q] = (uint32_t)s;
+            }
+        }
+        const uint32_t incl = wave_incl_scan_u32((uint32_t)s);
+        const uint32_t front = carry + incl - (uint32_t)s;
+        // (16-bit: + front in both halves; the halves end in [0, 32767], so no carry crosses them)
+        const uint32_t add = sizeof(CountT) == 2 ? front * 0x10001u : front;
+        if (mine) {
+#pragma unroll
+            for (uint32_t q = 0; q < kVecs; ++q)
+                at[q] = v4u{v[4 * q] + add, v[4 * q + 1] + add, v[4 * q + 2] + add, v[4 * q + 3] + add};
+        }
+        carry += __builtin_amdgcn_readlane(incl, 63);
     }
 }
 

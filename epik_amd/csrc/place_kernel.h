@@ -169,15 +169,18 @@ bool team_stream_is_wide(int waves, size_t lds_bytes, int bw);  // the build lau
 hipError_t team_stream_occupancy(int waves, int counts, int mode, int bw, size_t lds_bytes, int *blocks_per_cu);
 hipError_t launch_team_algorithmic_bytes(const TeamParams &tp, int waves, unsigned long long *d_total, hipStream_t stream);
 
-hipError_t launch_place_reads(const PlaceParams &p, DbLayout layout, bool runs, int counts, dim3 grid, dim3 block,
+// runs: 0 explicit cells, 1 (kRunsMixed) run-coded lists, kRunLists run-coded with every list a run and the counts
+// kept per list (16- and 32-bit counts; 8-bit counts take the run-coded kernel)
+enum : int { kRunsMixed = 1, kRunLists = 2 };
+hipError_t launch_place_reads(const PlaceParams &p, DbLayout layout, int runs, int counts, dim3 grid, dim3 block,
                               size_t lds_bytes, hipStream_t stream);
-hipError_t set_place_reads_lds_limit(DbLayout layout, bool runs, int counts, size_t lds_bytes);
-hipError_t place_reads_occupancy(DbLayout layout, bool runs, int counts, int block_threads, size_t lds_bytes,
+hipError_t set_place_reads_lds_limit(DbLayout layout, int runs, int counts, size_t lds_bytes);
+hipError_t place_reads_occupancy(DbLayout layout, int runs, int counts, int block_threads, size_t lds_bytes,
                                  int *blocks_per_cu);
 hipError_t launch_finish_reads(const PlaceParams &p, int counts, dim3 grid, dim3 block, size_t lds_bytes,
                                hipStream_t stream);
 hipError_t set_finish_reads_lds_limit(int counts, size_t lds_bytes);
-hipError_t launch_algorithmic_bytes(const PlaceParams &p, DbLayout layout, bool runs, unsigned long long *d_total,
+hipError_t launch_algorithmic_bytes(const PlaceParams &p, DbLayout layout, int runs, unsigned long long *d_total,
                                     hipStream_t stream);
 
 }  // namespace epik_amd

@@ -157,6 +157,12 @@ __global__ __launch_bounds__(256, 5) void place_reads_kernel(PlaceParams p)
                     total += __builtin_amdgcn_readlane(incl, 63);
                 }
             }
+            if constexpr (ListCounts<Layout>::value) {
+                // every list found is a run: its k-mer count goes in as an interval, once (add_run_count)
+#pragma unroll
+                for (int t = 0; t < kTilesPerPass; ++t)
+                    if (found_any[t] && llen[t] != 0u) add_run_count(lds, p.n_pad, llen[t]);
+            }
 #ifdef EPIK_AMD_ABLATION
             if (p.ablate & 8u) total = 0;   // lookups done, nothing streamed
 #endif
@@ -203,9 +209,15 @@ __global__ __launch_bounds__(256, 5) void place_reads_kernel(PlaceParams p)
                 if ((uint32_t)lane < n_padded - n_round) chunks[n_round + lane] = Layout::null_descriptor(p);
 
                 // (3) stream the chunks through the ring of kRing in-flight loads (place_device.hpp)
-                stream_round<Layout, CountT, kRing, false>(p, chunks, n_padded, score_top, count_top, nullptr, n_round);
+                if constexpr (ListCounts<Layout>::value)
+                    stream_round_lists<Layout, kRing>(p, chunks, n_padded, score_top, n_round);
+                else
+                    stream_round<Layout, CountT, kRing, false>(p, chunks, n_padded, score_top, count_top, nullptr, n_round);
             }
         }
+        // the counts out of their differences, before anything reads them (the ambiguous sweep, the partial vectors,
+        // the epilogue)
+        if constexpr (ListCounts<Layout>::value) materialize_counts(lds, p.n_pad);
 
         EPIK_STAMP(2)  // expansion + stream
         // ---- ambiguous k-mers (place.cpp:306-313, 373-415), after all exact ones ------
@@ -319,19 +331,24 @@ hipError_t dispatch_counts(int counts, F &&f)
     return hipErrorInvalidValue;
 }
 // runs: the packed lists in their run-coded form (place_device.hpp, kRuns; chosen by the image builder for
-// databases well beyond the Infinity Cache)
+// databases well beyond the Infinity Cache); kRunLists: every list a run, and 16- or 32-bit counts kept per list
+// (RunListLayout; the 8-bit kernel keeps the run ring)
+template <int kTable, typename F>
+hipError_t dispatch_runs(int runs, int counts, F &&f)
+{
+    if (runs == kRunLists && counts == kCounts16) return f.template operator()<RunListLayout<kTable>, uint16_t>();
+    if (runs == kRunLists && counts == kCounts32) return f.template operator()<RunListLayout<kTable>, uint32_t>();
+    return runs ? dispatch_counts<PackedLayout<kTable, true>>(counts, f) : dispatch_counts<PackedLayout<kTable>>(counts, f);
+}
 template <typename F>
-hipError_t dispatch(DbLayout layout, bool runs, int counts, F &&f)
+hipError_t dispatch(DbLayout layout, int runs, int counts, F &&f)
 {
     switch (layout) {
         case DbLayout::kCompact32: return dispatch_counts<CompactLayout<uint32_t>>(counts, f);
         case DbLayout::kCompact64: return dispatch_counts<CompactLayout<uint64_t>>(counts, f);
-        case DbLayout::kPacked:
-            return runs ? dispatch_counts<PackedLayout<kPlainTable, true>>(counts, f) : dispatch_counts<PackedLayout<kPlainTable>>(counts, f);
-        case DbLayout::kPaired:
-            return runs ? dispatch_counts<PackedLayout<kPairedTable, true>>(counts, f) : dispatch_counts<PackedLayout<kPairedTable>>(counts, f);
-        case DbLayout::kFiltered:
-            return runs ? dispatch_counts<PackedLayout<kFilteredTable, true>>(counts, f) : dispatch_counts<PackedLayout<kFilteredTable>>(counts, f);
+        case DbLayout::kPacked: return dispatch_runs<kPlainTable>(runs, counts, f);
+        case DbLayout::kPaired: return dispatch_runs<kPairedTable>(runs, counts, f);
+        case DbLayout::kFiltered: return dispatch_runs<kFilteredTable>(runs, counts, f);
         case DbLayout::kTeam: break;  // team_kernel.hip
     }
     return hipErrorInvalidValue;
@@ -339,7 +356,7 @@ hipError_t dispatch(DbLayout layout, bool runs, int counts, F &&f)
 
 }  // namespace
 
-hipError_t launch_place_reads(const PlaceParams &p, DbLayout layout, bool runs, int counts, dim3 grid, dim3 block,
+hipError_t launch_place_reads(const PlaceParams &p, DbLayout layout, int runs, int counts, dim3 grid, dim3 block,
                               size_t lds_bytes, hipStream_t stream)
 {
     return dispatch(layout, runs, counts, [&]<typename L, typename C>() {
@@ -351,7 +368,7 @@ hipError_t launch_place_reads(const PlaceParams &p, DbLayout layout, bool runs, 
 // The attribute is a cap per kernel and process, not a reservation (what a launch occupies is what it
 // asks for): it is always raised to the whole LDS of a CU, so that placers of different trees alive in
 // one process can never lower it under each other's launches.
-hipError_t set_place_reads_lds_limit(DbLayout layout, bool runs, int counts, size_t /*lds_bytes*/)
+hipError_t set_place_reads_lds_limit(DbLayout layout, int runs, int counts, size_t /*lds_bytes*/)
 {
     return dispatch(layout, runs, counts, [&]<typename L, typename C>() {
         return hipFuncSetAttribute(reinterpret_cast<const void *>(&place_reads_kernel<L, C>),
@@ -359,7 +376,7 @@ hipError_t set_place_reads_lds_limit(DbLayout layout, bool runs, int counts, siz
     });
 }
 
-hipError_t place_reads_occupancy(DbLayout layout, bool runs, int counts, int block_threads, size_t lds_bytes,
+hipError_t place_reads_occupancy(DbLayout layout, int runs, int counts, int block_threads, size_t lds_bytes,
                                  int *blocks_per_cu)
 {
     return dispatch(layout, runs, counts, [&]<typename L, typename C>() {
@@ -385,7 +402,7 @@ hipError_t set_finish_reads_lds_limit(int counts, size_t /*lds_bytes*/)
     });
 }
 
-hipError_t launch_algorithmic_bytes(const PlaceParams &p, DbLayout layout, bool runs, unsigned long long *d_total,
+hipError_t launch_algorithmic_bytes(const PlaceParams &p, DbLayout layout, int runs, unsigned long long *d_total,
                                     hipStream_t stream)
 {
     const dim3 block(256);

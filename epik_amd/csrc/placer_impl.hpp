@@ -31,6 +31,9 @@ struct epik_amd_placer {
     std::vector<uint32_t> h_char_class;  // the same on the host (shard_place.hip: which reads may hold an ambiguous k-mer)
     epik_amd::PlaceParams params{};  // batch fields are filled per call
     epik_amd::image::Plan plan{};    // kernel, layout and sizes chosen at create()
+    // run coding of the one-wavefront kernel, latched at create(): 0, epik_amd::kRunsMixed, or epik_amd::kRunLists (every
+    // list a run: 16- and 32-bit counts kept per list, db_image.hpp run_counts_apply; EPIK_AMD_RUN_COUNTS=ring turns it off)
+    int runs = 0;
     bool team = false;               // the team kernel (one workgroup per read) places; else one wavefront per read
     int team_waves = 0;
     const uint8_t *team_table = nullptr;

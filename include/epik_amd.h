@@ -154,6 +154,18 @@ typedef struct {
 int epik_amd_placer_plan_sizes(uint32_t kmer_size, uint32_t alphabet_size, uint32_t num_branches, uint32_t keep_at_most,
                                const epik_amd_list_bin *bins, uint64_t n_bins, uint32_t shard_index, uint32_t shard_count,
                                uint64_t free_bytes, epik_amd_plan *plan);
+/*
+ * Whether the one-wavefront kernel keeps the k-mer counts per LIST, with counts of `counts` (0/1/2 = 8/16/32 bits):
+ * *lists = 1 when the image is run-coded, every list the placer keeps is one ascending run of branches, and the counts
+ * are 16 or 32 bits, in the packed and paired layouts -- each list then adds to its run's counts once, and the posting
+ * ring carries scores only; 0: the counts go through the ring chunk by chunk (as for every other image).  The scores
+ * and counts are the same either way.  EPIK_AMD_RUN_COUNTS (read at create()): `ring` keeps the chunk-by-chunk counts
+ * everywhere, `lists` takes list counts in the filtered layout as well (by itself it keeps the ring there).  plan_run_counts: what
+ * create() would choose for this database (no device); run_counts: what this handle does.
+ */
+int epik_amd_placer_plan_run_counts(const epik_amd_placer_desc *desc, uint32_t shard_index, uint32_t shard_count,
+                                    uint64_t free_bytes, uint32_t counts, uint32_t *lists);
+int epik_amd_placer_run_counts(const epik_amd_placer *p, uint32_t counts, uint32_t *lists);
 /* The image create() uploads for that plan, written front to back into host buffers of
  * plan->table_bytes / filter_bytes / posting_bytes (NULL = that part is produced and dropped).
  * Host only; create() streams the same bytes to the device without holding them. */
