@@ -258,20 +258,19 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_placer_set_timing.argtypes = [vp, i32]
     lib.epik_amd_placer_last_kernel_ms.restype = i32
     lib.epik_amd_placer_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-    lib.epik_amd_placer_strand_workspace_bytes.restype = i32
-    lib.epik_amd_placer_strand_workspace_bytes.argtypes = [vp, u64, u64, ctypes.c_uint32, ctypes.POINTER(u64)]
-    lib.epik_amd_placer_place_strands_device.restype = i32
-    lib.epik_amd_placer_place_strands_device.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, u64, vp, vp, vp, vp, vp]
-    lib.epik_amd_placer_place_strands.restype = i32
-    lib.epik_amd_placer_place_strands.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, vp, vp, vp]
     lib.epik_amd_codon_table.restype = i32
     lib.epik_amd_codon_table.argtypes = [vp]
-    lib.epik_amd_placer_frame_workspace_bytes.restype = i32
-    lib.epik_amd_placer_frame_workspace_bytes.argtypes = [vp, u64, u64, ctypes.c_uint32, ctypes.POINTER(u64)]
-    lib.epik_amd_placer_place_frames_device.restype = i32
-    lib.epik_amd_placer_place_frames_device.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, u64, vp, vp, vp, vp, vp]
-    lib.epik_amd_placer_place_frames.restype = i32
-    lib.epik_amd_placer_place_frames.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, vp, vp, vp]
+    # (strand and frame placement: the same prototypes)
+    for names, argtypes in (
+            (("epik_amd_placer_strand_workspace_bytes", "epik_amd_placer_frame_workspace_bytes"),
+             [vp, u64, u64, ctypes.c_uint32, ctypes.POINTER(u64)]),
+            (("epik_amd_placer_place_strands_device", "epik_amd_placer_place_frames_device"),
+             [vp, vp, vp, u64, ctypes.c_uint32, vp, u64, vp, vp, vp, vp, vp]),
+            (("epik_amd_placer_place_strands", "epik_amd_placer_place_frames"),
+             [vp, vp, vp, u64, ctypes.c_uint32, vp, vp, vp, vp])):
+        for name in names:
+            getattr(lib, name).restype = i32
+            getattr(lib, name).argtypes = argtypes
     _lib = lib
     return lib
 

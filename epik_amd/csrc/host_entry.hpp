@@ -1,0 +1,167 @@
+// host_entry.hpp -- the host side shared by the placements around epik_amd_placer_place_device: the synchronous
+// host-buffer entry points of strand_place.hip and frame_place.hip are place_host_chunked over a HostVariant each;
+// shard_place.hip takes the HIP-error macro and the batch check.  Internal to libepik_amd.
+#ifndef EPIK_AMD_HOST_ENTRY_HPP
+#define EPIK_AMD_HOST_ENTRY_HPP
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "placer_impl.hpp"
+
+#define HIP_TRY(expr)                                                                                            \
+    do {                                                                                                         \
+        const hipError_t e_ = (expr);                                                                            \
+        if (e_ != hipSuccess) return epik_amd::fail_with(EPIK_AMD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+namespace epik_amd {
+
+// the kernels around the placement run workgroups of four waves
+constexpr uint32_t kWave = 64, kBlockWaves = 4, kBlock = kWave * kBlockWaves;
+
+inline uint64_t align_up(uint64_t x) { return (x + 255) / 256 * 256; }
+__host__ __device__ inline uint32_t bitrev4(uint32_t c) { return (c & 1u) << 3 | (c & 2u) << 1 | (c & 4u) >> 1 | (c & 8u) >> 3; }
+__host__ __device__ inline bool has_rows(uint32_t n_rows) { return n_rows != 0 && n_rows != EPIK_AMD_ROWS_COUNTS_TOO_NARROW; }
+
+// workgroups for `units` waves of work: at least one, at most max_blocks (the kernels stride over the rest)
+inline uint32_t grid_for(uint64_t units, uint64_t max_blocks)
+{
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((units + kBlockWaves - 1) / kBlockWaves, max_blocks));
+}
+
+// The checks epik_amd_placer_place makes of a host batch of n >= 1 reads, in its order and words; `longest` gets the
+// batch's longest read.
+inline int check_host_batch(const char *seqs, const uint64_t *seq_offsets, uint64_t n, const void *rows,
+                            const void *n_rows, uint64_t &longest)
+{
+    if (!seqs || !seq_offsets || !rows || !n_rows) return fail_with(EPIK_AMD_ERR_INVALID, "null host buffer");
+    if (seq_offsets[0] != 0) return fail_with(EPIK_AMD_ERR_INVALID, "seq_offsets[0] must be 0");
+    longest = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (seq_offsets[i + 1] < seq_offsets[i] || seq_offsets[i + 1] - seq_offsets[i] > 0xffffffffull)
+            return fail_with(EPIK_AMD_ERR_INVALID, "seq_offsets not monotone, or a read of 2^32 characters or more");
+        longest = std::max<uint64_t>(longest, seq_offsets[i + 1] - seq_offsets[i]);
+    }
+    return EPIK_AMD_OK;
+}
+
+// k-mers a sequence may have with counts of that width (capi.hip's rule: the top bit of 16- and 32-bit counts is a flag)
+inline uint64_t max_kmers_of_counts(int counts) { return counts == kCounts8 ? 255u : counts == kCounts16 ? 32767u : 0x7fffffffull; }
+
+// The count width of a host entry point, as epik_amd_placer_place chooses it, from the longest sequence the call
+// places: epik_amd_placer_choose_counts, or a forced width kept unless it cannot hold that sequence's k-mers (no read
+// comes back EPIK_AMD_ROWS_COUNTS_TOO_NARROW from a host entry point).  The handle's count state is restored when
+// the guard goes, however the call ends.
+struct CountWidthGuard {
+    CountWidthGuard(epik_amd_placer *p_, uint64_t longest) : p(p_), counts(p_->counts), hint(p_->longest_read_hint)
+    {
+        if (!p->counts_forced) {
+            rc = epik_amd_placer_choose_counts(p, longest);
+            return;
+        }
+        const uint64_t k = p->params.kmer_size, kmers = longest >= k ? longest - k + 1 : 0;
+        if (kmers > max_kmers_of_counts(p->counts)) p->counts = kmers > max_kmers_of_counts(kCounts16) ? kCounts32 : kCounts16;
+        p->longest_read_hint = longest;
+    }
+    ~CountWidthGuard() { p->counts = counts, p->longest_read_hint = hint; }
+    epik_amd_placer *p;
+    int counts;
+    uint64_t hint;
+    int rc = EPIK_AMD_OK;  // of the choice
+};
+
+// What place_host_chunked needs of a placement around epik_amd_placer_place_device
+struct HostVariant {
+    uint64_t chunk_reads, chunk_bytes;  // the device budget per chunk
+    const char *chunk_reads_env;        // overrides chunk_reads (tests: fewer reads per chunk)
+    // its epik_amd_placer_*_workspace_bytes
+    int (*workspace_bytes)(const epik_amd_placer *p, uint64_t n, uint64_t seq_bytes, uint32_t mode, uint64_t *bytes);
+    // the bytes at the start of the workspace zeroed before each chunk is placed (nullptr: none)
+    uint64_t (*zeroed_bytes)(const epik_amd_placer *p, uint64_t n, uint32_t mode);
+    // its asynchronous device entry; d_label: a byte per read (strand, frame)
+    int (*place_device)(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offsets, uint64_t n, uint32_t mode,
+                        void *d_workspace, uint64_t workspace_bytes, void *d_rows, void *d_n_rows, void *d_kmer_counts,
+                        void *d_label, hipStream_t stream);
+};
+
+// The synchronous host-buffer entry point of a variant, once the caller has checked the handle, the mode and the
+// batch (n >= 1, check_host_batch): the count width for `longest_placed`, the longest sequence the device entry
+// places; then the batch in chunks through one device allocation, each copied in, placed on the handle's stream,
+// copied out and waited for.
+inline int place_host_chunked(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                              uint32_t mode, uint64_t longest_placed, const HostVariant &v, epik_amd_placement *rows,
+                              uint32_t *n_rows, uint32_t *kmer_counts, uint8_t *label)
+{
+    HIP_TRY(hipSetDevice(p->device));
+    const CountWidthGuard width(p, longest_placed);
+    if (width.rc != EPIK_AMD_OK) return width.rc;
+
+    // chunks of at most chunk_reads reads and chunk_bytes characters (a longer read: a chunk of its own)
+    uint64_t chunk_reads = v.chunk_reads;
+    if (const char *e = std::getenv(v.chunk_reads_env)) chunk_reads = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+    std::vector<uint64_t> starts{0};
+    uint64_t max_reads = 0, max_bytes = 0;
+    for (uint64_t r0 = 0; r0 < n;) {
+        uint64_t r1 = r0 + 1;
+        while (r1 < n && r1 - r0 < chunk_reads && seq_offsets[r1 + 1] - seq_offsets[r0] <= v.chunk_bytes) ++r1;
+        max_reads = std::max(max_reads, r1 - r0);
+        max_bytes = std::max(max_bytes, seq_offsets[r1] - seq_offsets[r0]);
+        starts.push_back(r0 = r1);
+    }
+    const uint64_t keep = p->params.keep_at_most;
+    uint64_t ws_bytes = 0;
+    if (const int rc = v.workspace_bytes(p, max_reads, max_bytes, mode, &ws_bytes); rc != EPIK_AMD_OK) return rc;
+    // one allocation: seqs | offsets | rows | n_rows | counts | label | workspace
+    const uint64_t o_offs = align_up(max_bytes + 1), o_rows = o_offs + align_up((max_reads + 1) * sizeof(uint64_t));
+    const uint64_t o_nrows = o_rows + align_up(max_reads * keep * sizeof(epik_amd_placement));
+    const uint64_t o_counts = o_nrows + align_up(max_reads * sizeof(uint32_t));
+    const uint64_t o_label = o_counts + align_up(max_reads * keep * sizeof(uint32_t));
+    const uint64_t o_ws = o_label + align_up(max_reads);
+    struct ChunkBuffers {  // (freed however the call ends, after its stream has drained)
+        void *base = nullptr;
+        hipStream_t stream = nullptr;
+        ~ChunkBuffers()
+        {
+            if (stream) (void)hipStreamSynchronize(stream);
+            if (base) (void)hipFree(base);
+        }
+    } buf;
+    HIP_TRY(hipMalloc(&buf.base, o_ws + ws_bytes));
+    buf.stream = p->stream;
+    uint8_t *d = static_cast<uint8_t *>(buf.base);
+    auto *d_offs = reinterpret_cast<uint64_t *>(d + o_offs);
+    auto *d_rows = reinterpret_cast<epik_amd_placement *>(d + o_rows);
+    auto *d_nrows = reinterpret_cast<uint32_t *>(d + o_nrows);
+    auto *d_counts = reinterpret_cast<uint32_t *>(d + o_counts);
+    uint8_t *d_label = d + o_label, *d_ws = ws_bytes ? d + o_ws : nullptr;
+    std::vector<uint64_t> offs(max_reads + 1);
+    for (size_t c = 0; c + 1 < starts.size(); ++c) {
+        const uint64_t r0 = starts[c], cnt = starts[c + 1] - r0, b0 = seq_offsets[r0], bytes = seq_offsets[r0 + cnt] - b0;
+        for (uint64_t i = 0; i <= cnt; ++i) offs[i] = seq_offsets[r0 + i] - b0;
+        if (bytes) HIP_TRY(hipMemcpyAsync(d, seqs + b0, bytes, hipMemcpyHostToDevice, p->stream));
+        HIP_TRY(hipMemcpyAsync(d_offs, offs.data(), (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+        // rows beyond n_rows[i] are never written by the kernels: zero, as epik_amd_placer_place leaves them
+        HIP_TRY(hipMemsetAsync(d_rows, 0, cnt * keep * sizeof(epik_amd_placement), p->stream));
+        HIP_TRY(hipMemsetAsync(d_counts, 0, cnt * keep * sizeof(uint32_t), p->stream));
+        if (const uint64_t zeroed = v.zeroed_bytes ? v.zeroed_bytes(p, cnt, mode) : 0) HIP_TRY(hipMemsetAsync(d_ws, 0, zeroed, p->stream));
+        uint64_t chunk_ws = 0;
+        if (const int rc = v.workspace_bytes(p, cnt, bytes, mode, &chunk_ws); rc != EPIK_AMD_OK) return rc;
+        if (const int rc = v.place_device(p, d, d_offs, cnt, mode, d_ws, chunk_ws, d_rows, d_nrows, d_counts, d_label, p->stream);
+            rc != EPIK_AMD_OK)
+            return rc;
+        HIP_TRY(hipMemcpyAsync(rows + r0 * keep, d_rows, cnt * keep * sizeof(epik_amd_placement), hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipMemcpyAsync(n_rows + r0, d_nrows, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+        if (kmer_counts)
+            HIP_TRY(hipMemcpyAsync(kmer_counts + r0 * keep, d_counts, cnt * keep * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+        if (label) HIP_TRY(hipMemcpyAsync(label + r0, d_label, cnt, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+    }
+    return EPIK_AMD_OK;
+}
+
+}  // namespace epik_amd
+#endif

@@ -27,17 +27,11 @@
 #include <thread>
 #include <vector>
 
-#include "placer_impl.hpp"
+#include "host_entry.hpp"
 
 namespace {
 
 using epik_amd::fail_with;
-
-#define SHARD_TRY(expr)                                                                                  \
-    do {                                                                                                 \
-        const hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail_with(EPIK_AMD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 constexpr uint32_t kAmbNone = 0xffffffffu;
 
@@ -194,8 +188,6 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
     for (uint32_t g = 0; g < G; ++g)
         if (!shards[g]) return fail_with(EPIK_AMD_ERR_INVALID, "null placer");
     if (n == 0) return EPIK_AMD_OK;
-    if (!seqs || !seq_offsets || !rows || !n_rows) return fail_with(EPIK_AMD_ERR_INVALID, "null host buffer");
-    if (seq_offsets[0] != 0) return fail_with(EPIK_AMD_ERR_INVALID, "seq_offsets[0] must be 0");
     // ONE shard is the whole of what there is to place against: the one-pass placement, which streams a read's rows
     // once -- accumulate + finish stream them twice (as postings, then as list entries), 2.3 x the time for the same
     // rows (measured, round 4: 16.7 against 38.5 M reads/s at N = 9 999).  EPIK_AMD_SHARD_HALVES=1: the two halves
@@ -204,6 +196,8 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
         const char *halves = std::getenv("EPIK_AMD_SHARD_HALVES");
         if (!(halves && halves[0] == '1')) return epik_amd_placer_place(shards[0], seqs, seq_offsets, n, rows, n_rows, kmer_counts);
     }
+    uint64_t longest = 0;
+    if (const int rc = epik_amd::check_host_batch(seqs, seq_offsets, n, rows, n_rows, longest); rc != EPIK_AMD_OK) return rc;
     // every handle: the same tree and parameters, kernels that leave partial lists, the same list geometry
     epik_amd_partial_info info0{};
     for (uint32_t g = 0; g < G; ++g) {
@@ -221,13 +215,6 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
     }
     const uint32_t S = info0.slices, N = shards[0]->params.num_branches, keep = shards[0]->params.keep_at_most;
     const uint32_t k = shards[0]->params.kmer_size;
-    uint64_t longest = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (seq_offsets[i + 1] < seq_offsets[i] || seq_offsets[i + 1] - seq_offsets[i] > 0xffffffffull)
-            return fail_with(EPIK_AMD_ERR_INVALID, "seq_offsets not monotone, or a read of 2^32 characters or more");
-        const uint64_t len = seq_offsets[i + 1] - seq_offsets[i];
-        longest = std::max(longest, len);
-    }
     // the same count width everywhere (it is the format of the entries): what the longest read needs
     for (uint32_t g = 0; g < G; ++g)
         if (const int rc = epik_amd_placer_choose_counts(shards[g], longest); rc != EPIK_AMD_OK) return rc;
@@ -323,11 +310,11 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
     for (uint32_t g = 0; g < G; ++g) {
         ShardSide &s = sides[g];
         if (state->ready) {  // (the batch itself is new every call)
-            SHARD_TRY(hipSetDevice(s.device));
-            SHARD_TRY(s.seqs.reserve((size_t)seq_offsets[n] + 64));
-            SHARD_TRY(s.offsets.reserve((size_t)(n + 1) * sizeof(uint64_t)));
-            if (seq_offsets[n]) SHARD_TRY(hipMemcpyAsync(s.seqs.p, seqs, (size_t)seq_offsets[n], hipMemcpyHostToDevice, s.compute));
-            SHARD_TRY(hipMemcpyAsync(s.offsets.p, seq_offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s.compute));
+            HIP_TRY(hipSetDevice(s.device));
+            HIP_TRY(s.seqs.reserve((size_t)seq_offsets[n] + 64));
+            HIP_TRY(s.offsets.reserve((size_t)(n + 1) * sizeof(uint64_t)));
+            if (seq_offsets[n]) HIP_TRY(hipMemcpyAsync(s.seqs.p, seqs, (size_t)seq_offsets[n], hipMemcpyHostToDevice, s.compute));
+            HIP_TRY(hipMemcpyAsync(s.offsets.p, seq_offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s.compute));
             continue;
         }
         s.h = shards[g];
@@ -343,23 +330,23 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
             for (int q = 0; q < EPIK_AMD_MAX_SHARDS; ++q)
                 s.recv_entries[b][q].device = s.recv_index[b][q].device = s.recv_order[b][q].device = s.recv_avg[b][q].device = s.device;
         }
-        SHARD_TRY(hipSetDevice(s.device));
+        HIP_TRY(hipSetDevice(s.device));
         for (uint32_t r = 0; r < G; ++r)  // (direct copies over the link where the devices allow it; not fatal otherwise)
             if (shards[r]->device != s.device) {
                 (void)hipDeviceEnablePeerAccess(shards[r]->device, 0);
                 (void)hipGetLastError();
             }
         for (int b = 0; b < 2; ++b) {
-            SHARD_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_part[b]), G * sizeof(unsigned long long), hipHostMallocDefault));
-            SHARD_TRY(hipEventCreateWithFlags(&s.accumulated[b], hipEventDisableTiming));
-            SHARD_TRY(hipEventCreateWithFlags(&s.arrived[b], hipEventDisableTiming));
-            SHARD_TRY(hipEventCreateWithFlags(&s.finished[b], hipEventDisableTiming));
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_part[b]), G * sizeof(unsigned long long), hipHostMallocDefault));
+            HIP_TRY(hipEventCreateWithFlags(&s.accumulated[b], hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&s.arrived[b], hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&s.finished[b], hipEventDisableTiming));
         }
         // the whole batch, once, on every device
-        SHARD_TRY(s.seqs.reserve((size_t)seq_offsets[n] + 64));
-        SHARD_TRY(s.offsets.reserve((size_t)(n + 1) * sizeof(uint64_t)));
-        if (seq_offsets[n]) SHARD_TRY(hipMemcpyAsync(s.seqs.p, seqs, (size_t)seq_offsets[n], hipMemcpyHostToDevice, s.compute));
-        SHARD_TRY(hipMemcpyAsync(s.offsets.p, seq_offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s.compute));
+        HIP_TRY(s.seqs.reserve((size_t)seq_offsets[n] + 64));
+        HIP_TRY(s.offsets.reserve((size_t)(n + 1) * sizeof(uint64_t)));
+        if (seq_offsets[n]) HIP_TRY(hipMemcpyAsync(s.seqs.p, seqs, (size_t)seq_offsets[n], hipMemcpyHostToDevice, s.compute));
+        HIP_TRY(hipMemcpyAsync(s.offsets.p, seq_offsets, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s.compute));
     }
     state->ready = true;
 
@@ -408,34 +395,34 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
         }
         for (uint32_t g = 0; g < G; ++g) {
             ShardSide &s = sides[g];
-            SHARD_TRY(hipSetDevice(s.device));
+            HIP_TRY(hipSetDevice(s.device));
             const uint64_t cap = std::min<uint64_t>(std::max(entries_wanted(g, kmers), min_entries), 0xfffffff0ull);
             // (a buffer still in use by the copies of two chunks ago: they have been waited for in complete())
-            SHARD_TRY(s.entries[b].reserve((size_t)cap * entry_bytes));
+            HIP_TRY(s.entries[b].reserve((size_t)cap * entry_bytes));
             s.entries_cap[b] = cap;
-            SHARD_TRY(s.index[b].reserve((size_t)ch.per * G * S * 8u));
-            SHARD_TRY(s.part_entries[b].reserve(G * sizeof(unsigned long long)));
-            SHARD_TRY(hipMemsetAsync(s.index[b].p, 0, (size_t)ch.per * G * S * 8u, s.compute));
+            HIP_TRY(s.index[b].reserve((size_t)ch.per * G * S * 8u));
+            HIP_TRY(s.part_entries[b].reserve(G * sizeof(unsigned long long)));
+            HIP_TRY(hipMemsetAsync(s.index[b].p, 0, (size_t)ch.per * G * S * 8u, s.compute));
             void *d_slot = nullptr, *d_order = nullptr, *d_avg = nullptr;
             if (ch.amb_per_owner) {
                 const size_t cells = (size_t)ch.amb_per_owner * G * N;
-                SHARD_TRY(s.amb_slot[b].reserve(ch.count * sizeof(int32_t)));
-                SHARD_TRY(s.amb_order[b].reserve(cells * 4u));
-                SHARD_TRY(s.amb_avg[b].reserve(cells * 4u));
-                SHARD_TRY(s.my_slot[b].reserve(ch.count * sizeof(int32_t)));
+                HIP_TRY(s.amb_slot[b].reserve(ch.count * sizeof(int32_t)));
+                HIP_TRY(s.amb_order[b].reserve(cells * 4u));
+                HIP_TRY(s.amb_avg[b].reserve(cells * 4u));
+                HIP_TRY(s.my_slot[b].reserve(ch.count * sizeof(int32_t)));
                 if (s.h_slots_cap[b] < 2 * ch.count) {
                     if (s.h_slots[b]) (void)hipHostFree(s.h_slots[b]);
                     s.h_slots[b] = nullptr, s.h_slots_cap[b] = 0;
-                    SHARD_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_slots[b]), 2 * ch.count * sizeof(int32_t), hipHostMallocDefault));
+                    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_slots[b]), 2 * ch.count * sizeof(int32_t), hipHostMallocDefault));
                     s.h_slots_cap[b] = 2 * ch.count;
                 }
                 // (set b's copies of two chunks ago have been waited for in complete(), like its device buffers)
                 std::memcpy(s.h_slots[b], ch.slot.data(), ch.count * sizeof(int32_t));
                 std::memcpy(s.h_slots[b] + ch.count, ch.slot_in_part.data(), ch.count * sizeof(int32_t));
-                SHARD_TRY(hipMemcpyAsync(s.amb_slot[b].p, s.h_slots[b], ch.count * sizeof(int32_t), hipMemcpyHostToDevice, s.compute));
-                SHARD_TRY(hipMemcpyAsync(s.my_slot[b].p, s.h_slots[b] + ch.count, ch.count * sizeof(int32_t), hipMemcpyHostToDevice, s.compute));
-                SHARD_TRY(hipMemsetAsync(s.amb_order[b].p, 0xff, cells * 4u, s.compute));
-                SHARD_TRY(hipMemsetAsync(s.amb_avg[b].p, 0, cells * 4u, s.compute));
+                HIP_TRY(hipMemcpyAsync(s.amb_slot[b].p, s.h_slots[b], ch.count * sizeof(int32_t), hipMemcpyHostToDevice, s.compute));
+                HIP_TRY(hipMemcpyAsync(s.my_slot[b].p, s.h_slots[b] + ch.count, ch.count * sizeof(int32_t), hipMemcpyHostToDevice, s.compute));
+                HIP_TRY(hipMemsetAsync(s.amb_order[b].p, 0xff, cells * 4u, s.compute));
+                HIP_TRY(hipMemsetAsync(s.amb_avg[b].p, 0, cells * 4u, s.compute));
                 d_slot = s.amb_slot[b].p, d_order = s.amb_order[b].p, d_avg = s.amb_avg[b].p;
             }
             if (const int rc = epik_amd_placer_accumulate_lists_device(
@@ -443,8 +430,8 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
                     s.part_entries[b].p, d_slot, d_order, d_avg, s.compute);
                 rc != EPIK_AMD_OK)
                 return rc;
-            SHARD_TRY(hipMemcpyAsync(s.h_part[b], s.part_entries[b].p, G * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.compute));
-            SHARD_TRY(hipEventRecord(s.accumulated[b], s.compute));
+            HIP_TRY(hipMemcpyAsync(s.h_part[b], s.part_entries[b].p, G * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.compute));
+            HIP_TRY(hipEventRecord(s.accumulated[b], s.compute));
         }
         return EPIK_AMD_OK;
     };
@@ -454,8 +441,8 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
         for (;;) {  // (until every shard's lists fit: once more at most, with what they asked for)
             uint64_t worst = 0;
             for (uint32_t g = 0; g < G; ++g) {
-                SHARD_TRY(hipSetDevice(sides[g].device));
-                SHARD_TRY(hipEventSynchronize(sides[g].accumulated[b]));
+                HIP_TRY(hipSetDevice(sides[g].device));
+                HIP_TRY(hipEventSynchronize(sides[g].accumulated[b]));
                 uint64_t total = 0;
                 for (uint32_t r = 0; r < G; ++r) total += sides[g].h_part[b][r];
                 if (total > sides[g].entries_cap[b]) worst = std::max(worst, total);
@@ -469,7 +456,7 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
             const uint64_t begin = std::min(ch.count, r * ch.per), end = std::min(ch.count, (r + 1) * ch.per);
             const uint64_t m = end - begin;
             if (m == 0) continue;
-            SHARD_TRY(hipSetDevice(f.device));
+            HIP_TRY(hipSetDevice(f.device));
             const void *entries[EPIK_AMD_MAX_SHARDS], *index[EPIK_AMD_MAX_SHARDS];
             AmbSources amb{};
             amb.n_shards = G;
@@ -481,14 +468,14 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
                 const size_t bytes = (size_t)src.h_part[b][r] * entry_bytes, index_bytes = (size_t)m * S * 8u;
                 const uint8_t *src_entries = src.entries[b].as<uint8_t>() + first * entry_bytes;
                 const uint8_t *src_index = src.index[b].as<uint8_t>() + (size_t)r * ch.per * S * 8u;
-                SHARD_TRY(hipStreamWaitEvent(f.copy, src.accumulated[b], 0));
+                HIP_TRY(hipStreamWaitEvent(f.copy, src.accumulated[b], 0));
                 if (g == r) {  // its own part is where it is
                     entries[g] = src_entries, index[g] = src_index;
                 } else {
-                    SHARD_TRY(f.recv_entries[b][g].reserve(bytes + 16));
-                    SHARD_TRY(f.recv_index[b][g].reserve(index_bytes));
-                    SHARD_TRY(peer_copy(f.recv_entries[b][g].p, f.device, src_entries, src.device, bytes, f.copy));
-                    SHARD_TRY(peer_copy(f.recv_index[b][g].p, f.device, src_index, src.device, index_bytes, f.copy));
+                    HIP_TRY(f.recv_entries[b][g].reserve(bytes + 16));
+                    HIP_TRY(f.recv_index[b][g].reserve(index_bytes));
+                    HIP_TRY(peer_copy(f.recv_entries[b][g].p, f.device, src_entries, src.device, bytes, f.copy));
+                    HIP_TRY(peer_copy(f.recv_index[b][g].p, f.device, src_index, src.device, index_bytes, f.copy));
                     entries[g] = f.recv_entries[b][g].p, index[g] = f.recv_index[b][g].p;
                 }
                 if (ch.amb_per_owner) {  // the records of this finisher's slots
@@ -497,44 +484,44 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
                     if (g == r) {
                         amb.order[g] = reinterpret_cast<const uint32_t *>(o), amb.avg[g] = reinterpret_cast<const float *>(a);
                     } else {
-                        SHARD_TRY(f.recv_order[b][g].reserve(amb_cells * 4u));
-                        SHARD_TRY(f.recv_avg[b][g].reserve(amb_cells * 4u));
-                        SHARD_TRY(peer_copy(f.recv_order[b][g].p, f.device, o, src.device, amb_cells * 4u, f.copy));
-                        SHARD_TRY(peer_copy(f.recv_avg[b][g].p, f.device, a, src.device, amb_cells * 4u, f.copy));
+                        HIP_TRY(f.recv_order[b][g].reserve(amb_cells * 4u));
+                        HIP_TRY(f.recv_avg[b][g].reserve(amb_cells * 4u));
+                        HIP_TRY(peer_copy(f.recv_order[b][g].p, f.device, o, src.device, amb_cells * 4u, f.copy));
+                        HIP_TRY(peer_copy(f.recv_avg[b][g].p, f.device, a, src.device, amb_cells * 4u, f.copy));
                         amb.order[g] = f.recv_order[b][g].as<uint32_t>(), amb.avg[g] = f.recv_avg[b][g].as<float>();
                     }
                 }
             }
-            SHARD_TRY(hipEventRecord(f.arrived[b], f.copy));
-            SHARD_TRY(hipStreamWaitEvent(f.compute, f.arrived[b], 0));
+            HIP_TRY(hipEventRecord(f.arrived[b], f.copy));
+            HIP_TRY(hipStreamWaitEvent(f.compute, f.arrived[b], 0));
             void *d_slot = nullptr, *d_avg = nullptr;
             if (ch.amb_per_owner) {
-                SHARD_TRY(f.my_avg[b].reserve(amb_cells * 4u));
+                HIP_TRY(f.my_avg[b].reserve(amb_cells * 4u));
                 hipLaunchKernelGGL(combine_amb_kernel, dim3((unsigned)((amb_cells + 255) / 256)), dim3(256), 0, f.compute, amb,
                                    (uint64_t)amb_cells, f.my_avg[b].as<float>());
-                SHARD_TRY(hipGetLastError());
+                HIP_TRY(hipGetLastError());
                 d_slot = f.my_slot[b].as<int32_t>() + begin, d_avg = f.my_avg[b].p;  // (uploaded with the chunk, accumulate())
             }
-            SHARD_TRY(f.rows[b].reserve(m * keep * sizeof(epik_amd_placement)));
-            SHARD_TRY(f.n_rows[b].reserve(m * sizeof(uint32_t)));
-            SHARD_TRY(f.counts[b].reserve(m * keep * sizeof(uint32_t)));
-            SHARD_TRY(hipMemsetAsync(f.rows[b].p, 0, m * keep * sizeof(epik_amd_placement), f.compute));
-            SHARD_TRY(hipMemsetAsync(f.counts[b].p, 0, m * keep * sizeof(uint32_t), f.compute));
+            HIP_TRY(f.rows[b].reserve(m * keep * sizeof(epik_amd_placement)));
+            HIP_TRY(f.n_rows[b].reserve(m * sizeof(uint32_t)));
+            HIP_TRY(f.counts[b].reserve(m * keep * sizeof(uint32_t)));
+            HIP_TRY(hipMemsetAsync(f.rows[b].p, 0, m * keep * sizeof(epik_amd_placement), f.compute));
+            HIP_TRY(hipMemsetAsync(f.counts[b].p, 0, m * keep * sizeof(uint32_t), f.compute));
             if (const int rc = epik_amd_placer_finish_lists_device(
                     f.h, f.offsets.as<uint64_t>() + ch.first + begin, m, G, entries, index, d_slot, d_avg, f.rows[b].p,
                     f.n_rows[b].p, f.counts[b].p, f.compute);
                 rc != EPIK_AMD_OK)
                 return rc;
-            SHARD_TRY(f.h_rows[b].reserve(m * keep * sizeof(epik_amd_placement)));
-            SHARD_TRY(f.h_n_rows[b].reserve(m * sizeof(uint32_t)));
-            SHARD_TRY(f.h_counts[b].reserve(m * keep * sizeof(uint32_t)));
-            SHARD_TRY(hipMemcpyAsync(f.h_rows[b].p, f.rows[b].p, m * keep * sizeof(epik_amd_placement), hipMemcpyDeviceToHost, f.compute));
-            SHARD_TRY(hipMemcpyAsync(f.h_n_rows[b].p, f.n_rows[b].p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, f.compute));
+            HIP_TRY(f.h_rows[b].reserve(m * keep * sizeof(epik_amd_placement)));
+            HIP_TRY(f.h_n_rows[b].reserve(m * sizeof(uint32_t)));
+            HIP_TRY(f.h_counts[b].reserve(m * keep * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpyAsync(f.h_rows[b].p, f.rows[b].p, m * keep * sizeof(epik_amd_placement), hipMemcpyDeviceToHost, f.compute));
+            HIP_TRY(hipMemcpyAsync(f.h_n_rows[b].p, f.n_rows[b].p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, f.compute));
             if (kmer_counts)
-                SHARD_TRY(hipMemcpyAsync(f.h_counts[b].p, f.counts[b].p, m * keep * sizeof(uint32_t), hipMemcpyDeviceToHost, f.compute));
+                HIP_TRY(hipMemcpyAsync(f.h_counts[b].p, f.counts[b].p, m * keep * sizeof(uint32_t), hipMemcpyDeviceToHost, f.compute));
             f.out_at[b] = ch.first + begin;
             f.out_reads[b] = m;
-            SHARD_TRY(hipEventRecord(f.finished[b], f.compute));
+            HIP_TRY(hipEventRecord(f.finished[b], f.compute));
         }
         return EPIK_AMD_OK;
     };
@@ -543,8 +530,8 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
     auto wait_set = [&](int b) -> int {
         for (uint32_t r = 0; r < G; ++r) {
             ShardSide &f = sides[r];
-            SHARD_TRY(hipSetDevice(f.device));
-            SHARD_TRY(hipEventSynchronize(f.finished[b]));
+            HIP_TRY(hipSetDevice(f.device));
+            HIP_TRY(hipEventSynchronize(f.finished[b]));
             if (const uint64_t m = f.out_reads[b]) {  // its rows are home: into the caller's arrays
                 const uint64_t at = f.out_at[b];
                 std::memcpy(rows + at * keep, f.h_rows[b].p, m * keep * sizeof(epik_amd_placement));
@@ -574,9 +561,9 @@ int place_sharded_impl(epik_amd_placer *const *shards, uint32_t G, const char *s
         if (used[b])
             if (const int rc = wait_set(b); rc != EPIK_AMD_OK) return rc;
     for (uint32_t g = 0; g < G; ++g) {
-        SHARD_TRY(hipSetDevice(sides[g].device));
-        SHARD_TRY(hipStreamSynchronize(sides[g].copy));
-        SHARD_TRY(hipStreamSynchronize(sides[g].compute));
+        HIP_TRY(hipSetDevice(sides[g].device));
+        HIP_TRY(hipStreamSynchronize(sides[g].copy));
+        HIP_TRY(hipStreamSynchronize(sides[g].compute));
     }
     return EPIK_AMD_OK;
 }

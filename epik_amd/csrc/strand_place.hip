@@ -31,34 +31,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "placer_impl.hpp"
+#include "host_entry.hpp"
 
 namespace {
 
-using epik_amd::fail_with;
+using namespace epik_amd;
 
-#define STRAND_TRY(expr)                                                                                 \
-    do {                                                                                                 \
-        const hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail_with(EPIK_AMD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kBlockWaves = 4;
-constexpr uint32_t kBlock = kWave * kBlockWaves;
 constexpr uint64_t kMaxBlocks = 8192;  // (grid-stride beyond: a million reads is 256 K waves of work either way)
-constexpr uint64_t kAlign = 256;
-// the host entry's device budget per chunk (EPIK_AMD_STRAND_CHUNK_READS: fewer reads per chunk, for tests)
-constexpr uint64_t kChunkReads = 1u << 18, kChunkBytes = 64u << 20;
-
-inline uint64_t align_up(uint64_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-inline uint32_t bitrev4(uint32_t c) { return (c & 1u) << 3 | (c & 2u) << 1 | (c & 4u) >> 1 | (c & 8u) >> 3; }
-__host__ __device__ inline bool has_rows(uint32_t n_rows) { return n_rows != 0 && n_rows != EPIK_AMD_ROWS_COUNTS_TOO_NARROW; }
 
 // For every byte, a byte of the complemented class (by value in the kernel's arguments: no allocation)
 struct ComplementMap {
@@ -189,11 +170,6 @@ int complement_map(const epik_amd_placer *p, ComplementMap &map)
     return EPIK_AMD_OK;
 }
 
-uint32_t grid_for(uint64_t units)
-{
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((units + kBlockWaves - 1) / kBlockWaves, kMaxBlocks));
-}
-
 int place_strands_device_impl(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offsets, uint64_t n,
                               uint32_t mode, void *d_workspace, uint64_t workspace_bytes, void *d_rows, void *d_n_rows,
                               void *d_kmer_counts, void *d_strand, hipStream_t stream)
@@ -208,7 +184,7 @@ int place_strands_device_impl(epik_amd_placer *p, const void *d_seqs, const void
     ComplementMap map{};
     if (mode != EPIK_AMD_STRAND_FORWARD)
         if (const int rc = complement_map(p, map); rc != EPIK_AMD_OK) return rc;
-    STRAND_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipSetDevice(p->device));
     const auto *offs = static_cast<const uint64_t *>(d_seq_offsets);
     uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     uint8_t *strand = static_cast<uint8_t *>(d_strand);
@@ -218,19 +194,19 @@ int place_strands_device_impl(epik_amd_placer *p, const void *d_seqs, const void
             rc != EPIK_AMD_OK)
             return rc;
         if (mode == EPIK_AMD_STRAND_FORWARD) {
-            if (strand) STRAND_TRY(hipMemsetAsync(strand, 0, n, stream));
+            if (strand) HIP_TRY(hipMemsetAsync(strand, 0, n, stream));
             return EPIK_AMD_OK;
         }
     }
     uint8_t *rc_seqs = ws + l.seqs;
-    hipLaunchKernelGGL(revcomp_kernel, dim3(grid_for((n + kWave - 1) / kWave)), dim3(kBlock), 0, stream, static_cast<const uint8_t *>(d_seqs),
-                       offs, n, rc_seqs, workspace_bytes - l.seqs, map);
-    STRAND_TRY(hipGetLastError());
+    hipLaunchKernelGGL(revcomp_kernel, dim3(grid_for((n + kWave - 1) / kWave, kMaxBlocks)), dim3(kBlock), 0, stream,
+                       static_cast<const uint8_t *>(d_seqs), offs, n, rc_seqs, workspace_bytes - l.seqs, map);
+    HIP_TRY(hipGetLastError());
     if (mode == EPIK_AMD_STRAND_REVERSE) {
         if (const int rc = epik_amd_placer_place_device(p, rc_seqs, d_seq_offsets, n, d_rows, d_n_rows, d_kmer_counts, stream);
             rc != EPIK_AMD_OK)
             return rc;
-        if (strand) STRAND_TRY(hipMemsetAsync(strand, 1, n, stream));
+        if (strand) HIP_TRY(hipMemsetAsync(strand, 1, n, stream));
         return EPIK_AMD_OK;
     }
     auto *rev_rows = reinterpret_cast<epik_amd_placement *>(ws + l.rows);
@@ -239,110 +215,32 @@ int place_strands_device_impl(epik_amd_placer *p, const void *d_seqs, const void
     if (const int rc = epik_amd_placer_place_device(p, rc_seqs, d_seq_offsets, n, rev_rows, rev_n_rows, rev_counts, stream);
         rc != EPIK_AMD_OK)
         return rc;
-    hipLaunchKernelGGL(strand_select_kernel, dim3(grid_for((n + kWave - 1) / kWave)), dim3(kBlock), 0, stream, n, keep,
-                       static_cast<epik_amd_placement *>(d_rows), static_cast<uint32_t *>(d_n_rows),
+    hipLaunchKernelGGL(strand_select_kernel, dim3(grid_for((n + kWave - 1) / kWave, kMaxBlocks)), dim3(kBlock), 0, stream,
+                       n, keep, static_cast<epik_amd_placement *>(d_rows), static_cast<uint32_t *>(d_n_rows),
                        static_cast<uint32_t *>(d_kmer_counts), rev_rows, rev_n_rows, rev_counts, strand);
-    STRAND_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return EPIK_AMD_OK;
 }
 
-// device memory of one host-entry call, freed however the call ends (after its stream has drained)
-struct ChunkBuffers {
-    void *base = nullptr;
-    hipStream_t stream = nullptr;
-    ~ChunkBuffers()
-    {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (base) (void)hipFree(base);
-    }
-};
+// The host entry zeroes what a `both` placement holds ahead of the reversed bytes before every chunk:
+// strand_select_kernel copies all keep row slots of a read where reverse won, and the placement writes n_rows of them.
+uint64_t reverse_rows_bytes(const epik_amd_placer *p, uint64_t n, uint32_t mode)
+{
+    return layout_of(n, p->params.keep_at_most, mode).per_read_bytes;
+}
+
+constexpr HostVariant kStrandHost{.chunk_reads = 1u << 18, .chunk_bytes = 64u << 20, .chunk_reads_env = "EPIK_AMD_STRAND_CHUNK_READS",
+                                  .workspace_bytes = epik_amd_placer_strand_workspace_bytes,
+                                  .zeroed_bytes = reverse_rows_bytes, .place_device = place_strands_device_impl};
 
 int place_strands_impl(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n, uint32_t mode,
                        epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts, uint8_t *strand)
 {
     if (const int rc = check_handle(p, mode); rc != EPIK_AMD_OK) return rc;
     if (n == 0) return EPIK_AMD_OK;
-    if (!seqs || !seq_offsets || !rows || !n_rows) return fail_with(EPIK_AMD_ERR_INVALID, "null host buffer");
-    if (seq_offsets[0] != 0) return fail_with(EPIK_AMD_ERR_INVALID, "seq_offsets[0] must be 0");
     uint64_t longest = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (seq_offsets[i + 1] < seq_offsets[i] || seq_offsets[i + 1] - seq_offsets[i] > 0xffffffffull)
-            return fail_with(EPIK_AMD_ERR_INVALID, "seq_offsets not monotone, or a read of 2^32 characters or more");
-        longest = std::max<uint64_t>(longest, seq_offsets[i + 1] - seq_offsets[i]);
-    }
-    STRAND_TRY(hipSetDevice(p->device));
-    // The count width as epik_amd_placer_place chooses it from the batch's longest read, and the handle's count
-    // state as that call leaves it: restored on return.
-    struct restore_counts {
-        epik_amd_placer *p;
-        int counts;
-        uint64_t hint;
-        ~restore_counts() { p->counts = counts, p->longest_read_hint = hint; }
-    } restore{p, p->counts, p->longest_read_hint};
-    if (!p->counts_forced) {
-        if (const int rc = epik_amd_placer_choose_counts(p, longest); rc != EPIK_AMD_OK) return rc;
-    } else {
-        // (a forced width is kept unless it cannot hold the longest read's k-mers: no read comes back
-        // EPIK_AMD_ROWS_COUNTS_TOO_NARROW from a host entry point)
-        const uint64_t k = p->params.kmer_size, kmers = longest >= k ? longest - k + 1 : 0;
-        const uint64_t cap = p->counts == epik_amd::kCounts8 ? 255u : p->counts == epik_amd::kCounts16 ? 32767u : 0x7fffffffull;
-        if (kmers > cap) p->counts = kmers > 32767u ? epik_amd::kCounts32 : epik_amd::kCounts16;
-        p->longest_read_hint = longest;
-    }
-
-    // chunks of at most kChunkReads reads and kChunkBytes characters (a longer read: a chunk of its own)
-    uint64_t chunk_reads = kChunkReads;
-    if (const char *e = std::getenv("EPIK_AMD_STRAND_CHUNK_READS")) chunk_reads = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
-    std::vector<uint64_t> starts{0};
-    uint64_t max_reads = 0, max_bytes = 0;
-    for (uint64_t r0 = 0; r0 < n;) {
-        uint64_t r1 = r0 + 1;
-        while (r1 < n && r1 - r0 < chunk_reads && seq_offsets[r1 + 1] - seq_offsets[r0] <= kChunkBytes) ++r1;
-        max_reads = std::max(max_reads, r1 - r0);
-        max_bytes = std::max(max_bytes, seq_offsets[r1] - seq_offsets[r0]);
-        starts.push_back(r0 = r1);
-    }
-    const uint64_t keep = p->params.keep_at_most;
-    const WorkspaceLayout wl = layout_of(max_reads, (uint32_t)keep, mode);
-    const uint64_t ws_bytes = mode == EPIK_AMD_STRAND_FORWARD ? 0 : wl.seqs + align_up(max_bytes + 1);
-    // one allocation: seqs | offsets | rows | n_rows | counts | strand | workspace
-    const uint64_t o_offs = align_up(max_bytes + 1), o_rows = o_offs + align_up((max_reads + 1) * sizeof(uint64_t));
-    const uint64_t o_nrows = o_rows + align_up(max_reads * keep * sizeof(epik_amd_placement));
-    const uint64_t o_counts = o_nrows + align_up(max_reads * sizeof(uint32_t));
-    const uint64_t o_strand = o_counts + align_up(max_reads * keep * sizeof(uint32_t));
-    const uint64_t o_ws = o_strand + align_up(max_reads);
-    ChunkBuffers buf;
-    STRAND_TRY(hipMalloc(&buf.base, o_ws + ws_bytes));
-    buf.stream = p->stream;
-    uint8_t *d = static_cast<uint8_t *>(buf.base);
-    auto *d_offs = reinterpret_cast<uint64_t *>(d + o_offs);
-    auto *d_rows = reinterpret_cast<epik_amd_placement *>(d + o_rows);
-    auto *d_nrows = reinterpret_cast<uint32_t *>(d + o_nrows);
-    auto *d_counts = reinterpret_cast<uint32_t *>(d + o_counts);
-    uint8_t *d_strand = d + o_strand, *d_ws = ws_bytes ? d + o_ws : nullptr;
-    std::vector<uint64_t> offs(max_reads + 1);
-    for (size_t c = 0; c + 1 < starts.size(); ++c) {
-        const uint64_t r0 = starts[c], cnt = starts[c + 1] - r0, b0 = seq_offsets[r0], bytes = seq_offsets[r0 + cnt] - b0;
-        for (uint64_t i = 0; i <= cnt; ++i) offs[i] = seq_offsets[r0 + i] - b0;
-        if (bytes) STRAND_TRY(hipMemcpyAsync(d, seqs + b0, bytes, hipMemcpyHostToDevice, p->stream));
-        STRAND_TRY(hipMemcpyAsync(d_offs, offs.data(), (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
-        // rows beyond n_rows[i] are never written by the kernels: zero, as epik_amd_placer_place leaves them
-        STRAND_TRY(hipMemsetAsync(d_rows, 0, cnt * keep * sizeof(epik_amd_placement), p->stream));
-        STRAND_TRY(hipMemsetAsync(d_counts, 0, cnt * keep * sizeof(uint32_t), p->stream));
-        if (mode == EPIK_AMD_STRAND_BOTH) STRAND_TRY(hipMemsetAsync(d_ws, 0, layout_of(cnt, (uint32_t)keep, mode).per_read_bytes, p->stream));
-        const uint64_t chunk_ws = mode == EPIK_AMD_STRAND_FORWARD ? 0 : layout_of(cnt, (uint32_t)keep, mode).seqs + align_up(bytes + 1);
-        if (const int rc = place_strands_device_impl(p, d, d_offs, cnt, mode, d_ws, chunk_ws, d_rows, d_nrows, d_counts,
-                                                     d_strand, p->stream);
-            rc != EPIK_AMD_OK)
-            return rc;
-        STRAND_TRY(hipMemcpyAsync(rows + r0 * keep, d_rows, cnt * keep * sizeof(epik_amd_placement), hipMemcpyDeviceToHost, p->stream));
-        STRAND_TRY(hipMemcpyAsync(n_rows + r0, d_nrows, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
-        if (kmer_counts)
-            STRAND_TRY(hipMemcpyAsync(kmer_counts + r0 * keep, d_counts, cnt * keep * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
-        if (strand) STRAND_TRY(hipMemcpyAsync(strand + r0, d_strand, cnt, hipMemcpyDeviceToHost, p->stream));
-        STRAND_TRY(hipStreamSynchronize(p->stream));
-    }
-    return EPIK_AMD_OK;
+    if (const int rc = check_host_batch(seqs, seq_offsets, n, rows, n_rows, longest); rc != EPIK_AMD_OK) return rc;
+    return place_host_chunked(p, seqs, seq_offsets, n, mode, longest, kStrandHost, rows, n_rows, kmer_counts, strand);
 }
 
 }  // namespace

@@ -276,53 +276,65 @@ class Placer:
             self._handle, d_seqs, d_seq_offsets, int(n), d_rows, d_n_rows, d_kmer_counts or None,
             stream or None))
 
+    # -- strand and frame placement: the same bindings, around their own entry points and mode names --
     @staticmethod
-    def _strand_mode(mode) -> int:
+    def _mode(mode, names, what) -> int:
         if isinstance(mode, str):
-            if mode not in capi.STRANDS:
-                raise ValueError(f"unknown strand {mode!r}: expected one of {sorted(capi.STRANDS)}")
-            return capi.STRANDS[mode]
+            if mode not in names:
+                raise ValueError(f"unknown {what} {mode!r}: expected one of {sorted(names)}")
+            return names[mode]
         return int(mode)
 
-    def strand_workspace_bytes(self, n: int, seq_bytes: int, mode="both") -> int:
-        """Device workspace `place_strands_device` needs for n reads of seq_bytes characters
-        (`epik_amd_placer_strand_workspace_bytes`)."""
+    @staticmethod
+    def _strand_mode(mode) -> int:
+        return Placer._mode(mode, capi.STRANDS, "strand")
+
+    @staticmethod
+    def _frame_mode(mode) -> int:
+        return Placer._mode(mode, capi.FRAME_MODES, "translation")
+
+    def _workspace_bytes(self, fn, n: int, seq_bytes: int, mode: int) -> int:
         out = ctypes.c_uint64(0)
-        capi.check(self._lib.epik_amd_placer_strand_workspace_bytes(self._handle, int(n), int(seq_bytes),
-                                                                    self._strand_mode(mode), ctypes.byref(out)))
+        capi.check(fn(self._handle, int(n), int(seq_bytes), mode, ctypes.byref(out)))
         return int(out.value)
 
-    def place_strands(self, seqs: np.ndarray, seq_offsets: np.ndarray, mode="both"):
-        """`place_packed` on the strand(s) `mode` ("forward" / "reverse" / "both", or capi.STRAND_*) asks for
-        (`epik_amd_placer_place_strands`).  Returns (rows, n_rows, kmer_counts, strand[n] uint8: 0 = +, 1 = -)."""
+    def _place_labelled(self, fn, seqs: np.ndarray, seq_offsets: np.ndarray, mode: int):
+        """`place_packed` through a host entry point that also writes a byte per read (strand, frame)."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
         seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
         n = int(seq_offsets.shape[0] - 1)
         rows = np.zeros((n, self.keep_at_most), dtype=capi.PLACEMENT)
         n_rows = np.zeros(n, dtype=np.uint32)
         counts = np.zeros((n, self.keep_at_most), dtype=np.uint32)
-        strand = np.zeros(n, dtype=np.uint8)
-        capi.check(self._lib.epik_amd_placer_place_strands(
-            self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n, self._strand_mode(mode), rows.ctypes.data,
-            n_rows.ctypes.data, counts.ctypes.data, strand.ctypes.data))
-        return rows, n_rows, counts, strand
+        label = np.zeros(n, dtype=np.uint8)
+        capi.check(fn(self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n, mode, rows.ctypes.data,
+                      n_rows.ctypes.data, counts.ctypes.data, label.ctypes.data))
+        return rows, n_rows, counts, label
+
+    def _place_labelled_device(self, fn, d_seqs, d_seq_offsets, n, mode: int, d_workspace, workspace_bytes, d_rows,
+                               d_n_rows, d_kmer_counts, d_label, stream) -> None:
+        capi.check(fn(self._handle, d_seqs, d_seq_offsets, int(n), mode, d_workspace or None, int(workspace_bytes),
+                      d_rows, d_n_rows, d_kmer_counts or None, d_label or None, stream or None))
+
+    def strand_workspace_bytes(self, n: int, seq_bytes: int, mode="both") -> int:
+        """Device workspace `place_strands_device` needs for n reads of seq_bytes characters
+        (`epik_amd_placer_strand_workspace_bytes`)."""
+        return self._workspace_bytes(self._lib.epik_amd_placer_strand_workspace_bytes, n, seq_bytes,
+                                     self._strand_mode(mode))
+
+    def place_strands(self, seqs: np.ndarray, seq_offsets: np.ndarray, mode="both"):
+        """`place_packed` on the strand(s) `mode` ("forward" / "reverse" / "both", or capi.STRAND_*) asks for
+        (`epik_amd_placer_place_strands`).  Returns (rows, n_rows, kmer_counts, strand[n] uint8: 0 = +, 1 = -)."""
+        return self._place_labelled(self._lib.epik_amd_placer_place_strands, seqs, seq_offsets, self._strand_mode(mode))
 
     def place_strands_device(self, d_seqs: int, d_seq_offsets: int, n: int, mode, d_workspace: int, workspace_bytes: int,
                              d_rows: int, d_n_rows: int, d_kmer_counts: int = 0, d_strand: int = 0,
                              stream: int = 0) -> None:
         """`place_device` on the strand(s) `mode` asks for, asynchronous on `stream`; the caller's workspace of
         `strand_workspace_bytes(n, seq_bytes, mode)` (`epik_amd_placer_place_strands_device`)."""
-        capi.check(self._lib.epik_amd_placer_place_strands_device(
-            self._handle, d_seqs, d_seq_offsets, int(n), self._strand_mode(mode), d_workspace or None,
-            int(workspace_bytes), d_rows, d_n_rows, d_kmer_counts or None, d_strand or None, stream or None))
-
-    @staticmethod
-    def _frame_mode(mode) -> int:
-        if isinstance(mode, str):
-            if mode not in capi.FRAME_MODES:
-                raise ValueError(f"unknown translation {mode!r}: expected one of {sorted(capi.FRAME_MODES)}")
-            return capi.FRAME_MODES[mode]
-        return int(mode)
+        self._place_labelled_device(self._lib.epik_amd_placer_place_strands_device, d_seqs, d_seq_offsets, n,
+                                    self._strand_mode(mode), d_workspace, workspace_bytes, d_rows, d_n_rows,
+                                    d_kmer_counts, d_strand, stream)
 
     @staticmethod
     def codon_table() -> np.ndarray:
@@ -335,26 +347,14 @@ class Placer:
     def frame_workspace_bytes(self, n: int, seq_bytes: int, mode="both") -> int:
         """Device workspace `place_frames_device` needs for n nucleotide reads of seq_bytes characters
         (`epik_amd_placer_frame_workspace_bytes`)."""
-        out = ctypes.c_uint64(0)
-        capi.check(self._lib.epik_amd_placer_frame_workspace_bytes(self._handle, int(n), int(seq_bytes),
-                                                                   self._frame_mode(mode), ctypes.byref(out)))
-        return int(out.value)
+        return self._workspace_bytes(self._lib.epik_amd_placer_frame_workspace_bytes, n, seq_bytes,
+                                     self._frame_mode(mode))
 
     def place_frames(self, seqs: np.ndarray, seq_offsets: np.ndarray, mode="both"):
         """`place_packed` for nucleotide reads on this amino-acid database, through the frames `mode` ("forward" /
         "reverse" / "both", or capi.FRAMES_*) asks for; per read the best frame (`epik_amd_placer_place_frames`).
         Returns (rows, n_rows, kmer_counts, frame[n] uint8: 0..5 = +1 +2 +3 -1 -2 -3)."""
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
-        seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
-        n = int(seq_offsets.shape[0] - 1)
-        rows = np.zeros((n, self.keep_at_most), dtype=capi.PLACEMENT)
-        n_rows = np.zeros(n, dtype=np.uint32)
-        counts = np.zeros((n, self.keep_at_most), dtype=np.uint32)
-        frame = np.zeros(n, dtype=np.uint8)
-        capi.check(self._lib.epik_amd_placer_place_frames(
-            self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n, self._frame_mode(mode), rows.ctypes.data,
-            n_rows.ctypes.data, counts.ctypes.data, frame.ctypes.data))
-        return rows, n_rows, counts, frame
+        return self._place_labelled(self._lib.epik_amd_placer_place_frames, seqs, seq_offsets, self._frame_mode(mode))
 
     def place_frames_device(self, d_seqs: int, d_seq_offsets: int, n: int, mode, d_workspace: int,
                             workspace_bytes: int, d_rows: int, d_n_rows: int, d_kmer_counts: int = 0,
@@ -362,9 +362,9 @@ class Placer:
         """`place_frames` on device buffers, asynchronous on `stream`; the caller's workspace of
         `frame_workspace_bytes(n, seq_bytes, mode)` and count width (`choose_counts` with the longest frame,
         L // 3) (`epik_amd_placer_place_frames_device`)."""
-        capi.check(self._lib.epik_amd_placer_place_frames_device(
-            self._handle, d_seqs, d_seq_offsets, int(n), self._frame_mode(mode), d_workspace or None,
-            int(workspace_bytes), d_rows, d_n_rows, d_kmer_counts or None, d_frame or None, stream or None))
+        self._place_labelled_device(self._lib.epik_amd_placer_place_frames_device, d_seqs, d_seq_offsets, n,
+                                    self._frame_mode(mode), d_workspace, workspace_bytes, d_rows, d_n_rows,
+                                    d_kmer_counts, d_frame, stream)
 
     def accumulate_device(self, d_seqs: int, d_seq_offsets: int, n: int, d_scores: int, d_counts: int,
                           stream: int = 0, d_amb_slot: int = 0, d_amb_order: int = 0, d_amb_avg: int = 0) -> None:

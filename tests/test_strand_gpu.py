@@ -229,6 +229,53 @@ def test_host_entry_over_several_chunks(placer_cls, oracle_lib, small_case, monk
     assert_rows_match(*short, *(x[:50] for x in oracle_lib.Oracle.from_synth(db).place(*synth.pack_reads(reads[:50]))))
 
 
+@pytest.mark.parametrize("mode", ["forward", "reverse", "both"])
+def test_host_entry_zeroes_the_slots_past_n_rows(placer_cls, oracle_lib, small_case, monkeypatch, mode):
+    """Over several chunks, every row and count slot past n_rows[i] comes back zero: in `both`, also where the reverse
+    strand wins with fewer rows than the forward one (its rows come from the workspace the chunk before used)."""
+    _, db = small_case
+    rng = np.random.default_rng(9)
+    reads = mixed_reads(rng, 1500, db.kmer_size, max_len=150)
+    reads = [rc(r) if i % 3 == 0 else r for i, r in enumerate(reads)]
+    data, offs = synth.pack_reads(reads)
+    fwd, rev = oracle_strands(oracle_lib.Oracle.from_synth(db), data, offs)
+    want = {"forward": fwd, "reverse": rev, "both": both_rule(fwd, rev)[0]}[mode]
+    if mode == "both":
+        take = both_rule(fwd, rev)[1].astype(bool)
+        assert (take & (rev[1] < fwd[1])).any()
+    with placer_cls.from_synth(db) as pl:
+        keep = pl.keep_at_most
+        assert keep >= 7
+        monkeypatch.setenv("EPIK_AMD_STRAND_CHUNK_READS", "250")   # six chunks
+        rows, n, counts, _ = pl.place_strands(data, offs, mode)
+    assert_rows_match(rows, n, counts, *want)
+    past = np.arange(keep)[None, :] >= n[:, None]
+    assert past.any()
+    assert not np.frombuffer(rows[past].tobytes(), dtype=np.uint8).any() and not counts[past].any()
+
+
+@pytest.mark.parametrize("mode", ["forward", "reverse", "both"])
+@pytest.mark.parametrize("forced", ["2", "0"])
+def test_host_entry_widens_forced_counts_and_restores_them(placer_cls, oracle_lib, small_case, monkeypatch, forced,
+                                                           mode):
+    """test_parity_gpu's forced-width test for the strand host entry: a read with more k-mers than the forced width
+    holds is placed, not marked; the forced width is the handle's again afterwards (the device entry marks it)."""
+    import torch
+    _, db = small_case
+    monkeypatch.setenv("EPIK_AMD_WIDE_COUNTS", forced)   # 8-bit counts (255 k-mers) / 16-bit (32767)
+    rng = np.random.default_rng(22)
+    long_read = "".join(rng.choice(list("ACGT"), size=40_000 if forced == "0" else 700))
+    data, offs = synth.pack_reads(["ACGTACGTAC", long_read, "ACGTTGCA" * 4])
+    fwd, rev = oracle_strands(oracle_lib.Oracle.from_synth(db), data, offs)
+    want = {"forward": fwd, "reverse": rev, "both": both_rule(fwd, rev)[0]}[mode]
+    with placer_cls.from_synth(db) as pl:
+        got = pl.place_strands(data, offs, mode)
+        assert int(got[1].max()) <= pl.keep_at_most and capi.ROWS_COUNTS_TOO_NARROW not in got[1]
+        _, dev_n, _, _ = _device_run(pl, data, offs, mode, torch.cuda.Stream())
+    assert_rows_match(*got[:3], *want)
+    assert dev_n[1] == capi.ROWS_COUNTS_TOO_NARROW
+
+
 @pytest.mark.parametrize("keep_at_most,keep_factor", [(1, 0.01), (7, 0.01), (20, 0.01), (7, 0.3)])
 def test_keep_parameters(placer_cls, oracle_lib, small_case, keep_at_most, keep_factor):
     _, db = small_case

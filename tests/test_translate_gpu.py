@@ -211,6 +211,51 @@ def test_host_entry_over_several_chunks(placer_cls, oracle_lib, amino_small, mon
     assert all(a.tobytes() == b.tobytes() for a, b in zip(again, (rows, n, counts, frame)))
 
 
+@pytest.mark.parametrize("mode", MODES)
+def test_host_entry_zeroes_the_slots_past_n_rows(placer_cls, oracle_lib, amino_small, monkeypatch, mode):
+    """Over several chunks, every row and count slot past n_rows[i] comes back zero, also where the winning frame has
+    fewer rows than a losing one."""
+    _, db = amino_small
+    reads = _tricky_reads(np.random.default_rng(16), 1500)
+    data, offs = synth.pack_reads(reads)
+    orc = oracle_lib.Oracle.from_synth(db)
+    per_frame = orc.place(*synth.pack_reads([f for r in reads for f in frames(r, mode)]), num_threads=0)[1]
+    with placer_cls.from_synth(db) as pl:
+        keep = pl.keep_at_most
+        assert keep >= 7
+        want, _ = oracle_frames(orc, reads, mode, db.kmer_size, keep)
+        assert (has_rows(want[1]) & (want[1] < per_frame.reshape(len(reads), -1).max(axis=1))).any()
+        monkeypatch.setenv("EPIK_AMD_FRAME_CHUNK_READS", "333")   # five chunks
+        rows, n, counts, _ = pl.place_frames(data, offs, mode)
+    assert_rows_match(rows, n, counts, *want)
+    past = np.arange(keep)[None, :] >= n[:, None]
+    assert past.any()
+    assert not np.frombuffer(rows[past].tobytes(), dtype=np.uint8).any() and not counts[past].any()
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("forced", ["2", "0"])
+def test_host_entry_widens_forced_counts_and_restores_them(placer_cls, oracle_lib, amino_small, monkeypatch, forced,
+                                                           mode):
+    """test_parity_gpu's forced-width test for the frame host entry: a frame with more k-mers than the forced width
+    holds is placed, not marked; the forced width is the handle's again afterwards (the device entry marks it)."""
+    import torch
+    _, db = amino_small
+    monkeypatch.setenv("EPIK_AMD_WIDE_COUNTS", forced)   # 8-bit counts (255 k-mers) / 16-bit (32767)
+    rng = np.random.default_rng(23)
+    long_read = "".join(rng.choice(list("ACGT"), size=100_000 if forced == "0" else 900))
+    reads = ["ACGTACGTACGTACGT", long_read, "ATGGCTAAACGTGATGAACTTCAGGGTCCG"]
+    data, offs = synth.pack_reads(reads)
+    with placer_cls.from_synth(db) as pl:
+        want, want_frame = oracle_frames(oracle_lib.Oracle.from_synth(db), reads, mode, db.kmer_size, pl.keep_at_most)
+        got = pl.place_frames(data, offs, mode)
+        assert int(got[1].max()) <= pl.keep_at_most and capi.ROWS_COUNTS_TOO_NARROW not in got[1]
+        _, dev_n, _, _ = _device_run(pl, data, offs, mode, torch.cuda.Stream())
+    assert_rows_match(*got[:3], *want)
+    assert np.array_equal(got[3], want_frame)
+    assert dev_n[1] == capi.ROWS_COUNTS_TOO_NARROW
+
+
 def test_nucleotide_handle_is_refused(placer_cls, small_case):
     _, db = small_case
     data, offs = synth.pack_reads(["ACGTACGTACGT"])
