@@ -8,8 +8,9 @@ command taking -i/--database, -s/--states {nucl,amino}, --omega (1.5), --mu (1.0
 amino -- translates the options into that driver's flags (-d -q -j --omega --mu -o
 [--max-ram]) and runs it.  New options: --gpus, the number of MI355X devices the reads are
 sharded across; --db-shard; --strand, which strand of each nucleotide read is placed
-(forward as given, its reverse complement, or both and the better one per read); and --translate, with
--s amino: nucleotide reads translated into their frames, per read the best frame.
+(forward as given, its reverse complement, or both and the better one per read); --translate, with
+-s amino: nucleotide reads translated into their frames, per read the best frame; and --profile / --profile-only,
+the sample's abundance profile per branch beside the jplace or instead of it.
 """
 from __future__ import annotations
 
@@ -50,6 +51,10 @@ PLACE_OPTIONS = [
                             help="With -s amino: the reads are nucleotide reads; place their frames +1 +2 +3 (forward), "
                                  "-1 -2 -3 (reverse) or all six (both), the best frame per read (then also "
                                  "frames_<input>.tsv, one name<TAB>+1..-3 per read).")),
+    (("--profile",), dict(is_flag=True, help="Also write profile_<input>.tsv: per branch the summed like-weight ratios "
+                                             "and the reads placed best on it, with clade sums.")),
+    (("--profile-only",), dict(is_flag=True, help="Write profile_<input>.tsv and no jplace: the placements are summed on "
+                                                  "the device(s) and never leave them (not with --db-shard > 1).")),
 ]
 
 
@@ -64,7 +69,7 @@ def driver_path(states: str) -> str:
 
 
 def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpus, input_file, db_shard=1,
-                   strand="forward", translate=None):
+                   strand="forward", translate=None, profile=False, profile_only=False):
     argv = [driver_path(states), "-d", str(database), "-q", str(input_file), "-j", str(threads),
             "--omega", str(omega), "--mu", str(mu), "-o", str(outputdir)]
     if max_ram:
@@ -77,6 +82,10 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--strand", str(strand)]
     if translate is not None:
         argv += ["--translate", str(translate)]
+    if profile:
+        argv += ["--profile"]
+    if profile_only:
+        argv += ["--profile-only"]
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 

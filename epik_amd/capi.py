@@ -60,6 +60,15 @@ EXPORTS = (
     "epik_amd_placer_frame_workspace_bytes",
     "epik_amd_placer_place_frames_device",
     "epik_amd_placer_place_frames",
+    "epik_amd_profile_create",
+    "epik_amd_profile_destroy",
+    "epik_amd_profile_reset",
+    "epik_amd_profile_read",
+    "epik_amd_profile_info",
+    "epik_amd_profile_add_device",
+    "epik_amd_placer_profile_reads",
+    "epik_amd_placer_profile_strands",
+    "epik_amd_placer_profile_frames",
 )
 
 
@@ -127,6 +136,15 @@ class PartialInfo(ctypes.Structure):
     ]
 
 
+class ProfileTotals(ctypes.Structure):
+    """`epik_amd_profile_totals`."""
+
+    _fields_ = [("placed", ctypes.c_uint64), ("no_hit", ctypes.c_uint64), ("too_short", ctypes.c_uint64),
+                ("too_narrow", ctypes.c_uint64), ("bad_rows", ctypes.c_uint64)]
+
+
+#: fixed point of the like-weight ratios a profile sums (EPIK_AMD_PROFILE_LWR_BITS)
+PROFILE_LWR_BITS = 30
 MAX_SHARDS = 16
 #: count of a partial list that found no room in d_entries
 LIST_OVERFLOW = 0xFFFFFFFF
@@ -271,6 +289,24 @@ def load() -> ctypes.CDLL:
         for name in names:
             getattr(lib, name).restype = i32
             getattr(lib, name).argtypes = argtypes
+    # (the abundance profile)
+    lib.epik_amd_profile_create.restype = i32
+    lib.epik_amd_profile_create.argtypes = [vp, ctypes.POINTER(vp)]
+    lib.epik_amd_profile_destroy.restype = None
+    lib.epik_amd_profile_destroy.argtypes = [vp]
+    lib.epik_amd_profile_reset.restype = i32
+    lib.epik_amd_profile_reset.argtypes = [vp]
+    lib.epik_amd_profile_read.restype = i32
+    lib.epik_amd_profile_read.argtypes = [vp, vp, vp, ctypes.POINTER(ProfileTotals)]
+    lib.epik_amd_profile_info.restype = i32
+    lib.epik_amd_profile_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+    lib.epik_amd_profile_add_device.restype = i32
+    lib.epik_amd_profile_add_device.argtypes = [vp, vp, vp, vp, vp, u64, vp]
+    lib.epik_amd_placer_profile_reads.restype = i32
+    lib.epik_amd_placer_profile_reads.argtypes = [vp, vp, vp, vp, vp, u64]
+    for name in ("epik_amd_placer_profile_strands", "epik_amd_placer_profile_frames"):
+        getattr(lib, name).restype = i32
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, u64, ctypes.c_uint32, vp]
     _lib = lib
     return lib
 

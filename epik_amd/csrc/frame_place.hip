@@ -418,6 +418,18 @@ int place_frames_impl(epik_amd_placer *p, const char *seqs, const uint64_t *seq_
     return place_host_chunked(p, seqs, seq_offsets, n, mode, longest / 3, kFrameHost, rows, n_rows, kmer_counts, frame);
 }
 
+// the same placement with the rows left on the device and summed into a profile there (profile_place.hip)
+int profile_frames_impl(epik_amd_placer *p, epik_amd_profile *profile, const char *seqs, const uint64_t *seq_offsets,
+                        const uint32_t *weights, uint64_t n, uint32_t mode, uint8_t *frame)
+{
+    if (const int rc = check_handle(p, mode); rc != EPIK_AMD_OK) return rc;
+    if (!profile) return fail_with(EPIK_AMD_ERR_INVALID, "null profile");
+    if (n == 0) return EPIK_AMD_OK;
+    uint64_t longest = 0;
+    if (const int rc = check_host_reads(seqs, seq_offsets, n, longest); rc != EPIK_AMD_OK) return rc;
+    return profile_host_chunked(p, profile, seqs, seq_offsets, weights, n, mode, longest / 3, kFrameHost, frame);
+}
+
 }  // namespace
 
 extern "C" {
@@ -458,6 +470,17 @@ int epik_amd_placer_place_frames(epik_amd_placer *p, const char *seqs, const uin
         return place_frames_impl(p, seqs, seq_offsets, n, mode, rows, n_rows, kmer_counts, frame);
     } catch (const std::exception &e) {
         return fail_with(EPIK_AMD_ERR_INVALID, std::string("place_frames: ") + e.what());
+    }
+}
+
+int epik_amd_placer_profile_frames(epik_amd_placer *p, epik_amd_profile *profile, const char *seqs,
+                                   const uint64_t *seq_offsets, const uint32_t *weights, uint64_t n, uint32_t mode,
+                                   uint8_t *frame)
+{
+    try {
+        return profile_frames_impl(p, profile, seqs, seq_offsets, weights, n, mode, frame);
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("profile_frames: ") + e.what());
     }
 }
 

@@ -1,6 +1,7 @@
 // host_entry.hpp -- the host side shared by the placements around epik_amd_placer_place_device: the synchronous
-// host-buffer entry points of strand_place.hip and frame_place.hip are place_host_chunked over a HostVariant each;
-// shard_place.hip takes the HIP-error macro and the batch check.  Internal to libepik_amd.
+// host-buffer entry points of strand_place.hip and frame_place.hip are place_host_chunked over a HostVariant each, and
+// their profile-only twins (profile_place.hip: profile_host_chunked) the same with a sink per chunk and nothing copied
+// out; shard_place.hip takes the HIP-error macro and the batch check.  Internal to libepik_amd.
 #ifndef EPIK_AMD_HOST_ENTRY_HPP
 #define EPIK_AMD_HOST_ENTRY_HPP
 #include <hip/hip_runtime.h>
@@ -35,10 +36,17 @@ inline uint32_t grid_for(uint64_t units, uint64_t max_blocks)
 
 // The checks epik_amd_placer_place makes of a host batch of n >= 1 reads, in its order and words; `longest` gets the
 // batch's longest read.
+inline int check_host_reads(const char *seqs, const uint64_t *seq_offsets, uint64_t n, uint64_t &longest);
 inline int check_host_batch(const char *seqs, const uint64_t *seq_offsets, uint64_t n, const void *rows,
                             const void *n_rows, uint64_t &longest)
 {
     if (!seqs || !seq_offsets || !rows || !n_rows) return fail_with(EPIK_AMD_ERR_INVALID, "null host buffer");
+    return check_host_reads(seqs, seq_offsets, n, longest);
+}
+// ... the part of it that looks at the reads alone (an entry point that takes no rows back)
+inline int check_host_reads(const char *seqs, const uint64_t *seq_offsets, uint64_t n, uint64_t &longest)
+{
+    if (!seqs || !seq_offsets) return fail_with(EPIK_AMD_ERR_INVALID, "null host buffer");
     if (seq_offsets[0] != 0) return fail_with(EPIK_AMD_ERR_INVALID, "seq_offsets[0] must be 0");
     longest = 0;
     for (uint64_t i = 0; i < n; ++i) {
@@ -88,13 +96,23 @@ struct HostVariant {
                         void *d_label, hipStream_t stream);
 };
 
+// What may look at every chunk of place_host_chunked while it is on the device: called once the chunk is placed,
+// with its device rows, row counts and k-mer counts, the index of its first read in the batch and its number of reads;
+// whatever it enqueues goes on `stream`, the handle's, ahead of the copies out.
+struct ChunkSink {
+    int (*fn)(void *ctx, const epik_amd_placement *d_rows, const uint32_t *d_n_rows, const uint32_t *d_kmer_counts,
+              uint64_t first, uint64_t count, hipStream_t stream);
+    void *ctx;
+};
+
 // The synchronous host-buffer entry point of a variant, once the caller has checked the handle, the mode and the
 // batch (n >= 1, check_host_batch): the count width for `longest_placed`, the longest sequence the device entry
 // places; then the batch in chunks through one device allocation, each copied in, placed on the handle's stream,
-// copied out and waited for.
+// copied out and waited for.  rows, n_rows and kmer_counts may be NULL, each by itself: that part stays on the device
+// (with a sink and all three NULL nothing but the label bytes crosses back).
 inline int place_host_chunked(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
                               uint32_t mode, uint64_t longest_placed, const HostVariant &v, epik_amd_placement *rows,
-                              uint32_t *n_rows, uint32_t *kmer_counts, uint8_t *label)
+                              uint32_t *n_rows, uint32_t *kmer_counts, uint8_t *label, const ChunkSink *sink = nullptr)
 {
     HIP_TRY(hipSetDevice(p->device));
     const CountWidthGuard width(p, longest_placed);
@@ -153,8 +171,10 @@ inline int place_host_chunked(epik_amd_placer *p, const char *seqs, const uint64
         if (const int rc = v.place_device(p, d, d_offs, cnt, mode, d_ws, chunk_ws, d_rows, d_nrows, d_counts, d_label, p->stream);
             rc != EPIK_AMD_OK)
             return rc;
-        HIP_TRY(hipMemcpyAsync(rows + r0 * keep, d_rows, cnt * keep * sizeof(epik_amd_placement), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipMemcpyAsync(n_rows + r0, d_nrows, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+        if (sink)
+            if (const int rc = sink->fn(sink->ctx, d_rows, d_nrows, d_counts, r0, cnt, p->stream); rc != EPIK_AMD_OK) return rc;
+        if (rows) HIP_TRY(hipMemcpyAsync(rows + r0 * keep, d_rows, cnt * keep * sizeof(epik_amd_placement), hipMemcpyDeviceToHost, p->stream));
+        if (n_rows) HIP_TRY(hipMemcpyAsync(n_rows + r0, d_nrows, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
         if (kmer_counts)
             HIP_TRY(hipMemcpyAsync(kmer_counts + r0 * keep, d_counts, cnt * keep * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
         if (label) HIP_TRY(hipMemcpyAsync(label + r0, d_label, cnt, hipMemcpyDeviceToHost, p->stream));
@@ -162,6 +182,13 @@ inline int place_host_chunked(epik_amd_placer *p, const char *seqs, const uint64
     }
     return EPIK_AMD_OK;
 }
+
+// The profile-only host entry of a variant (profile_place.hip), once the caller has checked the handle, the mode and
+// the reads (n >= 1, check_host_reads): place_host_chunked with every chunk's rows added to `profile` on the device,
+// read i with weights[i] (NULL: 1), and nothing copied out but the label bytes (NULL: not even those).
+int profile_host_chunked(epik_amd_placer *p, epik_amd_profile *profile, const char *seqs, const uint64_t *seq_offsets,
+                         const uint32_t *weights, uint64_t n, uint32_t mode, uint64_t longest_placed, const HostVariant &v,
+                         uint8_t *label);
 
 }  // namespace epik_amd
 #endif

@@ -243,6 +243,18 @@ int place_strands_impl(epik_amd_placer *p, const char *seqs, const uint64_t *seq
     return place_host_chunked(p, seqs, seq_offsets, n, mode, longest, kStrandHost, rows, n_rows, kmer_counts, strand);
 }
 
+// the same placement with the rows left on the device and summed into a profile there (profile_place.hip)
+int profile_strands_impl(epik_amd_placer *p, epik_amd_profile *profile, const char *seqs, const uint64_t *seq_offsets,
+                         const uint32_t *weights, uint64_t n, uint32_t mode, uint8_t *strand)
+{
+    if (const int rc = check_handle(p, mode); rc != EPIK_AMD_OK) return rc;
+    if (!profile) return fail_with(EPIK_AMD_ERR_INVALID, "null profile");
+    if (n == 0) return EPIK_AMD_OK;
+    uint64_t longest = 0;
+    if (const int rc = check_host_reads(seqs, seq_offsets, n, longest); rc != EPIK_AMD_OK) return rc;
+    return profile_host_chunked(p, profile, seqs, seq_offsets, weights, n, mode, longest, kStrandHost, strand);
+}
+
 }  // namespace
 
 extern "C" {
@@ -275,6 +287,17 @@ int epik_amd_placer_place_strands(epik_amd_placer *p, const char *seqs, const ui
         return place_strands_impl(p, seqs, seq_offsets, n, mode, rows, n_rows, kmer_counts, strand);
     } catch (const std::exception &e) {
         return fail_with(EPIK_AMD_ERR_INVALID, std::string("place_strands: ") + e.what());
+    }
+}
+
+int epik_amd_placer_profile_strands(epik_amd_placer *p, epik_amd_profile *profile, const char *seqs,
+                                    const uint64_t *seq_offsets, const uint32_t *weights, uint64_t n, uint32_t mode,
+                                    uint8_t *strand)
+{
+    try {
+        return profile_strands_impl(p, profile, seqs, seq_offsets, weights, n, mode, strand);
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("profile_strands: ") + e.what());
     }
 }
 

@@ -8,7 +8,9 @@
 // (main.cpp:34-37) and the same final report lines (main.cpp:368-382).  Not reproduced:
 // the progress bar and colours (indicators/termcolor).  Added: --gpus N | --devices a,b,c (the database on
 // every device, batches shared out) and --db-shard G (the database cut in G by k-mer code, shard g on device g:
-// every batch is placed by all of them together -- a database larger than one device's memory).
+// every batch is placed by all of them together -- a database larger than one device's memory); --profile /
+// --profile-only (the sample's abundance profile, profile.hpp: beside the jplace, or instead of it and summed on the
+// devices).
 // The two binaries differ as the reference's do (epik/CMakeLists.txt:72,124): epik-dna
 // accepts DNA databases, epik-aa protein ones.
 #include <algorithm>
@@ -26,6 +28,7 @@
 #include <iostream>
 #include <limits>
 #include <map>
+#include <memory>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -35,6 +38,7 @@
 #include "phylo_kmer_db.hpp"
 #include "phylo_tree.hpp"
 #include "placer.hpp"
+#include "profile.hpp"
 #include "report.hpp"
 #include "seq_record.hpp"
 
@@ -181,6 +185,10 @@ const char* kHelp =
     "      --strand arg        forward | reverse (reverse complement) | both (the better per read) (default: forward)\n"
     "      --translate arg     Nucleotide reads on this amino-acid database: forward (frames +1 +2 +3) | reverse\n"
     "                          (-1 -2 -3) | both (all six); the best frame per read (epik-aa; default: off)\n"
+    "      --profile           Also write profile_<query>.tsv: per branch the summed like-weight ratios and the reads\n"
+    "                          placed best on it, with clade sums; reads without any hit are counted, not spread\n"
+    "      --profile-only      Write that profile and no jplace: the rows are summed on the device(s) and never\n"
+    "                          leave them (not with --db-shard > 1)\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -221,7 +229,7 @@ options parse_args(int argc, char** argv)
         } else {
             continue;  // positional arguments are ignored (epik.py passes the query twice, epik.py:88,96)
         }
-        if (name == "help") {
+        if (name == "help" || ((name == "profile" || name == "profile-only") && !have_value)) {  // flags
             opt.values[name] = "1";
             continue;
         }
@@ -282,6 +290,11 @@ int main(int argc, char** argv)
             if (std::stoul(parsed.get("db-shard", "1")) > 1)
                 throw std::runtime_error("--translate " + name + " does not work with --db-shard > 1");
         }
+        // --profile / --profile-only: checked before anything is opened or any device touched
+        const bool profile_only = parsed.has("profile-only"), with_profile = parsed.has("profile") || profile_only;
+        if (profile_only && std::stoul(parsed.get("db-shard", "1")) > 1)
+            throw std::runtime_error("--profile-only does not work with --db-shard > 1 (use --profile: the rows of a sharded "
+                                     "placement are finished on several devices)");
         const auto db_file = parsed.require("database");
         const auto query_file = parsed.require("query");
         const auto num_threads = (size_t)std::stoul(parsed.get("jobs", "1"));
@@ -354,14 +367,22 @@ int main(int argc, char** argv)
         epik_amd::placer placer(db, tree, keep_at_most, keep_factor, num_threads, devices, db_shards, load_shard);
         placer.set_strand(strand);
         if (translate) placer.set_translate(frames);
+        if (profile_only) placer.set_profile_only();
         db.drop_lists();  // the lists are on the devices now; tree, k and omega stay for the output
         const auto tree_as_newick = epik_amd::io::to_newick(tree, true);
         const auto jplace_filename = make_output_filename(query_file, output_dir);
         const auto invocation = make_invocation(argc, argv);
 
-        epik_amd::io::jplace_writer jplace(jplace_filename, invocation, tree_as_newick);
-        jplace.set_branch_lengths(placer.distal_lengths(), placer.pendant_lengths());
-        jplace.start();
+        // --profile-only: no jplace at all
+        std::unique_ptr<epik_amd::io::jplace_writer> jplace;
+        if (!profile_only) {
+            jplace.reset(new epik_amd::io::jplace_writer(jplace_filename, invocation, tree_as_newick));
+            jplace->set_branch_lengths(placer.distal_lengths(), placer.pendant_lengths());
+            jplace->start();
+        }
+        // --profile: summed by the writer thread from the rows it writes; --profile-only: read from the devices at the end
+        epik_amd::sample_profile profile(with_profile ? tree.get_node_count() : 0);
+        const auto profile_filename = epik_amd::make_profile_filename(query_file, output_dir);
         // --strand reverse|both: one "name<TAB>+|-" line per input record, input order
         std::ofstream strands_out;
         if (strand != epik_amd::strand_mode::forward) {
@@ -436,7 +457,9 @@ int main(int argc, char** argv)
                     for (const auto& item : ready) group.push_back(&item.placed);
                     if (group.empty()) continue;
                     write_clock.start();
-                    jplace.write(group, num_threads);
+                    if (jplace) jplace->write(group, num_threads);
+                    if (with_profile && !profile_only)
+                        for (const auto* placed : group) profile.add(*placed);
                     if (strands_out.is_open()) {
                         for (const auto& item : ready)
                             for (size_t i = 0; i < item.batch.size(); ++i)
@@ -511,12 +534,19 @@ int main(int argc, char** argv)
         if (std::getenv("EPIK_AMD_STAGE_TIMES"))
             std::cout << "stage read " << read_clock.ms() << " ms\nstage place " << place_ms
                       << " ms\nstage write " << write_clock.ms() << " ms" << std::endl;
-        jplace.end();
+        if (jplace) jplace->end();
+        if (profile_only) placer.read_profiles(profile.mass.data(), profile.best.data(), profile.totals);
+        if (with_profile) {
+            std::vector<size_t> subtree_num_nodes;
+            for (const auto& entry : db.tree_index()) subtree_num_nodes.push_back(entry.subtree_num_nodes);
+            epik_amd::write_profile_tsv(profile_filename, profile, subtree_num_nodes);
+        }
         if (num_iterations) average_speed /= (double)num_iterations;
         std::cout << std::endl
                   << "Placed " << num_seq_placed << " sequences.\nAverage speed: " << epik_amd::human_count(average_speed, false)
                   << " seq/s.\n";
-        std::cout << "Output: " << jplace_filename << std::endl;
+        if (jplace) std::cout << "Output: " << jplace_filename << std::endl;
+        if (with_profile) std::cout << "Profile: " << profile_filename << std::endl;
         if (strands_out.is_open()) {
             strands_out.close();
             if (!strands_out) throw std::runtime_error("Could not write " + make_strands_filename(query_file, output_dir));

@@ -12,6 +12,12 @@
 // strand only: its strand and frame entries are weak references here, and a library without it is an error when asked for.
 #pragma weak epik_amd_placer_place_strands
 #pragma weak epik_amd_placer_place_frames
+#pragma weak epik_amd_profile_create
+#pragma weak epik_amd_profile_destroy
+#pragma weak epik_amd_profile_read
+#pragma weak epik_amd_placer_profile_reads
+#pragma weak epik_amd_placer_profile_strands
+#pragma weak epik_amd_placer_profile_frames
 
 namespace epik_amd {
 
@@ -132,8 +138,44 @@ void placer::set_translate(translate_mode mode)
     _frames = mode;
 }
 
+void placer::set_profile_only()
+{
+    if (_sharded) throw std::runtime_error("GPU placer: --profile-only does not work with --db-shard > 1");
+    if (!&epik_amd_profile_create || !&epik_amd_profile_destroy || !&epik_amd_profile_read || !&epik_amd_placer_profile_reads ||
+        !&epik_amd_placer_profile_strands || !&epik_amd_placer_profile_frames)
+        throw std::runtime_error("GPU placer: this libepik_amd has no device profile");
+    if (!_profiles.empty()) return;
+    for (auto* h : _handles) {
+        epik_amd_profile* profile = nullptr;
+        if (epik_amd_profile_create(h, &profile) != EPIK_AMD_OK) {
+            const std::string message = epik_amd_last_error();
+            for (auto* made : _profiles) epik_amd_profile_destroy(made);
+            _profiles.clear();
+            throw std::runtime_error("GPU placer: " + message);
+        }
+        _profiles.push_back(profile);
+    }
+}
+
+void placer::read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_totals& totals) const
+{
+    const size_t n = _original_tree.get_node_count();
+    std::vector<uint64_t> m(n), b(n);
+    std::fill(mass, mass + n, 0), std::fill(best, best + n, 0);
+    totals = {};
+    for (auto* profile : _profiles) {
+        epik_amd_profile_totals t{};
+        if (epik_amd_profile_read(profile, m.data(), b.data(), &t) != EPIK_AMD_OK)
+            throw std::runtime_error(std::string("GPU placer: ") + epik_amd_last_error());
+        for (size_t i = 0; i < n; ++i) mass[i] += m[i], best[i] += b[i];
+        totals.placed += t.placed, totals.no_hit += t.no_hit, totals.too_short += t.too_short;
+        totals.too_narrow += t.too_narrow, totals.bad_rows += t.bad_rows;
+    }
+}
+
 placer::~placer() noexcept
 {
+    for (auto* profile : _profiles) epik_amd_profile_destroy(profile);
     for (auto* h : _handles) epik_amd_placer_destroy(h);
 }
 
@@ -240,6 +282,32 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
             at += seq.size();
         }
     });
+    if (profile_only()) {
+        // the rows stay on the device and are summed there; what comes back is the strand / frame byte per sequence
+        std::unique_ptr<uint32_t[]> weights(new uint32_t[n]);
+        for (size_t b = 0; b < batches.size(); ++b)
+            for (size_t u = 0; u < out[b].size(); ++u)
+                weights[first_unique[b] + u] = out[b].name_begin[u + 1] - out[b].name_begin[u];
+        std::unique_ptr<uint8_t[]> labels;
+        if (_translate || _strand != strand_mode::forward) labels.reset(new uint8_t[n]);
+        auto* handle = _handles[device_index];
+        auto* profile = _profiles[device_index];
+        const int rc = _translate ? epik_amd_placer_profile_frames(handle, profile, bytes.get(), offsets.get(), weights.get(), n,
+                                                                   (uint32_t)_frames, labels.get())
+                       : _strand != strand_mode::forward
+                           ? epik_amd_placer_profile_strands(handle, profile, bytes.get(), offsets.get(), weights.get(), n,
+                                                             (uint32_t)_strand, labels.get())
+                           : epik_amd_placer_profile_reads(handle, profile, bytes.get(), offsets.get(), weights.get(), n);
+        if (rc != EPIK_AMD_OK) throw std::runtime_error(std::string("GPU placer: ") + epik_amd_last_error());
+        for (size_t b = 0; b < batches.size(); ++b) {
+            auto& pb = out[b];
+            pb.row_begin.assign(pb.size() + 1, 0);
+            if (!labels) continue;
+            const uint8_t* first = labels.get() + first_unique[b];
+            (_translate ? pb.frames : pb.strands).assign(first, first + pb.size());
+        }
+        return out;
+    }
     std::unique_ptr<epik_amd_placement[]> rows(new epik_amd_placement[n * _keep_at_most]);
     std::unique_ptr<uint32_t[]> n_rows(new uint32_t[n]), counts(new uint32_t[n * _keep_at_most]);
     std::unique_ptr<uint8_t[]> strands;  // (reverse / both only: forward goes through epik_amd_placer_place as ever)

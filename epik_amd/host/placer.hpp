@@ -127,6 +127,14 @@ public:
     /// the placed batches say per sequence which frame won.  Amino-acid databases, replicated (not --db-shard) only.
     void set_translate(translate_mode mode);
     bool translating() const noexcept { return _translate; }
+    /// --profile-only: one device profile per handle (epik_amd_profile); from then on place_flat leaves the rows on the
+    /// device, adds them to the profile of its device there -- every unique sequence with the number of its records as
+    /// weight -- and returns batches without rows (sequences, names and the strand / frame bytes as ever).
+    /// Replicated databases only (not --db-shard).
+    void set_profile_only();
+    bool profile_only() const noexcept { return !_profiles.empty(); }
+    /// The profiles of all devices read back and summed; `mass` and `best` of num_branches cells each.
+    void read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_totals& totals) const;
     /// distal_length / pendant_length of a placement on branch b (place.cpp:110-123, 435-437)
     std::vector<double> distal_lengths() const;
     const std::vector<double>& pendant_lengths() const noexcept { return _pendant_lengths; }
@@ -140,6 +148,7 @@ private:
     const double _keep_factor;
     std::vector<double> _pendant_lengths;
     std::vector<epik_amd_placer*> _handles;  // one per device (replicated) or per shard (sharded)
+    std::vector<epik_amd_profile*> _profiles;  // set_profile_only(): one per handle
     bool _sharded = false;
     strand_mode _strand = strand_mode::forward;
     bool _translate = false;

@@ -336,6 +336,38 @@ class Placer:
                                     self._strand_mode(mode), d_workspace, workspace_bytes, d_rows, d_n_rows,
                                     d_kmer_counts, d_strand, stream)
 
+    # -- the abundance profile (epik_amd/profile.py) ----------------------------------------------
+    def profile(self):
+        """A new, empty device profile for this placer (`epik_amd_profile_create`)."""
+        from .profile import Profile
+        return Profile(self)
+
+    def profile_packed(self, profile, seqs: np.ndarray, seq_offsets: np.ndarray, weights=None, strand=None, translate=None):
+        """`place_packed` / `place_strands` / `place_frames` with the rows left on the device and added to `profile`
+        there, read i with weights[i] (None: 1): `epik_amd_placer_profile_reads` / `_strands` / `_frames`.  Returns the
+        strand or frame byte per read (None without `strand` and `translate`)."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+        n = int(seq_offsets.shape[0] - 1)
+        if strand is not None and translate is not None:
+            raise ValueError("strand and translate do not combine: translate=both already covers both strands")
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint32)
+        if w is not None and w.shape != (n,):
+            raise ValueError(f"weights must hold one value per read ({n}), not {w.shape}")
+        w_ptr = None if w is None else w.ctypes.data
+        if strand is None and translate is None:
+            capi.check(self._lib.epik_amd_placer_profile_reads(self._handle, profile._handle, seqs.ctypes.data,
+                                                               seq_offsets.ctypes.data, w_ptr, n))
+            return None
+        label = np.zeros(n, dtype=np.uint8)
+        if translate is not None:
+            fn, mode = self._lib.epik_amd_placer_profile_frames, self._frame_mode(translate)
+        else:
+            fn, mode = self._lib.epik_amd_placer_profile_strands, self._strand_mode(strand)
+        capi.check(fn(self._handle, profile._handle, seqs.ctypes.data, seq_offsets.ctypes.data, w_ptr, n, mode,
+                      label.ctypes.data))
+        return label
+
     @staticmethod
     def codon_table() -> np.ndarray:
         """The library's codon -> residue table: uint8[4096] indexed by the three nucleotide class masks, 4 bits each,
@@ -477,14 +509,16 @@ class Placer:
 
     # -- epik::placer::place ---------------------------------------------------------
     def place(self, seq_records: Iterable[Tuple[str, str]], num_threads: int = 1,
-              strand: str = "forward", translate=None) -> PlacedCollection:
+              strand: str = "forward", translate=None, profile=None) -> PlacedCollection:
         """`seq_records` = (header, sequence) pairs (i2l::seq_record).  `num_threads`
         is accepted for signature parity and ignored, as the parallelism is the GPU's.
         `strand`: "forward" (the reference's contract: each read as given), "reverse" (its reverse
         complement) or "both" (per read the better of the two; PlacedSequence.strand says which).
         `translate` (amino-acid databases): None places the reads as given; "forward" / "reverse" / "both" takes
         them as nucleotide reads and places their frames +1 +2 +3 / -1 -2 -3 / all six, per read the best one
-        (PlacedSequence.frame says which).  Duplicates are merged on the nucleotide string."""
+        (PlacedSequence.frame says which).  Duplicates are merged on the nucleotide string.
+        `profile` (a `Profile` of this placer): the placements are also added to it, every unique sequence with the
+        number of its records as weight."""
         del num_threads
         mode = self._strand_mode(strand)
         frame_mode = None if translate is None else self._frame_mode(translate)
@@ -506,6 +540,8 @@ class Placer:
             rows, n_rows, counts = self.place_packed(data, offsets)
         else:
             rows, n_rows, counts, strands = self.place_strands(data, offsets, mode)
+        if profile is not None:
+            profile.add_host(rows, n_rows, counts, [len(sequence_map[s]) for s in unique])
         if len(n_rows) and int(n_rows.max()) > self.keep_at_most:
             # (never from place_packed, which widens the counts by itself: a row count, not the
             # EPIK_AMD_ROWS_COUNTS_TOO_NARROW mark of the device entry points)

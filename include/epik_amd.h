@@ -423,6 +423,68 @@ int epik_amd_placer_place_frames(epik_amd_placer *p, const char *seqs, const uin
                                  uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows,
                                  uint32_t *kmer_counts, uint8_t *frame);
 
+/*
+ * The abundance profile of a sample, summed on the device from the rows a placement wrote.  No reference counterpart:
+ * the reference writes every read into a jplace (main.cpp:355-361) and leaves the sums to a second tool.
+ *
+ * Per branch, mass = the summed like-weight ratios of the rows on it, in fixed point, and best = the reads whose first
+ * row is on it; per sample, how many reads were placed, had no hit, were too short.  One rule:
+ *   q(x) = llrint(x * 2^EPIK_AMD_PROFILE_LWR_BITS), round half to even, for a double x in [0, 1].
+ *   Read i with weight w (uint32; 1 without weights; 0 adds nothing), keep = keep_at_most, tested in this order:
+ *     n_rows[i] == EPIK_AMD_ROWS_COUNTS_TOO_NARROW   totals.too_narrow += w
+ *     n_rows[i] == 0                                 totals.too_short  += w
+ *     kmer_counts[i * keep] == 0                     totals.no_hit     += w
+ *     otherwise                                      totals.placed     += w;  best[rows[i * keep].branch] += w;
+ *                                                    mass[rows[i * keep + j].branch] += w * q(rows[i * keep + j].lwr), j < n_rows[i]
+ *   The third line is the read none of whose k-mers is in the database: place.cpp:141-152 gives it keep_at_most
+ *   fabricated rows on branches 0, 1, 2, ... with LWR 1 / num_branches each, which a jplace cannot tell from
+ *   placements; their k-mer counts are 0.  A row of a placed read whose branch is >= num_branches (never from this
+ *   library) writes nothing and adds 1 to totals.bad_rows.  LWRs are taken as reported (after the keep_factor filter,
+ *   not renormalised).  Every accumulator is a uint64 and wraps modulo 2^64 (2^34 weighted reads on one branch).
+ * Integer adds commute: the result is the same bits whatever the batch size, the chunks, the grid, the number of
+ * profiles summed afterwards or the order of the calls.
+ *
+ * An epik_amd_profile is an object of its own, created for a placer's device, num_branches and keep_at_most (the
+ * placer may be destroyed before it); all zero at create() and after reset().
+ *   add_device  asynchronous on `stream` (a hipStream_t as void*; NULL = the default stream), allocates nothing: adds
+ *               the n reads whose rows [n][keep], n_rows [n] and k-mer counts [n][keep] a placement left in device
+ *               memory -- d_kmer_counts is required --, read i with d_weights[i] (uint32 [n]; NULL: 1).  n == 0 does
+ *               nothing.  Adds of one profile may run on several streams at once.
+ *   read        synchronises the profile's device, then copies out mass[num_branches], best[num_branches] and the
+ *               totals (each may be NULL).
+ *   reset       synchronises the device and zeroes the profile.
+ *   info        num_branches, and whether add_device sums in LDS first (trees whose 16 * num_branches bytes fit: up to 10 236) or
+ *               straight into global memory; EPIK_AMD_PROFILE_LDS=0|1, read at create(), forces either (tests).
+ * profile_reads / _strands / _frames: place / place_strands / place_frames with the rows left on the device and added
+ * to `profile` there -- nothing crosses back but the strand / frame byte per read (NULL: nothing at all).  weights:
+ * uint32 [n] on the HOST, or NULL.  The profile must have been created for this placer's device and shape.  Whole
+ * databases only.  Synchronous.
+ */
+#define EPIK_AMD_PROFILE_LWR_BITS 30
+typedef struct epik_amd_profile epik_amd_profile;
+typedef struct {
+    uint64_t placed;     /* weighted reads with rows and hits */
+    uint64_t no_hit;     /* ... whose rows are fabricated: none of their k-mers is in the database */
+    uint64_t too_short;  /* ... shorter than k */
+    uint64_t too_narrow; /* ... EPIK_AMD_ROWS_COUNTS_TOO_NARROW (device-pointer launches only) */
+    uint64_t bad_rows;   /* rows (not weighted) whose branch is >= num_branches */
+} epik_amd_profile_totals;
+int epik_amd_profile_create(const epik_amd_placer *p, epik_amd_profile **out);
+void epik_amd_profile_destroy(epik_amd_profile *profile);
+int epik_amd_profile_reset(epik_amd_profile *profile);
+int epik_amd_profile_read(epik_amd_profile *profile, uint64_t *mass, uint64_t *best, epik_amd_profile_totals *totals);
+int epik_amd_profile_info(const epik_amd_profile *profile, uint32_t *num_branches, uint32_t *lds_path);
+int epik_amd_profile_add_device(epik_amd_profile *profile, const void *d_rows, const void *d_n_rows,
+                                const void *d_kmer_counts, const void *d_weights, uint64_t n, void *stream);
+int epik_amd_placer_profile_reads(epik_amd_placer *p, epik_amd_profile *profile, const char *seqs,
+                                  const uint64_t *seq_offsets, const uint32_t *weights, uint64_t n);
+int epik_amd_placer_profile_strands(epik_amd_placer *p, epik_amd_profile *profile, const char *seqs,
+                                    const uint64_t *seq_offsets, const uint32_t *weights, uint64_t n, uint32_t mode,
+                                    uint8_t *strand);
+int epik_amd_placer_profile_frames(epik_amd_placer *p, epik_amd_profile *profile, const char *seqs,
+                                   const uint64_t *seq_offsets, const uint32_t *weights, uint64_t n, uint32_t mode,
+                                   uint8_t *frame);
+
 /* Which kernels the last launch of this handle ran (reports; a large-tree handle falls back from the three-kernel
  * placement to the one-kernel one when the device has no room for the scratch of a launch). */
 #define EPIK_AMD_PATH_WAVE 0u            /* place_reads_kernel: one wavefront per read */
