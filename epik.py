@@ -10,7 +10,8 @@ amino -- translates the options into that driver's flags (-d -q -j --omega --mu 
 sharded across; --db-shard; --strand, which strand of each nucleotide read is placed
 (forward as given, its reverse complement, or both and the better one per read); --translate, with
 -s amino: nucleotide reads translated into their frames, per read the best frame; and --profile / --profile-only,
-the sample's abundance profile per branch beside the jplace or instead of it.
+the sample's abundance profile per branch beside the jplace or instead of it; --mates, the second FASTA file of a
+paired-end sample: every pair gets one placement.
 """
 from __future__ import annotations
 
@@ -51,6 +52,12 @@ PLACE_OPTIONS = [
                             help="With -s amino: the reads are nucleotide reads; place their frames +1 +2 +3 (forward), "
                                  "-1 -2 -3 (reverse) or all six (both), the best frame per read (then also "
                                  "frames_<input>.tsv, one name<TAB>+1..-3 per read).")),
+    (("--mates",), dict(type=click.Path(exists=True, dir_okay=False), default=None,
+                        help="Paired-end reads: the FASTA file of the second mates, records in the order of the query "
+                             "file; every pair gets ONE placement, named by the query's records (-s nucl).")),
+    (("--mate-orientation",), dict(type=click.Choice(["fr", "ff"]), default="fr", show_default=True,
+                                   help="With --mates: fr, mate 2 is the reverse complement of the fragment's far end "
+                                        "(Illumina paired-end), or ff.")),
     (("--profile",), dict(is_flag=True, help="Also write profile_<input>.tsv: per branch the summed like-weight ratios "
                                              "and the reads placed best on it, with clade sums.")),
     (("--profile-only",), dict(is_flag=True, help="Write profile_<input>.tsv and no jplace: the placements are summed on "
@@ -69,7 +76,8 @@ def driver_path(states: str) -> str:
 
 
 def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpus, input_file, db_shard=1,
-                   strand="forward", translate=None, profile=False, profile_only=False):
+                   strand="forward", translate=None, profile=False, profile_only=False, mates=None,
+                   mate_orientation="fr"):
     argv = [driver_path(states), "-d", str(database), "-q", str(input_file), "-j", str(threads),
             "--omega", str(omega), "--mu", str(mu), "-o", str(outputdir)]
     if max_ram:
@@ -82,6 +90,10 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--strand", str(strand)]
     if translate is not None:
         argv += ["--translate", str(translate)]
+    if mates is not None:
+        argv += ["--mates", str(mates)]
+        if mate_orientation != "fr":
+            argv += ["--mate-orientation", str(mate_orientation)]
     if profile:
         argv += ["--profile"]
     if profile_only:

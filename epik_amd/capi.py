@@ -56,6 +56,10 @@ EXPORTS = (
     "epik_amd_placer_strand_workspace_bytes",
     "epik_amd_placer_place_strands_device",
     "epik_amd_placer_place_strands",
+    "epik_amd_placer_mates_separator",
+    "epik_amd_placer_mates_workspace_bytes",
+    "epik_amd_placer_place_mates_device",
+    "epik_amd_placer_place_mates",
     "epik_amd_codon_table",
     "epik_amd_placer_frame_workspace_bytes",
     "epik_amd_placer_place_frames_device",
@@ -69,6 +73,7 @@ EXPORTS = (
     "epik_amd_placer_profile_reads",
     "epik_amd_placer_profile_strands",
     "epik_amd_placer_profile_frames",
+    "epik_amd_placer_profile_mates",
 )
 
 
@@ -153,6 +158,11 @@ PATH_WAVE, PATH_TEAM_ONE_KERNEL, PATH_TEAM_STREAMED = 0, 1, 2
 #: strand modes of epik_amd_placer_place_strands[_device], and their names in Placer / epik.py / epik-dna --strand
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
 STRANDS = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
+
+#: orientation of the mates of a pair (epik_amd_placer_place_mates[_device]): FR, the default (mate 2 arrives as the
+#: reverse complement of the fragment's far end: Illumina paired-end), or FF, or-ed into the strand mode
+MATES_FF = 0x100
+MATE_ORIENTATIONS = {"fr": 0, "ff": MATES_FF}
 
 #: frame modes of epik_amd_placer_place_frames[_device] (+1 +2 +3 / -1 -2 -3 / all six), their names in Placer /
 #: epik.py / epik-aa --translate, and the names of the frame bytes 0..5
@@ -289,6 +299,15 @@ def load() -> ctypes.CDLL:
         for name in names:
             getattr(lib, name).restype = i32
             getattr(lib, name).argtypes = argtypes
+    # (mates: the strand placement's prototypes over pairs; the device entry is also told the characters of its batch)
+    lib.epik_amd_placer_mates_separator.restype = i32
+    lib.epik_amd_placer_mates_separator.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8)]
+    lib.epik_amd_placer_mates_workspace_bytes.restype = i32
+    lib.epik_amd_placer_mates_workspace_bytes.argtypes = [vp, u64, u64, ctypes.c_uint32, ctypes.POINTER(u64)]
+    lib.epik_amd_placer_place_mates_device.restype = i32
+    lib.epik_amd_placer_place_mates_device.argtypes = [vp, vp, vp, u64, u64, ctypes.c_uint32, vp, u64, vp, vp, vp, vp, vp]
+    lib.epik_amd_placer_place_mates.restype = i32
+    lib.epik_amd_placer_place_mates.argtypes = [vp, vp, vp, u64, ctypes.c_uint32, vp, vp, vp, vp]
     # (the abundance profile)
     lib.epik_amd_profile_create.restype = i32
     lib.epik_amd_profile_create.argtypes = [vp, ctypes.POINTER(vp)]
@@ -304,7 +323,7 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_profile_add_device.argtypes = [vp, vp, vp, vp, vp, u64, vp]
     lib.epik_amd_placer_profile_reads.restype = i32
     lib.epik_amd_placer_profile_reads.argtypes = [vp, vp, vp, vp, vp, u64]
-    for name in ("epik_amd_placer_profile_strands", "epik_amd_placer_profile_frames"):
+    for name in ("epik_amd_placer_profile_strands", "epik_amd_placer_profile_frames", "epik_amd_placer_profile_mates"):
         getattr(lib, name).restype = i32
         getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, u64, ctypes.c_uint32, vp]
     _lib = lib

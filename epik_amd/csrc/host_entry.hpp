@@ -1,7 +1,8 @@
 // host_entry.hpp -- the host side shared by the placements around epik_amd_placer_place_device: the synchronous
-// host-buffer entry points of strand_place.hip and frame_place.hip are place_host_chunked over a HostVariant each, and
-// their profile-only twins (profile_place.hip: profile_host_chunked) the same with a sink per chunk and nothing copied
-// out; shard_place.hip takes the HIP-error macro and the batch check.  Internal to libepik_amd.
+// host-buffer entry points of strand_place.hip, frame_place.hip and mates_place.hip are place_host_chunked over a
+// HostVariant each, and their profile-only twins (profile_place.hip: profile_host_chunked) the same with a sink per
+// chunk and nothing copied out; shard_place.hip takes the HIP-error macro and the batch check; the complement on
+// character classes serves strand_place.hip and mates_place.hip.  Internal to libepik_amd.
 #ifndef EPIK_AMD_HOST_ENTRY_HPP
 #define EPIK_AMD_HOST_ENTRY_HPP
 #include <hip/hip_runtime.h>
@@ -57,6 +58,32 @@ inline int check_host_reads(const char *seqs, const uint64_t *seq_offsets, uint6
     return EPIK_AMD_OK;
 }
 
+// For every byte, a byte of the complemented class (by value in a kernel's arguments: no allocation)
+struct ComplementMap {
+    uint8_t byte[256];
+};
+
+// For every byte c, a byte whose class is bitrev4(char_class[c]) -- from the handle's own table
+inline int complement_map(const epik_amd_placer *p, ComplementMap &map)
+{
+    if (p->h_char_class.size() != 256) return fail_with(EPIK_AMD_ERR_INVALID, "placer has no character table");
+    int rep[16];
+    std::fill(rep, rep + 16, -1);
+    for (int c = 255; c >= 0; --c) {  // (the smallest byte of each class)
+        const uint32_t cls = p->h_char_class[c];
+        if (cls > 15) return fail_with(EPIK_AMD_ERR_UNSUPPORTED, "character class outside the four nucleotide states");
+        rep[cls] = c;
+    }
+    for (int c = 0; c < 256; ++c) {
+        const uint32_t comp = bitrev4(p->h_char_class[c]);
+        if (rep[comp] < 0)
+            return fail_with(EPIK_AMD_ERR_UNSUPPORTED, "the character table has no character of class " + std::to_string(comp) +
+                                                           ", the complement of byte " + std::to_string(c) + "'s");
+        map.byte[c] = (uint8_t)rep[comp];
+    }
+    return EPIK_AMD_OK;
+}
+
 // k-mers a sequence may have with counts of that width (capi.hip's rule: the top bit of 16- and 32-bit counts is a flag)
 inline uint64_t max_kmers_of_counts(int counts) { return counts == kCounts8 ? 255u : counts == kCounts16 ? 32767u : 0x7fffffffull; }
 
@@ -94,10 +121,17 @@ struct HostVariant {
     int (*place_device)(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offsets, uint64_t n, uint32_t mode,
                         void *d_workspace, uint64_t workspace_bytes, void *d_rows, void *d_n_rows, void *d_kmer_counts,
                         void *d_label, hipStream_t stream);
+    // offsets an item takes in seq_offsets: 1, a read; 2, a pair of mates (reads 2i and 2i + 1) -- n, the chunks, rows
+    // and label bytes count items
+    uint64_t item_reads = 1;
+    // used instead of place_device when set: a device entry that is also told the characters of its batch
+    int (*place_device_sized)(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offsets, uint64_t n, uint64_t seq_bytes,
+                              uint32_t mode, void *d_workspace, uint64_t workspace_bytes, void *d_rows, void *d_n_rows,
+                              void *d_kmer_counts, void *d_label, hipStream_t stream) = nullptr;
 };
 
 // What may look at every chunk of place_host_chunked while it is on the device: called once the chunk is placed,
-// with its device rows, row counts and k-mer counts, the index of its first read in the batch and its number of reads;
+// with its device rows, row counts and k-mer counts, the index of its first item in the batch and its number of items;
 // whatever it enqueues goes on `stream`, the handle's, ahead of the copies out.
 struct ChunkSink {
     int (*fn)(void *ctx, const epik_amd_placement *d_rows, const uint32_t *d_n_rows, const uint32_t *d_kmer_counts,
@@ -118,23 +152,24 @@ inline int place_host_chunked(epik_amd_placer *p, const char *seqs, const uint64
     const CountWidthGuard width(p, longest_placed);
     if (width.rc != EPIK_AMD_OK) return width.rc;
 
-    // chunks of at most chunk_reads reads and chunk_bytes characters (a longer read: a chunk of its own)
+    // chunks of at most chunk_reads items and chunk_bytes characters (a longer item: a chunk of its own)
+    const uint64_t s = v.item_reads;
     uint64_t chunk_reads = v.chunk_reads;
     if (const char *e = std::getenv(v.chunk_reads_env)) chunk_reads = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
     std::vector<uint64_t> starts{0};
     uint64_t max_reads = 0, max_bytes = 0;
     for (uint64_t r0 = 0; r0 < n;) {
         uint64_t r1 = r0 + 1;
-        while (r1 < n && r1 - r0 < chunk_reads && seq_offsets[r1 + 1] - seq_offsets[r0] <= v.chunk_bytes) ++r1;
+        while (r1 < n && r1 - r0 < chunk_reads && seq_offsets[s * (r1 + 1)] - seq_offsets[s * r0] <= v.chunk_bytes) ++r1;
         max_reads = std::max(max_reads, r1 - r0);
-        max_bytes = std::max(max_bytes, seq_offsets[r1] - seq_offsets[r0]);
+        max_bytes = std::max(max_bytes, seq_offsets[s * r1] - seq_offsets[s * r0]);
         starts.push_back(r0 = r1);
     }
     const uint64_t keep = p->params.keep_at_most;
     uint64_t ws_bytes = 0;
     if (const int rc = v.workspace_bytes(p, max_reads, max_bytes, mode, &ws_bytes); rc != EPIK_AMD_OK) return rc;
     // one allocation: seqs | offsets | rows | n_rows | counts | label | workspace
-    const uint64_t o_offs = align_up(max_bytes + 1), o_rows = o_offs + align_up((max_reads + 1) * sizeof(uint64_t));
+    const uint64_t o_offs = align_up(max_bytes + 1), o_rows = o_offs + align_up((s * max_reads + 1) * sizeof(uint64_t));
     const uint64_t o_nrows = o_rows + align_up(max_reads * keep * sizeof(epik_amd_placement));
     const uint64_t o_counts = o_nrows + align_up(max_reads * sizeof(uint32_t));
     const uint64_t o_label = o_counts + align_up(max_reads * keep * sizeof(uint32_t));
@@ -156,19 +191,21 @@ inline int place_host_chunked(epik_amd_placer *p, const char *seqs, const uint64
     auto *d_nrows = reinterpret_cast<uint32_t *>(d + o_nrows);
     auto *d_counts = reinterpret_cast<uint32_t *>(d + o_counts);
     uint8_t *d_label = d + o_label, *d_ws = ws_bytes ? d + o_ws : nullptr;
-    std::vector<uint64_t> offs(max_reads + 1);
+    std::vector<uint64_t> offs(s * max_reads + 1);
     for (size_t c = 0; c + 1 < starts.size(); ++c) {
-        const uint64_t r0 = starts[c], cnt = starts[c + 1] - r0, b0 = seq_offsets[r0], bytes = seq_offsets[r0 + cnt] - b0;
-        for (uint64_t i = 0; i <= cnt; ++i) offs[i] = seq_offsets[r0 + i] - b0;
+        const uint64_t r0 = starts[c], cnt = starts[c + 1] - r0, b0 = seq_offsets[s * r0], bytes = seq_offsets[s * (r0 + cnt)] - b0;
+        for (uint64_t i = 0; i <= s * cnt; ++i) offs[i] = seq_offsets[s * r0 + i] - b0;
         if (bytes) HIP_TRY(hipMemcpyAsync(d, seqs + b0, bytes, hipMemcpyHostToDevice, p->stream));
-        HIP_TRY(hipMemcpyAsync(d_offs, offs.data(), (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+        HIP_TRY(hipMemcpyAsync(d_offs, offs.data(), (s * cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
         // rows beyond n_rows[i] are never written by the kernels: zero, as epik_amd_placer_place leaves them
         HIP_TRY(hipMemsetAsync(d_rows, 0, cnt * keep * sizeof(epik_amd_placement), p->stream));
         HIP_TRY(hipMemsetAsync(d_counts, 0, cnt * keep * sizeof(uint32_t), p->stream));
         if (const uint64_t zeroed = v.zeroed_bytes ? v.zeroed_bytes(p, cnt, mode) : 0) HIP_TRY(hipMemsetAsync(d_ws, 0, zeroed, p->stream));
         uint64_t chunk_ws = 0;
         if (const int rc = v.workspace_bytes(p, cnt, bytes, mode, &chunk_ws); rc != EPIK_AMD_OK) return rc;
-        if (const int rc = v.place_device(p, d, d_offs, cnt, mode, d_ws, chunk_ws, d_rows, d_nrows, d_counts, d_label, p->stream);
+        if (const int rc = v.place_device_sized
+                               ? v.place_device_sized(p, d, d_offs, cnt, bytes, mode, d_ws, chunk_ws, d_rows, d_nrows, d_counts, d_label, p->stream)
+                               : v.place_device(p, d, d_offs, cnt, mode, d_ws, chunk_ws, d_rows, d_nrows, d_counts, d_label, p->stream);
             rc != EPIK_AMD_OK)
             return rc;
         if (sink)

@@ -41,11 +41,6 @@ using namespace epik_amd;
 
 constexpr uint64_t kMaxBlocks = 8192;  // (grid-stride beyond: a million reads is 256 K waves of work either way)
 
-// For every byte, a byte of the complemented class (by value in the kernel's arguments: no allocation)
-struct ComplementMap {
-    uint8_t byte[256];
-};
-
 __global__ __launch_bounds__(kBlock) void revcomp_kernel(const uint8_t *__restrict__ seqs,
                                                          const uint64_t *__restrict__ seq_offsets, uint64_t n,
                                                          uint8_t *__restrict__ out, uint64_t out_cap, ComplementMap map)
@@ -146,27 +141,6 @@ int check_handle(const epik_amd_placer *p, uint32_t mode)
         return fail_with(EPIK_AMD_ERR_UNSUPPORTED, "strand placement needs a nucleotide placer (alphabet_size 4)");
     if (p->plan.shard_count > 1)
         return fail_with(EPIK_AMD_ERR_UNSUPPORTED, "strand placement needs a whole database, not a k-mer-space shard");
-    return EPIK_AMD_OK;
-}
-
-// For every byte c, a byte whose class is bitrev4(char_class[c]) -- from the handle's own table
-int complement_map(const epik_amd_placer *p, ComplementMap &map)
-{
-    if (p->h_char_class.size() != 256) return fail_with(EPIK_AMD_ERR_INVALID, "placer has no character table");
-    int rep[16];
-    std::fill(rep, rep + 16, -1);
-    for (int c = 255; c >= 0; --c) {  // (the smallest byte of each class)
-        const uint32_t cls = p->h_char_class[c];
-        if (cls > 15) return fail_with(EPIK_AMD_ERR_UNSUPPORTED, "character class outside the four nucleotide states");
-        rep[cls] = c;
-    }
-    for (int c = 0; c < 256; ++c) {
-        const uint32_t comp = bitrev4(p->h_char_class[c]);
-        if (rep[comp] < 0)
-            return fail_with(EPIK_AMD_ERR_UNSUPPORTED, "the character table has no character of class " + std::to_string(comp) +
-                                                           ", the complement of byte " + std::to_string(c) + "'s");
-        map.byte[c] = (uint8_t)rep[comp];
-    }
     return EPIK_AMD_OK;
 }
 

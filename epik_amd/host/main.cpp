@@ -10,10 +10,11 @@
 // every device, batches shared out) and --db-shard G (the database cut in G by k-mer code, shard g on device g:
 // every batch is placed by all of them together -- a database larger than one device's memory); --profile /
 // --profile-only (the sample's abundance profile, profile.hpp: beside the jplace, or instead of it and summed on the
-// devices).
+// devices); --mates FILE (paired-end reads: the second mates, one placement per pair).
 // The two binaries differ as the reference's do (epik/CMakeLists.txt:72,124): epik-dna
 // accepts DNA databases, epik-aa protein ones.
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -157,6 +158,16 @@ std::string make_frames_filename(const std::string& input_file, const std::strin
     return dir + "frames_" + base + ".tsv";
 }
 
+/// What two mates are both called: the header up to the first white space, without a trailing /1 or /2
+std::string_view mate_name(std::string_view header)
+{
+    size_t end = 0;
+    while (end < header.size() && !std::isspace((unsigned char)header[end])) ++end;
+    std::string_view name = header.substr(0, end);
+    if (name.size() >= 2 && name[name.size() - 2] == '/' && (name.back() == '1' || name.back() == '2')) name.remove_suffix(2);
+    return name;
+}
+
 }  // namespace
 #endif  // EPIK_AMD_NO_MAIN
 
@@ -185,6 +196,9 @@ const char* kHelp =
     "      --strand arg        forward | reverse (reverse complement) | both (the better per read) (default: forward)\n"
     "      --translate arg     Nucleotide reads on this amino-acid database: forward (frames +1 +2 +3) | reverse\n"
     "                          (-1 -2 -3) | both (all six); the best frame per read (epik-aa; default: off)\n"
+    "      --mates arg         Paired-end reads: the FASTA file of the second mates, records in the order of the query;\n"
+    "                          every pair gets ONE placement, named by the query's records (epik-dna)\n"
+    "      --mate-orientation arg  fr (mate 2 is the reverse complement of the fragment's far end) | ff (default: fr)\n"
     "      --profile           Also write profile_<query>.tsv: per branch the summed like-weight ratios and the reads\n"
     "                          placed best on it, with clade sums; reads without any hit are counted, not spread\n"
     "      --profile-only      Write that profile and no jplace: the rows are summed on the device(s) and never\n"
@@ -272,6 +286,19 @@ int main(int argc, char** argv)
 #endif
             if (std::stoul(parsed.get("db-shard", "1")) > 1)
                 throw std::runtime_error("--strand " + strand_name + " does not work with --db-shard > 1");
+        }
+        // --mates: checked before anything is opened or any device touched
+        const bool with_mates = parsed.has("mates");
+        const auto orientation_name = parsed.get("mate-orientation", "fr");
+        if (orientation_name != "fr" && orientation_name != "ff")
+            throw std::runtime_error("--mate-orientation must be fr or ff, not '" + orientation_name + "'");
+        if (parsed.has("mate-orientation") && !with_mates) throw std::runtime_error("--mate-orientation needs --mates");
+        if (with_mates) {
+#ifdef EPIK_AMD_AA
+            throw std::runtime_error("--mates places pairs of nucleotide reads only (epik-dna)");
+#endif
+            if (parsed.has("translate")) throw std::runtime_error("--mates does not work with --translate");
+            if (std::stoul(parsed.get("db-shard", "1")) > 1) throw std::runtime_error("--mates does not work with --db-shard > 1");
         }
         // --translate: checked before anything is opened or any device touched
         const bool translate = parsed.has("translate");
@@ -367,6 +394,7 @@ int main(int argc, char** argv)
         epik_amd::placer placer(db, tree, keep_at_most, keep_factor, num_threads, devices, db_shards, load_shard);
         placer.set_strand(strand);
         if (translate) placer.set_translate(frames);
+        if (with_mates) placer.set_mates(orientation_name == "ff" ? epik_amd::mate_orientation::ff : epik_amd::mate_orientation::fr);
         if (profile_only) placer.set_profile_only();
         db.drop_lists();  // the lists are on the devices now; tree, k and omega stay for the output
         const auto tree_as_newick = epik_amd::io::to_newick(tree, true);
@@ -415,6 +443,7 @@ int main(int argc, char** argv)
         struct work_item {
             size_t sequence = 0;                          // position of the batch in the input
             std::vector<epik_amd::seq_record> batch;     // owns the bytes the views below point into
+            std::vector<epik_amd::seq_record> mates;     // --mates: the second mate of every record of the batch
             epik_amd::impl::placed_batch placed;
         };
         const size_t n_devices = placer.device_count();
@@ -427,13 +456,36 @@ int main(int argc, char** argv)
         std::mutex stats_mutex;
         // (the records of a batch are views into the reader's mapping of the file: it stays until all is written)
         epik_amd::io::batch_fasta reader(query_file, batch_size);
+        // --mates: read in step with the query, record for record
+        std::unique_ptr<epik_amd::io::batch_fasta> mates_reader;
+        if (with_mates) mates_reader.reset(new epik_amd::io::batch_fasta(parsed.require("mates"), batch_size));
         std::thread reader_thread([&] {
             try {
+                size_t records = 0;
                 for (size_t sequence = 0;; ++sequence) {
                     read_clock.start();
                     auto batch = reader.next_batch();
+                    std::vector<epik_amd::seq_record> mates;
+                    if (mates_reader) {
+                        mates = mates_reader->next_batch();
+                        const size_t both = std::min(batch.size(), mates.size());
+                        for (size_t i = 0; i < both; ++i)
+                            if (mate_name(batch[i].header()) != mate_name(mates[i].header()))
+                                throw std::runtime_error("--mates: record " + std::to_string(records + i + 1) + " of the mates is '" +
+                                                         std::string(mate_name(mates[i].header())) + "', of the query '" +
+                                                         std::string(mate_name(batch[i].header())) +
+                                                         "': the mates must come in the order of the query");
+                        if (batch.size() != mates.size()) {
+                            const auto& longer = batch.size() > both ? batch : mates;
+                            throw std::runtime_error(std::string("--mates: the ") + (batch.size() > both ? "mates" : "query") +
+                                                     " end after " + std::to_string(records + both) + " records: no mate for record " +
+                                                     std::to_string(records + both + 1) + " ('" +
+                                                     std::string(mate_name(longer[both].header())) + "')");
+                        }
+                        records += both;
+                    }
                     read_clock.stop();
-                    if (batch.empty() || !to_place.push(work_item{sequence, std::move(batch), {}})) break;
+                    if (batch.empty() || !to_place.push(work_item{sequence, std::move(batch), std::move(mates), {}})) break;
                 }
             } catch (...) {
                 reader_error = std::current_exception();
@@ -492,8 +544,9 @@ int main(int argc, char** argv)
                         const auto begin_group = std::chrono::steady_clock::now();
                         place_clocks[device].start();
                         std::vector<const std::vector<epik_amd::seq_record>*> batches;
-                        for (const auto& item : group) batches.push_back(&item.batch);
-                        auto placed = placer.place_flat(batches, device, num_threads);
+                        std::vector<const std::vector<epik_amd::seq_record>*> mate_batches;
+                        for (const auto& item : group) batches.push_back(&item.batch), mate_batches.push_back(&item.mates);
+                        auto placed = placer.place_flat(batches, device, num_threads, with_mates ? &mate_batches : nullptr);
                         place_clocks[device].stop();
                         auto ms_diff = (float)std::chrono::duration_cast<std::chrono::microseconds>(
                                            std::chrono::steady_clock::now() - begin_group).count() / 1000.0f;

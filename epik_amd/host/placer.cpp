@@ -18,6 +18,8 @@
 #pragma weak epik_amd_placer_profile_reads
 #pragma weak epik_amd_placer_profile_strands
 #pragma weak epik_amd_placer_profile_frames
+#pragma weak epik_amd_placer_place_mates
+#pragma weak epik_amd_placer_profile_mates
 
 namespace epik_amd {
 
@@ -138,6 +140,17 @@ void placer::set_translate(translate_mode mode)
     _frames = mode;
 }
 
+void placer::set_mates(mate_orientation orientation)
+{
+    if (_sharded) throw std::runtime_error("GPU placer: --mates does not work with --db-shard > 1");
+    if (alphabet_size(_db.sequence_type()) != 4) throw std::runtime_error("GPU placer: --mates needs a nucleotide database");
+    if (_translate) throw std::runtime_error("GPU placer: --mates does not work with --translate");
+    if (!&epik_amd_placer_place_mates || !&epik_amd_placer_profile_mates)
+        throw std::runtime_error("GPU placer: this libepik_amd has no mates placement");
+    _mates = true;
+    _mates_mode = (uint32_t)orientation;
+}
+
 void placer::set_profile_only()
 {
     if (_sharded) throw std::runtime_error("GPU placer: --profile-only does not work with --db-shard > 1");
@@ -209,9 +222,13 @@ inline uint64_t hash_bytes(std::string_view s)
 }  // namespace
 
 std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::vector<seq_record>*>& batches,
-                                                   size_t device_index, size_t num_threads)
+                                                   size_t device_index, size_t num_threads,
+                                                   const std::vector<const std::vector<seq_record>*>* mate_batches)
 {
     if (device_index >= device_count()) throw std::runtime_error("GPU placer: no such device index");
+    if (_mates != (mate_batches != nullptr) || (mate_batches && mate_batches->size() != batches.size()))
+        throw std::runtime_error("GPU placer: a placer of pairs (set_mates) takes a batch of mates for every batch, any other none");
+    const size_t per = _mates ? 2 : 1;  // reads a unique item sends through the boundary
     std::vector<impl::placed_batch> out(batches.size());
     // identical sequences of a batch are placed once (place.cpp:73-81, 207-212); the unique reads of
     // all batches go through the boundary in one call.  The batches are independent of each other up to
@@ -219,6 +236,8 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
     std::vector<size_t> first_unique(batches.size() + 1, 0), first_byte(batches.size() + 1, 0);
     parallel_for(batches.size(), num_threads, [&](size_t b) {
         const auto& batch = *batches[b];
+        const std::vector<seq_record>* mates = mate_batches ? (*mate_batches)[b] : nullptr;
+        if (mates && mates->size() != batch.size()) throw std::runtime_error("GPU placer: a batch and its mates differ in size");
         impl::placed_batch pb;  // (the thread's own while it grows: neighbours in out[] share cache lines)
         if (batch.size() >= 0xffffffffull) throw std::runtime_error("GPU placer: a batch of 2^32 reads or more");
         // open addressing over the positions of the batch: slot -> index of a unique sequence + 1
@@ -230,19 +249,23 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         n_names.reserve(batch.size());
         size_t bytes = 0;
         for (size_t i = 0; i < batch.size(); ++i) {
-            const std::string_view seq = batch[i].sequence();
-            size_t slot = (size_t)hash_bytes(seq) & (cap - 1);
+            // (pairs: the same, by the PAIR of sequences)
+            const std::string_view seq = batch[i].sequence(), mate = mates ? (*mates)[i].sequence() : std::string_view();
+            uint64_t hash = hash_bytes(seq);
+            if (mates) hash = (hash ^ (hash_bytes(mate) + 0x9e3779b97f4a7c15ull + (hash << 6) + (hash >> 2)));
+            size_t slot = (size_t)hash & (cap - 1);
             for (;;) {
                 const uint32_t u = table[slot];
                 if (u == 0) {
                     table[slot] = (uint32_t)pb.sequences.size() + 1;
                     unique_of[i] = (uint32_t)pb.sequences.size();
                     pb.sequences.push_back(seq);
+                    if (mates) pb.mates.push_back(mate);
                     n_names.push_back(1);
-                    bytes += seq.size();
+                    bytes += seq.size() + mate.size();
                     break;
                 }
-                if (pb.sequences[u - 1] == seq) {
+                if (pb.sequences[u - 1] == seq && (!mates || pb.mates[u - 1] == mate)) {
                     unique_of[i] = u - 1;
                     ++n_names[u - 1];
                     break;
@@ -272,16 +295,23 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         return out;
     }
     std::unique_ptr<char[]> bytes(new char[first_byte.back() + 1]);
-    std::unique_ptr<uint64_t[]> offsets(new uint64_t[n + 1]);
-    offsets[n] = first_byte.back();
+    std::unique_ptr<uint64_t[]> offsets(new uint64_t[per * n + 1]);
+    offsets[per * n] = first_byte.back();
     parallel_for(batches.size(), num_threads, [&](size_t b) {
-        size_t at = first_byte[b], i = first_unique[b];
-        for (const auto seq : out[b].sequences) {
+        size_t at = first_byte[b], i = per * first_unique[b];
+        for (size_t u = 0; u < out[b].sequences.size(); ++u) {
+            const auto seq = out[b].sequences[u];
             offsets[i++] = at;
             std::memcpy(bytes.get() + at, seq.data(), seq.size());
             at += seq.size();
+            if (!_mates) continue;  // (interleaved: mate 1, mate 2 of every pair)
+            const auto mate = out[b].mates[u];
+            offsets[i++] = at;
+            std::memcpy(bytes.get() + at, mate.data(), mate.size());
+            at += mate.size();
         }
     });
+    const uint32_t mates_mode = (uint32_t)_strand | _mates_mode;
     if (profile_only()) {
         // the rows stay on the device and are summed there; what comes back is the strand / frame byte per sequence
         std::unique_ptr<uint32_t[]> weights(new uint32_t[n]);
@@ -292,7 +322,9 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         if (_translate || _strand != strand_mode::forward) labels.reset(new uint8_t[n]);
         auto* handle = _handles[device_index];
         auto* profile = _profiles[device_index];
-        const int rc = _translate ? epik_amd_placer_profile_frames(handle, profile, bytes.get(), offsets.get(), weights.get(), n,
+        const int rc = _mates ? epik_amd_placer_profile_mates(handle, profile, bytes.get(), offsets.get(), weights.get(), n,
+                                                               mates_mode, labels.get())
+                       : _translate ? epik_amd_placer_profile_frames(handle, profile, bytes.get(), offsets.get(), weights.get(), n,
                                                                    (uint32_t)_frames, labels.get())
                        : _strand != strand_mode::forward
                            ? epik_amd_placer_profile_strands(handle, profile, bytes.get(), offsets.get(), weights.get(), n,
@@ -313,7 +345,11 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
     std::unique_ptr<uint8_t[]> strands;  // (reverse / both only: forward goes through epik_amd_placer_place as ever)
     std::unique_ptr<uint8_t[]> frames;   // (translated placement only)
     int rc;
-    if (_translate) {
+    if (_mates) {
+        if (_strand != strand_mode::forward) strands.reset(new uint8_t[n]);
+        rc = epik_amd_placer_place_mates(_handles[device_index], bytes.get(), offsets.get(), n, mates_mode, rows.get(),
+                                         n_rows.get(), counts.get(), strands.get());
+    } else if (_translate) {
         frames.reset(new uint8_t[n]);
         rc = epik_amd_placer_place_frames(_handles[device_index], bytes.get(), offsets.get(), n, (uint32_t)_frames,
                                           rows.get(), n_rows.get(), counts.get(), frames.get());

@@ -64,6 +64,8 @@ struct placed_batch {
     std::vector<uint32_t> unique_of;          // [batch size]: the unique sequence of each record, input order
     // translated placement (placer::set_translate) only, else empty:
     std::vector<uint8_t> frames;              // [n_unique]: the frame placed, 0..5 = +1 +2 +3 -1 -2 -3
+    // pairs (placer::set_mates) only, else empty: `sequences` are the first mates, `strands` the fragments'
+    std::vector<std::string_view> mates;      // [n_unique]: the second mate, as given
     size_t size() const noexcept { return sequences.size(); }
 };
 
@@ -78,6 +80,10 @@ enum class strand_mode : uint32_t { forward = EPIK_AMD_STRAND_FORWARD, reverse =
 /// Which frames of a nucleotide read are placed on an amino-acid database (epik_amd_placer_place_frames): +1 +2 +3,
 /// -1 -2 -3, or all six; per read the best one.
 enum class translate_mode : uint32_t { forward = EPIK_AMD_FRAMES_FORWARD, reverse = EPIK_AMD_FRAMES_REVERSE, both = EPIK_AMD_FRAMES_BOTH };
+
+/// How the mates of a pair lie (epik_amd_placer_place_mates): FR, mate 2 the reverse complement of the fragment's far
+/// end (Illumina paired-end), or FF.
+enum class mate_orientation : uint32_t { fr = 0, ff = EPIK_AMD_MATES_FF };
 
 class placer {
 public:
@@ -111,8 +117,11 @@ public:
     std::vector<placed_collection> place_batches(const std::vector<const std::vector<seq_record>*>& batches,
                                                  size_t device_index, size_t num_threads = 1);
     /// The same placement in the driver's flat form (impl::placed_batch): what epik-dna / epik-aa call.
+    /// A placer of pairs (set_mates) is also given `mate_batches`: for every batch the second mates of its records, in
+    /// their order.  A batch is then de-duplicated by the PAIR of sequences and every unique pair placed once.
     std::vector<impl::placed_batch> place_flat(const std::vector<const std::vector<seq_record>*>& batches,
-                                               size_t device_index, size_t num_threads = 1);
+                                               size_t device_index, size_t num_threads = 1,
+                                               const std::vector<const std::vector<seq_record>*>* mate_batches = nullptr);
 
     /// How many callers may place at the same time (place_batches' device_index): the devices of a replicated
     /// database, ONE for a sharded one (all its handles work on every batch).
@@ -127,6 +136,11 @@ public:
     /// the placed batches say per sequence which frame won.  Amino-acid databases, replicated (not --db-shard) only.
     void set_translate(translate_mode mode);
     bool translating() const noexcept { return _translate; }
+    /// The records come in pairs, two mates of one fragment: place_flat takes the second mates beside every batch and
+    /// places each pair ONCE through epik_amd_placer_place_mates, on the strand(s) set_strand says (the fragment's).
+    /// Nucleotide databases, replicated (not --db-shard), not translated.
+    void set_mates(mate_orientation orientation);
+    bool pairing() const noexcept { return _mates; }
     /// --profile-only: one device profile per handle (epik_amd_profile); from then on place_flat leaves the rows on the
     /// device, adds them to the profile of its device there -- every unique sequence with the number of its records as
     /// weight -- and returns batches without rows (sequences, names and the strand / frame bytes as ever).
@@ -153,6 +167,8 @@ private:
     strand_mode _strand = strand_mode::forward;
     bool _translate = false;
     translate_mode _frames = translate_mode::both;
+    bool _mates = false;
+    uint32_t _mates_mode = 0;  // EPIK_AMD_MATES_FF or 0
 };
 
 }  // namespace epik_amd

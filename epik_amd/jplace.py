@@ -20,7 +20,9 @@ def write_jplace(path: str, placed, invocation: str, newick_tree: str) -> None:
             placements.append({
                 "p": [[p.branch_id, p.score, p.weight_ratio, p.distal_length, p.pendant_length]
                       for p in seq.placements],
-                "nm": [[h, 1] for h in batch.sequence_map[seq.sequence]],
+                # (a placed pair is known by both its mates, Placer.place(mates=...))
+                "nm": [[h, 1] for h in batch.sequence_map[seq.sequence if getattr(seq, "mate", None) is None
+                                                          else (seq.sequence, seq.mate)]],
             })
     doc = {"metadata": {"invocation": invocation}, "tree": newick_tree, "version": 3,
            "fields": FIELDS, "placements": placements}

@@ -24,6 +24,7 @@ from typing import Iterable, List, Sequence, Tuple
 import numpy as np
 
 from . import alphabet, capi
+from .mates import check_mate_names
 
 
 @dataclass
@@ -46,6 +47,7 @@ class PlacedSequence:
     placements: List[Placement]
     strand: str = "+"     # the strand placed: "-" when the reverse complement won (Placer.place(strand=...))
     frame: str = ""       # the frame placed, "+1" ... "-3" (Placer.place(translate=...)); "" when not translated
+    mate: str = None      # mate 2 as given, when a pair was placed (Placer.place(mates=...)): `sequence` is mate 1
 
 
 @dataclass
@@ -336,31 +338,90 @@ class Placer:
                                     self._strand_mode(mode), d_workspace, workspace_bytes, d_rows, d_n_rows,
                                     d_kmer_counts, d_strand, stream)
 
+    # -- paired-end reads, one placement per fragment ---------------------------------------------
+    @staticmethod
+    def _mates_mode(strand, orientation) -> int:
+        return Placer._strand_mode(strand) | Placer._mode(orientation, capi.MATE_ORIENTATIONS, "mate orientation")
+
+    def mates_separator(self) -> int:
+        """The byte the library puts between the mates of a pair (`epik_amd_placer_mates_separator`)."""
+        out = ctypes.c_uint8(0)
+        capi.check(self._lib.epik_amd_placer_mates_separator(self._handle, ctypes.byref(out)))
+        return int(out.value)
+
+    def mates_workspace_bytes(self, n_pairs: int, seq_bytes: int, strand="forward", orientation="fr") -> int:
+        """Device workspace `place_mates_device` needs for n_pairs pairs of seq_bytes characters in total
+        (`epik_amd_placer_mates_workspace_bytes`)."""
+        return self._workspace_bytes(self._lib.epik_amd_placer_mates_workspace_bytes, n_pairs, seq_bytes,
+                                     self._mates_mode(strand, orientation))
+
+    @staticmethod
+    def _pairs_of(seq_offsets: np.ndarray) -> int:
+        if seq_offsets.shape[0] % 2 != 1:
+            raise ValueError("an interleaved batch of pairs has an even number of reads (2 n + 1 offsets)")
+        return int(seq_offsets.shape[0] - 1) // 2
+
+    def place_mates(self, seqs: np.ndarray, seq_offsets: np.ndarray, strand="forward", orientation="fr"):
+        """One placement per pair of ONE interleaved batch -- read 2 i is mate 1, read 2 i + 1 mate 2 of pair i --: the
+        placement of mate 1 . separator . rc(mate 2) ("fr") or mate 1 . separator . mate 2 ("ff"), on the strand(s)
+        `strand` asks for (`epik_amd_placer_place_mates`).  Returns (rows, n_rows, kmer_counts, strand[n] uint8), all
+        per pair."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+        n = self._pairs_of(seq_offsets)
+        rows = np.zeros((n, self.keep_at_most), dtype=capi.PLACEMENT)
+        n_rows = np.zeros(n, dtype=np.uint32)
+        counts = np.zeros((n, self.keep_at_most), dtype=np.uint32)
+        label = np.zeros(n, dtype=np.uint8)
+        capi.check(self._lib.epik_amd_placer_place_mates(
+            self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n, self._mates_mode(strand, orientation),
+            rows.ctypes.data, n_rows.ctypes.data, counts.ctypes.data, label.ctypes.data))
+        return rows, n_rows, counts, label
+
+    def place_mates_device(self, d_seqs: int, d_seq_offsets: int, n_pairs: int, seq_bytes: int, strand, orientation,
+                           d_workspace: int, workspace_bytes: int, d_rows: int, d_n_rows: int, d_kmer_counts: int = 0,
+                           d_strand: int = 0, stream: int = 0) -> None:
+        """`place_mates` on device buffers, asynchronous on `stream`; the caller's workspace of
+        `mates_workspace_bytes(n_pairs, seq_bytes, ...)` and count width (`choose_counts` with the longest joined
+        sequence, len1 + len2 + 1) (`epik_amd_placer_place_mates_device`)."""
+        capi.check(self._lib.epik_amd_placer_place_mates_device(
+            self._handle, d_seqs, d_seq_offsets, int(n_pairs), int(seq_bytes), self._mates_mode(strand, orientation),
+            d_workspace or None, int(workspace_bytes), d_rows, d_n_rows, d_kmer_counts or None, d_strand or None,
+            stream or None))
+
     # -- the abundance profile (epik_amd/profile.py) ----------------------------------------------
     def profile(self):
         """A new, empty device profile for this placer (`epik_amd_profile_create`)."""
         from .profile import Profile
         return Profile(self)
 
-    def profile_packed(self, profile, seqs: np.ndarray, seq_offsets: np.ndarray, weights=None, strand=None, translate=None):
-        """`place_packed` / `place_strands` / `place_frames` with the rows left on the device and added to `profile`
-        there, read i with weights[i] (None: 1): `epik_amd_placer_profile_reads` / `_strands` / `_frames`.  Returns the
-        strand or frame byte per read (None without `strand` and `translate`)."""
+    def profile_packed(self, profile, seqs: np.ndarray, seq_offsets: np.ndarray, weights=None, strand=None, translate=None,
+                       mates=None):
+        """`place_packed` / `place_strands` / `place_frames` / `place_mates` with the rows left on the device and added
+        to `profile` there, read i with weights[i] (None: 1): `epik_amd_placer_profile_reads` / `_strands` / `_frames`
+        / `_mates`.  `mates` ("fr" / "ff"): the batch is interleaved pairs, counted and weighted per pair.  Returns
+        the strand or frame byte per read or pair (None without `strand`, `translate` and `mates`)."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
         seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
         n = int(seq_offsets.shape[0] - 1)
         if strand is not None and translate is not None:
             raise ValueError("strand and translate do not combine: translate=both already covers both strands")
+        if mates is not None:
+            if translate is not None:
+                raise ValueError("mates and translate do not combine: pairs are placed on nucleotide databases")
+            n = self._pairs_of(seq_offsets)
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint32)
         if w is not None and w.shape != (n,):
             raise ValueError(f"weights must hold one value per read ({n}), not {w.shape}")
         w_ptr = None if w is None else w.ctypes.data
-        if strand is None and translate is None:
+        if strand is None and translate is None and mates is None:
             capi.check(self._lib.epik_amd_placer_profile_reads(self._handle, profile._handle, seqs.ctypes.data,
                                                                seq_offsets.ctypes.data, w_ptr, n))
             return None
         label = np.zeros(n, dtype=np.uint8)
-        if translate is not None:
+        if mates is not None:
+            fn, mode = self._lib.epik_amd_placer_profile_mates, self._mates_mode(strand or "forward", mates)
+        elif translate is not None:
             fn, mode = self._lib.epik_amd_placer_profile_frames, self._frame_mode(translate)
         else:
             fn, mode = self._lib.epik_amd_placer_profile_strands, self._strand_mode(strand)
@@ -509,7 +570,8 @@ class Placer:
 
     # -- epik::placer::place ---------------------------------------------------------
     def place(self, seq_records: Iterable[Tuple[str, str]], num_threads: int = 1,
-              strand: str = "forward", translate=None, profile=None) -> PlacedCollection:
+              strand: str = "forward", translate=None, profile=None, mates=None,
+              mate_orientation: str = "fr") -> PlacedCollection:
         """`seq_records` = (header, sequence) pairs (i2l::seq_record).  `num_threads`
         is accepted for signature parity and ignored, as the parallelism is the GPU's.
         `strand`: "forward" (the reference's contract: each read as given), "reverse" (its reverse
@@ -518,23 +580,38 @@ class Placer:
         them as nucleotide reads and places their frames +1 +2 +3 / -1 -2 -3 / all six, per read the best one
         (PlacedSequence.frame says which).  Duplicates are merged on the nucleotide string.
         `profile` (a `Profile` of this placer): the placements are also added to it, every unique sequence with the
-        number of its records as weight."""
+        number of its records as weight.
+        `mates` (nucleotide databases): the second mates, (header, sequence) records in the order of `seq_records`;
+        every pair gets ONE placement, that of mate 1 . separator . rc(mate 2) (`mate_orientation` "fr") or mate 1 .
+        separator . mate 2 ("ff") (`place_mates`).  Duplicates are merged on the PAIR of sequences: `sequence_map` is
+        then keyed by (mate 1, mate 2) and holds mate 1's headers; PlacedSequence.sequence is mate 1, .mate mate 2,
+        .strand the fragment's strand."""
         del num_threads
         mode = self._strand_mode(strand)
         frame_mode = None if translate is None else self._frame_mode(translate)
         if frame_mode is not None and mode != capi.STRAND_FORWARD:
             raise ValueError("strand and translate do not combine: translate=both already covers both strands")
+        if mates is not None and frame_mode is not None:
+            raise ValueError("mates and translate do not combine: pairs are placed on nucleotide databases")
         sequence_map: dict = {}
-        for header, sequence in seq_records:          # place.cpp:73-81
-            sequence_map.setdefault(sequence, []).append(header)
+        if mates is not None:
+            seq_records, mates = list(seq_records), list(mates)
+            check_mate_names([h for h, _ in seq_records], [h for h, _ in mates])
+            for (header, sequence), (_, mate) in zip(seq_records, mates):
+                sequence_map.setdefault((sequence, mate), []).append(header)
+        else:
+            for header, sequence in seq_records:          # place.cpp:73-81
+                sequence_map.setdefault(sequence, []).append(header)
         unique = list(sequence_map.keys())            # place.cpp:52-63
-        bufs = [s.encode() for s in unique]
+        bufs = [s.encode() for s in unique] if mates is None else [m.encode() for pair in unique for m in pair]
         offsets = np.zeros(len(bufs) + 1, dtype=np.uint64)
         if bufs:
             offsets[1:] = np.cumsum([len(b) for b in bufs], dtype=np.uint64)
         data = np.frombuffer(b"".join(bufs), dtype=np.uint8) if bufs else np.zeros(0, np.uint8)
         strands = frames = None
-        if frame_mode is not None:
+        if mates is not None:
+            rows, n_rows, counts, strands = self.place_mates(data, offsets, mode, mate_orientation)
+        elif frame_mode is not None:
             rows, n_rows, counts, frames = self.place_frames(data, offsets, frame_mode)
         elif mode == capi.STRAND_FORWARD:
             rows, n_rows, counts = self.place_packed(data, offsets)
@@ -558,7 +635,8 @@ class Placer:
                     # rows fabricated for a read without hits carry 0.0 lengths (place.cpp:150)
                     distal_length=float(self.distal[b]) if in_tree and counts[i, r] else 0.0,
                     pendant_length=float(self.pendant[b]) if in_tree and counts[i, r] else 0.0))
-            placed.append(PlacedSequence(sequence=seq, placements=pl,
+            seq, mate = seq if mates is not None else (seq, None)
+            placed.append(PlacedSequence(sequence=seq, placements=pl, mate=mate,
                                          strand="-" if strands is not None and strands[i] else "+",
                                          frame=capi.FRAME_NAMES[int(frames[i])] if frames is not None else ""))
         return PlacedCollection(sequence_map=sequence_map, placed_seqs=placed)

@@ -373,6 +373,60 @@ int epik_amd_placer_place_strands(epik_amd_placer *p, const char *seqs, const ui
                                   uint32_t *kmer_counts, uint8_t *strand);
 
 /*
+ * Paired-end reads placed jointly: one placement per fragment.  No reference counterpart: the reference knows single
+ * reads only (place.cpp:294).
+ *
+ * The rule.  For a pair (m1, m2) of a nucleotide placer, with sep a byte of character class 0 (invalid) and rc() the
+ * reverse complement on classes defined above:
+ *     J = m1 . sep . rc(m2)     orientation FR (the default: Illumina paired-end)
+ *     J = m1 . sep . m2         orientation FF (EPIK_AMD_MATES_FF)
+ * The placement of the pair is the placement of J: rows, n_rows, k-mer counts and LWRs as epik_amd_placer_place gives
+ * them for the string J.  Windows that contain sep are skipped as windows over any invalid character are, so every
+ * branch receives the log-scores of both mates' k-mers, mate 1's first, in k-mer order.
+ *   sep     '-' when its class in the handle's table is 0, else the smallest byte of class 0 (none:
+ *           EPIK_AMD_ERR_UNSUPPORTED); mates_separator reports it, so that callers build the same J.
+ *   Strand  rc(m1 . sep . rc(m2)) = m2 . sep . rc(m1): the reverse strand of J is the pair with its mates swapped.  The
+ *           strand modes apply to J unchanged -- FORWARD: mate 1 lies on the database's strand; REVERSE; BOTH with the
+ *           rule and tie-break of place_strands -- and strand[i] is 0 / 1 per pair.
+ *   Consequences.  num_of_kmers is len(J) - k + 1 (place.cpp:322), which counts the k windows over sep as missing
+ *           k-mers: every score of a pair is lower by exactly one log_threshold than the sum of its mates' evidence
+ *           would give -- the same constant on every branch; ranking and LWRs do not depend on it.  A pair whose
+ *           mates are both shorter than k while len(J) >= k comes back as a read without hits (fabricated rows, k-mer
+ *           counts 0: no_hit in a profile), not with n_rows 0.  Mates that overlap count the shared k-mers twice.
+ * The batch is ONE interleaved batch in the layout of reads: seqs + uint64 seq_offsets[2 n + 1], read 2 i = mate 1 and
+ * read 2 i + 1 = mate 2 of pair i.  n counts pairs; rows [n][keep], n_rows [n], k-mer counts [n][keep] and strand [n]
+ * are per pair.  mode = a strand mode (EPIK_AMD_STRAND_*) in the low byte, | EPIK_AMD_MATES_FF for FF; any other bit:
+ * EPIK_AMD_ERR_INVALID.  Nucleotide handles of a whole database only (EPIK_AMD_ERR_UNSUPPORTED otherwise).
+ *
+ * place_mates_device: asynchronous on `stream`, never allocates.  seq_bytes = d_seq_offsets[2 n] - d_seq_offsets[0],
+ *   the characters of the batch; d_workspace (aligned to 8 bytes) of at least mates_workspace_bytes(n, seq_bytes, mode)
+ *   bytes, EPIK_AMD_ERR_INVALID when smaller: mate_join_kernel writes the joined sequences and their offsets
+ *   (seq_offsets[2 i] - seq_offsets[0] + i) there, place_strands_device places them.  A pair whose offsets lie outside
+ *   what seq_bytes says is not joined; nothing is written outside the workspace.  The count width is the caller's
+ *   (epik_amd_placer_choose_counts with the longest J, len1 + len2 + 1: 2 x 150 bp needs 16-bit counts); a pair
+ *   that does not fit comes back EPIK_AMD_ROWS_COUNTS_TOO_NARROW.  d_kmer_counts and d_strand may be NULL.  Row slots
+ *   past n_rows[i] keep what the caller's buffers held -- in BOTH, where the reverse strand wins, what the workspace
+ *   held: zero both beforehand to read zeros there, as place_mates does.
+ * place_mates: synchronous, host buffers; count width chosen from the batch's longest J as place() does, the handle's
+ *   count state left as place() leaves it; chunks of bounded size, by pairs, allocated and freed inside the call.
+ *   kmer_counts and strand may be NULL.
+ * profile_mates: place_mates with the rows left on the device and added to `profile` there (see below), pair i with
+ *   weights[i] (HOST uint32 [n], or NULL: 1): a fragment counts once.
+ */
+#define EPIK_AMD_MATES_FF 0x100u
+int epik_amd_placer_mates_separator(const epik_amd_placer *p, uint8_t *sep);
+/* bytes of device workspace place_mates_device needs for n_pairs pairs of seq_bytes characters in total */
+int epik_amd_placer_mates_workspace_bytes(const epik_amd_placer *p, uint64_t n_pairs, uint64_t seq_bytes,
+                                          uint32_t mode, uint64_t *bytes);
+int epik_amd_placer_place_mates_device(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offsets,
+                                       uint64_t n_pairs, uint64_t seq_bytes, uint32_t mode, void *d_workspace,
+                                       uint64_t workspace_bytes, void *d_rows, void *d_n_rows, void *d_kmer_counts,
+                                       void *d_strand, void *stream);
+int epik_amd_placer_place_mates(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n_pairs,
+                                uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                                uint8_t *strand);
+
+/*
  * Nucleotide reads placed on an amino-acid database through their translated frames.  No reference counterpart: the
  * reference places a read in the alphabet of its database (place.cpp:294).
  *   FORWARD  frames +1 +2 +3;  REVERSE  frames -1 -2 -3;  BOTH  all six.
@@ -455,9 +509,9 @@ int epik_amd_placer_place_frames(epik_amd_placer *p, const char *seqs, const uin
  *   reset       synchronises the device and zeroes the profile.
  *   info        num_branches, and whether add_device sums in LDS first (trees whose 16 * num_branches bytes fit: up to 10 236) or
  *               straight into global memory; EPIK_AMD_PROFILE_LDS=0|1, read at create(), forces either (tests).
- * profile_reads / _strands / _frames: place / place_strands / place_frames with the rows left on the device and added
- * to `profile` there -- nothing crosses back but the strand / frame byte per read (NULL: nothing at all).  weights:
- * uint32 [n] on the HOST, or NULL.  The profile must have been created for this placer's device and shape.  Whole
+ * profile_reads / _strands / _frames / _mates: place / place_strands / place_frames / place_mates with the rows left on
+ * the device and added to `profile` there -- nothing crosses back but the strand / frame byte per read or pair (NULL:
+ * nothing at all).  weights: uint32 [n] on the HOST, or NULL; profile_mates: n pairs, a weight per pair.  The profile must have been created for this placer's device and shape.  Whole
  * databases only.  Synchronous.
  */
 #define EPIK_AMD_PROFILE_LWR_BITS 30
@@ -484,6 +538,9 @@ int epik_amd_placer_profile_strands(epik_amd_placer *p, epik_amd_profile *profil
 int epik_amd_placer_profile_frames(epik_amd_placer *p, epik_amd_profile *profile, const char *seqs,
                                    const uint64_t *seq_offsets, const uint32_t *weights, uint64_t n, uint32_t mode,
                                    uint8_t *frame);
+int epik_amd_placer_profile_mates(epik_amd_placer *p, epik_amd_profile *profile, const char *seqs,
+                                  const uint64_t *seq_offsets, const uint32_t *weights, uint64_t n_pairs, uint32_t mode,
+                                  uint8_t *strand);
 
 /* Which kernels the last launch of this handle ran (reports; a large-tree handle falls back from the three-kernel
  * placement to the one-kernel one when the device has no room for the scratch of a launch). */
