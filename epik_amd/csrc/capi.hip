@@ -324,6 +324,11 @@ int create_impl(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t sh
     p->team = plan.layout == epik_amd::DbLayout::kTeam;
     const bool run_lists = image::run_counts_apply(plan, std::getenv("EPIK_AMD_RUN_COUNTS"));
     p->runs = run_lists ? epik_amd::kRunLists : plan.runs ? epik_amd::kRunsMixed : 0;
+    {
+        // the run-list ring's descriptors: near wherever the posting region allows it, unless "far" is asked for
+        const char *form = std::getenv("EPIK_AMD_RING_FORM");
+        p->ring_near = p->runs != 0 && plan.posting_bytes < epik_amd::kNearRegionBytes && !(form && std::strcmp(form, "far") == 0);
+    }
     p->db_bytes = plan.posting_bytes;
     CREATE_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     CREATE_TRY(hipStreamCreateWithFlags(&p->stream_in, hipStreamNonBlocking));
@@ -475,6 +480,17 @@ int create_impl(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t sh
             // + one trip of spare entries (the kernel prefetches a trip ahead)
             const uint32_t desc_bytes = epik_amd::kWaveDescBytes;
             g.lds_wave_bytes = epik_amd::wave_lds_bytes(pp.n_pad, counts);
+            // the run-list kernels (16- and 32-bit counts) with near descriptors: 64 slack rows instead of the clamp where
+            // they leave as many waves on a CU
+            if (p->ring_near) {
+                g.ring = epik_amd::kRingNear;
+                if (p->runs == epik_amd::kRunLists && counts != epik_amd::kCounts8 && epik_amd::wave_slack_is_free(pp.n_pad, counts) &&
+                    g.lds_wave_bytes + epik_amd::kWaveSlackBytes <= kMaxLdsPerBlock) {
+                    g.ring |= epik_amd::kRingSlack;
+                    g.lds_wave_bytes += epik_amd::kWaveSlackBytes;
+                }
+            }
+            const int runs = p->runs | g.ring;
             if (counts == epik_amd::kCounts8 && (pp.n_pad + 7u) / 8u > desc_bytes) {
                 g.max_blocks = 0;  // the 8-bit kernel keeps one flag bit per row in the descriptor area: no room
                 continue;
@@ -492,9 +508,9 @@ int create_impl(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t sh
             for (uint32_t wpb = 4; wpb >= 1; wpb >>= 1) {
                 const uint32_t block_bytes = wpb * g.lds_wave_bytes;
                 if (block_bytes > kMaxLdsPerBlock) continue;
-                CREATE_TRY(epik_amd::set_place_reads_lds_limit(p->layout, p->runs, counts, block_bytes));
+                CREATE_TRY(epik_amd::set_place_reads_lds_limit(p->layout, runs, counts, block_bytes));
                 int per_cu = 0;
-                CREATE_TRY(epik_amd::place_reads_occupancy(p->layout, p->runs, counts, (int)(wpb * 64u), block_bytes, &per_cu));
+                CREATE_TRY(epik_amd::place_reads_occupancy(p->layout, runs, counts, (int)(wpb * 64u), block_bytes, &per_cu));
                 const uint32_t lds_units = (block_bytes + epik_amd::kLdsGranule - 1u) / epik_amd::kLdsGranule;
                 per_cu = std::min<int>(per_cu, (int)(128u / std::max(lds_units, 1u)));
                 if (per_cu < 1) per_cu = 1;
@@ -506,7 +522,7 @@ int create_impl(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t sh
                 }
             }
             g.resident_waves = best_waves;
-            CREATE_TRY(epik_amd::set_place_reads_lds_limit(p->layout, p->runs, counts, g.lds_block_bytes));
+            CREATE_TRY(epik_amd::set_place_reads_lds_limit(p->layout, runs, counts, g.lds_block_bytes));
             CREATE_TRY(epik_amd::set_finish_reads_lds_limit(counts, g.lds_block_bytes));
         }
     }
@@ -970,7 +986,7 @@ static int launch(epik_amd_placer *p, launch_mode mode, const void *d_seqs, cons
         HIP_TRY(epik_amd::launch_finish_reads(pp, p->counts, dim3((unsigned)blocks), dim3(g.waves_per_block * 64u),
                                               g.lds_block_bytes, stream));
     } else {
-        HIP_TRY(epik_amd::launch_place_reads(pp, p->layout, p->runs, p->counts, dim3((unsigned)blocks),
+        HIP_TRY(epik_amd::launch_place_reads(pp, p->layout, p->runs | p->geo[p->counts].ring, p->counts, dim3((unsigned)blocks),
                                              dim3(g.waves_per_block * 64u), g.lds_block_bytes, stream));
     }
     if (timed) {
@@ -1114,6 +1130,15 @@ int epik_amd_placer_run_counts(const epik_amd_placer *p, uint32_t counts, uint32
     if (!p || !lists) return fail(EPIK_AMD_ERR_INVALID, "null argument");
     if (counts > (uint32_t)epik_amd::kCounts32) return fail(EPIK_AMD_ERR_INVALID, "counts must be 0, 1 or 2");
     *lists = !p->team && p->runs == epik_amd::kRunLists && counts != (uint32_t)epik_amd::kCounts8;
+    return EPIK_AMD_OK;
+}
+
+int epik_amd_placer_ring_form(const epik_amd_placer *p, uint32_t counts, uint32_t *form)
+{
+    if (!p || !form) return fail(EPIK_AMD_ERR_INVALID, "null argument");
+    if (counts > (uint32_t)epik_amd::kCounts32) return fail(EPIK_AMD_ERR_INVALID, "counts must be 0, 1 or 2");
+    const int ring = p->team ? 0 : p->geo[counts].ring;
+    *form = ((ring & epik_amd::kRingNear) ? EPIK_AMD_RING_NEAR : 0u) | ((ring & epik_amd::kRingSlack) ? EPIK_AMD_RING_SLACK : 0u);
     return EPIK_AMD_OK;
 }
 

@@ -52,12 +52,16 @@ constexpr uint32_t wave_lds_bytes(uint32_t n_pad, int counts)
 {
     return (n_pad * (4u + (1u << counts)) + kWaveDescBytes + 15u) & ~15u;
 }
+// ... and, a term of its own, the 64 slack rows the run-list ring may keep behind the score vector (place_device.hpp:
+// RunListLayout, kSlackRows): a lane behind a chunk's end then adds its +0.0 to row first + lane as it is, unclamped
+constexpr uint32_t kWaveSlackBytes = 64u * 4u;
 // Resident waves per CU of those kernels: workgroups of 4, 2 or 1 independent waves, whichever keeps most
-constexpr uint32_t wave_kernel_resident_waves(uint32_t n_pad, int counts)
+// (extra: bytes a wave takes on top of wave_lds_bytes)
+constexpr uint32_t wave_kernel_resident_waves(uint32_t n_pad, int counts, uint32_t extra = 0)
 {
     uint32_t best = 0;
     for (uint32_t wpb = 4; wpb >= 1; wpb >>= 1) {
-        const uint32_t block = wpb * wave_lds_bytes(n_pad, counts);
+        const uint32_t block = wpb * (wave_lds_bytes(n_pad, counts) + extra);
         if (block > kLdsPerCu) continue;
         const uint32_t units = (block + kLdsGranule - 1) / kLdsGranule;
         uint32_t blocks = 128u / (units ? units : 1u);
@@ -66,6 +70,21 @@ constexpr uint32_t wave_kernel_resident_waves(uint32_t n_pad, int counts)
     }
     return best;
 }
+
+// The slack rows are taken only where they cost no wave: N = 999 with 16-bit counts, 4 x (7 744 + 256) B = the 25 granules
+// the workgroup occupies anyway; N = 1 199 would go from 18 waves a CU to 16 and keeps the clamp.
+constexpr bool wave_slack_is_free(uint32_t n_pad, int counts)
+{
+    return wave_kernel_resident_waves(n_pad, counts, kWaveSlackBytes) == wave_kernel_resident_waves(n_pad, counts);
+}
+static_assert(wave_kernel_resident_waves(1024, kCounts16, kWaveSlackBytes) == 20 && wave_slack_is_free(1024, kCounts32),
+              "N = 999: the slack rows fit the granules the workgroup occupies");
+static_assert(wave_kernel_resident_waves(1216, kCounts16) == 18 && wave_kernel_resident_waves(1216, kCounts16, kWaveSlackBytes) == 16 &&
+                  wave_kernel_resident_waves(1216, kCounts32) == 14 && wave_kernel_resident_waves(1216, kCounts32, kWaveSlackBytes) == 12,
+              "N = 1 199: the slack rows would cost two waves a CU");
+// The near descriptors of the run-list ring address a chunk by its 32-bit byte offset in the posting region, and the
+// last lane of the last chunk reads at offset + 252: regions shorter than this many bytes
+constexpr uint64_t kNearRegionBytes = (1ull << 32) - 256u;
 
 // ---- team kernel ---------------------------------------------------------------------------------
 #ifndef EPIK_AMD_TEAM_RING

@@ -23,7 +23,16 @@ team_stream.hip) for the two hazards hipcc cannot see.
    Checked for every buffer load, walking back over EVERY path of the control-flow graph (through the compiler's
    basic-block labels as well as the local labels of an asm statement).
 
+The run-list ring (place_device.hpp: RunListLayout, near form) keeps ONE buffer resource for the whole launch: its
+words 0, 1 and 3 are loop-invariant scalar registers, a stage writes word 2 with a scalar instruction and hands the
+chunk's byte offset to the load as its SGPR offset operand, straight out of v_readlane -- hazard 2 covers that operand
+like the resource's words.  An `.if A == B` ... `.endif` of literals inside an asm statement (the s_nop of
+Layout::issue<kSettled>) is evaluated as the assembler does: a line it drops is not an instruction.
+
 Usage: lint_ring_asm.py place_kernel.s
+       lint_ring_asm.py --stages place_kernel.s [kernel-name regex]
+           the ring loop's stages, counted: per kernel, the instructions between consecutive ring loads of the loop
+           by class (tests/test_ring_stage_cpu.py holds the headline kernel to its budget with ring_stages())
 """
 import re
 import sys
@@ -83,6 +92,7 @@ class Code:
         self.label_at = {}  # label -> index of the instruction behind it
         pending = []
         asm = False
+        dropped = []        # open .if blocks: True where the assembler drops the lines
         for n, raw in enumerate(body):
             t = raw.strip()
             if t.startswith(";;#ASMSTART"):
@@ -90,6 +100,19 @@ class Code:
             elif t.startswith(";;#ASMEND"):
                 asm = False
             if not t or t.startswith((";", "//")):
+                continue
+            m = re.match(r"\.if\s+(-?\d+)\s*(==|!=)\s*(-?\d+)\s*$", t)
+            if m:
+                dropped.append((int(m.group(1)) == int(m.group(3))) != (m.group(2) == "=="))
+                continue
+            if t.startswith(".if"):
+                dropped.append(False)   # (a condition the lint cannot evaluate: keep the lines, the stricter reading for counts)
+                continue
+            if t.startswith(".endif"):
+                if dropped:
+                    dropped.pop()
+                continue
+            if any(dropped):
                 continue
             m = re.match(r"([.\w$]+):", t)
             if m and not t.startswith(("s_", "v_", "ds_", "buffer_", "global_", "flat_", "scratch_")):
@@ -239,6 +262,66 @@ def lint_settled(name, body, problems):
             problems.append(f"{name}: line {line}: {op} reads s{found[0]} {found[1]} wait state(s) behind `{found[2]}` (needs 5)")
 
 
+def classify(op):
+    """The issue class of an instruction, as the stage budget counts them."""
+    if op == "s_waitcnt":
+        return "wait"
+    if op == "s_nop":
+        return "nop"
+    if op.startswith(("s_branch", "s_cbranch", "s_setpc", "s_swappc", "s_call", "s_endpgm")):
+        return "branch"
+    if op.startswith("s_"):
+        return "salu"
+    if op.startswith("ds_"):
+        return "lds"
+    if op.startswith(("buffer_", "global_", "flat_", "scratch_")):
+        return "vmem"
+    if op.startswith("v_"):
+        return "valu"
+    return "other"
+
+
+def ring_stages(path, kernel_re):
+    """The steady-state stages of the ring loops of every kernel whose name matches: {kernel: [loop, ...]}, a loop being
+    the list of its gaps -- one dict per pair of consecutive asm-issued buffer loads of the loop body in program order,
+    {"total": n, class: n, ..., "ops": [...]} over the instructions strictly between them.  A ring loop is an innermost
+    backward branch whose body holds at least two asm-issued buffer loads (the first trip and the tail are straight-line
+    code, not loops; the gap across the back edge, which holds the trip's own bookkeeping and the branch, is not a
+    stage).  Also returned per kernel: its scratch bytes (.amdhsa_private_segment_fixed_size), None when not found."""
+    text = open(path).read()
+    scratch = {m.group(1): int(m.group(2)) for m in
+               re.finditer(r"\.amdhsa_kernel (\S+).*?\.amdhsa_private_segment_fixed_size\s+(\d+)", text, re.S)}
+    out = {}
+    for name, body in kernels(text.split("\n")):
+        if not re.search(kernel_re, name):
+            continue
+        code = Code(body)
+        loops = []
+        for k, (_, t) in enumerate(code.ins):
+            op, rest = operands_of(t)
+            if op.startswith(("s_branch", "s_cbranch")):
+                target = code.label_at.get(rest.split()[-1]) if rest else None
+                if target is not None and target <= k:
+                    loops.append((target, k))
+        found = []
+        for a, b in loops:
+            if any((c, d) != (a, b) and a <= c and d <= b for c, d in loops):
+                continue  # not innermost
+            loads = [k for k in range(a, b + 1) if code.in_asm[k] and operands_of(code.ins[k][1])[0].startswith("buffer_load_")]
+            if len(loads) < 2:
+                continue
+            gaps = []
+            for x, y in zip(loads, loads[1:]):
+                ops = [operands_of(code.ins[k][1])[0] for k in range(x + 1, y)]
+                gap = {"total": len(ops), "ops": ops}
+                for op in ops:
+                    gap[classify(op)] = gap.get(classify(op), 0) + 1
+                gaps.append(gap)
+            found.append(gaps)
+        out[name] = {"loops": found, "scratch": scratch.get(name)}
+    return out
+
+
 def lint(path):
     problems = []
     linted = 0
@@ -255,6 +338,13 @@ def lint(path):
 
 
 if __name__ == "__main__":
+    if sys.argv[1] == "--stages":
+        for kernel, what in ring_stages(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else "place_reads_kernel").items():
+            for gaps in what["loops"]:
+                print(kernel, f"scratch {what['scratch']}:", f"{len(gaps) + 1} loads;",
+                      "; ".join(" ".join(f"{k} {v}" for k, v in g.items() if k != "ops") for g in gaps[:1]),
+                      "| totals", [g["total"] for g in gaps])
+        sys.exit(0)
     out = lint(sys.argv[1])
     for p in out[:40]:
         print("LINT:", p)

@@ -193,11 +193,12 @@ struct CompactLayout {
     // what lookup() returns as `len` is the list's length and nothing else
     __device__ static __forceinline__ uint32_t length(uint32_t w) { return w; }
     // the descriptor of chunk c (`cnt` postings) of the list at byte offset `addr`
-    __device__ static __forceinline__ uint64_t descriptor(const PlaceParams &p, uint64_t addr, uint32_t /*w*/, uint32_t c, uint64_t cnt)
+    __device__ static __forceinline__ uint64_t descriptor(const PlaceParams &p, uint64_t addr, uint32_t /*w*/, uint32_t c, uint64_t cnt,
+                                                          uint32_t /*score_row0*/)
     {
         return (uint64_t)(p.postings + addr + (uint64_t)c * kChunkBytes) | (cnt << 48);
     }
-    __device__ static __forceinline__ uint64_t null_descriptor(const PlaceParams &p) { return (uint64_t)p.postings; }
+    __device__ static __forceinline__ uint64_t null_descriptor(const PlaceParams &p, uint32_t /*score_row0*/) { return (uint64_t)p.postings; }
     __device__ static __forceinline__ void lookup(const PlaceParams &p, uint32_t key, uint32_t /*position*/,
                                                   uint64_t &addr, uint32_t &len)
     {
@@ -222,7 +223,7 @@ struct CompactLayout {
     // kSettled: the caller has put five instructions or more between the v_readlane that made `f` and this
     // statement (stream_round's stages; lint_ring_asm.py checks the distance in the ISA)
     template <bool kSettled = false>
-    __device__ static __forceinline__ void issue(const uint32_t (&f)[kFields], uint32_t lane, uint32_t &cell,
+    __device__ static __forceinline__ void issue(const PlaceParams &, const uint32_t (&f)[kFields], uint32_t lane, uint32_t &cell,
                                                  uint32_t &score)
     {
         const v4i srd = {(int)f[0], (int)f[1], (int)f[2], kRawBufferFormat};
@@ -274,8 +275,13 @@ struct CompactLayout {
 // dummy row, never a posting's).  A list of 60 postings takes two 128-byte lines instead of three: a third fewer
 // lines requested per read, which is what bounds these kernels.
 enum : int { kPlainTable = 0, kPairedTable = 1, kFilteredTable = 2 };
-template <int kTable, bool kRuns = false>
+// kNearRuns (run-coded layouts over a posting region shorter than kNearRegionBytes, chosen at create() with the near form
+// of RunListLayout below): the chunk descriptor is the chunk's byte offset from p.postings | (cnt | first cell << 7) << 32,
+// two words a stage pulls out of the lanes instead of three prepared fields; the offset is the loads' scalar offset
+// under one buffer resource for the launch, whose third word a stage sets to offset + the chunk's bytes.
+template <int kTable, bool kRuns = false, bool kNearRuns = false>
 struct PackedLayout {
+    static_assert(kRuns || !kNearRuns, "near descriptors: the run-coded layouts");
     static constexpr int kLoads = 2;
     // kRuns: a run chunk is ONE load (its scores), a chunk with explicit cells two -- the cells FIRST, so that the
     // scores' arrival says both are there (loads return in order).  The ring waits for "at most N younger loads in
@@ -284,22 +290,24 @@ struct PackedLayout {
     static constexpr int kWaitLoads = kRuns ? 1 : 2;
     static constexpr uint32_t kChunkBytes = 64u * 6u;
     // kRuns: base lo, base hi, postings in the chunk | the chunk's first cell << 7; else the descriptor's two words
-    static constexpr int kFields = kRuns ? 3 : 2;
+    static constexpr int kFields = kRuns && !kNearRuns ? 3 : 2;
     __device__ static __forceinline__ uint32_t length(uint32_t w) { return kRuns ? (w & 0xffffu) : w; }
     // kRuns: byte offset / 2 from the start of the posting region (37 bits: 256 GiB) | cnt << 37 | first cell of the
     // chunk << 44 (0: explicit cells); else the chunk's address | cnt << 48
-    __device__ static __forceinline__ uint64_t descriptor(const PlaceParams &p, uint64_t addr, uint32_t w, uint32_t c, uint64_t cnt)
+    __device__ static __forceinline__ uint64_t descriptor(const PlaceParams &p, uint64_t addr, uint32_t w, uint32_t c, uint64_t cnt,
+                                                          uint32_t /*score_row0*/)
     {
         if constexpr (kRuns) {
             const uint32_t first_cell = w >> 16;
             const uint64_t at = addr + (uint64_t)c * (first_cell ? 256u : kChunkBytes);
             const uint64_t cell = first_cell ? (uint64_t)(first_cell - (c << 6)) : 0ull;  // the run goes down the cells
+            if constexpr (kNearRuns) return (uint64_t)(uint32_t)at | ((cnt | (cell << 7)) << 32);
             return (at >> 1) | (cnt << 37) | (cell << 44);
         } else {
             return (uint64_t)(p.postings + addr + (uint64_t)c * kChunkBytes) | (cnt << 48);
         }
     }
-    __device__ static __forceinline__ uint64_t null_descriptor(const PlaceParams &p) { return kRuns ? 0ull : (uint64_t)p.postings; }
+    __device__ static __forceinline__ uint64_t null_descriptor(const PlaceParams &p, uint32_t /*score_row0*/) { return kRuns ? 0ull : (uint64_t)p.postings; }
     // by code alone (the cold paths; the filter only saves traffic, the table is complete)
     __device__ static __forceinline__ void lookup(const PlaceParams &p, uint32_t key, uint32_t position,
                                                   uint64_t &addr, uint32_t &len)
@@ -339,7 +347,11 @@ struct PackedLayout {
     }
     __device__ static __forceinline__ void prepare(const PlaceParams &p, uint64_t d, uint32_t (&f)[kFields])
     {
-        if constexpr (kRuns) {
+        if constexpr (kNearRuns) {
+            (void)p;
+            f[0] = (uint32_t)d;          // byte offset
+            f[1] = (uint32_t)(d >> 32);  // cnt (7 bits) | first cell << 7
+        } else if constexpr (kRuns) {
             const uint64_t a = (uint64_t)p.postings + ((d & ((1ull << 37) - 1ull)) << 1);
             f[0] = (uint32_t)a;
             f[1] = (uint32_t)(a >> 32) & 0xffffu;
@@ -357,11 +369,36 @@ struct PackedLayout {
     // reads cell 0 (and, up to lane 1.5*cnt, a score made of cell bytes that lands on the dummy row).
     // (kSettled: see CompactLayout::issue)
     template <bool kSettled = false>
-    __device__ static __forceinline__ void issue(const uint32_t (&f)[kFields], uint32_t lane, uint32_t &cell,
+    __device__ static __forceinline__ void issue(const PlaceParams &p, const uint32_t (&f)[kFields], uint32_t lane, uint32_t &cell,
                                                  uint32_t &score)
     {
+        (void)p;
         // f[2] sits in a scalar register (v_readlane): the products are scalar instructions
-        if constexpr (kRuns) {
+        if constexpr (kNearRuns) {
+            // (words 0, 1 and 3 of the resource are the launch's; the explicit arm forms the cells' scalar offset,
+            // offset + 4 * cnt, itself: the run arm does not pay for it)
+            const uint32_t cnt = f[1] & 127u, first_cell = f[1] >> 7;
+            const uint64_t region = (uint64_t)p.postings;
+            const v4i srd = {(int)(uint32_t)region, (int)((uint32_t)(region >> 32) & 0xffffu),
+                             (int)(f[0] + cnt * (first_cell ? 4u : 6u)), kRawBufferFormat};
+            uint32_t cells_at;
+            asm volatile(".if %10 == 0\n\ts_nop 4\n\t.endif\n\t"
+                         "s_cmp_eq_u32 %6, 0\n\t"
+                         "s_cbranch_scc1 .Lexplicit%=\n\t"
+                         "buffer_load_dword %0, %3, %5, %9 offen\n\t"
+                         "v_sub_u32 %1, %6, %7\n\t"
+                         "v_cmp_gt_u32 vcc, %8, %7\n\t"
+                         "v_cndmask_b32 %1, 0, %1, vcc\n\t"
+                         "s_branch .Lissued%=\n"
+                         ".Lexplicit%=:\n\t"
+                         "s_lshl2_add_u32 %2, %8, %9\n\t"
+                         "buffer_load_ushort %1, %4, %5, %2 offen\n\t"
+                         "buffer_load_dword %0, %3, %5, %9 offen\n"
+                         ".Lissued%=:"
+                         : "=&v"(score), "=&v"(cell), "=&s"(cells_at)
+                         : "v"(lane * 4u), "v"(lane * 2u), "s"(srd), "s"(first_cell), "v"(lane), "s"(cnt), "s"(f[0]), "n"(kSettled ? 1 : 0)
+                         : "memory", "vcc", "scc");
+        } else if constexpr (kRuns) {
             // A run (first cell != 0): the cells are first_cell, first_cell - 1, ... down the lanes -- nothing to
             // fetch for them; the lanes behind the chunk's end get cell 0, the dummy row, as a load past the end
             // would give them.
@@ -421,46 +458,109 @@ struct PackedLayout {
 // into counts when the read's exact k-mers are streamed (materialize_counts) -- integer adds commute, only the float32
 // score adds need the k-mer order.  The ring then carries scores only (stream_round_lists): no cells to fetch, no
 // explicit-cell arm, one load per chunk, and a stage is an LDS read, an add and an LDS write.
-// Descriptor: the chunk's 128-byte line relative to p.postings (the region has fewer than 2^32 lines,
-// db_image.cpp) | (postings in the chunk | its first row << 7) << 32.
-template <int kTable>
+//
+// The chunk descriptor comes in two forms, chosen at create() (capi.hip; EPIK_AMD_RING_FORM=near|far forces one).
+// FAR (any posting region): the chunk's 128-byte line relative to p.postings (the region has fewer than 2^32 lines,
+// db_image.cpp) | (postings in the chunk | its first row << 7) << 32 -- a stage forms the chunk's address, the buffer
+// resource over it and the row's LDS address with nine scalar instructions.
+// NEAR (a posting region shorter than 2^32 - 256 bytes, kNearRegionBytes): everything a stage would derive is written
+// down by the descriptor pass, 64 chunks per vector instruction:
+//     word 0 = the chunk's byte offset from p.postings -- the refill's SCALAR OFFSET as it leaves v_readlane,
+//     word 1 = cnt * 4 (9 bits) | the LDS byte address of the chunk's first row in THIS wave's score vector << 9
+//              (an LDS address is below 160 KiB: 18 bits).
+// One buffer resource serves the whole launch: base p.postings, and only its third word, the number of bytes, is set
+// per chunk, to offset + cnt * 4.  The scalar offset takes part in the range check (tools/probe_buffer.hip, variant 3;
+// the explicit-cell arm above relies on it too), so lane l reads score l of the chunk when 4 l < cnt * 4 and +0.0
+// otherwise; offset + 4 * 63 + 4 never wraps because the region ends 256 bytes short of 2^32.  A stage is left with
+// three scalar instructions: cnt * 4 (s_and_b32), the resource's bytes (s_add), the row's address (s_lshr_b32).
+// A null descriptor is offset 0, cnt 0 -- a buffer of zero bytes that touches no memory -- and carries the wave's own
+// first row: row 0 of LDS belongs to another wave.
+//
+// kSlackRows (near form only; capi.hip takes them where 256 bytes more a wave leave as many waves on a CU, db_layout.h:
+// wave_slack_is_free): 64 slack rows lie behind the wave's score vector, cleared with it at workgroup start and never
+// written with anything but x + +0.0.  A lane's row is then first row + lane with no clamp to the dummy row: the
+// lanes behind a chunk's end add +0.0 to the rows that follow the chunk, real ones or slack.
+template <int kTable, bool kNearForm = false, bool kSlackRows = false>
 struct RunListLayout : PackedLayout<kTable, true> {
+    static_assert(kNearForm || !kSlackRows, "the slack rows come with the near descriptors");
     static constexpr bool kListCounts = true;
+    static constexpr bool kNear = kNearForm;
+    static constexpr uint32_t kSlackBytes = kSlackRows ? kWaveSlackBytes : 0u;
     static constexpr int kWaitLoads = 1;
     static constexpr int kFields = 2;
-    __device__ static __forceinline__ uint64_t descriptor(const PlaceParams &p, uint64_t addr, uint32_t w, uint32_t c, uint64_t cnt)
+    // (score_row0: the LDS byte address of row 0 of the wave's score vector)
+    __device__ static __forceinline__ uint64_t descriptor(const PlaceParams &p, uint64_t addr, uint32_t w, uint32_t c, uint64_t cnt,
+                                                          uint32_t score_row0)
     {
         // (a run's chunk c is 64 scores, two lines, from the list's first; its rows ascend from the list's first row)
-        const uint32_t line = (uint32_t)(addr >> 7) + 2u * c;
         const uint32_t row = p.n_pad - 1u - (w >> 16) + (c << 6);
-        return (uint64_t)line | ((uint64_t)((uint32_t)cnt | (row << 7)) << 32);
+        if constexpr (kNear) {
+            const uint32_t offset = (uint32_t)addr + 256u * c;
+            return (uint64_t)offset | ((uint64_t)(((uint32_t)cnt << 2) | ((score_row0 + (row << 2)) << 9)) << 32);
+        } else {
+            const uint32_t line = (uint32_t)(addr >> 7) + 2u * c;
+            return (uint64_t)line | ((uint64_t)((uint32_t)cnt | (row << 7)) << 32);
+        }
     }
-    // (no postings: every lane loads the +0.0 of an empty buffer, added to rows 0..63 or the dummy row)
-    __device__ static __forceinline__ uint64_t null_descriptor(const PlaceParams &) { return 0ull; }
+    // (no postings: every lane loads the +0.0 of an empty buffer, added to the wave's rows 0..63 or its dummy row)
+    __device__ static __forceinline__ uint64_t null_descriptor(const PlaceParams &, uint32_t score_row0)
+    {
+        return kNear ? (uint64_t)(score_row0 << 9) << 32 : 0ull;
+    }
     __device__ static __forceinline__ void prepare(const PlaceParams &, uint64_t d, uint32_t (&f)[kFields])
     {
         f[0] = (uint32_t)d;
         f[1] = (uint32_t)(d >> 32);
     }
-    // The refill of a slot: the chunk's scores, and the LDS address of the lane's row, min(row0 + lane, dummy row).
+    // The refill of a slot: the chunk's scores, and the LDS address of the lane's row -- row0 + lane, clamped to the
+    // dummy row unless the slack rows are there.
     // f[] sits in scalar registers (v_readlane): the buffer resource and the row's address are scalar instructions.
     template <bool kSettled = false>
     __device__ static __forceinline__ void issue(const PlaceParams &p, const uint32_t (&f)[kFields], uint32_t lane4,
                                                  uint32_t score_row0, uint32_t score_top, uint32_t &addr, uint32_t &score)
     {
-        const uint64_t a = (uint64_t)p.postings + ((uint64_t)f[0] << 7);
-        const uint32_t cnt = f[1] & 127u;
-        const uint32_t base = score_row0 + ((f[1] >> 7) << 2);
-        const v4i srd = {(int)(uint32_t)a, (int)((uint32_t)(a >> 32) & 0xffffu), (int)(cnt * 4u), kRawBufferFormat};
-        asm volatile(".if %6 == 0\n\ts_nop 4\n\t.endif\n\t"
-                     "buffer_load_dword %0, %2, %3, 0 offen\n\t"
-                     "v_add_u32 %1, %4, %2\n\t"
-                     "v_min_u32 %1, %5, %1"
-                     : "=&v"(score), "=&v"(addr)
-                     : "v"(lane4), "s"(srd), "s"(base), "s"(score_top), "n"(kSettled ? 1 : 0)
-                     : "memory");
+        if constexpr (kNear) {
+            // (words 0, 1 and 3 are the same for every chunk of the launch: the compiler keeps them where they are and
+            // a stage writes word 2 alone)
+            const uint64_t region = (uint64_t)p.postings;
+            const uint32_t cnt4 = f[1] & 0x1ffu;
+            const uint32_t base = f[1] >> 9;
+            const v4i srd = {(int)(uint32_t)region, (int)((uint32_t)(region >> 32) & 0xffffu), (int)(f[0] + cnt4), kRawBufferFormat};
+            if constexpr (kSlackRows)
+                asm volatile(".if %6 == 0\n\ts_nop 4\n\t.endif\n\t"
+                             "buffer_load_dword %0, %2, %3, %4 offen\n\t"
+                             "v_add_u32 %1, %5, %2"
+                             : "=&v"(score), "=&v"(addr)
+                             : "v"(lane4), "s"(srd), "s"(f[0]), "s"(base), "n"(kSettled ? 1 : 0)
+                             : "memory");
+            else
+                asm volatile(".if %7 == 0\n\ts_nop 4\n\t.endif\n\t"
+                             "buffer_load_dword %0, %2, %3, %4 offen\n\t"
+                             "v_add_u32 %1, %5, %2\n\t"
+                             "v_min_u32 %1, %6, %1"
+                             : "=&v"(score), "=&v"(addr)
+                             : "v"(lane4), "s"(srd), "s"(f[0]), "s"(base), "s"(score_top), "n"(kSettled ? 1 : 0)
+                             : "memory");
+        } else {
+            const uint64_t a = (uint64_t)p.postings + ((uint64_t)f[0] << 7);
+            const uint32_t cnt = f[1] & 127u;
+            const uint32_t base = score_row0 + ((f[1] >> 7) << 2);
+            const v4i srd = {(int)(uint32_t)a, (int)((uint32_t)(a >> 32) & 0xffffu), (int)(cnt * 4u), kRawBufferFormat};
+            asm volatile(".if %6 == 0\n\ts_nop 4\n\t.endif\n\t"
+                         "buffer_load_dword %0, %2, %3, 0 offen\n\t"
+                         "v_add_u32 %1, %4, %2\n\t"
+                         "v_min_u32 %1, %5, %1"
+                         : "=&v"(score), "=&v"(addr)
+                         : "v"(lane4), "s"(srd), "s"(base), "s"(score_top), "n"(kSettled ? 1 : 0)
+                         : "memory");
+        }
     }
 };
+// the slack rows a layout keeps behind the score vector, in bytes (RunListLayout with kSlackRows; every other layout none)
+template <typename Layout, typename = void>
+struct SlackBytes : std::integral_constant<uint32_t, 0u> {};
+template <typename Layout>
+struct SlackBytes<Layout, std::void_t<decltype(Layout::kSlackBytes)>> : std::integral_constant<uint32_t, Layout::kSlackBytes> {};
 template <typename Layout, typename = void>
 struct ListCounts : std::false_type {};
 template <typename Layout>
@@ -562,12 +662,13 @@ struct WaveLds {
     f32_t *score;    // [n_pad]
     count_t *count;  // [n_pad]
     u64_t *desc;     // [kTilesPerPass * 64 + kRing]
-    // carves the three arrays out of `base` (16-byte aligned, generic pointer into the kernel's LDS)
-    __device__ __forceinline__ void carve(unsigned char *base, uint32_t n_pad)
+    // carves the three arrays out of `base` (16-byte aligned, generic pointer into the kernel's LDS); slack_bytes: the
+    // slack rows between the score vector and the counts (RunListLayout with kSlackRows: 256, a multiple of 16; else 0)
+    __device__ __forceinline__ void carve(unsigned char *base, uint32_t n_pad, uint32_t slack_bytes = 0)
     {
         score = (f32_t *)reinterpret_cast<float *>(base);
-        count = (count_t *)reinterpret_cast<CountT *>(base + (size_t)n_pad * 4);
-        desc = (u64_t *)reinterpret_cast<uint64_t *>(base + (size_t)n_pad * (4 + sizeof(CountT)));
+        count = (count_t *)reinterpret_cast<CountT *>(base + (size_t)n_pad * 4 + slack_bytes);
+        desc = (u64_t *)reinterpret_cast<uint64_t *>(base + (size_t)n_pad * (4 + sizeof(CountT)) + slack_bytes);
     }
     __device__ __forceinline__ uint2 load(uint32_t i) const
     {
@@ -758,7 +859,7 @@ __device__ __forceinline__ void stream_round(const PlaceParams &p, const typenam
             uint32_t f[Layout::kFields];
 #pragma unroll
             for (int q = 0; q < Layout::kFields; ++q) f[q] = __builtin_amdgcn_readlane(field[q], i);
-            Layout::issue(f, (uint32_t)lane, ring_c[i], ring_s[i]);
+            Layout::issue(p, f, (uint32_t)lane, ring_c[i], ring_s[i]);
         }
         // slot 0 is the oldest of the kDepth in flight
         addresses(ring_c[0], std::integral_constant<int, Layout::kWaitLoads *(kDepth - 1)>{}, sa, ca, score_top, count_top);
@@ -785,7 +886,7 @@ __device__ __forceinline__ void stream_round(const PlaceParams &p, const typenam
                     addresses(ring_c[(i + 1) % kDepth], std::integral_constant<int, Layout::kWaitLoads *(kDepth - 2)>{}, sa_next, ca_next, score_top,
                               count_top);
                 },
-                [&]() { Layout::template issue<true>(f, (uint32_t)lane, ring_c[i], ring_s[i]); });
+                [&]() { Layout::template issue<true>(p, f, (uint32_t)lane, ring_c[i], ring_s[i]); });
             sa = sa_next, ca = ca_next;
         }
     }
@@ -817,8 +918,9 @@ __device__ __forceinline__ void stream_round(const PlaceParams &p, const typenam
 // scores, in flight, and the LDS address of the lane's row, computed when the slot is refilled -- it needs no load.
 // A stage: LDS read of the row, the refill's descriptor words out of the lanes, the wait for the slot (the oldest
 // of the kDepth in flight), the add, the LDS write, the refill.
-// Lanes past the chunk's end load +0.0 (the buffer's range check) and add it to row row0 + lane, clamped to the dummy
-// row: a real row, another branch's, keeps its bits, because a row cleared to +0.0 never holds -0.0 under
+// Lanes past the chunk's end load +0.0 (the buffer's range check) and add it to row row0 + lane -- clamped to the dummy
+// row, or, where the layout keeps 64 slack rows behind the vector, as it is: the slack holds +0.0 and receives nothing
+// but +0.0.  A real row, another branch's, keeps its bits, because a row cleared to +0.0 never holds -0.0 under
 // round-to-nearest adds (x + y is -0.0 only if both are -0.0, or x + -x rounded downwards), and x + +0.0 == x for
 // every x that is not -0.0.  The rows of one instruction are distinct but for the dummy row, where every lane
 // writes the same +0.0 sum.

@@ -51,7 +51,7 @@ struct PlaceParams {
     uint32_t max_kmers_cap;          // != 0: a read with more k-mers than this is not placed whatever the LDS counts hold
                                      // (the uint16 counts of the dense partial vectors: 65535)
     uint32_t n_pad;                  // LDS rows per wave: num_branches + the dummy row, rounded up to 64
-    uint32_t lds_wave_bytes;         // LDS bytes per wave (scores + counts + chunk descriptors)
+    uint32_t lds_wave_bytes;         // LDS bytes per wave (scores + slack rows, if any, + counts + chunk descriptors)
     uint32_t ablate;                 // timing experiments only (-DEPIK_AMD_ABLATION builds)
     unsigned long long *dbg;         // phase cycle sums (-DEPIK_AMD_ABLATION builds, EPIK_AMD_STAMPS=1)
 };
@@ -170,8 +170,11 @@ hipError_t team_stream_occupancy(int waves, int counts, int mode, int bw, size_t
 hipError_t launch_team_algorithmic_bytes(const TeamParams &tp, int waves, unsigned long long *d_total, hipStream_t stream);
 
 // runs: 0 explicit cells, 1 (kRunsMixed) run-coded lists, kRunLists run-coded with every list a run and the counts
-// kept per list (16- and 32-bit counts; 8-bit counts take the run-coded kernel)
-enum : int { kRunsMixed = 1, kRunLists = 2 };
+// kept per list (16- and 32-bit counts; 8-bit counts take the run-coded kernel).  Flags on top of kRunLists, per count
+// width (placer_impl.hpp: geometry::ring): kRingNear -- the ring's chunk descriptors in their near form (posting regions
+// below 4 GB), kRingSlack -- with it, 64 slack rows behind the score vector instead of the clamp to the dummy row
+// (place_device.hpp: RunListLayout)
+enum : int { kRunsMixed = 1, kRunLists = 2, kRingNear = 4, kRingSlack = 8 };
 hipError_t launch_place_reads(const PlaceParams &p, DbLayout layout, int runs, int counts, dim3 grid, dim3 block,
                               size_t lds_bytes, hipStream_t stream);
 hipError_t set_place_reads_lds_limit(DbLayout layout, int runs, int counts, size_t lds_bytes);

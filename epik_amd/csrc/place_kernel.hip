@@ -37,15 +37,21 @@ __global__ __launch_bounds__(256, 5) void place_reads_kernel(PlaceParams p)
     WaveLds<CountT> lds;
     {
         unsigned char *base = lds_raw + (size_t)wave_in_block * p.lds_wave_bytes;
-        lds.carve(base, p.n_pad);
+        lds.carve(base, p.n_pad, SlackBytes<Layout>::value);
     }
-    // LDS byte addresses of the dummy row (cell 0) in the two vectors: row = n_pad - 1 - cell
+    // LDS byte addresses of row 0 of the score vector and of the dummy row (cell 0) in the two vectors: row = n_pad - 1 - cell
+    const uint32_t score_row0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds.score);
     const uint32_t score_top = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds.score + (p.n_pad - 1u) * 4u);
     const uint32_t count_top = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds.count +
                                                               (p.n_pad - 1u) * (uint32_t)sizeof(CountT));
     // the argument block itself, for the out-of-line parts (no private copy of `p`)
     const PlaceParams *kp = (const PlaceParams *)__builtin_amdgcn_kernarg_segment_ptr();
     for (uint32_t i = lane; i < p.n_pad; i += kWave) lds.store(i, 0u, 0u);
+    // (the slack rows behind the score vector: +0.0 once, and nothing but x + +0.0 ever after)
+    if constexpr (SlackBytes<Layout>::value != 0) {
+        static_assert(SlackBytes<Layout>::value == (uint32_t)kWave * 4u, "one slack row per lane");
+        lds.score[p.n_pad + (uint32_t)lane] = 0.0f;
+    }
 
     const uint32_t k = p.kmer_size;
     const uint32_t sigma = p.alphabet_size;
@@ -184,7 +190,7 @@ __global__ __launch_bounds__(256, 5) void place_reads_kernel(PlaceParams p)
                         if (nch[t] > c && idx < kChunkCap) {
                             const uint32_t rest = Layout::length(llen[t]) - (c << 6);
                             const uint64_t cnt = rest < (uint32_t)kWave ? rest : (uint32_t)kWave;
-                            chunks[idx] = Layout::descriptor(p, start[t], llen[t], c, cnt);
+                            chunks[idx] = Layout::descriptor(p, start[t], llen[t], c, cnt, score_row0);
                         }
                     }
                     uint64_t long_lists = __ballot(nch[t] > kOwnChunks);
@@ -201,12 +207,12 @@ __global__ __launch_bounds__(256, 5) void place_reads_kernel(PlaceParams p)
                             if (idx < kChunkCap) {
                                 const uint32_t rest = l_len - (c << 6);
                                 const uint64_t cnt = rest < (uint32_t)kWave ? rest : (uint32_t)kWave;
-                                chunks[idx] = Layout::descriptor(p, l_start, l_w, c, cnt);
+                                chunks[idx] = Layout::descriptor(p, l_start, l_w, c, cnt, score_row0);
                             }
                         }
                     }
                 }
-                if ((uint32_t)lane < n_padded - n_round) chunks[n_round + lane] = Layout::null_descriptor(p);
+                if ((uint32_t)lane < n_padded - n_round) chunks[n_round + lane] = Layout::null_descriptor(p, score_row0);
 
                 // (3) stream the chunks through the ring of kRing in-flight loads (place_device.hpp)
                 if constexpr (ListCounts<Layout>::value)
@@ -332,12 +338,23 @@ hipError_t dispatch_counts(int counts, F &&f)
 }
 // runs: the packed lists in their run-coded form (place_device.hpp, kRuns; chosen by the image builder for
 // databases well beyond the Infinity Cache); kRunLists: every list a run, and 16- or 32-bit counts kept per list
-// (RunListLayout; the 8-bit kernel keeps the run ring)
-template <int kTable, typename F>
-hipError_t dispatch_runs(int runs, int counts, F &&f)
+// (RunListLayout; the 8-bit kernel keeps the run ring), with kRingNear / kRingSlack added to it the near descriptors
+// and the slack rows of that layout
+template <int kTable, typename C, typename F>
+hipError_t dispatch_ring(int ring, F &&f)
 {
-    if (runs == kRunLists && counts == kCounts16) return f.template operator()<RunListLayout<kTable>, uint16_t>();
-    if (runs == kRunLists && counts == kCounts32) return f.template operator()<RunListLayout<kTable>, uint32_t>();
+    if (ring == (kRingNear | kRingSlack)) return f.template operator()<RunListLayout<kTable, true, true>, C>();
+    if (ring == kRingNear) return f.template operator()<RunListLayout<kTable, true, false>, C>();
+    if (ring == 0) return f.template operator()<RunListLayout<kTable>, C>();
+    return hipErrorInvalidValue;
+}
+template <int kTable, typename F>
+hipError_t dispatch_runs(int runs_and_ring, int counts, F &&f)
+{
+    const int runs = runs_and_ring & ~(kRingNear | kRingSlack), ring = runs_and_ring & (kRingNear | kRingSlack);
+    if (runs == kRunLists && counts == kCounts16) return dispatch_ring<kTable, uint16_t>(ring, f);
+    if (runs == kRunLists && counts == kCounts32) return dispatch_ring<kTable, uint32_t>(ring, f);
+    if (runs && (ring & kRingNear)) return dispatch_counts<PackedLayout<kTable, true, true>>(counts, f);
     return runs ? dispatch_counts<PackedLayout<kTable, true>>(counts, f) : dispatch_counts<PackedLayout<kTable>>(counts, f);
 }
 template <typename F>

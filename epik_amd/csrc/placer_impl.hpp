@@ -34,6 +34,9 @@ struct epik_amd_placer {
     // run coding of the one-wavefront kernel, latched at create(): 0, epik_amd::kRunsMixed, or epik_amd::kRunLists (every
     // list a run: 16- and 32-bit counts kept per list, db_image.hpp run_counts_apply; EPIK_AMD_RUN_COUNTS=ring turns it off)
     int runs = 0;
+    // ... and the form of the run-list ring's chunk descriptors (RunListLayout), latched beside it: near where the posting
+    // region is shorter than epik_amd::kNearRegionBytes (EPIK_AMD_RING_FORM=near|far forces it where legal)
+    bool ring_near = false;
     bool team = false;               // the team kernel (one workgroup per read) places; else one wavefront per read
     int team_waves = 0;
     const uint8_t *team_table = nullptr;
@@ -71,6 +74,7 @@ struct epik_amd_placer {
         uint32_t lds_block_bytes = 0;
         uint32_t max_blocks = 0;
         uint32_t resident_waves = 0;  // per CU
+        int ring = 0;                 // kRingNear / kRingSlack of this count width, or-ed to `runs` for the kernel (place_kernel.h)
         // team_stream_kernel (team placement as front + streaming + merge kernels): workgroups of 4 waves -- [0], the
         // halves of a k-mer-space-sharded placement -- or of stream_bw[1] = 4 or 2 -- [1], the one-pass placement
         // (db_layout.h: stream_block_waves: two where that puts more waves on a CU)

@@ -166,6 +166,15 @@ int epik_amd_placer_plan_sizes(uint32_t kmer_size, uint32_t alphabet_size, uint3
 int epik_amd_placer_plan_run_counts(const epik_amd_placer_desc *desc, uint32_t shard_index, uint32_t shard_count,
                                     uint64_t free_bytes, uint32_t counts, uint32_t *lists);
 int epik_amd_placer_run_counts(const epik_amd_placer *p, uint32_t counts, uint32_t *lists);
+/* How the posting ring of the one-wavefront kernel finds the chunks of a run-coded image, for that count width: 0 -- by
+ * address or 128-byte line (any posting region; every image that is not run-coded); EPIK_AMD_RING_NEAR -- by 32-bit byte
+ * offset under one buffer resource for the launch (posting regions shorter than 2^32 - 256 bytes; a stage of the
+ * list-counts ring then takes 12 instructions instead of 19), there with EPIK_AMD_RING_SLACK where 64 slack rows behind
+ * the wave's score vector cost no resident wave and replace the clamp of a lane's row.  The output is the same in every form.
+ * EPIK_AMD_RING_FORM (read at create()): `far` keeps the line form; `near` is the default wherever it is legal. */
+#define EPIK_AMD_RING_NEAR 1u
+#define EPIK_AMD_RING_SLACK 2u
+int epik_amd_placer_ring_form(const epik_amd_placer *p, uint32_t counts, uint32_t *form);
 /* The image create() uploads for that plan, written front to back into host buffers of
  * plan->table_bytes / filter_bytes / posting_bytes (NULL = that part is produced and dropped).
  * Host only; create() streams the same bytes to the device without holding them. */
