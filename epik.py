@@ -11,7 +11,8 @@ sharded across; --db-shard; --strand, which strand of each nucleotide read is pl
 (forward as given, its reverse complement, or both and the better one per read); --translate, with
 -s amino: nucleotide reads translated into their frames, per read the best frame; and --profile / --profile-only,
 the sample's abundance profile per branch beside the jplace or instead of it; --mates, the second FASTA file of a
-paired-end sample: every pair gets one placement.
+paired-end sample: every pair gets one placement; --assign / --assign-mass, per read the LCA clade that holds that share
+of its placement mass and the EDPL.
 """
 from __future__ import annotations
 
@@ -62,6 +63,13 @@ PLACE_OPTIONS = [
                                              "and the reads placed best on it, with clade sums.")),
     (("--profile-only",), dict(is_flag=True, help="Write profile_<input>.tsv and no jplace: the placements are summed on "
                                                   "the device(s) and never leave them (not with --db-shard > 1).")),
+    (("--assign",), dict(is_flag=True, help="Also write assign_<input>.tsv (per read the LCA clade that holds --assign-mass "
+                                            "of its placement mass, its size and mass, and the EDPL) and "
+                                            "assign_clades_<input>.tsv (reads per branch and clade); computed on the "
+                                            "device(s) (not with --db-shard > 1).")),
+    (("--assign-mass",), dict(type=click.FloatRange(0.0, 1.0), default=None,
+                              help="With --assign: the share of a read's placement mass its clade must hold, in [0, 1] "
+                                   "[default: 0.95].")),
 ]
 
 
@@ -77,7 +85,11 @@ def driver_path(states: str) -> str:
 
 def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpus, input_file, db_shard=1,
                    strand="forward", translate=None, profile=False, profile_only=False, mates=None,
-                   mate_orientation="fr"):
+                   mate_orientation="fr", assign=False, assign_mass=None):
+    if assign_mass is not None and not assign:
+        raise click.UsageError("--assign-mass needs --assign")
+    if assign and db_shard != 1:
+        raise click.UsageError("--assign does not work with --db-shard > 1")
     argv = [driver_path(states), "-d", str(database), "-q", str(input_file), "-j", str(threads),
             "--omega", str(omega), "--mu", str(mu), "-o", str(outputdir)]
     if max_ram:
@@ -98,6 +110,10 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--profile"]
     if profile_only:
         argv += ["--profile-only"]
+    if assign:
+        argv += ["--assign"]
+        if assign_mass is not None:
+            argv += ["--assign-mass", repr(float(assign_mass))]
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 

@@ -21,6 +21,8 @@ OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED = 0, 1, 2, 3, 4
 
 #: numpy mirror of `epik_amd_placement` {branch, score, lwr} (16 bytes)
 PLACEMENT = np.dtype([("branch", np.uint32), ("score", np.float32), ("lwr", np.float64)])
+#: numpy mirror of `epik_amd_confidence` {clade, clade_mass_q, edpl} (16 bytes)
+CONFIDENCE = np.dtype([("clade", np.uint32), ("clade_mass_q", np.uint32), ("edpl", np.float64)])
 #: numpy mirror of `epik_amd_pkdb_value` / `i2l::pkdb_value` (8 bytes)
 PKDB_VALUE = np.dtype([("branch", np.uint32), ("score", np.float32)])
 
@@ -75,6 +77,16 @@ EXPORTS = (
     "epik_amd_placer_profile_strands",
     "epik_amd_placer_profile_frames",
     "epik_amd_placer_profile_mates",
+    "epik_amd_tree_create",
+    "epik_amd_tree_destroy",
+    "epik_amd_tree_info",
+    "epik_amd_tree_build_host",
+    "epik_amd_tree_lca_host",
+    "epik_amd_confidence_device",
+    "epik_amd_placer_confidence_reads",
+    "epik_amd_placer_confidence_strands",
+    "epik_amd_placer_confidence_frames",
+    "epik_amd_placer_confidence_mates",
 )
 
 
@@ -155,6 +167,11 @@ MAX_SHARDS = 16
 #: count of a partial list that found no room in d_entries
 LIST_OVERFLOW = 0xFFFFFFFF
 PATH_WAVE, PATH_TEAM_ONE_KERNEL, PATH_TEAM_STREAMED = 0, 1, 2
+
+#: parent of the root in epik_amd_tree_create, and the clades of the reads that get none (EPIK_AMD_CLADE_*)
+TREE_NO_PARENT = 0xFFFFFFFF
+CLADE_TOO_NARROW, CLADE_TOO_SHORT, CLADE_NO_HIT, CLADE_BAD_ROW = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
+CLADE_CLASSES = {CLADE_TOO_NARROW: "too_narrow", CLADE_TOO_SHORT: "too_short", CLADE_NO_HIT: "no_hit", CLADE_BAD_ROW: "bad_row"}
 
 #: strand modes of epik_amd_placer_place_strands[_device], and their names in Placer / epik.py / epik-dna --strand
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
@@ -329,6 +346,26 @@ def load() -> ctypes.CDLL:
     for name in ("epik_amd_placer_profile_strands", "epik_amd_placer_profile_frames", "epik_amd_placer_profile_mates"):
         getattr(lib, name).restype = i32
         getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, u64, ctypes.c_uint32, vp]
+    # (placement confidence: the tree, the kernel, the host entries -- their place_* twins' arguments, then tree, tau_q,
+    # conf, profile, weights)
+    u32 = ctypes.c_uint32
+    lib.epik_amd_tree_create.restype = i32
+    lib.epik_amd_tree_create.argtypes = [ctypes.c_int32, vp, vp, u32, ctypes.POINTER(vp)]
+    lib.epik_amd_tree_destroy.restype = None
+    lib.epik_amd_tree_destroy.argtypes = [vp]
+    lib.epik_amd_tree_info.restype = i32
+    lib.epik_amd_tree_info.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u64)]
+    lib.epik_amd_tree_build_host.restype = i32
+    lib.epik_amd_tree_build_host.argtypes = [vp, vp, u32, vp, ctypes.POINTER(u64)]
+    lib.epik_amd_tree_lca_host.restype = i32
+    lib.epik_amd_tree_lca_host.argtypes = [vp, vp, vp, u64, vp]
+    lib.epik_amd_confidence_device.restype = i32
+    lib.epik_amd_confidence_device.argtypes = [vp, vp, vp, vp, u64, u32, u32, vp, vp]
+    lib.epik_amd_placer_confidence_reads.restype = i32
+    lib.epik_amd_placer_confidence_reads.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, u32, vp, vp, vp]
+    for name in ("epik_amd_placer_confidence_strands", "epik_amd_placer_confidence_frames", "epik_amd_placer_confidence_mates"):
+        getattr(lib, name).restype = i32
+        getattr(lib, name).argtypes = [vp, vp, vp, u64, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -484,4 +484,21 @@ int epik_amd_placer_profile_frames(epik_amd_placer *p, epik_amd_profile *profile
     }
 }
 
+int epik_amd_placer_confidence_frames(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                                        uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                                        uint8_t *frame, const epik_amd_tree *tree, uint32_t tau_q, epik_amd_confidence *conf,
+                                        epik_amd_profile *profile, const uint32_t *weights)
+{
+    try {  // (place_frames with the confidence records of confidence_place.hip computed from each chunk's device rows)
+        if (const int rc = check_handle(p, mode); rc != EPIK_AMD_OK) return rc;
+        if (n == 0) return EPIK_AMD_OK;
+        uint64_t longest = 0;
+        if (const int rc = check_host_reads(seqs, seq_offsets, n, longest); rc != EPIK_AMD_OK) return rc;
+        return confidence_host_chunked(p, ConfidenceRequest{tree, tau_q, conf, profile, weights}, seqs, seq_offsets, n, mode,
+                                       longest / 3, kFrameHost, rows, n_rows, kmer_counts, frame);
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("confidence_frames: ") + e.what());
+    }
+}
+
 }  // extern "C"

@@ -227,5 +227,26 @@ int profile_host_chunked(epik_amd_placer *p, epik_amd_profile *profile, const ch
                          const uint32_t *weights, uint64_t n, uint32_t mode, uint64_t longest_placed, const HostVariant &v,
                          uint8_t *label);
 
+// ... and whether that profile was created for this placer's device and shape (EPIK_AMD_ERR_INVALID otherwise)
+int check_profile_pair(const epik_amd_placer *p, const epik_amd_profile *profile);
+
+// What a host entry with placement confidence adds to its place_* twin (confidence_place.hip): the tree and tau_q of
+// the rule, conf[n] on the host, and optionally a profile the rows are added to on the way, item i with weights[i]
+// (host, or NULL: 1).
+struct ConfidenceRequest {
+    const epik_amd_tree *tree;
+    uint32_t tau_q;
+    epik_amd_confidence *conf;
+    epik_amd_profile *profile;
+    const uint32_t *weights;
+};
+
+// The confidence host entry of a variant, once the caller has checked the handle, the mode and the reads (n >= 1,
+// check_host_reads): place_host_chunked with a sink that runs confidence_kernel on every chunk's device rows, copies
+// its 16 bytes per item back and chains the profile add; rows, n_rows and kmer_counts may be NULL, each by itself.
+int confidence_host_chunked(epik_amd_placer *p, const ConfidenceRequest &req, const char *seqs, const uint64_t *seq_offsets,
+                            uint64_t n, uint32_t mode, uint64_t longest_placed, const HostVariant &v, epik_amd_placement *rows,
+                            uint32_t *n_rows, uint32_t *kmer_counts, uint8_t *label);
+
 }  // namespace epik_amd
 #endif

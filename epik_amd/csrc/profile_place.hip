@@ -200,6 +200,8 @@ constexpr HostVariant kForwardHost{.chunk_reads = 1u << 18, .chunk_bytes = 64u <
 
 namespace epik_amd {
 
+int check_profile_pair(const epik_amd_placer *p, const epik_amd_profile *profile) { return check_pair(p, profile); }
+
 int profile_host_chunked(epik_amd_placer *p, epik_amd_profile *profile, const char *seqs, const uint64_t *seq_offsets,
                          const uint32_t *weights, uint64_t n, uint32_t mode, uint64_t longest_placed, const HostVariant &v,
                          uint8_t *label)

@@ -10,7 +10,8 @@
 // every device, batches shared out) and --db-shard G (the database cut in G by k-mer code, shard g on device g:
 // every batch is placed by all of them together -- a database larger than one device's memory); --profile /
 // --profile-only (the sample's abundance profile, profile.hpp: beside the jplace, or instead of it and summed on the
-// devices); --mates FILE (paired-end reads: the second mates, one placement per pair).
+// devices); --mates FILE (paired-end reads: the second mates, one placement per pair); --assign [--assign-mass T] (per
+// record the LCA clade that holds T of its placement mass and the EDPL, confidence.hpp, computed on the devices).
 // The two binaries differ as the reference's do (epik/CMakeLists.txt:72,124): epik-dna
 // accepts DNA databases, epik-aa protein ones.
 #include <algorithm>
@@ -23,6 +24,7 @@
 #include <fstream>
 #include <mutex>
 #include <thread>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iomanip>
@@ -35,6 +37,7 @@
 #include <string>
 #include <vector>
 
+#include "confidence.hpp"
 #include "jplace.hpp"
 #include "phylo_kmer_db.hpp"
 #include "phylo_tree.hpp"
@@ -203,6 +206,11 @@ const char* kHelp =
     "                          placed best on it, with clade sums; reads without any hit are counted, not spread\n"
     "      --profile-only      Write that profile and no jplace: the rows are summed on the device(s) and never\n"
     "                          leave them (not with --db-shard > 1)\n"
+    "      --assign            Also write assign_<query>.tsv -- per record the LCA clade that holds --assign-mass of its\n"
+    "                          placement mass, that clade's size and mass, and the EDPL -- and assign_clades_<query>.tsv,\n"
+    "                          the records assigned to each branch and clade; computed on the device(s) (not with\n"
+    "                          --db-shard > 1; with --profile-only the rows still never leave the device)\n"
+    "      --assign-mass arg   Share of a record's placement mass its clade must hold, in [0, 1] (default: 0.95)\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -243,7 +251,7 @@ options parse_args(int argc, char** argv)
         } else {
             continue;  // positional arguments are ignored (epik.py passes the query twice, epik.py:88,96)
         }
-        if (name == "help" || ((name == "profile" || name == "profile-only") && !have_value)) {  // flags
+        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign") && !have_value)) {  // flags
             opt.values[name] = "1";
             continue;
         }
@@ -322,6 +330,25 @@ int main(int argc, char** argv)
         if (profile_only && std::stoul(parsed.get("db-shard", "1")) > 1)
             throw std::runtime_error("--profile-only does not work with --db-shard > 1 (use --profile: the rows of a sharded "
                                      "placement are finished on several devices)");
+        // --assign / --assign-mass: checked before anything is opened or any device touched
+        const bool with_assign = parsed.has("assign");
+        if (parsed.has("assign-mass") && !with_assign) throw std::runtime_error("--assign-mass needs --assign");
+        if (with_assign && std::stoul(parsed.get("db-shard", "1")) > 1)
+            throw std::runtime_error("--assign does not work with --db-shard > 1 (the rows of a sharded placement are finished "
+                                     "on several devices)");
+        uint32_t assign_tau_q = 0;
+        if (with_assign) {
+            size_t used = 0;
+            const auto text = parsed.get("assign-mass", "0.95");
+            double tau = -1.0;
+            try {
+                tau = std::stod(text, &used);
+            } catch (const std::exception&) {
+                used = 0;
+            }
+            if (used != text.size() || used == 0) throw std::runtime_error("--assign-mass must be a number in [0, 1], not '" + text + "'");
+            assign_tau_q = epik_amd::assign_tau_q(tau);
+        }
         const auto db_file = parsed.require("database");
         const auto query_file = parsed.require("query");
         const auto num_threads = (size_t)std::stoul(parsed.get("jobs", "1"));
@@ -396,6 +423,12 @@ int main(int argc, char** argv)
         if (translate) placer.set_translate(frames);
         if (with_mates) placer.set_mates(orientation_name == "ff" ? epik_amd::mate_orientation::ff : epik_amd::mate_orientation::fr);
         if (profile_only) placer.set_profile_only();
+        // --assign: the rule's tree on every device; the host's copy names clade sizes and sums the clades
+        std::unique_ptr<epik_amd::confidence_tree> assign_tree;
+        if (with_assign) {
+            assign_tree.reset(new epik_amd::confidence_tree(tree));
+            placer.set_assign(assign_tau_q);
+        }
         db.drop_lists();  // the lists are on the devices now; tree, k and omega stay for the output
         const auto tree_as_newick = epik_amd::io::to_newick(tree, true);
         const auto jplace_filename = make_output_filename(query_file, output_dir);
@@ -416,6 +449,17 @@ int main(int argc, char** argv)
         if (strand != epik_amd::strand_mode::forward) {
             strands_out.open(make_strands_filename(query_file, output_dir));
             if (!strands_out) throw std::runtime_error("Could not open " + make_strands_filename(query_file, output_dir));
+        }
+        // --assign: one line per input record, input order, into a part file: the header line counts the records, which
+        // only the end of the input tells; the file proper is the header and then the part
+        std::ofstream assign_out;
+        const auto assign_filename = epik_amd::make_assign_filename(query_file, output_dir);
+        const auto assign_clades_filename = epik_amd::make_assign_clades_filename(query_file, output_dir);
+        epik_amd::assign_summary assign_sums(with_assign ? tree.get_node_count() : 0);
+        uint64_t assign_records = 0;
+        if (with_assign) {
+            assign_out.open(assign_filename + ".part", std::ios::binary);
+            if (!assign_out) throw std::runtime_error("Could not open " + assign_filename + ".part");
         }
         // --translate: one "name<TAB>+1..-3" line per input record, input order
         std::ofstream frames_out;
@@ -519,6 +563,19 @@ int main(int argc, char** argv)
                                             << (item.placed.strands[item.placed.unique_of[i]] ? '-' : '+') << '\n';
                         if (!strands_out) throw std::runtime_error("Could not write the strands file");
                     }
+                    if (assign_out.is_open()) {
+                        for (const auto& item : ready) {
+                            std::string lines;
+                            for (size_t i = 0; i < item.batch.size(); ++i) {
+                                const auto& record = item.placed.confidence[item.placed.unique_of[i]];
+                                lines += epik_amd::format_assign_line(item.batch[i].header(), record, *assign_tree);
+                                assign_sums.add(record, 1);
+                            }
+                            assign_out << lines;
+                            assign_records += item.batch.size();
+                        }
+                        if (!assign_out) throw std::runtime_error("Could not write the assign file");
+                    }
                     if (frames_out.is_open()) {
                         static const char* const names[6] = {"+1", "+2", "+3", "-1", "-2", "-3"};
                         for (const auto& item : ready)
@@ -594,12 +651,27 @@ int main(int argc, char** argv)
             for (const auto& entry : db.tree_index()) subtree_num_nodes.push_back(entry.subtree_num_nodes);
             epik_amd::write_profile_tsv(profile_filename, profile, subtree_num_nodes);
         }
+        if (with_assign) {
+            assign_out.close();
+            if (!assign_out) throw std::runtime_error("Could not write " + assign_filename + ".part");
+            {
+                std::ifstream part(assign_filename + ".part", std::ios::binary);
+                std::ofstream whole(assign_filename, std::ios::binary);
+                whole << epik_amd::format_assign_header(assign_tau_q, assign_records);
+                if (assign_records) whole << part.rdbuf();
+                whole.close();
+                if (!part || !whole) throw std::runtime_error("Could not write " + assign_filename);
+            }
+            std::remove((assign_filename + ".part").c_str());
+            epik_amd::write_text_file(assign_clades_filename, epik_amd::format_assign_clades_tsv(assign_sums, *assign_tree, assign_tau_q));
+        }
         if (num_iterations) average_speed /= (double)num_iterations;
         std::cout << std::endl
                   << "Placed " << num_seq_placed << " sequences.\nAverage speed: " << epik_amd::human_count(average_speed, false)
                   << " seq/s.\n";
         if (jplace) std::cout << "Output: " << jplace_filename << std::endl;
         if (with_profile) std::cout << "Profile: " << profile_filename << std::endl;
+        if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;
         if (strands_out.is_open()) {
             strands_out.close();
             if (!strands_out) throw std::runtime_error("Could not write " + make_strands_filename(query_file, output_dir));

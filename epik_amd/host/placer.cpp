@@ -20,6 +20,12 @@
 #pragma weak epik_amd_placer_profile_frames
 #pragma weak epik_amd_placer_place_mates
 #pragma weak epik_amd_placer_profile_mates
+#pragma weak epik_amd_tree_create
+#pragma weak epik_amd_tree_destroy
+#pragma weak epik_amd_placer_confidence_reads
+#pragma weak epik_amd_placer_confidence_strands
+#pragma weak epik_amd_placer_confidence_frames
+#pragma weak epik_amd_placer_confidence_mates
 
 namespace epik_amd {
 
@@ -95,6 +101,7 @@ placer::placer(const phylo_kmer_db& db, const phylo_tree& original_tree, size_t 
             throw std::runtime_error("GPU placer: " + message);
         }
         _handles.push_back(handle);
+        _devices.push_back(desc.device);
         if (_sharded && g == 0) {
             // A tree of the one-wavefront kernels leaves dense partial vectors, which place_sharded does not take:
             // said now, before the other shards are loaded and uploaded, not at the first batch.
@@ -170,6 +177,32 @@ void placer::set_profile_only()
     }
 }
 
+void placer::set_assign(uint32_t tau_q)
+{
+    if (_sharded) throw std::runtime_error("GPU placer: --assign does not work with --db-shard > 1");
+    if (!&epik_amd_tree_create || !&epik_amd_tree_destroy || !&epik_amd_placer_confidence_reads || !&epik_amd_placer_confidence_strands ||
+        !&epik_amd_placer_confidence_frames || !&epik_amd_placer_confidence_mates)
+        throw std::runtime_error("GPU placer: this libepik_amd has no placement confidence");
+    _tau_q = tau_q;
+    if (!_trees.empty()) return;
+    std::vector<uint32_t> parent;
+    std::vector<double> length;
+    for (const auto& node : _original_tree.nodes()) {
+        parent.push_back(node.parent < 0 ? EPIK_AMD_TREE_NO_PARENT : (uint32_t)node.parent);
+        length.push_back(node.branch_length);
+    }
+    for (size_t g = 0; g < _handles.size(); ++g) {
+        epik_amd_tree* tree = nullptr;
+        if (epik_amd_tree_create(_devices[g], parent.data(), length.data(), (uint32_t)parent.size(), &tree) != EPIK_AMD_OK) {
+            const std::string message = epik_amd_last_error();
+            for (auto* made : _trees) epik_amd_tree_destroy(made);
+            _trees.clear();
+            throw std::runtime_error("GPU placer: " + message);
+        }
+        _trees.push_back(tree);
+    }
+}
+
 void placer::read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_totals& totals) const
 {
     const size_t n = _original_tree.get_node_count();
@@ -189,6 +222,7 @@ void placer::read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_tota
 placer::~placer() noexcept
 {
     for (auto* profile : _profiles) epik_amd_profile_destroy(profile);
+    for (auto* tree : _trees) epik_amd_tree_destroy(tree);
     for (auto* h : _handles) epik_amd_placer_destroy(h);
 }
 
@@ -280,7 +314,7 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         pb.names.resize(batch.size());
         std::vector<uint32_t> at(pb.name_begin.begin(), pb.name_begin.end() - 1);
         for (size_t i = 0; i < batch.size(); ++i) pb.names[at[unique_of[i]]++] = batch[i].header();
-        if (_strand != strand_mode::forward || _translate) pb.unique_of = std::move(unique_of);  // (the strand / frame of each record)
+        if (_strand != strand_mode::forward || _translate || assigning()) pb.unique_of = std::move(unique_of);  // (the strand / frame / record of each record)
         first_unique[b + 1] = n_unique;
         first_byte[b + 1] = bytes;
         out[b] = std::move(pb);
@@ -322,7 +356,22 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         if (_translate || _strand != strand_mode::forward) labels.reset(new uint8_t[n]);
         auto* handle = _handles[device_index];
         auto* profile = _profiles[device_index];
-        const int rc = _mates ? epik_amd_placer_profile_mates(handle, profile, bytes.get(), offsets.get(), weights.get(), n,
+        std::unique_ptr<epik_amd_confidence[]> conf;
+        if (assigning()) {  // the same placement through the confidence entries: the rows stay, 16 bytes a sequence come back
+            conf.reset(new epik_amd_confidence[n]);
+        }
+        auto* tree = assigning() ? _trees[device_index] : nullptr;
+        const int rc = assigning()
+            ? (_mates ? epik_amd_placer_confidence_mates(handle, bytes.get(), offsets.get(), n, mates_mode, nullptr, nullptr, nullptr,
+                                                         labels.get(), tree, _tau_q, conf.get(), profile, weights.get())
+               : _translate ? epik_amd_placer_confidence_frames(handle, bytes.get(), offsets.get(), n, (uint32_t)_frames, nullptr, nullptr,
+                                                                nullptr, labels.get(), tree, _tau_q, conf.get(), profile, weights.get())
+               : _strand != strand_mode::forward
+                   ? epik_amd_placer_confidence_strands(handle, bytes.get(), offsets.get(), n, (uint32_t)_strand, nullptr, nullptr, nullptr,
+                                                        labels.get(), tree, _tau_q, conf.get(), profile, weights.get())
+                   : epik_amd_placer_confidence_reads(handle, bytes.get(), offsets.get(), n, nullptr, nullptr, nullptr, tree, _tau_q,
+                                                      conf.get(), profile, weights.get()))
+            : _mates ? epik_amd_placer_profile_mates(handle, profile, bytes.get(), offsets.get(), weights.get(), n,
                                                                mates_mode, labels.get())
                        : _translate ? epik_amd_placer_profile_frames(handle, profile, bytes.get(), offsets.get(), weights.get(), n,
                                                                    (uint32_t)_frames, labels.get())
@@ -334,6 +383,7 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         for (size_t b = 0; b < batches.size(); ++b) {
             auto& pb = out[b];
             pb.row_begin.assign(pb.size() + 1, 0);
+            if (conf) pb.confidence.assign(conf.get() + first_unique[b], conf.get() + first_unique[b] + pb.size());
             if (!labels) continue;
             const uint8_t* first = labels.get() + first_unique[b];
             (_translate ? pb.frames : pb.strands).assign(first, first + pb.size());
@@ -344,8 +394,30 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
     std::unique_ptr<uint32_t[]> n_rows(new uint32_t[n]), counts(new uint32_t[n * _keep_at_most]);
     std::unique_ptr<uint8_t[]> strands;  // (reverse / both only: forward goes through epik_amd_placer_place as ever)
     std::unique_ptr<uint8_t[]> frames;   // (translated placement only)
+    std::unique_ptr<epik_amd_confidence[]> conf;  // (--assign only)
     int rc;
-    if (_mates) {
+    if (assigning()) {
+        // the same placements through the confidence entries: the records come back beside the rows
+        conf.reset(new epik_amd_confidence[n]);
+        auto* handle = _handles[device_index];
+        auto* tree = _trees[device_index];
+        if (_mates) {
+            if (_strand != strand_mode::forward) strands.reset(new uint8_t[n]);
+            rc = epik_amd_placer_confidence_mates(handle, bytes.get(), offsets.get(), n, mates_mode, rows.get(), n_rows.get(), counts.get(),
+                                                  strands.get(), tree, _tau_q, conf.get(), nullptr, nullptr);
+        } else if (_translate) {
+            frames.reset(new uint8_t[n]);
+            rc = epik_amd_placer_confidence_frames(handle, bytes.get(), offsets.get(), n, (uint32_t)_frames, rows.get(), n_rows.get(),
+                                                   counts.get(), frames.get(), tree, _tau_q, conf.get(), nullptr, nullptr);
+        } else if (_strand != strand_mode::forward) {
+            strands.reset(new uint8_t[n]);
+            rc = epik_amd_placer_confidence_strands(handle, bytes.get(), offsets.get(), n, (uint32_t)_strand, rows.get(), n_rows.get(),
+                                                    counts.get(), strands.get(), tree, _tau_q, conf.get(), nullptr, nullptr);
+        } else {
+            rc = epik_amd_placer_confidence_reads(handle, bytes.get(), offsets.get(), n, rows.get(), n_rows.get(), counts.get(), tree,
+                                                  _tau_q, conf.get(), nullptr, nullptr);
+        }
+    } else if (_mates) {
         if (_strand != strand_mode::forward) strands.reset(new uint8_t[n]);
         rc = epik_amd_placer_place_mates(_handles[device_index], bytes.get(), offsets.get(), n, mates_mode, rows.get(),
                                          n_rows.get(), counts.get(), strands.get());
@@ -383,6 +455,7 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
             pb.strands.assign(strands.get() + first_unique[b], strands.get() + first_unique[b] + n_unique);
         }
         if (frames) pb.frames.assign(frames.get() + first_unique[b], frames.get() + first_unique[b] + n_unique);
+        if (conf) pb.confidence.assign(conf.get() + first_unique[b], conf.get() + first_unique[b] + n_unique);
         for (size_t u = 0; u < n_unique; ++u) {
             const size_t i = first_unique[b] + u;
             for (uint32_t r = 0; r < n_rows[i]; ++r) {

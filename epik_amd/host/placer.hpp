@@ -66,6 +66,8 @@ struct placed_batch {
     std::vector<uint8_t> frames;              // [n_unique]: the frame placed, 0..5 = +1 +2 +3 -1 -2 -3
     // pairs (placer::set_mates) only, else empty: `sequences` are the first mates, `strands` the fragments'
     std::vector<std::string_view> mates;      // [n_unique]: the second mate, as given
+    // placement confidence (placer::set_assign) only, else empty; `unique_of` is then filled as well:
+    std::vector<epik_amd_confidence> confidence;  // [n_unique]: LCA clade, its mass and the EDPL, from the device
     size_t size() const noexcept { return sequences.size(); }
 };
 
@@ -147,6 +149,12 @@ public:
     /// Replicated databases only (not --db-shard).
     void set_profile_only();
     bool profile_only() const noexcept { return !_profiles.empty(); }
+    /// --assign: one device tree per handle (epik_amd_tree, from the tree given to the constructor); from then on
+    /// place_flat goes through the epik_amd_placer_confidence_* entries and every placed batch carries the confidence
+    /// record of each unique sequence, computed on the device from its rows -- with set_profile_only() the rows still
+    /// never leave the device, only the 16 bytes per sequence do.  Replicated databases only (not --db-shard).
+    void set_assign(uint32_t tau_q);
+    bool assigning() const noexcept { return !_trees.empty(); }
     /// The profiles of all devices read back and summed; `mass` and `best` of num_branches cells each.
     void read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_totals& totals) const;
     /// distal_length / pendant_length of a placement on branch b (place.cpp:110-123, 435-437)
@@ -162,7 +170,10 @@ private:
     const double _keep_factor;
     std::vector<double> _pendant_lengths;
     std::vector<epik_amd_placer*> _handles;  // one per device (replicated) or per shard (sharded)
+    std::vector<int> _devices;               // ... and the device of each
     std::vector<epik_amd_profile*> _profiles;  // set_profile_only(): one per handle
+    std::vector<epik_amd_tree*> _trees;        // set_assign(): one per handle
+    uint32_t _tau_q = 0;
     bool _sharded = false;
     strand_mode _strand = strand_mode::forward;
     bool _translate = false;

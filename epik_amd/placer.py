@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Iterable, List, Sequence, Tuple
 
 import numpy as np
@@ -58,6 +58,8 @@ class PlacedCollection:
 
     sequence_map: dict
     placed_seqs: List[PlacedSequence]
+    #: Placer.place(assign=...): the confidence record of every placed sequence (capi.CONFIDENCE), in their order
+    confidence: np.ndarray = field(default=None, compare=False)
 
 
 def pendant_lengths(branch_length: np.ndarray, subtree_num_nodes: np.ndarray,
@@ -429,6 +431,62 @@ class Placer:
                       label.ctypes.data))
         return label
 
+    # -- placement confidence (epik_amd/confidence.py) ------------------------------------------
+    def tree(self, parent, branch_length):
+        """The tree of this placer's database on its device (`epik_amd_tree_create`): `parent[b]` of every post-order
+        id (the root's: -1 or capi.TREE_NO_PARENT) and the branch lengths."""
+        from .confidence import Tree
+        if len(parent) != self.num_branches:
+            raise ValueError(f"the tree has {len(parent)} branches, the placer {self.num_branches}")
+        return Tree(self.device, parent, branch_length)
+
+    def confidence_device(self, tree, d_rows: int, d_n_rows: int, d_kmer_counts: int, n: int, tau_q: int, d_out: int,
+                          stream: int = 0) -> None:
+        """The confidence records of the n reads whose rows a placement of this placer left in device memory, into
+        d_out (16 bytes a read), asynchronous on `stream` (`epik_amd_confidence_device`)."""
+        tree.confidence_device(d_rows, d_n_rows, d_kmer_counts, n, self.keep_at_most, tau_q, d_out, stream)
+
+    def confidence_packed(self, tree, seqs: np.ndarray, seq_offsets: np.ndarray, tau_q: int, profile=None, weights=None,
+                          strand=None, translate=None, mates=None, rows_out: bool = True):
+        """`place_packed` / `place_strands` / `place_frames` / `place_mates` with the confidence record of every read or
+        pair computed on the device from its rows: `epik_amd_placer_confidence_reads` / `_strands` / `_frames` /
+        `_mates`.  `profile`: the rows are also added to it there, item i with weights[i] (None: 1).  `rows_out=False`:
+        rows, row counts and k-mer counts stay on the device (None in the result).  Returns (rows, n_rows, kmer_counts,
+        label, conf): label the strand or frame byte per item (None without `strand`, `translate` and `mates`), conf
+        capi.CONFIDENCE records."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+        n = int(seq_offsets.shape[0] - 1)
+        if strand is not None and translate is not None:
+            raise ValueError("strand and translate do not combine: translate=both already covers both strands")
+        if mates is not None:
+            if translate is not None:
+                raise ValueError("mates and translate do not combine: pairs are placed on nucleotide databases")
+            n = self._pairs_of(seq_offsets)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint32)
+        if w is not None and w.shape != (n,):
+            raise ValueError(f"weights must hold one value per read ({n}), not {w.shape}")
+        rows = np.zeros((n, self.keep_at_most), dtype=capi.PLACEMENT) if rows_out else None
+        n_rows = np.zeros(n, dtype=np.uint32) if rows_out else None
+        counts = np.zeros((n, self.keep_at_most), dtype=np.uint32) if rows_out else None
+        conf = np.zeros(n, dtype=capi.CONFIDENCE)
+        out = [None if a is None else a.ctypes.data for a in (rows, n_rows, counts)]
+        tail = [tree._handle, int(tau_q), conf.ctypes.data, None if profile is None else profile._handle,
+                None if w is None else w.ctypes.data]
+        if strand is None and translate is None and mates is None:
+            capi.check(self._lib.epik_amd_placer_confidence_reads(self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n,
+                                                                  *out, *tail))
+            return rows, n_rows, counts, None, conf
+        label = np.zeros(n, dtype=np.uint8)
+        if mates is not None:
+            fn, mode = self._lib.epik_amd_placer_confidence_mates, self._mates_mode(strand or "forward", mates)
+        elif translate is not None:
+            fn, mode = self._lib.epik_amd_placer_confidence_frames, self._frame_mode(translate)
+        else:
+            fn, mode = self._lib.epik_amd_placer_confidence_strands, self._strand_mode(strand)
+        capi.check(fn(self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n, mode, *out, label.ctypes.data, *tail))
+        return rows, n_rows, counts, label, conf
+
     @staticmethod
     def codon_table() -> np.ndarray:
         """The library's codon -> residue table: uint8[4096] indexed by the three nucleotide class masks, 4 bits each,
@@ -571,7 +629,7 @@ class Placer:
     # -- epik::placer::place ---------------------------------------------------------
     def place(self, seq_records: Iterable[Tuple[str, str]], num_threads: int = 1,
               strand: str = "forward", translate=None, profile=None, mates=None,
-              mate_orientation: str = "fr") -> PlacedCollection:
+              mate_orientation: str = "fr", assign=None, tree=None) -> PlacedCollection:
         """`seq_records` = (header, sequence) pairs (i2l::seq_record).  `num_threads`
         is accepted for signature parity and ignored, as the parallelism is the GPU's.
         `strand`: "forward" (the reference's contract: each read as given), "reverse" (its reverse
@@ -585,8 +643,13 @@ class Placer:
         every pair gets ONE placement, that of mate 1 . separator . rc(mate 2) (`mate_orientation` "fr") or mate 1 .
         separator . mate 2 ("ff") (`place_mates`).  Duplicates are merged on the PAIR of sequences: `sequence_map` is
         then keyed by (mate 1, mate 2) and holds mate 1's headers; PlacedSequence.sequence is mate 1, .mate mate 2,
-        .strand the fragment's strand."""
+        .strand the fragment's strand.
+        `assign` (a mass tau in [0, 1]) with `tree` (a `Tree` of this placer, `Placer.tree`): the placement goes through
+        the confidence entries and PlacedCollection.confidence holds, per placed sequence, the LCA clade that holds
+        tau of its placement mass, that clade's mass and the EDPL, computed on the device."""
         del num_threads
+        if (assign is None) != (tree is None):
+            raise ValueError("assign (the mass tau) and tree (Placer.tree(...)) go together")
         mode = self._strand_mode(strand)
         frame_mode = None if translate is None else self._frame_mode(translate)
         if frame_mode is not None and mode != capi.STRAND_FORWARD:
@@ -608,8 +671,17 @@ class Placer:
         if bufs:
             offsets[1:] = np.cumsum([len(b) for b in bufs], dtype=np.uint64)
         data = np.frombuffer(b"".join(bufs), dtype=np.uint8) if bufs else np.zeros(0, np.uint8)
-        strands = frames = None
-        if mates is not None:
+        strands = frames = conf = None
+        if assign is not None:
+            from .confidence import tau_q
+            rows, n_rows, counts, label, conf = self.confidence_packed(
+                tree, data, offsets, tau_q(assign), strand=None if frame_mode is not None or (mates is None and mode == capi.STRAND_FORWARD) else mode,
+                translate=frame_mode, mates=None if mates is None else mate_orientation)
+            if frame_mode is not None:
+                frames = label
+            elif mates is not None or mode != capi.STRAND_FORWARD:
+                strands = label
+        elif mates is not None:
             rows, n_rows, counts, strands = self.place_mates(data, offsets, mode, mate_orientation)
         elif frame_mode is not None:
             rows, n_rows, counts, frames = self.place_frames(data, offsets, frame_mode)
@@ -639,4 +711,4 @@ class Placer:
             placed.append(PlacedSequence(sequence=seq, placements=pl, mate=mate,
                                          strand="-" if strands is not None and strands[i] else "+",
                                          frame=capi.FRAME_NAMES[int(frames[i])] if frames is not None else ""))
-        return PlacedCollection(sequence_map=sequence_map, placed_seqs=placed)
+        return PlacedCollection(sequence_map=sequence_map, placed_seqs=placed, confidence=conf)

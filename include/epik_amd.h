@@ -551,6 +551,104 @@ int epik_amd_placer_profile_mates(epik_amd_placer *p, epik_amd_profile *profile,
                                   const uint64_t *seq_offsets, const uint32_t *weights, uint64_t n_pairs, uint32_t mode,
                                   uint8_t *strand);
 
+/*
+ * Per-read placement confidence, computed on the device from the rows a placement wrote: the LCA clade that holds a
+ * given share of the read's placement mass, and the EDPL (expected distance between placement locations).  No reference
+ * counterpart: the reference writes a jplace and leaves both to a second tool.  One rule; the kernel
+ * (confidence_place.hip), the host mirror (epik_amd/host/confidence.cpp) and the tests' numpy are worded after it and
+ * must agree bit for bit, edpl included.
+ *
+ * The tree.  N = num_branches nodes with post-order ids; branch b joins node b to parent[b]; parent[b] > b for
+ *   b < N - 1 and parent[N - 1] = EPIK_AMD_TREE_NO_PARENT.  size[b] = the nodes of the subtree of b, b included;
+ *   first[b] = b - size[b] + 1; x lies in the clade of b <=> first[b] <= x <= b.  create() / build_host() refuse with
+ *   EPIK_AMD_ERR_INVALID and a message that names the branch ("branch <b>: ..."), checked in ascending b, per branch in
+ *   this order: a branch length that is negative or not finite; a second root (b < N - 1 without parent); a root with a
+ *   parent (b = N - 1); a parent not above its child (parent[b] <= b, or >= N); a node whose descendants are not
+ *   exactly [first[b], b].  Multifurcating trees and N = 1 are valid.
+ *   depth[b] = depth[parent[b]] + branch_length[b], the root's parent counting as depth 0: one double add each, from
+ *   the root down.  mid[b] = depth[b] - branch_length[b] / 2: a placement sits at the middle of its branch
+ *   (distal_length = branch_length / 2, place.cpp:110, 435); pendant lengths take no part.
+ *   lca(a, b) = the ancestor-or-self c of max(a, b), lowest in the tree, with first[c] <= min(first[a], first[b]).
+ *   d(a, a) = 0; if a lies in the clade of b, d(a, b) = mid[a] - mid[b], and the other way round; otherwise, with
+ *   c = lca(a, b), d(a, b) = (mid[a] - depth[c]) + (mid[b] - depth[c]), evaluated as parenthesised.
+ *
+ * The record of read i.  q() is the profile's; keep = keep_at_most; nr = min(n_rows[i], keep).  Tested in this order:
+ *     n_rows[i] == EPIK_AMD_ROWS_COUNTS_TOO_NARROW    clade = EPIK_AMD_CLADE_TOO_NARROW, the other fields 0
+ *     n_rows[i] == 0                                  clade = EPIK_AMD_CLADE_TOO_SHORT,  the other fields 0
+ *     kmer_counts[i * keep] == 0                      clade = EPIK_AMD_CLADE_NO_HIT,     the other fields 0
+ *     a row j < nr with branch >= N                   clade = EPIK_AMD_CLADE_BAD_ROW,    the other fields 0
+ *   (the third: the rows fabricated for a read without hits, place.cpp:141-152, produce no clade).  Otherwise, with
+ *   b_j and lwr_j the branch and like-weight ratio of row j:
+ *   clade         S_m = sum over j < m of q(lwr_j), S = S_nr; m = the smallest m >= 1 with S_m * 2^30 >= tau_q * S in
+ *                 uint64 (nr when there is none: only sums that wrap); tau_q in [0, 2^30], larger is
+ *                 EPIK_AMD_ERR_INVALID.  Rows come in (score descending, branch ascending) order: the prefix is the
+ *                 best rows.  clade = the lca of b_0 ... b_(m-1), folded left to right; tau_q = 0 gives b_0,
+ *                 tau_q = 2^30 the lca of all rows.
+ *   clade_mass_q  the sum of q(lwr_j) over all j < nr with first[clade] <= b_j <= clade, saturating at 2^32 - 1.
+ *   edpl          2 * sum over j < l < nr of (lwr_j * lwr_l) * d(b_j, b_l): the products as parenthesised, the pairs
+ *                 added in lexicographic (j, l) order, in double, round to nearest, multiply and add never fused; the
+ *                 sum over ordered pairs with the LWRs as reported (after keep_factor, not renormalised), as the
+ *                 profile takes them.  nr = 1 gives +0.0.
+ *   The rule reads slots past n_rows nowhere.  The record is a pure function of the read's rows and the tree: the same
+ *   bits whatever the grid, the chunks or the stream.
+ *
+ * An epik_amd_tree is an object of its own on `device`, independent of any placer.  It holds first, depth, mid and,
+ * for lca, binary lifting over parent[]: lift[l][b] = {the 2^l-th ancestor u of b (the root where there is none),
+ * first[u]}, l < levels = max(1, ceil(log2 N)) -- a query is at most levels + 1 dependent loads on any valid tree.
+ *   tree_create      validates, builds the tables on the host and uploads them.  EPIK_AMD_MAX_BLOCKS, read here, caps
+ *                    the grid of confidence_device (tests).
+ *   tree_info        num_branches, levels and the bytes of the tables (each may be NULL).
+ *   tree_build_host  the same tables into host memory, without a device: *table_bytes = their size; tables == NULL
+ *                    asks for the size alone.  tree_lca_host answers n queries on such tables with the very function
+ *                    the kernel calls (a[i], b[i] < N, else EPIK_AMD_ERR_INVALID).
+ *   confidence_device  asynchronous on `stream`, allocates nothing: d_out[i] for the n reads whose rows [n][keep],
+ *                    n_rows [n] and k-mer counts [n][keep] (required) a placement left in device memory; n == 0 does
+ *                    nothing.  keep in [1, 64], as a placer's keep_at_most.
+ *   confidence_reads / _strands / _frames / _mates: place / place_strands / place_frames / place_mates with `conf`
+ *                    [n] records (HOST) computed on the device from each chunk's rows; rows, n_rows and kmer_counts
+ *                    may be NULL, each by itself: that part stays on the device.  `profile` (optional): the rows are
+ *                    also added to it there, item i with weights[i] (HOST uint32 [n], or NULL: 1; without a profile
+ *                    the weights are not looked at).  The tree must be on the placer's device and have its
+ *                    num_branches.  Whole databases only.  Synchronous.
+ */
+#define EPIK_AMD_TREE_NO_PARENT 0xffffffffu
+#define EPIK_AMD_CLADE_TOO_NARROW 0xffffffffu
+#define EPIK_AMD_CLADE_TOO_SHORT 0xfffffffeu
+#define EPIK_AMD_CLADE_NO_HIT 0xfffffffdu
+#define EPIK_AMD_CLADE_BAD_ROW 0xfffffffcu
+typedef struct {
+    uint32_t clade;
+    uint32_t clade_mass_q;
+    double edpl;
+} epik_amd_confidence; /* 16 bytes */
+typedef struct epik_amd_tree epik_amd_tree;
+int epik_amd_tree_create(int32_t device, const uint32_t *parent, const double *branch_length, uint32_t num_branches,
+                         epik_amd_tree **out);
+void epik_amd_tree_destroy(epik_amd_tree *tree);
+int epik_amd_tree_info(const epik_amd_tree *tree, uint32_t *num_branches, uint32_t *levels, uint64_t *table_bytes);
+int epik_amd_tree_build_host(const uint32_t *parent, const double *branch_length, uint32_t num_branches, void *tables,
+                             uint64_t *table_bytes);
+int epik_amd_tree_lca_host(const void *tables, const uint32_t *a, const uint32_t *b, uint64_t n, uint32_t *out);
+int epik_amd_confidence_device(const epik_amd_tree *tree, const void *d_rows, const void *d_n_rows,
+                               const void *d_kmer_counts, uint64_t n, uint32_t keep, uint32_t tau_q, void *d_out,
+                               void *stream);
+int epik_amd_placer_confidence_reads(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                                     epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                                     const epik_amd_tree *tree, uint32_t tau_q, epik_amd_confidence *conf,
+                                     epik_amd_profile *profile, const uint32_t *weights);
+int epik_amd_placer_confidence_strands(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                                       uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                                       uint8_t *strand, const epik_amd_tree *tree, uint32_t tau_q,
+                                       epik_amd_confidence *conf, epik_amd_profile *profile, const uint32_t *weights);
+int epik_amd_placer_confidence_frames(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                                      uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                                      uint8_t *frame, const epik_amd_tree *tree, uint32_t tau_q,
+                                      epik_amd_confidence *conf, epik_amd_profile *profile, const uint32_t *weights);
+int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n_pairs,
+                                     uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                                     uint8_t *strand, const epik_amd_tree *tree, uint32_t tau_q,
+                                     epik_amd_confidence *conf, epik_amd_profile *profile, const uint32_t *weights);
+
 /* Which kernels the last launch of this handle ran (reports; a large-tree handle falls back from the three-kernel
  * placement to the one-kernel one when the device has no room for the scratch of a launch). */
 #define EPIK_AMD_PATH_WAVE 0u            /* place_reads_kernel: one wavefront per read */
