@@ -12,7 +12,8 @@ sharded across; --db-shard; --strand, which strand of each nucleotide read is pl
 -s amino: nucleotide reads translated into their frames, per read the best frame; and --profile / --profile-only,
 the sample's abundance profile per branch beside the jplace or instead of it; --mates, the second FASTA file of a
 paired-end sample: every pair gets one placement; --assign / --assign-mass, per read the LCA clade that holds that share
-of its placement mass and the EDPL.
+of its placement mass and the EDPL; --cohort, the input file is a list of samples (name<TAB>path lines): their profiles and
+the Kantorovich-Rubinstein distance between every two of them, cohort_samples_ / cohort_profile_ / cohort_kr_<list>.tsv.
 """
 from __future__ import annotations
 
@@ -70,6 +71,11 @@ PLACE_OPTIONS = [
     (("--assign-mass",), dict(type=click.FloatRange(0.0, 1.0), default=None,
                               help="With --assign: the share of a read's placement mass its clade must hold, in [0, 1] "
                                    "[default: 0.95].")),
+    (("--cohort",), dict(is_flag=True, help="The input file is a list of samples, one name<TAB>path line each (paths relative "
+                                            "to the list): writes no jplace but cohort_samples_<list>.tsv, "
+                                            "cohort_profile_<list>.tsv and cohort_kr_<list>.tsv, the KR distance between "
+                                            "every two samples (not with --mates, --profile, --profile-only, --assign or "
+                                            "--db-shard > 1).")),
 ]
 
 
@@ -85,11 +91,16 @@ def driver_path(states: str) -> str:
 
 def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpus, input_file, db_shard=1,
                    strand="forward", translate=None, profile=False, profile_only=False, mates=None,
-                   mate_orientation="fr", assign=False, assign_mass=None):
+                   mate_orientation="fr", assign=False, assign_mass=None, cohort=False):
     if assign_mass is not None and not assign:
         raise click.UsageError("--assign-mass needs --assign")
     if assign and db_shard != 1:
         raise click.UsageError("--assign does not work with --db-shard > 1")
+    if cohort:
+        for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
+                            ("--assign", assign), ("--db-shard > 1", db_shard != 1)):
+            if given:
+                raise click.UsageError(f"--cohort does not work with {flag}")
     argv = [driver_path(states), "-d", str(database), "-q", str(input_file), "-j", str(threads),
             "--omega", str(omega), "--mu", str(mu), "-o", str(outputdir)]
     if max_ram:
@@ -114,6 +125,8 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--assign"]
         if assign_mass is not None:
             argv += ["--assign-mass", repr(float(assign_mass))]
+    if cohort:
+        argv += ["--cohort"]
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 

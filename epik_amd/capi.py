@@ -87,6 +87,20 @@ EXPORTS = (
     "epik_amd_placer_confidence_strands",
     "epik_amd_placer_confidence_frames",
     "epik_amd_placer_confidence_mates",
+    "epik_amd_cohort_create",
+    "epik_amd_cohort_destroy",
+    "epik_amd_cohort_reset",
+    "epik_amd_cohort_info",
+    "epik_amd_cohort_read",
+    "epik_amd_cohort_add_cells",
+    "epik_amd_cohort_add_device",
+    "epik_amd_cohort_kr_device",
+    "epik_amd_cohort_kr",
+    "epik_amd_cohort_kr_host",
+    "epik_amd_placer_cohort_reads",
+    "epik_amd_placer_cohort_strands",
+    "epik_amd_placer_cohort_frames",
+    "epik_amd_placer_cohort_mates",
 )
 
 
@@ -366,6 +380,32 @@ def load() -> ctypes.CDLL:
     for name in ("epik_amd_placer_confidence_strands", "epik_amd_placer_confidence_frames", "epik_amd_placer_confidence_mates"):
         getattr(lib, name).restype = i32
         getattr(lib, name).argtypes = [vp, vp, vp, u64, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp]
+    # (a cohort of samples: the profile's entries with a sample per read, and the KR distance between the samples)
+    lib.epik_amd_cohort_create.restype = i32
+    lib.epik_amd_cohort_create.argtypes = [vp, u32, ctypes.POINTER(vp)]
+    lib.epik_amd_cohort_destroy.restype = None
+    lib.epik_amd_cohort_destroy.argtypes = [vp]
+    lib.epik_amd_cohort_reset.restype = i32
+    lib.epik_amd_cohort_reset.argtypes = [vp]
+    lib.epik_amd_cohort_info.restype = i32
+    lib.epik_amd_cohort_info.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    lib.epik_amd_cohort_read.restype = i32
+    lib.epik_amd_cohort_read.argtypes = [vp, vp, vp, vp, ctypes.POINTER(u64)]
+    lib.epik_amd_cohort_add_cells.restype = i32
+    lib.epik_amd_cohort_add_cells.argtypes = [vp, vp, vp, vp]
+    lib.epik_amd_cohort_add_device.restype = i32
+    lib.epik_amd_cohort_add_device.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp]
+    lib.epik_amd_cohort_kr_device.restype = i32
+    lib.epik_amd_cohort_kr_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.epik_amd_cohort_kr.restype = i32
+    lib.epik_amd_cohort_kr.argtypes = [vp, vp, vp, vp]
+    lib.epik_amd_cohort_kr_host.restype = i32
+    lib.epik_amd_cohort_kr_host.argtypes = [vp, u32, u32, vp, vp, vp]
+    lib.epik_amd_placer_cohort_reads.restype = i32
+    lib.epik_amd_placer_cohort_reads.argtypes = [vp, vp, vp, vp, vp, vp, u64]
+    for name in ("epik_amd_placer_cohort_strands", "epik_amd_placer_cohort_frames", "epik_amd_placer_cohort_mates"):
+        getattr(lib, name).restype = i32
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, vp, u64, u32, vp]
     _lib = lib
     return lib
 

@@ -1,0 +1,234 @@
+"""A cohort of samples placed on one tree (`epik_amd_cohort`, include/epik_amd.h): per sample the cells of a profile
+(`mass`, `best`, totals), summed on the device from the rows a placement left there with a sample per read, and the
+phylogenetic Kantorovich-Rubinstein distance between every two samples, computed there from those cells.  Integers
+and a strictly sequential sum per pair: the same bits whatever the order, the grid, the stream or the devices.
+
+`Cohort` is the ctypes side of the device object; `kr_host` the rule on the host (no device); `first_of` gives the
+first[] of a tree from its parents; `format_*` / `read_*` are the files the drivers write with --cohort
+(epik_amd/host/cohort.cpp and main.cpp write the same bytes).
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import capi
+from .profile import TOTALS
+
+SAMPLES_HEADER = "name\trecords\tplaced\tno_hit\ttoo_short\ttoo_narrow\ttotal_mass_q"
+PROFILE_HEADER = "name\tedge_num\tbest\tmass_q"
+_TOTALS_DTYPE = np.dtype([(k, "<u8") for k in TOTALS])
+
+
+def first_of(parent) -> np.ndarray:
+    """first[b] = b - size[b] + 1 of every post-order id, from parent[] (the root's: -1 or capi.TREE_NO_PARENT)."""
+    parent = np.asarray(parent, dtype=np.int64)
+    n = len(parent)
+    first = np.arange(n, dtype=np.int64)
+    for b in range(n - 1):
+        p = int(parent[b])
+        if not b < p < n:
+            raise ValueError(f"branch {b}: the parent {p} is not above its child")
+        first[p] = min(first[p], first[b])
+    return first.astype(np.uint32)
+
+
+def kr_host(mass, first, branch_length) -> np.ndarray:
+    """KR(s, t) of the rule for mass[S][N] on the host (`epik_amd_cohort_kr_host`): float64 [S][S]."""
+    lib = capi.load()
+    mass = np.ascontiguousarray(mass, dtype=np.uint64)
+    if mass.ndim != 2:
+        raise ValueError("mass must be [num_samples][num_branches]")
+    first = np.ascontiguousarray(first, dtype=np.uint32)
+    length = np.ascontiguousarray(branch_length, dtype=np.float64)
+    s, n = mass.shape
+    if first.shape != (n,) or length.shape != (n,):
+        raise ValueError(f"first and branch_length must hold one value per branch ({n})")
+    out = np.full((s, s), np.nan, dtype=np.float64)
+    capi.check(lib.epik_amd_cohort_kr_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, out.ctypes.data))
+    return out
+
+
+@dataclass
+class CohortCells:
+    """What a cohort holds on the host: `mass` and `best` uint64 [S][N], `totals` a record array [S] with the fields
+    of `epik_amd_profile_totals`, and `bad_samples`."""
+
+    mass: np.ndarray
+    best: np.ndarray
+    totals: np.ndarray
+    bad_samples: int = 0
+
+    def records(self) -> np.ndarray:
+        t = self.totals
+        return t["placed"] + t["no_hit"] + t["too_short"] + t["too_narrow"]
+
+
+class Cohort:
+    """A device cohort of `num_samples` samples for one placer (`epik_amd_cohort_create`): all zero at first.  A context
+    manager; `close()` frees it."""
+
+    def __init__(self, placer, num_samples: int):
+        self._lib = capi.load()
+        self._handle = ctypes.c_void_p()
+        if not 0 <= int(num_samples) <= 0xFFFFFFFF:
+            raise ValueError("num_samples must fit 32 bits")
+        capi.check(self._lib.epik_amd_cohort_create(placer._handle, int(num_samples), ctypes.byref(self._handle)))
+        self.device = placer.device
+        self.num_samples = int(num_samples)
+        self.num_branches = placer.num_branches
+        self.keep_at_most = placer.keep_at_most
+
+    def close(self) -> None:
+        if getattr(self, "_handle", None):
+            self._lib.epik_amd_cohort_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def lds_path(self) -> bool:
+        """Whether add_device sums the current sample in LDS first (else straight into global memory)."""
+        lds = ctypes.c_uint32(0)
+        capi.check(self._lib.epik_amd_cohort_info(self._handle, None, None, ctypes.byref(lds)))
+        return bool(lds.value)
+
+    def add_device(self, d_rows: int, d_n_rows: int, d_kmer_counts: int, d_samples: int, n: int, d_weights: int = 0,
+                   stream: int = 0) -> None:
+        """Device pointers, asynchronous on `stream` (`epik_amd_cohort_add_device`): read i goes to row d_samples[i]
+        (uint32); `d_weights` 0: every read once."""
+        capi.check(self._lib.epik_amd_cohort_add_device(self._handle, d_rows or None, d_n_rows or None, d_kmer_counts or None,
+                                                        d_weights or None, d_samples or None, int(n), stream or None))
+
+    def read(self) -> CohortCells:
+        """Synchronises the device and returns the cells (`epik_amd_cohort_read`)."""
+        shape = (self.num_samples, self.num_branches)
+        mass, best = np.zeros(shape, np.uint64), np.zeros(shape, np.uint64)
+        totals = np.zeros(self.num_samples, dtype=_TOTALS_DTYPE)
+        bad = ctypes.c_uint64(0)
+        capi.check(self._lib.epik_amd_cohort_read(self._handle, mass.ctypes.data, best.ctypes.data, totals.ctypes.data,
+                                                  ctypes.byref(bad)))
+        return CohortCells(mass, best, totals, int(bad.value))
+
+    def add_cells(self, mass=None, best=None, totals=None) -> None:
+        """Host arrays of the shapes `read` gives (each may be None) added in: merging the cohorts of several devices."""
+        shape = (self.num_samples, self.num_branches)
+        ptrs = []
+        keep = []
+        for arr in (mass, best):
+            if arr is None:
+                ptrs.append(None)
+                continue
+            arr = np.ascontiguousarray(arr, dtype=np.uint64)
+            if arr.shape != shape:
+                raise ValueError(f"cells must be {shape}, not {arr.shape}")
+            keep.append(arr)
+            ptrs.append(arr.ctypes.data)
+        if totals is None:
+            ptrs.append(None)
+        else:
+            totals = np.ascontiguousarray(totals, dtype=_TOTALS_DTYPE)
+            if totals.shape != (self.num_samples,):
+                raise ValueError(f"totals must hold one record per sample ({self.num_samples})")
+            keep.append(totals)
+            ptrs.append(totals.ctypes.data)
+        capi.check(self._lib.epik_amd_cohort_add_cells(self._handle, *ptrs))
+
+    def _lengths(self, tree, branch_length) -> np.ndarray:
+        length = np.ascontiguousarray(branch_length, dtype=np.float64)
+        if length.shape != (self.num_branches,):
+            raise ValueError(f"branch_length must hold one value per branch ({self.num_branches})")
+        if tree is None or not getattr(tree, "_handle", None):
+            raise ValueError("kr needs a device tree (Placer.tree)")
+        return length
+
+    def kr_device(self, tree, branch_length, d_out: int, stream: int = 0) -> None:
+        """KR(s, t) into d_out, float64 [S][S] in device memory, every cell written; asynchronous on `stream` once the
+        lengths (host) are copied (`epik_amd_cohort_kr_device`)."""
+        length = self._lengths(tree, branch_length)
+        capi.check(self._lib.epik_amd_cohort_kr_device(self._handle, tree._handle, length.ctypes.data, d_out or None,
+                                                       stream or None))
+
+    def kr(self, tree, branch_length) -> np.ndarray:
+        """KR(s, t) for all pairs, float64 [S][S] (`epik_amd_cohort_kr`)."""
+        length = self._lengths(tree, branch_length)
+        out = np.full((self.num_samples, self.num_samples), np.nan, dtype=np.float64)
+        capi.check(self._lib.epik_amd_cohort_kr(self._handle, tree._handle, length.ctypes.data, out.ctypes.data))
+        return out
+
+    def reset(self) -> None:
+        capi.check(self._lib.epik_amd_cohort_reset(self._handle))
+
+
+# ---- the files of --cohort -------------------------------------------------------------------------------------------
+def format_samples_tsv(names, cells: CohortCells) -> str:
+    lines = [SAMPLES_HEADER]
+    records = cells.records()
+    for s, name in enumerate(names):
+        t = cells.totals[s]
+        total_mass = int(cells.mass[s].sum(dtype=np.uint64))
+        lines.append(f"{name}\t{int(records[s])}\t{int(t['placed'])}\t{int(t['no_hit'])}\t{int(t['too_short'])}"
+                     f"\t{int(t['too_narrow'])}\t{total_mass}")
+    return "\n".join(lines) + "\n"
+
+
+def format_profile_tsv(names, cells: CohortCells) -> str:
+    lines = [PROFILE_HEADER]
+    for s, name in enumerate(names):
+        for b in np.flatnonzero((cells.mass[s] != 0) | (cells.best[s] != 0)):
+            lines.append(f"{name}\t{int(b)}\t{int(cells.best[s, b])}\t{int(cells.mass[s, b])}")
+    return "\n".join(lines) + "\n"
+
+
+def format_kr_tsv(names, kr) -> str:
+    lines = ["\t".join(["name", *names])]
+    for s, name in enumerate(names):
+        lines.append("\t".join([name, *("%.17g" % float(x) for x in kr[s])]))
+    return "\n".join(lines) + "\n"
+
+
+def read_samples_tsv(path: str):
+    """(names, {column: uint64 array})"""
+    with open(path, newline="") as fh:
+        if fh.readline().rstrip("\n") != SAMPLES_HEADER:
+            raise ValueError(f"{path}: not a cohort samples file")
+        rows = [line.rstrip("\n").split("\t") for line in fh]
+    cols = SAMPLES_HEADER.split("\t")[1:]
+    return [r[0] for r in rows], {c: np.array([int(r[i + 1]) for r in rows], dtype=np.uint64) for i, c in enumerate(cols)}
+
+
+def read_profile_tsv(path: str, names, num_branches: int):
+    """(mass, best), uint64 [S][N], from the long-format file."""
+    index = {name: s for s, name in enumerate(names)}
+    mass = np.zeros((len(names), num_branches), np.uint64)
+    best = np.zeros_like(mass)
+    with open(path, newline="") as fh:
+        if fh.readline().rstrip("\n") != PROFILE_HEADER:
+            raise ValueError(f"{path}: not a cohort profile file")
+        for line in fh:
+            name, edge, b, m = line.rstrip("\n").split("\t")
+            mass[index[name], int(edge)] = int(m)
+            best[index[name], int(edge)] = int(b)
+    return mass, best
+
+
+def read_kr_tsv(path: str):
+    """(names, float64 [S][S])"""
+    with open(path, newline="") as fh:
+        names = fh.readline().rstrip("\n").split("\t")[1:]
+        rows = [line.rstrip("\n").split("\t") for line in fh]
+    if [r[0] for r in rows] != names:
+        raise ValueError(f"{path}: the rows do not follow the first line's names")
+    return names, np.array([[float(x) for x in r[1:]] for r in rows], dtype=np.float64).reshape(len(names), len(names))

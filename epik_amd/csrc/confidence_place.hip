@@ -272,6 +272,13 @@ int confidence_host_chunked(epik_amd_placer *p, const ConfidenceRequest &req, co
     return place_host_chunked(p, seqs, seq_offsets, n, mode, longest_placed, v, rows, n_rows, kmer_counts, label, &sink);
 }
 
+int tree_first_device(const epik_amd_tree *tree, int *device, uint32_t *num_branches, const uint32_t **d_first)
+{
+    if (!tree) return fail_with(EPIK_AMD_ERR_INVALID, "null tree");
+    *device = tree->device, *num_branches = tree->num_branches, *d_first = tree->view.first;
+    return EPIK_AMD_OK;
+}
+
 }  // namespace epik_amd
 
 extern "C" {

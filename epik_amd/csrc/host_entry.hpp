@@ -248,5 +248,15 @@ int confidence_host_chunked(epik_amd_placer *p, const ConfidenceRequest &req, co
                             uint64_t n, uint32_t mode, uint64_t longest_placed, const HostVariant &v, epik_amd_placement *rows,
                             uint32_t *n_rows, uint32_t *kmer_counts, uint8_t *label);
 
+// What the cohort's KR distance needs of a tree (confidence_place.hip owns the object): its device, N and first[] there.
+int tree_first_device(const epik_amd_tree *tree, int *device, uint32_t *num_branches, const uint32_t **d_first);
+
+// The cohort host entry of a variant (cohort_place.hip), once the caller has checked the handle, the mode and the reads
+// (n >= 1, check_host_reads): profile_host_chunked with item i added to row samples[i] of `cohort` (HOST uint32 [n]);
+// weights and samples are uploaded once and every chunk's add takes both offset by the chunk's first item.
+int cohort_host_chunked(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
+                        const uint32_t *weights, const uint32_t *samples, uint64_t n, uint32_t mode, uint64_t longest_placed,
+                        const HostVariant &v, uint8_t *label);
+
 }  // namespace epik_amd
 #endif

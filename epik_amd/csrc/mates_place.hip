@@ -297,6 +297,21 @@ int epik_amd_placer_profile_mates(epik_amd_placer *p, epik_amd_profile *profile,
     }
 }
 
+int epik_amd_placer_cohort_mates(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
+                                  const uint32_t *weights, const uint32_t *samples, uint64_t n_pairs, uint32_t mode, uint8_t *strand)
+{
+    try {  // (profile_mates with a row of cells per sample: cohort_place.hip)
+        if (const int rc = check_handle(p, mode); rc != EPIK_AMD_OK) return rc;
+        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+        if (n_pairs == 0) return EPIK_AMD_OK;
+        uint64_t longest = 0;
+        if (const int rc = check_host_pairs(seqs, seq_offsets, n_pairs, longest); rc != EPIK_AMD_OK) return rc;
+        return cohort_host_chunked(p, cohort, seqs, seq_offsets, weights, samples, n_pairs, mode, longest, kMatesHost, strand);
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_mates: ") + e.what());
+    }
+}
+
 int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n_pairs,
                                        uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
                                        uint8_t *strand, const epik_amd_tree *tree, uint32_t tau_q, epik_amd_confidence *conf,

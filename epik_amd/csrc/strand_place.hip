@@ -275,6 +275,21 @@ int epik_amd_placer_profile_strands(epik_amd_placer *p, epik_amd_profile *profil
     }
 }
 
+int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
+                                    const uint32_t *weights, const uint32_t *samples, uint64_t n, uint32_t mode, uint8_t *strand)
+{
+    try {  // (profile_strands with a row of cells per sample: cohort_place.hip)
+        if (const int rc = check_handle(p, mode); rc != EPIK_AMD_OK) return rc;
+        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+        if (n == 0) return EPIK_AMD_OK;
+        uint64_t longest = 0;
+        if (const int rc = check_host_reads(seqs, seq_offsets, n, longest); rc != EPIK_AMD_OK) return rc;
+        return cohort_host_chunked(p, cohort, seqs, seq_offsets, weights, samples, n, mode, longest, kStrandHost, strand);
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_strands: ") + e.what());
+    }
+}
+
 int epik_amd_placer_confidence_strands(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
                                          uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
                                          uint8_t *strand, const epik_amd_tree *tree, uint32_t tau_q, epik_amd_confidence *conf,

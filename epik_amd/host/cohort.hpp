@@ -1,0 +1,68 @@
+// cohort.hpp -- a cohort of samples on the host: the rule of include/epik_amd.h (epik_amd_cohort) over rows in host
+// memory, the sum of cohorts, and the Kantorovich-Rubinstein distance between every two samples by the rule's
+// sequential loop.  libepik_amd's cohort_add_kernel and cohort_kr_kernel are the same rule on the device; both give the
+// same bits (this file is compiled with -ffp-contract=off, and epik_amd_cohort_kr_host is kr_matrix below).
+// No reference counterpart: the reference leaves sums and distances over jplace files to a second tool.
+// Needs nothing but the C header: libepik_amd compiles cohort.cpp too.
+#ifndef EPIK_AMD_HOST_COHORT_HPP
+#define EPIK_AMD_HOST_COHORT_HPP
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "epik_amd.h"
+
+namespace epik_amd {
+
+struct sample_cohort {
+    uint32_t num_samples = 0, num_branches = 0;
+    std::vector<uint64_t> mass;  // [num_samples][num_branches]
+    std::vector<uint64_t> best;  // [num_samples][num_branches]
+    std::vector<epik_amd_profile_totals> totals;  // [num_samples]
+    uint64_t bad_samples = 0;    // reads whose sample is >= num_samples: they add to no row
+
+    sample_cohort() = default;
+    sample_cohort(uint32_t samples, uint32_t branches)
+        : num_samples(samples), num_branches(branches), mass((size_t)samples * branches, 0), best((size_t)samples * branches, 0),
+          totals(samples, epik_amd_profile_totals{})
+    {
+    }
+
+    /// n reads in the form of the C ABI, read i of sample samples[i]: rows[n][keep], n_rows[n], kmer_counts[n][keep],
+    /// weights[n] (nullptr: 1)
+    void add_rows(const epik_amd_placement* rows, const uint32_t* n_rows, const uint32_t* kmer_counts, const uint32_t* weights,
+                  const uint32_t* samples, uint64_t n, uint32_t keep);
+    /// what a device cohort holds (epik_amd_cohort_read), or another host cohort: integer sums
+    void add_cells(const uint64_t* other_mass, const uint64_t* other_best, const epik_amd_profile_totals* other_totals);
+    void merge(const sample_cohort& other);
+};
+
+/// KR(s, t) of the rule for all pairs into out[num_samples][num_samples].  0, or EPIK_AMD_ERR_INVALID with `err`
+/// naming the branch whose first[] or length is not valid.
+int kr_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+              const double* branch_length, double* out, std::string& err);
+
+/// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
+/// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
+/// name or path, a name given before, or a file that cannot be read; and for a list without any sample.
+struct cohort_sample {
+    std::string name, path;
+};
+std::vector<cohort_sample> read_cohort_list(const std::string& list_file);
+
+/// <output_dir>/cohort_<what>_<basename(list)>.tsv, what = samples | profile | kr
+std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir);
+
+/// cohort_samples: a header line, then per sample in list order name, records, placed, no_hit, too_short, too_narrow,
+/// total_mass_q.  cohort_profile: long format, name, edge_num, best, mass_q for every (sample, branch) cell with a
+/// non-zero best or mass_q, samples in list order, branches by edge_num (the post-order id, the jplace's number).
+/// cohort_kr: a first line of names, then per sample its name and the distances to every sample as %.17g.
+std::string format_cohort_samples_tsv(const std::vector<cohort_sample>& samples, const sample_cohort& cohort);
+std::string format_cohort_profile_tsv(const std::vector<cohort_sample>& samples, const sample_cohort& cohort);
+std::string format_cohort_kr_tsv(const std::vector<cohort_sample>& samples, const std::vector<double>& kr);
+/// `text` into `filename` through `filename`.part, renamed when all of it is written
+void write_through_part(const std::string& filename, const std::string& text);
+
+}  // namespace epik_amd
+#endif

@@ -1,0 +1,90 @@
+// cohort_test.cpp -- the host cohort (cohort.cpp) driven from files, for tests/test_cohort_cpu.py; needs no GPU and no
+// libepik_amd.
+//   cohort_test add <out.bin> <in.bin>...   the cohort of every input, merged: uint64 mass[S][N], best[S][N],
+//                                           totals[S][5], bad_samples
+//   cohort_test kr <out.bin> <in.bin>       the KR matrix, float64 [S][S]
+// An `add` input holds, little endian: uint64 n, keep, num_branches, num_samples; epik_amd_placement rows[n][keep];
+// uint32 n_rows[n]; uint32 kmer_counts[n][keep]; uint32 weights[n]; uint32 samples[n].
+// A `kr` input: uint64 num_samples, num_branches; uint64 mass[S][N]; uint32 first[N]; float64 branch_length[N].
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "cohort.hpp"
+
+namespace {
+
+template <typename T>
+std::vector<T> read_array(std::ifstream& in, size_t count)
+{
+    std::vector<T> v(count);
+    in.read(reinterpret_cast<char*>(v.data()), (std::streamsize)(count * sizeof(T)));
+    if (!in) throw std::runtime_error("input file too short");
+    return v;
+}
+
+template <typename T>
+void write_array(std::ofstream& out, const T* data, size_t count)
+{
+    out.write(reinterpret_cast<const char*>(data), (std::streamsize)(count * sizeof(T)));
+}
+
+}  // namespace
+
+int main(int argc, char** argv)
+{
+    try {
+        if (argc >= 4 && std::strcmp(argv[1], "add") == 0) {
+            epik_amd::sample_cohort total;
+            for (int i = 3; i < argc; ++i) {
+                std::ifstream in(argv[i], std::ios::binary);
+                if (!in) throw std::runtime_error(std::string("cannot open ") + argv[i]);
+                const auto head = read_array<uint64_t>(in, 4);
+                const uint64_t n = head[0], keep = head[1];
+                const auto rows = read_array<epik_amd_placement>(in, n * keep);
+                const auto n_rows = read_array<uint32_t>(in, n);
+                const auto counts = read_array<uint32_t>(in, n * keep);
+                const auto weights = read_array<uint32_t>(in, n);
+                const auto samples = read_array<uint32_t>(in, n);
+                epik_amd::sample_cohort part((uint32_t)head[3], (uint32_t)head[2]);
+                part.add_rows(rows.data(), n_rows.data(), counts.data(), weights.data(), samples.data(), n, (uint32_t)keep);
+                if (i == 3)
+                    total = part;
+                else
+                    total.merge(part);
+            }
+            std::ofstream out(argv[2], std::ios::binary);
+            write_array(out, total.mass.data(), total.mass.size());
+            write_array(out, total.best.data(), total.best.size());
+            write_array(out, total.totals.data(), total.totals.size());
+            write_array(out, &total.bad_samples, 1);
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
+        if (argc == 4 && std::strcmp(argv[1], "kr") == 0) {
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            const auto mass = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const auto length = read_array<double>(in, N);
+            std::vector<double> kr(S * S);
+            std::string err;
+            if (epik_amd::kr_matrix(mass.data(), (uint32_t)S, (uint32_t)N, first.data(), length.data(), kr.data(), err) != 0)
+                throw std::runtime_error(err);
+            std::ofstream out(argv[2], std::ios::binary);
+            write_array(out, kr.data(), kr.size());
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
+        std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin>\n";
+        return 2;
+    } catch (const std::exception& error) {
+        std::cerr << "Error: " << error.what() << std::endl;
+        return 1;
+    }
+}

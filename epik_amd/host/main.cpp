@@ -11,7 +11,9 @@
 // every batch is placed by all of them together -- a database larger than one device's memory); --profile /
 // --profile-only (the sample's abundance profile, profile.hpp: beside the jplace, or instead of it and summed on the
 // devices); --mates FILE (paired-end reads: the second mates, one placement per pair); --assign [--assign-mass T] (per
-// record the LCA clade that holds T of its placement mass and the EDPL, confidence.hpp, computed on the devices).
+// record the LCA clade that holds T of its placement mass and the EDPL, confidence.hpp, computed on the devices);
+// --cohort (the query is a list of samples: their profiles and the KR distance between every two of them, cohort.hpp,
+// summed and computed on the devices, no jplace).
 // The two binaries differ as the reference's do (epik/CMakeLists.txt:72,124): epik-dna
 // accepts DNA databases, epik-aa protein ones.
 #include <algorithm>
@@ -37,6 +39,7 @@
 #include <string>
 #include <vector>
 
+#include "cohort.hpp"
 #include "confidence.hpp"
 #include "jplace.hpp"
 #include "phylo_kmer_db.hpp"
@@ -211,6 +214,12 @@ const char* kHelp =
     "                          the records assigned to each branch and clade; computed on the device(s) (not with\n"
     "                          --db-shard > 1; with --profile-only the rows still never leave the device)\n"
     "      --assign-mass arg   Share of a record's placement mass its clade must hold, in [0, 1] (default: 0.95)\n"
+    "      --cohort            The query is a list of samples, one name<TAB>path line each (paths relative to the list; blank\n"
+    "                          and # lines skipped).  Writes no jplace but cohort_samples_<list>.tsv (records per sample),\n"
+    "                          cohort_profile_<list>.tsv (name, edge_num, best, mass_q of every non-zero cell) and\n"
+    "                          cohort_kr_<list>.tsv (the Kantorovich-Rubinstein distance between every two samples), summed\n"
+    "                          and computed on the device(s); with --strand / --translate, not with --mates, --profile,\n"
+    "                          --profile-only, --assign or --db-shard > 1\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -251,7 +260,7 @@ options parse_args(int argc, char** argv)
         } else {
             continue;  // positional arguments are ignored (epik.py passes the query twice, epik.py:88,96)
         }
-        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign") && !have_value)) {  // flags
+        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort") && !have_value)) {  // flags
             opt.values[name] = "1";
             continue;
         }
@@ -349,6 +358,15 @@ int main(int argc, char** argv)
             if (used != text.size() || used == 0) throw std::runtime_error("--assign-mass must be a number in [0, 1], not '" + text + "'");
             assign_tau_q = epik_amd::assign_tau_q(tau);
         }
+        // --cohort: checked before anything is opened or any device touched
+        const bool with_cohort = parsed.has("cohort");
+        if (with_cohort) {
+            for (const char* other : {"mates", "profile-only", "profile", "assign"})
+                if (parsed.has(other)) throw std::runtime_error(std::string("--cohort does not work with --") + other);
+            if (std::stoul(parsed.get("db-shard", "1")) > 1)
+                throw std::runtime_error("--cohort does not work with --db-shard > 1 (the rows of a sharded placement are finished "
+                                         "on several devices)");
+        }
         const auto db_file = parsed.require("database");
         const auto query_file = parsed.require("query");
         const auto num_threads = (size_t)std::stoul(parsed.get("jobs", "1"));
@@ -359,6 +377,9 @@ int main(int argc, char** argv)
         const auto keep_factor = std::stod(parsed.get("keep-factor", "0.01"));
         const auto output_dir = parsed.require("output-dir");
         epik_amd::check_mu(user_mu);
+        // --cohort: the list of samples, every file of it looked at before the database or a device is
+        std::vector<epik_amd::cohort_sample> cohort_samples;
+        if (with_cohort) cohort_samples = epik_amd::read_cohort_list(query_file);
 
         size_t max_entries = std::numeric_limits<size_t>::max();
         if (parsed.has("max-ram")) {
@@ -423,6 +444,7 @@ int main(int argc, char** argv)
         if (translate) placer.set_translate(frames);
         if (with_mates) placer.set_mates(orientation_name == "ff" ? epik_amd::mate_orientation::ff : epik_amd::mate_orientation::fr);
         if (profile_only) placer.set_profile_only();
+        if (with_cohort) placer.set_cohort((uint32_t)cohort_samples.size());
         // --assign: the rule's tree on every device; the host's copy names clade sizes and sums the clades
         std::unique_ptr<epik_amd::confidence_tree> assign_tree;
         if (with_assign) {
@@ -436,7 +458,7 @@ int main(int argc, char** argv)
 
         // --profile-only: no jplace at all
         std::unique_ptr<epik_amd::io::jplace_writer> jplace;
-        if (!profile_only) {
+        if (!profile_only && !with_cohort) {
             jplace.reset(new epik_amd::io::jplace_writer(jplace_filename, invocation, tree_as_newick));
             jplace->set_branch_lengths(placer.distal_lengths(), placer.pendant_lengths());
             jplace->start();
@@ -446,7 +468,7 @@ int main(int argc, char** argv)
         const auto profile_filename = epik_amd::make_profile_filename(query_file, output_dir);
         // --strand reverse|both: one "name<TAB>+|-" line per input record, input order
         std::ofstream strands_out;
-        if (strand != epik_amd::strand_mode::forward) {
+        if (strand != epik_amd::strand_mode::forward && !with_cohort) {
             strands_out.open(make_strands_filename(query_file, output_dir));
             if (!strands_out) throw std::runtime_error("Could not open " + make_strands_filename(query_file, output_dir));
         }
@@ -463,14 +485,15 @@ int main(int argc, char** argv)
         }
         // --translate: one "name<TAB>+1..-3" line per input record, input order
         std::ofstream frames_out;
-        if (translate) {
+        if (translate && !with_cohort) {
             frames_out.open(make_frames_filename(query_file, output_dir));
             if (!frames_out) throw std::runtime_error("Could not open " + make_frames_filename(query_file, output_dir));
         }
 
         std::cout << "Instruction set: gfx950 (" << placer.handle_count()
                   << (db_shards > 1 ? " shard(s) of the database, one handle each)" : " device(s))") << std::endl;
-        std::cout << "Placing " << query_file << "..." << std::endl;
+        std::cout << "Placing " << query_file << (with_cohort ? " (" + std::to_string(cohort_samples.size()) + " samples)" : std::string())
+                  << "..." << std::endl;
         const auto begin = std::chrono::steady_clock::now();
         size_t num_seq_placed = 0;
         double average_speed = 0.0;
@@ -486,6 +509,8 @@ int main(int argc, char** argv)
         constexpr size_t kGroupBatches = 64;
         struct work_item {
             size_t sequence = 0;                          // position of the batch in the input
+            uint32_t sample = 0;                          // --cohort: the sample the batch belongs to
+            std::shared_ptr<epik_amd::io::batch_fasta> file;  // ... and its file, mapped while a batch of it is on its way
             std::vector<epik_amd::seq_record> batch;     // owns the bytes the views below point into
             std::vector<epik_amd::seq_record> mates;     // --mates: the second mate of every record of the batch
             epik_amd::impl::placed_batch placed;
@@ -499,16 +524,40 @@ int main(int argc, char** argv)
         std::vector<stage_clock> place_clocks(n_devices);
         std::mutex stats_mutex;
         // (the records of a batch are views into the reader's mapping of the file: it stays until all is written)
-        epik_amd::io::batch_fasta reader(query_file, batch_size);
+        // (--cohort: the query is the list; every sample's file is opened when its turn comes)
+        std::unique_ptr<epik_amd::io::batch_fasta> reader;
+        if (!with_cohort) reader.reset(new epik_amd::io::batch_fasta(query_file, batch_size));
         // --mates: read in step with the query, record for record
         std::unique_ptr<epik_amd::io::batch_fasta> mates_reader;
         if (with_mates) mates_reader.reset(new epik_amd::io::batch_fasta(parsed.require("mates"), batch_size));
         std::thread reader_thread([&] {
             try {
+                if (with_cohort) {
+                    // the samples in list order, every file in batches of its own: a batch never holds two samples, so
+                    // de-duplication stays per sample and a launch still takes the batches of many small samples
+                    size_t sequence = 0;
+                    bool open = true;
+                    for (uint32_t s = 0; s < cohort_samples.size() && open; ++s) {
+                        read_clock.start();
+                        auto file = std::make_shared<epik_amd::io::batch_fasta>(cohort_samples[s].path, batch_size);
+                        read_clock.stop();
+                        for (;;) {
+                            read_clock.start();
+                            auto batch = file->next_batch();
+                            read_clock.stop();
+                            if (batch.empty()) break;
+                            work_item item;
+                            item.sequence = sequence++, item.sample = s, item.file = file, item.batch = std::move(batch);
+                            if (!(open = to_place.push(std::move(item)))) break;
+                        }
+                    }
+                    to_place.close();
+                    return;
+                }
                 size_t records = 0;
                 for (size_t sequence = 0;; ++sequence) {
                     read_clock.start();
-                    auto batch = reader.next_batch();
+                    auto batch = reader->next_batch();
                     std::vector<epik_amd::seq_record> mates;
                     if (mates_reader) {
                         mates = mates_reader->next_batch();
@@ -529,7 +578,10 @@ int main(int argc, char** argv)
                         records += both;
                     }
                     read_clock.stop();
-                    if (batch.empty() || !to_place.push(work_item{sequence, std::move(batch), std::move(mates), {}})) break;
+                    if (batch.empty()) break;
+                    work_item item;
+                    item.sequence = sequence, item.batch = std::move(batch), item.mates = std::move(mates);
+                    if (!to_place.push(std::move(item))) break;
                 }
             } catch (...) {
                 reader_error = std::current_exception();
@@ -602,8 +654,11 @@ int main(int argc, char** argv)
                         place_clocks[device].start();
                         std::vector<const std::vector<epik_amd::seq_record>*> batches;
                         std::vector<const std::vector<epik_amd::seq_record>*> mate_batches;
-                        for (const auto& item : group) batches.push_back(&item.batch), mate_batches.push_back(&item.mates);
-                        auto placed = placer.place_flat(batches, device, num_threads, with_mates ? &mate_batches : nullptr);
+                        std::vector<uint32_t> batch_samples;
+                        for (const auto& item : group)
+                            batches.push_back(&item.batch), mate_batches.push_back(&item.mates), batch_samples.push_back(item.sample);
+                        auto placed = placer.place_flat(batches, device, num_threads, with_mates ? &mate_batches : nullptr,
+                                                        with_cohort ? &batch_samples : nullptr);
                         place_clocks[device].stop();
                         auto ms_diff = (float)std::chrono::duration_cast<std::chrono::microseconds>(
                                            std::chrono::steady_clock::now() - begin_group).count() / 1000.0f;
@@ -651,6 +706,18 @@ int main(int argc, char** argv)
             for (const auto& entry : db.tree_index()) subtree_num_nodes.push_back(entry.subtree_num_nodes);
             epik_amd::write_profile_tsv(profile_filename, profile, subtree_num_nodes);
         }
+        const auto cohort_samples_filename = epik_amd::make_cohort_filename("samples", query_file, output_dir);
+        const auto cohort_profile_filename = epik_amd::make_cohort_filename("profile", query_file, output_dir);
+        const auto cohort_kr_filename = epik_amd::make_cohort_filename("kr", query_file, output_dir);
+        if (with_cohort) {
+            // the handles' cohorts summed on the first device, read once, and the distances computed there
+            epik_amd::sample_cohort cohort((uint32_t)cohort_samples.size(), (uint32_t)tree.get_node_count());
+            std::vector<double> kr(cohort_samples.size() * cohort_samples.size());
+            placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data());
+            epik_amd::write_through_part(cohort_samples_filename, epik_amd::format_cohort_samples_tsv(cohort_samples, cohort));
+            epik_amd::write_through_part(cohort_profile_filename, epik_amd::format_cohort_profile_tsv(cohort_samples, cohort));
+            epik_amd::write_through_part(cohort_kr_filename, epik_amd::format_cohort_kr_tsv(cohort_samples, kr));
+        }
         if (with_assign) {
             assign_out.close();
             if (!assign_out) throw std::runtime_error("Could not write " + assign_filename + ".part");
@@ -671,6 +738,9 @@ int main(int argc, char** argv)
                   << " seq/s.\n";
         if (jplace) std::cout << "Output: " << jplace_filename << std::endl;
         if (with_profile) std::cout << "Profile: " << profile_filename << std::endl;
+        if (with_cohort)
+            std::cout << "Cohort samples: " << cohort_samples_filename << "\nCohort profile: " << cohort_profile_filename
+                      << "\nCohort distances: " << cohort_kr_filename << std::endl;
         if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;
         if (strands_out.is_open()) {
             strands_out.close();

@@ -26,6 +26,14 @@
 #pragma weak epik_amd_placer_confidence_strands
 #pragma weak epik_amd_placer_confidence_frames
 #pragma weak epik_amd_placer_confidence_mates
+#pragma weak epik_amd_cohort_create
+#pragma weak epik_amd_cohort_destroy
+#pragma weak epik_amd_cohort_read
+#pragma weak epik_amd_cohort_add_cells
+#pragma weak epik_amd_cohort_kr
+#pragma weak epik_amd_placer_cohort_reads
+#pragma weak epik_amd_placer_cohort_strands
+#pragma weak epik_amd_placer_cohort_frames
 
 namespace epik_amd {
 
@@ -203,6 +211,60 @@ void placer::set_assign(uint32_t tau_q)
     }
 }
 
+void placer::set_cohort(uint32_t num_samples)
+{
+    if (_sharded) throw std::runtime_error("GPU placer: --cohort does not work with --db-shard > 1");
+    if (_mates || profile_only() || assigning())
+        throw std::runtime_error("GPU placer: --cohort does not work with --mates, --profile-only or --assign");
+    if (!&epik_amd_cohort_create || !&epik_amd_cohort_destroy || !&epik_amd_cohort_read || !&epik_amd_cohort_add_cells ||
+        !&epik_amd_cohort_kr || !&epik_amd_placer_cohort_reads || !&epik_amd_placer_cohort_strands ||
+        !&epik_amd_placer_cohort_frames || !&epik_amd_tree_create || !&epik_amd_tree_destroy)
+        throw std::runtime_error("GPU placer: this libepik_amd has no device cohort");
+    if (!_cohorts.empty()) return;
+    _cohort_samples = num_samples;
+    for (auto* h : _handles) {
+        epik_amd_cohort* cohort = nullptr;
+        if (epik_amd_cohort_create(h, num_samples, &cohort) != EPIK_AMD_OK) {
+            const std::string message = epik_amd_last_error();
+            for (auto* made : _cohorts) epik_amd_cohort_destroy(made);
+            _cohorts.clear();
+            throw std::runtime_error("GPU placer: " + message);
+        }
+        _cohorts.push_back(cohort);
+    }
+}
+
+void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr)
+{
+    const auto check = [](int rc) {
+        if (rc != EPIK_AMD_OK) throw std::runtime_error(std::string("GPU placer: ") + epik_amd_last_error());
+    };
+    if (_cohorts.empty()) throw std::runtime_error("GPU placer: no cohort (set_cohort)");
+    // integer adds: the sum is the same bits whichever handle placed which batch
+    for (size_t g = 1; g < _cohorts.size(); ++g) {
+        check(epik_amd_cohort_read(_cohorts[g], mass, best, totals, nullptr));
+        check(epik_amd_cohort_add_cells(_cohorts[0], mass, best, totals));
+        epik_amd_cohort_destroy(_cohorts[g]);  // (summed once: a second read_cohort finds it all in the first)
+        _cohorts[g] = nullptr;
+    }
+    _cohorts.resize(1);
+    uint64_t bad_samples = 0;
+    check(epik_amd_cohort_read(_cohorts[0], mass, best, totals, &bad_samples));
+    if (bad_samples) throw std::runtime_error("GPU placer: " + std::to_string(bad_samples) + " reads of no sample of the cohort");
+    std::vector<uint32_t> parent;
+    std::vector<double> length;
+    for (const auto& node : _original_tree.nodes()) {
+        parent.push_back(node.parent < 0 ? EPIK_AMD_TREE_NO_PARENT : (uint32_t)node.parent);
+        length.push_back(node.branch_length);
+    }
+    epik_amd_tree* tree = nullptr;
+    check(epik_amd_tree_create(_devices[0], parent.data(), length.data(), (uint32_t)parent.size(), &tree));
+    const int rc = epik_amd_cohort_kr(_cohorts[0], tree, length.data(), kr);
+    const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
+    epik_amd_tree_destroy(tree);
+    if (rc != EPIK_AMD_OK) throw std::runtime_error("GPU placer: " + message);
+}
+
 void placer::read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_totals& totals) const
 {
     const size_t n = _original_tree.get_node_count();
@@ -222,6 +284,7 @@ void placer::read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_tota
 placer::~placer() noexcept
 {
     for (auto* profile : _profiles) epik_amd_profile_destroy(profile);
+    for (auto* cohort : _cohorts) epik_amd_cohort_destroy(cohort);
     for (auto* tree : _trees) epik_amd_tree_destroy(tree);
     for (auto* h : _handles) epik_amd_placer_destroy(h);
 }
@@ -257,11 +320,14 @@ inline uint64_t hash_bytes(std::string_view s)
 
 std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::vector<seq_record>*>& batches,
                                                    size_t device_index, size_t num_threads,
-                                                   const std::vector<const std::vector<seq_record>*>* mate_batches)
+                                                   const std::vector<const std::vector<seq_record>*>* mate_batches,
+                                                   const std::vector<uint32_t>* batch_samples)
 {
     if (device_index >= device_count()) throw std::runtime_error("GPU placer: no such device index");
     if (_mates != (mate_batches != nullptr) || (mate_batches && mate_batches->size() != batches.size()))
         throw std::runtime_error("GPU placer: a placer of pairs (set_mates) takes a batch of mates for every batch, any other none");
+    if (cohort_mode() != (batch_samples != nullptr) || (batch_samples && batch_samples->size() != batches.size()))
+        throw std::runtime_error("GPU placer: a placer of a cohort (set_cohort) takes the sample of every batch, any other none");
     const size_t per = _mates ? 2 : 1;  // reads a unique item sends through the boundary
     std::vector<impl::placed_batch> out(batches.size());
     // identical sequences of a batch are placed once (place.cpp:73-81, 207-212); the unique reads of
@@ -346,6 +412,28 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         }
     });
     const uint32_t mates_mode = (uint32_t)_strand | _mates_mode;
+    if (cohort_mode()) {
+        // the rows stay on the device and are summed there into the row of each batch's sample; nothing comes back
+        std::unique_ptr<uint32_t[]> weights(new uint32_t[n]), samples(new uint32_t[n]);
+        for (size_t b = 0; b < batches.size(); ++b)
+            for (size_t u = 0; u < out[b].size(); ++u) {
+                weights[first_unique[b] + u] = out[b].name_begin[u + 1] - out[b].name_begin[u];
+                samples[first_unique[b] + u] = (*batch_samples)[b];
+            }
+        auto* handle = _handles[device_index];
+        auto* cohort = _cohorts.size() > device_index ? _cohorts[device_index] : nullptr;
+        if (!cohort) throw std::runtime_error("GPU placer: the cohorts have been read (read_cohort ends a cohort placement)");
+        const int rc = _translate ? epik_amd_placer_cohort_frames(handle, cohort, bytes.get(), offsets.get(), weights.get(),
+                                                                  samples.get(), n, (uint32_t)_frames, nullptr)
+                       : _strand != strand_mode::forward
+                           ? epik_amd_placer_cohort_strands(handle, cohort, bytes.get(), offsets.get(), weights.get(),
+                                                            samples.get(), n, (uint32_t)_strand, nullptr)
+                           : epik_amd_placer_cohort_reads(handle, cohort, bytes.get(), offsets.get(), weights.get(),
+                                                          samples.get(), n);
+        if (rc != EPIK_AMD_OK) throw std::runtime_error(std::string("GPU placer: ") + epik_amd_last_error());
+        for (auto& pb : out) pb.row_begin.assign(pb.size() + 1, 0);
+        return out;
+    }
     if (profile_only()) {
         // the rows stay on the device and are summed there; what comes back is the strand / frame byte per sequence
         std::unique_ptr<uint32_t[]> weights(new uint32_t[n]);

@@ -123,7 +123,8 @@ public:
     /// their order.  A batch is then de-duplicated by the PAIR of sequences and every unique pair placed once.
     std::vector<impl::placed_batch> place_flat(const std::vector<const std::vector<seq_record>*>& batches,
                                                size_t device_index, size_t num_threads = 1,
-                                               const std::vector<const std::vector<seq_record>*>* mate_batches = nullptr);
+                                               const std::vector<const std::vector<seq_record>*>* mate_batches = nullptr,
+                                               const std::vector<uint32_t>* batch_samples = nullptr);
 
     /// How many callers may place at the same time (place_batches' device_index): the devices of a replicated
     /// database, ONE for a sharded one (all its handles work on every batch).
@@ -155,6 +156,16 @@ public:
     /// never leave the device, only the 16 bytes per sequence do.  Replicated databases only (not --db-shard).
     void set_assign(uint32_t tau_q);
     bool assigning() const noexcept { return !_trees.empty(); }
+    /// --cohort: one device cohort of `num_samples` samples per handle (epik_amd_cohort); from then on place_flat takes
+    /// the sample of every batch (`batch_samples`, one value a batch: a batch never holds two samples), leaves the rows
+    /// on the device and adds them to that sample's row there, every unique sequence with the number of its records as
+    /// weight; it returns batches without rows and without strand / frame bytes.  Replicated databases only.
+    void set_cohort(uint32_t num_samples);
+    bool cohort_mode() const noexcept { return !_cohorts.empty(); }
+    /// The cohorts of all handles summed into the first one's (epik_amd_cohort_add_cells), read back -- `mass` and `best`
+    /// of num_samples * num_branches cells each, `totals` of num_samples --, and the KR distance between every two
+    /// samples computed on that device: `kr` of num_samples * num_samples values.  Once, at the end.
+    void read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr);
     /// The profiles of all devices read back and summed; `mass` and `best` of num_branches cells each.
     void read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_totals& totals) const;
     /// distal_length / pendant_length of a placement on branch b (place.cpp:110-123, 435-437)
@@ -173,6 +184,8 @@ private:
     std::vector<int> _devices;               // ... and the device of each
     std::vector<epik_amd_profile*> _profiles;  // set_profile_only(): one per handle
     std::vector<epik_amd_tree*> _trees;        // set_assign(): one per handle
+    std::vector<epik_amd_cohort*> _cohorts;    // set_cohort(): one per handle
+    uint32_t _cohort_samples = 0;
     uint32_t _tau_q = 0;
     bool _sharded = false;
     strand_mode _strand = strand_mode::forward;

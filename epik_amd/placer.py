@@ -431,6 +431,48 @@ class Placer:
                       label.ctypes.data))
         return label
 
+    # -- a cohort of samples (epik_amd/cohort.py) -------------------------------------------------
+    def cohort(self, num_samples: int):
+        """A new, empty device cohort of `num_samples` samples for this placer (`epik_amd_cohort_create`)."""
+        from .cohort import Cohort
+        return Cohort(self, num_samples)
+
+    def cohort_packed(self, cohort, seqs: np.ndarray, seq_offsets: np.ndarray, samples, weights=None, strand=None,
+                      translate=None, mates=None):
+        """`profile_packed` with read (or pair) i added to row samples[i] of `cohort`: `epik_amd_placer_cohort_reads` /
+        `_strands` / `_frames` / `_mates`.  Returns the strand or frame byte per read or pair (None without `strand`,
+        `translate` and `mates`)."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+        n = int(seq_offsets.shape[0] - 1)
+        if strand is not None and translate is not None:
+            raise ValueError("strand and translate do not combine: translate=both already covers both strands")
+        if mates is not None:
+            if translate is not None:
+                raise ValueError("mates and translate do not combine: pairs are placed on nucleotide databases")
+            n = self._pairs_of(seq_offsets)
+        smp = np.ascontiguousarray(samples, dtype=np.uint32)
+        if smp.shape != (n,):
+            raise ValueError(f"samples must hold one value per read ({n}), not {smp.shape}")
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint32)
+        if w is not None and w.shape != (n,):
+            raise ValueError(f"weights must hold one value per read ({n}), not {w.shape}")
+        w_ptr = None if w is None else w.ctypes.data
+        if strand is None and translate is None and mates is None:
+            capi.check(self._lib.epik_amd_placer_cohort_reads(self._handle, cohort._handle, seqs.ctypes.data,
+                                                              seq_offsets.ctypes.data, w_ptr, smp.ctypes.data, n))
+            return None
+        label = np.zeros(n, dtype=np.uint8)
+        if mates is not None:
+            fn, mode = self._lib.epik_amd_placer_cohort_mates, self._mates_mode(strand or "forward", mates)
+        elif translate is not None:
+            fn, mode = self._lib.epik_amd_placer_cohort_frames, self._frame_mode(translate)
+        else:
+            fn, mode = self._lib.epik_amd_placer_cohort_strands, self._strand_mode(strand)
+        capi.check(fn(self._handle, cohort._handle, seqs.ctypes.data, seq_offsets.ctypes.data, w_ptr, smp.ctypes.data, n,
+                      mode, label.ctypes.data))
+        return label
+
     # -- placement confidence (epik_amd/confidence.py) ------------------------------------------
     def tree(self, parent, branch_length):
         """The tree of this placer's database on its device (`epik_amd_tree_create`): `parent[b]` of every post-order

@@ -649,6 +649,76 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
                                      uint8_t *strand, const epik_amd_tree *tree, uint32_t tau_q,
                                      epik_amd_confidence *conf, epik_amd_profile *profile, const uint32_t *weights);
 
+/*
+ * A cohort: the profiles of many samples placed on one tree, summed on the device, and the phylogenetic
+ * Kantorovich-Rubinstein (earth mover's) distance between every two of them.  No reference counterpart.  One rule
+ * (DESIGN.md 3.8); the kernels (cohort_place.hip), the host mirror (epik_amd/host/cohort.cpp) and the tests' numpy are
+ * worded after it and must agree bit for bit, the distances included.
+ *
+ * Cohort cells.  A cohort of S = num_samples samples over N = num_branches branches is S rows of
+ *   mass[N] | best[N] | totals[5], every cell a uint64 that wraps, laid out as a profile is.  Read i belongs to sample
+ *   samples[i] (uint32).  samples[i] < S: the read is added to that row by exactly the profile's rule above -- the four
+ *   classes in its order, q(lwr) = llrint(lwr * 2^30), the weights, bad_rows.  samples[i] >= S: the read adds to no row
+ *   and adds 1 (not its weight) to the cohort-wide counter bad_samples; nothing is written out of range.
+ *   Integer adds commute: the cells are the same bits whatever the order of the reads, the grouping of the samples, the
+ *   pieces, the grid, the stream or the number of devices whose cohorts are summed afterwards (add_cells).
+ *
+ * KR distance.  From mass[s][b], the tree's first[b] (the clade of b is the post-order id range [first[b], b]) and
+ *   branch_length[b], finite and >= 0.  Per sample s, in uint64 (wrapping; exact below 2^64):
+ *     T_s        = sum over b of mass[s][b]
+ *     clade_s[b] = sum over x = first[b] .. b of mass[s][x]        (a difference of the prefix sum)
+ *     below_s[b] = clade_s[b] - mass[s][b]
+ *     C_s[b] = (double)clade_s[b] / (double)T_s,  B_s[b] = (double)below_s[b] / (double)T_s
+ *   each one uint64 -> double conversion, round to nearest even, and one correctly rounded division.  A placement sits
+ *   at the middle of its branch (place.cpp:110, 435): below a point of the distal half of b lies below_s[b] of the mass,
+ *   of the proximal half clade_s[b].  Pendant lengths take no part.
+ *     KR(s, t) = acc after, for b = 0, 1, ..., N - 1 in THIS order, in double, nothing fused:
+ *                acc = acc + (0.5 * bl[b]) * (|C_s[b] - C_t[b]| + |B_s[b] - B_t[b]|),     acc = +0.0 at first
+ *   KR(s, s) = +0.0.  T_s == 0 or T_t == 0 and s != t: -1.0, no distance.  |x - y| = |y - x| bit for bit, so the matrix
+ *   is symmetric.  The sum over b is strictly sequential per pair: an implementation may share out the pairs, never
+ *   the branches of one pair.
+ *
+ * An epik_amd_cohort is an object of its own, created for a placer's device, num_branches and keep_at_most (whole
+ * databases only, not a k-mer-space shard) and num_samples >= 1; all zero at create() and after reset().
+ *   add_device  asynchronous on `stream`, allocates nothing: as epik_amd_profile_add_device, with d_samples (uint32 [n],
+ *               device memory, required).  Reads of one sample that lie together are summed in LDS first (info:
+ *               lds_path, the profile's limits and EPIK_AMD_PROFILE_LDS); any order is correct.
+ *   read        synchronises the device, then copies out mass[S][N], best[S][N], totals[S] and bad_samples (each may be
+ *               NULL).   add_cells: host arrays of those shapes (each may be NULL) added in -- merging devices.
+ *   kr_device   checks the tree (the cohort's device and N) and the lengths (HOST float64 [N]), synchronises the device,
+ *               copies the lengths, then enqueues the normalise and distance kernels on `stream`: d_out is float64
+ *               [S][S] in device memory, every cell written.  The first call allocates the workspace.   kr: the same
+ *               into host memory, synchronous.
+ *   kr_host     the rule on the host from mass[S][N] and first[N], no device at all; first[b] > b is refused.
+ * cohort_reads / _strands / _frames / _mates: the profile_* twins with samples[n] (HOST uint32) beside the weights.
+ */
+typedef struct epik_amd_cohort epik_amd_cohort;
+int epik_amd_cohort_create(const epik_amd_placer *p, uint32_t num_samples, epik_amd_cohort **out);
+void epik_amd_cohort_destroy(epik_amd_cohort *cohort);
+int epik_amd_cohort_reset(epik_amd_cohort *cohort);
+int epik_amd_cohort_info(const epik_amd_cohort *cohort, uint32_t *num_samples, uint32_t *num_branches, uint32_t *lds_path);
+int epik_amd_cohort_read(epik_amd_cohort *cohort, uint64_t *mass, uint64_t *best, epik_amd_profile_totals *totals,
+                         uint64_t *bad_samples);
+int epik_amd_cohort_add_cells(epik_amd_cohort *cohort, const uint64_t *mass, const uint64_t *best,
+                              const epik_amd_profile_totals *totals);
+int epik_amd_cohort_add_device(epik_amd_cohort *cohort, const void *d_rows, const void *d_n_rows, const void *d_kmer_counts,
+                               const void *d_weights, const void *d_samples, uint64_t n, void *stream);
+int epik_amd_cohort_kr_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out,
+                              void *stream);
+int epik_amd_cohort_kr(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, double *out);
+int epik_amd_cohort_kr_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                            const double *branch_length, double *out);
+int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
+                                 const uint32_t *weights, const uint32_t *samples, uint64_t n);
+int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
+                                   const uint32_t *weights, const uint32_t *samples, uint64_t n, uint32_t mode,
+                                   uint8_t *strand);
+int epik_amd_placer_cohort_frames(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
+                                  const uint32_t *weights, const uint32_t *samples, uint64_t n, uint32_t mode, uint8_t *frame);
+int epik_amd_placer_cohort_mates(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
+                                 const uint32_t *weights, const uint32_t *samples, uint64_t n_pairs, uint32_t mode,
+                                 uint8_t *strand);
+
 /* Which kernels the last launch of this handle ran (reports; a large-tree handle falls back from the three-kernel
  * placement to the one-kernel one when the device has no room for the scratch of a launch). */
 #define EPIK_AMD_PATH_WAVE 0u            /* place_reads_kernel: one wavefront per read */
