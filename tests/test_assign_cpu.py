@@ -2,7 +2,9 @@
 here over walks up parent[] -- it shares nothing with the library but the header's text --, the hand values of the
 rule, the LCA tables of libepik_amd (the function the kernel calls, on the host) against that walk, every validation
 error by the branch it names, the host mirror (epik_amd/host/confidence.cpp, through bin/confidence_test) against the
-restatement bit for bit on oracle rows, both TSVs both ways, the flags of the launcher and the drivers, the new symbols."""
+restatement bit for bit on oracle rows and on forged rows (forged_batch: every class and every edge of the rule's
+arithmetic, at eight values of keep on six trees), both TSVs both ways, the flags of the launcher and the drivers, the
+new symbols."""
 import ctypes
 import os
 import struct
@@ -216,6 +218,66 @@ def hand_read(keep=7):
     return rows, np.array([3], np.uint32), np.ones((1, keep), np.uint32)
 
 
+def star(leaves, seed=5):
+    """A star: every leaf hangs off the root, one multifurcation of `leaves` children.  (parent, lengths)."""
+    parent = np.full(leaves + 1, leaves, dtype=np.int64)
+    parent[leaves] = -1
+    return parent, np.random.default_rng(seed).uniform(0.01, 0.3, size=leaves + 1)
+
+
+def forged_batch(rng, n, keep, num_branches):
+    """(rows, n_rows, counts) that no placement writes: every class of the rule and the edges of its arithmetic, by
+    strides that cross each other (read i: LWRs by i % 8, n_rows by i // 8 % 8, the rest by 5, 11, 13 and 17).
+      branches  uniform over [0, N); every fifth read draws from min(N, 3) branches only: repeats, adjacent rows included
+      LWRs      finite, in [0, 1] a row: a sorted Dirichlet draw | all 1 / keep | all 0.0 (S == 0) | all 1.0 (clade_mass_q
+                saturates from 5 rows up, S << 30 wraps from 16) | dyadics 2^-e in no order (prefix sums meet tau_q * S
+                exactly) | 0.5, 0.25, 0.25 then zeros (hand_read; keep >= 3) | uniform, unsorted | a Dirichlet draw, unsorted
+      n_rows    1 ... keep (three eighths) | keep (two) | keep + 5, which the rule clamps | 0 | TOO_NARROW
+      counts    counts[i, 0] == 0 for every eleventh read
+      bad rows  every thirteenth read has one row, anywhere below keep, of branch N, N + 1 or 0xFFFFFFFF: past the
+                read's n_rows (not looked at), inside it but past the prefix, or inside the prefix
+      clamped   every seventeenth read (N >= 3) has n_rows = keep + 5, every LWR 1.0 and a hit, and all its rows on one
+                branch b, or on b and b + 1, with 1 <= b < N - 1: where S_m << 30 wraps past every threshold its prefix is
+                all of its rows -- keep of them; a prefix of n_rows rows would run on into rows that are not the read's
+    and poison() over every slot past n_rows."""
+    N, i = int(num_branches), np.arange(n)
+    rows = np.zeros((n, keep), dtype=capi.PLACEMENT)
+    rows["branch"] = rng.integers(0, N, size=(n, keep))
+    few = i % 5 == 2
+    rows["branch"][few] = rng.integers(0, min(N, 3), size=(int(few.sum()), keep))
+    rows["score"] = -rng.random((n, keep))
+    kind = i % 8
+    lwr = -np.sort(-rng.dirichlet(np.ones(keep), size=n), axis=1)
+    lwr[kind == 1] = 1.0 / keep
+    lwr[kind == 2] = 0.0
+    lwr[kind == 3] = 1.0
+    lwr[kind == 4] = 2.0 ** -rng.integers(0, 5, size=(int((kind == 4).sum()), keep)).astype(np.float64)
+    if keep >= 3:
+        lwr[kind == 5] = 0.0
+        lwr[kind == 5, :3] = [0.5, 0.25, 0.25]
+    lwr[kind == 6] = rng.random((int((kind == 6).sum()), keep))
+    lwr[kind == 7] = rng.dirichlet(np.ones(keep), size=int((kind == 7).sum()))
+    rows["lwr"] = lwr
+    n_kind = i // 8 % 8
+    n_rows = rng.integers(1, keep + 1, size=n).astype(np.uint32)
+    n_rows[(n_kind == 3) | (n_kind == 4)] = keep
+    n_rows[n_kind == 5] = keep + 5
+    n_rows[n_kind == 6] = 0
+    n_rows[n_kind == 7] = TOO_NARROW
+    counts = rng.integers(1, 300, size=(n, keep)).astype(np.uint32)
+    counts[i % 11 == 5, 0] = 0
+    bad = np.nonzero(i % 13 == 3)[0]
+    rows["branch"][bad, rng.integers(0, keep, size=len(bad))] = rng.choice([N, N + 1, 0xFFFFFFFF], size=len(bad))
+    if N >= 3:
+        over = np.nonzero(i % 17 == 7)[0]
+        b = rng.integers(1, N - 1, size=len(over))
+        pair = (np.arange(len(over)) % 2 == 1) & (b + 1 < N - 1)
+        rows["branch"][over] = b[:, None] + (pair[:, None] & (rng.random((len(over), keep)) < 0.5))
+        rows["lwr"][over], n_rows[over], counts[over, 0] = 1.0, keep + 5, 1
+    rows, counts = poison(rows, n_rows, counts)
+    return rows, n_rows, counts
+
+
 def test_hand_values_in_numpy():
     from epik_amd.confidence import tau_q
     t = RuleTree(HAND_PARENT, HAND_LENGTH)
@@ -383,6 +445,103 @@ def test_host_mirror_equals_the_rule_bit_for_bit_on_oracle_rows(host_bins, oracl
             assert (want["edpl"][ok][n_rows[ok] >= 2] > 0).all()
         if keep == 1:
             assert not want["edpl"].any() and np.array_equal(want["clade"][ok], rows["branch"][ok, 0])
+
+
+FORGED_KEEPS = (1, 2, 3, 7, 8, 13, 33, 64)
+FORGED_TAUS = (0, 1 << 29, int(np.rint(0.95 * 2 ** 30)), 1 << 30)      # 0, a half, tau_q(0.95), everything
+FORGED_TREES = {}
+
+
+def forged_tree(name):
+    """(parent, lengths, RuleTree) of the trees the forged batches lie on; `ladder<nodes>` is a caterpillar of that many
+    branches.  Some lengths are 0 (the hand tree keeps its own: its distances are written out above)."""
+    if name not in FORGED_TREES:
+        if name == "one_branch":
+            parent, lengths = [-1], [0.25]
+        elif name == "hand":
+            parent, lengths = HAND_PARENT, HAND_LENGTH
+        elif name == "multifurcating":
+            parent, lengths = MULTI_PARENT, np.arange(12) * 0.5
+        elif name == "star300":
+            parent, lengths = star(300)
+        elif name == "synth500":
+            tree = synth.make_tree(500, seed=13)
+            parent, lengths = tree.parent, tree.branch_length
+        else:
+            assert name.startswith("ladder"), name
+            parent, lengths = caterpillar(int(name[len("ladder"):]))
+        parent, lengths = np.array(parent, dtype=np.int64), np.array(lengths, dtype=np.float64)
+        if len(parent) > 12:
+            lengths[3::5] = 0.0
+        FORGED_TREES[name] = (parent, lengths, RuleTree(parent, lengths))
+    return FORGED_TREES[name]
+
+
+def never_reached(qs, tq):
+    """No prefix of the quantised LWRs qs meets tau_q * S in uint64: the rule's prefix is then all of the rows."""
+    total = sum(qs)
+    return all(((sum(qs[:m]) << LWR_BITS) & M64) < ((tq * total) & M64) for m in range(1, len(qs) + 1))
+
+
+def assert_every_case_occurs(rule, rows, n_rows, counts, tq, want):
+    """Conditions on a forged batch and on the records the restatement gives for it at tau_q = tq, none on the code under
+    test: every class of the rule occurs, and every edge forged_batch is there to reach."""
+    n, keep = rows.shape
+    live = np.where(n_rows == TOO_NARROW, 0, np.minimum(n_rows, keep)).astype(np.int64)
+    placed = want["clade"] < rule.n
+    classes = {c: int((want["clade"] == c).sum()) for c in (CLADE_TOO_NARROW, CLADE_TOO_SHORT, CLADE_NO_HIT, CLADE_BAD_ROW)}
+    assert placed.sum() > n // 4 and min(classes.values()) > 0, (tq, int(placed.sum()), classes)
+    assert placed.sum() + sum(classes.values()) == n
+    assert not want["edpl"][~placed].view(np.uint64).any() and not want["clade_mass_q"][~placed].any()
+    saturated = int((want["clade_mass_q"][placed] == 0xFFFFFFFF).sum())
+    moved = int((want["clade"][placed] != rows["branch"][placed, 0]).sum())
+    # (the all-ones reads whose rows lie on one branch: five rows of them or more lie in their clade whatever tau_q)
+    if keep >= 7:
+        assert saturated > 0, tq
+    # the clade is the first row's branch at tau_q 0.  Above it, a read moves off that branch when its first row holds
+    # less than tau_q of S and a later row of the prefix lies outside the first one's clade.  Fewest do at keep 2 and a
+    # half: the unsorted kinds (three eighths of the reads) where both rows are live (nine sixteenths) and the second is
+    # the heavier (a half), a tenth of the reads less those whose two branches share a clade -- a thirty-second is well
+    # below that.  With the whole mass it is every read of two rows or more that are not all in the clade of the first
+    if tq == 0:
+        assert moved == 0
+    elif keep > 1 and rule.n > 1:
+        assert moved >= placed.sum() // (8 if tq == 1 << 30 else 32), (moved, int(placed.sum()))
+    ids = np.nonzero(placed)[0]
+    q_of = {int(i): [q(x) for x in rows["lwr"][i, :live[i]]] for i in ids}
+    branches = {int(i): [int(b) for b in rows["branch"][i, :live[i]]] for i in ids}
+    assert ((n_rows[ids] > keep) & (n_rows[ids] != TOO_NARROW)).sum() > 0      # n_rows beyond keep: clamped
+    assert sum(1 for i in q_of if not any(q_of[i])) > 0                        # S == 0
+    if keep > 1:
+        assert sum(1 for b in branches.values() if len(set(b)) < len(b)) > 0                        # a branch twice in a read
+        assert sum(1 for b in branches.values() if any(x == y for x, y in zip(b, b[1:]))) > 0       # ... in adjacent rows
+        half = 1 << 29                                                         # a prefix sum that meets tau_q * S exactly
+        assert sum(1 for v in q_of.values() if sum(v) and any((sum(v[:m]) << LWR_BITS) == half * sum(v) for m in range(1, len(v))))
+        bad = np.nonzero(want["clade"] == CLADE_BAD_ROW)[0]                    # a bad row that is not the read's first
+        assert sum(1 for i in bad if rows["branch"][i, 0] < rule.n) > 0
+    if keep >= 16:
+        assert sum(1 for v in q_of.values() if sum(v) << LWR_BITS >= 1 << 64) > 0     # S * 2^30 beyond uint64: it wraps
+    # where keep rows of LWR 1.0 reach no threshold (S_m << 30 wraps below tau_q * S every time), a read of n_rows > keep
+    # does so whose clade leaves branch 0 out: a prefix of n_rows rows, not of min(n_rows, keep), takes in rows that are
+    # not the read's -- in the kernel the idle lanes of a group wider than keep, which hold branch 0 -- and another clade
+    if rule.n >= 3 and keep & (keep - 1) and never_reached([1 << LWR_BITS] * keep, tq):
+        assert sum(1 for i in q_of if n_rows[i] > keep and never_reached(q_of[i], tq) and rule.first[int(want["clade"][i])] > 0) > 0
+
+
+@pytest.mark.parametrize("tq", FORGED_TAUS)
+@pytest.mark.parametrize("keep", FORGED_KEEPS)
+@pytest.mark.parametrize("tree_name", ["one_branch", "hand", "multifurcating", "star300", "synth500", "ladder2001"])
+def test_host_mirror_equals_the_rule_bit_for_bit_on_forged_rows(host_bins, tmp_path, tree_name, keep, tq):
+    from epik_amd.confidence import tau_q
+    assert FORGED_TAUS == (0, tau_q(0.5), tau_q(0.95), tau_q(1))
+    assert never_reached([1 << LWR_BITS] * 33, tau_q(0.95)) and never_reached([1 << LWR_BITS] * 63, tau_q(0.5))
+    parent, lengths, rule = forged_tree(tree_name)
+    n = 1000 if keep <= 16 else 300
+    rows, n_rows, counts = forged_batch(np.random.default_rng([keep, len(parent)]), n, keep, len(parent))
+    want = numpy_rule(rule, rows, n_rows, counts, tq)
+    got = host_records(host_bins, tmp_path, rows, n_rows, counts, parent, lengths, tq)
+    assert same_bits(got, want), np.nonzero(got != want)[0][:10]
+    assert_every_case_occurs(rule, rows, n_rows, counts, tq, want)
 
 
 def _walk_clade_counts(assigned, parent):

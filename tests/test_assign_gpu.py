@@ -1,8 +1,9 @@
 """Placement confidence on the GPU (epik_amd_tree_*, epik_amd_confidence_device, epik_amd_placer_confidence_*,
 Placer.tree / confidence_device / confidence_packed / place(assign=), epik-dna / epik-aa --assign): the device records
 against the rule of include/epik_amd.h written out in test_assign_cpu.py -- bit for bit, edpl included, on the rows the
-placement has just written --, the same bits whatever the pieces, the stream, the grid or the chunks, through every host
-entry, and the drivers' files."""
+placement has just written, at the default keep_at_most and at six others, and on forged rows (test_assign_cpu.forged_batch)
+at every width of the kernel's lane groups --, the same bits whatever the pieces, the stream, the grid or the chunks,
+through every host entry, and the drivers' files."""
 import os
 import subprocess
 import sys
@@ -12,8 +13,9 @@ import pytest
 
 from conftest import select_kernel
 from epik_amd import capi, confidence, dbfile, mates, synth
-from test_assign_cpu import CLADE_BAD_ROW, CLADE_NO_HIT, CLADE_TOO_NARROW, CLADE_TOO_SHORT, RuleTree, caterpillar, numpy_rule, same_bits
-from test_profile_gpu import LARGE, DeviceBatch, _four_class_batch, _reads, _write_fasta, assert_profile
+from test_assign_cpu import (CLADE_BAD_ROW, CLADE_NO_HIT, CLADE_TOO_NARROW, CLADE_TOO_SHORT, FORGED_TAUS, HAND_LENGTH, HAND_PARENT,
+                             RuleTree, assert_every_case_occurs, caterpillar, forged_batch, forged_tree, hand_read, numpy_rule, poison, same_bits)
+from test_profile_gpu import LARGE, OTHER_KEEPS, DeviceBatch, _four_class_batch, _reads, _write_fasta, assert_profile, keep_case
 from test_profile_gpu import numpy_rule as profile_rule
 from test_strand_gpu import KERNELS
 
@@ -406,3 +408,194 @@ def test_drivers_assign_with_mates_and_frames(placer_cls, tmp_path):
     assert (outs["frames_assign"] / "assign_nt.fasta.tsv").read_bytes() == want
     assert (outs["frames_assign"] / "frames_nt.fasta.tsv").read_bytes() == (outs["frames"] / "frames_nt.fasta.tsv").read_bytes()
     assert _without_invocation(outs["frames_assign"] / "placements_nt.fasta.jplace") == _without_invocation(outs["frames"] / "placements_nt.fasta.jplace")
+
+
+# ---- forged rows: confidence_kernel at every group width, on every class and edge of the rule -------------------------
+#: every group width P of the kernel once exactly filled and once with idle lanes, on a binary and a multifurcating tree
+WIDTH_KEEPS = (1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 32, 33, 63, 64)
+#: ... and every tree at three widths; the ladder has 14 lift levels, and pairs that lie far apart
+FORGED_TREE_NAMES = ("one_branch", "hand", "multifurcating", "star300", "synth500", "ladder9999")
+FORGED_CASES = sorted({(t, k) for t in ("synth500", "multifurcating") for k in WIDTH_KEEPS} | {(t, k) for t in FORGED_TREE_NAMES for k in (7, 13, 64)})
+FORGED = {}
+
+
+def per_block(keep):
+    """The reads of a tile of confidence_kernel: 256 lanes in groups of P, the power of two >= keep."""
+    group = 1
+    while group < keep:
+        group *= 2
+    return 256 // group
+
+
+class ForgedCase:
+    """A forged batch on one tree at one keep, made once; the restatement's records per tau_q, computed once each and
+    left as they are.  n is no multiple of the tile: the last tile of a launch is partial."""
+
+    def __init__(self, tree_name, keep, n=None):
+        self.keep, self.n = keep, n or (1000 if keep <= 16 else 301)
+        assert self.n % per_block(keep) != 0
+        self.parent, self.lengths, self.rule = forged_tree(tree_name)
+        self.rows, self.n_rows, self.counts = forged_batch(np.random.default_rng([keep, len(self.parent)]), self.n, keep, len(self.parent))
+        self.wants = {}
+
+    def want(self, tq):
+        if tq not in self.wants:
+            self.wants[tq] = numpy_rule(self.rule, self.rows, self.n_rows, self.counts, tq)
+            assert_every_case_occurs(self.rule, self.rows, self.n_rows, self.counts, tq, self.wants[tq])
+        return self.wants[tq]
+
+
+def forged_case(tree_name, keep, n=None):
+    if (tree_name, keep, n) not in FORGED:
+        FORGED[tree_name, keep, n] = ForgedCase(tree_name, keep, n)
+    return FORGED[tree_name, keep, n]
+
+
+class ForgedDevice:
+    """Host rows in torch buffers on the device, and an output of n + 8 records filled with NaN."""
+
+    def __init__(self, rows, n_rows, counts):
+        import torch
+        self.torch, dev = torch, torch.device("cuda", 0)
+        self.n, self.keep = rows.shape
+        self.d_rows = torch.from_numpy(np.ascontiguousarray(rows).view(np.float64).reshape(-1)).to(dev)
+        self.d_n = torch.from_numpy(np.ascontiguousarray(n_rows, dtype=np.uint32).view(np.int32)).to(dev)
+        self.d_counts = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.uint32).view(np.int32).reshape(-1)).to(dev)
+        self.stream = torch.cuda.Stream()
+        self.fresh()
+
+    def fresh(self):
+        self.out = self.torch.full((2 * (self.n + 8),), float("nan"), dtype=self.torch.float64, device=self.d_rows.device)
+        self.before = self.out.cpu().numpy().copy()
+        self.torch.cuda.synchronize()
+
+    def run(self, tree, tq, first=0, count=None):
+        count = self.n - first if count is None else count
+        tree.confidence_device(self.d_rows.data_ptr() + first * self.keep * 16, self.d_n.data_ptr() + first * 4,
+                               self.d_counts.data_ptr() + first * self.keep * 4, count, self.keep, tq,
+                               self.out.data_ptr() + first * 16, self.stream.cuda_stream)
+
+    def records(self, written):
+        """The first `written` records; every record past them must be as it was."""
+        self.stream.synchronize()
+        got = self.out.cpu().numpy()
+        assert np.array_equal(got[2 * written:].view(np.uint64), self.before[2 * written:].view(np.uint64)), "a record past n was written"
+        return got[:2 * written].view(capi.CONFIDENCE)
+
+
+def poisoned(rows, n_rows, counts):
+    rows, counts = poison(rows, n_rows, counts)
+    return rows, n_rows, counts
+
+
+@pytest.fixture
+def forged_env(gpu_available, monkeypatch):
+    assert gpu_available, "pytest -m gpu needs a HIP device (no CPU fallback exists)"
+    for var in ENV:
+        monkeypatch.delenv(var, raising=False)
+    return monkeypatch
+
+
+def differing(got, want):
+    return np.nonzero(got.view(np.uint64).reshape(-1, 2) != want.view(np.uint64).reshape(-1, 2))[0][:10]
+
+
+@pytest.mark.parametrize("tq", FORGED_TAUS)
+@pytest.mark.parametrize("tree_name,keep", FORGED_CASES)
+def test_confidence_kernel_equals_the_rule_on_forged_rows(forged_env, tree_name, keep, tq):
+    case = forged_case(tree_name, keep)
+    want = case.want(tq)
+    batch = ForgedDevice(case.rows, case.n_rows, case.counts)
+    with confidence.Tree(0, case.parent, case.lengths) as tr:
+        batch.run(tr, tq)
+        got = batch.records(case.n)
+        assert same_bits(got, want), (tree_name, keep, tq, differing(got, want))
+        # one read; one read more than a tile
+        for n in (1, per_block(keep) + 1):
+            batch.fresh()
+            batch.run(tr, tq, 0, n)
+            got = batch.records(n)
+            assert same_bits(got, want[:n]), (tree_name, keep, tq, n, differing(got, want[:n]))
+
+
+@pytest.mark.parametrize("keep,n", [(1, 5001), (64, None)])
+def test_forged_rows_under_two_workgroups(forged_env, keep, n):
+    """EPIK_AMD_MAX_BLOCKS is read when the tree is created: a workgroup then walks many tiles of the grid stride (ten
+    of 256 reads at keep 1, thirty-eight of 4 at keep 64; the last one partial)."""
+    case = forged_case("synth500", keep, n)
+    assert (case.n + per_block(keep) - 1) // per_block(keep) >= 20
+    batch = ForgedDevice(case.rows, case.n_rows, case.counts)
+    forged_env.setenv("EPIK_AMD_MAX_BLOCKS", "2")
+    with confidence.Tree(0, case.parent, case.lengths) as tr:
+        for tq in (FORGED_TAUS[1], FORGED_TAUS[2]):
+            batch.fresh()
+            batch.run(tr, tq)
+            got = batch.records(case.n)
+            assert same_bits(got, case.want(tq)), (keep, tq, differing(got, case.want(tq)))
+
+
+@pytest.mark.parametrize("keep", [3, 7, 64])
+def test_forged_rows_in_uneven_pieces(forged_env, keep):
+    case = forged_case("multifurcating", keep)
+    cuts = [0, 1, 6, 7, 101, 102, 299, case.n]
+    assert all(c % per_block(keep) for c in cuts[1:]) and any((b - a) > per_block(keep) for a, b in zip(cuts, cuts[1:]))
+    batch = ForgedDevice(case.rows, case.n_rows, case.counts)
+    with confidence.Tree(0, case.parent, case.lengths) as tr:
+        for a, b in zip(cuts, cuts[1:]):
+            batch.run(tr, TAU_Q, a, b - a)
+        batch.run(tr, TAU_Q, 5, 0)                           # n == 0: nothing
+        got = batch.records(case.n)
+    assert same_bits(got, case.want(TAU_Q)), (keep, differing(got, case.want(TAU_Q)))
+
+
+@pytest.mark.parametrize("keep", [3, 7, 64])
+def test_hand_values_on_the_device(forged_env, keep):
+    rows, n_rows, counts = hand_read(keep)
+    with confidence.Tree(0, HAND_PARENT, HAND_LENGTH) as tr:
+        batch = ForgedDevice(*poisoned(rows, n_rows, counts))
+        for tau, clade, mass in ((0.5, 0, 1 << 29), (0.75, 2, 3 << 28), (0.95, 6, 1 << 30)):
+            batch.fresh()
+            batch.run(tr, confidence.tau_q(tau))
+            got = batch.records(1)[0]
+            assert (int(got["clade"]), int(got["clade_mass_q"]), float(got["edpl"])) == (clade, mass, 4.75), tau
+        # one row: +0.0, the clade is the branch whatever tau
+        rows["branch"][0, 0], n_rows[0] = 4, 1
+        batch = ForgedDevice(*poisoned(rows, n_rows, counts))
+        batch.run(tr, 1 << 30)
+        got = batch.records(1)
+        assert int(got["clade"][0]) == 4 and got["edpl"].view(np.uint64)[0] == 0 and int(got["clade_mass_q"][0]) == 1 << 29
+
+
+@pytest.mark.parametrize("keep", [0, 65])
+def test_a_keep_outside_1_to_64_is_refused(forged_env, keep):
+    rows, n_rows, counts = hand_read(7)
+    batch = ForgedDevice(rows, n_rows, counts)
+    with confidence.Tree(0, HAND_PARENT, HAND_LENGTH) as tr:
+        with pytest.raises(capi.EpikAmdError) as e:
+            tr.confidence_device(batch.d_rows.data_ptr(), batch.d_n.data_ptr(), batch.d_counts.data_ptr(), 1, keep, TAU_Q,
+                                 batch.out.data_ptr(), batch.stream.cuda_stream)
+        assert e.value.code == capi.ERR_INVALID and "keep" in str(e.value)
+    assert len(batch.records(0)) == 0                       # nothing was written
+
+
+# ---- other keep_at_most: the rows a placement wrote at that keep ------------------------------------------------------
+@pytest.mark.parametrize("tq", [1 << 29, TAU_Q])
+@pytest.mark.parametrize("keep", OTHER_KEEPS)
+def test_confidence_device_at_other_keep_at_most(placer_cls, monkeypatch, keep, tq):
+    for var in ENV:
+        monkeypatch.delenv(var, raising=False)
+    tree, db = keep_case()
+    reads = _reads(db.kmer_size, np.random.default_rng(keep), 600)
+    with placer_cls.from_synth(db, keep_at_most=keep) as pl, pl.tree(tree.parent, tree.branch_length) as tr:
+        assert pl.keep_at_most == keep
+        pl.choose_counts(200)
+        batch = DeviceBatch(pl, reads)
+        rows, n_rows, counts = batch.host()
+        assert rows.shape == (len(reads), keep)
+        got = records_of(device_records(pl, tr, batch, tq))[:len(reads)]
+    want = numpy_rule(RuleTree(tree.parent, tree.branch_length), rows, n_rows, counts, tq)
+    assert same_bits(got, want), (keep, tq, differing(got, want))
+    ok = want["clade"] < db.num_branches
+    print(f"keep {keep}: {int(ok.sum())} placed reads, at most {int(n_rows[ok].max())} rows, {int((n_rows[ok] == keep).sum())} reads of keep rows")
+    assert ok.sum() > 100 and (want["clade"] == CLADE_BAD_ROW).sum() == 0 and (want["clade"] == CLADE_TOO_SHORT).sum() > 0
+    assert (n_rows[ok] == keep).sum() > 0                   # (the CPU oracle fills all 64 rows for a third of these reads)

@@ -197,7 +197,7 @@ def hand_rows(rng, n, keep, num_branches):
     n_rows = rng.integers(0, keep + 1, size=n).astype(np.uint32)
     n_rows[::17] = 0xFFFFFFFF
     counts = rng.integers(0, 3, size=(n, keep)).astype(np.uint32)
-    rows["branch"][5::23, 1] = num_branches + 3       # bad rows
+    rows["branch"][5::23, min(1, keep - 1)] = num_branches + 3       # bad rows
     return rows, n_rows, counts
 
 

@@ -1,7 +1,7 @@
 """A cohort of samples on the GPU (epik_amd_cohort_*, epik_amd_placer_cohort_*, Placer.cohort, epik-dna / epik-aa
 --cohort): the cells against the profile's rule applied per sample, bit for bit whatever the grouping of the samples,
-the pieces, the grid, the path or the chunks; the KR distances against the host mirror and the numpy restatement, bit
-for bit; and the drivers' files."""
+the pieces, the grid, the path, the chunks or keep_at_most, bad rows in a workgroup's current sample and in any other
+included; the KR distances against the host mirror and the numpy restatement, bit for bit; and the drivers' files."""
 import os
 import subprocess
 
@@ -12,7 +12,7 @@ from conftest import select_kernel
 from epik_amd import capi, cohort as cohort_mod, dbfile, profile as profile_mod, synth
 from test_assign_cpu import caterpillar
 from test_cohort_cpu import assert_cells, numpy_cohort, numpy_first, numpy_kr, random_cells, same_bits
-from test_profile_gpu import LARGE, DeviceBatch, _reads, _write_fasta
+from test_profile_gpu import LARGE, OTHER_KEEPS, DeviceBatch, _reads, _write_fasta, forged_rows, keep_case
 from test_strand_gpu import KERNELS
 
 pytestmark = pytest.mark.gpu
@@ -162,6 +162,56 @@ def test_same_bits_whatever_the_pieces_the_grid_and_the_path(placer_cls, small_c
     assert want[3] == int((samples >= num_samples).sum()) > 2
     for name, got in results.items():
         assert_cells(got, want, name)
+
+
+def add_host(cohort, rows, n_rows, counts, weights, samples):
+    """Rows in host memory through Cohort.add_device."""
+    import torch
+    dev = torch.device("cuda", cohort.device)
+    arrays = (np.ascontiguousarray(rows, dtype=capi.PLACEMENT).view(np.float64).reshape(-1),) + tuple(
+        np.ascontiguousarray(a, dtype=np.uint32).view(np.int32).reshape(-1) for a in (n_rows, counts, samples, weights))
+    d_rows, d_n, d_counts, d_samples, d_w = (torch.from_numpy(a).to(dev) for a in arrays)
+    torch.cuda.synchronize(dev)
+    cohort.add_device(d_rows.data_ptr(), d_n.data_ptr(), d_counts.data_ptr(), d_samples.data_ptr(), len(n_rows), d_w.data_ptr())
+    torch.cuda.synchronize(dev)
+
+
+@pytest.mark.parametrize("lds", ["1", "0"])
+@pytest.mark.parametrize("keep", OTHER_KEEPS)
+def test_cohort_at_other_keep_at_most(placer_cls, monkeypatch, keep, lds):
+    for var in ENV:
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setenv("EPIK_AMD_PROFILE_LDS", lds)
+    _, db = keep_case()
+    rng = np.random.default_rng(100 + keep)
+    reads = _reads(db.kmer_size, rng, 600)
+    weights = rng.integers(0, 5, size=len(reads)).astype(np.uint32)
+    weights[::11] = 0
+    weights[5::13] = 0xFFFFFFFF
+    num_samples = 7
+    with placer_cls.from_synth(db, keep_at_most=keep) as pl, pl.cohort(num_samples) as cohort:
+        assert pl.keep_at_most == keep and cohort.lds_path == (lds == "1")
+        # the rows the placement has just written
+        pl.choose_counts(200)
+        batch = DeviceBatch(pl, reads, weights)
+        samples = _mixed_samples(len(reads), num_samples, rng)
+        add_to(batch, cohort, device_samples(batch, samples))
+        want = numpy_cohort(*batch.host(), weights, samples, num_samples, db.num_branches)
+        assert_cells(cohort.read(), want, f"placed rows, keep {keep}")
+        assert want[3] > 2 and sum(t["placed"] for t in want[2]) > 0 and sum(t["bad_rows"] for t in want[2]) == 0
+        # forged rows: bad rows in the workgroup's current sample and in any other -- the current sample changes within
+        # the batch, run by run and, interleaved, tile by tile --, reads of no sample, one sample without reads
+        rows, n_rows, counts, weights = forged_rows(rng, 700, keep, db.num_branches)
+        for name in ("runs", "interleaved"):
+            samples = _mixed_samples(700, num_samples, rng) if name == "runs" else (np.arange(700) % (num_samples + 2)).astype(np.uint32)
+            samples[samples == 3] = 1
+            want = numpy_cohort(rows, n_rows, counts, weights, samples, num_samples, db.num_branches)
+            cohort.reset()
+            add_host(cohort, rows, n_rows, counts, weights, samples)
+            assert_cells(cohort.read(), want, f"forged rows, {name}, keep {keep}")
+            assert want[3] > 0 and not want[0][3].any() and sum(want[2][3].values()) == 0
+            assert sum(1 for t in want[2] if t["bad_rows"] > 0) >= 2
+            assert ((n_rows == keep + 5) & (counts[:, 0] != 0) & (samples < num_samples)).sum() > 0
 
 
 def test_a_read_of_no_sample_adds_to_bad_samples_and_nothing_else(placer_cls, small_case, monkeypatch):

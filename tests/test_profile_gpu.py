@@ -1,7 +1,8 @@
 """The abundance profile on the GPU (epik_amd_profile_*, epik_amd_placer_profile_*, Placer.profile, epik-dna --profile /
 --profile-only): the device sums against the rule of include/epik_amd.h written out here in numpy -- bit for bit on the
-rows the placement wrote, within the project's LWR bar against the CPU oracle's rows --, the same bits whatever the
-pieces, the grid, the path or the chunks, and the drivers' files."""
+rows the placement wrote and on forged rows, at the default keep_at_most and at six others, within the project's LWR bar
+against the CPU oracle's rows --, the same bits whatever the pieces, the grid, the path or the chunks, and the drivers'
+files."""
 import os
 import subprocess
 import sys
@@ -360,6 +361,66 @@ def test_profile_frames_equal_add_device_over_the_placed_rows(placer_cls, monkey
         with pytest.raises(capi.EpikAmdError) as e:          # strands need a nucleotide handle
             pl.profile_packed(profile, data, offs, strand="both")
         assert e.value.code == capi.ERR_UNSUPPORTED
+
+
+# ---- other keep_at_most ------------------------------------------------------------------------------------------------
+#: the kernels map row slot 256 t + lane to (read, row) by a division by keep: other remainders of 256 than 7's
+OTHER_KEEPS = (1, 2, 3, 8, 13, 64)
+_KEEP_CASE = []
+
+
+def keep_case():
+    """(tree, db) of 79 branches -- enough for 64 rows a read --, k = 4."""
+    if not _KEEP_CASE:
+        tree = synth.make_tree(40, seed=30)
+        _KEEP_CASE.append((tree, synth.make_db(tree.num_nodes, kmer_size=4, seed=31, p_present=0.7)))
+    return _KEEP_CASE[0]
+
+
+def forged_rows(rng, n, keep, num_branches):
+    """test_cohort_cpu.hand_rows with reads whose n_rows lies beyond keep (every row of theirs counts), more bad rows,
+    and weights that include 0 and 0xFFFFFFFF."""
+    from test_cohort_cpu import hand_rows
+    rows, n_rows, counts = hand_rows(rng, n, keep, num_branches)
+    n_rows[4::19] = keep + 5
+    rows["branch"][2::7, 0] = num_branches + 1
+    weights = rng.integers(0, 4, size=n).astype(np.uint32)
+    weights[::11] = 0
+    weights[3::29] = 0xFFFFFFFF
+    return rows, n_rows, counts, weights
+
+
+@pytest.mark.parametrize("lds", ["1", "0"])
+@pytest.mark.parametrize("keep", OTHER_KEEPS)
+def test_profile_at_other_keep_at_most(placer_cls, monkeypatch, keep, lds):
+    for var in ("EPIK_AMD_KERNEL", "EPIK_AMD_LAYOUT", "EPIK_AMD_RUNS", "EPIK_AMD_MAX_BLOCKS", "EPIK_AMD_TEAM_FRONT"):
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setenv("EPIK_AMD_PROFILE_LDS", lds)
+    _, db = keep_case()
+    assert db.num_branches == 79
+    rng = np.random.default_rng(keep)
+    reads = _reads(db.kmer_size, rng, 600)
+    weights = rng.integers(0, 5, size=len(reads)).astype(np.uint32)
+    weights[::11] = 0
+    weights[5::13] = 0xFFFFFFFF
+    weights[-4:] = (1, 2, 3, 0xFFFFFFFF)                    # the fixed reads that end _reads count, whatever the draw
+    with placer_cls.from_synth(db, keep_at_most=keep) as pl, pl.profile() as profile:
+        assert pl.keep_at_most == keep and profile.lds_path == (lds == "1")
+        # the rows the placement has just written
+        pl.choose_counts(200)
+        batch = DeviceBatch(pl, reads, weights)
+        batch.add_to(profile)
+        rows, n_rows, counts = batch.host()
+        want = numpy_rule(rows, n_rows, counts, weights, db.num_branches)
+        assert_profile(profile.read(), want, f"placed rows, keep {keep}")
+        assert want[2]["placed"] > 0 and want[2]["no_hit"] > 0 and want[2]["too_short"] > 0 and want[2]["bad_rows"] == 0
+        # forged rows
+        rows, n_rows, counts, weights = forged_rows(rng, 700, keep, db.num_branches)
+        want = numpy_rule(rows, n_rows, counts, weights, db.num_branches)
+        profile.reset()
+        profile.add_host(rows, n_rows, counts, weights)
+        assert_profile(profile.read(), want, f"forged rows, keep {keep}")
+        assert min(want[2].values()) > 0 and ((n_rows == keep + 5) & (counts[:, 0] != 0)).sum() > 0
 
 
 def test_place_feeds_the_multiplicities(placer_cls, small_case, monkeypatch):
