@@ -13,7 +13,8 @@ sharded across; --db-shard; --strand, which strand of each nucleotide read is pl
 the sample's abundance profile per branch beside the jplace or instead of it; --mates, the second FASTA file of a
 paired-end sample: every pair gets one placement; --assign / --assign-mass, per read the LCA clade that holds that share
 of its placement mass and the EDPL; --cohort, the input file is a list of samples (name<TAB>path lines): their profiles and
-the Kantorovich-Rubinstein distance between every two of them, cohort_samples_ / cohort_profile_ / cohort_kr_<list>.tsv.
+the Kantorovich-Rubinstein distance between every two of them, cohort_samples_ / cohort_profile_ / cohort_kr_<list>.tsv;
+--cohort-squash, with --cohort: the squash clustering of the samples, cohort_squash_<list>.tsv and .nwk.
 """
 from __future__ import annotations
 
@@ -76,6 +77,9 @@ PLACE_OPTIONS = [
                                             "cohort_profile_<list>.tsv and cohort_kr_<list>.tsv, the KR distance between "
                                             "every two samples (not with --mates, --profile, --profile-only, --assign or "
                                             "--db-shard > 1).")),
+    (("--cohort-squash",), dict(is_flag=True, help="With --cohort: also cluster the samples by squash clustering on the device "
+                                                   "and write cohort_squash_<list>.tsv (a line per merge) and "
+                                                   "cohort_squash_<list>.nwk (the cluster tree).")),
 ]
 
 
@@ -91,11 +95,13 @@ def driver_path(states: str) -> str:
 
 def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpus, input_file, db_shard=1,
                    strand="forward", translate=None, profile=False, profile_only=False, mates=None,
-                   mate_orientation="fr", assign=False, assign_mass=None, cohort=False):
+                   mate_orientation="fr", assign=False, assign_mass=None, cohort=False, cohort_squash=False):
     if assign_mass is not None and not assign:
         raise click.UsageError("--assign-mass needs --assign")
     if assign and db_shard != 1:
         raise click.UsageError("--assign does not work with --db-shard > 1")
+    if cohort_squash and not cohort:
+        raise click.UsageError("--cohort-squash needs --cohort")
     if cohort:
         for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
                             ("--assign", assign), ("--db-shard > 1", db_shard != 1)):
@@ -127,6 +133,8 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
             argv += ["--assign-mass", repr(float(assign_mass))]
     if cohort:
         argv += ["--cohort"]
+    if cohort_squash:
+        argv += ["--cohort-squash"]
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 

@@ -23,6 +23,9 @@ OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED = 0, 1, 2, 3, 4
 PLACEMENT = np.dtype([("branch", np.uint32), ("score", np.float32), ("lwr", np.float64)])
 #: numpy mirror of `epik_amd_confidence` {clade, clade_mass_q, edpl} (16 bytes)
 CONFIDENCE = np.dtype([("clade", np.uint32), ("clade_mass_q", np.uint32), ("edpl", np.float64)])
+#: epik_amd_squash_merge (32 bytes)
+SQUASH_MERGE = np.dtype([("a", np.uint32), ("b", np.uint32), ("dist", np.float64), ("len_a", np.float64), ("len_b", np.float64)])
+SQUASH_NONE = 0xFFFFFFFF
 #: numpy mirror of `epik_amd_pkdb_value` / `i2l::pkdb_value` (8 bytes)
 PKDB_VALUE = np.dtype([("branch", np.uint32), ("score", np.float32)])
 
@@ -97,6 +100,9 @@ EXPORTS = (
     "epik_amd_cohort_kr_device",
     "epik_amd_cohort_kr",
     "epik_amd_cohort_kr_host",
+    "epik_amd_cohort_squash_device",
+    "epik_amd_cohort_squash",
+    "epik_amd_cohort_squash_host",
     "epik_amd_placer_cohort_reads",
     "epik_amd_placer_cohort_strands",
     "epik_amd_placer_cohort_frames",
@@ -401,6 +407,12 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_kr.argtypes = [vp, vp, vp, vp]
     lib.epik_amd_cohort_kr_host.restype = i32
     lib.epik_amd_cohort_kr_host.argtypes = [vp, u32, u32, vp, vp, vp]
+    lib.epik_amd_cohort_squash_device.restype = i32
+    lib.epik_amd_cohort_squash_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.epik_amd_cohort_squash.restype = i32
+    lib.epik_amd_cohort_squash.argtypes = [vp, vp, vp, vp, ctypes.POINTER(u32)]
+    lib.epik_amd_cohort_squash_host.restype = i32
+    lib.epik_amd_cohort_squash_host.argtypes = [vp, u32, u32, vp, vp, vp, ctypes.POINTER(u32)]
     lib.epik_amd_placer_cohort_reads.restype = i32
     lib.epik_amd_placer_cohort_reads.argtypes = [vp, vp, vp, vp, vp, vp, u64]
     for name in ("epik_amd_placer_cohort_strands", "epik_amd_placer_cohort_frames", "epik_amd_placer_cohort_mates"):

@@ -6,6 +6,10 @@ and a strictly sequential sum per pair: the same bits whatever the order, the gr
 `Cohort` is the ctypes side of the device object; `kr_host` the rule on the host (no device); `first_of` gives the
 first[] of a tree from its parents; `format_*` / `read_*` are the files the drivers write with --cohort
 (epik_amd/host/cohort.cpp and main.cpp write the same bytes).
+
+Squash clustering of the samples (the header's second rule): `Cohort.squash` / `squash_device` on the device,
+`squash_host` on the host, each giving the merge records (`capi.SQUASH_MERGE`); `format_squash_tsv`,
+`format_squash_newick` and `read_squash_tsv` are the two files of --cohort-squash.
 """
 from __future__ import annotations
 
@@ -17,6 +21,9 @@ import numpy as np
 from . import capi
 from .profile import TOTALS
 
+import re
+
+SQUASH_HEADER = "step\tnode\ta\tb\tsize\tdist\tlen_a\tlen_b"
 SAMPLES_HEADER = "name\trecords\tplaced\tno_hit\ttoo_short\ttoo_narrow\ttotal_mass_q"
 PROFILE_HEADER = "name\tedge_num\tbest\tmass_q"
 _TOTALS_DTYPE = np.dtype([(k, "<u8") for k in TOTALS])
@@ -49,6 +56,39 @@ def kr_host(mass, first, branch_length) -> np.ndarray:
     out = np.full((s, s), np.nan, dtype=np.float64)
     capi.check(lib.epik_amd_cohort_kr_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, out.ctypes.data))
     return out
+
+
+def _cells_and_tree(mass, first, branch_length):
+    mass = np.ascontiguousarray(mass, dtype=np.uint64)
+    if mass.ndim != 2:
+        raise ValueError("mass must be [num_samples][num_branches]")
+    first = np.ascontiguousarray(first, dtype=np.uint32)
+    length = np.ascontiguousarray(branch_length, dtype=np.float64)
+    if first.shape != (mass.shape[1],) or length.shape != (mass.shape[1],):
+        raise ValueError(f"first and branch_length must hold one value per branch ({mass.shape[1]})")
+    return mass, first, length
+
+
+def squash_host(mass, first, branch_length) -> np.ndarray:
+    """The squash clustering of the rule for mass[S][N] on the host (`epik_amd_cohort_squash_host`): the records of the
+    merges made, `capi.SQUASH_MERGE` [num_merges]."""
+    lib = capi.load()
+    mass, first, length = _cells_and_tree(mass, first, branch_length)
+    s, n = mass.shape
+    merges = np.zeros(max(s - 1, 0), dtype=capi.SQUASH_MERGE)
+    count = ctypes.c_uint32(0xFFFFFFFF)
+    capi.check(lib.epik_amd_cohort_squash_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data,
+                                               merges.ctypes.data if s > 1 else None, ctypes.byref(count)))
+    return _merges_made(merges, count.value)
+
+
+def _merges_made(merges, count):
+    """The first `count` records; the rest must be as the rule leaves them."""
+    rest = merges[count:]
+    if count > len(merges) or not ((rest["a"] == capi.SQUASH_NONE) & (rest["b"] == capi.SQUASH_NONE)).all() or \
+            rest["dist"].view(np.uint64).any() or rest["len_a"].view(np.uint64).any() or rest["len_b"].view(np.uint64).any():
+        raise RuntimeError("squash: the records past num_merges are not the unused record")
+    return merges[:count].copy()
 
 
 @dataclass
@@ -168,6 +208,23 @@ class Cohort:
         capi.check(self._lib.epik_amd_cohort_kr(self._handle, tree._handle, length.ctypes.data, out.ctypes.data))
         return out
 
+    def squash_device(self, tree, branch_length, d_merges: int, d_num_merges: int, stream: int = 0) -> None:
+        """The squash clustering into device memory: d_merges `capi.SQUASH_MERGE` [S - 1], every record written, and
+        d_num_merges one uint32; asynchronous on `stream` once the lengths (host) are copied, all steps enqueued
+        (`epik_amd_cohort_squash_device`)."""
+        length = self._lengths(tree, branch_length)
+        capi.check(self._lib.epik_amd_cohort_squash_device(self._handle, tree._handle, length.ctypes.data, d_merges or None,
+                                                           d_num_merges or None, stream or None))
+
+    def squash(self, tree, branch_length) -> np.ndarray:
+        """The records of the merges made, `capi.SQUASH_MERGE` [num_merges] (`epik_amd_cohort_squash`)."""
+        length = self._lengths(tree, branch_length)
+        merges = np.zeros(self.num_samples - 1, dtype=capi.SQUASH_MERGE)
+        count = ctypes.c_uint32(0xFFFFFFFF)
+        capi.check(self._lib.epik_amd_cohort_squash(self._handle, tree._handle, length.ctypes.data,
+                                                    merges.ctypes.data if len(merges) else None, ctypes.byref(count)))
+        return _merges_made(merges, count.value)
+
     def reset(self) -> None:
         capi.check(self._lib.epik_amd_cohort_reset(self._handle))
 
@@ -197,6 +254,70 @@ def format_kr_tsv(names, kr) -> str:
     for s, name in enumerate(names):
         lines.append("\t".join([name, *("%.17g" % float(x) for x in kr[s])]))
     return "\n".join(lines) + "\n"
+
+
+def _live_mask(names, live) -> np.ndarray:
+    live = np.asarray(live, dtype=bool)
+    if live.shape != (len(names),):
+        raise ValueError(f"live must hold one flag per sample ({len(names)})")
+    return live
+
+
+def format_squash_tsv(names, live, merges) -> str:
+    """cohort_squash_<list>.tsv: `live[s]`: sample s has mass (T_s > 0) and is clustered; `merges` the records made."""
+    live = _live_mask(names, live)
+    s = len(names)
+    lines = [f"# epik_amd squash v1  samples={s} clustered={int(live.sum())} merges={len(merges)}"]
+    lines += [f"# unclustered\t{name}" for name, alive in zip(names, live) if not alive]
+    lines.append(SQUASH_HEADER)
+    size = [1] * s
+    for t, m in enumerate(merges):
+        size.append(size[int(m["a"])] + size[int(m["b"])])
+        lines.append("\t".join([str(t), str(s + t), str(int(m["a"])), str(int(m["b"])), str(size[-1]),
+                                *("%.17g" % float(m[k]) for k in ("dist", "len_a", "len_b"))]))
+    return "\n".join(lines) + "\n"
+
+
+def newick_label(name: str) -> str:
+    """The name as it is when all of [A-Za-z0-9_.-], else in single quotes with the inner quotes doubled."""
+    return name if re.fullmatch(r"[A-Za-z0-9_.-]+", name) else "'" + name.replace("'", "''") + "'"
+
+
+def format_squash_newick(names, live, merges) -> str:
+    """cohort_squash_<list>.nwk: the cluster tree, child a before child b, no length at the root; `name;` for one
+    clustered sample, `;` for none."""
+    live = _live_mask(names, live)
+    text = [newick_label(name) if alive else "" for name, alive in zip(names, live)]
+    for m in merges:        # (bottom up: a record names only nodes made before it)
+        text.append("(%s:%.17g,%s:%.17g)" % (text[int(m["a"])], float(m["len_a"]), text[int(m["b"])], float(m["len_b"])))
+    if len(merges):
+        return text[-1] + ";\n"
+    return (text[int(np.flatnonzero(live)[0])] if live.any() else "") + ";\n"
+
+
+def read_squash_tsv(path: str):
+    """(merges, info): the records, `capi.SQUASH_MERGE` [M], and {"samples", "clustered", "merges", "unclustered": names,
+    "node", "size": arrays [M]}."""
+    with open(path, newline="") as fh:
+        head = re.fullmatch(r"# epik_amd squash v1  samples=(\d+) clustered=(\d+) merges=(\d+)", fh.readline().rstrip("\n"))
+        if not head:
+            raise ValueError(f"{path}: not a cohort squash file")
+        info = {"samples": int(head[1]), "clustered": int(head[2]), "merges": int(head[3]), "unclustered": []}
+        line = fh.readline().rstrip("\n")
+        while line.startswith("# unclustered\t"):
+            info["unclustered"].append(line.split("\t", 1)[1])
+            line = fh.readline().rstrip("\n")
+        if line != SQUASH_HEADER:
+            raise ValueError(f"{path}: not a cohort squash file")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    if len(rows) != info["merges"] or [int(r[0]) for r in rows] != list(range(len(rows))):
+        raise ValueError(f"{path}: the steps do not follow the first line's count")
+    merges = np.zeros(len(rows), dtype=capi.SQUASH_MERGE)
+    for t, r in enumerate(rows):
+        merges[t] = (int(r[2]), int(r[3]), float(r[5]), float(r[6]), float(r[7]))
+    info["node"] = np.array([int(r[1]) for r in rows], dtype=np.int64)
+    info["size"] = np.array([int(r[4]) for r in rows], dtype=np.int64)
+    return merges, info
 
 
 def read_samples_tsv(path: str):

@@ -1,0 +1,41 @@
+// cohort_device.hpp -- what cohort_place.hip and squash_place.hip share of a device cohort: the object itself and the
+// launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering starts from.
+#ifndef EPIK_AMD_COHORT_DEVICE_HPP
+#define EPIK_AMD_COHORT_DEVICE_HPP
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "epik_amd.h"
+
+struct epik_amd_cohort {
+    int device = 0;
+    uint32_t num_samples = 0, num_branches = 0, keep = 0;
+    bool lds = false;             // latched at create(): the LDS path
+    uint32_t lds_blocks = 0;      // ... and its grid: kMaxBlocks, or a workgroup per CU for the trees beyond kLdsBudget
+    uint32_t max_blocks_cap = 0;  // the placer's EPIK_AMD_MAX_BLOCKS
+    uint64_t *d_cells = nullptr;  // [S] x (mass[N] | best[N] | totals[kTotals]) | bad_samples
+    // the workspace of the KR distance, allocated by the first kr_device:
+    uint64_t *d_prefix = nullptr;  // [S][N]: inclusive prefix sums of mass
+    uint64_t *d_total = nullptr;   // [S]: T_s
+    double *d_planes = nullptr;    // C[N][Sp] | B[N][Sp]
+    double *d_half = nullptr;      // [N]: 0.5 * branch_length
+    // the workspace of the squash clustering, allocated by the first squash_device (squash_place.hip):
+    void *d_squash = nullptr;
+};
+
+namespace epik_amd {
+
+constexpr uint32_t kCohortTile = 32;  // samples a side of a tile of pairs: the planes' sample pitch is a multiple of it
+inline uint32_t cohort_padded_samples(const epik_amd_cohort *cohort)
+{
+    return (cohort->num_samples + kCohortTile - 1) / kCohortTile * kCohortTile;
+}
+
+// epik_amd_cohort_kr_device: the checks, the workspace, the lengths, then the normalise and distance kernels on `stream`
+int cohort_kr_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out,
+                      hipStream_t stream);
+
+}  // namespace epik_amd
+#endif

@@ -42,21 +42,8 @@
 #include <vector>
 
 #include "../host/cohort.hpp"
+#include "cohort_device.hpp"
 #include "host_entry.hpp"
-
-struct epik_amd_cohort {
-    int device = 0;
-    uint32_t num_samples = 0, num_branches = 0, keep = 0;
-    bool lds = false;             // latched at create(): the LDS path
-    uint32_t lds_blocks = 0;      // ... and its grid: kMaxBlocks, or a workgroup per CU for the trees beyond kLdsBudget
-    uint32_t max_blocks_cap = 0;  // the placer's EPIK_AMD_MAX_BLOCKS
-    uint64_t *d_cells = nullptr;  // [S] x (mass[N] | best[N] | totals[kTotals]) | bad_samples
-    // the workspace of the KR distance, allocated by the first kr_device:
-    uint64_t *d_prefix = nullptr;  // [S][N]: inclusive prefix sums of mass
-    uint64_t *d_total = nullptr;   // [S]: T_s
-    double *d_planes = nullptr;    // C[N][Sp] | B[N][Sp]
-    double *d_half = nullptr;      // [N]: 0.5 * branch_length
-};
 
 namespace {
 
@@ -68,7 +55,7 @@ constexpr uint64_t kLdsBudget = 48u << 10;         // as profile_place.hip: thre
 constexpr uint64_t kLdsLimit = (160u << 10) - 64;  // ... and one up to 10 236
 constexpr uint64_t kMaxBlocks = 1024;
 constexpr uint32_t kNoSample = 0xffffffffu;
-constexpr uint32_t kTile = 32;    // samples a side of a tile of pairs
+constexpr uint32_t kTile = kCohortTile;  // samples a side of a tile of pairs
 constexpr uint32_t kChunk = 32;   // branches staged at a time: 4 * 32 * 32 * 8 = 32 KB of LDS
 constexpr uint64_t kKrBlocks = 65536;
 
@@ -298,7 +285,7 @@ __global__ __launch_bounds__(kBlock) void cohort_kr_kernel(const double *__restr
 
 uint64_t row_stride(const epik_amd_cohort *cohort) { return 2ull * cohort->num_branches + kTotals; }
 uint64_t cell_count(const epik_amd_cohort *cohort) { return cohort->num_samples * row_stride(cohort) + 1; }
-uint32_t padded_samples(const epik_amd_cohort *cohort) { return (cohort->num_samples + kTile - 1) / kTile * kTile; }
+uint32_t padded_samples(const epik_amd_cohort *cohort) { return cohort_padded_samples(cohort); }
 
 // a cohort made for another device, tree or keep_at_most than the placer's would be summed wrongly, silently
 int check_pair(const epik_amd_placer *p, const epik_amd_cohort *cohort)
@@ -410,12 +397,17 @@ constexpr HostVariant kForwardHost{.chunk_reads = 1u << 18, .chunk_bytes = 64u <
 void free_cohort(epik_amd_cohort *cohort)
 {
     (void)hipFree(cohort->d_cells), (void)hipFree(cohort->d_prefix), (void)hipFree(cohort->d_total);
-    (void)hipFree(cohort->d_planes), (void)hipFree(cohort->d_half);
+    (void)hipFree(cohort->d_planes), (void)hipFree(cohort->d_half), (void)hipFree(cohort->d_squash);
 }
 
 }  // namespace
 
 namespace epik_amd {
+
+int cohort_kr_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out, hipStream_t stream)
+{
+    return kr_device_impl(cohort, tree, branch_length, d_out, stream);
+}
 
 int cohort_host_chunked(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                         const uint32_t *weights, const uint32_t *samples, uint64_t n, uint32_t mode, uint64_t longest_placed,

@@ -73,10 +73,18 @@ void sample_cohort::merge(const sample_cohort& other)
     bad_samples += other.bad_samples;
 }
 
-int kr_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
-              const double* branch_length, double* out, std::string& err)
+namespace {
+
+// what both the distance matrix and the clustering start from: first[] and the lengths checked, half[b] = 0.5 * bl[b],
+// T_s, and C[s][b], B[s][b] -- one conversion each and one division; T_s == 0 leaves the row unused
+struct kr_planes {
+    std::vector<double> C, B, half;
+    std::vector<uint64_t> total;
+};
+
+int make_planes(const uint64_t* mass, size_t S, size_t N, const uint32_t* first, const double* branch_length, kr_planes& p,
+                std::string& err)
 {
-    const size_t S = num_samples, N = num_branches;
     for (size_t b = 0; b < N; ++b) {
         if (first[b] > b) {
             err = "branch " + std::to_string(b) + ": first[b] = " + std::to_string(first[b]) + " is above the branch";
@@ -87,35 +95,92 @@ int kr_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches,
             return EPIK_AMD_ERR_INVALID;
         }
     }
-    // C[s][b], B[s][b]: one conversion each and one division; T_s == 0 leaves the row unused
-    std::vector<double> C(S * N), B(S * N), half(N);
-    std::vector<uint64_t> prefix(N + 1), total(S);
-    for (size_t b = 0; b < N; ++b) half[b] = 0.5 * branch_length[b];
+    p.C.assign(S * N, 0.0), p.B.assign(S * N, 0.0), p.half.assign(N, 0.0), p.total.assign(S, 0);
+    std::vector<uint64_t> prefix(N + 1);
+    for (size_t b = 0; b < N; ++b) p.half[b] = 0.5 * branch_length[b];
     for (size_t s = 0; s < S; ++s) {
         const uint64_t* m = mass + s * N;
         prefix[0] = 0;
         for (size_t b = 0; b < N; ++b) prefix[b + 1] = prefix[b] + m[b];
-        total[s] = prefix[N];
-        if (total[s] == 0) continue;
-        const double T = (double)total[s];
+        p.total[s] = prefix[N];
+        if (p.total[s] == 0) continue;
+        const double T = (double)p.total[s];
         for (size_t b = 0; b < N; ++b) {
             const uint64_t clade = prefix[b + 1] - prefix[first[b]], below = clade - m[b];
-            C[s * N + b] = (double)clade / T;
-            B[s * N + b] = (double)below / T;
+            p.C[s * N + b] = (double)clade / T;
+            p.B[s * N + b] = (double)below / T;
         }
     }
+    return EPIK_AMD_OK;
+}
+
+// the rule's sequential sum over two pairs of planes
+inline double kr_of(const double* cx, const double* bx, const double* cy, const double* by, const double* half, size_t N)
+{
+    double acc = 0.0;
+    for (size_t b = 0; b < N; ++b) acc = acc + half[b] * (std::fabs(cx[b] - cy[b]) + std::fabs(bx[b] - by[b]));
+    return acc;
+}
+
+}  // namespace
+
+int kr_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+              const double* branch_length, double* out, std::string& err)
+{
+    const size_t S = num_samples, N = num_branches;
+    kr_planes p;
+    if (const int rc = make_planes(mass, S, N, first, branch_length, p, err); rc != EPIK_AMD_OK) return rc;
     for (size_t s = 0; s < S; ++s) {
         out[s * S + s] = 0.0;
         for (size_t t = s + 1; t < S; ++t) {
             double acc = -1.0;
-            if (total[s] != 0 && total[t] != 0) {
-                const double *cs = &C[s * N], *ct = &C[t * N], *bs = &B[s * N], *bt = &B[t * N];
-                acc = 0.0;
-                for (size_t b = 0; b < N; ++b) acc = acc + half[b] * (std::fabs(cs[b] - ct[b]) + std::fabs(bs[b] - bt[b]));
-            }
+            if (p.total[s] != 0 && p.total[t] != 0)
+                acc = kr_of(&p.C[s * N], &p.B[s * N], &p.C[t * N], &p.B[t * N], p.half.data(), N);
             out[s * S + t] = out[t * S + s] = acc;
         }
     }
+    return EPIK_AMD_OK;
+}
+
+int squash_merges(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                  const double* branch_length, epik_amd_squash_merge* merges, uint32_t* num_merges, std::string& err)
+{
+    const size_t S = num_samples, N = num_branches;
+    kr_planes p;
+    if (const int rc = make_planes(mass, S, N, first, branch_length, p, err); rc != EPIK_AMD_OK) return rc;
+    std::vector<char> live(S);
+    std::vector<uint32_t> w(S, 1), node(S);
+    std::vector<double> D(S * S, 0.0), Cm(N), Bm(N);
+    for (size_t s = 0; s < S; ++s) live[s] = p.total[s] != 0, node[s] = (uint32_t)s;
+    for (size_t r = 0; r < S; ++r)
+        for (size_t c = r + 1; c < S; ++c)
+            if (live[r] && live[c])
+                D[r * S + c] = D[c * S + r] = kr_of(&p.C[r * N], &p.B[r * N], &p.C[c * N], &p.B[c * N], p.half.data(), N);
+    uint32_t t = 0;
+    for (;; ++t) {
+        // the first pair, in row-major order, with the smallest distance
+        size_t r = S, c = S;
+        for (size_t i = 0; i < S; ++i)
+            for (size_t j = i + 1; live[i] && j < S; ++j)
+                if (live[j] && (r == S || D[i * S + j] < D[r * S + c])) r = i, c = j;
+        if (r == S) break;
+        double *cr = &p.C[r * N], *br = &p.B[r * N];
+        const double *cc = &p.C[c * N], *bc = &p.B[c * N];
+        const double wr = (double)w[r], wc = (double)w[c], W = (double)(w[r] + w[c]);
+        for (size_t b = 0; b < N; ++b) {
+            Cm[b] = (wr * cr[b] + wc * cc[b]) / W;
+            Bm[b] = (wr * br[b] + wc * bc[b]) / W;
+        }
+        merges[t] = epik_amd_squash_merge{node[r], node[c], D[r * S + c], kr_of(Cm.data(), Bm.data(), cr, br, p.half.data(), N),
+                                          kr_of(Cm.data(), Bm.data(), cc, bc, p.half.data(), N)};
+        for (size_t b = 0; b < N; ++b) cr[b] = Cm[b], br[b] = Bm[b];
+        w[r] += w[c], node[r] = (uint32_t)(S + t), live[c] = 0;
+        for (size_t x = 0; x < S; ++x)
+            if (live[x] && x != r)
+                D[r * S + x] = D[x * S + r] = kr_of(cr, br, &p.C[x * N], &p.B[x * N], p.half.data(), N);
+    }
+    *num_merges = t;
+    for (size_t k = t; k + 1 < S; ++k) merges[k] = epik_amd_squash_merge{EPIK_AMD_SQUASH_NONE, EPIK_AMD_SQUASH_NONE, 0.0, 0.0, 0.0};
     return EPIK_AMD_OK;
 }
 
@@ -146,13 +211,14 @@ std::vector<cohort_sample> read_cohort_list(const std::string& list_file)
     return samples;
 }
 
-std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir)
+std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir,
+                                 const std::string& extension)
 {
     const auto slash = list_file.find_last_of('/');
     const std::string base = slash == std::string::npos ? list_file : list_file.substr(slash + 1);
     std::string dir = output_dir;
     if (!dir.empty() && dir.back() != '/') dir.push_back('/');
-    return dir + "cohort_" + what + "_" + base + ".tsv";
+    return dir + "cohort_" + what + "_" + base + extension;
 }
 
 std::string format_cohort_samples_tsv(const std::vector<cohort_sample>& samples, const sample_cohort& cohort)
@@ -198,6 +264,69 @@ std::string format_cohort_kr_tsv(const std::vector<cohort_sample>& samples, cons
         out += '\n';
     }
     return out;
+}
+
+namespace {
+
+std::string g17(double v)
+{
+    char text[40];
+    std::snprintf(text, sizeof text, "%.17g", v);
+    return text;
+}
+
+// a sample's name as a newick label: as it is when every character is of [A-Za-z0-9_.-], else '...', inner quotes doubled
+std::string newick_label(const std::string& name)
+{
+    bool plain = !name.empty();
+    for (const char ch : name)
+        plain = plain && ((ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z') || (ch >= '0' && ch <= '9') || ch == '_' || ch == '.' || ch == '-');
+    if (plain) return name;
+    std::string out = "'";
+    for (const char ch : name) {
+        if (ch == '\'') out += '\'';
+        out += ch;
+    }
+    return out + "'";
+}
+
+}  // namespace
+
+std::string format_squash_tsv(const std::vector<cohort_sample>& samples, const std::vector<char>& live,
+                              const epik_amd_squash_merge* merges, uint32_t num_merges)
+{
+    const size_t S = samples.size();
+    size_t clustered = 0;
+    for (size_t s = 0; s < S; ++s) clustered += live[s] ? 1 : 0;
+    std::string out = "# epik_amd squash v1  samples=" + std::to_string(S) + " clustered=" + std::to_string(clustered) +
+                      " merges=" + std::to_string(num_merges) + "\n";
+    for (size_t s = 0; s < S; ++s)
+        if (!live[s]) out += "# unclustered\t" + samples[s].name + "\n";
+    out += "step\tnode\ta\tb\tsize\tdist\tlen_a\tlen_b\n";
+    std::vector<uint64_t> size(S + num_merges, 1);
+    for (uint32_t t = 0; t < num_merges; ++t) {
+        size[S + t] = size.at(merges[t].a) + size.at(merges[t].b);
+        out += std::to_string(t) + '\t' + std::to_string(S + t) + '\t' + std::to_string(merges[t].a) + '\t' +
+               std::to_string(merges[t].b) + '\t' + std::to_string(size[S + t]) + '\t' + g17(merges[t].dist) + '\t' +
+               g17(merges[t].len_a) + '\t' + g17(merges[t].len_b) + '\n';
+    }
+    return out;
+}
+
+std::string format_squash_newick(const std::vector<cohort_sample>& samples, const std::vector<char>& live,
+                                 const epik_amd_squash_merge* merges, uint32_t num_merges)
+{
+    const size_t S = samples.size();
+    std::vector<std::string> text(S + num_merges);  // (bottom up: a record names only nodes made before it)
+    for (size_t s = 0; s < S; ++s)
+        if (live[s]) text[s] = newick_label(samples[s].name);
+    for (uint32_t t = 0; t < num_merges; ++t)
+        text[S + t] = "(" + std::move(text.at(merges[t].a)) + ":" + g17(merges[t].len_a) + "," + std::move(text.at(merges[t].b)) +
+                      ":" + g17(merges[t].len_b) + ")";
+    if (num_merges) return text[S + num_merges - 1] + ";\n";
+    for (size_t s = 0; s < S; ++s)
+        if (live[s]) return text[s] + ";\n";
+    return ";\n";
 }
 
 void write_through_part(const std::string& filename, const std::string& text)

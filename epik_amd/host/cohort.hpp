@@ -43,6 +43,12 @@ struct sample_cohort {
 int kr_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
               const double* branch_length, double* out, std::string& err);
 
+/// Squash clustering by the rule (include/epik_amd.h): merges[num_samples - 1], every record written, the unused ones as
+/// the rule says, and *num_merges.  The code behind epik_amd_cohort_squash_host; libepik_amd's squash kernels
+/// (squash_place.hip) give the same bits.  0, or EPIK_AMD_ERR_INVALID with `err` as kr_matrix.
+int squash_merges(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                  const double* branch_length, epik_amd_squash_merge* merges, uint32_t* num_merges, std::string& err);
+
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
 /// name or path, a name given before, or a file that cannot be read; and for a list without any sample.
@@ -51,8 +57,9 @@ struct cohort_sample {
 };
 std::vector<cohort_sample> read_cohort_list(const std::string& list_file);
 
-/// <output_dir>/cohort_<what>_<basename(list)>.tsv, what = samples | profile | kr
-std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir);
+/// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash
+std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir,
+                                 const std::string& extension = ".tsv");
 
 /// cohort_samples: a header line, then per sample in list order name, records, placed, no_hit, too_short, too_narrow,
 /// total_mass_q.  cohort_profile: long format, name, edge_num, best, mass_q for every (sample, branch) cell with a
@@ -61,6 +68,15 @@ std::string make_cohort_filename(const std::string& what, const std::string& lis
 std::string format_cohort_samples_tsv(const std::vector<cohort_sample>& samples, const sample_cohort& cohort);
 std::string format_cohort_profile_tsv(const std::vector<cohort_sample>& samples, const sample_cohort& cohort);
 std::string format_cohort_kr_tsv(const std::vector<cohort_sample>& samples, const std::vector<double>& kr);
+/// cohort_squash .tsv: "# epik_amd squash v1  samples=S clustered=S' merges=M", a "# unclustered<TAB>name" line per
+/// empty sample (live[s] == 0), the header step node a b size dist len_a len_b, a line per merge: a leaf is its index in
+/// list order, an internal node S + step, size the samples under the node, doubles as %.17g.  .nwk: the cluster tree,
+/// child a before child b, lengths %.17g, none at the root, leaves labelled with the names ('...' with inner quotes
+/// doubled for a name with a character outside [A-Za-z0-9_.-]); "name;" for one clustered sample, ";" for none.
+std::string format_squash_tsv(const std::vector<cohort_sample>& samples, const std::vector<char>& live,
+                              const epik_amd_squash_merge* merges, uint32_t num_merges);
+std::string format_squash_newick(const std::vector<cohort_sample>& samples, const std::vector<char>& live,
+                                 const epik_amd_squash_merge* merges, uint32_t num_merges);
 /// `text` into `filename` through `filename`.part, renamed when all of it is written
 void write_through_part(const std::string& filename, const std::string& text);
 

@@ -3,6 +3,8 @@
 //   cohort_test add <out.bin> <in.bin>...   the cohort of every input, merged: uint64 mass[S][N], best[S][N],
 //                                           totals[S][5], bad_samples
 //   cohort_test kr <out.bin> <in.bin>       the KR matrix, float64 [S][S]
+//   cohort_test squash <out.bin> <in.bin>   the squash clustering of a `kr` input: epik_amd_squash_merge [S - 1], then
+//                                           uint32 num_merges
 // An `add` input holds, little endian: uint64 n, keep, num_branches, num_samples; epik_amd_placement rows[n][keep];
 // uint32 n_rows[n]; uint32 kmer_counts[n][keep]; uint32 weights[n]; uint32 samples[n].
 // A `kr` input: uint64 num_samples, num_branches; uint64 mass[S][N]; uint32 first[N]; float64 branch_length[N].
@@ -81,7 +83,28 @@ int main(int argc, char** argv)
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }
-        std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin>\n";
+        if (argc == 4 && std::strcmp(argv[1], "squash") == 0) {
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto mass = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const auto length = read_array<double>(in, N);
+            std::vector<epik_amd_squash_merge> merges(S - 1);
+            uint32_t num_merges = 0;
+            std::string err;
+            if (epik_amd::squash_merges(mass.data(), (uint32_t)S, (uint32_t)N, first.data(), length.data(), merges.data(),
+                                        &num_merges, err) != 0)
+                throw std::runtime_error(err);
+            std::ofstream out(argv[2], std::ios::binary);
+            write_array(out, merges.data(), merges.size());
+            write_array(out, &num_merges, 1);
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
+        std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin> | squash <out.bin> <in.bin>\n";
         return 2;
     } catch (const std::exception& error) {
         std::cerr << "Error: " << error.what() << std::endl;

@@ -220,6 +220,9 @@ const char* kHelp =
     "                          cohort_kr_<list>.tsv (the Kantorovich-Rubinstein distance between every two samples), summed\n"
     "                          and computed on the device(s); with --strand / --translate, not with --mates, --profile,\n"
     "                          --profile-only, --assign or --db-shard > 1\n"
+    "      --cohort-squash     With --cohort: also cluster the samples by squash clustering (Matsen & Evans 2013) on the\n"
+    "                          device, every merged cluster the weighted average of its parts' masses, and write\n"
+    "                          cohort_squash_<list>.tsv (a line per merge) and cohort_squash_<list>.nwk (the cluster tree)\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -260,7 +263,7 @@ options parse_args(int argc, char** argv)
         } else {
             continue;  // positional arguments are ignored (epik.py passes the query twice, epik.py:88,96)
         }
-        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort") && !have_value)) {  // flags
+        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash") && !have_value)) {  // flags
             opt.values[name] = "1";
             continue;
         }
@@ -359,7 +362,8 @@ int main(int argc, char** argv)
             assign_tau_q = epik_amd::assign_tau_q(tau);
         }
         // --cohort: checked before anything is opened or any device touched
-        const bool with_cohort = parsed.has("cohort");
+        const bool with_cohort = parsed.has("cohort"), with_squash = parsed.has("cohort-squash");
+        if (with_squash && !with_cohort) throw std::runtime_error("--cohort-squash needs --cohort (it clusters the samples of the list)");
         if (with_cohort) {
             for (const char* other : {"mates", "profile-only", "profile", "assign"})
                 if (parsed.has(other)) throw std::runtime_error(std::string("--cohort does not work with --") + other);
@@ -709,14 +713,31 @@ int main(int argc, char** argv)
         const auto cohort_samples_filename = epik_amd::make_cohort_filename("samples", query_file, output_dir);
         const auto cohort_profile_filename = epik_amd::make_cohort_filename("profile", query_file, output_dir);
         const auto cohort_kr_filename = epik_amd::make_cohort_filename("kr", query_file, output_dir);
+        const auto cohort_squash_filename = epik_amd::make_cohort_filename("squash", query_file, output_dir);
+        const auto cohort_squash_tree_filename = epik_amd::make_cohort_filename("squash", query_file, output_dir, ".nwk");
         if (with_cohort) {
             // the handles' cohorts summed on the first device, read once, and the distances computed there
             epik_amd::sample_cohort cohort((uint32_t)cohort_samples.size(), (uint32_t)tree.get_node_count());
             std::vector<double> kr(cohort_samples.size() * cohort_samples.size());
-            placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data());
+            std::vector<epik_amd_squash_merge> merges(with_squash ? cohort_samples.size() - 1 : 0);
+            uint32_t num_merges = 0;
+            placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
+                               with_squash ? &num_merges : nullptr);
             epik_amd::write_through_part(cohort_samples_filename, epik_amd::format_cohort_samples_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_profile_filename, epik_amd::format_cohort_profile_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_kr_filename, epik_amd::format_cohort_kr_tsv(cohort_samples, kr));
+            if (with_squash) {
+                std::vector<char> live(cohort_samples.size());  // (T_s > 0, the sum wrapping as the rule's)
+                for (size_t s = 0; s < live.size(); ++s) {
+                    uint64_t total = 0;
+                    for (size_t b = 0; b < cohort.num_branches; ++b) total += cohort.mass[s * cohort.num_branches + b];
+                    live[s] = total != 0;
+                }
+                epik_amd::write_through_part(cohort_squash_filename,
+                                             epik_amd::format_squash_tsv(cohort_samples, live, merges.data(), num_merges));
+                epik_amd::write_through_part(cohort_squash_tree_filename,
+                                             epik_amd::format_squash_newick(cohort_samples, live, merges.data(), num_merges));
+            }
         }
         if (with_assign) {
             assign_out.close();
@@ -741,6 +762,9 @@ int main(int argc, char** argv)
         if (with_cohort)
             std::cout << "Cohort samples: " << cohort_samples_filename << "\nCohort profile: " << cohort_profile_filename
                       << "\nCohort distances: " << cohort_kr_filename << std::endl;
+        if (with_squash)
+            std::cout << "Cohort clustering: " << cohort_squash_filename << "\nCohort cluster tree: " << cohort_squash_tree_filename
+                      << std::endl;
         if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;
         if (strands_out.is_open()) {
             strands_out.close();

@@ -31,6 +31,7 @@
 #pragma weak epik_amd_cohort_read
 #pragma weak epik_amd_cohort_add_cells
 #pragma weak epik_amd_cohort_kr
+#pragma weak epik_amd_cohort_squash
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -234,8 +235,10 @@ void placer::set_cohort(uint32_t num_samples)
     }
 }
 
-void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr)
+void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
+                         epik_amd_squash_merge* merges, uint32_t* num_merges)
 {
+    if (num_merges && !&epik_amd_cohort_squash) throw std::runtime_error("GPU placer: this libepik_amd has no squash clustering");
     const auto check = [](int rc) {
         if (rc != EPIK_AMD_OK) throw std::runtime_error(std::string("GPU placer: ") + epik_amd_last_error());
     };
@@ -259,7 +262,8 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
     }
     epik_amd_tree* tree = nullptr;
     check(epik_amd_tree_create(_devices[0], parent.data(), length.data(), (uint32_t)parent.size(), &tree));
-    const int rc = epik_amd_cohort_kr(_cohorts[0], tree, length.data(), kr);
+    int rc = epik_amd_cohort_kr(_cohorts[0], tree, length.data(), kr);
+    if (rc == EPIK_AMD_OK && num_merges) rc = epik_amd_cohort_squash(_cohorts[0], tree, length.data(), merges, num_merges);
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);
     if (rc != EPIK_AMD_OK) throw std::runtime_error("GPU placer: " + message);

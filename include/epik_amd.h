@@ -678,6 +678,25 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *   is symmetric.  The sum over b is strictly sequential per pair: an implementation may share out the pairs, never
  *   the branches of one pair.
  *
+ * Squash clustering (Matsen & Evans 2013) of the cohort's samples.  From mass[S][N], first[N] and branch_length[N] as
+ *   for the KR distance; T_s, C_s[b], B_s[b] are exactly those above, and KR(x, y) over ANY two pairs of planes
+ *   (C_x, B_x), (C_y, B_y) is the sequential sum above: acc = +0.0, then for b = 0 .. N - 1 in this order, in double,
+ *   nothing fused, acc = acc + (0.5 * bl[b]) * (|C_x[b] - C_y[b]| + |B_x[b] - B_y[b]|).
+ *   Slots.  Slot s = sample s, s in [0, S).  A slot is live iff T_s > 0: empty samples are never clustered.
+ *     w[s] = 1, node[s] = s, D[r][c] = KR(r, c) for live r != c (the matrix epik_amd_cohort_kr gives).
+ *   Step t = 0, 1, ...: scan the pairs (r, c), r < c, both live, in row-major order (r ascending, then c ascending) and
+ *     take the FIRST pair with the smallest D[r][c] (strict <: ties go to the earlier pair).  With fewer than two live
+ *     slots the clustering is over.
+ *   Merged planes, for every b, W = (double)(w[r] + w[c]), each operation rounded on its own:
+ *     C_m[b] = ((double)w[r] * C_r[b] + (double)w[c] * C_c[b]) / W,        B_m[b] likewise.
+ *   Record t = {a = node[r], b = node[c], dist = D[r][c], len_a = KR(m, r), len_b = KR(m, c)}, the two lengths with
+ *     the planes of r and c as they were before the merge.
+ *   Then slot r takes the planes of m, w[r] += w[c], node[r] = S + t, slot c dies, and D[r][x] = D[x][r] = KR(m, x)
+ *     for every live x != r.
+ *   Result.  max(0, live - 1) merges; the records past them are {0xffffffff, 0xffffffff, 0, 0, 0}.  The sum over b
+ *     stays strictly sequential per pair: an implementation may share out the clusters x, the branches of the
+ *     AVERAGING and the scan, never the branches of one distance.
+ *
  * An epik_amd_cohort is an object of its own, created for a placer's device, num_branches and keep_at_most (whole
  * databases only, not a k-mer-space shard) and num_samples >= 1; all zero at create() and after reset().
  *   add_device  asynchronous on `stream`, allocates nothing: as epik_amd_profile_add_device, with d_samples (uint32 [n],
@@ -690,6 +709,12 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *               [S][S] in device memory, every cell written.  The first call allocates the workspace.   kr: the same
  *               into host memory, synchronous.
  *   kr_host     the rule on the host from mass[S][N] and first[N], no device at all; first[b] > b is refused.
+ *   squash_device  checks and workspace as kr_device (the first call allocates a distance matrix of its own beside it),
+ *               then enqueues the normalise and distance kernels and all S - 1 steps on `stream`, no readback in
+ *               between: d_merges is epik_amd_squash_merge [S - 1] and d_num_merges one uint32 in device memory, every
+ *               record written.  S = 1 is valid: zero merges (d_merges may be NULL then).  The cells are not changed.
+ *               squash: the same into host memory, synchronous.
+ *   squash_host the rule on the host, as kr_host.
  * cohort_reads / _strands / _frames / _mates: the profile_* twins with samples[n] (HOST uint32) beside the weights.
  */
 typedef struct epik_amd_cohort epik_amd_cohort;
@@ -708,6 +733,18 @@ int epik_amd_cohort_kr_device(epik_amd_cohort *cohort, const epik_amd_tree *tree
 int epik_amd_cohort_kr(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, double *out);
 int epik_amd_cohort_kr_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                             const double *branch_length, double *out);
+typedef struct epik_amd_squash_merge {
+    uint32_t a, b;       /* the two nodes merged: a leaf is its sample, an internal node S + the step that made it */
+    double dist;         /* D[r][c] when they were merged */
+    double len_a, len_b; /* KR(merged, a), KR(merged, b): the edge lengths of the cluster tree */
+} epik_amd_squash_merge; /* 32 bytes */
+#define EPIK_AMD_SQUASH_NONE 0xffffffffu
+int epik_amd_cohort_squash_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                                  void *d_merges, void *d_num_merges, void *stream);
+int epik_amd_cohort_squash(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                           epik_amd_squash_merge *merges, uint32_t *num_merges);
+int epik_amd_cohort_squash_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                const double *branch_length, epik_amd_squash_merge *merges, uint32_t *num_merges);
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n);
 int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
