@@ -15,6 +15,8 @@ paired-end sample: every pair gets one placement; --assign / --assign-mass, per 
 of its placement mass and the EDPL; --cohort, the input file is a list of samples (name<TAB>path lines): their profiles and
 the Kantorovich-Rubinstein distance between every two of them, cohort_samples_ / cohort_profile_ / cohort_kr_<list>.tsv;
 --cohort-squash, with --cohort: the squash clustering of the samples, cohort_squash_<list>.tsv and .nwk.
+--cohort-epca, with --cohort: the edge principal components of the samples, cohort_epca_<list>.tsv and
+cohort_epca_edges_<list>.tsv; --cohort-epca-components K of them (default 5).
 """
 from __future__ import annotations
 
@@ -80,6 +82,12 @@ PLACE_OPTIONS = [
     (("--cohort-squash",), dict(is_flag=True, help="With --cohort: also cluster the samples by squash clustering on the device "
                                                    "and write cohort_squash_<list>.tsv (a line per merge) and "
                                                    "cohort_squash_<list>.nwk (the cluster tree).")),
+    (("--cohort-epca",), dict(is_flag=True, help="With --cohort: also compute the edge principal components of the samples on "
+                                                 "the device and write cohort_epca_<list>.tsv (the components and every "
+                                                 "sample's projections) and cohort_epca_edges_<list>.tsv (the components' "
+                                                 "coefficients per inner branch).")),
+    (("--cohort-epca-components",), dict(type=click.IntRange(1, 64), default=None,
+                                         help="With --cohort-epca: the number of components, in [1, 64] [default: 5].")),
 ]
 
 
@@ -95,13 +103,18 @@ def driver_path(states: str) -> str:
 
 def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpus, input_file, db_shard=1,
                    strand="forward", translate=None, profile=False, profile_only=False, mates=None,
-                   mate_orientation="fr", assign=False, assign_mass=None, cohort=False, cohort_squash=False):
+                   mate_orientation="fr", assign=False, assign_mass=None, cohort=False, cohort_squash=False,
+                   cohort_epca=False, cohort_epca_components=None):
     if assign_mass is not None and not assign:
         raise click.UsageError("--assign-mass needs --assign")
     if assign and db_shard != 1:
         raise click.UsageError("--assign does not work with --db-shard > 1")
     if cohort_squash and not cohort:
         raise click.UsageError("--cohort-squash needs --cohort")
+    if cohort_epca and not cohort:
+        raise click.UsageError("--cohort-epca needs --cohort")
+    if cohort_epca_components is not None and not cohort_epca:
+        raise click.UsageError("--cohort-epca-components needs --cohort-epca")
     if cohort:
         for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
                             ("--assign", assign), ("--db-shard > 1", db_shard != 1)):
@@ -135,6 +148,10 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--cohort"]
     if cohort_squash:
         argv += ["--cohort-squash"]
+    if cohort_epca:
+        argv += ["--cohort-epca"]
+        if cohort_epca_components is not None:
+            argv += ["--cohort-epca-components", str(int(cohort_epca_components))]
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 

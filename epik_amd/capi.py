@@ -26,6 +26,11 @@ CONFIDENCE = np.dtype([("clade", np.uint32), ("clade_mass_q", np.uint32), ("edpl
 #: epik_amd_squash_merge (32 bytes)
 SQUASH_MERGE = np.dtype([("a", np.uint32), ("b", np.uint32), ("dist", np.float64), ("len_a", np.float64), ("len_b", np.float64)])
 SQUASH_NONE = 0xFFFFFFFF
+#: epik_amd_epca_info (32 bytes)
+EPCA_INFO = np.dtype([("used", np.uint32), ("components", np.uint32), ("sweeps", np.uint32), ("converged", np.uint32),
+                      ("trace", np.float64), ("scale", np.float64)])
+EPCA_MAX_COMPONENTS = 64
+EPCA_MAX_SWEEPS = 64
 #: numpy mirror of `epik_amd_pkdb_value` / `i2l::pkdb_value` (8 bytes)
 PKDB_VALUE = np.dtype([("branch", np.uint32), ("score", np.float32)])
 
@@ -103,6 +108,9 @@ EXPORTS = (
     "epik_amd_cohort_squash_device",
     "epik_amd_cohort_squash",
     "epik_amd_cohort_squash_host",
+    "epik_amd_cohort_epca_device",
+    "epik_amd_cohort_epca",
+    "epik_amd_cohort_epca_host",
     "epik_amd_placer_cohort_reads",
     "epik_amd_placer_cohort_strands",
     "epik_amd_placer_cohort_frames",
@@ -413,6 +421,12 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_squash.argtypes = [vp, vp, vp, vp, ctypes.POINTER(u32)]
     lib.epik_amd_cohort_squash_host.restype = i32
     lib.epik_amd_cohort_squash_host.argtypes = [vp, u32, u32, vp, vp, vp, ctypes.POINTER(u32)]
+    lib.epik_amd_cohort_epca_device.restype = i32
+    lib.epik_amd_cohort_epca_device.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
+    lib.epik_amd_cohort_epca.restype = i32
+    lib.epik_amd_cohort_epca.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+    lib.epik_amd_cohort_epca_host.restype = i32
+    lib.epik_amd_cohort_epca_host.argtypes = [vp, u32, u32, vp, u32, vp, vp, vp, vp]
     lib.epik_amd_placer_cohort_reads.restype = i32
     lib.epik_amd_placer_cohort_reads.argtypes = [vp, vp, vp, vp, vp, vp, u64]
     for name in ("epik_amd_placer_cohort_strands", "epik_amd_placer_cohort_frames", "epik_amd_placer_cohort_mates"):

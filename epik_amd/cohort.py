@@ -10,6 +10,10 @@ first[] of a tree from its parents; `format_*` / `read_*` are the files the driv
 Squash clustering of the samples (the header's second rule): `Cohort.squash` / `squash_device` on the device,
 `squash_host` on the host, each giving the merge records (`capi.SQUASH_MERGE`); `format_squash_tsv`,
 `format_squash_newick` and `read_squash_tsv` are the two files of --cohort-squash.
+
+Edge principal components of the samples (the header's third rule): `Cohort.epca` / `epca_device` on the device,
+`epca_host` on the host, each giving an `Epca`; `format_epca_tsv`, `format_epca_edges_tsv` and their readers are the two
+files of --cohort-epca.
 """
 from __future__ import annotations
 
@@ -89,6 +93,55 @@ def _merges_made(merges, count):
             rest["dist"].view(np.uint64).any() or rest["len_a"].view(np.uint64).any() or rest["len_b"].view(np.uint64).any():
         raise RuntimeError("squash: the records past num_merges are not the unused record")
     return merges[:count].copy()
+
+
+@dataclass
+class Epca:
+    """Edge principal components as the rule leaves them: `mu` float64 [K], `proj` float64 [S][K], `edge` float64 [K][N]
+    and `info`, one `capi.EPCA_INFO` record (used, components, sweeps, converged, trace, scale)."""
+
+    mu: np.ndarray
+    proj: np.ndarray
+    edge: np.ndarray
+    info: np.ndarray
+
+    @property
+    def components(self) -> int:
+        return int(self.info["components"])
+
+    def null(self) -> np.ndarray:
+        """Per component k < components whether it is null: !(mu_k > 2^-40 * scale)."""
+        return ~(self.mu[:self.components] > np.ldexp(1.0, -40) * float(self.info["scale"]))
+
+
+def _components(num_components) -> int:
+    k = int(num_components)
+    if not 0 <= k <= 0xFFFFFFFF:
+        raise ValueError("num_components must fit 32 bits")
+    return k
+
+
+def _epca_buffers(s, n, k):
+    k = max(k, 1)            # (a refused K still needs somewhere to point)
+    return Epca(np.full(k, np.nan), np.full((s, k), np.nan), np.full((k, n), np.nan), np.zeros(1, dtype=capi.EPCA_INFO))
+
+
+def epca_host(mass, first, num_components: int = 5) -> Epca:
+    """The edge principal components of the rule for mass[S][N] on the host (`epik_amd_cohort_epca_host`)."""
+    lib = capi.load()
+    mass = np.ascontiguousarray(mass, dtype=np.uint64)
+    if mass.ndim != 2:
+        raise ValueError("mass must be [num_samples][num_branches]")
+    first = np.ascontiguousarray(first, dtype=np.uint32)
+    if first.shape != (mass.shape[1],):
+        raise ValueError(f"first must hold one value per branch ({mass.shape[1]})")
+    s, n = mass.shape
+    k = _components(num_components)
+    out = _epca_buffers(s, n, k)
+    capi.check(lib.epik_amd_cohort_epca_host(mass.ctypes.data, s, n, first.ctypes.data, k, out.mu.ctypes.data,
+                                             out.proj.ctypes.data, out.edge.ctypes.data, out.info.ctypes.data))
+    out.info = out.info[0]
+    return out
 
 
 @dataclass
@@ -225,6 +278,26 @@ class Cohort:
                                                     merges.ctypes.data if len(merges) else None, ctypes.byref(count)))
         return _merges_made(merges, count.value)
 
+    def epca_device(self, tree, num_components: int, d_mu: int, d_proj: int, d_edge: int, d_info: int, stream: int = 0) -> None:
+        """The edge principal components into device memory: d_mu float64 [K], d_proj float64 [S][K], d_edge float64
+        [K][N], d_info one `capi.EPCA_INFO`, every cell written.  Synchronises `stream` once for the number of used
+        samples and, on the eigensolver's global path, once per sweep (`epik_amd_cohort_epca_device`)."""
+        if tree is None or not getattr(tree, "_handle", None):
+            raise ValueError("epca needs a device tree (Placer.tree)")
+        capi.check(self._lib.epik_amd_cohort_epca_device(self._handle, tree._handle, _components(num_components), d_mu or None,
+                                                         d_proj or None, d_edge or None, d_info or None, stream or None))
+
+    def epca(self, tree, num_components: int = 5) -> Epca:
+        """The edge principal components of the samples, an `Epca` (`epik_amd_cohort_epca`)."""
+        if tree is None or not getattr(tree, "_handle", None):
+            raise ValueError("epca needs a device tree (Placer.tree)")
+        k = _components(num_components)
+        out = _epca_buffers(self.num_samples, self.num_branches, k)
+        capi.check(self._lib.epik_amd_cohort_epca(self._handle, tree._handle, k, out.mu.ctypes.data, out.proj.ctypes.data,
+                                                  out.edge.ctypes.data, out.info.ctypes.data))
+        out.info = out.info[0]
+        return out
+
     def reset(self) -> None:
         capi.check(self._lib.epik_amd_cohort_reset(self._handle))
 
@@ -318,6 +391,94 @@ def read_squash_tsv(path: str):
     info["node"] = np.array([int(r[1]) for r in rows], dtype=np.int64)
     info["size"] = np.array([int(r[4]) for r in rows], dtype=np.int64)
     return merges, info
+
+
+# ---- the files of --cohort-epca ----------------------------------------------------------------------------------------
+def _epca_columns(k: int) -> str:
+    return "".join(f"\tpc{i + 1}" for i in range(k))
+
+
+def format_epca_tsv(names, used, epca: Epca) -> str:
+    """cohort_epca_<list>.tsv (`used[s]`: sample s has mass, T_s > 0): the first line, a `# unused` line per sample without mass, a `# component` line per
+    component (k from 1; mu, lambda = mu / max(L - 1, 1), fraction = mu / trace or 0; null|ok), the column names, then
+    per used sample, in list order, its name and its projections; doubles as %.17g."""
+    info = epca.info
+    is_used = _live_mask(names, used)
+    used, kc = int(info["used"]), int(info["components"])
+    s = len(names)
+    if int(is_used.sum()) != used:
+        raise ValueError("the used flags do not fit the number of used samples")
+    lines = [f"# epik_amd epca v1  samples={s} used={used} components={kc} sweeps={int(info['sweeps'])} "
+             f"converged={int(info['converged'])}"]
+    lines += [f"# unused\t{name}" for name, u in zip(names, is_used) if not u]
+    trace, null = float(info["trace"]), epca.null()
+    for k in range(kc):
+        mu = float(epca.mu[k])
+        lam, fraction = mu / float(max(used - 1, 1)), (mu / trace if trace != 0 else 0.0)
+        lines.append("# component\t%d\t%.17g\t%.17g\t%.17g\t%s" % (k + 1, mu, lam, fraction, "null" if null[k] else "ok"))
+    lines.append("name" + _epca_columns(kc))
+    for i, name in enumerate(names):
+        if is_used[i]:
+            lines.append("\t".join([name, *("%.17g" % float(x) for x in epca.proj[i, :kc])]))
+    return "\n".join(lines) + "\n"
+
+
+def format_epca_edges_tsv(first, epca: Epca) -> str:
+    """cohort_epca_edges_<list>.tsv: edge_num and the components' coefficients for every inner branch (first[b] < b) in id
+    order; doubles as %.17g."""
+    kc = int(epca.info["components"])
+    first = np.asarray(first, dtype=np.int64)
+    lines = ["edge_num" + _epca_columns(kc)]
+    for b in np.flatnonzero(first < np.arange(len(first))):
+        lines.append("\t".join([str(int(b)), *("%.17g" % float(x) for x in epca.edge[:kc, b])]))
+    return "\n".join(lines) + "\n"
+
+
+def read_epca_tsv(path: str):
+    """(names, proj, info): the used samples' names, float64 [L][K'], and {"samples", "used", "components", "sweeps",
+    "converged", "unused": names, "mu", "lambda", "fraction": float64 [K'], "null": bool [K']}."""
+    with open(path, newline="") as fh:
+        head = re.fullmatch(r"# epik_amd epca v1  samples=(\d+) used=(\d+) components=(\d+) sweeps=(\d+) converged=([01])",
+                            fh.readline().rstrip("\n"))
+        if not head:
+            raise ValueError(f"{path}: not a cohort epca file")
+        info = dict(zip(("samples", "used", "components", "sweeps", "converged"), (int(x) for x in head.groups())))
+        info["unused"] = []
+        comps = []
+        line = fh.readline().rstrip("\n")
+        while line.startswith("# "):
+            kind, rest = line[2:].split("\t", 1)
+            if kind == "unused":
+                info["unused"].append(rest)
+            elif kind == "component":
+                comps.append(rest.split("\t"))
+            else:
+                raise ValueError(f"{path}: not a cohort epca file")
+            line = fh.readline().rstrip("\n")
+        kc = info["components"]
+        if line != "name" + _epca_columns(kc) or [int(c[0]) for c in comps] != list(range(1, kc + 1)):
+            raise ValueError(f"{path}: the components do not follow the first line's count")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    if len(rows) != info["used"] or any(len(r) != kc + 1 for r in rows):
+        raise ValueError(f"{path}: the rows do not follow the first line's counts")
+    info["mu"] = np.array([float(c[1]) for c in comps], dtype=np.float64)
+    info["lambda"] = np.array([float(c[2]) for c in comps], dtype=np.float64)
+    info["fraction"] = np.array([float(c[3]) for c in comps], dtype=np.float64)
+    info["null"] = np.array([c[4] == "null" for c in comps], dtype=bool)
+    proj = np.array([[float(x) for x in r[1:]] for r in rows], dtype=np.float64).reshape(len(rows), kc)
+    return [r[0] for r in rows], proj, info
+
+
+def read_epca_edges_tsv(path: str):
+    """(edge_num int64 [E], coefficients float64 [E][K'])"""
+    with open(path, newline="") as fh:
+        head = fh.readline().rstrip("\n").split("\t")
+        if head[0] != "edge_num" or head[1:] != [f"pc{i + 1}" for i in range(len(head) - 1)]:
+            raise ValueError(f"{path}: not a cohort epca edges file")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    kc = len(head) - 1
+    return (np.array([int(r[0]) for r in rows], dtype=np.int64),
+            np.array([[float(x) for x in r[1:]] for r in rows], dtype=np.float64).reshape(len(rows), kc))
 
 
 def read_samples_tsv(path: str):

@@ -1,5 +1,6 @@
-// cohort_device.hpp -- what cohort_place.hip and squash_place.hip share of a device cohort: the object itself and the
-// launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering starts from.
+// cohort_device.hpp -- what cohort_place.hip, squash_place.hip and epca_place.hip share of a device cohort: the object
+// itself and the launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering and the
+// edge principal components start from.
 #ifndef EPIK_AMD_COHORT_DEVICE_HPP
 #define EPIK_AMD_COHORT_DEVICE_HPP
 
@@ -23,6 +24,8 @@ struct epik_amd_cohort {
     double *d_half = nullptr;      // [N]: 0.5 * branch_length
     // the workspace of the squash clustering, allocated by the first squash_device (squash_place.hip):
     void *d_squash = nullptr;
+    // the workspace of the edge principal components, allocated by the first epca_device (epca_place.hip):
+    void *d_epca = nullptr;
 };
 
 namespace epik_amd {
@@ -32,6 +35,10 @@ inline uint32_t cohort_padded_samples(const epik_amd_cohort *cohort)
 {
     return (cohort->num_samples + kCohortTile - 1) / kCohortTile * kCohortTile;
 }
+
+// the checks of the cohort and the tree (device, N), the device drained, the workspace of the planes, then the normalise
+// kernel on `stream`: T_s in d_total, C and B in d_planes; *d_first: the tree's first[] on the device
+int cohort_normalise_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, hipStream_t stream, const uint32_t **d_first);
 
 // epik_amd_cohort_kr_device: the checks, the workspace, the lengths, then the normalise and distance kernels on `stream`
 int cohort_kr_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out,

@@ -325,23 +325,22 @@ int add_device_impl(epik_amd_cohort *cohort, const void *d_rows, const void *d_n
     return EPIK_AMD_OK;
 }
 
-int kr_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out, hipStream_t stream)
+// the tree of a distance or of anything else that starts from the planes: on the cohort's device, of its N; its first[]
+int check_tree(const epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t **d_first)
 {
     if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (!branch_length || !d_out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
     int tree_device = 0;
     uint32_t tree_branches = 0;
-    const uint32_t *d_first = nullptr;
-    if (const int rc = tree_first_device(tree, &tree_device, &tree_branches, &d_first); rc != EPIK_AMD_OK) return rc;
+    if (const int rc = tree_first_device(tree, &tree_device, &tree_branches, d_first); rc != EPIK_AMD_OK) return rc;
     if (tree_device != cohort->device || tree_branches != cohort->num_branches)
         return fail_with(EPIK_AMD_ERR_INVALID, "the tree does not fit the cohort (device or num_branches differ)");
+    return EPIK_AMD_OK;
+}
+
+// the device drained, the workspace of the planes, then cohort_normalise_kernel on `stream`
+int normalise_launch(epik_amd_cohort *cohort, const uint32_t *d_first, hipStream_t stream)
+{
     const uint32_t N = cohort->num_branches, S = cohort->num_samples, padded = padded_samples(cohort);
-    std::vector<double> half(N);
-    for (uint32_t b = 0; b < N; ++b) {
-        if (!(branch_length[b] >= 0.0) || !std::isfinite(branch_length[b]))
-            return fail_with(EPIK_AMD_ERR_INVALID, "branch " + std::to_string(b) + ": the branch length is negative or not finite");
-        half[b] = 0.5 * branch_length[b];
-    }
     HIP_TRY(hipSetDevice(cohort->device));
     HIP_TRY(hipDeviceSynchronize());  // (the adds enqueued so far, and a distance still reading the lengths)
     if (!cohort->d_planes) {
@@ -352,12 +351,30 @@ int kr_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const dou
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&cohort->d_planes), plane_bytes));
         HIP_TRY(hipMemset(cohort->d_planes, 0, plane_bytes));  // (the padding samples of the last tile stay zero)
     }
-    HIP_TRY(hipMemcpy(cohort->d_half, half.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
     const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    const uint64_t side = padded / kTile, tiles = side * (side + 1) / 2;
     hipLaunchKernelGGL(cohort_normalise_kernel, dim3((uint32_t)std::min<uint64_t>({S, kMaxBlocks, cap})), dim3(kBlock), 0, stream,
                        cohort->d_cells, d_first, S, N, padded, cohort->d_prefix, cohort->d_total, cohort->d_planes);
     HIP_TRY(hipGetLastError());
+    return EPIK_AMD_OK;
+}
+
+int kr_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out, hipStream_t stream)
+{
+    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    if (!branch_length || !d_out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    const uint32_t *d_first = nullptr;
+    if (const int rc = check_tree(cohort, tree, &d_first); rc != EPIK_AMD_OK) return rc;
+    const uint32_t N = cohort->num_branches, S = cohort->num_samples, padded = padded_samples(cohort);
+    std::vector<double> half(N);
+    for (uint32_t b = 0; b < N; ++b) {
+        if (!(branch_length[b] >= 0.0) || !std::isfinite(branch_length[b]))
+            return fail_with(EPIK_AMD_ERR_INVALID, "branch " + std::to_string(b) + ": the branch length is negative or not finite");
+        half[b] = 0.5 * branch_length[b];
+    }
+    if (const int rc = normalise_launch(cohort, d_first, stream); rc != EPIK_AMD_OK) return rc;
+    HIP_TRY(hipMemcpy(cohort->d_half, half.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
+    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
+    const uint64_t side = padded / kTile, tiles = side * (side + 1) / 2;
     hipLaunchKernelGGL(cohort_kr_kernel, dim3((uint32_t)std::min<uint64_t>({tiles, kKrBlocks, cap})), dim3(kBlock), 0, stream,
                        cohort->d_planes, cohort->d_half, cohort->d_total, S, N, padded, static_cast<double *>(d_out));
     HIP_TRY(hipGetLastError());
@@ -397,12 +414,18 @@ constexpr HostVariant kForwardHost{.chunk_reads = 1u << 18, .chunk_bytes = 64u <
 void free_cohort(epik_amd_cohort *cohort)
 {
     (void)hipFree(cohort->d_cells), (void)hipFree(cohort->d_prefix), (void)hipFree(cohort->d_total);
-    (void)hipFree(cohort->d_planes), (void)hipFree(cohort->d_half), (void)hipFree(cohort->d_squash);
+    (void)hipFree(cohort->d_planes), (void)hipFree(cohort->d_half), (void)hipFree(cohort->d_squash), (void)hipFree(cohort->d_epca);
 }
 
 }  // namespace
 
 namespace epik_amd {
+
+int cohort_normalise_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, hipStream_t stream, const uint32_t **d_first)
+{
+    if (const int rc = check_tree(cohort, tree, d_first); rc != EPIK_AMD_OK) return rc;
+    return normalise_launch(cohort, *d_first, stream);
+}
 
 int cohort_kr_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out, hipStream_t stream)
 {

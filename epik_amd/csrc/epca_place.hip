@@ -1,0 +1,582 @@
+// epca_place.hip -- edge principal components (Matsen & Evans 2013) of a cohort's samples on the device:
+// epik_amd_cohort_epca_device / _epca / _epca_host (include/epik_amd.h).
+//
+// No reference counterpart.  The rule is stated once, in include/epik_amd.h beside the KR and squash rules (DESIGN.md
+// 3.10; epik_amd/host/cohort.cpp: epca_components is the same rule on the CPU).  Every sum the rule orders is walked in
+// that order by one lane, and every rotation of a Jacobi round is formed from the matrix as it was when the round began,
+// so the results are the same bits here, on the host and in the tests' numpy.  Nothing is fused (__dmul_rn / __dadd_rn /
+// __dsub_rn / __ddiv_rn / __dsqrt_rn; the file is built with -ffp-contract=off as well).  No MFMA: the Gram matrix is a
+// product, but the order in which v_mfma_f64_* adds up its terms is not documented, and the rule fixes that order.
+//
+// Start-up: cohort_normalise_kernel (cohort_place.hip) leaves T_s and the planes C, B [b][Sp].
+//   epca_index_kernel    the used samples (T_s > 0) in ascending s: used[j], jof[s], and L -- which the host reads back:
+//                        the grids, the round-robin schedule and the choice of the eigensolver's path depend on it.
+//   epca_centre_kernel   a lane a branch: X_j[b], the sequential sum over j for the mean, Y into a plane [b][Lp], used
+//                        samples compacted, sample fastest, Lp a multiple of the tile, the padding zero.
+//   epca_gram_kernel     cohort_kr_kernel's tile with one plane and a product for |a - b|: 32 x 32 pairs on or above the
+//                        diagonal, 2 x 2 a lane, 32 branches staged in LDS a chunk, b ascending, mirrored on the way out.
+//   epca_scale_kernel    scale, trace and tol by one lane in the rule's order; V = I and the sweep counters zeroed.
+// The eigensolver, two paths that give the same bits (every element of a phase is one expression of the matrix before
+// that phase, whoever computes it):
+//   epca_jacobi_lds_kernel  L <= 64: one workgroup, A and V in LDS (2 * 32 KB), all rounds and sweeps in one launch.  A
+//                        phase computes its 16 elements a lane into registers, a barrier, the write-back, a barrier.
+//   epca_params_kernel / epca_column_kernel / epca_row_kernel  any L: three launches a round, grid-stride.  The
+//                        column kernel goes from A to a second matrix and turns V in place (a lane owns both columns
+//                        of a pair), the row kernel goes back to A: every (i, j) from (min, max) -- the mirror.  The
+//                        host reads the sweep's rotation counter, 4 bytes, once a sweep.
+// Then epca_order_kernel (the ranks by counting), epca_raw_kernel (a lane per (b, k), j ascending), epca_sign_kernel
+// (the (|value|, b) reduction, a workgroup a component) and epca_finish_kernel (edge, proj and the info block).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../host/cohort.hpp"
+#include "cohort_device.hpp"
+#include "host_entry.hpp"
+
+namespace {
+
+using namespace epik_amd;
+
+constexpr uint32_t kNone = 0xffffffffu;
+constexpr uint32_t kTile = kCohortTile;
+constexpr uint32_t kChunk = 32;                              // branches staged at a time: 2 * 32 * 32 * 8 = 16 KB of LDS
+constexpr uint32_t kMaxK = EPIK_AMD_EPCA_MAX_COMPONENTS;
+constexpr uint32_t kMaxSweeps = EPIK_AMD_EPCA_MAX_SWEEPS;
+constexpr uint32_t kLdsSide = 64;                            // the LDS path: A and V of up to 64 x 64 doubles
+constexpr uint32_t kLdsHeld = kLdsSide * kLdsSide / kBlock;  // elements of a matrix a lane holds across a barrier
+constexpr uint64_t kMaxBlocks = 1024;
+constexpr uint64_t kGramBlocks = 65536;
+
+static_assert(sizeof(epik_amd_epca_info) == 32);
+static_assert(kBlock == 256 && kTile == 32, "a lane owns 2 x 2 pairs of a 32 x 32 tile");
+static_assert(kLdsHeld * kBlock == kLdsSide * kLdsSide);
+
+// the workspace, one allocation: what the kernels take
+struct EpcaSpace {
+    double *Y;         // [N][Lp]
+    double *A, *A1;    // [L][L] each: the matrix, and the matrix after the column phase
+    double *V;         // [L][L]
+    double *cs, *sn;   // [L]: c_j, s_j of the round at hand
+    double *gs;        // scale, trace, tol
+    double *root, *sign;  // [kMaxK]: sqrt(mu_k), +-1
+    uint32_t *used, *jof, *partner;  // [S]: the sample of index j; the index of sample s or kNone; j' or kNone
+    uint32_t *count;                 // L
+    uint32_t *counters;              // [kMaxSweeps]: the rotations of a sweep (the global path)
+    uint32_t *status;                // sweeps, converged (the LDS path)
+    uint32_t *column, *null_k;       // [kMaxK]: j(k); whether component k is null
+};
+
+size_t epca_space(void *base, uint32_t S, uint32_t N, uint32_t padded, EpcaSpace *sp)
+{
+    size_t at = 0;
+    const auto take = [&](size_t bytes) {
+        const size_t offset = at;
+        at += (bytes + 15) / 16 * 16;
+        return offset;
+    };
+    const size_t dd = sizeof(double), uu = sizeof(uint32_t), SS = (size_t)S * S;
+    const size_t Y = take((size_t)N * padded * dd), A = take(SS * dd), A1 = take(SS * dd), V = take(SS * dd);
+    const size_t cs = take(S * dd), sn = take(S * dd), gs = take(4 * dd), root = take(kMaxK * dd), sign = take(kMaxK * dd);
+    const size_t used = take(S * uu), jof = take(S * uu), partner = take(S * uu), count = take(uu);
+    const size_t counters = take(kMaxSweeps * uu), status = take(2 * uu), column = take(kMaxK * uu), null_k = take(kMaxK * uu);
+    if (sp) {
+        char *b = static_cast<char *>(base);
+        const auto d = [&](size_t o) { return reinterpret_cast<double *>(b + o); };
+        const auto u = [&](size_t o) { return reinterpret_cast<uint32_t *>(b + o); };
+        *sp = EpcaSpace{d(Y), d(A), d(A1), d(V), d(cs), d(sn), d(gs), d(root), d(sign), u(used), u(jof), u(partner), u(count),
+                        u(counters), u(status), u(column), u(null_k)};
+    }
+    return at;
+}
+
+__global__ __launch_bounds__(kBlock) void epca_index_kernel(const uint64_t *__restrict__ total, uint32_t num_samples,
+                                                            uint32_t *__restrict__ used, uint32_t *__restrict__ jof,
+                                                            uint32_t *__restrict__ count)
+{
+    for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < num_samples; s += gridDim.x * kBlock) {
+        uint32_t j = 0;
+        for (uint32_t t = 0; t < s; ++t) j += total[t] != 0 ? 1u : 0u;
+        const bool mine = total[s] != 0;
+        jof[s] = mine ? j : kNone;
+        if (mine) used[j] = s;  // (j < the number of used samples <= num_samples)
+        if (s == num_samples - 1) *count = j + (mine ? 1u : 0u);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void epca_centre_kernel(const double *__restrict__ planes, const uint32_t *__restrict__ first,
+                                                             const uint32_t *__restrict__ used, uint32_t num_branches,
+                                                             uint32_t padded, uint32_t L, uint32_t Lp, double *__restrict__ Y)
+{
+    const double *C = planes, *B = planes + (uint64_t)num_branches * padded;
+    for (uint32_t b = blockIdx.x * kBlock + threadIdx.x; b < num_branches; b += gridDim.x * kBlock) {
+        const bool inner = first[b] < b;
+        double *y = Y + (uint64_t)b * Lp;
+        double acc = 0.0;
+        for (uint32_t j = 0; j < L; ++j) {  // ascending: the rule's order
+            const uint64_t at = (uint64_t)b * padded + used[j];
+            const double x = inner ? __dsub_rn(__dadd_rn(B[at], C[at]), 1.0) : 0.0;
+            y[j] = x;
+            acc = __dadd_rn(acc, x);
+        }
+        const double mean = __ddiv_rn(acc, (double)L);
+        for (uint32_t j = 0; j < L; ++j) y[j] = __dsub_rn(y[j], mean);
+        for (uint32_t j = L; j < Lp; ++j) y[j] = 0.0;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void epca_gram_kernel(const double *__restrict__ Y, uint32_t num_branches, uint32_t L,
+                                                           uint32_t Lp, double *__restrict__ G)
+{
+    __shared__ double y_row[kChunk][kTile], y_col[kChunk][kTile];
+    const uint32_t side = Lp / kTile, tx = threadIdx.x % 16, ty = threadIdx.x / 16;
+    const uint64_t tiles = (uint64_t)side * (side + 1) / 2;
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        // tile (ti, tj), ti <= tj, counted along the rows of the upper triangle
+        uint32_t ti = 0;
+        uint64_t rem = tile;
+        while (rem >= side - ti) rem -= side - ti, ++ti;
+        const uint32_t tj = ti + (uint32_t)rem;
+        double acc00 = 0.0, acc01 = 0.0, acc10 = 0.0, acc11 = 0.0;
+        for (uint32_t b0 = 0; b0 < num_branches; b0 += kChunk) {
+            const uint32_t kc = num_branches - b0 < kChunk ? num_branches - b0 : kChunk;
+            for (uint32_t e = threadIdx.x; e < kc * kTile; e += kBlock) {
+                const uint32_t k = e / kTile, x = e % kTile;
+                const uint64_t at = (uint64_t)(b0 + k) * Lp;
+                y_row[k][x] = Y[at + ti * kTile + x];
+                y_col[k][x] = Y[at + tj * kTile + x];
+            }
+            __syncthreads();
+            for (uint32_t k = 0; k < kc; ++k) {  // ascending, one branch after the other: the rule's order
+                const double r0 = y_row[k][ty], r1 = y_row[k][ty + 16], c0 = y_col[k][tx], c1 = y_col[k][tx + 16];
+                acc00 = __dadd_rn(acc00, __dmul_rn(r0, c0));
+                acc01 = __dadd_rn(acc01, __dmul_rn(r0, c1));
+                acc10 = __dadd_rn(acc10, __dmul_rn(r1, c0));
+                acc11 = __dadd_rn(acc11, __dmul_rn(r1, c1));
+            }
+            __syncthreads();
+        }
+        const double acc[2][2] = {{acc00, acc01}, {acc10, acc11}};
+#pragma unroll
+        for (uint32_t u = 0; u < 2; ++u)
+#pragma unroll
+            for (uint32_t v = 0; v < 2; ++v) {
+                const uint32_t r = ti * kTile + ty + 16 * u, c = tj * kTile + tx + 16 * v;
+                if (r >= L || c >= L || r > c) continue;  // (a diagonal tile: its upper half, mirrored)
+                G[(uint64_t)r * L + c] = acc[u][v];
+                G[(uint64_t)c * L + r] = acc[u][v];
+            }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void epca_scale_kernel(const double *__restrict__ G, uint32_t L, double *__restrict__ gs,
+                                                            double *__restrict__ V, uint32_t *__restrict__ counters)
+{
+    const uint64_t cells = (uint64_t)L * L;
+    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < cells; e += (uint64_t)gridDim.x * kBlock)
+        V[e] = e / L == e % L ? 1.0 : 0.0;
+    if (blockIdx.x == 0 && threadIdx.x < kMaxSweeps) counters[threadIdx.x] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        double scale = 0.0, trace = 0.0;
+        for (uint32_t j = 0; j < L; ++j) {  // ascending: the rule's order
+            const double g = G[(uint64_t)j * L + j];
+            if (g > scale) scale = g;
+            trace = __dadd_rn(trace, g);
+        }
+        gs[0] = scale, gs[1] = trace, gs[2] = __dmul_rn(0x1p-52, scale);
+    }
+}
+
+// pair i of round r of the round-robin schedule over m indices (m even), ordered
+__device__ inline void pair_of(uint32_t m, uint32_t r, uint32_t i, uint32_t &p, uint32_t &q)
+{
+    const uint32_t x = i ? (r + i) % (m - 1) : r, y = i ? (r + m - 1 - i) % (m - 1) : m - 1;
+    p = x < y ? x : y, q = x < y ? y : x;
+}
+
+// the rotation of a pair from A as it is at the start of the round; whether it rotates
+__device__ inline bool rotation_of(double app, double aqq, double apq, double tol, double &c, double &s)
+{
+    if (!(fabs(apq) > tol)) return false;
+    const double theta = __ddiv_rn(__dsub_rn(aqq, app), __dmul_rn(2.0, apq));
+    double t = __ddiv_rn(1.0, __dadd_rn(fabs(theta), __dsqrt_rn(__dadd_rn(__dmul_rn(theta, theta), 1.0))));
+    if (theta < 0.0) t = -t;
+    c = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dmul_rn(t, t), 1.0)));
+    s = __dmul_rn(t, c);
+    return true;
+}
+
+// c * a - s * b: two products, then one subtraction
+__device__ inline double turned(double c, double a, double s, double b) { return __dsub_rn(__dmul_rn(c, a), __dmul_rn(s, b)); }
+
+__global__ __launch_bounds__(kBlock) void epca_jacobi_lds_kernel(double *__restrict__ A_g, double *__restrict__ V_g, uint32_t L,
+                                                                 const double *__restrict__ gs, uint32_t *__restrict__ status)
+{
+    extern __shared__ double lds_matrices[];  // A[L][L] | V[L][L]
+    __shared__ double cs[kLdsSide], sn[kLdsSide];
+    __shared__ uint32_t partner[kLdsSide];
+    __shared__ uint32_t rotated;
+    const uint32_t cells = L * L, m = L + L % 2, tid = threadIdx.x;
+    double *A = lds_matrices, *V = lds_matrices + cells;
+    for (uint32_t e = tid; e < cells; e += kBlock) A[e] = A_g[e], V[e] = e / L == e % L ? 1.0 : 0.0;
+    if (tid == 0) rotated = 0;
+    const double tol = gs[2];
+    __syncthreads();
+    uint32_t sweeps = 0, converged = 0;
+    while (sweeps < kMaxSweeps && !converged) {  // (uniform: every lane reads the same counter)
+        ++sweeps;
+        for (uint32_t r = 0; r + 1 < m; ++r) {
+            if (tid < m / 2) {  // every index below L is in exactly one pair of the round: partner[] is written whole
+                uint32_t p, q;
+                pair_of(m, r, tid, p, q);
+                if (q >= L) {
+                    partner[p] = kNone;
+                } else {
+                    double c = 1.0, s = 0.0;
+                    const bool turn = rotation_of(A[p * L + p], A[q * L + q], A[p * L + q], tol, c, s);
+                    partner[p] = turn ? q : kNone, partner[q] = turn ? p : kNone;
+                    cs[p] = c, cs[q] = c, sn[p] = s, sn[q] = -s;
+                    if (turn) atomicAdd(&rotated, 1u);
+                }
+            }
+            __syncthreads();
+            double a[kLdsHeld], v[kLdsHeld];
+#pragma unroll
+            for (uint32_t k = 0; k < kLdsHeld; ++k) {  // the column phase, into registers
+                const uint32_t e = tid + k * kBlock;
+                if (e >= cells) continue;
+                const uint32_t i = e / L, j = e - i * L, jp = partner[j];
+                a[k] = jp != kNone ? turned(cs[j], A[e], sn[j], A[i * L + jp]) : A[e];
+                v[k] = jp != kNone ? turned(cs[j], V[e], sn[j], V[i * L + jp]) : V[e];
+            }
+            __syncthreads();
+#pragma unroll
+            for (uint32_t k = 0; k < kLdsHeld; ++k) {
+                const uint32_t e = tid + k * kBlock;
+                if (e < cells) A[e] = a[k], V[e] = v[k];
+            }
+            __syncthreads();
+#pragma unroll
+            for (uint32_t k = 0; k < kLdsHeld; ++k) {  // the row phase on (min, max): the mirror
+                const uint32_t e = tid + k * kBlock;
+                if (e >= cells) continue;
+                const uint32_t i = e / L, j = e - i * L, lo = i < j ? i : j, hi = i < j ? j : i, lp = partner[lo];
+                a[k] = lp == kNone ? A[lo * L + hi] : lp == hi ? 0.0 : turned(cs[lo], A[lo * L + hi], sn[lo], A[lp * L + hi]);
+            }
+            __syncthreads();
+#pragma unroll
+            for (uint32_t k = 0; k < kLdsHeld; ++k) {
+                const uint32_t e = tid + k * kBlock;
+                if (e < cells) A[e] = a[k];
+            }
+            __syncthreads();  // (and partner[] may be written again)
+        }
+        converged = rotated == 0 ? 1u : 0u;
+        __syncthreads();
+        if (tid == 0) rotated = 0;
+        __syncthreads();
+    }
+    for (uint32_t e = tid; e < cells; e += kBlock) A_g[e] = A[e], V_g[e] = V[e];
+    if (tid == 0) status[0] = sweeps, status[1] = converged;
+}
+
+__global__ __launch_bounds__(kBlock) void epca_params_kernel(const double *__restrict__ A, uint32_t L, uint32_t m, uint32_t r,
+                                                             const double *__restrict__ gs, double *__restrict__ cs,
+                                                             double *__restrict__ sn, uint32_t *__restrict__ partner,
+                                                             uint32_t *__restrict__ counter)
+{
+    const double tol = gs[2];
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < m / 2; i += gridDim.x * kBlock) {
+        uint32_t p, q;
+        pair_of(m, r, i, p, q);
+        if (q >= L) {
+            partner[p] = kNone;
+            continue;
+        }
+        double c = 1.0, s = 0.0;
+        const bool turn = rotation_of(A[(uint64_t)p * L + p], A[(uint64_t)q * L + q], A[(uint64_t)p * L + q], tol, c, s);
+        partner[p] = turn ? q : kNone, partner[q] = turn ? p : kNone;
+        cs[p] = c, cs[q] = c, sn[p] = s, sn[q] = -s;
+        if (turn) atomicAdd(counter, 1u);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void epca_column_kernel(const double *__restrict__ A, double *__restrict__ A1,
+                                                             double *__restrict__ V, uint32_t L, const double *__restrict__ cs,
+                                                             const double *__restrict__ sn, const uint32_t *__restrict__ partner)
+{
+    const uint64_t cells = (uint64_t)L * L;
+    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < cells; e += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t i = (uint32_t)(e / L), j = (uint32_t)(e - (uint64_t)i * L), jp = partner[j];
+        if (jp == kNone) {
+            A1[e] = A[e];
+            continue;
+        }
+        const uint64_t other = (uint64_t)i * L + jp;
+        A1[e] = turned(cs[j], A[e], sn[j], A[other]);
+        if (j < jp) {  // V in place: this lane owns both columns of the pair in row i
+            const double vj = V[e], vp = V[other];
+            V[e] = turned(cs[j], vj, sn[j], vp);
+            V[other] = turned(cs[jp], vp, sn[jp], vj);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void epca_row_kernel(const double *__restrict__ A1, double *__restrict__ A, uint32_t L,
+                                                          const double *__restrict__ cs, const double *__restrict__ sn,
+                                                          const uint32_t *__restrict__ partner)
+{
+    const uint64_t cells = (uint64_t)L * L;
+    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < cells; e += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t i = (uint32_t)(e / L), j = (uint32_t)(e - (uint64_t)i * L);
+        const uint32_t lo = i < j ? i : j, hi = i < j ? j : i, lp = partner[lo];
+        const uint64_t at = (uint64_t)lo * L + hi;
+        A[e] = lp == kNone ? A1[at] : lp == hi ? 0.0 : turned(cs[lo], A1[at], sn[lo], A1[(uint64_t)lp * L + hi]);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void epca_order_kernel(const double *__restrict__ A, uint32_t L, uint32_t K, uint32_t Kc,
+                                                            const double *__restrict__ gs, uint32_t *__restrict__ column,
+                                                            uint32_t *__restrict__ null_k, double *__restrict__ root,
+                                                            double *__restrict__ mu)
+{
+    const double floor_mu = __dmul_rn(0x1p-40, gs[0]);
+    for (uint32_t j = threadIdx.x; j < L; j += kBlock) {
+        const double mine = A[(uint64_t)j * L + j];
+        uint32_t rank = 0;
+        for (uint32_t i = 0; i < L; ++i) {
+            const double other = A[(uint64_t)i * L + i];
+            rank += other > mine || (other == mine && i < j) ? 1u : 0u;
+        }
+        if (rank < Kc) {  // (the ranks are a permutation: every k < Kc is written once)
+            const bool is_null = !(mine > floor_mu);
+            column[rank] = j, null_k[rank] = is_null ? 1u : 0u, mu[rank] = mine;
+            root[rank] = is_null ? 0.0 : __dsqrt_rn(mine);
+        }
+    }
+    for (uint32_t k = Kc + threadIdx.x; k < K; k += kBlock) mu[k] = 0.0;
+}
+
+__global__ __launch_bounds__(kBlock) void epca_raw_kernel(const double *__restrict__ V, const double *__restrict__ Y, uint32_t L,
+                                                          uint32_t Lp, uint32_t num_branches, uint32_t K, uint32_t Kc,
+                                                          const uint32_t *__restrict__ column, const uint32_t *__restrict__ null_k,
+                                                          double *__restrict__ edge)
+{
+    const uint64_t cells = (uint64_t)K * num_branches;
+    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < cells; e += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t b = (uint32_t)(e / K), k = (uint32_t)(e - (uint64_t)b * K);  // k fastest: a wave shares its rows of Y
+        double acc = 0.0;
+        if (k < Kc && !null_k[k]) {
+            const double *v = V + column[k], *y = Y + (uint64_t)b * Lp;
+            for (uint32_t j = 0; j < L; ++j) acc = __dadd_rn(acc, __dmul_rn(v[(uint64_t)j * L], y[j]));  // ascending: the rule's order
+        }
+        edge[(uint64_t)k * num_branches + b] = acc;
+    }
+}
+
+// whether (|v|, b) comes before (|best_v|, best_b): the larger magnitude, then the smaller branch
+__device__ inline bool larger_first(double v, uint32_t b, double best_v, uint32_t best_b)
+{
+    return b != kNone && (best_b == kNone || fabs(v) > fabs(best_v) || (fabs(v) == fabs(best_v) && b < best_b));
+}
+
+__global__ __launch_bounds__(kBlock) void epca_sign_kernel(const double *__restrict__ edge, uint32_t num_branches, uint32_t Kc,
+                                                           double *__restrict__ sign)
+{
+    __shared__ double wave_val[kBlockWaves];
+    __shared__ uint32_t wave_at[kBlockWaves];
+    for (uint32_t k = blockIdx.x; k < Kc; k += gridDim.x) {
+        const double *raw = edge + (uint64_t)k * num_branches;
+        double val = 0.0;
+        uint32_t at = kNone;
+        for (uint32_t b = threadIdx.x; b < num_branches; b += kBlock) {  // (ascending in a lane: strict > keeps the first)
+            const double v = raw[b];
+            if (at == kNone || fabs(v) > fabs(val)) val = v, at = b;
+        }
+#pragma unroll
+        for (int d = kWave / 2; d > 0; d >>= 1) {
+            const double ov = __shfl_down(val, d);
+            const uint32_t oa = __shfl_down(at, d);
+            if (larger_first(ov, oa, val, at)) val = ov, at = oa;
+        }
+        if (threadIdx.x % kWave == 0) wave_val[threadIdx.x / kWave] = val, wave_at[threadIdx.x / kWave] = at;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (uint32_t w = 1; w < kBlockWaves; ++w)
+                if (larger_first(wave_val[w], wave_at[w], val, at)) val = wave_val[w], at = wave_at[w];
+            sign[k] = val < 0.0 ? -1.0 : 1.0;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void epca_finish_kernel(double *__restrict__ edge, double *__restrict__ proj,
+                                                             const double *__restrict__ V, const uint32_t *__restrict__ jof,
+                                                             const uint32_t *__restrict__ column, const uint32_t *__restrict__ null_k,
+                                                             const double *__restrict__ root, const double *__restrict__ sign,
+                                                             uint32_t num_samples, uint32_t num_branches, uint32_t K, uint32_t Kc,
+                                                             uint32_t L, const double *__restrict__ gs, const uint32_t *status,
+                                                             uint32_t sweeps, uint32_t converged, epik_amd_epca_info *__restrict__ info)
+{
+    const uint64_t edges = (uint64_t)K * num_branches, projs = (uint64_t)num_samples * K;
+    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < edges + projs; e += (uint64_t)gridDim.x * kBlock) {
+        if (e < edges) {
+            const uint32_t k = (uint32_t)(e / num_branches);
+            edge[e] = k < Kc && !null_k[k] ? __dmul_rn(sign[k], __ddiv_rn(edge[e], root[k])) : 0.0;
+        } else {
+            const uint64_t at = e - edges;
+            const uint32_t s = (uint32_t)(at / K), k = (uint32_t)(at - (uint64_t)s * K), j = jof[s];
+            proj[at] = k < Kc && !null_k[k] && j != kNone ? __dmul_rn(sign[k], __dmul_rn(V[(uint64_t)j * L + column[k]], root[k])) : 0.0;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        *info = epik_amd_epca_info{L, Kc, status ? status[0] : sweeps, status ? status[1] : converged, gs[1], gs[0]};
+}
+
+int epca_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_t K, void *d_mu, void *d_proj, void *d_edge,
+                     void *d_info, hipStream_t stream)
+{
+    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    if (K < 1 || K > kMaxK)
+        return fail_with(EPIK_AMD_ERR_INVALID, "num_components = " + std::to_string(K) + " is outside [1, 64]");
+    if (!d_mu || !d_proj || !d_edge || !d_info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    // the checks of the tree, the planes' workspace, T_s and the planes
+    const uint32_t *d_first = nullptr;
+    if (const int rc = cohort_normalise_enqueue(cohort, tree, stream, &d_first); rc != EPIK_AMD_OK) return rc;
+    const uint32_t N = cohort->num_branches, S = cohort->num_samples, padded = cohort_padded_samples(cohort);
+    if (!cohort->d_epca) HIP_TRY(hipMalloc(&cohort->d_epca, epca_space(nullptr, S, N, padded, nullptr)));
+    EpcaSpace sp;
+    epca_space(cohort->d_epca, S, N, padded, &sp);
+    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
+    const auto blocks = [&](uint64_t units, uint64_t per, uint64_t most) {
+        return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(units + per - 1) / per, most, cap})));
+    };
+    hipLaunchKernelGGL(epca_index_kernel, blocks(S, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, cohort->d_total, S, sp.used, sp.jof,
+                       sp.count);
+    HIP_TRY(hipGetLastError());
+    uint32_t L = 0;
+    HIP_TRY(hipMemcpyAsync(&L, sp.count, sizeof L, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (L > S) return fail_with(EPIK_AMD_ERR_HIP, "cohort_epca: the device counted more used samples than there are samples");
+    const uint32_t Lp = (L + kTile - 1) / kTile * kTile, Kc = std::min(K, L), m = L + L % 2;
+    const uint64_t cells = (uint64_t)L * L;
+    if (L) {
+        hipLaunchKernelGGL(epca_centre_kernel, blocks(N, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, cohort->d_planes, d_first,
+                           sp.used, N, padded, L, Lp, sp.Y);
+        const uint64_t side = Lp / kTile;
+        hipLaunchKernelGGL(epca_gram_kernel, blocks(side * (side + 1) / 2, 1, kGramBlocks), dim3(kBlock), 0, stream, sp.Y, N, L, Lp,
+                           sp.A);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(epca_scale_kernel, blocks(cells, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, sp.A, L, sp.gs, sp.V, sp.counters);
+    HIP_TRY(hipGetLastError());
+    // EPIK_AMD_EPCA_LDS=0 (tests), read at the call: the global path whatever L
+    const char *env = std::getenv("EPIK_AMD_EPCA_LDS");
+    const bool lds = L <= kLdsSide && !(env && std::strcmp(env, "0") == 0);
+    uint32_t sweeps = 1, converged = 1;  // (L = 0: one empty sweep)
+    if (L && lds) {
+        const size_t lds_bytes = 2 * (size_t)cells * sizeof(double);
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&epca_jacobi_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(2 * kLdsSide * kLdsSide * sizeof(double))));
+        hipLaunchKernelGGL(epca_jacobi_lds_kernel, dim3(1), dim3(kBlock), lds_bytes, stream, sp.A, sp.V, L, sp.gs, sp.status);
+        HIP_TRY(hipGetLastError());
+    } else if (L) {
+        const dim3 pair_grid = blocks(m / 2, kBlock, kMaxBlocks), cell_grid = blocks(cells, kBlock, kMaxBlocks);
+        sweeps = 0, converged = 0;
+        while (sweeps < kMaxSweeps && !converged) {
+            for (uint32_t r = 0; r + 1 < m; ++r) {
+                hipLaunchKernelGGL(epca_params_kernel, pair_grid, dim3(kBlock), 0, stream, sp.A, L, m, r, sp.gs, sp.cs, sp.sn,
+                                   sp.partner, sp.counters + sweeps);
+                hipLaunchKernelGGL(epca_column_kernel, cell_grid, dim3(kBlock), 0, stream, sp.A, sp.A1, sp.V, L, sp.cs, sp.sn,
+                                   sp.partner);
+                hipLaunchKernelGGL(epca_row_kernel, cell_grid, dim3(kBlock), 0, stream, sp.A1, sp.A, L, sp.cs, sp.sn, sp.partner);
+            }
+            HIP_TRY(hipGetLastError());
+            uint32_t rotated = 0;  // the one readback of a sweep
+            HIP_TRY(hipMemcpyAsync(&rotated, sp.counters + sweeps, sizeof rotated, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            ++sweeps;
+            converged = rotated == 0 ? 1u : 0u;
+        }
+    }
+    auto *mu = static_cast<double *>(d_mu), *proj = static_cast<double *>(d_proj), *edge = static_cast<double *>(d_edge);
+    hipLaunchKernelGGL(epca_order_kernel, dim3(1), dim3(kBlock), 0, stream, sp.A, L, K, Kc, sp.gs, sp.column, sp.null_k, sp.root, mu);
+    hipLaunchKernelGGL(epca_raw_kernel, blocks((uint64_t)K * N, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, sp.V, sp.Y, L, Lp, N, K,
+                       Kc, sp.column, sp.null_k, edge);
+    hipLaunchKernelGGL(epca_sign_kernel, blocks(std::max(Kc, 1u), 1, kMaxBlocks), dim3(kBlock), 0, stream, edge, N, Kc, sp.sign);
+    hipLaunchKernelGGL(epca_finish_kernel, blocks((uint64_t)K * N + (uint64_t)S * K, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, edge,
+                       proj, sp.V, sp.jof, sp.column, sp.null_k, sp.root, sp.sign, S, N, K, Kc, L, sp.gs,
+                       L && lds ? sp.status : nullptr, sweeps, converged, static_cast<epik_amd_epca_info *>(d_info));
+    HIP_TRY(hipGetLastError());
+    return EPIK_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int epik_amd_cohort_epca_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_t num_components, void *d_mu,
+                                void *d_proj, void *d_edge, void *d_info, void *stream)
+{
+    try {
+        return epca_device_impl(cohort, tree, num_components, d_mu, d_proj, d_edge, d_info, static_cast<hipStream_t>(stream));
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_epca_device: ") + e.what());
+    }
+}
+
+int epik_amd_cohort_epca(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_t num_components, double *mu, double *proj,
+                         double *edge, epik_amd_epca_info *info)
+{
+    try {
+        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+        const size_t K = num_components, S = cohort->num_samples, N = cohort->num_branches;
+        if (K < 1 || K > kMaxK)
+            return fail_with(EPIK_AMD_ERR_INVALID, "num_components = " + std::to_string(K) + " is outside [1, 64]");
+        if (!mu || !proj || !edge || !info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+        HIP_TRY(hipSetDevice(cohort->device));
+        struct Results {
+            void *d = nullptr;
+            ~Results()
+            {
+                if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
+            }
+        } m;
+        const size_t doubles = K + S * K + K * N;  // mu | proj | edge, then the info block
+        HIP_TRY(hipMalloc(&m.d, doubles * sizeof(double) + sizeof(epik_amd_epca_info)));
+        double *d = static_cast<double *>(m.d);
+        if (const int rc = epca_device_impl(cohort, tree, num_components, d, d + K, d + K + S * K, d + doubles, nullptr); rc != EPIK_AMD_OK)
+            return rc;
+        HIP_TRY(hipMemcpy(mu, d, K * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(proj, d + K, S * K * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(edge, d + K + S * K, K * N * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(info, d + doubles, sizeof *info, hipMemcpyDeviceToHost));
+        return EPIK_AMD_OK;
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_epca: ") + e.what());
+    }
+}
+
+int epik_amd_cohort_epca_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                              uint32_t num_components, double *mu, double *proj, double *edge, epik_amd_epca_info *info)
+{
+    try {
+        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
+        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
+        if (!mass || !first || !mu || !proj || !edge || !info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+        std::string err;
+        if (const int rc = epca_components(mass, num_samples, num_branches, first, num_components, mu, proj, edge, info, err);
+            rc != EPIK_AMD_OK)
+            return fail_with(rc, err);
+        return EPIK_AMD_OK;
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_epca_host: ") + e.what());
+    }
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
 #include "cohort.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <fstream>
@@ -76,7 +77,8 @@ void sample_cohort::merge(const sample_cohort& other)
 namespace {
 
 // what both the distance matrix and the clustering start from: first[] and the lengths checked, half[b] = 0.5 * bl[b],
-// T_s, and C[s][b], B[s][b] -- one conversion each and one division; T_s == 0 leaves the row unused
+// T_s, and C[s][b], B[s][b] -- one conversion each and one division; T_s == 0 leaves the row unused.  Edge PCA takes no
+// lengths: branch_length may be null, and half stays zero
 struct kr_planes {
     std::vector<double> C, B, half;
     std::vector<uint64_t> total;
@@ -90,14 +92,14 @@ int make_planes(const uint64_t* mass, size_t S, size_t N, const uint32_t* first,
             err = "branch " + std::to_string(b) + ": first[b] = " + std::to_string(first[b]) + " is above the branch";
             return EPIK_AMD_ERR_INVALID;
         }
-        if (!(branch_length[b] >= 0.0) || !std::isfinite(branch_length[b])) {
+        if (branch_length && (!(branch_length[b] >= 0.0) || !std::isfinite(branch_length[b]))) {
             err = "branch " + std::to_string(b) + ": the branch length is negative or not finite";
             return EPIK_AMD_ERR_INVALID;
         }
     }
     p.C.assign(S * N, 0.0), p.B.assign(S * N, 0.0), p.half.assign(N, 0.0), p.total.assign(S, 0);
     std::vector<uint64_t> prefix(N + 1);
-    for (size_t b = 0; b < N; ++b) p.half[b] = 0.5 * branch_length[b];
+    for (size_t b = 0; branch_length && b < N; ++b) p.half[b] = 0.5 * branch_length[b];
     for (size_t s = 0; s < S; ++s) {
         const uint64_t* m = mass + s * N;
         prefix[0] = 0;
@@ -181,6 +183,124 @@ int squash_merges(const uint64_t* mass, uint32_t num_samples, uint32_t num_branc
     }
     *num_merges = t;
     for (size_t k = t; k + 1 < S; ++k) merges[k] = epik_amd_squash_merge{EPIK_AMD_SQUASH_NONE, EPIK_AMD_SQUASH_NONE, 0.0, 0.0, 0.0};
+    return EPIK_AMD_OK;
+}
+
+int epca_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                    uint32_t num_components, double* mu, double* proj, double* edge, epik_amd_epca_info* info, std::string& err)
+{
+    const size_t S = num_samples, N = num_branches, K = num_components;
+    if (K < 1 || K > EPIK_AMD_EPCA_MAX_COMPONENTS) {
+        err = "num_components = " + std::to_string(K) + " is outside [1, 64]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    kr_planes p;
+    if (const int rc = make_planes(mass, S, N, first, nullptr, p, err); rc != EPIK_AMD_OK) return rc;
+    std::vector<size_t> used;
+    for (size_t s = 0; s < S; ++s)
+        if (p.total[s] != 0) used.push_back(s);
+    const size_t L = used.size(), Kc = std::min(K, L);
+    // the centred imbalances Y[j][b]
+    std::vector<double> Y(L * N, 0.0);
+    for (size_t b = 0; b < N; ++b) {
+        const bool inner = first[b] < b;
+        double acc = 0.0;
+        for (size_t j = 0; j < L; ++j) {
+            const double x = inner ? (p.B[used[j] * N + b] + p.C[used[j] * N + b]) - 1.0 : 0.0;
+            Y[j * N + b] = x;
+            acc = acc + x;
+        }
+        const double mean = L ? acc / (double)L : 0.0;
+        for (size_t j = 0; j < L; ++j) Y[j * N + b] = Y[j * N + b] - mean;
+    }
+    // the Gram matrix, its scale and trace
+    std::vector<double> A(L * L, 0.0), V(L * L, 0.0), A1(L * L), V1(L * L);
+    for (size_t i = 0; i < L; ++i)
+        for (size_t j = i; j < L; ++j) {
+            const double *yi = &Y[i * N], *yj = &Y[j * N];
+            double acc = 0.0;
+            for (size_t b = 0; b < N; ++b) acc = acc + yi[b] * yj[b];
+            A[i * L + j] = A[j * L + i] = acc;
+        }
+    double scale = 0.0, trace = 0.0;
+    for (size_t j = 0; j < L; ++j) {
+        if (A[j * L + j] > scale) scale = A[j * L + j];
+        trace = trace + A[j * L + j];
+        V[j * L + j] = 1.0;
+    }
+    const double tol = std::ldexp(1.0, -52) * scale;
+    // cyclic Jacobi, round-robin, the rotations of a round applied together
+    const size_t m = L + L % 2;
+    std::vector<double> cs(L), sn(L);
+    std::vector<size_t> partner(L);
+    std::vector<char> rot(L);
+    uint32_t sweeps = 0, converged = 0;
+    while (sweeps < EPIK_AMD_EPCA_MAX_SWEEPS && !converged) {
+        ++sweeps;
+        size_t rotated = 0;
+        for (size_t r = 0; r + 1 < m; ++r) {
+            std::fill(rot.begin(), rot.end(), 0);
+            size_t in_round = 0;
+            for (size_t i = 0; i < m / 2; ++i) {
+                const size_t x = i ? (r + i) % (m - 1) : r, y = i ? (r + m - 1 - i) % (m - 1) : m - 1;
+                const size_t pp = std::min(x, y), q = std::max(x, y);
+                if (q >= L) continue;
+                const double apq = A[pp * L + q];
+                if (!(std::fabs(apq) > tol)) continue;
+                const double theta = (A[q * L + q] - A[pp * L + pp]) / (2.0 * apq);
+                double t = 1.0 / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                if (theta < 0.0) t = -t;
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                rot[pp] = rot[q] = 1, cs[pp] = cs[q] = c, sn[pp] = s, sn[q] = -s, partner[pp] = q, partner[q] = pp;
+                ++in_round;
+            }
+            if (!in_round) continue;
+            rotated += in_round;
+            for (size_t i = 0; i < L; ++i)  // the column phase, on the full matrix
+                for (size_t j = 0; j < L; ++j) {
+                    const bool turn = rot[j];
+                    A1[i * L + j] = turn ? cs[j] * A[i * L + j] - sn[j] * A[i * L + partner[j]] : A[i * L + j];
+                    V1[i * L + j] = turn ? cs[j] * V[i * L + j] - sn[j] * V[i * L + partner[j]] : V[i * L + j];
+                }
+            V.swap(V1);
+            for (size_t i = 0; i < L; ++i)  // the row phase on i <= j, mirrored
+                for (size_t j = i; j < L; ++j) {
+                    const double v = rot[i] ? cs[i] * A1[i * L + j] - sn[i] * A1[partner[i] * L + j] : A1[i * L + j];
+                    A[i * L + j] = A[j * L + i] = v;
+                }
+            for (size_t j = 0; j < L; ++j)
+                if (rot[j]) A[j * L + partner[j]] = 0.0;
+        }
+        converged = rotated == 0;
+    }
+    // the components: by (mu descending, j ascending)
+    std::vector<size_t> column(Kc);
+    for (size_t j = 0; j < L; ++j) {
+        size_t rank = 0;
+        for (size_t i = 0; i < L; ++i)
+            rank += A[i * L + i] > A[j * L + j] || (A[i * L + i] == A[j * L + j] && i < j) ? 1 : 0;
+        if (rank < Kc) column[rank] = j;
+    }
+    std::fill(mu, mu + K, 0.0), std::fill(proj, proj + S * K, 0.0), std::fill(edge, edge + K * N, 0.0);
+    const double floor_mu = std::ldexp(1.0, -40) * scale;
+    std::vector<double> raw(N);
+    for (size_t k = 0; k < Kc; ++k) {
+        const size_t jk = column[k];
+        mu[k] = A[jk * L + jk];
+        if (!(mu[k] > floor_mu)) continue;
+        const double r = std::sqrt(mu[k]);
+        size_t at = 0;
+        for (size_t b = 0; b < N; ++b) {
+            double acc = 0.0;
+            for (size_t j = 0; j < L; ++j) acc = acc + V[j * L + jk] * Y[j * N + b];
+            raw[b] = acc;
+            if (std::fabs(acc) > std::fabs(raw[at])) at = b;
+        }
+        const double sign = raw[at] < 0.0 ? -1.0 : 1.0;
+        for (size_t b = 0; b < N; ++b) edge[k * N + b] = sign * (raw[b] / r);
+        for (size_t j = 0; j < L; ++j) proj[used[j] * K + k] = sign * (V[j * L + jk] * r);
+    }
+    *info = epik_amd_epca_info{(uint32_t)L, (uint32_t)Kc, sweeps, converged, trace, scale};
     return EPIK_AMD_OK;
 }
 
@@ -327,6 +447,46 @@ std::string format_squash_newick(const std::vector<cohort_sample>& samples, cons
     for (size_t s = 0; s < S; ++s)
         if (live[s]) return text[s] + ";\n";
     return ";\n";
+}
+
+std::string format_epca_tsv(const std::vector<cohort_sample>& samples, const std::vector<char>& used, uint32_t num_components,
+                            const double* mu, const double* proj, const epik_amd_epca_info& info)
+{
+    const size_t S = samples.size(), K = num_components, Kc = info.components;
+    std::string out = "# epik_amd epca v1  samples=" + std::to_string(S) + " used=" + std::to_string(info.used) +
+                      " components=" + std::to_string(Kc) + " sweeps=" + std::to_string(info.sweeps) +
+                      " converged=" + std::to_string(info.converged) + "\n";
+    for (size_t s = 0; s < S; ++s)
+        if (!used[s]) out += "# unused\t" + samples[s].name + "\n";
+    const double floor_mu = std::ldexp(1.0, -40) * info.scale, denominator = (double)std::max<uint32_t>(info.used, 2) - 1.0;
+    for (size_t k = 0; k < Kc; ++k)
+        out += "# component\t" + std::to_string(k + 1) + '\t' + g17(mu[k]) + '\t' + g17(mu[k] / denominator) + '\t' +
+               g17(info.trace != 0.0 ? mu[k] / info.trace : 0.0) + '\t' + (mu[k] > floor_mu ? "ok" : "null") + '\n';
+    out += "name";
+    for (size_t k = 0; k < Kc; ++k) out += "\tpc" + std::to_string(k + 1);
+    out += '\n';
+    for (size_t s = 0; s < S; ++s) {
+        if (!used[s]) continue;
+        out += samples[s].name;
+        for (size_t k = 0; k < Kc; ++k) out += '\t' + g17(proj[s * K + k]);
+        out += '\n';
+    }
+    return out;
+}
+
+std::string format_epca_edges_tsv(const std::vector<uint32_t>& first, const double* edge, const epik_amd_epca_info& info)
+{
+    const size_t N = first.size(), Kc = info.components;
+    std::string out = "edge_num";
+    for (size_t k = 0; k < Kc; ++k) out += "\tpc" + std::to_string(k + 1);
+    out += '\n';
+    for (size_t b = 0; b < N; ++b) {
+        if (!(first[b] < b)) continue;
+        out += std::to_string(b);
+        for (size_t k = 0; k < Kc; ++k) out += '\t' + g17(edge[k * N + b]);
+        out += '\n';
+    }
+    return out;
 }
 
 void write_through_part(const std::string& filename, const std::string& text)

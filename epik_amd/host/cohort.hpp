@@ -49,6 +49,12 @@ int kr_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches,
 int squash_merges(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                   const double* branch_length, epik_amd_squash_merge* merges, uint32_t* num_merges, std::string& err);
 
+/// Edge principal components by the rule (include/epik_amd.h): mu[K], proj[S][K], edge[K][N] and *info, every cell
+/// written.  The code behind epik_amd_cohort_epca_host; libepik_amd's kernels (epca_place.hip) give the same bits.  0, or
+/// EPIK_AMD_ERR_INVALID with `err` naming K outside [1, 64] or the branch whose first[] is above it.
+int epca_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                    uint32_t num_components, double* mu, double* proj, double* edge, epik_amd_epca_info* info, std::string& err);
+
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
 /// name or path, a name given before, or a file that cannot be read; and for a list without any sample.
@@ -57,7 +63,7 @@ struct cohort_sample {
 };
 std::vector<cohort_sample> read_cohort_list(const std::string& list_file);
 
-/// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash
+/// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash | epca | epca_edges
 std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir,
                                  const std::string& extension = ".tsv");
 
@@ -77,6 +83,14 @@ std::string format_squash_tsv(const std::vector<cohort_sample>& samples, const s
                               const epik_amd_squash_merge* merges, uint32_t num_merges);
 std::string format_squash_newick(const std::vector<cohort_sample>& samples, const std::vector<char>& live,
                                  const epik_amd_squash_merge* merges, uint32_t num_merges);
+/// cohort_epca .tsv: "# epik_amd epca v1  samples=S used=L components=K' sweeps=n converged=0|1", a "# unused<TAB>name"
+/// line per sample without mass (used[s] == 0), a "# component<TAB>k<TAB>mu<TAB>lambda<TAB>fraction<TAB>null|ok" line per
+/// component (k from 1, lambda = mu / max(L - 1, 1), fraction = mu / trace or 0), the column names name pc1 .. pcK', then
+/// per used sample in list order its name and proj[s][0 .. K'), the rows of proj K = num_components wide; doubles %.17g.
+/// cohort_epca_edges .tsv: edge_num pc1 .. pcK', a line per inner branch (first[b] < b) in id order from edge[K][N].
+std::string format_epca_tsv(const std::vector<cohort_sample>& samples, const std::vector<char>& used, uint32_t num_components,
+                            const double* mu, const double* proj, const epik_amd_epca_info& info);
+std::string format_epca_edges_tsv(const std::vector<uint32_t>& first, const double* edge, const epik_amd_epca_info& info);
 /// `text` into `filename` through `filename`.part, renamed when all of it is written
 void write_through_part(const std::string& filename, const std::string& text);
 

@@ -5,6 +5,8 @@
 //   cohort_test kr <out.bin> <in.bin>       the KR matrix, float64 [S][S]
 //   cohort_test squash <out.bin> <in.bin>   the squash clustering of a `kr` input: epik_amd_squash_merge [S - 1], then
 //                                           uint32 num_merges
+//   cohort_test epca <out.bin> <in.bin> <K> the edge principal components of a `kr` input (its lengths are not used):
+//                                           float64 mu[K], proj[S][K], edge[K][N], then epik_amd_epca_info
 // An `add` input holds, little endian: uint64 n, keep, num_branches, num_samples; epik_amd_placement rows[n][keep];
 // uint32 n_rows[n]; uint32 kmer_counts[n][keep]; uint32 weights[n]; uint32 samples[n].
 // A `kr` input: uint64 num_samples, num_branches; uint64 mass[S][N]; uint32 first[N]; float64 branch_length[N].
@@ -104,7 +106,32 @@ int main(int argc, char** argv)
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }
-        std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin> | squash <out.bin> <in.bin>\n";
+        if (argc == 5 && std::strcmp(argv[1], "epca") == 0) {
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto mass = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const unsigned long K = std::stoul(argv[4]);
+            if (K < 1 || K > EPIK_AMD_EPCA_MAX_COMPONENTS) throw std::runtime_error("num_components = " + std::to_string(K) + " is outside [1, 64]");
+            std::vector<double> mu(K), proj(S * K), edge(K * N);
+            epik_amd_epca_info info{};
+            std::string err;
+            if (epik_amd::epca_components(mass.data(), (uint32_t)S, (uint32_t)N, first.data(), (uint32_t)K, mu.data(), proj.data(),
+                                          edge.data(), &info, err) != 0)
+                throw std::runtime_error(err);
+            std::ofstream out(argv[2], std::ios::binary);
+            write_array(out, mu.data(), mu.size());
+            write_array(out, proj.data(), proj.size());
+            write_array(out, edge.data(), edge.size());
+            write_array(out, &info, 1);
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
+        std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin> | squash <out.bin> <in.bin> | "
+                     "epca <out.bin> <in.bin> <K>\n";
         return 2;
     } catch (const std::exception& error) {
         std::cerr << "Error: " << error.what() << std::endl;

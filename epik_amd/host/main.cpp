@@ -223,6 +223,10 @@ const char* kHelp =
     "      --cohort-squash     With --cohort: also cluster the samples by squash clustering (Matsen & Evans 2013) on the\n"
     "                          device, every merged cluster the weighted average of its parts' masses, and write\n"
     "                          cohort_squash_<list>.tsv (a line per merge) and cohort_squash_<list>.nwk (the cluster tree)\n"
+    "      --cohort-epca       With --cohort: also compute the edge principal components of the samples (Matsen & Evans 2013)\n"
+    "                          on the device and write cohort_epca_<list>.tsv (the components and every sample's\n"
+    "                          projections) and cohort_epca_edges_<list>.tsv (the components' coefficients per inner branch)\n"
+    "      --cohort-epca-components arg  With --cohort-epca: the number of components, in [1, 64] (default: 5)\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -263,7 +267,7 @@ options parse_args(int argc, char** argv)
         } else {
             continue;  // positional arguments are ignored (epik.py passes the query twice, epik.py:88,96)
         }
-        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash") && !have_value)) {  // flags
+        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca") && !have_value)) {  // flags
             opt.values[name] = "1";
             continue;
         }
@@ -364,6 +368,25 @@ int main(int argc, char** argv)
         // --cohort: checked before anything is opened or any device touched
         const bool with_cohort = parsed.has("cohort"), with_squash = parsed.has("cohort-squash");
         if (with_squash && !with_cohort) throw std::runtime_error("--cohort-squash needs --cohort (it clusters the samples of the list)");
+        const bool with_epca = parsed.has("cohort-epca");
+        if (with_epca && !with_cohort)
+            throw std::runtime_error("--cohort-epca needs --cohort (it takes the principal components of the samples of the list)");
+        if (parsed.has("cohort-epca-components") && !with_epca)
+            throw std::runtime_error("--cohort-epca-components needs --cohort-epca (the flag that computes the components)");
+        uint32_t epca_components = 5;
+        if (with_epca) {
+            const auto text = parsed.get("cohort-epca-components", "5");
+            size_t used = 0;
+            unsigned long k = 0;
+            try {
+                k = std::stoul(text, &used);
+            } catch (const std::exception&) {
+                used = 0;
+            }
+            if (used != text.size() || used == 0 || text[0] == '-' || k < 1 || k > EPIK_AMD_EPCA_MAX_COMPONENTS)
+                throw std::runtime_error("--cohort-epca-components must be a whole number in [1, 64], not '" + text + "'");
+            epca_components = (uint32_t)k;
+        }
         if (with_cohort) {
             for (const char* other : {"mates", "profile-only", "profile", "assign"})
                 if (parsed.has(other)) throw std::runtime_error(std::string("--cohort does not work with --") + other);
@@ -715,24 +738,36 @@ int main(int argc, char** argv)
         const auto cohort_kr_filename = epik_amd::make_cohort_filename("kr", query_file, output_dir);
         const auto cohort_squash_filename = epik_amd::make_cohort_filename("squash", query_file, output_dir);
         const auto cohort_squash_tree_filename = epik_amd::make_cohort_filename("squash", query_file, output_dir, ".nwk");
+        const auto cohort_epca_filename = epik_amd::make_cohort_filename("epca", query_file, output_dir);
+        const auto cohort_epca_edges_filename = epik_amd::make_cohort_filename("epca_edges", query_file, output_dir);
+        bool epca_converged = true;
         if (with_cohort) {
             // the handles' cohorts summed on the first device, read once, and the distances computed there
             epik_amd::sample_cohort cohort((uint32_t)cohort_samples.size(), (uint32_t)tree.get_node_count());
             std::vector<double> kr(cohort_samples.size() * cohort_samples.size());
             std::vector<epik_amd_squash_merge> merges(with_squash ? cohort_samples.size() - 1 : 0);
             uint32_t num_merges = 0;
+            epik_amd::placer::cohort_epca epca;
+            epca.num_components = epca_components;
             placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
-                               with_squash ? &num_merges : nullptr);
+                               with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr);
             epik_amd::write_through_part(cohort_samples_filename, epik_amd::format_cohort_samples_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_profile_filename, epik_amd::format_cohort_profile_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_kr_filename, epik_amd::format_cohort_kr_tsv(cohort_samples, kr));
+            std::vector<char> live(cohort_samples.size());  // (T_s > 0, the sum wrapping as the rule's)
+            for (size_t s = 0; s < live.size(); ++s) {
+                uint64_t total = 0;
+                for (size_t b = 0; b < cohort.num_branches; ++b) total += cohort.mass[s * cohort.num_branches + b];
+                live[s] = total != 0;
+            }
+            if (with_epca) {
+                epik_amd::write_through_part(cohort_epca_filename, epik_amd::format_epca_tsv(cohort_samples, live, epca.num_components,
+                                                                                             epca.mu.data(), epca.proj.data(), epca.info));
+                epik_amd::write_through_part(cohort_epca_edges_filename,
+                                             epik_amd::format_epca_edges_tsv(epca.first, epca.edge.data(), epca.info));
+                epca_converged = epca.info.converged != 0;
+            }
             if (with_squash) {
-                std::vector<char> live(cohort_samples.size());  // (T_s > 0, the sum wrapping as the rule's)
-                for (size_t s = 0; s < live.size(); ++s) {
-                    uint64_t total = 0;
-                    for (size_t b = 0; b < cohort.num_branches; ++b) total += cohort.mass[s * cohort.num_branches + b];
-                    live[s] = total != 0;
-                }
                 epik_amd::write_through_part(cohort_squash_filename,
                                              epik_amd::format_squash_tsv(cohort_samples, live, merges.data(), num_merges));
                 epik_amd::write_through_part(cohort_squash_tree_filename,
@@ -765,6 +800,12 @@ int main(int argc, char** argv)
         if (with_squash)
             std::cout << "Cohort clustering: " << cohort_squash_filename << "\nCohort cluster tree: " << cohort_squash_tree_filename
                       << std::endl;
+        if (with_epca)
+            std::cout << "Cohort principal components: " << cohort_epca_filename << "\nCohort component edges: " << cohort_epca_edges_filename
+                      << std::endl;
+        if (!epca_converged)
+            std::cout << "Warning: the edge principal components did not converge in " << EPIK_AMD_EPCA_MAX_SWEEPS
+                      << " sweeps (converged=0 in " << cohort_epca_filename << ")" << std::endl;
         if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;
         if (strands_out.is_open()) {
             strands_out.close();

@@ -32,6 +32,7 @@
 #pragma weak epik_amd_cohort_add_cells
 #pragma weak epik_amd_cohort_kr
 #pragma weak epik_amd_cohort_squash
+#pragma weak epik_amd_cohort_epca
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -236,9 +237,10 @@ void placer::set_cohort(uint32_t num_samples)
 }
 
 void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
-                         epik_amd_squash_merge* merges, uint32_t* num_merges)
+                         epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca)
 {
     if (num_merges && !&epik_amd_cohort_squash) throw std::runtime_error("GPU placer: this libepik_amd has no squash clustering");
+    if (epca && !&epik_amd_cohort_epca) throw std::runtime_error("GPU placer: this libepik_amd has no edge principal components");
     const auto check = [](int rc) {
         if (rc != EPIK_AMD_OK) throw std::runtime_error(std::string("GPU placer: ") + epik_amd_last_error());
     };
@@ -264,6 +266,17 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
     check(epik_amd_tree_create(_devices[0], parent.data(), length.data(), (uint32_t)parent.size(), &tree));
     int rc = epik_amd_cohort_kr(_cohorts[0], tree, length.data(), kr);
     if (rc == EPIK_AMD_OK && num_merges) rc = epik_amd_cohort_squash(_cohorts[0], tree, length.data(), merges, num_merges);
+    if (rc == EPIK_AMD_OK && epca) {
+        const size_t N = parent.size(), K = epca->num_components;
+        epca->mu.assign(K, 0.0), epca->proj.assign((size_t)_cohort_samples * K, 0.0), epca->edge.assign(K * N, 0.0);
+        epca->first.resize(N);
+        for (size_t b = 0; b < N; ++b) epca->first[b] = (uint32_t)b;  // (post-order ids: a parent comes after its children)
+        for (size_t b = 0; b < N; ++b)
+            if (parent[b] != EPIK_AMD_TREE_NO_PARENT && parent[b] < N)
+                epca->first[parent[b]] = std::min(epca->first[parent[b]], epca->first[b]);
+        rc = epik_amd_cohort_epca(_cohorts[0], tree, epca->num_components, epca->mu.data(), epca->proj.data(), epca->edge.data(),
+                                  &epca->info);
+    }
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);
     if (rc != EPIK_AMD_OK) throw std::runtime_error("GPU placer: " + message);

@@ -165,9 +165,17 @@ public:
     /// The cohorts of all handles summed into the first one's (epik_amd_cohort_add_cells), read back -- `mass` and `best`
     /// of num_samples * num_branches cells each, `totals` of num_samples --, and the KR distance between every two
     /// samples computed on that device: `kr` of num_samples * num_samples values.  Once, at the end.  With `num_merges`
-    /// (--cohort-squash) the squash clustering of the samples too, there: `merges` of num_samples - 1 records.
+    /// (--cohort-squash) the squash clustering of the samples too, there: `merges` of num_samples - 1 records.  With
+    /// `epca` (--cohort-epca) their edge principal components too: `epca->num_components` is K on entry; mu of K, proj
+    /// of num_samples * K, edge of K * num_branches values, the info block and the tree's first[] on return.
+    struct cohort_epca {
+        uint32_t num_components = 0;
+        std::vector<double> mu, proj, edge;
+        epik_amd_epca_info info{};
+        std::vector<uint32_t> first;
+    };
     void read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
-                     epik_amd_squash_merge* merges = nullptr, uint32_t* num_merges = nullptr);
+                     epik_amd_squash_merge* merges = nullptr, uint32_t* num_merges = nullptr, cohort_epca* epca = nullptr);
     /// The profiles of all devices read back and summed; `mass` and `best` of num_branches cells each.
     void read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_totals& totals) const;
     /// distal_length / pendant_length of a placement on branch b (place.cpp:110-123, 435-437)

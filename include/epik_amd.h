@@ -697,6 +697,43 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *     stays strictly sequential per pair: an implementation may share out the clusters x, the branches of the
  *     AVERAGING and the scan, never the branches of one distance.
  *
+ * Edge principal components (Matsen & Evans 2013) of the cohort's samples.  From mass[S][N], first[N] and K in [1, 64];
+ *   no branch lengths.  All arithmetic is IEEE double, every operation rounded on its own, nothing fused.
+ *   Used samples.  T_s, C_s[b], B_s[b] are exactly those of the KR rule.  Sample s is used iff T_s > 0; the used
+ *     samples, in ascending s, get the indices j = 0 .. L - 1.  L may be 0.
+ *   Imbalance.  Branch b is inner iff first[b] < b.  For an inner b, X_j[b] = (B_s[b] + C_s[b]) - 1.0: the mass strictly
+ *     distal of b minus the mass strictly proximal of it, the branch's own mass on neither side (as guppy and gappa
+ *     count it).  For every other b, X_j[b] = +0.0.
+ *   Centring.  mean[b] = (acc after j = 0 .. L - 1 in this order, acc = acc + X_j[b], acc = +0.0 at first) / (double)L,
+ *     Y_j[b] = X_j[b] - mean[b].
+ *   Gram matrix.  For i <= j, G[i][j] = acc after b = 0 .. N - 1 in THIS order, acc = acc + (Y_i[b] * Y_j[b]),
+ *     acc = +0.0 at first; G[j][i] = G[i][j].  The sum over b is strictly sequential per pair: an implementation may
+ *     share out the pairs, never the branches of one pair.  scale = max over j of G[j][j] (+0.0 for L = 0); trace = the
+ *     sequential sum of G[j][j], j ascending, from +0.0; tol = 2^-52 * scale.
+ *   Eigen-decomposition: cyclic Jacobi in round-robin order, the rotations of a round applied together.  A = G, V = I,
+ *     m = L + (L mod 2).  A sweep is the rounds r = 0 .. m - 2; round r holds the pairs {r, m - 1} and, for
+ *     i = 1 .. m/2 - 1, {(r + i) mod (m - 1), (r - i + m - 1) mod (m - 1)}, each ordered (p, q) with p < q.  A pair with
+ *     q >= L (the phantom index of an odd L) does nothing.  For every other pair, from A as it is at the START of the
+ *     round: apq = A[p][q]; the pair rotates iff |apq| > tol, and then
+ *       theta = (A[q][q] - A[p][p]) / (2.0 * apq),   t = 1.0 / (|theta| + sqrt(theta * theta + 1.0)), negated iff theta < 0,
+ *       c = 1.0 / sqrt(t * t + 1.0),   s = t * c;
+ *     index p gets (c_p, s_p, p') = (c, s, q), index q gets (c_q, s_q, q') = (c, -s, p).  Then three phases, in order:
+ *       column phase, on the full matrix: for every i and every rotating j, A1[i][j] = c_j * A[i][j] - s_j * A[i][j'],
+ *         two products then one subtraction; other elements are unchanged.  V1[i][j] likewise from V.
+ *       row phase: for i <= j with i rotating, A2[i][j] = c_i * A1[i][j] - s_i * A1[i'][j]; otherwise
+ *         A2[i][j] = A1[i][j].  Then A2[j][i] = A2[i][j].
+ *       for every rotated pair A2[p][q] = A2[q][p] = +0.0.
+ *     Sweeps run until a whole sweep rotates no pair: converged = 1, and `sweeps` counts that last sweep too.  After 64
+ *     sweeps at the latest: converged = 0, and the results are taken from A and V as they stand.  L <= 1: one empty sweep.
+ *   Components.  mu_j = A[j][j], ordered by (mu descending, j ascending); K' = min(K, L); component k is null iff
+ *     !(mu_k > 2^-40 * scale).  For a non-null k, with j(k) the column of V it came from: r = sqrt(mu_k);
+ *     raw[b] = the sum over j = 0 .. L - 1 in this order of V[j][j(k)] * Y_j[b], from +0.0; b* = the first b with the
+ *     largest |raw[b]|, sign = -1 iff raw[b*] < 0, else +1;
+ *       edge[k][b] = sign * (raw[b] / r),      proj[s][k] = sign * (V[j(s)][j(k)] * r).
+ *     Both are +0.0 for a null k, for k >= K' and for an unused s.  mu[k] is written as computed for k < K', +0.0 beyond.
+ *   The files derive, one division each: lambda_k = mu_k / (double)max(L - 1, 1); fraction_k = mu_k / trace, 0 when
+ *     trace is 0.
+ *
  * An epik_amd_cohort is an object of its own, created for a placer's device, num_branches and keep_at_most (whole
  * databases only, not a k-mer-space shard) and num_samples >= 1; all zero at create() and after reset().
  *   add_device  asynchronous on `stream`, allocates nothing: as epik_amd_profile_add_device, with d_samples (uint32 [n],
@@ -715,6 +752,14 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *               record written.  S = 1 is valid: zero merges (d_merges may be NULL then).  The cells are not changed.
  *               squash: the same into host memory, synchronous.
  *   squash_host the rule on the host, as kr_host.
+ *   epca_device checks the tree as kr_device (no lengths) and K in [1, 64]; the first call allocates a workspace of its
+ *               own, kept until destroy(): about 24 * S^2 + 8 * N * Sp bytes (three S x S matrices and the centred
+ *               plane; Sp = S rounded up to 32), sized by S whatever the number of used samples.  d_mu float64 [K], d_proj float64 [S][K], d_edge float64 [K][N] and d_info one epik_amd_epca_info, all
+ *               in device memory, every cell written.  It synchronises `stream` once for the number of used samples
+ *               and, beyond 64 of them (the eigensolver's global path; EPIK_AMD_EPCA_LDS=0, read at the call, forces it),
+ *               once per sweep for the sweep's rotation counter; the results are enqueued on `stream`.  The cells are
+ *               not changed.   epca: the same into host memory, synchronous.
+ *   epca_host   the rule on the host from mass[S][N] and first[N], no device; first[b] > b is refused.
  * cohort_reads / _strands / _frames / _mates: the profile_* twins with samples[n] (HOST uint32) beside the weights.
  */
 typedef struct epik_amd_cohort epik_amd_cohort;
@@ -745,6 +790,19 @@ int epik_amd_cohort_squash(epik_amd_cohort *cohort, const epik_amd_tree *tree, c
                            epik_amd_squash_merge *merges, uint32_t *num_merges);
 int epik_amd_cohort_squash_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                 const double *branch_length, epik_amd_squash_merge *merges, uint32_t *num_merges);
+typedef struct epik_amd_epca_info {
+    uint32_t used, components; /* L, and K' = min(K, L) */
+    uint32_t sweeps, converged;
+    double trace, scale;
+} epik_amd_epca_info; /* 32 bytes */
+#define EPIK_AMD_EPCA_MAX_COMPONENTS 64u
+#define EPIK_AMD_EPCA_MAX_SWEEPS 64u
+int epik_amd_cohort_epca_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_t num_components, void *d_mu,
+                                void *d_proj, void *d_edge, void *d_info, void *stream);
+int epik_amd_cohort_epca(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_t num_components, double *mu,
+                         double *proj, double *edge, epik_amd_epca_info *info);
+int epik_amd_cohort_epca_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                              uint32_t num_components, double *mu, double *proj, double *edge, epik_amd_epca_info *info);
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n);
 int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
