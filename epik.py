@@ -17,6 +17,8 @@ the Kantorovich-Rubinstein distance between every two of them, cohort_samples_ /
 --cohort-squash, with --cohort: the squash clustering of the samples, cohort_squash_<list>.tsv and .nwk.
 --cohort-epca, with --cohort: the edge principal components of the samples, cohort_epca_<list>.tsv and
 cohort_epca_edges_<list>.tsv; --cohort-epca-components K of them (default 5).
+--cohort-kmeans K, with --cohort: the phylogenetic k-means of the samples into at most K clusters, cohort_kmeans_<list>.tsv
+and cohort_kmeans_centroids_<list>.tsv; --cohort-kmeans-iterations M at the most (default 100).
 """
 from __future__ import annotations
 
@@ -88,6 +90,13 @@ PLACE_OPTIONS = [
                                                  "coefficients per inner branch).")),
     (("--cohort-epca-components",), dict(type=click.IntRange(1, 64), default=None,
                                          help="With --cohort-epca: the number of components, in [1, 64] [default: 5].")),
+    (("--cohort-kmeans",), dict(type=click.IntRange(1, 64), default=None,
+                                help="With --cohort: also cluster the samples into at most this many clusters, in [1, 64], by "
+                                     "phylogenetic k-means on the device and write cohort_kmeans_<list>.tsv (the clusters and "
+                                     "every sample's cluster and distance) and cohort_kmeans_centroids_<list>.tsv (the "
+                                     "centroids' masses).")),
+    (("--cohort-kmeans-iterations",), dict(type=click.IntRange(1, 1000), default=None,
+                                           help="With --cohort-kmeans: the most iterations, in [1, 1000] [default: 100].")),
 ]
 
 
@@ -104,7 +113,7 @@ def driver_path(states: str) -> str:
 def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpus, input_file, db_shard=1,
                    strand="forward", translate=None, profile=False, profile_only=False, mates=None,
                    mate_orientation="fr", assign=False, assign_mass=None, cohort=False, cohort_squash=False,
-                   cohort_epca=False, cohort_epca_components=None):
+                   cohort_epca=False, cohort_epca_components=None, cohort_kmeans=None, cohort_kmeans_iterations=None):
     if assign_mass is not None and not assign:
         raise click.UsageError("--assign-mass needs --assign")
     if assign and db_shard != 1:
@@ -115,6 +124,10 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         raise click.UsageError("--cohort-epca needs --cohort")
     if cohort_epca_components is not None and not cohort_epca:
         raise click.UsageError("--cohort-epca-components needs --cohort-epca")
+    if cohort_kmeans is not None and not cohort:
+        raise click.UsageError("--cohort-kmeans needs --cohort")
+    if cohort_kmeans_iterations is not None and cohort_kmeans is None:
+        raise click.UsageError("--cohort-kmeans-iterations needs --cohort-kmeans")
     if cohort:
         for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
                             ("--assign", assign), ("--db-shard > 1", db_shard != 1)):
@@ -152,6 +165,10 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--cohort-epca"]
         if cohort_epca_components is not None:
             argv += ["--cohort-epca-components", str(int(cohort_epca_components))]
+    if cohort_kmeans is not None:
+        argv += ["--cohort-kmeans", str(int(cohort_kmeans))]
+        if cohort_kmeans_iterations is not None:
+            argv += ["--cohort-kmeans-iterations", str(int(cohort_kmeans_iterations))]
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 

@@ -31,6 +31,13 @@ EPCA_INFO = np.dtype([("used", np.uint32), ("components", np.uint32), ("sweeps",
                       ("trace", np.float64), ("scale", np.float64)])
 EPCA_MAX_COMPONENTS = 64
 EPCA_MAX_SWEEPS = 64
+#: epik_amd_kmeans_info (16 bytes), epik_amd_kmeans_sample (16 bytes), epik_amd_kmeans_cluster (24 bytes)
+KMEANS_INFO = np.dtype([("used", np.uint32), ("clusters", np.uint32), ("iterations", np.uint32), ("converged", np.uint32)])
+KMEANS_SAMPLE = np.dtype([("cluster", np.uint32), ("zero", np.uint32), ("dist", np.float64)])
+KMEANS_CLUSTER = np.dtype([("size", np.uint32), ("seed", np.uint32), ("sum_dist", np.float64), ("sum_sq", np.float64)])
+KMEANS_MAX_CLUSTERS = 64
+KMEANS_MAX_ITERATIONS = 1000
+KMEANS_NONE = 0xFFFFFFFF
 #: numpy mirror of `epik_amd_pkdb_value` / `i2l::pkdb_value` (8 bytes)
 PKDB_VALUE = np.dtype([("branch", np.uint32), ("score", np.float32)])
 
@@ -111,6 +118,9 @@ EXPORTS = (
     "epik_amd_cohort_epca_device",
     "epik_amd_cohort_epca",
     "epik_amd_cohort_epca_host",
+    "epik_amd_cohort_kmeans_device",
+    "epik_amd_cohort_kmeans",
+    "epik_amd_cohort_kmeans_host",
     "epik_amd_placer_cohort_reads",
     "epik_amd_placer_cohort_strands",
     "epik_amd_placer_cohort_frames",
@@ -427,6 +437,12 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_epca.argtypes = [vp, vp, u32, vp, vp, vp, vp]
     lib.epik_amd_cohort_epca_host.restype = i32
     lib.epik_amd_cohort_epca_host.argtypes = [vp, u32, u32, vp, u32, vp, vp, vp, vp]
+    lib.epik_amd_cohort_kmeans_device.restype = i32
+    lib.epik_amd_cohort_kmeans_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp]
+    lib.epik_amd_cohort_kmeans.restype = i32
+    lib.epik_amd_cohort_kmeans.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp]
+    lib.epik_amd_cohort_kmeans_host.restype = i32
+    lib.epik_amd_cohort_kmeans_host.argtypes = [vp, u32, u32, vp, vp, u32, u32, vp, vp, vp, vp]
     lib.epik_amd_placer_cohort_reads.restype = i32
     lib.epik_amd_placer_cohort_reads.argtypes = [vp, vp, vp, vp, vp, vp, u64]
     for name in ("epik_amd_placer_cohort_strands", "epik_amd_placer_cohort_frames", "epik_amd_placer_cohort_mates"):

@@ -14,6 +14,10 @@ Squash clustering of the samples (the header's second rule): `Cohort.squash` / `
 Edge principal components of the samples (the header's third rule): `Cohort.epca` / `epca_device` on the device,
 `epca_host` on the host, each giving an `Epca`; `format_epca_tsv`, `format_epca_edges_tsv` and their readers are the two
 files of --cohort-epca.
+
+Phylogenetic k-means of the samples (the header's fourth rule): `Cohort.kmeans` / `kmeans_device` on the device,
+`kmeans_host` on the host, each giving a `Kmeans`; `format_kmeans_tsv`, `format_kmeans_centroids_tsv` and their readers are
+the two files of --cohort-kmeans.
 """
 from __future__ import annotations
 
@@ -140,6 +144,49 @@ def epca_host(mass, first, num_components: int = 5) -> Epca:
     out = _epca_buffers(s, n, k)
     capi.check(lib.epik_amd_cohort_epca_host(mass.ctypes.data, s, n, first.ctypes.data, k, out.mu.ctypes.data,
                                              out.proj.ctypes.data, out.edge.ctypes.data, out.info.ctypes.data))
+    out.info = out.info[0]
+    return out
+
+
+@dataclass
+class Kmeans:
+    """Phylogenetic k-means as the rule leaves it: `samples` `capi.KMEANS_SAMPLE` [S], `clusters` `capi.KMEANS_CLUSTER`
+    [K], `centroids` float64 [K][N] and `info`, one `capi.KMEANS_INFO` record (used, clusters, iterations, converged)."""
+
+    samples: np.ndarray
+    clusters: np.ndarray
+    centroids: np.ndarray
+    info: np.ndarray
+
+    @property
+    def num_clusters(self) -> int:
+        return int(self.info["clusters"])
+
+
+def _count32(value, what) -> int:
+    v = int(value)
+    if not 0 <= v <= 0xFFFFFFFF:
+        raise ValueError(f"{what} must fit 32 bits")
+    return v
+
+
+def _kmeans_buffers(s, n, k):
+    k = min(max(k, 1), 0x10000)            # (a refused K still needs somewhere to point)
+    return Kmeans(np.full(s, 0xAB, dtype=np.uint8).repeat(16).view(capi.KMEANS_SAMPLE),
+                  np.full(k, 0xAB, dtype=np.uint8).repeat(24).view(capi.KMEANS_CLUSTER), np.full((k, n), np.nan),
+                  np.zeros(1, dtype=capi.KMEANS_INFO))
+
+
+def kmeans_host(mass, first, branch_length, num_clusters: int, max_iterations: int = 100) -> Kmeans:
+    """The phylogenetic k-means of the rule for mass[S][N] on the host (`epik_amd_cohort_kmeans_host`)."""
+    lib = capi.load()
+    mass, first, length = _cells_and_tree(mass, first, branch_length)
+    s, n = mass.shape
+    k, m = _count32(num_clusters, "num_clusters"), _count32(max_iterations, "max_iterations")
+    out = _kmeans_buffers(s, n, k)
+    capi.check(lib.epik_amd_cohort_kmeans_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, k, m,
+                                               out.samples.ctypes.data, out.clusters.ctypes.data, out.centroids.ctypes.data,
+                                               out.info.ctypes.data))
     out.info = out.info[0]
     return out
 
@@ -295,6 +342,27 @@ class Cohort:
         out = _epca_buffers(self.num_samples, self.num_branches, k)
         capi.check(self._lib.epik_amd_cohort_epca(self._handle, tree._handle, k, out.mu.ctypes.data, out.proj.ctypes.data,
                                                   out.edge.ctypes.data, out.info.ctypes.data))
+        out.info = out.info[0]
+        return out
+
+    def kmeans_device(self, tree, branch_length, num_clusters: int, max_iterations: int, d_samples: int, d_clusters: int,
+                      d_centroids: int, d_info: int, stream: int = 0) -> None:
+        """The phylogenetic k-means into device memory: d_samples `capi.KMEANS_SAMPLE` [S], d_clusters
+        `capi.KMEANS_CLUSTER` [K], d_centroids float64 [K][N], d_info one `capi.KMEANS_INFO`, every cell written.
+        Synchronises `stream` once per iteration (`epik_amd_cohort_kmeans_device`)."""
+        length = self._lengths(tree, branch_length)
+        capi.check(self._lib.epik_amd_cohort_kmeans_device(self._handle, tree._handle, length.ctypes.data,
+                                                           _count32(num_clusters, "num_clusters"),
+                                                           _count32(max_iterations, "max_iterations"), d_samples or None,
+                                                           d_clusters or None, d_centroids or None, d_info or None, stream or None))
+
+    def kmeans(self, tree, branch_length, num_clusters: int, max_iterations: int = 100) -> Kmeans:
+        """The phylogenetic k-means of the samples, a `Kmeans` (`epik_amd_cohort_kmeans`)."""
+        length = self._lengths(tree, branch_length)
+        k, m = _count32(num_clusters, "num_clusters"), _count32(max_iterations, "max_iterations")
+        out = _kmeans_buffers(self.num_samples, self.num_branches, k)
+        capi.check(self._lib.epik_amd_cohort_kmeans(self._handle, tree._handle, length.ctypes.data, k, m, out.samples.ctypes.data,
+                                                    out.clusters.ctypes.data, out.centroids.ctypes.data, out.info.ctypes.data))
         out.info = out.info[0]
         return out
 
@@ -479,6 +547,88 @@ def read_epca_edges_tsv(path: str):
     kc = len(head) - 1
     return (np.array([int(r[0]) for r in rows], dtype=np.int64),
             np.array([[float(x) for x in r[1:]] for r in rows], dtype=np.float64).reshape(len(rows), kc))
+
+
+# ---- the files of --cohort-kmeans --------------------------------------------------------------------------------------
+def format_kmeans_tsv(names, kmeans: Kmeans) -> str:
+    """cohort_kmeans_<list>.tsv: the first line, a `# unused` line per sample without mass, a `# cluster` line per cluster
+    k < K' (k, size, the seed's name, sum_dist, sum_sq), the column names, then per used sample, in list order, its name,
+    cluster and dist; doubles as %.17g."""
+    info, samples = kmeans.info, kmeans.samples
+    if len(samples) != len(names):
+        raise ValueError("one record per sample")
+    used = samples["cluster"] != capi.KMEANS_NONE
+    if int(used.sum()) != int(info["used"]):
+        raise ValueError("the records do not fit the number of used samples")
+    lines = [f"# epik_amd kmeans v1  samples={len(names)} used={int(info['used'])} clusters={int(info['clusters'])} "
+             f"iterations={int(info['iterations'])} converged={int(info['converged'])}"]
+    lines += [f"# unused\t{name}" for name, u in zip(names, used) if not u]
+    for k in range(int(info["clusters"])):
+        c = kmeans.clusters[k]
+        lines.append("# cluster\t%d\t%d\t%s\t%.17g\t%.17g" % (k, int(c["size"]), names[int(c["seed"])], float(c["sum_dist"]),
+                                                              float(c["sum_sq"])))
+    lines.append("name\tcluster\tdist")
+    for i, name in enumerate(names):
+        if used[i]:
+            lines.append("%s\t%d\t%.17g" % (name, int(samples["cluster"][i]), float(samples["dist"][i])))
+    return "\n".join(lines) + "\n"
+
+
+def format_kmeans_centroids_tsv(kmeans: Kmeans) -> str:
+    """cohort_kmeans_centroids_<list>.tsv: cluster, edge_num and mass for every non-zero cell of the centroids of the
+    clusters k < K'; doubles as %.17g."""
+    lines = ["cluster\tedge_num\tmass"]
+    for k in range(int(kmeans.info["clusters"])):
+        row = kmeans.centroids[k]
+        lines += ["%d\t%d\t%.17g" % (k, int(b), float(row[b])) for b in np.flatnonzero(row != 0)]
+    return "\n".join(lines) + "\n"
+
+
+def read_kmeans_tsv(path: str):
+    """(names, cluster int64 [L], dist float64 [L], info): the used samples in list order, and {"samples", "used",
+    "clusters", "iterations", "converged", "unused": names, "size": int64 [K'], "seed": names, "sum_dist", "sum_sq":
+    float64 [K']}."""
+    with open(path, newline="") as fh:
+        head = re.fullmatch(r"# epik_amd kmeans v1  samples=(\d+) used=(\d+) clusters=(\d+) iterations=(\d+) converged=([01])",
+                            fh.readline().rstrip("\n"))
+        if not head:
+            raise ValueError(f"{path}: not a cohort kmeans file")
+        info = dict(zip(("samples", "used", "clusters", "iterations", "converged"), (int(x) for x in head.groups())))
+        info["unused"] = []
+        clusters = []
+        line = fh.readline().rstrip("\n")
+        while line.startswith("# "):
+            kind, rest = line[2:].split("\t", 1)
+            if kind == "unused":
+                info["unused"].append(rest)
+            elif kind == "cluster":
+                clusters.append(rest.split("\t"))
+            else:
+                raise ValueError(f"{path}: not a cohort kmeans file")
+            line = fh.readline().rstrip("\n")
+        if line != "name\tcluster\tdist" or [int(c[0]) for c in clusters] != list(range(info["clusters"])):
+            raise ValueError(f"{path}: the clusters do not follow the first line's count")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    if len(rows) != info["used"] or any(len(r) != 3 for r in rows) or any(len(c) != 5 for c in clusters):
+        raise ValueError(f"{path}: the rows do not follow the first line's counts")
+    info["size"] = np.array([int(c[1]) for c in clusters], dtype=np.int64)
+    info["seed"] = [c[2] for c in clusters]
+    info["sum_dist"] = np.array([float(c[3]) for c in clusters], dtype=np.float64)
+    info["sum_sq"] = np.array([float(c[4]) for c in clusters], dtype=np.float64)
+    return ([r[0] for r in rows], np.array([int(r[1]) for r in rows], dtype=np.int64),
+            np.array([float(r[2]) for r in rows], dtype=np.float64), info)
+
+
+def read_kmeans_centroids_tsv(path: str, num_clusters: int, num_branches: int) -> np.ndarray:
+    """The centroids, float64 [num_clusters][num_branches], zero where the file has no line."""
+    out = np.zeros((num_clusters, num_branches), dtype=np.float64)
+    with open(path, newline="") as fh:
+        if fh.readline().rstrip("\n") != "cluster\tedge_num\tmass":
+            raise ValueError(f"{path}: not a cohort kmeans centroids file")
+        for ln in fh:
+            k, b, v = ln.rstrip("\n").split("\t")
+            out[int(k), int(b)] = float(v)
+    return out
 
 
 def read_samples_tsv(path: str):

@@ -1,4 +1,4 @@
-// cohort_device.hpp -- what cohort_place.hip, squash_place.hip and epca_place.hip share of a device cohort: the object
+// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip and kmeans_place.hip share of a device cohort: the object
 // itself and the launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering and the
 // edge principal components start from.
 #ifndef EPIK_AMD_COHORT_DEVICE_HPP
@@ -26,6 +26,8 @@ struct epik_amd_cohort {
     void *d_squash = nullptr;
     // the workspace of the edge principal components, allocated by the first epca_device (epca_place.hip):
     void *d_epca = nullptr;
+    // the workspace of the phylogenetic k-means, allocated by the first kmeans_device (kmeans_place.hip):
+    void *d_kmeans = nullptr;
 };
 
 namespace epik_amd {

@@ -304,6 +304,113 @@ int epca_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_bra
     return EPIK_AMD_OK;
 }
 
+int kmeans_clusters(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                    const double* branch_length, uint32_t num_clusters, uint32_t max_iterations, epik_amd_kmeans_sample* samples,
+                    epik_amd_kmeans_cluster* clusters, double* centroids, epik_amd_kmeans_info* info, std::string& err)
+{
+    const size_t S = num_samples, N = num_branches, K = num_clusters;
+    if (K < 1 || K > EPIK_AMD_KMEANS_MAX_CLUSTERS) {
+        err = "num_clusters = " + std::to_string(K) + " is outside [1, 64]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if (max_iterations < 1 || max_iterations > EPIK_AMD_KMEANS_MAX_ITERATIONS) {
+        err = "max_iterations = " + std::to_string(max_iterations) + " is outside [1, 1000]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    kr_planes p;
+    if (const int rc = make_planes(mass, S, N, first, branch_length, p, err); rc != EPIK_AMD_OK) return rc;
+    std::vector<size_t> used;
+    for (size_t s = 0; s < S; ++s)
+        if (p.total[s] != 0) used.push_back(s);
+    const size_t L = used.size(), Kc = std::min(K, L);
+    const double* half = p.half.data();
+    for (size_t s = 0; s < S; ++s) samples[s] = epik_amd_kmeans_sample{EPIK_AMD_KMEANS_NONE, 0u, -1.0};
+    for (size_t k = 0; k < K; ++k) clusters[k] = epik_amd_kmeans_cluster{0u, EPIK_AMD_KMEANS_NONE, 0.0, 0.0};
+    std::fill(centroids, centroids + K * N, 0.0);
+    *info = epik_amd_kmeans_info{0u, 0u, 0u, 1u};
+    if (L == 0) return EPIK_AMD_OK;
+    const auto plane_c = [&](size_t j) { return &p.C[used[j] * N]; };
+    const auto plane_b = [&](size_t j) { return &p.B[used[j] * N]; };
+    // the average of the planes of `members` (ascending j) into cc[N], cb[N]
+    const auto average = [&](const std::vector<size_t>& members, double* cc, double* cb) {
+        const double size = (double)members.size();
+        for (size_t b = 0; b < N; ++b) {
+            double acc_c = 0.0, acc_b = 0.0;
+            for (const size_t j : members) acc_c = acc_c + plane_c(j)[b], acc_b = acc_b + plane_b(j)[b];
+            cc[b] = acc_c / size, cb[b] = acc_b / size;
+        }
+    };
+    // the seeding: the sample nearest the grand mean, then farthest first
+    std::vector<double> cent_c(Kc * N), cent_b(Kc * N), mind(L);
+    std::vector<size_t> everyone(L), seed(Kc);
+    std::vector<char> is_centre(L, 0);
+    for (size_t j = 0; j < L; ++j) everyone[j] = j;
+    {
+        std::vector<double> mc(N), mb(N);
+        average(everyone, mc.data(), mb.data());
+        size_t at = 0;
+        double best = 0.0;
+        for (size_t j = 0; j < L; ++j) {
+            const double d = kr_of(mc.data(), mb.data(), plane_c(j), plane_b(j), half, N);
+            if (j == 0 || d < best) best = d, at = j;
+        }
+        seed[0] = at;
+    }
+    for (size_t k = 0; k < Kc; ++k) {
+        if (k) {
+            size_t at = L;
+            for (size_t j = 0; j < L; ++j)
+                if (!is_centre[j] && (at == L || mind[j] > mind[at])) at = j;
+            seed[k] = at;
+        }
+        const size_t c = seed[k];
+        is_centre[c] = 1;
+        std::copy(plane_c(c), plane_c(c) + N, &cent_c[k * N]);
+        std::copy(plane_b(c), plane_b(c) + N, &cent_b[k * N]);
+        for (size_t j = 0; j < L; ++j) {
+            const double d = kr_of(&cent_c[k * N], &cent_b[k * N], plane_c(j), plane_b(j), half, N);
+            mind[j] = k == 0 || d < mind[j] ? d : mind[j];
+        }
+    }
+    // the iterations
+    std::vector<size_t> assign(L, K);  // (K: none)
+    std::vector<double> dist(L, 0.0);
+    std::vector<std::vector<size_t>> members(Kc);
+    uint32_t iterations = 0, converged = 0;
+    for (;;) {
+        ++iterations;
+        size_t changed = 0;
+        for (auto& list : members) list.clear();
+        for (size_t j = 0; j < L; ++j) {
+            size_t at = 0;
+            double best = 0.0;
+            for (size_t k = 0; k < Kc; ++k) {
+                const double d = kr_of(plane_c(j), plane_b(j), &cent_c[k * N], &cent_b[k * N], half, N);
+                if (k == 0 || d < best) best = d, at = k;
+            }
+            changed += assign[j] != at ? 1 : 0;
+            assign[j] = at, dist[j] = best;
+            members[at].push_back(j);
+        }
+        if (changed == 0) {
+            converged = 1;
+            break;
+        }
+        if (iterations == max_iterations) break;
+        for (size_t k = 0; k < Kc; ++k)
+            if (!members[k].empty()) average(members[k], &cent_c[k * N], &cent_b[k * N]);
+    }
+    for (size_t j = 0; j < L; ++j) samples[used[j]] = epik_amd_kmeans_sample{(uint32_t)assign[j], 0u, dist[j]};
+    for (size_t k = 0; k < Kc; ++k) {
+        double sum = 0.0, sq = 0.0;
+        for (const size_t j : members[k]) sum = sum + dist[j], sq = sq + dist[j] * dist[j];
+        clusters[k] = epik_amd_kmeans_cluster{(uint32_t)members[k].size(), (uint32_t)used[seed[k]], sum, sq};
+        for (size_t b = 0; b < N; ++b) centroids[k * N + b] = cent_c[k * N + b] - cent_b[k * N + b];
+    }
+    *info = epik_amd_kmeans_info{(uint32_t)L, (uint32_t)Kc, iterations, converged};
+    return EPIK_AMD_OK;
+}
+
 std::vector<cohort_sample> read_cohort_list(const std::string& list_file)
 {
     std::ifstream in(list_file);
@@ -486,6 +593,35 @@ std::string format_epca_edges_tsv(const std::vector<uint32_t>& first, const doub
         for (size_t k = 0; k < Kc; ++k) out += '\t' + g17(edge[k * N + b]);
         out += '\n';
     }
+    return out;
+}
+
+std::string format_kmeans_tsv(const std::vector<cohort_sample>& samples, const epik_amd_kmeans_sample* records,
+                              const epik_amd_kmeans_cluster* clusters, const epik_amd_kmeans_info& info)
+{
+    const size_t S = samples.size();
+    std::string out = "# epik_amd kmeans v1  samples=" + std::to_string(S) + " used=" + std::to_string(info.used) +
+                      " clusters=" + std::to_string(info.clusters) + " iterations=" + std::to_string(info.iterations) +
+                      " converged=" + std::to_string(info.converged) + "\n";
+    for (size_t s = 0; s < S; ++s)
+        if (records[s].cluster == EPIK_AMD_KMEANS_NONE) out += "# unused\t" + samples[s].name + "\n";
+    for (size_t k = 0; k < info.clusters; ++k)
+        out += "# cluster\t" + std::to_string(k) + '\t' + std::to_string(clusters[k].size) + '\t' + samples.at(clusters[k].seed).name +
+               '\t' + g17(clusters[k].sum_dist) + '\t' + g17(clusters[k].sum_sq) + '\n';
+    out += "name\tcluster\tdist\n";
+    for (size_t s = 0; s < S; ++s)
+        if (records[s].cluster != EPIK_AMD_KMEANS_NONE)
+            out += samples[s].name + '\t' + std::to_string(records[s].cluster) + '\t' + g17(records[s].dist) + '\n';
+    return out;
+}
+
+std::string format_kmeans_centroids_tsv(const double* centroids, uint32_t num_branches, const epik_amd_kmeans_info& info)
+{
+    const size_t N = num_branches;
+    std::string out = "cluster\tedge_num\tmass\n";
+    for (size_t k = 0; k < info.clusters; ++k)
+        for (size_t b = 0; b < N; ++b)
+            if (centroids[k * N + b] != 0.0) out += std::to_string(k) + '\t' + std::to_string(b) + '\t' + g17(centroids[k * N + b]) + '\n';
     return out;
 }
 

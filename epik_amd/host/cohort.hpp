@@ -55,6 +55,14 @@ int squash_merges(const uint64_t* mass, uint32_t num_samples, uint32_t num_branc
 int epca_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                     uint32_t num_components, double* mu, double* proj, double* edge, epik_amd_epca_info* info, std::string& err);
 
+/// Phylogenetic k-means by the rule (include/epik_amd.h): samples[S], clusters[K], centroids[K][N] and *info, every cell
+/// written.  The code behind epik_amd_cohort_kmeans_host; libepik_amd's kernels (kmeans_place.hip) give the same bits.
+/// 0, or EPIK_AMD_ERR_INVALID with `err` naming num_clusters outside [1, 64], max_iterations outside [1, 1000], the branch
+/// whose first[] is above it or whose length is negative or not finite.
+int kmeans_clusters(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                    const double* branch_length, uint32_t num_clusters, uint32_t max_iterations, epik_amd_kmeans_sample* samples,
+                    epik_amd_kmeans_cluster* clusters, double* centroids, epik_amd_kmeans_info* info, std::string& err);
+
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
 /// name or path, a name given before, or a file that cannot be read; and for a list without any sample.
@@ -63,7 +71,8 @@ struct cohort_sample {
 };
 std::vector<cohort_sample> read_cohort_list(const std::string& list_file);
 
-/// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash | epca | epca_edges
+/// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash | epca | epca_edges | kmeans |
+/// kmeans_centroids
 std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir,
                                  const std::string& extension = ".tsv");
 
@@ -91,6 +100,13 @@ std::string format_squash_newick(const std::vector<cohort_sample>& samples, cons
 std::string format_epca_tsv(const std::vector<cohort_sample>& samples, const std::vector<char>& used, uint32_t num_components,
                             const double* mu, const double* proj, const epik_amd_epca_info& info);
 std::string format_epca_edges_tsv(const std::vector<uint32_t>& first, const double* edge, const epik_amd_epca_info& info);
+/// cohort_kmeans .tsv: "# epik_amd kmeans v1  samples=S used=L clusters=K' iterations=i converged=0|1", a "# unused<TAB>name"
+/// line per sample without mass, a "# cluster<TAB>k<TAB>size<TAB>seed name<TAB>sum_dist<TAB>sum_sq" line per cluster
+/// k < K', the column names name cluster dist, then per used sample in list order its name, cluster and dist; doubles %.17g.
+/// cohort_kmeans_centroids .tsv: cluster edge_num mass, a line per non-zero cell of centroids[K][N], k < K'.
+std::string format_kmeans_tsv(const std::vector<cohort_sample>& samples, const epik_amd_kmeans_sample* records,
+                              const epik_amd_kmeans_cluster* clusters, const epik_amd_kmeans_info& info);
+std::string format_kmeans_centroids_tsv(const double* centroids, uint32_t num_branches, const epik_amd_kmeans_info& info);
 /// `text` into `filename` through `filename`.part, renamed when all of it is written
 void write_through_part(const std::string& filename, const std::string& text);
 

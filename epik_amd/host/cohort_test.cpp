@@ -7,6 +7,9 @@
 //                                           uint32 num_merges
 //   cohort_test epca <out.bin> <in.bin> <K> the edge principal components of a `kr` input (its lengths are not used):
 //                                           float64 mu[K], proj[S][K], edge[K][N], then epik_amd_epca_info
+//   cohort_test kmeans <out.bin> <in.bin> <K> <max_iterations>
+//                                           the phylogenetic k-means of a `kr` input: epik_amd_kmeans_sample [S],
+//                                           epik_amd_kmeans_cluster [K], float64 centroids[K][N], then epik_amd_kmeans_info
 // An `add` input holds, little endian: uint64 n, keep, num_branches, num_samples; epik_amd_placement rows[n][keep];
 // uint32 n_rows[n]; uint32 kmer_counts[n][keep]; uint32 weights[n]; uint32 samples[n].
 // A `kr` input: uint64 num_samples, num_branches; uint64 mass[S][N]; uint32 first[N]; float64 branch_length[N].
@@ -130,8 +133,37 @@ int main(int argc, char** argv)
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }
+        if (argc == 6 && std::strcmp(argv[1], "kmeans") == 0) {
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto mass = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const auto length = read_array<double>(in, N);
+            const unsigned long K = std::stoul(argv[4]), max_iterations = std::stoul(argv[5]);
+            if (K < 1 || K > EPIK_AMD_KMEANS_MAX_CLUSTERS) throw std::runtime_error("num_clusters = " + std::to_string(K) + " is outside [1, 64]");
+            if (max_iterations < 1 || max_iterations > EPIK_AMD_KMEANS_MAX_ITERATIONS)
+                throw std::runtime_error("max_iterations = " + std::to_string(max_iterations) + " is outside [1, 1000]");
+            std::vector<epik_amd_kmeans_sample> samples(S);
+            std::vector<epik_amd_kmeans_cluster> clusters(K);
+            std::vector<double> centroids(K * N);
+            epik_amd_kmeans_info info{};
+            std::string err;
+            if (epik_amd::kmeans_clusters(mass.data(), (uint32_t)S, (uint32_t)N, first.data(), length.data(), (uint32_t)K,
+                                          (uint32_t)max_iterations, samples.data(), clusters.data(), centroids.data(), &info, err) != 0)
+                throw std::runtime_error(err);
+            std::ofstream out(argv[2], std::ios::binary);
+            write_array(out, samples.data(), samples.size());
+            write_array(out, clusters.data(), clusters.size());
+            write_array(out, centroids.data(), centroids.size());
+            write_array(out, &info, 1);
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
         std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin> | squash <out.bin> <in.bin> | "
-                     "epca <out.bin> <in.bin> <K>\n";
+                     "epca <out.bin> <in.bin> <K> | kmeans <out.bin> <in.bin> <K> <max_iterations>\n";
         return 2;
     } catch (const std::exception& error) {
         std::cerr << "Error: " << error.what() << std::endl;

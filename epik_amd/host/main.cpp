@@ -227,6 +227,10 @@ const char* kHelp =
     "                          on the device and write cohort_epca_<list>.tsv (the components and every sample's\n"
     "                          projections) and cohort_epca_edges_<list>.tsv (the components' coefficients per inner branch)\n"
     "      --cohort-epca-components arg  With --cohort-epca: the number of components, in [1, 64] (default: 5)\n"
+    "      --cohort-kmeans arg With --cohort: also cluster the samples into at most arg clusters, in [1, 64], by phylogenetic\n"
+    "                          k-means (Czech et al. 2019) on the device and write cohort_kmeans_<list>.tsv (the clusters and\n"
+    "                          every sample's cluster and distance) and cohort_kmeans_centroids_<list>.tsv (the centroids' masses)\n"
+    "      --cohort-kmeans-iterations arg  With --cohort-kmeans: the most iterations, in [1, 1000] (default: 100)\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -386,6 +390,28 @@ int main(int argc, char** argv)
             if (used != text.size() || used == 0 || text[0] == '-' || k < 1 || k > EPIK_AMD_EPCA_MAX_COMPONENTS)
                 throw std::runtime_error("--cohort-epca-components must be a whole number in [1, 64], not '" + text + "'");
             epca_components = (uint32_t)k;
+        }
+        const bool with_kmeans = parsed.has("cohort-kmeans");
+        if (with_kmeans && !with_cohort) throw std::runtime_error("--cohort-kmeans needs --cohort (it clusters the samples of the list)");
+        if (parsed.has("cohort-kmeans-iterations") && !with_kmeans)
+            throw std::runtime_error("--cohort-kmeans-iterations needs --cohort-kmeans (the flag that clusters the samples)");
+        uint32_t kmeans_clusters = 0, kmeans_iterations = 100;
+        if (with_kmeans) {
+            const auto whole_number = [&](const std::string& flag, const std::string& fallback, unsigned long most) {
+                const auto text = parsed.get(flag, fallback);
+                size_t used = 0;
+                unsigned long v = 0;
+                try {
+                    v = std::stoul(text, &used);
+                } catch (const std::exception&) {
+                    used = 0;
+                }
+                if (used != text.size() || used == 0 || text[0] == '-' || v < 1 || v > most)
+                    throw std::runtime_error("--" + flag + " must be a whole number in [1, " + std::to_string(most) + "], not '" + text + "'");
+                return (uint32_t)v;
+            };
+            kmeans_clusters = whole_number("cohort-kmeans", "", EPIK_AMD_KMEANS_MAX_CLUSTERS);
+            kmeans_iterations = whole_number("cohort-kmeans-iterations", "100", EPIK_AMD_KMEANS_MAX_ITERATIONS);
         }
         if (with_cohort) {
             for (const char* other : {"mates", "profile-only", "profile", "assign"})
@@ -740,7 +766,9 @@ int main(int argc, char** argv)
         const auto cohort_squash_tree_filename = epik_amd::make_cohort_filename("squash", query_file, output_dir, ".nwk");
         const auto cohort_epca_filename = epik_amd::make_cohort_filename("epca", query_file, output_dir);
         const auto cohort_epca_edges_filename = epik_amd::make_cohort_filename("epca_edges", query_file, output_dir);
-        bool epca_converged = true;
+        const auto cohort_kmeans_filename = epik_amd::make_cohort_filename("kmeans", query_file, output_dir);
+        const auto cohort_kmeans_centroids_filename = epik_amd::make_cohort_filename("kmeans_centroids", query_file, output_dir);
+        bool epca_converged = true, kmeans_converged = true;
         if (with_cohort) {
             // the handles' cohorts summed on the first device, read once, and the distances computed there
             epik_amd::sample_cohort cohort((uint32_t)cohort_samples.size(), (uint32_t)tree.get_node_count());
@@ -749,8 +777,10 @@ int main(int argc, char** argv)
             uint32_t num_merges = 0;
             epik_amd::placer::cohort_epca epca;
             epca.num_components = epca_components;
+            epik_amd::placer::cohort_kmeans kmeans;
+            kmeans.num_clusters = kmeans_clusters, kmeans.max_iterations = kmeans_iterations;
             placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
-                               with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr);
+                               with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr, with_kmeans ? &kmeans : nullptr);
             epik_amd::write_through_part(cohort_samples_filename, epik_amd::format_cohort_samples_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_profile_filename, epik_amd::format_cohort_profile_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_kr_filename, epik_amd::format_cohort_kr_tsv(cohort_samples, kr));
@@ -766,6 +796,14 @@ int main(int argc, char** argv)
                 epik_amd::write_through_part(cohort_epca_edges_filename,
                                              epik_amd::format_epca_edges_tsv(epca.first, epca.edge.data(), epca.info));
                 epca_converged = epca.info.converged != 0;
+            }
+            if (with_kmeans) {
+                epik_amd::write_through_part(cohort_kmeans_filename, epik_amd::format_kmeans_tsv(cohort_samples, kmeans.samples.data(),
+                                                                                                 kmeans.clusters.data(), kmeans.info));
+                epik_amd::write_through_part(cohort_kmeans_centroids_filename,
+                                             epik_amd::format_kmeans_centroids_tsv(kmeans.centroids.data(), (uint32_t)cohort.num_branches,
+                                                                                   kmeans.info));
+                kmeans_converged = kmeans.info.converged != 0;
             }
             if (with_squash) {
                 epik_amd::write_through_part(cohort_squash_filename,
@@ -806,6 +844,12 @@ int main(int argc, char** argv)
         if (!epca_converged)
             std::cout << "Warning: the edge principal components did not converge in " << EPIK_AMD_EPCA_MAX_SWEEPS
                       << " sweeps (converged=0 in " << cohort_epca_filename << ")" << std::endl;
+        if (with_kmeans)
+            std::cout << "Cohort k-means: " << cohort_kmeans_filename << "\nCohort k-means centroids: " << cohort_kmeans_centroids_filename
+                      << std::endl;
+        if (!kmeans_converged)
+            std::cout << "Warning: the phylogenetic k-means did not converge in " << kmeans_iterations
+                      << " iterations (converged=0 in " << cohort_kmeans_filename << ")" << std::endl;
         if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;
         if (strands_out.is_open()) {
             strands_out.close();

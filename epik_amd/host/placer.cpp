@@ -33,6 +33,7 @@
 #pragma weak epik_amd_cohort_kr
 #pragma weak epik_amd_cohort_squash
 #pragma weak epik_amd_cohort_epca
+#pragma weak epik_amd_cohort_kmeans
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -237,8 +238,9 @@ void placer::set_cohort(uint32_t num_samples)
 }
 
 void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
-                         epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca)
+                         epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans)
 {
+    if (kmeans && !&epik_amd_cohort_kmeans) throw std::runtime_error("GPU placer: this libepik_amd has no phylogenetic k-means");
     if (num_merges && !&epik_amd_cohort_squash) throw std::runtime_error("GPU placer: this libepik_amd has no squash clustering");
     if (epca && !&epik_amd_cohort_epca) throw std::runtime_error("GPU placer: this libepik_amd has no edge principal components");
     const auto check = [](int rc) {
@@ -276,6 +278,13 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
                 epca->first[parent[b]] = std::min(epca->first[parent[b]], epca->first[b]);
         rc = epik_amd_cohort_epca(_cohorts[0], tree, epca->num_components, epca->mu.data(), epca->proj.data(), epca->edge.data(),
                                   &epca->info);
+    }
+    if (rc == EPIK_AMD_OK && kmeans) {
+        const size_t N = parent.size(), K = kmeans->num_clusters;
+        kmeans->samples.assign(_cohort_samples, epik_amd_kmeans_sample{}), kmeans->clusters.assign(K, epik_amd_kmeans_cluster{});
+        kmeans->centroids.assign(K * N, 0.0);
+        rc = epik_amd_cohort_kmeans(_cohorts[0], tree, length.data(), kmeans->num_clusters, kmeans->max_iterations,
+                                    kmeans->samples.data(), kmeans->clusters.data(), kmeans->centroids.data(), &kmeans->info);
     }
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);

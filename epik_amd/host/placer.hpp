@@ -174,8 +174,18 @@ public:
         epik_amd_epca_info info{};
         std::vector<uint32_t> first;
     };
+    /// With `kmeans` (--cohort-kmeans) their phylogenetic k-means too: num_clusters (K) and max_iterations on entry;
+    /// samples of num_samples records, clusters of K, centroids of K * num_branches values and the info block on return.
+    struct cohort_kmeans {
+        uint32_t num_clusters = 0, max_iterations = 0;
+        std::vector<epik_amd_kmeans_sample> samples;
+        std::vector<epik_amd_kmeans_cluster> clusters;
+        std::vector<double> centroids;
+        epik_amd_kmeans_info info{};
+    };
     void read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
-                     epik_amd_squash_merge* merges = nullptr, uint32_t* num_merges = nullptr, cohort_epca* epca = nullptr);
+                     epik_amd_squash_merge* merges = nullptr, uint32_t* num_merges = nullptr, cohort_epca* epca = nullptr,
+                     cohort_kmeans* kmeans = nullptr);
     /// The profiles of all devices read back and summed; `mass` and `best` of num_branches cells each.
     void read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_totals& totals) const;
     /// distal_length / pendant_length of a placement on branch b (place.cpp:110-123, 435-437)

@@ -734,6 +734,35 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *   The files derive, one division each: lambda_k = mu_k / (double)max(L - 1, 1); fraction_k = mu_k / trace, 0 when
  *     trace is 0.
  *
+ * Phylogenetic k-means (Czech et al. 2019) of the cohort's samples.  From mass[S][N], first[N], branch_length[N] as for
+ *   the KR distance, K in [1, 64] and max_iterations in [1, 1000].  All arithmetic is IEEE double, every operation
+ *   rounded on its own, nothing fused.  T_s, C_s[b], B_s[b] are exactly those of the KR rule, and KR(x, y) over ANY two
+ *   pairs of planes is the KR rule's sequential sum: acc = +0.0, then for b = 0 .. N - 1 in this order
+ *   acc = acc + (0.5 * bl[b]) * (|C_x[b] - C_y[b]| + |B_x[b] - B_y[b]|).  An implementation may share out the (sample,
+ *   centroid) pairs and the branches of an AVERAGING, never the branches of one distance or the members of one average.
+ *   Used samples.  Sample s is used iff T_s > 0; the used samples, in ascending s, get j = 0 .. L - 1.  K' = min(K, L).
+ *     L = 0: info = {0, 0, 0, 1} and every other output as for an unused sample or a cluster >= K'.
+ *   Seeding (farthest first, deterministic).  Grand mean: M.C[b] = (acc after j = 0 .. L - 1 in this order,
+ *     acc = acc + C_j[b], acc = +0.0 at first) / (double)L, M.B likewise.  Centre 0 is the first j with the smallest
+ *     KR(M, j) (strict <); then mind[j] = KR(centre 0, j).  Centre k = 1 .. K' - 1 is the first j, not yet a centre, with
+ *     the largest mind[j] (strict >; a mind of 0 qualifies, so two identical samples can both become centres); then
+ *     mind[j] = min(mind[j], KR(centre k, j)).  Centroid k starts as the planes of centre k; seed[k] is that centre's
+ *     sample index s (not j).
+ *   Iteration i = 1, 2, ..., in this order:
+ *     1. D[j][k] = KR(j, centroid k) for all j and k < K'.
+ *     2. new[j] = the first k with the smallest D[j][k] (strict <).  changed = the number of j with new[j] != assign[j];
+ *        assign is "none" before iteration 1, so iteration 1 never converges when L >= 1.  Then assign = new.
+ *     3. changed == 0: converged = 1, iterations = i, stop.
+ *     4. i == max_iterations: converged = 0, iterations = i, stop (no update follows the last assignment).
+ *     5. Update, for every k with at least one member: centroid_k.C[b] = (acc after its members in ascending j,
+ *        acc = acc + C_j[b], acc = +0.0 at first) / (double)size_k, .B likewise.  A cluster without members keeps the
+ *        planes it has.
+ *   Results.  Per sample {cluster, 0, dist}, dist = D[j][assign[j]] of the last step 1; an unused sample gets
+ *     {0xffffffff, 0, -1.0}.  Per cluster k < K {size, seed, sum_dist, sum_sq}, the two sums over the members in
+ *     ascending j from +0.0, sum_sq adding dist * dist; {0, 0xffffffff, +0.0, +0.0} for k >= K'.
+ *     centroids[K][N] = centroid_k.C[b] - centroid_k.B[b], the centroid's own mass on b, +0.0 for k >= K'.
+ *     info = {used L, clusters K', iterations, converged}.  Every cell of every output is written.
+ *
  * An epik_amd_cohort is an object of its own, created for a placer's device, num_branches and keep_at_most (whole
  * databases only, not a k-mer-space shard) and num_samples >= 1; all zero at create() and after reset().
  *   add_device  asynchronous on `stream`, allocates nothing: as epik_amd_profile_add_device, with d_samples (uint32 [n],
@@ -760,6 +789,14 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *               once per sweep for the sweep's rotation counter; the results are enqueued on `stream`.  The cells are
  *               not changed.   epca: the same into host memory, synchronous.
  *   epca_host   the rule on the host from mass[S][N] and first[N], no device; first[b] > b is refused.
+ *   kmeans_device  checks the tree and the lengths as kr_device, K in [1, 64] and max_iterations in [1, 1000]; the first
+ *               call allocates a workspace of its own, kept until destroy(): about 16 * N * 64 + 8 * S * 64 bytes (the
+ *               centroid planes and D).  d_samples is epik_amd_kmeans_sample [S], d_clusters epik_amd_kmeans_cluster [K],
+ *               d_centroids float64 [K][N] and d_info one epik_amd_kmeans_info, all in device memory, every cell written.
+ *               The seeding is enqueued whole; then it synchronises `stream` once per iteration for `changed` (4 bytes
+ *               each time); the results are enqueued on `stream`.  The cells are not changed.
+ *               kmeans: the same into host memory, synchronous.
+ *   kmeans_host the rule on the host from mass[S][N] and first[N], no device; first[b] > b is refused.
  * cohort_reads / _strands / _frames / _mates: the profile_* twins with samples[n] (HOST uint32) beside the weights.
  */
 typedef struct epik_amd_cohort epik_amd_cohort;
@@ -803,6 +840,31 @@ int epik_amd_cohort_epca(epik_amd_cohort *cohort, const epik_amd_tree *tree, uin
                          double *proj, double *edge, epik_amd_epca_info *info);
 int epik_amd_cohort_epca_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                               uint32_t num_components, double *mu, double *proj, double *edge, epik_amd_epca_info *info);
+typedef struct epik_amd_kmeans_info {
+    uint32_t used, clusters; /* L, and K' = min(K, L) */
+    uint32_t iterations, converged;
+} epik_amd_kmeans_info; /* 16 bytes */
+typedef struct epik_amd_kmeans_sample {
+    uint32_t cluster, zero; /* EPIK_AMD_KMEANS_NONE for a sample without mass */
+    double dist;            /* KR(sample, its centroid) at the last assignment; -1.0 without mass */
+} epik_amd_kmeans_sample; /* 16 bytes */
+typedef struct epik_amd_kmeans_cluster {
+    uint32_t size, seed;     /* its members; the sample that seeded it, EPIK_AMD_KMEANS_NONE for k >= K' */
+    double sum_dist, sum_sq; /* over its members: dist, dist * dist */
+} epik_amd_kmeans_cluster; /* 24 bytes */
+#define EPIK_AMD_KMEANS_MAX_CLUSTERS 64u
+#define EPIK_AMD_KMEANS_MAX_ITERATIONS 1000u
+#define EPIK_AMD_KMEANS_NONE 0xffffffffu
+int epik_amd_cohort_kmeans_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                                  uint32_t num_clusters, uint32_t max_iterations, void *d_samples, void *d_clusters,
+                                  void *d_centroids, void *d_info, void *stream);
+int epik_amd_cohort_kmeans(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                           uint32_t num_clusters, uint32_t max_iterations, epik_amd_kmeans_sample *samples,
+                           epik_amd_kmeans_cluster *clusters, double *centroids, epik_amd_kmeans_info *info);
+int epik_amd_cohort_kmeans_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                const double *branch_length, uint32_t num_clusters, uint32_t max_iterations,
+                                epik_amd_kmeans_sample *samples, epik_amd_kmeans_cluster *clusters, double *centroids,
+                                epik_amd_kmeans_info *info);
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n);
 int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
