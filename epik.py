@@ -19,6 +19,9 @@ the Kantorovich-Rubinstein distance between every two of them, cohort_samples_ /
 cohort_epca_edges_<list>.tsv; --cohort-epca-components K of them (default 5).
 --cohort-kmeans K, with --cohort: the phylogenetic k-means of the samples into at most K clusters, cohort_kmeans_<list>.tsv
 and cohort_kmeans_centroids_<list>.tsv; --cohort-kmeans-iterations M at the most (default 100).
+--cohort-alpha, with --cohort: the alpha diversity indices of every sample, cohort_alpha_<list>.tsv.
+--cohort-rarefy KMAX, with --cohort: every sample's rarefaction curve up to depth KMAX, cohort_rarefy_<list>.tsv;
+--cohort-rarefy-step STEP between two depths (default max(1, ceil(KMAX / 64))).
 """
 from __future__ import annotations
 
@@ -97,6 +100,16 @@ PLACE_OPTIONS = [
                                      "centroids' masses).")),
     (("--cohort-kmeans-iterations",), dict(type=click.IntRange(1, 1000), default=None,
                                            help="With --cohort-kmeans: the most iterations, in [1, 1000] [default: 100].")),
+    (("--cohort-alpha",), dict(is_flag=True, help="With --cohort: also compute the alpha diversity of every sample on the device "
+                                                  "(PD, rooted PD, balance-weighted PD at 0.5 and 1, quadratic entropy) and "
+                                                  "write cohort_alpha_<list>.tsv.")),
+    (("--cohort-rarefy",), dict(type=click.IntRange(1, 1 << 20), default=None,
+                                help="With --cohort: also compute every sample's rarefaction curve on the device, the expected "
+                                     "PD and rooted PD of k reads up to this depth, in [1, 1048576], and write "
+                                     "cohort_rarefy_<list>.tsv.")),
+    (("--cohort-rarefy-step",), dict(type=click.IntRange(1, 1 << 20), default=None,
+                                     help="With --cohort-rarefy: the distance between two depths; floor(depth / step) must lie "
+                                          "in [1, 256] [default: max(1, ceil(depth / 64))].")),
 ]
 
 
@@ -113,7 +126,8 @@ def driver_path(states: str) -> str:
 def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpus, input_file, db_shard=1,
                    strand="forward", translate=None, profile=False, profile_only=False, mates=None,
                    mate_orientation="fr", assign=False, assign_mass=None, cohort=False, cohort_squash=False,
-                   cohort_epca=False, cohort_epca_components=None, cohort_kmeans=None, cohort_kmeans_iterations=None):
+                   cohort_epca=False, cohort_epca_components=None, cohort_kmeans=None, cohort_kmeans_iterations=None,
+                   cohort_alpha=False, cohort_rarefy=None, cohort_rarefy_step=None):
     if assign_mass is not None and not assign:
         raise click.UsageError("--assign-mass needs --assign")
     if assign and db_shard != 1:
@@ -128,6 +142,17 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         raise click.UsageError("--cohort-kmeans needs --cohort")
     if cohort_kmeans_iterations is not None and cohort_kmeans is None:
         raise click.UsageError("--cohort-kmeans-iterations needs --cohort-kmeans")
+    if cohort_alpha and not cohort:
+        raise click.UsageError("--cohort-alpha needs --cohort")
+    if cohort_rarefy is not None and not cohort:
+        raise click.UsageError("--cohort-rarefy needs --cohort")
+    if cohort_rarefy_step is not None and cohort_rarefy is None:
+        raise click.UsageError("--cohort-rarefy-step needs --cohort-rarefy")
+    if cohort_rarefy is not None:
+        step = int(cohort_rarefy_step) if cohort_rarefy_step is not None else max(1, -(-int(cohort_rarefy) // 64))
+        if not 1 <= int(cohort_rarefy) // step <= 256:
+            raise click.UsageError(f"--cohort-rarefy-step {step}: floor({int(cohort_rarefy)} / {step}) depths of --cohort-rarefy "
+                                   "must lie in [1, 256]")
     if cohort:
         for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
                             ("--assign", assign), ("--db-shard > 1", db_shard != 1)):
@@ -169,6 +194,12 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--cohort-kmeans", str(int(cohort_kmeans))]
         if cohort_kmeans_iterations is not None:
             argv += ["--cohort-kmeans-iterations", str(int(cohort_kmeans_iterations))]
+    if cohort_alpha:
+        argv += ["--cohort-alpha"]
+    if cohort_rarefy is not None:
+        argv += ["--cohort-rarefy", str(int(cohort_rarefy))]
+        if cohort_rarefy_step is not None:
+            argv += ["--cohort-rarefy-step", str(int(cohort_rarefy_step))]
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 

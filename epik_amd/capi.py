@@ -38,6 +38,12 @@ KMEANS_CLUSTER = np.dtype([("size", np.uint32), ("seed", np.uint32), ("sum_dist"
 KMEANS_MAX_CLUSTERS = 64
 KMEANS_MAX_ITERATIONS = 1000
 KMEANS_NONE = 0xFFFFFFFF
+#: epik_amd_alpha (40 bytes): the five alpha diversity indices of a sample
+ALPHA = np.dtype([("pd", np.float64), ("rooted_pd", np.float64), ("bwpd_half", np.float64), ("bwpd_one", np.float64),
+                  ("quadratic", np.float64)])
+DIVERSITY_BLOCK = 256
+RAREFY_MAX_DEPTHS = 256
+RAREFY_MAX_DEPTH = 1 << 20
 #: numpy mirror of `epik_amd_pkdb_value` / `i2l::pkdb_value` (8 bytes)
 PKDB_VALUE = np.dtype([("branch", np.uint32), ("score", np.float32)])
 
@@ -121,6 +127,12 @@ EXPORTS = (
     "epik_amd_cohort_kmeans_device",
     "epik_amd_cohort_kmeans",
     "epik_amd_cohort_kmeans_host",
+    "epik_amd_cohort_alpha_device",
+    "epik_amd_cohort_alpha",
+    "epik_amd_cohort_alpha_host",
+    "epik_amd_cohort_rarefy_device",
+    "epik_amd_cohort_rarefy",
+    "epik_amd_cohort_rarefy_host",
     "epik_amd_placer_cohort_reads",
     "epik_amd_placer_cohort_strands",
     "epik_amd_placer_cohort_frames",
@@ -443,6 +455,18 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_kmeans.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp]
     lib.epik_amd_cohort_kmeans_host.restype = i32
     lib.epik_amd_cohort_kmeans_host.argtypes = [vp, u32, u32, vp, vp, u32, u32, vp, vp, vp, vp]
+    lib.epik_amd_cohort_alpha_device.restype = i32
+    lib.epik_amd_cohort_alpha_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.epik_amd_cohort_alpha.restype = i32
+    lib.epik_amd_cohort_alpha.argtypes = [vp, vp, vp, vp]
+    lib.epik_amd_cohort_alpha_host.restype = i32
+    lib.epik_amd_cohort_alpha_host.argtypes = [vp, u32, u32, vp, vp, vp]
+    lib.epik_amd_cohort_rarefy_device.restype = i32
+    lib.epik_amd_cohort_rarefy_device.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+    lib.epik_amd_cohort_rarefy.restype = i32
+    lib.epik_amd_cohort_rarefy.argtypes = [vp, vp, vp, u32, u32, vp]
+    lib.epik_amd_cohort_rarefy_host.restype = i32
+    lib.epik_amd_cohort_rarefy_host.argtypes = [vp, u32, u32, vp, vp, u32, u32, vp]
     lib.epik_amd_placer_cohort_reads.restype = i32
     lib.epik_amd_placer_cohort_reads.argtypes = [vp, vp, vp, vp, vp, vp, u64]
     for name in ("epik_amd_placer_cohort_strands", "epik_amd_placer_cohort_frames", "epik_amd_placer_cohort_mates"):

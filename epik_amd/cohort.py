@@ -18,6 +18,10 @@ files of --cohort-epca.
 Phylogenetic k-means of the samples (the header's fourth rule): `Cohort.kmeans` / `kmeans_device` on the device,
 `kmeans_host` on the host, each giving a `Kmeans`; `format_kmeans_tsv`, `format_kmeans_centroids_tsv` and their readers are
 the two files of --cohort-kmeans.
+
+Alpha diversity and rarefaction curves of the samples (the header's fifth rule): `Cohort.alpha` / `alpha_device` and
+`Cohort.rarefy` / `rarefy_device` on the device, `alpha_host` and `rarefy_host` on the host; `format_alpha_tsv`,
+`format_rarefy_tsv` and their readers are the files of --cohort-alpha and --cohort-rarefy.
 """
 from __future__ import annotations
 
@@ -188,6 +192,33 @@ def kmeans_host(mass, first, branch_length, num_clusters: int, max_iterations: i
                                                out.samples.ctypes.data, out.clusters.ctypes.data, out.centroids.ctypes.data,
                                                out.info.ctypes.data))
     out.info = out.info[0]
+    return out
+
+
+def alpha_host(mass, first, branch_length) -> np.ndarray:
+    """The alpha diversity indices of the rule for mass[S][N] on the host (`epik_amd_cohort_alpha_host`): `capi.ALPHA` [S]."""
+    lib = capi.load()
+    mass, first, length = _cells_and_tree(mass, first, branch_length)
+    s, n = mass.shape
+    out = np.full(s * 5, np.nan).view(capi.ALPHA)
+    capi.check(lib.epik_amd_cohort_alpha_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, out.ctypes.data))
+    return out
+
+
+def _curve_buffer(s, num_depths) -> np.ndarray:
+    return np.full((s, min(max(num_depths, 1), 0x10000), 2), np.nan)   # (refused depths still need somewhere to point)
+
+
+def rarefy_host(best, first, branch_length, depth_step: int, num_depths: int) -> np.ndarray:
+    """The rarefaction curves of the rule for best[S][N] on the host (`epik_amd_cohort_rarefy_host`): float64 [S][J][2],
+    the expected unrooted and rooted PD of k_j = j * depth_step reads, {-1, -1} beyond a sample's reads."""
+    lib = capi.load()
+    best, first, length = _cells_and_tree(best, first, branch_length)
+    s, n = best.shape
+    step, depths = _count32(depth_step, "depth_step"), _count32(num_depths, "num_depths")
+    out = _curve_buffer(s, depths)
+    capi.check(lib.epik_amd_cohort_rarefy_host(best.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, step, depths,
+                                               out.ctypes.data))
     return out
 
 
@@ -364,6 +395,36 @@ class Cohort:
         capi.check(self._lib.epik_amd_cohort_kmeans(self._handle, tree._handle, length.ctypes.data, k, m, out.samples.ctypes.data,
                                                     out.clusters.ctypes.data, out.centroids.ctypes.data, out.info.ctypes.data))
         out.info = out.info[0]
+        return out
+
+    def alpha_device(self, tree, branch_length, d_alpha: int, stream: int = 0) -> None:
+        """The alpha diversity indices into d_alpha, `capi.ALPHA` [S] in device memory, every cell written; asynchronous
+        on `stream` once the lengths (host) are copied, no readback (`epik_amd_cohort_alpha_device`)."""
+        length = self._lengths(tree, branch_length)
+        capi.check(self._lib.epik_amd_cohort_alpha_device(self._handle, tree._handle, length.ctypes.data, d_alpha or None,
+                                                          stream or None))
+
+    def alpha(self, tree, branch_length) -> np.ndarray:
+        """The alpha diversity indices of the samples, `capi.ALPHA` [S] (`epik_amd_cohort_alpha`)."""
+        length = self._lengths(tree, branch_length)
+        out = np.full(self.num_samples * 5, np.nan).view(capi.ALPHA)
+        capi.check(self._lib.epik_amd_cohort_alpha(self._handle, tree._handle, length.ctypes.data, out.ctypes.data))
+        return out
+
+    def rarefy_device(self, tree, branch_length, depth_step: int, num_depths: int, d_curve: int, stream: int = 0) -> None:
+        """The rarefaction curves into d_curve, float64 [S][J][2] in device memory, every cell written; asynchronous on
+        `stream` once the lengths (host) are copied, no readback (`epik_amd_cohort_rarefy_device`)."""
+        length = self._lengths(tree, branch_length)
+        capi.check(self._lib.epik_amd_cohort_rarefy_device(self._handle, tree._handle, length.ctypes.data,
+                                                           _count32(depth_step, "depth_step"), _count32(num_depths, "num_depths"),
+                                                           d_curve or None, stream or None))
+
+    def rarefy(self, tree, branch_length, depth_step: int, num_depths: int) -> np.ndarray:
+        """The rarefaction curves of the samples, float64 [S][J][2] (`epik_amd_cohort_rarefy`)."""
+        length = self._lengths(tree, branch_length)
+        step, depths = _count32(depth_step, "depth_step"), _count32(num_depths, "num_depths")
+        out = _curve_buffer(self.num_samples, depths)
+        capi.check(self._lib.epik_amd_cohort_rarefy(self._handle, tree._handle, length.ctypes.data, step, depths, out.ctypes.data))
         return out
 
     def reset(self) -> None:
@@ -629,6 +690,95 @@ def read_kmeans_centroids_tsv(path: str, num_clusters: int, num_branches: int) -
             k, b, v = ln.rstrip("\n").split("\t")
             out[int(k), int(b)] = float(v)
     return out
+
+
+ALPHA_HEADER = "name\tpd\trooted_pd\tbwpd_0.5\tbwpd_1\tquadratic_entropy"
+RAREFY_HEADER = "name\tk\treads\tpd\trooted_pd"
+_ALPHA_FIELDS = ("pd", "rooted_pd", "bwpd_half", "bwpd_one", "quadratic")
+
+
+def format_alpha_tsv(names, alpha) -> str:
+    """cohort_alpha_<list>.tsv: the first line, a `# unused` line per sample without mass (pd == -1), the column names,
+    then per used sample, in list order, its name and the five indices; doubles as %.17g."""
+    alpha = np.asarray(alpha)
+    if alpha.dtype != capi.ALPHA or alpha.shape != (len(names),):
+        raise ValueError("one capi.ALPHA record per sample")
+    used = alpha["pd"] != -1.0
+    lines = [f"# epik_amd alpha v1  samples={len(names)} used={int(used.sum())}"]
+    lines += [f"# unused\t{name}" for name, u in zip(names, used) if not u]
+    lines.append(ALPHA_HEADER)
+    for i, name in enumerate(names):
+        if used[i]:
+            lines.append(name + "".join("\t%.17g" % float(alpha[f][i]) for f in _ALPHA_FIELDS))
+    return "\n".join(lines) + "\n"
+
+
+def read_alpha_tsv(path: str):
+    """(names, alpha `capi.ALPHA` [L], info): the used samples in list order, and {"samples", "used", "unused": names}."""
+    with open(path, newline="") as fh:
+        head = re.fullmatch(r"# epik_amd alpha v1  samples=(\d+) used=(\d+)", fh.readline().rstrip("\n"))
+        if not head:
+            raise ValueError(f"{path}: not a cohort alpha file")
+        info = {"samples": int(head.group(1)), "used": int(head.group(2)), "unused": []}
+        line = fh.readline().rstrip("\n")
+        while line.startswith("# unused\t"):
+            info["unused"].append(line.split("\t", 1)[1])
+            line = fh.readline().rstrip("\n")
+        if line != ALPHA_HEADER:
+            raise ValueError(f"{path}: not a cohort alpha file")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    if len(rows) != info["used"] or any(len(r) != 6 for r in rows) or len(info["unused"]) != info["samples"] - info["used"]:
+        raise ValueError(f"{path}: the rows do not follow the first line's counts")
+    alpha = np.zeros(len(rows), dtype=capi.ALPHA)
+    for i, r in enumerate(rows):
+        alpha[i] = tuple(float(x) for x in r[1:])
+    return [r[0] for r in rows], alpha, info
+
+
+def reads_of(best) -> np.ndarray:
+    """n_s of the rule: the wrapping sum of best[s][:], uint64 [S]."""
+    return np.asarray(best, dtype=np.uint64).sum(axis=1, dtype=np.uint64)
+
+
+def format_rarefy_tsv(names, reads, depth_step: int, curve) -> str:
+    """cohort_rarefy_<list>.tsv: the first line, a `# unused` line per sample that is not rarefiable (`reads`[s] = n_s is 0
+    or >= 2^53), the column names, then, long format, name, k, reads, pd and rooted_pd for every used sample and every
+    k_j <= n_s of curve[S][J][2]; doubles as %.17g."""
+    curve = np.asarray(curve, dtype=np.float64)
+    reads = [int(x) for x in reads]
+    step = int(depth_step)
+    if curve.ndim != 3 or curve.shape[0] != len(names) or curve.shape[2] != 2 or len(reads) != len(names):
+        raise ValueError("curve must be [num_samples][num_depths][2], with one read count per sample")
+    used = [0 < n < (1 << 53) for n in reads]
+    lines = [f"# epik_amd rarefy v1  samples={len(names)} used={sum(used)} step={step} depths={curve.shape[1]}"]
+    lines += [f"# unused\t{name}" for name, u in zip(names, used) if not u]
+    lines.append(RAREFY_HEADER)
+    for i, name in enumerate(names):
+        if used[i]:
+            lines += ["%s\t%d\t%d\t%.17g\t%.17g" % (name, (j + 1) * step, reads[i], float(curve[i, j, 0]), float(curve[i, j, 1]))
+                      for j in range(min(curve.shape[1], reads[i] // step))]
+    return "\n".join(lines) + "\n"
+
+
+def read_rarefy_tsv(path: str):
+    """(rows, info): rows a list of (name, k, reads, pd, rooted_pd) in file order, and {"samples", "used", "step", "depths",
+    "unused": names}."""
+    with open(path, newline="") as fh:
+        head = re.fullmatch(r"# epik_amd rarefy v1  samples=(\d+) used=(\d+) step=(\d+) depths=(\d+)", fh.readline().rstrip("\n"))
+        if not head:
+            raise ValueError(f"{path}: not a cohort rarefy file")
+        info = dict(zip(("samples", "used", "step", "depths"), (int(x) for x in head.groups())))
+        info["unused"] = []
+        line = fh.readline().rstrip("\n")
+        while line.startswith("# unused\t"):
+            info["unused"].append(line.split("\t", 1)[1])
+            line = fh.readline().rstrip("\n")
+        if line != RAREFY_HEADER:
+            raise ValueError(f"{path}: not a cohort rarefy file")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    if any(len(r) != 5 for r in rows) or len(info["unused"]) != info["samples"] - info["used"]:
+        raise ValueError(f"{path}: the rows do not follow the first line's counts")
+    return [(r[0], int(r[1]), int(r[2]), float(r[3]), float(r[4])) for r in rows], info
 
 
 def read_samples_tsv(path: str):

@@ -1,4 +1,4 @@
-// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip and kmeans_place.hip share of a device cohort: the object
+// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, kmeans_place.hip and diversity_place.hip share of a device cohort: the object
 // itself and the launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering and the
 // edge principal components start from.
 #ifndef EPIK_AMD_COHORT_DEVICE_HPP
@@ -28,6 +28,11 @@ struct epik_amd_cohort {
     void *d_epca = nullptr;
     // the workspace of the phylogenetic k-means, allocated by the first kmeans_device (kmeans_place.hip):
     void *d_kmeans = nullptr;
+    // the workspace of the alpha diversity and the rarefaction curves (diversity_place.hip): the counts and the alpha
+    // partials, allocated by the first alpha_device or rarefy_device; the curve's partials, for rarefy_depths depths
+    void *d_diversity = nullptr;
+    void *d_rarefy = nullptr;
+    uint32_t rarefy_depths = 0;
 };
 
 namespace epik_amd {

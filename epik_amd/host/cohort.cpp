@@ -411,6 +411,162 @@ int kmeans_clusters(const uint64_t* mass, uint32_t num_samples, uint32_t num_bra
     return EPIK_AMD_OK;
 }
 
+namespace {
+
+constexpr size_t kDiversityBlock = EPIK_AMD_DIVERSITY_BLOCK;
+
+// first[] and the lengths as make_planes checks them, and half[b] = 0.5 * bl[b]
+int check_tree_lengths(size_t N, const uint32_t* first, const double* branch_length, std::vector<double>& half, std::string& err)
+{
+    half.assign(N, 0.0);
+    for (size_t b = 0; b < N; ++b) {
+        if (first[b] > b) {
+            err = "branch " + std::to_string(b) + ": first[b] = " + std::to_string(first[b]) + " is above the branch";
+            return EPIK_AMD_ERR_INVALID;
+        }
+        if (!(branch_length[b] >= 0.0) || !std::isfinite(branch_length[b])) {
+            err = "branch " + std::to_string(b) + ": the branch length is negative or not finite";
+            return EPIK_AMD_ERR_INVALID;
+        }
+        half[b] = 0.5 * branch_length[b];
+    }
+    return EPIK_AMD_OK;
+}
+
+// the rule's blocked sum: the terms of a block in ascending b, then the blocks in ascending g
+struct blocked_sum {
+    double acc = 0.0, block = 0.0;
+    void add(size_t b, double term)
+    {
+        block = block + term;
+        if ((b + 1) % kDiversityBlock == 0) close();
+    }
+    void close() { acc = acc + block, block = 0.0; }
+    double result(size_t N)
+    {
+        if (N % kDiversityBlock != 0) close();  // the ragged last block
+        return acc;
+    }
+};
+
+inline double balance(double d)
+{
+    const double w = std::min(d, 1.0 - d);
+    return w > 0.0 ? w : 0.0;
+}
+
+}  // namespace
+
+int alpha_indices(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                  const double* branch_length, epik_amd_alpha* alpha, std::string& err)
+{
+    const size_t S = num_samples, N = num_branches;
+    std::vector<double> half;
+    if (const int rc = check_tree_lengths(N, first, branch_length, half, err); rc != EPIK_AMD_OK) return rc;
+    std::vector<uint64_t> prefix(N + 1);
+    for (size_t s = 0; s < S; ++s) {
+        const uint64_t* m = mass + s * N;
+        prefix[0] = 0;
+        for (size_t b = 0; b < N; ++b) prefix[b + 1] = prefix[b] + m[b];
+        const uint64_t total = prefix[N];
+        if (total == 0) {
+            alpha[s] = epik_amd_alpha{-1.0, -1.0, -1.0, -1.0, -1.0};
+            continue;
+        }
+        const double T = (double)total;
+        blocked_sum pd, rooted, bw_half, bw_one, quadratic;
+        for (size_t b = 0; b < N; ++b) {
+            const uint64_t clade = prefix[b + 1] - prefix[first[b]], below = clade - m[b];
+            const double C = (double)clade / T, B = (double)below / T, h = half[b];
+            const double wb = balance(B), wc = balance(C);
+            pd.add(b, h * ((below > 0 && below < total ? 1.0 : 0.0) + (clade > 0 && clade < total ? 1.0 : 0.0)));
+            rooted.add(b, h * ((below > 0 ? 1.0 : 0.0) + (clade > 0 ? 1.0 : 0.0)));
+            bw_half.add(b, h * (std::sqrt(2.0 * wb) + std::sqrt(2.0 * wc)));
+            bw_one.add(b, h * (2.0 * wb + 2.0 * wc));
+            quadratic.add(b, h * (B * (1.0 - B) + C * (1.0 - C)));
+        }
+        alpha[s] = epik_amd_alpha{pd.result(N), rooted.result(N), bw_half.result(N), bw_one.result(N), quadratic.result(N)};
+    }
+    return EPIK_AMD_OK;
+}
+
+int rarefy_depths_valid(uint32_t depth_step, uint32_t num_depths, std::string& err)
+{
+    if (depth_step < 1 || depth_step > EPIK_AMD_RAREFY_MAX_DEPTH) {
+        err = "depth_step = " + std::to_string(depth_step) + " is outside [1, 2^20]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if (num_depths < 1 || num_depths > EPIK_AMD_RAREFY_MAX_DEPTHS) {
+        err = "num_depths = " + std::to_string(num_depths) + " is outside [1, 256]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if ((uint64_t)depth_step * num_depths > EPIK_AMD_RAREFY_MAX_DEPTH) {
+        err = "num_depths * depth_step = " + std::to_string((uint64_t)depth_step * num_depths) + " is above 2^20, the deepest depth";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    return EPIK_AMD_OK;
+}
+
+int rarefy_curves(const uint64_t* best, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                  const double* branch_length, uint32_t depth_step, uint32_t num_depths, double* curve, std::string& err)
+{
+    const size_t S = num_samples, N = num_branches, J = num_depths;
+    if (const int rc = rarefy_depths_valid(depth_step, num_depths, err); rc != EPIK_AMD_OK) return rc;
+    std::vector<double> half;
+    if (const int rc = check_tree_lengths(N, first, branch_length, half, err); rc != EPIK_AMD_OK) return rc;
+    std::vector<uint64_t> prefix(N + 1), side(4 * N);
+    std::vector<double> value(4 * N), factor(4 * N), recip(depth_step);
+    std::vector<blocked_sum> sums(2 * J);
+    constexpr size_t kTile = 1024;
+    for (size_t s = 0; s < S; ++s) {
+        const uint64_t* m = best + s * N;
+        double* out = curve + s * J * 2;
+        std::fill(out, out + 2 * J, -1.0);
+        prefix[0] = 0;
+        for (size_t b = 0; b < N; ++b) prefix[b + 1] = prefix[b] + m[b];
+        const uint64_t n = prefix[N];
+        if (n == 0 || n >= (1ull << 53)) continue;  // not rarefiable
+        const size_t depths = (size_t)std::min<uint64_t>(J, n / depth_step);  // the j with k_j <= n
+        if (depths == 0) continue;
+        // the four sides of every branch, side by side: below, all but below, clade, all but clade.  value = Q(side, k) and
+        // factor = (double)(n - side - k), kept by subtracting 1.0 (exact below 2^53: the bits of the conversion).  A side
+        // with side >= n starts at the factor +0.0, every other side reaches it at k = n - side: the product is a zero from
+        // then on, as the rule says, whose sign cannot reach an output; |value| is taken all the same.  The empty side,
+        // exactly 1 by the rule, is picked at the output.  One pass over the sides per depth, nothing carried from side to
+        // side: the compiler may take several at a time, each operation still rounded on its own.
+        for (size_t b = 0; b < N; ++b) {
+            const uint64_t cc = prefix[b + 1] - prefix[first[b]], cb = cc - m[b];
+            side[b] = cb, side[N + b] = n - cb, side[2 * N + b] = cc, side[3 * N + b] = n - cc;
+        }
+        for (size_t i = 0; i < 4 * N; ++i) value[i] = 1.0, factor[i] = side[i] < n ? (double)(n - side[i]) : 0.0;
+        std::fill(sums.begin(), sums.end(), blocked_sum{});
+        const auto chance = [&](size_t i) { return side[i] == 0 ? 1.0 : std::fabs(value[i]); };
+        uint64_t k = 0;
+        for (size_t j = 0; j < depths; ++j) {
+            for (size_t i = 0; i < depth_step; ++i) recip[i] = 1.0 / (double)(n - k - i);  // r_k of the depths up to k_j
+            for (size_t tile = 0; tile < 4 * N; tile += kTile) {  // (a tile of sides stays in the first-level cache)
+                double *__restrict__ q = value.data() + tile, *__restrict__ f = factor.data() + tile;
+                const size_t count = std::min(kTile, 4 * N - tile);
+                for (size_t step = 0; step < depth_step; ++step) {
+                    const double r = recip[step];
+                    for (size_t i = 0; i < count; ++i) q[i] = (q[i] * f[i]) * r, f[i] = f[i] - 1.0;
+                }
+            }
+            k += depth_step;
+            for (size_t b = 0; b < N; ++b) {
+                const double ru_b = 1.0 - chance(b), ru_c = 1.0 - chance(2 * N + b);
+                double uu_b = ru_b - chance(N + b), uu_c = ru_c - chance(3 * N + b);
+                if (!(uu_b > 0.0)) uu_b = 0.0;
+                if (!(uu_c > 0.0)) uu_c = 0.0;
+                sums[2 * j].add(b, half[b] * (uu_b + uu_c));
+                sums[2 * j + 1].add(b, half[b] * (ru_b + ru_c));
+            }
+            out[2 * j] = sums[2 * j].result(N), out[2 * j + 1] = sums[2 * j + 1].result(N);
+        }
+    }
+    return EPIK_AMD_OK;
+}
+
 std::vector<cohort_sample> read_cohort_list(const std::string& list_file)
 {
     std::ifstream in(list_file);
@@ -622,6 +778,43 @@ std::string format_kmeans_centroids_tsv(const double* centroids, uint32_t num_br
     for (size_t k = 0; k < info.clusters; ++k)
         for (size_t b = 0; b < N; ++b)
             if (centroids[k * N + b] != 0.0) out += std::to_string(k) + '\t' + std::to_string(b) + '\t' + g17(centroids[k * N + b]) + '\n';
+    return out;
+}
+
+std::string format_alpha_tsv(const std::vector<cohort_sample>& samples, const epik_amd_alpha* alpha)
+{
+    const size_t S = samples.size();
+    size_t used = 0;
+    for (size_t s = 0; s < S; ++s) used += alpha[s].pd != -1.0;
+    std::string out = "# epik_amd alpha v1  samples=" + std::to_string(S) + " used=" + std::to_string(used) + "\n";
+    for (size_t s = 0; s < S; ++s)
+        if (alpha[s].pd == -1.0) out += "# unused\t" + samples[s].name + "\n";
+    out += "name\tpd\trooted_pd\tbwpd_0.5\tbwpd_1\tquadratic_entropy\n";
+    for (size_t s = 0; s < S; ++s)
+        if (alpha[s].pd != -1.0)
+            out += samples[s].name + '\t' + g17(alpha[s].pd) + '\t' + g17(alpha[s].rooted_pd) + '\t' + g17(alpha[s].bwpd_half) + '\t' +
+                   g17(alpha[s].bwpd_one) + '\t' + g17(alpha[s].quadratic) + '\n';
+    return out;
+}
+
+std::string format_rarefy_tsv(const std::vector<cohort_sample>& samples, const uint64_t* reads, uint32_t depth_step,
+                              uint32_t num_depths, const double* curve)
+{
+    const size_t S = samples.size(), J = num_depths;
+    const auto rarefiable = [&](size_t s) { return reads[s] != 0 && reads[s] < (1ull << 53); };
+    size_t used = 0;
+    for (size_t s = 0; s < S; ++s) used += rarefiable(s);
+    std::string out = "# epik_amd rarefy v1  samples=" + std::to_string(S) + " used=" + std::to_string(used) +
+                      " step=" + std::to_string(depth_step) + " depths=" + std::to_string(J) + "\n";
+    for (size_t s = 0; s < S; ++s)
+        if (!rarefiable(s)) out += "# unused\t" + samples[s].name + "\n";
+    out += "name\tk\treads\tpd\trooted_pd\n";
+    for (size_t s = 0; s < S; ++s) {
+        if (!rarefiable(s)) continue;
+        for (size_t j = 0; j < J && (uint64_t)(j + 1) * depth_step <= reads[s]; ++j)
+            out += samples[s].name + '\t' + std::to_string((uint64_t)(j + 1) * depth_step) + '\t' + std::to_string(reads[s]) + '\t' +
+                   g17(curve[(s * J + j) * 2]) + '\t' + g17(curve[(s * J + j) * 2 + 1]) + '\n';
+    }
     return out;
 }
 

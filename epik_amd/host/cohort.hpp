@@ -63,6 +63,21 @@ int kmeans_clusters(const uint64_t* mass, uint32_t num_samples, uint32_t num_bra
                     const double* branch_length, uint32_t num_clusters, uint32_t max_iterations, epik_amd_kmeans_sample* samples,
                     epik_amd_kmeans_cluster* clusters, double* centroids, epik_amd_kmeans_info* info, std::string& err);
 
+/// Alpha diversity by the rule (include/epik_amd.h): alpha[S], every record written.  The code behind
+/// epik_amd_cohort_alpha_host; libepik_amd's kernels (diversity_place.hip) give the same bits.  0, or EPIK_AMD_ERR_INVALID
+/// with `err` naming the branch whose first[] is above it or whose length is negative or not finite.
+int alpha_indices(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                  const double* branch_length, epik_amd_alpha* alpha, std::string& err);
+
+/// depth_step >= 1, num_depths in [1, 256] and num_depths * depth_step <= 2^20: 0, or EPIK_AMD_ERR_INVALID with `err`
+int rarefy_depths_valid(uint32_t depth_step, uint32_t num_depths, std::string& err);
+
+/// Rarefaction curves by the rule (include/epik_amd.h) from best[S][N]: curve[S][J][2], every cell written.  The code
+/// behind epik_amd_cohort_rarefy_host; the kernels of diversity_place.hip give the same bits.  Errors as alpha_indices,
+/// and the depths as rarefy_depths_valid.
+int rarefy_curves(const uint64_t* best, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                  const double* branch_length, uint32_t depth_step, uint32_t num_depths, double* curve, std::string& err);
+
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
 /// name or path, a name given before, or a file that cannot be read; and for a list without any sample.
@@ -72,7 +87,7 @@ struct cohort_sample {
 std::vector<cohort_sample> read_cohort_list(const std::string& list_file);
 
 /// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash | epca | epca_edges | kmeans |
-/// kmeans_centroids
+/// kmeans_centroids | alpha | rarefy
 std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir,
                                  const std::string& extension = ".tsv");
 
@@ -107,6 +122,15 @@ std::string format_epca_edges_tsv(const std::vector<uint32_t>& first, const doub
 std::string format_kmeans_tsv(const std::vector<cohort_sample>& samples, const epik_amd_kmeans_sample* records,
                               const epik_amd_kmeans_cluster* clusters, const epik_amd_kmeans_info& info);
 std::string format_kmeans_centroids_tsv(const double* centroids, uint32_t num_branches, const epik_amd_kmeans_info& info);
+/// cohort_alpha .tsv: "# epik_amd alpha v1  samples=S used=L", a "# unused<TAB>name" line per sample without mass
+/// (pd == -1.0), the column names name pd rooted_pd bwpd_0.5 bwpd_1 quadratic_entropy, then a line per used sample in
+/// list order; doubles %.17g.
+std::string format_alpha_tsv(const std::vector<cohort_sample>& samples, const epik_amd_alpha* alpha);
+/// cohort_rarefy .tsv: "# epik_amd rarefy v1  samples=S used=L step=STEP depths=J", a "# unused<TAB>name" line per sample
+/// that is not rarefiable (reads[s] = n_s is 0 or >= 2^53), the column names name k reads pd rooted_pd, then, long format,
+/// a line for every used sample and every k_j <= n_s from curve[S][J][2]; doubles %.17g.
+std::string format_rarefy_tsv(const std::vector<cohort_sample>& samples, const uint64_t* reads, uint32_t depth_step,
+                              uint32_t num_depths, const double* curve);
 /// `text` into `filename` through `filename`.part, renamed when all of it is written
 void write_through_part(const std::string& filename, const std::string& text);
 

@@ -10,6 +10,9 @@
 //   cohort_test kmeans <out.bin> <in.bin> <K> <max_iterations>
 //                                           the phylogenetic k-means of a `kr` input: epik_amd_kmeans_sample [S],
 //                                           epik_amd_kmeans_cluster [K], float64 centroids[K][N], then epik_amd_kmeans_info
+//   cohort_test alpha <out.bin> <in.bin>    the alpha diversity of a `kr` input: epik_amd_alpha [S]
+//   cohort_test rarefy <out.bin> <in.bin> <depth_step> <num_depths>
+//                                           the rarefaction curves of a `kr` input whose cells are `best`: float64 [S][J][2]
 // An `add` input holds, little endian: uint64 n, keep, num_branches, num_samples; epik_amd_placement rows[n][keep];
 // uint32 n_rows[n]; uint32 kmer_counts[n][keep]; uint32 weights[n]; uint32 samples[n].
 // A `kr` input: uint64 num_samples, num_branches; uint64 mass[S][N]; uint32 first[N]; float64 branch_length[N].
@@ -162,8 +165,40 @@ int main(int argc, char** argv)
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }
+        if ((argc == 4 && std::strcmp(argv[1], "alpha") == 0) || (argc == 6 && std::strcmp(argv[1], "rarefy") == 0)) {
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto cells = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const auto length = read_array<double>(in, N);
+            std::string err;
+            std::ofstream out;
+            if (argc == 4) {
+                std::vector<epik_amd_alpha> alpha(S);
+                if (epik_amd::alpha_indices(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), length.data(), alpha.data(), err) != 0)
+                    throw std::runtime_error(err);
+                out.open(argv[2], std::ios::binary);
+                write_array(out, alpha.data(), alpha.size());
+            } else {
+                const unsigned long step = std::stoul(argv[4]), depths = std::stoul(argv[5]);
+                if (step > 0xfffffffful || depths > 0xfffffffful) throw std::runtime_error("depth_step and num_depths must fit 32 bits");
+                if (epik_amd::rarefy_depths_valid((uint32_t)step, (uint32_t)depths, err) != 0) throw std::runtime_error(err);
+                std::vector<double> curve(S * depths * 2);
+                if (epik_amd::rarefy_curves(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), length.data(), (uint32_t)step,
+                                            (uint32_t)depths, curve.data(), err) != 0)
+                    throw std::runtime_error(err);
+                out.open(argv[2], std::ios::binary);
+                write_array(out, curve.data(), curve.size());
+            }
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
         std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin> | squash <out.bin> <in.bin> | "
-                     "epca <out.bin> <in.bin> <K> | kmeans <out.bin> <in.bin> <K> <max_iterations>\n";
+                     "epca <out.bin> <in.bin> <K> | kmeans <out.bin> <in.bin> <K> <max_iterations> | alpha <out.bin> <in.bin> | "
+                     "rarefy <out.bin> <in.bin> <depth_step> <num_depths>\n";
         return 2;
     } catch (const std::exception& error) {
         std::cerr << "Error: " << error.what() << std::endl;

@@ -231,6 +231,13 @@ const char* kHelp =
     "                          k-means (Czech et al. 2019) on the device and write cohort_kmeans_<list>.tsv (the clusters and\n"
     "                          every sample's cluster and distance) and cohort_kmeans_centroids_<list>.tsv (the centroids' masses)\n"
     "      --cohort-kmeans-iterations arg  With --cohort-kmeans: the most iterations, in [1, 1000] (default: 100)\n"
+    "      --cohort-alpha      With --cohort: also compute the alpha diversity of every sample (McCoy & Matsen 2013: PD, rooted PD,\n"
+    "                          balance-weighted PD at 0.5 and 1, quadratic entropy) on the device and write cohort_alpha_<list>.tsv\n"
+    "      --cohort-rarefy arg With --cohort: also compute every sample's rarefaction curve (Nipperess & Matsen 2013: the expected\n"
+    "                          PD and rooted PD of k reads drawn without replacement) up to depth arg, in [1, 1048576], on the\n"
+    "                          device and write cohort_rarefy_<list>.tsv\n"
+    "      --cohort-rarefy-step arg  With --cohort-rarefy: the distance between two depths (default: max(1, ceil(depth / 64)));\n"
+    "                          floor(depth / step) must lie in [1, 256]\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -271,7 +278,7 @@ options parse_args(int argc, char** argv)
         } else {
             continue;  // positional arguments are ignored (epik.py passes the query twice, epik.py:88,96)
         }
-        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca") && !have_value)) {  // flags
+        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca" || name == "cohort-alpha") && !have_value)) {  // flags
             opt.values[name] = "1";
             continue;
         }
@@ -412,6 +419,34 @@ int main(int argc, char** argv)
             };
             kmeans_clusters = whole_number("cohort-kmeans", "", EPIK_AMD_KMEANS_MAX_CLUSTERS);
             kmeans_iterations = whole_number("cohort-kmeans-iterations", "100", EPIK_AMD_KMEANS_MAX_ITERATIONS);
+        }
+        const bool with_alpha = parsed.has("cohort-alpha"), with_rarefy = parsed.has("cohort-rarefy");
+        if (with_alpha && !with_cohort) throw std::runtime_error("--cohort-alpha needs --cohort (it measures the samples of the list)");
+        if (with_rarefy && !with_cohort) throw std::runtime_error("--cohort-rarefy needs --cohort (it rarefies the samples of the list)");
+        if (parsed.has("cohort-rarefy-step") && !with_rarefy)
+            throw std::runtime_error("--cohort-rarefy-step needs --cohort-rarefy (the flag that computes the curves)");
+        uint32_t rarefy_step = 0, rarefy_depths = 0;
+        if (with_rarefy) {
+            const auto whole_number = [&](const std::string& flag, const std::string& text) {
+                size_t used = 0;
+                unsigned long v = 0;
+                try {
+                    v = std::stoul(text, &used);
+                } catch (const std::exception&) {
+                    used = 0;
+                }
+                if (used != text.size() || used == 0 || text[0] == '-' || v < 1 || v > EPIK_AMD_RAREFY_MAX_DEPTH)
+                    throw std::runtime_error("--" + flag + " must be a whole number in [1, 1048576], not '" + text + "'");
+                return (uint32_t)v;
+            };
+            const uint32_t deepest = whole_number("cohort-rarefy", parsed.get("cohort-rarefy", ""));
+            rarefy_step = std::max(1u, (deepest + 63) / 64);
+            if (parsed.has("cohort-rarefy-step")) rarefy_step = whole_number("cohort-rarefy-step", parsed.get("cohort-rarefy-step", ""));
+            rarefy_depths = deepest / rarefy_step;
+            if (rarefy_depths < 1 || rarefy_depths > EPIK_AMD_RAREFY_MAX_DEPTHS)
+                throw std::runtime_error("--cohort-rarefy-step " + std::to_string(rarefy_step) + " gives floor(" + std::to_string(deepest) +
+                                         " / " + std::to_string(rarefy_step) + ") = " + std::to_string(rarefy_depths) +
+                                         " depths of --cohort-rarefy: the number must lie in [1, 256]");
         }
         if (with_cohort) {
             for (const char* other : {"mates", "profile-only", "profile", "assign"})
@@ -768,6 +803,8 @@ int main(int argc, char** argv)
         const auto cohort_epca_edges_filename = epik_amd::make_cohort_filename("epca_edges", query_file, output_dir);
         const auto cohort_kmeans_filename = epik_amd::make_cohort_filename("kmeans", query_file, output_dir);
         const auto cohort_kmeans_centroids_filename = epik_amd::make_cohort_filename("kmeans_centroids", query_file, output_dir);
+        const auto cohort_alpha_filename = epik_amd::make_cohort_filename("alpha", query_file, output_dir);
+        const auto cohort_rarefy_filename = epik_amd::make_cohort_filename("rarefy", query_file, output_dir);
         bool epca_converged = true, kmeans_converged = true;
         if (with_cohort) {
             // the handles' cohorts summed on the first device, read once, and the distances computed there
@@ -779,8 +816,11 @@ int main(int argc, char** argv)
             epca.num_components = epca_components;
             epik_amd::placer::cohort_kmeans kmeans;
             kmeans.num_clusters = kmeans_clusters, kmeans.max_iterations = kmeans_iterations;
+            epik_amd::placer::cohort_diversity diversity;
+            diversity.with_alpha = with_alpha, diversity.depth_step = rarefy_step, diversity.num_depths = rarefy_depths;
             placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
-                               with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr, with_kmeans ? &kmeans : nullptr);
+                               with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr, with_kmeans ? &kmeans : nullptr,
+                               with_alpha || with_rarefy ? &diversity : nullptr);
             epik_amd::write_through_part(cohort_samples_filename, epik_amd::format_cohort_samples_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_profile_filename, epik_amd::format_cohort_profile_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_kr_filename, epik_amd::format_cohort_kr_tsv(cohort_samples, kr));
@@ -804,6 +844,15 @@ int main(int argc, char** argv)
                                              epik_amd::format_kmeans_centroids_tsv(kmeans.centroids.data(), (uint32_t)cohort.num_branches,
                                                                                    kmeans.info));
                 kmeans_converged = kmeans.info.converged != 0;
+            }
+            if (with_alpha)
+                epik_amd::write_through_part(cohort_alpha_filename, epik_amd::format_alpha_tsv(cohort_samples, diversity.alpha.data()));
+            if (with_rarefy) {
+                std::vector<uint64_t> reads(cohort_samples.size(), 0);  // (n_s, the sum wrapping as the rule's)
+                for (size_t s = 0; s < reads.size(); ++s)
+                    for (size_t b = 0; b < cohort.num_branches; ++b) reads[s] += cohort.best[s * cohort.num_branches + b];
+                epik_amd::write_through_part(cohort_rarefy_filename, epik_amd::format_rarefy_tsv(cohort_samples, reads.data(), rarefy_step,
+                                                                                                 rarefy_depths, diversity.curve.data()));
             }
             if (with_squash) {
                 epik_amd::write_through_part(cohort_squash_filename,
@@ -850,6 +899,8 @@ int main(int argc, char** argv)
         if (!kmeans_converged)
             std::cout << "Warning: the phylogenetic k-means did not converge in " << kmeans_iterations
                       << " iterations (converged=0 in " << cohort_kmeans_filename << ")" << std::endl;
+        if (with_alpha) std::cout << "Cohort alpha diversity: " << cohort_alpha_filename << std::endl;
+        if (with_rarefy) std::cout << "Cohort rarefaction curves: " << cohort_rarefy_filename << std::endl;
         if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;
         if (strands_out.is_open()) {
             strands_out.close();

@@ -34,6 +34,8 @@
 #pragma weak epik_amd_cohort_squash
 #pragma weak epik_amd_cohort_epca
 #pragma weak epik_amd_cohort_kmeans
+#pragma weak epik_amd_cohort_alpha
+#pragma weak epik_amd_cohort_rarefy
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -238,8 +240,11 @@ void placer::set_cohort(uint32_t num_samples)
 }
 
 void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
-                         epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans)
+                         epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans,
+                         cohort_diversity* diversity)
 {
+    if (diversity && (!&epik_amd_cohort_alpha || !&epik_amd_cohort_rarefy))
+        throw std::runtime_error("GPU placer: this libepik_amd has no alpha diversity and rarefaction");
     if (kmeans && !&epik_amd_cohort_kmeans) throw std::runtime_error("GPU placer: this libepik_amd has no phylogenetic k-means");
     if (num_merges && !&epik_amd_cohort_squash) throw std::runtime_error("GPU placer: this libepik_amd has no squash clustering");
     if (epca && !&epik_amd_cohort_epca) throw std::runtime_error("GPU placer: this libepik_amd has no edge principal components");
@@ -285,6 +290,15 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
         kmeans->centroids.assign(K * N, 0.0);
         rc = epik_amd_cohort_kmeans(_cohorts[0], tree, length.data(), kmeans->num_clusters, kmeans->max_iterations,
                                     kmeans->samples.data(), kmeans->clusters.data(), kmeans->centroids.data(), &kmeans->info);
+    }
+    if (rc == EPIK_AMD_OK && diversity && diversity->with_alpha) {
+        diversity->alpha.assign(_cohort_samples, epik_amd_alpha{});
+        rc = epik_amd_cohort_alpha(_cohorts[0], tree, length.data(), diversity->alpha.data());
+    }
+    if (rc == EPIK_AMD_OK && diversity && diversity->num_depths) {
+        diversity->curve.assign((size_t)_cohort_samples * diversity->num_depths * 2, 0.0);
+        rc = epik_amd_cohort_rarefy(_cohorts[0], tree, length.data(), diversity->depth_step, diversity->num_depths,
+                                    diversity->curve.data());
     }
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);

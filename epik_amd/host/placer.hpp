@@ -183,9 +183,18 @@ public:
         std::vector<double> centroids;
         epik_amd_kmeans_info info{};
     };
+    /// With `diversity` (--cohort-alpha, --cohort-rarefy): with_alpha asks for the alpha indices, alpha of num_samples
+    /// records on return; num_depths > 0 asks for the rarefaction curves at the depths j * depth_step, curve of
+    /// num_samples * num_depths * 2 values on return.
+    struct cohort_diversity {
+        bool with_alpha = false;
+        uint32_t depth_step = 0, num_depths = 0;
+        std::vector<epik_amd_alpha> alpha;
+        std::vector<double> curve;
+    };
     void read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                      epik_amd_squash_merge* merges = nullptr, uint32_t* num_merges = nullptr, cohort_epca* epca = nullptr,
-                     cohort_kmeans* kmeans = nullptr);
+                     cohort_kmeans* kmeans = nullptr, cohort_diversity* diversity = nullptr);
     /// The profiles of all devices read back and summed; `mass` and `best` of num_branches cells each.
     void read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_totals& totals) const;
     /// distal_length / pendant_length of a placement on branch b (place.cpp:110-123, 435-437)

@@ -763,6 +763,43 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *     centroids[K][N] = centroid_k.C[b] - centroid_k.B[b], the centroid's own mass on b, +0.0 for k >= K'.
  *     info = {used L, clusters K', iterations, converged}.  Every cell of every output is written.
  *
+ * Alpha diversity and rarefaction (McCoy & Matsen 2013; Nipperess & Matsen 2013) of the cohort's samples: how diverse
+ *   each sample is, and whether it was sequenced deeply enough to say.  From mass[S][N] (the indices), best[S][N] (the
+ *   curve), first[N] and branch_length[N] as for the KR distance.  All arithmetic is IEEE double, every operation rounded
+ *   on its own, nothing fused; + - * /, sqrt (correctly rounded), min and comparisons only.  Denormals take part as IEEE
+ *   says.  Phylogenetic entropy (-D log D) and BWPD at a general theta are deliberately left out: no log or pow gives
+ *   the same bits in the kernels, on the host and in numpy.
+ *   Blocked sum BS(t) over the branches, EPIK_AMD_DIVERSITY_BLOCK = 256: block g covers b = 256 g .. min(256 g + 255,
+ *     N - 1); p_g = acc after those b in ascending order, acc = acc + t[b], acc = +0.0 at first; BS = acc after g
+ *     ascending, acc = acc + p_g, from +0.0.  A fixed order, as the sequential one is; blocked because here the branches,
+ *     not the pairs, are the parallelism (64 samples must still fill the device).  An implementation may share out the
+ *     samples, the blocks and the depths, never the branches of one block or the blocks of one sum.
+ *   half[b] = 0.5 * bl[b].  A placement sits at the middle of its branch, so a branch is two half branches: the distal
+ *     one with `below` on its far side, the proximal one with `clade`.
+ *   Alpha indices, from mass.  T_s, clade_s[b], below_s[b], C_s[b], B_s[b] are exactly those of the KR rule.  For a half
+ *     branch with the integer x (below or clade) and D (B or C):
+ *       u(x) = 1.0 iff 0 < x < T_s (integer compare), else +0.0        r(x) = 1.0 iff x > 0, else +0.0
+ *       w(D) = min(D, 1.0 - D), replaced by +0.0 unless w > 0.0
+ *       h(D) = sqrt(2.0 * w)        l(D) = 2.0 * w        e(D) = D * (1.0 - D)
+ *     For each f of the five, term_f[b] = half[b] * (f(distal) + f(proximal)), and
+ *       alpha[s] = {pd = BS(term_u), rooted_pd = BS(term_r), bwpd_half = BS(term_h), bwpd_one = BS(term_l),
+ *                   quadratic = BS(term_e)};      T_s == 0: all five are -1.0.
+ *     With cells that wrapped the values mean nothing, but they are still these bits.
+ *   Rarefaction, from best (every read a unit mass at its best branch, as guppy rarefact takes it).  In uint64, wrapping:
+ *       n_s = sum over b of best[s][b],   cc_s[b] = sum over x = first[b] .. b of best[s][x],   cb_s[b] = cc_s[b] - best[s][b].
+ *     A sample is rarefiable iff 0 < n_s < 2^53.  Parameters: depth_step >= 1, num_depths J in [1, 256],
+ *     J * depth_step <= 2^20; the depths are k_j = j * depth_step, j = 1 .. J.  Per sample (n = n_s) and integer m:
+ *       Q(m, 0) = 1.0, and for k = 0, 1, ...: Q(m, k + 1) =
+ *         +1.0 if m == 0 (an empty side gives exactly 1, not a product of roundings);
+ *         +0.0 if m >= n - k (uint64 compare);
+ *         (Q(m, k) * (double)(n - m - k)) * r_k otherwise, r_k = 1.0 / (double)(n - k).
+ *     That is C(n - m, k) / C(n, k): the chance that none of k reads drawn without replacement is one of the m.
+ *     For k_j <= n_s and each half branch x in {cb, cc}: miss = Q(x, k_j), all = Q(n - x, k_j) (the subtraction wraps),
+ *       ru = 1.0 - miss,   uu = (1.0 - miss) - all, replaced by +0.0 unless uu > 0.0,
+ *       term_u[b] = half[b] * (uu(cb) + uu(cc)),   term_r[b] the same with ru,
+ *       curve[s][j] = {BS(term_u), BS(term_r)}: the expected unrooted and rooted PD of k_j reads.
+ *     k_j > n_s, or a sample that is not rarefiable: {-1.0, -1.0}.  Every cell of every output is written.
+ *
  * An epik_amd_cohort is an object of its own, created for a placer's device, num_branches and keep_at_most (whole
  * databases only, not a k-mer-space shard) and num_samples >= 1; all zero at create() and after reset().
  *   add_device  asynchronous on `stream`, allocates nothing: as epik_amd_profile_add_device, with d_samples (uint32 [n],
@@ -797,6 +834,16 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *               each time); the results are enqueued on `stream`.  The cells are not changed.
  *               kmeans: the same into host memory, synchronous.
  *   kmeans_host the rule on the host from mass[S][N] and first[N], no device; first[b] > b is refused.
+ *   alpha_device  checks the tree and the lengths as kr_device; the first alpha_device or rarefy_device allocates a
+ *               workspace of its own, kept until destroy(): 16 * S * N + 8 * S bytes (cb, cc and n_s) and
+ *               8 * S * ceil(N / 256) * max(5, 2 * 256) bytes of block partials.  d_alpha is epik_amd_alpha [S] in device
+ *               memory, every cell written.  Once enqueued on `stream` it needs no readback.  The cells are not changed.
+ *               alpha: the same into host memory, synchronous.
+ *   alpha_host  the rule on the host from mass[S][N] and first[N], no device; first[b] > b is refused.
+ *   rarefy_device  checks as alpha_device, depth_step >= 1, num_depths in [1, 256] and num_depths * depth_step <= 2^20;
+ *               d_curve is float64 [S][J][2] in device memory, every cell written.  No readback; the cells are not changed.
+ *               rarefy: the same into host memory, synchronous.
+ *   rarefy_host the rule on the host from best[S][N] and first[N], no device; first[b] > b is refused.
  * cohort_reads / _strands / _frames / _mates: the profile_* twins with samples[n] (HOST uint32) beside the weights.
  */
 typedef struct epik_amd_cohort epik_amd_cohort;
@@ -865,6 +912,26 @@ int epik_amd_cohort_kmeans_host(const uint64_t *mass, uint32_t num_samples, uint
                                 const double *branch_length, uint32_t num_clusters, uint32_t max_iterations,
                                 epik_amd_kmeans_sample *samples, epik_amd_kmeans_cluster *clusters, double *centroids,
                                 epik_amd_kmeans_info *info);
+typedef struct epik_amd_alpha {
+    double pd, rooted_pd;       /* unrooted and rooted phylogenetic diversity */
+    double bwpd_half, bwpd_one; /* balance-weighted PD at theta = 0.5 and 1 */
+    double quadratic;           /* Rao's quadratic entropy */
+} epik_amd_alpha; /* 40 bytes */
+#define EPIK_AMD_DIVERSITY_BLOCK 256u
+#define EPIK_AMD_RAREFY_MAX_DEPTHS 256u
+#define EPIK_AMD_RAREFY_MAX_DEPTH (1u << 20)
+int epik_amd_cohort_alpha_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                                 void *d_alpha, void *stream);
+int epik_amd_cohort_alpha(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                          epik_amd_alpha *alpha);
+int epik_amd_cohort_alpha_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                               const double *branch_length, epik_amd_alpha *alpha);
+int epik_amd_cohort_rarefy_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                                  uint32_t depth_step, uint32_t num_depths, void *d_curve, void *stream);
+int epik_amd_cohort_rarefy(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                           uint32_t depth_step, uint32_t num_depths, double *curve);
+int epik_amd_cohort_rarefy_host(const uint64_t *best, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                const double *branch_length, uint32_t depth_step, uint32_t num_depths, double *curve);
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n);
 int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
