@@ -58,6 +58,7 @@ EXPORTS = (
     "epik_amd_placer_plan_run_counts",
     "epik_amd_placer_run_counts",
     "epik_amd_placer_ring_form",
+    "epik_amd_placer_table_form",
     "epik_amd_placer_destroy",
     "epik_amd_placer_place",
     "epik_amd_placer_place_device",
@@ -336,6 +337,8 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_placer_run_counts.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     lib.epik_amd_placer_ring_form.restype = i32
     lib.epik_amd_placer_ring_form.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+    lib.epik_amd_placer_table_form.restype = i32
+    lib.epik_amd_placer_table_form.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
     lib.epik_amd_placer_destroy.restype = None
     lib.epik_amd_placer_destroy.argtypes = [vp]
     lib.epik_amd_placer_place.restype = i32

@@ -369,6 +369,8 @@ int create_impl(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t sh
     pp.table = p->d_table;
     pp.filter = p->d_filter;
     pp.filter_rec_bytes = plan.filter_rec_bytes;
+    pp.entry_len_bits = plan.len_bits;
+    pp.entry_cell_bits = plan.cell_bits;
     pp.postings = p->d_postings;
     pp.char_class = p->d_char_class;
     pp.sigma_pow_km1 = (uint32_t)(d->num_keys / d->alphabet_size);
@@ -1139,6 +1141,19 @@ int epik_amd_placer_ring_form(const epik_amd_placer *p, uint32_t counts, uint32_
     if (counts > (uint32_t)epik_amd::kCounts32) return fail(EPIK_AMD_ERR_INVALID, "counts must be 0, 1 or 2");
     const int ring = p->team ? 0 : p->geo[counts].ring;
     *form = ((ring & epik_amd::kRingNear) ? EPIK_AMD_RING_NEAR : 0u) | ((ring & epik_amd::kRingSlack) ? EPIK_AMD_RING_SLACK : 0u);
+    return EPIK_AMD_OK;
+}
+
+int epik_amd_placer_table_form(const epik_amd_placer *p, uint32_t *form)
+{
+    if (!p || !form) return fail(EPIK_AMD_ERR_INVALID, "null argument");
+    switch (p->layout) {
+        case epik_amd::DbLayout::kPacked:
+        case epik_amd::DbLayout::kFiltered: *form = EPIK_AMD_TABLE_BY_CODE; break;
+        case epik_amd::DbLayout::kPaired: *form = EPIK_AMD_TABLE_PAIRED; break;
+        case epik_amd::DbLayout::kTripled: *form = EPIK_AMD_TABLE_TRIPLED; break;
+        default: *form = 0u;
+    }
     return EPIK_AMD_OK;
 }
 

@@ -292,8 +292,8 @@ int decide_kernel(uint32_t num_branches, const char *forced_kernel, const char *
     }
     if (forced_layout && forced_layout[0] && std::strcmp(forced_layout, "compact") != 0 &&
         std::strcmp(forced_layout, "packed") != 0 && std::strcmp(forced_layout, "paired") != 0 &&
-        std::strcmp(forced_layout, "filtered") != 0)
-        return fail(EPIK_AMD_ERR_INVALID, "EPIK_AMD_LAYOUT must be compact, packed, paired or filtered");
+        std::strcmp(forced_layout, "filtered") != 0 && std::strcmp(forced_layout, "tripled") != 0)
+        return fail(EPIK_AMD_ERR_INVALID, "EPIK_AMD_LAYOUT must be compact, packed, paired, tripled or filtered");
     return EPIK_AMD_OK;
 }
 
@@ -343,6 +343,7 @@ WaveLayout choose_wave_layout(uint32_t alphabet_size, uint64_t num_keys, uint64_
     const bool can_pair = alphabet_size == 4, can_filter = alphabet_size <= 32;
     const bool table_fits = num_keys * 16u <= free_mem / 4;
     WaveLayout w;
+    if (forced_layout && std::strcmp(forced_layout, "tripled") == 0) forced_layout = "paired";  // (the paired image, its table re-keyed: plan_tripled)
     if (forced_layout && forced_layout[0]) {
         w.filtered = can_filter && (std::strcmp(forced_layout, "filtered") == 0 ||
                                     (!can_pair && std::strcmp(forced_layout, "paired") == 0));
@@ -355,6 +356,50 @@ WaveLayout choose_wave_layout(uint32_t alphabet_size, uint64_t num_keys, uint64_
     }
     return w;
 }
+// The tripled table in place of the paired one (db_layout.h: kTripled; place_device.hpp documents the lookup): called on a
+// finished paired plan, `lines` the 128-byte lines of its posting region.  What a database must have to TAKE it: four
+// letters, k >= 3, the whole key space (of three consecutive k-mers of a read a shard holds one as a rule), every kept list
+// a run and the near form of the run-list kernels (the only kernels instantiated for it; EPIK_AMD_RUN_COUNTS=ring and
+// EPIK_AMD_RING_FORM=far therefore keep the paired table), and entries of 42 bits.  EPIK_AMD_LAYOUT=tripled asks for it --
+// an error where the database cannot take it.  By itself it is chosen where it saves fabric traffic
+// (profiles/r08_table_traffic_bound.txt): the paired table larger than one XCD's 4 MiB of L2 -- below that its lines
+// come from L2 --, and the image not moved from inside the Infinity Cache to beyond it by the table's growth.
+constexpr uint64_t kL2BytesPerXcd = 4ull << 20;
+int plan_tripled(const char *forced_layout, uint32_t kmer_size, uint32_t num_branches, uint64_t num_keys, uint64_t lines, Plan &plan,
+                 std::string &err)
+{
+    const bool forced = forced_layout && std::strcmp(forced_layout, "tripled") == 0;
+    if (forced_layout && forced_layout[0] && !forced) return EPIK_AMD_OK;  // (another layout was asked for)
+    const char *why = nullptr;
+    const char *ring_form = std::getenv("EPIK_AMD_RING_FORM");
+    const uint32_t len_bits = bits_of(num_branches), cell_bits = bits_of(plan.n_pad - 1u);
+    if (plan.layout != DbLayout::kPaired) why = "the tripled table needs a 4-letter alphabet and the one-wavefront kernels";
+    else if (kmer_size < 3) why = "the tripled table needs k >= 3";
+    else if (plan.shard_count != 1) why = "a k-mer-space shard keeps the paired table";
+    else if (!plan.runs || !run_counts_apply(plan, std::getenv("EPIK_AMD_RUN_COUNTS")))
+        why = "the tripled table needs run-coded lists that are all runs, with counts kept per list";
+    else if (plan.posting_bytes >= kNearRegionBytes || (ring_form && std::strcmp(ring_form, "far") == 0))
+        why = "the tripled table needs the near form of the run-list ring";
+    else if (len_bits + cell_bits + bits_of(lines) > kTripledEntryBits)
+        why = "len, first cell and line of a list do not fit the 42 bits of a tripled table entry";
+    if (why) {
+        if (!forced) return EPIK_AMD_OK;
+        err = why;
+        return EPIK_AMD_ERR_UNSUPPORTED;
+    }
+    const uint64_t tripled_table = (num_keys / 4u) * 128u + 8u;
+    if (!forced) {
+        if (num_keys * 16u <= kL2BytesPerXcd) return EPIK_AMD_OK;  // (the paired table's entries: k = 9 is exactly 4 MiB and stays)
+        if (plan.table_bytes + plan.posting_bytes <= kInfinityCacheBytes && tripled_table + plan.posting_bytes > kInfinityCacheBytes)
+            return EPIK_AMD_OK;
+    }
+    plan.layout = DbLayout::kTripled;
+    plan.table_bytes = tripled_table;
+    plan.len_bits = len_bits;
+    plan.cell_bits = cell_bits;
+    return EPIK_AMD_OK;
+}
+
 // table and presence filter of the packed layouts
 void size_packed_tables(uint32_t alphabet_size, uint64_t num_keys, const WaveLayout &w, Plan &plan)
 {
@@ -387,6 +432,8 @@ int make_plan(const Source &src, size_t free_mem, const char *forced_layout, con
     KernelDecision kernel;
     if (const int rc = decide_kernel(d->num_branches, forced_kernel, forced_layout, plan, kernel, err); rc != EPIK_AMD_OK) return rc;
     const bool team = kernel.team;
+    const bool want_tripled = forced_layout && std::strcmp(forced_layout, "tripled") == 0;
+    if (team && want_tripled) return fail(EPIK_AMD_ERR_UNSUPPORTED, "the tripled table is a layout of the one-wavefront kernels");
 
     {
         Cursor all(src);
@@ -476,7 +523,7 @@ int make_plan(const Source &src, size_t free_mem, const char *forced_layout, con
     if (lines >= (1ull << 32)) return fail(EPIK_AMD_ERR_UNSUPPORTED, "posting region of 512 GiB or more");
     plan.posting_bytes = lines * 128u + 512u;
     size_packed_tables(d->alphabet_size, d->num_keys, w, plan);
-    return EPIK_AMD_OK;
+    return plan_tripled(forced_layout, d->kmer_size, d->num_branches, d->num_keys, lines, plan, err);
 }
 
 int plan_sizes(const SizeDesc &z, size_t free_mem, const char *forced_layout, const char *forced_kernel, Plan &plan,
@@ -515,6 +562,8 @@ int plan_sizes(const SizeDesc &z, size_t free_mem, const char *forced_layout, co
     if (plan.kept_entries >= (1ull << 40)) return fail(EPIK_AMD_ERR_UNSUPPORTED, "more than 2^40 postings");
     KernelDecision kernel;
     if (const int rc = decide_kernel(z.num_branches, forced_kernel, forced_layout, plan, kernel, err); rc != EPIK_AMD_OK) return rc;
+    if (kernel.team && forced_layout && std::strcmp(forced_layout, "tripled") == 0)
+        return fail(EPIK_AMD_ERR_UNSUPPORTED, "the tripled table is a layout of the one-wavefront kernels");
     if (kernel.team) {
         if (const int rc = plan_team_geometry(z.num_branches, z.keep_at_most, z.alphabet_size, z.kmer_size, num_keys, kernel, plan, err);
             rc != EPIK_AMD_OK)
@@ -571,7 +620,7 @@ int plan_sizes(const SizeDesc &z, size_t free_mem, const char *forced_layout, co
     if (lines >= (1ull << 32)) return fail(EPIK_AMD_ERR_UNSUPPORTED, "posting region of 512 GiB or more");
     plan.posting_bytes = lines * 128u + 512u;
     size_packed_tables(z.alphabet_size, num_keys, w, plan);
-    return EPIK_AMD_OK;
+    return plan_tripled(forced_layout, z.kmer_size, z.num_branches, num_keys, lines, plan, err);
 }
 
 int build(const Source &src, const Plan &plan, Sink &table, Sink *filter, Sink &postings, std::string &err)
@@ -721,7 +770,43 @@ int build(const Source &src, const Plan &plan, Sink &table, Sink *filter, Sink &
             }
         }
         postings.reserve(512);
-        if (plan.layout == DbLayout::kPaired) {
+        if (plan.layout == DbLayout::kTripled) {
+            // Block X (a (k-1)-mer, 128 bytes) holds 24 entries of 42 bits: the four codes a.X (slots 0-3), the four X.b
+            // (slots 4-7) and the sixteen Y.b.b' (slots 8 + 4 b + b'), Y = the last k-2 letters of X.  The line of a code
+            // is the number of lines of all codes in front of it: nine cursors walk the key space in step -- one per
+            // quarter (a.X), one over all codes (X.b), and one per leading letter z of X for Y.b.b', which walks the
+            // WHOLE key space while X walks the quarter z, from line 0 at the quarter's start.  No per-code array.
+            const uint64_t blocks = num_keys / 4, quarter = blocks / 4;  // 4^(k-1), 4^(k-2)
+            const uint32_t cell_shift = plan.len_bits, line_shift = plan.len_bits + plan.cell_bits;
+            RecordWriter out(table, 128, blocks);
+            uint64_t quarter_line[4] = {plan.quarter_lines[0], plan.quarter_lines[1], plan.quarter_lines[2],
+                                        plan.quarter_lines[3]};
+            uint64_t seq_line = 0, tail_line = 0;
+            Cursor quarter_at[4] = {Cursor(src), Cursor(src), Cursor(src), Cursor(src)}, seq_at(src);
+            Cursor tail_at[4] = {Cursor(src), Cursor(src), Cursor(src), Cursor(src)};
+            auto put = [&](uint8_t *block, uint32_t slot, Cursor &at, uint64_t code, uint64_t &line) {
+                uint64_t first = 0;
+                const uint64_t len = at.list(code, &first);
+                if (len == 0) return;  // an absent code: all zero
+                const uint32_t w = run_entry_word(d->values + first, len, runs, top);
+                const uint64_t e = (uint64_t)(w & 0xffffu) | ((uint64_t)(w >> 16) << cell_shift) | (line << line_shift);
+                const uint32_t bit = kTripledEntryBits * slot;
+                uint64_t have;
+                std::memcpy(&have, block + (bit >> 3), 8);
+                have |= e << (bit & 7u);
+                std::memcpy(block + (bit >> 3), &have, 8);
+                line += run_lines(d->values + first, len, runs);
+            };
+            for (uint64_t x = 0; x < blocks; ++x) {
+                uint8_t *block = out.next();
+                const uint64_t z = x / quarter, y = x % quarter;
+                if (y == 0) tail_line = 0;
+                for (uint32_t a = 0; a < 4; ++a) put(block, a, quarter_at[a], a * blocks + x, quarter_line[a]);
+                for (uint32_t b = 0; b < 4; ++b) put(block, 4 + b, seq_at, x * 4 + b, seq_line);
+                for (uint32_t bb = 0; bb < 16; ++bb) put(block, 8 + bb, tail_at[z], y * 16 + bb, tail_line);
+            }
+            table.reserve(8);
+        } else if (plan.layout == DbLayout::kPaired) {
             // Block X (a (k-1)-mer) holds the entries of the four codes a.X (slots 0-3) and the four X.b
             // (slots 4-7).  The line of a code is the number of lines of all codes in front of it: five
             // cursors walk the key space in step -- one per quarter (a.X, a fixed, X rising) and one over

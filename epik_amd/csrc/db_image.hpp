@@ -105,6 +105,8 @@ struct Plan {
     bool run_lists = false;  // packed layouts: EVERY kept list is a run (of fewer than 65536 postings)
     uint64_t quarter_lines[4] = {0, 0, 0, 0};  // paired table: posting lines in front of each quarter of the key space
     uint32_t wave_resident[3] = {0, 0, 0};     // resident waves per CU by count width (what chose the kernel)
+    // tripled table: an entry is len | first cell << len_bits | line << (len_bits + cell_bits), 42 bits in all
+    uint32_t len_bits = 0, cell_bits = 0;
     // k-mer-space shard (include/epik_amd.h): the placer keeps the lists of the codes with code % shard_count ==
     // shard_index.  The sliced table of such a placer holds an entry per code OF THE SHARD, at code / shard_count
     // (table_keys of them per pass): 1 / shard_count of the bytes, and the kernels test code % shard_count before

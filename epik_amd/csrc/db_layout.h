@@ -28,7 +28,19 @@ enum class DbLayout : int {
                      // databases): one filter word per two lookups, the table only for present codes
     kTeam = 5,       // the team kernel's layout (team_kernel.hip): every list pre-split into one
                      // sublist per slice of the branch range, a {line, len[W]} entry per code and pass
+    kTripled = 6,    // kPaired's lists; the table keyed by the (k-1)-mer X that THREE consecutive k-mers of a read
+                     // share -- a.X, X.b and X[1:].b.b' --: one table line per three lookups, a 128-byte block of
+                     // 24 entries of 42 bits per (k-1)-mer (place_device.hpp, db_image.cpp)
 };
+// the tripled table: 24 entries of kTripledEntryBits at bit kTripledEntryBits * slot of a 128-byte block (the last 16 bits 0)
+constexpr uint32_t kTripledEntryBits = 42u;
+constexpr uint32_t kTripledSlots = 24u;
+constexpr uint32_t bits_of(uint64_t v)
+{
+    uint32_t n = 0;
+    for (; v; v >>= 1) ++n;
+    return n;
+}
 
 // Width of the per-branch k-mer counts in LDS: 16 bits by default (reads of up to 32767 k-mers),
 // 32 for longer reads, 8 (reads of up to 255 k-mers) when that lets more waves share a CU.

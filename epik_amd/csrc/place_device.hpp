@@ -274,7 +274,16 @@ struct CompactLayout {
 // table entry, whose first word is then len | first cell << 16 (0: the cells are stored, as above; cell 0 is the
 // dummy row, never a posting's).  A list of 60 postings takes two 128-byte lines instead of three: a third fewer
 // lines requested per read, which is what bounds these kernels.
-enum : int { kPlainTable = 0, kPairedTable = 1, kFilteredTable = 2 };
+//
+// kTripled (4-letter alphabets, run-coded databases whose paired table is beyond L2; db_image.cpp: plan_tripled) takes the
+// pairing one step further: THREE consecutive k-mers of a read, at positions 3t, 3t+1, 3t+2, share X = read[3t+1 .. 3t+k-1]
+// -- they are a.X, X.b and X[1:].b.b' -- and block X holds all 24 codes of those forms (slots 0-3 by a, 4-7 by b,
+// 8 + 4 b + b'): one line for three lanes.  24 entries in 128 bytes leave 42 bits for one: len | first cell << len_bits |
+// line << (len_bits + cell_bits), the widths in PlaceParams, an absent code all zero, at bit 42 * slot of the block.
+// Every code is stored six times (the table is 128 bytes per (k-1)-mer), and each form alone is complete: a lane that
+// does not know the letter in front of its window (lane 0 of a tile, an invalid or ambiguous character there) looks its
+// k-mer up as a.X -- one line of its own, the right entry.
+enum : int { kPlainTable = 0, kPairedTable = 1, kFilteredTable = 2, kTripledTable = 3 };
 // kNearRuns (run-coded layouts over a posting region shorter than kNearRegionBytes, chosen at create() with the near form
 // of RunListLayout below): the chunk descriptor is the chunk's byte offset from p.postings | (cnt | first cell << 7) << 32,
 // two words a stage pulls out of the lanes instead of three prepared fields; the offset is the loads' scalar offset
@@ -308,10 +317,35 @@ struct PackedLayout {
         }
     }
     __device__ static __forceinline__ uint64_t null_descriptor(const PlaceParams &p, uint32_t /*score_row0*/) { return kRuns ? 0ull : (uint64_t)p.postings; }
+    // tripled table: the entry of `slot` in `block`, as (addr, len | first cell << 16).  The 42 bits begin at any even bit
+    // of a dword, so six of the 24 slots straddle three dwords: the lane loads the three dwords from the entry's first
+    // and funnel-shifts them down.  Slot 23 (bit 966: dwords 30 and 31, the block's last) loads from dword 29 instead
+    // and shifts by 32 more, so that no lookup reads past its block's line.
+    __device__ static __forceinline__ void tripled_entry(const PlaceParams &p, uint32_t block, uint32_t slot, uint64_t &addr,
+                                                         uint32_t &len)
+    {
+        const uint32_t bit = kTripledEntryBits * slot;
+        const bool last = slot == kTripledSlots - 1u;
+        const uint32_t *__restrict__ d = static_cast<const uint32_t *>(p.table) + (uint64_t)block * 32u + (last ? 29u : bit >> 5);
+        const uint32_t d0 = d[0], d1 = d[1], d2 = d[2];
+        const uint32_t w0 = last ? d1 : d0, w1 = last ? d2 : d1, w2 = last ? 0u : d2;
+        const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, bit & 31u);
+        const uint32_t hi = __builtin_amdgcn_alignbit(w2, w1, bit & 31u) & ((1u << (kTripledEntryBits - 32u)) - 1u);
+        const uint64_t e = ((uint64_t)hi << 32) | lo;
+        const uint32_t l = lo & ((1u << p.entry_len_bits) - 1u);
+        const uint32_t cell = (uint32_t)(e >> p.entry_len_bits) & ((1u << p.entry_cell_bits) - 1u);
+        len = l | (cell << 16);
+        addr = (e >> (p.entry_len_bits + p.entry_cell_bits)) << 7;
+    }
     // by code alone (the cold paths; the filter only saves traffic, the table is complete)
     __device__ static __forceinline__ void lookup(const PlaceParams &p, uint32_t key, uint32_t position,
                                                   uint64_t &addr, uint32_t &len)
     {
+        if constexpr (kTable == kTripledTable) {  // by code alone: as a.X, whatever the position
+            const uint32_t shift = 2u * p.kmer_size - 2u;
+            tripled_entry(p, key & ((1u << shift) - 1u), key >> shift, addr, len);
+            return;
+        }
         uint64_t entry = key;
         if (kTable == kPairedTable) {
             const uint32_t shift = 2u * p.kmer_size - 2u;  // X = k-1 letters of 2 bits
@@ -342,6 +376,21 @@ struct PackedLayout {
                 word = (((uint64_t)dwords[1] << 32) | dwords[0]) >> (8u * ((uint32_t)at & 3u));
             }
             wanted = ((word >> bit) & 1ull) != 0;
+        }
+        if constexpr (kTable == kTripledTable) {
+            // the letter in front of the window, and whether it is one: the state of lane - 1 | 4, one whole-wave DPP shift
+            // (wave_shr:1; lane 0 gets 0: no letter)
+            const uint32_t mine = t.first | ((t.cls != 0u && (t.cls & (t.cls - 1u)) == 0u) ? 4u : 0u);
+            const uint32_t before = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0x138, 0xf, 0xf, true);
+            const uint32_t shift = 2u * p.kmer_size - 2u;  // X = k-1 letters of 2 bits
+            uint32_t phase = position % 3u;
+            if (phase == 2u && before < 4u) phase = 0u;
+            const uint32_t block = phase == 0u ? t.key & ((1u << shift) - 1u)
+                                   : phase == 1u ? t.key >> 2
+                                                 : ((before & 3u) << (shift - 2u)) | (t.key >> 4);
+            const uint32_t slot = phase == 0u ? t.first : phase == 1u ? 4u + (t.key & 3u) : 8u + (t.key & 15u);
+            if (wanted) tripled_entry(p, block, slot, addr, len);
+            return;
         }
         if (wanted) lookup(p, t.key, position, addr, len);
     }

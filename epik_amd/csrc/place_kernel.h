@@ -16,7 +16,8 @@ namespace epik_amd {
 // one batch of reads.
 struct PlaceParams {
     const void *table;           // compact: OffT offsets[num_keys + 1]; packed: uint2 {len, line}[num_keys];
-                                 // paired: uint2 {len, line}[num_keys / 4][8]
+                                 // paired: uint2 {len, line}[num_keys / 4][8]; tripled: [num_keys / 4] blocks of 128 bytes,
+                                 // 24 entries of 42 bits each
     const uint64_t *filter;      // filtered: [alphabet_size^(kmer_size-1)] presence records of filter_rec_bytes each
     uint32_t sigma_pow_km1;      // alphabet_size^(kmer_size-1)
     uint32_t filter_rec_bytes;   // 8: 64-bit words; 5: 40 bits packed (any byte: read as two dwords)
@@ -52,6 +53,8 @@ struct PlaceParams {
                                      // (the uint16 counts of the dense partial vectors: 65535)
     uint32_t n_pad;                  // LDS rows per wave: num_branches + the dummy row, rounded up to 64
     uint32_t lds_wave_bytes;         // LDS bytes per wave (scores + slack rows, if any, + counts + chunk descriptors)
+    uint32_t entry_len_bits;         // tripled table: an entry is len | first cell << entry_len_bits |
+    uint32_t entry_cell_bits;        //   line << (entry_len_bits + entry_cell_bits), 42 bits
     uint32_t ablate;                 // timing experiments only (-DEPIK_AMD_ABLATION builds)
     unsigned long long *dbg;         // phase cycle sums (-DEPIK_AMD_ABLATION builds, EPIK_AMD_STAMPS=1)
 };

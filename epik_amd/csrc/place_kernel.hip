@@ -357,6 +357,23 @@ hipError_t dispatch_runs(int runs_and_ring, int counts, F &&f)
     if (runs && (ring & kRingNear)) return dispatch_counts<PackedLayout<kTable, true, true>>(counts, f);
     return runs ? dispatch_counts<PackedLayout<kTable, true>>(counts, f) : dispatch_counts<PackedLayout<kTable>>(counts, f);
 }
+// the tripled table: only what such a handle can launch (db_image.cpp: plan_tripled) -- every list a run and the near
+// descriptors: list counts with 16 and 32 bits, with or without the slack rows, and the near run ring with 8
+template <typename F>
+hipError_t dispatch_tripled(int runs_and_ring, int counts, F &&f)
+{
+    const int runs = runs_and_ring & ~(kRingNear | kRingSlack);
+    if (runs != kRunLists || !(runs_and_ring & kRingNear)) return hipErrorInvalidValue;
+    const bool slack = (runs_and_ring & kRingSlack) != 0;
+    if (counts == kCounts8) return f.template operator()<PackedLayout<kTripledTable, true, true>, uint8_t>();
+    if (counts == kCounts16)
+        return slack ? f.template operator()<RunListLayout<kTripledTable, true, true>, uint16_t>()
+                     : f.template operator()<RunListLayout<kTripledTable, true, false>, uint16_t>();
+    if (counts == kCounts32)
+        return slack ? f.template operator()<RunListLayout<kTripledTable, true, true>, uint32_t>()
+                     : f.template operator()<RunListLayout<kTripledTable, true, false>, uint32_t>();
+    return hipErrorInvalidValue;
+}
 template <typename F>
 hipError_t dispatch(DbLayout layout, int runs, int counts, F &&f)
 {
@@ -366,6 +383,7 @@ hipError_t dispatch(DbLayout layout, int runs, int counts, F &&f)
         case DbLayout::kPacked: return dispatch_runs<kPlainTable>(runs, counts, f);
         case DbLayout::kPaired: return dispatch_runs<kPairedTable>(runs, counts, f);
         case DbLayout::kFiltered: return dispatch_runs<kFilteredTable>(runs, counts, f);
+        case DbLayout::kTripled: return dispatch_tripled(runs, counts, f);
         case DbLayout::kTeam: break;  // team_kernel.hip
     }
     return hipErrorInvalidValue;
@@ -424,6 +442,7 @@ hipError_t launch_algorithmic_bytes(const PlaceParams &p, DbLayout layout, int r
 {
     const dim3 block(256);
     const dim3 grid((unsigned)((p.n_reads + 255) / 256));
+    if (layout == DbLayout::kTripled) runs = kRunLists | kRingNear;  // (any of its instantiations: the lookup by code is the same)
     return dispatch(layout, runs, kCounts16, [&]<typename L, typename C>() {
         hipLaunchKernelGGL((algorithmic_bytes_kernel<L>), grid, block, 0, stream, p, d_total);
         return hipGetLastError();

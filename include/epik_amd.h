@@ -121,7 +121,7 @@ int epik_amd_placer_create(const epik_amd_placer_desc *desc, epik_amd_placer **o
  */
 typedef struct {
     uint32_t kernel;         /* 0 = one wavefront per read, 1 = one workgroup per read */
-    uint32_t layout;         /* 0/1 compact CSR (32/64-bit offsets), 2 packed, 3 paired, 4 filtered, 5 sliced */
+    uint32_t layout;         /* 0/1 compact CSR (32/64-bit offsets), 2 packed, 3 paired, 4 filtered, 5 sliced, 6 tripled */
     uint32_t team_waves;
     uint32_t team_passes;
     uint32_t slice_rows;
@@ -175,6 +175,18 @@ int epik_amd_placer_run_counts(const epik_amd_placer *p, uint32_t counts, uint32
 #define EPIK_AMD_RING_NEAR 1u
 #define EPIK_AMD_RING_SLACK 2u
 int epik_amd_placer_ring_form(const epik_amd_placer *p, uint32_t counts, uint32_t *form);
+/* Which k-mer table the one-wavefront kernel of this handle looks its k-mers up in: keyed by code, by the (k-1)-mer two
+ * consecutive k-mers of a read share (one 128-byte line per two lookups), or by the (k-1)-mer three of them share (one
+ * line per three: 128 bytes per (k-1)-mer, 24 entries of 42 bits; 4-letter alphabets, k >= 3, whole databases whose kept
+ * lists are all runs and take the near ring, entries that fit 42 bits).  The output is the same with every table.
+ * EPIK_AMD_LAYOUT (read at create()): `tripled` asks for the last -- an error where the database cannot take it;
+ * `paired` keeps the paired table.  By itself create() takes the tripled table where the paired one is larger than an
+ * XCD's 4 MiB of L2 and the larger table does not move the image out of the 256 MiB Infinity Cache.
+ * 0 for the sliced layout and the compact CSR. */
+#define EPIK_AMD_TABLE_BY_CODE 1u
+#define EPIK_AMD_TABLE_PAIRED 2u
+#define EPIK_AMD_TABLE_TRIPLED 3u
+int epik_amd_placer_table_form(const epik_amd_placer *p, uint32_t *form);
 /* The image create() uploads for that plan, written front to back into host buffers of
  * plan->table_bytes / filter_bytes / posting_bytes (NULL = that part is produced and dropped).
  * Host only; create() streams the same bytes to the device without holding them. */

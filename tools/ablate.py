@@ -5,7 +5,7 @@ Runs the bench workload through several variants IN ONE PROCESS, interleaved ove
 rounds (devices differ by several percent: never compare across runs).  A variant is a
 comma-separated list of key=value:
     lib=<suffix>     epik_amd/libepik_amd<suffix>.so   (e.g. lib=_ablate, lib=_exp1; default: the product lib)
-    layout=compact|packed|paired, kernel=wave|team4|team8, wide=0|1|2, front=0|1 (team placement as one kernel | front + streaming + merge kernels), grid=<percent of the resident workgroups>,
+    layout=compact|packed|paired|tripled, kernel=wave|team4|team8, wide=0|1|2, front=0|1 (team placement as one kernel | front + streaming + merge kernels), grid=<percent of the resident workgroups>,
     ablate=<bitmask>, stamps=1   (env read at placer creation)
 LEAVES=<n> sets the tree (N = 2n - 1), N_READS the batch, CLADES=1 the workload of bench.py --clades.
 Example: tools/ablate.py lib=_ablate,layout=compact lib=_exp,layout=compact
@@ -92,6 +92,8 @@ def main():
         name = ",".join(f"{k}={v}" for k, v in kv.items())
         print(f"{name:48s} min {min(t):7.3f}  median {sorted(t)[len(t) // 2]:7.3f} ms/step  "
               f"{n / min(t) / 1e3:7.2f} M reads/s", flush=True)
+        if os.environ.get("SHOW_ROUNDS"):  # every round's figure, in the order taken: the spread of a variant
+            print("    rounds: " + " ".join(f"{x:.3f}" for x in t), flush=True)
     for lib, h in placers:
         lib.epik_amd_placer_destroy(h)
 
