@@ -110,6 +110,16 @@ PLACE_OPTIONS = [
     (("--cohort-rarefy-step",), dict(type=click.IntRange(1, 1 << 20), default=None,
                                      help="With --cohort-rarefy: the distance between two depths; floor(depth / step) must lie "
                                           "in [1, 256] [default: max(1, ceil(depth / 64))].")),
+    (("--taxonomy",), dict(type=click.Path(), default=None,
+                           help="A taxonomy file, one leaf_label<TAB>A;B;C line per reference leaf: also write taxa_<input>.tsv "
+                                "(per taxon the reads assigned to it and the mass placed in it, with clade sums) or, with "
+                                "--cohort, cohort_taxa_<list>.tsv, the sample x taxon table; summed on the device(s) (not with "
+                                "--assign or --db-shard > 1).")),
+    (("--taxonomy-mass",), dict(type=float, default=None,
+                                help="With --taxonomy: the share of a read's placement mass its taxon must hold, in (0.5, 1] "
+                                     "[default: 0.95].")),
+    (("--taxonomy-per-read",), dict(is_flag=True, help="With --taxonomy: also write taxa_reads_<input>.tsv, per read its taxon, "
+                                                       "that taxon's share of the mass and the taxon of its best row.")),
 ]
 
 
@@ -127,7 +137,18 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                    strand="forward", translate=None, profile=False, profile_only=False, mates=None,
                    mate_orientation="fr", assign=False, assign_mass=None, cohort=False, cohort_squash=False,
                    cohort_epca=False, cohort_epca_components=None, cohort_kmeans=None, cohort_kmeans_iterations=None,
-                   cohort_alpha=False, cohort_rarefy=None, cohort_rarefy_step=None):
+                   cohort_alpha=False, cohort_rarefy=None, cohort_rarefy_step=None, taxonomy=None, taxonomy_mass=None,
+                   taxonomy_per_read=False):
+    if taxonomy_mass is not None and taxonomy is None:
+        raise click.UsageError("--taxonomy-mass needs --taxonomy")
+    if taxonomy_per_read and taxonomy is None:
+        raise click.UsageError("--taxonomy-per-read needs --taxonomy")
+    if taxonomy is not None and assign:
+        raise click.UsageError("--taxonomy does not work with --assign")
+    if taxonomy is not None and db_shard != 1:
+        raise click.UsageError("--taxonomy does not work with --db-shard > 1")
+    if taxonomy_mass is not None and not 0.5 < float(taxonomy_mass) <= 1.0:
+        raise click.UsageError("--taxonomy-mass must lie in (0.5, 1]")
     if assign_mass is not None and not assign:
         raise click.UsageError("--assign-mass needs --assign")
     if assign and db_shard != 1:
@@ -200,6 +221,12 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--cohort-rarefy", str(int(cohort_rarefy))]
         if cohort_rarefy_step is not None:
             argv += ["--cohort-rarefy-step", str(int(cohort_rarefy_step))]
+    if taxonomy is not None:
+        argv += ["--taxonomy", str(taxonomy)]
+        if taxonomy_mass is not None:
+            argv += ["--taxonomy-mass", repr(float(taxonomy_mass))]
+        if taxonomy_per_read:
+            argv += ["--taxonomy-per-read"]
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 

@@ -23,6 +23,10 @@ OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED = 0, 1, 2, 3, 4
 PLACEMENT = np.dtype([("branch", np.uint32), ("score", np.float32), ("lwr", np.float64)])
 #: numpy mirror of `epik_amd_confidence` {clade, clade_mass_q, edpl} (16 bytes)
 CONFIDENCE = np.dtype([("clade", np.uint32), ("clade_mass_q", np.uint32), ("edpl", np.float64)])
+#: numpy mirror of `epik_amd_taxon_record` {taxon, taxon_mass_q, first_taxon, total_q} (16 bytes)
+TAXON_RECORD = np.dtype([("taxon", np.uint32), ("taxon_mass_q", np.uint32), ("first_taxon", np.uint32), ("total_q", np.uint32)])
+#: numpy mirror of `epik_amd_taxa_totals` (48 bytes)
+TAXA_TOTALS = np.dtype([(name, np.uint64) for name in ("placed", "no_hit", "too_short", "too_narrow", "no_mass", "bad_reads")])
 #: epik_amd_squash_merge (32 bytes)
 SQUASH_MERGE = np.dtype([("a", np.uint32), ("b", np.uint32), ("dist", np.float64), ("len_a", np.float64), ("len_b", np.float64)])
 SQUASH_NONE = 0xFFFFFFFF
@@ -138,6 +142,18 @@ EXPORTS = (
     "epik_amd_placer_cohort_strands",
     "epik_amd_placer_cohort_frames",
     "epik_amd_placer_cohort_mates",
+    "epik_amd_taxonomy_create",
+    "epik_amd_taxonomy_destroy",
+    "epik_amd_taxonomy_reset",
+    "epik_amd_taxonomy_info",
+    "epik_amd_taxonomy_read",
+    "epik_amd_taxonomy_add_cells",
+    "epik_amd_taxonomy_add_device",
+    "epik_amd_taxonomy_assign_host",
+    "epik_amd_placer_taxa_reads",
+    "epik_amd_placer_taxa_strands",
+    "epik_amd_placer_taxa_frames",
+    "epik_amd_placer_taxa_mates",
 )
 
 
@@ -223,6 +239,12 @@ PATH_WAVE, PATH_TEAM_ONE_KERNEL, PATH_TEAM_STREAMED = 0, 1, 2
 TREE_NO_PARENT = 0xFFFFFFFF
 CLADE_TOO_NARROW, CLADE_TOO_SHORT, CLADE_NO_HIT, CLADE_BAD_ROW = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
 CLADE_CLASSES = {CLADE_TOO_NARROW: "too_narrow", CLADE_TOO_SHORT: "too_short", CLADE_NO_HIT: "no_hit", CLADE_BAD_ROW: "bad_row"}
+
+#: the taxa of the reads that get none (EPIK_AMD_TAXON_*)
+TAXON_TOO_NARROW, TAXON_TOO_SHORT, TAXON_NO_HIT, TAXON_BAD_ROW, TAXON_NO_MASS = (0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC,
+                                                                                 0xFFFFFFFB)
+TAXON_CLASSES = {TAXON_TOO_NARROW: "too_narrow", TAXON_TOO_SHORT: "too_short", TAXON_NO_HIT: "no_hit", TAXON_BAD_ROW: "bad_row",
+                 TAXON_NO_MASS: "no_mass"}
 
 #: strand modes of epik_amd_placer_place_strands[_device], and their names in Placer / epik.py / epik-dna --strand
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
@@ -475,6 +497,30 @@ def load() -> ctypes.CDLL:
     for name in ("epik_amd_placer_cohort_strands", "epik_amd_placer_cohort_frames", "epik_amd_placer_cohort_mates"):
         getattr(lib, name).restype = i32
         getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, vp, u64, u32, vp]
+    # (taxonomic assignment: the object, its kernel, the rule on the host)
+    lib.epik_amd_taxonomy_create.restype = i32
+    lib.epik_amd_taxonomy_create.argtypes = [vp, vp, u32, vp, u32, ctypes.POINTER(vp)]
+    lib.epik_amd_taxonomy_destroy.restype = None
+    lib.epik_amd_taxonomy_destroy.argtypes = [vp]
+    lib.epik_amd_taxonomy_reset.restype = i32
+    lib.epik_amd_taxonomy_reset.argtypes = [vp]
+    lib.epik_amd_taxonomy_info.restype = i32
+    lib.epik_amd_taxonomy_info.argtypes = [vp] + [ctypes.POINTER(u32)] * 4
+    lib.epik_amd_taxonomy_read.restype = i32
+    lib.epik_amd_taxonomy_read.argtypes = [vp, vp, vp, vp, ctypes.POINTER(u64)]
+    lib.epik_amd_taxonomy_add_cells.restype = i32
+    lib.epik_amd_taxonomy_add_cells.argtypes = [vp, vp, vp, vp]
+    lib.epik_amd_taxonomy_add_device.restype = i32
+    lib.epik_amd_taxonomy_add_device.argtypes = [vp, vp, vp, vp, vp, vp, u64, u32, vp, vp]
+    lib.epik_amd_taxonomy_assign_host.restype = i32
+    lib.epik_amd_taxonomy_assign_host.argtypes = [vp, u32, vp, u32, u32, vp, vp, vp, vp, vp, u64, u32, u32, vp, vp, vp, vp,
+                                                  ctypes.POINTER(u64)]
+    # (the host entries: their place_* twins' arguments, then taxonomy, tau_q, records, weights, samples, profile, cohort)
+    lib.epik_amd_placer_taxa_reads.restype = i32
+    lib.epik_amd_placer_taxa_reads.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    for name in ("epik_amd_placer_taxa_strands", "epik_amd_placer_taxa_frames", "epik_amd_placer_taxa_mates"):
+        getattr(lib, name).restype = i32
+        getattr(lib, name).argtypes = [vp, vp, vp, u64, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 

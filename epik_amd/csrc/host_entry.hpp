@@ -258,5 +258,26 @@ int cohort_host_chunked(epik_amd_placer *p, epik_amd_cohort *cohort, const char 
                         const uint32_t *weights, const uint32_t *samples, uint64_t n, uint32_t mode, uint64_t longest_placed,
                         const HostVariant &v, uint8_t *label);
 
+// What a host entry with taxonomic assignment adds to its place_* twin (taxa_place.hip): the object whose cells every
+// chunk's rows are added to, tau_q, records[n] on the host (NULL: the records are not computed: cells only), weights
+// and samples of the items (host, or NULL: 1 and sample 0), and optionally a profile OR a cohort (not both) that the
+// same rows are added to on the way.
+struct TaxaRequest {
+    epik_amd_taxonomy *taxonomy;
+    uint32_t tau_q;
+    epik_amd_taxon_record *records;
+    const uint32_t *weights, *samples;
+    epik_amd_profile *profile;
+    epik_amd_cohort *cohort;
+};
+
+// The taxonomy host entry of a variant, once the caller has checked the handle, the mode and the reads (n >= 1,
+// check_host_reads): place_host_chunked with a sink that runs taxa_kernel on every chunk's device rows, copies the
+// records back where they are asked for and chains the profile or the cohort add; weights and samples are uploaded once;
+// rows, n_rows and kmer_counts may be NULL, each by itself.
+int taxa_host_chunked(epik_amd_placer *p, const TaxaRequest &req, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                      uint32_t mode, uint64_t longest_placed, const HostVariant &v, epik_amd_placement *rows, uint32_t *n_rows,
+                      uint32_t *kmer_counts, uint8_t *label);
+
 }  // namespace epik_amd
 #endif

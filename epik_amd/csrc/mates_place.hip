@@ -329,4 +329,22 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
     }
 }
 
+int epik_amd_placer_taxa_mates(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n_pairs,
+                                       uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                                       uint8_t *strand, epik_amd_taxonomy *taxonomy, uint32_t tau_q,
+        epik_amd_taxon_record *records, const uint32_t *weights, const uint32_t *samples, epik_amd_profile *profile,
+        epik_amd_cohort *cohort)
+{
+    try {  // (the same with the taxonomic assignment of taxa_place.hip run on each chunk's device rows)
+        if (const int rc = check_handle(p, mode); rc != EPIK_AMD_OK) return rc;
+        if (n_pairs == 0) return EPIK_AMD_OK;
+        uint64_t longest = 0;
+        if (const int rc = check_host_pairs(seqs, seq_offsets, n_pairs, longest); rc != EPIK_AMD_OK) return rc;
+        return taxa_host_chunked(p, TaxaRequest{taxonomy, tau_q, records, weights, samples, profile, cohort}, seqs, seq_offsets, n_pairs, mode,
+                                       longest, kMatesHost, rows, n_rows, kmer_counts, strand);
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("taxa_mates: ") + e.what());
+    }
+}
+
 }  // extern "C"

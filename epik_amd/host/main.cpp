@@ -41,6 +41,7 @@
 
 #include "cohort.hpp"
 #include "confidence.hpp"
+#include "taxonomy.hpp"
 #include "jplace.hpp"
 #include "phylo_kmer_db.hpp"
 #include "phylo_tree.hpp"
@@ -214,6 +215,12 @@ const char* kHelp =
     "                          the records assigned to each branch and clade; computed on the device(s) (not with\n"
     "                          --db-shard > 1; with --profile-only the rows still never leave the device)\n"
     "      --assign-mass arg   Share of a record's placement mass its clade must hold, in [0, 1] (default: 0.95)\n"
+    "      --taxonomy arg      A taxonomy file, one leaf_label<TAB>A;B;C line per reference leaf.  Also write taxa_<query>.tsv --\n"
+    "                          per taxon the records assigned to it and the mass placed in it, and the same over its clade --\n"
+    "                          or, with --cohort, cohort_taxa_<list>.tsv, the sample x taxon table; summed on the device(s)\n"
+    "                          (not with --assign or --db-shard > 1)\n"
+    "      --taxonomy-mass arg Share of a record's placement mass its taxon must hold, in (0.5, 1] (default: 0.95)\n"
+    "      --taxonomy-per-read Also write taxa_reads_<query>.tsv: per record its taxon, that taxon's share and its best row's taxon\n"
     "      --cohort            The query is a list of samples, one name<TAB>path line each (paths relative to the list; blank\n"
     "                          and # lines skipped).  Writes no jplace but cohort_samples_<list>.tsv (records per sample),\n"
     "                          cohort_profile_<list>.tsv (name, edge_num, best, mass_q of every non-zero cell) and\n"
@@ -278,7 +285,7 @@ options parse_args(int argc, char** argv)
         } else {
             continue;  // positional arguments are ignored (epik.py passes the query twice, epik.py:88,96)
         }
-        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca" || name == "cohort-alpha") && !have_value)) {  // flags
+        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca" || name == "cohort-alpha" || name == "taxonomy-per-read") && !have_value)) {  // flags
             opt.values[name] = "1";
             continue;
         }
@@ -455,6 +462,30 @@ int main(int argc, char** argv)
                 throw std::runtime_error("--cohort does not work with --db-shard > 1 (the rows of a sharded placement are finished "
                                          "on several devices)");
         }
+        // --taxonomy / --taxonomy-mass / --taxonomy-per-read: checked before anything is opened or any device touched
+        const bool with_taxonomy = parsed.has("taxonomy"), taxonomy_per_read = parsed.has("taxonomy-per-read");
+        if (parsed.has("taxonomy-mass") && !with_taxonomy) throw std::runtime_error("--taxonomy-mass needs --taxonomy");
+        if (taxonomy_per_read && !with_taxonomy) throw std::runtime_error("--taxonomy-per-read needs --taxonomy");
+        uint32_t taxonomy_tau_q = 0;
+        if (with_taxonomy) {
+            if (with_assign) throw std::runtime_error("--taxonomy does not work with --assign (both in one pass is not built)");
+            if (std::stoul(parsed.get("db-shard", "1")) > 1)
+                throw std::runtime_error("--taxonomy does not work with --db-shard > 1 (the rows of a sharded placement are finished "
+                                         "on several devices)");
+            size_t used = 0;
+            const auto text = parsed.get("taxonomy-mass", "0.95");
+            double share = -1.0;
+            try {
+                share = std::stod(text, &used);
+            } catch (const std::exception&) {
+                used = 0;
+            }
+            if (used != text.size() || used == 0 || !(share > 0.5) || !(share <= 1.0))
+                throw std::runtime_error("--taxonomy-mass must be a number in (0.5, 1], not '" + text + "'");
+            taxonomy_tau_q = epik_amd::assign_tau_q(share);
+            if (taxonomy_tau_q <= (1u << 29) || taxonomy_tau_q > (1u << 30))
+                throw std::runtime_error("--taxonomy-mass must be a number in (0.5, 1], not '" + text + "'");
+        }
         const auto db_file = parsed.require("database");
         const auto query_file = parsed.require("query");
         const auto num_threads = (size_t)std::stoul(parsed.get("jobs", "1"));
@@ -468,6 +499,15 @@ int main(int argc, char** argv)
         // --cohort: the list of samples, every file of it looked at before the database or a device is
         std::vector<epik_amd::cohort_sample> cohort_samples;
         if (with_cohort) cohort_samples = epik_amd::read_cohort_list(query_file);
+
+        // --taxonomy: the file read, and every error of it named by its line, before the database or a device is
+        epik_amd::taxonomy taxa;
+        if (with_taxonomy) {
+            std::ifstream in(parsed.require("taxonomy"), std::ios::binary);
+            if (!in) throw std::runtime_error("Could not open the taxonomy file " + parsed.require("taxonomy"));
+            std::string err;
+            if (epik_amd::parse_taxonomy(in, taxa, err) != 0) throw std::runtime_error(parsed.require("taxonomy") + ": " + err);
+        }
 
         size_t max_entries = std::numeric_limits<size_t>::max();
         if (parsed.has("max-ram")) {
@@ -539,6 +579,19 @@ int main(int argc, char** argv)
             assign_tree.reset(new epik_amd::confidence_tree(tree));
             placer.set_assign(assign_tau_q);
         }
+        // --taxonomy: the branches labelled from the tree's leaves, one object per device (a row of cells per sample)
+        if (with_taxonomy) {
+            std::vector<uint32_t> parent, label;
+            std::vector<std::string> names;
+            for (const auto& node : tree.nodes()) {
+                parent.push_back(node.parent < 0 ? EPIK_AMD_TREE_NO_PARENT : (uint32_t)node.parent);
+                names.push_back(node.get_label());
+            }
+            std::string err;
+            if (epik_amd::label_branches(taxa, parent.data(), names, (uint32_t)parent.size(), label, err) != 0)
+                throw std::runtime_error(parsed.require("taxonomy") + ": " + err);
+            placer.set_taxonomy(taxa.parent, label, taxonomy_tau_q, taxonomy_per_read);
+        }
         db.drop_lists();  // the lists are on the devices now; tree, k and omega stay for the output
         const auto tree_as_newick = epik_amd::io::to_newick(tree, true);
         const auto jplace_filename = make_output_filename(query_file, output_dir);
@@ -570,6 +623,21 @@ int main(int argc, char** argv)
         if (with_assign) {
             assign_out.open(assign_filename + ".part", std::ios::binary);
             if (!assign_out) throw std::runtime_error("Could not open " + assign_filename + ".part");
+        }
+        // --taxonomy-per-read: as the assign file, through a part file
+        std::ofstream taxa_reads_out;
+        const auto in_dir = [&](const std::string& prefix) {
+            const auto slash = query_file.find_last_of('/');
+            std::string dir = output_dir;
+            if (!dir.empty() && dir.back() != '/') dir.push_back('/');
+            return dir + prefix + (slash == std::string::npos ? query_file : query_file.substr(slash + 1)) + ".tsv";
+        };
+        const auto taxa_filename = with_cohort ? epik_amd::make_cohort_filename("taxa", query_file, output_dir) : in_dir("taxa_");
+        const auto taxa_reads_filename = in_dir("taxa_reads_");
+        uint64_t taxa_reads_records = 0;
+        if (taxonomy_per_read) {
+            taxa_reads_out.open(taxa_reads_filename + ".part", std::ios::binary);
+            if (!taxa_reads_out) throw std::runtime_error("Could not open " + taxa_reads_filename + ".part");
         }
         // --translate: one "name<TAB>+1..-3" line per input record, input order
         std::ofstream frames_out;
@@ -715,6 +783,17 @@ int main(int argc, char** argv)
                             assign_records += item.batch.size();
                         }
                         if (!assign_out) throw std::runtime_error("Could not write the assign file");
+                    }
+                    if (taxa_reads_out.is_open()) {
+                        for (const auto& item : ready) {
+                            std::string lines;
+                            for (size_t i = 0; i < item.batch.size(); ++i)
+                                lines += epik_amd::format_taxa_reads_line(std::string(item.batch[i].header()),
+                                                                          item.placed.taxa_records[item.placed.unique_of[i]], taxa);
+                            taxa_reads_out << lines;
+                            taxa_reads_records += item.batch.size();
+                        }
+                        if (!taxa_reads_out) throw std::runtime_error("Could not write the taxa reads file");
                     }
                     if (frames_out.is_open()) {
                         static const char* const names[6] = {"+1", "+2", "+3", "-1", "-2", "-3"};
@@ -875,6 +954,32 @@ int main(int argc, char** argv)
             std::remove((assign_filename + ".part").c_str());
             epik_amd::write_text_file(assign_clades_filename, epik_amd::format_assign_clades_tsv(assign_sums, *assign_tree, assign_tau_q));
         }
+        if (with_taxonomy) {
+            // the devices' objects summed on the first, read once; the clade columns are prefix sums taken here
+            const uint32_t rows_of_cells = with_cohort ? (uint32_t)cohort_samples.size() : 1;
+            epik_amd::taxa_cells cells(rows_of_cells, taxa.num_taxa());
+            placer.read_taxonomy(cells.direct.data(), cells.assigned.data(), cells.totals.data());
+            if (with_cohort) {
+                std::vector<std::string> names;
+                for (const auto& sample : cohort_samples) names.push_back(sample.name);
+                epik_amd::write_through_part(taxa_filename, epik_amd::format_cohort_taxa_tsv(names, cells, taxa, taxonomy_tau_q));
+            } else {
+                epik_amd::write_through_part(taxa_filename, epik_amd::format_taxa_tsv(cells, 0, taxa, taxonomy_tau_q));
+            }
+            if (taxonomy_per_read) {
+                taxa_reads_out.close();
+                if (!taxa_reads_out) throw std::runtime_error("Could not write " + taxa_reads_filename + ".part");
+                {
+                    std::ifstream part(taxa_reads_filename + ".part", std::ios::binary);
+                    std::ofstream whole(taxa_reads_filename, std::ios::binary);
+                    whole << epik_amd::format_taxa_reads_header(taxonomy_tau_q, taxa_reads_records);
+                    if (taxa_reads_records) whole << part.rdbuf();
+                    whole.close();
+                    if (!part || !whole) throw std::runtime_error("Could not write " + taxa_reads_filename);
+                }
+                std::remove((taxa_reads_filename + ".part").c_str());
+            }
+        }
         if (num_iterations) average_speed /= (double)num_iterations;
         std::cout << std::endl
                   << "Placed " << num_seq_placed << " sequences.\nAverage speed: " << epik_amd::human_count(average_speed, false)
@@ -901,6 +1006,8 @@ int main(int argc, char** argv)
                       << " iterations (converged=0 in " << cohort_kmeans_filename << ")" << std::endl;
         if (with_alpha) std::cout << "Cohort alpha diversity: " << cohort_alpha_filename << std::endl;
         if (with_rarefy) std::cout << "Cohort rarefaction curves: " << cohort_rarefy_filename << std::endl;
+        if (with_taxonomy) std::cout << "Taxa: " << taxa_filename << std::endl;
+        if (taxonomy_per_read) std::cout << "Taxa of the reads: " << taxa_reads_filename << std::endl;
         if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;
         if (strands_out.is_open()) {
             strands_out.close();

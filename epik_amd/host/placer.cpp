@@ -39,6 +39,14 @@
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
+#pragma weak epik_amd_taxonomy_create
+#pragma weak epik_amd_taxonomy_destroy
+#pragma weak epik_amd_taxonomy_read
+#pragma weak epik_amd_taxonomy_add_cells
+#pragma weak epik_amd_placer_taxa_reads
+#pragma weak epik_amd_placer_taxa_strands
+#pragma weak epik_amd_placer_taxa_frames
+#pragma weak epik_amd_placer_taxa_mates
 
 namespace epik_amd {
 
@@ -239,6 +247,47 @@ void placer::set_cohort(uint32_t num_samples)
     }
 }
 
+void placer::set_taxonomy(const std::vector<uint32_t>& taxon_parent, const std::vector<uint32_t>& label, uint32_t tau_q, bool per_read)
+{
+    if (_sharded) throw std::runtime_error("GPU placer: --taxonomy does not work with --db-shard > 1");
+    if (assigning()) throw std::runtime_error("GPU placer: --taxonomy does not work with --assign");
+    if (!&epik_amd_taxonomy_create || !&epik_amd_taxonomy_destroy || !&epik_amd_taxonomy_read || !&epik_amd_taxonomy_add_cells ||
+        !&epik_amd_placer_taxa_reads || !&epik_amd_placer_taxa_strands || !&epik_amd_placer_taxa_frames || !&epik_amd_placer_taxa_mates)
+        throw std::runtime_error("GPU placer: this libepik_amd has no taxonomic assignment");
+    if (label.size() != _original_tree.get_node_count()) throw std::runtime_error("GPU placer: the labels do not fit the tree");
+    _taxa_tau_q = tau_q, _taxa_per_read = per_read, _num_taxa = (uint32_t)taxon_parent.size();
+    if (!_taxa.empty()) return;
+    for (auto* h : _handles) {
+        epik_amd_taxonomy* taxa = nullptr;
+        if (epik_amd_taxonomy_create(h, taxon_parent.data(), _num_taxa, label.data(), cohort_mode() ? _cohort_samples : 1, &taxa) != EPIK_AMD_OK) {
+            const std::string message = epik_amd_last_error();
+            for (auto* made : _taxa) epik_amd_taxonomy_destroy(made);
+            _taxa.clear();
+            throw std::runtime_error("GPU placer: " + message);
+        }
+        _taxa.push_back(taxa);
+    }
+}
+
+void placer::read_taxonomy(uint64_t* direct, uint64_t* assigned, epik_amd_taxa_totals* totals)
+{
+    const auto check = [](int rc) {
+        if (rc != EPIK_AMD_OK) throw std::runtime_error(std::string("GPU placer: ") + epik_amd_last_error());
+    };
+    if (_taxa.empty()) throw std::runtime_error("GPU placer: no taxonomy (set_taxonomy)");
+    // integer adds: the sum is the same bits whichever handle placed which batch
+    for (size_t g = 1; g < _taxa.size(); ++g) {
+        check(epik_amd_taxonomy_read(_taxa[g], direct, assigned, totals, nullptr));
+        check(epik_amd_taxonomy_add_cells(_taxa[0], direct, assigned, totals));
+        epik_amd_taxonomy_destroy(_taxa[g]);  // (summed once: a second read finds it all in the first)
+        _taxa[g] = nullptr;
+    }
+    _taxa.resize(1);
+    uint64_t bad_samples = 0;
+    check(epik_amd_taxonomy_read(_taxa[0], direct, assigned, totals, &bad_samples));
+    if (bad_samples) throw std::runtime_error("GPU placer: " + std::to_string(bad_samples) + " reads of no sample of the taxonomy object");
+}
+
 void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                          epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans,
                          cohort_diversity* diversity)
@@ -326,6 +375,8 @@ placer::~placer() noexcept
     for (auto* profile : _profiles) epik_amd_profile_destroy(profile);
     for (auto* cohort : _cohorts) epik_amd_cohort_destroy(cohort);
     for (auto* tree : _trees) epik_amd_tree_destroy(tree);
+    for (auto* taxa : _taxa)
+        if (taxa) epik_amd_taxonomy_destroy(taxa);
     for (auto* h : _handles) epik_amd_placer_destroy(h);
 }
 
@@ -420,7 +471,7 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         pb.names.resize(batch.size());
         std::vector<uint32_t> at(pb.name_begin.begin(), pb.name_begin.end() - 1);
         for (size_t i = 0; i < batch.size(); ++i) pb.names[at[unique_of[i]]++] = batch[i].header();
-        if (_strand != strand_mode::forward || _translate || assigning()) pb.unique_of = std::move(unique_of);  // (the strand / frame / record of each record)
+        if (_strand != strand_mode::forward || _translate || assigning() || _taxa_per_read) pb.unique_of = std::move(unique_of);  // (the strand / frame / record of each record)
         first_unique[b + 1] = n_unique;
         first_byte[b + 1] = bytes;
         out[b] = std::move(pb);
@@ -452,6 +503,50 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
         }
     });
     const uint32_t mates_mode = (uint32_t)_strand | _mates_mode;
+    // --taxonomy: the entry of the run's placement with every chunk's rows added to this device's taxonomy object;
+    // whatever pointer is null stays on the device.  Every unique sequence weighs the number of its records.
+    std::unique_ptr<uint32_t[]> taxa_weights;
+    std::unique_ptr<epik_amd_taxon_record[]> taxa_records;
+    const auto taxa_call = [&](epik_amd_placement* t_rows, uint32_t* t_n_rows, uint32_t* t_counts, uint8_t* t_labels,
+                               const uint32_t* t_samples, epik_amd_profile* t_profile, epik_amd_cohort* t_cohort) {
+        taxa_weights.reset(new uint32_t[n]);
+        for (size_t b = 0; b < batches.size(); ++b)
+            for (size_t u = 0; u < out[b].size(); ++u)
+                taxa_weights[first_unique[b] + u] = out[b].name_begin[u + 1] - out[b].name_begin[u];
+        if (_taxa_per_read) taxa_records.reset(new epik_amd_taxon_record[n]);
+        auto* handle = _handles[device_index];
+        auto* taxa = _taxa.size() > device_index ? _taxa[device_index] : nullptr;
+        if (!taxa) throw std::runtime_error("GPU placer: the taxonomy objects have been read (read_taxonomy ends the placement)");
+        const int t_rc =
+            _mates ? epik_amd_placer_taxa_mates(handle, bytes.get(), offsets.get(), n, mates_mode, t_rows, t_n_rows, t_counts, t_labels,
+                                                taxa, _taxa_tau_q, taxa_records.get(), taxa_weights.get(), t_samples, t_profile, t_cohort)
+            : _translate ? epik_amd_placer_taxa_frames(handle, bytes.get(), offsets.get(), n, (uint32_t)_frames, t_rows, t_n_rows, t_counts,
+                                                       t_labels, taxa, _taxa_tau_q, taxa_records.get(), taxa_weights.get(), t_samples,
+                                                       t_profile, t_cohort)
+            : _strand != strand_mode::forward
+                ? epik_amd_placer_taxa_strands(handle, bytes.get(), offsets.get(), n, (uint32_t)_strand, t_rows, t_n_rows, t_counts,
+                                               t_labels, taxa, _taxa_tau_q, taxa_records.get(), taxa_weights.get(), t_samples, t_profile,
+                                               t_cohort)
+                : epik_amd_placer_taxa_reads(handle, bytes.get(), offsets.get(), n, t_rows, t_n_rows, t_counts, taxa, _taxa_tau_q,
+                                             taxa_records.get(), taxa_weights.get(), t_samples, t_profile, t_cohort);
+        if (t_rc != EPIK_AMD_OK) throw std::runtime_error(std::string("GPU placer: ") + epik_amd_last_error());
+        if (taxa_records)
+            for (size_t b = 0; b < batches.size(); ++b)
+                out[b].taxa_records.assign(taxa_records.get() + first_unique[b], taxa_records.get() + first_unique[b] + out[b].size());
+        return t_rc;
+    };
+    if (cohort_mode() && taxonomy_mode()) {
+        // the cohort's placement with the taxonomy in front: the same rows go to both, sample by sample; nothing but the
+        // records (per_read) comes back
+        std::unique_ptr<uint32_t[]> samples(new uint32_t[n]);
+        for (size_t b = 0; b < batches.size(); ++b)
+            for (size_t u = 0; u < out[b].size(); ++u) samples[first_unique[b] + u] = (*batch_samples)[b];
+        auto* cohort = _cohorts.size() > device_index ? _cohorts[device_index] : nullptr;
+        if (!cohort) throw std::runtime_error("GPU placer: the cohorts have been read (read_cohort ends a cohort placement)");
+        taxa_call(nullptr, nullptr, nullptr, nullptr, samples.get(), nullptr, cohort);
+        for (auto& pb : out) pb.row_begin.assign(pb.size() + 1, 0);
+        return out;
+    }
     if (cohort_mode()) {
         // the rows stay on the device and are summed there into the row of each batch's sample; nothing comes back
         std::unique_ptr<uint32_t[]> weights(new uint32_t[n]), samples(new uint32_t[n]);
@@ -489,7 +584,8 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
             conf.reset(new epik_amd_confidence[n]);
         }
         auto* tree = assigning() ? _trees[device_index] : nullptr;
-        const int rc = assigning()
+        const int rc = taxonomy_mode() ? taxa_call(nullptr, nullptr, nullptr, labels.get(), nullptr, profile, nullptr)
+            : assigning()
             ? (_mates ? epik_amd_placer_confidence_mates(handle, bytes.get(), offsets.get(), n, mates_mode, nullptr, nullptr, nullptr,
                                                          labels.get(), tree, _tau_q, conf.get(), profile, weights.get())
                : _translate ? epik_amd_placer_confidence_frames(handle, bytes.get(), offsets.get(), n, (uint32_t)_frames, nullptr, nullptr,
@@ -524,7 +620,12 @@ std::vector<impl::placed_batch> placer::place_flat(const std::vector<const std::
     std::unique_ptr<uint8_t[]> frames;   // (translated placement only)
     std::unique_ptr<epik_amd_confidence[]> conf;  // (--assign only)
     int rc;
-    if (assigning()) {
+    if (taxonomy_mode()) {
+        // the same placements through the taxonomy entries: the rows come back as ever, the cells stay on the device
+        if (_translate) frames.reset(new uint8_t[n]);
+        else if (_strand != strand_mode::forward) strands.reset(new uint8_t[n]);
+        rc = taxa_call(rows.get(), n_rows.get(), counts.get(), _translate ? frames.get() : strands.get(), nullptr, nullptr, nullptr);
+    } else if (assigning()) {
         // the same placements through the confidence entries: the records come back beside the rows
         conf.reset(new epik_amd_confidence[n]);
         auto* handle = _handles[device_index];

@@ -68,6 +68,8 @@ struct placed_batch {
     std::vector<std::string_view> mates;      // [n_unique]: the second mate, as given
     // placement confidence (placer::set_assign) only, else empty; `unique_of` is then filled as well:
     std::vector<epik_amd_confidence> confidence;  // [n_unique]: LCA clade, its mass and the EDPL, from the device
+    // taxonomic assignment with records (placer::set_taxonomy, per_read) only, else empty; `unique_of` is then filled as well:
+    std::vector<epik_amd_taxon_record> taxa_records;  // [n_unique]: the taxon, its mass, the first row's taxon, the total
     size_t size() const noexcept { return sequences.size(); }
 };
 
@@ -195,6 +197,17 @@ public:
     void read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                      epik_amd_squash_merge* merges = nullptr, uint32_t* num_merges = nullptr, cohort_epca* epca = nullptr,
                      cohort_kmeans* kmeans = nullptr, cohort_diversity* diversity = nullptr);
+    /// --taxonomy: one device taxonomy object per handle (epik_amd_taxonomy) from taxon_parent[T] and label[N], with one
+    /// row of cells per sample of the cohort (call set_cohort first) or one row; from then on place_flat goes through
+    /// the epik_amd_placer_taxa_* entries: every unique sequence is added with the number of its records as weight, a
+    /// profile (set_profile_only) or the cohort is chained onto the same rows, and whatever the run does not write
+    /// stays on the device.  per_read: every placed batch carries the record of each unique sequence.  Replicated
+    /// databases only (not --db-shard), not with set_assign.
+    void set_taxonomy(const std::vector<uint32_t>& taxon_parent, const std::vector<uint32_t>& label, uint32_t tau_q, bool per_read);
+    bool taxonomy_mode() const noexcept { return !_taxa.empty(); }
+    /// The objects of all handles summed into the first one's (epik_amd_taxonomy_add_cells) and read back: direct and
+    /// assigned of num_samples * num_taxa cells each, totals of num_samples.  Once, at the end.
+    void read_taxonomy(uint64_t* direct, uint64_t* assigned, epik_amd_taxa_totals* totals);
     /// The profiles of all devices read back and summed; `mass` and `best` of num_branches cells each.
     void read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_totals& totals) const;
     /// distal_length / pendant_length of a placement on branch b (place.cpp:110-123, 435-437)
@@ -214,6 +227,9 @@ private:
     std::vector<epik_amd_profile*> _profiles;  // set_profile_only(): one per handle
     std::vector<epik_amd_tree*> _trees;        // set_assign(): one per handle
     std::vector<epik_amd_cohort*> _cohorts;    // set_cohort(): one per handle
+    std::vector<epik_amd_taxonomy*> _taxa;     // set_taxonomy(): one per handle
+    uint32_t _taxa_tau_q = 0, _num_taxa = 0;
+    bool _taxa_per_read = false;
     uint32_t _cohort_samples = 0;
     uint32_t _tau_q = 0;
     bool _sharded = false;

@@ -473,6 +473,57 @@ class Placer:
                       mode, label.ctypes.data))
         return label
 
+    # -- taxonomic assignment (epik_amd/taxonomy.py) -------------------------------------------
+    def taxonomy(self, taxon_parent, label, num_samples: int = 1):
+        """A new, empty device taxonomy object for this placer (`epik_amd_taxonomy_create`): `taxon_parent[t]` of every
+        taxon (post-order ids; the root's: -1 or capi.TREE_NO_PARENT), `label[b]` of every branch."""
+        from .taxonomy import DeviceTaxonomy
+        return DeviceTaxonomy(self, taxon_parent, label, num_samples)
+
+    def taxa_packed(self, taxonomy, seqs: np.ndarray, seq_offsets: np.ndarray, tau_q: int, weights=None, samples=None,
+                    profile=None, cohort=None, strand=None, translate=None, mates=None, rows_out: bool = True,
+                    records_out: bool = True):
+        """`place_packed` / `place_strands` / `place_frames` / `place_mates` with every read's (or pair's) rows added to
+        the device `taxonomy` object there: `epik_amd_placer_taxa_reads` / `_strands` / `_frames` / `_mates`.  Item i
+        counts weights[i] times (None: once) for row samples[i] (None: row 0); `profile` or `cohort` (not both): the
+        rows are also added to it.  `rows_out=False`: rows, row counts and k-mer counts stay on the device;
+        `records_out=False`: no record is computed.  Returns (rows, n_rows, kmer_counts, label, records)."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+        n = int(seq_offsets.shape[0] - 1)
+        if strand is not None and translate is not None:
+            raise ValueError("strand and translate do not combine: translate=both already covers both strands")
+        if mates is not None:
+            if translate is not None:
+                raise ValueError("mates and translate do not combine: pairs are placed on nucleotide databases")
+            n = self._pairs_of(seq_offsets)
+        per_item = []
+        for what, a in (("weights", weights), ("samples", samples)):
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+            if a is not None and a.shape != (n,):
+                raise ValueError(f"{what} must hold one value per read ({n}), not {a.shape}")
+            per_item.append(a)
+        rows = np.zeros((n, self.keep_at_most), dtype=capi.PLACEMENT) if rows_out else None
+        n_rows = np.zeros(n, dtype=np.uint32) if rows_out else None
+        counts = np.zeros((n, self.keep_at_most), dtype=np.uint32) if rows_out else None
+        records = np.zeros(n, dtype=capi.TAXON_RECORD) if records_out else None
+        ptr = (lambda a: None if a is None else a.ctypes.data)
+        out = [ptr(a) for a in (rows, n_rows, counts)]
+        tail = [taxonomy._handle, int(tau_q), ptr(records), ptr(per_item[0]), ptr(per_item[1]),
+                None if profile is None else profile._handle, None if cohort is None else cohort._handle]
+        if strand is None and translate is None and mates is None:
+            capi.check(self._lib.epik_amd_placer_taxa_reads(self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n, *out, *tail))
+            return rows, n_rows, counts, None, records
+        label = np.zeros(n, dtype=np.uint8)
+        if mates is not None:
+            fn, mode = self._lib.epik_amd_placer_taxa_mates, self._mates_mode(strand or "forward", mates)
+        elif translate is not None:
+            fn, mode = self._lib.epik_amd_placer_taxa_frames, self._frame_mode(translate)
+        else:
+            fn, mode = self._lib.epik_amd_placer_taxa_strands, self._strand_mode(strand)
+        capi.check(fn(self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n, mode, *out, label.ctypes.data, *tail))
+        return rows, n_rows, counts, label, records
+
     # -- placement confidence (epik_amd/confidence.py) ------------------------------------------
     def tree(self, parent, branch_length):
         """The tree of this placer's database on its device (`epik_amd_tree_create`): `parent[b]` of every post-order

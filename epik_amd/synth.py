@@ -136,6 +136,42 @@ def make_tree(n_leaves: int, seed: int = 42, mean_branch_length: float = 0.05) -
     return tree
 
 
+def synth_taxonomy(tree: SynthTree, ranks: int, seed: int = 46) -> str:
+    """The text of a taxonomy file that follows `tree`: rank r = 1 .. `ranks` cuts the tree at an even share of its
+    median leaf depth, and a leaf's element of that rank names its ancestor there (a leaf above the cut has a shorter
+    path; `ranks` 0 gives the root alone).  A seeded few leaves (one in sixteen, at least one where there are two) are
+    then moved to the taxopath of another leaf, so that the inner branches above them back off toward the root.  One
+    line per leaf, in a seeded order, with comment lines, a blank line and blanks around some elements."""
+    rng = np.random.default_rng(seed)
+    n = tree.num_nodes
+    depth = np.zeros(n, dtype=np.int64)
+    for b in range(n - 2, -1, -1):
+        depth[b] = depth[tree.parent[b]] + 1
+    leaves = [b for b in range(n) if tree.children[b, 0] < 0]
+    median = int(np.median(depth[leaves])) if leaves else 0
+    cuts = [max(1, (r * max(median, 1) + ranks) // (ranks + 1)) for r in range(1, ranks + 1)]
+    paths = {}
+    for leaf in leaves:
+        chain = [leaf]                      # the leaf and its ancestors, from the leaf up
+        while tree.parent[chain[-1]] >= 0:
+            chain.append(int(tree.parent[chain[-1]]))
+        chain.reverse()                     # chain[d]: the ancestor at depth d
+        paths[leaf] = [f"rank{r}_{chain[d]}" for r, d in enumerate(cuts, 1) if d < len(chain)]
+    if len(leaves) >= 2:
+        moved = rng.choice(len(leaves), size=max(1, len(leaves) // 16), replace=False)
+        for k in moved:
+            other = leaves[int(rng.integers(0, len(leaves)))]
+            paths[leaves[int(k)]] = list(paths[other])
+    lines = ["# leaf<TAB>taxopath", ""]
+    for k in rng.permutation(len(leaves)):
+        leaf = leaves[int(k)]
+        elements = [f" {e} " if (leaf + i) % 5 == 0 else e for i, e in enumerate(paths[leaf])]
+        lines.append(f"{tree.labels[leaf]}\t{';'.join(elements) if elements else '-'}")
+        if k % 7 == 3:
+            lines.append("  # a comment between the leaves")
+    return "\n".join(lines) + "\n"
+
+
 @dataclass
 class SynthDB:
     """A phylo-k-mer database in CSR form: key -> values[offsets[key]:offsets[key+1]]."""

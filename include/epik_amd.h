@@ -955,6 +955,144 @@ int epik_amd_placer_cohort_mates(epik_amd_placer *p, epik_amd_cohort *cohort, co
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n_pairs, uint32_t mode,
                                  uint8_t *strand);
 
+/*
+ * Taxonomic assignment of reads and samples, computed on the device from the rows a placement wrote: the lowest taxon
+ * that holds a given share of a read's placement mass, and per sample the reads assigned to and the mass placed in
+ * every taxon.  No reference counterpart: the reference writes a jplace and leaves the question to a second tool.  One
+ * rule; the kernel (taxa_place.hip), the host mirror (epik_amd/host/taxonomy.cpp) and the tests' numpy
+ * are worded after it and must agree bit for bit.
+ *
+ * The taxonomy.  A text file, one line per reference leaf: leaf_label <TAB> taxopath, the taxopath A;B;C.  Blank lines
+ *   and lines that begin with '#' are skipped; blanks around the label and around every path element are stripped; an
+ *   empty element, or a line without a tab, is an error that names the line ("line <n>: ..."), and so is a leaf given
+ *   twice (the second line).  The taxopath "-" is the empty path.  The taxa are the distinct non-empty prefixes of all
+ *   taxopaths and a root, the empty path.  Ids are post-order over this trie, the children of a taxon in bytewise order
+ *   of their names: the root is T - 1, taxon_parent[t] > t for t < T - 1 and taxon_parent[T - 1] =
+ *   EPIK_AMD_TREE_NO_PARENT -- the conventions of epik_amd_tree, whose validation, first[] and lca serve the taxonomy
+ *   unchanged, with branch lengths of zero.
+ *   label[b], b < N.  Of a leaf branch: the taxon of the leaf's full taxopath (a tree leaf that the file does not give
+ *   is an error that names the leaf, a label of the file that is no leaf one that names its line).  Of an inner branch:
+ *   the taxonomy lca of the labels of its children, which is their longest common prefix.  A row on branch b counts for
+ *   the taxon shared by everything below b.
+ *
+ * The record of read i.  q(), keep and nr = min(n_rows[i], keep) are the confidence rule's, and the first four tests
+ *   come in its order:
+ *     n_rows[i] == EPIK_AMD_ROWS_COUNTS_TOO_NARROW    taxon = EPIK_AMD_TAXON_TOO_NARROW, the other fields 0
+ *     n_rows[i] == 0                                  taxon = EPIK_AMD_TAXON_TOO_SHORT,  the other fields 0
+ *     kmer_counts[i * keep] == 0                      taxon = EPIK_AMD_TAXON_NO_HIT,     the other fields 0
+ *     a row j < nr with branch >= N                   taxon = EPIK_AMD_TAXON_BAD_ROW,    the other fields 0
+ *   otherwise t_j = label[b_j] and S = the sum over j < nr of q(lwr_j), an exact integer (uint64; with LWRs in [0, 1]
+ *   and keep <= 64 it is at most 2^36):
+ *     S == 0                                          taxon = EPIK_AMD_TAXON_NO_MASS,    the other fields 0
+ *   otherwise, with mass(c) = the sum of q(lwr_j) over j < nr with first[c] <= t_j <= c:
+ *   taxon         the lowest taxon c with mass(c) * 2^30 >= tau_q * S, compared as exact integers (they fit 67 bits;
+ *                 nothing wraps -- unlike the confidence rule).  tau_q lies in (2^29, 2^30], anything else is
+ *                 EPIK_AMD_ERR_INVALID: with more than half of the mass required, two taxa that qualify share a row,
+ *                 so one holds the other -- the qualifying taxa are a chain that ends in the root, which always
+ *                 qualifies, and the lowest of them is the one of the smallest id.
+ *   taxon_mass_q  mass(taxon), saturating at 2^32 - 1.
+ *   first_taxon   t_0.
+ *   total_q       S, saturating at 2^32 - 1.
+ *   The rule reads slots past n_rows nowhere.  The record is a pure function of the read's rows, label[] and the
+ *   taxonomy: the same bits whatever the grid, the chunks or the stream.
+ *
+ * The cells.  num_samples rows, one per sample (1 outside a cohort); a row is direct[T] | assigned[T] | the totals,
+ *   uint64 that wrap.  Read i belongs to sample samples[i] (NULL: 0) and has weight w (uint32; NULL: 1; 0 adds nothing):
+ *     TOO_NARROW   totals.too_narrow += w          TOO_SHORT   totals.too_short += w
+ *     NO_HIT       totals.no_hit += w              NO_MASS     totals.no_mass += w
+ *     BAD_ROW      totals.bad_reads += 1, and nothing else
+ *     otherwise    totals.placed += w; assigned[taxon] += w; direct[t_j] += w * q(lwr_j) for every j < nr
+ *   samples[i] >= num_samples adds 1 to bad_samples and touches no row (the record is written all the same).  Integer
+ *   adds commute: the cells are the same bits whatever the order, the grouping, the pieces or the devices summed
+ *   afterwards.  The cells of a clade are a difference of a prefix sum over [first[t], t].
+ *
+ * An epik_amd_taxonomy is an object of its own, created for a placer's device, num_branches and keep_at_most (the
+ * placer may be destroyed before it) from taxon_parent[num_taxa], label[num_branches] and num_samples >= 1; all zero at
+ * create() and after reset().  create() refuses with EPIK_AMD_ERR_INVALID an invalid taxonomy ("taxon <t>: ...", the
+ * checks of epik_amd_tree_create worded for taxa), a label >= num_taxa ("branch <b>: ...") and a k-mer-space shard.
+ *   add_device   asynchronous on `stream`, allocates nothing: the records of the n reads whose rows, n_rows and k-mer
+ *                counts (required) a placement left in device memory into d_records[n] (NULL: none are written) and
+ *                their adds into the cells; d_weights, d_samples: uint32 [n] or NULL.  n == 0 does nothing.  Adds of
+ *                one object may run on several streams at once.
+ *   read         synchronises the device, then copies out direct[S][T], assigned[S][T], totals[S] and bad_samples (each
+ *                may be NULL); add_cells adds such arrays in (the objects of several devices summed into one); reset
+ *                zeroes the cells.
+ *   info         num_taxa, num_samples, num_branches, and whether add_device sums the current sample in LDS first
+ *                (16 * num_taxa bytes beside the kernel's own; EPIK_AMD_PROFILE_LDS=0|1, read at create(), forces
+ *                either: tests).
+ *   taxa_reads / _strands / _frames / _mates: place / place_strands / place_frames / place_mates with every chunk's rows
+ *                added to `taxonomy` on the device, item i with weights[i] into row samples[i] (HOST uint32 [n], or NULL: 1
+ *                and row 0; both are uploaded once).  records [n] (HOST, or NULL: no record is computed), rows, n_rows and
+ *                kmer_counts may be NULL, each by itself: that part stays on the device.  `profile` or `cohort` (not
+ *                both; a cohort needs samples): the same rows are also added to it there.  Refused with
+ *                EPIK_AMD_ERR_INVALID: tau_q out of range, an object created for another placer (device, num_branches or
+ *                keep_at_most differ), a k-mer-space shard, nulls.  Synchronous.
+ *   add_device takes raw device pointers and cannot know which placer wrote them: the caller answers for rows of the
+ *   object's keep_at_most and num_branches.  A batch holds fewer than 2^32 reads (EPIK_AMD_ERR_INVALID otherwise).
+ *   assign_host  the same rule with no device: records[n] (may be NULL) and the cells ADDED into direct[S][T],
+ *                assigned[S][T], totals[S] and *bad_samples (all four, or none of them).
+ */
+#define EPIK_AMD_TAXON_TOO_NARROW 0xffffffffu
+#define EPIK_AMD_TAXON_TOO_SHORT 0xfffffffeu
+#define EPIK_AMD_TAXON_NO_HIT 0xfffffffdu
+#define EPIK_AMD_TAXON_BAD_ROW 0xfffffffcu
+#define EPIK_AMD_TAXON_NO_MASS 0xfffffffbu
+typedef struct {
+    uint32_t taxon;
+    uint32_t taxon_mass_q;
+    uint32_t first_taxon;
+    uint32_t total_q;
+} epik_amd_taxon_record; /* 16 bytes */
+typedef struct {
+    uint64_t placed;     /* weighted reads that were assigned a taxon */
+    uint64_t no_hit;     /* ... whose rows are fabricated: none of their k-mers is in the database */
+    uint64_t too_short;  /* ... shorter than k */
+    uint64_t too_narrow; /* ... EPIK_AMD_ROWS_COUNTS_TOO_NARROW (device-pointer launches only) */
+    uint64_t no_mass;    /* ... whose rows hold no mass at all */
+    uint64_t bad_reads;  /* reads (not weighted) with a row whose branch is >= num_branches */
+} epik_amd_taxa_totals;
+typedef struct epik_amd_taxonomy epik_amd_taxonomy;
+int epik_amd_taxonomy_create(const epik_amd_placer *p, const uint32_t *taxon_parent, uint32_t num_taxa,
+                             const uint32_t *label, uint32_t num_samples, epik_amd_taxonomy **out);
+void epik_amd_taxonomy_destroy(epik_amd_taxonomy *taxonomy);
+int epik_amd_taxonomy_reset(epik_amd_taxonomy *taxonomy);
+int epik_amd_taxonomy_info(const epik_amd_taxonomy *taxonomy, uint32_t *num_taxa, uint32_t *num_samples,
+                           uint32_t *num_branches, uint32_t *lds_path);
+int epik_amd_taxonomy_read(epik_amd_taxonomy *taxonomy, uint64_t *direct, uint64_t *assigned,
+                           epik_amd_taxa_totals *totals, uint64_t *bad_samples);
+int epik_amd_taxonomy_add_cells(epik_amd_taxonomy *taxonomy, const uint64_t *direct, const uint64_t *assigned,
+                                const epik_amd_taxa_totals *totals);
+int epik_amd_taxonomy_add_device(epik_amd_taxonomy *taxonomy, const void *d_rows, const void *d_n_rows,
+                                 const void *d_kmer_counts, const void *d_weights, const void *d_samples, uint64_t n,
+                                 uint32_t tau_q, void *d_records, void *stream);
+int epik_amd_taxonomy_assign_host(const uint32_t *taxon_parent, uint32_t num_taxa, const uint32_t *label,
+                                  uint32_t num_branches, uint32_t keep, const epik_amd_placement *rows,
+                                  const uint32_t *n_rows, const uint32_t *kmer_counts, const uint32_t *weights,
+                                  const uint32_t *samples, uint64_t n, uint32_t num_samples, uint32_t tau_q,
+                                  epik_amd_taxon_record *records, uint64_t *direct, uint64_t *assigned,
+                                  epik_amd_taxa_totals *totals, uint64_t *bad_samples);
+
+int epik_amd_placer_taxa_reads(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                               epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                               epik_amd_taxonomy *taxonomy, uint32_t tau_q, epik_amd_taxon_record *records,
+                               const uint32_t *weights, const uint32_t *samples, epik_amd_profile *profile,
+                               epik_amd_cohort *cohort);
+int epik_amd_placer_taxa_strands(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                                 uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                                 uint8_t *strand, epik_amd_taxonomy *taxonomy, uint32_t tau_q,
+                                 epik_amd_taxon_record *records, const uint32_t *weights, const uint32_t *samples,
+                                 epik_amd_profile *profile, epik_amd_cohort *cohort);
+int epik_amd_placer_taxa_frames(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                                uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                                uint8_t *frame, epik_amd_taxonomy *taxonomy, uint32_t tau_q,
+                                epik_amd_taxon_record *records, const uint32_t *weights, const uint32_t *samples,
+                                epik_amd_profile *profile, epik_amd_cohort *cohort);
+int epik_amd_placer_taxa_mates(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n_pairs,
+                               uint32_t mode, epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts,
+                               uint8_t *strand, epik_amd_taxonomy *taxonomy, uint32_t tau_q,
+                               epik_amd_taxon_record *records, const uint32_t *weights, const uint32_t *samples,
+                               epik_amd_profile *profile, epik_amd_cohort *cohort);
+
 /* Which kernels the last launch of this handle ran (reports; a large-tree handle falls back from the three-kernel
  * placement to the one-kernel one when the device has no room for the scratch of a launch). */
 #define EPIK_AMD_PATH_WAVE 0u            /* place_reads_kernel: one wavefront per read */
