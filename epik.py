@@ -22,6 +22,9 @@ and cohort_kmeans_centroids_<list>.tsv; --cohort-kmeans-iterations M at the most
 --cohort-alpha, with --cohort: the alpha diversity indices of every sample, cohort_alpha_<list>.tsv.
 --cohort-rarefy KMAX, with --cohort: every sample's rarefaction curve up to depth KMAX, cohort_rarefy_<list>.tsv;
 --cohort-rarefy-step STEP between two depths (default max(1, ceil(KMAX / 64))).
+--cohort-correlation FILE, with --cohort: the correlation of every branch's mass and imbalance with the columns of the
+per-sample metadata in FILE (a TSV), cohort_correlation_<list>.tsv.
+--cohort-dispersion, with --cohort: how every branch's mass and imbalance vary across the samples, cohort_dispersion_<list>.tsv.
 """
 from __future__ import annotations
 
@@ -110,6 +113,15 @@ PLACE_OPTIONS = [
     (("--cohort-rarefy-step",), dict(type=click.IntRange(1, 1 << 20), default=None,
                                      help="With --cohort-rarefy: the distance between two depths; floor(depth / step) must lie "
                                           "in [1, 256] [default: max(1, ceil(depth / 64))].")),
+    (("--cohort-correlation",), dict(type=click.Path(), default=None,
+                                     help="With --cohort: a TSV of per-sample metadata (header sample<TAB>name1<TAB>..., 1 to 64 "
+                                          "numeric columns, empty or NA for a missing value): also correlate every branch's mass "
+                                          "and imbalance with every column on the device (Pearson and Spearman) and write "
+                                          "cohort_correlation_<list>.tsv.")),
+    (("--cohort-dispersion",), dict(is_flag=True, help="With --cohort: also compute how every branch's mass and imbalance vary "
+                                                       "across the samples on the device (mean, variance, standard deviation, "
+                                                       "coefficient of variation, variance to mean) and write "
+                                                       "cohort_dispersion_<list>.tsv.")),
     (("--taxonomy",), dict(type=click.Path(), default=None,
                            help="A taxonomy file, one leaf_label<TAB>A;B;C line per reference leaf: also write taxa_<input>.tsv "
                                 "(per taxon the reads assigned to it and the mass placed in it, with clade sums) or, with "
@@ -138,7 +150,7 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                    mate_orientation="fr", assign=False, assign_mass=None, cohort=False, cohort_squash=False,
                    cohort_epca=False, cohort_epca_components=None, cohort_kmeans=None, cohort_kmeans_iterations=None,
                    cohort_alpha=False, cohort_rarefy=None, cohort_rarefy_step=None, taxonomy=None, taxonomy_mass=None,
-                   taxonomy_per_read=False):
+                   taxonomy_per_read=False, cohort_correlation=None, cohort_dispersion=False):
     if taxonomy_mass is not None and taxonomy is None:
         raise click.UsageError("--taxonomy-mass needs --taxonomy")
     if taxonomy_per_read and taxonomy is None:
@@ -174,6 +186,10 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         if not 1 <= int(cohort_rarefy) // step <= 256:
             raise click.UsageError(f"--cohort-rarefy-step {step}: floor({int(cohort_rarefy)} / {step}) depths of --cohort-rarefy "
                                    "must lie in [1, 256]")
+    if cohort_correlation is not None and not cohort:
+        raise click.UsageError("--cohort-correlation needs --cohort")
+    if cohort_dispersion and not cohort:
+        raise click.UsageError("--cohort-dispersion needs --cohort")
     if cohort:
         for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
                             ("--assign", assign), ("--db-shard > 1", db_shard != 1)):
@@ -221,6 +237,10 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--cohort-rarefy", str(int(cohort_rarefy))]
         if cohort_rarefy_step is not None:
             argv += ["--cohort-rarefy-step", str(int(cohort_rarefy_step))]
+    if cohort_correlation is not None:
+        argv += ["--cohort-correlation", str(cohort_correlation)]
+    if cohort_dispersion:
+        argv += ["--cohort-dispersion"]
     if taxonomy is not None:
         argv += ["--taxonomy", str(taxonomy)]
         if taxonomy_mass is not None:

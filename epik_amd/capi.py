@@ -46,6 +46,14 @@ KMEANS_NONE = 0xFFFFFFFF
 ALPHA = np.dtype([("pd", np.float64), ("rooted_pd", np.float64), ("bwpd_half", np.float64), ("bwpd_one", np.float64),
                   ("quadratic", np.float64)])
 DIVERSITY_BLOCK = 256
+#: epik_amd_correlation (32 bytes) and epik_amd_dispersion (64 bytes): a branch's records; NA is the bit pattern NA_BITS
+CORRELATION = np.dtype([("mass_pearson", np.float64), ("mass_spearman", np.float64), ("imbalance_pearson", np.float64),
+                        ("imbalance_spearman", np.float64)])
+DISPERSION = np.dtype([("mass_mean", np.float64), ("mass_var", np.float64), ("mass_sd", np.float64), ("mass_cv", np.float64),
+                       ("mass_vmr", np.float64), ("imbalance_mean", np.float64), ("imbalance_var", np.float64),
+                       ("imbalance_sd", np.float64)])
+CORRELATION_MAX_COLUMNS = 64
+NA_BITS = 0x7FF8000000000000
 RAREFY_MAX_DEPTHS = 256
 RAREFY_MAX_DEPTH = 1 << 20
 #: numpy mirror of `epik_amd_pkdb_value` / `i2l::pkdb_value` (8 bytes)
@@ -138,6 +146,12 @@ EXPORTS = (
     "epik_amd_cohort_rarefy_device",
     "epik_amd_cohort_rarefy",
     "epik_amd_cohort_rarefy_host",
+    "epik_amd_cohort_correlation_device",
+    "epik_amd_cohort_correlation",
+    "epik_amd_cohort_correlation_host",
+    "epik_amd_cohort_dispersion_device",
+    "epik_amd_cohort_dispersion",
+    "epik_amd_cohort_dispersion_host",
     "epik_amd_placer_cohort_reads",
     "epik_amd_placer_cohort_strands",
     "epik_amd_placer_cohort_frames",
@@ -492,6 +506,18 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_rarefy.argtypes = [vp, vp, vp, u32, u32, vp]
     lib.epik_amd_cohort_rarefy_host.restype = i32
     lib.epik_amd_cohort_rarefy_host.argtypes = [vp, u32, u32, vp, vp, u32, u32, vp]
+    lib.epik_amd_cohort_correlation_device.restype = i32
+    lib.epik_amd_cohort_correlation_device.argtypes = [vp, vp, vp, u32, vp, vp, vp]
+    lib.epik_amd_cohort_correlation.restype = i32
+    lib.epik_amd_cohort_correlation.argtypes = [vp, vp, vp, u32, vp, vp]
+    lib.epik_amd_cohort_correlation_host.restype = i32
+    lib.epik_amd_cohort_correlation_host.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp]
+    lib.epik_amd_cohort_dispersion_device.restype = i32
+    lib.epik_amd_cohort_dispersion_device.argtypes = [vp, vp, vp, vp]
+    lib.epik_amd_cohort_dispersion.restype = i32
+    lib.epik_amd_cohort_dispersion.argtypes = [vp, vp, vp]
+    lib.epik_amd_cohort_dispersion_host.restype = i32
+    lib.epik_amd_cohort_dispersion_host.argtypes = [vp, u32, u32, vp, vp]
     lib.epik_amd_placer_cohort_reads.restype = i32
     lib.epik_amd_placer_cohort_reads.argtypes = [vp, vp, vp, vp, vp, vp, u64]
     for name in ("epik_amd_placer_cohort_strands", "epik_amd_placer_cohort_frames", "epik_amd_placer_cohort_mates"):

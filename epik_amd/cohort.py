@@ -22,6 +22,11 @@ the two files of --cohort-kmeans.
 Alpha diversity and rarefaction curves of the samples (the header's fifth rule): `Cohort.alpha` / `alpha_device` and
 `Cohort.rarefy` / `rarefy_device` on the device, `alpha_host` and `rarefy_host` on the host; `format_alpha_tsv`,
 `format_rarefy_tsv` and their readers are the files of --cohort-alpha and --cohort-rarefy.
+
+Edge correlation with per-sample metadata and edge dispersion (the header's sixth rule): `Cohort.correlation` /
+`correlation_device` and `Cohort.dispersion` / `dispersion_device` on the device, `correlation_host` and `dispersion_host`
+on the host; `read_metadata` reads the file of --cohort-correlation; `format_correlation_tsv`, `format_dispersion_tsv` and
+their readers are the files of --cohort-correlation and --cohort-dispersion.
 """
 from __future__ import annotations
 
@@ -219,6 +224,51 @@ def rarefy_host(best, first, branch_length, depth_step: int, num_depths: int) ->
     out = _curve_buffer(s, depths)
     capi.check(lib.epik_amd_cohort_rarefy_host(best.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, step, depths,
                                                out.ctypes.data))
+    return out
+
+
+def _mass_and_first(mass, first):
+    mass = np.ascontiguousarray(mass, dtype=np.uint64)
+    if mass.ndim != 2:
+        raise ValueError("mass must be [num_samples][num_branches]")
+    first = np.ascontiguousarray(first, dtype=np.uint32)
+    if first.shape != (mass.shape[1],):
+        raise ValueError(f"first must hold one value per branch ({mass.shape[1]})")
+    return mass, first
+
+
+def _metadata(meta, num_samples: int) -> np.ndarray:
+    meta = np.ascontiguousarray(meta, dtype=np.float64)
+    if meta.ndim != 2 or meta.shape[0] != num_samples:
+        raise ValueError(f"meta must be [num_samples = {num_samples}][num_columns]")
+    return meta
+
+
+def _na(count: int, dtype) -> np.ndarray:
+    return np.full(count * len(dtype.names), np.nan).view(dtype)
+
+
+def correlation_host(mass, first, meta):
+    """The edge correlation of the rule for mass[S][N] and meta[S][M] (NaN: missing) on the host
+    (`epik_amd_cohort_correlation_host`): (`capi.CORRELATION` [M][N], used uint32 [M])."""
+    lib = capi.load()
+    mass, first = _mass_and_first(mass, first)
+    s, n = mass.shape
+    meta = _metadata(meta, s)
+    m = meta.shape[1]
+    out, used = _na(max(m, 1) * n, capi.CORRELATION), np.zeros(max(m, 1), dtype=np.uint32)
+    capi.check(lib.epik_amd_cohort_correlation_host(mass.ctypes.data, s, n, first.ctypes.data, meta.ctypes.data, m,
+                                                    out.ctypes.data, used.ctypes.data))
+    return out.reshape(max(m, 1), n), used
+
+
+def dispersion_host(mass, first) -> np.ndarray:
+    """The edge dispersion of the rule for mass[S][N] on the host (`epik_amd_cohort_dispersion_host`): `capi.DISPERSION` [N]."""
+    lib = capi.load()
+    mass, first = _mass_and_first(mass, first)
+    s, n = mass.shape
+    out = _na(n, capi.DISPERSION)
+    capi.check(lib.epik_amd_cohort_dispersion_host(mass.ctypes.data, s, n, first.ctypes.data, out.ctypes.data))
     return out
 
 
@@ -425,6 +475,43 @@ class Cohort:
         step, depths = _count32(depth_step, "depth_step"), _count32(num_depths, "num_depths")
         out = _curve_buffer(self.num_samples, depths)
         capi.check(self._lib.epik_amd_cohort_rarefy(self._handle, tree._handle, length.ctypes.data, step, depths, out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _tree_handle(tree, what):
+        if tree is None or not getattr(tree, "_handle", None):
+            raise ValueError(f"{what} needs a device tree (Placer.tree)")
+        return tree._handle
+
+    def correlation_device(self, tree, meta, d_out: int, d_used: int, stream: int = 0) -> None:
+        """The edge correlation with meta[S][M] (host; NaN: missing) into d_out, `capi.CORRELATION` [M][N], and d_used,
+        uint32 [M], in device memory, every cell written; asynchronous on `stream` once the columns are copied, no readback
+        (`epik_amd_cohort_correlation_device`)."""
+        meta = _metadata(meta, self.num_samples)
+        capi.check(self._lib.epik_amd_cohort_correlation_device(self._handle, self._tree_handle(tree, "correlation"),
+                                                                meta.ctypes.data, meta.shape[1], d_out or None, d_used or None,
+                                                                stream or None))
+
+    def correlation(self, tree, meta):
+        """The edge correlation of the samples with meta[S][M]: (`capi.CORRELATION` [M][N], used uint32 [M])
+        (`epik_amd_cohort_correlation`)."""
+        meta = _metadata(meta, self.num_samples)
+        m, n = meta.shape[1], self.num_branches
+        out, used = _na(max(m, 1) * n, capi.CORRELATION), np.zeros(max(m, 1), dtype=np.uint32)
+        capi.check(self._lib.epik_amd_cohort_correlation(self._handle, self._tree_handle(tree, "correlation"), meta.ctypes.data, m,
+                                                         out.ctypes.data, used.ctypes.data))
+        return out.reshape(max(m, 1), n), used
+
+    def dispersion_device(self, tree, d_out: int, stream: int = 0) -> None:
+        """The edge dispersion into d_out, `capi.DISPERSION` [N] in device memory, every cell written; asynchronous on
+        `stream`, no readback (`epik_amd_cohort_dispersion_device`)."""
+        capi.check(self._lib.epik_amd_cohort_dispersion_device(self._handle, self._tree_handle(tree, "dispersion"), d_out or None,
+                                                               stream or None))
+
+    def dispersion(self, tree) -> np.ndarray:
+        """The edge dispersion of the samples, `capi.DISPERSION` [N] (`epik_amd_cohort_dispersion`)."""
+        out = _na(self.num_branches, capi.DISPERSION)
+        capi.check(self._lib.epik_amd_cohort_dispersion(self._handle, self._tree_handle(tree, "dispersion"), out.ctypes.data))
         return out
 
     def reset(self) -> None:
@@ -779,6 +866,175 @@ def read_rarefy_tsv(path: str):
     if any(len(r) != 5 for r in rows) or len(info["unused"]) != info["samples"] - info["used"]:
         raise ValueError(f"{path}: the rows do not follow the first line's counts")
     return [(r[0], int(r[1]), int(r[2]), float(r[3]), float(r[4])) for r in rows], info
+
+
+_NUMBER = re.compile(r"[+-]?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?")
+
+
+def read_metadata(path: str, names):
+    """The metadata file of --cohort-correlation for the samples `names` of the list: (columns, float64 [S][M] in list order
+    with NaN for a missing value, the number of lines skipped because their sample is not in the list).  A TSV: the header
+    `sample<TAB>name1<TAB>...` (1 to 64 unique, non-empty names), then a line per sample; blank lines and `#` lines are
+    skipped; a value is empty or `NA` (missing) or a decimal number.  ValueError naming the line, and the column where there
+    is one, for anything else, and naming the sample of the list that the file lacks."""
+    index = {name: s for s, name in enumerate(names)}
+    columns, values, seen, skipped = None, None, {}, 0
+    with open(path, newline="") as fh:
+        for number, line in enumerate(fh, 1):
+            line = line.rstrip("\n")
+            if line.endswith("\r"):
+                line = line[:-1]
+            if not line or line.startswith("#"):
+                continue
+            where = f"{path} line {number}"
+            fields = line.split("\t")
+            if columns is None:
+                if fields[0] != "sample":
+                    raise ValueError(f"{where}: the header must begin with 'sample'")
+                if not 2 <= len(fields) <= 1 + capi.CORRELATION_MAX_COLUMNS:
+                    raise ValueError(f"{where}: the header names {len(fields) - 1} columns, not 1 to 64")
+                columns = fields[1:]
+                for c, name in enumerate(columns):
+                    if not name:
+                        raise ValueError(f"{where}: column {c + 1} has an empty name")
+                    if name in columns[:c]:
+                        raise ValueError(f"{where}: the column name '{name}' is given twice")
+                values = np.full((len(names), len(columns)), np.nan)
+                continue
+            if len(fields) != len(columns) + 1:
+                raise ValueError(f"{where}: {len(fields)} fields, not {len(columns) + 1}")
+            s = index.get(fields[0])
+            if s is None:
+                skipped += 1
+                continue
+            if s in seen:
+                raise ValueError(f"{where}: the sample '{fields[0]}' is given twice (first on line {seen[s]})")
+            seen[s] = number
+            for c, text in enumerate(fields[1:]):
+                if text in ("", "NA"):
+                    continue
+                if not _NUMBER.fullmatch(text):
+                    raise ValueError(f"{where}, column {columns[c]}: '{text}' is not a number, empty or NA")
+                value = float(text)
+                if value in (float("inf"), float("-inf")):
+                    raise ValueError(f"{where}, column {columns[c]}: '{text}' overflows a double")
+                values[s, c] = value
+    if columns is None:
+        raise ValueError(f"{path} has no header line")
+    for s, name in enumerate(names):
+        if s not in seen:
+            raise ValueError(f"{path} has no line for the sample '{name}'")
+    return columns, values, skipped
+
+
+CORRELATION_HEADER = "edge_num\tcolumn\tmass_pearson\tmass_spearman\timbalance_pearson\timbalance_spearman"
+DISPERSION_HEADER = ("edge_num\tmass_mean\tmass_var\tmass_sd\tmass_cv\tmass_vmr\timbalance_mean\timbalance_var\t"
+                     "imbalance_sd")
+
+
+def _g17_or_na(v) -> str:
+    v = float(v)
+    return "NA" if v != v else "%.17g" % v
+
+
+def _na_or_float(text: str) -> float:
+    return float(np.uint64(capi.NA_BITS).view(np.float64)) if text == "NA" else float(text)
+
+
+def _used_head(what: str, names, totals, more: str = ""):
+    totals = [int(x) for x in totals]
+    if len(totals) != len(names):
+        raise ValueError("one total mass per sample")
+    lines = [f"# epik_amd {what} v1  samples={len(names)} used={sum(t != 0 for t in totals)}{more}"]
+    return lines + [f"# unused\t{name}" for name, t in zip(names, totals) if t == 0]
+
+
+def totals_of(mass) -> np.ndarray:
+    """T_s of the rule: the wrapping sum of mass[s][:], uint64 [S]."""
+    return np.asarray(mass, dtype=np.uint64).sum(axis=1, dtype=np.uint64)
+
+
+def format_correlation_tsv(names, totals, columns, records, used) -> str:
+    """cohort_correlation_<list>.tsv: the first line, a `# unused` line per sample without mass (`totals`[s] = T_s is 0), a
+    `# column` line per column with its number of samples, the column names, then, long format, for every branch and every
+    column the four correlations of records `capi.CORRELATION` [M][N]; doubles as %.17g, NA as NA."""
+    records = np.asarray(records)
+    if records.dtype != capi.CORRELATION or records.ndim != 2 or records.shape[0] != len(columns) or len(used) != len(columns):
+        raise ValueError("records must be capi.CORRELATION [num_columns][num_branches], with one count per column")
+    lines = _used_head("correlation", names, totals, f" columns={len(columns)}")
+    lines += [f"# column\t{c}\t{name}\t{int(used[c])}" for c, name in enumerate(columns)]
+    lines.append(CORRELATION_HEADER)
+    for b in range(records.shape[1]):
+        for c, name in enumerate(columns):
+            lines.append(f"{b}\t{name}" + "".join("\t" + _g17_or_na(records[f][c, b]) for f in capi.CORRELATION.names))
+    return "\n".join(lines) + "\n"
+
+
+def _read_used_head(fh, what: str, pattern: str, path: str):
+    head = re.fullmatch(rf"# epik_amd {what} v1  samples=(\d+) used=(\d+){pattern}", fh.readline().rstrip("\n"))
+    if not head:
+        raise ValueError(f"{path}: not a cohort {what} file")
+    info = {"samples": int(head.group(1)), "used": int(head.group(2)), "unused": []}
+    line = fh.readline().rstrip("\n")
+    while line.startswith("# unused\t"):
+        info["unused"].append(line.split("\t", 1)[1])
+        line = fh.readline().rstrip("\n")
+    if len(info["unused"]) != info["samples"] - info["used"]:
+        raise ValueError(f"{path}: the unused samples do not follow the first line's counts")
+    return head, info, line
+
+
+def read_correlation_tsv(path: str):
+    """(columns, records `capi.CORRELATION` [M][N], used uint32 [M], info {"samples", "used", "unused": names})"""
+    with open(path, newline="") as fh:
+        head, info, line = _read_used_head(fh, "correlation", r" columns=(\d+)", path)
+        columns, used = [], []
+        while line.startswith("# column\t"):
+            _, c, name, count = line.split("\t")
+            if int(c) != len(columns):
+                raise ValueError(f"{path}: the columns are not numbered in order")
+            columns.append(name), used.append(int(count))
+            line = fh.readline().rstrip("\n")
+        if line != CORRELATION_HEADER or len(columns) != int(head.group(3)):
+            raise ValueError(f"{path}: not a cohort correlation file")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    m = len(columns)
+    if len(rows) % m or any(len(r) != 6 for r in rows):
+        raise ValueError(f"{path}: the rows do not follow the first line's counts")
+    records = np.zeros((m, len(rows) // m), dtype=capi.CORRELATION)
+    for i, r in enumerate(rows):
+        if int(r[0]) != i // m or r[1] != columns[i % m]:
+            raise ValueError(f"{path}: row {i} is out of order")
+        records[i % m, i // m] = tuple(_na_or_float(x) for x in r[2:])
+    return columns, records, np.array(used, dtype=np.uint32), info
+
+
+def format_dispersion_tsv(names, totals, records) -> str:
+    """cohort_dispersion_<list>.tsv: the first line, the `# unused` lines, the column names, then per branch the eight
+    fields of records `capi.DISPERSION` [N]; doubles as %.17g, NA as NA."""
+    records = np.asarray(records)
+    if records.dtype != capi.DISPERSION or records.ndim != 1:
+        raise ValueError("records must be capi.DISPERSION [num_branches]")
+    lines = _used_head("dispersion", names, totals)
+    lines.append(DISPERSION_HEADER)
+    for b in range(records.shape[0]):
+        lines.append(str(b) + "".join("\t" + _g17_or_na(records[f][b]) for f in capi.DISPERSION.names))
+    return "\n".join(lines) + "\n"
+
+
+def read_dispersion_tsv(path: str):
+    """(records `capi.DISPERSION` [N], info {"samples", "used", "unused": names})"""
+    with open(path, newline="") as fh:
+        _, info, line = _read_used_head(fh, "dispersion", "", path)
+        if line != DISPERSION_HEADER:
+            raise ValueError(f"{path}: not a cohort dispersion file")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    if any(len(r) != 9 or int(r[0]) != i for i, r in enumerate(rows)):
+        raise ValueError(f"{path}: the rows are not one per branch in order")
+    records = np.zeros(len(rows), dtype=capi.DISPERSION)
+    for i, r in enumerate(rows):
+        records[i] = tuple(_na_or_float(x) for x in r[1:])
+    return records, info
 
 
 def read_samples_tsv(path: str):

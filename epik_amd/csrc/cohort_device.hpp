@@ -1,4 +1,4 @@
-// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, kmeans_place.hip and diversity_place.hip share of a device cohort: the object
+// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, kmeans_place.hip, diversity_place.hip and correlation_place.hip share of a device cohort: the object
 // itself and the launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering and the
 // edge principal components start from.
 #ifndef EPIK_AMD_COHORT_DEVICE_HPP
@@ -33,6 +33,9 @@ struct epik_amd_cohort {
     void *d_diversity = nullptr;
     void *d_rarefy = nullptr;
     uint32_t rarefy_depths = 0;
+    // the workspace of the edge correlation and dispersion, allocated by the first correlation_device or dispersion_device
+    // (correlation_place.hip):
+    void *d_correlation = nullptr;
 };
 
 namespace epik_amd {

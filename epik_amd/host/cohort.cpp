@@ -3,7 +3,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <fstream>
+#include <map>
 #include <set>
 #include <stdexcept>
 
@@ -567,6 +570,261 @@ int rarefy_curves(const uint64_t* best, uint32_t num_samples, uint32_t num_branc
     return EPIK_AMD_OK;
 }
 
+namespace {
+
+inline double na_value()
+{
+    const uint64_t bits = EPIK_AMD_NA_BITS;
+    double v;
+    std::memcpy(&v, &bits, sizeof v);
+    return v;
+}
+
+// the rule's midranks by counting
+void midranks(const std::vector<double>& x, std::vector<double>& rank)
+{
+    const size_t L = x.size();
+    rank.resize(L);
+    for (size_t j = 0; j < L; ++j) {
+        size_t less = 0, equal = 0;
+        for (size_t i = 0; i < L; ++i) less += x[i] < x[j], equal += x[i] == x[j];
+        rank[j] = (double)less + 0.5 * (double)(equal + 1);
+    }
+}
+
+// what the rule's Pearson needs of one vector: the mean, the deviations, and their sum of squares (L >= 1)
+struct centred {
+    double mean = 0.0, ss = 0.0;
+    std::vector<double> d;
+    void of(const std::vector<double>& x)
+    {
+        const size_t L = x.size();
+        double acc = 0.0;
+        for (size_t j = 0; j < L; ++j) acc = acc + x[j];
+        mean = acc / (double)L;
+        d.resize(L);
+        ss = 0.0;
+        for (size_t j = 0; j < L; ++j) d[j] = x[j] - mean, ss = ss + d[j] * d[j];
+    }
+};
+
+double pearson_of(const centred& x, const centred& y)
+{
+    const size_t L = x.d.size();
+    if (L < 3) return na_value();
+    double sxy = 0.0;
+    for (size_t j = 0; j < L; ++j) sxy = sxy + x.d[j] * y.d[j];
+    const double den = std::sqrt(x.ss) * std::sqrt(y.ss);
+    if (!(den > 0.0)) return na_value();
+    double r = sxy / den;
+    if (r < -1.0) r = -1.0;
+    if (r > 1.0) r = 1.0;
+    return r;
+}
+
+// the masses and imbalances of branch b over the samples of `list`
+void branch_vectors(const uint64_t* mass, const kr_planes& p, size_t N, size_t b, const std::vector<size_t>& list,
+                    std::vector<double>& xm, std::vector<double>& xi)
+{
+    xm.resize(list.size()), xi.resize(list.size());
+    for (size_t j = 0; j < list.size(); ++j) {
+        const size_t s = list[j];
+        xm[j] = (double)mass[s * N + b] / (double)p.total[s];
+        xi[j] = (p.B[s * N + b] + p.C[s * N + b]) - 1.0;
+    }
+}
+
+}  // namespace
+
+int correlation_columns_valid(const double* meta, uint32_t num_samples, uint32_t num_columns, std::string& err)
+{
+    if (num_columns < 1 || num_columns > EPIK_AMD_CORRELATION_MAX_COLUMNS) {
+        err = "num_columns = " + std::to_string(num_columns) + " is outside [1, 64]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    for (size_t s = 0; s < num_samples; ++s)
+        for (size_t c = 0; c < num_columns; ++c)
+            if (std::isinf(meta[s * num_columns + c])) {
+                err = "sample " + std::to_string(s) + ", column " + std::to_string(c) + ": the metadata value is infinite";
+                return EPIK_AMD_ERR_INVALID;
+            }
+    return EPIK_AMD_OK;
+}
+
+int correlation_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                        const double* meta, uint32_t num_columns, epik_amd_correlation* out, uint32_t* used, std::string& err)
+{
+    const size_t S = num_samples, N = num_branches, M = num_columns;
+    if (const int rc = correlation_columns_valid(meta, num_samples, num_columns, err); rc != EPIK_AMD_OK) return rc;
+    kr_planes p;
+    if (const int rc = make_planes(mass, S, N, first, nullptr, p, err); rc != EPIK_AMD_OK) return rc;
+    const double na = na_value();
+    // the columns with the same U_c side by side: mx, dx, sxx and the ranks of x do not depend on y, so they are formed
+    // once per set and branch, by the same operations in the same order as for a column on its own
+    std::map<std::vector<size_t>, std::vector<size_t>> columns_of;
+    for (size_t c = 0; c < M; ++c) {
+        std::vector<size_t> list;
+        for (size_t s = 0; s < S; ++s)
+            if (p.total[s] != 0 && !std::isnan(meta[s * M + c])) list.push_back(s);
+        used[c] = (uint32_t)list.size();
+        columns_of[std::move(list)].push_back(c);
+    }
+    std::vector<double> y, ry, xm, xi, rm, ri;
+    centred cxm, cxi, crm, cri;
+    for (const auto& [list, columns] : columns_of) {
+        const size_t L = list.size();
+        std::vector<centred> cy(columns.size()), cry(columns.size());
+        for (size_t q = 0; q < columns.size() && L >= 3; ++q) {
+            y.resize(L);
+            for (size_t j = 0; j < L; ++j) y[j] = meta[list[j] * M + columns[q]];
+            midranks(y, ry), cy[q].of(y), cry[q].of(ry);
+        }
+        for (size_t b = 0; b < N; ++b) {
+            for (const size_t c : columns) out[c * N + b] = epik_amd_correlation{na, na, na, na};
+            if (L < 3) continue;
+            const bool inner = first[b] < b;
+            branch_vectors(mass, p, N, b, list, xm, xi);
+            midranks(xm, rm), cxm.of(xm), crm.of(rm);
+            if (inner) midranks(xi, ri), cxi.of(xi), cri.of(ri);
+            for (size_t q = 0; q < columns.size(); ++q) {
+                epik_amd_correlation& r = out[columns[q] * N + b];
+                r.mass_pearson = pearson_of(cxm, cy[q]), r.mass_spearman = pearson_of(crm, cry[q]);
+                if (inner) r.imbalance_pearson = pearson_of(cxi, cy[q]), r.imbalance_spearman = pearson_of(cri, cry[q]);
+            }
+        }
+    }
+    return EPIK_AMD_OK;
+}
+
+int dispersion_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                       epik_amd_dispersion* out, std::string& err)
+{
+    const size_t S = num_samples, N = num_branches;
+    kr_planes p;
+    if (const int rc = make_planes(mass, S, N, first, nullptr, p, err); rc != EPIK_AMD_OK) return rc;
+    const double na = na_value();
+    std::vector<size_t> list;
+    for (size_t s = 0; s < S; ++s)
+        if (p.total[s] != 0) list.push_back(s);
+    const size_t L = list.size();
+    std::vector<double> xm, xi;
+    centred cm, ci;
+    for (size_t b = 0; b < N; ++b) {
+        epik_amd_dispersion& r = out[b];
+        r = epik_amd_dispersion{na, na, na, na, na, na, na, na};
+        if (L == 0) continue;
+        branch_vectors(mass, p, N, b, list, xm, xi);
+        cm.of(xm);
+        r.mass_mean = cm.mean, r.mass_var = cm.ss / (double)L, r.mass_sd = std::sqrt(r.mass_var);
+        if (r.mass_mean > 0.0) r.mass_cv = r.mass_sd / r.mass_mean, r.mass_vmr = r.mass_var / r.mass_mean;
+        if (!(first[b] < b)) continue;
+        ci.of(xi);
+        r.imbalance_mean = ci.mean, r.imbalance_var = ci.ss / (double)L, r.imbalance_sd = std::sqrt(r.imbalance_var);
+    }
+    return EPIK_AMD_OK;
+}
+
+namespace {
+
+// [+-]?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?
+bool is_number(const std::string& v)
+{
+    size_t i = 0;
+    const auto digits = [&] {
+        const size_t from = i;
+        while (i < v.size() && v[i] >= '0' && v[i] <= '9') ++i;
+        return i - from;
+    };
+    if (i < v.size() && (v[i] == '+' || v[i] == '-')) ++i;
+    const size_t whole = digits();
+    size_t fraction = 0;
+    if (i < v.size() && v[i] == '.') {
+        ++i;
+        fraction = digits();
+    }
+    if (whole + fraction == 0) return false;
+    if (i < v.size() && (v[i] == 'e' || v[i] == 'E')) {
+        ++i;
+        if (i < v.size() && (v[i] == '+' || v[i] == '-')) ++i;
+        if (digits() == 0) return false;
+    }
+    return i == v.size();
+}
+
+std::vector<std::string> split_tabs(const std::string& line)
+{
+    std::vector<std::string> fields;
+    size_t from = 0;
+    for (;;) {
+        const size_t tab = line.find('\t', from);
+        fields.push_back(line.substr(from, tab == std::string::npos ? tab : tab - from));
+        if (tab == std::string::npos) return fields;
+        from = tab + 1;
+    }
+}
+
+}  // namespace
+
+cohort_metadata read_cohort_metadata(const std::string& file, const std::vector<cohort_sample>& samples)
+{
+    std::ifstream in(file);
+    if (!in) throw std::runtime_error("--cohort-correlation: cannot open the metadata file " + file);
+    std::map<std::string, size_t> index;
+    for (size_t s = 0; s < samples.size(); ++s) index[samples[s].name] = s;
+    cohort_metadata meta;
+    std::vector<size_t> seen(samples.size(), 0);  // the line that gave the sample, 0: none yet
+    bool have_header = false;
+    std::string line;
+    for (size_t number = 1; std::getline(in, line); ++number) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        const std::string where = "--cohort-correlation: " + file + " line " + std::to_string(number);
+        const auto fields = split_tabs(line);
+        if (!have_header) {
+            if (fields[0] != "sample") throw std::runtime_error(where + ": the header must begin with 'sample'");
+            if (fields.size() < 2 || fields.size() > 1 + EPIK_AMD_CORRELATION_MAX_COLUMNS)
+                throw std::runtime_error(where + ": the header names " + std::to_string(fields.size() - 1) +
+                                         " columns, not 1 to 64");
+            std::set<std::string> names;
+            for (size_t c = 1; c < fields.size(); ++c) {
+                if (fields[c].empty()) throw std::runtime_error(where + ": column " + std::to_string(c) + " has an empty name");
+                if (!names.insert(fields[c]).second)
+                    throw std::runtime_error(where + ": the column name '" + fields[c] + "' is given twice");
+                meta.columns.push_back(fields[c]);
+            }
+            meta.values.assign(samples.size() * meta.columns.size(), na_value());
+            have_header = true;
+            continue;
+        }
+        const size_t M = meta.columns.size();
+        if (fields.size() != M + 1)
+            throw std::runtime_error(where + ": " + std::to_string(fields.size()) + " fields, not " + std::to_string(M + 1));
+        const auto found = index.find(fields[0]);
+        if (found == index.end()) {
+            ++meta.skipped;
+            continue;
+        }
+        const size_t s = found->second;
+        if (seen[s])
+            throw std::runtime_error(where + ": the sample '" + fields[0] + "' is given twice (first on line " +
+                                     std::to_string(seen[s]) + ")");
+        seen[s] = number;
+        for (size_t c = 0; c < M; ++c) {
+            const std::string& v = fields[c + 1];
+            if (v.empty() || v == "NA") continue;
+            const std::string at = where + ", column " + meta.columns[c] + ": ";
+            if (!is_number(v)) throw std::runtime_error(at + "'" + v + "' is not a number, empty or NA");
+            const double value = std::strtod(v.c_str(), nullptr);
+            if (std::isinf(value)) throw std::runtime_error(at + "'" + v + "' overflows a double");
+            meta.values[s * M + c] = value;
+        }
+    }
+    if (!have_header) throw std::runtime_error("--cohort-correlation: " + file + " has no header line");
+    for (size_t s = 0; s < samples.size(); ++s)
+        if (!seen[s]) throw std::runtime_error("--cohort-correlation: " + file + " has no line for the sample '" + samples[s].name + "'");
+    return meta;
+}
+
 std::vector<cohort_sample> read_cohort_list(const std::string& list_file)
 {
     std::ifstream in(list_file);
@@ -814,6 +1072,59 @@ std::string format_rarefy_tsv(const std::vector<cohort_sample>& samples, const u
         for (size_t j = 0; j < J && (uint64_t)(j + 1) * depth_step <= reads[s]; ++j)
             out += samples[s].name + '\t' + std::to_string((uint64_t)(j + 1) * depth_step) + '\t' + std::to_string(reads[s]) + '\t' +
                    g17(curve[(s * J + j) * 2]) + '\t' + g17(curve[(s * J + j) * 2 + 1]) + '\n';
+    }
+    return out;
+}
+
+namespace {
+
+std::string g17_or_na(double v) { return std::isnan(v) ? std::string("NA") : g17(v); }
+
+// the first line of a file over the used samples (T_s > 0), then a "# unused" line per sample without mass
+std::string used_head(const std::vector<cohort_sample>& samples, const uint64_t* totals, const char* what, const std::string& more)
+{
+    size_t used = 0;
+    std::string unused;
+    for (size_t s = 0; s < samples.size(); ++s) {
+        if (totals[s] != 0)
+            ++used;
+        else
+            unused += "# unused\t" + samples[s].name + "\n";
+    }
+    return "# epik_amd " + std::string(what) + " v1  samples=" + std::to_string(samples.size()) + " used=" + std::to_string(used) +
+           more + "\n" + unused;
+}
+
+}  // namespace
+
+std::string format_correlation_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                                   const std::vector<std::string>& columns, uint32_t num_branches,
+                                   const epik_amd_correlation* records, const uint32_t* used_of)
+{
+    const size_t N = num_branches, M = columns.size();
+    std::string out = used_head(samples, totals, "correlation", " columns=" + std::to_string(M));
+    for (size_t c = 0; c < M; ++c) out += "# column\t" + std::to_string(c) + '\t' + columns[c] + '\t' + std::to_string(used_of[c]) + '\n';
+    out += "edge_num\tcolumn\tmass_pearson\tmass_spearman\timbalance_pearson\timbalance_spearman\n";
+    for (size_t b = 0; b < N; ++b)
+        for (size_t c = 0; c < M; ++c) {
+            const epik_amd_correlation& r = records[c * N + b];
+            out += std::to_string(b) + '\t' + columns[c] + '\t' + g17_or_na(r.mass_pearson) + '\t' + g17_or_na(r.mass_spearman) + '\t' +
+                   g17_or_na(r.imbalance_pearson) + '\t' + g17_or_na(r.imbalance_spearman) + '\n';
+        }
+    return out;
+}
+
+std::string format_dispersion_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, uint32_t num_branches,
+                                  const epik_amd_dispersion* records)
+{
+    std::string out = used_head(samples, totals, "dispersion", "");
+    out += "edge_num\tmass_mean\tmass_var\tmass_sd\tmass_cv\tmass_vmr\timbalance_mean\timbalance_var\timbalance_sd\n";
+    for (size_t b = 0; b < num_branches; ++b) {
+        const epik_amd_dispersion& r = records[b];
+        out += std::to_string(b);
+        for (const double v : {r.mass_mean, r.mass_var, r.mass_sd, r.mass_cv, r.mass_vmr, r.imbalance_mean, r.imbalance_var, r.imbalance_sd})
+            out += '\t' + g17_or_na(v);
+        out += '\n';
     }
     return out;
 }

@@ -78,6 +78,19 @@ int rarefy_depths_valid(uint32_t depth_step, uint32_t num_depths, std::string& e
 int rarefy_curves(const uint64_t* best, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                   const double* branch_length, uint32_t depth_step, uint32_t num_depths, double* curve, std::string& err);
 
+/// num_columns in [1, 64] and no infinity in meta[S][M]: 0, or EPIK_AMD_ERR_INVALID with `err` naming the cause
+int correlation_columns_valid(const double* meta, uint32_t num_samples, uint32_t num_columns, std::string& err);
+
+/// Edge correlation by the rule (include/epik_amd.h): out[M][N] and used[M], every cell written.  The code behind
+/// epik_amd_cohort_correlation_host; libepik_amd's kernels (correlation_place.hip) give the same bits.  0, or
+/// EPIK_AMD_ERR_INVALID with `err` naming the branch whose first[] is above it, or as correlation_columns_valid.
+int correlation_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                        const double* meta, uint32_t num_columns, epik_amd_correlation* out, uint32_t* used, std::string& err);
+
+/// Edge dispersion by the rule: out[N], every cell written.  The code behind epik_amd_cohort_dispersion_host.
+int dispersion_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                       epik_amd_dispersion* out, std::string& err);
+
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
 /// name or path, a name given before, or a file that cannot be read; and for a list without any sample.
@@ -86,8 +99,21 @@ struct cohort_sample {
 };
 std::vector<cohort_sample> read_cohort_list(const std::string& list_file);
 
+/// The metadata of --cohort-correlation: a TSV whose header is sample<TAB>name1<TAB>... (1 to 64 unique, non-empty
+/// names), then one line per sample; blank lines and lines that begin with '#' are skipped.  A value is empty or NA (both
+/// missing: NaN in `values`) or a decimal number, [+-]?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?, read by strtod.  Throws
+/// std::runtime_error naming the line, and the column where there is one, for anything else, a value that overflows to
+/// infinity, a wrong field count or a sample given twice; and naming the sample of the list that the file lacks.  A line
+/// whose name is not in the list is skipped and counted.
+struct cohort_metadata {
+    std::vector<std::string> columns;
+    std::vector<double> values;  // [S][M], in the order of the list
+    size_t skipped = 0;
+};
+cohort_metadata read_cohort_metadata(const std::string& file, const std::vector<cohort_sample>& samples);
+
 /// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash | epca | epca_edges | kmeans |
-/// kmeans_centroids | alpha | rarefy
+/// kmeans_centroids | alpha | rarefy | correlation | dispersion
 std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir,
                                  const std::string& extension = ".tsv");
 
@@ -131,6 +157,17 @@ std::string format_alpha_tsv(const std::vector<cohort_sample>& samples, const ep
 /// a line for every used sample and every k_j <= n_s from curve[S][J][2]; doubles %.17g.
 std::string format_rarefy_tsv(const std::vector<cohort_sample>& samples, const uint64_t* reads, uint32_t depth_step,
                               uint32_t num_depths, const double* curve);
+/// cohort_correlation .tsv: "# epik_amd correlation v1  samples=S used=L columns=M", a "# unused<TAB>name" line per sample
+/// without mass (totals[s] = T_s is 0), a "# column<TAB>c<TAB>name<TAB>used_c" line per column, the column names edge_num
+/// column mass_pearson mass_spearman imbalance_pearson imbalance_spearman, then, long format, a line for every branch and
+/// every column from records[M][N]; doubles %.17g, NA as NA.
+std::string format_correlation_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                                   const std::vector<std::string>& columns, uint32_t num_branches,
+                                   const epik_amd_correlation* records, const uint32_t* used_of);
+/// cohort_dispersion .tsv: "# epik_amd dispersion v1  samples=S used=L", the "# unused" lines, the column names edge_num
+/// and the eight fields, then a line per branch.
+std::string format_dispersion_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, uint32_t num_branches,
+                                  const epik_amd_dispersion* records);
 /// `text` into `filename` through `filename`.part, renamed when all of it is written
 void write_through_part(const std::string& filename, const std::string& text);
 

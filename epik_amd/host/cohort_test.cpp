@@ -13,6 +13,11 @@
 //   cohort_test alpha <out.bin> <in.bin>    the alpha diversity of a `kr` input: epik_amd_alpha [S]
 //   cohort_test rarefy <out.bin> <in.bin> <depth_step> <num_depths>
 //                                           the rarefaction curves of a `kr` input whose cells are `best`: float64 [S][J][2]
+//   cohort_test correlation <out.bin> <in.bin> <meta.bin>
+//                                           the edge correlation of a `kr` input (its lengths are not used) with a raw
+//                                           `meta` file, float64 [S][M]: epik_amd_correlation [M][N], then uint32 used[M]
+//   cohort_test dispersion <out.bin> <in.bin>
+//                                           the edge dispersion of a `kr` input: epik_amd_dispersion [N]
 // An `add` input holds, little endian: uint64 n, keep, num_branches, num_samples; epik_amd_placement rows[n][keep];
 // uint32 n_rows[n]; uint32 kmer_counts[n][keep]; uint32 weights[n]; uint32 samples[n].
 // A `kr` input: uint64 num_samples, num_branches; uint64 mass[S][N]; uint32 first[N]; float64 branch_length[N].
@@ -196,9 +201,47 @@ int main(int argc, char** argv)
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }
+        if ((argc == 5 && std::strcmp(argv[1], "correlation") == 0) || (argc == 4 && std::strcmp(argv[1], "dispersion") == 0)) {
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto cells = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            std::string err;
+            std::ofstream out;
+            if (argc == 5) {
+                std::ifstream meta_in(argv[4], std::ios::binary | std::ios::ate);
+                if (!meta_in) throw std::runtime_error(std::string("cannot open ") + argv[4]);
+                const uint64_t bytes = (uint64_t)meta_in.tellg();
+                meta_in.seekg(0);
+                if (bytes == 0 || bytes % (S * sizeof(double)) != 0) throw std::runtime_error("the meta file is not float64 [S][M]");
+                const uint64_t M = bytes / (S * sizeof(double));
+                if (M > EPIK_AMD_CORRELATION_MAX_COLUMNS) throw std::runtime_error("the meta file has more than 64 columns");
+                const auto meta = read_array<double>(meta_in, S * M);
+                std::vector<epik_amd_correlation> records(M * N);
+                std::vector<uint32_t> used(M);
+                if (epik_amd::correlation_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), meta.data(), (uint32_t)M,
+                                                  records.data(), used.data(), err) != 0)
+                    throw std::runtime_error(err);
+                out.open(argv[2], std::ios::binary);
+                write_array(out, records.data(), records.size());
+                write_array(out, used.data(), used.size());
+            } else {
+                std::vector<epik_amd_dispersion> records(N);
+                if (epik_amd::dispersion_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), records.data(), err) != 0)
+                    throw std::runtime_error(err);
+                out.open(argv[2], std::ios::binary);
+                write_array(out, records.data(), records.size());
+            }
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
         std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin> | squash <out.bin> <in.bin> | "
                      "epca <out.bin> <in.bin> <K> | kmeans <out.bin> <in.bin> <K> <max_iterations> | alpha <out.bin> <in.bin> | "
-                     "rarefy <out.bin> <in.bin> <depth_step> <num_depths>\n";
+                     "rarefy <out.bin> <in.bin> <depth_step> <num_depths> | correlation <out.bin> <in.bin> <meta.bin> | "
+                     "dispersion <out.bin> <in.bin>\n";
         return 2;
     } catch (const std::exception& error) {
         std::cerr << "Error: " << error.what() << std::endl;

@@ -245,6 +245,12 @@ const char* kHelp =
     "                          device and write cohort_rarefy_<list>.tsv\n"
     "      --cohort-rarefy-step arg  With --cohort-rarefy: the distance between two depths (default: max(1, ceil(depth / 64)));\n"
     "                          floor(depth / step) must lie in [1, 256]\n"
+    "      --cohort-correlation arg  With --cohort: also correlate every branch's mass and imbalance with the per-sample metadata\n"
+    "                          of the TSV file arg (Czech et al. 2019: Pearson and Spearman; header sample<TAB>name1<TAB>..., 1 to 64\n"
+    "                          columns, empty or NA for a missing value) on the device and write cohort_correlation_<list>.tsv\n"
+    "      --cohort-dispersion With --cohort: also compute how every branch's mass and imbalance vary across the samples (mean,\n"
+    "                          variance, standard deviation, coefficient of variation, variance to mean) on the device and write\n"
+    "                          cohort_dispersion_<list>.tsv\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -285,7 +291,7 @@ options parse_args(int argc, char** argv)
         } else {
             continue;  // positional arguments are ignored (epik.py passes the query twice, epik.py:88,96)
         }
-        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca" || name == "cohort-alpha" || name == "taxonomy-per-read") && !have_value)) {  // flags
+        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca" || name == "cohort-alpha" || name == "cohort-dispersion" || name == "taxonomy-per-read") && !have_value)) {  // flags
             opt.values[name] = "1";
             continue;
         }
@@ -455,6 +461,11 @@ int main(int argc, char** argv)
                                          " / " + std::to_string(rarefy_step) + ") = " + std::to_string(rarefy_depths) +
                                          " depths of --cohort-rarefy: the number must lie in [1, 256]");
         }
+        const bool with_correlation = parsed.has("cohort-correlation"), with_dispersion = parsed.has("cohort-dispersion");
+        if (with_correlation && !with_cohort)
+            throw std::runtime_error("--cohort-correlation needs --cohort (it correlates the samples of the list with their metadata)");
+        if (with_dispersion && !with_cohort)
+            throw std::runtime_error("--cohort-dispersion needs --cohort (it measures the branches across the samples of the list)");
         if (with_cohort) {
             for (const char* other : {"mates", "profile-only", "profile", "assign"})
                 if (parsed.has(other)) throw std::runtime_error(std::string("--cohort does not work with --") + other);
@@ -499,6 +510,13 @@ int main(int argc, char** argv)
         // --cohort: the list of samples, every file of it looked at before the database or a device is
         std::vector<epik_amd::cohort_sample> cohort_samples;
         if (with_cohort) cohort_samples = epik_amd::read_cohort_list(query_file);
+        // --cohort-correlation: the metadata read, and every error of it named by its line, before the database or a device is
+        epik_amd::cohort_metadata metadata;
+        if (with_correlation) {
+            metadata = epik_amd::read_cohort_metadata(parsed.require("cohort-correlation"), cohort_samples);
+            std::cout << "Cohort metadata: " << metadata.columns.size() << " columns, " << metadata.skipped
+                      << " lines of samples that are not in the list skipped" << std::endl;
+        }
 
         // --taxonomy: the file read, and every error of it named by its line, before the database or a device is
         epik_amd::taxonomy taxa;
@@ -884,6 +902,8 @@ int main(int argc, char** argv)
         const auto cohort_kmeans_centroids_filename = epik_amd::make_cohort_filename("kmeans_centroids", query_file, output_dir);
         const auto cohort_alpha_filename = epik_amd::make_cohort_filename("alpha", query_file, output_dir);
         const auto cohort_rarefy_filename = epik_amd::make_cohort_filename("rarefy", query_file, output_dir);
+        const auto cohort_correlation_filename = epik_amd::make_cohort_filename("correlation", query_file, output_dir);
+        const auto cohort_dispersion_filename = epik_amd::make_cohort_filename("dispersion", query_file, output_dir);
         bool epca_converged = true, kmeans_converged = true;
         if (with_cohort) {
             // the handles' cohorts summed on the first device, read once, and the distances computed there
@@ -897,9 +917,11 @@ int main(int argc, char** argv)
             kmeans.num_clusters = kmeans_clusters, kmeans.max_iterations = kmeans_iterations;
             epik_amd::placer::cohort_diversity diversity;
             diversity.with_alpha = with_alpha, diversity.depth_step = rarefy_step, diversity.num_depths = rarefy_depths;
+            epik_amd::placer::cohort_edges edges;
+            edges.meta = metadata.values.data(), edges.num_columns = (uint32_t)metadata.columns.size(), edges.with_dispersion = with_dispersion;
             placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
                                with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr, with_kmeans ? &kmeans : nullptr,
-                               with_alpha || with_rarefy ? &diversity : nullptr);
+                               with_alpha || with_rarefy ? &diversity : nullptr, with_correlation || with_dispersion ? &edges : nullptr);
             epik_amd::write_through_part(cohort_samples_filename, epik_amd::format_cohort_samples_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_profile_filename, epik_amd::format_cohort_profile_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_kr_filename, epik_amd::format_cohort_kr_tsv(cohort_samples, kr));
@@ -932,6 +954,20 @@ int main(int argc, char** argv)
                     for (size_t b = 0; b < cohort.num_branches; ++b) reads[s] += cohort.best[s * cohort.num_branches + b];
                 epik_amd::write_through_part(cohort_rarefy_filename, epik_amd::format_rarefy_tsv(cohort_samples, reads.data(), rarefy_step,
                                                                                                  rarefy_depths, diversity.curve.data()));
+            }
+            if (with_correlation || with_dispersion) {
+                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
+                for (size_t s = 0; s < mass_of.size(); ++s)
+                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
+                if (with_correlation)
+                    epik_amd::write_through_part(cohort_correlation_filename,
+                                                 epik_amd::format_correlation_tsv(cohort_samples, mass_of.data(), metadata.columns,
+                                                                                  (uint32_t)cohort.num_branches, edges.correlation.data(),
+                                                                                  edges.used.data()));
+                if (with_dispersion)
+                    epik_amd::write_through_part(cohort_dispersion_filename,
+                                                 epik_amd::format_dispersion_tsv(cohort_samples, mass_of.data(), (uint32_t)cohort.num_branches,
+                                                                                 edges.dispersion.data()));
             }
             if (with_squash) {
                 epik_amd::write_through_part(cohort_squash_filename,
@@ -1006,6 +1042,8 @@ int main(int argc, char** argv)
                       << " iterations (converged=0 in " << cohort_kmeans_filename << ")" << std::endl;
         if (with_alpha) std::cout << "Cohort alpha diversity: " << cohort_alpha_filename << std::endl;
         if (with_rarefy) std::cout << "Cohort rarefaction curves: " << cohort_rarefy_filename << std::endl;
+        if (with_correlation) std::cout << "Cohort edge correlation: " << cohort_correlation_filename << std::endl;
+        if (with_dispersion) std::cout << "Cohort edge dispersion: " << cohort_dispersion_filename << std::endl;
         if (with_taxonomy) std::cout << "Taxa: " << taxa_filename << std::endl;
         if (taxonomy_per_read) std::cout << "Taxa of the reads: " << taxa_reads_filename << std::endl;
         if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;

@@ -36,6 +36,8 @@
 #pragma weak epik_amd_cohort_kmeans
 #pragma weak epik_amd_cohort_alpha
 #pragma weak epik_amd_cohort_rarefy
+#pragma weak epik_amd_cohort_correlation
+#pragma weak epik_amd_cohort_dispersion
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -290,8 +292,10 @@ void placer::read_taxonomy(uint64_t* direct, uint64_t* assigned, epik_amd_taxa_t
 
 void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                          epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans,
-                         cohort_diversity* diversity)
+                         cohort_diversity* diversity, cohort_edges* edges)
 {
+    if (edges && (!&epik_amd_cohort_correlation || !&epik_amd_cohort_dispersion))
+        throw std::runtime_error("GPU placer: this libepik_amd has no edge correlation and dispersion");
     if (diversity && (!&epik_amd_cohort_alpha || !&epik_amd_cohort_rarefy))
         throw std::runtime_error("GPU placer: this libepik_amd has no alpha diversity and rarefaction");
     if (kmeans && !&epik_amd_cohort_kmeans) throw std::runtime_error("GPU placer: this libepik_amd has no phylogenetic k-means");
@@ -348,6 +352,16 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
         diversity->curve.assign((size_t)_cohort_samples * diversity->num_depths * 2, 0.0);
         rc = epik_amd_cohort_rarefy(_cohorts[0], tree, length.data(), diversity->depth_step, diversity->num_depths,
                                     diversity->curve.data());
+    }
+    if (rc == EPIK_AMD_OK && edges && edges->num_columns) {
+        edges->correlation.assign((size_t)edges->num_columns * parent.size(), epik_amd_correlation{});
+        edges->used.assign(edges->num_columns, 0);
+        rc = epik_amd_cohort_correlation(_cohorts[0], tree, edges->meta, edges->num_columns, edges->correlation.data(),
+                                         edges->used.data());
+    }
+    if (rc == EPIK_AMD_OK && edges && edges->with_dispersion) {
+        edges->dispersion.assign(parent.size(), epik_amd_dispersion{});
+        rc = epik_amd_cohort_dispersion(_cohorts[0], tree, edges->dispersion.data());
     }
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);

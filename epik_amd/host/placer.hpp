@@ -194,9 +194,20 @@ public:
         std::vector<epik_amd_alpha> alpha;
         std::vector<double> curve;
     };
+    /// With `edges` (--cohort-correlation, --cohort-dispersion): num_columns > 0 asks for the edge correlation with
+    /// meta[S][M], correlation of M * num_branches records and used of M counts on return; with_dispersion asks for the edge
+    /// dispersion, dispersion of num_branches records on return.
+    struct cohort_edges {
+        const double* meta = nullptr;
+        uint32_t num_columns = 0;
+        bool with_dispersion = false;
+        std::vector<epik_amd_correlation> correlation;
+        std::vector<uint32_t> used;
+        std::vector<epik_amd_dispersion> dispersion;
+    };
     void read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                      epik_amd_squash_merge* merges = nullptr, uint32_t* num_merges = nullptr, cohort_epca* epca = nullptr,
-                     cohort_kmeans* kmeans = nullptr, cohort_diversity* diversity = nullptr);
+                     cohort_kmeans* kmeans = nullptr, cohort_diversity* diversity = nullptr, cohort_edges* edges = nullptr);
     /// --taxonomy: one device taxonomy object per handle (epik_amd_taxonomy) from taxon_parent[T] and label[N], with one
     /// row of cells per sample of the cohort (call set_cohort first) or one row; from then on place_flat goes through
     /// the epik_amd_placer_taxa_* entries: every unique sequence is added with the number of its records as weight, a

@@ -812,6 +812,35 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *       curve[s][j] = {BS(term_u), BS(term_r)}: the expected unrooted and rooted PD of k_j reads.
  *     k_j > n_s, or a sample that is not rarefiable: {-1.0, -1.0}.  Every cell of every output is written.
  *
+ * Edge correlation and edge dispersion (Czech et al. 2019; `gappa analyze correlation` and `dispersion`) of the cohort's
+ *   samples: which branches' masses or imbalances go up and down with a column of per-sample metadata, and which vary
+ *   across the samples at all.  From mass[S][N], first[N] and, for the correlation, meta[S][M], doubles, M in
+ *   [1, EPIK_AMD_CORRELATION_MAX_COLUMNS = 64]; any NaN in meta means "missing", an infinity is refused with
+ *   EPIK_AMD_ERR_INVALID.  No branch lengths are taken.  All arithmetic is IEEE double, every operation rounded on its
+ *   own, nothing fused; + - * /, sqrt (correctly rounded), min, max and comparisons only.
+ *   Used samples.  T_s, C_s[b], B_s[b] are exactly those of the KR rule.  Sample s is used iff T_s > 0.  Column c's set U_c
+ *     is the used samples whose meta[s][c] is not NaN, in ascending s, indexed j = 0 .. L_c - 1.
+ *   The two quantities of a branch: the mass xm_j[b] = (double)mass[s][b] / (double)T_s, and the imbalance
+ *     xi_j[b] = (B_s[b] + C_s[b]) - 1.0 of the epca rule, for an inner b (first[b] < b).
+ *   NA is the one bit pattern 0x7ff8000000000000 (EPIK_AMD_NA_BITS).  It is always written, never computed: no value that
+ *     reaches an output is an arithmetic NaN, so the guards below come before the divisions.
+ *   Pearson P(x, y) of two vectors over j = 0 .. L - 1:
+ *       mx = (sequential sum of x from +0.0, j ascending) / (double)L,   my likewise,   dx_j = x_j - mx,   dy_j = y_j - my,
+ *       sxx, syy, sxy = the sequential sums of dx * dx, dy * dy, dx * dy from +0.0, j ascending,
+ *       den = sqrt(sxx) * sqrt(syy);      NA unless L >= 3 and den > 0.0, else min(max(sxy / den, -1.0), 1.0).
+ *   Midranks: rank(x)_j = (double)#{i : x_i < x_j} + 0.5 * (double)(#{i : x_i == x_j} + 1), the second count with j itself.
+ *     Exact half-integers, so an implementation may sort or count.  -0.0 == +0.0, as the comparison says.
+ *   Per column c and branch b, over U_c, an epik_amd_correlation:
+ *       mass_pearson = P(xm[b], y_c),   mass_spearman = P(rank(xm[b]), rank(y_c)),
+ *       imbalance_pearson, imbalance_spearman: the same with xi; both NA where b is not inner (first[b] == b).
+ *     used[c] = L_c.  An implementation may share out branches, columns and kinds, never the samples of one sum; it may
+ *     reuse work between columns with the same U_c (mx, dx, sxx and the ranks of x do not depend on y).
+ *   Dispersion, per branch over all used samples (L of them), an epik_amd_dispersion:
+ *       mass_mean = mx,  mass_var = sxx / (double)L,  mass_sd = sqrt(mass_var),  mass_cv = mass_sd / mass_mean,
+ *       mass_vmr = mass_var / mass_mean (both NA unless mass_mean > 0.0),  imbalance_mean, imbalance_var, imbalance_sd
+ *       likewise (NA for a branch that is not inner).  All eight are NA when L = 0.
+ *   Every cell of every output is written.  With cells that wrapped the values mean nothing, but they are still these bits.
+ *
  * An epik_amd_cohort is an object of its own, created for a placer's device, num_branches and keep_at_most (whole
  * databases only, not a k-mer-space shard) and num_samples >= 1; all zero at create() and after reset().
  *   add_device  asynchronous on `stream`, allocates nothing: as epik_amd_profile_add_device, with d_samples (uint32 [n],
@@ -856,6 +885,20 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *               d_curve is float64 [S][J][2] in device memory, every cell written.  No readback; the cells are not changed.
  *               rarefy: the same into host memory, synchronous.
  *   rarefy_host the rule on the host from best[S][N] and first[N], no device; first[b] > b is refused.
+ *   correlation_device  checks the tree as epca_device (its device and N), the nulls, num_columns in [1, 64] and meta
+ *               (HOST, [S][M], read before the call returns) for an infinity.  The first correlation_device or
+ *               dispersion_device allocates a workspace of its own, kept until destroy(): with Sp = S rounded up to 32,
+ *               8 * N * Sp bytes (the masses, sample-fastest), 8 * Sp * (3 * 64 + 4 * 256) bytes (the columns, their
+ *               deviations and ranks, and the general path's vectors of 256 workgroups), 4 * Sp * 65 bytes (the lists
+ *               U_c) and under 4 KiB of tables.  d_out is epik_amd_correlation [M][N] and d_used uint32 [M] in device
+ *               memory, every cell written.  Once enqueued on `stream` it needs no readback.  The cells are not changed.
+ *               EPIK_AMD_CORRELATION_LDS=0, read at the call, forces the path that keeps a branch's vectors in global
+ *               memory (taken anyway beyond 1 024 samples); the bits are the same.
+ *               correlation: the same into host memory, synchronous.
+ *   correlation_host  the rule on the host from mass[S][N], first[N] and meta[S][M], no device; first[b] > b is refused.
+ *   dispersion_device  checks as correlation_device, takes no metadata; d_out is epik_amd_dispersion [N] in device memory,
+ *               every cell written.  dispersion: the same into host memory, synchronous.
+ *   dispersion_host  the rule on the host from mass[S][N] and first[N], no device; first[b] > b is refused.
  * cohort_reads / _strands / _frames / _mates: the profile_* twins with samples[n] (HOST uint32) beside the weights.
  */
 typedef struct epik_amd_cohort epik_amd_cohort;
@@ -944,6 +987,26 @@ int epik_amd_cohort_rarefy(epik_amd_cohort *cohort, const epik_amd_tree *tree, c
                            uint32_t depth_step, uint32_t num_depths, double *curve);
 int epik_amd_cohort_rarefy_host(const uint64_t *best, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                 const double *branch_length, uint32_t depth_step, uint32_t num_depths, double *curve);
+typedef struct epik_amd_correlation {
+    double mass_pearson, mass_spearman;
+    double imbalance_pearson, imbalance_spearman; /* EPIK_AMD_NA_BITS for a branch that is not inner */
+} epik_amd_correlation; /* 32 bytes */
+typedef struct epik_amd_dispersion {
+    double mass_mean, mass_var, mass_sd, mass_cv, mass_vmr;
+    double imbalance_mean, imbalance_var, imbalance_sd;
+} epik_amd_dispersion; /* 64 bytes */
+#define EPIK_AMD_CORRELATION_MAX_COLUMNS 64u
+#define EPIK_AMD_NA_BITS 0x7ff8000000000000ull
+int epik_amd_cohort_correlation_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *meta,
+                                       uint32_t num_columns, void *d_out, void *d_used, void *stream);
+int epik_amd_cohort_correlation(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *meta, uint32_t num_columns,
+                                epik_amd_correlation *out, uint32_t *used);
+int epik_amd_cohort_correlation_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                     const double *meta, uint32_t num_columns, epik_amd_correlation *out, uint32_t *used);
+int epik_amd_cohort_dispersion_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, void *d_out, void *stream);
+int epik_amd_cohort_dispersion(epik_amd_cohort *cohort, const epik_amd_tree *tree, epik_amd_dispersion *out);
+int epik_amd_cohort_dispersion_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                    epik_amd_dispersion *out);
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n);
 int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
