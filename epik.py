@@ -25,6 +25,9 @@ and cohort_kmeans_centroids_<list>.tsv; --cohort-kmeans-iterations M at the most
 --cohort-correlation FILE, with --cohort: the correlation of every branch's mass and imbalance with the columns of the
 per-sample metadata in FILE (a TSV), cohort_correlation_<list>.tsv.
 --cohort-dispersion, with --cohort: how every branch's mass and imbalance vary across the samples, cohort_dispersion_<list>.tsv.
+--cohort-permanova FILE, with --cohort: whether the groups of samples in every factor column of FILE (a TSV) differ
+(PERMANOVA over the KR distances), cohort_permanova_<list>.tsv; --cohort-permanova-permutations P (default 999),
+--cohort-permanova-seed X (default 1), --cohort-permanova-pairwise for every two groups as well.
 """
 from __future__ import annotations
 
@@ -122,6 +125,17 @@ PLACE_OPTIONS = [
                                                        "across the samples on the device (mean, variance, standard deviation, "
                                                        "coefficient of variation, variance to mean) and write "
                                                        "cohort_dispersion_<list>.tsv.")),
+    (("--cohort-permanova",), dict(type=click.Path(), default=None,
+                                   help="With --cohort: a TSV of per-sample factors (header sample<TAB>factor1<TAB>..., 1 to 64 "
+                                        "columns of labels, empty or NA for a missing one): also test whether the groups of every "
+                                        "column differ (PERMANOVA over the KR distances) on the device and write "
+                                        "cohort_permanova_<list>.tsv.")),
+    (("--cohort-permanova-permutations",), dict(type=click.IntRange(1, 999999), default=None,
+                                                help="With --cohort-permanova: the number of permutations [default: 999].")),
+    (("--cohort-permanova-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
+                                        help="With --cohort-permanova: the seed of the permutations, a uint64 [default: 1].")),
+    (("--cohort-permanova-pairwise",), dict(is_flag=True, help="With --cohort-permanova: also test every two groups of every "
+                                                               "column (at most 32 groups a column).")),
     (("--taxonomy",), dict(type=click.Path(), default=None,
                            help="A taxonomy file, one leaf_label<TAB>A;B;C line per reference leaf: also write taxa_<input>.tsv "
                                 "(per taxon the reads assigned to it and the mass placed in it, with clade sums) or, with "
@@ -150,7 +164,8 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                    mate_orientation="fr", assign=False, assign_mass=None, cohort=False, cohort_squash=False,
                    cohort_epca=False, cohort_epca_components=None, cohort_kmeans=None, cohort_kmeans_iterations=None,
                    cohort_alpha=False, cohort_rarefy=None, cohort_rarefy_step=None, taxonomy=None, taxonomy_mass=None,
-                   taxonomy_per_read=False, cohort_correlation=None, cohort_dispersion=False):
+                   taxonomy_per_read=False, cohort_correlation=None, cohort_dispersion=False, cohort_permanova=None,
+                   cohort_permanova_permutations=None, cohort_permanova_seed=None, cohort_permanova_pairwise=False):
     if taxonomy_mass is not None and taxonomy is None:
         raise click.UsageError("--taxonomy-mass needs --taxonomy")
     if taxonomy_per_read and taxonomy is None:
@@ -190,6 +205,13 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         raise click.UsageError("--cohort-correlation needs --cohort")
     if cohort_dispersion and not cohort:
         raise click.UsageError("--cohort-dispersion needs --cohort")
+    if cohort_permanova is not None and not cohort:
+        raise click.UsageError("--cohort-permanova needs --cohort")
+    for flag, given in (("--cohort-permanova-permutations", cohort_permanova_permutations is not None),
+                        ("--cohort-permanova-seed", cohort_permanova_seed is not None),
+                        ("--cohort-permanova-pairwise", cohort_permanova_pairwise)):
+        if given and cohort_permanova is None:
+            raise click.UsageError(f"{flag} needs --cohort-permanova")
     if cohort:
         for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
                             ("--assign", assign), ("--db-shard > 1", db_shard != 1)):
@@ -241,6 +263,14 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--cohort-correlation", str(cohort_correlation)]
     if cohort_dispersion:
         argv += ["--cohort-dispersion"]
+    if cohort_permanova is not None:
+        argv += ["--cohort-permanova", str(cohort_permanova)]
+        if cohort_permanova_permutations is not None:
+            argv += ["--cohort-permanova-permutations", str(int(cohort_permanova_permutations))]
+        if cohort_permanova_seed is not None:
+            argv += ["--cohort-permanova-seed", str(int(cohort_permanova_seed))]
+        if cohort_permanova_pairwise:
+            argv += ["--cohort-permanova-pairwise"]
     if taxonomy is not None:
         argv += ["--taxonomy", str(taxonomy)]
         if taxonomy_mass is not None:

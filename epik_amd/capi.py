@@ -53,6 +53,15 @@ DISPERSION = np.dtype([("mass_mean", np.float64), ("mass_var", np.float64), ("ma
                        ("mass_vmr", np.float64), ("imbalance_mean", np.float64), ("imbalance_var", np.float64),
                        ("imbalance_sd", np.float64)])
 CORRELATION_MAX_COLUMNS = 64
+#: epik_amd_permanova (56 bytes): a test's record; the doubles of an undefined test are NA_BITS
+PERMANOVA = np.dtype([("used", np.uint32), ("groups", np.uint32), ("at_most", np.uint64), ("ss_total", np.float64),
+                      ("ss_within", np.float64), ("f", np.float64), ("r2", np.float64), ("p", np.float64)])
+PERMANOVA_MAX_COLUMNS = 64
+PERMANOVA_MAX_GROUPS = 256
+PERMANOVA_MAX_PAIR_GROUPS = 32
+PERMANOVA_PAIR_SLOTS = 496
+PERMANOVA_MAX_PERMUTATIONS = 999999
+PERMANOVA_MISSING = 0xFFFFFFFF
 NA_BITS = 0x7FF8000000000000
 RAREFY_MAX_DEPTHS = 256
 RAREFY_MAX_DEPTH = 1 << 20
@@ -152,6 +161,10 @@ EXPORTS = (
     "epik_amd_cohort_dispersion_device",
     "epik_amd_cohort_dispersion",
     "epik_amd_cohort_dispersion_host",
+    "epik_amd_cohort_permanova_device",
+    "epik_amd_cohort_permanova",
+    "epik_amd_cohort_permanova_host",
+    "epik_amd_cohort_permanova_kr_host",
     "epik_amd_placer_cohort_reads",
     "epik_amd_placer_cohort_strands",
     "epik_amd_placer_cohort_frames",
@@ -518,6 +531,14 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_dispersion.argtypes = [vp, vp, vp]
     lib.epik_amd_cohort_dispersion_host.restype = i32
     lib.epik_amd_cohort_dispersion_host.argtypes = [vp, u32, u32, vp, vp]
+    lib.epik_amd_cohort_permanova_device.restype = i32
+    lib.epik_amd_cohort_permanova_device.argtypes = [vp, vp, vp, u32, u32, u64, i32, vp, vp, vp, vp]
+    lib.epik_amd_cohort_permanova.restype = i32
+    lib.epik_amd_cohort_permanova.argtypes = [vp, vp, vp, vp, u32, u32, u64, i32, vp, vp, vp]
+    lib.epik_amd_cohort_permanova_host.restype = i32
+    lib.epik_amd_cohort_permanova_host.argtypes = [vp, u32, u32, vp, vp, vp, u32, u32, u64, i32, vp, vp, vp]
+    lib.epik_amd_cohort_permanova_kr_host.restype = i32
+    lib.epik_amd_cohort_permanova_kr_host.argtypes = [vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp]
     lib.epik_amd_placer_cohort_reads.restype = i32
     lib.epik_amd_placer_cohort_reads.argtypes = [vp, vp, vp, vp, vp, vp, u64]
     for name in ("epik_amd_placer_cohort_strands", "epik_amd_placer_cohort_frames", "epik_amd_placer_cohort_mates"):

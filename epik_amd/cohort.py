@@ -27,6 +27,10 @@ Edge correlation with per-sample metadata and edge dispersion (the header's sixt
 `correlation_device` and `Cohort.dispersion` / `dispersion_device` on the device, `correlation_host` and `dispersion_host`
 on the host; `read_metadata` reads the file of --cohort-correlation; `format_correlation_tsv`, `format_dispersion_tsv` and
 their readers are the files of --cohort-correlation and --cohort-dispersion.
+
+PERMANOVA of the samples' groups over the KR distances (the header's seventh rule): `Cohort.permanova` /
+`permanova_device` on the device, `permanova_host` and `permanova_kr_host` on the host; `read_factors` reads the file of
+--cohort-permanova; `format_permanova_tsv` and `read_permanova_tsv` are its output file.
 """
 from __future__ import annotations
 
@@ -273,6 +277,72 @@ def dispersion_host(mass, first) -> np.ndarray:
 
 
 @dataclass
+class Permanova:
+    """What PERMANOVA gives: `records` `capi.PERMANOVA` [M][1 + Q] (slot 0 the whole column, the pair (g, h) at
+    `pair_slot(g, h)`; Q = 496 with pairwise, else 0), `ssw` float64 [M][1 + Q][P + 1] (SSW of permutation 0 .. P; None
+    where not asked for) and `group_ss` float64 [M][256] (W_g / n_g of the observed labelling)."""
+    records: np.ndarray
+    ssw: np.ndarray | None
+    group_ss: np.ndarray
+
+
+def pair_slot(g: int, h: int) -> int:
+    """The slot of the pair of groups g < h in a column's row of tests."""
+    if not 0 <= g < h < capi.PERMANOVA_MAX_PAIR_GROUPS:
+        raise ValueError("a pair is g < h < 32")
+    return 1 + h * (h - 1) // 2 + g
+
+
+def _labels(labels, num_samples: int) -> np.ndarray:
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    if labels.ndim != 2 or labels.shape[0] != num_samples:
+        raise ValueError(f"labels must be [num_samples = {num_samples}][num_columns]")
+    return labels
+
+
+def _permanova_buffers(m: int, permutations: int, pairwise: bool, with_ssw: bool):
+    slots = 1 + (capi.PERMANOVA_PAIR_SLOTS if pairwise else 0)
+    records = np.zeros((max(m, 1), slots), dtype=capi.PERMANOVA)
+    ssw = np.full((max(m, 1), slots, min(max(int(permutations), 0), capi.PERMANOVA_MAX_PERMUTATIONS) + 1), np.nan) if with_ssw else None
+    return records, ssw, np.full((max(m, 1), capi.PERMANOVA_MAX_GROUPS), np.nan)
+
+
+def permanova_kr_host(kr, totals, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
+                      with_ssw: bool = True) -> Permanova:
+    """PERMANOVA of the rule from a KR matrix kr[S][S] and totals[S] (T_s) on the host
+    (`epik_amd_cohort_permanova_kr_host`)."""
+    lib = capi.load()
+    kr = np.ascontiguousarray(kr, dtype=np.float64)
+    if kr.ndim != 2 or kr.shape[0] != kr.shape[1]:
+        raise ValueError("kr must be [num_samples][num_samples]")
+    s = kr.shape[0]
+    totals = np.ascontiguousarray(totals, dtype=np.uint64)
+    if totals.shape != (s,):
+        raise ValueError("one total mass per sample")
+    labels = _labels(labels, s)
+    records, ssw, group_ss = _permanova_buffers(labels.shape[1], permutations, pairwise, with_ssw)
+    capi.check(lib.epik_amd_cohort_permanova_kr_host(kr.ctypes.data, totals.ctypes.data, s, labels.ctypes.data, labels.shape[1],
+                                                     int(permutations), int(seed), int(bool(pairwise)), records.ctypes.data,
+                                                     ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data))
+    return Permanova(records, ssw, group_ss)
+
+
+def permanova_host(mass, first, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
+                   with_ssw: bool = True) -> Permanova:
+    """PERMANOVA of the rule for mass[S][N] and labels[S][M] (0xffffffff: missing) on the host
+    (`epik_amd_cohort_permanova_host`)."""
+    lib = capi.load()
+    mass, first, length = _cells_and_tree(mass, first, branch_length)
+    s, n = mass.shape
+    labels = _labels(labels, s)
+    records, ssw, group_ss = _permanova_buffers(labels.shape[1], permutations, pairwise, with_ssw)
+    capi.check(lib.epik_amd_cohort_permanova_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, labels.ctypes.data,
+                                                  labels.shape[1], int(permutations), int(seed), int(bool(pairwise)),
+                                                  records.ctypes.data, ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data))
+    return Permanova(records, ssw, group_ss)
+
+
+@dataclass
 class CohortCells:
     """What a cohort holds on the host: `mass` and `best` uint64 [S][N], `totals` a record array [S] with the fields
     of `epik_amd_profile_totals`, and `bad_samples`."""
@@ -513,6 +583,30 @@ class Cohort:
         out = _na(self.num_branches, capi.DISPERSION)
         capi.check(self._lib.epik_amd_cohort_dispersion(self._handle, self._tree_handle(tree, "dispersion"), out.ctypes.data))
         return out
+
+    def permanova_device(self, d_kr: int, labels, permutations: int, seed: int, pairwise: bool, d_out: int, d_ssw: int = 0,
+                         d_group_ss: int = 0, stream: int = 0) -> None:
+        """PERMANOVA of labels[S][M] (host; 0xffffffff: missing) over d_kr, float64 [S][S] in device memory as `kr_device`
+        wrote it, into d_out, `capi.PERMANOVA` [M][1 + Q], and where given d_ssw, float64 [M][1 + Q][P + 1], and
+        d_group_ss, float64 [M][256], every cell written; asynchronous on `stream` once the labels are copied, no readback
+        (`epik_amd_cohort_permanova_device`)."""
+        labels = _labels(labels, self.num_samples)
+        capi.check(self._lib.epik_amd_cohort_permanova_device(self._handle, d_kr or None, labels.ctypes.data, labels.shape[1],
+                                                              int(permutations), int(seed), int(bool(pairwise)), d_out or None,
+                                                              d_ssw or None, d_group_ss or None, stream or None))
+
+    def permanova(self, tree, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
+                  with_ssw: bool = False) -> Permanova:
+        """PERMANOVA of the samples' groups in every column of labels[S][M] over their KR distances
+        (`epik_amd_cohort_permanova`)."""
+        length = self._lengths(tree, branch_length)
+        labels = _labels(labels, self.num_samples)
+        records, ssw, group_ss = _permanova_buffers(labels.shape[1], permutations, pairwise, with_ssw)
+        capi.check(self._lib.epik_amd_cohort_permanova(self._handle, tree._handle, length.ctypes.data, labels.ctypes.data,
+                                                       labels.shape[1], int(permutations), int(seed), int(bool(pairwise)),
+                                                       records.ctypes.data, ssw.ctypes.data if with_ssw else None,
+                                                       group_ss.ctypes.data))
+        return Permanova(records, ssw, group_ss)
 
     def reset(self) -> None:
         capi.check(self._lib.epik_amd_cohort_reset(self._handle))
@@ -1035,6 +1129,153 @@ def read_dispersion_tsv(path: str):
     for i, r in enumerate(rows):
         records[i] = tuple(_na_or_float(x) for x in r[1:])
     return records, info
+
+
+def read_factors(path: str, names, pairwise: bool = False):
+    """The factor file of --cohort-permanova for the samples `names` of the list: (columns, uint32 labels [S][M] in list
+    order with 0xffffffff for a missing one, label_names [M][id], the number of lines skipped because their sample is not in
+    the list).  A TSV as `read_metadata`'s, but a value is a label: any non-empty text without a tab; empty or `NA` is
+    missing.  A column's labels are numbered by first appearance in the file among the list's samples.  ValueError naming the
+    line, and the column where there is one, for a wrong field count, a sample given twice or a column with more than 256
+    distinct labels (32 with `pairwise`), and naming the sample of the list that the file lacks."""
+    index = {name: s for s, name in enumerate(names)}
+    most = capi.PERMANOVA_MAX_PAIR_GROUPS if pairwise else capi.PERMANOVA_MAX_GROUPS
+    columns, labels, label_names, ids, seen, skipped = None, None, None, None, {}, 0
+    with open(path, newline="") as fh:
+        for number, line in enumerate(fh, 1):
+            line = line.rstrip("\n")
+            if line.endswith("\r"):
+                line = line[:-1]
+            if not line or line.startswith("#"):
+                continue
+            where = f"{path} line {number}"
+            fields = line.split("\t")
+            if columns is None:
+                if fields[0] != "sample":
+                    raise ValueError(f"{where}: the header must begin with 'sample'")
+                if not 2 <= len(fields) <= 1 + capi.PERMANOVA_MAX_COLUMNS:
+                    raise ValueError(f"{where}: the header names {len(fields) - 1} columns, not 1 to 64")
+                columns = fields[1:]
+                for c, name in enumerate(columns):
+                    if not name:
+                        raise ValueError(f"{where}: column {c + 1} has an empty name")
+                    if name in columns[:c]:
+                        raise ValueError(f"{where}: the column name '{name}' is given twice")
+                labels = np.full((len(names), len(columns)), capi.PERMANOVA_MISSING, dtype=np.uint32)
+                label_names, ids = [[] for _ in columns], [{} for _ in columns]
+                continue
+            if len(fields) != len(columns) + 1:
+                raise ValueError(f"{where}: {len(fields)} fields, not {len(columns) + 1}")
+            s = index.get(fields[0])
+            if s is None:
+                skipped += 1
+                continue
+            if s in seen:
+                raise ValueError(f"{where}: the sample '{fields[0]}' is given twice (first on line {seen[s]})")
+            seen[s] = number
+            for c, text in enumerate(fields[1:]):
+                if text in ("", "NA"):
+                    continue
+                if text not in ids[c]:
+                    if len(label_names[c]) == most:
+                        raise ValueError(f"{where}, column {columns[c]}: '{text}' is label number {most + 1}, more than {most}" +
+                                         (" (the most of --cohort-permanova-pairwise)" if pairwise else ""))
+                    ids[c][text] = len(label_names[c])
+                    label_names[c].append(text)
+                labels[s, c] = ids[c][text]
+    if columns is None:
+        raise ValueError(f"{path} has no header line")
+    for s, name in enumerate(names):
+        if s not in seen:
+            raise ValueError(f"{path} has no line for the sample '{name}'")
+    return columns, labels, label_names, skipped
+
+
+PERMANOVA_HEADER = "column\ta\tb\tused\tgroups\tss_total\tss_among\tss_within\tf\tr2\tat_most\tp"
+
+
+def groups_of(labels, totals):
+    """The groups of every column in the rule's order: [(label ids by group, sizes by group)] per column, the groups numbered
+    by first appearance among the samples with mass and a label."""
+    labels, out = np.asarray(labels), []
+    for c in range(labels.shape[1]):
+        order, sizes = [], {}
+        for s in range(labels.shape[0]):
+            v = int(labels[s, c])
+            if int(totals[s]) == 0 or v == capi.PERMANOVA_MISSING:
+                continue
+            if v not in sizes:
+                order.append(v)
+                sizes[v] = 0
+            sizes[v] += 1
+        out.append((order, [sizes[v] for v in order]))
+    return out
+
+
+def format_permanova_tsv(names, totals, columns, label_names, labels, permutations: int, seed: int, pairwise: bool, records,
+                         group_ss) -> str:
+    """cohort_permanova_<list>.tsv: the first line, a `# unused` line per sample without mass, a `# column` line per column
+    (its used samples and groups), a `# group` line per group (label, size, W_g / n_g of the observed labelling), the column
+    names, then per column the whole test (a = b = *) and, with pairwise, its pairs in slot order; ss_among is
+    ss_total - ss_within; doubles as %.17g, NA as NA."""
+    records, labels = np.asarray(records), np.asarray(labels)
+    slots = 1 + (capi.PERMANOVA_PAIR_SLOTS if pairwise else 0)
+    if records.dtype != capi.PERMANOVA or records.shape != (len(columns), slots) or labels.shape != (len(names), len(columns)):
+        raise ValueError("records must be capi.PERMANOVA [num_columns][1 + Q], labels [num_samples][num_columns]")
+    lines = _used_head("permanova", names, totals,
+                       f" columns={len(columns)} permutations={int(permutations)} seed={int(seed)} pairwise={int(bool(pairwise))}")
+    groups = groups_of(labels, totals)
+    lines += [f"# column\t{c}\t{name}\t{int(records['used'][c, 0])}\t{int(records['groups'][c, 0])}" for c, name in enumerate(columns)]
+    for c, (order, sizes) in enumerate(groups):
+        lines += [f"# group\t{c}\t{g}\t{label_names[c][v]}\t{sizes[g]}\t{_g17_or_na(group_ss[c][g])}" for g, v in enumerate(order)]
+    lines.append(PERMANOVA_HEADER)
+
+    def line(c, a, b, r):
+        total, within = float(r["ss_total"]), float(r["ss_within"])
+        among = total if total != total else total - within
+        return "\t".join([columns[c], a, b, str(int(r["used"])), str(int(r["groups"])), _g17_or_na(total), _g17_or_na(among),
+                          _g17_or_na(within), _g17_or_na(r["f"]), _g17_or_na(r["r2"]), str(int(r["at_most"])), _g17_or_na(r["p"])])
+
+    for c, (order, _) in enumerate(groups):
+        lines.append(line(c, "*", "*", records[c, 0]))
+        if pairwise:
+            for h in range(1, len(order)):
+                for g in range(h):
+                    lines.append(line(c, label_names[c][order[g]], label_names[c][order[h]], records[c, pair_slot(g, h)]))
+    return "\n".join(lines) + "\n"
+
+
+def read_permanova_tsv(path: str):
+    """(columns, rows [(column, a, b, record `capi.PERMANOVA`, ss_among)], groups [(c, g, label, n, ss_within_g)],
+    info {"samples", "used", "unused", "permutations", "seed", "pairwise", "column_used", "column_groups"})"""
+    with open(path, newline="") as fh:
+        head, info, line = _read_used_head(fh, "permanova", r" columns=(\d+) permutations=(\d+) seed=(\d+) pairwise=([01])", path)
+        info.update(permutations=int(head.group(4)), seed=int(head.group(5)), pairwise=head.group(6) == "1", column_used=[],
+                    column_groups=[])
+        columns, groups = [], []
+        while line.startswith("# column\t"):
+            _, c, name, used, count = line.split("\t")
+            if int(c) != len(columns):
+                raise ValueError(f"{path}: the columns are not numbered in order")
+            columns.append(name), info["column_used"].append(int(used)), info["column_groups"].append(int(count))
+            line = fh.readline().rstrip("\n")
+        while line.startswith("# group\t"):
+            _, c, g, label, n, ss = line.split("\t")
+            groups.append((int(c), int(g), label, int(n), _na_or_float(ss)))
+            line = fh.readline().rstrip("\n")
+        if line != PERMANOVA_HEADER or len(columns) != int(head.group(3)):
+            raise ValueError(f"{path}: not a cohort permanova file")
+        rows = []
+        for ln in fh:
+            r = ln.rstrip("\n").split("\t")
+            if len(r) != 12 or r[0] not in columns:
+                raise ValueError(f"{path}: not a row of a cohort permanova file: {ln!r}")
+            record = np.zeros((), dtype=capi.PERMANOVA)
+            record["used"], record["groups"], record["at_most"] = int(r[3]), int(r[4]), int(r[10])
+            for f, text in zip(("ss_total", "ss_within", "f", "r2", "p"), (r[5], r[7], r[8], r[9], r[11])):
+                record[f] = _na_or_float(text)
+            rows.append((r[0], r[1], r[2], record, _na_or_float(r[6])))
+    return columns, rows, groups, info
 
 
 def read_samples_tsv(path: str):

@@ -1,4 +1,4 @@
-// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, kmeans_place.hip, diversity_place.hip and correlation_place.hip share of a device cohort: the object
+// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, kmeans_place.hip, diversity_place.hip, correlation_place.hip and permanova_place.hip share of a device cohort: the object
 // itself and the launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering and the
 // edge principal components start from.
 #ifndef EPIK_AMD_COHORT_DEVICE_HPP
@@ -36,6 +36,10 @@ struct epik_amd_cohort {
     // the workspace of the edge correlation and dispersion, allocated by the first correlation_device or dispersion_device
     // (correlation_place.hip):
     void *d_correlation = nullptr;
+    // the workspace of PERMANOVA, allocated by the first permanova_device and grown by a call that needs more
+    // (permanova_place.hip):
+    void *d_permanova = nullptr;
+    size_t permanova_bytes = 0;
 };
 
 namespace epik_amd {

@@ -825,6 +825,227 @@ cohort_metadata read_cohort_metadata(const std::string& file, const std::vector<
     return meta;
 }
 
+namespace {
+
+// the rule's key of position i in permutation p: the splitmix64 finaliser of a counter
+inline uint64_t permanova_key(uint64_t seed, uint32_t p, uint32_t i)
+{
+    uint64_t z = seed + (((uint64_t)p << 32) | i) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// SSW(mu) over the compact block A[n][n]: the rule's three chains; W_g / n_g into `terms` where asked for
+double permanova_ssw(const std::vector<double>& A, size_t n, const std::vector<uint32_t>& mu, const std::vector<uint32_t>& size,
+                     std::vector<double>& t, double* terms)
+{
+    for (size_t i = 0; i < n; ++i) {
+        double acc = 0.0;
+        for (size_t j = i + 1; j < n; ++j)
+            if (mu[j] == mu[i]) acc = acc + A[i * n + j];
+        t[i] = acc;
+    }
+    double ssw = 0.0;
+    for (size_t g = 0; g < size.size(); ++g) {
+        double w = 0.0;
+        for (size_t i = 0; i < n; ++i)
+            if (mu[i] == g) w = w + t[i];
+        const double term = w / (double)size[g];
+        if (terms) terms[g] = term;
+        ssw = ssw + term;
+    }
+    return ssw;
+}
+
+// one test of the rule: the samples idx[n] with the groups lam[n] of sizes size[G]
+void permanova_test(const double* kr, size_t S, const std::vector<uint32_t>& idx, const std::vector<uint32_t>& lam,
+                    const std::vector<uint32_t>& size, uint32_t P, uint64_t seed, epik_amd_permanova& rec, double* ssw, double* terms)
+{
+    const size_t n = idx.size(), G = size.size();
+    rec.used = (uint32_t)n, rec.groups = (uint32_t)G;
+    if (G < 2 || n < G + 1) return;
+    std::vector<double> A(n * n), t(n);
+    for (size_t i = 0; i < n; ++i)
+        for (size_t j = 0; j < n; ++j) {
+            const double d = kr[(size_t)idx[i] * S + idx[j]];
+            A[i * n + j] = d * d;
+        }
+    const double T = permanova_ssw(A, n, std::vector<uint32_t>(n, 0), std::vector<uint32_t>(1, 1), t, nullptr);  // (W_0 / 1.0)
+    const double ssw0 = permanova_ssw(A, n, lam, size, t, terms);
+    if (ssw) ssw[0] = ssw0;
+    rec.ss_total = T / (double)n, rec.ss_within = ssw0;
+    const double among = rec.ss_total - ssw0;
+    if (rec.ss_total != 0.0) {
+        rec.r2 = among / rec.ss_total;
+        if (ssw0 != 0.0) rec.f = (among / (double)(G - 1)) / (ssw0 / (double)(n - G));
+    }
+    std::vector<std::pair<uint64_t, uint32_t>> keys(n);
+    std::vector<uint32_t> mu(n);
+    uint64_t at_most = 0;
+    for (uint32_t p = 1; p <= P; ++p) {
+        for (uint32_t i = 0; i < n; ++i) keys[i] = {permanova_key(seed, p, i), i};
+        std::sort(keys.begin(), keys.end());
+        for (size_t r = 0; r < n; ++r) mu[keys[r].second] = lam[r];  // (rank_p(keys[r].second) = r)
+        const double v = permanova_ssw(A, n, mu, size, t, nullptr);
+        if (ssw) ssw[p] = v;
+        at_most += v <= ssw0;
+    }
+    rec.at_most = at_most;
+    rec.p = (double)(1 + at_most) / (double)(P + 1);
+}
+
+}  // namespace
+
+int permanova_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint32_t num_columns, uint32_t num_permutations,
+                              bool pairwise, std::string& err)
+{
+    if (num_columns < 1 || num_columns > EPIK_AMD_PERMANOVA_MAX_COLUMNS) {
+        err = "num_columns = " + std::to_string(num_columns) + " is outside [1, 64]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if (num_permutations < 1 || num_permutations > EPIK_AMD_PERMANOVA_MAX_PERMUTATIONS) {
+        err = "num_permutations = " + std::to_string(num_permutations) + " is outside [1, 999999]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    for (size_t c = 0; c < num_columns; ++c) {
+        std::set<uint32_t> distinct;
+        for (size_t s = 0; s < num_samples; ++s) {
+            const uint32_t v = labels[s * num_columns + c];
+            if (v == EPIK_AMD_PERMANOVA_MISSING) continue;
+            if (v >= EPIK_AMD_PERMANOVA_MAX_GROUPS) {
+                err = "sample " + std::to_string(s) + ", column " + std::to_string(c) + ": the label " + std::to_string(v) +
+                      " is not below 256";
+                return EPIK_AMD_ERR_INVALID;
+            }
+            distinct.insert(v);
+        }
+        if (pairwise && distinct.size() > EPIK_AMD_PERMANOVA_MAX_PAIR_GROUPS) {
+            err = "column " + std::to_string(c) + ": " + std::to_string(distinct.size()) + " distinct labels, pairwise takes 32 at the most";
+            return EPIK_AMD_ERR_INVALID;
+        }
+    }
+    return EPIK_AMD_OK;
+}
+
+int permanova_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
+                            uint32_t num_columns, uint32_t num_permutations, uint64_t seed, bool pairwise, epik_amd_permanova* out,
+                            double* ssw, double* group_ss, std::string& err)
+{
+    const size_t S = num_samples, M = num_columns, P = num_permutations;
+    if (const int rc = permanova_arguments_valid(labels, num_samples, num_columns, num_permutations, pairwise, err); rc != EPIK_AMD_OK)
+        return rc;
+    const size_t slots = 1 + (pairwise ? EPIK_AMD_PERMANOVA_PAIR_SLOTS : 0);
+    const double na = na_value();
+    for (size_t e = 0; e < M * slots; ++e) out[e] = epik_amd_permanova{0, 0, 0, na, na, na, na, na};
+    if (ssw) std::fill(ssw, ssw + M * slots * (P + 1), na);
+    if (group_ss) std::fill(group_ss, group_ss + M * EPIK_AMD_PERMANOVA_MAX_GROUPS, na);
+    for (size_t c = 0; c < M; ++c) {
+        std::vector<uint32_t> idx, lam, size, group_of(EPIK_AMD_PERMANOVA_MAX_GROUPS, EPIK_AMD_PERMANOVA_MISSING);
+        for (size_t s = 0; s < S; ++s) {
+            const uint32_t v = labels[s * M + c];
+            if (totals[s] == 0 || v == EPIK_AMD_PERMANOVA_MISSING) continue;
+            if (group_of[v] == EPIK_AMD_PERMANOVA_MISSING) group_of[v] = (uint32_t)size.size(), size.push_back(0);
+            idx.push_back((uint32_t)s), lam.push_back(group_of[v]), ++size[group_of[v]];
+        }
+        permanova_test(kr, S, idx, lam, size, num_permutations, seed, out[c * slots], ssw ? ssw + c * slots * (P + 1) : nullptr,
+                       group_ss ? group_ss + c * EPIK_AMD_PERMANOVA_MAX_GROUPS : nullptr);
+        if (!pairwise) continue;
+        for (size_t h = 1; h < size.size(); ++h)
+            for (size_t g = 0; g < h; ++g) {
+                std::vector<uint32_t> sub, two;
+                for (size_t i = 0; i < idx.size(); ++i)
+                    if (lam[i] == g || lam[i] == h) sub.push_back(idx[i]), two.push_back(lam[i] == h);
+                const size_t slot = c * slots + 1 + h * (h - 1) / 2 + g;
+                permanova_test(kr, S, sub, two, {size[g], size[h]}, num_permutations, seed, out[slot],
+                               ssw ? ssw + slot * (P + 1) : nullptr, nullptr);
+            }
+    }
+    return EPIK_AMD_OK;
+}
+
+int permanova_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                      const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
+                      uint64_t seed, bool pairwise, epik_amd_permanova* out, double* ssw, double* group_ss, std::string& err)
+{
+    const size_t S = num_samples, N = num_branches;
+    if (const int rc = permanova_arguments_valid(labels, num_samples, num_columns, num_permutations, pairwise, err); rc != EPIK_AMD_OK)
+        return rc;
+    std::vector<double> kr(S * S);
+    if (const int rc = kr_matrix(mass, num_samples, num_branches, first, branch_length, kr.data(), err); rc != EPIK_AMD_OK) return rc;
+    std::vector<uint64_t> totals(S, 0);
+    for (size_t s = 0; s < S; ++s)
+        for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
+    return permanova_records_of_kr(kr.data(), totals.data(), num_samples, labels, num_columns, num_permutations, seed, pairwise, out,
+                                   ssw, group_ss, err);
+}
+
+cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise)
+{
+    std::ifstream in(file);
+    if (!in) throw std::runtime_error("--cohort-permanova: cannot open the factor file " + file);
+    std::map<std::string, size_t> index;
+    for (size_t s = 0; s < samples.size(); ++s) index[samples[s].name] = s;
+    cohort_factors factors;
+    std::vector<size_t> seen(samples.size(), 0);  // the line that gave the sample, 0: none yet
+    std::vector<std::map<std::string, uint32_t>> id_of;
+    bool have_header = false;
+    std::string line;
+    for (size_t number = 1; std::getline(in, line); ++number) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        const std::string where = "--cohort-permanova: " + file + " line " + std::to_string(number);
+        const auto fields = split_tabs(line);
+        if (!have_header) {
+            if (fields[0] != "sample") throw std::runtime_error(where + ": the header must begin with 'sample'");
+            if (fields.size() < 2 || fields.size() > 1 + EPIK_AMD_PERMANOVA_MAX_COLUMNS)
+                throw std::runtime_error(where + ": the header names " + std::to_string(fields.size() - 1) + " columns, not 1 to 64");
+            std::set<std::string> names;
+            for (size_t c = 1; c < fields.size(); ++c) {
+                if (fields[c].empty()) throw std::runtime_error(where + ": column " + std::to_string(c) + " has an empty name");
+                if (!names.insert(fields[c]).second)
+                    throw std::runtime_error(where + ": the column name '" + fields[c] + "' is given twice");
+                factors.columns.push_back(fields[c]);
+            }
+            factors.labels.assign(samples.size() * factors.columns.size(), EPIK_AMD_PERMANOVA_MISSING);
+            factors.names.resize(factors.columns.size()), id_of.resize(factors.columns.size());
+            have_header = true;
+            continue;
+        }
+        const size_t M = factors.columns.size();
+        if (fields.size() != M + 1)
+            throw std::runtime_error(where + ": " + std::to_string(fields.size()) + " fields, not " + std::to_string(M + 1));
+        const auto found = index.find(fields[0]);
+        if (found == index.end()) {
+            ++factors.skipped;
+            continue;
+        }
+        const size_t s = found->second;
+        if (seen[s])
+            throw std::runtime_error(where + ": the sample '" + fields[0] + "' is given twice (first on line " +
+                                     std::to_string(seen[s]) + ")");
+        seen[s] = number;
+        for (size_t c = 0; c < M; ++c) {
+            const std::string& v = fields[c + 1];
+            if (v.empty() || v == "NA") continue;
+            const auto [it, fresh] = id_of[c].emplace(v, (uint32_t)factors.names[c].size());
+            if (fresh) {
+                const size_t most = pairwise ? EPIK_AMD_PERMANOVA_MAX_PAIR_GROUPS : EPIK_AMD_PERMANOVA_MAX_GROUPS;
+                if (factors.names[c].size() == most)
+                    throw std::runtime_error(where + ", column " + factors.columns[c] + ": '" + v + "' is label number " +
+                                             std::to_string(most + 1) + ", more than " + std::to_string(most) +
+                                             (pairwise ? " (the most of --cohort-permanova-pairwise)" : ""));
+                factors.names[c].push_back(v);
+            }
+            factors.labels[s * M + c] = it->second;
+        }
+    }
+    if (!have_header) throw std::runtime_error("--cohort-permanova: " + file + " has no header line");
+    for (size_t s = 0; s < samples.size(); ++s)
+        if (!seen[s]) throw std::runtime_error("--cohort-permanova: " + file + " has no line for the sample '" + samples[s].name + "'");
+    return factors;
+}
+
 std::vector<cohort_sample> read_cohort_list(const std::string& list_file)
 {
     std::ifstream in(list_file);
@@ -1125,6 +1346,51 @@ std::string format_dispersion_tsv(const std::vector<cohort_sample>& samples, con
         for (const double v : {r.mass_mean, r.mass_var, r.mass_sd, r.mass_cv, r.mass_vmr, r.imbalance_mean, r.imbalance_var, r.imbalance_sd})
             out += '\t' + g17_or_na(v);
         out += '\n';
+    }
+    return out;
+}
+
+std::string format_permanova_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                                 const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
+                                 const uint32_t* labels, uint32_t num_permutations, uint64_t seed, bool pairwise,
+                                 const epik_amd_permanova* records, const double* group_ss)
+{
+    const size_t S = samples.size(), M = columns.size(), slots = 1 + (pairwise ? EPIK_AMD_PERMANOVA_PAIR_SLOTS : 0);
+    std::string out = used_head(samples, totals, "permanova",
+                                " columns=" + std::to_string(M) + " permutations=" + std::to_string(num_permutations) +
+                                    " seed=" + std::to_string(seed) + " pairwise=" + (pairwise ? "1" : "0"));
+    // the groups of every column in the rule's order: by first appearance among the used samples
+    std::vector<std::vector<uint32_t>> label_of(M), size_of(M);
+    for (size_t c = 0; c < M; ++c) {
+        std::map<uint32_t, uint32_t> group_of;
+        for (size_t s = 0; s < S; ++s) {
+            const uint32_t v = labels[s * M + c];
+            if (totals[s] == 0 || v == EPIK_AMD_PERMANOVA_MISSING) continue;
+            const auto [it, fresh] = group_of.emplace(v, (uint32_t)label_of[c].size());
+            if (fresh) label_of[c].push_back(v), size_of[c].push_back(0);
+            ++size_of[c][it->second];
+        }
+    }
+    for (size_t c = 0; c < M; ++c)
+        out += "# column\t" + std::to_string(c) + '\t' + columns[c] + '\t' + std::to_string(records[c * slots].used) + '\t' +
+               std::to_string(records[c * slots].groups) + '\n';
+    for (size_t c = 0; c < M; ++c)
+        for (size_t g = 0; g < label_of[c].size(); ++g)
+            out += "# group\t" + std::to_string(c) + '\t' + std::to_string(g) + '\t' + names[c][label_of[c][g]] + '\t' +
+                   std::to_string(size_of[c][g]) + '\t' + g17_or_na(group_ss[c * EPIK_AMD_PERMANOVA_MAX_GROUPS + g]) + '\n';
+    out += "column\ta\tb\tused\tgroups\tss_total\tss_among\tss_within\tf\tr2\tat_most\tp\n";
+    const auto line = [&](size_t c, const std::string& a, const std::string& b, const epik_amd_permanova& r) {
+        const double among = std::isnan(r.ss_total) ? r.ss_total : r.ss_total - r.ss_within;
+        out += columns[c] + '\t' + a + '\t' + b + '\t' + std::to_string(r.used) + '\t' + std::to_string(r.groups) + '\t' +
+               g17_or_na(r.ss_total) + '\t' + g17_or_na(among) + '\t' + g17_or_na(r.ss_within) + '\t' + g17_or_na(r.f) + '\t' +
+               g17_or_na(r.r2) + '\t' + std::to_string(r.at_most) + '\t' + g17_or_na(r.p) + '\n';
+    };
+    for (size_t c = 0; c < M; ++c) {
+        line(c, "*", "*", records[c * slots]);
+        if (!pairwise) continue;
+        for (size_t h = 1; h < label_of[c].size(); ++h)
+            for (size_t g = 0; g < h; ++g)
+                line(c, names[c][label_of[c][g]], names[c][label_of[c][h]], records[c * slots + 1 + h * (h - 1) / 2 + g]);
     }
     return out;
 }

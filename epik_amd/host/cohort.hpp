@@ -91,6 +91,22 @@ int correlation_records(const uint64_t* mass, uint32_t num_samples, uint32_t num
 int dispersion_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                        epik_amd_dispersion* out, std::string& err);
 
+/// num_columns in [1, 64], num_permutations in [1, 999 999], every label below 256 or 0xffffffff (missing) and, with
+/// pairwise, at most 32 distinct labels a column: 0, or EPIK_AMD_ERR_INVALID with `err` naming the cause
+int permanova_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint32_t num_columns, uint32_t num_permutations,
+                              bool pairwise, std::string& err);
+
+/// PERMANOVA by the rule (include/epik_amd.h) from a KR matrix kr[S][S] and totals[S] (T_s): out[M][1 + Q], and where not
+/// null ssw[M][1 + Q][P + 1] and group_ss[M][256], every cell written.  libepik_amd's kernels (permanova_place.hip) give the
+/// same bits.  0, or as permanova_arguments_valid.
+int permanova_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
+                            uint32_t num_columns, uint32_t num_permutations, uint64_t seed, bool pairwise, epik_amd_permanova* out,
+                            double* ssw, double* group_ss, std::string& err);
+/// The same from the cells: kr_matrix, then permanova_records_of_kr.  The code behind epik_amd_cohort_permanova_host.
+int permanova_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                      const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
+                      uint64_t seed, bool pairwise, epik_amd_permanova* out, double* ssw, double* group_ss, std::string& err);
+
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
 /// name or path, a name given before, or a file that cannot be read; and for a list without any sample.
@@ -112,8 +128,21 @@ struct cohort_metadata {
 };
 cohort_metadata read_cohort_metadata(const std::string& file, const std::vector<cohort_sample>& samples);
 
+/// The factors of --cohort-permanova: a TSV as read_cohort_metadata's, but a value is a label: any non-empty text without a
+/// tab; empty or NA is missing (0xffffffff in `labels`).  The labels of a column are numbered by first appearance in the
+/// file among the list's samples: names[c][id].  Throws std::runtime_error naming the line, and the column where there is
+/// one, for a wrong field count, a sample given twice, a column with more than 256 distinct labels (32 with `pairwise`);
+/// and naming the sample of the list that the file lacks.  A line whose name is not in the list is skipped and counted.
+struct cohort_factors {
+    std::vector<std::string> columns;
+    std::vector<std::vector<std::string>> names;  // [M]: the labels of a column by id
+    std::vector<uint32_t> labels;                 // [S][M], in the order of the list
+    size_t skipped = 0;
+};
+cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise);
+
 /// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash | epca | epca_edges | kmeans |
-/// kmeans_centroids | alpha | rarefy | correlation | dispersion
+/// kmeans_centroids | alpha | rarefy | correlation | dispersion | permanova
 std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir,
                                  const std::string& extension = ".tsv");
 
@@ -168,6 +197,16 @@ std::string format_correlation_tsv(const std::vector<cohort_sample>& samples, co
 /// and the eight fields, then a line per branch.
 std::string format_dispersion_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, uint32_t num_branches,
                                   const epik_amd_dispersion* records);
+/// cohort_permanova .tsv: "# epik_amd permanova v1  samples=S used=L columns=M permutations=P seed=X pairwise=0|1", the
+/// "# unused" lines, a "# column<TAB>c<TAB>name<TAB>used_c<TAB>groups_c" line per column, a "# group<TAB>c<TAB>g<TAB>label<TAB>n<TAB>
+/// ss_within_g" line per group (the groups in the rule's order, from labels[S][M], totals[S] and names[c][id]; ss_within_g from
+/// group_ss[M][256]), the column names column a b used groups ss_total ss_among ss_within f r2 at_most p, then per column
+/// the whole test (a = b = *) and, with pairwise, its pairs in slot order from records[M][1 + Q]; ss_among is
+/// ss_total - ss_within; doubles %.17g, NA as NA.
+std::string format_permanova_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                                 const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
+                                 const uint32_t* labels, uint32_t num_permutations, uint64_t seed, bool pairwise,
+                                 const epik_amd_permanova* records, const double* group_ss);
 /// `text` into `filename` through `filename`.part, renamed when all of it is written
 void write_through_part(const std::string& filename, const std::string& text);
 

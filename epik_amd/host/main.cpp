@@ -18,6 +18,7 @@
 // accepts DNA databases, epik-aa protein ones.
 #include <algorithm>
 #include <cctype>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -251,6 +252,14 @@ const char* kHelp =
     "      --cohort-dispersion With --cohort: also compute how every branch's mass and imbalance vary across the samples (mean,\n"
     "                          variance, standard deviation, coefficient of variation, variance to mean) on the device and write\n"
     "                          cohort_dispersion_<list>.tsv\n"
+    "      --cohort-permanova arg  With --cohort: also test, for every factor column of the TSV file arg (header\n"
+    "                          sample<TAB>factor1<TAB>..., 1 to 64 columns of labels, empty or NA for a missing one), whether its\n"
+    "                          groups of samples differ (PERMANOVA over the KR distances, Anderson 2001) on the device and write\n"
+    "                          cohort_permanova_<list>.tsv\n"
+    "      --cohort-permanova-permutations arg  With --cohort-permanova: the number of permutations in [1, 999999] (default: 999)\n"
+    "      --cohort-permanova-seed arg  With --cohort-permanova: the seed of the permutations, a uint64 (default: 1)\n"
+    "      --cohort-permanova-pairwise  With --cohort-permanova: also test every two groups of every column (at most 32 groups\n"
+    "                          a column)\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -291,7 +300,7 @@ options parse_args(int argc, char** argv)
         } else {
             continue;  // positional arguments are ignored (epik.py passes the query twice, epik.py:88,96)
         }
-        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca" || name == "cohort-alpha" || name == "cohort-dispersion" || name == "taxonomy-per-read") && !have_value)) {  // flags
+        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca" || name == "cohort-alpha" || name == "cohort-dispersion" || name == "cohort-permanova-pairwise" || name == "taxonomy-per-read") && !have_value)) {  // flags
             opt.values[name] = "1";
             continue;
         }
@@ -466,6 +475,31 @@ int main(int argc, char** argv)
             throw std::runtime_error("--cohort-correlation needs --cohort (it correlates the samples of the list with their metadata)");
         if (with_dispersion && !with_cohort)
             throw std::runtime_error("--cohort-dispersion needs --cohort (it measures the branches across the samples of the list)");
+        const bool with_permanova = parsed.has("cohort-permanova"), permanova_pairwise = parsed.has("cohort-permanova-pairwise");
+        if (with_permanova && !with_cohort)
+            throw std::runtime_error("--cohort-permanova needs --cohort (it tests the groups of the samples of the list)");
+        for (const char* dependent : {"cohort-permanova-permutations", "cohort-permanova-seed", "cohort-permanova-pairwise"})
+            if (parsed.has(dependent) && !with_permanova)
+                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-permanova" +
+                                         (with_cohort ? "" : " (and that needs --cohort )"));
+        uint32_t permanova_permutations = 999;
+        uint64_t permanova_seed = 1;
+        if (parsed.has("cohort-permanova-permutations")) {
+            const std::string text = parsed.require("cohort-permanova-permutations");
+            char* end = nullptr;
+            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
+            if (!end || *end || v < 1 || v > EPIK_AMD_PERMANOVA_MAX_PERMUTATIONS)
+                throw std::runtime_error("--cohort-permanova-permutations " + text + ": the number must lie in [1, 999999]");
+            permanova_permutations = (uint32_t)v;
+        }
+        if (parsed.has("cohort-permanova-seed")) {
+            const std::string text = parsed.require("cohort-permanova-seed");
+            char* end = nullptr;
+            errno = 0;
+            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
+            if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-permanova-seed " + text + ": not a uint64");
+            permanova_seed = v;
+        }
         if (with_cohort) {
             for (const char* other : {"mates", "profile-only", "profile", "assign"})
                 if (parsed.has(other)) throw std::runtime_error(std::string("--cohort does not work with --") + other);
@@ -515,6 +549,13 @@ int main(int argc, char** argv)
         if (with_correlation) {
             metadata = epik_amd::read_cohort_metadata(parsed.require("cohort-correlation"), cohort_samples);
             std::cout << "Cohort metadata: " << metadata.columns.size() << " columns, " << metadata.skipped
+                      << " lines of samples that are not in the list skipped" << std::endl;
+        }
+        // --cohort-permanova: the factors read, and every error of it named by its line, before the database or a device is
+        epik_amd::cohort_factors factors;
+        if (with_permanova) {
+            factors = epik_amd::read_cohort_factors(parsed.require("cohort-permanova"), cohort_samples, permanova_pairwise);
+            std::cout << "Cohort factors: " << factors.columns.size() << " columns, " << factors.skipped
                       << " lines of samples that are not in the list skipped" << std::endl;
         }
 
@@ -904,6 +945,7 @@ int main(int argc, char** argv)
         const auto cohort_rarefy_filename = epik_amd::make_cohort_filename("rarefy", query_file, output_dir);
         const auto cohort_correlation_filename = epik_amd::make_cohort_filename("correlation", query_file, output_dir);
         const auto cohort_dispersion_filename = epik_amd::make_cohort_filename("dispersion", query_file, output_dir);
+        const auto cohort_permanova_filename = epik_amd::make_cohort_filename("permanova", query_file, output_dir);
         bool epca_converged = true, kmeans_converged = true;
         if (with_cohort) {
             // the handles' cohorts summed on the first device, read once, and the distances computed there
@@ -919,9 +961,13 @@ int main(int argc, char** argv)
             diversity.with_alpha = with_alpha, diversity.depth_step = rarefy_step, diversity.num_depths = rarefy_depths;
             epik_amd::placer::cohort_edges edges;
             edges.meta = metadata.values.data(), edges.num_columns = (uint32_t)metadata.columns.size(), edges.with_dispersion = with_dispersion;
+            epik_amd::placer::cohort_permanova permanova;
+            permanova.labels = factors.labels.data(), permanova.num_columns = (uint32_t)factors.columns.size();
+            permanova.num_permutations = permanova_permutations, permanova.seed = permanova_seed, permanova.pairwise = permanova_pairwise;
             placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
                                with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr, with_kmeans ? &kmeans : nullptr,
-                               with_alpha || with_rarefy ? &diversity : nullptr, with_correlation || with_dispersion ? &edges : nullptr);
+                               with_alpha || with_rarefy ? &diversity : nullptr, with_correlation || with_dispersion ? &edges : nullptr,
+                               with_permanova ? &permanova : nullptr);
             epik_amd::write_through_part(cohort_samples_filename, epik_amd::format_cohort_samples_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_profile_filename, epik_amd::format_cohort_profile_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_kr_filename, epik_amd::format_cohort_kr_tsv(cohort_samples, kr));
@@ -968,6 +1014,16 @@ int main(int argc, char** argv)
                     epik_amd::write_through_part(cohort_dispersion_filename,
                                                  epik_amd::format_dispersion_tsv(cohort_samples, mass_of.data(), (uint32_t)cohort.num_branches,
                                                                                  edges.dispersion.data()));
+            }
+            if (with_permanova) {
+                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
+                for (size_t s = 0; s < mass_of.size(); ++s)
+                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
+                epik_amd::write_through_part(cohort_permanova_filename,
+                                             epik_amd::format_permanova_tsv(cohort_samples, mass_of.data(), factors.columns, factors.names,
+                                                                            factors.labels.data(), permanova_permutations, permanova_seed,
+                                                                            permanova_pairwise, permanova.records.data(),
+                                                                            permanova.group_ss.data()));
             }
             if (with_squash) {
                 epik_amd::write_through_part(cohort_squash_filename,
@@ -1044,6 +1100,7 @@ int main(int argc, char** argv)
         if (with_rarefy) std::cout << "Cohort rarefaction curves: " << cohort_rarefy_filename << std::endl;
         if (with_correlation) std::cout << "Cohort edge correlation: " << cohort_correlation_filename << std::endl;
         if (with_dispersion) std::cout << "Cohort edge dispersion: " << cohort_dispersion_filename << std::endl;
+        if (with_permanova) std::cout << "Cohort PERMANOVA: " << cohort_permanova_filename << std::endl;
         if (with_taxonomy) std::cout << "Taxa: " << taxa_filename << std::endl;
         if (taxonomy_per_read) std::cout << "Taxa of the reads: " << taxa_reads_filename << std::endl;
         if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;

@@ -38,6 +38,7 @@
 #pragma weak epik_amd_cohort_rarefy
 #pragma weak epik_amd_cohort_correlation
 #pragma weak epik_amd_cohort_dispersion
+#pragma weak epik_amd_cohort_permanova
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -292,8 +293,9 @@ void placer::read_taxonomy(uint64_t* direct, uint64_t* assigned, epik_amd_taxa_t
 
 void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                          epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans,
-                         cohort_diversity* diversity, cohort_edges* edges)
+                         cohort_diversity* diversity, cohort_edges* edges, cohort_permanova* permanova)
 {
+    if (permanova && !&epik_amd_cohort_permanova) throw std::runtime_error("GPU placer: this libepik_amd has no PERMANOVA");
     if (edges && (!&epik_amd_cohort_correlation || !&epik_amd_cohort_dispersion))
         throw std::runtime_error("GPU placer: this libepik_amd has no edge correlation and dispersion");
     if (diversity && (!&epik_amd_cohort_alpha || !&epik_amd_cohort_rarefy))
@@ -362,6 +364,14 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
     if (rc == EPIK_AMD_OK && edges && edges->with_dispersion) {
         edges->dispersion.assign(parent.size(), epik_amd_dispersion{});
         rc = epik_amd_cohort_dispersion(_cohorts[0], tree, edges->dispersion.data());
+    }
+    if (rc == EPIK_AMD_OK && permanova) {
+        const size_t slots = 1 + (permanova->pairwise ? EPIK_AMD_PERMANOVA_PAIR_SLOTS : 0);
+        permanova->records.assign(permanova->num_columns * slots, epik_amd_permanova{});
+        permanova->group_ss.assign((size_t)permanova->num_columns * EPIK_AMD_PERMANOVA_MAX_GROUPS, 0.0);
+        rc = epik_amd_cohort_permanova(_cohorts[0], tree, length.data(), permanova->labels, permanova->num_columns,
+                                       permanova->num_permutations, permanova->seed, permanova->pairwise ? 1 : 0,
+                                       permanova->records.data(), nullptr, permanova->group_ss.data());
     }
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);

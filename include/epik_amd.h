@@ -841,6 +841,42 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *       likewise (NA for a branch that is not inner).  All eight are NA when L = 0.
  *   Every cell of every output is written.  With cells that wrapped the values mean nothing, but they are still these bits.
  *
+ * PERMANOVA (Anderson 2001; `adonis`) of the cohort's samples over the KR distances: are the groups of a factor column
+ *   different?  From the matrix KR[S][S] of the KR rule, T_s, and labels[S][M], uint32, M in
+ *   [1, EPIK_AMD_PERMANOVA_MAX_COLUMNS = 64]: a label is below EPIK_AMD_PERMANOVA_MAX_GROUPS = 256, 0xffffffff means
+ *   "missing"; P = num_permutations in [1, 999 999] and a uint64 seed.  All arithmetic is IEEE double, every operation
+ *   rounded on its own, nothing fused; + - * / and comparisons only.
+ *   Used samples and groups.  Per column c, U_c is the samples with T_s > 0 and a label in c, in list order, L = |U_c|;
+ *     positions 0 .. L - 1 index U_c.  The groups are the distinct labels in U_c, numbered by first appearance: G groups
+ *     of sizes n_g; lambda_i is the group of position i.
+ *   Squared distances.  A[i][j] = KR(u_i, u_j) * KR(u_i, u_j): one multiply of the KR doubles.  Symmetric bit for bit.
+ *   The sums of a labelling mu.  Every sum is a sequential chain from +0.0:
+ *       t_i = sum over j > i, ascending, with mu_j == mu_i, of A[i][j],
+ *       W_g = sum over i, ascending, with mu_i == g, of t_i,
+ *       SSW(mu) = sum over g, ascending, of W_g / (double)n_g      (each term a division).
+ *     With every position in one group: r_i = t_i, T = W_0, and ss_total = T / (double)L.
+ *     An implementation may share out rows, groups, permutations and tests; it may never split one chain.
+ *   The observed test.  SSW_0 = SSW(lambda),  ss_within = SSW_0,  ss_among = ss_total - SSW_0,
+ *       f = (ss_among / (double)(G - 1)) / (SSW_0 / (double)(L - G)),   r2 = ss_among / ss_total.
+ *   Permutations.  For p = 1 .. P and position i, in uint64 arithmetic mod 2^64 (the splitmix64 finaliser of a counter):
+ *       z = seed + (((uint64)p << 32) | i) * 0x9E3779B97F4A7C15,   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9,
+ *       z = (z ^ z >> 27) * 0x94D049BB133111EB,                     key_p(i) = z ^ z >> 31.
+ *     rank_p(i) = the number of positions whose (key, position) is smaller (the keys of one permutation never tie: the
+ *     mix is a bijection; the position is in the rule anyway).  mu^p_i = lambda_{rank_p(i)}: the sizes do not change.
+ *     Permutation 0 is the identity, mu^0 = lambda.
+ *       at_most = #{p in 1 .. P : SSW(mu^p) <= SSW_0},     p = (double)(1 + at_most) / (double)(P + 1).
+ *     ss_total is the same for every labelling, so SSW <= SSW_0 is the textbook's F >= F_0 without a division.
+ *   Undefined.  G < 2 or L - G < 1: every double of the record is EPIK_AMD_NA_BITS and at_most = 0 (used = L and
+ *     groups = G are still written).  SSW_0 == 0.0 or ss_total == 0.0: f is NA; ss_total == 0.0: r2 is NA; p is defined.
+ *   Pairwise.  For groups g < h < EPIK_AMD_PERMANOVA_MAX_PAIR_GROUPS = 32 of a column: the same rule on the sub-list of
+ *     U_c whose label is g or h, the positions renumbered inside it (the keys come from those positions), g before h as
+ *     the two groups; undefined if n_g + n_h - 2 < 1.
+ *   Results.  out[M][1 + Q], Q = EPIK_AMD_PERMANOVA_PAIR_SLOTS = 496 with pairwise and 0 without: slot 0 is the whole
+ *     column, the pair (g, h) is slot 1 + h (h - 1) / 2 + g; a slot without a pair (h >= G) has used = groups = 0,
+ *     at_most = 0 and NA doubles.  ssw[M][1 + Q][P + 1], where asked for: SSW(mu^p) for p = 0 .. P, NA for a test that is
+ *     undefined or a slot without a pair.  group_ss[M][256], where asked for: W_g / (double)n_g of lambda for g < G of a
+ *     column whose test is defined, NA otherwise.  Every cell of every output is written.
+ *
  * An epik_amd_cohort is an object of its own, created for a placer's device, num_branches and keep_at_most (whole
  * databases only, not a k-mer-space shard) and num_samples >= 1; all zero at create() and after reset().
  *   add_device  asynchronous on `stream`, allocates nothing: as epik_amd_profile_add_device, with d_samples (uint32 [n],
@@ -899,6 +935,21 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *   dispersion_device  checks as correlation_device, takes no metadata; d_out is epik_amd_dispersion [N] in device memory,
  *               every cell written.  dispersion: the same into host memory, synchronous.
  *   dispersion_host  the rule on the host from mass[S][N] and first[N], no device; first[b] > b is refused.
+ *   permanova_device  takes d_kr, float64 [S][S] in device memory as kr_device wrote it for the cells as they are (so T_s
+ *               is in the cohort's workspace: a cohort whose kr_device never ran is refused), and labels (HOST [S][M],
+ *               read before the call returns): refused are a null cohort, d_kr, labels or d_out, num_columns outside
+ *               [1, 64], num_permutations outside [1, 999 999], a label in [256, 0xffffffff) and, with pairwise, a column
+ *               with more than 32 distinct labels.  Synchronises the device, then the workspace (grown where a call needs
+ *               more, kept until destroy(): with Sp = S rounded up to 32, 8 S^2 bytes of squared distances, 9 Sp bytes a
+ *               column, or 164 Sp with pairwise, for the labels and the tests' lists, 44 bytes a test, 1 KiB a column, and
+ *               44 Sp bytes for each of 256 workgroups of the general path).  d_out is epik_amd_permanova [M][1 + Q]; d_ssw (may be null) float64 [M][1 + Q][P + 1]; d_group_ss
+ *               (may be null) float64 [M][256]; all in device memory.  Once enqueued on `stream` it needs no readback.
+ *               The cells and d_kr are not changed.  A test of up to 1 024 positions keeps its labellings, keys and row
+ *               sums in LDS; beyond, or with EPIK_AMD_PERMANOVA_LDS=0 (read at the call), in global memory: the same bits.
+ *               permanova: runs kr_device itself (tree and lengths checked as there), the same into host memory,
+ *               synchronous; ssw and group_ss may be null.
+ *   permanova_host  the rule on the host from mass[S][N], first[N], branch_length[N] and the labels, no device.
+ *               permanova_kr_host: the same from a matrix kr[S][S] and totals[S] (T_s; only > 0 matters).
  * cohort_reads / _strands / _frames / _mates: the profile_* twins with samples[n] (HOST uint32) beside the weights.
  */
 typedef struct epik_amd_cohort epik_amd_cohort;
@@ -1007,6 +1058,30 @@ int epik_amd_cohort_dispersion_device(epik_amd_cohort *cohort, const epik_amd_tr
 int epik_amd_cohort_dispersion(epik_amd_cohort *cohort, const epik_amd_tree *tree, epik_amd_dispersion *out);
 int epik_amd_cohort_dispersion_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                     epik_amd_dispersion *out);
+typedef struct epik_amd_permanova {
+    uint32_t used, groups; /* L and G of the test; 0, 0 for a slot without a pair */
+    uint64_t at_most;      /* #{p >= 1 : SSW(mu^p) <= SSW_0} */
+    double ss_total, ss_within, f, r2, p;
+} epik_amd_permanova; /* 56 bytes */
+#define EPIK_AMD_PERMANOVA_MAX_COLUMNS 64u
+#define EPIK_AMD_PERMANOVA_MAX_GROUPS 256u
+#define EPIK_AMD_PERMANOVA_MAX_PAIR_GROUPS 32u
+#define EPIK_AMD_PERMANOVA_PAIR_SLOTS 496u
+#define EPIK_AMD_PERMANOVA_MAX_PERMUTATIONS 999999u
+#define EPIK_AMD_PERMANOVA_MISSING 0xffffffffu
+int epik_amd_cohort_permanova_device(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, uint32_t num_columns,
+                                     uint32_t num_permutations, uint64_t seed, int pairwise, void *d_out, void *d_ssw,
+                                     void *d_group_ss, void *stream);
+int epik_amd_cohort_permanova(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                              const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
+                              int pairwise, epik_amd_permanova *out, double *ssw, double *group_ss);
+int epik_amd_cohort_permanova_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                   const double *branch_length, const uint32_t *labels, uint32_t num_columns,
+                                   uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permanova *out, double *ssw,
+                                   double *group_ss);
+int epik_amd_cohort_permanova_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
+                                      uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
+                                      epik_amd_permanova *out, double *ssw, double *group_ss);
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n);
 int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
