@@ -28,6 +28,9 @@ per-sample metadata in FILE (a TSV), cohort_correlation_<list>.tsv.
 --cohort-permanova FILE, with --cohort: whether the groups of samples in every factor column of FILE (a TSV) differ
 (PERMANOVA over the KR distances), cohort_permanova_<list>.tsv; --cohort-permanova-permutations P (default 999),
 --cohort-permanova-seed X (default 1), --cohort-permanova-pairwise for every two groups as well.
+--cohort-edge-test FILE, with --cohort: on which branches the groups of every factor column of FILE (a TSV) differ (per
+branch ANOVA and Kruskal-Wallis of mass and imbalance by permutation, max-statistic adjusted), cohort_edgetest_<list>.tsv;
+--cohort-edge-test-permutations P (default 999), --cohort-edge-test-seed X (default 1).
 """
 from __future__ import annotations
 
@@ -136,6 +139,15 @@ PLACE_OPTIONS = [
                                         help="With --cohort-permanova: the seed of the permutations, a uint64 [default: 1].")),
     (("--cohort-permanova-pairwise",), dict(is_flag=True, help="With --cohort-permanova: also test every two groups of every "
                                                                "column (at most 32 groups a column).")),
+    (("--cohort-edge-test",), dict(type=click.Path(), default=None,
+                                   help="With --cohort: a TSV of per-sample factors as --cohort-permanova's (at most 32 labels a "
+                                        "column): also test on which branches the groups of every column differ (ANOVA and "
+                                        "Kruskal-Wallis of every branch's mass and imbalance by permutation, with the max-statistic "
+                                        "adjustment) on the device and write cohort_edgetest_<list>.tsv.")),
+    (("--cohort-edge-test-permutations",), dict(type=click.IntRange(1, 999999), default=None,
+                                                help="With --cohort-edge-test: the number of permutations [default: 999].")),
+    (("--cohort-edge-test-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
+                                        help="With --cohort-edge-test: the seed of the permutations, a uint64 [default: 1].")),
     (("--taxonomy",), dict(type=click.Path(), default=None,
                            help="A taxonomy file, one leaf_label<TAB>A;B;C line per reference leaf: also write taxa_<input>.tsv "
                                 "(per taxon the reads assigned to it and the mass placed in it, with clade sums) or, with "
@@ -165,7 +177,8 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                    cohort_epca=False, cohort_epca_components=None, cohort_kmeans=None, cohort_kmeans_iterations=None,
                    cohort_alpha=False, cohort_rarefy=None, cohort_rarefy_step=None, taxonomy=None, taxonomy_mass=None,
                    taxonomy_per_read=False, cohort_correlation=None, cohort_dispersion=False, cohort_permanova=None,
-                   cohort_permanova_permutations=None, cohort_permanova_seed=None, cohort_permanova_pairwise=False):
+                   cohort_permanova_permutations=None, cohort_permanova_seed=None, cohort_permanova_pairwise=False,
+                   cohort_edge_test=None, cohort_edge_test_permutations=None, cohort_edge_test_seed=None):
     if taxonomy_mass is not None and taxonomy is None:
         raise click.UsageError("--taxonomy-mass needs --taxonomy")
     if taxonomy_per_read and taxonomy is None:
@@ -212,6 +225,12 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                         ("--cohort-permanova-pairwise", cohort_permanova_pairwise)):
         if given and cohort_permanova is None:
             raise click.UsageError(f"{flag} needs --cohort-permanova")
+    if cohort_edge_test is not None and not cohort:
+        raise click.UsageError("--cohort-edge-test needs --cohort")
+    for flag, given in (("--cohort-edge-test-permutations", cohort_edge_test_permutations is not None),
+                        ("--cohort-edge-test-seed", cohort_edge_test_seed is not None)):
+        if given and cohort_edge_test is None:
+            raise click.UsageError(f"{flag} needs --cohort-edge-test")
     if cohort:
         for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
                             ("--assign", assign), ("--db-shard > 1", db_shard != 1)):
@@ -271,6 +290,12 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
             argv += ["--cohort-permanova-seed", str(int(cohort_permanova_seed))]
         if cohort_permanova_pairwise:
             argv += ["--cohort-permanova-pairwise"]
+    if cohort_edge_test is not None:
+        argv += ["--cohort-edge-test", str(cohort_edge_test)]
+        if cohort_edge_test_permutations is not None:
+            argv += ["--cohort-edge-test-permutations", str(int(cohort_edge_test_permutations))]
+        if cohort_edge_test_seed is not None:
+            argv += ["--cohort-edge-test-seed", str(int(cohort_edge_test_seed))]
     if taxonomy is not None:
         argv += ["--taxonomy", str(taxonomy)]
         if taxonomy_mass is not None:

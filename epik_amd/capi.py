@@ -62,6 +62,17 @@ PERMANOVA_MAX_PAIR_GROUPS = 32
 PERMANOVA_PAIR_SLOTS = 496
 PERMANOVA_MAX_PERMUTATIONS = 999999
 PERMANOVA_MISSING = 0xFFFFFFFF
+#: epik_amd_edgetest_family (48 bytes) and epik_amd_edgetest (208 bytes): a (column, branch)'s record of the edge test; the
+#: families are mass, rank(mass), imbalance, rank(imbalance); the doubles of an undefined family are NA_BITS
+EDGETEST_FAMILY = np.dtype([("eta2", np.float64), ("stat", np.float64), ("p", np.float64), ("p_adj", np.float64),
+                            ("at_least", np.uint64), ("max_at_least", np.uint64)])
+EDGETEST = np.dtype([("used", np.uint32), ("groups", np.uint32), ("family", EDGETEST_FAMILY, (4,)), ("top_mass", np.uint32),
+                     ("top_imbalance", np.uint32)])
+EDGETEST_MAX_COLUMNS = 64
+EDGETEST_MAX_GROUPS = 32
+EDGETEST_FAMILIES = 4
+EDGETEST_MAX_PERMUTATIONS = 999999
+EDGETEST_MISSING = 0xFFFFFFFF
 NA_BITS = 0x7FF8000000000000
 RAREFY_MAX_DEPTHS = 256
 RAREFY_MAX_DEPTH = 1 << 20
@@ -165,6 +176,9 @@ EXPORTS = (
     "epik_amd_cohort_permanova",
     "epik_amd_cohort_permanova_host",
     "epik_amd_cohort_permanova_kr_host",
+    "epik_amd_cohort_edgetest_device",
+    "epik_amd_cohort_edgetest",
+    "epik_amd_cohort_edgetest_host",
     "epik_amd_placer_cohort_reads",
     "epik_amd_placer_cohort_strands",
     "epik_amd_placer_cohort_frames",
@@ -539,6 +553,12 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_permanova_host.argtypes = [vp, u32, u32, vp, vp, vp, u32, u32, u64, i32, vp, vp, vp]
     lib.epik_amd_cohort_permanova_kr_host.restype = i32
     lib.epik_amd_cohort_permanova_kr_host.argtypes = [vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp]
+    lib.epik_amd_cohort_edgetest_device.restype = i32
+    lib.epik_amd_cohort_edgetest_device.argtypes = [vp, vp, vp, u32, u32, u64, vp, vp, vp, vp]
+    lib.epik_amd_cohort_edgetest.restype = i32
+    lib.epik_amd_cohort_edgetest.argtypes = [vp, vp, vp, u32, u32, u64, vp, vp, vp]
+    lib.epik_amd_cohort_edgetest_host.restype = i32
+    lib.epik_amd_cohort_edgetest_host.argtypes = [vp, u32, u32, vp, vp, u32, u32, u64, vp, vp, vp]
     lib.epik_amd_placer_cohort_reads.restype = i32
     lib.epik_amd_placer_cohort_reads.argtypes = [vp, vp, vp, vp, vp, vp, u64]
     for name in ("epik_amd_placer_cohort_strands", "epik_amd_placer_cohort_frames", "epik_amd_placer_cohort_mates"):

@@ -31,6 +31,11 @@ their readers are the files of --cohort-correlation and --cohort-dispersion.
 PERMANOVA of the samples' groups over the KR distances (the header's seventh rule): `Cohort.permanova` /
 `permanova_device` on the device, `permanova_host` and `permanova_kr_host` on the host; `read_factors` reads the file of
 --cohort-permanova; `format_permanova_tsv` and `read_permanova_tsv` are its output file.
+
+The edge test (the header's eighth rule): which branches differ between the groups of a factor column, by permutation with
+the max-statistic adjustment: `Cohort.edgetest` / `edgetest_device` on the device, `edgetest_host` on the host;
+`read_factors(..., most=32)` reads the file of --cohort-edge-test; `format_edgetest_tsv` and `read_edgetest_tsv` are its
+output file.
 """
 from __future__ import annotations
 
@@ -343,6 +348,37 @@ def permanova_host(mass, first, branch_length, labels, permutations: int = 999, 
 
 
 @dataclass
+class Edgetest:
+    """What the edge test gives: `records` `capi.EDGETEST` [M][N], `stat` float64 [M][4][N][P + 1] (eta of the labellings
+    0 .. P; None where not asked for) and `max` float64 [M][4][P + 1] (the maxima over a family's defined branches)."""
+    records: np.ndarray
+    stat: np.ndarray | None
+    max: np.ndarray | None
+
+
+def _edgetest_buffers(m: int, n: int, permutations: int, with_stat: bool, with_max: bool):
+    row = min(max(int(permutations), 0), capi.EDGETEST_MAX_PERMUTATIONS) + 1
+    records = np.zeros((max(m, 1), n), dtype=capi.EDGETEST)
+    stat = np.full((max(m, 1), capi.EDGETEST_FAMILIES, n, row), np.nan) if with_stat else None
+    return records, stat, np.full((max(m, 1), capi.EDGETEST_FAMILIES, row), np.nan) if with_max else None
+
+
+def edgetest_host(mass, first, labels, permutations: int = 999, seed: int = 1, with_stat: bool = True,
+                  with_max: bool = True) -> Edgetest:
+    """The edge test of the rule for mass[S][N] and labels[S][M] (0xffffffff: missing) on the host, one thread
+    (`epik_amd_cohort_edgetest_host`)."""
+    lib = capi.load()
+    mass, first = _mass_and_first(mass, first)
+    s, n = mass.shape
+    labels = _labels(labels, s)
+    records, stat, most = _edgetest_buffers(labels.shape[1], n, permutations, with_stat, with_max)
+    capi.check(lib.epik_amd_cohort_edgetest_host(mass.ctypes.data, s, n, first.ctypes.data, labels.ctypes.data, labels.shape[1],
+                                                 int(permutations), int(seed), records.ctypes.data,
+                                                 stat.ctypes.data if with_stat else None, most.ctypes.data if with_max else None))
+    return Edgetest(records, stat, most)
+
+
+@dataclass
 class CohortCells:
     """What a cohort holds on the host: `mass` and `best` uint64 [S][N], `totals` a record array [S] with the fields
     of `epik_amd_profile_totals`, and `bad_samples`."""
@@ -607,6 +643,29 @@ class Cohort:
                                                        records.ctypes.data, ssw.ctypes.data if with_ssw else None,
                                                        group_ss.ctypes.data))
         return Permanova(records, ssw, group_ss)
+
+    def edgetest_device(self, tree, labels, permutations: int, seed: int, d_out: int, d_stat: int = 0, d_max: int = 0,
+                        stream: int = 0) -> None:
+        """The edge test of labels[S][M] (host; 0xffffffff: missing) into d_out, `capi.EDGETEST` [M][N], and where given
+        d_stat, float64 [M][4][N][P + 1], and d_max, float64 [M][4][P + 1], all in device memory, every cell written;
+        asynchronous on `stream` once the labels are copied, no readback (`epik_amd_cohort_edgetest_device`)."""
+        labels = _labels(labels, self.num_samples)
+        capi.check(self._lib.epik_amd_cohort_edgetest_device(self._handle, self._tree_handle(tree, "edgetest_device"),
+                                                             labels.ctypes.data, labels.shape[1], int(permutations), int(seed),
+                                                             d_out or None, d_stat or None, d_max or None, stream or None))
+
+    def edgetest(self, tree, labels, permutations: int = 999, seed: int = 1, with_stat: bool = False,
+                 with_max: bool = False) -> Edgetest:
+        """Which branches differ between the groups of every column of labels[S][M]: per branch the one-way ANOVA and
+        Kruskal-Wallis of its mass and imbalance by permutation, with the max-statistic adjustment
+        (`epik_amd_cohort_edgetest`)."""
+        labels = _labels(labels, self.num_samples)
+        records, stat, most = _edgetest_buffers(labels.shape[1], self.num_branches, permutations, with_stat, with_max)
+        capi.check(self._lib.epik_amd_cohort_edgetest(self._handle, self._tree_handle(tree, "edgetest"), labels.ctypes.data,
+                                                      labels.shape[1], int(permutations), int(seed), records.ctypes.data,
+                                                      stat.ctypes.data if with_stat else None,
+                                                      most.ctypes.data if with_max else None))
+        return Edgetest(records, stat, most)
 
     def reset(self) -> None:
         capi.check(self._lib.epik_amd_cohort_reset(self._handle))
@@ -1131,15 +1190,18 @@ def read_dispersion_tsv(path: str):
     return records, info
 
 
-def read_factors(path: str, names, pairwise: bool = False):
+def read_factors(path: str, names, pairwise: bool = False, most: int | None = None):
     """The factor file of --cohort-permanova for the samples `names` of the list: (columns, uint32 labels [S][M] in list
     order with 0xffffffff for a missing one, label_names [M][id], the number of lines skipped because their sample is not in
     the list).  A TSV as `read_metadata`'s, but a value is a label: any non-empty text without a tab; empty or `NA` is
     missing.  A column's labels are numbered by first appearance in the file among the list's samples.  ValueError naming the
     line, and the column where there is one, for a wrong field count, a sample given twice or a column with more than 256
-    distinct labels (32 with `pairwise`), and naming the sample of the list that the file lacks."""
+    distinct labels (32 with `pairwise`; `most`, where given, is the cap instead: 32 for --cohort-edge-test), and naming the
+    sample of the list that the file lacks."""
     index = {name: s for s, name in enumerate(names)}
-    most = capi.PERMANOVA_MAX_PAIR_GROUPS if pairwise else capi.PERMANOVA_MAX_GROUPS
+    capped = most is not None
+    if not capped:
+        most = capi.PERMANOVA_MAX_PAIR_GROUPS if pairwise else capi.PERMANOVA_MAX_GROUPS
     columns, labels, label_names, ids, seen, skipped = None, None, None, None, {}, 0
     with open(path, newline="") as fh:
         for number, line in enumerate(fh, 1):
@@ -1179,7 +1241,7 @@ def read_factors(path: str, names, pairwise: bool = False):
                 if text not in ids[c]:
                     if len(label_names[c]) == most:
                         raise ValueError(f"{where}, column {columns[c]}: '{text}' is label number {most + 1}, more than {most}" +
-                                         (" (the most of --cohort-permanova-pairwise)" if pairwise else ""))
+                                         (" (the most of --cohort-permanova-pairwise)" if pairwise and not capped else ""))
                     ids[c][text] = len(label_names[c])
                     label_names[c].append(text)
                 labels[s, c] = ids[c][text]
@@ -1275,6 +1337,71 @@ def read_permanova_tsv(path: str):
             for f, text in zip(("ss_total", "ss_within", "f", "r2", "p"), (r[5], r[7], r[8], r[9], r[11])):
                 record[f] = _na_or_float(text)
             rows.append((r[0], r[1], r[2], record, _na_or_float(r[6])))
+    return columns, rows, groups, info
+
+
+EDGETEST_HEADER = "edge_num\tcolumn" + "".join(f"\t{kind}_{field}" for kind in ("mass", "imbalance")
+                                               for field in ("eta2", "f", "p", "p_adj", "top", "h", "kw_p", "kw_p_adj"))
+
+
+def format_edgetest_tsv(names, totals, columns, label_names, labels, permutations: int, seed: int, records) -> str:
+    """cohort_edgetest_<list>.tsv: the first line, a `# unused` line per sample without mass, a `# column` line per column
+    (its used samples and groups), a `# group` line per group (label, size), the column names, then per column a line per
+    branch with at least one defined family: eta2, F, p, p_adj, the label of the group with the largest mean, H and the
+    Kruskal-Wallis p and p_adj, of the mass and then of the imbalance; doubles as %.17g, NA as NA."""
+    records, labels = np.asarray(records), np.asarray(labels)
+    if records.dtype != capi.EDGETEST or records.ndim != 2 or records.shape[0] != len(columns) or \
+            labels.shape != (len(names), len(columns)):
+        raise ValueError("records must be capi.EDGETEST [num_columns][num_branches], labels [num_samples][num_columns]")
+    lines = _used_head("edgetest", names, totals, f" columns={len(columns)} permutations={int(permutations)} seed={int(seed)}")
+    groups = groups_of(labels, totals)
+    lines += [f"# column\t{c}\t{name}\t{int(records['used'][c, 0])}\t{int(records['groups'][c, 0])}" for c, name in enumerate(columns)]
+    for c, (order, sizes) in enumerate(groups):
+        lines += [f"# group\t{c}\t{g}\t{label_names[c][v]}\t{sizes[g]}" for g, v in enumerate(order)]
+    lines.append(EDGETEST_HEADER)
+    for c, (order, _) in enumerate(groups):
+        defined = ~np.isnan(records["family"]["eta2"][c]).all(axis=1)
+        for b in np.flatnonzero(defined):
+            r = records[c, b]
+            fields = [str(int(b)), columns[c]]
+            for kind, top in ((0, int(r["top_mass"])), (1, int(r["top_imbalance"]))):
+                plain, ranks = r["family"][2 * kind], r["family"][2 * kind + 1]
+                fields += [_g17_or_na(plain["eta2"]), _g17_or_na(plain["stat"]), _g17_or_na(plain["p"]), _g17_or_na(plain["p_adj"]),
+                           "NA" if top == capi.EDGETEST_MISSING else label_names[c][order[top]], _g17_or_na(ranks["stat"]),
+                           _g17_or_na(ranks["p"]), _g17_or_na(ranks["p_adj"])]
+            lines.append("\t".join(fields))
+    return "\n".join(lines) + "\n"
+
+
+def read_edgetest_tsv(path: str):
+    """(columns, rows [{"edge_num", "column", "mass_eta2", ..., "imbalance_kw_p_adj"}] with floats (nan for NA) and the
+    `top` fields as labels (None for NA), groups [(c, g, label, n)], info {"samples", "used", "unused", "permutations",
+    "seed", "column_used", "column_groups"})"""
+    with open(path, newline="") as fh:
+        head, info, line = _read_used_head(fh, "edgetest", r" columns=(\d+) permutations=(\d+) seed=(\d+)", path)
+        info.update(permutations=int(head.group(4)), seed=int(head.group(5)), column_used=[], column_groups=[])
+        columns, groups = [], []
+        while line.startswith("# column\t"):
+            _, c, name, used, count = line.split("\t")
+            if int(c) != len(columns):
+                raise ValueError(f"{path}: the columns are not numbered in order")
+            columns.append(name), info["column_used"].append(int(used)), info["column_groups"].append(int(count))
+            line = fh.readline().rstrip("\n")
+        while line.startswith("# group\t"):
+            _, c, g, label, n = line.split("\t")
+            groups.append((int(c), int(g), label, int(n)))
+            line = fh.readline().rstrip("\n")
+        if line != EDGETEST_HEADER or len(columns) != int(head.group(3)):
+            raise ValueError(f"{path}: not a cohort edgetest file")
+        keys, rows = EDGETEST_HEADER.split("\t"), []
+        for ln in fh:
+            r = ln.rstrip("\n").split("\t")
+            if len(r) != len(keys) or r[1] not in columns:
+                raise ValueError(f"{path}: not a row of a cohort edgetest file: {ln!r}")
+            row = {"edge_num": int(r[0]), "column": r[1]}
+            for key, text in zip(keys[2:], r[2:]):
+                row[key] = (None if text == "NA" else text) if key.endswith("_top") else _na_or_float(text)
+            rows.append(row)
     return columns, rows, groups, info
 
 

@@ -1,14 +1,17 @@
-// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, kmeans_place.hip, diversity_place.hip, correlation_place.hip and permanova_place.hip share of a device cohort: the object
+// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, kmeans_place.hip, diversity_place.hip, correlation_place.hip, permanova_place.hip and edgetest_place.hip share of a device cohort: the object
 // itself and the launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering and the
-// edge principal components start from.
+// edge principal components start from; and the device code that the correlation, PERMANOVA and the edge test have in
+// common: a branch's vectors and midranks, the permutation key, and a column's list and groups.
 #ifndef EPIK_AMD_COHORT_DEVICE_HPP
 #define EPIK_AMD_COHORT_DEVICE_HPP
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 
 #include "epik_amd.h"
+#include "host_entry.hpp"
 
 struct epik_amd_cohort {
     int device = 0;
@@ -40,6 +43,10 @@ struct epik_amd_cohort {
     // (permanova_place.hip):
     void *d_permanova = nullptr;
     size_t permanova_bytes = 0;
+    // the workspace of the edge test, allocated by the first edgetest_device and grown by a call that needs more
+    // (edgetest_place.hip):
+    void *d_edgetest = nullptr;
+    size_t edgetest_bytes = 0;
 };
 
 namespace epik_amd {
@@ -57,6 +64,176 @@ int cohort_normalise_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree,
 // epik_amd_cohort_kr_device: the checks, the workspace, the lengths, then the normalise and distance kernels on `stream`
 int cohort_kr_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out,
                       hipStream_t stream);
+
+// correlation_place.hip: the checks of epca_device, the device drained, T_s and the planes C and B, the workspace of the
+// correlation, then xm as a plane [N][Sp], sample-fastest, on `stream`: *d_first the tree's first[], *d_X the plane
+int cohort_mass_plane_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, hipStream_t stream, const uint32_t **d_first,
+                              const double **d_X);
+
+constexpr uint32_t kCohortLdsSamples = 1024;   // the most samples whose four vectors stay in LDS (32 KiB)
+constexpr uint32_t kCohortCountSamples = 128;  // up to here the LDS path counts its ranks; beyond, it sorts
+static_assert(kBlock == 256 && kCohortLdsSamples % kBlock == 0 && 2 * kCohortCountSamples <= kCohortLdsSamples);
+
+#ifdef __HIPCC__
+// the midrank of x_j among x[0 .. L): the rule's two counts
+__device__ inline double midrank(const double *x, uint32_t L, double xj)
+{
+    uint32_t less = 0, equal = 0;
+#pragma unroll 4
+    for (uint32_t i = 0; i < L; ++i) {
+        const double v = x[i];  // a broadcast
+        less += v < xj, equal += v == xj;
+    }
+    return __dadd_rn((double)less, __dmul_rn(0.5, (double)(equal + 1)));
+}
+
+// the midrank of xj among the finite values of sorted[0 .. P), ascending (the padding is +inf): two binary searches, the
+// number of values below xj and of those not above it -- the rule's two counts, found in another way
+__device__ inline double midrank_sorted(const double *sorted, uint32_t P, double xj)
+{
+    uint32_t lo = 0, hi = P;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) / 2;
+        if (sorted[mid] < xj) lo = mid + 1; else hi = mid;
+    }
+    const uint32_t less = lo;
+    hi = P;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) / 2;
+        if (sorted[mid] <= xj) lo = mid + 1; else hi = mid;
+    }
+    return __dadd_rn((double)less, __dmul_rn(0.5, (double)(lo - less + 1)));
+}
+
+// d[0 .. L) becomes d - mean(d); returns the sequential sum of the squares: one lane's work
+__device__ inline double centre(double *d, uint32_t L, double *mean_out = nullptr)
+{
+    double acc = 0.0;
+    for (uint32_t j = 0; j < L; ++j) acc = __dadd_rn(acc, d[j]);
+    const double mean = __ddiv_rn(acc, (double)L);
+    if (mean_out) *mean_out = mean;
+    double ss = 0.0;
+    for (uint32_t j = 0; j < L; ++j) {
+        const double dev = __dsub_rn(d[j], mean);
+        d[j] = dev;
+        ss = __dadd_rn(ss, __dmul_rn(dev, dev));
+    }
+    return ss;
+}
+
+// A workgroup of kBlock lanes: xm and xi of a branch over the L samples of `list` into vec[0 .. L) and vec[pitch ..], and
+// with kRanks their midranks into vec[2 pitch ..] and vec[3 pitch ..] (xi and its ranks are 0.0 unless `inner`).  xrow, crow
+// and brow are the branch's rows of the planes.  kLds: vec is LDS with pitch = kCohortLdsSamples, and beyond
+// kCohortCountSamples samples the values are sorted in the ranks' place (a bitonic network over the next power of two, the
+// padding +inf), every lane's ranks found in the sorted copy and kept in registers, then stored over it; else a lane ranks
+// its j against broadcasts of all i.  The ranks are exact either way.  Every condition around a barrier is uniform; the
+// vectors are complete when it returns.
+template <bool kLds, bool kRanks>
+__device__ inline void branch_vectors(const double *__restrict__ xrow, const double *__restrict__ crow, const double *__restrict__ brow,
+                                      const uint32_t *__restrict__ list, uint32_t L, bool inner, double *vec, uint32_t pitch)
+{
+    for (uint32_t j = threadIdx.x; j < L; j += kBlock) {
+        const uint32_t s = list[j];
+        vec[j] = xrow[s];
+        vec[pitch + j] = inner ? __dsub_rn(__dadd_rn(brow[s], crow[s]), 1.0) : 0.0;
+    }
+    __syncthreads();
+    if (kRanks && kLds && L > kCohortCountSamples) {
+        double *sm = vec + 2 * pitch, *si = vec + 3 * pitch;
+        uint32_t P = 2 * kCohortCountSamples;
+        while (P < L) P <<= 1;  // (<= kCohortLdsSamples)
+        for (uint32_t j = threadIdx.x; j < P; j += kBlock) {
+            sm[j] = j < L ? vec[j] : HUGE_VAL;
+            si[j] = j < L ? vec[pitch + j] : HUGE_VAL;
+        }
+        __syncthreads();
+        for (uint32_t k = 2; k <= P; k <<= 1)
+            for (uint32_t step = k >> 1; step > 0; step >>= 1) {
+                for (uint32_t e = threadIdx.x; e < P / 2; e += kBlock) {
+                    const uint32_t i = 2 * e - (e & (step - 1)), l = i + step;  // (l < P)
+                    const bool up = (i & k) == 0;
+                    const double a = sm[i], c = sm[l];
+                    if ((a > c) == up) sm[i] = c, sm[l] = a;
+                    if (inner) {
+                        const double ai = si[i], ci = si[l];
+                        if ((ai > ci) == up) si[i] = ci, si[l] = ai;
+                    }
+                }
+                __syncthreads();
+            }
+        double rank_m[kCohortLdsSamples / kBlock], rank_i[kCohortLdsSamples / kBlock];
+#pragma unroll
+        for (uint32_t q = 0; q < kCohortLdsSamples / kBlock; ++q) {
+            const uint32_t j = q * kBlock + threadIdx.x;
+            rank_m[q] = j < L ? midrank_sorted(sm, P, vec[j]) : 0.0;
+            rank_i[q] = j < L && inner ? midrank_sorted(si, P, vec[pitch + j]) : 0.0;
+        }
+        __syncthreads();  // (every search is done: the sorted copies become the ranks)
+#pragma unroll
+        for (uint32_t q = 0; q < kCohortLdsSamples / kBlock; ++q) {
+            const uint32_t j = q * kBlock + threadIdx.x;
+            if (j < L) sm[j] = rank_m[q], si[j] = rank_i[q];
+        }
+        __syncthreads();
+    } else if (kRanks) {
+        for (uint32_t j = threadIdx.x; j < L; j += kBlock) {
+            vec[2 * pitch + j] = midrank(vec, L, vec[j]);
+            vec[3 * pitch + j] = inner ? midrank(vec + pitch, L, vec[pitch + j]) : 0.0;
+        }
+        __syncthreads();
+    }
+}
+
+// the PERMANOVA rule's key of position i in permutation p: the splitmix64 finaliser of a counter
+__device__ inline uint64_t permutation_key(uint64_t seed, uint32_t p, uint32_t i)
+{
+    uint64_t z = seed + (((uint64_t)p << 32) | i) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// the lanes of a wave whose `flag` is set append (sample, group) to the list in the order of the lanes; returns how many did
+__device__ inline uint32_t append_in_order(bool flag, uint32_t at, uint32_t sample, uint32_t group, uint32_t *__restrict__ idx,
+                                           uint8_t *__restrict__ lam)
+{
+    const unsigned long long mask = __ballot(flag);
+    if (flag) {
+        const uint32_t pos = at + __popcll(mask & ((1ull << threadIdx.x) - 1));
+        idx[pos] = sample, lam[pos] = (uint8_t)group;
+    }
+    return __popcll(mask);
+}
+
+// One wave (a workgroup of kWave lanes): the PERMANOVA rule's U_c of a column in list order into idx and lam, its groups
+// numbered by first appearance (ballots keep the order) and their sizes.  lab: the column's labels by sample, each below
+// kGroups (a power of two) or `missing`; group_of[kGroups] and size[kGroups] are the workgroup's, in LDS.  L and G are uniform.
+template <uint32_t kGroups>
+__device__ inline void column_list(const uint64_t *__restrict__ total, const uint32_t *__restrict__ lab, uint32_t num_samples,
+                                   uint32_t missing, uint32_t *group_of, uint32_t *size, uint32_t *__restrict__ idx,
+                                   uint8_t *__restrict__ lam, uint32_t &L, uint32_t &G)
+{
+    for (uint32_t g = threadIdx.x; g < kGroups; g += kWave) group_of[g] = missing, size[g] = 0;
+    __syncthreads();
+    L = 0, G = 0;
+    for (uint32_t base = 0; base < num_samples; base += kWave) {
+        const uint32_t s = base + threadIdx.x;
+        const uint32_t v = s < num_samples ? lab[s] : missing;
+        const bool flag = s < num_samples && total[s] != 0 && v != missing;  // (v < kGroups: the host has checked)
+        for (;;) {  // the labels not seen before take the next numbers, the first lane first
+            const unsigned long long fresh = __ballot(flag && group_of[v & (kGroups - 1)] == missing);
+            if (!fresh) break;
+            if (threadIdx.x == (uint32_t)__ffsll((long long)fresh) - 1) group_of[v] = G;
+            ++G;
+            __syncthreads();
+        }
+        const uint32_t g = flag ? group_of[v] : 0;
+        if (flag) atomicAdd(&size[g], 1u);
+        L += append_in_order(flag, L, s, g, idx, lam);
+    }
+    __syncthreads();
+}
+#endif
 
 }  // namespace epik_amd
 #endif

@@ -416,7 +416,7 @@ void free_cohort(epik_amd_cohort *cohort)
     (void)hipFree(cohort->d_cells), (void)hipFree(cohort->d_prefix), (void)hipFree(cohort->d_total);
     (void)hipFree(cohort->d_planes), (void)hipFree(cohort->d_half), (void)hipFree(cohort->d_squash), (void)hipFree(cohort->d_epca);
     (void)hipFree(cohort->d_kmeans), (void)hipFree(cohort->d_diversity), (void)hipFree(cohort->d_rarefy);
-    (void)hipFree(cohort->d_correlation), (void)hipFree(cohort->d_permanova);
+    (void)hipFree(cohort->d_correlation), (void)hipFree(cohort->d_permanova), (void)hipFree(cohort->d_edgetest);
 }
 
 }  // namespace

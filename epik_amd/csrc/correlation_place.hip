@@ -46,8 +46,8 @@ using namespace epik_amd;
 constexpr uint32_t kTile = kCohortTile;                         // the planes' sample pitch is a multiple of it
 constexpr uint32_t kColumns = EPIK_AMD_CORRELATION_MAX_COLUMNS;
 constexpr uint32_t kAllUsed = kColumns;                         // the list after the groups': every used sample
-constexpr uint32_t kLdsSamples = 1024;                          // the most samples whose four vectors stay in LDS (32 KiB)
-constexpr uint32_t kCountSamples = 128;                         // up to here the LDS path counts its ranks; beyond, it sorts
+constexpr uint32_t kLdsSamples = kCohortLdsSamples;             // the most samples whose four vectors stay in LDS (32 KiB)
+constexpr uint32_t kCountSamples = kCohortCountSamples;         // up to here the LDS path counts its ranks; beyond, it sorts
 constexpr uint32_t kGeneralBlocks = 256;                        // workgroups of the general path: each has a slice
 constexpr uint32_t kVectors = 4;                                // xm, xi, rank(xm), rank(xi)
 constexpr uint32_t kTotals = 5;                                 // the totals that end a row of cells (cohort_place.hip)
@@ -148,51 +148,6 @@ __global__ __launch_bounds__(kWave) void correlation_lists_kernel(const uint64_t
     }
 }
 
-// the midrank of x_j among x[0 .. L): the rule's two counts
-__device__ inline double midrank(const double *x, uint32_t L, double xj)
-{
-    uint32_t less = 0, equal = 0;
-#pragma unroll 4
-    for (uint32_t i = 0; i < L; ++i) {
-        const double v = x[i];  // a broadcast
-        less += v < xj, equal += v == xj;
-    }
-    return __dadd_rn((double)less, __dmul_rn(0.5, (double)(equal + 1)));
-}
-
-// the midrank of xj among the finite values of sorted[0 .. P), ascending (the padding is +inf): two binary searches, the
-// number of values below xj and of those not above it -- the rule's two counts, found in another way
-__device__ inline double midrank_sorted(const double *sorted, uint32_t P, double xj)
-{
-    uint32_t lo = 0, hi = P;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) / 2;
-        if (sorted[mid] < xj) lo = mid + 1; else hi = mid;
-    }
-    const uint32_t less = lo;
-    hi = P;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) / 2;
-        if (sorted[mid] <= xj) lo = mid + 1; else hi = mid;
-    }
-    return __dadd_rn((double)less, __dmul_rn(0.5, (double)(lo - less + 1)));
-}
-
-// d[0 .. L) becomes d - mean(d); returns the sequential sum of the squares: one lane's work
-__device__ inline double centre(double *d, uint32_t L)
-{
-    double acc = 0.0;
-    for (uint32_t j = 0; j < L; ++j) acc = __dadd_rn(acc, d[j]);
-    const double mean = __ddiv_rn(acc, (double)L);
-    double ss = 0.0;
-    for (uint32_t j = 0; j < L; ++j) {
-        const double dev = __dsub_rn(d[j], mean);
-        d[j] = dev;
-        ss = __dadd_rn(ss, __dmul_rn(dev, dev));
-    }
-    return ss;
-}
-
 __global__ __launch_bounds__(kBlock) void correlation_columns_kernel(const double *__restrict__ y, const uint32_t *__restrict__ lists,
                                                                      uint32_t num_columns, uint32_t padded, double *__restrict__ dy,
                                                                      double *__restrict__ dr, CorrTables *__restrict__ tab,
@@ -244,58 +199,7 @@ __global__ __launch_bounds__(kBlock) void correlation_branch_kernel(const double
         const bool defined = L >= (kDisp ? 1u : 3u);  // (uniform, as is every condition around a barrier below)
         if (defined) {
             const double *xrow = X + (uint64_t)b * padded, *crow = C + (uint64_t)b * padded, *brow = B + (uint64_t)b * padded;
-            for (uint32_t j = threadIdx.x; j < L; j += kBlock) {
-                const uint32_t s = list[j];
-                vec[j] = xrow[s];
-                vec[pitch + j] = inner ? __dsub_rn(__dadd_rn(brow[s], crow[s]), 1.0) : 0.0;
-            }
-            __syncthreads();
-            if (!kDisp && kLds && L > kCountSamples) {
-                // the values sorted in the ranks' place (a bitonic network over the next power of two, the padding +inf),
-                // every lane's ranks found in the sorted copy and kept in registers, then stored over it
-                double *sm = vec + 2 * pitch, *si = vec + 3 * pitch;
-                uint32_t P = 2 * kCountSamples;
-                while (P < L) P <<= 1;  // (<= kLdsSamples)
-                for (uint32_t j = threadIdx.x; j < P; j += kBlock) {
-                    sm[j] = j < L ? vec[j] : HUGE_VAL;
-                    si[j] = j < L ? vec[pitch + j] : HUGE_VAL;
-                }
-                __syncthreads();
-                for (uint32_t k = 2; k <= P; k <<= 1)
-                    for (uint32_t step = k >> 1; step > 0; step >>= 1) {
-                        for (uint32_t e = threadIdx.x; e < P / 2; e += kBlock) {
-                            const uint32_t i = 2 * e - (e & (step - 1)), l = i + step;  // (l < P)
-                            const bool up = (i & k) == 0;
-                            const double a = sm[i], c = sm[l];
-                            if ((a > c) == up) sm[i] = c, sm[l] = a;
-                            if (inner) {
-                                const double ai = si[i], ci = si[l];
-                                if ((ai > ci) == up) si[i] = ci, si[l] = ai;
-                            }
-                        }
-                        __syncthreads();
-                    }
-                double rank_m[kLdsSamples / kBlock], rank_i[kLdsSamples / kBlock];
-#pragma unroll
-                for (uint32_t q = 0; q < kLdsSamples / kBlock; ++q) {
-                    const uint32_t j = q * kBlock + threadIdx.x;
-                    rank_m[q] = j < L ? midrank_sorted(sm, P, vec[j]) : 0.0;
-                    rank_i[q] = j < L && inner ? midrank_sorted(si, P, vec[pitch + j]) : 0.0;
-                }
-                __syncthreads();  // (every search is done: the sorted copies become the ranks)
-#pragma unroll
-                for (uint32_t q = 0; q < kLdsSamples / kBlock; ++q) {
-                    const uint32_t j = q * kBlock + threadIdx.x;
-                    if (j < L) sm[j] = rank_m[q], si[j] = rank_i[q];
-                }
-                __syncthreads();
-            } else if (!kDisp) {
-                for (uint32_t j = threadIdx.x; j < L; j += kBlock) {
-                    vec[2 * pitch + j] = midrank(vec, L, vec[j]);
-                    vec[3 * pitch + j] = inner ? midrank(vec + pitch, L, vec[pitch + j]) : 0.0;
-                }
-                __syncthreads();
-            }
+            branch_vectors<kLds, !kDisp>(xrow, crow, brow, list, L, inner, vec, pitch);  // (cohort_device.hpp)
             if (threadIdx.x < nvec) {
                 const double *v = vec + threadIdx.x * pitch;
                 double acc = 0.0;
@@ -486,6 +390,19 @@ int check_host(uint32_t num_samples, uint32_t num_branches)
 }
 
 }  // namespace
+
+namespace epik_amd {
+
+int cohort_mass_plane_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, hipStream_t stream, const uint32_t **d_first,
+                              const double **d_X)
+{
+    CorrSpace sp;
+    if (const int rc = correlation_begin(cohort, tree, stream, d_first, &sp); rc != EPIK_AMD_OK) return rc;
+    *d_X = sp.X;
+    return EPIK_AMD_OK;
+}
+
+}  // namespace epik_amd
 
 extern "C" {
 

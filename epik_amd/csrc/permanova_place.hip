@@ -119,18 +119,6 @@ __global__ __launch_bounds__(kBlock) void permanova_square_kernel(const double *
     }
 }
 
-// the lanes whose `flag` is set append (sample, group) to the list in the order of the lanes; returns how many did
-__device__ inline uint32_t append_in_order(bool flag, uint32_t at, uint32_t sample, uint32_t group, uint32_t *__restrict__ idx,
-                                           uint8_t *__restrict__ lam)
-{
-    const unsigned long long mask = __ballot(flag);
-    if (flag) {
-        const uint32_t pos = at + __popcll(mask & ((1ull << threadIdx.x) - 1));
-        idx[pos] = sample, lam[pos] = (uint8_t)group;
-    }
-    return __popcll(mask);
-}
-
 __global__ __launch_bounds__(kWave) void permanova_columns_kernel(const uint64_t *__restrict__ total, const uint32_t *__restrict__ lab,
                                                                   uint32_t num_samples, uint32_t padded, uint32_t num_columns,
                                                                   uint32_t slots, uint32_t lists, uint32_t *__restrict__ idx,
@@ -140,29 +128,11 @@ __global__ __launch_bounds__(kWave) void permanova_columns_kernel(const uint64_t
 {
     __shared__ uint32_t group_of[kGroups], size[kGroups];
     for (uint32_t c = blockIdx.x; c < num_columns; c += gridDim.x) {
-        for (uint32_t g = threadIdx.x; g < kGroups; g += kWave) {
-            group_of[g] = kMissing, size[g] = 0;
-            if (group_ss) group_ss[(uint64_t)c * kGroups + g] = na_value();
-        }
-        __syncthreads();
+        if (group_ss)
+            for (uint32_t g = threadIdx.x; g < kGroups; g += kWave) group_ss[(uint64_t)c * kGroups + g] = na_value();
         const uint64_t offset = (uint64_t)c * lists * padded;
-        uint32_t L = 0, G = 0;  // (uniform)
-        for (uint32_t base = 0; base < num_samples; base += kWave) {
-            const uint32_t s = base + threadIdx.x;
-            const uint32_t v = s < num_samples ? lab[(uint64_t)c * padded + s] : kMissing;
-            const bool flag = s < num_samples && total[s] != 0 && v != kMissing;  // (v < kGroups: the host has checked)
-            for (;;) {  // the labels not seen before take the next numbers, the first lane first
-                const unsigned long long fresh = __ballot(flag && group_of[v & (kGroups - 1)] == kMissing);
-                if (!fresh) break;
-                if (threadIdx.x == (uint32_t)__ffsll((long long)fresh) - 1) group_of[v] = G;
-                ++G;
-                __syncthreads();
-            }
-            const uint32_t g = flag ? group_of[v] : 0;
-            if (flag) atomicAdd(&size[g], 1u);
-            L += append_in_order(flag, L, s, g, idx + offset, lam + offset);
-        }
-        __syncthreads();
+        uint32_t L, G;  // (uniform)
+        column_list<kGroups>(total, lab + (uint64_t)c * padded, num_samples, kMissing, group_of, size, idx + offset, lam + offset, L, G);
         for (uint32_t g = threadIdx.x; g < kGroups; g += kWave) cols[c].size[g] = size[g];
         if (threadIdx.x == 0) {
             const bool defined = G >= 2 && L >= G + 1;
@@ -216,14 +186,6 @@ __global__ __launch_bounds__(kWave) void permanova_pairs_kernel(uint32_t padded,
             if (defined) active[atomicAdd(active + (uint64_t)num_columns * slots, 1u)] = test;
         }
     }
-}
-
-__device__ inline uint64_t permanova_key(uint64_t seed, uint32_t p, uint32_t i)
-{
-    uint64_t z = seed + (((uint64_t)p << 32) | i) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
 }
 
 struct SswArgs {
@@ -307,7 +269,7 @@ __global__ __launch_bounds__(kBlock) void permanova_ssw_kernel(const SswArgs a)
                 continue;
             }
             const uint32_t p = p0 + k;
-            for (uint32_t i = tid; i < n; i += threads) keys[i] = permanova_key(a.seed, p, i);
+            for (uint32_t i = tid; i < n; i += threads) keys[i] = permutation_key(a.seed, p, i);
             __syncthreads();
             if (kLds && n > kCountPositions) {
                 // (key, position) sorted by a bitonic network over the next power of two, the padding above every pair:

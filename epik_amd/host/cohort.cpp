@@ -980,10 +980,173 @@ int permanova_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_b
                                    ssw, group_ss, err);
 }
 
-cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise)
+namespace {
+
+// the rule's midranks by sorting: the same two counts as midranks(), found in another way (exact half-integers)
+void midranks_sorted(const std::vector<double>& x, std::vector<uint32_t>& order, std::vector<double>& rank)
+{
+    const size_t L = x.size();
+    order.resize(L), rank.resize(L);
+    for (size_t j = 0; j < L; ++j) order[j] = (uint32_t)j;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return x[a] < x[b]; });
+    for (size_t from = 0; from < L;) {
+        size_t to = from + 1;
+        while (to < L && x[order[to]] == x[order[from]]) ++to;
+        const double r = (double)from + 0.5 * (double)(to - from + 1);
+        for (size_t k = from; k < to; ++k) rank[order[k]] = r;
+        from = to;
+    }
+}
+
+// A(mu) of the rule for the deviations d: the chains S_g in `sums`, then the chain over g
+inline double edgetest_among(const double* d, const uint8_t* mu, size_t L, const std::vector<uint32_t>& size, double* sums)
+{
+    const size_t G = size.size();
+    for (size_t g = 0; g < G; ++g) sums[g] = 0.0;
+    for (size_t i = 0; i < L; ++i) sums[mu[i]] = sums[mu[i]] + d[i];
+    double among = 0.0;
+    for (size_t g = 0; g < G; ++g) among = among + (sums[g] * sums[g]) / (double)size[g];
+    return among;
+}
+
+}  // namespace
+
+int edgetest_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint32_t num_columns, uint32_t num_permutations,
+                             std::string& err)
+{
+    if (num_columns < 1 || num_columns > EPIK_AMD_EDGETEST_MAX_COLUMNS) {
+        err = "num_columns = " + std::to_string(num_columns) + " is outside [1, 64]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if (num_permutations < 1 || num_permutations > EPIK_AMD_EDGETEST_MAX_PERMUTATIONS) {
+        err = "num_permutations = " + std::to_string(num_permutations) + " is outside [1, 999999]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    for (size_t s = 0; s < num_samples; ++s)
+        for (size_t c = 0; c < num_columns; ++c) {
+            const uint32_t v = labels[s * num_columns + c];
+            if (v != EPIK_AMD_EDGETEST_MISSING && v >= EPIK_AMD_EDGETEST_MAX_GROUPS) {
+                err = "sample " + std::to_string(s) + ", column " + std::to_string(c) + ": the label " + std::to_string(v) +
+                      " is not below 32";
+                return EPIK_AMD_ERR_INVALID;
+            }
+        }
+    return EPIK_AMD_OK;
+}
+
+int edgetest_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                     const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, epik_amd_edgetest* out,
+                     double* stat, double* max, std::string& err)
+{
+    constexpr size_t F = EPIK_AMD_EDGETEST_FAMILIES;
+    const size_t S = num_samples, N = num_branches, M = num_columns, P = num_permutations, row = P + 1;
+    if (const int rc = edgetest_arguments_valid(labels, num_samples, num_columns, num_permutations, err); rc != EPIK_AMD_OK) return rc;
+    kr_planes planes;
+    if (const int rc = make_planes(mass, S, N, first, nullptr, planes, err); rc != EPIK_AMD_OK) return rc;
+    const double na = na_value();
+    const epik_amd_edgetest_family none{na, na, na, na, 0, 0};
+    if (stat) std::fill(stat, stat + M * F * N * row, na);
+    if (max) std::fill(max, max + M * F * row, na);
+    for (size_t c = 0; c < M; ++c) {
+        std::vector<size_t> list;
+        std::vector<uint32_t> lam, size, group_of(EPIK_AMD_EDGETEST_MAX_GROUPS, EPIK_AMD_EDGETEST_MISSING);
+        for (size_t s = 0; s < S; ++s) {
+            const uint32_t v = labels[s * M + c];
+            if (planes.total[s] == 0 || v == EPIK_AMD_EDGETEST_MISSING) continue;
+            if (group_of[v] == EPIK_AMD_EDGETEST_MISSING) group_of[v] = (uint32_t)size.size(), size.push_back(0);
+            list.push_back(s), lam.push_back(group_of[v]), ++size[group_of[v]];
+        }
+        const size_t L = list.size(), G = size.size();
+        for (size_t b = 0; b < N; ++b) {
+            epik_amd_edgetest& r = out[c * N + b];
+            r.used = (uint32_t)L, r.groups = (uint32_t)G, r.top_mass = r.top_imbalance = EPIK_AMD_EDGETEST_MISSING;
+            for (size_t f = 0; f < F; ++f) r.family[f] = none;
+        }
+        if (G < 2 || L < G + 1) continue;
+        // the labellings in chunks of permutations, a byte a position: the vectors of a branch are formed once a chunk
+        const size_t chunk = std::max<size_t>(1, ((size_t)64 << 20) / L);
+        std::vector<uint8_t> mu(std::min(chunk, row) * L);
+        std::vector<std::pair<uint64_t, uint32_t>> keys(L);
+        std::vector<double> mmax(F * row, 0.0), sums(G), rank;
+        std::vector<char> any(F, 0);
+        std::vector<double> x[F];
+        std::vector<uint32_t> order;
+        centred dev[F];
+        for (size_t p0 = 0; p0 < row; p0 += chunk) {
+            const size_t np = std::min(chunk, row - p0);
+            for (size_t k = 0; k < np; ++k) {
+                uint8_t* m = mu.data() + k * L;
+                const uint32_t p = (uint32_t)(p0 + k);
+                if (p == 0) {
+                    for (size_t i = 0; i < L; ++i) m[i] = (uint8_t)lam[i];
+                    continue;
+                }
+                for (uint32_t i = 0; i < L; ++i) keys[i] = {permanova_key(seed, p, i), i};
+                std::sort(keys.begin(), keys.end());
+                for (size_t q = 0; q < L; ++q) m[keys[q].second] = (uint8_t)lam[q];  // (rank_p(keys[q].second) = q)
+            }
+            for (size_t b = 0; b < N; ++b) {
+                epik_amd_edgetest& r = out[c * N + b];
+                const bool inner = first[b] < b;
+                branch_vectors(mass, planes, N, b, list, x[0], x[2]);
+                midranks_sorted(x[0], order, x[1]);
+                if (inner) midranks_sorted(x[2], order, x[3]);
+                for (size_t f = 0; f < (inner ? F : 2); ++f) {
+                    dev[f].of(x[f]);
+                    const double sxx = dev[f].ss;
+                    if (!(sxx > 0.0)) continue;
+                    const double* d = dev[f].d.data();
+                    epik_amd_edgetest_family& fam = r.family[f];
+                    if (p0 == 0) {
+                        const double among = edgetest_among(d, mu.data(), L, size, sums.data());
+                        fam.eta2 = among / sxx, fam.at_least = 0, fam.max_at_least = 0;
+                        if (f % 2 == 0) {
+                            const double ssw = sxx - among;
+                            if (ssw > 0.0) fam.stat = (among / (double)(G - 1)) / (ssw / (double)(L - G));
+                            uint32_t top = 0;
+                            double best = sums[0] / (double)size[0];
+                            for (size_t g = 1; g < G; ++g)
+                                if (const double mean = sums[g] / (double)size[g]; mean > best) best = mean, top = (uint32_t)g;
+                            (f == 0 ? r.top_mass : r.top_imbalance) = top;
+                        } else {
+                            fam.stat = (double)(L - 1) * fam.eta2;
+                        }
+                        any[f] = 1;
+                    }
+                    uint64_t at_least = 0;
+                    for (size_t k = 0; k < np; ++k) {
+                        const double eta = edgetest_among(d, mu.data() + k * L, L, size, sums.data()) / sxx;
+                        if (stat) stat[((c * F + f) * N + b) * row + p0 + k] = eta;
+                        if (eta > mmax[f * row + p0 + k]) mmax[f * row + p0 + k] = eta;
+                        at_least += p0 + k >= 1 && eta >= fam.eta2;
+                    }
+                    fam.at_least += at_least;
+                }
+            }
+        }
+        // max_at_least by a search in the sorted maxima: a count, exact however it is found
+        for (size_t f = 0; f < F; ++f) {
+            if (!any[f]) continue;
+            if (max) std::copy(mmax.begin() + f * row, mmax.begin() + (f + 1) * row, max + (c * F + f) * row);
+            std::vector<double> sorted(mmax.begin() + f * row + 1, mmax.begin() + (f + 1) * row);
+            std::sort(sorted.begin(), sorted.end());
+            for (size_t b = 0; b < N; ++b) {
+                epik_amd_edgetest_family& fam = out[c * N + b].family[f];
+                if (std::isnan(fam.eta2)) continue;
+                fam.max_at_least = (uint64_t)(sorted.end() - std::lower_bound(sorted.begin(), sorted.end(), fam.eta2));
+                fam.p = (double)(1 + fam.at_least) / (double)(P + 1);
+                fam.p_adj = (double)(1 + fam.max_at_least) / (double)(P + 1);
+            }
+        }
+    }
+    return EPIK_AMD_OK;
+}
+
+cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise, size_t most_labels,
+                                   const char* flag)
 {
     std::ifstream in(file);
-    if (!in) throw std::runtime_error("--cohort-permanova: cannot open the factor file " + file);
+    if (!in) throw std::runtime_error(std::string(flag) + ": cannot open the factor file " + file);
     std::map<std::string, size_t> index;
     for (size_t s = 0; s < samples.size(); ++s) index[samples[s].name] = s;
     cohort_factors factors;
@@ -994,7 +1157,7 @@ cohort_factors read_cohort_factors(const std::string& file, const std::vector<co
     for (size_t number = 1; std::getline(in, line); ++number) {
         if (!line.empty() && line.back() == '\r') line.pop_back();
         if (line.empty() || line[0] == '#') continue;
-        const std::string where = "--cohort-permanova: " + file + " line " + std::to_string(number);
+        const std::string where = std::string(flag) + ": " + file + " line " + std::to_string(number);
         const auto fields = split_tabs(line);
         if (!have_header) {
             if (fields[0] != "sample") throw std::runtime_error(where + ": the header must begin with 'sample'");
@@ -1030,19 +1193,19 @@ cohort_factors read_cohort_factors(const std::string& file, const std::vector<co
             if (v.empty() || v == "NA") continue;
             const auto [it, fresh] = id_of[c].emplace(v, (uint32_t)factors.names[c].size());
             if (fresh) {
-                const size_t most = pairwise ? EPIK_AMD_PERMANOVA_MAX_PAIR_GROUPS : EPIK_AMD_PERMANOVA_MAX_GROUPS;
+                const size_t most = most_labels ? most_labels : pairwise ? EPIK_AMD_PERMANOVA_MAX_PAIR_GROUPS : EPIK_AMD_PERMANOVA_MAX_GROUPS;
                 if (factors.names[c].size() == most)
                     throw std::runtime_error(where + ", column " + factors.columns[c] + ": '" + v + "' is label number " +
                                              std::to_string(most + 1) + ", more than " + std::to_string(most) +
-                                             (pairwise ? " (the most of --cohort-permanova-pairwise)" : ""));
+                                             (pairwise && !most_labels ? " (the most of --cohort-permanova-pairwise)" : ""));
                 factors.names[c].push_back(v);
             }
             factors.labels[s * M + c] = it->second;
         }
     }
-    if (!have_header) throw std::runtime_error("--cohort-permanova: " + file + " has no header line");
+    if (!have_header) throw std::runtime_error(std::string(flag) + ": " + file + " has no header line");
     for (size_t s = 0; s < samples.size(); ++s)
-        if (!seen[s]) throw std::runtime_error("--cohort-permanova: " + file + " has no line for the sample '" + samples[s].name + "'");
+        if (!seen[s]) throw std::runtime_error(std::string(flag) + ": " + file + " has no line for the sample '" + samples[s].name + "'");
     return factors;
 }
 
@@ -1392,6 +1555,57 @@ std::string format_permanova_tsv(const std::vector<cohort_sample>& samples, cons
             for (size_t g = 0; g < h; ++g)
                 line(c, names[c][label_of[c][g]], names[c][label_of[c][h]], records[c * slots + 1 + h * (h - 1) / 2 + g]);
     }
+    return out;
+}
+
+std::string format_edgetest_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                                const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
+                                const uint32_t* labels, uint32_t num_branches, uint32_t num_permutations, uint64_t seed,
+                                const epik_amd_edgetest* records)
+{
+    const size_t S = samples.size(), M = columns.size(), N = num_branches;
+    std::string out = used_head(samples, totals, "edgetest",
+                                " columns=" + std::to_string(M) + " permutations=" + std::to_string(num_permutations) +
+                                    " seed=" + std::to_string(seed));
+    // the groups of every column in the rule's order: by first appearance among the used samples
+    std::vector<std::vector<uint32_t>> label_of(M), size_of(M);
+    for (size_t c = 0; c < M; ++c) {
+        std::map<uint32_t, uint32_t> group_of;
+        for (size_t s = 0; s < S; ++s) {
+            const uint32_t v = labels[s * M + c];
+            if (totals[s] == 0 || v == EPIK_AMD_EDGETEST_MISSING) continue;
+            const auto [it, fresh] = group_of.emplace(v, (uint32_t)label_of[c].size());
+            if (fresh) label_of[c].push_back(v), size_of[c].push_back(0);
+            ++size_of[c][it->second];
+        }
+    }
+    for (size_t c = 0; c < M; ++c)
+        out += "# column\t" + std::to_string(c) + '\t' + columns[c] + '\t' + std::to_string(records[c * N].used) + '\t' +
+               std::to_string(records[c * N].groups) + '\n';
+    for (size_t c = 0; c < M; ++c)
+        for (size_t g = 0; g < label_of[c].size(); ++g)
+            out += "# group\t" + std::to_string(c) + '\t' + std::to_string(g) + '\t' + names[c][label_of[c][g]] + '\t' +
+                   std::to_string(size_of[c][g]) + '\n';
+    out += "edge_num\tcolumn";
+    for (const char* kind : {"mass", "imbalance"})
+        for (const char* field : {"eta2", "f", "p", "p_adj", "top", "h", "kw_p", "kw_p_adj"}) out += std::string("\t") + kind + '_' + field;
+    out += '\n';
+    for (size_t c = 0; c < M; ++c)
+        for (size_t b = 0; b < N; ++b) {
+            const epik_amd_edgetest& r = records[c * N + b];
+            bool any = false;
+            for (const auto& fam : r.family) any = any || !std::isnan(fam.eta2);
+            if (!any) continue;
+            out += std::to_string(b) + '\t' + columns[c];
+            for (size_t kind = 0; kind < 2; ++kind) {
+                const epik_amd_edgetest_family &plain = r.family[2 * kind], &ranks = r.family[2 * kind + 1];
+                const uint32_t top = kind ? r.top_imbalance : r.top_mass;
+                out += '\t' + g17_or_na(plain.eta2) + '\t' + g17_or_na(plain.stat) + '\t' + g17_or_na(plain.p) + '\t' +
+                       g17_or_na(plain.p_adj) + '\t' + (top == EPIK_AMD_EDGETEST_MISSING ? std::string("NA") : names[c][label_of[c][top]]) +
+                       '\t' + g17_or_na(ranks.stat) + '\t' + g17_or_na(ranks.p) + '\t' + g17_or_na(ranks.p_adj);
+            }
+            out += '\n';
+        }
     return out;
 }
 

@@ -107,6 +107,17 @@ int permanova_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_b
                       const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
                       uint64_t seed, bool pairwise, epik_amd_permanova* out, double* ssw, double* group_ss, std::string& err);
 
+/// num_columns in [1, 64], num_permutations in [1, 999 999], every label below 32 or 0xffffffff (missing): 0, or
+/// EPIK_AMD_ERR_INVALID with `err` naming the cause
+int edgetest_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint32_t num_columns, uint32_t num_permutations,
+                             std::string& err);
+/// The edge test by the rule (include/epik_amd.h), one thread: out[M][N], and where not null stat[M][4][N][P + 1] and
+/// max[M][4][P + 1], every cell written.  libepik_amd's kernels (edgetest_place.hip) give the same bits.  The code behind
+/// epik_amd_cohort_edgetest_host.  0, or as edgetest_arguments_valid; first[b] > b is refused.
+int edgetest_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                     const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, epik_amd_edgetest* out,
+                     double* stat, double* max, std::string& err);
+
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
 /// name or path, a name given before, or a file that cannot be read; and for a list without any sample.
@@ -139,10 +150,12 @@ struct cohort_factors {
     std::vector<uint32_t> labels;                 // [S][M], in the order of the list
     size_t skipped = 0;
 };
-cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise);
+/// `most_labels`, where not 0, is the cap instead (32 for --cohort-edge-test); `flag` begins every message.
+cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise,
+                                   size_t most_labels = 0, const char* flag = "--cohort-permanova");
 
 /// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash | epca | epca_edges | kmeans |
-/// kmeans_centroids | alpha | rarefy | correlation | dispersion | permanova
+/// kmeans_centroids | alpha | rarefy | correlation | dispersion | permanova | edgetest
 std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir,
                                  const std::string& extension = ".tsv");
 
@@ -207,6 +220,15 @@ std::string format_permanova_tsv(const std::vector<cohort_sample>& samples, cons
                                  const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
                                  const uint32_t* labels, uint32_t num_permutations, uint64_t seed, bool pairwise,
                                  const epik_amd_permanova* records, const double* group_ss);
+/// cohort_edgetest .tsv: "# epik_amd edgetest v1  samples=S used=L columns=M permutations=P seed=X", the "# unused" lines, a
+/// "# column<TAB>c<TAB>name<TAB>used_c<TAB>groups_c" line per column, a "# group<TAB>c<TAB>g<TAB>label<TAB>n" line per group (the
+/// groups in the rule's order), the column names edge_num column and, for mass and imbalance, _eta2 _f _p _p_adj _top _h _kw_p
+/// _kw_p_adj, then per column a line per branch with at least one defined family, from records[M][N]; top is the group's
+/// label; doubles %.17g, NA as NA.
+std::string format_edgetest_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                                const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
+                                const uint32_t* labels, uint32_t num_branches, uint32_t num_permutations, uint64_t seed,
+                                const epik_amd_edgetest* records);
 /// `text` into `filename` through `filename`.part, renamed when all of it is written
 void write_through_part(const std::string& filename, const std::string& text);
 

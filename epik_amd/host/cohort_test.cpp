@@ -24,6 +24,12 @@
 //   cohort_test permanova-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed> <pairwise>
 //                                           the file of --cohort-permanova for a `kr` input whose samples are named by the
 //                                           lines of names.txt, through the factor file's reader and the formatter
+//   cohort_test edgetest <out.bin> <in.bin> <labels.bin> <P> <seed>
+//                                           the edge test of a `kr` input with a raw `labels` file, uint32 [S][M]:
+//                                           epik_amd_edgetest [M][N], float64 stat[M][4][N][P + 1], float64 max[M][4][P + 1]
+//   cohort_test edgetest-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed>
+//                                           the file of --cohort-edge-test for a `kr` input whose samples are named by the
+//                                           lines of names.txt, through the factor file's reader and the formatter
 // An `add` input holds, little endian: uint64 n, keep, num_branches, num_samples; epik_amd_placement rows[n][keep];
 // uint32 n_rows[n]; uint32 kmer_counts[n][keep]; uint32 weights[n]; uint32 samples[n].
 // A `kr` input: uint64 num_samples, num_branches; uint64 mass[S][N]; uint32 first[N]; float64 branch_length[N].
@@ -305,11 +311,68 @@ int main(int argc, char** argv)
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }
+        if ((argc == 7 && std::strcmp(argv[1], "edgetest") == 0) || (argc == 8 && std::strcmp(argv[1], "edgetest-tsv") == 0)) {
+            const bool tsv = argc == 8;
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto cells = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const uint32_t P = (uint32_t)std::strtoul(argv[argc - 2], nullptr, 10);
+            const uint64_t seed = std::strtoull(argv[argc - 1], nullptr, 10);
+            std::vector<uint32_t> labels;
+            epik_amd::cohort_factors factors;
+            std::vector<epik_amd::cohort_sample> samples;
+            if (tsv) {
+                std::ifstream names(argv[4]);
+                if (!names) throw std::runtime_error(std::string("cannot open ") + argv[4]);
+                for (std::string line; std::getline(names, line);) samples.push_back({line, ""});
+                if (samples.size() != S) throw std::runtime_error("the names file does not name every sample");
+                factors = epik_amd::read_cohort_factors(argv[5], samples, false, EPIK_AMD_EDGETEST_MAX_GROUPS, "--cohort-edge-test");
+                std::cout << "Cohort edge-test factors: " << factors.columns.size() << " columns, " << factors.skipped
+                          << " lines of samples that are not in the list skipped" << std::endl;
+                labels = factors.labels;
+            } else {
+                std::ifstream labels_in(argv[4], std::ios::binary | std::ios::ate);
+                if (!labels_in) throw std::runtime_error(std::string("cannot open ") + argv[4]);
+                const uint64_t bytes = (uint64_t)labels_in.tellg();
+                labels_in.seekg(0);
+                if (bytes == 0 || bytes % (S * sizeof(uint32_t)) != 0) throw std::runtime_error("the labels file is not uint32 [S][M]");
+                labels = read_array<uint32_t>(labels_in, bytes / sizeof(uint32_t));
+            }
+            const uint64_t M = labels.size() / S, row = (uint64_t)P + 1;
+            if (M > EPIK_AMD_EDGETEST_MAX_COLUMNS) throw std::runtime_error("the labels file has more than 64 columns");
+            if (P < 1 || P > EPIK_AMD_EDGETEST_MAX_PERMUTATIONS) throw std::runtime_error("P is outside [1, 999999]");
+            std::vector<epik_amd_edgetest> records(M * N);
+            std::vector<double> stat(tsv ? 0 : M * EPIK_AMD_EDGETEST_FAMILIES * N * row), max(tsv ? 0 : M * EPIK_AMD_EDGETEST_FAMILIES * row);
+            std::string err;
+            if (epik_amd::edgetest_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), labels.data(), (uint32_t)M, P, seed,
+                                           records.data(), tsv ? nullptr : stat.data(), tsv ? nullptr : max.data(), err) != 0)
+                throw std::runtime_error(err);
+            if (tsv) {
+                std::vector<uint64_t> totals(S, 0);
+                for (uint64_t s = 0; s < S; ++s)
+                    for (uint64_t b = 0; b < N; ++b) totals[s] += cells[s * N + b];
+                epik_amd::write_through_part(argv[2], epik_amd::format_edgetest_tsv(samples, totals.data(), factors.columns, factors.names,
+                                                                                    labels.data(), (uint32_t)N, P, seed, records.data()));
+                return 0;
+            }
+            std::ofstream out(argv[2], std::ios::binary);
+            write_array(out, records.data(), records.size());
+            write_array(out, stat.data(), stat.size());
+            write_array(out, max.data(), max.size());
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
         std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin> | squash <out.bin> <in.bin> | "
                      "epca <out.bin> <in.bin> <K> | kmeans <out.bin> <in.bin> <K> <max_iterations> | alpha <out.bin> <in.bin> | "
                      "rarefy <out.bin> <in.bin> <depth_step> <num_depths> | correlation <out.bin> <in.bin> <meta.bin> | "
                      "dispersion <out.bin> <in.bin> | permanova <out.bin> <in.bin> <labels.bin> <P> <seed> <pairwise> | "
-                     "permanova-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed> <pairwise>\n";
+                     "permanova-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed> <pairwise> | "
+                     "edgetest <out.bin> <in.bin> <labels.bin> <P> <seed> | "
+                     "edgetest-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed>\n";
         return 2;
     } catch (const std::exception& error) {
         std::cerr << "Error: " << error.what() << std::endl;

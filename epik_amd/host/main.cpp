@@ -260,6 +260,12 @@ const char* kHelp =
     "      --cohort-permanova-seed arg  With --cohort-permanova: the seed of the permutations, a uint64 (default: 1)\n"
     "      --cohort-permanova-pairwise  With --cohort-permanova: also test every two groups of every column (at most 32 groups\n"
     "                          a column)\n"
+    "      --cohort-edge-test arg  With --cohort: also test, for every factor column of the TSV file arg (as --cohort-permanova's,\n"
+    "                          at most 32 labels a column), on which branches its groups of samples differ: the one-way ANOVA and\n"
+    "                          Kruskal-Wallis of every branch's mass and imbalance by permutation, with the max-statistic\n"
+    "                          adjustment (Westfall & Young 1993), on the device; writes cohort_edgetest_<list>.tsv\n"
+    "      --cohort-edge-test-permutations arg  With --cohort-edge-test: the number of permutations in [1, 999999] (default: 999)\n"
+    "      --cohort-edge-test-seed arg  With --cohort-edge-test: the seed of the permutations, a uint64 (default: 1)\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -500,6 +506,31 @@ int main(int argc, char** argv)
             if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-permanova-seed " + text + ": not a uint64");
             permanova_seed = v;
         }
+        const bool with_edgetest = parsed.has("cohort-edge-test");
+        if (with_edgetest && !with_cohort)
+            throw std::runtime_error("--cohort-edge-test needs --cohort (it tests the branches between the groups of the samples of the list)");
+        for (const char* dependent : {"cohort-edge-test-permutations", "cohort-edge-test-seed"})
+            if (parsed.has(dependent) && !with_edgetest)
+                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-edge-test" +
+                                         (with_cohort ? "" : " (and that needs --cohort )"));
+        uint32_t edgetest_permutations = 999;
+        uint64_t edgetest_seed = 1;
+        if (parsed.has("cohort-edge-test-permutations")) {
+            const std::string text = parsed.require("cohort-edge-test-permutations");
+            char* end = nullptr;
+            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
+            if (!end || *end || v < 1 || v > EPIK_AMD_EDGETEST_MAX_PERMUTATIONS)
+                throw std::runtime_error("--cohort-edge-test-permutations " + text + ": the number must lie in [1, 999999]");
+            edgetest_permutations = (uint32_t)v;
+        }
+        if (parsed.has("cohort-edge-test-seed")) {
+            const std::string text = parsed.require("cohort-edge-test-seed");
+            char* end = nullptr;
+            errno = 0;
+            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
+            if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-edge-test-seed " + text + ": not a uint64");
+            edgetest_seed = v;
+        }
         if (with_cohort) {
             for (const char* other : {"mates", "profile-only", "profile", "assign"})
                 if (parsed.has(other)) throw std::runtime_error(std::string("--cohort does not work with --") + other);
@@ -556,6 +587,15 @@ int main(int argc, char** argv)
         if (with_permanova) {
             factors = epik_amd::read_cohort_factors(parsed.require("cohort-permanova"), cohort_samples, permanova_pairwise);
             std::cout << "Cohort factors: " << factors.columns.size() << " columns, " << factors.skipped
+                      << " lines of samples that are not in the list skipped" << std::endl;
+        }
+
+        // --cohort-edge-test: the same reader with the edge test's cap, before the database or a device is
+        epik_amd::cohort_factors edge_factors;
+        if (with_edgetest) {
+            edge_factors = epik_amd::read_cohort_factors(parsed.require("cohort-edge-test"), cohort_samples, false,
+                                                         EPIK_AMD_EDGETEST_MAX_GROUPS, "--cohort-edge-test");
+            std::cout << "Cohort edge-test factors: " << edge_factors.columns.size() << " columns, " << edge_factors.skipped
                       << " lines of samples that are not in the list skipped" << std::endl;
         }
 
@@ -946,6 +986,7 @@ int main(int argc, char** argv)
         const auto cohort_correlation_filename = epik_amd::make_cohort_filename("correlation", query_file, output_dir);
         const auto cohort_dispersion_filename = epik_amd::make_cohort_filename("dispersion", query_file, output_dir);
         const auto cohort_permanova_filename = epik_amd::make_cohort_filename("permanova", query_file, output_dir);
+        const auto cohort_edgetest_filename = epik_amd::make_cohort_filename("edgetest", query_file, output_dir);
         bool epca_converged = true, kmeans_converged = true;
         if (with_cohort) {
             // the handles' cohorts summed on the first device, read once, and the distances computed there
@@ -964,10 +1005,13 @@ int main(int argc, char** argv)
             epik_amd::placer::cohort_permanova permanova;
             permanova.labels = factors.labels.data(), permanova.num_columns = (uint32_t)factors.columns.size();
             permanova.num_permutations = permanova_permutations, permanova.seed = permanova_seed, permanova.pairwise = permanova_pairwise;
+            epik_amd::placer::cohort_edgetest edgetest;
+            edgetest.labels = edge_factors.labels.data(), edgetest.num_columns = (uint32_t)edge_factors.columns.size();
+            edgetest.num_permutations = edgetest_permutations, edgetest.seed = edgetest_seed;
             placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
                                with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr, with_kmeans ? &kmeans : nullptr,
                                with_alpha || with_rarefy ? &diversity : nullptr, with_correlation || with_dispersion ? &edges : nullptr,
-                               with_permanova ? &permanova : nullptr);
+                               with_permanova ? &permanova : nullptr, with_edgetest ? &edgetest : nullptr);
             epik_amd::write_through_part(cohort_samples_filename, epik_amd::format_cohort_samples_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_profile_filename, epik_amd::format_cohort_profile_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_kr_filename, epik_amd::format_cohort_kr_tsv(cohort_samples, kr));
@@ -1024,6 +1068,16 @@ int main(int argc, char** argv)
                                                                             factors.labels.data(), permanova_permutations, permanova_seed,
                                                                             permanova_pairwise, permanova.records.data(),
                                                                             permanova.group_ss.data()));
+            }
+            if (with_edgetest) {
+                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
+                for (size_t s = 0; s < mass_of.size(); ++s)
+                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
+                epik_amd::write_through_part(cohort_edgetest_filename,
+                                             epik_amd::format_edgetest_tsv(cohort_samples, mass_of.data(), edge_factors.columns,
+                                                                           edge_factors.names, edge_factors.labels.data(),
+                                                                           (uint32_t)cohort.num_branches, edgetest_permutations,
+                                                                           edgetest_seed, edgetest.records.data()));
             }
             if (with_squash) {
                 epik_amd::write_through_part(cohort_squash_filename,
@@ -1101,6 +1155,7 @@ int main(int argc, char** argv)
         if (with_correlation) std::cout << "Cohort edge correlation: " << cohort_correlation_filename << std::endl;
         if (with_dispersion) std::cout << "Cohort edge dispersion: " << cohort_dispersion_filename << std::endl;
         if (with_permanova) std::cout << "Cohort PERMANOVA: " << cohort_permanova_filename << std::endl;
+        if (with_edgetest) std::cout << "Cohort edge test: " << cohort_edgetest_filename << std::endl;
         if (with_taxonomy) std::cout << "Taxa: " << taxa_filename << std::endl;
         if (taxonomy_per_read) std::cout << "Taxa of the reads: " << taxa_reads_filename << std::endl;
         if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;

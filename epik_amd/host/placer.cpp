@@ -39,6 +39,7 @@
 #pragma weak epik_amd_cohort_correlation
 #pragma weak epik_amd_cohort_dispersion
 #pragma weak epik_amd_cohort_permanova
+#pragma weak epik_amd_cohort_edgetest
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -293,8 +294,10 @@ void placer::read_taxonomy(uint64_t* direct, uint64_t* assigned, epik_amd_taxa_t
 
 void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                          epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans,
-                         cohort_diversity* diversity, cohort_edges* edges, cohort_permanova* permanova)
+                         cohort_diversity* diversity, cohort_edges* edges, cohort_permanova* permanova,
+                         cohort_edgetest* edgetest)
 {
+    if (edgetest && !&epik_amd_cohort_edgetest) throw std::runtime_error("GPU placer: this libepik_amd has no edge test");
     if (permanova && !&epik_amd_cohort_permanova) throw std::runtime_error("GPU placer: this libepik_amd has no PERMANOVA");
     if (edges && (!&epik_amd_cohort_correlation || !&epik_amd_cohort_dispersion))
         throw std::runtime_error("GPU placer: this libepik_amd has no edge correlation and dispersion");
@@ -372,6 +375,11 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
         rc = epik_amd_cohort_permanova(_cohorts[0], tree, length.data(), permanova->labels, permanova->num_columns,
                                        permanova->num_permutations, permanova->seed, permanova->pairwise ? 1 : 0,
                                        permanova->records.data(), nullptr, permanova->group_ss.data());
+    }
+    if (rc == EPIK_AMD_OK && edgetest) {
+        edgetest->records.assign((size_t)edgetest->num_columns * parent.size(), epik_amd_edgetest{});
+        rc = epik_amd_cohort_edgetest(_cohorts[0], tree, edgetest->labels, edgetest->num_columns, edgetest->num_permutations,
+                                      edgetest->seed, edgetest->records.data(), nullptr, nullptr);
     }
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);

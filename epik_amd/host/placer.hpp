@@ -215,10 +215,18 @@ public:
         std::vector<epik_amd_permanova> records;
         std::vector<double> group_ss;
     };
+    /// With `edgetest` (--cohort-edge-test): the edge test of labels[S][M] with num_permutations permutations from `seed`,
+    /// records of M * N (column, branch) pairs on return.
+    struct cohort_edgetest {
+        const uint32_t* labels = nullptr;
+        uint32_t num_columns = 0, num_permutations = 999;
+        uint64_t seed = 1;
+        std::vector<epik_amd_edgetest> records;
+    };
     void read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                      epik_amd_squash_merge* merges = nullptr, uint32_t* num_merges = nullptr, cohort_epca* epca = nullptr,
                      cohort_kmeans* kmeans = nullptr, cohort_diversity* diversity = nullptr, cohort_edges* edges = nullptr,
-                     cohort_permanova* permanova = nullptr);
+                     cohort_permanova* permanova = nullptr, cohort_edgetest* edgetest = nullptr);
     /// --taxonomy: one device taxonomy object per handle (epik_amd_taxonomy) from taxon_parent[T] and label[N], with one
     /// row of cells per sample of the cohort (call set_cohort first) or one row; from then on place_flat goes through
     /// the epik_amd_placer_taxa_* entries: every unique sequence is added with the number of its records as weight, a

@@ -877,6 +877,38 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *     undefined or a slot without a pair.  group_ss[M][256], where asked for: W_g / (double)n_g of lambda for g < G of a
  *     column whose test is defined, NA otherwise.  Every cell of every output is written.
  *
+ * Edge test (per-branch one-way ANOVA and Kruskal-Wallis by permutation, with the single-step max-statistic adjustment of
+ *   Westfall & Young 1993): on which branches do the groups of a factor column differ?  From mass[S][N], first[N] and
+ *   labels[S][M] as for PERMANOVA, M in [1, 64], but a label is below EPIK_AMD_EDGETEST_MAX_GROUPS = 32 (0xffffffff means
+ *   "missing"); P = num_permutations in [1, 999 999] and a uint64 seed.  All arithmetic is IEEE double, every operation
+ *   rounded on its own, nothing fused; + - * / and comparisons only.  NA is EPIK_AMD_NA_BITS, written and never computed.
+ *   Samples and groups.  U_c, L, the positions, the groups by first appearance, G, n_g and lambda are exactly those of the
+ *     PERMANOVA rule: the same for every branch of a column.
+ *   Labellings.  mu^p, p = 0 .. P, is exactly the PERMANOVA rule's labelling of U_c: the same keys from the same seed, the
+ *     same ranking, mu^0 = lambda.  A column tested with the same seed under both rules sees the same relabellings.
+ *   Families.  Four vectors x over the positions of a branch b, f = 0 .. 3: xm[b], the mass of the correlation rule;
+ *     rank(xm[b]), its midranks over U_c by the correlation rule; xi[b], the imbalance (inner branches only); rank(xi[b]).
+ *   Sums.  mx = (sequential sum of x from +0.0, i ascending) / (double)L,   d_i = x_i - mx,
+ *       sxx = the sequential sum of d_i * d_i from +0.0, i ascending;  for a labelling mu:
+ *       S_g = the sequential sum from +0.0 over i ascending with mu_i == g of d_i,
+ *       A(mu) = the sequential sum from +0.0 over g ascending of (S_g * S_g) / (double)n_g,     eta(mu) = A(mu) / sxx.
+ *     An implementation may share out columns, branches, families, labellings and groups; it may never split one chain.
+ *     (No S_g is ever -0.0: a chain from +0.0 cannot reach it.  So adding +0.0 to a chain changes nothing.)
+ *   Defined.  A family of a branch is defined iff G >= 2, L - G >= 1 and sxx > 0.0 and, for f = 2 and 3, b is inner.
+ *     (sxx is the computed double: identical values whose running sum rounds leave deviations of an ulp and count as varying.)
+ *   Observed.  eta2 = eta(lambda).  f = 0 and 2: ssw = sxx - A(lambda),
+ *       stat = (A(lambda) / (double)(G - 1)) / (ssw / (double)(L - G)), the one-way ANOVA F, NA unless ssw > 0.0.
+ *     f = 1 and 3: stat = (double)(L - 1) * eta2, the Kruskal-Wallis H with its tie correction (SSA / SST of midranks).
+ *   Permutation p-values.  at_least = #{p in 1 .. P : eta(mu^p) >= eta2},   p = (double)(1 + at_least) / (double)(P + 1);
+ *       Mmax_p = the maximum over the defined branches of family f in column c of eta_b(mu^p)   (every eta is >= +0.0, so
+ *       a maximum over the bit patterns is exact whatever the order),
+ *       max_at_least = #{p in 1 .. P : Mmax_p >= eta2},   p_adj = (double)(1 + max_at_least) / (double)(P + 1).
+ *   Direction.  top_mass and top_imbalance: the group g with the largest S_g / (double)n_g of lambda in family 0 and in
+ *     family 2, the lowest g of a tie; 0xffffffff where that family is undefined.
+ *   An undefined family: its doubles are NA and its counts 0.  used = L and groups = G are always written.
+ *   Results.  out[M][N] records.  stat[M][4][N][P + 1], where asked for: eta(mu^p), NA where undefined.  max[M][4][P + 1],
+ *     where asked for: Mmax_p with p = 0 as well, NA for a family without a defined branch.  Every cell is written.
+ *
  * An epik_amd_cohort is an object of its own, created for a placer's device, num_branches and keep_at_most (whole
  * databases only, not a k-mer-space shard) and num_samples >= 1; all zero at create() and after reset().
  *   add_device  asynchronous on `stream`, allocates nothing: as epik_amd_profile_add_device, with d_samples (uint32 [n],
@@ -950,6 +982,19 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *               synchronous; ssw and group_ss may be null.
  *   permanova_host  the rule on the host from mass[S][N], first[N], branch_length[N] and the labels, no device.
  *               permanova_kr_host: the same from a matrix kr[S][S] and totals[S] (T_s; only > 0 matters).
+ *   edgetest_device  checks the tree as correlation_device (its device and N) and labels (HOST [S][M], read before the call
+ *               returns): refused are a null cohort, tree, labels or d_out, num_columns outside [1, 64], num_permutations
+ *               outside [1, 999 999] and a label in [32, 0xffffffff).  It shares the workspace of correlation_device (the
+ *               masses, sample-fastest) and keeps one of its own until destroy(), grown where a call needs more: with Sp = S
+ *               rounded up to 32, 32 * N * Sp bytes (the four centred vectors of every branch), 32 * (P + 1) bytes (Mmax),
+ *               1 024 * Sp bytes (a chunk of 1 024 labellings, a byte a position), 32 * Sp bytes for each of 256 workgroups
+ *               of the general path, 9 * Sp bytes a column and 40 * N bytes of tables.  The columns run one after another
+ *               in it, the permutations in chunks of 1 024.  d_out is epik_amd_edgetest [M][N]; d_stat (may be null) float64
+ *               [M][4][N][P + 1]; d_max (may be null) float64 [M][4][P + 1]; all in device memory.  Once enqueued on
+ *               `stream` it needs no readback.  The cells are not changed.  A column of up to 1 024 positions keeps a
+ *               branch's vectors in LDS; beyond, or with EPIK_AMD_EDGETEST_LDS=0 (read at the call), in global memory:
+ *               the same bits.   edgetest: the same into host memory, synchronous; stat and max may be null.
+ *   edgetest_host  the rule on the host from mass[S][N], first[N] and the labels, no device; first[b] > b is refused.
  * cohort_reads / _strands / _frames / _mates: the profile_* twins with samples[n] (HOST uint32) beside the weights.
  */
 typedef struct epik_amd_cohort epik_amd_cohort;
@@ -1082,6 +1127,28 @@ int epik_amd_cohort_permanova_host(const uint64_t *mass, uint32_t num_samples, u
 int epik_amd_cohort_permanova_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
                                       uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                       epik_amd_permanova *out, double *ssw, double *group_ss);
+typedef struct epik_amd_edgetest_family {
+    double eta2, stat, p, p_adj;        /* stat: F for the families 0 and 2, H for 1 and 3 */
+    uint64_t at_least, max_at_least;    /* #{p >= 1 : eta(mu^p) >= eta2}, #{p >= 1 : Mmax_p >= eta2} */
+} epik_amd_edgetest_family; /* 48 bytes */
+typedef struct epik_amd_edgetest {
+    uint32_t used, groups;              /* L and G of the column */
+    epik_amd_edgetest_family family[4]; /* mass, rank(mass), imbalance, rank(imbalance) */
+    uint32_t top_mass, top_imbalance;   /* the group with the largest mean of family 0 and 2; 0xffffffff where undefined */
+} epik_amd_edgetest; /* 208 bytes */
+#define EPIK_AMD_EDGETEST_MAX_COLUMNS 64u
+#define EPIK_AMD_EDGETEST_MAX_GROUPS 32u
+#define EPIK_AMD_EDGETEST_FAMILIES 4u
+#define EPIK_AMD_EDGETEST_MAX_PERMUTATIONS 999999u
+#define EPIK_AMD_EDGETEST_MISSING 0xffffffffu
+int epik_amd_cohort_edgetest_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels,
+                                    uint32_t num_columns, uint32_t num_permutations, uint64_t seed, void *d_out, void *d_stat,
+                                    void *d_max, void *stream);
+int epik_amd_cohort_edgetest(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels, uint32_t num_columns,
+                             uint32_t num_permutations, uint64_t seed, epik_amd_edgetest *out, double *stat, double *max);
+int epik_amd_cohort_edgetest_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                  const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
+                                  epik_amd_edgetest *out, double *stat, double *max);
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n);
 int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
