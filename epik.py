@@ -31,6 +31,12 @@ per-sample metadata in FILE (a TSV), cohort_correlation_<list>.tsv.
 --cohort-edge-test FILE, with --cohort: on which branches the groups of every factor column of FILE (a TSV) differ (per
 branch ANOVA and Kruskal-Wallis of mass and imbalance by permutation, max-statistic adjusted), cohort_edgetest_<list>.tsv;
 --cohort-edge-test-permutations P (default 999), --cohort-edge-test-seed X (default 1).
+--cohort-permdisp FILE, with --cohort: whether the groups of every factor column of FILE (a TSV, as --cohort-permanova's, at
+most 32 labels a column) differ in spread (PERMDISP: distances to group centroids, permutation of residuals),
+cohort_permdisp_<list>.tsv; --cohort-permdisp-permutations P (default 999), --cohort-permdisp-seed X (default 1),
+--cohort-permdisp-pairwise.
+--cohort-pcoa, with --cohort: the principal coordinates of the samples over the KR distances, all eigenvalues with the
+negative ones of a distance that is not Euclidean, cohort_pcoa_<list>.tsv; --cohort-pcoa-components K axes (default 5).
 """
 from __future__ import annotations
 
@@ -148,6 +154,20 @@ PLACE_OPTIONS = [
                                                 help="With --cohort-edge-test: the number of permutations [default: 999].")),
     (("--cohort-edge-test-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
                                         help="With --cohort-edge-test: the seed of the permutations, a uint64 [default: 1].")),
+    (("--cohort-permdisp",), dict(type=click.Path(), default=None,
+                                  help="With --cohort: a TSV of factors (as --cohort-permanova's, at most 32 labels a column): also "
+                                       "test on the device whether the groups of every column differ in spread (PERMDISP, distances "
+                                       "to group centroids over the KR distances) and write cohort_permdisp_<list>.tsv.")),
+    (("--cohort-permdisp-permutations",), dict(type=click.IntRange(1, 999999), default=None,
+                                               help="With --cohort-permdisp: the number of permutations [default: 999].")),
+    (("--cohort-permdisp-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
+                                       help="With --cohort-permdisp: the seed of the permutations, a uint64 [default: 1].")),
+    (("--cohort-permdisp-pairwise",), dict(is_flag=True, help="With --cohort-permdisp: also test every two groups of every column.")),
+    (("--cohort-pcoa",), dict(is_flag=True, help="With --cohort: also compute the principal coordinates of the samples over "
+                                                 "their KR distances on the device and write cohort_pcoa_<list>.tsv (all "
+                                                 "eigenvalues, the negative ones included, and every sample's coordinates).")),
+    (("--cohort-pcoa-components",), dict(type=click.IntRange(1, 64), default=None,
+                                         help="With --cohort-pcoa: the number of axes, in [1, 64] [default: 5].")),
     (("--taxonomy",), dict(type=click.Path(), default=None,
                            help="A taxonomy file, one leaf_label<TAB>A;B;C line per reference leaf: also write taxa_<input>.tsv "
                                 "(per taxon the reads assigned to it and the mass placed in it, with clade sums) or, with "
@@ -178,7 +198,9 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                    cohort_alpha=False, cohort_rarefy=None, cohort_rarefy_step=None, taxonomy=None, taxonomy_mass=None,
                    taxonomy_per_read=False, cohort_correlation=None, cohort_dispersion=False, cohort_permanova=None,
                    cohort_permanova_permutations=None, cohort_permanova_seed=None, cohort_permanova_pairwise=False,
-                   cohort_edge_test=None, cohort_edge_test_permutations=None, cohort_edge_test_seed=None):
+                   cohort_edge_test=None, cohort_edge_test_permutations=None, cohort_edge_test_seed=None,
+                   cohort_pcoa=False, cohort_pcoa_components=None, cohort_permdisp=None, cohort_permdisp_permutations=None,
+                   cohort_permdisp_seed=None, cohort_permdisp_pairwise=False):
     if taxonomy_mass is not None and taxonomy is None:
         raise click.UsageError("--taxonomy-mass needs --taxonomy")
     if taxonomy_per_read and taxonomy is None:
@@ -231,6 +253,17 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                         ("--cohort-edge-test-seed", cohort_edge_test_seed is not None)):
         if given and cohort_edge_test is None:
             raise click.UsageError(f"{flag} needs --cohort-edge-test")
+    if cohort_permdisp is not None and not cohort:
+        raise click.UsageError("--cohort-permdisp needs --cohort")
+    for flag, given in (("--cohort-permdisp-permutations", cohort_permdisp_permutations is not None),
+                        ("--cohort-permdisp-seed", cohort_permdisp_seed is not None),
+                        ("--cohort-permdisp-pairwise", cohort_permdisp_pairwise)):
+        if given and cohort_permdisp is None:
+            raise click.UsageError(f"{flag} needs --cohort-permdisp")
+    if cohort_pcoa and not cohort:
+        raise click.UsageError("--cohort-pcoa needs --cohort")
+    if cohort_pcoa_components is not None and not cohort_pcoa:
+        raise click.UsageError("--cohort-pcoa-components needs --cohort-pcoa")
     if cohort:
         for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
                             ("--assign", assign), ("--db-shard > 1", db_shard != 1)):
@@ -296,6 +329,18 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
             argv += ["--cohort-edge-test-permutations", str(int(cohort_edge_test_permutations))]
         if cohort_edge_test_seed is not None:
             argv += ["--cohort-edge-test-seed", str(int(cohort_edge_test_seed))]
+    if cohort_permdisp is not None:
+        argv += ["--cohort-permdisp", str(cohort_permdisp)]
+        if cohort_permdisp_permutations is not None:
+            argv += ["--cohort-permdisp-permutations", str(int(cohort_permdisp_permutations))]
+        if cohort_permdisp_seed is not None:
+            argv += ["--cohort-permdisp-seed", str(int(cohort_permdisp_seed))]
+        if cohort_permdisp_pairwise:
+            argv += ["--cohort-permdisp-pairwise"]
+    if cohort_pcoa:
+        argv += ["--cohort-pcoa"]
+        if cohort_pcoa_components is not None:
+            argv += ["--cohort-pcoa-components", str(int(cohort_pcoa_components))]
     if taxonomy is not None:
         argv += ["--taxonomy", str(taxonomy)]
         if taxonomy_mass is not None:

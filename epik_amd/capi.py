@@ -34,6 +34,10 @@ SQUASH_NONE = 0xFFFFFFFF
 EPCA_INFO = np.dtype([("used", np.uint32), ("components", np.uint32), ("sweeps", np.uint32), ("converged", np.uint32),
                       ("trace", np.float64), ("scale", np.float64)])
 EPCA_MAX_COMPONENTS = 64
+#: epik_amd_pcoa_info (48 bytes)
+PCOA_INFO = np.dtype([("used", np.uint32), ("components", np.uint32), ("sweeps", np.uint32), ("converged", np.uint32),
+                      ("trace", np.float64), ("scale", np.float64), ("pos", np.float64), ("neg", np.float64)])
+PCOA_MAX_COMPONENTS = 64
 EPCA_MAX_SWEEPS = 64
 #: epik_amd_kmeans_info (16 bytes), epik_amd_kmeans_sample (16 bytes), epik_amd_kmeans_cluster (24 bytes)
 KMEANS_INFO = np.dtype([("used", np.uint32), ("clusters", np.uint32), ("iterations", np.uint32), ("converged", np.uint32)])
@@ -62,6 +66,14 @@ PERMANOVA_MAX_PAIR_GROUPS = 32
 PERMANOVA_PAIR_SLOTS = 496
 PERMANOVA_MAX_PERMUTATIONS = 999999
 PERMANOVA_MISSING = 0xFFFFFFFF
+#: epik_amd_permdisp (48 bytes): a test's record; the doubles of an undefined test are NA_BITS
+PERMDISP = np.dtype([("used", np.uint32), ("groups", np.uint32), ("clipped", np.uint32), ("pad", np.uint32),
+                     ("at_least", np.uint64), ("eta2", np.float64), ("f", np.float64), ("p", np.float64)])
+PERMDISP_MAX_COLUMNS = 64
+PERMDISP_MAX_GROUPS = 32
+PERMDISP_PAIR_SLOTS = 496
+PERMDISP_MAX_PERMUTATIONS = 999999
+PERMDISP_MISSING = 0xFFFFFFFF
 #: epik_amd_edgetest_family (48 bytes) and epik_amd_edgetest (208 bytes): a (column, branch)'s record of the edge test; the
 #: families are mass, rank(mass), imbalance, rank(imbalance); the doubles of an undefined family are NA_BITS
 EDGETEST_FAMILY = np.dtype([("eta2", np.float64), ("stat", np.float64), ("p", np.float64), ("p_adj", np.float64),
@@ -176,9 +188,17 @@ EXPORTS = (
     "epik_amd_cohort_permanova",
     "epik_amd_cohort_permanova_host",
     "epik_amd_cohort_permanova_kr_host",
+    "epik_amd_cohort_pcoa_device",
+    "epik_amd_cohort_pcoa",
+    "epik_amd_cohort_pcoa_host",
+    "epik_amd_cohort_pcoa_kr_host",
     "epik_amd_cohort_edgetest_device",
     "epik_amd_cohort_edgetest",
     "epik_amd_cohort_edgetest_host",
+    "epik_amd_cohort_permdisp_device",
+    "epik_amd_cohort_permdisp",
+    "epik_amd_cohort_permdisp_host",
+    "epik_amd_cohort_permdisp_kr_host",
     "epik_amd_placer_cohort_reads",
     "epik_amd_placer_cohort_strands",
     "epik_amd_placer_cohort_frames",
@@ -553,6 +573,22 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_permanova_host.argtypes = [vp, u32, u32, vp, vp, vp, u32, u32, u64, i32, vp, vp, vp]
     lib.epik_amd_cohort_permanova_kr_host.restype = i32
     lib.epik_amd_cohort_permanova_kr_host.argtypes = [vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp]
+    lib.epik_amd_cohort_pcoa_device.restype = i32
+    lib.epik_amd_cohort_pcoa_device.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+    lib.epik_amd_cohort_pcoa.restype = i32
+    lib.epik_amd_cohort_pcoa.argtypes = [vp, vp, vp, u32, vp, vp, vp]
+    lib.epik_amd_cohort_pcoa_host.restype = i32
+    lib.epik_amd_cohort_pcoa_host.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp, vp]
+    lib.epik_amd_cohort_pcoa_kr_host.restype = i32
+    lib.epik_amd_cohort_pcoa_kr_host.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+    lib.epik_amd_cohort_permdisp_device.restype = i32
+    lib.epik_amd_cohort_permdisp_device.argtypes = [vp, vp, vp, u32, u32, u64, i32, vp, vp, vp, vp, vp]
+    lib.epik_amd_cohort_permdisp.restype = i32
+    lib.epik_amd_cohort_permdisp.argtypes = [vp, vp, vp, vp, u32, u32, u64, i32, vp, vp, vp, vp]
+    lib.epik_amd_cohort_permdisp_host.restype = i32
+    lib.epik_amd_cohort_permdisp_host.argtypes = [vp, u32, u32, vp, vp, vp, u32, u32, u64, i32, vp, vp, vp, vp]
+    lib.epik_amd_cohort_permdisp_kr_host.restype = i32
+    lib.epik_amd_cohort_permdisp_kr_host.argtypes = [vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp, vp]
     lib.epik_amd_cohort_edgetest_device.restype = i32
     lib.epik_amd_cohort_edgetest_device.argtypes = [vp, vp, vp, u32, u32, u64, vp, vp, vp, vp]
     lib.epik_amd_cohort_edgetest.restype = i32

@@ -31,11 +31,17 @@ their readers are the files of --cohort-correlation and --cohort-dispersion.
 PERMANOVA of the samples' groups over the KR distances (the header's seventh rule): `Cohort.permanova` /
 `permanova_device` on the device, `permanova_host` and `permanova_kr_host` on the host; `read_factors` reads the file of
 --cohort-permanova; `format_permanova_tsv` and `read_permanova_tsv` are its output file.
+PERMDISP, the test of the groups' dispersions that goes with it (the header's PERMDISP rule): `Cohort.permdisp` /
+`permdisp_device` on the device, `permdisp_host` and `permdisp_kr_host` on the host; `format_permdisp_tsv` is its output file.
 
 The edge test (the header's eighth rule): which branches differ between the groups of a factor column, by permutation with
 the max-statistic adjustment: `Cohort.edgetest` / `edgetest_device` on the device, `edgetest_host` on the host;
 `read_factors(..., most=32)` reads the file of --cohort-edge-test; `format_edgetest_tsv` and `read_edgetest_tsv` are its
 output file.
+
+Principal coordinates of the samples over the KR distances (the header's ninth rule): `Cohort.pcoa` / `pcoa_device` on the
+device, `pcoa_host` and `pcoa_kr_host` on the host, each giving a `Pcoa` with all eigenvalues, the negative ones included;
+`format_pcoa_tsv` and `read_pcoa_tsv` are the file of --cohort-pcoa.
 """
 from __future__ import annotations
 
@@ -162,6 +168,69 @@ def epca_host(mass, first, num_components: int = 5) -> Epca:
     out = _epca_buffers(s, n, k)
     capi.check(lib.epik_amd_cohort_epca_host(mass.ctypes.data, s, n, first.ctypes.data, k, out.mu.ctypes.data,
                                              out.proj.ctypes.data, out.edge.ctypes.data, out.info.ctypes.data))
+    out.info = out.info[0]
+    return out
+
+
+@dataclass
+class Pcoa:
+    """Principal coordinates as the rule leaves them: `mu` float64 [S] (all L eigenvalues by (mu descending, j ascending),
+    the negative ones included, +0.0 beyond), `coord` float64 [S][K] and `info`, one `capi.PCOA_INFO` record (used,
+    components, sweeps, converged, trace, scale, pos, neg)."""
+
+    mu: np.ndarray
+    coord: np.ndarray
+    info: np.ndarray
+
+    @property
+    def components(self) -> int:
+        return int(self.info["components"])
+
+    def kinds(self) -> list:
+        """Per eigenvalue k < used its class: "real" (mu_k > 2^-40 * scale), "negative" (mu_k < -2^-40 * scale) or "null"."""
+        floor = np.ldexp(1.0, -40) * float(self.info["scale"])
+        return ["real" if m > floor else "negative" if m < -floor else "null" for m in self.mu[:int(self.info["used"])]]
+
+    @property
+    def negative(self) -> float:
+        """-neg / pos, 0 when pos is 0: how far the distances are from Euclidean."""
+        pos, neg = float(self.info["pos"]), float(self.info["neg"])
+        return (0.0 - neg) / pos if pos != 0 else 0.0
+
+
+def _pcoa_buffers(s, k):
+    k = max(k, 1)            # (a refused K still needs somewhere to point)
+    return Pcoa(np.full(s, np.nan), np.full((s, k), np.nan), np.zeros(1, dtype=capi.PCOA_INFO))
+
+
+def pcoa_kr_host(kr, totals, num_components: int = 5) -> Pcoa:
+    """The principal coordinates of the rule from a KR matrix kr[S][S] and totals[S] (T_s) on the host
+    (`epik_amd_cohort_pcoa_kr_host`)."""
+    lib = capi.load()
+    kr = np.ascontiguousarray(kr, dtype=np.float64)
+    if kr.ndim != 2 or kr.shape[0] != kr.shape[1]:
+        raise ValueError("kr must be [num_samples][num_samples]")
+    s = kr.shape[0]
+    totals = np.ascontiguousarray(totals, dtype=np.uint64)
+    if totals.shape != (s,):
+        raise ValueError("one total mass per sample")
+    k = _components(num_components)
+    out = _pcoa_buffers(s, k)
+    capi.check(lib.epik_amd_cohort_pcoa_kr_host(kr.ctypes.data, totals.ctypes.data, s, k, out.mu.ctypes.data, out.coord.ctypes.data,
+                                                out.info.ctypes.data))
+    out.info = out.info[0]
+    return out
+
+
+def pcoa_host(mass, first, branch_length, num_components: int = 5) -> Pcoa:
+    """The principal coordinates of the rule for mass[S][N] on the host (`epik_amd_cohort_pcoa_host`)."""
+    lib = capi.load()
+    mass, first, length = _cells_and_tree(mass, first, branch_length)
+    s, n = mass.shape
+    k = _components(num_components)
+    out = _pcoa_buffers(s, k)
+    capi.check(lib.epik_amd_cohort_pcoa_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, k, out.mu.ctypes.data,
+                                             out.coord.ctypes.data, out.info.ctypes.data))
     out.info = out.info[0]
     return out
 
@@ -345,6 +414,60 @@ def permanova_host(mass, first, branch_length, labels, permutations: int = 999, 
                                                   labels.shape[1], int(permutations), int(seed), int(bool(pairwise)),
                                                   records.ctypes.data, ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data))
     return Permanova(records, ssw, group_ss)
+
+
+@dataclass
+class Permdisp:
+    """What PERMDISP gives: `records` `capi.PERMDISP` [M][1 + Q] (the slots of `Permanova`), `stat` float64 [M][1 + Q][P + 1]
+    (eta2 in slot 0, eta_r of the permutations 1 .. P; None where not asked for), `group_mean` float64 [M][32] (the mean
+    distance to centroid of every group) and `z` float64 [M][S] (the distances by sample, NA outside U_c)."""
+    records: np.ndarray
+    stat: np.ndarray | None
+    group_mean: np.ndarray
+    z: np.ndarray
+
+
+def _permdisp_buffers(m: int, s: int, permutations: int, pairwise: bool, with_stat: bool) -> Permdisp:
+    slots = 1 + (capi.PERMDISP_PAIR_SLOTS if pairwise else 0)
+    records = np.zeros((max(m, 1), slots), dtype=capi.PERMDISP)
+    stat = np.full((max(m, 1), slots, min(max(int(permutations), 0), capi.PERMDISP_MAX_PERMUTATIONS) + 1), np.nan) if with_stat else None
+    return Permdisp(records, stat, np.full((max(m, 1), capi.PERMDISP_MAX_GROUPS), np.nan), np.full((max(m, 1), s), np.nan))
+
+
+def permdisp_kr_host(kr, totals, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
+                     with_stat: bool = True) -> Permdisp:
+    """PERMDISP of the rule from a KR matrix kr[S][S] and totals[S] (T_s) on the host (`epik_amd_cohort_permdisp_kr_host`)."""
+    lib = capi.load()
+    kr = np.ascontiguousarray(kr, dtype=np.float64)
+    if kr.ndim != 2 or kr.shape[0] != kr.shape[1]:
+        raise ValueError("kr must be [num_samples][num_samples]")
+    s = kr.shape[0]
+    totals = np.ascontiguousarray(totals, dtype=np.uint64)
+    if totals.shape != (s,):
+        raise ValueError("one total mass per sample")
+    labels = _labels(labels, s)
+    out = _permdisp_buffers(labels.shape[1], s, permutations, pairwise, with_stat)
+    capi.check(lib.epik_amd_cohort_permdisp_kr_host(kr.ctypes.data, totals.ctypes.data, s, labels.ctypes.data, labels.shape[1],
+                                                    int(permutations), int(seed), int(bool(pairwise)), out.records.ctypes.data,
+                                                    out.stat.ctypes.data if with_stat else None, out.group_mean.ctypes.data,
+                                                    out.z.ctypes.data))
+    return out
+
+
+def permdisp_host(mass, first, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
+                  with_stat: bool = True) -> Permdisp:
+    """PERMDISP of the rule for mass[S][N] and labels[S][M] (0xffffffff: missing) on the host
+    (`epik_amd_cohort_permdisp_host`)."""
+    lib = capi.load()
+    mass, first, length = _cells_and_tree(mass, first, branch_length)
+    s, n = mass.shape
+    labels = _labels(labels, s)
+    out = _permdisp_buffers(labels.shape[1], s, permutations, pairwise, with_stat)
+    capi.check(lib.epik_amd_cohort_permdisp_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, labels.ctypes.data,
+                                                 labels.shape[1], int(permutations), int(seed), int(bool(pairwise)),
+                                                 out.records.ctypes.data, out.stat.ctypes.data if with_stat else None,
+                                                 out.group_mean.ctypes.data, out.z.ctypes.data))
+    return out
 
 
 @dataclass
@@ -644,6 +767,48 @@ class Cohort:
                                                        group_ss.ctypes.data))
         return Permanova(records, ssw, group_ss)
 
+    def permdisp_device(self, d_kr: int, labels, permutations: int, seed: int, pairwise: bool, d_out: int, d_group_mean: int,
+                        d_z: int, d_stat: int = 0, stream: int = 0) -> None:
+        """PERMDISP of labels[S][M] (host; 0xffffffff: missing) over d_kr, float64 [S][S] in device memory as `kr_device`
+        wrote it, into d_out, `capi.PERMDISP` [M][1 + Q], d_group_mean, float64 [M][32], d_z, float64 [M][S], and where given
+        d_stat, float64 [M][1 + Q][P + 1], every cell written; asynchronous on `stream` once the labels are copied, no
+        readback (`epik_amd_cohort_permdisp_device`)."""
+        labels = _labels(labels, self.num_samples)
+        capi.check(self._lib.epik_amd_cohort_permdisp_device(self._handle, d_kr or None, labels.ctypes.data, labels.shape[1],
+                                                             int(permutations), int(seed), int(bool(pairwise)), d_out or None,
+                                                             d_stat or None, d_group_mean or None, d_z or None, stream or None))
+
+    def permdisp(self, tree, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
+                 with_stat: bool = False) -> Permdisp:
+        """PERMDISP of the samples' groups in every column of labels[S][M]: do they differ in their distances to the group
+        centroids over the KR distances (`epik_amd_cohort_permdisp`)."""
+        length = self._lengths(tree, branch_length)
+        labels = _labels(labels, self.num_samples)
+        out = _permdisp_buffers(labels.shape[1], self.num_samples, permutations, pairwise, with_stat)
+        capi.check(self._lib.epik_amd_cohort_permdisp(self._handle, tree._handle, length.ctypes.data, labels.ctypes.data,
+                                                      labels.shape[1], int(permutations), int(seed), int(bool(pairwise)),
+                                                      out.records.ctypes.data, out.stat.ctypes.data if with_stat else None,
+                                                      out.group_mean.ctypes.data, out.z.ctypes.data))
+        return out
+
+    def pcoa_device(self, d_kr: int, num_components: int, d_mu: int, d_coord: int, d_info: int, stream: int = 0) -> None:
+        """The principal coordinates over d_kr, float64 [S][S] in device memory as `kr_device` wrote it, into device memory:
+        d_mu float64 [S], d_coord float64 [S][K], d_info one `capi.PCOA_INFO`, every cell written.  Synchronises `stream`
+        once for the number of used samples and, on the eigensolver's global path, once per sweep
+        (`epik_amd_cohort_pcoa_device`)."""
+        capi.check(self._lib.epik_amd_cohort_pcoa_device(self._handle, d_kr or None, _components(num_components), d_mu or None,
+                                                         d_coord or None, d_info or None, stream or None))
+
+    def pcoa(self, tree, branch_length, num_components: int = 5) -> Pcoa:
+        """The principal coordinates of the samples over their KR distances, a `Pcoa` (`epik_amd_cohort_pcoa`)."""
+        length = self._lengths(tree, branch_length)
+        k = _components(num_components)
+        out = _pcoa_buffers(self.num_samples, k)
+        capi.check(self._lib.epik_amd_cohort_pcoa(self._handle, tree._handle, length.ctypes.data, k, out.mu.ctypes.data,
+                                                  out.coord.ctypes.data, out.info.ctypes.data))
+        out.info = out.info[0]
+        return out
+
     def edgetest_device(self, tree, labels, permutations: int, seed: int, d_out: int, d_stat: int = 0, d_max: int = 0,
                         stream: int = 0) -> None:
         """The edge test of labels[S][M] (host; 0xffffffff: missing) into d_out, `capi.EDGETEST` [M][N], and where given
@@ -851,6 +1016,63 @@ def read_epca_edges_tsv(path: str):
 
 
 # ---- the files of --cohort-kmeans --------------------------------------------------------------------------------------
+# ---- the file of --cohort-pcoa ------------------------------------------------------------------------------------------
+def format_pcoa_tsv(names, totals, pcoa: Pcoa) -> str:
+    """cohort_pcoa_<list>.tsv (`totals[s]`: T_s, only > 0 matters): the first line with negative = -neg / pos, a `# unused`
+    line per sample without mass, a `# eigenvalue` line for each of the L eigenvalues (k from 1; mu, fraction = mu / pos or
+    0; real|null|negative), the column names, then per used sample, in list order, its name and its coordinates; doubles
+    as %.17g."""
+    info = pcoa.info
+    is_used = np.asarray(totals) != 0
+    used, kc = int(info["used"]), int(info["components"])
+    if len(is_used) != len(names) or int(is_used.sum()) != used:
+        raise ValueError("the totals do not fit the number of used samples")
+    lines = [f"# epik_amd pcoa v1  samples={len(names)} used={used} components={kc} sweeps={int(info['sweeps'])} "
+             f"converged={int(info['converged'])} negative={'%.17g' % pcoa.negative}"]
+    lines += [f"# unused\t{name}" for name, u in zip(names, is_used) if not u]
+    pos = float(info["pos"])
+    for k, kind in enumerate(pcoa.kinds()):
+        mu = float(pcoa.mu[k])
+        lines.append("# eigenvalue\t%d\t%.17g\t%.17g\t%s" % (k + 1, mu, mu / pos if pos != 0 else 0.0, kind))
+    lines.append("name" + _epca_columns(kc))
+    for i, name in enumerate(names):
+        if is_used[i]:
+            lines.append("\t".join([name, *("%.17g" % float(x) for x in pcoa.coord[i, :kc])]))
+    return "\n".join(lines) + "\n"
+
+
+def read_pcoa_tsv(path: str):
+    """(names, coord, info): the used samples' names, float64 [L][K'], and {"samples", "used", "components", "sweeps",
+    "converged", "negative", "unused": names, "mu", "fraction": float64 [L], "kind": the classes}."""
+    with open(path, newline="") as fh:
+        head = re.fullmatch(r"# epik_amd pcoa v1  samples=(\d+) used=(\d+) components=(\d+) sweeps=(\d+) converged=([01]) "
+                            r"negative=(\S+)", fh.readline().rstrip("\n"))
+        if not head:
+            raise ValueError(f"{path}: not a cohort pcoa file")
+        info = dict(zip(("samples", "used", "components", "sweeps", "converged"), map(int, head.groups()[:5])))
+        info["negative"] = float(head.group(6))
+        unused, eig, line = [], [], fh.readline().rstrip("\n")
+        while line.startswith("# "):
+            fields = line.split("\t")
+            if fields[0] == "# unused" and len(fields) == 2:
+                unused.append(fields[1])
+            elif fields[0] == "# eigenvalue" and len(fields) == 5:
+                eig.append(fields[1:])
+            else:
+                raise ValueError(f"{path}: not a cohort pcoa file")
+            line = fh.readline().rstrip("\n")
+        kc = info["components"]
+        if line != "name" + _epca_columns(kc) or [int(e[0]) for e in eig] != list(range(1, info["used"] + 1)):
+            raise ValueError(f"{path}: the eigenvalues or the column names do not fit the first line")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh if ln.strip()]
+    if len(rows) != info["used"] or any(len(r) != kc + 1 for r in rows):
+        raise ValueError(f"{path}: the rows do not fit the first line")
+    info.update(unused=unused, mu=np.array([float(e[1]) for e in eig]), fraction=np.array([float(e[2]) for e in eig]),
+                kind=[e[3] for e in eig])
+    coord = np.array([[float(x) for x in r[1:]] for r in rows], dtype=np.float64).reshape(len(rows), kc)
+    return [r[0] for r in rows], coord, info
+
+
 def format_kmeans_tsv(names, kmeans: Kmeans) -> str:
     """cohort_kmeans_<list>.tsv: the first line, a `# unused` line per sample without mass, a `# cluster` line per cluster
     k < K' (k, size, the seed's name, sum_dist, sum_sq), the column names, then per used sample, in list order, its name,
@@ -1304,6 +1526,46 @@ def format_permanova_tsv(names, totals, columns, label_names, labels, permutatio
             for h in range(1, len(order)):
                 for g in range(h):
                     lines.append(line(c, label_names[c][order[g]], label_names[c][order[h]], records[c, pair_slot(g, h)]))
+    return "\n".join(lines) + "\n"
+
+
+PERMDISP_HEADER = "column\ta\tb\tused\tgroups\tclipped\teta2\tf\tat_least\tp"
+
+
+def format_permdisp_tsv(names, totals, columns, label_names, labels, permutations: int, seed: int, pairwise: bool, records,
+                        group_mean, z) -> str:
+    """cohort_permdisp_<list>.tsv: the first line, the `# unused`, `# column` and `# group` lines as cohort_permanova's (a
+    group's last field is its mean distance to centroid), the column names, per column the whole test (a = b = *) and, with
+    pairwise, its pairs in slot order; then `# distances`, the column names column name label distance and, per column, a
+    line per sample with mass and a label, in list order; doubles as %.17g, NA as NA."""
+    records, labels = np.asarray(records), np.asarray(labels)
+    slots = 1 + (capi.PERMDISP_PAIR_SLOTS if pairwise else 0)
+    if records.dtype != capi.PERMDISP or records.shape != (len(columns), slots) or labels.shape != (len(names), len(columns)):
+        raise ValueError("records must be capi.PERMDISP [num_columns][1 + Q], labels [num_samples][num_columns]")
+    lines = _used_head("permdisp", names, totals,
+                       f" columns={len(columns)} permutations={int(permutations)} seed={int(seed)} pairwise={int(bool(pairwise))}")
+    groups = groups_of(labels, totals)
+    lines += [f"# column\t{c}\t{name}\t{int(records['used'][c, 0])}\t{int(records['groups'][c, 0])}" for c, name in enumerate(columns)]
+    for c, (order, sizes) in enumerate(groups):
+        lines += [f"# group\t{c}\t{g}\t{label_names[c][v]}\t{sizes[g]}\t{_g17_or_na(group_mean[c][g])}" for g, v in enumerate(order)]
+    lines.append(PERMDISP_HEADER)
+
+    def line(c, a, b, r):
+        return "\t".join([columns[c], a, b, str(int(r["used"])), str(int(r["groups"])), str(int(r["clipped"])), _g17_or_na(r["eta2"]),
+                          _g17_or_na(r["f"]), str(int(r["at_least"])), _g17_or_na(r["p"])])
+
+    for c, (order, _) in enumerate(groups):
+        lines.append(line(c, "*", "*", records[c, 0]))
+        if pairwise:
+            for h in range(1, len(order)):
+                for g in range(h):
+                    lines.append(line(c, label_names[c][order[g]], label_names[c][order[h]], records[c, pair_slot(g, h)]))
+    lines += ["# distances", "column\tname\tlabel\tdistance"]
+    for c, column in enumerate(columns):
+        for s, name in enumerate(names):
+            v = int(labels[s, c])
+            if int(totals[s]) != 0 and v != capi.PERMDISP_MISSING:
+                lines.append(f"{column}\t{name}\t{label_names[c][v]}\t{_g17_or_na(z[c][s])}")
     return "\n".join(lines) + "\n"
 
 

@@ -1,7 +1,7 @@
-// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, kmeans_place.hip, diversity_place.hip, correlation_place.hip, permanova_place.hip and edgetest_place.hip share of a device cohort: the object
+// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, pcoa_place.hip, kmeans_place.hip, diversity_place.hip, correlation_place.hip, permanova_place.hip, edgetest_place.hip and permdisp_place.hip share of a device cohort: the object
 // itself and the launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering and the
 // edge principal components start from; and the device code that the correlation, PERMANOVA and the edge test have in
-// common: a branch's vectors and midranks, the permutation key, and a column's list and groups.
+// common: a branch's vectors and midranks, the permutation key and rank, and a column's list and groups.
 #ifndef EPIK_AMD_COHORT_DEVICE_HPP
 #define EPIK_AMD_COHORT_DEVICE_HPP
 
@@ -29,6 +29,8 @@ struct epik_amd_cohort {
     void *d_squash = nullptr;
     // the workspace of the edge principal components, allocated by the first epca_device (epca_place.hip):
     void *d_epca = nullptr;
+    // the workspace of the principal coordinates, allocated by the first pcoa_device (pcoa_place.hip):
+    void *d_pcoa = nullptr;
     // the workspace of the phylogenetic k-means, allocated by the first kmeans_device (kmeans_place.hip):
     void *d_kmeans = nullptr;
     // the workspace of the alpha diversity and the rarefaction curves (diversity_place.hip): the counts and the alpha
@@ -47,6 +49,10 @@ struct epik_amd_cohort {
     // (edgetest_place.hip):
     void *d_edgetest = nullptr;
     size_t edgetest_bytes = 0;
+    // the workspace of PERMDISP, allocated by the first permdisp_device and grown by a call that needs more
+    // (permdisp_place.hip):
+    void *d_permdisp = nullptr;
+    size_t permdisp_bytes = 0;
 };
 
 namespace epik_amd {
@@ -70,8 +76,15 @@ int cohort_kr_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, const 
 int cohort_mass_plane_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, hipStream_t stream, const uint32_t **d_first,
                               const double **d_X);
 
+// The used samples (T_s > 0 in d_total, which the normalise kernel left) in ascending s, enqueued on `stream`: used[j], jof[s]
+// (kCohortNoIndex for a sample without mass) and L into *count, all uint32 in device memory.  What the edge principal
+// components and the principal coordinates start from (cohort_place.hip).
+constexpr uint32_t kCohortNoIndex = 0xffffffffu;
+int cohort_used_index_enqueue(const epik_amd_cohort *cohort, uint32_t *used, uint32_t *jof, uint32_t *count, hipStream_t stream);
+
 constexpr uint32_t kCohortLdsSamples = 1024;   // the most samples whose four vectors stay in LDS (32 KiB)
 constexpr uint32_t kCohortCountSamples = 128;  // up to here the LDS path counts its ranks; beyond, it sorts
+constexpr uint32_t kCohortKeyTile = 1024;      // the keys a workgroup ranks a labelling against at a time (permutation_rank)
 static_assert(kBlock == 256 && kCohortLdsSamples % kBlock == 0 && 2 * kCohortCountSamples <= kCohortLdsSamples);
 
 #ifdef __HIPCC__
@@ -191,6 +204,28 @@ __device__ inline uint64_t permutation_key(uint64_t seed, uint32_t p, uint32_t i
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
+}
+
+// A workgroup of kBlock lanes, every lane calling it (it has barriers; L and p are uniform): rank_p(i) of the PERMANOVA rule
+// among the L positions, counted against tiles of keys in tile[kCohortKeyTile] (LDS).  Permutation 0 is the identity.  A
+// lane whose i is not below L gets a number that means nothing.
+__device__ inline uint32_t permutation_rank(uint64_t seed, uint32_t p, uint32_t i, uint32_t L, uint64_t *tile)
+{
+    if (p == 0) return i;  // (uniform)
+    const uint64_t mine = permutation_key(seed, p, i);
+    uint32_t rank = 0;
+    for (uint32_t j0 = 0; j0 < L; j0 += kCohortKeyTile) {
+        const uint32_t nt = min(kCohortKeyTile, L - j0);
+        __syncthreads();  // (the tile is written again)
+        for (uint32_t j = threadIdx.x; j < nt; j += kBlock) tile[j] = permutation_key(seed, p, j0 + j);
+        __syncthreads();
+#pragma unroll 4
+        for (uint32_t j = 0; j < nt; ++j) {
+            const uint64_t other = tile[j];  // a broadcast
+            rank += other < mine || (other == mine && j0 + j < i);
+        }
+    }
+    return rank;
 }
 
 // the lanes of a wave whose `flag` is set append (sample, group) to the list in the order of the lanes; returns how many did

@@ -411,12 +411,28 @@ int place_forward(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offs
 constexpr HostVariant kForwardHost{.chunk_reads = 1u << 18, .chunk_bytes = 64u << 20, .chunk_reads_env = "EPIK_AMD_PROFILE_CHUNK_READS",
                                    .workspace_bytes = no_workspace, .zeroed_bytes = nullptr, .place_device = place_forward};
 
+// the used samples (T_s > 0) in ascending s: used[j], jof[s] (kCohortNoIndex for a sample without mass) and L into *count
+__global__ __launch_bounds__(kBlock) void used_index_kernel(const uint64_t *__restrict__ total, uint32_t num_samples,
+                                                            uint32_t *__restrict__ used, uint32_t *__restrict__ jof,
+                                                            uint32_t *__restrict__ count)
+{
+    for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < num_samples; s += gridDim.x * kBlock) {
+        uint32_t j = 0;
+        for (uint32_t t = 0; t < s; ++t) j += total[t] != 0 ? 1u : 0u;
+        const bool mine = total[s] != 0;
+        jof[s] = mine ? j : kCohortNoIndex;
+        if (mine) used[j] = s;  // (j < the number of used samples <= num_samples)
+        if (s == num_samples - 1) *count = j + (mine ? 1u : 0u);
+    }
+}
+
 void free_cohort(epik_amd_cohort *cohort)
 {
     (void)hipFree(cohort->d_cells), (void)hipFree(cohort->d_prefix), (void)hipFree(cohort->d_total);
     (void)hipFree(cohort->d_planes), (void)hipFree(cohort->d_half), (void)hipFree(cohort->d_squash), (void)hipFree(cohort->d_epca);
+    (void)hipFree(cohort->d_pcoa);
     (void)hipFree(cohort->d_kmeans), (void)hipFree(cohort->d_diversity), (void)hipFree(cohort->d_rarefy);
-    (void)hipFree(cohort->d_correlation), (void)hipFree(cohort->d_permanova), (void)hipFree(cohort->d_edgetest);
+    (void)hipFree(cohort->d_correlation), (void)hipFree(cohort->d_permanova), (void)hipFree(cohort->d_edgetest), (void)hipFree(cohort->d_permdisp);
 }
 
 }  // namespace
@@ -432,6 +448,15 @@ int cohort_normalise_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree,
 int cohort_kr_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out, hipStream_t stream)
 {
     return kr_device_impl(cohort, tree, branch_length, d_out, stream);
+}
+
+int cohort_used_index_enqueue(const epik_amd_cohort *cohort, uint32_t *used, uint32_t *jof, uint32_t *count, hipStream_t stream)
+{
+    const uint64_t S = cohort->num_samples, cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
+    const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(S + kBlock - 1) / kBlock, 1024, cap})));
+    hipLaunchKernelGGL(used_index_kernel, grid, dim3(kBlock), 0, stream, cohort->d_total, cohort->num_samples, used, jof, count);
+    HIP_TRY(hipGetLastError());
+    return EPIK_AMD_OK;
 }
 
 int cohort_host_chunked(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,

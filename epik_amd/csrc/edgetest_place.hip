@@ -57,7 +57,7 @@ constexpr uint32_t kLdsPositions = kCohortLdsSamples;  // the most samples whose
 constexpr uint32_t kRegisterGroups = 4;                // up to here the accumulators of a lane are registers (2 or 4 a family)
 constexpr uint32_t kChunk = 1024;                      // the labellings made at a time
 constexpr uint32_t kLdsLanes = 128;                    // the lanes of a workgroup whose accumulators are in LDS (32 KiB at G = 32)
-constexpr uint32_t kKeyTile = 1024;                    // the keys a workgroup ranks against at a time
+constexpr uint32_t kKeyTile = kCohortKeyTile;          // the keys a workgroup ranks against at a time
 constexpr uint32_t kGeneralBlocks = 256;               // workgroups of the observed kernel's general path: each has a slice
 constexpr uint64_t kManyBlocks = 65536;
 
@@ -231,22 +231,7 @@ __global__ __launch_bounds__(kBlock) void edgetest_labellings_kernel(const EdgeA
         const uint32_t p = a.p0 + k;
         for (uint32_t base = 0; base < L; base += kBlock) {
             const uint32_t i = base + tid;
-            uint32_t rank = i;  // (permutation 0 is the identity)
-            if (p != 0) {
-                const uint64_t mine = permutation_key(a.seed, p, i);
-                rank = 0;
-                for (uint32_t j0 = 0; j0 < L; j0 += kKeyTile) {
-                    const uint32_t nt = min(kKeyTile, L - j0);
-                    __syncthreads();  // (the tile is written again)
-                    for (uint32_t j = tid; j < nt; j += kBlock) tile[j] = permutation_key(a.seed, p, j0 + j);
-                    __syncthreads();
-#pragma unroll 4
-                    for (uint32_t j = 0; j < nt; ++j) {
-                        const uint64_t other = tile[j];  // a broadcast
-                        rank += other < mine || (other == mine && j0 + j < i);
-                    }
-                }
-            }
+            const uint32_t rank = permutation_rank(a.seed, p, i, L, tile);  // (permutation 0 is the identity)
             if (i < L) mu8[((uint64_t)(i / 4) * kChunk + k) * 4 + i % 4] = lam[rank];  // (rank < L)
         }
     }

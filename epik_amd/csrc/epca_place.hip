@@ -9,21 +9,15 @@
 // product, but the order in which v_mfma_f64_* adds up its terms is not documented, and the rule fixes that order.
 //
 // Start-up: cohort_normalise_kernel (cohort_place.hip) leaves T_s and the planes C, B [b][Sp].
-//   epca_index_kernel    the used samples (T_s > 0) in ascending s: used[j], jof[s], and L -- which the host reads back:
+//   used_index_kernel    (cohort_place.hip) the used samples (T_s > 0) in ascending s: used[j], jof[s], and L -- which the host reads back:
 //                        the grids, the round-robin schedule and the choice of the eigensolver's path depend on it.
 //   epca_centre_kernel   a lane a branch: X_j[b], the sequential sum over j for the mean, Y into a plane [b][Lp], used
 //                        samples compacted, sample fastest, Lp a multiple of the tile, the padding zero.
 //   epca_gram_kernel     cohort_kr_kernel's tile with one plane and a product for |a - b|: 32 x 32 pairs on or above the
 //                        diagonal, 2 x 2 a lane, 32 branches staged in LDS a chunk, b ascending, mirrored on the way out.
 //   epca_scale_kernel    scale, trace and tol by one lane in the rule's order; V = I and the sweep counters zeroed.
-// The eigensolver, two paths that give the same bits (every element of a phase is one expression of the matrix before
-// that phase, whoever computes it):
-//   epca_jacobi_lds_kernel  L <= 64: one workgroup, A and V in LDS (2 * 32 KB), all rounds and sweeps in one launch.  A
-//                        phase computes its 16 elements a lane into registers, a barrier, the write-back, a barrier.
-//   epca_params_kernel / epca_column_kernel / epca_row_kernel  any L: three launches a round, grid-stride.  The
-//                        column kernel goes from A to a second matrix and turns V in place (a lane owns both columns
-//                        of a pair), the row kernel goes back to A: every (i, j) from (min, max) -- the mirror.  The
-//                        host reads the sweep's rotation counter, 4 bytes, once a sweep.
+// The eigensolver is jacobi_place.hip's (shared with pcoa_place.hip): one launch in LDS for L <= 64, three launches a
+// round beyond, the same bits; the host reads the sweep's rotation counter, 4 bytes, once a sweep there.
 // Then epca_order_kernel (the ranks by counting), epca_raw_kernel (a lane per (b, k), j ascending), epca_sign_kernel
 // (the (|value|, b) reduction, a workgroup a component) and epca_finish_kernel (edge, proj and the info block).
 #include <hip/hip_runtime.h>
@@ -38,24 +32,22 @@
 #include "../host/cohort.hpp"
 #include "cohort_device.hpp"
 #include "host_entry.hpp"
+#include "jacobi_device.hpp"
 
 namespace {
 
 using namespace epik_amd;
 
-constexpr uint32_t kNone = 0xffffffffu;
+constexpr uint32_t kNone = kCohortNoIndex;
 constexpr uint32_t kTile = kCohortTile;
 constexpr uint32_t kChunk = 32;                              // branches staged at a time: 2 * 32 * 32 * 8 = 16 KB of LDS
 constexpr uint32_t kMaxK = EPIK_AMD_EPCA_MAX_COMPONENTS;
-constexpr uint32_t kMaxSweeps = EPIK_AMD_EPCA_MAX_SWEEPS;
-constexpr uint32_t kLdsSide = 64;                            // the LDS path: A and V of up to 64 x 64 doubles
-constexpr uint32_t kLdsHeld = kLdsSide * kLdsSide / kBlock;  // elements of a matrix a lane holds across a barrier
+constexpr uint32_t kMaxSweeps = kJacobiMaxSweeps;
 constexpr uint64_t kMaxBlocks = 1024;
 constexpr uint64_t kGramBlocks = 65536;
 
 static_assert(sizeof(epik_amd_epca_info) == 32);
 static_assert(kBlock == 256 && kTile == 32, "a lane owns 2 x 2 pairs of a 32 x 32 tile");
-static_assert(kLdsHeld * kBlock == kLdsSide * kLdsSide);
 
 // the workspace, one allocation: what the kernels take
 struct EpcaSpace {
@@ -93,20 +85,6 @@ size_t epca_space(void *base, uint32_t S, uint32_t N, uint32_t padded, EpcaSpace
                         u(counters), u(status), u(column), u(null_k)};
     }
     return at;
-}
-
-__global__ __launch_bounds__(kBlock) void epca_index_kernel(const uint64_t *__restrict__ total, uint32_t num_samples,
-                                                            uint32_t *__restrict__ used, uint32_t *__restrict__ jof,
-                                                            uint32_t *__restrict__ count)
-{
-    for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < num_samples; s += gridDim.x * kBlock) {
-        uint32_t j = 0;
-        for (uint32_t t = 0; t < s; ++t) j += total[t] != 0 ? 1u : 0u;
-        const bool mine = total[s] != 0;
-        jof[s] = mine ? j : kNone;
-        if (mine) used[j] = s;  // (j < the number of used samples <= num_samples)
-        if (s == num_samples - 1) *count = j + (mine ? 1u : 0u);
-    }
 }
 
 __global__ __launch_bounds__(kBlock) void epca_centre_kernel(const double *__restrict__ planes, const uint32_t *__restrict__ first,
@@ -189,154 +167,6 @@ __global__ __launch_bounds__(kBlock) void epca_scale_kernel(const double *__rest
             trace = __dadd_rn(trace, g);
         }
         gs[0] = scale, gs[1] = trace, gs[2] = __dmul_rn(0x1p-52, scale);
-    }
-}
-
-// pair i of round r of the round-robin schedule over m indices (m even), ordered
-__device__ inline void pair_of(uint32_t m, uint32_t r, uint32_t i, uint32_t &p, uint32_t &q)
-{
-    const uint32_t x = i ? (r + i) % (m - 1) : r, y = i ? (r + m - 1 - i) % (m - 1) : m - 1;
-    p = x < y ? x : y, q = x < y ? y : x;
-}
-
-// the rotation of a pair from A as it is at the start of the round; whether it rotates
-__device__ inline bool rotation_of(double app, double aqq, double apq, double tol, double &c, double &s)
-{
-    if (!(fabs(apq) > tol)) return false;
-    const double theta = __ddiv_rn(__dsub_rn(aqq, app), __dmul_rn(2.0, apq));
-    double t = __ddiv_rn(1.0, __dadd_rn(fabs(theta), __dsqrt_rn(__dadd_rn(__dmul_rn(theta, theta), 1.0))));
-    if (theta < 0.0) t = -t;
-    c = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dmul_rn(t, t), 1.0)));
-    s = __dmul_rn(t, c);
-    return true;
-}
-
-// c * a - s * b: two products, then one subtraction
-__device__ inline double turned(double c, double a, double s, double b) { return __dsub_rn(__dmul_rn(c, a), __dmul_rn(s, b)); }
-
-__global__ __launch_bounds__(kBlock) void epca_jacobi_lds_kernel(double *__restrict__ A_g, double *__restrict__ V_g, uint32_t L,
-                                                                 const double *__restrict__ gs, uint32_t *__restrict__ status)
-{
-    extern __shared__ double lds_matrices[];  // A[L][L] | V[L][L]
-    __shared__ double cs[kLdsSide], sn[kLdsSide];
-    __shared__ uint32_t partner[kLdsSide];
-    __shared__ uint32_t rotated;
-    const uint32_t cells = L * L, m = L + L % 2, tid = threadIdx.x;
-    double *A = lds_matrices, *V = lds_matrices + cells;
-    for (uint32_t e = tid; e < cells; e += kBlock) A[e] = A_g[e], V[e] = e / L == e % L ? 1.0 : 0.0;
-    if (tid == 0) rotated = 0;
-    const double tol = gs[2];
-    __syncthreads();
-    uint32_t sweeps = 0, converged = 0;
-    while (sweeps < kMaxSweeps && !converged) {  // (uniform: every lane reads the same counter)
-        ++sweeps;
-        for (uint32_t r = 0; r + 1 < m; ++r) {
-            if (tid < m / 2) {  // every index below L is in exactly one pair of the round: partner[] is written whole
-                uint32_t p, q;
-                pair_of(m, r, tid, p, q);
-                if (q >= L) {
-                    partner[p] = kNone;
-                } else {
-                    double c = 1.0, s = 0.0;
-                    const bool turn = rotation_of(A[p * L + p], A[q * L + q], A[p * L + q], tol, c, s);
-                    partner[p] = turn ? q : kNone, partner[q] = turn ? p : kNone;
-                    cs[p] = c, cs[q] = c, sn[p] = s, sn[q] = -s;
-                    if (turn) atomicAdd(&rotated, 1u);
-                }
-            }
-            __syncthreads();
-            double a[kLdsHeld], v[kLdsHeld];
-#pragma unroll
-            for (uint32_t k = 0; k < kLdsHeld; ++k) {  // the column phase, into registers
-                const uint32_t e = tid + k * kBlock;
-                if (e >= cells) continue;
-                const uint32_t i = e / L, j = e - i * L, jp = partner[j];
-                a[k] = jp != kNone ? turned(cs[j], A[e], sn[j], A[i * L + jp]) : A[e];
-                v[k] = jp != kNone ? turned(cs[j], V[e], sn[j], V[i * L + jp]) : V[e];
-            }
-            __syncthreads();
-#pragma unroll
-            for (uint32_t k = 0; k < kLdsHeld; ++k) {
-                const uint32_t e = tid + k * kBlock;
-                if (e < cells) A[e] = a[k], V[e] = v[k];
-            }
-            __syncthreads();
-#pragma unroll
-            for (uint32_t k = 0; k < kLdsHeld; ++k) {  // the row phase on (min, max): the mirror
-                const uint32_t e = tid + k * kBlock;
-                if (e >= cells) continue;
-                const uint32_t i = e / L, j = e - i * L, lo = i < j ? i : j, hi = i < j ? j : i, lp = partner[lo];
-                a[k] = lp == kNone ? A[lo * L + hi] : lp == hi ? 0.0 : turned(cs[lo], A[lo * L + hi], sn[lo], A[lp * L + hi]);
-            }
-            __syncthreads();
-#pragma unroll
-            for (uint32_t k = 0; k < kLdsHeld; ++k) {
-                const uint32_t e = tid + k * kBlock;
-                if (e < cells) A[e] = a[k];
-            }
-            __syncthreads();  // (and partner[] may be written again)
-        }
-        converged = rotated == 0 ? 1u : 0u;
-        __syncthreads();
-        if (tid == 0) rotated = 0;
-        __syncthreads();
-    }
-    for (uint32_t e = tid; e < cells; e += kBlock) A_g[e] = A[e], V_g[e] = V[e];
-    if (tid == 0) status[0] = sweeps, status[1] = converged;
-}
-
-__global__ __launch_bounds__(kBlock) void epca_params_kernel(const double *__restrict__ A, uint32_t L, uint32_t m, uint32_t r,
-                                                             const double *__restrict__ gs, double *__restrict__ cs,
-                                                             double *__restrict__ sn, uint32_t *__restrict__ partner,
-                                                             uint32_t *__restrict__ counter)
-{
-    const double tol = gs[2];
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < m / 2; i += gridDim.x * kBlock) {
-        uint32_t p, q;
-        pair_of(m, r, i, p, q);
-        if (q >= L) {
-            partner[p] = kNone;
-            continue;
-        }
-        double c = 1.0, s = 0.0;
-        const bool turn = rotation_of(A[(uint64_t)p * L + p], A[(uint64_t)q * L + q], A[(uint64_t)p * L + q], tol, c, s);
-        partner[p] = turn ? q : kNone, partner[q] = turn ? p : kNone;
-        cs[p] = c, cs[q] = c, sn[p] = s, sn[q] = -s;
-        if (turn) atomicAdd(counter, 1u);
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void epca_column_kernel(const double *__restrict__ A, double *__restrict__ A1,
-                                                             double *__restrict__ V, uint32_t L, const double *__restrict__ cs,
-                                                             const double *__restrict__ sn, const uint32_t *__restrict__ partner)
-{
-    const uint64_t cells = (uint64_t)L * L;
-    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < cells; e += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t i = (uint32_t)(e / L), j = (uint32_t)(e - (uint64_t)i * L), jp = partner[j];
-        if (jp == kNone) {
-            A1[e] = A[e];
-            continue;
-        }
-        const uint64_t other = (uint64_t)i * L + jp;
-        A1[e] = turned(cs[j], A[e], sn[j], A[other]);
-        if (j < jp) {  // V in place: this lane owns both columns of the pair in row i
-            const double vj = V[e], vp = V[other];
-            V[e] = turned(cs[j], vj, sn[j], vp);
-            V[other] = turned(cs[jp], vp, sn[jp], vj);
-        }
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void epca_row_kernel(const double *__restrict__ A1, double *__restrict__ A, uint32_t L,
-                                                          const double *__restrict__ cs, const double *__restrict__ sn,
-                                                          const uint32_t *__restrict__ partner)
-{
-    const uint64_t cells = (uint64_t)L * L;
-    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < cells; e += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t i = (uint32_t)(e / L), j = (uint32_t)(e - (uint64_t)i * L);
-        const uint32_t lo = i < j ? i : j, hi = i < j ? j : i, lp = partner[lo];
-        const uint64_t at = (uint64_t)lo * L + hi;
-        A[e] = lp == kNone ? A1[at] : lp == hi ? 0.0 : turned(cs[lo], A1[at], sn[lo], A1[(uint64_t)lp * L + hi]);
     }
 }
 
@@ -456,14 +286,12 @@ int epca_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_
     const auto blocks = [&](uint64_t units, uint64_t per, uint64_t most) {
         return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(units + per - 1) / per, most, cap})));
     };
-    hipLaunchKernelGGL(epca_index_kernel, blocks(S, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, cohort->d_total, S, sp.used, sp.jof,
-                       sp.count);
-    HIP_TRY(hipGetLastError());
+    if (const int rc = cohort_used_index_enqueue(cohort, sp.used, sp.jof, sp.count, stream); rc != EPIK_AMD_OK) return rc;
     uint32_t L = 0;
     HIP_TRY(hipMemcpyAsync(&L, sp.count, sizeof L, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (L > S) return fail_with(EPIK_AMD_ERR_HIP, "cohort_epca: the device counted more used samples than there are samples");
-    const uint32_t Lp = (L + kTile - 1) / kTile * kTile, Kc = std::min(K, L), m = L + L % 2;
+    const uint32_t Lp = (L + kTile - 1) / kTile * kTile, Kc = std::min(K, L);
     const uint64_t cells = (uint64_t)L * L;
     if (L) {
         hipLaunchKernelGGL(epca_centre_kernel, blocks(N, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, cohort->d_planes, d_first,
@@ -477,32 +305,11 @@ int epca_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_
     HIP_TRY(hipGetLastError());
     // EPIK_AMD_EPCA_LDS=0 (tests), read at the call: the global path whatever L
     const char *env = std::getenv("EPIK_AMD_EPCA_LDS");
-    const bool lds = L <= kLdsSide && !(env && std::strcmp(env, "0") == 0);
+    const bool lds = L <= kJacobiLdsSide && !(env && std::strcmp(env, "0") == 0);
     uint32_t sweeps = 1, converged = 1;  // (L = 0: one empty sweep)
-    if (L && lds) {
-        const size_t lds_bytes = 2 * (size_t)cells * sizeof(double);
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&epca_jacobi_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(2 * kLdsSide * kLdsSide * sizeof(double))));
-        hipLaunchKernelGGL(epca_jacobi_lds_kernel, dim3(1), dim3(kBlock), lds_bytes, stream, sp.A, sp.V, L, sp.gs, sp.status);
-        HIP_TRY(hipGetLastError());
-    } else if (L) {
-        const dim3 pair_grid = blocks(m / 2, kBlock, kMaxBlocks), cell_grid = blocks(cells, kBlock, kMaxBlocks);
-        sweeps = 0, converged = 0;
-        while (sweeps < kMaxSweeps && !converged) {
-            for (uint32_t r = 0; r + 1 < m; ++r) {
-                hipLaunchKernelGGL(epca_params_kernel, pair_grid, dim3(kBlock), 0, stream, sp.A, L, m, r, sp.gs, sp.cs, sp.sn,
-                                   sp.partner, sp.counters + sweeps);
-                hipLaunchKernelGGL(epca_column_kernel, cell_grid, dim3(kBlock), 0, stream, sp.A, sp.A1, sp.V, L, sp.cs, sp.sn,
-                                   sp.partner);
-                hipLaunchKernelGGL(epca_row_kernel, cell_grid, dim3(kBlock), 0, stream, sp.A1, sp.A, L, sp.cs, sp.sn, sp.partner);
-            }
-            HIP_TRY(hipGetLastError());
-            uint32_t rotated = 0;  // the one readback of a sweep
-            HIP_TRY(hipMemcpyAsync(&rotated, sp.counters + sweeps, sizeof rotated, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            ++sweeps;
-            converged = rotated == 0 ? 1u : 0u;
-        }
+    if (L) {
+        const JacobiSpace js{sp.A, sp.A1, sp.V, sp.cs, sp.sn, sp.gs, sp.partner, sp.counters, sp.status};
+        if (const int rc = jacobi_sweeps(js, L, lds, cap, stream, sweeps, converged); rc != EPIK_AMD_OK) return rc;
     }
     auto *mu = static_cast<double *>(d_mu), *proj = static_cast<double *>(d_proj), *edge = static_cast<double *>(d_edge);
     hipLaunchKernelGGL(epca_order_kernel, dim3(1), dim3(kBlock), 0, stream, sp.A, L, K, Kc, sp.gs, sp.column, sp.null_k, sp.root, mu);

@@ -189,56 +189,19 @@ int squash_merges(const uint64_t* mass, uint32_t num_samples, uint32_t num_branc
     return EPIK_AMD_OK;
 }
 
-int epca_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
-                    uint32_t num_components, double* mu, double* proj, double* edge, epik_amd_epca_info* info, std::string& err)
+namespace {
+
+// The Jacobi paragraph of the edge-PCA rule on A[L][L] (symmetric) and V[L][L] (the identity on entry): cyclic, round-robin,
+// the rotations of a round applied together.  The principal coordinates take it as it is.
+void jacobi_sweeps(std::vector<double>& A, std::vector<double>& V, size_t L, double tol, uint32_t& sweeps, uint32_t& converged)
 {
-    const size_t S = num_samples, N = num_branches, K = num_components;
-    if (K < 1 || K > EPIK_AMD_EPCA_MAX_COMPONENTS) {
-        err = "num_components = " + std::to_string(K) + " is outside [1, 64]";
-        return EPIK_AMD_ERR_INVALID;
-    }
-    kr_planes p;
-    if (const int rc = make_planes(mass, S, N, first, nullptr, p, err); rc != EPIK_AMD_OK) return rc;
-    std::vector<size_t> used;
-    for (size_t s = 0; s < S; ++s)
-        if (p.total[s] != 0) used.push_back(s);
-    const size_t L = used.size(), Kc = std::min(K, L);
-    // the centred imbalances Y[j][b]
-    std::vector<double> Y(L * N, 0.0);
-    for (size_t b = 0; b < N; ++b) {
-        const bool inner = first[b] < b;
-        double acc = 0.0;
-        for (size_t j = 0; j < L; ++j) {
-            const double x = inner ? (p.B[used[j] * N + b] + p.C[used[j] * N + b]) - 1.0 : 0.0;
-            Y[j * N + b] = x;
-            acc = acc + x;
-        }
-        const double mean = L ? acc / (double)L : 0.0;
-        for (size_t j = 0; j < L; ++j) Y[j * N + b] = Y[j * N + b] - mean;
-    }
-    // the Gram matrix, its scale and trace
-    std::vector<double> A(L * L, 0.0), V(L * L, 0.0), A1(L * L), V1(L * L);
-    for (size_t i = 0; i < L; ++i)
-        for (size_t j = i; j < L; ++j) {
-            const double *yi = &Y[i * N], *yj = &Y[j * N];
-            double acc = 0.0;
-            for (size_t b = 0; b < N; ++b) acc = acc + yi[b] * yj[b];
-            A[i * L + j] = A[j * L + i] = acc;
-        }
-    double scale = 0.0, trace = 0.0;
-    for (size_t j = 0; j < L; ++j) {
-        if (A[j * L + j] > scale) scale = A[j * L + j];
-        trace = trace + A[j * L + j];
-        V[j * L + j] = 1.0;
-    }
-    const double tol = std::ldexp(1.0, -52) * scale;
-    // cyclic Jacobi, round-robin, the rotations of a round applied together
+    std::vector<double> A1(L * L), V1(L * L);
     const size_t m = L + L % 2;
     std::vector<double> cs(L), sn(L);
     std::vector<size_t> partner(L);
     std::vector<char> rot(L);
-    uint32_t sweeps = 0, converged = 0;
-    while (sweeps < EPIK_AMD_EPCA_MAX_SWEEPS && !converged) {
+    sweeps = 0, converged = 0;
+    while (sweeps < EPIK_AMD_JACOBI_MAX_SWEEPS && !converged) {
         ++sweeps;
         size_t rotated = 0;
         for (size_t r = 0; r + 1 < m; ++r) {
@@ -276,6 +239,55 @@ int epca_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_bra
         }
         converged = rotated == 0;
     }
+}
+
+}  // namespace
+
+int epca_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                    uint32_t num_components, double* mu, double* proj, double* edge, epik_amd_epca_info* info, std::string& err)
+{
+    const size_t S = num_samples, N = num_branches, K = num_components;
+    if (K < 1 || K > EPIK_AMD_EPCA_MAX_COMPONENTS) {
+        err = "num_components = " + std::to_string(K) + " is outside [1, 64]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    kr_planes p;
+    if (const int rc = make_planes(mass, S, N, first, nullptr, p, err); rc != EPIK_AMD_OK) return rc;
+    std::vector<size_t> used;
+    for (size_t s = 0; s < S; ++s)
+        if (p.total[s] != 0) used.push_back(s);
+    const size_t L = used.size(), Kc = std::min(K, L);
+    // the centred imbalances Y[j][b]
+    std::vector<double> Y(L * N, 0.0);
+    for (size_t b = 0; b < N; ++b) {
+        const bool inner = first[b] < b;
+        double acc = 0.0;
+        for (size_t j = 0; j < L; ++j) {
+            const double x = inner ? (p.B[used[j] * N + b] + p.C[used[j] * N + b]) - 1.0 : 0.0;
+            Y[j * N + b] = x;
+            acc = acc + x;
+        }
+        const double mean = L ? acc / (double)L : 0.0;
+        for (size_t j = 0; j < L; ++j) Y[j * N + b] = Y[j * N + b] - mean;
+    }
+    // the Gram matrix, its scale and trace
+    std::vector<double> A(L * L, 0.0), V(L * L, 0.0);
+    for (size_t i = 0; i < L; ++i)
+        for (size_t j = i; j < L; ++j) {
+            const double *yi = &Y[i * N], *yj = &Y[j * N];
+            double acc = 0.0;
+            for (size_t b = 0; b < N; ++b) acc = acc + yi[b] * yj[b];
+            A[i * L + j] = A[j * L + i] = acc;
+        }
+    double scale = 0.0, trace = 0.0;
+    for (size_t j = 0; j < L; ++j) {
+        if (A[j * L + j] > scale) scale = A[j * L + j];
+        trace = trace + A[j * L + j];
+        V[j * L + j] = 1.0;
+    }
+    const double tol = std::ldexp(1.0, -52) * scale;
+    uint32_t sweeps = 0, converged = 0;
+    jacobi_sweeps(A, V, L, tol, sweeps, converged);
     // the components: by (mu descending, j ascending)
     std::vector<size_t> column(Kc);
     for (size_t j = 0; j < L; ++j) {
@@ -980,6 +992,88 @@ int permanova_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_b
                                    ssw, group_ss, err);
 }
 
+int pcoa_components_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, uint32_t num_components, double* mu,
+                          double* coord, epik_amd_pcoa_info* info, std::string& err)
+{
+    const size_t S = num_samples, K = num_components;
+    if (K < 1 || K > EPIK_AMD_PCOA_MAX_COMPONENTS) {
+        err = "num_components = " + std::to_string(K) + " is outside [1, 64]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    std::vector<size_t> used;
+    for (size_t s = 0; s < S; ++s)
+        if (totals[s] != 0) used.push_back(s);
+    const size_t L = used.size(), Kc = std::min(K, L);
+    // the squared distances, Gower's centring, the scale and the trace
+    std::vector<double> A(L * L, 0.0), V(L * L, 0.0), r(L);
+    for (size_t i = 0; i < L; ++i)
+        for (size_t j = 0; j < L; ++j) {
+            const double d = kr[used[i] * S + used[j]];
+            A[i * L + j] = d * d;
+        }
+    double g = 0.0;
+    for (size_t i = 0; i < L; ++i) {
+        double acc = 0.0;
+        for (size_t j = 0; j < L; ++j) acc = acc + A[j * L + i];  // (KR[u_j][u_i], the element the device's lanes read)
+        r[i] = acc / (double)L;
+        g = g + r[i];
+    }
+    if (L) g = g / (double)L;
+    for (size_t i = 0; i < L; ++i)
+        for (size_t j = i; j < L; ++j) A[i * L + j] = A[j * L + i] = -0.5 * (((A[i * L + j] - r[i]) - r[j]) + g);
+    double scale = 0.0, trace = 0.0;
+    for (size_t j = 0; j < L; ++j) {
+        if (std::fabs(A[j * L + j]) > scale) scale = std::fabs(A[j * L + j]);
+        trace = trace + A[j * L + j];
+        V[j * L + j] = 1.0;
+    }
+    uint32_t sweeps = 0, converged = 0;
+    jacobi_sweeps(A, V, L, std::ldexp(1.0, -52) * scale, sweeps, converged);
+    // the axes: by (mu descending, j ascending), all L of them
+    std::vector<size_t> column(L);
+    for (size_t j = 0; j < L; ++j) {
+        size_t rank = 0;
+        for (size_t i = 0; i < L; ++i)
+            rank += A[i * L + i] > A[j * L + j] || (A[i * L + i] == A[j * L + j] && i < j) ? 1 : 0;
+        column[rank] = j;
+    }
+    std::fill(mu, mu + S, 0.0), std::fill(coord, coord + S * K, 0.0);
+    const double floor_mu = std::ldexp(1.0, -40) * scale;
+    double pos = 0.0, neg = 0.0;
+    for (size_t k = 0; k < L; ++k) {
+        const size_t jk = column[k];
+        mu[k] = A[jk * L + jk];
+        if (mu[k] > floor_mu) pos = pos + mu[k];
+        if (mu[k] < -floor_mu) neg = neg + mu[k];
+        if (k >= Kc || !(mu[k] > floor_mu)) continue;
+        const double root = std::sqrt(mu[k]);
+        size_t at = 0;
+        for (size_t j = 0; j < L; ++j)
+            if (std::fabs(V[j * L + jk]) > std::fabs(V[at * L + jk])) at = j;
+        const double sign = V[at * L + jk] < 0.0 ? -1.0 : 1.0;
+        for (size_t j = 0; j < L; ++j) coord[used[j] * K + k] = sign * (V[j * L + jk] * root);
+    }
+    *info = epik_amd_pcoa_info{(uint32_t)L, (uint32_t)Kc, sweeps, converged, trace, scale, pos, neg};
+    return EPIK_AMD_OK;
+}
+
+int pcoa_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                    const double* branch_length, uint32_t num_components, double* mu, double* coord, epik_amd_pcoa_info* info,
+                    std::string& err)
+{
+    const size_t S = num_samples, N = num_branches;
+    if (num_components < 1 || num_components > EPIK_AMD_PCOA_MAX_COMPONENTS) {
+        err = "num_components = " + std::to_string(num_components) + " is outside [1, 64]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    std::vector<double> kr(S * S);
+    if (const int rc = kr_matrix(mass, num_samples, num_branches, first, branch_length, kr.data(), err); rc != EPIK_AMD_OK) return rc;
+    std::vector<uint64_t> totals(S, 0);
+    for (size_t s = 0; s < S; ++s)
+        for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
+    return pcoa_components_of_kr(kr.data(), totals.data(), num_samples, num_components, mu, coord, info, err);
+}
+
 namespace {
 
 // the rule's midranks by sorting: the same two counts as midranks(), found in another way (exact half-integers)
@@ -1140,6 +1234,144 @@ int edgetest_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_br
         }
     }
     return EPIK_AMD_OK;
+}
+
+namespace {
+
+// what the tests of a column share under the PERMDISP rule: z, r and the clipped flags by position
+struct permdisp_column {
+    std::vector<double> z, r;
+    std::vector<char> clip;
+};
+
+// one test of the PERMDISP rule: the column's positions pos[n] with the groups lam[n] of sizes size[G]
+void permdisp_test(const permdisp_column& col, const std::vector<uint32_t>& pos, const std::vector<uint8_t>& lam,
+                   const std::vector<uint32_t>& size, uint32_t P, uint64_t seed, epik_amd_permdisp& rec, double* stat)
+{
+    const size_t n = pos.size(), G = size.size();
+    rec.used = (uint32_t)n, rec.groups = (uint32_t)G;
+    for (size_t i = 0; i < n; ++i) rec.clipped += col.clip[pos[i]] != 0;
+    if (G < 2 || n < G + 1) return;
+    std::vector<double> x(n), sums(G);
+    for (size_t i = 0; i < n; ++i) x[i] = col.z[pos[i]];
+    centred dz, dr;
+    dz.of(x);
+    if (!(dz.ss > 0.0)) return;
+    const double among = edgetest_among(dz.d.data(), lam.data(), n, size, sums.data());
+    rec.eta2 = among / dz.ss;
+    const double ssw = dz.ss - among;
+    if (ssw > 0.0) rec.f = (among / (double)(G - 1)) / (ssw / (double)(n - G));
+    if (stat) stat[0] = rec.eta2;
+    for (size_t i = 0; i < n; ++i) x[i] = col.r[pos[i]];
+    dr.of(x);
+    if (!(dr.ss > 0.0)) {  // nothing to permute: every permuted statistic is a tie
+        rec.at_least = P;
+        if (stat) std::fill(stat + 1, stat + 1 + P, rec.eta2);
+    } else {
+        std::vector<std::pair<uint64_t, uint32_t>> keys(n);
+        std::vector<uint8_t> mu(n);
+        for (uint32_t p = 1; p <= P; ++p) {
+            for (uint32_t i = 0; i < n; ++i) keys[i] = {permanova_key(seed, p, i), i};
+            std::sort(keys.begin(), keys.end());
+            for (size_t q = 0; q < n; ++q) mu[keys[q].second] = lam[q];  // (rank_p(keys[q].second) = q)
+            const double eta = edgetest_among(dr.d.data(), mu.data(), n, size, sums.data()) / dr.ss;
+            if (stat) stat[p] = eta;
+            rec.at_least += eta >= rec.eta2;
+        }
+    }
+    rec.p = (double)(1 + rec.at_least) / (double)(P + 1);
+}
+
+}  // namespace
+
+int permdisp_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint32_t num_columns, uint32_t num_permutations,
+                             std::string& err)
+{
+    return edgetest_arguments_valid(labels, num_samples, num_columns, num_permutations, err);  // (the same caps)
+}
+
+int permdisp_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
+                           uint32_t num_columns, uint32_t num_permutations, uint64_t seed, bool pairwise, epik_amd_permdisp* out,
+                           double* stat, double* group_mean, double* z, std::string& err)
+{
+    const size_t S = num_samples, M = num_columns, P = num_permutations;
+    if (const int rc = permdisp_arguments_valid(labels, num_samples, num_columns, num_permutations, err); rc != EPIK_AMD_OK) return rc;
+    const size_t slots = 1 + (pairwise ? EPIK_AMD_PERMDISP_PAIR_SLOTS : 0);
+    const double na = na_value();
+    for (size_t e = 0; e < M * slots; ++e) out[e] = epik_amd_permdisp{0, 0, 0, 0, 0, na, na, na};
+    if (stat) std::fill(stat, stat + M * slots * (P + 1), na);
+    std::fill(group_mean, group_mean + M * EPIK_AMD_PERMDISP_MAX_GROUPS, na);
+    std::fill(z, z + M * S, na);
+    for (size_t c = 0; c < M; ++c) {
+        std::vector<uint32_t> idx, size, group_of(EPIK_AMD_PERMDISP_MAX_GROUPS, EPIK_AMD_PERMDISP_MISSING);
+        std::vector<uint8_t> lam;
+        for (size_t s = 0; s < S; ++s) {
+            const uint32_t v = labels[s * M + c];
+            if (totals[s] == 0 || v == EPIK_AMD_PERMDISP_MISSING) continue;
+            if (group_of[v] == EPIK_AMD_PERMDISP_MISSING) group_of[v] = (uint32_t)size.size(), size.push_back(0);
+            idx.push_back((uint32_t)s), lam.push_back((uint8_t)group_of[v]), ++size[group_of[v]];
+        }
+        const size_t L = idx.size(), G = size.size();
+        // the distances to the centroids: t_i and W_g are PERMANOVA's chains under lambda; A2[i][j] is the square of KR[u_j][u_i]
+        const auto a2 = [&](size_t i, size_t j) {
+            const double d = kr[(size_t)idx[j] * S + idx[i]];
+            return d * d;
+        };
+        std::vector<double> w(G, 0.0), mean(G, 0.0), m(L);
+        for (size_t i = 0; i < L; ++i) {
+            double t = 0.0, all = 0.0;
+            for (size_t j = 0; j < L; ++j) {
+                if (lam[j] != lam[i]) continue;
+                const double a = a2(i, j);
+                all = all + a;
+                if (j > i) t = t + a;
+            }
+            w[lam[i]] = w[lam[i]] + t;
+            m[i] = all / (double)size[lam[i]];
+        }
+        permdisp_column col;
+        col.z.resize(L), col.r.resize(L), col.clip.resize(L);
+        for (size_t i = 0; i < L; ++i) {
+            const uint32_t g = lam[i];
+            const double z2 = m[i] - (w[g] / (double)size[g]) / (double)size[g];
+            col.clip[i] = z2 < 0.0;
+            col.z[i] = z2 > 0.0 ? std::sqrt(z2) : 0.0;
+            mean[g] = mean[g] + col.z[i];
+            z[c * S + idx[i]] = col.z[i];
+        }
+        for (size_t g = 0; g < G; ++g) group_mean[c * EPIK_AMD_PERMDISP_MAX_GROUPS + g] = mean[g] = mean[g] / (double)size[g];
+        for (size_t i = 0; i < L; ++i) col.r[i] = col.z[i] - mean[lam[i]];
+        std::vector<uint32_t> pos(L);
+        for (size_t i = 0; i < L; ++i) pos[i] = (uint32_t)i;
+        permdisp_test(col, pos, lam, size, num_permutations, seed, out[c * slots], stat ? stat + c * slots * (P + 1) : nullptr);
+        if (!pairwise) continue;
+        for (size_t h = 1; h < G; ++h)
+            for (size_t g = 0; g < h; ++g) {
+                std::vector<uint32_t> sub;
+                std::vector<uint8_t> two;
+                for (size_t i = 0; i < L; ++i)
+                    if (lam[i] == g || lam[i] == h) sub.push_back((uint32_t)i), two.push_back(lam[i] == h);
+                const size_t slot = c * slots + 1 + h * (h - 1) / 2 + g;
+                permdisp_test(col, sub, two, {size[g], size[h]}, num_permutations, seed, out[slot],
+                              stat ? stat + slot * (P + 1) : nullptr);
+            }
+    }
+    return EPIK_AMD_OK;
+}
+
+int permdisp_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                     const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
+                     uint64_t seed, bool pairwise, epik_amd_permdisp* out, double* stat, double* group_mean, double* z, std::string& err)
+{
+    const size_t S = num_samples, N = num_branches;
+    if (const int rc = permdisp_arguments_valid(labels, num_samples, num_columns, num_permutations, err); rc != EPIK_AMD_OK) return rc;
+    std::vector<double> kr(S * S);
+    if (const int rc = kr_matrix(mass, num_samples, num_branches, first, branch_length, kr.data(), err); rc != EPIK_AMD_OK) return rc;
+    std::vector<uint64_t> totals(S, 0);
+    for (size_t s = 0; s < S; ++s)
+        for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
+    return permdisp_records_of_kr(kr.data(), totals.data(), num_samples, labels, num_columns, num_permutations, seed, pairwise, out,
+                                  stat, group_mean, z, err);
 }
 
 cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise, size_t most_labels,
@@ -1394,6 +1626,32 @@ std::string format_epca_edges_tsv(const std::vector<uint32_t>& first, const doub
     return out;
 }
 
+std::string format_pcoa_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, uint32_t num_components,
+                            const double* mu, const double* coord, const epik_amd_pcoa_info& info)
+{
+    const size_t S = samples.size(), K = num_components, Kc = info.components, L = info.used;
+    const double floor_mu = std::ldexp(1.0, -40) * info.scale;
+    std::string out = "# epik_amd pcoa v1  samples=" + std::to_string(S) + " used=" + std::to_string(L) +
+                      " components=" + std::to_string(Kc) + " sweeps=" + std::to_string(info.sweeps) +
+                      " converged=" + std::to_string(info.converged) +
+                      " negative=" + g17(info.pos != 0.0 ? (0.0 - info.neg) / info.pos : 0.0) + "\n";
+    for (size_t s = 0; s < S; ++s)
+        if (totals[s] == 0) out += "# unused\t" + samples[s].name + "\n";
+    for (size_t k = 0; k < L; ++k)
+        out += "# eigenvalue\t" + std::to_string(k + 1) + '\t' + g17(mu[k]) + '\t' + g17(info.pos != 0.0 ? mu[k] / info.pos : 0.0) +
+               '\t' + (mu[k] > floor_mu ? "real" : mu[k] < -floor_mu ? "negative" : "null") + '\n';
+    out += "name";
+    for (size_t k = 0; k < Kc; ++k) out += "\tpc" + std::to_string(k + 1);
+    out += '\n';
+    for (size_t s = 0; s < S; ++s) {
+        if (totals[s] == 0) continue;
+        out += samples[s].name;
+        for (size_t k = 0; k < Kc; ++k) out += '\t' + g17(coord[s * K + k]);
+        out += '\n';
+    }
+    return out;
+}
+
 std::string format_kmeans_tsv(const std::vector<cohort_sample>& samples, const epik_amd_kmeans_sample* records,
                               const epik_amd_kmeans_cluster* clusters, const epik_amd_kmeans_info& info)
 {
@@ -1605,6 +1863,57 @@ std::string format_edgetest_tsv(const std::vector<cohort_sample>& samples, const
                        '\t' + g17_or_na(ranks.stat) + '\t' + g17_or_na(ranks.p) + '\t' + g17_or_na(ranks.p_adj);
             }
             out += '\n';
+        }
+    return out;
+}
+
+std::string format_permdisp_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                                const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
+                                const uint32_t* labels, uint32_t num_permutations, uint64_t seed, bool pairwise,
+                                const epik_amd_permdisp* records, const double* group_mean, const double* z)
+{
+    const size_t S = samples.size(), M = columns.size(), slots = 1 + (pairwise ? EPIK_AMD_PERMDISP_PAIR_SLOTS : 0);
+    std::string out = used_head(samples, totals, "permdisp",
+                                " columns=" + std::to_string(M) + " permutations=" + std::to_string(num_permutations) +
+                                    " seed=" + std::to_string(seed) + " pairwise=" + (pairwise ? "1" : "0"));
+    // the groups of every column in the rule's order: by first appearance among the used samples
+    std::vector<std::vector<uint32_t>> label_of(M), size_of(M);
+    for (size_t c = 0; c < M; ++c) {
+        std::map<uint32_t, uint32_t> group_of;
+        for (size_t s = 0; s < S; ++s) {
+            const uint32_t v = labels[s * M + c];
+            if (totals[s] == 0 || v == EPIK_AMD_PERMDISP_MISSING) continue;
+            const auto [it, fresh] = group_of.emplace(v, (uint32_t)label_of[c].size());
+            if (fresh) label_of[c].push_back(v), size_of[c].push_back(0);
+            ++size_of[c][it->second];
+        }
+    }
+    for (size_t c = 0; c < M; ++c)
+        out += "# column\t" + std::to_string(c) + '\t' + columns[c] + '\t' + std::to_string(records[c * slots].used) + '\t' +
+               std::to_string(records[c * slots].groups) + '\n';
+    for (size_t c = 0; c < M; ++c)
+        for (size_t g = 0; g < label_of[c].size(); ++g)
+            out += "# group\t" + std::to_string(c) + '\t' + std::to_string(g) + '\t' + names[c][label_of[c][g]] + '\t' +
+                   std::to_string(size_of[c][g]) + '\t' + g17_or_na(group_mean[c * EPIK_AMD_PERMDISP_MAX_GROUPS + g]) + '\n';
+    out += "column\ta\tb\tused\tgroups\tclipped\teta2\tf\tat_least\tp\n";
+    const auto line = [&](size_t c, const std::string& a, const std::string& b, const epik_amd_permdisp& r) {
+        out += columns[c] + '\t' + a + '\t' + b + '\t' + std::to_string(r.used) + '\t' + std::to_string(r.groups) + '\t' +
+               std::to_string(r.clipped) + '\t' + g17_or_na(r.eta2) + '\t' + g17_or_na(r.f) + '\t' + std::to_string(r.at_least) + '\t' +
+               g17_or_na(r.p) + '\n';
+    };
+    for (size_t c = 0; c < M; ++c) {
+        line(c, "*", "*", records[c * slots]);
+        if (!pairwise) continue;
+        for (size_t h = 1; h < label_of[c].size(); ++h)
+            for (size_t g = 0; g < h; ++g)
+                line(c, names[c][label_of[c][g]], names[c][label_of[c][h]], records[c * slots + 1 + h * (h - 1) / 2 + g]);
+    }
+    out += "# distances\ncolumn\tname\tlabel\tdistance\n";
+    for (size_t c = 0; c < M; ++c)
+        for (size_t s = 0; s < S; ++s) {
+            const uint32_t v = labels[s * M + c];
+            if (totals[s] == 0 || v == EPIK_AMD_PERMDISP_MISSING) continue;
+            out += columns[c] + '\t' + samples[s].name + '\t' + names[c][v] + '\t' + g17_or_na(z[c * S + s]) + '\n';
         }
     return out;
 }

@@ -107,6 +107,16 @@ int permanova_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_b
                       const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
                       uint64_t seed, bool pairwise, epik_amd_permanova* out, double* ssw, double* group_ss, std::string& err);
 
+/// Principal coordinates by the rule (include/epik_amd.h) from a KR matrix kr[S][S] and totals[S] (T_s): mu[S], coord[S][K]
+/// and *info, every cell written.  libepik_amd's kernels (pcoa_place.hip) give the same bits.  0, or EPIK_AMD_ERR_INVALID
+/// with `err` naming K outside [1, 64].
+int pcoa_components_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, uint32_t num_components, double* mu,
+                          double* coord, epik_amd_pcoa_info* info, std::string& err);
+/// The same from the cells: kr_matrix, then pcoa_components_of_kr.  The code behind epik_amd_cohort_pcoa_host.
+int pcoa_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                    const double* branch_length, uint32_t num_components, double* mu, double* coord, epik_amd_pcoa_info* info,
+                    std::string& err);
+
 /// num_columns in [1, 64], num_permutations in [1, 999 999], every label below 32 or 0xffffffff (missing): 0, or
 /// EPIK_AMD_ERR_INVALID with `err` naming the cause
 int edgetest_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint32_t num_columns, uint32_t num_permutations,
@@ -117,6 +127,21 @@ int edgetest_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint3
 int edgetest_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                      const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, epik_amd_edgetest* out,
                      double* stat, double* max, std::string& err);
+
+/// num_columns in [1, 64], num_permutations in [1, 999 999], every label below 32 or 0xffffffff (missing): 0, or
+/// EPIK_AMD_ERR_INVALID with `err` naming the cause
+int permdisp_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint32_t num_columns, uint32_t num_permutations,
+                             std::string& err);
+/// PERMDISP by the rule (include/epik_amd.h) from the matrix kr[S][S] and totals[S], one thread: out[M][1 + Q], group_mean[M][32],
+/// z[M][S] and, where not null, stat[M][1 + Q][P + 1], every cell written.  libepik_amd's kernels (permdisp_place.hip) give the
+/// same bits.  The code behind epik_amd_cohort_permdisp_kr_host.  0, or as permdisp_arguments_valid.
+int permdisp_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
+                           uint32_t num_columns, uint32_t num_permutations, uint64_t seed, bool pairwise, epik_amd_permdisp* out,
+                           double* stat, double* group_mean, double* z, std::string& err);
+/// The same from mass[S][N]: the KR matrix by kr_matrix first.  The code behind epik_amd_cohort_permdisp_host.
+int permdisp_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                     const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
+                     uint64_t seed, bool pairwise, epik_amd_permdisp* out, double* stat, double* group_mean, double* z, std::string& err);
 
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
@@ -154,8 +179,8 @@ struct cohort_factors {
 cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise,
                                    size_t most_labels = 0, const char* flag = "--cohort-permanova");
 
-/// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash | epca | epca_edges | kmeans |
-/// kmeans_centroids | alpha | rarefy | correlation | dispersion | permanova | edgetest
+/// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash | epca | epca_edges | pcoa | kmeans |
+/// kmeans_centroids | alpha | rarefy | correlation | dispersion | permanova | edgetest | permdisp
 std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir,
                                  const std::string& extension = ".tsv");
 
@@ -183,6 +208,13 @@ std::string format_squash_newick(const std::vector<cohort_sample>& samples, cons
 std::string format_epca_tsv(const std::vector<cohort_sample>& samples, const std::vector<char>& used, uint32_t num_components,
                             const double* mu, const double* proj, const epik_amd_epca_info& info);
 std::string format_epca_edges_tsv(const std::vector<uint32_t>& first, const double* edge, const epik_amd_epca_info& info);
+/// cohort_pcoa .tsv: "# epik_amd pcoa v1  samples=S used=L components=K' sweeps=n converged=0|1 negative=x" (x = -neg / pos,
+/// 0 when pos is 0), a "# unused<TAB>name" line per sample without mass (totals[s] == 0), a "# eigenvalue<TAB>k<TAB>mu<TAB>
+/// fraction<TAB>real|null|negative" line for each of the L eigenvalues (k from 1, fraction = mu / pos or 0), the column names
+/// name pc1 .. pcK', then per used sample in list order its name and coord[s][0 .. K'), the rows of coord K = num_components
+/// wide; doubles %.17g.
+std::string format_pcoa_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, uint32_t num_components,
+                            const double* mu, const double* coord, const epik_amd_pcoa_info& info);
 /// cohort_kmeans .tsv: "# epik_amd kmeans v1  samples=S used=L clusters=K' iterations=i converged=0|1", a "# unused<TAB>name"
 /// line per sample without mass, a "# cluster<TAB>k<TAB>size<TAB>seed name<TAB>sum_dist<TAB>sum_sq" line per cluster
 /// k < K', the column names name cluster dist, then per used sample in list order its name, cluster and dist; doubles %.17g.
@@ -229,6 +261,15 @@ std::string format_edgetest_tsv(const std::vector<cohort_sample>& samples, const
                                 const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
                                 const uint32_t* labels, uint32_t num_branches, uint32_t num_permutations, uint64_t seed,
                                 const epik_amd_edgetest* records);
+/// cohort_permdisp .tsv: "# epik_amd permdisp v1  samples=S used=L columns=M permutations=P seed=X pairwise=0|1", the "# unused"
+/// lines, the "# column" lines as cohort_permanova's, a "# group<TAB>c<TAB>g<TAB>label<TAB>n<TAB>mean_distance" line per group (from
+/// group_mean[M][32]), the column names column a b used groups clipped eta2 f at_least p, per column the whole test (a = b = *)
+/// and, with pairwise, its pairs in slot order from records[M][1 + Q]; then "# distances", the column names column name label
+/// distance and, per column, a line per sample of U_c in list order from z[M][S]; doubles %.17g, NA as NA.
+std::string format_permdisp_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                                const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
+                                const uint32_t* labels, uint32_t num_permutations, uint64_t seed, bool pairwise,
+                                const epik_amd_permdisp* records, const double* group_mean, const double* z);
 /// `text` into `filename` through `filename`.part, renamed when all of it is written
 void write_through_part(const std::string& filename, const std::string& text);
 

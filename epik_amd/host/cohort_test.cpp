@@ -7,6 +7,11 @@
 //                                           uint32 num_merges
 //   cohort_test epca <out.bin> <in.bin> <K> the edge principal components of a `kr` input (its lengths are not used):
 //                                           float64 mu[K], proj[S][K], edge[K][N], then epik_amd_epca_info
+//   cohort_test pcoa <out.bin> <in.bin> <K> the principal coordinates of a `kr` input: float64 mu[S], coord[S][K], then
+//                                           epik_amd_pcoa_info
+//   cohort_test pcoa-tsv <out.tsv> <in.bin> <names.txt> <K>
+//                                           the file of --cohort-pcoa for a `kr` input whose samples are named by the lines
+//                                           of names.txt, through the formatter
 //   cohort_test kmeans <out.bin> <in.bin> <K> <max_iterations>
 //                                           the phylogenetic k-means of a `kr` input: epik_amd_kmeans_sample [S],
 //                                           epik_amd_kmeans_cluster [K], float64 centroids[K][N], then epik_amd_kmeans_info
@@ -21,6 +26,11 @@
 //   cohort_test permanova <out.bin> <in.bin> <labels.bin> <P> <seed> <pairwise>
 //                                           PERMANOVA of a `kr` input with a raw `labels` file, uint32 [S][M]:
 //                                           epik_amd_permanova [M][1 + Q], float64 ssw[M][1 + Q][P + 1], float64 group_ss[M][256]
+//   cohort_test permdisp <out.bin> <in.bin> <labels.bin> <P> <seed> <pairwise>
+//                                           PERMDISP of a `kr` input, arguments as permanova's (a label below 32):
+//                                           epik_amd_permdisp [M][1 + Q], float64 stat[M][1 + Q][P + 1], group_mean[M][32], z[M][S]
+//   cohort_test permdisp-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed> <pairwise>
+//                                           the file of --cohort-permdisp, as permanova-tsv
 //   cohort_test permanova-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed> <pairwise>
 //                                           the file of --cohort-permanova for a `kr` input whose samples are named by the
 //                                           lines of names.txt, through the factor file's reader and the formatter
@@ -154,6 +164,44 @@ int main(int argc, char** argv)
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }
+        if ((argc == 5 && std::strcmp(argv[1], "pcoa") == 0) || (argc == 6 && std::strcmp(argv[1], "pcoa-tsv") == 0)) {
+            const bool tsv = argc == 6;
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto mass = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const auto length = read_array<double>(in, N);
+            const unsigned long K = std::stoul(argv[argc - 1]);
+            if (K < 1 || K > EPIK_AMD_PCOA_MAX_COMPONENTS) throw std::runtime_error("num_components = " + std::to_string(K) + " is outside [1, 64]");
+            std::vector<double> mu(S), coord(S * K);
+            epik_amd_pcoa_info info{};
+            std::string err;
+            if (epik_amd::pcoa_components(mass.data(), (uint32_t)S, (uint32_t)N, first.data(), length.data(), (uint32_t)K, mu.data(),
+                                          coord.data(), &info, err) != 0)
+                throw std::runtime_error(err);
+            if (tsv) {
+                std::vector<epik_amd::cohort_sample> samples;
+                std::ifstream names(argv[4]);
+                if (!names) throw std::runtime_error(std::string("cannot open ") + argv[4]);
+                for (std::string line; std::getline(names, line);) samples.push_back({line, ""});
+                if (samples.size() != S) throw std::runtime_error("the names file does not name every sample");
+                std::vector<uint64_t> totals(S, 0);
+                for (uint64_t s = 0; s < S; ++s)
+                    for (uint64_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
+                epik_amd::write_through_part(argv[2], epik_amd::format_pcoa_tsv(samples, totals.data(), (uint32_t)K, mu.data(),
+                                                                                coord.data(), info));
+                return 0;
+            }
+            std::ofstream out(argv[2], std::ios::binary);
+            write_array(out, mu.data(), mu.size());
+            write_array(out, coord.data(), coord.size());
+            write_array(out, &info, 1);
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
         if (argc == 6 && std::strcmp(argv[1], "kmeans") == 0) {
             std::ifstream in(argv[3], std::ios::binary);
             if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
@@ -251,8 +299,9 @@ int main(int argc, char** argv)
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }
-        if ((argc == 8 && std::strcmp(argv[1], "permanova") == 0) || (argc == 9 && std::strcmp(argv[1], "permanova-tsv") == 0)) {
-            const bool tsv = argc == 9;
+        if ((argc == 8 && (std::strcmp(argv[1], "permanova") == 0 || std::strcmp(argv[1], "permdisp") == 0)) ||
+            (argc == 9 && (std::strcmp(argv[1], "permanova-tsv") == 0 || std::strcmp(argv[1], "permdisp-tsv") == 0))) {
+            const bool tsv = argc == 9, disp = std::strncmp(argv[1], "permdisp", 8) == 0;
             std::ifstream in(argv[3], std::ios::binary);
             if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
             const auto head = read_array<uint64_t>(in, 2);
@@ -272,7 +321,8 @@ int main(int argc, char** argv)
                 if (!names) throw std::runtime_error(std::string("cannot open ") + argv[4]);
                 for (std::string line; std::getline(names, line);) samples.push_back({line, ""});
                 if (samples.size() != S) throw std::runtime_error("the names file does not name every sample");
-                factors = epik_amd::read_cohort_factors(argv[5], samples, pairwise);
+                factors = disp ? epik_amd::read_cohort_factors(argv[5], samples, false, EPIK_AMD_PERMDISP_MAX_GROUPS, "--cohort-permdisp")
+                               : epik_amd::read_cohort_factors(argv[5], samples, pairwise);
                 std::cout << "Cohort factors: " << factors.columns.size() << " columns, " << factors.skipped
                           << " lines of samples that are not in the list skipped" << std::endl;
                 labels = factors.labels;
@@ -288,6 +338,31 @@ int main(int argc, char** argv)
             if (M > EPIK_AMD_PERMANOVA_MAX_COLUMNS) throw std::runtime_error("the labels file has more than 64 columns");
             if (P < 1 || P > EPIK_AMD_PERMANOVA_MAX_PERMUTATIONS) throw std::runtime_error("P is outside [1, 999999]");
             const uint64_t tests = M * (1 + (pairwise ? EPIK_AMD_PERMANOVA_PAIR_SLOTS : 0));
+            if (disp) {
+                std::vector<epik_amd_permdisp> records(tests);
+                std::vector<double> stat(tsv ? 0 : tests * ((uint64_t)P + 1)), group_mean(M * EPIK_AMD_PERMDISP_MAX_GROUPS), z(M * S);
+                std::string err;
+                if (epik_amd::permdisp_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), lengths.data(), labels.data(),
+                                               (uint32_t)M, P, seed, pairwise, records.data(), tsv ? nullptr : stat.data(),
+                                               group_mean.data(), z.data(), err) != 0)
+                    throw std::runtime_error(err);
+                if (tsv) {
+                    std::vector<uint64_t> totals(S, 0);
+                    for (uint64_t s = 0; s < S; ++s)
+                        for (uint64_t b = 0; b < N; ++b) totals[s] += cells[s * N + b];
+                    epik_amd::write_through_part(argv[2], epik_amd::format_permdisp_tsv(samples, totals.data(), factors.columns, factors.names,
+                                                                                        labels.data(), P, seed, pairwise, records.data(),
+                                                                                        group_mean.data(), z.data()));
+                    return 0;
+                }
+                std::ofstream out(argv[2], std::ios::binary);
+                write_array(out, records.data(), records.size());
+                write_array(out, stat.data(), stat.size());
+                write_array(out, group_mean.data(), group_mean.size());
+                write_array(out, z.data(), z.size());
+                if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+                return 0;
+            }
             std::vector<epik_amd_permanova> records(tests);
             std::vector<double> ssw(tsv ? 0 : tests * ((uint64_t)P + 1)), group_ss(M * EPIK_AMD_PERMANOVA_MAX_GROUPS);
             std::string err;
@@ -367,10 +442,12 @@ int main(int argc, char** argv)
             return 0;
         }
         std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin> | squash <out.bin> <in.bin> | "
-                     "epca <out.bin> <in.bin> <K> | kmeans <out.bin> <in.bin> <K> <max_iterations> | alpha <out.bin> <in.bin> | "
+                     "epca <out.bin> <in.bin> <K> | pcoa <out.bin> <in.bin> <K> | pcoa-tsv <out.tsv> <in.bin> <names.txt> <K> | kmeans <out.bin> <in.bin> <K> <max_iterations> | alpha <out.bin> <in.bin> | "
                      "rarefy <out.bin> <in.bin> <depth_step> <num_depths> | correlation <out.bin> <in.bin> <meta.bin> | "
                      "dispersion <out.bin> <in.bin> | permanova <out.bin> <in.bin> <labels.bin> <P> <seed> <pairwise> | "
                      "permanova-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed> <pairwise> | "
+                     "permdisp <out.bin> <in.bin> <labels.bin> <P> <seed> <pairwise> | "
+                     "permdisp-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed> <pairwise> | "
                      "edgetest <out.bin> <in.bin> <labels.bin> <P> <seed> | "
                      "edgetest-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed>\n";
         return 2;

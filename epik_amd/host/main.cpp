@@ -235,6 +235,10 @@ const char* kHelp =
     "                          on the device and write cohort_epca_<list>.tsv (the components and every sample's\n"
     "                          projections) and cohort_epca_edges_<list>.tsv (the components' coefficients per inner branch)\n"
     "      --cohort-epca-components arg  With --cohort-epca: the number of components, in [1, 64] (default: 5)\n"
+    "      --cohort-pcoa       With --cohort: also compute the principal coordinates (Gower 1966) of the samples over their KR\n"
+    "                          distances on the device and write cohort_pcoa_<list>.tsv (all eigenvalues, the negative ones of a\n"
+    "                          distance that is not Euclidean included, and every sample's coordinates)\n"
+    "      --cohort-pcoa-components arg  With --cohort-pcoa: the number of axes, in [1, 64] (default: 5)\n"
     "      --cohort-kmeans arg With --cohort: also cluster the samples into at most arg clusters, in [1, 64], by phylogenetic\n"
     "                          k-means (Czech et al. 2019) on the device and write cohort_kmeans_<list>.tsv (the clusters and\n"
     "                          every sample's cluster and distance) and cohort_kmeans_centroids_<list>.tsv (the centroids' masses)\n"
@@ -260,6 +264,13 @@ const char* kHelp =
     "      --cohort-permanova-seed arg  With --cohort-permanova: the seed of the permutations, a uint64 (default: 1)\n"
     "      --cohort-permanova-pairwise  With --cohort-permanova: also test every two groups of every column (at most 32 groups\n"
     "                          a column)\n"
+    "      --cohort-permdisp arg  With --cohort: also test, for every factor column of the TSV file arg (as --cohort-permanova's,\n"
+    "                          at most 32 labels a column), whether its groups differ in spread: PERMDISP (Anderson 2006), the\n"
+    "                          distances to the group centroids over the KR distances, by permutation of residuals on the\n"
+    "                          device; cohort_permdisp_<list>.tsv\n"
+    "      --cohort-permdisp-permutations arg  With --cohort-permdisp: the number of permutations in [1, 999999] (default: 999)\n"
+    "      --cohort-permdisp-seed arg  With --cohort-permdisp: the seed of the permutations, a uint64 (default: 1)\n"
+    "      --cohort-permdisp-pairwise  With --cohort-permdisp: also test every two groups of every column\n"
     "      --cohort-edge-test arg  With --cohort: also test, for every factor column of the TSV file arg (as --cohort-permanova's,\n"
     "                          at most 32 labels a column), on which branches its groups of samples differ: the one-way ANOVA and\n"
     "                          Kruskal-Wallis of every branch's mass and imbalance by permutation, with the max-statistic\n"
@@ -306,7 +317,7 @@ options parse_args(int argc, char** argv)
         } else {
             continue;  // positional arguments are ignored (epik.py passes the query twice, epik.py:88,96)
         }
-        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca" || name == "cohort-alpha" || name == "cohort-dispersion" || name == "cohort-permanova-pairwise" || name == "taxonomy-per-read") && !have_value)) {  // flags
+        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca" || name == "cohort-pcoa" || name == "cohort-alpha" || name == "cohort-dispersion" || name == "cohort-permanova-pairwise" || name == "cohort-permdisp-pairwise" || name == "taxonomy-per-read") && !have_value)) {  // flags
             opt.values[name] = "1";
             continue;
         }
@@ -426,6 +437,25 @@ int main(int argc, char** argv)
                 throw std::runtime_error("--cohort-epca-components must be a whole number in [1, 64], not '" + text + "'");
             epca_components = (uint32_t)k;
         }
+        const bool with_pcoa = parsed.has("cohort-pcoa");
+        if (with_pcoa && !with_cohort)
+            throw std::runtime_error("--cohort-pcoa needs --cohort (it takes the principal coordinates of the samples of the list)");
+        if (parsed.has("cohort-pcoa-components") && !with_pcoa)
+            throw std::runtime_error("--cohort-pcoa-components needs --cohort-pcoa (the flag that computes the coordinates)");
+        uint32_t pcoa_components = 5;
+        if (with_pcoa) {
+            const auto text = parsed.get("cohort-pcoa-components", "5");
+            size_t used = 0;
+            unsigned long k = 0;
+            try {
+                k = std::stoul(text, &used);
+            } catch (const std::exception&) {
+                used = 0;
+            }
+            if (used != text.size() || used == 0 || text[0] == '-' || k < 1 || k > EPIK_AMD_PCOA_MAX_COMPONENTS)
+                throw std::runtime_error("--cohort-pcoa-components must be a whole number in [1, 64], not '" + text + "'");
+            pcoa_components = (uint32_t)k;
+        }
         const bool with_kmeans = parsed.has("cohort-kmeans");
         if (with_kmeans && !with_cohort) throw std::runtime_error("--cohort-kmeans needs --cohort (it clusters the samples of the list)");
         if (parsed.has("cohort-kmeans-iterations") && !with_kmeans)
@@ -505,6 +535,31 @@ int main(int argc, char** argv)
             const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
             if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-permanova-seed " + text + ": not a uint64");
             permanova_seed = v;
+        }
+        const bool with_permdisp = parsed.has("cohort-permdisp"), permdisp_pairwise = parsed.has("cohort-permdisp-pairwise");
+        if (with_permdisp && !with_cohort)
+            throw std::runtime_error("--cohort-permdisp needs --cohort (it tests the dispersions of the groups of the samples of the list)");
+        for (const char* dependent : {"cohort-permdisp-permutations", "cohort-permdisp-seed", "cohort-permdisp-pairwise"})
+            if (parsed.has(dependent) && !with_permdisp)
+                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-permdisp" +
+                                         (with_cohort ? "" : " (and that needs --cohort )"));
+        uint32_t permdisp_permutations = 999;
+        uint64_t permdisp_seed = 1;
+        if (parsed.has("cohort-permdisp-permutations")) {
+            const std::string text = parsed.require("cohort-permdisp-permutations");
+            char* end = nullptr;
+            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
+            if (!end || *end || v < 1 || v > EPIK_AMD_PERMDISP_MAX_PERMUTATIONS)
+                throw std::runtime_error("--cohort-permdisp-permutations " + text + ": the number must lie in [1, 999999]");
+            permdisp_permutations = (uint32_t)v;
+        }
+        if (parsed.has("cohort-permdisp-seed")) {
+            const std::string text = parsed.require("cohort-permdisp-seed");
+            char* end = nullptr;
+            errno = 0;
+            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
+            if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-permdisp-seed " + text + ": not a uint64");
+            permdisp_seed = v;
         }
         const bool with_edgetest = parsed.has("cohort-edge-test");
         if (with_edgetest && !with_cohort)
@@ -596,6 +651,15 @@ int main(int argc, char** argv)
             edge_factors = epik_amd::read_cohort_factors(parsed.require("cohort-edge-test"), cohort_samples, false,
                                                          EPIK_AMD_EDGETEST_MAX_GROUPS, "--cohort-edge-test");
             std::cout << "Cohort edge-test factors: " << edge_factors.columns.size() << " columns, " << edge_factors.skipped
+                      << " lines of samples that are not in the list skipped" << std::endl;
+        }
+
+        // --cohort-permdisp: the same reader with the cap of 32 labels, before the database or a device is
+        epik_amd::cohort_factors disp_factors;
+        if (with_permdisp) {
+            disp_factors = epik_amd::read_cohort_factors(parsed.require("cohort-permdisp"), cohort_samples, false,
+                                                         EPIK_AMD_PERMDISP_MAX_GROUPS, "--cohort-permdisp");
+            std::cout << "Cohort PERMDISP factors: " << disp_factors.columns.size() << " columns, " << disp_factors.skipped
                       << " lines of samples that are not in the list skipped" << std::endl;
         }
 
@@ -979,6 +1043,7 @@ int main(int argc, char** argv)
         const auto cohort_squash_tree_filename = epik_amd::make_cohort_filename("squash", query_file, output_dir, ".nwk");
         const auto cohort_epca_filename = epik_amd::make_cohort_filename("epca", query_file, output_dir);
         const auto cohort_epca_edges_filename = epik_amd::make_cohort_filename("epca_edges", query_file, output_dir);
+        const auto cohort_pcoa_filename = epik_amd::make_cohort_filename("pcoa", query_file, output_dir);
         const auto cohort_kmeans_filename = epik_amd::make_cohort_filename("kmeans", query_file, output_dir);
         const auto cohort_kmeans_centroids_filename = epik_amd::make_cohort_filename("kmeans_centroids", query_file, output_dir);
         const auto cohort_alpha_filename = epik_amd::make_cohort_filename("alpha", query_file, output_dir);
@@ -987,7 +1052,9 @@ int main(int argc, char** argv)
         const auto cohort_dispersion_filename = epik_amd::make_cohort_filename("dispersion", query_file, output_dir);
         const auto cohort_permanova_filename = epik_amd::make_cohort_filename("permanova", query_file, output_dir);
         const auto cohort_edgetest_filename = epik_amd::make_cohort_filename("edgetest", query_file, output_dir);
-        bool epca_converged = true, kmeans_converged = true;
+        const auto cohort_permdisp_filename = epik_amd::make_cohort_filename("permdisp", query_file, output_dir);
+        uint64_t permdisp_clipped = 0;
+        bool epca_converged = true, kmeans_converged = true, pcoa_converged = true;
         if (with_cohort) {
             // the handles' cohorts summed on the first device, read once, and the distances computed there
             epik_amd::sample_cohort cohort((uint32_t)cohort_samples.size(), (uint32_t)tree.get_node_count());
@@ -1008,10 +1075,16 @@ int main(int argc, char** argv)
             epik_amd::placer::cohort_edgetest edgetest;
             edgetest.labels = edge_factors.labels.data(), edgetest.num_columns = (uint32_t)edge_factors.columns.size();
             edgetest.num_permutations = edgetest_permutations, edgetest.seed = edgetest_seed;
+            epik_amd::placer::cohort_pcoa pcoa;
+            pcoa.num_components = pcoa_components;
+            epik_amd::placer::cohort_permdisp permdisp;
+            permdisp.labels = disp_factors.labels.data(), permdisp.num_columns = (uint32_t)disp_factors.columns.size();
+            permdisp.num_permutations = permdisp_permutations, permdisp.seed = permdisp_seed, permdisp.pairwise = permdisp_pairwise;
             placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
                                with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr, with_kmeans ? &kmeans : nullptr,
                                with_alpha || with_rarefy ? &diversity : nullptr, with_correlation || with_dispersion ? &edges : nullptr,
-                               with_permanova ? &permanova : nullptr, with_edgetest ? &edgetest : nullptr);
+                               with_permanova ? &permanova : nullptr, with_edgetest ? &edgetest : nullptr, with_pcoa ? &pcoa : nullptr,
+                               with_permdisp ? &permdisp : nullptr);
             epik_amd::write_through_part(cohort_samples_filename, epik_amd::format_cohort_samples_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_profile_filename, epik_amd::format_cohort_profile_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_kr_filename, epik_amd::format_cohort_kr_tsv(cohort_samples, kr));
@@ -1078,6 +1151,27 @@ int main(int argc, char** argv)
                                                                            edge_factors.names, edge_factors.labels.data(),
                                                                            (uint32_t)cohort.num_branches, edgetest_permutations,
                                                                            edgetest_seed, edgetest.records.data()));
+            }
+            if (with_permdisp) {
+                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
+                for (size_t s = 0; s < mass_of.size(); ++s)
+                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
+                epik_amd::write_through_part(cohort_permdisp_filename,
+                                             epik_amd::format_permdisp_tsv(cohort_samples, mass_of.data(), disp_factors.columns,
+                                                                           disp_factors.names, disp_factors.labels.data(),
+                                                                           permdisp_permutations, permdisp_seed, permdisp_pairwise,
+                                                                           permdisp.records.data(), permdisp.group_mean.data(),
+                                                                           permdisp.z.data()));
+                const size_t slots = permdisp.records.size() / disp_factors.columns.size();
+                for (size_t c = 0; c < disp_factors.columns.size(); ++c) permdisp_clipped += permdisp.records[c * slots].clipped;
+            }
+            if (with_pcoa) {
+                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
+                for (size_t s = 0; s < mass_of.size(); ++s)
+                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
+                epik_amd::write_through_part(cohort_pcoa_filename, epik_amd::format_pcoa_tsv(cohort_samples, mass_of.data(), pcoa.num_components,
+                                                                                             pcoa.mu.data(), pcoa.coord.data(), pcoa.info));
+                pcoa_converged = pcoa.info.converged != 0;
             }
             if (with_squash) {
                 epik_amd::write_through_part(cohort_squash_filename,
@@ -1156,6 +1250,14 @@ int main(int argc, char** argv)
         if (with_dispersion) std::cout << "Cohort edge dispersion: " << cohort_dispersion_filename << std::endl;
         if (with_permanova) std::cout << "Cohort PERMANOVA: " << cohort_permanova_filename << std::endl;
         if (with_edgetest) std::cout << "Cohort edge test: " << cohort_edgetest_filename << std::endl;
+        if (with_permdisp) std::cout << "Cohort PERMDISP: " << cohort_permdisp_filename << std::endl;
+        if (permdisp_clipped)
+            std::cout << "Warning: " << permdisp_clipped << " squared distances to a group centroid are negative (the KR distance is not "
+                      << "Euclidean) and count as zero (the clipped column of " << cohort_permdisp_filename << ")" << std::endl;
+        if (with_pcoa) std::cout << "Cohort principal coordinates: " << cohort_pcoa_filename << std::endl;
+        if (!pcoa_converged)
+            std::cout << "Warning: the principal coordinates did not converge in " << EPIK_AMD_PCOA_MAX_SWEEPS
+                      << " sweeps (converged=0 in " << cohort_pcoa_filename << ")" << std::endl;
         if (with_taxonomy) std::cout << "Taxa: " << taxa_filename << std::endl;
         if (taxonomy_per_read) std::cout << "Taxa of the reads: " << taxa_reads_filename << std::endl;
         if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;

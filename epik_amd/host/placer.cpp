@@ -40,6 +40,8 @@
 #pragma weak epik_amd_cohort_dispersion
 #pragma weak epik_amd_cohort_permanova
 #pragma weak epik_amd_cohort_edgetest
+#pragma weak epik_amd_cohort_pcoa
+#pragma weak epik_amd_cohort_permdisp
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -295,8 +297,10 @@ void placer::read_taxonomy(uint64_t* direct, uint64_t* assigned, epik_amd_taxa_t
 void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                          epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans,
                          cohort_diversity* diversity, cohort_edges* edges, cohort_permanova* permanova,
-                         cohort_edgetest* edgetest)
+                         cohort_edgetest* edgetest, cohort_pcoa* pcoa, cohort_permdisp* permdisp)
 {
+    if (permdisp && !&epik_amd_cohort_permdisp) throw std::runtime_error("GPU placer: this libepik_amd has no PERMDISP");
+    if (pcoa && !&epik_amd_cohort_pcoa) throw std::runtime_error("GPU placer: this libepik_amd has no principal coordinates");
     if (edgetest && !&epik_amd_cohort_edgetest) throw std::runtime_error("GPU placer: this libepik_amd has no edge test");
     if (permanova && !&epik_amd_cohort_permanova) throw std::runtime_error("GPU placer: this libepik_amd has no PERMANOVA");
     if (edges && (!&epik_amd_cohort_correlation || !&epik_amd_cohort_dispersion))
@@ -380,6 +384,19 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
         edgetest->records.assign((size_t)edgetest->num_columns * parent.size(), epik_amd_edgetest{});
         rc = epik_amd_cohort_edgetest(_cohorts[0], tree, edgetest->labels, edgetest->num_columns, edgetest->num_permutations,
                                       edgetest->seed, edgetest->records.data(), nullptr, nullptr);
+    }
+    if (rc == EPIK_AMD_OK && pcoa) {
+        pcoa->mu.assign(_cohort_samples, 0.0), pcoa->coord.assign((size_t)_cohort_samples * pcoa->num_components, 0.0);
+        rc = epik_amd_cohort_pcoa(_cohorts[0], tree, length.data(), pcoa->num_components, pcoa->mu.data(), pcoa->coord.data(), &pcoa->info);
+    }
+    if (rc == EPIK_AMD_OK && permdisp) {
+        const size_t slots = 1 + (permdisp->pairwise ? EPIK_AMD_PERMDISP_PAIR_SLOTS : 0);
+        permdisp->records.assign(permdisp->num_columns * slots, epik_amd_permdisp{});
+        permdisp->group_mean.assign((size_t)permdisp->num_columns * EPIK_AMD_PERMDISP_MAX_GROUPS, 0.0);
+        permdisp->z.assign((size_t)permdisp->num_columns * _cohort_samples, 0.0);
+        rc = epik_amd_cohort_permdisp(_cohorts[0], tree, length.data(), permdisp->labels, permdisp->num_columns,
+                                      permdisp->num_permutations, permdisp->seed, permdisp->pairwise ? 1 : 0, permdisp->records.data(),
+                                      nullptr, permdisp->group_mean.data(), permdisp->z.data());
     }
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);

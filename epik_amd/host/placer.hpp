@@ -223,10 +223,28 @@ public:
         uint64_t seed = 1;
         std::vector<epik_amd_edgetest> records;
     };
+    /// With `pcoa` (--cohort-pcoa): the principal coordinates of the samples over the KR distances; num_components is K on
+    /// entry; mu of num_samples eigenvalues, coord of num_samples * K values and the info block on return.
+    struct cohort_pcoa {
+        uint32_t num_components = 0;
+        std::vector<double> mu, coord;
+        epik_amd_pcoa_info info{};
+    };
+    /// With `permdisp` (--cohort-permdisp): PERMDISP of labels[S][M] with num_permutations permutations from `seed`, with the
+    /// pairs of groups too where `pairwise`; records of M * (1 + Q) tests, group_mean of M * 32 and z of M * S values on return.
+    struct cohort_permdisp {
+        const uint32_t* labels = nullptr;
+        uint32_t num_columns = 0, num_permutations = 999;
+        uint64_t seed = 1;
+        bool pairwise = false;
+        std::vector<epik_amd_permdisp> records;
+        std::vector<double> group_mean, z;
+    };
     void read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                      epik_amd_squash_merge* merges = nullptr, uint32_t* num_merges = nullptr, cohort_epca* epca = nullptr,
                      cohort_kmeans* kmeans = nullptr, cohort_diversity* diversity = nullptr, cohort_edges* edges = nullptr,
-                     cohort_permanova* permanova = nullptr, cohort_edgetest* edgetest = nullptr);
+                     cohort_permanova* permanova = nullptr, cohort_edgetest* edgetest = nullptr, cohort_pcoa* pcoa = nullptr,
+                     cohort_permdisp* permdisp = nullptr);
     /// --taxonomy: one device taxonomy object per handle (epik_amd_taxonomy) from taxon_parent[T] and label[N], with one
     /// row of cells per sample of the cohort (call set_cohort first) or one row; from then on place_flat goes through
     /// the epik_amd_placer_taxa_* entries: every unique sequence is added with the number of its records as weight, a

@@ -877,6 +877,33 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *     undefined or a slot without a pair.  group_ss[M][256], where asked for: W_g / (double)n_g of lambda for g < G of a
  *     column whose test is defined, NA otherwise.  Every cell of every output is written.
  *
+ * Principal coordinates (Gower 1966; classical scaling, `cmdscale`, `pcoa`) of the cohort's samples over the KR distances:
+ *   the ordination in which beta diversity is drawn.  From the matrix KR[S][S] of the KR rule, T_s and K in [1, 64].  The KR
+ *   distance on a tree is not Euclidean, so the doubly centred matrix may be indefinite: the negative eigenvalues are
+ *   written out, never hidden.  All arithmetic is IEEE double, every operation rounded on its own, nothing fused.
+ *   Used samples.  Sample s is used iff T_s > 0; the used samples, in ascending s, get the indices j = 0 .. L - 1 (u_j is
+ *     the sample of index j).  L may be 0.
+ *   Squares.  A2[i][j] = KR(u_i, u_j) * KR(u_i, u_j): one multiply, the PERMANOVA rule's squared distances.  The matrix is
+ *     symmetric bit for bit as kr_device writes it.  For a forged one: r_i reads KR[u_j][u_i], and B[i][j], i <= j, reads
+ *     KR[u_i][u_j]; the device, the host mirror (_pcoa_kr_host) and the tests' restatement all read those elements.
+ *   Centring (Gower).  Every sum is a sequential chain from +0.0:
+ *       r_i = (sum over j = 0 .. L - 1, ascending, of A2[i][j]) / (double)L,     g = (sum over i ascending of r_i) / (double)L,
+ *       for i <= j: B[i][j] = -0.5 * (((A2[i][j] - r_i) - r_j) + g),  and B[j][i] = B[i][j].
+ *     scale = max over j of |B[j][j]| (+0.0 for L = 0); trace = the sequential sum of B[j][j], j ascending, from +0.0;
+ *     tol = 2^-52 * scale.
+ *   Eigen-decomposition.  Exactly the Jacobi paragraph of the edge-PCA rule with A = B and this tol: the same rounds, the
+ *     same three phases, the 64-sweep cap, `sweeps` and `converged`.
+ *   Components.  mu_j = A[j][j], ordered by (mu descending, j ascending): mu[k], k = 0 .. L - 1, ALL L eigenvalues, the
+ *     negative ones included; mu[k] = +0.0 for k >= L.  K' = min(K, L).  Axis k < K' is real iff mu_k > 2^-40 * scale.
+ *     For a real axis, with j(k) the column of V it came from: j* = the first j with the largest |V[j][j(k)]|,
+ *     sign = -1 iff V[j*][j(k)] < 0, else +1, and
+ *       coord[s][k] = sign * (V[j(s)][j(k)] * sqrt(mu_k)).
+ *     coord is +0.0 for an axis that is not real, for k >= K' and for an unused s.
+ *     pos = the sequential sum from +0.0, k ascending, of the mu_k > 2^-40 * scale; neg = the same sum of the
+ *     mu_k < -(2^-40 * scale) (so neg <= 0).  An eigenvalue in neither sum is `null`.
+ *   The file derives, one division each: fraction_k = mu_k / pos, 0 when pos is 0; negative = -neg / pos, 0 when pos is 0:
+ *     how far the cohort is from Euclidean.  Every cell of every output is written.
+ *
  * Edge test (per-branch one-way ANOVA and Kruskal-Wallis by permutation, with the single-step max-statistic adjustment of
  *   Westfall & Young 1993): on which branches do the groups of a factor column differ?  From mass[S][N], first[N] and
  *   labels[S][M] as for PERMANOVA, M in [1, 64], but a label is below EPIK_AMD_EDGETEST_MAX_GROUPS = 32 (0xffffffff means
@@ -908,6 +935,36 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *   An undefined family: its doubles are NA and its counts 0.  used = L and groups = G are always written.
  *   Results.  out[M][N] records.  stat[M][4][N][P + 1], where asked for: eta(mu^p), NA where undefined.  max[M][4][P + 1],
  *     where asked for: Mmax_p with p = 0 as well, NA for a family without a defined branch.  Every cell is written.
+ *
+ * PERMDISP (Anderson 2006; vegan's `betadisper` + `permutest`, centroids) of the cohort's samples over the KR distances: do the
+ *   groups of a factor column differ in spread?  The companion of a significant PERMANOVA, which cannot tell a difference in
+ *   location from one in dispersion.  From the matrix KR[S][S], T_s, labels[S][M] (a label below 32, the edge test's cap, or
+ *   0xffffffff), P in [1, 999 999] and a uint64 seed.  All arithmetic is IEEE double, every operation rounded on its own.
+ *   U_c, the positions, the groups by first appearance, G, n_g, lambda, the labellings mu^p (the same keys from the same seed,
+ *     mu^0 = lambda) and A2 = KR * KR are exactly those of the PERMANOVA rule.  A2[i][j] below is read as the square of
+ *     KR[u_j][u_i] (the matrix is symmetric bit for bit as kr_device writes it; a forged matrix must be too).
+ *   Distances to centroids, per column, in closed form (no eigenvectors: betadisper's "real-axes distance^2 minus
+ *     imaginary-axes distance^2").  With W_g the PERMANOVA chain of group g under lambda:
+ *       c_g = (W_g / (double)n_g) / (double)n_g,
+ *       m_i = (the sequential sum from +0.0 over the positions j of the group g of i, ascending, j = i included, of
+ *              A2[i][j]) / (double)n_g,       z2_i = m_i - c_g,      z_i = z2_i > 0.0 ? sqrt(z2_i) : +0.0,
+ *       mean_g = (the sequential sum from +0.0 of z_i over the positions of g, ascending) / (double)n_g,  r_i = z_i - mean_g.
+ *     A position with z2_i < 0.0 is `clipped` (vegan sets those to zero with a warning).  z, mean and r are those of the
+ *     whole column whatever test uses them: a centroid does not depend on the other groups.
+ *   A test is a list of n positions of the column in ascending order with G groups: the whole column, or, pairwise, for
+ *     groups g < h < 32 the positions of g or h, renumbered 0 .. n - 1 (the keys come from those numbers), g before h.
+ *   Observed.  The edge-test rule's sums over the test's positions with x = z: mx, d, sxx, S_g of lambda, A(lambda);
+ *       eta2 = A(lambda) / sxx,  ssw = sxx - A(lambda),  f = (A(lambda) / (double)(G - 1)) / (ssw / (double)(n - G)), NA
+ *       unless ssw > 0.0.  The test is defined iff G >= 2, n - G >= 1 and sxx > 0.0.
+ *   Permutations of residuals (permutest.betadisper).  The edge-test rule's sums with x = r give eta_r(mu) = A_r(mu) / sxx_r;
+ *       at_least = #{p in 1 .. P : eta_r(mu^p) >= eta2},     p = (double)(1 + at_least) / (double)(P + 1).
+ *     F increases with eta at fixed (G, n): the textbook's F_p >= F_0 without a division.  If sxx_r is not > 0.0 there is
+ *     nothing to permute: at_least = P, p = 1, and every permuted statistic is written as eta2 (a tie).
+ *   Results.  out[M][1 + Q] of epik_amd_permdisp in the PERMANOVA slot layout (Q = 496 with pairwise, 0 without): used = n,
+ *     groups = G and clipped (the clipped positions of the test) are always written, 0 for a slot without a pair; an
+ *     undefined test has at_least = 0 and NA doubles.  stat[M][1 + Q][P + 1], where asked for: eta2 in slot 0, eta_r(mu^p) in
+ *     slot p, NA for an undefined test.  group_mean[M][32]: mean_g for g < G, NA beyond.  z[M][S]: z of the sample's
+ *     position, NA for a sample outside U_c.  Both for every column, defined or not.  Every cell of every output is written.
  *
  * An epik_amd_cohort is an object of its own, created for a placer's device, num_branches and keep_at_most (whole
  * databases only, not a k-mer-space shard) and num_samples >= 1; all zero at create() and after reset().
@@ -982,6 +1039,17 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *               synchronous; ssw and group_ss may be null.
  *   permanova_host  the rule on the host from mass[S][N], first[N], branch_length[N] and the labels, no device.
  *               permanova_kr_host: the same from a matrix kr[S][S] and totals[S] (T_s; only > 0 matters).
+ *   pcoa_device  takes d_kr as permanova_device does (so T_s is in the cohort's workspace: a cohort whose kr_device never
+ *               ran is refused) and K in [1, 64]; refused are a null cohort, d_kr, d_mu, d_coord or d_info.  Synchronises
+ *               the device, then the workspace of its own (allocated by the first call, kept until destroy(): about
+ *               24 * S^2 + 40 * S bytes, three S x S matrices and the vectors).  d_mu float64 [S], d_coord float64 [S][K]
+ *               and d_info one epik_amd_pcoa_info, all in device memory, every cell written.  It synchronises `stream`
+ *               once for the number of used samples and, beyond 64 of them (the eigensolver's global path;
+ *               EPIK_AMD_PCOA_LDS=0, read at the call, forces it), once per sweep for the sweep's rotation counter; the
+ *               results are enqueued on `stream`.  The cells and d_kr are not changed.
+ *               pcoa: runs kr_device itself (tree and lengths checked as there), the same into host memory, synchronous.
+ *   pcoa_host   the rule on the host from mass[S][N], first[N] and branch_length[N], no device.
+ *               pcoa_kr_host: the same from a matrix kr[S][S] and totals[S] (T_s; only > 0 matters).
  *   edgetest_device  checks the tree as correlation_device (its device and N) and labels (HOST [S][M], read before the call
  *               returns): refused are a null cohort, tree, labels or d_out, num_columns outside [1, 64], num_permutations
  *               outside [1, 999 999] and a label in [32, 0xffffffff).  It shares the workspace of correlation_device (the
@@ -995,6 +1063,18 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *               branch's vectors in LDS; beyond, or with EPIK_AMD_EDGETEST_LDS=0 (read at the call), in global memory:
  *               the same bits.   edgetest: the same into host memory, synchronous; stat and max may be null.
  *   edgetest_host  the rule on the host from mass[S][N], first[N] and the labels, no device; first[b] > b is refused.
+ *   permdisp_device  takes d_kr and labels as permanova_device does (a cohort whose kr_device never ran is refused): refused
+ *               are a null cohort, d_kr, labels, d_out, d_group_mean or d_z, num_columns outside [1, 64], num_permutations
+ *               outside [1, 999 999] and a label in [32, 0xffffffff).  Synchronises the device, then a workspace of its own,
+ *               grown where a call needs more and kept until destroy(): with Sp = S rounded up to 32 and lists = 32 with
+ *               pairwise, 1 without, about 37 Sp bytes a column, 13 Sp * lists bytes of the tests' lists and residuals,
+ *               1 024 Sp * lists bytes of a chunk of 1 024 labellings (a byte a position) and 64 bytes a test.  The columns
+ *               run one after another in it, the permutations in chunks of 1 024.  d_out is epik_amd_permdisp [M][1 + Q];
+ *               d_stat (may be null) float64 [M][1 + Q][P + 1]; d_group_mean float64 [M][32]; d_z float64 [M][S]; all in
+ *               device memory.  Once enqueued on `stream` it needs no readback.  The cells and d_kr are not changed.
+ *               permdisp: runs kr_device itself, the same into host memory, synchronous; stat may be null.
+ *   permdisp_host  the rule on the host from mass[S][N], first[N], branch_length[N] and the labels, no device.
+ *               permdisp_kr_host: the same from a matrix kr[S][S] and totals[S] (T_s; only > 0 matters).
  * cohort_reads / _strands / _frames / _mates: the profile_* twins with samples[n] (HOST uint32) beside the weights.
  */
 typedef struct epik_amd_cohort epik_amd_cohort;
@@ -1031,7 +1111,9 @@ typedef struct epik_amd_epca_info {
     double trace, scale;
 } epik_amd_epca_info; /* 32 bytes */
 #define EPIK_AMD_EPCA_MAX_COMPONENTS 64u
-#define EPIK_AMD_EPCA_MAX_SWEEPS 64u
+#define EPIK_AMD_JACOBI_MAX_SWEEPS 64u /* the cap of the Jacobi paragraph, whoever uses it */
+#define EPIK_AMD_EPCA_MAX_SWEEPS EPIK_AMD_JACOBI_MAX_SWEEPS
+#define EPIK_AMD_PCOA_MAX_SWEEPS EPIK_AMD_JACOBI_MAX_SWEEPS
 int epik_amd_cohort_epca_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_t num_components, void *d_mu,
                                 void *d_proj, void *d_edge, void *d_info, void *stream);
 int epik_amd_cohort_epca(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_t num_components, double *mu,
@@ -1127,6 +1209,22 @@ int epik_amd_cohort_permanova_host(const uint64_t *mass, uint32_t num_samples, u
 int epik_amd_cohort_permanova_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
                                       uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                       epik_amd_permanova *out, double *ssw, double *group_ss);
+typedef struct epik_amd_pcoa_info {
+    uint32_t used, components; /* L, and K' = min(K, L) */
+    uint32_t sweeps, converged;
+    double trace, scale;
+    double pos, neg;           /* the sums of the eigenvalues above 2^-40 * scale and below its negative */
+} epik_amd_pcoa_info; /* 48 bytes */
+#define EPIK_AMD_PCOA_MAX_COMPONENTS 64u
+int epik_amd_cohort_pcoa_device(epik_amd_cohort *cohort, const void *d_kr, uint32_t num_components, void *d_mu, void *d_coord,
+                                void *d_info, void *stream);
+int epik_amd_cohort_pcoa(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                         uint32_t num_components, double *mu, double *coord, epik_amd_pcoa_info *info);
+int epik_amd_cohort_pcoa_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                              const double *branch_length, uint32_t num_components, double *mu, double *coord,
+                              epik_amd_pcoa_info *info);
+int epik_amd_cohort_pcoa_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, uint32_t num_components,
+                                 double *mu, double *coord, epik_amd_pcoa_info *info);
 typedef struct epik_amd_edgetest_family {
     double eta2, stat, p, p_adj;        /* stat: F for the families 0 and 2, H for 1 and 3 */
     uint64_t at_least, max_at_least;    /* #{p >= 1 : eta(mu^p) >= eta2}, #{p >= 1 : Mmax_p >= eta2} */
@@ -1149,6 +1247,30 @@ int epik_amd_cohort_edgetest(epik_amd_cohort *cohort, const epik_amd_tree *tree,
 int epik_amd_cohort_edgetest_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                   const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
                                   epik_amd_edgetest *out, double *stat, double *max);
+typedef struct epik_amd_permdisp {
+    uint32_t used, groups; /* n and G of the test; 0, 0 for a slot without a pair */
+    uint32_t clipped, pad; /* the positions of the test with z2 < 0; pad is 0 */
+    uint64_t at_least;     /* #{p >= 1 : eta_r(mu^p) >= eta2} */
+    double eta2, f, p;
+} epik_amd_permdisp; /* 48 bytes */
+#define EPIK_AMD_PERMDISP_MAX_COLUMNS 64u
+#define EPIK_AMD_PERMDISP_MAX_GROUPS 32u
+#define EPIK_AMD_PERMDISP_PAIR_SLOTS 496u
+#define EPIK_AMD_PERMDISP_MAX_PERMUTATIONS 999999u
+#define EPIK_AMD_PERMDISP_MISSING 0xffffffffu
+int epik_amd_cohort_permdisp_device(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, uint32_t num_columns,
+                                    uint32_t num_permutations, uint64_t seed, int pairwise, void *d_out, void *d_stat,
+                                    void *d_group_mean, void *d_z, void *stream);
+int epik_amd_cohort_permdisp(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                             const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
+                             int pairwise, epik_amd_permdisp *out, double *stat, double *group_mean, double *z);
+int epik_amd_cohort_permdisp_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                  const double *branch_length, const uint32_t *labels, uint32_t num_columns,
+                                  uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permdisp *out, double *stat,
+                                  double *group_mean, double *z);
+int epik_amd_cohort_permdisp_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
+                                     uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
+                                     epik_amd_permdisp *out, double *stat, double *group_mean, double *z);
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n);
 int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
