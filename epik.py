@@ -37,6 +37,9 @@ cohort_permdisp_<list>.tsv; --cohort-permdisp-permutations P (default 999), --co
 --cohort-permdisp-pairwise.
 --cohort-pcoa, with --cohort: the principal coordinates of the samples over the KR distances, all eigenvalues with the
 negative ones of a distance that is not Euclidean, cohort_pcoa_<list>.tsv; --cohort-pcoa-components K axes (default 5).
+--cohort-unifrac LIST, with --cohort: the UniFrac distances between every two samples, LIST a comma-separated subset of
+unweighted, weighted, generalized, or all; cohort_unifrac_<metric>_<list>.tsv each.  --cohort-distance NAME (kr, unweighted,
+weighted, generalized): the distance --cohort-permanova, --cohort-pcoa and --cohort-permdisp run over (default kr).
 """
 from __future__ import annotations
 
@@ -52,6 +55,8 @@ HERE = os.path.dirname(os.path.realpath(__file__))
 DRIVERS = {"nucl": "epik-dna", "amino": "epik-aa"}
 
 # (flags, click keyword arguments) -- one row per option of `place`
+COHORT_DISTANCES = ("kr", "unweighted", "weighted", "generalized")  # EPIK_AMD_DISTANCE_* by number
+
 PLACE_OPTIONS = [
     (("-i", "--database"), dict(required=True, type=click.Path(exists=True, dir_okay=False),
                                 help="Phylo-k-mer database to place against.")),
@@ -168,6 +173,13 @@ PLACE_OPTIONS = [
                                                  "eigenvalues, the negative ones included, and every sample's coordinates).")),
     (("--cohort-pcoa-components",), dict(type=click.IntRange(1, 64), default=None,
                                          help="With --cohort-pcoa: the number of axes, in [1, 64] [default: 5].")),
+    (("--cohort-unifrac",), dict(type=str, default=None,
+                                 help="With --cohort: also compute UniFrac distances between every two samples on the device: a "
+                                      "comma-separated subset of unweighted, weighted, generalized, or all; writes "
+                                      "cohort_unifrac_<metric>_<list>.tsv each.  The tree is rooted where the database's is.")),
+    (("--cohort-distance",), dict(type=click.Choice(COHORT_DISTANCES), default=None,
+                                  help="With --cohort-permanova, --cohort-pcoa or --cohort-permdisp: the distance they run over "
+                                       "[default: kr]; another one is named at the end of the first line of their files.")),
     (("--taxonomy",), dict(type=click.Path(), default=None,
                            help="A taxonomy file, one leaf_label<TAB>A;B;C line per reference leaf: also write taxa_<input>.tsv "
                                 "(per taxon the reads assigned to it and the mass placed in it, with clade sums) or, with "
@@ -200,7 +212,7 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                    cohort_permanova_permutations=None, cohort_permanova_seed=None, cohort_permanova_pairwise=False,
                    cohort_edge_test=None, cohort_edge_test_permutations=None, cohort_edge_test_seed=None,
                    cohort_pcoa=False, cohort_pcoa_components=None, cohort_permdisp=None, cohort_permdisp_permutations=None,
-                   cohort_permdisp_seed=None, cohort_permdisp_pairwise=False):
+                   cohort_permdisp_seed=None, cohort_permdisp_pairwise=False, cohort_unifrac=None, cohort_distance=None):
     if taxonomy_mass is not None and taxonomy is None:
         raise click.UsageError("--taxonomy-mass needs --taxonomy")
     if taxonomy_per_read and taxonomy is None:
@@ -264,6 +276,22 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         raise click.UsageError("--cohort-pcoa needs --cohort")
     if cohort_pcoa_components is not None and not cohort_pcoa:
         raise click.UsageError("--cohort-pcoa-components needs --cohort-pcoa")
+    if cohort_unifrac is not None:
+        if not cohort:
+            raise click.UsageError("--cohort-unifrac needs --cohort")
+        names = str(cohort_unifrac).split(",")
+        for i, name in enumerate(names):
+            if str(cohort_unifrac) == "all":
+                break
+            if name not in COHORT_DISTANCES[1:]:
+                raise click.UsageError(f"--cohort-unifrac: '{name}' is no UniFrac distance (unweighted, weighted, generalized, or all)")
+            if name in names[:i]:
+                raise click.UsageError(f"--cohort-unifrac: '{name}' is given twice")
+    if cohort_distance is not None:
+        if cohort_distance not in COHORT_DISTANCES:
+            raise click.UsageError(f"--cohort-distance must be kr, unweighted, weighted or generalized, not '{cohort_distance}'")
+        if cohort_permanova is None and not cohort_pcoa and cohort_permdisp is None:
+            raise click.UsageError("--cohort-distance needs --cohort-permanova, --cohort-pcoa or --cohort-permdisp")
     if cohort:
         for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
                             ("--assign", assign), ("--db-shard > 1", db_shard != 1)):
@@ -341,6 +369,10 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--cohort-pcoa"]
         if cohort_pcoa_components is not None:
             argv += ["--cohort-pcoa-components", str(int(cohort_pcoa_components))]
+    if cohort_unifrac is not None:
+        argv += ["--cohort-unifrac", str(cohort_unifrac)]
+    if cohort_distance is not None:
+        argv += ["--cohort-distance", str(cohort_distance)]
     if taxonomy is not None:
         argv += ["--taxonomy", str(taxonomy)]
         if taxonomy_mass is not None:

@@ -163,6 +163,9 @@ EXPORTS = (
     "epik_amd_cohort_kr_device",
     "epik_amd_cohort_kr",
     "epik_amd_cohort_kr_host",
+    "epik_amd_cohort_unifrac_device",
+    "epik_amd_cohort_unifrac",
+    "epik_amd_cohort_unifrac_host",
     "epik_amd_cohort_squash_device",
     "epik_amd_cohort_squash",
     "epik_amd_cohort_squash_host",
@@ -187,10 +190,14 @@ EXPORTS = (
     "epik_amd_cohort_permanova_device",
     "epik_amd_cohort_permanova",
     "epik_amd_cohort_permanova_host",
+    "epik_amd_cohort_permanova_metric",
+    "epik_amd_cohort_permanova_metric_host",
     "epik_amd_cohort_permanova_kr_host",
     "epik_amd_cohort_pcoa_device",
     "epik_amd_cohort_pcoa",
     "epik_amd_cohort_pcoa_host",
+    "epik_amd_cohort_pcoa_metric",
+    "epik_amd_cohort_pcoa_metric_host",
     "epik_amd_cohort_pcoa_kr_host",
     "epik_amd_cohort_edgetest_device",
     "epik_amd_cohort_edgetest",
@@ -198,6 +205,8 @@ EXPORTS = (
     "epik_amd_cohort_permdisp_device",
     "epik_amd_cohort_permdisp",
     "epik_amd_cohort_permdisp_host",
+    "epik_amd_cohort_permdisp_metric",
+    "epik_amd_cohort_permdisp_metric_host",
     "epik_amd_cohort_permdisp_kr_host",
     "epik_amd_placer_cohort_reads",
     "epik_amd_placer_cohort_strands",
@@ -523,6 +532,12 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_kr.argtypes = [vp, vp, vp, vp]
     lib.epik_amd_cohort_kr_host.restype = i32
     lib.epik_amd_cohort_kr_host.argtypes = [vp, u32, u32, vp, vp, vp]
+    lib.epik_amd_cohort_unifrac_device.restype = i32
+    lib.epik_amd_cohort_unifrac_device.argtypes = [vp, vp, vp, u32, vp, vp]
+    lib.epik_amd_cohort_unifrac.restype = i32
+    lib.epik_amd_cohort_unifrac.argtypes = [vp, vp, vp, u32, vp]
+    lib.epik_amd_cohort_unifrac_host.restype = i32
+    lib.epik_amd_cohort_unifrac_host.argtypes = [vp, u32, u32, vp, vp, u32, vp]
     lib.epik_amd_cohort_squash_device.restype = i32
     lib.epik_amd_cohort_squash_device.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.epik_amd_cohort_squash.restype = i32
@@ -571,6 +586,10 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_permanova.argtypes = [vp, vp, vp, vp, u32, u32, u64, i32, vp, vp, vp]
     lib.epik_amd_cohort_permanova_host.restype = i32
     lib.epik_amd_cohort_permanova_host.argtypes = [vp, u32, u32, vp, vp, vp, u32, u32, u64, i32, vp, vp, vp]
+    lib.epik_amd_cohort_permanova_metric.restype = i32
+    lib.epik_amd_cohort_permanova_metric.argtypes = [vp, vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp]
+    lib.epik_amd_cohort_permanova_metric_host.restype = i32
+    lib.epik_amd_cohort_permanova_metric_host.argtypes = [vp, u32, u32, vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp]
     lib.epik_amd_cohort_permanova_kr_host.restype = i32
     lib.epik_amd_cohort_permanova_kr_host.argtypes = [vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp]
     lib.epik_amd_cohort_pcoa_device.restype = i32
@@ -579,6 +598,10 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_pcoa.argtypes = [vp, vp, vp, u32, vp, vp, vp]
     lib.epik_amd_cohort_pcoa_host.restype = i32
     lib.epik_amd_cohort_pcoa_host.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp, vp]
+    lib.epik_amd_cohort_pcoa_metric.restype = i32
+    lib.epik_amd_cohort_pcoa_metric.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp]
+    lib.epik_amd_cohort_pcoa_metric_host.restype = i32
+    lib.epik_amd_cohort_pcoa_metric_host.argtypes = [vp, u32, u32, vp, vp, u32, u32, vp, vp, vp]
     lib.epik_amd_cohort_pcoa_kr_host.restype = i32
     lib.epik_amd_cohort_pcoa_kr_host.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     lib.epik_amd_cohort_permdisp_device.restype = i32
@@ -587,6 +610,10 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_permdisp.argtypes = [vp, vp, vp, vp, u32, u32, u64, i32, vp, vp, vp, vp]
     lib.epik_amd_cohort_permdisp_host.restype = i32
     lib.epik_amd_cohort_permdisp_host.argtypes = [vp, u32, u32, vp, vp, vp, u32, u32, u64, i32, vp, vp, vp, vp]
+    lib.epik_amd_cohort_permdisp_metric.restype = i32
+    lib.epik_amd_cohort_permdisp_metric.argtypes = [vp, vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp, vp]
+    lib.epik_amd_cohort_permdisp_metric_host.restype = i32
+    lib.epik_amd_cohort_permdisp_metric_host.argtypes = [vp, u32, u32, vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp, vp]
     lib.epik_amd_cohort_permdisp_kr_host.restype = i32
     lib.epik_amd_cohort_permdisp_kr_host.argtypes = [vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp, vp]
     lib.epik_amd_cohort_edgetest_device.restype = i32

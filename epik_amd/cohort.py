@@ -42,6 +42,11 @@ output file.
 Principal coordinates of the samples over the KR distances (the header's ninth rule): `Cohort.pcoa` / `pcoa_device` on the
 device, `pcoa_host` and `pcoa_kr_host` on the host, each giving a `Pcoa` with all eigenvalues, the negative ones included;
 `format_pcoa_tsv` and `read_pcoa_tsv` are the file of --cohort-pcoa.
+
+The UniFrac distances between every two samples (the header's UniFrac rule; `DISTANCES` names them): `Cohort.unifrac` /
+`unifrac_device` on the device, `unifrac_host` on the host; `format_unifrac_tsv` and `read_unifrac_tsv` are the files of
+--cohort-unifrac.  PERMANOVA, PERMDISP and the principal coordinates take `metric=` (a name of `DISTANCES` or its number,
+KR by default): the distance they run over, which --cohort-distance chooses and their files' first line then names.
 """
 from __future__ import annotations
 
@@ -87,6 +92,34 @@ def kr_host(mass, first, branch_length) -> np.ndarray:
         raise ValueError(f"first and branch_length must hold one value per branch ({n})")
     out = np.full((s, s), np.nan, dtype=np.float64)
     capi.check(lib.epik_amd_cohort_kr_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, out.ctypes.data))
+    return out
+
+
+#: the distances by their number (EPIK_AMD_DISTANCE_*): KR and the three UniFrac distances
+DISTANCES = ("kr", "unweighted", "weighted", "generalized")
+
+
+def metric_id(metric) -> int:
+    """EPIK_AMD_DISTANCE_* of a name of `DISTANCES`; a number is passed on as it is (the library refuses a bad one)."""
+    if isinstance(metric, str):
+        if metric not in DISTANCES:
+            raise ValueError(f"unknown distance {metric!r} (one of {', '.join(DISTANCES)})")
+        return DISTANCES.index(metric)
+    metric = int(metric)
+    if not 0 <= metric <= 0xffffffff:
+        raise ValueError(f"metric = {metric} is no uint32")
+    return metric
+
+
+def unifrac_host(mass, first, branch_length, metric) -> np.ndarray:
+    """The UniFrac distance `metric` of the rule for mass[S][N] on the host (`epik_amd_cohort_unifrac_host`): float64
+    [S][S]."""
+    lib = capi.load()
+    mass, first, length = _cells_and_tree(mass, first, branch_length)
+    s, n = mass.shape
+    out = np.full((s, s), np.nan, dtype=np.float64)
+    capi.check(lib.epik_amd_cohort_unifrac_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, metric_id(metric),
+                                                out.ctypes.data))
     return out
 
 
@@ -222,15 +255,16 @@ def pcoa_kr_host(kr, totals, num_components: int = 5) -> Pcoa:
     return out
 
 
-def pcoa_host(mass, first, branch_length, num_components: int = 5) -> Pcoa:
-    """The principal coordinates of the rule for mass[S][N] on the host (`epik_amd_cohort_pcoa_host`)."""
+def pcoa_host(mass, first, branch_length, num_components: int = 5, metric="kr") -> Pcoa:
+    """The principal coordinates of the rule for mass[S][N] over the distance `metric` on the host
+    (`epik_amd_cohort_pcoa_metric_host`)."""
     lib = capi.load()
     mass, first, length = _cells_and_tree(mass, first, branch_length)
     s, n = mass.shape
     k = _components(num_components)
     out = _pcoa_buffers(s, k)
-    capi.check(lib.epik_amd_cohort_pcoa_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, k, out.mu.ctypes.data,
-                                             out.coord.ctypes.data, out.info.ctypes.data))
+    capi.check(lib.epik_amd_cohort_pcoa_metric_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, metric_id(metric), k,
+                                                    out.mu.ctypes.data, out.coord.ctypes.data, out.info.ctypes.data))
     out.info = out.info[0]
     return out
 
@@ -402,17 +436,18 @@ def permanova_kr_host(kr, totals, labels, permutations: int = 999, seed: int = 1
 
 
 def permanova_host(mass, first, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
-                   with_ssw: bool = True) -> Permanova:
-    """PERMANOVA of the rule for mass[S][N] and labels[S][M] (0xffffffff: missing) on the host
-    (`epik_amd_cohort_permanova_host`)."""
+                   with_ssw: bool = True, metric="kr") -> Permanova:
+    """PERMANOVA of the rule for mass[S][N] and labels[S][M] (0xffffffff: missing) over the distance `metric` on the host
+    (`epik_amd_cohort_permanova_metric_host`)."""
     lib = capi.load()
     mass, first, length = _cells_and_tree(mass, first, branch_length)
     s, n = mass.shape
     labels = _labels(labels, s)
     records, ssw, group_ss = _permanova_buffers(labels.shape[1], permutations, pairwise, with_ssw)
-    capi.check(lib.epik_amd_cohort_permanova_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, labels.ctypes.data,
-                                                  labels.shape[1], int(permutations), int(seed), int(bool(pairwise)),
-                                                  records.ctypes.data, ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data))
+    capi.check(lib.epik_amd_cohort_permanova_metric_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data,
+                                                         metric_id(metric), labels.ctypes.data, labels.shape[1], int(permutations),
+                                                         int(seed), int(bool(pairwise)), records.ctypes.data,
+                                                         ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data))
     return Permanova(records, ssw, group_ss)
 
 
@@ -455,18 +490,19 @@ def permdisp_kr_host(kr, totals, labels, permutations: int = 999, seed: int = 1,
 
 
 def permdisp_host(mass, first, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
-                  with_stat: bool = True) -> Permdisp:
-    """PERMDISP of the rule for mass[S][N] and labels[S][M] (0xffffffff: missing) on the host
-    (`epik_amd_cohort_permdisp_host`)."""
+                  with_stat: bool = True, metric="kr") -> Permdisp:
+    """PERMDISP of the rule for mass[S][N] and labels[S][M] (0xffffffff: missing) over the distance `metric` on the host
+    (`epik_amd_cohort_permdisp_metric_host`)."""
     lib = capi.load()
     mass, first, length = _cells_and_tree(mass, first, branch_length)
     s, n = mass.shape
     labels = _labels(labels, s)
     out = _permdisp_buffers(labels.shape[1], s, permutations, pairwise, with_stat)
-    capi.check(lib.epik_amd_cohort_permdisp_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, labels.ctypes.data,
-                                                 labels.shape[1], int(permutations), int(seed), int(bool(pairwise)),
-                                                 out.records.ctypes.data, out.stat.ctypes.data if with_stat else None,
-                                                 out.group_mean.ctypes.data, out.z.ctypes.data))
+    capi.check(lib.epik_amd_cohort_permdisp_metric_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data,
+                                                        metric_id(metric), labels.ctypes.data, labels.shape[1], int(permutations),
+                                                        int(seed), int(bool(pairwise)), out.records.ctypes.data,
+                                                        out.stat.ctypes.data if with_stat else None, out.group_mean.ctypes.data,
+                                                        out.z.ctypes.data))
     return out
 
 
@@ -618,6 +654,21 @@ class Cohort:
         capi.check(self._lib.epik_amd_cohort_kr(self._handle, tree._handle, length.ctypes.data, out.ctypes.data))
         return out
 
+    def unifrac_device(self, tree, branch_length, metric, d_out: int, stream: int = 0) -> None:
+        """The UniFrac distance `metric` into d_out, float64 [S][S] in device memory, every cell written; asynchronous on
+        `stream` once the lengths (host) are copied (`epik_amd_cohort_unifrac_device`)."""
+        length = self._lengths(tree, branch_length)
+        capi.check(self._lib.epik_amd_cohort_unifrac_device(self._handle, tree._handle, length.ctypes.data, metric_id(metric),
+                                                            d_out or None, stream or None))
+
+    def unifrac(self, tree, branch_length, metric) -> np.ndarray:
+        """The UniFrac distance `metric` for all pairs, float64 [S][S] (`epik_amd_cohort_unifrac`)."""
+        length = self._lengths(tree, branch_length)
+        out = np.full((self.num_samples, self.num_samples), np.nan, dtype=np.float64)
+        capi.check(self._lib.epik_amd_cohort_unifrac(self._handle, tree._handle, length.ctypes.data, metric_id(metric),
+                                                     out.ctypes.data))
+        return out
+
     def squash_device(self, tree, branch_length, d_merges: int, d_num_merges: int, stream: int = 0) -> None:
         """The squash clustering into device memory: d_merges `capi.SQUASH_MERGE` [S - 1], every record written, and
         d_num_merges one uint32; asynchronous on `stream` once the lengths (host) are copied, all steps enqueued
@@ -755,16 +806,16 @@ class Cohort:
                                                               d_ssw or None, d_group_ss or None, stream or None))
 
     def permanova(self, tree, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
-                  with_ssw: bool = False) -> Permanova:
-        """PERMANOVA of the samples' groups in every column of labels[S][M] over their KR distances
-        (`epik_amd_cohort_permanova`)."""
+                  with_ssw: bool = False, metric="kr") -> Permanova:
+        """PERMANOVA of the samples' groups in every column of labels[S][M] over their distances `metric`, KR by default
+        (`epik_amd_cohort_permanova_metric`)."""
         length = self._lengths(tree, branch_length)
         labels = _labels(labels, self.num_samples)
         records, ssw, group_ss = _permanova_buffers(labels.shape[1], permutations, pairwise, with_ssw)
-        capi.check(self._lib.epik_amd_cohort_permanova(self._handle, tree._handle, length.ctypes.data, labels.ctypes.data,
-                                                       labels.shape[1], int(permutations), int(seed), int(bool(pairwise)),
-                                                       records.ctypes.data, ssw.ctypes.data if with_ssw else None,
-                                                       group_ss.ctypes.data))
+        capi.check(self._lib.epik_amd_cohort_permanova_metric(self._handle, tree._handle, length.ctypes.data, metric_id(metric),
+                                                              labels.ctypes.data, labels.shape[1], int(permutations), int(seed),
+                                                              int(bool(pairwise)), records.ctypes.data,
+                                                              ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data))
         return Permanova(records, ssw, group_ss)
 
     def permdisp_device(self, d_kr: int, labels, permutations: int, seed: int, pairwise: bool, d_out: int, d_group_mean: int,
@@ -779,16 +830,17 @@ class Cohort:
                                                              d_stat or None, d_group_mean or None, d_z or None, stream or None))
 
     def permdisp(self, tree, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
-                 with_stat: bool = False) -> Permdisp:
+                 with_stat: bool = False, metric="kr") -> Permdisp:
         """PERMDISP of the samples' groups in every column of labels[S][M]: do they differ in their distances to the group
-        centroids over the KR distances (`epik_amd_cohort_permdisp`)."""
+        centroids over the distances `metric`, KR by default (`epik_amd_cohort_permdisp_metric`)."""
         length = self._lengths(tree, branch_length)
         labels = _labels(labels, self.num_samples)
         out = _permdisp_buffers(labels.shape[1], self.num_samples, permutations, pairwise, with_stat)
-        capi.check(self._lib.epik_amd_cohort_permdisp(self._handle, tree._handle, length.ctypes.data, labels.ctypes.data,
-                                                      labels.shape[1], int(permutations), int(seed), int(bool(pairwise)),
-                                                      out.records.ctypes.data, out.stat.ctypes.data if with_stat else None,
-                                                      out.group_mean.ctypes.data, out.z.ctypes.data))
+        capi.check(self._lib.epik_amd_cohort_permdisp_metric(self._handle, tree._handle, length.ctypes.data, metric_id(metric),
+                                                             labels.ctypes.data, labels.shape[1], int(permutations), int(seed),
+                                                             int(bool(pairwise)), out.records.ctypes.data,
+                                                             out.stat.ctypes.data if with_stat else None, out.group_mean.ctypes.data,
+                                                             out.z.ctypes.data))
         return out
 
     def pcoa_device(self, d_kr: int, num_components: int, d_mu: int, d_coord: int, d_info: int, stream: int = 0) -> None:
@@ -799,13 +851,14 @@ class Cohort:
         capi.check(self._lib.epik_amd_cohort_pcoa_device(self._handle, d_kr or None, _components(num_components), d_mu or None,
                                                          d_coord or None, d_info or None, stream or None))
 
-    def pcoa(self, tree, branch_length, num_components: int = 5) -> Pcoa:
-        """The principal coordinates of the samples over their KR distances, a `Pcoa` (`epik_amd_cohort_pcoa`)."""
+    def pcoa(self, tree, branch_length, num_components: int = 5, metric="kr") -> Pcoa:
+        """The principal coordinates of the samples over their distances `metric`, KR by default, a `Pcoa`
+        (`epik_amd_cohort_pcoa_metric`)."""
         length = self._lengths(tree, branch_length)
         k = _components(num_components)
         out = _pcoa_buffers(self.num_samples, k)
-        capi.check(self._lib.epik_amd_cohort_pcoa(self._handle, tree._handle, length.ctypes.data, k, out.mu.ctypes.data,
-                                                  out.coord.ctypes.data, out.info.ctypes.data))
+        capi.check(self._lib.epik_amd_cohort_pcoa_metric(self._handle, tree._handle, length.ctypes.data, metric_id(metric), k,
+                                                         out.mu.ctypes.data, out.coord.ctypes.data, out.info.ctypes.data))
         out.info = out.info[0]
         return out
 
@@ -861,6 +914,22 @@ def format_kr_tsv(names, kr) -> str:
     for s, name in enumerate(names):
         lines.append("\t".join([name, *("%.17g" % float(x) for x in kr[s])]))
     return "\n".join(lines) + "\n"
+
+
+def format_unifrac_tsv(names, matrix) -> str:
+    """cohort_unifrac_<metric>_<list>.tsv: the square layout of `format_kr_tsv`, doubles as %.17g."""
+    return format_kr_tsv(names, matrix)
+
+
+def _distance_field(distance) -> str:
+    """What the first line of a PCoA, PERMANOVA or PERMDISP file ends in: nothing over KR, else <TAB>distance=NAME."""
+    name = DISTANCES[metric_id(distance)] if not isinstance(distance, str) else distance
+    if name not in DISTANCES:
+        raise ValueError(f"unknown distance {name!r} (one of {', '.join(DISTANCES)})")
+    return "" if name == "kr" else f"\tdistance={name}"
+
+
+_DISTANCE_FIELD = r"(?:\tdistance=(unweighted|weighted|generalized))?"
 
 
 def _live_mask(names, live) -> np.ndarray:
@@ -1017,18 +1086,18 @@ def read_epca_edges_tsv(path: str):
 
 # ---- the files of --cohort-kmeans --------------------------------------------------------------------------------------
 # ---- the file of --cohort-pcoa ------------------------------------------------------------------------------------------
-def format_pcoa_tsv(names, totals, pcoa: Pcoa) -> str:
+def format_pcoa_tsv(names, totals, pcoa: Pcoa, distance="kr") -> str:
     """cohort_pcoa_<list>.tsv (`totals[s]`: T_s, only > 0 matters): the first line with negative = -neg / pos, a `# unused`
     line per sample without mass, a `# eigenvalue` line for each of the L eigenvalues (k from 1; mu, fraction = mu / pos or
     0; real|null|negative), the column names, then per used sample, in list order, its name and its coordinates; doubles
-    as %.17g."""
+    as %.17g.  Over a `distance` other than KR the first line ends in <TAB>distance=NAME."""
     info = pcoa.info
     is_used = np.asarray(totals) != 0
     used, kc = int(info["used"]), int(info["components"])
     if len(is_used) != len(names) or int(is_used.sum()) != used:
         raise ValueError("the totals do not fit the number of used samples")
     lines = [f"# epik_amd pcoa v1  samples={len(names)} used={used} components={kc} sweeps={int(info['sweeps'])} "
-             f"converged={int(info['converged'])} negative={'%.17g' % pcoa.negative}"]
+             f"converged={int(info['converged'])} negative={'%.17g' % pcoa.negative}" + _distance_field(distance)]
     lines += [f"# unused\t{name}" for name, u in zip(names, is_used) if not u]
     pos = float(info["pos"])
     for k, kind in enumerate(pcoa.kinds()):
@@ -1043,14 +1112,17 @@ def format_pcoa_tsv(names, totals, pcoa: Pcoa) -> str:
 
 def read_pcoa_tsv(path: str):
     """(names, coord, info): the used samples' names, float64 [L][K'], and {"samples", "used", "components", "sweeps",
-    "converged", "negative", "unused": names, "mu", "fraction": float64 [L], "kind": the classes}."""
+    "converged", "negative", "unused": names, "mu", "fraction": float64 [L], "kind": the classes; and "distance", a name of
+    `DISTANCES`, only where the first line has the field: a file over KR has none}."""
     with open(path, newline="") as fh:
         head = re.fullmatch(r"# epik_amd pcoa v1  samples=(\d+) used=(\d+) components=(\d+) sweeps=(\d+) converged=([01]) "
-                            r"negative=(\S+)", fh.readline().rstrip("\n"))
+                            r"negative=([^\s]+)" + _DISTANCE_FIELD, fh.readline().rstrip("\n"))
         if not head:
             raise ValueError(f"{path}: not a cohort pcoa file")
         info = dict(zip(("samples", "used", "components", "sweeps", "converged"), map(int, head.groups()[:5])))
         info["negative"] = float(head.group(6))
+        if head.group(7):                     # (a file over KR has no such field, and its info no such key)
+            info["distance"] = head.group(7)
         unused, eig, line = [], [], fh.readline().rstrip("\n")
         while line.startswith("# "):
             fields = line.split("\t")
@@ -1316,11 +1388,11 @@ def _na_or_float(text: str) -> float:
     return float(np.uint64(capi.NA_BITS).view(np.float64)) if text == "NA" else float(text)
 
 
-def _used_head(what: str, names, totals, more: str = ""):
+def _used_head(what: str, names, totals, more: str = "", distance="kr"):
     totals = [int(x) for x in totals]
     if len(totals) != len(names):
         raise ValueError("one total mass per sample")
-    lines = [f"# epik_amd {what} v1  samples={len(names)} used={sum(t != 0 for t in totals)}{more}"]
+    lines = [f"# epik_amd {what} v1  samples={len(names)} used={sum(t != 0 for t in totals)}{more}" + _distance_field(distance)]
     return lines + [f"# unused\t{name}" for name, t in zip(names, totals) if t == 0]
 
 
@@ -1497,7 +1569,7 @@ def groups_of(labels, totals):
 
 
 def format_permanova_tsv(names, totals, columns, label_names, labels, permutations: int, seed: int, pairwise: bool, records,
-                         group_ss) -> str:
+                         group_ss, distance="kr") -> str:
     """cohort_permanova_<list>.tsv: the first line, a `# unused` line per sample without mass, a `# column` line per column
     (its used samples and groups), a `# group` line per group (label, size, W_g / n_g of the observed labelling), the column
     names, then per column the whole test (a = b = *) and, with pairwise, its pairs in slot order; ss_among is
@@ -1507,7 +1579,8 @@ def format_permanova_tsv(names, totals, columns, label_names, labels, permutatio
     if records.dtype != capi.PERMANOVA or records.shape != (len(columns), slots) or labels.shape != (len(names), len(columns)):
         raise ValueError("records must be capi.PERMANOVA [num_columns][1 + Q], labels [num_samples][num_columns]")
     lines = _used_head("permanova", names, totals,
-                       f" columns={len(columns)} permutations={int(permutations)} seed={int(seed)} pairwise={int(bool(pairwise))}")
+                       f" columns={len(columns)} permutations={int(permutations)} seed={int(seed)} pairwise={int(bool(pairwise))}",
+                       distance)
     groups = groups_of(labels, totals)
     lines += [f"# column\t{c}\t{name}\t{int(records['used'][c, 0])}\t{int(records['groups'][c, 0])}" for c, name in enumerate(columns)]
     for c, (order, sizes) in enumerate(groups):
@@ -1533,17 +1606,19 @@ PERMDISP_HEADER = "column\ta\tb\tused\tgroups\tclipped\teta2\tf\tat_least\tp"
 
 
 def format_permdisp_tsv(names, totals, columns, label_names, labels, permutations: int, seed: int, pairwise: bool, records,
-                        group_mean, z) -> str:
+                        group_mean, z, distance="kr") -> str:
     """cohort_permdisp_<list>.tsv: the first line, the `# unused`, `# column` and `# group` lines as cohort_permanova's (a
     group's last field is its mean distance to centroid), the column names, per column the whole test (a = b = *) and, with
     pairwise, its pairs in slot order; then `# distances`, the column names column name label distance and, per column, a
-    line per sample with mass and a label, in list order; doubles as %.17g, NA as NA."""
+    line per sample with mass and a label, in list order; doubles as %.17g, NA as NA.  Over a `distance` other than KR the
+    first line ends in <TAB>distance=NAME."""
     records, labels = np.asarray(records), np.asarray(labels)
     slots = 1 + (capi.PERMDISP_PAIR_SLOTS if pairwise else 0)
     if records.dtype != capi.PERMDISP or records.shape != (len(columns), slots) or labels.shape != (len(names), len(columns)):
         raise ValueError("records must be capi.PERMDISP [num_columns][1 + Q], labels [num_samples][num_columns]")
     lines = _used_head("permdisp", names, totals,
-                       f" columns={len(columns)} permutations={int(permutations)} seed={int(seed)} pairwise={int(bool(pairwise))}")
+                       f" columns={len(columns)} permutations={int(permutations)} seed={int(seed)} pairwise={int(bool(pairwise))}",
+                       distance)
     groups = groups_of(labels, totals)
     lines += [f"# column\t{c}\t{name}\t{int(records['used'][c, 0])}\t{int(records['groups'][c, 0])}" for c, name in enumerate(columns)]
     for c, (order, sizes) in enumerate(groups):
@@ -1571,11 +1646,15 @@ def format_permdisp_tsv(names, totals, columns, label_names, labels, permutation
 
 def read_permanova_tsv(path: str):
     """(columns, rows [(column, a, b, record `capi.PERMANOVA`, ss_among)], groups [(c, g, label, n, ss_within_g)],
-    info {"samples", "used", "unused", "permutations", "seed", "pairwise", "column_used", "column_groups"})"""
+    info {"samples", "used", "unused", "permutations", "seed", "pairwise", "column_used", "column_groups"; and "distance", a
+    name of `DISTANCES`, only where the first line has the field: a file over KR has none})"""
     with open(path, newline="") as fh:
-        head, info, line = _read_used_head(fh, "permanova", r" columns=(\d+) permutations=(\d+) seed=(\d+) pairwise=([01])", path)
+        head, info, line = _read_used_head(fh, "permanova", r" columns=(\d+) permutations=(\d+) seed=(\d+) pairwise=([01])"
+                                           + _DISTANCE_FIELD, path)
         info.update(permutations=int(head.group(4)), seed=int(head.group(5)), pairwise=head.group(6) == "1", column_used=[],
                     column_groups=[])
+        if head.group(7):                     # (a file over KR has no such field, and its info no such key)
+            info["distance"] = head.group(7)
         columns, groups = [], []
         while line.startswith("# column\t"):
             _, c, name, used, count = line.split("\t")
@@ -1600,6 +1679,49 @@ def read_permanova_tsv(path: str):
                 record[f] = _na_or_float(text)
             rows.append((r[0], r[1], r[2], record, _na_or_float(r[6])))
     return columns, rows, groups, info
+
+
+def read_permdisp_tsv(path: str):
+    """(columns, rows [(column, a, b, record `capi.PERMDISP`)], groups [(c, g, label, n, mean_distance)], distances [(column,
+    name, label, distance)], info as `read_permanova_tsv`'s)"""
+    with open(path, newline="") as fh:
+        head, info, line = _read_used_head(fh, "permdisp", r" columns=(\d+) permutations=(\d+) seed=(\d+) pairwise=([01])"
+                                           + _DISTANCE_FIELD, path)
+        info.update(permutations=int(head.group(4)), seed=int(head.group(5)), pairwise=head.group(6) == "1", column_used=[],
+                    column_groups=[])
+        if head.group(7):                     # (a file over KR has no such field, and its info no such key)
+            info["distance"] = head.group(7)
+        columns, groups = [], []
+        while line.startswith("# column\t"):
+            _, c, name, used, count = line.split("\t")
+            if int(c) != len(columns):
+                raise ValueError(f"{path}: the columns are not numbered in order")
+            columns.append(name), info["column_used"].append(int(used)), info["column_groups"].append(int(count))
+            line = fh.readline().rstrip("\n")
+        while line.startswith("# group\t"):
+            _, c, g, label, n, mean = line.split("\t")
+            groups.append((int(c), int(g), label, int(n), _na_or_float(mean)))
+            line = fh.readline().rstrip("\n")
+        if line != PERMDISP_HEADER or len(columns) != int(head.group(3)):
+            raise ValueError(f"{path}: not a cohort permdisp file")
+        rows, distances, tail = [], [], False
+        for ln in fh:
+            r = ln.rstrip("\n").split("\t")
+            if r == ["# distances"]:
+                tail = True
+                if fh.readline().rstrip("\n") != "column\tname\tlabel\tdistance":
+                    raise ValueError(f"{path}: not a cohort permdisp file")
+            elif tail and len(r) == 4 and r[0] in columns:
+                distances.append((r[0], r[1], r[2], _na_or_float(r[3])))
+            elif not tail and len(r) == 10 and r[0] in columns:
+                record = np.zeros((), dtype=capi.PERMDISP)
+                record["used"], record["groups"], record["clipped"], record["at_least"] = int(r[3]), int(r[4]), int(r[5]), int(r[8])
+                for f, text in zip(("eta2", "f", "p"), (r[6], r[7], r[9])):
+                    record[f] = _na_or_float(text)
+                rows.append((r[0], r[1], r[2], record))
+            else:
+                raise ValueError(f"{path}: not a row of a cohort permdisp file: {ln!r}")
+    return columns, rows, groups, distances, info
 
 
 EDGETEST_HEADER = "edge_num\tcolumn" + "".join(f"\t{kind}_{field}" for kind in ("mass", "imbalance")
@@ -1700,3 +1822,8 @@ def read_kr_tsv(path: str):
     if [r[0] for r in rows] != names:
         raise ValueError(f"{path}: the rows do not follow the first line's names")
     return names, np.array([[float(x) for x in r[1:]] for r in rows], dtype=np.float64).reshape(len(names), len(names))
+
+
+def read_unifrac_tsv(path: str):
+    """(names, float64 [S][S]) of a cohort_unifrac_<metric>_<list>.tsv"""
+    return read_kr_tsv(path)

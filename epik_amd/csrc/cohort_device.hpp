@@ -1,4 +1,4 @@
-// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, pcoa_place.hip, kmeans_place.hip, diversity_place.hip, correlation_place.hip, permanova_place.hip, edgetest_place.hip and permdisp_place.hip share of a device cohort: the object
+// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, pcoa_place.hip, kmeans_place.hip, diversity_place.hip, correlation_place.hip, permanova_place.hip, edgetest_place.hip, permdisp_place.hip and unifrac_place.hip share of a device cohort: the object
 // itself and the launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering and the
 // edge principal components start from; and the device code that the correlation, PERMANOVA and the edge test have in
 // common: a branch's vectors and midranks, the permutation key and rank, and a column's list and groups.
@@ -70,6 +70,11 @@ int cohort_normalise_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree,
 // epik_amd_cohort_kr_device: the checks, the workspace, the lengths, then the normalise and distance kernels on `stream`
 int cohort_kr_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out,
                       hipStream_t stream);
+
+// unifrac_place.hip: the matrix of distance `metric` (EPIK_AMD_DISTANCE_*) into d_out on `stream`: cohort_kr_enqueue for KR,
+// epik_amd_cohort_unifrac_device for the UniFrac distances; any other metric is refused with a message that names it
+int cohort_distance_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                            void *d_out, hipStream_t stream);
 
 // correlation_place.hip: the checks of epca_device, the device drained, T_s and the planes C and B, the workspace of the
 // correlation, then xm as a plane [N][Sp], sample-fastest, on `stream`: *d_first the tree's first[], *d_X the plane

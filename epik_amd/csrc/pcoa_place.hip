@@ -281,6 +281,12 @@ int epik_amd_cohort_pcoa_device(epik_amd_cohort *cohort, const void *d_kr, uint3
 int epik_amd_cohort_pcoa(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t num_components,
                          double *mu, double *coord, epik_amd_pcoa_info *info)
 {
+    return epik_amd_cohort_pcoa_metric(cohort, tree, branch_length, EPIK_AMD_DISTANCE_KR, num_components, mu, coord, info);
+}
+
+int epik_amd_cohort_pcoa_metric(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                                uint32_t num_components, double *mu, double *coord, epik_amd_pcoa_info *info)
+{
     try {
         if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
         if (const int rc = components_valid(num_components); rc != EPIK_AMD_OK) return rc;
@@ -291,7 +297,7 @@ int epik_amd_cohort_pcoa(epik_amd_cohort *cohort, const epik_amd_tree *tree, con
         const size_t doubles = S + S * K;  // mu | coord, then the info block
         HIP_TRY(hipMalloc(&kr.d, S * S * sizeof(double)));
         HIP_TRY(hipMalloc(&m.d, doubles * sizeof(double) + sizeof(epik_amd_pcoa_info)));
-        if (const int rc = cohort_kr_enqueue(cohort, tree, branch_length, kr.d, nullptr); rc != EPIK_AMD_OK) return rc;
+        if (const int rc = cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr); rc != EPIK_AMD_OK) return rc;
         double *d = static_cast<double *>(m.d);
         if (const int rc = pcoa_device_impl(cohort, kr.d, num_components, d, d + S, d + doubles, nullptr); rc != EPIK_AMD_OK) return rc;
         HIP_TRY(hipMemcpy(mu, d, S * sizeof(double), hipMemcpyDeviceToHost));
@@ -307,12 +313,20 @@ int epik_amd_cohort_pcoa_host(const uint64_t *mass, uint32_t num_samples, uint32
                               const double *branch_length, uint32_t num_components, double *mu, double *coord,
                               epik_amd_pcoa_info *info)
 {
+    return epik_amd_cohort_pcoa_metric_host(mass, num_samples, num_branches, first, branch_length, EPIK_AMD_DISTANCE_KR, num_components, mu,
+                                            coord, info);
+}
+
+int epik_amd_cohort_pcoa_metric_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                     const double *branch_length, uint32_t metric, uint32_t num_components, double *mu, double *coord,
+                                     epik_amd_pcoa_info *info)
+{
     try {
         if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
         if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
         if (!mass || !first || !branch_length || !mu || !coord || !info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
         std::string err;
-        if (const int rc = pcoa_components(mass, num_samples, num_branches, first, branch_length, num_components, mu, coord, info, err);
+        if (const int rc = pcoa_components(mass, num_samples, num_branches, first, branch_length, num_components, mu, coord, info, err, metric);
             rc != EPIK_AMD_OK)
             return fail_with(rc, err);
         return EPIK_AMD_OK;

@@ -480,6 +480,14 @@ int epik_amd_cohort_permanova(epik_amd_cohort *cohort, const epik_amd_tree *tree
                               uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permanova *out,
                               double *ssw, double *group_ss)
 {
+    return epik_amd_cohort_permanova_metric(cohort, tree, branch_length, EPIK_AMD_DISTANCE_KR, labels, num_columns, num_permutations, seed,
+                                            pairwise, out, ssw, group_ss);
+}
+
+int epik_amd_cohort_permanova_metric(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                                     const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
+                                     epik_amd_permanova *out, double *ssw, double *group_ss)
+{
     try {
         if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
         if (num_columns < 1 || num_columns > kColumns)
@@ -496,7 +504,7 @@ int epik_amd_cohort_permanova(epik_amd_cohort *cohort, const epik_amd_tree *tree
         HIP_TRY(hipMalloc(&r.d, out_bytes));
         if (ssw) HIP_TRY(hipMalloc(&s.d, ssw_bytes));
         if (group_ss) HIP_TRY(hipMalloc(&g.d, group_bytes));
-        if (const int rc = cohort_kr_enqueue(cohort, tree, branch_length, kr.d, nullptr); rc != EPIK_AMD_OK) return rc;
+        if (const int rc = cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr); rc != EPIK_AMD_OK) return rc;
         if (const int rc = permanova_device_impl(cohort, kr.d, labels, num_columns, num_permutations, seed, pairwise != 0, r.d, s.d, g.d,
                                                  nullptr);
             rc != EPIK_AMD_OK)
@@ -515,13 +523,22 @@ int epik_amd_cohort_permanova_host(const uint64_t *mass, uint32_t num_samples, u
                                    uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permanova *out, double *ssw,
                                    double *group_ss)
 {
+    return epik_amd_cohort_permanova_metric_host(mass, num_samples, num_branches, first, branch_length, EPIK_AMD_DISTANCE_KR, labels,
+                                                 num_columns, num_permutations, seed, pairwise, out, ssw, group_ss);
+}
+
+int epik_amd_cohort_permanova_metric_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                          const double *branch_length, uint32_t metric, const uint32_t *labels, uint32_t num_columns,
+                                          uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permanova *out, double *ssw,
+                                          double *group_ss)
+{
     try {
         if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
         if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
         if (!mass || !first || !branch_length || !labels || !out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
         std::string err;
         if (const int rc = permanova_records(mass, num_samples, num_branches, first, branch_length, labels, num_columns,
-                                             num_permutations, seed, pairwise != 0, out, ssw, group_ss, err);
+                                             num_permutations, seed, pairwise != 0, out, ssw, group_ss, err, metric);
             rc != EPIK_AMD_OK)
             return fail_with(rc, err);
         return EPIK_AMD_OK;

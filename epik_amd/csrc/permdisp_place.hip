@@ -492,6 +492,14 @@ int epik_amd_cohort_permdisp(epik_amd_cohort *cohort, const epik_amd_tree *tree,
                              uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permdisp *out,
                              double *stat, double *group_mean, double *z)
 {
+    return epik_amd_cohort_permdisp_metric(cohort, tree, branch_length, EPIK_AMD_DISTANCE_KR, labels, num_columns, num_permutations, seed,
+                                           pairwise, out, stat, group_mean, z);
+}
+
+int epik_amd_cohort_permdisp_metric(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                                    const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
+                                    epik_amd_permdisp *out, double *stat, double *group_mean, double *z)
+{
     try {
         if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
         if (num_columns < 1 || num_columns > kColumns)
@@ -509,7 +517,7 @@ int epik_amd_cohort_permdisp(epik_amd_cohort *cohort, const epik_amd_tree *tree,
         if (stat) HIP_TRY(hipMalloc(&s.d, stat_bytes));
         HIP_TRY(hipMalloc(&g.d, mean_bytes));
         HIP_TRY(hipMalloc(&zz.d, z_bytes));
-        if (const int rc = cohort_kr_enqueue(cohort, tree, branch_length, kr.d, nullptr); rc != EPIK_AMD_OK) return rc;
+        if (const int rc = cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr); rc != EPIK_AMD_OK) return rc;
         if (const int rc = permdisp_device_impl(cohort, kr.d, labels, num_columns, num_permutations, seed, pairwise != 0, r.d, s.d, g.d,
                                                 zz.d, nullptr);
             rc != EPIK_AMD_OK)
@@ -529,6 +537,15 @@ int epik_amd_cohort_permdisp_host(const uint64_t *mass, uint32_t num_samples, ui
                                   uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permdisp *out, double *stat,
                                   double *group_mean, double *z)
 {
+    return epik_amd_cohort_permdisp_metric_host(mass, num_samples, num_branches, first, branch_length, EPIK_AMD_DISTANCE_KR, labels,
+                                                num_columns, num_permutations, seed, pairwise, out, stat, group_mean, z);
+}
+
+int epik_amd_cohort_permdisp_metric_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                         const double *branch_length, uint32_t metric, const uint32_t *labels, uint32_t num_columns,
+                                         uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permdisp *out, double *stat,
+                                         double *group_mean, double *z)
+{
     try {
         if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
         if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
@@ -536,7 +553,7 @@ int epik_amd_cohort_permdisp_host(const uint64_t *mass, uint32_t num_samples, ui
             return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
         std::string err;
         if (const int rc = permdisp_records(mass, num_samples, num_branches, first, branch_length, labels, num_columns, num_permutations,
-                                            seed, pairwise != 0, out, stat, group_mean, z, err);
+                                            seed, pairwise != 0, out, stat, group_mean, z, err, metric);
             rc != EPIK_AMD_OK)
             return fail_with(rc, err);
         return EPIK_AMD_OK;

@@ -147,6 +147,78 @@ int kr_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches,
     return EPIK_AMD_OK;
 }
 
+namespace {
+
+// one half-branch of one pair: its terms of the UniFrac rule's tn_b and td_b
+template <uint32_t Metric>
+inline void unifrac_half(double x, double y, double& tn, double& td)
+{
+    if (Metric == EPIK_AMD_DISTANCE_UNWEIGHTED) {
+        const bool px = x > 0.0, py = y > 0.0;
+        tn = px != py ? 1.0 : 0.0;
+        td = px || py ? 1.0 : 0.0;
+    } else if (Metric == EPIK_AMD_DISTANCE_WEIGHTED) {
+        tn = std::fabs(x - y);
+        td = x + y;
+    } else {
+        const double sum = x + y;
+        td = std::sqrt(sum);
+        tn = sum > 0.0 ? td * (std::fabs(x - y) / sum) : 0.0;
+    }
+}
+
+// the rule's two sequential sums over two pairs of planes, then den == 0 and the one division
+template <uint32_t Metric>
+double unifrac_of(const double* cx, const double* bx, const double* cy, const double* by, const double* half, size_t N)
+{
+    double num = 0.0, den = 0.0;
+    for (size_t b = 0; b < N; ++b) {
+        double cn, cd, bn, bd;
+        unifrac_half<Metric>(cx[b], cy[b], cn, cd);
+        unifrac_half<Metric>(bx[b], by[b], bn, bd);
+        num = num + half[b] * (cn + bn);
+        den = den + half[b] * (cd + bd);
+    }
+    return den == 0.0 ? 0.0 : num / den;
+}
+
+}  // namespace
+
+int unifrac_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                   const double* branch_length, uint32_t metric, double* out, std::string& err)
+{
+    if (metric < EPIK_AMD_DISTANCE_UNWEIGHTED || metric > EPIK_AMD_DISTANCE_GENERALIZED) {
+        err = "metric = " + std::to_string(metric) + " is no UniFrac distance (1 unweighted, 2 weighted, 3 generalized)";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    const size_t S = num_samples, N = num_branches;
+    kr_planes p;
+    if (const int rc = make_planes(mass, S, N, first, branch_length, p, err); rc != EPIK_AMD_OK) return rc;
+    const auto of = metric == EPIK_AMD_DISTANCE_UNWEIGHTED ? unifrac_of<EPIK_AMD_DISTANCE_UNWEIGHTED>
+                    : metric == EPIK_AMD_DISTANCE_WEIGHTED ? unifrac_of<EPIK_AMD_DISTANCE_WEIGHTED>
+                                                           : unifrac_of<EPIK_AMD_DISTANCE_GENERALIZED>;
+    for (size_t s = 0; s < S; ++s) {
+        out[s * S + s] = 0.0;
+        for (size_t t = s + 1; t < S; ++t) {
+            double d = -1.0;
+            if (p.total[s] != 0 && p.total[t] != 0) d = of(&p.C[s * N], &p.B[s * N], &p.C[t * N], &p.B[t * N], p.half.data(), N);
+            out[s * S + t] = out[t * S + s] = d;
+        }
+    }
+    return EPIK_AMD_OK;
+}
+
+int distance_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                    const double* branch_length, uint32_t metric, double* out, std::string& err)
+{
+    if (metric == EPIK_AMD_DISTANCE_KR) return kr_matrix(mass, num_samples, num_branches, first, branch_length, out, err);
+    if (metric > EPIK_AMD_DISTANCE_GENERALIZED) {
+        err = "metric = " + std::to_string(metric) + " is no distance (0 kr, 1 unweighted, 2 weighted, 3 generalized)";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    return unifrac_matrix(mass, num_samples, num_branches, first, branch_length, metric, out, err);
+}
+
 int squash_merges(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                   const double* branch_length, epik_amd_squash_merge* merges, uint32_t* num_merges, std::string& err)
 {
@@ -978,13 +1050,15 @@ int permanova_records_of_kr(const double* kr, const uint64_t* totals, uint32_t n
 
 int permanova_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                       const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
-                      uint64_t seed, bool pairwise, epik_amd_permanova* out, double* ssw, double* group_ss, std::string& err)
+                      uint64_t seed, bool pairwise, epik_amd_permanova* out, double* ssw, double* group_ss, std::string& err,
+                      uint32_t metric)
 {
     const size_t S = num_samples, N = num_branches;
     if (const int rc = permanova_arguments_valid(labels, num_samples, num_columns, num_permutations, pairwise, err); rc != EPIK_AMD_OK)
         return rc;
     std::vector<double> kr(S * S);
-    if (const int rc = kr_matrix(mass, num_samples, num_branches, first, branch_length, kr.data(), err); rc != EPIK_AMD_OK) return rc;
+    if (const int rc = distance_matrix(mass, num_samples, num_branches, first, branch_length, metric, kr.data(), err); rc != EPIK_AMD_OK)
+        return rc;
     std::vector<uint64_t> totals(S, 0);
     for (size_t s = 0; s < S; ++s)
         for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
@@ -1059,7 +1133,7 @@ int pcoa_components_of_kr(const double* kr, const uint64_t* totals, uint32_t num
 
 int pcoa_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                     const double* branch_length, uint32_t num_components, double* mu, double* coord, epik_amd_pcoa_info* info,
-                    std::string& err)
+                    std::string& err, uint32_t metric)
 {
     const size_t S = num_samples, N = num_branches;
     if (num_components < 1 || num_components > EPIK_AMD_PCOA_MAX_COMPONENTS) {
@@ -1067,7 +1141,8 @@ int pcoa_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_bra
         return EPIK_AMD_ERR_INVALID;
     }
     std::vector<double> kr(S * S);
-    if (const int rc = kr_matrix(mass, num_samples, num_branches, first, branch_length, kr.data(), err); rc != EPIK_AMD_OK) return rc;
+    if (const int rc = distance_matrix(mass, num_samples, num_branches, first, branch_length, metric, kr.data(), err); rc != EPIK_AMD_OK)
+        return rc;
     std::vector<uint64_t> totals(S, 0);
     for (size_t s = 0; s < S; ++s)
         for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
@@ -1361,12 +1436,14 @@ int permdisp_records_of_kr(const double* kr, const uint64_t* totals, uint32_t nu
 
 int permdisp_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                      const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
-                     uint64_t seed, bool pairwise, epik_amd_permdisp* out, double* stat, double* group_mean, double* z, std::string& err)
+                     uint64_t seed, bool pairwise, epik_amd_permdisp* out, double* stat, double* group_mean, double* z, std::string& err,
+                     uint32_t metric)
 {
     const size_t S = num_samples, N = num_branches;
     if (const int rc = permdisp_arguments_valid(labels, num_samples, num_columns, num_permutations, err); rc != EPIK_AMD_OK) return rc;
     std::vector<double> kr(S * S);
-    if (const int rc = kr_matrix(mass, num_samples, num_branches, first, branch_length, kr.data(), err); rc != EPIK_AMD_OK) return rc;
+    if (const int rc = distance_matrix(mass, num_samples, num_branches, first, branch_length, metric, kr.data(), err); rc != EPIK_AMD_OK)
+        return rc;
     std::vector<uint64_t> totals(S, 0);
     for (size_t s = 0; s < S; ++s)
         for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
@@ -1504,6 +1581,43 @@ std::string format_cohort_profile_tsv(const std::vector<cohort_sample>& samples,
     return out;
 }
 
+const char* distance_name(uint32_t metric)
+{
+    static const char* const names[] = {"kr", "unweighted", "weighted", "generalized"};
+    if (metric > EPIK_AMD_DISTANCE_GENERALIZED) throw std::runtime_error("metric = " + std::to_string(metric) + " is no distance");
+    return names[metric];
+}
+
+uint32_t distance_of_name(const std::string& name, bool with_kr)
+{
+    for (uint32_t metric = with_kr ? EPIK_AMD_DISTANCE_KR : EPIK_AMD_DISTANCE_UNWEIGHTED; metric <= EPIK_AMD_DISTANCE_GENERALIZED; ++metric)
+        if (name == distance_name(metric)) return metric;
+    return 0xffffffffu;
+}
+
+std::vector<uint32_t> parse_unifrac_list(const std::string& list)
+{
+    std::vector<uint32_t> metrics;
+    if (list == "all") return {EPIK_AMD_DISTANCE_UNWEIGHTED, EPIK_AMD_DISTANCE_WEIGHTED, EPIK_AMD_DISTANCE_GENERALIZED};
+    for (size_t at = 0; at <= list.size();) {
+        const size_t comma = std::min(list.find(',', at), list.size());
+        const std::string name = list.substr(at, comma - at);
+        const uint32_t metric = distance_of_name(name, false);
+        if (metric == 0xffffffffu)
+            throw std::runtime_error("--cohort-unifrac: '" + name + "' is no UniFrac distance (unweighted, weighted, generalized, or all)");
+        if (std::find(metrics.begin(), metrics.end(), metric) != metrics.end())
+            throw std::runtime_error("--cohort-unifrac: '" + name + "' is given twice");
+        metrics.push_back(metric);
+        at = comma + 1;
+    }
+    return metrics;
+}
+
+std::string distance_field(uint32_t metric)
+{
+    return metric == EPIK_AMD_DISTANCE_KR ? std::string() : std::string("\tdistance=") + distance_name(metric);
+}
+
 std::string format_cohort_kr_tsv(const std::vector<cohort_sample>& samples, const std::vector<double>& kr)
 {
     const size_t S = samples.size();
@@ -1627,14 +1741,14 @@ std::string format_epca_edges_tsv(const std::vector<uint32_t>& first, const doub
 }
 
 std::string format_pcoa_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, uint32_t num_components,
-                            const double* mu, const double* coord, const epik_amd_pcoa_info& info)
+                            const double* mu, const double* coord, const epik_amd_pcoa_info& info, uint32_t distance)
 {
     const size_t S = samples.size(), K = num_components, Kc = info.components, L = info.used;
     const double floor_mu = std::ldexp(1.0, -40) * info.scale;
     std::string out = "# epik_amd pcoa v1  samples=" + std::to_string(S) + " used=" + std::to_string(L) +
                       " components=" + std::to_string(Kc) + " sweeps=" + std::to_string(info.sweeps) +
                       " converged=" + std::to_string(info.converged) +
-                      " negative=" + g17(info.pos != 0.0 ? (0.0 - info.neg) / info.pos : 0.0) + "\n";
+                      " negative=" + g17(info.pos != 0.0 ? (0.0 - info.neg) / info.pos : 0.0) + distance_field(distance) + "\n";
     for (size_t s = 0; s < S; ++s)
         if (totals[s] == 0) out += "# unused\t" + samples[s].name + "\n";
     for (size_t k = 0; k < L; ++k)
@@ -1774,12 +1888,12 @@ std::string format_dispersion_tsv(const std::vector<cohort_sample>& samples, con
 std::string format_permanova_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
                                  const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
                                  const uint32_t* labels, uint32_t num_permutations, uint64_t seed, bool pairwise,
-                                 const epik_amd_permanova* records, const double* group_ss)
+                                 const epik_amd_permanova* records, const double* group_ss, uint32_t distance)
 {
     const size_t S = samples.size(), M = columns.size(), slots = 1 + (pairwise ? EPIK_AMD_PERMANOVA_PAIR_SLOTS : 0);
     std::string out = used_head(samples, totals, "permanova",
                                 " columns=" + std::to_string(M) + " permutations=" + std::to_string(num_permutations) +
-                                    " seed=" + std::to_string(seed) + " pairwise=" + (pairwise ? "1" : "0"));
+                                    " seed=" + std::to_string(seed) + " pairwise=" + (pairwise ? "1" : "0") + distance_field(distance));
     // the groups of every column in the rule's order: by first appearance among the used samples
     std::vector<std::vector<uint32_t>> label_of(M), size_of(M);
     for (size_t c = 0; c < M; ++c) {
@@ -1870,12 +1984,12 @@ std::string format_edgetest_tsv(const std::vector<cohort_sample>& samples, const
 std::string format_permdisp_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
                                 const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
                                 const uint32_t* labels, uint32_t num_permutations, uint64_t seed, bool pairwise,
-                                const epik_amd_permdisp* records, const double* group_mean, const double* z)
+                                const epik_amd_permdisp* records, const double* group_mean, const double* z, uint32_t distance)
 {
     const size_t S = samples.size(), M = columns.size(), slots = 1 + (pairwise ? EPIK_AMD_PERMDISP_PAIR_SLOTS : 0);
     std::string out = used_head(samples, totals, "permdisp",
                                 " columns=" + std::to_string(M) + " permutations=" + std::to_string(num_permutations) +
-                                    " seed=" + std::to_string(seed) + " pairwise=" + (pairwise ? "1" : "0"));
+                                    " seed=" + std::to_string(seed) + " pairwise=" + (pairwise ? "1" : "0") + distance_field(distance));
     // the groups of every column in the rule's order: by first appearance among the used samples
     std::vector<std::vector<uint32_t>> label_of(M), size_of(M);
     for (size_t c = 0; c < M; ++c) {

@@ -43,6 +43,16 @@ struct sample_cohort {
 int kr_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
               const double* branch_length, double* out, std::string& err);
 
+/// The UniFrac distance `metric` (EPIK_AMD_DISTANCE_UNWEIGHTED, _WEIGHTED or _GENERALIZED) of the rule for all pairs into
+/// out[num_samples][num_samples].  The code behind epik_amd_cohort_unifrac_host; cohort_unifrac_kernel (unifrac_place.hip)
+/// gives the same bits.  0, or EPIK_AMD_ERR_INVALID with `err` as kr_matrix, or naming a metric outside 1 .. 3.
+int unifrac_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                   const double* branch_length, uint32_t metric, double* out, std::string& err);
+
+/// kr_matrix for EPIK_AMD_DISTANCE_KR, unifrac_matrix for the three UniFrac distances; any other metric is refused by name
+int distance_matrix(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                    const double* branch_length, uint32_t metric, double* out, std::string& err);
+
 /// Squash clustering by the rule (include/epik_amd.h): merges[num_samples - 1], every record written, the unused ones as
 /// the rule says, and *num_merges.  The code behind epik_amd_cohort_squash_host; libepik_amd's squash kernels
 /// (squash_place.hip) give the same bits.  0, or EPIK_AMD_ERR_INVALID with `err` as kr_matrix.
@@ -102,20 +112,23 @@ int permanova_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint
 int permanova_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
                             uint32_t num_columns, uint32_t num_permutations, uint64_t seed, bool pairwise, epik_amd_permanova* out,
                             double* ssw, double* group_ss, std::string& err);
-/// The same from the cells: kr_matrix, then permanova_records_of_kr.  The code behind epik_amd_cohort_permanova_host.
+/// The same from the cells: distance_matrix, then permanova_records_of_kr.  The code behind epik_amd_cohort_permanova_host
+/// and _permanova_metric_host.
 int permanova_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                       const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
-                      uint64_t seed, bool pairwise, epik_amd_permanova* out, double* ssw, double* group_ss, std::string& err);
+                      uint64_t seed, bool pairwise, epik_amd_permanova* out, double* ssw, double* group_ss, std::string& err,
+                      uint32_t metric = EPIK_AMD_DISTANCE_KR);
 
 /// Principal coordinates by the rule (include/epik_amd.h) from a KR matrix kr[S][S] and totals[S] (T_s): mu[S], coord[S][K]
 /// and *info, every cell written.  libepik_amd's kernels (pcoa_place.hip) give the same bits.  0, or EPIK_AMD_ERR_INVALID
 /// with `err` naming K outside [1, 64].
 int pcoa_components_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, uint32_t num_components, double* mu,
                           double* coord, epik_amd_pcoa_info* info, std::string& err);
-/// The same from the cells: kr_matrix, then pcoa_components_of_kr.  The code behind epik_amd_cohort_pcoa_host.
+/// The same from the cells: distance_matrix, then pcoa_components_of_kr.  The code behind epik_amd_cohort_pcoa_host and
+/// _pcoa_metric_host.
 int pcoa_components(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                     const double* branch_length, uint32_t num_components, double* mu, double* coord, epik_amd_pcoa_info* info,
-                    std::string& err);
+                    std::string& err, uint32_t metric = EPIK_AMD_DISTANCE_KR);
 
 /// num_columns in [1, 64], num_permutations in [1, 999 999], every label below 32 or 0xffffffff (missing): 0, or
 /// EPIK_AMD_ERR_INVALID with `err` naming the cause
@@ -138,10 +151,12 @@ int permdisp_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint3
 int permdisp_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
                            uint32_t num_columns, uint32_t num_permutations, uint64_t seed, bool pairwise, epik_amd_permdisp* out,
                            double* stat, double* group_mean, double* z, std::string& err);
-/// The same from mass[S][N]: the KR matrix by kr_matrix first.  The code behind epik_amd_cohort_permdisp_host.
+/// The same from mass[S][N]: the matrix by distance_matrix first.  The code behind epik_amd_cohort_permdisp_host and
+/// _permdisp_metric_host.
 int permdisp_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                      const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
-                     uint64_t seed, bool pairwise, epik_amd_permdisp* out, double* stat, double* group_mean, double* z, std::string& err);
+                     uint64_t seed, bool pairwise, epik_amd_permdisp* out, double* stat, double* group_mean, double* z, std::string& err,
+                     uint32_t metric = EPIK_AMD_DISTANCE_KR);
 
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
@@ -180,7 +195,7 @@ cohort_factors read_cohort_factors(const std::string& file, const std::vector<co
                                    size_t most_labels = 0, const char* flag = "--cohort-permanova");
 
 /// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash | epca | epca_edges | pcoa | kmeans |
-/// kmeans_centroids | alpha | rarefy | correlation | dispersion | permanova | edgetest | permdisp
+/// kmeans_centroids | alpha | rarefy | correlation | dispersion | permanova | edgetest | permdisp | unifrac_<metric>
 std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir,
                                  const std::string& extension = ".tsv");
 
@@ -191,6 +206,20 @@ std::string make_cohort_filename(const std::string& what, const std::string& lis
 std::string format_cohort_samples_tsv(const std::vector<cohort_sample>& samples, const sample_cohort& cohort);
 std::string format_cohort_profile_tsv(const std::vector<cohort_sample>& samples, const sample_cohort& cohort);
 std::string format_cohort_kr_tsv(const std::vector<cohort_sample>& samples, const std::vector<double>& kr);
+/// kr | unweighted | weighted | generalized of EPIK_AMD_DISTANCE_*; throws for any other metric.  distance_of_name: the
+/// metric of such a name (KR only `with_kr`), or 0xffffffff.  distance_field: what the first line of a cohort_pcoa,
+/// cohort_permanova or cohort_permdisp file ends in: nothing over KR, else <TAB>distance=NAME.
+const char* distance_name(uint32_t metric);
+uint32_t distance_of_name(const std::string& name, bool with_kr);
+std::string distance_field(uint32_t metric);
+/// The LIST of --cohort-unifrac: a comma-separated subset of unweighted, weighted, generalized, or all; the metrics in the
+/// order given.  Throws std::runtime_error naming an unknown or repeated name.
+std::vector<uint32_t> parse_unifrac_list(const std::string& list);
+/// cohort_unifrac_<metric> .tsv: the square layout of cohort_kr, doubles %.17g
+inline std::string format_cohort_unifrac_tsv(const std::vector<cohort_sample>& samples, const std::vector<double>& matrix)
+{
+    return format_cohort_kr_tsv(samples, matrix);
+}
 /// cohort_squash .tsv: "# epik_amd squash v1  samples=S clustered=S' merges=M", a "# unclustered<TAB>name" line per
 /// empty sample (live[s] == 0), the header step node a b size dist len_a len_b, a line per merge: a leaf is its index in
 /// list order, an internal node S + step, size the samples under the node, doubles as %.17g.  .nwk: the cluster tree,
@@ -212,9 +241,10 @@ std::string format_epca_edges_tsv(const std::vector<uint32_t>& first, const doub
 /// 0 when pos is 0), a "# unused<TAB>name" line per sample without mass (totals[s] == 0), a "# eigenvalue<TAB>k<TAB>mu<TAB>
 /// fraction<TAB>real|null|negative" line for each of the L eigenvalues (k from 1, fraction = mu / pos or 0), the column names
 /// name pc1 .. pcK', then per used sample in list order its name and coord[s][0 .. K'), the rows of coord K = num_components
-/// wide; doubles %.17g.
+/// wide; doubles %.17g.  Over a `distance` other than KR the first line ends in distance_field(distance).
 std::string format_pcoa_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, uint32_t num_components,
-                            const double* mu, const double* coord, const epik_amd_pcoa_info& info);
+                            const double* mu, const double* coord, const epik_amd_pcoa_info& info,
+                            uint32_t distance = EPIK_AMD_DISTANCE_KR);
 /// cohort_kmeans .tsv: "# epik_amd kmeans v1  samples=S used=L clusters=K' iterations=i converged=0|1", a "# unused<TAB>name"
 /// line per sample without mass, a "# cluster<TAB>k<TAB>size<TAB>seed name<TAB>sum_dist<TAB>sum_sq" line per cluster
 /// k < K', the column names name cluster dist, then per used sample in list order its name, cluster and dist; doubles %.17g.
@@ -247,11 +277,12 @@ std::string format_dispersion_tsv(const std::vector<cohort_sample>& samples, con
 /// ss_within_g" line per group (the groups in the rule's order, from labels[S][M], totals[S] and names[c][id]; ss_within_g from
 /// group_ss[M][256]), the column names column a b used groups ss_total ss_among ss_within f r2 at_most p, then per column
 /// the whole test (a = b = *) and, with pairwise, its pairs in slot order from records[M][1 + Q]; ss_among is
-/// ss_total - ss_within; doubles %.17g, NA as NA.
+/// ss_total - ss_within; doubles %.17g, NA as NA.  Over a `distance` other than KR the first line ends in distance_field(distance).
 std::string format_permanova_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
                                  const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
                                  const uint32_t* labels, uint32_t num_permutations, uint64_t seed, bool pairwise,
-                                 const epik_amd_permanova* records, const double* group_ss);
+                                 const epik_amd_permanova* records, const double* group_ss,
+                                 uint32_t distance = EPIK_AMD_DISTANCE_KR);
 /// cohort_edgetest .tsv: "# epik_amd edgetest v1  samples=S used=L columns=M permutations=P seed=X", the "# unused" lines, a
 /// "# column<TAB>c<TAB>name<TAB>used_c<TAB>groups_c" line per column, a "# group<TAB>c<TAB>g<TAB>label<TAB>n" line per group (the
 /// groups in the rule's order), the column names edge_num column and, for mass and imbalance, _eta2 _f _p _p_adj _top _h _kw_p
@@ -265,11 +296,13 @@ std::string format_edgetest_tsv(const std::vector<cohort_sample>& samples, const
 /// lines, the "# column" lines as cohort_permanova's, a "# group<TAB>c<TAB>g<TAB>label<TAB>n<TAB>mean_distance" line per group (from
 /// group_mean[M][32]), the column names column a b used groups clipped eta2 f at_least p, per column the whole test (a = b = *)
 /// and, with pairwise, its pairs in slot order from records[M][1 + Q]; then "# distances", the column names column name label
-/// distance and, per column, a line per sample of U_c in list order from z[M][S]; doubles %.17g, NA as NA.
+/// distance and, per column, a line per sample of U_c in list order from z[M][S]; doubles %.17g, NA as NA.  Over a `distance`
+/// other than KR the first line ends in distance_field(distance).
 std::string format_permdisp_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
                                 const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
                                 const uint32_t* labels, uint32_t num_permutations, uint64_t seed, bool pairwise,
-                                const epik_amd_permdisp* records, const double* group_mean, const double* z);
+                                const epik_amd_permdisp* records, const double* group_mean, const double* z,
+                                uint32_t distance = EPIK_AMD_DISTANCE_KR);
 /// `text` into `filename` through `filename`.part, renamed when all of it is written
 void write_through_part(const std::string& filename, const std::string& text);
 

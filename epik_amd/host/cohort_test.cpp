@@ -3,6 +3,9 @@
 //   cohort_test add <out.bin> <in.bin>...   the cohort of every input, merged: uint64 mass[S][N], best[S][N],
 //                                           totals[S][5], bad_samples
 //   cohort_test kr <out.bin> <in.bin>       the KR matrix, float64 [S][S]
+//   cohort_test unifrac <out.bin> <in.bin> <metric>
+//                                           the UniFrac matrix of a `kr` input, metric 1 (unweighted), 2 (weighted) or 3
+//                                           (generalized): float64 [S][S]
 //   cohort_test squash <out.bin> <in.bin>   the squash clustering of a `kr` input: epik_amd_squash_merge [S - 1], then
 //                                           uint32 num_merges
 //   cohort_test epca <out.bin> <in.bin> <K> the edge principal components of a `kr` input (its lengths are not used):
@@ -116,6 +119,24 @@ int main(int argc, char** argv)
                 throw std::runtime_error(err);
             std::ofstream out(argv[2], std::ios::binary);
             write_array(out, kr.data(), kr.size());
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
+        if (argc == 5 && std::strcmp(argv[1], "unifrac") == 0) {
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            const auto mass = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const auto length = read_array<double>(in, N);
+            std::vector<double> matrix(S * S);
+            std::string err;
+            if (epik_amd::unifrac_matrix(mass.data(), (uint32_t)S, (uint32_t)N, first.data(), length.data(),
+                                         (uint32_t)std::strtoul(argv[4], nullptr, 10), matrix.data(), err) != 0)
+                throw std::runtime_error(err);
+            std::ofstream out(argv[2], std::ios::binary);
+            write_array(out, matrix.data(), matrix.size());
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }

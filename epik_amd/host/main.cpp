@@ -239,6 +239,13 @@ const char* kHelp =
     "                          distances on the device and write cohort_pcoa_<list>.tsv (all eigenvalues, the negative ones of a\n"
     "                          distance that is not Euclidean included, and every sample's coordinates)\n"
     "      --cohort-pcoa-components arg  With --cohort-pcoa: the number of axes, in [1, 64] (default: 5)\n"
+    "      --cohort-unifrac arg  With --cohort: also compute the UniFrac distances between every two samples on the device: arg is\n"
+    "                          a comma-separated subset of unweighted (Lozupone & Knight 2005), weighted (normalised; Lozupone et al.\n"
+    "                          2007) and generalized (alpha = 0.5; Chen et al. 2012), or all; writes cohort_unifrac_<metric>_<list>.tsv\n"
+    "                          each.  The tree is rooted where the database's tree is: UniFrac depends on the rooting, KR does not\n"
+    "      --cohort-distance arg  With --cohort-permanova, --cohort-pcoa or --cohort-permdisp: the distance they run over: kr\n"
+    "                          (default), unweighted, weighted or generalized; with another than kr the first line of their files\n"
+    "                          ends in <TAB>distance=arg\n"
     "      --cohort-kmeans arg With --cohort: also cluster the samples into at most arg clusters, in [1, 64], by phylogenetic\n"
     "                          k-means (Czech et al. 2019) on the device and write cohort_kmeans_<list>.tsv (the clusters and\n"
     "                          every sample's cluster and distance) and cohort_kmeans_centroids_<list>.tsv (the centroids' masses)\n"
@@ -560,6 +567,22 @@ int main(int argc, char** argv)
             const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
             if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-permdisp-seed " + text + ": not a uint64");
             permdisp_seed = v;
+        }
+        // --cohort-unifrac / --cohort-distance: checked before anything is opened or any device touched
+        const bool with_unifrac = parsed.has("cohort-unifrac");
+        if (with_unifrac && !with_cohort)
+            throw std::runtime_error("--cohort-unifrac needs --cohort (it takes the UniFrac distances between the samples of the list)");
+        const std::vector<uint32_t> unifrac_metrics =
+            with_unifrac ? epik_amd::parse_unifrac_list(parsed.require("cohort-unifrac")) : std::vector<uint32_t>{};
+        uint32_t cohort_distance = EPIK_AMD_DISTANCE_KR;
+        if (parsed.has("cohort-distance")) {
+            if (!with_permanova && !with_pcoa && !with_permdisp)
+                throw std::runtime_error("--cohort-distance needs --cohort-permanova, --cohort-pcoa or --cohort-permdisp (the analyses that "
+                                         "run over a distance)");
+            const std::string name = parsed.require("cohort-distance");
+            cohort_distance = epik_amd::distance_of_name(name, true);
+            if (cohort_distance == 0xffffffffu)
+                throw std::runtime_error("--cohort-distance must be kr, unweighted, weighted or generalized, not '" + name + "'");
         }
         const bool with_edgetest = parsed.has("cohort-edge-test");
         if (with_edgetest && !with_cohort)
@@ -1053,6 +1076,9 @@ int main(int argc, char** argv)
         const auto cohort_permanova_filename = epik_amd::make_cohort_filename("permanova", query_file, output_dir);
         const auto cohort_edgetest_filename = epik_amd::make_cohort_filename("edgetest", query_file, output_dir);
         const auto cohort_permdisp_filename = epik_amd::make_cohort_filename("permdisp", query_file, output_dir);
+        const auto cohort_unifrac_filename = [&](uint32_t metric) {
+            return epik_amd::make_cohort_filename(std::string("unifrac_") + epik_amd::distance_name(metric), query_file, output_dir);
+        };
         uint64_t permdisp_clipped = 0;
         bool epca_converged = true, kmeans_converged = true, pcoa_converged = true;
         if (with_cohort) {
@@ -1080,11 +1106,17 @@ int main(int argc, char** argv)
             epik_amd::placer::cohort_permdisp permdisp;
             permdisp.labels = disp_factors.labels.data(), permdisp.num_columns = (uint32_t)disp_factors.columns.size();
             permdisp.num_permutations = permdisp_permutations, permdisp.seed = permdisp_seed, permdisp.pairwise = permdisp_pairwise;
+            epik_amd::placer::cohort_unifrac unifrac;
+            unifrac.metrics = unifrac_metrics, unifrac.distance = cohort_distance;
             placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
                                with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr, with_kmeans ? &kmeans : nullptr,
                                with_alpha || with_rarefy ? &diversity : nullptr, with_correlation || with_dispersion ? &edges : nullptr,
                                with_permanova ? &permanova : nullptr, with_edgetest ? &edgetest : nullptr, with_pcoa ? &pcoa : nullptr,
-                               with_permdisp ? &permdisp : nullptr);
+                               with_permdisp ? &permdisp : nullptr,
+                               with_unifrac || cohort_distance != EPIK_AMD_DISTANCE_KR ? &unifrac : nullptr);
+            for (size_t i = 0; i < unifrac_metrics.size(); ++i)
+                epik_amd::write_through_part(cohort_unifrac_filename(unifrac_metrics[i]),
+                                             epik_amd::format_cohort_unifrac_tsv(cohort_samples, unifrac.matrix[i]));
             epik_amd::write_through_part(cohort_samples_filename, epik_amd::format_cohort_samples_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_profile_filename, epik_amd::format_cohort_profile_tsv(cohort_samples, cohort));
             epik_amd::write_through_part(cohort_kr_filename, epik_amd::format_cohort_kr_tsv(cohort_samples, kr));
@@ -1140,7 +1172,7 @@ int main(int argc, char** argv)
                                              epik_amd::format_permanova_tsv(cohort_samples, mass_of.data(), factors.columns, factors.names,
                                                                             factors.labels.data(), permanova_permutations, permanova_seed,
                                                                             permanova_pairwise, permanova.records.data(),
-                                                                            permanova.group_ss.data()));
+                                                                            permanova.group_ss.data(), cohort_distance));
             }
             if (with_edgetest) {
                 std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
@@ -1161,7 +1193,7 @@ int main(int argc, char** argv)
                                                                            disp_factors.names, disp_factors.labels.data(),
                                                                            permdisp_permutations, permdisp_seed, permdisp_pairwise,
                                                                            permdisp.records.data(), permdisp.group_mean.data(),
-                                                                           permdisp.z.data()));
+                                                                           permdisp.z.data(), cohort_distance));
                 const size_t slots = permdisp.records.size() / disp_factors.columns.size();
                 for (size_t c = 0; c < disp_factors.columns.size(); ++c) permdisp_clipped += permdisp.records[c * slots].clipped;
             }
@@ -1170,7 +1202,8 @@ int main(int argc, char** argv)
                 for (size_t s = 0; s < mass_of.size(); ++s)
                     for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
                 epik_amd::write_through_part(cohort_pcoa_filename, epik_amd::format_pcoa_tsv(cohort_samples, mass_of.data(), pcoa.num_components,
-                                                                                             pcoa.mu.data(), pcoa.coord.data(), pcoa.info));
+                                                                                             pcoa.mu.data(), pcoa.coord.data(), pcoa.info,
+                                                                                             cohort_distance));
                 pcoa_converged = pcoa.info.converged != 0;
             }
             if (with_squash) {
@@ -1229,6 +1262,8 @@ int main(int argc, char** argv)
         if (with_cohort)
             std::cout << "Cohort samples: " << cohort_samples_filename << "\nCohort profile: " << cohort_profile_filename
                       << "\nCohort distances: " << cohort_kr_filename << std::endl;
+        for (const uint32_t metric : unifrac_metrics)
+            std::cout << "Cohort UniFrac distances (" << epik_amd::distance_name(metric) << "): " << cohort_unifrac_filename(metric) << std::endl;
         if (with_squash)
             std::cout << "Cohort clustering: " << cohort_squash_filename << "\nCohort cluster tree: " << cohort_squash_tree_filename
                       << std::endl;
@@ -1252,7 +1287,8 @@ int main(int argc, char** argv)
         if (with_edgetest) std::cout << "Cohort edge test: " << cohort_edgetest_filename << std::endl;
         if (with_permdisp) std::cout << "Cohort PERMDISP: " << cohort_permdisp_filename << std::endl;
         if (permdisp_clipped)
-            std::cout << "Warning: " << permdisp_clipped << " squared distances to a group centroid are negative (the KR distance is not "
+            std::cout << "Warning: " << permdisp_clipped << " squared distances to a group centroid are negative (the "
+                      << (cohort_distance == EPIK_AMD_DISTANCE_KR ? "KR" : epik_amd::distance_name(cohort_distance)) << " distance is not "
                       << "Euclidean) and count as zero (the clipped column of " << cohort_permdisp_filename << ")" << std::endl;
         if (with_pcoa) std::cout << "Cohort principal coordinates: " << cohort_pcoa_filename << std::endl;
         if (!pcoa_converged)

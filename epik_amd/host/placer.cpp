@@ -42,6 +42,10 @@
 #pragma weak epik_amd_cohort_edgetest
 #pragma weak epik_amd_cohort_pcoa
 #pragma weak epik_amd_cohort_permdisp
+#pragma weak epik_amd_cohort_unifrac
+#pragma weak epik_amd_cohort_permanova_metric
+#pragma weak epik_amd_cohort_pcoa_metric
+#pragma weak epik_amd_cohort_permdisp_metric
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -297,8 +301,12 @@ void placer::read_taxonomy(uint64_t* direct, uint64_t* assigned, epik_amd_taxa_t
 void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                          epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans,
                          cohort_diversity* diversity, cohort_edges* edges, cohort_permanova* permanova,
-                         cohort_edgetest* edgetest, cohort_pcoa* pcoa, cohort_permdisp* permdisp)
+                         cohort_edgetest* edgetest, cohort_pcoa* pcoa, cohort_permdisp* permdisp, cohort_unifrac* unifrac)
 {
+    const uint32_t distance = unifrac ? unifrac->distance : EPIK_AMD_DISTANCE_KR;
+    if (unifrac && (!&epik_amd_cohort_unifrac || !&epik_amd_cohort_permanova_metric || !&epik_amd_cohort_pcoa_metric ||
+                    !&epik_amd_cohort_permdisp_metric))
+        throw std::runtime_error("GPU placer: this libepik_amd has no UniFrac distances");
     if (permdisp && !&epik_amd_cohort_permdisp) throw std::runtime_error("GPU placer: this libepik_amd has no PERMDISP");
     if (pcoa && !&epik_amd_cohort_pcoa) throw std::runtime_error("GPU placer: this libepik_amd has no principal coordinates");
     if (edgetest && !&epik_amd_cohort_edgetest) throw std::runtime_error("GPU placer: this libepik_amd has no edge test");
@@ -334,6 +342,9 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
     epik_amd_tree* tree = nullptr;
     check(epik_amd_tree_create(_devices[0], parent.data(), length.data(), (uint32_t)parent.size(), &tree));
     int rc = epik_amd_cohort_kr(_cohorts[0], tree, length.data(), kr);
+    if (unifrac) unifrac->matrix.assign(unifrac->metrics.size(), std::vector<double>((size_t)_cohort_samples * _cohort_samples, 0.0));
+    for (size_t i = 0; rc == EPIK_AMD_OK && unifrac && i < unifrac->metrics.size(); ++i)
+        rc = epik_amd_cohort_unifrac(_cohorts[0], tree, length.data(), unifrac->metrics[i], unifrac->matrix[i].data());
     if (rc == EPIK_AMD_OK && num_merges) rc = epik_amd_cohort_squash(_cohorts[0], tree, length.data(), merges, num_merges);
     if (rc == EPIK_AMD_OK && epca) {
         const size_t N = parent.size(), K = epca->num_components;
@@ -376,9 +387,13 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
         const size_t slots = 1 + (permanova->pairwise ? EPIK_AMD_PERMANOVA_PAIR_SLOTS : 0);
         permanova->records.assign(permanova->num_columns * slots, epik_amd_permanova{});
         permanova->group_ss.assign((size_t)permanova->num_columns * EPIK_AMD_PERMANOVA_MAX_GROUPS, 0.0);
-        rc = epik_amd_cohort_permanova(_cohorts[0], tree, length.data(), permanova->labels, permanova->num_columns,
-                                       permanova->num_permutations, permanova->seed, permanova->pairwise ? 1 : 0,
-                                       permanova->records.data(), nullptr, permanova->group_ss.data());
+        rc = distance != EPIK_AMD_DISTANCE_KR
+                 ? epik_amd_cohort_permanova_metric(_cohorts[0], tree, length.data(), distance, permanova->labels, permanova->num_columns,
+                                                    permanova->num_permutations, permanova->seed, permanova->pairwise ? 1 : 0,
+                                                    permanova->records.data(), nullptr, permanova->group_ss.data())
+                 : epik_amd_cohort_permanova(_cohorts[0], tree, length.data(), permanova->labels, permanova->num_columns,
+                                             permanova->num_permutations, permanova->seed, permanova->pairwise ? 1 : 0,
+                                             permanova->records.data(), nullptr, permanova->group_ss.data());
     }
     if (rc == EPIK_AMD_OK && edgetest) {
         edgetest->records.assign((size_t)edgetest->num_columns * parent.size(), epik_amd_edgetest{});
@@ -387,16 +402,24 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
     }
     if (rc == EPIK_AMD_OK && pcoa) {
         pcoa->mu.assign(_cohort_samples, 0.0), pcoa->coord.assign((size_t)_cohort_samples * pcoa->num_components, 0.0);
-        rc = epik_amd_cohort_pcoa(_cohorts[0], tree, length.data(), pcoa->num_components, pcoa->mu.data(), pcoa->coord.data(), &pcoa->info);
+        rc = distance != EPIK_AMD_DISTANCE_KR
+                 ? epik_amd_cohort_pcoa_metric(_cohorts[0], tree, length.data(), distance, pcoa->num_components, pcoa->mu.data(),
+                                               pcoa->coord.data(), &pcoa->info)
+                 : epik_amd_cohort_pcoa(_cohorts[0], tree, length.data(), pcoa->num_components, pcoa->mu.data(), pcoa->coord.data(),
+                                        &pcoa->info);
     }
     if (rc == EPIK_AMD_OK && permdisp) {
         const size_t slots = 1 + (permdisp->pairwise ? EPIK_AMD_PERMDISP_PAIR_SLOTS : 0);
         permdisp->records.assign(permdisp->num_columns * slots, epik_amd_permdisp{});
         permdisp->group_mean.assign((size_t)permdisp->num_columns * EPIK_AMD_PERMDISP_MAX_GROUPS, 0.0);
         permdisp->z.assign((size_t)permdisp->num_columns * _cohort_samples, 0.0);
-        rc = epik_amd_cohort_permdisp(_cohorts[0], tree, length.data(), permdisp->labels, permdisp->num_columns,
-                                      permdisp->num_permutations, permdisp->seed, permdisp->pairwise ? 1 : 0, permdisp->records.data(),
-                                      nullptr, permdisp->group_mean.data(), permdisp->z.data());
+        rc = distance != EPIK_AMD_DISTANCE_KR
+                 ? epik_amd_cohort_permdisp_metric(_cohorts[0], tree, length.data(), distance, permdisp->labels, permdisp->num_columns,
+                                                   permdisp->num_permutations, permdisp->seed, permdisp->pairwise ? 1 : 0,
+                                                   permdisp->records.data(), nullptr, permdisp->group_mean.data(), permdisp->z.data())
+                 : epik_amd_cohort_permdisp(_cohorts[0], tree, length.data(), permdisp->labels, permdisp->num_columns,
+                                            permdisp->num_permutations, permdisp->seed, permdisp->pairwise ? 1 : 0,
+                                            permdisp->records.data(), nullptr, permdisp->group_mean.data(), permdisp->z.data());
     }
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);

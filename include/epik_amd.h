@@ -690,6 +690,25 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *   is symmetric.  The sum over b is strictly sequential per pair: an implementation may share out the pairs, never
  *   the branches of one pair.
  *
+ * UniFrac distances: unweighted (Lozupone & Knight 2005), normalised weighted (Lozupone et al. 2007) and
+ *   generalised at alpha = 0.5 (Chen et al. 2012).  From C_s[b], B_s[b], T_s, first[] and h_b = 0.5 * bl[b] exactly as the KR
+ *   rule has them: a placement sits at the middle of its branch, so a branch is two half-branches with the shares C
+ *   (proximal half) and B (distal half).  The tree is taken as rooted where the database's tree is (post-order, the root
+ *   last): KR does not depend on the rooting, UniFrac does.  For a pair (s, t), num = den = +0.0 at first, then for
+ *   b = 0, 1, ..., N - 1 in THIS order, in double, nothing fused:
+ *       num = num + h_b * tn_b,        den = den + h_b * td_b
+ *   with, by metric (the id is EPIK_AMD_DISTANCE_*; [p] is 1 where p holds, else 0):
+ *     unweighted (1)   tn_b = (double)([C_s>0] != [C_t>0]) + (double)([B_s>0] != [B_t>0])
+ *                      td_b = (double)([C_s>0] or [C_t>0]) + (double)([B_s>0] or [B_t>0])
+ *     weighted (2)     tn_b = |C_s - C_t| + |B_s - B_t|   (KR's term),       td_b = (C_s + C_t) + (B_s + B_t)
+ *     generalized (3)  tn_b = g(C_s, C_t) + g(B_s, B_t),  g(x, y) = (x + y) > 0 ? sqrt(x + y) * (|x - y| / (x + y)) : 0
+ *                      td_b = sqrt(C_s + C_t) + sqrt(B_s + B_t)
+ *   sqrt and every division correctly rounded.  Then, in this order: D(s, s) = +0.0; D(s, t) = -1.0 where T_s == 0 or
+ *   T_t == 0, as KR writes it; D(s, t) = +0.0 where den == 0; otherwise D(s, t) = num / den, one correctly rounded
+ *   division.  So weighted's num is KR(s, t) bit for bit, all three lie in [0, 1], two samples with disjoint support are
+ *   at unweighted 1.0 and identical rows at 0.0, exactly.  The sum over b is strictly sequential per pair, as KR's.
+ *   Other alpha (they need pow), variance-adjusted UniFrac and UniFrac for squash and k-means are left out.
+ *
  * Squash clustering (Matsen & Evans 2013) of the cohort's samples.  From mass[S][N], first[N] and branch_length[N] as
  *   for the KR distance; T_s, C_s[b], B_s[b] are exactly those above, and KR(x, y) over ANY two pairs of planes
  *   (C_x, B_x), (C_y, B_y) is the sequential sum above: acc = +0.0, then for b = 0 .. N - 1 in this order, in double,
@@ -978,6 +997,19 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *               [S][S] in device memory, every cell written.  The first call allocates the workspace.   kr: the same
  *               into host memory, synchronous.
  *   kr_host     the rule on the host from mass[S][N] and first[N], no device at all; first[b] > b is refused.
+ *   unifrac_device  the checks of kr_device with its messages (tree, device, N, a negative or non-finite length names its
+ *               branch), and metric outside 1 .. 3 (EPIK_AMD_DISTANCE_UNWEIGHTED, _WEIGHTED, _GENERALIZED) is refused with a
+ *               message that names it.  Synchronises the device, copies the lengths, then enqueues ONE normalisation and the
+ *               distance kernel on `stream` in kr_device's workspace: d_out is float64 [S][S] in device memory, every cell
+ *               written.  The cells and a d_kr computed earlier are not changed.  Afterwards the cohort counts as
+ *               normalised: permanova_device, pcoa_device and permdisp_device take d_out as they take kr_device's matrix.
+ *               unifrac: the same into host memory, synchronous.
+ *   unifrac_host  the rule on the host from mass[S][N], first[N] and branch_length[N], no device; first[b] > b is refused.
+ *   permanova_metric / pcoa_metric / permdisp_metric: permanova, pcoa and permdisp with `metric` (EPIK_AMD_DISTANCE_KR or one
+ *               of the three above; any other is refused with a message that names it) after branch_length: they run
+ *               kr_device or unifrac_device themselves and hand the matrix on.  permanova, pcoa and permdisp are these with
+ *               EPIK_AMD_DISTANCE_KR.  permanova_metric_host / pcoa_metric_host / permdisp_metric_host: the host mirrors
+ *               likewise, kr_host or unifrac_host and then the *_kr_host entry.
  *   squash_device  checks and workspace as kr_device (the first call allocates a distance matrix of its own beside it),
  *               then enqueues the normalise and distance kernels and all S - 1 steps on `stream`, no readback in
  *               between: d_merges is epik_amd_squash_merge [S - 1] and d_num_merges one uint32 in device memory, every
@@ -1093,6 +1125,16 @@ int epik_amd_cohort_kr_device(epik_amd_cohort *cohort, const epik_amd_tree *tree
 int epik_amd_cohort_kr(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, double *out);
 int epik_amd_cohort_kr_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                             const double *branch_length, double *out);
+#define EPIK_AMD_DISTANCE_KR 0u
+#define EPIK_AMD_DISTANCE_UNWEIGHTED 1u
+#define EPIK_AMD_DISTANCE_WEIGHTED 2u
+#define EPIK_AMD_DISTANCE_GENERALIZED 3u
+int epik_amd_cohort_unifrac_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                                   uint32_t metric, void *d_out, void *stream);
+int epik_amd_cohort_unifrac(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                            double *out);
+int epik_amd_cohort_unifrac_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                 const double *branch_length, uint32_t metric, double *out);
 typedef struct epik_amd_squash_merge {
     uint32_t a, b;       /* the two nodes merged: a leaf is its sample, an internal node S + the step that made it */
     double dist;         /* D[r][c] when they were merged */
@@ -1206,6 +1248,13 @@ int epik_amd_cohort_permanova_host(const uint64_t *mass, uint32_t num_samples, u
                                    const double *branch_length, const uint32_t *labels, uint32_t num_columns,
                                    uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permanova *out, double *ssw,
                                    double *group_ss);
+int epik_amd_cohort_permanova_metric(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                                     uint32_t metric, const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations,
+                                     uint64_t seed, int pairwise, epik_amd_permanova *out, double *ssw, double *group_ss);
+int epik_amd_cohort_permanova_metric_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches,
+                                          const uint32_t *first, const double *branch_length, uint32_t metric,
+                                          const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
+                                          int pairwise, epik_amd_permanova *out, double *ssw, double *group_ss);
 int epik_amd_cohort_permanova_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
                                       uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                       epik_amd_permanova *out, double *ssw, double *group_ss);
@@ -1223,6 +1272,11 @@ int epik_amd_cohort_pcoa(epik_amd_cohort *cohort, const epik_amd_tree *tree, con
 int epik_amd_cohort_pcoa_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                               const double *branch_length, uint32_t num_components, double *mu, double *coord,
                               epik_amd_pcoa_info *info);
+int epik_amd_cohort_pcoa_metric(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                                uint32_t num_components, double *mu, double *coord, epik_amd_pcoa_info *info);
+int epik_amd_cohort_pcoa_metric_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                     const double *branch_length, uint32_t metric, uint32_t num_components, double *mu,
+                                     double *coord, epik_amd_pcoa_info *info);
 int epik_amd_cohort_pcoa_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, uint32_t num_components,
                                  double *mu, double *coord, epik_amd_pcoa_info *info);
 typedef struct epik_amd_edgetest_family {
@@ -1268,6 +1322,14 @@ int epik_amd_cohort_permdisp_host(const uint64_t *mass, uint32_t num_samples, ui
                                   const double *branch_length, const uint32_t *labels, uint32_t num_columns,
                                   uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permdisp *out, double *stat,
                                   double *group_mean, double *z);
+int epik_amd_cohort_permdisp_metric(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                                    uint32_t metric, const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations,
+                                    uint64_t seed, int pairwise, epik_amd_permdisp *out, double *stat, double *group_mean,
+                                    double *z);
+int epik_amd_cohort_permdisp_metric_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                         const double *branch_length, uint32_t metric, const uint32_t *labels,
+                                         uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
+                                         epik_amd_permdisp *out, double *stat, double *group_mean, double *z);
 int epik_amd_cohort_permdisp_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
                                      uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                      epik_amd_permdisp *out, double *stat, double *group_mean, double *z);
