@@ -35,6 +35,10 @@ branch ANOVA and Kruskal-Wallis of mass and imbalance by permutation, max-statis
 most 32 labels a column) differ in spread (PERMDISP: distances to group centroids, permutation of residuals),
 cohort_permdisp_<list>.tsv; --cohort-permdisp-permutations P (default 999), --cohort-permdisp-seed X (default 1),
 --cohort-permdisp-pairwise.
+--cohort-model FILE --cohort-model-terms LIST, with --cohort: the sequential model adonis2(D ~ term1 + term2 + ..., by = "terms")
+over the columns of FILE (a TSV, as --cohort-permanova's) that LIST names, comma-separated f:NAME (a factor) or n:NAME (a
+numeric covariate) in test order, cohort_model_<list>.tsv; --cohort-model-permutations P (default 999), --cohort-model-seed X
+(default 1).
 --cohort-pcoa, with --cohort: the principal coordinates of the samples over the KR distances, all eigenvalues with the
 negative ones of a distance that is not Euclidean, cohort_pcoa_<list>.tsv; --cohort-pcoa-components K axes (default 5).
 --cohort-unifrac LIST, with --cohort: the UniFrac distances between every two samples, LIST a comma-separated subset of
@@ -168,6 +172,17 @@ PLACE_OPTIONS = [
     (("--cohort-permdisp-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
                                        help="With --cohort-permdisp: the seed of the permutations, a uint64 [default: 1].")),
     (("--cohort-permdisp-pairwise",), dict(is_flag=True, help="With --cohort-permdisp: also test every two groups of every column.")),
+    (("--cohort-model",), dict(type=click.Path(), default=None,
+                               help="With --cohort: a TSV of factors and covariates (laid out as --cohort-permanova's): also fit on "
+                                    "the device the sequential model of the terms of --cohort-model-terms, each tested after the "
+                                    "ones before it, and write cohort_model_<list>.tsv.")),
+    (("--cohort-model-terms",), dict(type=str, default=None,
+                                     help="With --cohort-model (required): the terms in test order, comma-separated f:NAME (a "
+                                          "factor) or n:NAME (a numeric covariate).")),
+    (("--cohort-model-permutations",), dict(type=click.IntRange(1, 999999), default=None,
+                                            help="With --cohort-model: the number of permutations [default: 999].")),
+    (("--cohort-model-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
+                                    help="With --cohort-model: the seed of the permutations, a uint64 [default: 1].")),
     (("--cohort-pcoa",), dict(is_flag=True, help="With --cohort: also compute the principal coordinates of the samples over "
                                                  "their KR distances on the device and write cohort_pcoa_<list>.tsv (all "
                                                  "eigenvalues, the negative ones included, and every sample's coordinates).")),
@@ -212,7 +227,8 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                    cohort_permanova_permutations=None, cohort_permanova_seed=None, cohort_permanova_pairwise=False,
                    cohort_edge_test=None, cohort_edge_test_permutations=None, cohort_edge_test_seed=None,
                    cohort_pcoa=False, cohort_pcoa_components=None, cohort_permdisp=None, cohort_permdisp_permutations=None,
-                   cohort_permdisp_seed=None, cohort_permdisp_pairwise=False, cohort_unifrac=None, cohort_distance=None):
+                   cohort_permdisp_seed=None, cohort_permdisp_pairwise=False, cohort_unifrac=None, cohort_distance=None,
+                   cohort_model=None, cohort_model_terms=None, cohort_model_permutations=None, cohort_model_seed=None):
     if taxonomy_mass is not None and taxonomy is None:
         raise click.UsageError("--taxonomy-mass needs --taxonomy")
     if taxonomy_per_read and taxonomy is None:
@@ -272,6 +288,15 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                         ("--cohort-permdisp-pairwise", cohort_permdisp_pairwise)):
         if given and cohort_permdisp is None:
             raise click.UsageError(f"{flag} needs --cohort-permdisp")
+    if cohort_model is not None and not cohort:
+        raise click.UsageError("--cohort-model needs --cohort")
+    for flag, given in (("--cohort-model-terms", cohort_model_terms is not None),
+                        ("--cohort-model-permutations", cohort_model_permutations is not None),
+                        ("--cohort-model-seed", cohort_model_seed is not None)):
+        if given and cohort_model is None:
+            raise click.UsageError(f"{flag} needs --cohort-model")
+    if cohort_model is not None and cohort_model_terms is None:
+        raise click.UsageError("--cohort-model needs --cohort-model-terms")
     if cohort_pcoa and not cohort:
         raise click.UsageError("--cohort-pcoa needs --cohort")
     if cohort_pcoa_components is not None and not cohort_pcoa:
@@ -290,7 +315,7 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
     if cohort_distance is not None:
         if cohort_distance not in COHORT_DISTANCES:
             raise click.UsageError(f"--cohort-distance must be kr, unweighted, weighted or generalized, not '{cohort_distance}'")
-        if cohort_permanova is None and not cohort_pcoa and cohort_permdisp is None:
+        if cohort_permanova is None and not cohort_pcoa and cohort_permdisp is None and cohort_model is None:
             raise click.UsageError("--cohort-distance needs --cohort-permanova, --cohort-pcoa or --cohort-permdisp")
     if cohort:
         for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
@@ -365,6 +390,12 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
             argv += ["--cohort-permdisp-seed", str(int(cohort_permdisp_seed))]
         if cohort_permdisp_pairwise:
             argv += ["--cohort-permdisp-pairwise"]
+    if cohort_model is not None:
+        argv += ["--cohort-model", str(cohort_model), "--cohort-model-terms", str(cohort_model_terms)]
+        if cohort_model_permutations is not None:
+            argv += ["--cohort-model-permutations", str(int(cohort_model_permutations))]
+        if cohort_model_seed is not None:
+            argv += ["--cohort-model-seed", str(int(cohort_model_seed))]
     if cohort_pcoa:
         argv += ["--cohort-pcoa"]
         if cohort_pcoa_components is not None:

@@ -85,6 +85,17 @@ EDGETEST_MAX_GROUPS = 32
 EDGETEST_FAMILIES = 4
 EDGETEST_MAX_PERMUTATIONS = 999999
 EDGETEST_MISSING = 0xFFFFFFFF
+#: epik_amd_model_term (48 bytes) and epik_amd_model_info (40 bytes): a term's record of the sequential model (the whole
+#: model's is the last) and the info block; the doubles of an undefined record are NA_BITS
+MODEL_TERM = np.dtype([("df", np.uint32), ("columns", np.uint32), ("at_least", np.uint64), ("ss", np.float64), ("f", np.float64),
+                       ("r2", np.float64), ("p", np.float64)])
+MODEL_INFO = np.dtype([("used", np.uint32), ("terms", np.uint32), ("columns", np.uint32), ("rank", np.uint32),
+                       ("df_res", np.int64), ("ss_total", np.float64), ("ss_res", np.float64)])
+MODEL_MAX_TERMS = 16
+MODEL_MAX_COLUMNS = 64
+MODEL_MAX_GROUPS = 32
+MODEL_MAX_PERMUTATIONS = 999999
+MODEL_MISSING = 0xFFFFFFFF
 NA_BITS = 0x7FF8000000000000
 RAREFY_MAX_DEPTHS = 256
 RAREFY_MAX_DEPTH = 1 << 20
@@ -193,6 +204,12 @@ EXPORTS = (
     "epik_amd_cohort_permanova_metric",
     "epik_amd_cohort_permanova_metric_host",
     "epik_amd_cohort_permanova_kr_host",
+    "epik_amd_cohort_model_device",
+    "epik_amd_cohort_model",
+    "epik_amd_cohort_model_metric",
+    "epik_amd_cohort_model_host",
+    "epik_amd_cohort_model_metric_host",
+    "epik_amd_cohort_model_kr_host",
     "epik_amd_cohort_pcoa_device",
     "epik_amd_cohort_pcoa",
     "epik_amd_cohort_pcoa_host",
@@ -592,6 +609,18 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_permanova_metric_host.argtypes = [vp, u32, u32, vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp]
     lib.epik_amd_cohort_permanova_kr_host.restype = i32
     lib.epik_amd_cohort_permanova_kr_host.argtypes = [vp, vp, u32, vp, u32, u32, u64, i32, vp, vp, vp]
+    lib.epik_amd_cohort_model_device.restype = i32
+    lib.epik_amd_cohort_model_device.argtypes = [vp, vp, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp, vp]
+    lib.epik_amd_cohort_model.restype = i32
+    lib.epik_amd_cohort_model.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp]
+    lib.epik_amd_cohort_model_metric.restype = i32
+    lib.epik_amd_cohort_model_metric.argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp]
+    lib.epik_amd_cohort_model_host.restype = i32
+    lib.epik_amd_cohort_model_host.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp]
+    lib.epik_amd_cohort_model_metric_host.restype = i32
+    lib.epik_amd_cohort_model_metric_host.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp]
+    lib.epik_amd_cohort_model_kr_host.restype = i32
+    lib.epik_amd_cohort_model_kr_host.argtypes = [vp, vp, u32, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp]
     lib.epik_amd_cohort_pcoa_device.restype = i32
     lib.epik_amd_cohort_pcoa_device.argtypes = [vp, vp, u32, vp, vp, vp, vp]
     lib.epik_amd_cohort_pcoa.restype = i32

@@ -507,6 +507,72 @@ def permdisp_host(mass, first, branch_length, labels, permutations: int = 999, s
 
 
 @dataclass
+class Model:
+    """What the sequential model gives: `records` `capi.MODEL_TERM` [T + 1] (the terms in test order, then the whole model),
+    `info` one `capi.MODEL_INFO`, `stat` float64 [T + 1][P + 1] (F of permutation 0 .. P; None where not asked for) and
+    `aliased` uint8 [64] (1 for a column of the design that was dropped)."""
+    records: np.ndarray
+    info: np.void
+    stat: np.ndarray | None
+    aliased: np.ndarray
+
+
+def _design(kind, labels, values, num_samples: int):
+    """kind[T] (0 a factor, 1 numeric), labels[S][T] uint32 and values[S][T] float64 as the C ABI takes them."""
+    kind = np.ascontiguousarray(kind, dtype=np.uint32)
+    if kind.ndim != 1:
+        raise ValueError("kind must be [num_terms]")
+    shape = (num_samples, kind.shape[0])
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    if labels.shape != shape or values.shape != shape:
+        raise ValueError(f"labels and values must be [num_samples = {num_samples}][num_terms = {kind.shape[0]}]")
+    return kind, labels, values
+
+
+def _model_buffers(t: int, permutations: int, with_stat: bool):
+    records = np.zeros(max(t, 0) + 1, dtype=capi.MODEL_TERM)
+    info = np.zeros(1, dtype=capi.MODEL_INFO)
+    stat = np.full((max(t, 0) + 1, min(max(int(permutations), 0), capi.MODEL_MAX_PERMUTATIONS) + 1), np.nan) if with_stat else None
+    return records, info, stat, np.zeros(capi.MODEL_MAX_COLUMNS, dtype=np.uint8)
+
+
+def model_kr_host(kr, totals, kind, labels, values, permutations: int = 999, seed: int = 1, with_stat: bool = True) -> Model:
+    """The sequential model of the rule from a distance matrix kr[S][S] and totals[S] (T_s) on the host
+    (`epik_amd_cohort_model_kr_host`)."""
+    lib = capi.load()
+    kr = np.ascontiguousarray(kr, dtype=np.float64)
+    if kr.ndim != 2 or kr.shape[0] != kr.shape[1]:
+        raise ValueError("kr must be [num_samples][num_samples]")
+    s = kr.shape[0]
+    totals = np.ascontiguousarray(totals, dtype=np.uint64)
+    if totals.shape != (s,):
+        raise ValueError("one total mass per sample")
+    kind, labels, values = _design(kind, labels, values, s)
+    records, info, stat, aliased = _model_buffers(kind.shape[0], permutations, with_stat)
+    capi.check(lib.epik_amd_cohort_model_kr_host(kr.ctypes.data, totals.ctypes.data, s, kind.ctypes.data, labels.ctypes.data,
+                                                 values.ctypes.data, kind.shape[0], int(permutations), int(seed), records.ctypes.data,
+                                                 info.ctypes.data, stat.ctypes.data if with_stat else None, aliased.ctypes.data))
+    return Model(records, info[0], stat, aliased)
+
+
+def model_host(mass, first, branch_length, kind, labels, values, permutations: int = 999, seed: int = 1, with_stat: bool = True,
+               metric="kr") -> Model:
+    """The sequential model of the rule for mass[S][N] and the design kind[T], labels[S][T] (0xffffffff: missing) and
+    values[S][T] (NaN: missing) over the distance `metric` on the host (`epik_amd_cohort_model_metric_host`)."""
+    lib = capi.load()
+    mass, first, length = _cells_and_tree(mass, first, branch_length)
+    s, n = mass.shape
+    kind, labels, values = _design(kind, labels, values, s)
+    records, info, stat, aliased = _model_buffers(kind.shape[0], permutations, with_stat)
+    capi.check(lib.epik_amd_cohort_model_metric_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, metric_id(metric),
+                                                     kind.ctypes.data, labels.ctypes.data, values.ctypes.data, kind.shape[0],
+                                                     int(permutations), int(seed), records.ctypes.data, info.ctypes.data,
+                                                     stat.ctypes.data if with_stat else None, aliased.ctypes.data))
+    return Model(records, info[0], stat, aliased)
+
+
+@dataclass
 class Edgetest:
     """What the edge test gives: `records` `capi.EDGETEST` [M][N], `stat` float64 [M][4][N][P + 1] (eta of the labellings
     0 .. P; None where not asked for) and `max` float64 [M][4][P + 1] (the maxima over a family's defined branches)."""
@@ -884,6 +950,31 @@ class Cohort:
                                                       stat.ctypes.data if with_stat else None,
                                                       most.ctypes.data if with_max else None))
         return Edgetest(records, stat, most)
+
+    def model_device(self, d_kr: int, kind, labels, values, permutations: int, seed: int, d_out: int, d_info: int, d_aliased: int,
+                     d_stat: int = 0, stream: int = 0) -> None:
+        """The sequential model of the design kind[T], labels[S][T] and values[S][T] (host) over d_kr, float64 [S][S] in
+        device memory as `kr_device` wrote it, into d_out, `capi.MODEL_TERM` [T + 1], d_info, one `capi.MODEL_INFO`, d_aliased,
+        64 bytes, and where given d_stat, float64 [T + 1][P + 1], every cell written; asynchronous on `stream` once the design
+        is copied, no readback (`epik_amd_cohort_model_device`)."""
+        kind, labels, values = _design(kind, labels, values, self.num_samples)
+        capi.check(self._lib.epik_amd_cohort_model_device(self._handle, d_kr or None, kind.ctypes.data, labels.ctypes.data,
+                                                          values.ctypes.data, kind.shape[0], int(permutations), int(seed),
+                                                          d_out or None, d_info or None, d_stat or None, d_aliased or None,
+                                                          stream or None))
+
+    def model(self, tree, branch_length, kind, labels, values, permutations: int = 999, seed: int = 1, with_stat: bool = False,
+              metric="kr") -> Model:
+        """The sequential model of the samples over their distances `metric`, KR by default: every term of the design tested
+        after the terms before it (`epik_amd_cohort_model_metric`)."""
+        length = self._lengths(tree, branch_length)
+        kind, labels, values = _design(kind, labels, values, self.num_samples)
+        records, info, stat, aliased = _model_buffers(kind.shape[0], permutations, with_stat)
+        capi.check(self._lib.epik_amd_cohort_model_metric(self._handle, tree._handle, length.ctypes.data, metric_id(metric),
+                                                          kind.ctypes.data, labels.ctypes.data, values.ctypes.data, kind.shape[0],
+                                                          int(permutations), int(seed), records.ctypes.data, info.ctypes.data,
+                                                          stat.ctypes.data if with_stat else None, aliased.ctypes.data))
+        return Model(records, info[0], stat, aliased)
 
     def reset(self) -> None:
         capi.check(self._lib.epik_amd_cohort_reset(self._handle))
@@ -1827,3 +1918,190 @@ def read_kr_tsv(path: str):
 def read_unifrac_tsv(path: str):
     """(names, float64 [S][S]) of a cohort_unifrac_<metric>_<list>.tsv"""
     return read_kr_tsv(path)
+
+
+def read_design(path: str, terms: str, names):
+    """The design of --cohort-model for the samples `names` of the list: `path` a TSV in the layout of the factor file, `terms`
+    the comma-separated f:NAME / n:NAME of --cohort-model-terms in test order.  (term names [T], kind uint32 [T], labels uint32
+    [S][T], values float64 [S][T], label_names [T] by id, the number of lines skipped because their sample is not in the
+    list).  ValueError as `read_cohort_design` of host/cohort.cpp raises its errors, naming the line and the column."""
+    columns, kind = [], []
+    for term in terms.split(","):
+        where = f"--cohort-model-terms: term {len(columns) + 1} ('{term}')"
+        if len(term) < 3 or term[1] != ":" or term[0] not in "fn":
+            raise ValueError(f"{where} is not f:NAME (a factor) or n:NAME (numeric)")
+        if term[2:] in columns:
+            raise ValueError(f"{where}: the column '{term[2:]}' is given twice")
+        if len(columns) == capi.MODEL_MAX_TERMS:
+            raise ValueError("--cohort-model-terms: more than 16 terms")
+        columns.append(term[2:]), kind.append(int(term[0] == "n"))
+    t_count = len(columns)
+    index = {name: s for s, name in enumerate(names)}
+    labels = np.full((len(names), t_count), capi.MODEL_MISSING, dtype=np.uint32)
+    values = np.full((len(names), t_count), np.nan)
+    label_names, ids, seen, skipped, field_of, width = [[] for _ in columns], [{} for _ in columns], {}, 0, None, 0
+    with open(path, newline="") as fh:
+        for number, line in enumerate(fh, 1):
+            line = line.rstrip("\n")
+            if line.endswith("\r"):
+                line = line[:-1]
+            if not line or line.startswith("#"):
+                continue
+            where = f"{path} line {number}"
+            fields = line.split("\t")
+            if field_of is None:
+                if fields[0] != "sample":
+                    raise ValueError(f"{where}: the header must begin with 'sample'")
+                if len(fields) < 2:
+                    raise ValueError(f"{where}: the header names no column")
+                for c, name in enumerate(fields[1:]):
+                    if not name:
+                        raise ValueError(f"{where}: column {c + 1} has an empty name")
+                    if name in fields[1:c + 1]:
+                        raise ValueError(f"{where}: the column name '{name}' is given twice")
+                for t, name in enumerate(columns):
+                    if name not in fields[1:]:
+                        raise ValueError(f"{where}: the header has no column '{name}' (term {t + 1} of --cohort-model-terms)")
+                field_of, width = [fields.index(name, 1) for name in columns], len(fields)
+                continue
+            if len(fields) != width:
+                raise ValueError(f"{where}: {len(fields)} fields, not {width}")
+            s = index.get(fields[0])
+            if s is None:
+                skipped += 1
+                continue
+            if s in seen:
+                raise ValueError(f"{where}: the sample '{fields[0]}' is given twice (first on line {seen[s]})")
+            seen[s] = number
+            for t in range(t_count):
+                text = fields[field_of[t]]
+                if text in ("", "NA"):
+                    continue
+                at = f"{where}, column {columns[t]}: "
+                if kind[t]:
+                    if not _NUMBER.fullmatch(text):
+                        raise ValueError(f"{at}'{text}' is not a number, empty or NA")
+                    value = float(text)
+                    if value in (float("inf"), float("-inf")):
+                        raise ValueError(f"{at}'{text}' overflows a double")
+                    values[s, t] = value
+                    continue
+                if text not in ids[t]:
+                    if len(label_names[t]) == capi.MODEL_MAX_GROUPS:
+                        raise ValueError(f"{at}'{text}' is label number 33, more than 32")
+                    ids[t][text] = len(label_names[t])
+                    label_names[t].append(text)
+                labels[s, t] = ids[t][text]
+    if field_of is None:
+        raise ValueError(f"{path} has no header line")
+    for s, name in enumerate(names):
+        if s not in seen:
+            raise ValueError(f"{path} has no line for the sample '{name}'")
+    return columns, np.array(kind, dtype=np.uint32), labels, values, label_names, skipped
+
+
+MODEL_HEADER = "term\tdf\tss\tr2\tf\tat_least\tp"
+
+
+def format_model_tsv(names, totals, terms, kind, label_names, labels, values, permutations: int, seed: int, model: Model,
+                     distance="kr") -> str:
+    """cohort_model_<list>.tsv: the first line (used = the complete cases with mass), a `# unused` line per sample without mass,
+    a `# incomplete` line per sample with mass that lacks a value (with the first term it lacks), a `# term` line per term, a
+    `# group` line per group of a factor term in the rule's order, a `# aliased` line per dropped column, the column names, a
+    line per term, then `model`, `residual` (df_res, ss_res, 1 less every term's r2 in one chain) and `total`; doubles as
+    %.17g, NA as NA."""
+    kind, labels, values = np.asarray(kind), np.asarray(labels), np.asarray(values, dtype=np.float64)
+    totals = [int(x) for x in totals]
+    t_count, info, records = len(terms), model.info, model.records
+    if labels.shape != (len(names), t_count) or values.shape != labels.shape or len(records) != t_count + 1 or len(totals) != len(names):
+        raise ValueError("labels and values must be [num_samples][num_terms], the records [num_terms + 1]")
+    lines = [f"# epik_amd model v1  samples={len(names)} used={int(info['used'])} terms={t_count} columns={int(info['columns'])} "
+             f"rank={int(info['rank'])} permutations={int(permutations)} seed={int(seed)}" + _distance_field(distance)]
+    lines += [f"# unused\t{name}" for name, t in zip(names, totals) if t == 0]
+    lacks = np.where(kind[None, :] != 0, np.isnan(values), labels == capi.MODEL_MISSING)
+    used = []
+    for s, name in enumerate(names):
+        if totals[s] == 0:
+            continue
+        if lacks[s].any():
+            lines.append(f"# incomplete\t{name}\t{terms[int(np.argmax(lacks[s]))]}")
+        else:
+            used.append(s)
+    lines += [f"# term\t{t}\t{'n' if kind[t] else 'f'}\t{terms[t]}\t{int(records['columns'][t])}\t{int(records['df'][t])}"
+              for t in range(t_count)]
+    column_of, groups = [], []
+    for t in range(t_count):
+        if kind[t]:
+            column_of.append((t, "-"))
+            continue
+        order, sizes = [], {}
+        for s in used:
+            v = int(labels[s, t])
+            if v not in sizes:
+                order.append(v)
+            sizes[v] = sizes.get(v, 0) + 1
+        groups += [f"# group\t{t}\t{g}\t{label_names[t][v]}\t{sizes[v]}" for g, v in enumerate(order)]
+        column_of += [(t, label_names[t][v]) for v in order[1:]]
+    lines += groups
+    lines += [f"# aliased\t{t}\t{label}" for c, (t, label) in enumerate(column_of[:capi.MODEL_MAX_COLUMNS]) if model.aliased[c]]
+    lines.append(MODEL_HEADER)
+    rest = np.float64(1.0)
+    for k in range(t_count + 1):
+        r = records[k]
+        undefined = bool(np.isnan(r["p"]))
+        lines.append("\t".join([terms[k] if k < t_count else "model", str(int(r["df"])), _g17_or_na(r["ss"]), _g17_or_na(r["r2"]),
+                                _g17_or_na(r["f"]), "NA" if undefined else str(int(r["at_least"])), _g17_or_na(r["p"])]))
+        if k < t_count and int(r["df"]) and not np.isnan(r["r2"]):
+            rest = rest - np.float64(r["r2"])
+    total = float(info["ss_total"]) > 0.0
+    lines.append(f"residual\t{int(info['df_res'])}\t{_g17_or_na(info['ss_res'])}\t{_g17_or_na(rest) if total else 'NA'}\tNA\tNA\tNA")
+    lines.append(f"total\t{int(info['used']) - 1}\t{_g17_or_na(info['ss_total'])}\t{'1' if total else 'NA'}\tNA\tNA\tNA")
+    return "\n".join(lines) + "\n"
+
+
+def read_model_tsv(path: str):
+    """(terms [(name, 'f' | 'n', columns, df)], records `capi.MODEL_TERM` [T + 1] (the model's last), info: samples, used,
+    columns, rank, permutations, seed, unused, incomplete [(name, term)], groups [(term, g, label, n)], aliased [(term, label)],
+    residual (df, ss, r2), total (df, ss, r2) and, over another distance than KR, distance)."""
+    with open(path, newline="") as fh:
+        first = fh.readline().rstrip("\n")
+        head = re.fullmatch(r"# epik_amd model v1  samples=(\d+) used=(\d+) terms=(\d+) columns=(\d+) rank=(\d+) permutations=(\d+) "
+                            r"seed=(\d+)" + _DISTANCE_FIELD, first)
+        if not head:
+            raise ValueError(f"{path}: not a cohort model file")
+        info = dict(samples=int(head.group(1)), used=int(head.group(2)), columns=int(head.group(4)), rank=int(head.group(5)),
+                    permutations=int(head.group(6)), seed=int(head.group(7)), unused=[], incomplete=[], groups=[], aliased=[])
+        if head.group(8):
+            info["distance"] = head.group(8)
+        terms, rows = [], []
+        line = fh.readline().rstrip("\n")
+        while line.startswith("# "):
+            r = line.split("\t")
+            if r[0] == "# unused" and len(r) == 2:
+                info["unused"].append(r[1])
+            elif r[0] == "# incomplete" and len(r) == 3:
+                info["incomplete"].append((r[1], r[2]))
+            elif r[0] == "# term" and len(r) == 6 and int(r[1]) == len(terms):
+                terms.append((r[3], r[2], int(r[4]), int(r[5])))
+            elif r[0] == "# group" and len(r) == 5:
+                info["groups"].append((int(r[1]), int(r[2]), r[3], int(r[4])))
+            elif r[0] == "# aliased" and len(r) == 3:
+                info["aliased"].append((int(r[1]), r[2]))
+            else:
+                raise ValueError(f"{path}: not a line of a cohort model file: {line!r}")
+            line = fh.readline().rstrip("\n")
+        if line != MODEL_HEADER or len(terms) != int(head.group(3)):
+            raise ValueError(f"{path}: not a cohort model file")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    if len(rows) != len(terms) + 3 or any(len(r) != 7 for r in rows) or [r[0] for r in rows[-3:]] != ["model", "residual", "total"]:
+        raise ValueError(f"{path}: not a cohort model file")
+    records = np.zeros(len(terms) + 1, dtype=capi.MODEL_TERM)
+    for k, r in enumerate(rows[:-2]):
+        records["df"][k] = int(r[1])
+        records["columns"][k] = terms[k][2] if k < len(terms) else info["columns"]
+        records["at_least"][k] = 0 if r[5] == "NA" else int(r[5])
+        for f, text in zip(("ss", "r2", "f", "p"), (r[2], r[3], r[4], r[6])):
+            records[f][k] = _na_or_float(text)
+    for name, r in (("residual", rows[-2]), ("total", rows[-1])):
+        info[name] = (int(r[1]), _na_or_float(r[2]), _na_or_float(r[3]))
+    return terms, records, info

@@ -1,4 +1,4 @@
-// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, pcoa_place.hip, kmeans_place.hip, diversity_place.hip, correlation_place.hip, permanova_place.hip, edgetest_place.hip, permdisp_place.hip and unifrac_place.hip share of a device cohort: the object
+// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, pcoa_place.hip, kmeans_place.hip, diversity_place.hip, correlation_place.hip, permanova_place.hip, edgetest_place.hip, permdisp_place.hip, model_place.hip and unifrac_place.hip share of a device cohort: the object
 // itself and the launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering and the
 // edge principal components start from; and the device code that the correlation, PERMANOVA and the edge test have in
 // common: a branch's vectors and midranks, the permutation key and rank, and a column's list and groups.
@@ -53,6 +53,10 @@ struct epik_amd_cohort {
     // (permdisp_place.hip):
     void *d_permdisp = nullptr;
     size_t permdisp_bytes = 0;
+    // the workspace of the sequential model, allocated by the first model_device and grown by a call that needs more
+    // (model_place.hip):
+    void *d_model = nullptr;
+    size_t model_bytes = 0;
 };
 
 namespace epik_amd {
@@ -93,6 +97,13 @@ constexpr uint32_t kCohortKeyTile = 1024;      // the keys a workgroup ranks a l
 static_assert(kBlock == 256 && kCohortLdsSamples % kBlock == 0 && 2 * kCohortCountSamples <= kCohortLdsSamples);
 
 #ifdef __HIPCC__
+// B[i][j], i <= j, of the principal coordinates' centring from the distance and the means: what pcoa_place.hip and
+// model_place.hip form their Gower matrix of
+__device__ inline double gower_centred(double d, double ri, double rj, double g)
+{
+    return __dmul_rn(-0.5, __dadd_rn(__dsub_rn(__dsub_rn(__dmul_rn(d, d), ri), rj), g));
+}
+
 // the midrank of x_j among x[0 .. L): the rule's two counts
 __device__ inline double midrank(const double *x, uint32_t L, double xj)
 {

@@ -433,6 +433,7 @@ void free_cohort(epik_amd_cohort *cohort)
     (void)hipFree(cohort->d_pcoa);
     (void)hipFree(cohort->d_kmeans), (void)hipFree(cohort->d_diversity), (void)hipFree(cohort->d_rarefy);
     (void)hipFree(cohort->d_correlation), (void)hipFree(cohort->d_permanova), (void)hipFree(cohort->d_edgetest), (void)hipFree(cohort->d_permdisp);
+    (void)hipFree(cohort->d_model);
 }
 
 }  // namespace

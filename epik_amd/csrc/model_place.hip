@@ -1,0 +1,629 @@
+// model_place.hip -- the sequential distance-based linear model (McArdle & Anderson 2001; `adonis2`, by = "terms") of a
+// cohort's samples over their distances on the device: do the samples still differ by a term once the terms before it are
+// accounted for?  epik_amd_cohort_model_device / _model / _model_metric / _model_host / _model_metric_host / _model_kr_host
+// (include/epik_amd.h).
+//
+// No reference counterpart.  The rule is stated once, in include/epik_amd.h beside the PERMDISP rule (DESIGN.md 3.21;
+// epik_amd/host/cohort.cpp: model_records_of_kr is the same rule on the CPU).  Every sum is a sequential chain from +0.0 in
+// one lane (__dadd_rn / __dsub_rn / __dmul_rn / __ddiv_rn / __dsqrt_rn; the file is built with -ffp-contract=off as well).  No
+// MFMA: the chains have a fixed order.  NA is stored as its bit pattern and never computed.
+//
+//   model_terms_kernel   a wave a term: the complete cases with mass in list order (the host has set the label of every term
+//                        to `missing` for a sample that lacks any value, so every term sees the same list) and the groups of
+//                        a factor by first appearance: column_list of cohort_device.hpp, PERMANOVA's.
+//   model_rows_kernel, model_total_kernel, model_centre_kernel
+//                        the Gower matrix B[L][L] over the list exactly as pcoa_place.hip forms it (gower_centred is the
+//                        shared element), and ss_total, the chain of its diagonal, in one lane.
+//   model_basis_kernel   one workgroup: a column at a time, centred, then classical Gram-Schmidt twice: a lane a k for the
+//                        chains h_k (Q is [L][64], so the lanes read a line), a lane an i for the update, one lane for the mean,
+//                        n0 and n1.  Q, df, the aliased bytes and df_res.
+//   model_ss_kernel      the hot kernel, a workgroup a batch of kPerms permutations.  A lane owns row i and keeps
+//                        kPerms x kCols chains t_c in registers; for j ascending it reads B[j][i] (a coalesced line, and B[i][j]:
+//                        B is symmetric bit for bit) and multiplies it into the rows Q[sigma_p(j)][c0 .. c0 + kCols), the same
+//                        address for the whole wave (the arrangement is read through readfirstlane: uniform loads).  One read of
+//                        B feeds kPerms x kCols chains; a design of more than kCols accepted columns takes a pass over B for
+//                        every kCols of them.  Then a lane a (permutation, column): the chain s_c over t, which sits in LDS up to
+//                        kLdsPositions samples and in the workgroup's slice of global memory beyond (or with
+//                        EPIK_AMD_MODEL_LDS=0): the same code on other pointers.  Then a lane a permutation: SS_k and SS_model;
+//                        and a lane a term: F of every permutation and one vector atomic for the unit's count.  sigma_p is
+//                        permutation_rank of cohort_device.hpp.  Launched twice: the identity alone, which writes the records,
+//                        the info block and F_0; then the permutations 1 .. P.
+//   model_finish_kernel  p = (1 + at_least) / (P + 1), and NA into the rows of stat whose test is undefined.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../host/cohort.hpp"
+#include "cohort_device.hpp"
+#include "host_entry.hpp"
+
+namespace {
+
+using namespace epik_amd;
+
+constexpr uint32_t kTerms = EPIK_AMD_MODEL_MAX_TERMS;
+constexpr uint32_t kColumns = EPIK_AMD_MODEL_MAX_COLUMNS;
+constexpr uint32_t kGroups = EPIK_AMD_MODEL_MAX_GROUPS;
+constexpr uint32_t kMissing = EPIK_AMD_MODEL_MISSING;
+constexpr uint32_t kPerms = 4;             // the permutations a workgroup carries through one pass over B
+constexpr uint32_t kChunk = 8;             // the columns a lane accumulates at a time: kPerms * kChunk chains in registers
+constexpr uint32_t kSmallColumns = 4;      // a design of up to here columns accumulates kSmallColumns at a time instead
+constexpr uint32_t kLdsPositions = 128;    // the most samples whose row sums and arrangements stay in LDS (34 KiB)
+constexpr uint32_t kGeneralBlocks = 256;   // workgroups of the general path: each has a slice
+constexpr uint64_t kManyBlocks = 65536;
+constexpr uint32_t kPitch = kColumns;      // doubles a row of Q
+
+static_assert(sizeof(epik_amd_model_term) == 48 && sizeof(epik_amd_model_info) == 40, "the records are 48 and 40 bytes");
+static_assert(kBlock == 256 && kWave == 64 && kColumns % kChunk == 0 && kChunk % kSmallColumns == 0);
+static_assert(kPerms * (kTerms + 1) <= kBlock && kPerms * kChunk <= kBlock && kColumns <= kBlock);
+
+// what the kernels hand on to one another, in the workspace
+struct ModelMeta {
+    uint32_t L, C, R, testable;
+    int64_t df_res;
+    double g, ss_total, ss_res;
+    uint32_t groups[kTerms];
+    uint32_t df[kTerms + 1], columns[kTerms + 1], first[kTerms + 1];  // of a term, and of the whole model; first: its first accepted column
+    double f0[kTerms + 1];
+};
+
+struct ModelKinds {
+    uint32_t kind[kTerms];
+};
+
+struct ModelSpace {
+    double *B;        // [S][S]: the Gower matrix, L x L compact
+    double *Q;        // [Sp][kPitch]: the basis, a position a row
+    double *r, *v;    // [Sp]: the row means; the column at work
+    double *val;      // [T][Sp]: the values by sample
+    double *scratch;  // [slices] x (t[kPerms][kChunk][Sp] | sigma[kPerms][Sp]): a slice a workgroup of the general path, none on the LDS path
+    ModelMeta *meta;
+    uint32_t *lab;    // [T][Sp]: the labels by sample, `missing` for a sample that is no complete case
+    uint32_t *idx;    // [T][Sp]: the samples of the positions (every term's list is the same)
+    uint8_t *lam;     // [T][Sp]: the groups of the positions
+};
+
+constexpr size_t kSliceBytes = kPerms * kChunk * 8 + kPerms * 4;  // the bytes of a slice per padded sample
+
+size_t model_space(void *base, uint32_t S, uint32_t padded, uint32_t T, uint32_t slices, ModelSpace *sp)
+{
+    size_t at = 0;
+    const auto take = [&](size_t bytes) {
+        const size_t offset = at;
+        at += (bytes + 15) / 16 * 16;
+        return offset;
+    };
+    const size_t B = take((size_t)S * S * 8), Q = take((size_t)padded * kPitch * 8), r = take((size_t)padded * 8), v = take((size_t)padded * 8);
+    const size_t val = take((size_t)T * padded * 8), scratch = take((size_t)slices * kSliceBytes * padded);
+    const size_t meta = take(sizeof(ModelMeta)), lab = take((size_t)T * padded * 4), idx = take((size_t)T * padded * 4);
+    const size_t lam = take((size_t)T * padded);
+    if (sp) {
+        char *b = static_cast<char *>(base);
+        const auto d = [&](size_t o) { return reinterpret_cast<double *>(b + o); };
+        const auto u = [&](size_t o) { return reinterpret_cast<uint32_t *>(b + o); };
+        *sp = ModelSpace{d(B), d(Q), d(r), d(v), d(val), d(scratch), reinterpret_cast<ModelMeta *>(b + meta), u(lab), u(idx),
+                         reinterpret_cast<uint8_t *>(b + lam)};
+    }
+    return at;
+}
+
+__device__ inline double na_value() { return __longlong_as_double((long long)EPIK_AMD_NA_BITS); }
+
+__global__ __launch_bounds__(kWave) void model_terms_kernel(const uint64_t *__restrict__ total, const uint32_t *__restrict__ lab,
+                                                            uint32_t num_samples, uint32_t padded, uint32_t num_terms,
+                                                            uint32_t *__restrict__ idx, uint8_t *__restrict__ lam,
+                                                            ModelMeta *__restrict__ meta)
+{
+    __shared__ uint32_t group_of[kGroups], size[kGroups];
+    for (uint32_t t = blockIdx.x; t < num_terms; t += gridDim.x) {
+        const uint64_t offset = (uint64_t)t * padded;
+        uint32_t L, G;  // (uniform)
+        column_list<kGroups>(total, lab + offset, num_samples, kMissing, group_of, size, idx + offset, lam + offset, L, G);
+        if (threadIdx.x == 0) {
+            meta->groups[t] = G;
+            if (t == 0) meta->L = L;
+        }
+        __syncthreads();  // (the tables are written again)
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void model_rows_kernel(const double *__restrict__ kr, const uint32_t *__restrict__ used,
+                                                            uint32_t num_samples, const ModelMeta *__restrict__ meta,
+                                                            double *__restrict__ r)
+{
+    const uint32_t L = meta->L;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < L; i += gridDim.x * kBlock) {
+        const double *column = kr + used[i];  // KR[u_j][u_i] = KR[u_i][u_j]
+        double acc = 0.0;
+#pragma unroll 4  // (the reads of four values are in flight ahead of the dependent adds)
+        for (uint32_t j = 0; j < L; ++j) {  // ascending: the rule's order
+            const double d = column[(uint64_t)used[j] * num_samples];
+            acc = __dadd_rn(acc, __dmul_rn(d, d));
+        }
+        r[i] = __ddiv_rn(acc, (double)L);
+    }
+}
+
+__global__ __launch_bounds__(kWave) void model_total_kernel(const double *__restrict__ kr, const uint32_t *__restrict__ used,
+                                                            uint32_t num_samples, ModelMeta *__restrict__ meta,
+                                                            const double *__restrict__ r)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const uint32_t L = meta->L;
+    double g = 0.0;
+    for (uint32_t i = 0; i < L; ++i) g = __dadd_rn(g, r[i]);  // ascending: the rule's order
+    if (L) g = __ddiv_rn(g, (double)L);
+    double total = 0.0;
+    for (uint32_t j = 0; j < L; ++j) {
+        const uint32_t s = used[j];
+        total = __dadd_rn(total, gower_centred(kr[(uint64_t)s * num_samples + s], r[j], r[j], g));
+    }
+    meta->g = g, meta->ss_total = total;
+}
+
+__global__ __launch_bounds__(kBlock) void model_centre_kernel(const double *__restrict__ kr, const uint32_t *__restrict__ used,
+                                                              uint32_t num_samples, const ModelMeta *__restrict__ meta,
+                                                              const double *__restrict__ r, double *__restrict__ B)
+{
+    const uint32_t L = meta->L;
+    const uint64_t cells = (uint64_t)L * L;
+    const double g = meta->g;
+    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < cells; e += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t i = (uint32_t)(e / L), j = (uint32_t)(e - (uint64_t)i * L), lo = i < j ? i : j, hi = i < j ? j : i;
+        B[e] = gower_centred(kr[(uint64_t)used[lo] * num_samples + used[hi]], r[lo], r[hi], g);
+    }
+}
+
+// one workgroup; every condition around a barrier is uniform (L, G, R and the acceptance come from shared memory)
+__global__ __launch_bounds__(kBlock) void model_basis_kernel(const ModelKinds kinds, uint32_t num_terms, uint32_t padded,
+                                                             const double *__restrict__ val, const uint32_t *__restrict__ idx,
+                                                             const uint8_t *__restrict__ lam, double *v, double *Q,
+                                                             ModelMeta *meta, uint8_t *__restrict__ aliased)
+{
+    __shared__ double h[kColumns];
+    __shared__ double mean_of, root_of;
+    __shared__ uint32_t accepted;
+    const uint32_t tid = threadIdx.x, L = meta->L;
+    uint32_t C = 0, R = 0;
+    for (uint32_t t = 0; t < num_terms; ++t) {
+        const bool numeric = kinds.kind[t] != 0;
+        const uint32_t G = meta->groups[t], width = numeric ? 1 : G ? G - 1 : 0, first = R;
+        const uint64_t offset = (uint64_t)t * padded;
+        for (uint32_t w = 0; w < width; ++w, ++C) {
+            for (uint32_t i = tid; i < L; i += kBlock) v[i] = numeric ? val[offset + idx[i]] : lam[offset + i] == w + 1 ? 1.0 : 0.0;
+            __syncthreads();
+            if (tid == 0 && L) {
+                double acc = 0.0;
+#pragma unroll 4
+                for (uint32_t i = 0; i < L; ++i) acc = __dadd_rn(acc, v[i]);
+                mean_of = __ddiv_rn(acc, (double)L);
+            }
+            __syncthreads();
+            for (uint32_t i = tid; i < L; i += kBlock) v[i] = __dsub_rn(v[i], mean_of);
+            __syncthreads();
+            double n0 = 0.0;  // (lane 0's)
+            if (tid == 0) {
+#pragma unroll 4
+                for (uint32_t i = 0; i < L; ++i) n0 = __dadd_rn(n0, __dmul_rn(v[i], v[i]));
+            }
+            for (uint32_t pass = 0; pass < 2; ++pass) {
+                for (uint32_t k = tid; k < R; k += kBlock) {
+                    double acc = 0.0;
+#pragma unroll 4
+                    for (uint32_t i = 0; i < L; ++i) acc = __dadd_rn(acc, __dmul_rn(Q[(uint64_t)i * kPitch + k], v[i]));
+                    h[k] = acc;
+                }
+                __syncthreads();
+                for (uint32_t i = tid; i < L; i += kBlock) {
+                    const double *row = Q + (uint64_t)i * kPitch;
+                    double x = v[i];
+                    for (uint32_t k = 0; k < R; ++k) x = __dsub_rn(x, __dmul_rn(h[k], row[k]));
+                    v[i] = x;
+                }
+                __syncthreads();
+            }
+            if (tid == 0) {
+                double n1 = 0.0;
+#pragma unroll 4
+                for (uint32_t i = 0; i < L; ++i) n1 = __dadd_rn(n1, __dmul_rn(v[i], v[i]));
+                const bool accept = n0 > 0.0 && n1 > __dmul_rn(0x1p-40, n0);
+                accepted = accept, root_of = accept ? __dsqrt_rn(n1) : 0.0;
+                aliased[C] = accept ? 0 : 1;
+            }
+            __syncthreads();
+            if (accepted) {
+                for (uint32_t i = tid; i < L; i += kBlock) Q[(uint64_t)i * kPitch + R] = __ddiv_rn(v[i], root_of);
+                ++R;
+            }
+            __syncthreads();  // (v, the acceptance and Q are complete before the next column)
+        }
+        if (tid == 0) meta->df[t] = R - first, meta->columns[t] = width, meta->first[t] = first;
+    }
+    for (uint32_t c = C + tid; c < kColumns; c += kBlock) aliased[c] = 0;
+    if (tid == 0) {
+        meta->C = C, meta->R = R, meta->df[num_terms] = R, meta->columns[num_terms] = C, meta->first[num_terms] = 0;
+        meta->df_res = (int64_t)L - 1 - (int64_t)R;
+    }
+}
+
+struct SsArgs {
+    const double *B, *Q;
+    ModelMeta *meta;
+    double *scratch;
+    epik_amd_model_term *out;
+    epik_amd_model_info *info;
+    double *stat;  // or null
+    uint64_t seed;
+    uint32_t num_terms, num_permutations, pitch;
+};
+
+// F of a term from its sums: the rule's three divisions, +infinity where the residual is not > 0
+__device__ inline double f_of(double ss, uint32_t df, double res, int64_t df_res)
+{
+    if (!(res > 0.0)) return HUGE_VAL;
+    return __ddiv_rn(__ddiv_rn(ss, (double)df), __ddiv_rn(res, (double)df_res));
+}
+
+// kObserved: the identity alone, and the records; else the permutations 1 .. P, kPerms a unit.  kCols: the chains of a
+// permutation that a lane keeps at a time.
+template <bool kLds, bool kObserved, uint32_t kCols>
+__global__ __launch_bounds__(kBlock) void model_ss_kernel(const SsArgs a)
+{
+    extern __shared__ __align__(16) unsigned char dynamic_lds[];
+    __shared__ uint64_t tile[kCohortKeyTile];
+    __shared__ double s_of[kPerms][kColumns];     // s_c of permutation k
+    __shared__ double ss_of[kPerms][kTerms + 1];  // SS_k of permutation k, SS_model last
+    __shared__ ModelMeta m;
+    const uint32_t tid = threadIdx.x, pitch = a.pitch, T = a.num_terms, P = a.num_permutations;
+    if (tid == 0) m = *a.meta;
+    __syncthreads();
+    const uint32_t L = m.L, R = m.R;
+    if (!kObserved && (!m.testable || R == 0)) return;  // (uniform: no F is defined)
+    double *t;
+    uint32_t *sigma;
+    if (kLds) {
+        t = reinterpret_cast<double *>(dynamic_lds);
+    } else {
+        // (kSliceBytes * pitch bytes a slice, pitch % 32 == 0: every slice is aligned)
+        t = reinterpret_cast<double *>(reinterpret_cast<char *>(a.scratch) + (uint64_t)blockIdx.x * kSliceBytes * pitch);
+    }
+    sigma = reinterpret_cast<uint32_t *>(t + (uint64_t)kPerms * kChunk * pitch);
+    const uint32_t units = kObserved ? 1 : (P + kPerms - 1) / kPerms;
+    for (uint32_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
+        const uint32_t p0 = kObserved ? 0 : 1 + unit * kPerms, np = kObserved ? 1 : min(kPerms, P + 1 - p0);
+        for (uint32_t k = 0; k < kPerms; ++k) {
+            const uint32_t p = k < np ? p0 + k : 0;  // (beyond np: filling, the identity)
+            for (uint32_t base = 0; base < L; base += kBlock) {  // (every lane calls: it has barriers)
+                const uint32_t i = base + tid, rank = permutation_rank(a.seed, p, i, L, tile);
+                if (i < L) sigma[k * pitch + i] = rank;
+            }
+        }
+        __syncthreads();
+        for (uint32_t c0 = 0; c0 < R; c0 += kCols) {
+            for (uint32_t i = tid; i < L; i += kBlock) {
+                double acc[kPerms][kCols];
+#pragma unroll
+                for (uint32_t k = 0; k < kPerms; ++k)
+#pragma unroll
+                    for (uint32_t c = 0; c < kCols; ++c) acc[k][c] = 0.0;
+                const double *column = a.B + i;  // B[j][i] = B[i][j]
+                for (uint32_t j = 0; j < L; ++j) {  // ascending: the rule's order
+                    const double b = column[(uint64_t)j * L];
+#pragma unroll
+                    for (uint32_t k = 0; k < kPerms; ++k) {
+                        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)sigma[k * pitch + j]);  // (the wave shares j)
+                        const double *row = a.Q + (uint64_t)at * kPitch + c0;
+#pragma unroll
+                        for (uint32_t c = 0; c < kCols; ++c) acc[k][c] = __dadd_rn(acc[k][c], __dmul_rn(b, row[c]));
+                    }
+                }
+#pragma unroll
+                for (uint32_t k = 0; k < kPerms; ++k)
+#pragma unroll
+                    for (uint32_t c = 0; c < kCols; ++c) t[(uint64_t)(k * kCols + c) * pitch + i] = acc[k][c];
+            }
+            __syncthreads();
+            for (uint32_t e = tid; e < kPerms * kCols; e += kBlock) {
+                const uint32_t k = e / kCols, c = e % kCols;
+                if (c0 + c >= R) continue;
+                const double *tk = t + (uint64_t)e * pitch;
+                const uint32_t *sk = sigma + k * pitch;
+                double s = 0.0;
+#pragma unroll 4
+                for (uint32_t i = 0; i < L; ++i) s = __dadd_rn(s, __dmul_rn(a.Q[(uint64_t)sk[i] * kPitch + c0 + c], tk[i]));
+                s_of[k][c0 + c] = s;
+            }
+            __syncthreads();  // (t is written again)
+        }
+        if (tid < kPerms) {
+            double model = 0.0;
+            for (uint32_t term = 0; term < T; ++term) {
+                double ss = 0.0;
+                for (uint32_t w = 0; w < m.df[term]; ++w) ss = __dadd_rn(ss, s_of[tid][m.first[term] + w]);
+                ss_of[tid][term] = ss;
+                model = __dadd_rn(model, ss);
+            }
+            ss_of[tid][T] = model;
+        }
+        __syncthreads();
+        if (kObserved) {
+            if (tid == 0) {
+                const double ss_res = __dsub_rn(m.ss_total, ss_of[0][T]);
+                const bool testable = m.df_res >= 1 && ss_res > 0.0;
+                a.meta->ss_res = ss_res, a.meta->testable = testable;
+                *a.info = epik_amd_model_info{L, T, m.C, R, m.df_res, m.ss_total, ss_res};
+                for (uint32_t term = 0; term <= T; ++term) {
+                    epik_amd_model_term rec{m.df[term], m.columns[term], 0, na_value(), na_value(), na_value(), na_value()};
+                    double f0 = na_value();
+                    if (rec.df) {
+                        rec.ss = ss_of[0][term];
+                        if (m.ss_total > 0.0) rec.r2 = __ddiv_rn(rec.ss, m.ss_total);
+                        if (testable) rec.f = f0 = f_of(rec.ss, rec.df, ss_res, m.df_res);
+                        if (testable && a.stat) a.stat[(uint64_t)term * (P + 1)] = f0;
+                    }
+                    a.out[term] = rec, a.meta->f0[term] = f0;
+                }
+            }
+        } else if (tid <= T && m.df[tid]) {
+            unsigned long long count = 0;
+            for (uint32_t k = 0; k < np; ++k) {
+                const double f = f_of(ss_of[k][tid], m.df[tid], __dsub_rn(m.ss_total, ss_of[k][T]), m.df_res);
+                if (a.stat) a.stat[(uint64_t)tid * (P + 1) + p0 + k] = f;
+                count += f >= m.f0[tid];
+            }
+            if (count) atomicAdd(reinterpret_cast<unsigned long long *>(&a.out[tid].at_least), count);
+        }
+        __syncthreads();  // (the arrangements and the sums are written again)
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void model_finish_kernel(const ModelMeta *__restrict__ meta, uint32_t num_terms,
+                                                              uint32_t num_permutations, epik_amd_model_term *__restrict__ out,
+                                                              double *__restrict__ stat)
+{
+    const uint64_t first = (uint64_t)blockIdx.x * kBlock + threadIdx.x, stride = (uint64_t)gridDim.x * kBlock;
+    const bool testable = meta->testable != 0;
+    for (uint64_t term = first; term <= num_terms; term += stride)
+        if (testable && meta->df[term])
+            out[term].p = __ddiv_rn((double)(1 + out[term].at_least), (double)(num_permutations + 1));
+    if (!stat) return;
+    const uint64_t row = (uint64_t)num_permutations + 1;
+    for (uint64_t e = first; e < (num_terms + 1) * row; e += stride)
+        if (!(testable && meta->df[e / row])) stat[e] = na_value();
+}
+
+dim3 grid_of(const epik_amd_cohort *cohort, uint64_t units, uint64_t most)
+{
+    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
+    return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({units, most, cap})));
+}
+
+// EPIK_AMD_MODEL_LDS=0 (tests), read at the call: the general path whatever S
+bool lds_path(uint32_t S)
+{
+    const char *env = std::getenv("EPIK_AMD_MODEL_LDS");
+    return S <= kLdsPositions && !(env && std::strcmp(env, "0") == 0);
+}
+
+int check_arguments(const uint32_t *kind, const uint32_t *labels, const double *values, uint32_t S, uint32_t T, uint32_t P)
+{
+    std::string err;
+    if (const int rc = model_arguments_valid(kind, labels, values, S, T, P, err); rc != EPIK_AMD_OK) return fail_with(rc, err);
+    return EPIK_AMD_OK;
+}
+
+int terms_valid(uint32_t T)
+{
+    if (T < 1 || T > kTerms) return fail_with(EPIK_AMD_ERR_INVALID, "num_terms = " + std::to_string(T) + " is outside [1, 16]");
+    return EPIK_AMD_OK;
+}
+
+template <bool kLds, uint32_t kCols>
+void launch_ss(const epik_amd_cohort *cohort, const SsArgs &args, size_t dynamic, hipStream_t stream)
+{
+    const uint64_t units = (args.num_permutations + kPerms - 1) / kPerms, most = kLds ? kManyBlocks : kGeneralBlocks;
+    hipLaunchKernelGGL((model_ss_kernel<kLds, true, kCols>), dim3(1), dim3(kBlock), dynamic, stream, args);
+    hipLaunchKernelGGL((model_ss_kernel<kLds, false, kCols>), grid_of(cohort, units, most), dim3(kBlock), dynamic, stream, args);
+}
+
+int model_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *kind, const uint32_t *labels, const double *values,
+                      uint32_t T, uint32_t P, uint64_t seed, void *d_out, void *d_info, void *d_stat, void *d_aliased, hipStream_t stream)
+{
+    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    if (const int rc = terms_valid(T); rc != EPIK_AMD_OK) return rc;
+    if (!d_kr || !kind || !labels || !values || !d_out || !d_info || !d_aliased) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    const uint32_t S = cohort->num_samples, padded = cohort_padded_samples(cohort);
+    if (const int rc = check_arguments(kind, labels, values, S, T, P); rc != EPIK_AMD_OK) return rc;
+    if (!cohort->d_total)
+        return fail_with(EPIK_AMD_ERR_INVALID, "the cohort has no distances yet: d_kr must be what kr_device wrote for this cohort");
+    HIP_TRY(hipSetDevice(cohort->device));
+    HIP_TRY(hipDeviceSynchronize());  // (the distances enqueued on whatever stream, and an earlier call that reads the workspace)
+    const bool lds = lds_path(S);
+    // the general path's workgroups, each with a slice: the grid that launch_ss makes of the permutations' units
+    const uint32_t slices = lds ? 0 : grid_of(cohort, (P + kPerms - 1) / kPerms, kGeneralBlocks).x;
+    const size_t bytes = model_space(nullptr, S, padded, T, slices, nullptr);
+    if (bytes > cohort->model_bytes) {
+        (void)hipFree(cohort->d_model);
+        cohort->d_model = nullptr, cohort->model_bytes = 0;
+        HIP_TRY(hipMalloc(&cohort->d_model, bytes));
+        cohort->model_bytes = bytes;
+    }
+    ModelSpace sp;
+    model_space(cohort->d_model, S, padded, T, slices, &sp);
+    // the design by term; a sample that lacks any value is missing in every term, so every term lists the complete cases
+    std::vector<uint32_t> lab((size_t)T * padded, kMissing);
+    std::vector<double> val((size_t)T * padded, 0.0);
+    ModelKinds kinds{};
+    size_t bound = 0;  // the columns as the rule counts them: at least those of the used samples
+    for (uint32_t t = 0; t < T; ++t) {
+        kinds.kind[t] = kind[t];
+        std::set<uint32_t> distinct;
+        for (uint32_t s = 0; s < S; ++s)
+            if (!kind[t] && labels[(size_t)s * T + t] != kMissing) distinct.insert(labels[(size_t)s * T + t]);
+        bound += kind[t] ? 1 : distinct.empty() ? 0 : distinct.size() - 1;
+    }
+    for (uint32_t s = 0; s < S; ++s) {
+        bool complete = true;
+        for (uint32_t t = 0; t < T; ++t)
+            complete = complete && (kind[t] ? !std::isnan(values[(size_t)s * T + t]) : labels[(size_t)s * T + t] != kMissing);
+        if (!complete) continue;
+        for (uint32_t t = 0; t < T; ++t) {
+            lab[(size_t)t * padded + s] = kind[t] ? 0 : labels[(size_t)s * T + t];
+            val[(size_t)t * padded + s] = kind[t] ? values[(size_t)s * T + t] : 0.0;
+        }
+    }
+    HIP_TRY(hipMemcpy(sp.lab, lab.data(), lab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sp.val, val.data(), val.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(sp.meta, 0, sizeof(ModelMeta), stream));
+    HIP_TRY(hipMemsetAsync(sp.Q, 0, (size_t)padded * kPitch * sizeof(double), stream));  // (a lane reads whole chunks of a row)
+    const auto *kr = static_cast<const double *>(d_kr);
+    const uint64_t cells = (uint64_t)S * S;
+    hipLaunchKernelGGL(model_terms_kernel, grid_of(cohort, T, kTerms), dim3(kWave), 0, stream, cohort->d_total, sp.lab, S, padded, T, sp.idx,
+                       sp.lam, sp.meta);
+    hipLaunchKernelGGL(model_rows_kernel, grid_of(cohort, (S + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, kr, sp.idx, S,
+                       sp.meta, sp.r);
+    hipLaunchKernelGGL(model_total_kernel, dim3(1), dim3(kWave), 0, stream, kr, sp.idx, S, sp.meta, sp.r);
+    hipLaunchKernelGGL(model_centre_kernel, grid_of(cohort, (cells + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, kr, sp.idx,
+                       S, sp.meta, sp.r, sp.B);
+    hipLaunchKernelGGL(model_basis_kernel, dim3(1), dim3(kBlock), 0, stream, kinds, T, padded, sp.val, sp.idx, sp.lam, sp.v, sp.Q, sp.meta,
+                       static_cast<uint8_t *>(d_aliased));
+    const uint32_t pitch = lds ? kLdsPositions : padded;
+    const SsArgs args{sp.B, sp.Q, sp.meta, sp.scratch, static_cast<epik_amd_model_term *>(d_out),
+                      static_cast<epik_amd_model_info *>(d_info), static_cast<double *>(d_stat), seed, T, P, pitch};
+    const size_t dynamic = lds ? kSliceBytes * pitch : 0;
+    const bool small = bound <= kSmallColumns;
+    if (lds && small) launch_ss<true, kSmallColumns>(cohort, args, dynamic, stream);
+    else if (lds) launch_ss<true, kChunk>(cohort, args, dynamic, stream);
+    else if (small) launch_ss<false, kSmallColumns>(cohort, args, dynamic, stream);
+    else launch_ss<false, kChunk>(cohort, args, dynamic, stream);
+    const uint64_t finish = d_stat ? (uint64_t)(T + 1) * (P + 1) : T + 1;
+    hipLaunchKernelGGL(model_finish_kernel, grid_of(cohort, (finish + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, sp.meta,
+                       T, P, static_cast<epik_amd_model_term *>(d_out), static_cast<double *>(d_stat));
+    HIP_TRY(hipGetLastError());
+    return EPIK_AMD_OK;
+}
+
+// a result in device memory for the synchronous entry, freed however the call ends
+struct Result {
+    void *d = nullptr;
+    ~Result()
+    {
+        if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int epik_amd_cohort_model_device(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *kind, const uint32_t *labels,
+                                 const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed, void *d_out,
+                                 void *d_info, void *d_stat, void *d_aliased, void *stream)
+{
+    try {
+        return model_device_impl(cohort, d_kr, kind, labels, values, num_terms, num_permutations, seed, d_out, d_info, d_stat, d_aliased,
+                                 static_cast<hipStream_t>(stream));
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_model_device: ") + e.what());
+    }
+}
+
+int epik_amd_cohort_model(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, const uint32_t *kind,
+                          const uint32_t *labels, const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed,
+                          epik_amd_model_term *out, epik_amd_model_info *info, double *stat, uint8_t *aliased)
+{
+    return epik_amd_cohort_model_metric(cohort, tree, branch_length, EPIK_AMD_DISTANCE_KR, kind, labels, values, num_terms,
+                                        num_permutations, seed, out, info, stat, aliased);
+}
+
+int epik_amd_cohort_model_metric(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                                 const uint32_t *kind, const uint32_t *labels, const double *values, uint32_t num_terms,
+                                 uint32_t num_permutations, uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info,
+                                 double *stat, uint8_t *aliased)
+{
+    try {
+        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+        if (const int rc = terms_valid(num_terms); rc != EPIK_AMD_OK) return rc;
+        if (!kind || !labels || !values || !out || !info || !aliased) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+        const uint32_t S = cohort->num_samples;
+        if (const int rc = check_arguments(kind, labels, values, S, num_terms, num_permutations); rc != EPIK_AMD_OK) return rc;
+        const size_t out_bytes = ((size_t)num_terms + 1) * sizeof(epik_amd_model_term);
+        const size_t stat_bytes = ((size_t)num_terms + 1) * ((size_t)num_permutations + 1) * sizeof(double);
+        HIP_TRY(hipSetDevice(cohort->device));
+        Result kr, r, s;
+        HIP_TRY(hipMalloc(&kr.d, (size_t)S * S * sizeof(double)));
+        HIP_TRY(hipMalloc(&r.d, out_bytes + sizeof(epik_amd_model_info) + kColumns));  // the records | the info block | aliased
+        if (stat) HIP_TRY(hipMalloc(&s.d, stat_bytes));
+        if (const int rc = cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr); rc != EPIK_AMD_OK) return rc;
+        char *d = static_cast<char *>(r.d);
+        if (const int rc = model_device_impl(cohort, kr.d, kind, labels, values, num_terms, num_permutations, seed, d, d + out_bytes, s.d,
+                                             d + out_bytes + sizeof(epik_amd_model_info), nullptr);
+            rc != EPIK_AMD_OK)
+            return rc;
+        HIP_TRY(hipMemcpy(out, d, out_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(info, d + out_bytes, sizeof *info, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(aliased, d + out_bytes + sizeof *info, kColumns, hipMemcpyDeviceToHost));
+        if (stat) HIP_TRY(hipMemcpy(stat, s.d, stat_bytes, hipMemcpyDeviceToHost));
+        return EPIK_AMD_OK;
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_model: ") + e.what());
+    }
+}
+
+int epik_amd_cohort_model_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                               const double *branch_length, const uint32_t *kind, const uint32_t *labels, const double *values,
+                               uint32_t num_terms, uint32_t num_permutations, uint64_t seed, epik_amd_model_term *out,
+                               epik_amd_model_info *info, double *stat, uint8_t *aliased)
+{
+    return epik_amd_cohort_model_metric_host(mass, num_samples, num_branches, first, branch_length, EPIK_AMD_DISTANCE_KR, kind, labels,
+                                             values, num_terms, num_permutations, seed, out, info, stat, aliased);
+}
+
+int epik_amd_cohort_model_metric_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                      const double *branch_length, uint32_t metric, const uint32_t *kind, const uint32_t *labels,
+                                      const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed,
+                                      epik_amd_model_term *out, epik_amd_model_info *info, double *stat, uint8_t *aliased)
+{
+    try {
+        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
+        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
+        if (const int rc = terms_valid(num_terms); rc != EPIK_AMD_OK) return rc;
+        if (!mass || !first || !branch_length || !kind || !labels || !values || !out || !info || !aliased)
+            return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+        std::string err;
+        if (const int rc = model_records(mass, num_samples, num_branches, first, branch_length, kind, labels, values, num_terms,
+                                         num_permutations, seed, out, info, stat, aliased, err, metric);
+            rc != EPIK_AMD_OK)
+            return fail_with(rc, err);
+        return EPIK_AMD_OK;
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_model_host: ") + e.what());
+    }
+}
+
+int epik_amd_cohort_model_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *kind,
+                                  const uint32_t *labels, const double *values, uint32_t num_terms, uint32_t num_permutations,
+                                  uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info, double *stat, uint8_t *aliased)
+{
+    try {
+        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
+        if (const int rc = terms_valid(num_terms); rc != EPIK_AMD_OK) return rc;
+        if (!kr || !totals || !kind || !labels || !values || !out || !info || !aliased) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+        std::string err;
+        if (const int rc = model_records_of_kr(kr, totals, num_samples, kind, labels, values, num_terms, num_permutations, seed, out, info,
+                                               stat, aliased, err);
+            rc != EPIK_AMD_OK)
+            return fail_with(rc, err);
+        return EPIK_AMD_OK;
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_model_kr_host: ") + e.what());
+    }
+}
+
+}  // extern "C"

@@ -97,12 +97,6 @@ __global__ __launch_bounds__(kBlock) void pcoa_rows_kernel(const double *__restr
     }
 }
 
-// B[i][j], i <= j, of the rule from the squared distance and the means
-__device__ inline double centred(double d, double ri, double rj, double g)
-{
-    return __dmul_rn(-0.5, __dadd_rn(__dsub_rn(__dsub_rn(__dmul_rn(d, d), ri), rj), g));
-}
-
 __global__ __launch_bounds__(kBlock) void pcoa_scale_kernel(const double *__restrict__ kr, const uint32_t *__restrict__ used,
                                                             uint32_t num_samples, uint32_t L, const double *__restrict__ r,
                                                             double *__restrict__ gs, double *__restrict__ V,
@@ -119,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void pcoa_scale_kernel(const double *__rest
         double scale = 0.0, trace = 0.0;
         for (uint32_t j = 0; j < L; ++j) {
             const uint32_t s = used[j];
-            const double b = centred(kr[(uint64_t)s * num_samples + s], r[j], r[j], g);
+            const double b = gower_centred(kr[(uint64_t)s * num_samples + s], r[j], r[j], g);
             if (fabs(b) > scale) scale = fabs(b);
             trace = __dadd_rn(trace, b);
         }
@@ -135,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void pcoa_centre_kernel(const double *__res
     const double g = gs[3];
     for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < cells; e += (uint64_t)gridDim.x * kBlock) {
         const uint32_t i = (uint32_t)(e / L), j = (uint32_t)(e - (uint64_t)i * L), lo = i < j ? i : j, hi = i < j ? j : i;
-        B[e] = centred(kr[(uint64_t)used[lo] * num_samples + used[hi]], r[lo], r[hi], g);
+        B[e] = gower_centred(kr[(uint64_t)used[lo] * num_samples + used[hi]], r[lo], r[hi], g);
     }
 }
 

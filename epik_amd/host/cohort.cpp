@@ -1451,6 +1451,213 @@ int permdisp_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_br
                                   stat, group_mean, z, err);
 }
 
+int model_arguments_valid(const uint32_t* kind, const uint32_t* labels, const double* values, uint32_t num_samples,
+                          uint32_t num_terms, uint32_t num_permutations, std::string& err)
+{
+    const size_t S = num_samples, T = num_terms;
+    if (num_terms < 1 || num_terms > EPIK_AMD_MODEL_MAX_TERMS) {
+        err = "num_terms = " + std::to_string(num_terms) + " is outside [1, 16]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if (num_permutations < 1 || num_permutations > EPIK_AMD_MODEL_MAX_PERMUTATIONS) {
+        err = "num_permutations = " + std::to_string(num_permutations) + " is outside [1, 999999]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    size_t columns = 0;
+    for (size_t t = 0; t < T; ++t) {
+        if (kind[t] > 1) {
+            err = "term " + std::to_string(t) + ": the kind " + std::to_string(kind[t]) + " is neither 0 (a factor) nor 1 (numeric)";
+            return EPIK_AMD_ERR_INVALID;
+        }
+        std::set<uint32_t> distinct;
+        for (size_t s = 0; s < S; ++s) {
+            if (kind[t]) {
+                if (std::isinf(values[s * T + t])) {
+                    err = "sample " + std::to_string(s) + ", term " + std::to_string(t) + ": the value is infinite";
+                    return EPIK_AMD_ERR_INVALID;
+                }
+                continue;
+            }
+            const uint32_t v = labels[s * T + t];
+            if (v == EPIK_AMD_MODEL_MISSING) continue;
+            if (v >= EPIK_AMD_MODEL_MAX_GROUPS) {
+                err = "sample " + std::to_string(s) + ", term " + std::to_string(t) + ": the label " + std::to_string(v) +
+                      " is not below 32";
+                return EPIK_AMD_ERR_INVALID;
+            }
+            distinct.insert(v);
+        }
+        columns += kind[t] ? 1 : distinct.empty() ? 0 : distinct.size() - 1;
+    }
+    if (columns > EPIK_AMD_MODEL_MAX_COLUMNS) {
+        err = "the design has " + std::to_string(columns) + " columns, a model takes 64 at the most";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    return EPIK_AMD_OK;
+}
+
+int model_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* kind, const uint32_t* labels,
+                        const double* values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed, epik_amd_model_term* out,
+                        epik_amd_model_info* info, double* stat, uint8_t* aliased, std::string& err)
+{
+    const size_t S = num_samples, T = num_terms, P = num_permutations;
+    if (const int rc = model_arguments_valid(kind, labels, values, num_samples, num_terms, num_permutations, err); rc != EPIK_AMD_OK)
+        return rc;
+    const double na = na_value();
+    // 1: the complete cases with mass
+    std::vector<size_t> used;
+    for (size_t s = 0; s < S; ++s) {
+        bool complete = totals[s] != 0;
+        for (size_t t = 0; t < T && complete; ++t)
+            complete = kind[t] ? !std::isnan(values[s * T + t]) : labels[s * T + t] != EPIK_AMD_MODEL_MISSING;
+        if (complete) used.push_back(s);
+    }
+    const size_t L = used.size();
+    // 2: the Gower matrix, as pcoa_components_of_kr forms it
+    std::vector<double> B(L * L, 0.0), r(L);
+    for (size_t i = 0; i < L; ++i)
+        for (size_t j = 0; j < L; ++j) {
+            const double d = kr[used[i] * S + used[j]];
+            B[i * L + j] = d * d;
+        }
+    double g = 0.0;
+    for (size_t i = 0; i < L; ++i) {
+        double acc = 0.0;
+        for (size_t j = 0; j < L; ++j) acc = acc + B[j * L + i];  // (KR[u_j][u_i], the element the device's lanes read)
+        r[i] = acc / (double)L;
+        g = g + r[i];
+    }
+    if (L) g = g / (double)L;
+    for (size_t i = 0; i < L; ++i)
+        for (size_t j = i; j < L; ++j) B[i * L + j] = B[j * L + i] = -0.5 * (((B[i * L + j] - r[i]) - r[j]) + g);
+    double ss_total = 0.0;
+    for (size_t i = 0; i < L; ++i) ss_total = ss_total + B[i * L + i];
+    // 3 and 4: the columns in term order, centred, and the basis by classical Gram-Schmidt twice
+    std::vector<std::vector<double>> Q;
+    std::vector<uint32_t> df(T + 1, 0), columns(T + 1, 0);
+    std::fill(aliased, aliased + EPIK_AMD_MODEL_MAX_COLUMNS, (uint8_t)0);
+    size_t C = 0;
+    std::vector<double> v(L), h;
+    for (size_t t = 0; t < T; ++t) {
+        std::vector<uint32_t> lam(L, 0), group_of(EPIK_AMD_MODEL_MAX_GROUPS, EPIK_AMD_MODEL_MISSING);
+        uint32_t G = 0;
+        if (!kind[t])
+            for (size_t i = 0; i < L; ++i) {
+                const uint32_t label = labels[used[i] * T + t];
+                if (group_of[label] == EPIK_AMD_MODEL_MISSING) group_of[label] = G++;
+                lam[i] = group_of[label];
+            }
+        const uint32_t width = kind[t] ? 1 : G ? G - 1 : 0;
+        for (uint32_t w = 0; w < width; ++w, ++C) {
+            ++columns[t];
+            for (size_t i = 0; i < L; ++i) v[i] = kind[t] ? values[used[i] * T + t] : lam[i] == w + 1 ? 1.0 : 0.0;
+            double n0 = 0.0;
+            if (L) {
+                double acc = 0.0;
+                for (size_t i = 0; i < L; ++i) acc = acc + v[i];
+                const double mean = acc / (double)L;
+                for (size_t i = 0; i < L; ++i) v[i] = v[i] - mean, n0 = n0 + v[i] * v[i];
+            }
+            for (int pass = 0; pass < 2; ++pass) {
+                h.assign(Q.size(), 0.0);
+                for (size_t k = 0; k < Q.size(); ++k)
+                    for (size_t i = 0; i < L; ++i) h[k] = h[k] + Q[k][i] * v[i];
+                for (size_t i = 0; i < L; ++i)
+                    for (size_t k = 0; k < Q.size(); ++k) v[i] = v[i] - h[k] * Q[k][i];
+            }
+            double n1 = 0.0;
+            for (size_t i = 0; i < L; ++i) n1 = n1 + v[i] * v[i];
+            if (n0 > 0.0 && n1 > std::ldexp(1.0, -40) * n0) {
+                const double root = std::sqrt(n1);
+                Q.emplace_back(L);
+                for (size_t i = 0; i < L; ++i) Q.back()[i] = v[i] / root;
+                ++df[t];
+            } else {
+                aliased[C] = 1;
+            }
+        }
+    }
+    const size_t R = Q.size();
+    df[T] = (uint32_t)R, columns[T] = (uint32_t)C;
+    const int64_t df_res = (int64_t)L - 1 - (int64_t)R;
+    // 5: SS_k of an arrangement into ss[T + 1], the model's last
+    std::vector<double> tc(L);
+    const auto sums = [&](const std::vector<uint32_t>& sigma, std::vector<double>& ss) {
+        size_t c = 0;
+        double model = 0.0;
+        for (size_t t = 0; t < T; ++t) {
+            double term = 0.0;
+            for (uint32_t w = 0; w < df[t]; ++w, ++c) {
+                const std::vector<double>& q = Q[c];
+                double s = 0.0;
+                for (size_t i = 0; i < L; ++i) {
+                    double acc = 0.0;
+                    const double* row = B.data() + i * L;
+                    for (size_t j = 0; j < L; ++j) acc = acc + row[j] * q[sigma[j]];
+                    s = s + q[sigma[i]] * acc;
+                }
+                term = term + s;
+            }
+            ss[t] = term;
+            model = model + term;
+        }
+        ss[T] = model;
+    };
+    std::vector<uint32_t> sigma(L);
+    for (size_t i = 0; i < L; ++i) sigma[i] = (uint32_t)i;
+    std::vector<double> ss0(T + 1), ss(T + 1), f0(T + 1, na);
+    sums(sigma, ss0);
+    const double ss_res = ss_total - ss0[T];
+    *info = epik_amd_model_info{(uint32_t)L, (uint32_t)T, (uint32_t)C, (uint32_t)R, df_res, ss_total, ss_res};
+    const bool testable = df_res >= 1 && ss_res > 0.0;
+    if (stat) std::fill(stat, stat + (T + 1) * (P + 1), na);
+    for (size_t k = 0; k <= T; ++k) {
+        out[k] = epik_amd_model_term{df[k], columns[k], 0, na, na, na, na};
+        if (!df[k]) continue;
+        out[k].ss = ss0[k];
+        if (ss_total > 0.0) out[k].r2 = ss0[k] / ss_total;
+        if (testable) out[k].f = f0[k] = (ss0[k] / (double)df[k]) / (ss_res / (double)df_res);
+        if (testable && stat) stat[k * (P + 1)] = f0[k];
+    }
+    if (!testable || !R) return EPIK_AMD_OK;
+    // 6 and 7: the permutations
+    std::vector<std::pair<uint64_t, uint32_t>> keys(L);
+    for (uint32_t p = 1; p <= P; ++p) {
+        for (uint32_t i = 0; i < L; ++i) keys[i] = {permanova_key(seed, p, i), i};
+        std::sort(keys.begin(), keys.end());
+        for (size_t rank = 0; rank < L; ++rank) sigma[keys[rank].second] = (uint32_t)rank;
+        sums(sigma, ss);
+        const double res = ss_total - ss[T];
+        for (size_t k = 0; k <= T; ++k) {
+            if (!df[k]) continue;
+            const double f = res > 0.0 ? (ss[k] / (double)df[k]) / (res / (double)df_res) : HUGE_VAL;
+            if (stat) stat[k * (P + 1) + p] = f;
+            out[k].at_least += f >= f0[k];
+        }
+    }
+    for (size_t k = 0; k <= T; ++k)
+        if (df[k]) out[k].p = (double)(1 + out[k].at_least) / (double)(P + 1);
+    return EPIK_AMD_OK;
+}
+
+int model_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                  const double* branch_length, const uint32_t* kind, const uint32_t* labels, const double* values, uint32_t num_terms,
+                  uint32_t num_permutations, uint64_t seed, epik_amd_model_term* out, epik_amd_model_info* info, double* stat,
+                  uint8_t* aliased, std::string& err, uint32_t metric)
+{
+    const size_t S = num_samples, N = num_branches;
+    if (const int rc = model_arguments_valid(kind, labels, values, num_samples, num_terms, num_permutations, err); rc != EPIK_AMD_OK)
+        return rc;
+    std::vector<double> kr(S * S);
+    if (const int rc = distance_matrix(mass, num_samples, num_branches, first, branch_length, metric, kr.data(), err); rc != EPIK_AMD_OK)
+        return rc;
+    std::vector<uint64_t> totals(S, 0);
+    for (size_t s = 0; s < S; ++s)
+        for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
+    return model_records_of_kr(kr.data(), totals.data(), num_samples, kind, labels, values, num_terms, num_permutations, seed, out, info,
+                               stat, aliased, err);
+}
+
 cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise, size_t most_labels,
                                    const char* flag)
 {
@@ -1516,6 +1723,98 @@ cohort_factors read_cohort_factors(const std::string& file, const std::vector<co
     for (size_t s = 0; s < samples.size(); ++s)
         if (!seen[s]) throw std::runtime_error(std::string(flag) + ": " + file + " has no line for the sample '" + samples[s].name + "'");
     return factors;
+}
+
+cohort_design read_cohort_design(const std::string& file, const std::string& terms, const std::vector<cohort_sample>& samples)
+{
+    const std::string flag = "--cohort-model";
+    cohort_design design;
+    // the terms: f:NAME or n:NAME, comma-separated, in test order
+    for (size_t at = 0; at <= terms.size();) {
+        const size_t comma = std::min(terms.find(',', at), terms.size());
+        const std::string term = terms.substr(at, comma - at);
+        at = comma + 1;
+        const std::string where = "--cohort-model-terms: term " + std::to_string(design.terms.size() + 1) + " ('" + term + "')";
+        if (term.size() < 3 || term[1] != ':' || (term[0] != 'f' && term[0] != 'n'))
+            throw std::runtime_error(where + " is not f:NAME (a factor) or n:NAME (numeric)");
+        const std::string name = term.substr(2);
+        if (std::find(design.terms.begin(), design.terms.end(), name) != design.terms.end())
+            throw std::runtime_error(where + ": the column '" + name + "' is given twice");
+        if (design.terms.size() == EPIK_AMD_MODEL_MAX_TERMS) throw std::runtime_error("--cohort-model-terms: more than 16 terms");
+        design.terms.push_back(name), design.kind.push_back(term[0] == 'n');
+    }
+    const size_t T = design.terms.size();
+    std::ifstream in(file);
+    if (!in) throw std::runtime_error(flag + ": cannot open the design file " + file);
+    std::map<std::string, size_t> index;
+    for (size_t s = 0; s < samples.size(); ++s) index[samples[s].name] = s;
+    design.names.resize(T);
+    design.labels.assign(samples.size() * T, EPIK_AMD_MODEL_MISSING);
+    design.values.assign(samples.size() * T, std::nan(""));
+    std::vector<size_t> seen(samples.size(), 0), field_of(T, 0);  // the line that gave the sample; the field of a term
+    std::vector<std::map<std::string, uint32_t>> id_of(T);
+    size_t fields_a_line = 0;
+    std::string line;
+    for (size_t number = 1; std::getline(in, line); ++number) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        const std::string where = flag + ": " + file + " line " + std::to_string(number);
+        const auto fields = split_tabs(line);
+        if (!fields_a_line) {
+            if (fields[0] != "sample") throw std::runtime_error(where + ": the header must begin with 'sample'");
+            if (fields.size() < 2) throw std::runtime_error(where + ": the header names no column");
+            std::set<std::string> names;
+            for (size_t c = 1; c < fields.size(); ++c) {
+                if (fields[c].empty()) throw std::runtime_error(where + ": column " + std::to_string(c) + " has an empty name");
+                if (!names.insert(fields[c]).second)
+                    throw std::runtime_error(where + ": the column name '" + fields[c] + "' is given twice");
+            }
+            for (size_t t = 0; t < T; ++t) {
+                const auto found = std::find(fields.begin() + 1, fields.end(), design.terms[t]);
+                if (found == fields.end())
+                    throw std::runtime_error(where + ": the header has no column '" + design.terms[t] + "' (term " + std::to_string(t + 1) +
+                                             " of --cohort-model-terms)");
+                field_of[t] = (size_t)(found - fields.begin());
+            }
+            fields_a_line = fields.size();
+            continue;
+        }
+        if (fields.size() != fields_a_line)
+            throw std::runtime_error(where + ": " + std::to_string(fields.size()) + " fields, not " + std::to_string(fields_a_line));
+        const auto found = index.find(fields[0]);
+        if (found == index.end()) {
+            ++design.skipped;
+            continue;
+        }
+        const size_t s = found->second;
+        if (seen[s])
+            throw std::runtime_error(where + ": the sample '" + fields[0] + "' is given twice (first on line " +
+                                     std::to_string(seen[s]) + ")");
+        seen[s] = number;
+        for (size_t t = 0; t < T; ++t) {
+            const std::string& v = fields[field_of[t]];
+            if (v.empty() || v == "NA") continue;
+            const std::string at = where + ", column " + design.terms[t] + ": ";
+            if (design.kind[t]) {
+                if (!is_number(v)) throw std::runtime_error(at + "'" + v + "' is not a number, empty or NA");
+                const double value = std::strtod(v.c_str(), nullptr);
+                if (std::isinf(value)) throw std::runtime_error(at + "'" + v + "' overflows a double");
+                design.values[s * T + t] = value;
+                continue;
+            }
+            const auto [it, fresh] = id_of[t].emplace(v, (uint32_t)design.names[t].size());
+            if (fresh) {
+                if (design.names[t].size() == EPIK_AMD_MODEL_MAX_GROUPS)
+                    throw std::runtime_error(at + "'" + v + "' is label number 33, more than 32");
+                design.names[t].push_back(v);
+            }
+            design.labels[s * T + t] = it->second;
+        }
+    }
+    if (!fields_a_line) throw std::runtime_error(flag + ": " + file + " has no header line");
+    for (size_t s = 0; s < samples.size(); ++s)
+        if (!seen[s]) throw std::runtime_error(flag + ": " + file + " has no line for the sample '" + samples[s].name + "'");
+    return design;
 }
 
 std::vector<cohort_sample> read_cohort_list(const std::string& list_file)
@@ -2029,6 +2328,73 @@ std::string format_permdisp_tsv(const std::vector<cohort_sample>& samples, const
             if (totals[s] == 0 || v == EPIK_AMD_PERMDISP_MISSING) continue;
             out += columns[c] + '\t' + samples[s].name + '\t' + names[c][v] + '\t' + g17_or_na(z[c * S + s]) + '\n';
         }
+    return out;
+}
+
+std::string format_model_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, const cohort_design& design,
+                             uint32_t num_permutations, uint64_t seed, const epik_amd_model_term* records,
+                             const epik_amd_model_info& info, const uint8_t* aliased, uint32_t distance)
+{
+    const size_t S = samples.size(), T = design.terms.size();
+    std::string out = "# epik_amd model v1  samples=" + std::to_string(S) + " used=" + std::to_string(info.used) +
+                      " terms=" + std::to_string(T) + " columns=" + std::to_string(info.columns) + " rank=" + std::to_string(info.rank) +
+                      " permutations=" + std::to_string(num_permutations) + " seed=" + std::to_string(seed) + distance_field(distance) + "\n";
+    for (size_t s = 0; s < S; ++s)
+        if (totals[s] == 0) out += "# unused\t" + samples[s].name + "\n";
+    const auto lacks = [&](size_t s, size_t t) {
+        return design.kind[t] ? std::isnan(design.values[s * T + t]) : design.labels[s * T + t] == EPIK_AMD_MODEL_MISSING;
+    };
+    std::vector<size_t> used;
+    for (size_t s = 0; s < S; ++s) {
+        if (totals[s] == 0) continue;
+        size_t t = 0;
+        while (t < T && !lacks(s, t)) ++t;
+        if (t == T)
+            used.push_back(s);
+        else
+            out += "# incomplete\t" + samples[s].name + "\t" + design.terms[t] + "\n";
+    }
+    for (size_t t = 0; t < T; ++t)
+        out += "# term\t" + std::to_string(t) + (design.kind[t] ? "\tn\t" : "\tf\t") + design.terms[t] + "\t" +
+               std::to_string(records[t].columns) + "\t" + std::to_string(records[t].df) + "\n";
+    // the groups of the factor terms in the rule's order, and the label of every column
+    std::vector<std::string> column_label;
+    std::vector<size_t> column_term;
+    std::string groups;
+    for (size_t t = 0; t < T; ++t) {
+        if (design.kind[t]) {
+            column_label.push_back("-"), column_term.push_back(t);
+            continue;
+        }
+        std::vector<uint32_t> order, size_of(EPIK_AMD_MODEL_MAX_GROUPS, 0);
+        for (const size_t s : used) {
+            const uint32_t v = design.labels[s * T + t];
+            if (v >= EPIK_AMD_MODEL_MAX_GROUPS) continue;
+            if (!size_of[v]) order.push_back(v);
+            ++size_of[v];
+        }
+        for (size_t g = 0; g < order.size(); ++g) {
+            groups += "# group\t" + std::to_string(t) + "\t" + std::to_string(g) + "\t" + design.names[t][order[g]] + "\t" +
+                      std::to_string(size_of[order[g]]) + "\n";
+            if (g) column_label.push_back(design.names[t][order[g]]), column_term.push_back(t);
+        }
+    }
+    out += groups;
+    for (size_t c = 0; c < column_label.size() && c < EPIK_AMD_MODEL_MAX_COLUMNS; ++c)
+        if (aliased[c]) out += "# aliased\t" + std::to_string(column_term[c]) + "\t" + column_label[c] + "\n";
+    out += "term\tdf\tss\tr2\tf\tat_least\tp\n";
+    double rest = 1.0;
+    for (size_t k = 0; k <= T; ++k) {
+        const epik_amd_model_term& r = records[k];
+        out += (k < T ? design.terms[k] : std::string("model")) + "\t" + std::to_string(r.df) + "\t" + g17_or_na(r.ss) + "\t" +
+               g17_or_na(r.r2) + "\t" + g17_or_na(r.f) + "\t" + (std::isnan(r.p) ? std::string("NA") : std::to_string(r.at_least)) + "\t" +
+               g17_or_na(r.p) + "\n";
+        if (k < T && r.df && !std::isnan(r.r2)) rest = rest - r.r2;
+    }
+    const bool total = info.ss_total > 0.0;
+    out += "residual\t" + std::to_string(info.df_res) + "\t" + g17(info.ss_res) + "\t" + (total ? g17(rest) : std::string("NA")) +
+           "\tNA\tNA\tNA\n";
+    out += "total\t" + std::to_string((int64_t)info.used - 1) + "\t" + g17(info.ss_total) + "\t" + (total ? "1" : "NA") + "\tNA\tNA\tNA\n";
     return out;
 }
 

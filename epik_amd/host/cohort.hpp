@@ -158,6 +158,24 @@ int permdisp_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_br
                      uint64_t seed, bool pairwise, epik_amd_permdisp* out, double* stat, double* group_mean, double* z, std::string& err,
                      uint32_t metric = EPIK_AMD_DISTANCE_KR);
 
+/// num_terms in [1, 16], every kind 0 or 1, num_permutations in [1, 999 999], every label of a factor term below 32 or
+/// 0xffffffff (missing), no infinite value of a numeric term, and at most 64 columns as the rule counts them: 0, or
+/// EPIK_AMD_ERR_INVALID with `err` naming the cause
+int model_arguments_valid(const uint32_t* kind, const uint32_t* labels, const double* values, uint32_t num_samples,
+                          uint32_t num_terms, uint32_t num_permutations, std::string& err);
+/// The sequential model by the rule (include/epik_amd.h) from the matrix kr[S][S] and totals[S], one thread: out[T + 1], *info,
+/// aliased[64] and, where not null, stat[T + 1][P + 1], every cell written.  libepik_amd's kernels (model_place.hip) give the
+/// same bits.  The code behind epik_amd_cohort_model_kr_host.  0, or as model_arguments_valid.
+int model_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* kind, const uint32_t* labels,
+                        const double* values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed, epik_amd_model_term* out,
+                        epik_amd_model_info* info, double* stat, uint8_t* aliased, std::string& err);
+/// The same from mass[S][N]: the matrix by distance_matrix first.  The code behind epik_amd_cohort_model_host and
+/// _model_metric_host.
+int model_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                  const double* branch_length, const uint32_t* kind, const uint32_t* labels, const double* values, uint32_t num_terms,
+                  uint32_t num_permutations, uint64_t seed, epik_amd_model_term* out, epik_amd_model_info* info, double* stat,
+                  uint8_t* aliased, std::string& err, uint32_t metric = EPIK_AMD_DISTANCE_KR);
+
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
 /// name or path, a name given before, or a file that cannot be read; and for a list without any sample.
@@ -194,8 +212,26 @@ struct cohort_factors {
 cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise,
                                    size_t most_labels = 0, const char* flag = "--cohort-permanova");
 
+/// The design of --cohort-model: FILE is a TSV in the layout of the factor file, `terms` the LIST of --cohort-model-terms, a
+/// comma-separated f:NAME (a factor) or n:NAME (numeric) per term in test order, NAME a column of FILE.  Cells are text by the
+/// factor reader's rules (empty or NA is missing); a numeric term's cells are numbers by the metadata reader's rule.  The labels
+/// of a factor term are numbered by first appearance in the file among the list's samples: names[t][id].  Throws
+/// std::runtime_error for an empty list, more than 16 terms, a prefix other than f: or n:, a term given twice, a column the
+/// header lacks, and, naming the line and the column, for a cell of a numeric term that is no number or overflows, a factor
+/// term with more than 32 labels, a wrong field count or a sample given twice; and naming the sample of the list that the
+/// file lacks.  A line whose name is not in the list is skipped and counted.
+struct cohort_design {
+    std::vector<std::string> terms;               // [T]: the column names
+    std::vector<uint32_t> kind;                   // [T]: 0 a factor, 1 numeric
+    std::vector<std::vector<std::string>> names;  // [T]: the labels of a factor term by id
+    std::vector<uint32_t> labels;                 // [S][T], in the order of the list
+    std::vector<double> values;                   // [S][T]
+    size_t skipped = 0;
+};
+cohort_design read_cohort_design(const std::string& file, const std::string& terms, const std::vector<cohort_sample>& samples);
+
 /// <output_dir>/cohort_<what>_<basename(list)><extension>, what = samples | profile | kr | squash | epca | epca_edges | pcoa | kmeans |
-/// kmeans_centroids | alpha | rarefy | correlation | dispersion | permanova | edgetest | permdisp | unifrac_<metric>
+/// kmeans_centroids | alpha | rarefy | correlation | dispersion | permanova | edgetest | permdisp | model | unifrac_<metric>
 std::string make_cohort_filename(const std::string& what, const std::string& list_file, const std::string& output_dir,
                                  const std::string& extension = ".tsv");
 
@@ -303,6 +339,16 @@ std::string format_permdisp_tsv(const std::vector<cohort_sample>& samples, const
                                 const uint32_t* labels, uint32_t num_permutations, uint64_t seed, bool pairwise,
                                 const epik_amd_permdisp* records, const double* group_mean, const double* z,
                                 uint32_t distance = EPIK_AMD_DISTANCE_KR);
+/// cohort_model .tsv: "# epik_amd model v1  samples=S used=L terms=T columns=C rank=R permutations=P seed=X" (L the complete
+/// cases with mass), a "# unused<TAB>name" line per sample without mass, a "# incomplete<TAB>name<TAB>term" line per sample with
+/// mass that lacks a value (the first term it lacks), a "# term<TAB>k<TAB>f|n<TAB>name<TAB>columns<TAB>df" line per term, a
+/// "# group<TAB>k<TAB>g<TAB>label<TAB>n" line per group of a factor term (the groups in the rule's order), a "# aliased<TAB>k<TAB>label
+/// or -" line per dropped column, the column names term df ss r2 f at_least p, a line per term in order, then model, residual
+/// (df_res, ss_res, and 1 less the r2 of every term with a column, one subtraction chain in term order) and total (L - 1,
+/// ss_total, 1); doubles %.17g, NA where undefined.  Over a `distance` other than KR the first line ends in distance_field(distance).
+std::string format_model_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, const cohort_design& design,
+                             uint32_t num_permutations, uint64_t seed, const epik_amd_model_term* records,
+                             const epik_amd_model_info& info, const uint8_t* aliased, uint32_t distance = EPIK_AMD_DISTANCE_KR);
 /// `text` into `filename` through `filename`.part, renamed when all of it is written
 void write_through_part(const std::string& filename, const std::string& text);
 

@@ -43,6 +43,13 @@
 //   cohort_test edgetest-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed>
 //                                           the file of --cohort-edge-test for a `kr` input whose samples are named by the
 //                                           lines of names.txt, through the factor file's reader and the formatter
+//   cohort_test model <out.bin> <in.bin> <design.bin> <P> <seed>
+//                                           the sequential model of a `kr` input with a `design` file, uint64 T, uint32 kind[T],
+//                                           uint32 labels[S][T], float64 values[S][T]: epik_amd_model_term [T + 1],
+//                                           epik_amd_model_info, float64 stat[T + 1][P + 1], uint8 aliased[64]
+//   cohort_test model-tsv <out.tsv> <in.bin> <names.txt> <design.tsv> <terms> <P> <seed>
+//                                           the file of --cohort-model for a `kr` input whose samples are named by the lines of
+//                                           names.txt, through the design file's reader and the formatter
 // An `add` input holds, little endian: uint64 n, keep, num_branches, num_samples; epik_amd_placement rows[n][keep];
 // uint32 n_rows[n]; uint32 kmer_counts[n][keep]; uint32 weights[n]; uint32 samples[n].
 // A `kr` input: uint64 num_samples, num_branches; uint64 mass[S][N]; uint32 first[N]; float64 branch_length[N].
@@ -462,6 +469,76 @@ int main(int argc, char** argv)
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }
+        if (argc == 9 && std::strcmp(argv[1], "model-tsv") == 0) {
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto cells = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const auto lengths = read_array<double>(in, N);
+            const uint32_t P = (uint32_t)std::strtoul(argv[7], nullptr, 10);
+            const uint64_t seed = std::strtoull(argv[8], nullptr, 10);
+            std::vector<epik_amd::cohort_sample> samples;
+            std::ifstream names(argv[4]);
+            if (!names) throw std::runtime_error(std::string("cannot open ") + argv[4]);
+            for (std::string line; std::getline(names, line);) samples.push_back({line, ""});
+            if (samples.size() != S) throw std::runtime_error("the names file does not name every sample");
+            const epik_amd::cohort_design design = epik_amd::read_cohort_design(argv[5], argv[6], samples);
+            std::cout << "Cohort model design: " << design.terms.size() << " terms, " << design.skipped
+                      << " lines of samples that are not in the list skipped" << std::endl;
+            const size_t T = design.terms.size();
+            std::vector<epik_amd_model_term> records(T + 1);
+            epik_amd_model_info info{};
+            std::vector<uint8_t> aliased(EPIK_AMD_MODEL_MAX_COLUMNS);
+            std::string err;
+            if (epik_amd::model_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), lengths.data(), design.kind.data(),
+                                        design.labels.data(), design.values.data(), (uint32_t)T, P, seed, records.data(), &info, nullptr,
+                                        aliased.data(), err) != 0)
+                throw std::runtime_error(err);
+            std::vector<uint64_t> totals(S, 0);
+            for (uint64_t s = 0; s < S; ++s)
+                for (uint64_t b = 0; b < N; ++b) totals[s] += cells[s * N + b];
+            epik_amd::write_through_part(argv[2], epik_amd::format_model_tsv(samples, totals.data(), design, P, seed, records.data(), info,
+                                                                             aliased.data()));
+            return 0;
+        }
+        if (argc == 7 && std::strcmp(argv[1], "model") == 0) {
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto cells = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const auto lengths = read_array<double>(in, N);
+            const uint32_t P = (uint32_t)std::strtoul(argv[5], nullptr, 10);
+            const uint64_t seed = std::strtoull(argv[6], nullptr, 10);
+            std::ifstream design(argv[4], std::ios::binary);
+            if (!design) throw std::runtime_error(std::string("cannot open ") + argv[4]);
+            const uint64_t T = read_array<uint64_t>(design, 1)[0];
+            if (T < 1 || T > EPIK_AMD_MODEL_MAX_TERMS) throw std::runtime_error("the design file has a number of terms outside [1, 16]");
+            if (P < 1 || P > EPIK_AMD_MODEL_MAX_PERMUTATIONS) throw std::runtime_error("P is outside [1, 999999]");
+            const auto kind = read_array<uint32_t>(design, T);
+            const auto labels = read_array<uint32_t>(design, S * T);
+            const auto values = read_array<double>(design, S * T);
+            std::vector<epik_amd_model_term> records(T + 1);
+            epik_amd_model_info info{};
+            std::vector<double> stat((T + 1) * ((uint64_t)P + 1));
+            std::vector<uint8_t> aliased(EPIK_AMD_MODEL_MAX_COLUMNS);
+            std::string err;
+            if (epik_amd::model_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), lengths.data(), kind.data(), labels.data(),
+                                        values.data(), (uint32_t)T, P, seed, records.data(), &info, stat.data(), aliased.data(), err) != 0)
+                throw std::runtime_error(err);
+            std::ofstream out(argv[2], std::ios::binary);
+            write_array(out, records.data(), records.size());
+            write_array(out, &info, 1);
+            write_array(out, stat.data(), stat.size());
+            write_array(out, aliased.data(), aliased.size());
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
         std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin> | squash <out.bin> <in.bin> | "
                      "epca <out.bin> <in.bin> <K> | pcoa <out.bin> <in.bin> <K> | pcoa-tsv <out.tsv> <in.bin> <names.txt> <K> | kmeans <out.bin> <in.bin> <K> <max_iterations> | alpha <out.bin> <in.bin> | "
                      "rarefy <out.bin> <in.bin> <depth_step> <num_depths> | correlation <out.bin> <in.bin> <meta.bin> | "
@@ -470,7 +547,9 @@ int main(int argc, char** argv)
                      "permdisp <out.bin> <in.bin> <labels.bin> <P> <seed> <pairwise> | "
                      "permdisp-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed> <pairwise> | "
                      "edgetest <out.bin> <in.bin> <labels.bin> <P> <seed> | "
-                     "edgetest-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed>\n";
+                     "edgetest-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed> | "
+                     "model <out.bin> <in.bin> <design.bin> <P> <seed> | "
+                     "model-tsv <out.tsv> <in.bin> <names.txt> <design.tsv> <terms> <P> <seed>\n";
         return 2;
     } catch (const std::exception& error) {
         std::cerr << "Error: " << error.what() << std::endl;

@@ -278,6 +278,13 @@ const char* kHelp =
     "      --cohort-permdisp-permutations arg  With --cohort-permdisp: the number of permutations in [1, 999999] (default: 999)\n"
     "      --cohort-permdisp-seed arg  With --cohort-permdisp: the seed of the permutations, a uint64 (default: 1)\n"
     "      --cohort-permdisp-pairwise  With --cohort-permdisp: also test every two groups of every column\n"
+    "      --cohort-model arg     With --cohort: also fit, on the device, the sequential model adonis2(D ~ term1 + term2 + ...,\n"
+    "                          by = \"terms\") over the columns of the TSV file arg (as --cohort-permanova's) that\n"
+    "                          --cohort-model-terms names; cohort_model_<list>.tsv\n"
+    "      --cohort-model-terms arg  With --cohort-model (required): the terms in test order, comma-separated f:NAME (a factor)\n"
+    "                          or n:NAME (a numeric covariate); at most 16 terms and 64 design columns\n"
+    "      --cohort-model-permutations arg  With --cohort-model: the number of permutations in [1, 999999] (default: 999)\n"
+    "      --cohort-model-seed arg  With --cohort-model: the seed of the permutations, a uint64 (default: 1)\n"
     "      --cohort-edge-test arg  With --cohort: also test, for every factor column of the TSV file arg (as --cohort-permanova's,\n"
     "                          at most 32 labels a column), on which branches its groups of samples differ: the one-way ANOVA and\n"
     "                          Kruskal-Wallis of every branch's mass and imbalance by permutation, with the max-statistic\n"
@@ -568,6 +575,33 @@ int main(int argc, char** argv)
             if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-permdisp-seed " + text + ": not a uint64");
             permdisp_seed = v;
         }
+        const bool with_model = parsed.has("cohort-model");
+        if (with_model && !with_cohort)
+            throw std::runtime_error("--cohort-model needs --cohort (it fits a model of the samples of the list)");
+        for (const char* dependent : {"cohort-model-terms", "cohort-model-permutations", "cohort-model-seed"})
+            if (parsed.has(dependent) && !with_model)
+                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-model" +
+                                         (with_cohort ? "" : " (and that needs --cohort )"));
+        if (with_model && !parsed.has("cohort-model-terms"))
+            throw std::runtime_error("--cohort-model needs --cohort-model-terms (the terms of the model, f:NAME or n:NAME, in test order)");
+        uint32_t model_permutations = 999;
+        uint64_t model_seed = 1;
+        if (parsed.has("cohort-model-permutations")) {
+            const std::string text = parsed.require("cohort-model-permutations");
+            char* end = nullptr;
+            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
+            if (!end || *end || v < 1 || v > EPIK_AMD_MODEL_MAX_PERMUTATIONS)
+                throw std::runtime_error("--cohort-model-permutations " + text + ": the number must lie in [1, 999999]");
+            model_permutations = (uint32_t)v;
+        }
+        if (parsed.has("cohort-model-seed")) {
+            const std::string text = parsed.require("cohort-model-seed");
+            char* end = nullptr;
+            errno = 0;
+            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
+            if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-model-seed " + text + ": not a uint64");
+            model_seed = v;
+        }
         // --cohort-unifrac / --cohort-distance: checked before anything is opened or any device touched
         const bool with_unifrac = parsed.has("cohort-unifrac");
         if (with_unifrac && !with_cohort)
@@ -576,9 +610,9 @@ int main(int argc, char** argv)
             with_unifrac ? epik_amd::parse_unifrac_list(parsed.require("cohort-unifrac")) : std::vector<uint32_t>{};
         uint32_t cohort_distance = EPIK_AMD_DISTANCE_KR;
         if (parsed.has("cohort-distance")) {
-            if (!with_permanova && !with_pcoa && !with_permdisp)
+            if (!with_permanova && !with_pcoa && !with_permdisp && !with_model)
                 throw std::runtime_error("--cohort-distance needs --cohort-permanova, --cohort-pcoa or --cohort-permdisp (the analyses that "
-                                         "run over a distance)");
+                                         "run over a distance; --cohort-model is one too)");
             const std::string name = parsed.require("cohort-distance");
             cohort_distance = epik_amd::distance_of_name(name, true);
             if (cohort_distance == 0xffffffffu)
@@ -683,6 +717,14 @@ int main(int argc, char** argv)
             disp_factors = epik_amd::read_cohort_factors(parsed.require("cohort-permdisp"), cohort_samples, false,
                                                          EPIK_AMD_PERMDISP_MAX_GROUPS, "--cohort-permdisp");
             std::cout << "Cohort PERMDISP factors: " << disp_factors.columns.size() << " columns, " << disp_factors.skipped
+                      << " lines of samples that are not in the list skipped" << std::endl;
+        }
+
+        // --cohort-model: the design read, and every error of it named by its line and column, before the database or a device is
+        epik_amd::cohort_design design;
+        if (with_model) {
+            design = epik_amd::read_cohort_design(parsed.require("cohort-model"), parsed.require("cohort-model-terms"), cohort_samples);
+            std::cout << "Cohort model design: " << design.terms.size() << " terms, " << design.skipped
                       << " lines of samples that are not in the list skipped" << std::endl;
         }
 
@@ -1076,6 +1118,8 @@ int main(int argc, char** argv)
         const auto cohort_permanova_filename = epik_amd::make_cohort_filename("permanova", query_file, output_dir);
         const auto cohort_edgetest_filename = epik_amd::make_cohort_filename("edgetest", query_file, output_dir);
         const auto cohort_permdisp_filename = epik_amd::make_cohort_filename("permdisp", query_file, output_dir);
+        const auto cohort_model_filename = epik_amd::make_cohort_filename("model", query_file, output_dir);
+        size_t model_aliased = 0;
         const auto cohort_unifrac_filename = [&](uint32_t metric) {
             return epik_amd::make_cohort_filename(std::string("unifrac_") + epik_amd::distance_name(metric), query_file, output_dir);
         };
@@ -1108,12 +1152,16 @@ int main(int argc, char** argv)
             permdisp.num_permutations = permdisp_permutations, permdisp.seed = permdisp_seed, permdisp.pairwise = permdisp_pairwise;
             epik_amd::placer::cohort_unifrac unifrac;
             unifrac.metrics = unifrac_metrics, unifrac.distance = cohort_distance;
+            epik_amd::placer::cohort_model model;
+            model.kind = design.kind.data(), model.labels = design.labels.data(), model.values = design.values.data();
+            model.num_terms = (uint32_t)design.terms.size(), model.num_permutations = model_permutations, model.seed = model_seed;
             placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
                                with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr, with_kmeans ? &kmeans : nullptr,
                                with_alpha || with_rarefy ? &diversity : nullptr, with_correlation || with_dispersion ? &edges : nullptr,
                                with_permanova ? &permanova : nullptr, with_edgetest ? &edgetest : nullptr, with_pcoa ? &pcoa : nullptr,
                                with_permdisp ? &permdisp : nullptr,
-                               with_unifrac || cohort_distance != EPIK_AMD_DISTANCE_KR ? &unifrac : nullptr);
+                               with_unifrac || cohort_distance != EPIK_AMD_DISTANCE_KR ? &unifrac : nullptr,
+                               with_model ? &model : nullptr);
             for (size_t i = 0; i < unifrac_metrics.size(); ++i)
                 epik_amd::write_through_part(cohort_unifrac_filename(unifrac_metrics[i]),
                                              epik_amd::format_cohort_unifrac_tsv(cohort_samples, unifrac.matrix[i]));
@@ -1196,6 +1244,16 @@ int main(int argc, char** argv)
                                                                            permdisp.z.data(), cohort_distance));
                 const size_t slots = permdisp.records.size() / disp_factors.columns.size();
                 for (size_t c = 0; c < disp_factors.columns.size(); ++c) permdisp_clipped += permdisp.records[c * slots].clipped;
+            }
+            if (with_model) {
+                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
+                for (size_t s = 0; s < mass_of.size(); ++s)
+                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
+                epik_amd::write_through_part(cohort_model_filename,
+                                             epik_amd::format_model_tsv(cohort_samples, mass_of.data(), design, model_permutations, model_seed,
+                                                                        model.records.data(), model.info, model.aliased.data(),
+                                                                        cohort_distance));
+                for (const uint8_t byte : model.aliased) model_aliased += byte;
             }
             if (with_pcoa) {
                 std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
@@ -1286,6 +1344,10 @@ int main(int argc, char** argv)
         if (with_permanova) std::cout << "Cohort PERMANOVA: " << cohort_permanova_filename << std::endl;
         if (with_edgetest) std::cout << "Cohort edge test: " << cohort_edgetest_filename << std::endl;
         if (with_permdisp) std::cout << "Cohort PERMDISP: " << cohort_permdisp_filename << std::endl;
+        if (with_model) std::cout << "Cohort model: " << cohort_model_filename << std::endl;
+        if (model_aliased)
+            std::cout << "Warning: " << model_aliased << " columns of the design are explained by the columns before them and were "
+                      << "dropped (the # aliased lines of " << cohort_model_filename << ")" << std::endl;
         if (permdisp_clipped)
             std::cout << "Warning: " << permdisp_clipped << " squared distances to a group centroid are negative (the "
                       << (cohort_distance == EPIK_AMD_DISTANCE_KR ? "KR" : epik_amd::distance_name(cohort_distance)) << " distance is not "

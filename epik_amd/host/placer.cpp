@@ -46,6 +46,7 @@
 #pragma weak epik_amd_cohort_permanova_metric
 #pragma weak epik_amd_cohort_pcoa_metric
 #pragma weak epik_amd_cohort_permdisp_metric
+#pragma weak epik_amd_cohort_model_metric
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -301,8 +302,10 @@ void placer::read_taxonomy(uint64_t* direct, uint64_t* assigned, epik_amd_taxa_t
 void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                          epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans,
                          cohort_diversity* diversity, cohort_edges* edges, cohort_permanova* permanova,
-                         cohort_edgetest* edgetest, cohort_pcoa* pcoa, cohort_permdisp* permdisp, cohort_unifrac* unifrac)
+                         cohort_edgetest* edgetest, cohort_pcoa* pcoa, cohort_permdisp* permdisp, cohort_unifrac* unifrac,
+                         cohort_model* model)
 {
+    if (model && !&epik_amd_cohort_model_metric) throw std::runtime_error("GPU placer: this libepik_amd has no sequential model");
     const uint32_t distance = unifrac ? unifrac->distance : EPIK_AMD_DISTANCE_KR;
     if (unifrac && (!&epik_amd_cohort_unifrac || !&epik_amd_cohort_permanova_metric || !&epik_amd_cohort_pcoa_metric ||
                     !&epik_amd_cohort_permdisp_metric))
@@ -420,6 +423,13 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
                  : epik_amd_cohort_permdisp(_cohorts[0], tree, length.data(), permdisp->labels, permdisp->num_columns,
                                             permdisp->num_permutations, permdisp->seed, permdisp->pairwise ? 1 : 0,
                                             permdisp->records.data(), nullptr, permdisp->group_mean.data(), permdisp->z.data());
+    }
+    if (rc == EPIK_AMD_OK && model) {
+        model->records.assign((size_t)model->num_terms + 1, epik_amd_model_term{});
+        model->aliased.assign(EPIK_AMD_MODEL_MAX_COLUMNS, 0);
+        rc = epik_amd_cohort_model_metric(_cohorts[0], tree, length.data(), distance, model->kind, model->labels, model->values,
+                                          model->num_terms, model->num_permutations, model->seed, model->records.data(), &model->info,
+                                          nullptr, model->aliased.data());
     }
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);

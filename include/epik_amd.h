@@ -985,6 +985,48 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *     slot p, NA for an undefined test.  group_mean[M][32]: mean_g for g < G, NA beyond.  z[M][S]: z of the sample's
  *     position, NA for a sample outside U_c.  Both for every column, defined or not.  Every cell of every output is written.
  *
+ * Sequential model (McArdle & Anderson 2001; vegan's `adonis2(D ~ a + b + c, by = "terms")`): do the samples still differ by
+ *   a term once the terms before it are accounted for?  From the matrix KR[S][S] (or another distance), T_s, and a design of
+ *   T terms in [1, EPIK_AMD_MODEL_MAX_TERMS = 16] in test order: kind[T] (0 a factor, 1 numeric), labels[S][T] (uint32, a
+ *   factor's label below EPIK_AMD_MODEL_MAX_GROUPS = 32, 0xffffffff missing; ignored for a numeric term), values[S][T]
+ *   (double, NaN missing, never infinite; ignored for a factor); P in [1, 999 999] and a uint64 seed.  All arithmetic is IEEE
+ *   double, every operation rounded on its own (+ - * / sqrt), nothing fused; every sum is a sequential chain from +0.0.
+ *   The design may have EPIK_AMD_MODEL_MAX_COLUMNS = 64 columns at the most, counted on the arguments as given whatever the
+ *   used samples: a numeric term counts 1, a factor the number of its distinct labels over all S samples less one (0 for none).
+ *   1 Used samples.  U is the samples with T_s > 0 and a value for EVERY term (complete cases), in list order, L = |U|;
+ *     positions 0 .. L - 1 index U.  A factor's groups are its distinct labels in U numbered by first appearance, G of them.
+ *   2 Gower matrix.  B[L][L] over U exactly as the centring paragraph of the principal coordinates forms it (A2 one multiply,
+ *     r_i, g, B[i][j] for i <= j and mirrored).  ss_total = the chain of B[i][i], i ascending (+0.0 for L = 0).
+ *   3 Columns, in term order: a numeric term gives one column of its values; a factor term gives G - 1 columns (none for
+ *     G = 0), the indicators (1.0 or 0.0) of the groups 1 .. G - 1, group 0 the baseline.  C columns in all.  Each is centred:
+ *       mean = (chain over i ascending of x_i) / (double)L,   x_i = x_i - mean,   n0 = chain of x_i * x_i.
+ *     (L = 0: no mean is formed, n0 = +0.0.)
+ *   4 Basis, classical Gram-Schmidt twice.  For each column v in order, with q_0 .. q_{m-1} the columns accepted so far, two
+ *     times over: h_k = chain over i ascending of q_k[i] * v[i] for every k (all from the same v), then
+ *     v[i] = (..((v[i] - h_0 * q_0[i]) - h_1 * q_1[i]) ..), k ascending.  Then n1 = chain of v[i] * v[i].  The column is
+ *     accepted iff n0 > 0.0 and n1 > 2^-40 * n0 (one multiply), and then q_m[i] = v[i] / sqrt(n1), a division each; otherwise
+ *     it is aliased and dropped (a constant column, a covariate given twice, a factor nested in an earlier one).
+ *     df_k = the accepted columns of term k,  R = their number in all,  df_res = L - 1 - R (an int64; may be negative).
+ *   5 The sums of squares of an arrangement sigma of the positions (Q_sigma[i] = the row of Q at position sigma(i)):
+ *       t_c[i] = chain over j = 0 .. L - 1 ascending of B[i][j] * q_c[sigma(j)]      (the full row; symmetry is not used),
+ *       s_c = chain over i ascending of q_c[sigma(i)] * t_c[i],      SS_k = chain of s_c over the accepted columns of term k
+ *       in order (+0.0 for none),   SS_model = chain of SS_k over the terms in order,   SS_res = ss_total - SS_model,
+ *       F_k = (SS_k / (double)df_k) / (SS_res / (double)df_res),   R2_k = SS_k / ss_total,
+ *     and for the whole model the same with SS_model and R.  A sigma whose SS_res is not > 0.0 has F = +infinity.
+ *   6 Permutations.  sigma_p(i) = rank_p(i) of the PERMANOVA rule among the L positions: the same keys from the same seed,
+ *     so both rules see the same shuffles.  Whole rows of Q move, B stays.  sigma_0 is the identity.
+ *   7 Counts.  at_least_k = #{p in 1 .. P : F_k(sigma_p) >= F_k(sigma_0)} (B is indefinite for a tree distance, so SS_res of
+ *     a permutation may fail to be > 0.0: its +infinity counts, the conservative side);  p = (double)(1 + at_least) / (double)(P + 1).
+ *   8 Results.  out[T + 1] of epik_amd_model_term, the terms and then the whole model (df = R, columns = C): df and columns
+ *     are always written.  df = 0: the doubles are NA and at_least = 0.  Otherwise ss is written, r2 unless ss_total is not
+ *     > 0.0 (NA), and f, at_least and p unless df_res < 1 or the observed SS_res is not > 0.0 (NA, 0, NA).
+ *     info: used = L, terms = T, columns = C, rank = R, df_res, ss_total, ss_res (the observed one).
+ *     stat[T + 1][P + 1], where asked for: F of sigma_p, p = 0 the observed one; NA for a record whose f is NA.
+ *     aliased[64]: 1 for a column that was dropped, in column order, 0 otherwise and beyond C.  Every cell is written.
+ *   By hand: four samples at 0, 1, 2, 3 on a line, the factor (a, a, b, b) and then the covariate (0, 1, 2, 3): ss_total = 5,
+ *     q_0 = (-1/2, -1/2, 1/2, 1/2) and SS_1 = 4, q_1 = (-1/2, 1/2, -1/2, 1/2) and SS_2 = 1, SS_res = 0: both F are NA, R2 = 0.8
+ *     and 0.2.  The factor alone: SS_res = 1, F = 8, R2 = 0.8, PERMANOVA's numbers for that column.
+ *
  * An epik_amd_cohort is an object of its own, created for a placer's device, num_branches and keep_at_most (whole
  * databases only, not a k-mer-space shard) and num_samples >= 1; all zero at create() and after reset().
  *   add_device  asynchronous on `stream`, allocates nothing: as epik_amd_profile_add_device, with d_samples (uint32 [n],
@@ -1107,6 +1149,23 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *               permdisp: runs kr_device itself, the same into host memory, synchronous; stat may be null.
  *   permdisp_host  the rule on the host from mass[S][N], first[N], branch_length[N] and the labels, no device.
  *               permdisp_kr_host: the same from a matrix kr[S][S] and totals[S] (T_s; only > 0 matters).
+ *   model_device  takes d_kr as permanova_device does (a cohort whose kr_device never ran is refused) and the design, kind[T],
+ *               labels[S][T] and values[S][T] (HOST, read before the call returns): refused are a null cohort, d_kr, kind,
+ *               labels, values, d_out, d_info or d_aliased, num_terms outside [1, 16], a kind other than 0 or 1,
+ *               num_permutations outside [1, 999 999], a factor's label in [32, 0xffffffff), an infinite value of a numeric
+ *               term and a design of more than 64 columns.  Synchronises the device, then a workspace of its own, grown where
+ *               a call needs more and kept until destroy(): with Sp = S rounded up to 32, 8 S^2 bytes (B), 17 Sp bytes a term,
+ *               528 Sp bytes (the basis Q, 64 columns wide, and two vectors) and, beyond 128 samples, 272 Sp bytes for each workgroup of
+ *               the permutations, min(ceil(P / 4), 256, EPIK_AMD_MAX_BLOCKS) of them (the row sums of 4 permutations and 8
+ *               columns, and their arrangements).  d_out is epik_amd_model_term [T + 1],
+ *               d_info one epik_amd_model_info, d_stat (may be null) float64 [T + 1][P + 1], d_aliased 64 bytes; all in
+ *               device memory.  Once enqueued on `stream` it needs no readback.  The cells and d_kr are not changed.  A
+ *               design of up to 128 positions keeps the row sums and arrangements in LDS; beyond, or with
+ *               EPIK_AMD_MODEL_LDS=0 (read at the call), in global memory: the same bits.
+ *               model: runs kr_device itself, the same into host memory, synchronous; stat may be null.  model_metric: with
+ *               `metric` as permanova_metric.
+ *   model_host  the rule on the host from mass[S][N], first[N], branch_length[N] and the design, no device; model_metric_host
+ *               with `metric`.  model_kr_host: the same from a matrix kr[S][S] and totals[S] (T_s; only > 0 matters).
  * cohort_reads / _strands / _frames / _mates: the profile_* twins with samples[n] (HOST uint32) beside the weights.
  */
 typedef struct epik_amd_cohort epik_amd_cohort;
@@ -1333,6 +1392,43 @@ int epik_amd_cohort_permdisp_metric_host(const uint64_t *mass, uint32_t num_samp
 int epik_amd_cohort_permdisp_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
                                      uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                      epik_amd_permdisp *out, double *stat, double *group_mean, double *z);
+typedef struct epik_amd_model_term {
+    uint32_t df, columns; /* the accepted columns of the term and all of them; R and C for the whole model */
+    uint64_t at_least;    /* #{p >= 1 : F(sigma_p) >= F(sigma_0)} */
+    double ss, f, r2, p;
+} epik_amd_model_term; /* 48 bytes */
+typedef struct epik_amd_model_info {
+    uint32_t used, terms, columns, rank; /* L, T, C, R */
+    int64_t df_res;                      /* L - 1 - R */
+    double ss_total, ss_res;
+} epik_amd_model_info; /* 40 bytes */
+#define EPIK_AMD_MODEL_MAX_TERMS 16u
+#define EPIK_AMD_MODEL_MAX_COLUMNS 64u
+#define EPIK_AMD_MODEL_MAX_GROUPS 32u
+#define EPIK_AMD_MODEL_MAX_PERMUTATIONS 999999u
+#define EPIK_AMD_MODEL_MISSING 0xffffffffu
+int epik_amd_cohort_model_device(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *kind, const uint32_t *labels,
+                                 const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed, void *d_out,
+                                 void *d_info, void *d_stat, void *d_aliased, void *stream);
+int epik_amd_cohort_model(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, const uint32_t *kind,
+                          const uint32_t *labels, const double *values, uint32_t num_terms, uint32_t num_permutations,
+                          uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info, double *stat, uint8_t *aliased);
+int epik_amd_cohort_model_metric(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                                 const uint32_t *kind, const uint32_t *labels, const double *values, uint32_t num_terms,
+                                 uint32_t num_permutations, uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info,
+                                 double *stat, uint8_t *aliased);
+int epik_amd_cohort_model_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                               const double *branch_length, const uint32_t *kind, const uint32_t *labels, const double *values,
+                               uint32_t num_terms, uint32_t num_permutations, uint64_t seed, epik_amd_model_term *out,
+                               epik_amd_model_info *info, double *stat, uint8_t *aliased);
+int epik_amd_cohort_model_metric_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                      const double *branch_length, uint32_t metric, const uint32_t *kind, const uint32_t *labels,
+                                      const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed,
+                                      epik_amd_model_term *out, epik_amd_model_info *info, double *stat, uint8_t *aliased);
+int epik_amd_cohort_model_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *kind,
+                                  const uint32_t *labels, const double *values, uint32_t num_terms, uint32_t num_permutations,
+                                  uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info, double *stat,
+                                  uint8_t *aliased);
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n);
 int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
