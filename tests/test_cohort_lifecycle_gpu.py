@@ -40,13 +40,16 @@ from test_permanova_cpu import factor_columns, same_permanova
 from test_permanova_gpu import SLOTS, device_permanova_raw, sparser
 from test_squash_cpu import host_all_records
 from test_squash_gpu import device_all_records
+from test_unifrac_cpu import METRICS
+from test_unifrac_gpu import device_matrix
 
 pytestmark = pytest.mark.gpu
 U64 = np.uint64
 COUNT_SAMPLES = 128          # cohort_device.hpp: kCohortCountSamples, where the ranking goes from counting to sorting
 SWITCHES = ("EPIK_AMD_EDGETEST_LDS", "EPIK_AMD_PERMANOVA_LDS", "EPIK_AMD_EPCA_LDS", "EPIK_AMD_CORRELATION_LDS")
 ANALYSES = ("kr", "squash", "epca", "kmeans", "alpha", "rarefy", "correlation", "dispersion", "permanova", "edgetest")
-STAGES = ("dense", "thin", "zero", "two", "same", "sum")
+UNIFRAC = tuple(METRICS)      # "unweighted", "weighted", "generalized": names that mirrors() and run_analysis() take as well
+STAGES = ("dense","thin", "zero", "two", "same", "sum")
 DEPTH_STEP = 7
 # the parameters of the six stages: each moves against the stage before
 CLUSTERS = (64, 5, 33, 1, 64, 5)
@@ -103,6 +106,9 @@ def mirrors(mass, best, first, bl, params, only=ANALYSES):
     p, want = params, {}
     if "kr" in only:
         want["kr"] = cohort_mod.kr_host(mass, first, bl)
+    for metric in UNIFRAC:               # (not among ANALYSES: the walk leaves them to test_unifrac_gpu; the edge sweep asks)
+        if metric in only:
+            want[metric] = cohort_mod.unifrac_host(mass, first, bl, metric)
     if "squash" in only:
         want["squash"] = host_all_records(mass, first, bl)
     if "epca" in only:
@@ -224,6 +230,9 @@ def run_analysis(name, pl, cohort, tree, bl, params, want, what):
     p = params
     if name == "kr":
         got = device_kr_raw(pl, cohort, tree, bl)
+        assert same_bits(got, want), (what, np.argwhere(got.view(U64) != want.view(U64))[:8])
+    elif name in UNIFRAC:
+        _, got = device_matrix(pl, cohort, tree, bl, name)
         assert same_bits(got, want), (what, np.argwhere(got.view(U64) != want.view(U64))[:8])
     elif name == "squash":
         records, count = device_all_records(pl, cohort, tree, bl, torch.cuda.Stream())

@@ -1,4 +1,5 @@
-"""The observed statistics of the edge test and of PERMANOVA against the textbook forms, which are not shaped like the rule.
+"""The observed statistics of the edge test and of PERMANOVA, and the KR and UniFrac distances, against the textbook forms,
+which are not shaped like the rule.
 
 The numpy restatements of test_edgetest_cpu and test_permanova_cpu follow the rule term by term (eta = A / sxx from centred
 sums, ssw = sxx - A, SSW from the rows' chains) and would share a wrong formula with it.  Here the host mirror
@@ -21,6 +22,22 @@ A wrong degree of freedom, a missing tie correction or L in place of L - 1 moves
 
 The worst relative deviations measured over every defined branch of the cases below: F 2.3e-13 (f_oneway 3.0e-14), H 4.1e-16
 (kruskal 5.9e-11), pseudo-F 3.6e-14, R^2 3.5e-14.
+
+The distances that feed PERMANOVA, PCoA, PERMDISP and the model are held to the numpy restatements bit for bit elsewhere, and
+those follow the rule's prefix sums over first[b] .. b term by term.  Here kr_host and unifrac_host are held to forms that
+walk parent pointers and know neither first[] nor C and B, on random multifurcating trees and stars of 7, 15, 16 and 33
+branches (test_cohort_edges_cpu.cohort_edge_tree), six samples, one of them empty, every pair of the other five:
+  KR           the optimal-transport cost between the two samples' masses, each branch's mass at its midpoint, under the
+               path length between midpoints: scipy.optimize.linprog (HiGHS), where scipy imports;
+  weighted     KR over Lozupone's normaliser sum_a (p_a + q_a) depth(a), depth from a's midpoint to the top of the root branch;
+  unweighted   Lozupone & Knight's share of the half branches that lead to one sample alone, from the sets of mass-bearing
+               branches at or below each half branch, in fractions;
+  generalized  Chen's sum with alpha = 0.5 over the same sets, in 60-digit decimals from the integer masses.
+The worst relative deviations of the mirror from these forms, measured over those cases: KR 4.5e-16, weighted 3.8e-16,
+unweighted 3.5e-16, generalized 7.2e-16; the bounds are 16 times these.  The error of KR relative to itself grows like
+1 / weighted UniFrac (compared_pairs), which is asserted to be at least 1e-3 for every compared pair.  Shown once on a
+scratch copy of the forms: mass at the upper end of its branch instead of the midpoint, a branch's own mass counted below
+both of its halves, or the root branch left out of depth() each move some value by more than 1e-3 relative.
 """
 import math
 from fractions import Fraction
@@ -30,14 +47,16 @@ import pytest
 
 from epik_amd import cohort as cohort_mod, synth
 from test_cohort_cpu import numpy_first, random_cells
+from test_cohort_edges_cpu import cohort_edge_tree
 from test_correlation_cpu import is_na
 from test_edgetest_cpu import column_groups, numpy_midranks, numpy_vectors, sparser
 from test_permanova_cpu import MISSING
 
 try:
     from scipy import stats as scipy_stats
+    from scipy.optimize import linprog
 except ImportError:
-    scipy_stats = None
+    scipy_stats = linprog = None
 
 F_BOUND, H_BOUND = 1e-10, 1e-7
 CASES = ((7, 33), (999, 70))             # (N, S)
@@ -162,3 +181,176 @@ def test_pseudo_f_and_r2_are_anderson_s(num_branches, num_samples, kind):
         note(worst, "R2", relative(float(rec["r2"]), ss_among / ss_total))
     print(num_branches, num_samples, kind, {k: f"{v:.2e}" for k, v in worst.items()})
     assert worst["pseudo-F"] <= F_BOUND and worst["R2"] <= F_BOUND, worst
+
+
+# ---- the distances against forms that are not shaped like the rule ---------------------------------------------------
+# The rule takes a distance from prefix sums over first[b] .. b: clade mass C and the mass below B per branch, and a sum of
+# half lengths times |C_s - C_t| + |B_s - B_t| (or its UniFrac counterparts).  The forms below know nothing of first[], of
+# clades as ranges or of C and B: they walk parent pointers.
+DISTANCE_TREES = tuple((n, shape) for n in (7, 15, 16, 33) for shape in ("random", "star"))
+DISTANCE_SAMPLES = 6
+# 16 times the worst relative deviation of the host mirror from the form, measured over DISTANCE_TREES (the docstring)
+KR_LP_BOUND = 16 * 4.5e-16
+WEIGHTED_BOUND = 16 * 3.8e-16
+UNWEIGHTED_BOUND = 16 * 3.5e-16
+GENERALIZED_BOUND = 16 * 7.2e-16
+WELL_CONDITIONED = 1e-3
+
+
+def distance_case(num_branches, shape):
+    """(parent, bl, first, mass, used): six samples, sample 1 empty, on a tree of test_cohort_edges_cpu."""
+    parent, bl = cohort_edge_tree(num_branches, shape)
+    rng = np.random.default_rng(2700 + 2 * num_branches + (shape == "star"))
+    mass = random_cells(rng, DISTANCE_SAMPLES, num_branches, empty=1, bits=42)
+    used = np.flatnonzero(mass.any(axis=1))
+    assert used.tolist() == [0, 2, 3, 4, 5]
+    return parent, bl, numpy_first(parent), mass, used
+
+
+def compared_pairs(mass, first, bl, used):
+    """The pairs of samples with mass, (S - 1)(S - 2) / 2 of them; each one's weighted UniFrac is at least 1e-3 in the mirror.
+    A rounded quotient C_s is off by 2^-53 of its own size, so |C_s - C_t| is off by that much of C_s + C_t and KR, relative to
+    itself, by 2^-53 * den / num = 2^-53 / weighted UniFrac: two samples that nearly agree have no digits to compare."""
+    weighted = cohort_mod.unifrac_host(mass, first, bl, "weighted")
+    pairs = [(int(s), int(t)) for i, s in enumerate(used) for t in used[i + 1:]]
+    assert len(pairs) >= (DISTANCE_SAMPLES - 1) * (DISTANCE_SAMPLES - 2) // 2
+    assert min(float(weighted[s, t]) for s, t in pairs) >= WELL_CONDITIONED, weighted
+    return pairs
+
+
+def chain(parent, a):
+    """a, its parent, ... , the root."""
+    out = []
+    while a >= 0:
+        out.append(int(a))
+        a = int(parent[a])
+    return out
+
+
+def midpoint_distance(parent, bl, a, b):
+    """The length of the path between the midpoints of the branches a and b: up from each to the first branch that lies above
+    both.  Where that is one of the two the path ends at its midpoint; otherwise the two climbs meet at its lower end."""
+    if a == b:
+        return 0.0
+    up_a, up_b = chain(parent, a), chain(parent, b)
+    meet = next(x for x in up_a if x in up_b)
+    terms = []
+    for start, up in ((a, up_a), (b, up_b)):
+        if start != meet:
+            terms += [bl[start] / 2] + [bl[y] for y in up[1:up.index(meet)]]
+    if meet in (a, b):
+        terms.append(bl[meet] / 2)
+    return math.fsum(terms)
+
+
+def depth(parent, bl, a):
+    """From the midpoint of a to the upper end of the root branch."""
+    return math.fsum([bl[a] / 2] + [bl[y] for y in chain(parent, a)[1:]])
+
+
+def shares(mass_row):
+    return mass_row.astype(np.float64) / float(mass_row.sum(dtype=np.uint64))
+
+
+def transport_cost(p, q, cost):
+    """min sum f_ab cost_ab over f >= 0 with row sums p and column sums q (Kantorovich's form of the KR distance)."""
+    rows, cols = np.flatnonzero(p), np.flatnonzero(q)
+    a_eq = np.zeros((len(rows) + len(cols), len(rows) * len(cols)))
+    for i in range(len(rows)):
+        a_eq[i, i * len(cols):(i + 1) * len(cols)] = 1.0
+    for j in range(len(cols)):
+        a_eq[len(rows) + j, j::len(cols)] = 1.0
+    res = linprog(cost[np.ix_(rows, cols)].ravel(), A_eq=a_eq, b_eq=np.concatenate([p[rows], q[cols]]), bounds=(0, None), method="highs")
+    assert res.status == 0, res.message
+    return float(res.fun)
+
+
+@pytest.mark.parametrize("num_branches, shape", DISTANCE_TREES)
+def test_kr_is_the_optimal_transport_cost_between_the_midpoints(num_branches, shape):
+    """Where scipy imports, against the optimum of the linear program; everywhere, against the transport problem that needs no
+    solver: towards a sample with all its mass on one branch there is one plan, every share along the cost matrix's column
+    (shares and costs above 0 only: that sum is as well conditioned as the mirror's, and held to the same bound)."""
+    parent, bl, first, mass, used = distance_case(num_branches, shape)
+    kr = cohort_mod.kr_host(mass, first, bl)
+    n = num_branches
+    cost = np.array([[midpoint_distance(parent, bl, a, b) for b in range(n)] for a in range(n)])
+    assert (cost == cost.T).all() and (cost[~np.eye(n, dtype=bool)] >= 0).all()
+    # a sample on one branch: the only plan moves every share p_a from a to that branch
+    for b in (0, n // 2, n - 1):
+        point = np.zeros((1, n), np.uint64)
+        point[0, b] = 5
+        to_point = cohort_mod.kr_host(np.concatenate([mass[used], point]), first, bl)[-1, :-1]
+        for i, s in enumerate(used):
+            plan = math.fsum((shares(mass[s]) * cost[:, b]).tolist())
+            assert relative(float(to_point[i]), plan) <= KR_LP_BOUND, (b, s, float(to_point[i]), plan)
+    worst = 0.0
+    for s, t in compared_pairs(mass, first, bl, used):
+        if linprog is not None:
+            worst = max(worst, relative(float(kr[s, t]), transport_cost(shares(mass[s]), shares(mass[t]), cost)))
+    print(num_branches, shape, f"KR against the transport optimum {worst:.2e}")
+    assert worst <= KR_LP_BOUND, worst
+
+
+@pytest.mark.parametrize("num_branches, shape", DISTANCE_TREES)
+def test_weighted_unifrac_is_kr_over_lozupone_s_normaliser(num_branches, shape):
+    """Lozupone et al. (2007): the raw weighted distance over sum_a (p_a + q_a) depth(a), the mass-weighted mean distance of
+    either sample from the root."""
+    parent, bl, first, mass, used = distance_case(num_branches, shape)
+    kr = cohort_mod.kr_host(mass, first, bl)
+    weighted = cohort_mod.unifrac_host(mass, first, bl, "weighted")
+    depths = [depth(parent, bl, a) for a in range(num_branches)]
+    worst = 0.0
+    for s, t in compared_pairs(mass, first, bl, used):
+        p, q = shares(mass[s]), shares(mass[t])
+        normaliser = math.fsum((p[a] + q[a]) * depths[a] for a in range(num_branches))
+        worst = max(worst, relative(float(weighted[s, t]), float(kr[s, t]) / normaliser))
+    print(num_branches, shape, f"weighted UniFrac against KR over the normaliser {worst:.2e}")
+    assert worst <= WEIGHTED_BOUND, worst
+
+
+def half_branch_sets(parent, mass_row):
+    """(upper[b], lower[b]): the branches with mass at or below the upper and the lower half of every branch.  A branch's own
+    mass sits at its midpoint: below the upper half, not below the lower one."""
+    upper, lower = [set() for _ in parent], [set() for _ in parent]
+    for a in np.flatnonzero(mass_row).tolist():
+        upper[a].add(a)
+        for y in chain(parent, a)[1:]:
+            upper[y].add(a)
+            lower[y].add(a)
+    return upper, lower
+
+
+@pytest.mark.parametrize("num_branches, shape", DISTANCE_TREES)
+def test_unweighted_and_generalized_unifrac_from_descendant_sets(num_branches, shape):
+    """Lozupone & Knight (2005): the length of the tree that leads to one sample alone over the length that leads to either;
+    Chen et al. (2012) with alpha = 0.5: sum h (x + y)^alpha |x - y| / (x + y) over sum h (x + y)^alpha, x and y the shares
+    below a half branch.  The first in fractions, the second in 60-digit decimals from the integer masses; rounded once."""
+    import decimal
+    parent, bl, first, mass, used = distance_case(num_branches, shape)
+    got_u = cohort_mod.unifrac_host(mass, first, bl, "unweighted")
+    got_g = cohort_mod.unifrac_host(mass, first, bl, "generalized")
+    sets = {int(s): half_branch_sets(parent, mass[s]) for s in used}
+    total = {int(s): int(mass[s].sum(dtype=np.uint64)) for s in used}
+    worst = {}
+    with decimal.localcontext() as ctx:
+        ctx.prec = 60
+        D = decimal.Decimal
+        for s, t in compared_pairs(mass, first, bl, used):
+            one, either, num, den = Fraction(0), Fraction(0), D(0), D(0)
+            for b in range(num_branches):
+                for half in (0, 1):
+                    in_s, in_t = sets[s][half][b], sets[t][half][b]
+                    if not in_s and not in_t:
+                        continue
+                    either += Fraction(float(bl[b])) / 2
+                    if not in_s or not in_t:
+                        one += Fraction(float(bl[b])) / 2
+                    x = D(sum(int(mass[s, a]) for a in in_s)) / D(total[s])
+                    y = D(sum(int(mass[t, a]) for a in in_t)) / D(total[t])
+                    h = D(float(bl[b])) / 2
+                    num += h * (x + y).sqrt() * abs(x - y) / (x + y)
+                    den += h * (x + y).sqrt()
+            note(worst, "unweighted", relative(float(got_u[s, t]), float(one / either)))
+            note(worst, "generalized", relative(float(got_g[s, t]), float(num / den)))
+    print(num_branches, shape, {k: f"{v:.2e}" for k, v in worst.items()})
+    assert worst["unweighted"] <= UNWEIGHTED_BOUND and worst["generalized"] <= GENERALIZED_BOUND, worst
