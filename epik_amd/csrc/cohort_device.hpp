@@ -1,7 +1,8 @@
-// cohort_device.hpp -- what cohort_place.hip, squash_place.hip, epca_place.hip, pcoa_place.hip, kmeans_place.hip, diversity_place.hip, correlation_place.hip, permanova_place.hip, edgetest_place.hip, permdisp_place.hip, model_place.hip and unifrac_place.hip share of a device cohort: the object
-// itself and the launch of the normalise and distance kernels (cohort_place.hip), which the squash clustering and the
-// edge principal components start from; and the device code that the correlation, PERMANOVA and the edge test have in
-// common: a branch's vectors and midranks, the permutation key and rank, and a column's list and groups.
+// cohort_device.hpp -- what the cohort analyses share of a device cohort.  For the host: the object itself with its workspace
+// slots, and the enqueue calls that one analysis offers the others (the normalise and distance kernels, the mass plane, the
+// index of the used samples).  For the kernels (under __HIPCC__): NA, the Gower centring of a distance matrix, a branch's
+// vectors and midranks, the permutation key and rank, and a column's list and groups.  The host code around the kernels is
+// in cohort_entry.hpp.
 #ifndef EPIK_AMD_COHORT_DEVICE_HPP
 #define EPIK_AMD_COHORT_DEVICE_HPP
 
@@ -12,6 +13,28 @@
 
 #include "epik_amd.h"
 #include "host_entry.hpp"
+
+// a workspace of one analysis on the cohort's device
+struct CohortSpace {
+    void *d = nullptr;
+    size_t bytes = 0;
+};
+
+// one entry a workspace (kSpaceRarefy: the curve's partials, beside the counts and the alpha partials of kSpaceDiversity)
+enum CohortSpaceId : uint32_t {
+    kSpaceSquash,
+    kSpaceEpca,
+    kSpacePcoa,
+    kSpaceKmeans,
+    kSpaceDiversity,
+    kSpaceRarefy,
+    kSpaceCorrelation,
+    kSpacePermanova,
+    kSpaceEdgetest,
+    kSpacePermdisp,
+    kSpaceModel,
+    kCohortSpaces
+};
 
 struct epik_amd_cohort {
     int device = 0;
@@ -25,38 +48,9 @@ struct epik_amd_cohort {
     uint64_t *d_total = nullptr;   // [S]: T_s
     double *d_planes = nullptr;    // C[N][Sp] | B[N][Sp]
     double *d_half = nullptr;      // [N]: 0.5 * branch_length
-    // the workspace of the squash clustering, allocated by the first squash_device (squash_place.hip):
-    void *d_squash = nullptr;
-    // the workspace of the edge principal components, allocated by the first epca_device (epca_place.hip):
-    void *d_epca = nullptr;
-    // the workspace of the principal coordinates, allocated by the first pcoa_device (pcoa_place.hip):
-    void *d_pcoa = nullptr;
-    // the workspace of the phylogenetic k-means, allocated by the first kmeans_device (kmeans_place.hip):
-    void *d_kmeans = nullptr;
-    // the workspace of the alpha diversity and the rarefaction curves (diversity_place.hip): the counts and the alpha
-    // partials, allocated by the first alpha_device or rarefy_device; the curve's partials, for rarefy_depths depths
-    void *d_diversity = nullptr;
-    void *d_rarefy = nullptr;
-    uint32_t rarefy_depths = 0;
-    // the workspace of the edge correlation and dispersion, allocated by the first correlation_device or dispersion_device
-    // (correlation_place.hip):
-    void *d_correlation = nullptr;
-    // the workspace of PERMANOVA, allocated by the first permanova_device and grown by a call that needs more
-    // (permanova_place.hip):
-    void *d_permanova = nullptr;
-    size_t permanova_bytes = 0;
-    // the workspace of the edge test, allocated by the first edgetest_device and grown by a call that needs more
-    // (edgetest_place.hip):
-    void *d_edgetest = nullptr;
-    size_t edgetest_bytes = 0;
-    // the workspace of PERMDISP, allocated by the first permdisp_device and grown by a call that needs more
-    // (permdisp_place.hip):
-    void *d_permdisp = nullptr;
-    size_t permdisp_bytes = 0;
-    // the workspace of the sequential model, allocated by the first model_device and grown by a call that needs more
-    // (model_place.hip):
-    void *d_model = nullptr;
-    size_t model_bytes = 0;
+    // the workspaces of the analyses, each allocated by its first call and grown by a call that needs more
+    // (cohort_entry.hpp: cohort_space_ensure)
+    CohortSpace space[kCohortSpaces];
 };
 
 namespace epik_amd {
@@ -97,11 +91,49 @@ constexpr uint32_t kCohortKeyTile = 1024;      // the keys a workgroup ranks a l
 static_assert(kBlock == 256 && kCohortLdsSamples % kBlock == 0 && 2 * kCohortCountSamples <= kCohortLdsSamples);
 
 #ifdef __HIPCC__
-// B[i][j], i <= j, of the principal coordinates' centring from the distance and the means: what pcoa_place.hip and
-// model_place.hip form their Gower matrix of
+// NA is stored as its bit pattern and never computed
+__device__ inline double na_value() { return __longlong_as_double((long long)EPIK_AMD_NA_BITS); }
+
+// The Gower centring of the distances kr[S][S] among the L samples used[0 .. L), as pcoa_place.hip and model_place.hip form
+// it; every sum is a sequential chain in the rule's order.
+// B[i][j], i <= j, from the distance and the means
 __device__ inline double gower_centred(double d, double ri, double rj, double g)
 {
     return __dmul_rn(-0.5, __dadd_rn(__dsub_rn(__dsub_rn(__dmul_rn(d, d), ri), rj), g));
+}
+
+// r_i: the mean of the squared distances of row i
+__device__ inline double gower_row_mean(const double *__restrict__ kr, const uint32_t *__restrict__ used, uint32_t num_samples,
+                                        uint32_t L, uint32_t i)
+{
+    const double *column = kr + used[i];  // KR[u_j][u_i] = KR[u_i][u_j]
+    double acc = 0.0;
+#pragma unroll 4  // (the reads of four values are in flight ahead of the dependent adds)
+    for (uint32_t j = 0; j < L; ++j) {  // ascending: the rule's order
+        const double d = column[(uint64_t)used[j] * num_samples];
+        acc = __dadd_rn(acc, __dmul_rn(d, d));
+    }
+    return __ddiv_rn(acc, (double)L);
+}
+
+// g: the mean of r[0 .. L) (0.0 of no sample); one lane's work
+__device__ inline double gower_mean_of_means(const double *__restrict__ r, uint32_t L)
+{
+    double g = 0.0;
+    for (uint32_t i = 0; i < L; ++i) g = __dadd_rn(g, r[i]);  // ascending: the rule's order
+    if (L) g = __ddiv_rn(g, (double)L);
+    return g;
+}
+
+// B[L][L], a grid of workgroups of kBlock lanes striding over the cells
+__device__ inline void gower_centre_cells(const double *__restrict__ kr, const uint32_t *__restrict__ used, uint32_t num_samples,
+                                          uint32_t L, const double *__restrict__ r, double g, double *__restrict__ B)
+{
+    const uint64_t cells = (uint64_t)L * L;
+    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < cells; e += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t i = (uint32_t)(e / L), j = (uint32_t)(e - (uint64_t)i * L), lo = i < j ? i : j, hi = i < j ? j : i;
+        B[e] = gower_centred(kr[(uint64_t)used[lo] * num_samples + used[hi]], r[lo], r[hi], g);
+    }
 }
 
 // the midrank of x_j among x[0 .. L): the rule's two counts

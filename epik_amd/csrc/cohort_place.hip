@@ -42,8 +42,7 @@
 #include <vector>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 
 namespace {
 
@@ -291,7 +290,7 @@ uint32_t padded_samples(const epik_amd_cohort *cohort) { return cohort_padded_sa
 int check_pair(const epik_amd_placer *p, const epik_amd_cohort *cohort)
 {
     if (!p) return fail_with(EPIK_AMD_ERR_INVALID, "null placer");
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    COHORT_TRY(check_cohort(cohort));
     if (cohort->device != p->device || cohort->num_branches != p->params.num_branches || cohort->keep != p->params.keep_at_most)
         return fail_with(EPIK_AMD_ERR_INVALID, "the cohort was created for another placer (device, num_branches or keep_at_most differ)");
     return EPIK_AMD_OK;
@@ -300,7 +299,7 @@ int check_pair(const epik_amd_placer *p, const epik_amd_cohort *cohort)
 int add_device_impl(epik_amd_cohort *cohort, const void *d_rows, const void *d_n_rows, const void *d_kmer_counts,
                     const void *d_weights, const void *d_samples, uint64_t n, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    COHORT_TRY(check_cohort(cohort));
     if (n == 0) return EPIK_AMD_OK;
     if (!d_rows || !d_n_rows || !d_kmer_counts)
         return fail_with(EPIK_AMD_ERR_INVALID, "null device buffer (the k-mer counts are required: they tell a read without hits)");
@@ -308,9 +307,7 @@ int add_device_impl(epik_amd_cohort *cohort, const void *d_rows, const void *d_n
     if (n > 0xffffffffull) return fail_with(EPIK_AMD_ERR_INVALID, "a batch of 2^32 reads or more");
     HIP_TRY(hipSetDevice(cohort->device));
     const uint64_t tiles = (n * cohort->keep + kBlock - 1) / kBlock;
-    const uint64_t own_blocks = cohort->lds ? cohort->lds_blocks : kMaxBlocks;
-    const uint64_t max_blocks = cohort->max_blocks_cap ? std::min<uint64_t>(own_blocks, cohort->max_blocks_cap) : own_blocks;
-    const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min(tiles, max_blocks)));
+    const dim3 grid = cohort_grid(cohort, tiles, cohort->lds ? cohort->lds_blocks : kMaxBlocks);
     const auto *rows = static_cast<const u32x4 *>(d_rows);
     const auto *n_rows = static_cast<const uint32_t *>(d_n_rows), *counts = static_cast<const uint32_t *>(d_kmer_counts);
     const auto *weights = static_cast<const uint32_t *>(d_weights), *samples = static_cast<const uint32_t *>(d_samples);
@@ -328,10 +325,10 @@ int add_device_impl(epik_amd_cohort *cohort, const void *d_rows, const void *d_n
 // the tree of a distance or of anything else that starts from the planes: on the cohort's device, of its N; its first[]
 int check_tree(const epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t **d_first)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    COHORT_TRY(check_cohort(cohort));
     int tree_device = 0;
     uint32_t tree_branches = 0;
-    if (const int rc = tree_first_device(tree, &tree_device, &tree_branches, d_first); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(tree_first_device(tree, &tree_device, &tree_branches, d_first));
     if (tree_device != cohort->device || tree_branches != cohort->num_branches)
         return fail_with(EPIK_AMD_ERR_INVALID, "the tree does not fit the cohort (device or num_branches differ)");
     return EPIK_AMD_OK;
@@ -351,32 +348,26 @@ int normalise_launch(epik_amd_cohort *cohort, const uint32_t *d_first, hipStream
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&cohort->d_planes), plane_bytes));
         HIP_TRY(hipMemset(cohort->d_planes, 0, plane_bytes));  // (the padding samples of the last tile stay zero)
     }
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    hipLaunchKernelGGL(cohort_normalise_kernel, dim3((uint32_t)std::min<uint64_t>({S, kMaxBlocks, cap})), dim3(kBlock), 0, stream,
-                       cohort->d_cells, d_first, S, N, padded, cohort->d_prefix, cohort->d_total, cohort->d_planes);
+    hipLaunchKernelGGL(cohort_normalise_kernel, cohort_grid(cohort, S, kMaxBlocks), dim3(kBlock), 0, stream, cohort->d_cells, d_first, S, N,
+                       padded, cohort->d_prefix, cohort->d_total, cohort->d_planes);
     HIP_TRY(hipGetLastError());
     return EPIK_AMD_OK;
 }
 
 int kr_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (!branch_length || !d_out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(check_present(branch_length, d_out));
     const uint32_t *d_first = nullptr;
-    if (const int rc = check_tree(cohort, tree, &d_first); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(check_tree(cohort, tree, &d_first));
     const uint32_t N = cohort->num_branches, S = cohort->num_samples, padded = padded_samples(cohort);
-    std::vector<double> half(N);
-    for (uint32_t b = 0; b < N; ++b) {
-        if (!(branch_length[b] >= 0.0) || !std::isfinite(branch_length[b]))
-            return fail_with(EPIK_AMD_ERR_INVALID, "branch " + std::to_string(b) + ": the branch length is negative or not finite");
-        half[b] = 0.5 * branch_length[b];
-    }
-    if (const int rc = normalise_launch(cohort, d_first, stream); rc != EPIK_AMD_OK) return rc;
+    std::vector<double> half;
+    COHORT_TRY(half_branch_lengths(branch_length, N, half));
+    COHORT_TRY(normalise_launch(cohort, d_first, stream));
     HIP_TRY(hipMemcpy(cohort->d_half, half.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
     const uint64_t side = padded / kTile, tiles = side * (side + 1) / 2;
-    hipLaunchKernelGGL(cohort_kr_kernel, dim3((uint32_t)std::min<uint64_t>({tiles, kKrBlocks, cap})), dim3(kBlock), 0, stream,
-                       cohort->d_planes, cohort->d_half, cohort->d_total, S, N, padded, static_cast<double *>(d_out));
+    hipLaunchKernelGGL(cohort_kr_kernel, cohort_grid(cohort, tiles, kKrBlocks), dim3(kBlock), 0, stream, cohort->d_planes, cohort->d_half,
+                       cohort->d_total, S, N, padded, static_cast<double *>(d_out));
     HIP_TRY(hipGetLastError());
     return EPIK_AMD_OK;
 }
@@ -429,11 +420,8 @@ __global__ __launch_bounds__(kBlock) void used_index_kernel(const uint64_t *__re
 void free_cohort(epik_amd_cohort *cohort)
 {
     (void)hipFree(cohort->d_cells), (void)hipFree(cohort->d_prefix), (void)hipFree(cohort->d_total);
-    (void)hipFree(cohort->d_planes), (void)hipFree(cohort->d_half), (void)hipFree(cohort->d_squash), (void)hipFree(cohort->d_epca);
-    (void)hipFree(cohort->d_pcoa);
-    (void)hipFree(cohort->d_kmeans), (void)hipFree(cohort->d_diversity), (void)hipFree(cohort->d_rarefy);
-    (void)hipFree(cohort->d_correlation), (void)hipFree(cohort->d_permanova), (void)hipFree(cohort->d_edgetest), (void)hipFree(cohort->d_permdisp);
-    (void)hipFree(cohort->d_model);
+    (void)hipFree(cohort->d_planes), (void)hipFree(cohort->d_half);
+    for (CohortSpace &space : cohort->space) (void)hipFree(space.d);
 }
 
 }  // namespace
@@ -442,7 +430,7 @@ namespace epik_amd {
 
 int cohort_normalise_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, hipStream_t stream, const uint32_t **d_first)
 {
-    if (const int rc = check_tree(cohort, tree, d_first); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(check_tree(cohort, tree, d_first));
     return normalise_launch(cohort, *d_first, stream);
 }
 
@@ -453,9 +441,8 @@ int cohort_kr_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree, const 
 
 int cohort_used_index_enqueue(const epik_amd_cohort *cohort, uint32_t *used, uint32_t *jof, uint32_t *count, hipStream_t stream)
 {
-    const uint64_t S = cohort->num_samples, cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(S + kBlock - 1) / kBlock, 1024, cap})));
-    hipLaunchKernelGGL(used_index_kernel, grid, dim3(kBlock), 0, stream, cohort->d_total, cohort->num_samples, used, jof, count);
+    hipLaunchKernelGGL(used_index_kernel, cohort_grid_per(cohort, cohort->num_samples, kBlock, 1024), dim3(kBlock), 0, stream, cohort->d_total,
+                       cohort->num_samples, used, jof, count);
     HIP_TRY(hipGetLastError());
     return EPIK_AMD_OK;
 }
@@ -464,7 +451,7 @@ int cohort_host_chunked(epik_amd_placer *p, epik_amd_cohort *cohort, const char 
                         const uint32_t *weights, const uint32_t *samples, uint64_t n, uint32_t mode, uint64_t longest_placed,
                         const HostVariant &v, uint8_t *label)
 {
-    if (const int rc = check_pair(p, cohort); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(check_pair(p, cohort));
     if (!samples) return fail_with(EPIK_AMD_ERR_INVALID, "null samples (a cohort placement names the sample of every read)");
     HIP_TRY(hipSetDevice(p->device));
     struct DeviceArrays {  // (freed however the call ends; place_host_chunked has drained the stream by then, or never used it)
@@ -498,7 +485,7 @@ int epik_amd_cohort_create(const epik_amd_placer *p, uint32_t num_samples, epik_
     if (!out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
     *out = nullptr;
     if (!p) return fail_with(EPIK_AMD_ERR_INVALID, "null placer");
-    if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
+    COHORT_TRY(check_host_samples(num_samples));
     if (p->plan.shard_count > 1)
         return fail_with(EPIK_AMD_ERR_INVALID, "a cohort needs a whole database, not a k-mer-space shard");
     auto *cohort = new (std::nothrow) epik_amd_cohort;
@@ -554,7 +541,7 @@ void epik_amd_cohort_destroy(epik_amd_cohort *cohort)
 
 int epik_amd_cohort_reset(epik_amd_cohort *cohort)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    COHORT_TRY(check_cohort(cohort));
     HIP_TRY(hipSetDevice(cohort->device));
     HIP_TRY(hipDeviceSynchronize());  // (the adds enqueued so far, on whatever stream)
     HIP_TRY(hipMemset(cohort->d_cells, 0, cell_count(cohort) * sizeof(uint64_t)));
@@ -564,7 +551,7 @@ int epik_amd_cohort_reset(epik_amd_cohort *cohort)
 
 int epik_amd_cohort_info(const epik_amd_cohort *cohort, uint32_t *num_samples, uint32_t *num_branches, uint32_t *lds_path)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    COHORT_TRY(check_cohort(cohort));
     if (num_samples) *num_samples = cohort->num_samples;
     if (num_branches) *num_branches = cohort->num_branches;
     if (lds_path) *lds_path = cohort->lds ? 1 : 0;
@@ -574,7 +561,7 @@ int epik_amd_cohort_info(const epik_amd_cohort *cohort, uint32_t *num_samples, u
 int epik_amd_cohort_read(epik_amd_cohort *cohort, uint64_t *mass, uint64_t *best, epik_amd_profile_totals *totals,
                          uint64_t *bad_samples)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    COHORT_TRY(check_cohort(cohort));
     HIP_TRY(hipSetDevice(cohort->device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t n = cohort->num_branches, S = cohort->num_samples, pitch = row_stride(cohort) * sizeof(uint64_t);
@@ -589,8 +576,8 @@ int epik_amd_cohort_read(epik_amd_cohort *cohort, uint64_t *mass, uint64_t *best
 int epik_amd_cohort_add_cells(epik_amd_cohort *cohort, const uint64_t *mass, const uint64_t *best,
                               const epik_amd_profile_totals *totals)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    return guarded("cohort_add_cells", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
         const size_t n = cohort->num_branches, S = cohort->num_samples, stride = row_stride(cohort);
         std::vector<uint64_t> cells(S * stride, 0);
         for (size_t s = 0; s < S; ++s) {
@@ -599,14 +586,8 @@ int epik_amd_cohort_add_cells(epik_amd_cohort *cohort, const uint64_t *mass, con
             if (totals) std::memcpy(&cells[s * stride + 2 * n], totals + s, sizeof *totals);
         }
         HIP_TRY(hipSetDevice(cohort->device));
-        struct Upload {
-            void *d = nullptr;
-            ~Upload()
-            {
-                if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-            }
-        } up;
-        HIP_TRY(hipMalloc(&up.d, cells.size() * sizeof(uint64_t)));
+        DeviceResult up;
+        COHORT_TRY(up.alloc(cells.size() * sizeof(uint64_t)));
         HIP_TRY(hipMemcpy(up.d, cells.data(), cells.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
         HIP_TRY(hipDeviceSynchronize());  // (the adds enqueued so far: this one is no atomic)
         const uint64_t blocks = std::min<uint64_t>((cells.size() + kBlock - 1) / kBlock, cohort->max_blocks_cap ? cohort->max_blocks_cap : kMaxBlocks);
@@ -615,9 +596,7 @@ int epik_amd_cohort_add_cells(epik_amd_cohort *cohort, const uint64_t *mass, con
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());
         return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_add_cells: ") + e.what());
-    }
+    });
 }
 
 int epik_amd_cohort_add_device(epik_amd_cohort *cohort, const void *d_rows, const void *d_n_rows, const void *d_kmer_counts,
@@ -629,64 +608,44 @@ int epik_amd_cohort_add_device(epik_amd_cohort *cohort, const void *d_rows, cons
 int epik_amd_cohort_kr_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_out,
                               void *stream)
 {
-    try {
-        return kr_device_impl(cohort, tree, branch_length, d_out, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_kr_device: ") + e.what());
-    }
+    return guarded("cohort_kr_device", [&]() -> int { return kr_device_impl(cohort, tree, branch_length, d_out, static_cast<hipStream_t>(stream)); });
 }
 
 int epik_amd_cohort_kr(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, double *out)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (!out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_kr", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(check_present(out));
         const size_t bytes = (size_t)cohort->num_samples * cohort->num_samples * sizeof(double);
         HIP_TRY(hipSetDevice(cohort->device));
-        struct Matrix {
-            void *d = nullptr;
-            ~Matrix()
-            {
-                if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-            }
-        } m;
-        HIP_TRY(hipMalloc(&m.d, bytes));
-        if (const int rc = kr_device_impl(cohort, tree, branch_length, m.d, nullptr); rc != EPIK_AMD_OK) return rc;
-        HIP_TRY(hipMemcpy(out, m.d, bytes, hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_kr: ") + e.what());
-    }
+        DeviceResult m;
+        COHORT_TRY(m.alloc(bytes));
+        COHORT_TRY(kr_device_impl(cohort, tree, branch_length, m.d, nullptr));
+        return m.copy_to(out, bytes);
+    });
 }
 
 int epik_amd_cohort_kr_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                             const double *branch_length, double *out)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
-        if (!mass || !first || !branch_length || !out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_kr_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(check_present(mass, first, branch_length, out));
         std::string err;
-        if (const int rc = kr_matrix(mass, num_samples, num_branches, first, branch_length, out, err); rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_kr_host: ") + e.what());
-    }
+        return rule_result(kr_matrix(mass, num_samples, num_branches, first, branch_length, out, err), err);
+    });
 }
 
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n)
 {
-    try {  // std::vector: nothing may leave through the C ABI
-        if (const int rc = check_pair(p, cohort); rc != EPIK_AMD_OK) return rc;
+    return guarded("cohort_reads", [&]() -> int {
+        COHORT_TRY(check_pair(p, cohort));
         if (n == 0) return EPIK_AMD_OK;
         uint64_t longest = 0;
-        if (const int rc = check_host_reads(seqs, seq_offsets, n, longest); rc != EPIK_AMD_OK) return rc;
+        COHORT_TRY(check_host_reads(seqs, seq_offsets, n, longest));
         return cohort_host_chunked(p, cohort, seqs, seq_offsets, weights, samples, n, 0, longest, kForwardHost, nullptr);
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_reads: ") + e.what());
-    }
+    });
 }
 
 }  // extern "C"

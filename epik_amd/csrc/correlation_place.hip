@@ -27,17 +27,13 @@
 //                               dispersion.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 
 namespace {
 
@@ -77,23 +73,18 @@ struct CorrSpace {
 
 size_t correlation_space(void *base, uint32_t N, uint32_t padded, CorrSpace *sp)
 {
-    const size_t plane = (size_t)N * padded * sizeof(double), cols = (size_t)kColumns * padded * sizeof(double);
-    const size_t scratch = (size_t)kGeneralBlocks * kVectors * padded * sizeof(double);
-    const size_t lists = ((size_t)(kColumns + 1) * padded * sizeof(uint32_t) + 15) / 16 * 16;
-    if (sp) {
-        char *b = static_cast<char *>(base);
-        *sp = CorrSpace{reinterpret_cast<double *>(b),
-                        reinterpret_cast<double *>(b + plane),
-                        reinterpret_cast<double *>(b + plane + cols),
-                        reinterpret_cast<double *>(b + plane + 2 * cols),
-                        reinterpret_cast<double *>(b + plane + 3 * cols),
-                        reinterpret_cast<uint32_t *>(b + plane + 3 * cols + scratch),
-                        reinterpret_cast<CorrTables *>(b + plane + 3 * cols + scratch + lists)};
-    }
-    return plane + 3 * cols + scratch + lists + sizeof(CorrTables);
+    const size_t cols = (size_t)kColumns * padded;
+    Carver c(base);
+    const CorrSpace parts{.X = c.take<double>((size_t)N * padded),
+                          .y = c.take<double>(cols),
+                          .dy = c.take<double>(cols),
+                          .dr = c.take<double>(cols),
+                          .scratch = c.take<double>((size_t)kGeneralBlocks * kVectors * padded),
+                          .lists = c.take<uint32_t>((size_t)(kColumns + 1) * padded),
+                          .tab = c.take<CorrTables>(1)};
+    if (sp) *sp = parts;
+    return c.bytes();
 }
-
-__device__ inline double na_value() { return __longlong_as_double((long long)EPIK_AMD_NA_BITS); }
 
 __global__ __launch_bounds__(kBlock) void correlation_mass_kernel(const uint64_t *__restrict__ g_cells, const uint64_t *__restrict__ total,
                                                                   uint32_t num_samples, uint32_t num_branches, uint32_t padded,
@@ -265,28 +256,15 @@ __global__ __launch_bounds__(kBlock) void correlation_branch_kernel(const double
     }
 }
 
-dim3 grid_of(const epik_amd_cohort *cohort, uint64_t units, uint64_t most)
-{
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({units, most, cap})));
-}
-
-// EPIK_AMD_CORRELATION_LDS=0 (tests), read at the call: the general path whatever S
-bool lds_path(uint32_t S)
-{
-    const char *env = std::getenv("EPIK_AMD_CORRELATION_LDS");
-    return S <= kLdsSamples && !(env && std::strcmp(env, "0") == 0);
-}
-
 // the checks of epca_device, the device drained, T_s and the planes, the workspace, then xm as a plane
 int correlation_begin(epik_amd_cohort *cohort, const epik_amd_tree *tree, hipStream_t stream, const uint32_t **d_first, CorrSpace *sp)
 {
-    if (const int rc = cohort_normalise_enqueue(cohort, tree, stream, d_first); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(cohort_normalise_enqueue(cohort, tree, stream, d_first));
     const uint32_t N = cohort->num_branches, S = cohort->num_samples, padded = cohort_padded_samples(cohort);
-    if (!cohort->d_correlation) HIP_TRY(hipMalloc(&cohort->d_correlation, correlation_space(nullptr, N, padded, nullptr)));
-    correlation_space(cohort->d_correlation, N, padded, sp);
+    COHORT_TRY(cohort_space_ensure(cohort, kSpaceCorrelation, correlation_space(nullptr, N, padded, nullptr)));
+    correlation_space(cohort->space[kSpaceCorrelation].d, N, padded, sp);
     const uint64_t tiles = (uint64_t)((N + kTile - 1) / kTile) * (padded / kTile);
-    hipLaunchKernelGGL(correlation_mass_kernel, grid_of(cohort, tiles, kManyBlocks), dim3(kBlock), 0, stream, cohort->d_cells,
+    hipLaunchKernelGGL(correlation_mass_kernel, cohort_grid(cohort, tiles, kManyBlocks), dim3(kBlock), 0, stream, cohort->d_cells,
                        cohort->d_total, S, N, padded, sp->X);
     return EPIK_AMD_OK;
 }
@@ -296,31 +274,30 @@ void branch_launch(epik_amd_cohort *cohort, const CorrSpace &sp, const uint32_t 
 {
     const uint32_t N = cohort->num_branches, padded = cohort_padded_samples(cohort);
     const uint64_t units = (uint64_t)N * groups;
-    if (lds_path(cohort->num_samples))
-        hipLaunchKernelGGL((correlation_branch_kernel<true, kDisp>), grid_of(cohort, units, kManyBlocks), dim3(kBlock), 0, stream, sp.X,
+    if (lds_switch("EPIK_AMD_CORRELATION_LDS", cohort->num_samples, kLdsSamples))  // (=0, tests: the general path whatever S)
+        hipLaunchKernelGGL((correlation_branch_kernel<true, kDisp>), cohort_grid(cohort, units, kManyBlocks), dim3(kBlock), 0, stream, sp.X,
                            cohort->d_planes, d_first, sp.lists, sp.dy, sp.dr, sp.tab, N, padded, sp.scratch,
                            static_cast<double *>(d_out));
     else
-        hipLaunchKernelGGL((correlation_branch_kernel<false, kDisp>), grid_of(cohort, units, kGeneralBlocks), dim3(kBlock), 0, stream,
+        hipLaunchKernelGGL((correlation_branch_kernel<false, kDisp>), cohort_grid(cohort, units, kGeneralBlocks), dim3(kBlock), 0, stream,
                            sp.X, cohort->d_planes, d_first, sp.lists, sp.dy, sp.dr, sp.tab, N, padded, sp.scratch,
                            static_cast<double *>(d_out));
 }
 
-int check_columns(const double *meta, uint32_t num_samples, uint32_t num_columns)
+int check_values(const double *meta, uint32_t num_samples, uint32_t num_columns)
 {
     std::string err;
-    if (const int rc = correlation_columns_valid(meta, num_samples, num_columns, err); rc != EPIK_AMD_OK) return fail_with(rc, err);
-    return EPIK_AMD_OK;
+    return rule_result(correlation_columns_valid(meta, num_samples, num_columns, err), err);
 }
 
 int correlation_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *meta, uint32_t M, void *d_out,
                             void *d_used, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (M < 1 || M > kColumns) return fail_with(EPIK_AMD_ERR_INVALID, "num_columns = " + std::to_string(M) + " is outside [1, 64]");
-    if (!meta || !d_out || !d_used) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(check_columns(M));
+    COHORT_TRY(check_present(meta, d_out, d_used));
     const uint32_t S = cohort->num_samples, padded = cohort_padded_samples(cohort);
-    if (const int rc = check_columns(meta, S, M); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(check_values(meta, S, M));
     // the columns by sample, and their groups: columns with the same pattern of missing values have the same U_c
     std::vector<double> y((size_t)M * padded, 0.0);
     CorrTables tab{};
@@ -345,13 +322,13 @@ int correlation_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, 
     }
     const uint32_t *d_first = nullptr;
     CorrSpace sp;
-    if (const int rc = correlation_begin(cohort, tree, stream, &d_first, &sp); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(correlation_begin(cohort, tree, stream, &d_first, &sp));
     // (correlation_begin has drained the device of every call before: nothing reads the columns or the tables)
     HIP_TRY(hipMemcpy(sp.y, y.data(), y.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(sp.tab, &tab, sizeof tab, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(correlation_lists_kernel, grid_of(cohort, tab.num_groups, kColumns), dim3(kWave), 0, stream, cohort->d_total, sp.y,
+    hipLaunchKernelGGL(correlation_lists_kernel, cohort_grid(cohort, tab.num_groups, kColumns), dim3(kWave), 0, stream, cohort->d_total, sp.y,
                        S, padded, 0u, tab.num_groups, sp.lists, sp.tab);
-    hipLaunchKernelGGL(correlation_columns_kernel, grid_of(cohort, M, kColumns), dim3(kBlock), 0, stream, sp.y, sp.lists, M, padded, sp.dy,
+    hipLaunchKernelGGL(correlation_columns_kernel, cohort_grid(cohort, M, kColumns), dim3(kBlock), 0, stream, sp.y, sp.lists, M, padded, sp.dy,
                        sp.dr, sp.tab, static_cast<uint32_t *>(d_used));
     branch_launch<false>(cohort, sp, d_first, tab.num_groups, d_out, stream);
     HIP_TRY(hipGetLastError());
@@ -360,32 +337,16 @@ int correlation_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, 
 
 int dispersion_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, void *d_out, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (!d_out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(check_present(d_out));
     const uint32_t S = cohort->num_samples, padded = cohort_padded_samples(cohort);
     const uint32_t *d_first = nullptr;
     CorrSpace sp;
-    if (const int rc = correlation_begin(cohort, tree, stream, &d_first, &sp); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(correlation_begin(cohort, tree, stream, &d_first, &sp));
     hipLaunchKernelGGL(correlation_lists_kernel, dim3(1), dim3(kWave), 0, stream, cohort->d_total, sp.y, S, padded, kAllUsed, 1u,
                        sp.lists, sp.tab);
     branch_launch<true>(cohort, sp, d_first, 1, d_out, stream);
     HIP_TRY(hipGetLastError());
-    return EPIK_AMD_OK;
-}
-
-// a result in device memory for the synchronous entries, freed however the call ends
-struct Result {
-    void *d = nullptr;
-    ~Result()
-    {
-        if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-    }
-};
-
-int check_host(uint32_t num_samples, uint32_t num_branches)
-{
-    if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-    if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
     return EPIK_AMD_OK;
 }
 
@@ -397,7 +358,7 @@ int cohort_mass_plane_enqueue(epik_amd_cohort *cohort, const epik_amd_tree *tree
                               const double **d_X)
 {
     CorrSpace sp;
-    if (const int rc = correlation_begin(cohort, tree, stream, d_first, &sp); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(correlation_begin(cohort, tree, stream, d_first, &sp));
     *d_X = sp.X;
     return EPIK_AMD_OK;
 }
@@ -409,90 +370,68 @@ extern "C" {
 int epik_amd_cohort_correlation_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *meta, uint32_t num_columns,
                                        void *d_out, void *d_used, void *stream)
 {
-    try {
+    return guarded("cohort_correlation_device", [&]() -> int {
         return correlation_device_impl(cohort, tree, meta, num_columns, d_out, d_used, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_correlation_device: ") + e.what());
-    }
+    });
 }
 
 int epik_amd_cohort_correlation(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *meta, uint32_t num_columns,
                                 epik_amd_correlation *out, uint32_t *used)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (num_columns < 1 || num_columns > kColumns)
-            return fail_with(EPIK_AMD_ERR_INVALID, "num_columns = " + std::to_string(num_columns) + " is outside [1, 64]");
-        if (!meta || !out || !used) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_correlation", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(check_columns(num_columns));
+        COHORT_TRY(check_present(meta, out, used));
         const size_t bytes = (size_t)num_columns * cohort->num_branches * sizeof(epik_amd_correlation);
         HIP_TRY(hipSetDevice(cohort->device));
-        Result r, u;
-        HIP_TRY(hipMalloc(&r.d, bytes));
-        HIP_TRY(hipMalloc(&u.d, num_columns * sizeof(uint32_t)));
-        if (const int rc = correlation_device_impl(cohort, tree, meta, num_columns, r.d, u.d, nullptr); rc != EPIK_AMD_OK) return rc;
-        HIP_TRY(hipMemcpy(out, r.d, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(used, u.d, num_columns * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_correlation: ") + e.what());
-    }
+        DeviceResult r, u;
+        COHORT_TRY(r.alloc(bytes));
+        COHORT_TRY(u.alloc(num_columns * sizeof(uint32_t)));
+        COHORT_TRY(correlation_device_impl(cohort, tree, meta, num_columns, r.d, u.d, nullptr));
+        COHORT_TRY(r.copy_to(out, bytes));
+        return u.copy_to(used, num_columns * sizeof(uint32_t));
+    });
 }
 
 int epik_amd_cohort_correlation_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                      const double *meta, uint32_t num_columns, epik_amd_correlation *out, uint32_t *used)
 {
-    try {
-        if (const int rc = check_host(num_samples, num_branches); rc != EPIK_AMD_OK) return rc;
-        if (!mass || !first || !meta || !out || !used) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_correlation_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(check_present(mass, first, meta, out, used));
         std::string err;
-        if (const int rc = correlation_records(mass, num_samples, num_branches, first, meta, num_columns, out, used, err);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_correlation_host: ") + e.what());
-    }
+        return rule_result(correlation_records(mass, num_samples, num_branches, first, meta, num_columns, out, used, err), err);
+    });
 }
 
 int epik_amd_cohort_dispersion_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, void *d_out, void *stream)
 {
-    try {
-        return dispersion_device_impl(cohort, tree, d_out, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_dispersion_device: ") + e.what());
-    }
+    return guarded("cohort_dispersion_device", [&]() -> int { return dispersion_device_impl(cohort, tree, d_out, static_cast<hipStream_t>(stream)); });
 }
 
 int epik_amd_cohort_dispersion(epik_amd_cohort *cohort, const epik_amd_tree *tree, epik_amd_dispersion *out)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (!out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_dispersion", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(check_present(out));
         const size_t bytes = (size_t)cohort->num_branches * sizeof(epik_amd_dispersion);
         HIP_TRY(hipSetDevice(cohort->device));
-        Result r;
-        HIP_TRY(hipMalloc(&r.d, bytes));
-        if (const int rc = dispersion_device_impl(cohort, tree, r.d, nullptr); rc != EPIK_AMD_OK) return rc;
-        HIP_TRY(hipMemcpy(out, r.d, bytes, hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_dispersion: ") + e.what());
-    }
+        DeviceResult r;
+        COHORT_TRY(r.alloc(bytes));
+        COHORT_TRY(dispersion_device_impl(cohort, tree, r.d, nullptr));
+        return r.copy_to(out, bytes);
+    });
 }
 
 int epik_amd_cohort_dispersion_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                     epik_amd_dispersion *out)
 {
-    try {
-        if (const int rc = check_host(num_samples, num_branches); rc != EPIK_AMD_OK) return rc;
-        if (!mass || !first || !out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_dispersion_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(check_present(mass, first, out));
         std::string err;
-        if (const int rc = dispersion_records(mass, num_samples, num_branches, first, out, err); rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_dispersion_host: ") + e.what());
-    }
+        return rule_result(dispersion_records(mass, num_samples, num_branches, first, out, err), err);
+    });
 }
 
 }  // extern "C"

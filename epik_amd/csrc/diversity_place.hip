@@ -29,14 +29,12 @@
 // the kernel takes |Q| all the same.  The empty side is picked at the output.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <string>
 #include <vector>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 
 namespace {
 
@@ -65,14 +63,16 @@ uint32_t num_blocks_of(uint32_t N) { return (N + kDivBlock - 1) / kDivBlock; }
 
 size_t diversity_space(void *base, uint32_t S, uint32_t N, DiversitySpace *sp)
 {
-    const size_t cells = (size_t)S * N * sizeof(uint64_t), reads = ((size_t)S * sizeof(uint64_t) + 15) / 16 * 16;
-    const size_t partial = (size_t)S * num_blocks_of(N) * kIndices * sizeof(double);
-    if (sp) {
-        char *b = static_cast<char *>(base);
-        *sp = DiversitySpace{reinterpret_cast<uint64_t *>(b), reinterpret_cast<uint64_t *>(b + cells),
-                             reinterpret_cast<uint64_t *>(b + 2 * cells), reinterpret_cast<double *>(b + 2 * cells + reads)};
-    }
-    return 2 * cells + reads + partial;
+    // (cb and cc are one part, cc straight behind cb: S * N may be odd, and a part of its own would begin 8 bytes later)
+    const size_t cells = (size_t)S * N;
+    Carver c(base);
+    uint64_t *counts = c.take<uint64_t>(2 * cells);
+    const DiversitySpace parts{.cb = counts,
+                               .cc = counts ? counts + cells : nullptr,
+                               .reads = c.take<uint64_t>(S),
+                               .partial = c.take<double>((size_t)S * num_blocks_of(N) * kIndices)};
+    if (sp) *sp = parts;
+    return c.bytes();
 }
 
 __global__ __launch_bounds__(kBlock) void diversity_counts_kernel(const uint64_t *__restrict__ g_cells, const uint32_t *__restrict__ first,
@@ -281,38 +281,28 @@ int diversity_begin(epik_amd_cohort *cohort, const epik_amd_tree *tree, const do
                     const uint32_t **d_first, DiversitySpace *sp)
 {
     const uint32_t N = cohort->num_branches, S = cohort->num_samples;
-    std::vector<double> half(N);
-    for (uint32_t b = 0; b < N; ++b) {
-        if (!(branch_length[b] >= 0.0) || !std::isfinite(branch_length[b]))
-            return fail_with(EPIK_AMD_ERR_INVALID, "branch " + std::to_string(b) + ": the branch length is negative or not finite");
-        half[b] = 0.5 * branch_length[b];
-    }
-    if (const int rc = cohort_normalise_enqueue(cohort, tree, stream, d_first); rc != EPIK_AMD_OK) return rc;
+    std::vector<double> half;
+    COHORT_TRY(half_branch_lengths(branch_length, N, half));
+    COHORT_TRY(cohort_normalise_enqueue(cohort, tree, stream, d_first));
     HIP_TRY(hipMemcpy(cohort->d_half, half.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
-    if (!cohort->d_diversity) HIP_TRY(hipMalloc(&cohort->d_diversity, diversity_space(nullptr, S, N, nullptr)));
-    diversity_space(cohort->d_diversity, S, N, sp);
+    COHORT_TRY(cohort_space_ensure(cohort, kSpaceDiversity, diversity_space(nullptr, S, N, nullptr)));
+    diversity_space(cohort->space[kSpaceDiversity].d, S, N, sp);
     return EPIK_AMD_OK;
-}
-
-dim3 grid_of(const epik_amd_cohort *cohort, uint64_t units, uint64_t per)
-{
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(units + per - 1) / per, kManyBlocks, cap})));
 }
 
 int alpha_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_alpha,
                       hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (!branch_length || !d_alpha) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(check_present(branch_length, d_alpha));
     const uint32_t N = cohort->num_branches, S = cohort->num_samples, padded = cohort_padded_samples(cohort);
     const uint32_t *d_first = nullptr;
     DiversitySpace sp;
-    if (const int rc = diversity_begin(cohort, tree, branch_length, stream, &d_first, &sp); rc != EPIK_AMD_OK) return rc;
-    hipLaunchKernelGGL(diversity_alpha_kernel, grid_of(cohort, (uint64_t)S * num_blocks_of(N), 1), dim3(kBlock), 0, stream,
+    COHORT_TRY(diversity_begin(cohort, tree, branch_length, stream, &d_first, &sp));
+    hipLaunchKernelGGL(diversity_alpha_kernel, cohort_grid(cohort, (uint64_t)S * num_blocks_of(N), kManyBlocks), dim3(kBlock), 0, stream,
                        cohort->d_cells, d_first, cohort->d_prefix, cohort->d_total, cohort->d_planes, cohort->d_half, S, N, padded,
                        sp.partial);
-    hipLaunchKernelGGL(diversity_finish_alpha_kernel, grid_of(cohort, (uint64_t)S * kIndices, kBlock), dim3(kBlock), 0, stream,
+    hipLaunchKernelGGL(diversity_finish_alpha_kernel, cohort_grid_per(cohort, (uint64_t)S * kIndices, kBlock, kManyBlocks), dim3(kBlock), 0, stream,
                        sp.partial, cohort->d_total, S, N, static_cast<double *>(d_alpha));
     HIP_TRY(hipGetLastError());
     return EPIK_AMD_OK;
@@ -321,55 +311,39 @@ int alpha_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const 
 int check_depths(uint32_t depth_step, uint32_t num_depths)
 {
     std::string err;
-    if (const int rc = rarefy_depths_valid(depth_step, num_depths, err); rc != EPIK_AMD_OK) return fail_with(rc, err);
-    return EPIK_AMD_OK;
+    return rule_result(rarefy_depths_valid(depth_step, num_depths, err), err);
 }
 
 int rarefy_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t depth_step,
                        uint32_t num_depths, void *d_curve, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (!branch_length || !d_curve) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
-    if (const int rc = check_depths(depth_step, num_depths); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(check_present(branch_length, d_curve));
+    COHORT_TRY(check_depths(depth_step, num_depths));
     const uint32_t N = cohort->num_branches, S = cohort->num_samples;
     const uint32_t *d_first = nullptr;
     DiversitySpace sp;
-    if (const int rc = diversity_begin(cohort, tree, branch_length, stream, &d_first, &sp); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(diversity_begin(cohort, tree, branch_length, stream, &d_first, &sp));
     // the block partials of the curve, [S][G][J][2]: kept, and allocated anew only for more depths than any call before
-    if (cohort->rarefy_depths < num_depths) {
-        (void)hipFree(cohort->d_rarefy);  // (diversity_begin has drained the device)
-        cohort->d_rarefy = nullptr, cohort->rarefy_depths = 0;
-        HIP_TRY(hipMalloc(&cohort->d_rarefy, (size_t)S * num_blocks_of(N) * num_depths * 2 * sizeof(double)));
-        cohort->rarefy_depths = num_depths;
-    }
-    double *partial = static_cast<double *>(cohort->d_rarefy);
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    hipLaunchKernelGGL(diversity_counts_kernel, dim3((uint32_t)std::min<uint64_t>({S, kManyBlocks, cap})), dim3(kBlock), 0, stream,
-                       cohort->d_cells, d_first, S, N, sp.cb, sp.cc, sp.reads);
-    hipLaunchKernelGGL(diversity_rarefy_kernel, grid_of(cohort, (uint64_t)S * num_blocks_of(N), 1), dim3(kBlock), 0, stream, sp.cb,
+    // (diversity_begin has drained the device)
+    COHORT_TRY(cohort_space_ensure(cohort, kSpaceRarefy, (size_t)S * num_blocks_of(N) * num_depths * 2 * sizeof(double)));
+    double *partial = static_cast<double *>(cohort->space[kSpaceRarefy].d);
+    hipLaunchKernelGGL(diversity_counts_kernel, cohort_grid(cohort, S, kManyBlocks), dim3(kBlock), 0, stream, cohort->d_cells, d_first, S, N,
+                       sp.cb, sp.cc, sp.reads);
+    hipLaunchKernelGGL(diversity_rarefy_kernel, cohort_grid(cohort, (uint64_t)S * num_blocks_of(N), kManyBlocks), dim3(kBlock), 0, stream, sp.cb,
                        sp.cc, sp.reads, cohort->d_half, S, N, depth_step, num_depths, partial);
-    hipLaunchKernelGGL(diversity_finish_rarefy_kernel, grid_of(cohort, (uint64_t)S * num_depths * 2, kBlock), dim3(kBlock), 0, stream,
+    hipLaunchKernelGGL(diversity_finish_rarefy_kernel, cohort_grid_per(cohort, (uint64_t)S * num_depths * 2, kBlock, kManyBlocks), dim3(kBlock), 0, stream,
                        partial, sp.reads, S, N, depth_step, num_depths, static_cast<double *>(d_curve));
     HIP_TRY(hipGetLastError());
     return EPIK_AMD_OK;
 }
 
-// a result in device memory for the synchronous entries, freed however the call ends
-struct Result {
-    void *d = nullptr;
-    ~Result()
-    {
-        if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-    }
-};
-
+// the shape and the arguments of a _host entry
 int check_host(uint32_t num_samples, uint32_t num_branches, const void *cells, const uint32_t *first, const double *branch_length,
                const void *out)
 {
-    if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-    if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
-    if (!cells || !first || !branch_length || !out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
-    return EPIK_AMD_OK;
+    COHORT_TRY(check_host_shape(num_samples, num_branches));
+    return check_present(cells, first, branch_length, out);
 }
 
 }  // namespace
@@ -379,88 +353,66 @@ extern "C" {
 int epik_amd_cohort_alpha_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_alpha,
                                  void *stream)
 {
-    try {
-        return alpha_device_impl(cohort, tree, branch_length, d_alpha, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_alpha_device: ") + e.what());
-    }
+    return guarded("cohort_alpha_device", [&]() -> int { return alpha_device_impl(cohort, tree, branch_length, d_alpha, static_cast<hipStream_t>(stream)); });
 }
 
 int epik_amd_cohort_alpha(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, epik_amd_alpha *alpha)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (!alpha) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_alpha", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(check_present(alpha));
         const size_t bytes = (size_t)cohort->num_samples * sizeof(epik_amd_alpha);
         HIP_TRY(hipSetDevice(cohort->device));
-        Result r;
-        HIP_TRY(hipMalloc(&r.d, bytes));
-        if (const int rc = alpha_device_impl(cohort, tree, branch_length, r.d, nullptr); rc != EPIK_AMD_OK) return rc;
-        HIP_TRY(hipMemcpy(alpha, r.d, bytes, hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_alpha: ") + e.what());
-    }
+        DeviceResult r;
+        COHORT_TRY(r.alloc(bytes));
+        COHORT_TRY(alpha_device_impl(cohort, tree, branch_length, r.d, nullptr));
+        return r.copy_to(alpha, bytes);
+    });
 }
 
 int epik_amd_cohort_alpha_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                const double *branch_length, epik_amd_alpha *alpha)
 {
-    try {
-        if (const int rc = check_host(num_samples, num_branches, mass, first, branch_length, alpha); rc != EPIK_AMD_OK) return rc;
+    return guarded("cohort_alpha_host", [&]() -> int {
+        COHORT_TRY(check_host(num_samples, num_branches, mass, first, branch_length, alpha));
         std::string err;
-        if (const int rc = alpha_indices(mass, num_samples, num_branches, first, branch_length, alpha, err); rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_alpha_host: ") + e.what());
-    }
+        return rule_result(alpha_indices(mass, num_samples, num_branches, first, branch_length, alpha, err), err);
+    });
 }
 
 int epik_amd_cohort_rarefy_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
                                   uint32_t depth_step, uint32_t num_depths, void *d_curve, void *stream)
 {
-    try {
+    return guarded("cohort_rarefy_device", [&]() -> int {
         return rarefy_device_impl(cohort, tree, branch_length, depth_step, num_depths, d_curve, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_rarefy_device: ") + e.what());
-    }
+    });
 }
 
 int epik_amd_cohort_rarefy(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t depth_step,
                            uint32_t num_depths, double *curve)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (!curve) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
-        if (const int rc = check_depths(depth_step, num_depths); rc != EPIK_AMD_OK) return rc;
+    return guarded("cohort_rarefy", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(check_present(curve));
+        COHORT_TRY(check_depths(depth_step, num_depths));
         const size_t bytes = (size_t)cohort->num_samples * num_depths * 2 * sizeof(double);
         HIP_TRY(hipSetDevice(cohort->device));
-        Result r;
-        HIP_TRY(hipMalloc(&r.d, bytes));
-        if (const int rc = rarefy_device_impl(cohort, tree, branch_length, depth_step, num_depths, r.d, nullptr); rc != EPIK_AMD_OK)
-            return rc;
-        HIP_TRY(hipMemcpy(curve, r.d, bytes, hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_rarefy: ") + e.what());
-    }
+        DeviceResult r;
+        COHORT_TRY(r.alloc(bytes));
+        COHORT_TRY(rarefy_device_impl(cohort, tree, branch_length, depth_step, num_depths, r.d, nullptr));
+        return r.copy_to(curve, bytes);
+    });
 }
 
 int epik_amd_cohort_rarefy_host(const uint64_t *best, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                 const double *branch_length, uint32_t depth_step, uint32_t num_depths, double *curve)
 {
-    try {
-        if (const int rc = check_depths(depth_step, num_depths); rc != EPIK_AMD_OK) return rc;
-        if (const int rc = check_host(num_samples, num_branches, best, first, branch_length, curve); rc != EPIK_AMD_OK) return rc;
+    return guarded("cohort_rarefy_host", [&]() -> int {
+        COHORT_TRY(check_depths(depth_step, num_depths));
+        COHORT_TRY(check_host(num_samples, num_branches, best, first, branch_length, curve));
         std::string err;
-        if (const int rc = rarefy_curves(best, num_samples, num_branches, first, branch_length, depth_step, num_depths, curve, err);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_rarefy_host: ") + e.what());
-    }
+        return rule_result(rarefy_curves(best, num_samples, num_branches, first, branch_length, depth_step, num_depths, curve, err), err);
+    });
 }
 
 }  // extern "C"

@@ -36,14 +36,11 @@
 
 #include <algorithm>
 #include <cstddef>
-#include <cstdlib>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 
 namespace {
 
@@ -87,29 +84,21 @@ struct EdgeSpace {
 
 size_t edgetest_space(void *base, uint32_t N, uint32_t padded, uint32_t M, uint32_t P, EdgeSpace *sp)
 {
-    const auto up = [](size_t v) { return (v + 15) / 16 * 16; };
-    const size_t d = (size_t)N * kFamilies * padded * 8, scratch = (size_t)kGeneralBlocks * kFamilies * padded * 8;
-    const size_t sxx = (size_t)N * kFamilies * 8, mmax = up((size_t)kFamilies * ((size_t)P + 1) * 8), mu = (size_t)padded * kChunk;
-    const size_t lab = (size_t)M * padded * 4, defined = up((size_t)N * 4), active = up(((size_t)N + 1 + kFamilies) * 4);
-    const size_t cols = up(M * sizeof(EdgeColumn)), lam = (size_t)M * padded;
-    if (sp) {
-        char *b = static_cast<char *>(base);
-        sp->D = reinterpret_cast<double *>(b), b += d;
-        sp->scratch = reinterpret_cast<double *>(b), b += scratch;
-        sp->sxx = reinterpret_cast<double *>(b), b += sxx;
-        sp->mmax = reinterpret_cast<uint64_t *>(b), b += mmax;
-        sp->MU = reinterpret_cast<uint32_t *>(b), b += mu;
-        sp->lab = reinterpret_cast<uint32_t *>(b), b += lab;
-        sp->idx = reinterpret_cast<uint32_t *>(b), b += lab;
-        sp->defined = reinterpret_cast<uint32_t *>(b), b += defined;
-        sp->active = reinterpret_cast<uint32_t *>(b), b += active;
-        sp->cols = reinterpret_cast<EdgeColumn *>(b), b += cols;
-        sp->lam = reinterpret_cast<uint8_t *>(b);
-    }
-    return d + scratch + sxx + mmax + mu + 2 * lab + defined + active + cols + lam;
+    Carver c(base);
+    const EdgeSpace parts{.D = c.take<double>((size_t)N * kFamilies * padded),
+                          .scratch = c.take<double>((size_t)kGeneralBlocks * kFamilies * padded),
+                          .sxx = c.take<double>((size_t)N * kFamilies),
+                          .mmax = c.take<uint64_t>((size_t)kFamilies * ((size_t)P + 1)),
+                          .MU = c.take<uint32_t>((size_t)padded * kChunk / 4),
+                          .lab = c.take<uint32_t>((size_t)M * padded),
+                          .idx = c.take<uint32_t>((size_t)M * padded),
+                          .defined = c.take<uint32_t>(N),
+                          .active = c.take<uint32_t>((size_t)N + 1 + kFamilies),
+                          .cols = c.take<EdgeColumn>(M),
+                          .lam = c.take<uint8_t>((size_t)M * padded)};
+    if (sp) *sp = parts;
+    return c.bytes();
 }
-
-__device__ inline double na_value() { return __longlong_as_double((long long)EPIK_AMD_NA_BITS); }
 
 __global__ __launch_bounds__(kWave) void edgetest_columns_kernel(const uint64_t *__restrict__ total, const uint32_t *__restrict__ lab,
                                                                  uint32_t num_samples, uint32_t padded, uint32_t num_columns,
@@ -384,19 +373,6 @@ __global__ __launch_bounds__(kBlock) void edgetest_finish_kernel(const EdgeArgs 
         }
 }
 
-dim3 grid_of(const epik_amd_cohort *cohort, uint64_t units, uint64_t most)
-{
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({units, most, cap})));
-}
-
-// EPIK_AMD_EDGETEST_LDS=0 (tests), read at the call: the general path whatever S
-bool lds_path(uint32_t S)
-{
-    const char *env = std::getenv("EPIK_AMD_EDGETEST_LDS");
-    return S <= kLdsPositions && !(env && std::strcmp(env, "0") == 0);
-}
-
 template <uint32_t kG>
 void chains_launch(bool lds, dim3 grid, uint32_t lanes, size_t dynamic, hipStream_t stream, const EdgeArgs &args)
 {
@@ -409,46 +385,30 @@ void chains_launch(bool lds, dim3 grid, uint32_t lanes, size_t dynamic, hipStrea
 int check_arguments(const uint32_t *labels, uint32_t S, uint32_t M, uint32_t P)
 {
     std::string err;
-    if (const int rc = edgetest_arguments_valid(labels, S, M, P, err); rc != EPIK_AMD_OK) return fail_with(rc, err);
-    return EPIK_AMD_OK;
+    return rule_result(edgetest_arguments_valid(labels, S, M, P, err), err);
 }
 
 int edgetest_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels, uint32_t M, uint32_t P,
                          uint64_t seed, void *d_out, void *d_stat, void *d_max, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (M < 1 || M > kColumns) return fail_with(EPIK_AMD_ERR_INVALID, "num_columns = " + std::to_string(M) + " is outside [1, 64]");
-    if (!tree || !labels || !d_out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(check_columns(M));
+    COHORT_TRY(check_present(tree, labels, d_out));
     const uint32_t S = cohort->num_samples, N = cohort->num_branches, padded = cohort_padded_samples(cohort);
-    if (const int rc = check_arguments(labels, S, M, P); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(check_arguments(labels, S, M, P));
     // the largest G of a column decides where the accumulators are: the distinct labels bound it
-    uint32_t most_groups = 0;
-    for (uint32_t c = 0; c < M; ++c) {
-        uint32_t seen = 0;
-        for (uint32_t s = 0; s < S; ++s)
-            if (const uint32_t v = labels[(size_t)s * M + c]; v != kMissing) seen |= 1u << v;
-        most_groups = std::max<uint32_t>(most_groups, (uint32_t)__builtin_popcount(seen));
-    }
+    const uint32_t most_groups = most_distinct_labels(labels, S, M, kMissing);
     const uint32_t *d_first = nullptr;
     const double *d_X = nullptr;
     // (the checks of the tree; the device drained of every call before: nothing reads the workspace)
-    if (const int rc = cohort_mass_plane_enqueue(cohort, tree, stream, &d_first, &d_X); rc != EPIK_AMD_OK) return rc;
-    const size_t bytes = edgetest_space(nullptr, N, padded, M, P, nullptr);
-    if (bytes > cohort->edgetest_bytes) {
-        (void)hipFree(cohort->d_edgetest);
-        cohort->d_edgetest = nullptr, cohort->edgetest_bytes = 0;
-        HIP_TRY(hipMalloc(&cohort->d_edgetest, bytes));
-        cohort->edgetest_bytes = bytes;
-    }
+    COHORT_TRY(cohort_mass_plane_enqueue(cohort, tree, stream, &d_first, &d_X));
+    COHORT_TRY(cohort_space_ensure(cohort, kSpaceEdgetest, edgetest_space(nullptr, N, padded, M, P, nullptr)));
     EdgeSpace sp;
-    edgetest_space(cohort->d_edgetest, N, padded, M, P, &sp);
-    std::vector<uint32_t> lab((size_t)M * padded, kMissing);
-    for (uint32_t s = 0; s < S; ++s)
-        for (uint32_t c = 0; c < M; ++c) lab[(size_t)c * padded + s] = labels[(size_t)s * M + c];
-    HIP_TRY(hipMemcpy(sp.lab, lab.data(), lab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(edgetest_columns_kernel, grid_of(cohort, M, kColumns), dim3(kWave), 0, stream, cohort->d_total, sp.lab, S, padded, M,
+    edgetest_space(cohort->space[kSpaceEdgetest].d, N, padded, M, P, &sp);
+    COHORT_TRY(upload_labels_by_column(labels, S, M, padded, kMissing, sp.lab));
+    hipLaunchKernelGGL(edgetest_columns_kernel, cohort_grid(cohort, M, kColumns), dim3(kWave), 0, stream, cohort->d_total, sp.lab, S, padded, M,
                        sp.idx, sp.lam, sp.cols);
-    const bool lds = lds_path(S);
+    const bool lds = lds_switch("EPIK_AMD_EDGETEST_LDS", S, kLdsPositions);  // (=0, tests: the general path whatever S)
     const uint32_t lanes = most_groups <= kRegisterGroups ? kBlock : kLdsLanes;
     const size_t dynamic = (lds ? (size_t)2 * padded * 8 : 0) + (most_groups <= kRegisterGroups ? 0 : (size_t)most_groups * lanes * 8);
     const uint64_t row = (uint64_t)P + 1;
@@ -459,14 +419,14 @@ int edgetest_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, con
         HIP_TRY(hipMemsetAsync(sp.active + N, 0, (1 + kFamilies) * sizeof(uint32_t), stream));
         HIP_TRY(hipMemsetAsync(sp.mmax, 0, kFamilies * row * sizeof(uint64_t), stream));
         if (lds)
-            hipLaunchKernelGGL((edgetest_observed_kernel<true>), grid_of(cohort, N, kManyBlocks), dim3(kBlock), 0, stream, args);
+            hipLaunchKernelGGL((edgetest_observed_kernel<true>), cohort_grid(cohort, N, kManyBlocks), dim3(kBlock), 0, stream, args);
         else
-            hipLaunchKernelGGL((edgetest_observed_kernel<false>), grid_of(cohort, N, kGeneralBlocks), dim3(kBlock), 0, stream, args);
+            hipLaunchKernelGGL((edgetest_observed_kernel<false>), cohort_grid(cohort, N, kGeneralBlocks), dim3(kBlock), 0, stream, args);
         for (uint64_t p0 = 0; p0 < row; p0 += kChunk) {
             args.p0 = (uint32_t)p0, args.np = (uint32_t)std::min<uint64_t>(kChunk, row - p0);
-            hipLaunchKernelGGL(edgetest_labellings_kernel, grid_of(cohort, args.np, kManyBlocks), dim3(kBlock), 0, stream, args);
+            hipLaunchKernelGGL(edgetest_labellings_kernel, cohort_grid(cohort, args.np, kManyBlocks), dim3(kBlock), 0, stream, args);
             const uint64_t subs = (args.np + lanes - 1) / lanes;
-            const dim3 grid = grid_of(cohort, (uint64_t)N * subs, kManyBlocks);
+            const dim3 grid = cohort_grid(cohort, (uint64_t)N * subs, kManyBlocks);
             if (most_groups <= 2)
                 chains_launch<2>(lds, grid, lanes, dynamic, stream, args);
             else if (most_groups <= kRegisterGroups)
@@ -475,20 +435,11 @@ int edgetest_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, con
                 chains_launch<0>(lds, grid, lanes, dynamic, stream, args);
         }
         const uint64_t finish = d_stat ? (uint64_t)N * kFamilies * row : std::max<uint64_t>((uint64_t)N * kFamilies, d_max ? kFamilies * row : 0);
-        hipLaunchKernelGGL(edgetest_finish_kernel, grid_of(cohort, (finish + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, args);
+        hipLaunchKernelGGL(edgetest_finish_kernel, cohort_grid(cohort, (finish + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, args);
     }
     HIP_TRY(hipGetLastError());
     return EPIK_AMD_OK;
 }
-
-// a result in device memory for the synchronous entry, freed however the call ends
-struct Result {
-    void *d = nullptr;
-    ~Result()
-    {
-        if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-    }
-};
 
 }  // namespace
 
@@ -497,61 +448,48 @@ extern "C" {
 int epik_amd_cohort_edgetest_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels, uint32_t num_columns,
                                     uint32_t num_permutations, uint64_t seed, void *d_out, void *d_stat, void *d_max, void *stream)
 {
-    try {
+    return guarded("cohort_edgetest_device", [&]() -> int {
         return edgetest_device_impl(cohort, tree, labels, num_columns, num_permutations, seed, d_out, d_stat, d_max,
                                     static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_edgetest_device: ") + e.what());
-    }
+    });
 }
 
 int epik_amd_cohort_edgetest(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels, uint32_t num_columns,
                              uint32_t num_permutations, uint64_t seed, epik_amd_edgetest *out, double *stat, double *max)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (num_columns < 1 || num_columns > kColumns)
-            return fail_with(EPIK_AMD_ERR_INVALID, "num_columns = " + std::to_string(num_columns) + " is outside [1, 64]");
-        if (!tree || !labels || !out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
-        if (const int rc = check_arguments(labels, cohort->num_samples, num_columns, num_permutations); rc != EPIK_AMD_OK) return rc;
+    return guarded("cohort_edgetest", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(check_columns(num_columns));
+        COHORT_TRY(check_present(tree, labels, out));
+        COHORT_TRY(check_arguments(labels, cohort->num_samples, num_columns, num_permutations));
         const size_t row = (size_t)num_permutations + 1, N = cohort->num_branches;
         const size_t out_bytes = (size_t)num_columns * N * sizeof(epik_amd_edgetest);
         const size_t stat_bytes = (size_t)num_columns * kFamilies * N * row * sizeof(double);
         const size_t max_bytes = (size_t)num_columns * kFamilies * row * sizeof(double);
         HIP_TRY(hipSetDevice(cohort->device));
-        Result r, s, m;
-        HIP_TRY(hipMalloc(&r.d, out_bytes));
-        if (stat) HIP_TRY(hipMalloc(&s.d, stat_bytes));
-        if (max) HIP_TRY(hipMalloc(&m.d, max_bytes));
-        if (const int rc = edgetest_device_impl(cohort, tree, labels, num_columns, num_permutations, seed, r.d, s.d, m.d, nullptr);
-            rc != EPIK_AMD_OK)
-            return rc;
-        HIP_TRY(hipMemcpy(out, r.d, out_bytes, hipMemcpyDeviceToHost));
-        if (stat) HIP_TRY(hipMemcpy(stat, s.d, stat_bytes, hipMemcpyDeviceToHost));
-        if (max) HIP_TRY(hipMemcpy(max, m.d, max_bytes, hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_edgetest: ") + e.what());
-    }
+        DeviceResult r, s, m;
+        COHORT_TRY(r.alloc(out_bytes));
+        COHORT_TRY(s.alloc(stat_bytes, stat != nullptr));
+        COHORT_TRY(m.alloc(max_bytes, max != nullptr));
+        COHORT_TRY(edgetest_device_impl(cohort, tree, labels, num_columns, num_permutations, seed, r.d, s.d, m.d, nullptr));
+        COHORT_TRY(r.copy_to(out, out_bytes));
+        COHORT_TRY(s.copy_to(stat, stat_bytes));
+        return m.copy_to(max, max_bytes);
+    });
 }
 
 int epik_amd_cohort_edgetest_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                   const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
                                   epik_amd_edgetest *out, double *stat, double *max)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
-        if (!mass || !first || !labels || !out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_edgetest_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(check_present(mass, first, labels, out));
         std::string err;
-        if (const int rc = edgetest_records(mass, num_samples, num_branches, first, labels, num_columns, num_permutations, seed, out, stat,
-                                            max, err);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_edgetest_host: ") + e.what());
-    }
+        return rule_result(edgetest_records(mass, num_samples, num_branches, first, labels, num_columns, num_permutations, seed, out, stat,
+                                            max, err),
+                           err);
+    });
 }
 
 }  // extern "C"

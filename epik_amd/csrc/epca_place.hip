@@ -24,14 +24,11 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 #include "jacobi_device.hpp"
 
 namespace {
@@ -66,25 +63,27 @@ struct EpcaSpace {
 
 size_t epca_space(void *base, uint32_t S, uint32_t N, uint32_t padded, EpcaSpace *sp)
 {
-    size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t offset = at;
-        at += (bytes + 15) / 16 * 16;
-        return offset;
-    };
-    const size_t dd = sizeof(double), uu = sizeof(uint32_t), SS = (size_t)S * S;
-    const size_t Y = take((size_t)N * padded * dd), A = take(SS * dd), A1 = take(SS * dd), V = take(SS * dd);
-    const size_t cs = take(S * dd), sn = take(S * dd), gs = take(4 * dd), root = take(kMaxK * dd), sign = take(kMaxK * dd);
-    const size_t used = take(S * uu), jof = take(S * uu), partner = take(S * uu), count = take(uu);
-    const size_t counters = take(kMaxSweeps * uu), status = take(2 * uu), column = take(kMaxK * uu), null_k = take(kMaxK * uu);
-    if (sp) {
-        char *b = static_cast<char *>(base);
-        const auto d = [&](size_t o) { return reinterpret_cast<double *>(b + o); };
-        const auto u = [&](size_t o) { return reinterpret_cast<uint32_t *>(b + o); };
-        *sp = EpcaSpace{d(Y), d(A), d(A1), d(V), d(cs), d(sn), d(gs), d(root), d(sign), u(used), u(jof), u(partner), u(count),
-                        u(counters), u(status), u(column), u(null_k)};
-    }
-    return at;
+    const size_t SS = (size_t)S * S;
+    Carver c(base);
+    const EpcaSpace parts{.Y = c.take<double>((size_t)N * padded),
+                          .A = c.take<double>(SS),
+                          .A1 = c.take<double>(SS),
+                          .V = c.take<double>(SS),
+                          .cs = c.take<double>(S),
+                          .sn = c.take<double>(S),
+                          .gs = c.take<double>(4),
+                          .root = c.take<double>(kMaxK),
+                          .sign = c.take<double>(kMaxK),
+                          .used = c.take<uint32_t>(S),
+                          .jof = c.take<uint32_t>(S),
+                          .partner = c.take<uint32_t>(S),
+                          .count = c.take<uint32_t>(1),
+                          .counters = c.take<uint32_t>(kMaxSweeps),
+                          .status = c.take<uint32_t>(2),
+                          .column = c.take<uint32_t>(kMaxK),
+                          .null_k = c.take<uint32_t>(kMaxK)};
+    if (sp) *sp = parts;
+    return c.bytes();
 }
 
 __global__ __launch_bounds__(kBlock) void epca_centre_kernel(const double *__restrict__ planes, const uint32_t *__restrict__ first,
@@ -268,25 +267,27 @@ __global__ __launch_bounds__(kBlock) void epca_finish_kernel(double *__restrict_
         *info = epik_amd_epca_info{L, Kc, status ? status[0] : sweeps, status ? status[1] : converged, gs[1], gs[0]};
 }
 
+int components_valid(uint32_t K)
+{
+    if (K < 1 || K > kMaxK) return fail_with(EPIK_AMD_ERR_INVALID, "num_components = " + std::to_string(K) + " is outside [1, 64]");
+    return EPIK_AMD_OK;
+}
+
 int epca_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_t K, void *d_mu, void *d_proj, void *d_edge,
                      void *d_info, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (K < 1 || K > kMaxK)
-        return fail_with(EPIK_AMD_ERR_INVALID, "num_components = " + std::to_string(K) + " is outside [1, 64]");
-    if (!d_mu || !d_proj || !d_edge || !d_info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
-    // the checks of the tree, the planes' workspace, T_s and the planes
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(components_valid(K));
+    COHORT_TRY(check_present(d_mu, d_proj, d_edge, d_info));
+    // the checks of the tree, the device drained, the planes' workspace, T_s and the planes
     const uint32_t *d_first = nullptr;
-    if (const int rc = cohort_normalise_enqueue(cohort, tree, stream, &d_first); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(cohort_normalise_enqueue(cohort, tree, stream, &d_first));
     const uint32_t N = cohort->num_branches, S = cohort->num_samples, padded = cohort_padded_samples(cohort);
-    if (!cohort->d_epca) HIP_TRY(hipMalloc(&cohort->d_epca, epca_space(nullptr, S, N, padded, nullptr)));
+    COHORT_TRY(cohort_space_ensure(cohort, kSpaceEpca, epca_space(nullptr, S, N, padded, nullptr)));
     EpcaSpace sp;
-    epca_space(cohort->d_epca, S, N, padded, &sp);
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    const auto blocks = [&](uint64_t units, uint64_t per, uint64_t most) {
-        return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(units + per - 1) / per, most, cap})));
-    };
-    if (const int rc = cohort_used_index_enqueue(cohort, sp.used, sp.jof, sp.count, stream); rc != EPIK_AMD_OK) return rc;
+    epca_space(cohort->space[kSpaceEpca].d, S, N, padded, &sp);
+    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;  // (the eigensolver's)
+    COHORT_TRY(cohort_used_index_enqueue(cohort, sp.used, sp.jof, sp.count, stream));
     uint32_t L = 0;
     HIP_TRY(hipMemcpyAsync(&L, sp.count, sizeof L, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -294,29 +295,27 @@ int epca_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_
     const uint32_t Lp = (L + kTile - 1) / kTile * kTile, Kc = std::min(K, L);
     const uint64_t cells = (uint64_t)L * L;
     if (L) {
-        hipLaunchKernelGGL(epca_centre_kernel, blocks(N, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, cohort->d_planes, d_first,
+        hipLaunchKernelGGL(epca_centre_kernel, cohort_grid_per(cohort, N, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, cohort->d_planes, d_first,
                            sp.used, N, padded, L, Lp, sp.Y);
         const uint64_t side = Lp / kTile;
-        hipLaunchKernelGGL(epca_gram_kernel, blocks(side * (side + 1) / 2, 1, kGramBlocks), dim3(kBlock), 0, stream, sp.Y, N, L, Lp,
+        hipLaunchKernelGGL(epca_gram_kernel, cohort_grid_per(cohort, side * (side + 1) / 2, 1, kGramBlocks), dim3(kBlock), 0, stream, sp.Y, N, L, Lp,
                            sp.A);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(epca_scale_kernel, blocks(cells, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, sp.A, L, sp.gs, sp.V, sp.counters);
+    hipLaunchKernelGGL(epca_scale_kernel, cohort_grid_per(cohort, cells, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, sp.A, L, sp.gs, sp.V, sp.counters);
     HIP_TRY(hipGetLastError());
-    // EPIK_AMD_EPCA_LDS=0 (tests), read at the call: the global path whatever L
-    const char *env = std::getenv("EPIK_AMD_EPCA_LDS");
-    const bool lds = L <= kJacobiLdsSide && !(env && std::strcmp(env, "0") == 0);
+    const bool lds = lds_switch("EPIK_AMD_EPCA_LDS", L, kJacobiLdsSide);  // (=0, tests: the global path whatever L)
     uint32_t sweeps = 1, converged = 1;  // (L = 0: one empty sweep)
     if (L) {
         const JacobiSpace js{sp.A, sp.A1, sp.V, sp.cs, sp.sn, sp.gs, sp.partner, sp.counters, sp.status};
-        if (const int rc = jacobi_sweeps(js, L, lds, cap, stream, sweeps, converged); rc != EPIK_AMD_OK) return rc;
+        COHORT_TRY(jacobi_sweeps(js, L, lds, cap, stream, sweeps, converged));
     }
     auto *mu = static_cast<double *>(d_mu), *proj = static_cast<double *>(d_proj), *edge = static_cast<double *>(d_edge);
     hipLaunchKernelGGL(epca_order_kernel, dim3(1), dim3(kBlock), 0, stream, sp.A, L, K, Kc, sp.gs, sp.column, sp.null_k, sp.root, mu);
-    hipLaunchKernelGGL(epca_raw_kernel, blocks((uint64_t)K * N, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, sp.V, sp.Y, L, Lp, N, K,
+    hipLaunchKernelGGL(epca_raw_kernel, cohort_grid_per(cohort, (uint64_t)K * N, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, sp.V, sp.Y, L, Lp, N, K,
                        Kc, sp.column, sp.null_k, edge);
-    hipLaunchKernelGGL(epca_sign_kernel, blocks(std::max(Kc, 1u), 1, kMaxBlocks), dim3(kBlock), 0, stream, edge, N, Kc, sp.sign);
-    hipLaunchKernelGGL(epca_finish_kernel, blocks((uint64_t)K * N + (uint64_t)S * K, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, edge,
+    hipLaunchKernelGGL(epca_sign_kernel, cohort_grid_per(cohort, std::max(Kc, 1u), 1, kMaxBlocks), dim3(kBlock), 0, stream, edge, N, Kc, sp.sign);
+    hipLaunchKernelGGL(epca_finish_kernel, cohort_grid_per(cohort, (uint64_t)K * N + (uint64_t)S * K, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, edge,
                        proj, sp.V, sp.jof, sp.column, sp.null_k, sp.root, sp.sign, S, N, K, Kc, L, sp.gs,
                        L && lds ? sp.status : nullptr, sweeps, converged, static_cast<epik_amd_epca_info *>(d_info));
     HIP_TRY(hipGetLastError());
@@ -330,60 +329,41 @@ extern "C" {
 int epik_amd_cohort_epca_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_t num_components, void *d_mu,
                                 void *d_proj, void *d_edge, void *d_info, void *stream)
 {
-    try {
+    return guarded("cohort_epca_device", [&]() -> int {
         return epca_device_impl(cohort, tree, num_components, d_mu, d_proj, d_edge, d_info, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_epca_device: ") + e.what());
-    }
+    });
 }
 
 int epik_amd_cohort_epca(epik_amd_cohort *cohort, const epik_amd_tree *tree, uint32_t num_components, double *mu, double *proj,
                          double *edge, epik_amd_epca_info *info)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    return guarded("cohort_epca", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
         const size_t K = num_components, S = cohort->num_samples, N = cohort->num_branches;
-        if (K < 1 || K > kMaxK)
-            return fail_with(EPIK_AMD_ERR_INVALID, "num_components = " + std::to_string(K) + " is outside [1, 64]");
-        if (!mu || !proj || !edge || !info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+        COHORT_TRY(components_valid(num_components));
+        COHORT_TRY(check_present(mu, proj, edge, info));
         HIP_TRY(hipSetDevice(cohort->device));
-        struct Results {
-            void *d = nullptr;
-            ~Results()
-            {
-                if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-            }
-        } m;
-        const size_t doubles = K + S * K + K * N;  // mu | proj | edge, then the info block
-        HIP_TRY(hipMalloc(&m.d, doubles * sizeof(double) + sizeof(epik_amd_epca_info)));
+        DeviceResult m;
+        const size_t dd = sizeof(double), doubles = K + S * K + K * N;  // mu | proj | edge, then the info block
+        COHORT_TRY(m.alloc(doubles * dd + sizeof(epik_amd_epca_info)));
         double *d = static_cast<double *>(m.d);
-        if (const int rc = epca_device_impl(cohort, tree, num_components, d, d + K, d + K + S * K, d + doubles, nullptr); rc != EPIK_AMD_OK)
-            return rc;
-        HIP_TRY(hipMemcpy(mu, d, K * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(proj, d + K, S * K * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(edge, d + K + S * K, K * N * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(info, d + doubles, sizeof *info, hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_epca: ") + e.what());
-    }
+        COHORT_TRY(epca_device_impl(cohort, tree, num_components, d, d + K, d + K + S * K, d + doubles, nullptr));
+        COHORT_TRY(m.copy_to(mu, K * dd));
+        COHORT_TRY(m.copy_to(proj, S * K * dd, K * dd));
+        COHORT_TRY(m.copy_to(edge, K * N * dd, (K + S * K) * dd));
+        return m.copy_to(info, sizeof *info, doubles * dd);
+    });
 }
 
 int epik_amd_cohort_epca_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                               uint32_t num_components, double *mu, double *proj, double *edge, epik_amd_epca_info *info)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
-        if (!mass || !first || !mu || !proj || !edge || !info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_epca_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(check_present(mass, first, mu, proj, edge, info));
         std::string err;
-        if (const int rc = epca_components(mass, num_samples, num_branches, first, num_components, mu, proj, edge, info, err);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_epca_host: ") + e.what());
-    }
+        return rule_result(epca_components(mass, num_samples, num_branches, first, num_components, mu, proj, edge, info, err), err);
+    });
 }
 
 }  // extern "C"

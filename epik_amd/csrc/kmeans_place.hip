@@ -41,8 +41,7 @@
 #include <vector>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 
 namespace {
 
@@ -82,27 +81,20 @@ struct KmeansSpace {
 
 size_t kmeans_space(void *base, uint32_t S, uint32_t N, KmeansSpace *sp)
 {
-    size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t offset = at;
-        at += (bytes + 15) / 16 * 16;
-        return offset;
-    };
-    const size_t cent = take(2 * (size_t)N * kMaxK * sizeof(double)), column = take(2 * (size_t)N * sizeof(double));
-    const size_t D = take((size_t)S * kMaxK * sizeof(double)), mind = take((size_t)S * sizeof(double));
-    const size_t dist = take((size_t)S * sizeof(double)), ctl = take(sizeof(KmeansControl));
-    const size_t used = take((size_t)S * sizeof(uint32_t)), all = take((size_t)S * sizeof(uint32_t));
-    const size_t assign = take((size_t)S * sizeof(uint32_t)), is_centre = take((size_t)S * sizeof(uint32_t));
-    const size_t members = take((size_t)kMaxK * S * sizeof(uint32_t));
-    if (sp) {
-        char *b = static_cast<char *>(base);
-        *sp = KmeansSpace{reinterpret_cast<double *>(b + cent), reinterpret_cast<double *>(b + column), reinterpret_cast<double *>(b + D),
-                          reinterpret_cast<double *>(b + mind), reinterpret_cast<double *>(b + dist),
-                          reinterpret_cast<KmeansControl *>(b + ctl), reinterpret_cast<uint32_t *>(b + used),
-                          reinterpret_cast<uint32_t *>(b + all), reinterpret_cast<uint32_t *>(b + assign),
-                          reinterpret_cast<uint32_t *>(b + is_centre), reinterpret_cast<uint32_t *>(b + members)};
-    }
-    return at;
+    Carver c(base);
+    const KmeansSpace parts{.cent = c.take<double>(2 * (size_t)N * kMaxK),
+                            .column = c.take<double>(2 * (size_t)N),
+                            .D = c.take<double>((size_t)S * kMaxK),
+                            .mind = c.take<double>(S),
+                            .dist = c.take<double>(S),
+                            .ctl = c.take<KmeansControl>(1),
+                            .used = c.take<uint32_t>(S),
+                            .all = c.take<uint32_t>(S),
+                            .assign = c.take<uint32_t>(S),
+                            .is_centre = c.take<uint32_t>(S),
+                            .members = c.take<uint32_t>((size_t)kMaxK * S)};
+    if (sp) *sp = parts;
+    return c.bytes();
 }
 
 // the i < count with pred(i), in ascending order, into out[]; their number.  One workgroup of kBlock, every lane calls.
@@ -393,38 +385,29 @@ int kmeans_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const
                        uint32_t max_iterations, void *d_samples, void *d_clusters, void *d_centroids, void *d_info,
                        hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (!branch_length || !d_samples || !d_clusters || !d_centroids || !d_info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
-    if (const int rc = check_counts(K, max_iterations); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(check_present(branch_length, d_samples, d_clusters, d_centroids, d_info));
+    COHORT_TRY(check_counts(K, max_iterations));
     const uint32_t N = cohort->num_branches, S = cohort->num_samples, padded = cohort_padded_samples(cohort);
-    std::vector<double> half(N);
-    for (uint32_t b = 0; b < N; ++b) {
-        if (!(branch_length[b] >= 0.0) || !std::isfinite(branch_length[b]))
-            return fail_with(EPIK_AMD_ERR_INVALID, "branch " + std::to_string(b) + ": the branch length is negative or not finite");
-        half[b] = 0.5 * branch_length[b];
-    }
+    std::vector<double> half;
+    COHORT_TRY(half_branch_lengths(branch_length, N, half));
     // the checks of the tree, the device drained, then T_s and the planes
     const uint32_t *d_first = nullptr;
-    if (const int rc = cohort_normalise_enqueue(cohort, tree, stream, &d_first); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(cohort_normalise_enqueue(cohort, tree, stream, &d_first));
     HIP_TRY(hipMemcpy(cohort->d_half, half.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
-    if (!cohort->d_kmeans) {
-        const size_t bytes = kmeans_space(nullptr, S, N, nullptr);
-        HIP_TRY(hipMalloc(&cohort->d_kmeans, bytes));
-        HIP_TRY(hipMemset(cohort->d_kmeans, 0, bytes));  // (the centroid planes beyond K' are read by the distance tiles)
-    }
+    const size_t bytes = kmeans_space(nullptr, S, N, nullptr);
+    bool fresh = false;
+    COHORT_TRY(cohort_space_ensure(cohort, kSpaceKmeans, bytes, &fresh));
     KmeansSpace sp;
-    kmeans_space(cohort->d_kmeans, S, N, &sp);
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    const auto blocks = [&](uint64_t units, uint64_t per) {
-        return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(units + per - 1) / per, kManyBlocks, cap})));
-    };
+    kmeans_space(cohort->space[kSpaceKmeans].d, S, N, &sp);
+    if (fresh) HIP_TRY(hipMemset(cohort->space[kSpaceKmeans].d, 0, bytes));  // (the centroid planes beyond K' are read by the distance tiles)
     double *cent_c = sp.cent, *cent_b = sp.cent + (uint64_t)N * kMaxK;
     hipLaunchKernelGGL(kmeans_init_kernel, dim3(1), dim3(kBlock), 0, stream, cohort->d_total, S, K, sp.ctl, sp.used, sp.all, sp.assign,
                        sp.is_centre);
-    hipLaunchKernelGGL(kmeans_average_kernel, blocks(N, kBlock), dim3(kBlock), 0, stream, cohort->d_planes, N, padded, S, sp.ctl, sp.used,
+    hipLaunchKernelGGL(kmeans_average_kernel, cohort_grid_per(cohort, N, kBlock, kManyBlocks), dim3(kBlock), 0, stream, cohort->d_planes, N, padded, S, sp.ctl, sp.used,
                        sp.all, true, sp.column, sp.column + N, 1u);
     HIP_TRY(hipGetLastError());
-    const dim3 column_grid = blocks(S, kWave), pick_grid = blocks(N, kBlock);
+    const dim3 column_grid = cohort_grid_per(cohort, S, kWave, kManyBlocks), pick_grid = cohort_grid_per(cohort, N, kBlock, kManyBlocks);
     for (uint32_t pass = 0; pass < K; ++pass) {
         hipLaunchKernelGGL(kmeans_column_kernel, column_grid, dim3(kWave), 0, stream, cohort->d_planes, N, padded, cohort->d_half,
                            sp.column, sp.ctl, sp.used, pass, sp.mind, sp.is_centre);
@@ -433,8 +416,9 @@ int kmeans_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const
         HIP_TRY(hipGetLastError());
     }
     const uint64_t tiles = (uint64_t)((S + kTileS - 1) / kTileS) * ((K + kTileK - 1) / kTileK);
-    const dim3 dist_grid = blocks(tiles, 1), sample_grid = blocks(S, kBlock), member_grid = blocks(K, 1);
-    const dim3 update_grid = blocks((uint64_t)N * K, kBlock);
+    const dim3 dist_grid = cohort_grid(cohort, tiles, kManyBlocks), sample_grid = cohort_grid_per(cohort, S, kBlock, kManyBlocks);
+    const dim3 member_grid = cohort_grid(cohort, K, kManyBlocks);
+    const dim3 update_grid = cohort_grid_per(cohort, (uint64_t)N * K, kBlock, kManyBlocks);
     uint32_t iterations = 0, converged = 0;
     for (;;) {
         ++iterations;
@@ -456,7 +440,7 @@ int kmeans_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const
                            sp.members, false, cent_c, cent_b, kMaxK);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(kmeans_finish_kernel, blocks(std::max<uint64_t>(S, (uint64_t)K * N), kBlock), dim3(kBlock), 0, stream, sp.ctl,
+    hipLaunchKernelGGL(kmeans_finish_kernel, cohort_grid_per(cohort, std::max<uint64_t>(S, (uint64_t)K * N), kBlock, kManyBlocks), dim3(kBlock), 0, stream, sp.ctl,
                        cohort->d_total, sp.used, sp.assign, sp.dist, sp.members, sp.cent, S, N, K, iterations, converged,
                        static_cast<epik_amd_kmeans_sample *>(d_samples), static_cast<epik_amd_kmeans_cluster *>(d_clusters),
                        static_cast<double *>(d_centroids), static_cast<epik_amd_kmeans_info *>(d_info));
@@ -472,50 +456,35 @@ int epik_amd_cohort_kmeans_device(epik_amd_cohort *cohort, const epik_amd_tree *
                                   uint32_t num_clusters, uint32_t max_iterations, void *d_samples, void *d_clusters,
                                   void *d_centroids, void *d_info, void *stream)
 {
-    try {
-        return kmeans_device_impl(cohort, tree, branch_length, num_clusters, max_iterations, d_samples, d_clusters, d_centroids,
-                                  d_info, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_kmeans_device: ") + e.what());
-    }
+    return guarded("cohort_kmeans_device", [&]() -> int {
+        return kmeans_device_impl(cohort, tree, branch_length, num_clusters, max_iterations, d_samples, d_clusters, d_centroids, d_info,
+                                  static_cast<hipStream_t>(stream));
+    });
 }
 
 int epik_amd_cohort_kmeans(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
                            uint32_t num_clusters, uint32_t max_iterations, epik_amd_kmeans_sample *samples,
                            epik_amd_kmeans_cluster *clusters, double *centroids, epik_amd_kmeans_info *info)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (!samples || !clusters || !centroids || !info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
-        if (const int rc = check_counts(num_clusters, max_iterations); rc != EPIK_AMD_OK) return rc;
+    return guarded("cohort_kmeans", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(check_present(samples, clusters, centroids, info));
+        COHORT_TRY(check_counts(num_clusters, max_iterations));
         const size_t S = cohort->num_samples, N = cohort->num_branches, K = num_clusters;
         const size_t sample_bytes = S * sizeof(epik_amd_kmeans_sample), cluster_bytes = K * sizeof(epik_amd_kmeans_cluster);
         const size_t centroid_bytes = K * N * sizeof(double);
         HIP_TRY(hipSetDevice(cohort->device));
-        struct Results {
-            void *d = nullptr;
-            ~Results()
-            {
-                if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-            }
-        } r;
+        DeviceResult r;
         // the centroids, the samples, the clusters, then the info block: every part begins on a multiple of 8
-        HIP_TRY(hipMalloc(&r.d, centroid_bytes + sample_bytes + cluster_bytes + sizeof(epik_amd_kmeans_info)));
-        char *base = static_cast<char *>(r.d);
-        void *d_samples = base + centroid_bytes, *d_clusters = base + centroid_bytes + sample_bytes;
-        void *d_info = base + centroid_bytes + sample_bytes + cluster_bytes;
-        if (const int rc = kmeans_device_impl(cohort, tree, branch_length, num_clusters, max_iterations, d_samples, d_clusters, r.d,
-                                              d_info, nullptr);
-            rc != EPIK_AMD_OK)
-            return rc;
-        HIP_TRY(hipMemcpy(centroids, r.d, centroid_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(samples, d_samples, sample_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(clusters, d_clusters, cluster_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(info, d_info, sizeof(epik_amd_kmeans_info), hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_kmeans: ") + e.what());
-    }
+        const size_t samples_at = centroid_bytes, clusters_at = samples_at + sample_bytes, info_at = clusters_at + cluster_bytes;
+        COHORT_TRY(r.alloc(info_at + sizeof(epik_amd_kmeans_info)));
+        COHORT_TRY(kmeans_device_impl(cohort, tree, branch_length, num_clusters, max_iterations, r.at(samples_at), r.at(clusters_at), r.d,
+                                      r.at(info_at), nullptr));
+        COHORT_TRY(r.copy_to(centroids, centroid_bytes));
+        COHORT_TRY(r.copy_to(samples, sample_bytes, samples_at));
+        COHORT_TRY(r.copy_to(clusters, cluster_bytes, clusters_at));
+        return r.copy_to(info, sizeof(epik_amd_kmeans_info), info_at);
+    });
 }
 
 int epik_amd_cohort_kmeans_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
@@ -523,20 +492,14 @@ int epik_amd_cohort_kmeans_host(const uint64_t *mass, uint32_t num_samples, uint
                                 epik_amd_kmeans_sample *samples, epik_amd_kmeans_cluster *clusters, double *centroids,
                                 epik_amd_kmeans_info *info)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
-        if (!mass || !first || !branch_length || !samples || !clusters || !centroids || !info)
-            return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_kmeans_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(check_present(mass, first, branch_length, samples, clusters, centroids, info));
         std::string err;
-        if (const int rc = kmeans_clusters(mass, num_samples, num_branches, first, branch_length, num_clusters, max_iterations,
-                                           samples, clusters, centroids, info, err);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_kmeans_host: ") + e.what());
-    }
+        return rule_result(kmeans_clusters(mass, num_samples, num_branches, first, branch_length, num_clusters, max_iterations, samples,
+                                           clusters, centroids, info, err),
+                           err);
+    });
 }
 
 }  // extern "C"

@@ -31,17 +31,13 @@
 //   model_finish_kernel  p = (1 + at_least) / (P + 1), and NA into the rows of stat whose test is undefined.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <set>
 #include <string>
 #include <vector>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 
 namespace {
 
@@ -93,27 +89,20 @@ constexpr size_t kSliceBytes = kPerms * kChunk * 8 + kPerms * 4;  // the bytes o
 
 size_t model_space(void *base, uint32_t S, uint32_t padded, uint32_t T, uint32_t slices, ModelSpace *sp)
 {
-    size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t offset = at;
-        at += (bytes + 15) / 16 * 16;
-        return offset;
-    };
-    const size_t B = take((size_t)S * S * 8), Q = take((size_t)padded * kPitch * 8), r = take((size_t)padded * 8), v = take((size_t)padded * 8);
-    const size_t val = take((size_t)T * padded * 8), scratch = take((size_t)slices * kSliceBytes * padded);
-    const size_t meta = take(sizeof(ModelMeta)), lab = take((size_t)T * padded * 4), idx = take((size_t)T * padded * 4);
-    const size_t lam = take((size_t)T * padded);
-    if (sp) {
-        char *b = static_cast<char *>(base);
-        const auto d = [&](size_t o) { return reinterpret_cast<double *>(b + o); };
-        const auto u = [&](size_t o) { return reinterpret_cast<uint32_t *>(b + o); };
-        *sp = ModelSpace{d(B), d(Q), d(r), d(v), d(val), d(scratch), reinterpret_cast<ModelMeta *>(b + meta), u(lab), u(idx),
-                         reinterpret_cast<uint8_t *>(b + lam)};
-    }
-    return at;
+    Carver c(base);
+    const ModelSpace parts{.B = c.take<double>((size_t)S * S),
+                           .Q = c.take<double>((size_t)padded * kPitch),
+                           .r = c.take<double>(padded),
+                           .v = c.take<double>(padded),
+                           .val = c.take<double>((size_t)T * padded),
+                           .scratch = c.take<double>((size_t)slices * kSliceBytes * padded / sizeof(double)),
+                           .meta = c.take<ModelMeta>(1),
+                           .lab = c.take<uint32_t>((size_t)T * padded),
+                           .idx = c.take<uint32_t>((size_t)T * padded),
+                           .lam = c.take<uint8_t>((size_t)T * padded)};
+    if (sp) *sp = parts;
+    return c.bytes();
 }
-
-__device__ inline double na_value() { return __longlong_as_double((long long)EPIK_AMD_NA_BITS); }
 
 __global__ __launch_bounds__(kWave) void model_terms_kernel(const uint64_t *__restrict__ total, const uint32_t *__restrict__ lab,
                                                             uint32_t num_samples, uint32_t padded, uint32_t num_terms,
@@ -138,16 +127,7 @@ __global__ __launch_bounds__(kBlock) void model_rows_kernel(const double *__rest
                                                             double *__restrict__ r)
 {
     const uint32_t L = meta->L;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < L; i += gridDim.x * kBlock) {
-        const double *column = kr + used[i];  // KR[u_j][u_i] = KR[u_i][u_j]
-        double acc = 0.0;
-#pragma unroll 4  // (the reads of four values are in flight ahead of the dependent adds)
-        for (uint32_t j = 0; j < L; ++j) {  // ascending: the rule's order
-            const double d = column[(uint64_t)used[j] * num_samples];
-            acc = __dadd_rn(acc, __dmul_rn(d, d));
-        }
-        r[i] = __ddiv_rn(acc, (double)L);
-    }
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < L; i += gridDim.x * kBlock) r[i] = gower_row_mean(kr, used, num_samples, L, i);
 }
 
 __global__ __launch_bounds__(kWave) void model_total_kernel(const double *__restrict__ kr, const uint32_t *__restrict__ used,
@@ -156,9 +136,7 @@ __global__ __launch_bounds__(kWave) void model_total_kernel(const double *__rest
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     const uint32_t L = meta->L;
-    double g = 0.0;
-    for (uint32_t i = 0; i < L; ++i) g = __dadd_rn(g, r[i]);  // ascending: the rule's order
-    if (L) g = __ddiv_rn(g, (double)L);
+    const double g = gower_mean_of_means(r, L);
     double total = 0.0;
     for (uint32_t j = 0; j < L; ++j) {
         const uint32_t s = used[j];
@@ -171,13 +149,7 @@ __global__ __launch_bounds__(kBlock) void model_centre_kernel(const double *__re
                                                               uint32_t num_samples, const ModelMeta *__restrict__ meta,
                                                               const double *__restrict__ r, double *__restrict__ B)
 {
-    const uint32_t L = meta->L;
-    const uint64_t cells = (uint64_t)L * L;
-    const double g = meta->g;
-    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < cells; e += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t i = (uint32_t)(e / L), j = (uint32_t)(e - (uint64_t)i * L), lo = i < j ? i : j, hi = i < j ? j : i;
-        B[e] = gower_centred(kr[(uint64_t)used[lo] * num_samples + used[hi]], r[lo], r[hi], g);
-    }
+    gower_centre_cells(kr, used, num_samples, meta->L, r, meta->g, B);
 }
 
 // one workgroup; every condition around a barrier is uniform (L, G, R and the acceptance come from shared memory)
@@ -398,24 +370,10 @@ __global__ __launch_bounds__(kBlock) void model_finish_kernel(const ModelMeta *_
         if (!(testable && meta->df[e / row])) stat[e] = na_value();
 }
 
-dim3 grid_of(const epik_amd_cohort *cohort, uint64_t units, uint64_t most)
-{
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({units, most, cap})));
-}
-
-// EPIK_AMD_MODEL_LDS=0 (tests), read at the call: the general path whatever S
-bool lds_path(uint32_t S)
-{
-    const char *env = std::getenv("EPIK_AMD_MODEL_LDS");
-    return S <= kLdsPositions && !(env && std::strcmp(env, "0") == 0);
-}
-
 int check_arguments(const uint32_t *kind, const uint32_t *labels, const double *values, uint32_t S, uint32_t T, uint32_t P)
 {
     std::string err;
-    if (const int rc = model_arguments_valid(kind, labels, values, S, T, P, err); rc != EPIK_AMD_OK) return fail_with(rc, err);
-    return EPIK_AMD_OK;
+    return rule_result(model_arguments_valid(kind, labels, values, S, T, P, err), err);
 }
 
 int terms_valid(uint32_t T)
@@ -429,33 +387,26 @@ void launch_ss(const epik_amd_cohort *cohort, const SsArgs &args, size_t dynamic
 {
     const uint64_t units = (args.num_permutations + kPerms - 1) / kPerms, most = kLds ? kManyBlocks : kGeneralBlocks;
     hipLaunchKernelGGL((model_ss_kernel<kLds, true, kCols>), dim3(1), dim3(kBlock), dynamic, stream, args);
-    hipLaunchKernelGGL((model_ss_kernel<kLds, false, kCols>), grid_of(cohort, units, most), dim3(kBlock), dynamic, stream, args);
+    hipLaunchKernelGGL((model_ss_kernel<kLds, false, kCols>), cohort_grid(cohort, units, most), dim3(kBlock), dynamic, stream, args);
 }
 
 int model_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *kind, const uint32_t *labels, const double *values,
                       uint32_t T, uint32_t P, uint64_t seed, void *d_out, void *d_info, void *d_stat, void *d_aliased, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (const int rc = terms_valid(T); rc != EPIK_AMD_OK) return rc;
-    if (!d_kr || !kind || !labels || !values || !d_out || !d_info || !d_aliased) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(terms_valid(T));
+    COHORT_TRY(check_present(d_kr, kind, labels, values, d_out, d_info, d_aliased));
     const uint32_t S = cohort->num_samples, padded = cohort_padded_samples(cohort);
-    if (const int rc = check_arguments(kind, labels, values, S, T, P); rc != EPIK_AMD_OK) return rc;
-    if (!cohort->d_total)
-        return fail_with(EPIK_AMD_ERR_INVALID, "the cohort has no distances yet: d_kr must be what kr_device wrote for this cohort");
+    COHORT_TRY(check_arguments(kind, labels, values, S, T, P));
+    COHORT_TRY(check_has_distances(cohort));
     HIP_TRY(hipSetDevice(cohort->device));
     HIP_TRY(hipDeviceSynchronize());  // (the distances enqueued on whatever stream, and an earlier call that reads the workspace)
-    const bool lds = lds_path(S);
+    const bool lds = lds_switch("EPIK_AMD_MODEL_LDS", S, kLdsPositions);  // (=0, tests: the general path whatever S)
     // the general path's workgroups, each with a slice: the grid that launch_ss makes of the permutations' units
-    const uint32_t slices = lds ? 0 : grid_of(cohort, (P + kPerms - 1) / kPerms, kGeneralBlocks).x;
-    const size_t bytes = model_space(nullptr, S, padded, T, slices, nullptr);
-    if (bytes > cohort->model_bytes) {
-        (void)hipFree(cohort->d_model);
-        cohort->d_model = nullptr, cohort->model_bytes = 0;
-        HIP_TRY(hipMalloc(&cohort->d_model, bytes));
-        cohort->model_bytes = bytes;
-    }
+    const uint32_t slices = lds ? 0 : cohort_grid(cohort, (P + kPerms - 1) / kPerms, kGeneralBlocks).x;
+    COHORT_TRY(cohort_space_ensure(cohort, kSpaceModel, model_space(nullptr, S, padded, T, slices, nullptr)));
     ModelSpace sp;
-    model_space(cohort->d_model, S, padded, T, slices, &sp);
+    model_space(cohort->space[kSpaceModel].d, S, padded, T, slices, &sp);
     // the design by term; a sample that lacks any value is missing in every term, so every term lists the complete cases
     std::vector<uint32_t> lab((size_t)T * padded, kMissing);
     std::vector<double> val((size_t)T * padded, 0.0);
@@ -484,12 +435,12 @@ int model_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t 
     HIP_TRY(hipMemsetAsync(sp.Q, 0, (size_t)padded * kPitch * sizeof(double), stream));  // (a lane reads whole chunks of a row)
     const auto *kr = static_cast<const double *>(d_kr);
     const uint64_t cells = (uint64_t)S * S;
-    hipLaunchKernelGGL(model_terms_kernel, grid_of(cohort, T, kTerms), dim3(kWave), 0, stream, cohort->d_total, sp.lab, S, padded, T, sp.idx,
+    hipLaunchKernelGGL(model_terms_kernel, cohort_grid(cohort, T, kTerms), dim3(kWave), 0, stream, cohort->d_total, sp.lab, S, padded, T, sp.idx,
                        sp.lam, sp.meta);
-    hipLaunchKernelGGL(model_rows_kernel, grid_of(cohort, (S + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, kr, sp.idx, S,
+    hipLaunchKernelGGL(model_rows_kernel, cohort_grid(cohort, (S + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, kr, sp.idx, S,
                        sp.meta, sp.r);
     hipLaunchKernelGGL(model_total_kernel, dim3(1), dim3(kWave), 0, stream, kr, sp.idx, S, sp.meta, sp.r);
-    hipLaunchKernelGGL(model_centre_kernel, grid_of(cohort, (cells + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, kr, sp.idx,
+    hipLaunchKernelGGL(model_centre_kernel, cohort_grid(cohort, (cells + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, kr, sp.idx,
                        S, sp.meta, sp.r, sp.B);
     hipLaunchKernelGGL(model_basis_kernel, dim3(1), dim3(kBlock), 0, stream, kinds, T, padded, sp.val, sp.idx, sp.lam, sp.v, sp.Q, sp.meta,
                        static_cast<uint8_t *>(d_aliased));
@@ -503,20 +454,11 @@ int model_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t 
     else if (small) launch_ss<false, kSmallColumns>(cohort, args, dynamic, stream);
     else launch_ss<false, kChunk>(cohort, args, dynamic, stream);
     const uint64_t finish = d_stat ? (uint64_t)(T + 1) * (P + 1) : T + 1;
-    hipLaunchKernelGGL(model_finish_kernel, grid_of(cohort, (finish + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, sp.meta,
+    hipLaunchKernelGGL(model_finish_kernel, cohort_grid(cohort, (finish + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, sp.meta,
                        T, P, static_cast<epik_amd_model_term *>(d_out), static_cast<double *>(d_stat));
     HIP_TRY(hipGetLastError());
     return EPIK_AMD_OK;
 }
-
-// a result in device memory for the synchronous entry, freed however the call ends
-struct Result {
-    void *d = nullptr;
-    ~Result()
-    {
-        if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-    }
-};
 
 }  // namespace
 
@@ -526,12 +468,10 @@ int epik_amd_cohort_model_device(epik_amd_cohort *cohort, const void *d_kr, cons
                                  const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed, void *d_out,
                                  void *d_info, void *d_stat, void *d_aliased, void *stream)
 {
-    try {
+    return guarded("cohort_model_device", [&]() -> int {
         return model_device_impl(cohort, d_kr, kind, labels, values, num_terms, num_permutations, seed, d_out, d_info, d_stat, d_aliased,
                                  static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_model_device: ") + e.what());
-    }
+    });
 }
 
 int epik_amd_cohort_model(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, const uint32_t *kind,
@@ -547,33 +487,27 @@ int epik_amd_cohort_model_metric(epik_amd_cohort *cohort, const epik_amd_tree *t
                                  uint32_t num_permutations, uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info,
                                  double *stat, uint8_t *aliased)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (const int rc = terms_valid(num_terms); rc != EPIK_AMD_OK) return rc;
-        if (!kind || !labels || !values || !out || !info || !aliased) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_model", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(terms_valid(num_terms));
+        COHORT_TRY(check_present(kind, labels, values, out, info, aliased));
         const uint32_t S = cohort->num_samples;
-        if (const int rc = check_arguments(kind, labels, values, S, num_terms, num_permutations); rc != EPIK_AMD_OK) return rc;
+        COHORT_TRY(check_arguments(kind, labels, values, S, num_terms, num_permutations));
         const size_t out_bytes = ((size_t)num_terms + 1) * sizeof(epik_amd_model_term);
         const size_t stat_bytes = ((size_t)num_terms + 1) * ((size_t)num_permutations + 1) * sizeof(double);
         HIP_TRY(hipSetDevice(cohort->device));
-        Result kr, r, s;
-        HIP_TRY(hipMalloc(&kr.d, (size_t)S * S * sizeof(double)));
-        HIP_TRY(hipMalloc(&r.d, out_bytes + sizeof(epik_amd_model_info) + kColumns));  // the records | the info block | aliased
-        if (stat) HIP_TRY(hipMalloc(&s.d, stat_bytes));
-        if (const int rc = cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr); rc != EPIK_AMD_OK) return rc;
-        char *d = static_cast<char *>(r.d);
-        if (const int rc = model_device_impl(cohort, kr.d, kind, labels, values, num_terms, num_permutations, seed, d, d + out_bytes, s.d,
-                                             d + out_bytes + sizeof(epik_amd_model_info), nullptr);
-            rc != EPIK_AMD_OK)
-            return rc;
-        HIP_TRY(hipMemcpy(out, d, out_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(info, d + out_bytes, sizeof *info, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(aliased, d + out_bytes + sizeof *info, kColumns, hipMemcpyDeviceToHost));
-        if (stat) HIP_TRY(hipMemcpy(stat, s.d, stat_bytes, hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_model: ") + e.what());
-    }
+        DeviceResult kr, r, s;
+        COHORT_TRY(kr.alloc((size_t)S * S * sizeof(double)));
+        COHORT_TRY(r.alloc(out_bytes + sizeof(epik_amd_model_info) + kColumns));  // the records | the info block | aliased
+        COHORT_TRY(s.alloc(stat_bytes, stat != nullptr));
+        COHORT_TRY(cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr));
+        COHORT_TRY(model_device_impl(cohort, kr.d, kind, labels, values, num_terms, num_permutations, seed, r.d, r.at(out_bytes), s.d,
+                                     r.at(out_bytes + sizeof(epik_amd_model_info)), nullptr));
+        COHORT_TRY(r.copy_to(out, out_bytes));
+        COHORT_TRY(r.copy_to(info, sizeof *info, out_bytes));
+        COHORT_TRY(r.copy_to(aliased, kColumns, out_bytes + sizeof *info));
+        return s.copy_to(stat, stat_bytes);
+    });
 }
 
 int epik_amd_cohort_model_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
@@ -590,40 +524,30 @@ int epik_amd_cohort_model_metric_host(const uint64_t *mass, uint32_t num_samples
                                       const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed,
                                       epik_amd_model_term *out, epik_amd_model_info *info, double *stat, uint8_t *aliased)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
-        if (const int rc = terms_valid(num_terms); rc != EPIK_AMD_OK) return rc;
-        if (!mass || !first || !branch_length || !kind || !labels || !values || !out || !info || !aliased)
-            return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_model_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(terms_valid(num_terms));
+        COHORT_TRY(check_present(mass, first, branch_length, kind, labels, values, out, info, aliased));
         std::string err;
-        if (const int rc = model_records(mass, num_samples, num_branches, first, branch_length, kind, labels, values, num_terms,
-                                         num_permutations, seed, out, info, stat, aliased, err, metric);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_model_host: ") + e.what());
-    }
+        return rule_result(model_records(mass, num_samples, num_branches, first, branch_length, kind, labels, values, num_terms,
+                                         num_permutations, seed, out, info, stat, aliased, err, metric),
+                           err);
+    });
 }
 
 int epik_amd_cohort_model_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *kind,
                                   const uint32_t *labels, const double *values, uint32_t num_terms, uint32_t num_permutations,
                                   uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info, double *stat, uint8_t *aliased)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (const int rc = terms_valid(num_terms); rc != EPIK_AMD_OK) return rc;
-        if (!kr || !totals || !kind || !labels || !values || !out || !info || !aliased) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_model_kr_host", [&]() -> int {
+        COHORT_TRY(check_host_samples(num_samples));
+        COHORT_TRY(terms_valid(num_terms));
+        COHORT_TRY(check_present(kr, totals, kind, labels, values, out, info, aliased));
         std::string err;
-        if (const int rc = model_records_of_kr(kr, totals, num_samples, kind, labels, values, num_terms, num_permutations, seed, out, info,
-                                               stat, aliased, err);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_model_kr_host: ") + e.what());
-    }
+        return rule_result(model_records_of_kr(kr, totals, num_samples, kind, labels, values, num_terms, num_permutations, seed, out, info,
+                                               stat, aliased, err),
+                           err);
+    });
 }
 
 }  // extern "C"

@@ -25,13 +25,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <string>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 #include "jacobi_device.hpp"
 
 namespace {
@@ -61,40 +58,34 @@ struct PcoaSpace {
 
 size_t pcoa_space(void *base, uint32_t S, PcoaSpace *sp)
 {
-    size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t offset = at;
-        at += (bytes + 15) / 16 * 16;
-        return offset;
-    };
-    const size_t dd = sizeof(double), uu = sizeof(uint32_t), SS = (size_t)S * S;
-    const size_t A = take(SS * dd), A1 = take(SS * dd), V = take(SS * dd), r = take(S * dd), cs = take(S * dd), sn = take(S * dd);
-    const size_t gs = take(4 * dd), pn = take(2 * dd), root = take(kMaxK * dd), sign = take(kMaxK * dd);
-    const size_t used = take(S * uu), jof = take(S * uu), partner = take(S * uu), count = take(uu);
-    const size_t counters = take(kJacobiMaxSweeps * uu), status = take(2 * uu), column = take(kMaxK * uu), real_k = take(kMaxK * uu);
-    if (sp) {
-        char *b = static_cast<char *>(base);
-        const auto d = [&](size_t o) { return reinterpret_cast<double *>(b + o); };
-        const auto u = [&](size_t o) { return reinterpret_cast<uint32_t *>(b + o); };
-        *sp = PcoaSpace{d(A), d(A1), d(V), d(r), d(cs), d(sn), d(gs), d(pn), d(root), d(sign), u(used), u(jof), u(partner),
-                        u(count), u(counters), u(status), u(column), u(real_k)};
-    }
-    return at;
+    const size_t SS = (size_t)S * S;
+    Carver c(base);
+    const PcoaSpace parts{.A = c.take<double>(SS),
+                          .A1 = c.take<double>(SS),
+                          .V = c.take<double>(SS),
+                          .r = c.take<double>(S),
+                          .cs = c.take<double>(S),
+                          .sn = c.take<double>(S),
+                          .gs = c.take<double>(4),
+                          .pn = c.take<double>(2),
+                          .root = c.take<double>(kMaxK),
+                          .sign = c.take<double>(kMaxK),
+                          .used = c.take<uint32_t>(S),
+                          .jof = c.take<uint32_t>(S),
+                          .partner = c.take<uint32_t>(S),
+                          .count = c.take<uint32_t>(1),
+                          .counters = c.take<uint32_t>(kJacobiMaxSweeps),
+                          .status = c.take<uint32_t>(2),
+                          .column = c.take<uint32_t>(kMaxK),
+                          .real_k = c.take<uint32_t>(kMaxK)};
+    if (sp) *sp = parts;
+    return c.bytes();
 }
 
 __global__ __launch_bounds__(kBlock) void pcoa_rows_kernel(const double *__restrict__ kr, const uint32_t *__restrict__ used,
                                                            uint32_t num_samples, uint32_t L, double *__restrict__ r)
 {
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < L; i += gridDim.x * kBlock) {
-        const double *column = kr + used[i];  // KR[u_j][u_i] = KR[u_i][u_j]
-        double acc = 0.0;
-#pragma unroll 4  // (the reads of four values are in flight ahead of the dependent adds)
-        for (uint32_t j = 0; j < L; ++j) {  // ascending: the rule's order
-            const double d = column[(uint64_t)used[j] * num_samples];
-            acc = __dadd_rn(acc, __dmul_rn(d, d));
-        }
-        r[i] = __ddiv_rn(acc, (double)L);
-    }
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < L; i += gridDim.x * kBlock) r[i] = gower_row_mean(kr, used, num_samples, L, i);
 }
 
 __global__ __launch_bounds__(kBlock) void pcoa_scale_kernel(const double *__restrict__ kr, const uint32_t *__restrict__ used,
@@ -107,9 +98,7 @@ __global__ __launch_bounds__(kBlock) void pcoa_scale_kernel(const double *__rest
         V[e] = e / L == e % L ? 1.0 : 0.0;
     if (blockIdx.x == 0 && threadIdx.x < kJacobiMaxSweeps) counters[threadIdx.x] = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        double g = 0.0;
-        for (uint32_t i = 0; i < L; ++i) g = __dadd_rn(g, r[i]);  // ascending: the rule's order
-        if (L) g = __ddiv_rn(g, (double)L);
+        const double g = gower_mean_of_means(r, L);
         double scale = 0.0, trace = 0.0;
         for (uint32_t j = 0; j < L; ++j) {
             const uint32_t s = used[j];
@@ -125,12 +114,7 @@ __global__ __launch_bounds__(kBlock) void pcoa_centre_kernel(const double *__res
                                                              uint32_t num_samples, uint32_t L, const double *__restrict__ r,
                                                              const double *__restrict__ gs, double *__restrict__ B)
 {
-    const uint64_t cells = (uint64_t)L * L;
-    const double g = gs[3];
-    for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < cells; e += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t i = (uint32_t)(e / L), j = (uint32_t)(e - (uint64_t)i * L), lo = i < j ? i : j, hi = i < j ? j : i;
-        B[e] = gower_centred(kr[(uint64_t)used[lo] * num_samples + used[hi]], r[lo], r[hi], g);
-    }
+    gower_centre_cells(kr, used, num_samples, L, r, gs[3], B);
 }
 
 __global__ __launch_bounds__(kBlock) void pcoa_order_kernel(const double *__restrict__ A, const double *__restrict__ V, uint32_t L,
@@ -205,58 +189,44 @@ int components_valid(uint32_t K)
 
 int pcoa_device_impl(epik_amd_cohort *cohort, const void *d_kr, uint32_t K, void *d_mu, void *d_coord, void *d_info, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (const int rc = components_valid(K); rc != EPIK_AMD_OK) return rc;
-    if (!d_kr || !d_mu || !d_coord || !d_info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
-    if (!cohort->d_total)
-        return fail_with(EPIK_AMD_ERR_INVALID, "the cohort has no distances yet: d_kr must be what kr_device wrote for this cohort");
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(components_valid(K));
+    COHORT_TRY(check_present(d_kr, d_mu, d_coord, d_info));
+    COHORT_TRY(check_has_distances(cohort));
     HIP_TRY(hipSetDevice(cohort->device));
     HIP_TRY(hipDeviceSynchronize());  // (the distances enqueued on whatever stream, and an earlier call that reads the workspace)
     const uint32_t S = cohort->num_samples;
-    if (!cohort->d_pcoa) HIP_TRY(hipMalloc(&cohort->d_pcoa, pcoa_space(nullptr, S, nullptr)));
+    COHORT_TRY(cohort_space_ensure(cohort, kSpacePcoa, pcoa_space(nullptr, S, nullptr)));
     PcoaSpace sp;
-    pcoa_space(cohort->d_pcoa, S, &sp);
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    const auto blocks = [&](uint64_t units) {
-        return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(units + kBlock - 1) / kBlock, kMaxBlocks, cap})));
-    };
+    pcoa_space(cohort->space[kSpacePcoa].d, S, &sp);
+    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;  // (the eigensolver's)
     const auto *kr = static_cast<const double *>(d_kr);
-    if (const int rc = cohort_used_index_enqueue(cohort, sp.used, sp.jof, sp.count, stream); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(cohort_used_index_enqueue(cohort, sp.used, sp.jof, sp.count, stream));
     uint32_t L = 0;
     HIP_TRY(hipMemcpyAsync(&L, sp.count, sizeof L, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (L > S) return fail_with(EPIK_AMD_ERR_HIP, "cohort_pcoa: the device counted more used samples than there are samples");
     const uint32_t Kc = std::min(K, L);
     const uint64_t cells = (uint64_t)L * L;
-    if (L) hipLaunchKernelGGL(pcoa_rows_kernel, blocks(L), dim3(kBlock), 0, stream, kr, sp.used, S, L, sp.r);
-    hipLaunchKernelGGL(pcoa_scale_kernel, blocks(cells), dim3(kBlock), 0, stream, kr, sp.used, S, L, sp.r, sp.gs, sp.V, sp.counters);
-    if (L) hipLaunchKernelGGL(pcoa_centre_kernel, blocks(cells), dim3(kBlock), 0, stream, kr, sp.used, S, L, sp.r, sp.gs, sp.A);
+    if (L) hipLaunchKernelGGL(pcoa_rows_kernel, cohort_grid_per(cohort, L, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, kr, sp.used, S, L, sp.r);
+    hipLaunchKernelGGL(pcoa_scale_kernel, cohort_grid_per(cohort, cells, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, kr, sp.used, S, L, sp.r, sp.gs, sp.V, sp.counters);
+    if (L) hipLaunchKernelGGL(pcoa_centre_kernel, cohort_grid_per(cohort, cells, kBlock, kMaxBlocks), dim3(kBlock), 0, stream, kr, sp.used, S, L, sp.r, sp.gs, sp.A);
     HIP_TRY(hipGetLastError());
-    // EPIK_AMD_PCOA_LDS=0 (tests), read at the call: the eigensolver's global path whatever L
-    const char *env = std::getenv("EPIK_AMD_PCOA_LDS");
-    const bool lds = L <= kJacobiLdsSide && !(env && std::strcmp(env, "0") == 0);
+    const bool lds = lds_switch("EPIK_AMD_PCOA_LDS", L, kJacobiLdsSide);  // (=0, tests: the eigensolver's global path whatever L)
     uint32_t sweeps = 1, converged = 1;  // (L = 0: one empty sweep)
     if (L) {
         const JacobiSpace js{sp.A, sp.A1, sp.V, sp.cs, sp.sn, sp.gs, sp.partner, sp.counters, sp.status};
-        if (const int rc = jacobi_sweeps(js, L, lds, cap, stream, sweeps, converged); rc != EPIK_AMD_OK) return rc;
+        COHORT_TRY(jacobi_sweeps(js, L, lds, cap, stream, sweeps, converged));
     }
     hipLaunchKernelGGL(pcoa_order_kernel, dim3(1), dim3(kBlock), 0, stream, sp.A, sp.V, L, S, Kc, sp.gs, sp.column, sp.real_k, sp.root,
                        sp.sign, sp.pn, static_cast<double *>(d_mu));
-    hipLaunchKernelGGL(pcoa_coord_kernel, blocks((uint64_t)S * K), dim3(kBlock), 0, stream, static_cast<double *>(d_coord), sp.V, sp.jof,
+    hipLaunchKernelGGL(pcoa_coord_kernel, cohort_grid_per(cohort, (uint64_t)S * K, kBlock, kMaxBlocks), dim3(kBlock), 0, stream,
+                       static_cast<double *>(d_coord), sp.V, sp.jof,
                        sp.column, sp.real_k, sp.root, sp.sign, S, K, Kc, L, sp.gs, sp.pn, L && lds ? sp.status : nullptr, sweeps,
                        converged, static_cast<epik_amd_pcoa_info *>(d_info));
     HIP_TRY(hipGetLastError());
     return EPIK_AMD_OK;
 }
-
-// a result in device memory for the synchronous entry, freed however the call ends
-struct Result {
-    void *d = nullptr;
-    ~Result()
-    {
-        if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-    }
-};
 
 }  // namespace
 
@@ -265,11 +235,9 @@ extern "C" {
 int epik_amd_cohort_pcoa_device(epik_amd_cohort *cohort, const void *d_kr, uint32_t num_components, void *d_mu, void *d_coord,
                                 void *d_info, void *stream)
 {
-    try {
+    return guarded("cohort_pcoa_device", [&]() -> int {
         return pcoa_device_impl(cohort, d_kr, num_components, d_mu, d_coord, d_info, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_pcoa_device: ") + e.what());
-    }
+    });
 }
 
 int epik_amd_cohort_pcoa(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t num_components,
@@ -281,26 +249,23 @@ int epik_amd_cohort_pcoa(epik_amd_cohort *cohort, const epik_amd_tree *tree, con
 int epik_amd_cohort_pcoa_metric(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
                                 uint32_t num_components, double *mu, double *coord, epik_amd_pcoa_info *info)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (const int rc = components_valid(num_components); rc != EPIK_AMD_OK) return rc;
-        if (!mu || !coord || !info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_pcoa", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(components_valid(num_components));
+        COHORT_TRY(check_present(mu, coord, info));
         const size_t K = num_components, S = cohort->num_samples;
         HIP_TRY(hipSetDevice(cohort->device));
-        Result kr, m;
+        DeviceResult kr, m;
         const size_t doubles = S + S * K;  // mu | coord, then the info block
-        HIP_TRY(hipMalloc(&kr.d, S * S * sizeof(double)));
-        HIP_TRY(hipMalloc(&m.d, doubles * sizeof(double) + sizeof(epik_amd_pcoa_info)));
-        if (const int rc = cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr); rc != EPIK_AMD_OK) return rc;
+        COHORT_TRY(kr.alloc(S * S * sizeof(double)));
+        COHORT_TRY(m.alloc(doubles * sizeof(double) + sizeof(epik_amd_pcoa_info)));
+        COHORT_TRY(cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr));
         double *d = static_cast<double *>(m.d);
-        if (const int rc = pcoa_device_impl(cohort, kr.d, num_components, d, d + S, d + doubles, nullptr); rc != EPIK_AMD_OK) return rc;
-        HIP_TRY(hipMemcpy(mu, d, S * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(coord, d + S, S * K * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(info, d + doubles, sizeof *info, hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_pcoa: ") + e.what());
-    }
+        COHORT_TRY(pcoa_device_impl(cohort, kr.d, num_components, d, d + S, d + doubles, nullptr));
+        COHORT_TRY(m.copy_to(mu, S * sizeof(double)));
+        COHORT_TRY(m.copy_to(coord, S * K * sizeof(double), S * sizeof(double)));
+        return m.copy_to(info, sizeof *info, doubles * sizeof(double));
+    });
 }
 
 int epik_amd_cohort_pcoa_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
@@ -315,33 +280,24 @@ int epik_amd_cohort_pcoa_metric_host(const uint64_t *mass, uint32_t num_samples,
                                      const double *branch_length, uint32_t metric, uint32_t num_components, double *mu, double *coord,
                                      epik_amd_pcoa_info *info)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
-        if (!mass || !first || !branch_length || !mu || !coord || !info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_pcoa_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(check_present(mass, first, branch_length, mu, coord, info));
         std::string err;
-        if (const int rc = pcoa_components(mass, num_samples, num_branches, first, branch_length, num_components, mu, coord, info, err, metric);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_pcoa_host: ") + e.what());
-    }
+        return rule_result(pcoa_components(mass, num_samples, num_branches, first, branch_length, num_components, mu, coord, info, err, metric),
+                           err);
+    });
 }
 
 int epik_amd_cohort_pcoa_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, uint32_t num_components, double *mu,
                                  double *coord, epik_amd_pcoa_info *info)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (!kr || !totals || !mu || !coord || !info) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_pcoa_kr_host", [&]() -> int {
+        COHORT_TRY(check_host_samples(num_samples));
+        COHORT_TRY(check_present(kr, totals, mu, coord, info));
         std::string err;
-        if (const int rc = pcoa_components_of_kr(kr, totals, num_samples, num_components, mu, coord, info, err); rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_pcoa_kr_host: ") + e.what());
-    }
+        return rule_result(pcoa_components_of_kr(kr, totals, num_samples, num_components, mu, coord, info, err), err);
+    });
 }
 
 }  // extern "C"

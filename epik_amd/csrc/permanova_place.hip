@@ -27,15 +27,11 @@
 //   permanova_finish_kernel   p = (1 + at_most) / (P + 1), and NA into the ssw of the tests that did not run.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 
 namespace {
 
@@ -85,25 +81,18 @@ constexpr size_t kSliceBytes = kPerms * 8 + 8 + 4;  // the bytes of a slice per 
 size_t permanova_space(void *base, uint32_t S, uint32_t padded, uint32_t M, bool pairwise, PermSpace *sp)
 {
     const size_t slots = 1 + (pairwise ? kPairSlots : 0), lists = pairwise ? kPairGroups : 1, tests = M * slots;
-    const auto up = [](size_t v) { return (v + 15) / 16 * 16; };
-    const size_t a2 = up((size_t)S * S * sizeof(double)), scratch = up((size_t)kGeneralBlocks * kSliceBytes * padded);
-    const size_t lab = up((size_t)M * padded * 4), idx = up((size_t)M * lists * padded * 4), active = up((tests + 1) * 4);
-    const size_t cols = up(M * sizeof(PermColumn)), tst = up(tests * sizeof(PermTest)), lam = up((size_t)M * lists * padded);
-    if (sp) {
-        char *b = static_cast<char *>(base);
-        sp->A2 = reinterpret_cast<double *>(b), b += a2;
-        sp->scratch = reinterpret_cast<double *>(b), b += scratch;
-        sp->lab = reinterpret_cast<uint32_t *>(b), b += lab;
-        sp->idx = reinterpret_cast<uint32_t *>(b), b += idx;
-        sp->active = reinterpret_cast<uint32_t *>(b), b += active;
-        sp->cols = reinterpret_cast<PermColumn *>(b), b += cols;
-        sp->tests = reinterpret_cast<PermTest *>(b), b += tst;
-        sp->lam = reinterpret_cast<uint8_t *>(b);
-    }
-    return a2 + scratch + lab + idx + active + cols + tst + lam;
+    Carver c(base);
+    const PermSpace parts{.A2 = c.take<double>((size_t)S * S),
+                          .scratch = c.take<double>((size_t)kGeneralBlocks * kSliceBytes * padded / sizeof(double)),
+                          .lab = c.take<uint32_t>((size_t)M * padded),
+                          .idx = c.take<uint32_t>((size_t)M * lists * padded),
+                          .active = c.take<uint32_t>(tests + 1),
+                          .cols = c.take<PermColumn>(M),
+                          .tests = c.take<PermTest>(tests),
+                          .lam = c.take<uint8_t>((size_t)M * lists * padded)};
+    if (sp) *sp = parts;
+    return c.bytes();
 }
-
-__device__ inline double na_value() { return __longlong_as_double((long long)EPIK_AMD_NA_BITS); }
 
 __device__ inline void na_record(epik_amd_permanova *r, uint32_t used, uint32_t groups)
 {
@@ -372,63 +361,39 @@ __global__ __launch_bounds__(kBlock) void permanova_finish_kernel(const PermTest
         if (!tests[e / row].defined) ssw[e] = na_value();
 }
 
-dim3 grid_of(const epik_amd_cohort *cohort, uint64_t units, uint64_t most)
-{
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({units, most, cap})));
-}
-
-// EPIK_AMD_PERMANOVA_LDS=0 (tests), read at the call: the general path whatever S
-bool lds_path(uint32_t S)
-{
-    const char *env = std::getenv("EPIK_AMD_PERMANOVA_LDS");
-    return S <= kLdsPositions && !(env && std::strcmp(env, "0") == 0);
-}
-
 int check_arguments(const uint32_t *labels, uint32_t S, uint32_t M, uint32_t P, bool pairwise)
 {
     std::string err;
-    if (const int rc = permanova_arguments_valid(labels, S, M, P, pairwise, err); rc != EPIK_AMD_OK) return fail_with(rc, err);
-    return EPIK_AMD_OK;
+    return rule_result(permanova_arguments_valid(labels, S, M, P, pairwise, err), err);
 }
 
 int permanova_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, uint32_t M, uint32_t P, uint64_t seed,
                           bool pairwise, void *d_out, void *d_ssw, void *d_group_ss, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (M < 1 || M > kColumns) return fail_with(EPIK_AMD_ERR_INVALID, "num_columns = " + std::to_string(M) + " is outside [1, 64]");
-    if (!d_kr || !labels || !d_out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(check_columns(M));
+    COHORT_TRY(check_present(d_kr, labels, d_out));
     const uint32_t S = cohort->num_samples, padded = cohort_padded_samples(cohort);
-    if (const int rc = check_arguments(labels, S, M, P, pairwise); rc != EPIK_AMD_OK) return rc;
-    if (!cohort->d_total)
-        return fail_with(EPIK_AMD_ERR_INVALID, "the cohort has no distances yet: d_kr must be what kr_device wrote for this cohort");
+    COHORT_TRY(check_arguments(labels, S, M, P, pairwise));
+    COHORT_TRY(check_has_distances(cohort));
     HIP_TRY(hipSetDevice(cohort->device));
     HIP_TRY(hipDeviceSynchronize());  // (the distances enqueued on whatever stream, and an earlier call that reads the workspace)
-    const size_t bytes = permanova_space(nullptr, S, padded, M, pairwise, nullptr);
-    if (bytes > cohort->permanova_bytes) {
-        (void)hipFree(cohort->d_permanova);
-        cohort->d_permanova = nullptr, cohort->permanova_bytes = 0;
-        HIP_TRY(hipMalloc(&cohort->d_permanova, bytes));
-        cohort->permanova_bytes = bytes;
-    }
+    COHORT_TRY(cohort_space_ensure(cohort, kSpacePermanova, permanova_space(nullptr, S, padded, M, pairwise, nullptr)));
     PermSpace sp;
-    permanova_space(cohort->d_permanova, S, padded, M, pairwise, &sp);
-    std::vector<uint32_t> lab((size_t)M * padded, kMissing);
-    for (uint32_t s = 0; s < S; ++s)
-        for (uint32_t c = 0; c < M; ++c) lab[(size_t)c * padded + s] = labels[(size_t)s * M + c];
-    HIP_TRY(hipMemcpy(sp.lab, lab.data(), lab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    permanova_space(cohort->space[kSpacePermanova].d, S, padded, M, pairwise, &sp);
+    COHORT_TRY(upload_labels_by_column(labels, S, M, padded, kMissing, sp.lab));
     const uint32_t slots = 1 + (pairwise ? kPairSlots : 0), lists = pairwise ? kPairGroups : 1, tests = M * slots;
     HIP_TRY(hipMemsetAsync(sp.active + tests, 0, sizeof(uint32_t), stream));
     auto *out = static_cast<epik_amd_permanova *>(d_out);
     const uint64_t cells = (uint64_t)S * S;
-    hipLaunchKernelGGL(permanova_square_kernel, grid_of(cohort, (cells + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream,
+    hipLaunchKernelGGL(permanova_square_kernel, cohort_grid(cohort, (cells + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream,
                        static_cast<const double *>(d_kr), cells, sp.A2);
-    hipLaunchKernelGGL(permanova_columns_kernel, grid_of(cohort, M, kColumns), dim3(kWave), 0, stream, cohort->d_total, sp.lab, S, padded,
+    hipLaunchKernelGGL(permanova_columns_kernel, cohort_grid(cohort, M, kColumns), dim3(kWave), 0, stream, cohort->d_total, sp.lab, S, padded,
                        M, slots, lists, sp.idx, sp.lam, sp.cols, sp.tests, sp.active, out, static_cast<double *>(d_group_ss));
     if (pairwise)
-        hipLaunchKernelGGL(permanova_pairs_kernel, grid_of(cohort, (uint64_t)M * kPairSlots, kManyBlocks), dim3(kWave), 0, stream, padded,
+        hipLaunchKernelGGL(permanova_pairs_kernel, cohort_grid(cohort, (uint64_t)M * kPairSlots, kManyBlocks), dim3(kWave), 0, stream, padded,
                            M, sp.idx, sp.lam, sp.cols, sp.tests, sp.active, out);
-    const bool lds = lds_path(S);
+    const bool lds = lds_switch("EPIK_AMD_PERMANOVA_LDS", S, kLdsPositions);  // (=0, tests: the general path whatever S)
     uint32_t pitch = padded;  // the general path's; the LDS path's: a power of two, for the sort
     if (lds)
         for (pitch = kWave; pitch < S; pitch <<= 1) {}
@@ -438,27 +403,18 @@ int permanova_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint3
     const dim3 block(S <= kSmallSamples ? kWave : kBlock);
     const uint64_t chunks = (P + kPerms - 1) / kPerms, most = lds ? kManyBlocks : kGeneralBlocks;
     if (lds) {
-        hipLaunchKernelGGL((permanova_ssw_kernel<true, true>), grid_of(cohort, tests, most), block, dynamic, stream, args);
-        hipLaunchKernelGGL((permanova_ssw_kernel<true, false>), grid_of(cohort, tests * chunks, most), block, dynamic, stream, args);
+        hipLaunchKernelGGL((permanova_ssw_kernel<true, true>), cohort_grid(cohort, tests, most), block, dynamic, stream, args);
+        hipLaunchKernelGGL((permanova_ssw_kernel<true, false>), cohort_grid(cohort, tests * chunks, most), block, dynamic, stream, args);
     } else {
-        hipLaunchKernelGGL((permanova_ssw_kernel<false, true>), grid_of(cohort, tests, most), block, 0, stream, args);
-        hipLaunchKernelGGL((permanova_ssw_kernel<false, false>), grid_of(cohort, tests * chunks, most), block, 0, stream, args);
+        hipLaunchKernelGGL((permanova_ssw_kernel<false, true>), cohort_grid(cohort, tests, most), block, 0, stream, args);
+        hipLaunchKernelGGL((permanova_ssw_kernel<false, false>), cohort_grid(cohort, tests * chunks, most), block, 0, stream, args);
     }
     const uint64_t finish = d_ssw ? (uint64_t)tests * (P + 1) : tests;
-    hipLaunchKernelGGL(permanova_finish_kernel, grid_of(cohort, (finish + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream,
+    hipLaunchKernelGGL(permanova_finish_kernel, cohort_grid(cohort, (finish + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream,
                        sp.tests, tests, P, out, static_cast<double *>(d_ssw));
     HIP_TRY(hipGetLastError());
     return EPIK_AMD_OK;
 }
-
-// a result in device memory for the synchronous entry, freed however the call ends
-struct Result {
-    void *d = nullptr;
-    ~Result()
-    {
-        if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-    }
-};
 
 }  // namespace
 
@@ -468,12 +424,10 @@ int epik_amd_cohort_permanova_device(epik_amd_cohort *cohort, const void *d_kr, 
                                      uint32_t num_permutations, uint64_t seed, int pairwise, void *d_out, void *d_ssw,
                                      void *d_group_ss, void *stream)
 {
-    try {
+    return guarded("cohort_permanova_device", [&]() -> int {
         return permanova_device_impl(cohort, d_kr, labels, num_columns, num_permutations, seed, pairwise != 0, d_out, d_ssw, d_group_ss,
                                      static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_permanova_device: ") + e.what());
-    }
+    });
 }
 
 int epik_amd_cohort_permanova(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, const uint32_t *labels,
@@ -488,34 +442,27 @@ int epik_amd_cohort_permanova_metric(epik_amd_cohort *cohort, const epik_amd_tre
                                      const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                      epik_amd_permanova *out, double *ssw, double *group_ss)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (num_columns < 1 || num_columns > kColumns)
-            return fail_with(EPIK_AMD_ERR_INVALID, "num_columns = " + std::to_string(num_columns) + " is outside [1, 64]");
-        if (!labels || !out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_permanova", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(check_columns(num_columns));
+        COHORT_TRY(check_present(labels, out));
         const uint32_t S = cohort->num_samples;
-        if (const int rc = check_arguments(labels, S, num_columns, num_permutations, pairwise != 0); rc != EPIK_AMD_OK) return rc;
+        COHORT_TRY(check_arguments(labels, S, num_columns, num_permutations, pairwise != 0));
         const size_t tests = (size_t)num_columns * (1 + (pairwise ? kPairSlots : 0));
         const size_t out_bytes = tests * sizeof(epik_amd_permanova), ssw_bytes = tests * ((size_t)num_permutations + 1) * sizeof(double);
         const size_t group_bytes = (size_t)num_columns * kGroups * sizeof(double);
         HIP_TRY(hipSetDevice(cohort->device));
-        Result kr, r, s, g;
-        HIP_TRY(hipMalloc(&kr.d, (size_t)S * S * sizeof(double)));
-        HIP_TRY(hipMalloc(&r.d, out_bytes));
-        if (ssw) HIP_TRY(hipMalloc(&s.d, ssw_bytes));
-        if (group_ss) HIP_TRY(hipMalloc(&g.d, group_bytes));
-        if (const int rc = cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr); rc != EPIK_AMD_OK) return rc;
-        if (const int rc = permanova_device_impl(cohort, kr.d, labels, num_columns, num_permutations, seed, pairwise != 0, r.d, s.d, g.d,
-                                                 nullptr);
-            rc != EPIK_AMD_OK)
-            return rc;
-        HIP_TRY(hipMemcpy(out, r.d, out_bytes, hipMemcpyDeviceToHost));
-        if (ssw) HIP_TRY(hipMemcpy(ssw, s.d, ssw_bytes, hipMemcpyDeviceToHost));
-        if (group_ss) HIP_TRY(hipMemcpy(group_ss, g.d, group_bytes, hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_permanova: ") + e.what());
-    }
+        DeviceResult kr, r, s, g;
+        COHORT_TRY(kr.alloc((size_t)S * S * sizeof(double)));
+        COHORT_TRY(r.alloc(out_bytes));
+        COHORT_TRY(s.alloc(ssw_bytes, ssw != nullptr));
+        COHORT_TRY(g.alloc(group_bytes, group_ss != nullptr));
+        COHORT_TRY(cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr));
+        COHORT_TRY(permanova_device_impl(cohort, kr.d, labels, num_columns, num_permutations, seed, pairwise != 0, r.d, s.d, g.d, nullptr));
+        COHORT_TRY(r.copy_to(out, out_bytes));
+        COHORT_TRY(s.copy_to(ssw, ssw_bytes));
+        return g.copy_to(group_ss, group_bytes);
+    });
 }
 
 int epik_amd_cohort_permanova_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
@@ -532,37 +479,28 @@ int epik_amd_cohort_permanova_metric_host(const uint64_t *mass, uint32_t num_sam
                                           uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permanova *out, double *ssw,
                                           double *group_ss)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
-        if (!mass || !first || !branch_length || !labels || !out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_permanova_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(check_present(mass, first, branch_length, labels, out));
         std::string err;
-        if (const int rc = permanova_records(mass, num_samples, num_branches, first, branch_length, labels, num_columns,
-                                             num_permutations, seed, pairwise != 0, out, ssw, group_ss, err, metric);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_permanova_host: ") + e.what());
-    }
+        return rule_result(permanova_records(mass, num_samples, num_branches, first, branch_length, labels, num_columns, num_permutations,
+                                             seed, pairwise != 0, out, ssw, group_ss, err, metric),
+                           err);
+    });
 }
 
 int epik_amd_cohort_permanova_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
                                       uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                       epik_amd_permanova *out, double *ssw, double *group_ss)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (!kr || !totals || !labels || !out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_permanova_kr_host", [&]() -> int {
+        COHORT_TRY(check_host_samples(num_samples));
+        COHORT_TRY(check_present(kr, totals, labels, out));
         std::string err;
-        if (const int rc = permanova_records_of_kr(kr, totals, num_samples, labels, num_columns, num_permutations, seed, pairwise != 0,
-                                                   out, ssw, group_ss, err);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_permanova_kr_host: ") + e.what());
-    }
+        return rule_result(permanova_records_of_kr(kr, totals, num_samples, labels, num_columns, num_permutations, seed, pairwise != 0, out,
+                                                   ssw, group_ss, err),
+                           err);
+    });
 }
 
 }  // extern "C"

@@ -31,14 +31,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 
 namespace {
 
@@ -89,34 +86,27 @@ struct DispSpace {
 size_t permdisp_space(void *base, uint32_t padded, uint32_t M, bool pairwise, DispSpace *sp)
 {
     const size_t slots = 1 + (pairwise ? kPairSlots : 0), lists = pairwise ? kGroups : 1;
-    const auto up = [](size_t v) { return (v + 15) / 16 * 16; };
-    const size_t column = up((size_t)M * padded * 8), pool = up((size_t)M * lists * padded * 8), lab = up((size_t)M * padded * 4);
-    const size_t pos = up((size_t)M * lists * padded * 4), active = up(M * slots * 4), count = up((size_t)M * 4);
-    const size_t cols = up(M * sizeof(DispColumn)), tests = up(M * slots * sizeof(DispTest)), lam = up((size_t)M * padded);
-    const size_t two = up((size_t)M * lists * padded), mu = up(lists * padded * kChunk);
-    if (sp) {
-        char *b = static_cast<char *>(base);
-        sp->t = reinterpret_cast<double *>(b), b += column;
-        sp->m = reinterpret_cast<double *>(b), b += column;
-        sp->z = reinterpret_cast<double *>(b), b += column;
-        sp->r = reinterpret_cast<double *>(b), b += column;
-        sp->dr = reinterpret_cast<double *>(b), b += pool;
-        sp->lab = reinterpret_cast<uint32_t *>(b), b += lab;
-        sp->idx = reinterpret_cast<uint32_t *>(b), b += lab;
-        sp->pos = reinterpret_cast<uint32_t *>(b), b += pos;
-        sp->active = reinterpret_cast<uint32_t *>(b), b += active;
-        sp->count = reinterpret_cast<uint32_t *>(b), b += count;
-        sp->cols = reinterpret_cast<DispColumn *>(b), b += cols;
-        sp->tests = reinterpret_cast<DispTest *>(b), b += tests;
-        sp->lam = reinterpret_cast<uint8_t *>(b), b += lam;
-        sp->clip = reinterpret_cast<uint8_t *>(b), b += lam;
-        sp->two = reinterpret_cast<uint8_t *>(b), b += two;
-        sp->MU = reinterpret_cast<uint8_t *>(b);
-    }
-    return 4 * column + pool + 2 * lab + pos + active + count + cols + tests + 2 * lam + two + mu;
+    const size_t column = (size_t)M * padded, pool = (size_t)M * lists * padded;
+    Carver c(base);
+    const DispSpace parts{.t = c.take<double>(column),
+                          .m = c.take<double>(column),
+                          .z = c.take<double>(column),
+                          .r = c.take<double>(column),
+                          .dr = c.take<double>(pool),
+                          .lab = c.take<uint32_t>(column),
+                          .idx = c.take<uint32_t>(column),
+                          .pos = c.take<uint32_t>(pool),
+                          .active = c.take<uint32_t>(M * slots),
+                          .count = c.take<uint32_t>(M),
+                          .cols = c.take<DispColumn>(M),
+                          .tests = c.take<DispTest>(M * slots),
+                          .lam = c.take<uint8_t>(column),
+                          .clip = c.take<uint8_t>(column),
+                          .two = c.take<uint8_t>(pool),
+                          .MU = c.take<uint8_t>(lists * padded * kChunk)};
+    if (sp) *sp = parts;
+    return c.bytes();
 }
-
-__device__ inline double na_value() { return __longlong_as_double((long long)EPIK_AMD_NA_BITS); }
 
 struct DispArgs {
     const double *kr;
@@ -379,65 +369,41 @@ __global__ __launch_bounds__(kBlock) void permdisp_finish_kernel(const DispArgs 
     }
 }
 
-dim3 grid_of(const epik_amd_cohort *cohort, uint64_t units, uint64_t most)
-{
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({units, most, cap})));
-}
-
 int check_arguments(const uint32_t *labels, uint32_t S, uint32_t M, uint32_t P)
 {
     std::string err;
-    if (const int rc = permdisp_arguments_valid(labels, S, M, P, err); rc != EPIK_AMD_OK) return fail_with(rc, err);
-    return EPIK_AMD_OK;
+    return rule_result(permdisp_arguments_valid(labels, S, M, P, err), err);
 }
 
 int permdisp_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, uint32_t M, uint32_t P, uint64_t seed,
                          bool pairwise, void *d_out, void *d_stat, void *d_group_mean, void *d_z, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (M < 1 || M > kColumns) return fail_with(EPIK_AMD_ERR_INVALID, "num_columns = " + std::to_string(M) + " is outside [1, 64]");
-    if (!d_kr || !labels || !d_out || !d_group_mean || !d_z) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(check_columns(M));
+    COHORT_TRY(check_present(d_kr, labels, d_out, d_group_mean, d_z));
     const uint32_t S = cohort->num_samples, padded = cohort_padded_samples(cohort);
-    if (const int rc = check_arguments(labels, S, M, P); rc != EPIK_AMD_OK) return rc;
-    if (!cohort->d_total)
-        return fail_with(EPIK_AMD_ERR_INVALID, "the cohort has no distances yet: d_kr must be what kr_device wrote for this cohort");
+    COHORT_TRY(check_arguments(labels, S, M, P));
+    COHORT_TRY(check_has_distances(cohort));
     // the distinct labels of a column bound its G: the largest decides where the accumulators are, and each bounds the tests
     // of its column that can have something to permute (the grids of its launches; none below two labels)
-    uint32_t most_groups = 0;
-    std::vector<uint32_t> most_tests(M, 0);
-    for (uint32_t c = 0; c < M; ++c) {
-        uint32_t seen = 0;
-        for (uint32_t s = 0; s < S; ++s)
-            if (const uint32_t v = labels[(size_t)s * M + c]; v != kMissing) seen |= 1u << v;
-        const uint32_t distinct = (uint32_t)__builtin_popcount(seen);
-        most_groups = std::max<uint32_t>(most_groups, distinct);
-        if (distinct >= 2) most_tests[c] = 1 + (pairwise ? distinct * (distinct - 1) / 2 : 0);
-    }
+    std::vector<uint32_t> most_tests;
+    const uint32_t most_groups = most_distinct_labels(labels, S, M, kMissing, &most_tests);
+    for (uint32_t &n : most_tests) n = n >= 2 ? 1 + (pairwise ? n * (n - 1) / 2 : 0) : 0;
     HIP_TRY(hipSetDevice(cohort->device));
     HIP_TRY(hipDeviceSynchronize());  // (the distances enqueued on whatever stream, and an earlier call that reads the workspace)
-    const size_t bytes = permdisp_space(nullptr, padded, M, pairwise, nullptr);
-    if (bytes > cohort->permdisp_bytes) {
-        (void)hipFree(cohort->d_permdisp);
-        cohort->d_permdisp = nullptr, cohort->permdisp_bytes = 0;
-        HIP_TRY(hipMalloc(&cohort->d_permdisp, bytes));
-        cohort->permdisp_bytes = bytes;
-    }
+    COHORT_TRY(cohort_space_ensure(cohort, kSpacePermdisp, permdisp_space(nullptr, padded, M, pairwise, nullptr)));
     DispArgs args{};
-    permdisp_space(cohort->d_permdisp, padded, M, pairwise, &args.sp);
-    std::vector<uint32_t> lab((size_t)M * padded, kMissing);
-    for (uint32_t s = 0; s < S; ++s)
-        for (uint32_t c = 0; c < M; ++c) lab[(size_t)c * padded + s] = labels[(size_t)s * M + c];
-    HIP_TRY(hipMemcpy(args.sp.lab, lab.data(), lab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    permdisp_space(cohort->space[kSpacePermdisp].d, padded, M, pairwise, &args.sp);
+    COHORT_TRY(upload_labels_by_column(labels, S, M, padded, kMissing, args.sp.lab));
     const uint32_t slots = 1 + (pairwise ? kPairSlots : 0), lists = pairwise ? kGroups : 1;
     args.kr = static_cast<const double *>(d_kr), args.out = static_cast<epik_amd_permdisp *>(d_out);
     args.stat = static_cast<double *>(d_stat), args.group_mean = static_cast<double *>(d_group_mean), args.z = static_cast<double *>(d_z);
     args.seed = seed, args.num_samples = S, args.padded = padded, args.num_columns = M, args.slots = slots, args.lists = lists;
     args.num_permutations = P;
     const uint64_t tests = (uint64_t)M * slots;
-    hipLaunchKernelGGL(permdisp_columns_kernel, grid_of(cohort, M, kColumns), dim3(kWave), 0, stream, cohort->d_total, args);
-    hipLaunchKernelGGL(permdisp_distance_kernel, grid_of(cohort, M, kColumns), dim3(kBlock), 0, stream, args);
-    hipLaunchKernelGGL(permdisp_tests_kernel, grid_of(cohort, tests, kManyBlocks), dim3(kWave), 0, stream, args);
+    hipLaunchKernelGGL(permdisp_columns_kernel, cohort_grid(cohort, M, kColumns), dim3(kWave), 0, stream, cohort->d_total, args);
+    hipLaunchKernelGGL(permdisp_distance_kernel, cohort_grid(cohort, M, kColumns), dim3(kBlock), 0, stream, args);
+    hipLaunchKernelGGL(permdisp_tests_kernel, cohort_grid(cohort, tests, kManyBlocks), dim3(kWave), 0, stream, args);
     const bool registers = most_groups <= kRegisterGroups;
     const uint32_t lanes = registers ? kBlock : kLdsLanes;
     const size_t dynamic = registers ? 0 : (size_t)kGroups * lanes * sizeof(double);
@@ -448,29 +414,20 @@ int permdisp_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32
         for (uint32_t p0 = 1; p0 <= P; p0 += kChunk) {
             args.column = c, args.p0 = p0, args.np = std::min<uint32_t>(kChunk, P + 1 - p0);
             const uint64_t subs = (args.np + lanes - 1) / lanes, listed = most_tests[c];
-            hipLaunchKernelGGL(permdisp_labellings_kernel, grid_of(cohort, listed * args.np, kManyBlocks), dim3(kBlock), 0, stream, args);
+            hipLaunchKernelGGL(permdisp_labellings_kernel, cohort_grid(cohort, listed * args.np, kManyBlocks), dim3(kBlock), 0, stream, args);
             if (registers)
-                hipLaunchKernelGGL(permdisp_chains_kernel<kRegisterGroups>, grid_of(cohort, listed * subs, kManyBlocks), dim3(lanes), 0,
+                hipLaunchKernelGGL(permdisp_chains_kernel<kRegisterGroups>, cohort_grid(cohort, listed * subs, kManyBlocks), dim3(lanes), 0,
                                    stream, args);
             else
-                hipLaunchKernelGGL(permdisp_chains_kernel<0>, grid_of(cohort, listed * subs, kManyBlocks), dim3(lanes), dynamic, stream,
+                hipLaunchKernelGGL(permdisp_chains_kernel<0>, cohort_grid(cohort, listed * subs, kManyBlocks), dim3(lanes), dynamic, stream,
                                    args);
         }
     }
     const uint64_t finish = d_stat ? tests * ((uint64_t)P + 1) : tests;
-    hipLaunchKernelGGL(permdisp_finish_kernel, grid_of(cohort, (finish + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, args);
+    hipLaunchKernelGGL(permdisp_finish_kernel, cohort_grid(cohort, (finish + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, args);
     HIP_TRY(hipGetLastError());
     return EPIK_AMD_OK;
 }
-
-// a result in device memory for the synchronous entry, freed however the call ends
-struct Result {
-    void *d = nullptr;
-    ~Result()
-    {
-        if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-    }
-};
 
 }  // namespace
 
@@ -480,12 +437,10 @@ int epik_amd_cohort_permdisp_device(epik_amd_cohort *cohort, const void *d_kr, c
                                     uint32_t num_permutations, uint64_t seed, int pairwise, void *d_out, void *d_stat,
                                     void *d_group_mean, void *d_z, void *stream)
 {
-    try {
+    return guarded("cohort_permdisp_device", [&]() -> int {
         return permdisp_device_impl(cohort, d_kr, labels, num_columns, num_permutations, seed, pairwise != 0, d_out, d_stat, d_group_mean,
                                     d_z, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_permdisp_device: ") + e.what());
-    }
+    });
 }
 
 int epik_amd_cohort_permdisp(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, const uint32_t *labels,
@@ -500,36 +455,30 @@ int epik_amd_cohort_permdisp_metric(epik_amd_cohort *cohort, const epik_amd_tree
                                     const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                     epik_amd_permdisp *out, double *stat, double *group_mean, double *z)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (num_columns < 1 || num_columns > kColumns)
-            return fail_with(EPIK_AMD_ERR_INVALID, "num_columns = " + std::to_string(num_columns) + " is outside [1, 64]");
-        if (!labels || !out || !group_mean || !z) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_permdisp", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(check_columns(num_columns));
+        COHORT_TRY(check_present(labels, out, group_mean, z));
         const uint32_t S = cohort->num_samples;
-        if (const int rc = check_arguments(labels, S, num_columns, num_permutations); rc != EPIK_AMD_OK) return rc;
+        COHORT_TRY(check_arguments(labels, S, num_columns, num_permutations));
         const size_t tests = (size_t)num_columns * (1 + (pairwise ? kPairSlots : 0));
         const size_t out_bytes = tests * sizeof(epik_amd_permdisp), stat_bytes = tests * ((size_t)num_permutations + 1) * sizeof(double);
         const size_t mean_bytes = (size_t)num_columns * kGroups * sizeof(double), z_bytes = (size_t)num_columns * S * sizeof(double);
         HIP_TRY(hipSetDevice(cohort->device));
-        Result kr, r, s, g, zz;
-        HIP_TRY(hipMalloc(&kr.d, (size_t)S * S * sizeof(double)));
-        HIP_TRY(hipMalloc(&r.d, out_bytes));
-        if (stat) HIP_TRY(hipMalloc(&s.d, stat_bytes));
-        HIP_TRY(hipMalloc(&g.d, mean_bytes));
-        HIP_TRY(hipMalloc(&zz.d, z_bytes));
-        if (const int rc = cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr); rc != EPIK_AMD_OK) return rc;
-        if (const int rc = permdisp_device_impl(cohort, kr.d, labels, num_columns, num_permutations, seed, pairwise != 0, r.d, s.d, g.d,
-                                                zz.d, nullptr);
-            rc != EPIK_AMD_OK)
-            return rc;
-        HIP_TRY(hipMemcpy(out, r.d, out_bytes, hipMemcpyDeviceToHost));
-        if (stat) HIP_TRY(hipMemcpy(stat, s.d, stat_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(group_mean, g.d, mean_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(z, zz.d, z_bytes, hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_permdisp: ") + e.what());
-    }
+        DeviceResult kr, r, s, g, zz;
+        COHORT_TRY(kr.alloc((size_t)S * S * sizeof(double)));
+        COHORT_TRY(r.alloc(out_bytes));
+        COHORT_TRY(s.alloc(stat_bytes, stat != nullptr));
+        COHORT_TRY(g.alloc(mean_bytes));
+        COHORT_TRY(zz.alloc(z_bytes));
+        COHORT_TRY(cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr));
+        COHORT_TRY(permdisp_device_impl(cohort, kr.d, labels, num_columns, num_permutations, seed, pairwise != 0, r.d, s.d, g.d, zz.d,
+                                        nullptr));
+        COHORT_TRY(r.copy_to(out, out_bytes));
+        COHORT_TRY(s.copy_to(stat, stat_bytes));
+        COHORT_TRY(g.copy_to(group_mean, mean_bytes));
+        return zz.copy_to(z, z_bytes);
+    });
 }
 
 int epik_amd_cohort_permdisp_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
@@ -546,38 +495,28 @@ int epik_amd_cohort_permdisp_metric_host(const uint64_t *mass, uint32_t num_samp
                                          uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permdisp *out, double *stat,
                                          double *group_mean, double *z)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
-        if (!mass || !first || !branch_length || !labels || !out || !group_mean || !z)
-            return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_permdisp_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(check_present(mass, first, branch_length, labels, out, group_mean, z));
         std::string err;
-        if (const int rc = permdisp_records(mass, num_samples, num_branches, first, branch_length, labels, num_columns, num_permutations,
-                                            seed, pairwise != 0, out, stat, group_mean, z, err, metric);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_permdisp_host: ") + e.what());
-    }
+        return rule_result(permdisp_records(mass, num_samples, num_branches, first, branch_length, labels, num_columns, num_permutations,
+                                            seed, pairwise != 0, out, stat, group_mean, z, err, metric),
+                           err);
+    });
 }
 
 int epik_amd_cohort_permdisp_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
                                      uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                      epik_amd_permdisp *out, double *stat, double *group_mean, double *z)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (!kr || !totals || !labels || !out || !group_mean || !z) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_permdisp_kr_host", [&]() -> int {
+        COHORT_TRY(check_host_samples(num_samples));
+        COHORT_TRY(check_present(kr, totals, labels, out, group_mean, z));
         std::string err;
-        if (const int rc = permdisp_records_of_kr(kr, totals, num_samples, labels, num_columns, num_permutations, seed, pairwise != 0,
-                                                  out, stat, group_mean, z, err);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_permdisp_kr_host: ") + e.what());
-    }
+        return rule_result(permdisp_records_of_kr(kr, totals, num_samples, labels, num_columns, num_permutations, seed, pairwise != 0, out,
+                                                  stat, group_mean, z, err),
+                           err);
+    });
 }
 
 }  // extern "C"

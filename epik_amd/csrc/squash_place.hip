@@ -40,8 +40,7 @@
 #include <vector>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 
 namespace {
 
@@ -72,23 +71,17 @@ struct SquashSpace {
 // the bytes of the workspace for S samples and N branches; with `base`, where its parts lie
 size_t squash_space(void *base, uint32_t S, uint32_t N, SquashSpace *sp)
 {
-    size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t offset = at;
-        at += (bytes + 15) / 16 * 16;
-        return offset;
-    };
-    const size_t D = take((size_t)S * S * sizeof(double)), merged = take(2 * (size_t)N * sizeof(double));
-    const size_t row_val = take((size_t)S * sizeof(double)), ctl = take(sizeof(SquashControl));
-    const size_t row_col = take((size_t)S * sizeof(uint32_t)), live = take((size_t)S * sizeof(uint32_t));
-    const size_t w = take((size_t)S * sizeof(uint32_t)), node = take((size_t)S * sizeof(uint32_t));
-    if (sp) {
-        char *b = static_cast<char *>(base);
-        *sp = SquashSpace{reinterpret_cast<double *>(b + D), reinterpret_cast<double *>(b + merged), reinterpret_cast<double *>(b + row_val),
-                          reinterpret_cast<SquashControl *>(b + ctl), reinterpret_cast<uint32_t *>(b + row_col),
-                          reinterpret_cast<uint32_t *>(b + live), reinterpret_cast<uint32_t *>(b + w), reinterpret_cast<uint32_t *>(b + node)};
-    }
-    return at;
+    Carver c(base);
+    const SquashSpace parts{.D = c.take<double>((size_t)S * S),
+                            .merged = c.take<double>(2 * (size_t)N),
+                            .row_val = c.take<double>(S),
+                            .ctl = c.take<SquashControl>(1),
+                            .row_col = c.take<uint32_t>(S),
+                            .live = c.take<uint32_t>(S),
+                            .w = c.take<uint32_t>(S),
+                            .node = c.take<uint32_t>(S)};
+    if (sp) *sp = parts;
+    return c.bytes();
 }
 
 __global__ __launch_bounds__(kBlock) void squash_init_kernel(const uint64_t *__restrict__ total, uint32_t num_samples,
@@ -271,26 +264,24 @@ __global__ __launch_bounds__(kWave) void squash_dist_kernel(const double *__rest
 int squash_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, void *d_merges,
                        void *d_num_merges, hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    COHORT_TRY(check_cohort(cohort));
     const uint32_t N = cohort->num_branches, S = cohort->num_samples, padded = cohort_padded_samples(cohort);
-    if (!branch_length || !d_num_merges || (!d_merges && S > 1)) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    COHORT_TRY(check_present(branch_length, d_num_merges));
+    if (S > 1) COHORT_TRY(check_present(d_merges));
     HIP_TRY(hipSetDevice(cohort->device));
-    if (!cohort->d_squash) HIP_TRY(hipMalloc(&cohort->d_squash, squash_space(nullptr, S, N, nullptr)));
+    // (one size a cohort: allocated by the first call and never freed by a later one, so the device need not be drained yet)
+    COHORT_TRY(cohort_space_ensure(cohort, kSpaceSquash, squash_space(nullptr, S, N, nullptr)));
     SquashSpace sp;
-    squash_space(cohort->d_squash, S, N, &sp);
+    squash_space(cohort->space[kSpaceSquash].d, S, N, &sp);
     // the checks of the tree and the lengths, the planes and D = the KR matrix; it will be overwritten
-    if (const int rc = cohort_kr_enqueue(cohort, tree, branch_length, sp.D, stream); rc != EPIK_AMD_OK) return rc;
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
-    const auto blocks = [&](uint64_t units, uint64_t per, uint64_t most) {
-        return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(units + per - 1) / per, most, cap})));
-    };
+    COHORT_TRY(cohort_kr_enqueue(cohort, tree, branch_length, sp.D, stream));
     auto *merges = static_cast<epik_amd_squash_merge *>(d_merges);
     auto *num_merges = static_cast<uint32_t *>(d_num_merges);
-    hipLaunchKernelGGL(squash_init_kernel, blocks(S, kBlock, kRowBlocks), dim3(kBlock), 0, stream, cohort->d_total, S, sp.live, sp.w,
+    hipLaunchKernelGGL(squash_init_kernel, cohort_grid_per(cohort, S, kBlock, kRowBlocks), dim3(kBlock), 0, stream, cohort->d_total, S, sp.live, sp.w,
                        sp.node, sp.ctl, num_merges);
     HIP_TRY(hipGetLastError());
-    const dim3 row_grid = blocks(std::max(S, (N + kBlock - 1) / kBlock * kBlockWaves), kBlockWaves, kRowBlocks);
-    const dim3 pick_grid = blocks(N, kBlock, kPickBlocks), dist_grid = blocks(S, kWave, kRowBlocks);
+    const dim3 row_grid = cohort_grid_per(cohort, std::max(S, (N + kBlock - 1) / kBlock * kBlockWaves), kBlockWaves, kRowBlocks);
+    const dim3 pick_grid = cohort_grid_per(cohort, N, kBlock, kPickBlocks), dist_grid = cohort_grid_per(cohort, S, kWave, kRowBlocks);
     for (uint32_t step = 0; step + 1 < S; ++step) {
         hipLaunchKernelGGL(squash_rows_kernel, row_grid, dim3(kBlock), 0, stream, cohort->d_planes, N, padded, sp.merged, sp.ctl, sp.D,
                            sp.live, S, sp.row_val, sp.row_col);
@@ -310,55 +301,38 @@ extern "C" {
 int epik_amd_cohort_squash_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
                                   void *d_merges, void *d_num_merges, void *stream)
 {
-    try {
+    return guarded("cohort_squash_device", [&]() -> int {
         return squash_device_impl(cohort, tree, branch_length, d_merges, d_num_merges, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_squash_device: ") + e.what());
-    }
+    });
 }
 
 int epik_amd_cohort_squash(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
                            epik_amd_squash_merge *merges, uint32_t *num_merges)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
+    return guarded("cohort_squash", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
         const size_t records = cohort->num_samples - 1, bytes = records * sizeof(epik_amd_squash_merge);
-        if (!num_merges || (!merges && records)) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+        COHORT_TRY(check_present(num_merges));
+        if (records) COHORT_TRY(check_present(merges));
         HIP_TRY(hipSetDevice(cohort->device));
-        struct Records {
-            void *d = nullptr;
-            ~Records()
-            {
-                if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-            }
-        } m;
-        HIP_TRY(hipMalloc(&m.d, bytes + sizeof(uint32_t)));  // the records, then the count
-        void *d_count = static_cast<char *>(m.d) + bytes;
-        if (const int rc = squash_device_impl(cohort, tree, branch_length, m.d, d_count, nullptr); rc != EPIK_AMD_OK) return rc;
-        if (records) HIP_TRY(hipMemcpy(merges, m.d, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(num_merges, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_squash: ") + e.what());
-    }
+        DeviceResult m;
+        COHORT_TRY(m.alloc(bytes + sizeof(uint32_t)));  // the records, then the count
+        COHORT_TRY(squash_device_impl(cohort, tree, branch_length, m.d, m.at(bytes), nullptr));
+        if (records) COHORT_TRY(m.copy_to(merges, bytes));
+        return m.copy_to(num_merges, sizeof(uint32_t), bytes);
+    });
 }
 
 int epik_amd_cohort_squash_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                 const double *branch_length, epik_amd_squash_merge *merges, uint32_t *num_merges)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
-        if (!mass || !first || !branch_length || !num_merges || (!merges && num_samples > 1))
-            return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_squash_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(check_present(mass, first, branch_length, num_merges));
+        if (num_samples > 1) COHORT_TRY(check_present(merges));
         std::string err;
-        if (const int rc = squash_merges(mass, num_samples, num_branches, first, branch_length, merges, num_merges, err);
-            rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_squash_host: ") + e.what());
-    }
+        return rule_result(squash_merges(mass, num_samples, num_branches, first, branch_length, merges, num_merges, err), err);
+    });
 }
 
 }  // extern "C"

@@ -20,14 +20,12 @@
 // either only reaches the accumulators of its own pairs, which the rule overwrites (-1.0) or the bounds keep from memory.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <string>
 #include <vector>
 
 #include "../host/cohort.hpp"
-#include "cohort_device.hpp"
-#include "host_entry.hpp"
+#include "cohort_entry.hpp"
 
 namespace {
 
@@ -139,23 +137,18 @@ int metric_valid(uint32_t metric)
 int unifrac_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric, void *d_out,
                         hipStream_t stream)
 {
-    if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-    if (!branch_length || !d_out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
-    if (const int rc = metric_valid(metric); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(check_cohort(cohort));
+    COHORT_TRY(check_present(branch_length, d_out));
+    COHORT_TRY(metric_valid(metric));
     const uint32_t N = cohort->num_branches, S = cohort->num_samples, padded = cohort_padded_samples(cohort);
-    std::vector<double> half(N);
-    for (uint32_t b = 0; b < N; ++b) {
-        if (!(branch_length[b] >= 0.0) || !std::isfinite(branch_length[b]))
-            return fail_with(EPIK_AMD_ERR_INVALID, "branch " + std::to_string(b) + ": the branch length is negative or not finite");
-        half[b] = 0.5 * branch_length[b];
-    }
+    std::vector<double> half;
+    COHORT_TRY(half_branch_lengths(branch_length, N, half));
     // the checks of the tree, the device drained (a distance still reading d_half), the planes: one normalisation a call
     const uint32_t *d_first = nullptr;
-    if (const int rc = cohort_normalise_enqueue(cohort, tree, stream, &d_first); rc != EPIK_AMD_OK) return rc;
+    COHORT_TRY(cohort_normalise_enqueue(cohort, tree, stream, &d_first));
     HIP_TRY(hipMemcpy(cohort->d_half, half.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
-    const uint64_t cap = cohort->max_blocks_cap ? cohort->max_blocks_cap : ~0ull;
     const uint64_t side = padded / kTile, tiles = side * (side + 1) / 2;
-    const dim3 grid((uint32_t)std::min<uint64_t>({tiles, kUnifracBlocks, cap}));
+    const dim3 grid = cohort_grid(cohort, tiles, kUnifracBlocks);
     auto *out = static_cast<double *>(d_out);
     if (metric == EPIK_AMD_DISTANCE_UNWEIGHTED)
         hipLaunchKernelGGL(cohort_unifrac_kernel<EPIK_AMD_DISTANCE_UNWEIGHTED>, grid, dim3(kBlock), 0, stream, cohort->d_planes,
@@ -191,51 +184,35 @@ extern "C" {
 int epik_amd_cohort_unifrac_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
                                    void *d_out, void *stream)
 {
-    try {
+    return guarded("cohort_unifrac_device", [&]() -> int {
         return unifrac_device_impl(cohort, tree, branch_length, metric, d_out, static_cast<hipStream_t>(stream));
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_unifrac_device: ") + e.what());
-    }
+    });
 }
 
 int epik_amd_cohort_unifrac(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
                             double *out)
 {
-    try {
-        if (!cohort) return fail_with(EPIK_AMD_ERR_INVALID, "null cohort");
-        if (!out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_unifrac", [&]() -> int {
+        COHORT_TRY(check_cohort(cohort));
+        COHORT_TRY(check_present(out));
         const size_t bytes = (size_t)cohort->num_samples * cohort->num_samples * sizeof(double);
         HIP_TRY(hipSetDevice(cohort->device));
-        struct Matrix {
-            void *d = nullptr;
-            ~Matrix()
-            {
-                if (d) (void)hipDeviceSynchronize(), (void)hipFree(d);
-            }
-        } m;
-        HIP_TRY(hipMalloc(&m.d, bytes));
-        if (const int rc = unifrac_device_impl(cohort, tree, branch_length, metric, m.d, nullptr); rc != EPIK_AMD_OK) return rc;
-        HIP_TRY(hipMemcpy(out, m.d, bytes, hipMemcpyDeviceToHost));
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_unifrac: ") + e.what());
-    }
+        DeviceResult m;
+        COHORT_TRY(m.alloc(bytes));
+        COHORT_TRY(unifrac_device_impl(cohort, tree, branch_length, metric, m.d, nullptr));
+        return m.copy_to(out, bytes);
+    });
 }
 
 int epik_amd_cohort_unifrac_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                  const double *branch_length, uint32_t metric, double *out)
 {
-    try {
-        if (num_samples == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a cohort has at least one sample (num_samples is 0)");
-        if (num_branches == 0) return fail_with(EPIK_AMD_ERR_INVALID, "a tree has at least one branch");
-        if (!mass || !first || !branch_length || !out) return fail_with(EPIK_AMD_ERR_INVALID, "null argument");
+    return guarded("cohort_unifrac_host", [&]() -> int {
+        COHORT_TRY(check_host_shape(num_samples, num_branches));
+        COHORT_TRY(check_present(mass, first, branch_length, out));
         std::string err;
-        if (const int rc = unifrac_matrix(mass, num_samples, num_branches, first, branch_length, metric, out, err); rc != EPIK_AMD_OK)
-            return fail_with(rc, err);
-        return EPIK_AMD_OK;
-    } catch (const std::exception &e) {
-        return fail_with(EPIK_AMD_ERR_INVALID, std::string("cohort_unifrac_host: ") + e.what());
-    }
+        return rule_result(unifrac_matrix(mass, num_samples, num_branches, first, branch_length, metric, out, err), err);
+    });
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // host_test.cpp -- CPU unit checks of the host-side callers (FASTA, Newick, jplace
-// formatting, --max-ram parsing, database container).  Run by tests/test_host_cpu.py;
+// formatting, --max-ram parsing, database container, the workspace carver).  Run by tests/test_host_cpu.py;
 // exits non-zero on the first failure.  No GPU call is made.
 #include <cmath>
 #include <cstdio>
@@ -14,6 +14,8 @@
 #include "seq_record.hpp"
 
 #include "report.hpp"
+
+#include "../csrc/carve.hpp"
 
 static int failures = 0;
 #define CHECK(cond)                                                              \
@@ -184,6 +186,44 @@ int main(int argc, char** argv)
             threw = std::string(e.what()).find("EPIKAMD1") != std::string::npos;
         }
         CHECK(threw);
+    }
+
+    // --- the carver of the cohort analyses' workspaces (csrc/carve.hpp) ---
+    {
+        // the same list of parts, once to size the allocation (a null base) and once to name its parts
+        struct Parts {
+            double* a;
+            char* none;
+            uint32_t* b;
+            char *c1, *c15, *c16, *c17;
+            size_t bytes;
+        };
+        const auto carve = [](void* base) {
+            Carver c(base);
+            Parts p{};
+            p.a = c.take<double>(3), p.none = c.take<char>(0), p.b = c.take<uint32_t>(5);
+            p.c1 = c.take<char>(1), p.c15 = c.take<char>(15), p.c16 = c.take<char>(16), p.c17 = c.take<char>(17);
+            p.bytes = c.bytes();
+            return p;
+        };
+        const Parts sized = carve(nullptr);
+        CHECK(!sized.a && !sized.none && !sized.b && !sized.c1 && !sized.c15 && !sized.c16 && !sized.c17);
+        CHECK(sized.bytes == 32 + 0 + 32 + 16 + 16 + 16 + 32);  // (24, 0, 20, 1, 15, 16 and 17 bytes, each rounded up to 16)
+        alignas(16) char buffer[160];
+        const Parts p = carve(buffer);
+        CHECK(p.bytes == sized.bytes && p.bytes <= sizeof buffer);
+        const char* starts[] = {reinterpret_cast<char*>(p.a), p.none, reinterpret_cast<char*>(p.b), p.c1, p.c15, p.c16, p.c17};
+        const size_t sizes[] = {3 * sizeof(double), 0, 5 * sizeof(uint32_t), 1, 15, 16, 17};
+        for (size_t i = 0; i < 7; ++i) {
+            const size_t at = (size_t)(starts[i] - buffer);
+            CHECK(at % 16 == 0 && starts[i] >= buffer && at + sizes[i] <= p.bytes);
+            // in order, and no part reaches the next one (the part of 0 bytes shares its start with the part after it)
+            if (i + 1 < 7) CHECK(starts[i] + sizes[i] <= starts[i + 1]);
+        }
+        CHECK(p.none == reinterpret_cast<char*>(p.b));  // a part of 0 elements takes nothing
+        CHECK(p.c15 - p.c1 == 16 && p.c16 - p.c15 == 16 && p.c17 - p.c16 == 16 && buffer + p.bytes - p.c17 == 32);
+        CHECK(Carver::rounded(0) == 0 && Carver::rounded(1) == 16 && Carver::rounded(15) == 16 && Carver::rounded(16) == 16 &&
+              Carver::rounded(17) == 32);
     }
     if (failures == 0) std::cout << "host tests ok" << std::endl;
     return failures ? 1 : 0;

@@ -1,7 +1,8 @@
 """PERMDISP of a cohort's samples over their KR distances on the device: epik_amd_cohort_permdisp / _permdisp_device against the
 host mirror and the rule restated in numpy (test_permdisp_cpu.numpy_permdisp), bit for bit, the records, every stat[p], the
 group means and z; both accumulator paths (G <= 4 in registers, beyond in LDS), the chunk of labellings stepped over, two
-workgroups; the star fed through d_kr; no side effects; the errors.  (epik-dna --cohort --cohort-pcoa --cohort-permdisp
+workgroups; the star fed through d_kr; no side effects; the errors; one handle called with one column, three columns pairwise
+and one column again (the workspace grows, then the larger buffer is carved for the smaller shape).  (epik-dna --cohort --cohort-pcoa --cohort-permdisp
 --cohort-permanova end to end is in test_pcoa_gpu.)
 """
 import numpy as np
@@ -121,6 +122,53 @@ def test_permdisp_equals_the_host_mirror_and_the_restatement_bit_for_bit(placer_
                     assert lean.stat is None and lean.records[0].tobytes() == want.records[0].tobytes(), what
         for key in env:
             monkeypatch.delenv(key)
+
+
+# the switches of the analyses around PERMDISP (test_cohort_lifecycle_gpu, test_model_lifecycle_gpu): "0" forces their general paths
+SWITCHES = ("EPIK_AMD_EDGETEST_LDS", "EPIK_AMD_PERMANOVA_LDS", "EPIK_AMD_EPCA_LDS", "EPIK_AMD_CORRELATION_LDS", "EPIK_AMD_MODEL_LDS",
+            "EPIK_AMD_PCOA_LDS")
+GROWTH = {}
+
+
+def growth_calls():
+    """The KR matrix of 70 samples on the tree of 7 branches (padded to 96, one sample without mass) and three calls at P = 9 with
+    the host mirror's Permdisp: one column; three columns pairwise, whose workspace is some thirty times the first call's (the
+    pool of labellings alone has 32 lists for 1); and one column again."""
+    if not GROWTH:
+        parent, bl, first, db = kr_case(7)
+        rng = np.random.default_rng(2377)
+        mass = random_cells(rng, 70, 7, empty=1, bits=42)
+        kr, totals = cohort_mod.kr_host(mass, first, bl), cohort_mod.totals_of(mass)
+        one, three = capped_labels(rng, 70, False)[:, 1:2].copy(), capped_labels(rng, 70, True)
+        calls = [(labels, 9, int(rng.integers(0, 1 << 63)), pairwise) for labels, pairwise in ((one, False), (three, True), (one, False))]
+        assert [c[0].shape for c in calls] == [(70, 1), (70, 3), (70, 1)]
+        GROWTH["case"] = (parent, bl, db, mass, kr, [(c, cohort_mod.permdisp_kr_host(kr, totals, *c)) for c in calls])
+    return GROWTH["case"]
+
+
+@pytest.mark.parametrize("variant", ("as created", "the general paths"))
+def test_the_workspace_grows_with_the_columns_and_is_carved_again_for_fewer(placer_cls, monkeypatch, variant):
+    """One handle, one matrix: the second call needs a larger workspace than the first allocated, the third carves the larger
+    buffer for the smaller shape.  A workspace kept too small, or parts laid out for another shape, cannot give these bytes."""
+    import torch
+    for var in ENV + SWITCHES:
+        monkeypatch.delenv(var, raising=False)
+    if variant == "the general paths":
+        for switch in SWITCHES:
+            monkeypatch.setenv(switch, "0")
+    parent, bl, db, mass, kr, calls = growth_calls()
+    # the comparison cannot pass on NAs alone, and the pairwise call has defined pairs
+    assert all(not np.isnan(want.records["p"][:, 0]).any() for _, want in calls)
+    assert int((~np.isnan(calls[1][1].records["p"][:, 1:])).sum()) >= 3
+    with placer_cls.from_synth(db) as pl, pl.tree(parent, bl) as tree, pl.cohort(70) as cohort:
+        cohort.add_cells(mass, None, None)
+        d_kr = torch.full((70 * 70,), np.nan, dtype=torch.float64, device=f"cuda:{pl.device}")
+        cohort.kr_device(tree, bl, d_kr.data_ptr())
+        torch.cuda.synchronize()
+        assert same_bits(d_kr.cpu().numpy().reshape(70, 70), kr), variant
+        for k, (call, want) in enumerate(calls):
+            same_permdisp(device_permdisp_raw(pl, cohort, d_kr, *call), want, (variant, "call", k + 1))
+        assert same_bits(d_kr.cpu().numpy().reshape(70, 70), kr), (variant, "after")
 
 
 def test_the_star_through_d_kr_and_the_errors(placer_cls, monkeypatch):
