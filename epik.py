@@ -39,6 +39,9 @@ cohort_permdisp_<list>.tsv; --cohort-permdisp-permutations P (default 999), --co
 over the columns of FILE (a TSV, as --cohort-permanova's) that LIST names, comma-separated f:NAME (a factor) or n:NAME (a
 numeric covariate) in test order, cohort_model_<list>.tsv; --cohort-model-permutations P (default 999), --cohort-model-seed X
 (default 1).
+--cohort-strata FILE [--cohort-strata-column NAME], with any of the four tests above: permute within strata only (a subject
+sampled several times, a batch); a column of FILE (a TSV, as --cohort-permanova's, any number of labels) gives every sample
+its stratum, NAME is required when FILE has several columns; the tests' files end their first line in <TAB>strata=NAME.
 --cohort-pcoa, with --cohort: the principal coordinates of the samples over the KR distances, all eigenvalues with the
 negative ones of a distance that is not Euclidean, cohort_pcoa_<list>.tsv; --cohort-pcoa-components K axes (default 5).
 --cohort-unifrac LIST, with --cohort: the UniFrac distances between every two samples, LIST a comma-separated subset of
@@ -183,6 +186,12 @@ PLACE_OPTIONS = [
                                             help="With --cohort-model: the number of permutations [default: 999].")),
     (("--cohort-model-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
                                     help="With --cohort-model: the seed of the permutations, a uint64 [default: 1].")),
+    (("--cohort-strata",), dict(type=click.Path(), default=None,
+                                help="With --cohort-permanova, --cohort-permdisp, --cohort-edge-test or --cohort-model: a TSV (laid "
+                                     "out as --cohort-permanova's, any number of labels) whose column gives every sample its "
+                                     "stratum: those tests permute within strata only (repeated measures, batches).")),
+    (("--cohort-strata-column",), dict(type=str, default=None,
+                                       help="With --cohort-strata: the column of its file; required when the file has several.")),
     (("--cohort-pcoa",), dict(is_flag=True, help="With --cohort: also compute the principal coordinates of the samples over "
                                                  "their KR distances on the device and write cohort_pcoa_<list>.tsv (all "
                                                  "eigenvalues, the negative ones included, and every sample's coordinates).")),
@@ -228,7 +237,8 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                    cohort_edge_test=None, cohort_edge_test_permutations=None, cohort_edge_test_seed=None,
                    cohort_pcoa=False, cohort_pcoa_components=None, cohort_permdisp=None, cohort_permdisp_permutations=None,
                    cohort_permdisp_seed=None, cohort_permdisp_pairwise=False, cohort_unifrac=None, cohort_distance=None,
-                   cohort_model=None, cohort_model_terms=None, cohort_model_permutations=None, cohort_model_seed=None):
+                   cohort_model=None, cohort_model_terms=None, cohort_model_permutations=None, cohort_model_seed=None,
+                   cohort_strata=None, cohort_strata_column=None):
     if taxonomy_mass is not None and taxonomy is None:
         raise click.UsageError("--taxonomy-mass needs --taxonomy")
     if taxonomy_per_read and taxonomy is None:
@@ -297,6 +307,11 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
             raise click.UsageError(f"{flag} needs --cohort-model")
     if cohort_model is not None and cohort_model_terms is None:
         raise click.UsageError("--cohort-model needs --cohort-model-terms")
+    if cohort_strata_column is not None and cohort_strata is None:
+        raise click.UsageError("--cohort-strata-column needs --cohort-strata")
+    if cohort_strata is not None and cohort_permanova is None and cohort_permdisp is None and cohort_edge_test is None \
+            and cohort_model is None:
+        raise click.UsageError("--cohort-strata needs --cohort-permanova, --cohort-permdisp, --cohort-edge-test or --cohort-model")
     if cohort_pcoa and not cohort:
         raise click.UsageError("--cohort-pcoa needs --cohort")
     if cohort_pcoa_components is not None and not cohort_pcoa:
@@ -390,6 +405,10 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
             argv += ["--cohort-permdisp-seed", str(int(cohort_permdisp_seed))]
         if cohort_permdisp_pairwise:
             argv += ["--cohort-permdisp-pairwise"]
+    if cohort_strata is not None:
+        argv += ["--cohort-strata", str(cohort_strata)]
+        if cohort_strata_column is not None:
+            argv += ["--cohort-strata-column", str(cohort_strata_column)]
     if cohort_model is not None:
         argv += ["--cohort-model", str(cohort_model), "--cohort-model-terms", str(cohort_model_terms)]
         if cohort_model_permutations is not None:

@@ -225,6 +225,21 @@ EXPORTS = (
     "epik_amd_cohort_permdisp_metric",
     "epik_amd_cohort_permdisp_metric_host",
     "epik_amd_cohort_permdisp_kr_host",
+    "epik_amd_cohort_permanova_strata_device",
+    "epik_amd_cohort_permanova_strata",
+    "epik_amd_cohort_permanova_strata_host",
+    "epik_amd_cohort_permanova_strata_kr_host",
+    "epik_amd_cohort_permdisp_strata_device",
+    "epik_amd_cohort_permdisp_strata",
+    "epik_amd_cohort_permdisp_strata_host",
+    "epik_amd_cohort_permdisp_strata_kr_host",
+    "epik_amd_cohort_model_strata_device",
+    "epik_amd_cohort_model_strata",
+    "epik_amd_cohort_model_strata_host",
+    "epik_amd_cohort_model_strata_kr_host",
+    "epik_amd_cohort_edgetest_strata_device",
+    "epik_amd_cohort_edgetest_strata",
+    "epik_amd_cohort_edgetest_strata_host",
     "epik_amd_placer_cohort_reads",
     "epik_amd_placer_cohort_strands",
     "epik_amd_placer_cohort_frames",
@@ -651,6 +666,19 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_edgetest.argtypes = [vp, vp, vp, u32, u32, u64, vp, vp, vp]
     lib.epik_amd_cohort_edgetest_host.restype = i32
     lib.epik_amd_cohort_edgetest_host.argtypes = [vp, u32, u32, vp, vp, u32, u32, u64, vp, vp, vp]
+    # (the strata rule's entries: a sibling's arguments, then strata)
+    for name, sibling in (("permanova_strata_device", "permanova_device"), ("permanova_strata", "permanova_metric"),
+                          ("permanova_strata_host", "permanova_metric_host"), ("permanova_strata_kr_host", "permanova_kr_host"),
+                          ("permdisp_strata_device", "permdisp_device"), ("permdisp_strata", "permdisp_metric"),
+                          ("permdisp_strata_host", "permdisp_metric_host"), ("permdisp_strata_kr_host", "permdisp_kr_host"),
+                          ("model_strata_device", "model_device"), ("model_strata", "model_metric"),
+                          ("model_strata_host", "model_metric_host"), ("model_strata_kr_host", "model_kr_host"),
+                          ("edgetest_strata_device", "edgetest_device"), ("edgetest_strata", "edgetest"),
+                          ("edgetest_strata_host", "edgetest_host")):
+        if not hasattr(lib, "epik_amd_cohort_" + name):  # (an older library named by EPIK_AMD_LIB: tools/strata_rate.py's yardstick)
+            continue
+        getattr(lib, "epik_amd_cohort_" + name).restype = i32
+        getattr(lib, "epik_amd_cohort_" + name).argtypes = getattr(lib, "epik_amd_cohort_" + sibling).argtypes + [vp]
     lib.epik_amd_placer_cohort_reads.restype = i32
     lib.epik_amd_placer_cohort_reads.argtypes = [vp, vp, vp, vp, vp, vp, u64]
     for name in ("epik_amd_placer_cohort_strands", "epik_amd_placer_cohort_frames", "epik_amd_placer_cohort_mates"):

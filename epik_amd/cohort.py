@@ -408,6 +408,39 @@ def _labels(labels, num_samples: int) -> np.ndarray:
     return labels
 
 
+#: the entry that takes strata, by the entry that a call without them goes through
+_STRATA_ENTRY = {
+    "permanova_device": "permanova_strata_device",
+    "permanova_metric": "permanova_strata",
+    "permanova_metric_host": "permanova_strata_host",
+    "permanova_kr_host": "permanova_strata_kr_host",
+    "permdisp_device": "permdisp_strata_device",
+    "permdisp_metric": "permdisp_strata",
+    "permdisp_metric_host": "permdisp_strata_host",
+    "permdisp_kr_host": "permdisp_strata_kr_host",
+    "model_device": "model_strata_device",
+    "model_metric": "model_strata",
+    "model_metric_host": "model_strata_host",
+    "model_kr_host": "model_strata_kr_host",
+    "edgetest_device": "edgetest_strata_device",
+    "edgetest": "edgetest_strata",
+    "edgetest_host": "edgetest_strata_host",
+}
+
+
+def _call(lib, entry: str, strata, num_samples: int, *args) -> None:
+    """`epik_amd_cohort_<entry>(*args)`, checked.  With `strata` (one id per sample, any uint32: the permutations stay
+    within them, the strata rule of include/epik_amd.h) its `_strata` sibling is called with them as the last argument;
+    without, the entry itself, as before."""
+    if strata is None:
+        capi.check(getattr(lib, "epik_amd_cohort_" + entry)(*args))
+        return
+    strata = np.ascontiguousarray(strata, dtype=np.uint32)
+    if strata.shape != (num_samples,):
+        raise ValueError(f"strata must be [num_samples = {num_samples}]")
+    capi.check(getattr(lib, "epik_amd_cohort_" + _STRATA_ENTRY[entry])(*args, strata.ctypes.data))
+
+
 def _permanova_buffers(m: int, permutations: int, pairwise: bool, with_ssw: bool):
     slots = 1 + (capi.PERMANOVA_PAIR_SLOTS if pairwise else 0)
     records = np.zeros((max(m, 1), slots), dtype=capi.PERMANOVA)
@@ -416,7 +449,7 @@ def _permanova_buffers(m: int, permutations: int, pairwise: bool, with_ssw: bool
 
 
 def permanova_kr_host(kr, totals, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
-                      with_ssw: bool = True) -> Permanova:
+                      with_ssw: bool = True, strata=None) -> Permanova:
     """PERMANOVA of the rule from a KR matrix kr[S][S] and totals[S] (T_s) on the host
     (`epik_amd_cohort_permanova_kr_host`)."""
     lib = capi.load()
@@ -429,14 +462,14 @@ def permanova_kr_host(kr, totals, labels, permutations: int = 999, seed: int = 1
         raise ValueError("one total mass per sample")
     labels = _labels(labels, s)
     records, ssw, group_ss = _permanova_buffers(labels.shape[1], permutations, pairwise, with_ssw)
-    capi.check(lib.epik_amd_cohort_permanova_kr_host(kr.ctypes.data, totals.ctypes.data, s, labels.ctypes.data, labels.shape[1],
-                                                     int(permutations), int(seed), int(bool(pairwise)), records.ctypes.data,
-                                                     ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data))
+    _call(lib, "permanova_kr_host", strata, s, kr.ctypes.data, totals.ctypes.data, s, labels.ctypes.data, labels.shape[1],
+          int(permutations), int(seed), int(bool(pairwise)), records.ctypes.data,
+          ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data)
     return Permanova(records, ssw, group_ss)
 
 
 def permanova_host(mass, first, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
-                   with_ssw: bool = True, metric="kr") -> Permanova:
+                   with_ssw: bool = True, metric="kr", strata=None) -> Permanova:
     """PERMANOVA of the rule for mass[S][N] and labels[S][M] (0xffffffff: missing) over the distance `metric` on the host
     (`epik_amd_cohort_permanova_metric_host`)."""
     lib = capi.load()
@@ -444,10 +477,10 @@ def permanova_host(mass, first, branch_length, labels, permutations: int = 999, 
     s, n = mass.shape
     labels = _labels(labels, s)
     records, ssw, group_ss = _permanova_buffers(labels.shape[1], permutations, pairwise, with_ssw)
-    capi.check(lib.epik_amd_cohort_permanova_metric_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data,
-                                                         metric_id(metric), labels.ctypes.data, labels.shape[1], int(permutations),
-                                                         int(seed), int(bool(pairwise)), records.ctypes.data,
-                                                         ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data))
+    _call(lib, "permanova_metric_host", strata, s, mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data,
+          metric_id(metric), labels.ctypes.data, labels.shape[1], int(permutations),
+          int(seed), int(bool(pairwise)), records.ctypes.data,
+          ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data)
     return Permanova(records, ssw, group_ss)
 
 
@@ -470,7 +503,7 @@ def _permdisp_buffers(m: int, s: int, permutations: int, pairwise: bool, with_st
 
 
 def permdisp_kr_host(kr, totals, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
-                     with_stat: bool = True) -> Permdisp:
+                     with_stat: bool = True, strata=None) -> Permdisp:
     """PERMDISP of the rule from a KR matrix kr[S][S] and totals[S] (T_s) on the host (`epik_amd_cohort_permdisp_kr_host`)."""
     lib = capi.load()
     kr = np.ascontiguousarray(kr, dtype=np.float64)
@@ -482,15 +515,15 @@ def permdisp_kr_host(kr, totals, labels, permutations: int = 999, seed: int = 1,
         raise ValueError("one total mass per sample")
     labels = _labels(labels, s)
     out = _permdisp_buffers(labels.shape[1], s, permutations, pairwise, with_stat)
-    capi.check(lib.epik_amd_cohort_permdisp_kr_host(kr.ctypes.data, totals.ctypes.data, s, labels.ctypes.data, labels.shape[1],
-                                                    int(permutations), int(seed), int(bool(pairwise)), out.records.ctypes.data,
-                                                    out.stat.ctypes.data if with_stat else None, out.group_mean.ctypes.data,
-                                                    out.z.ctypes.data))
+    _call(lib, "permdisp_kr_host", strata, s, kr.ctypes.data, totals.ctypes.data, s, labels.ctypes.data, labels.shape[1],
+          int(permutations), int(seed), int(bool(pairwise)), out.records.ctypes.data,
+          out.stat.ctypes.data if with_stat else None, out.group_mean.ctypes.data,
+          out.z.ctypes.data)
     return out
 
 
 def permdisp_host(mass, first, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
-                  with_stat: bool = True, metric="kr") -> Permdisp:
+                  with_stat: bool = True, metric="kr", strata=None) -> Permdisp:
     """PERMDISP of the rule for mass[S][N] and labels[S][M] (0xffffffff: missing) over the distance `metric` on the host
     (`epik_amd_cohort_permdisp_metric_host`)."""
     lib = capi.load()
@@ -498,11 +531,11 @@ def permdisp_host(mass, first, branch_length, labels, permutations: int = 999, s
     s, n = mass.shape
     labels = _labels(labels, s)
     out = _permdisp_buffers(labels.shape[1], s, permutations, pairwise, with_stat)
-    capi.check(lib.epik_amd_cohort_permdisp_metric_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data,
-                                                        metric_id(metric), labels.ctypes.data, labels.shape[1], int(permutations),
-                                                        int(seed), int(bool(pairwise)), out.records.ctypes.data,
-                                                        out.stat.ctypes.data if with_stat else None, out.group_mean.ctypes.data,
-                                                        out.z.ctypes.data))
+    _call(lib, "permdisp_metric_host", strata, s, mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data,
+          metric_id(metric), labels.ctypes.data, labels.shape[1], int(permutations),
+          int(seed), int(bool(pairwise)), out.records.ctypes.data,
+          out.stat.ctypes.data if with_stat else None, out.group_mean.ctypes.data,
+          out.z.ctypes.data)
     return out
 
 
@@ -537,7 +570,8 @@ def _model_buffers(t: int, permutations: int, with_stat: bool):
     return records, info, stat, np.zeros(capi.MODEL_MAX_COLUMNS, dtype=np.uint8)
 
 
-def model_kr_host(kr, totals, kind, labels, values, permutations: int = 999, seed: int = 1, with_stat: bool = True) -> Model:
+def model_kr_host(kr, totals, kind, labels, values, permutations: int = 999, seed: int = 1, with_stat: bool = True,
+                  strata=None) -> Model:
     """The sequential model of the rule from a distance matrix kr[S][S] and totals[S] (T_s) on the host
     (`epik_amd_cohort_model_kr_host`)."""
     lib = capi.load()
@@ -550,14 +584,14 @@ def model_kr_host(kr, totals, kind, labels, values, permutations: int = 999, see
         raise ValueError("one total mass per sample")
     kind, labels, values = _design(kind, labels, values, s)
     records, info, stat, aliased = _model_buffers(kind.shape[0], permutations, with_stat)
-    capi.check(lib.epik_amd_cohort_model_kr_host(kr.ctypes.data, totals.ctypes.data, s, kind.ctypes.data, labels.ctypes.data,
-                                                 values.ctypes.data, kind.shape[0], int(permutations), int(seed), records.ctypes.data,
-                                                 info.ctypes.data, stat.ctypes.data if with_stat else None, aliased.ctypes.data))
+    _call(lib, "model_kr_host", strata, s, kr.ctypes.data, totals.ctypes.data, s, kind.ctypes.data, labels.ctypes.data,
+          values.ctypes.data, kind.shape[0], int(permutations), int(seed), records.ctypes.data,
+          info.ctypes.data, stat.ctypes.data if with_stat else None, aliased.ctypes.data)
     return Model(records, info[0], stat, aliased)
 
 
 def model_host(mass, first, branch_length, kind, labels, values, permutations: int = 999, seed: int = 1, with_stat: bool = True,
-               metric="kr") -> Model:
+               metric="kr", strata=None) -> Model:
     """The sequential model of the rule for mass[S][N] and the design kind[T], labels[S][T] (0xffffffff: missing) and
     values[S][T] (NaN: missing) over the distance `metric` on the host (`epik_amd_cohort_model_metric_host`)."""
     lib = capi.load()
@@ -565,10 +599,10 @@ def model_host(mass, first, branch_length, kind, labels, values, permutations: i
     s, n = mass.shape
     kind, labels, values = _design(kind, labels, values, s)
     records, info, stat, aliased = _model_buffers(kind.shape[0], permutations, with_stat)
-    capi.check(lib.epik_amd_cohort_model_metric_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, metric_id(metric),
-                                                     kind.ctypes.data, labels.ctypes.data, values.ctypes.data, kind.shape[0],
-                                                     int(permutations), int(seed), records.ctypes.data, info.ctypes.data,
-                                                     stat.ctypes.data if with_stat else None, aliased.ctypes.data))
+    _call(lib, "model_metric_host", strata, s, mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, metric_id(metric),
+          kind.ctypes.data, labels.ctypes.data, values.ctypes.data, kind.shape[0],
+          int(permutations), int(seed), records.ctypes.data, info.ctypes.data,
+          stat.ctypes.data if with_stat else None, aliased.ctypes.data)
     return Model(records, info[0], stat, aliased)
 
 
@@ -589,7 +623,7 @@ def _edgetest_buffers(m: int, n: int, permutations: int, with_stat: bool, with_m
 
 
 def edgetest_host(mass, first, labels, permutations: int = 999, seed: int = 1, with_stat: bool = True,
-                  with_max: bool = True) -> Edgetest:
+                  with_max: bool = True, strata=None) -> Edgetest:
     """The edge test of the rule for mass[S][N] and labels[S][M] (0xffffffff: missing) on the host, one thread
     (`epik_amd_cohort_edgetest_host`)."""
     lib = capi.load()
@@ -597,9 +631,9 @@ def edgetest_host(mass, first, labels, permutations: int = 999, seed: int = 1, w
     s, n = mass.shape
     labels = _labels(labels, s)
     records, stat, most = _edgetest_buffers(labels.shape[1], n, permutations, with_stat, with_max)
-    capi.check(lib.epik_amd_cohort_edgetest_host(mass.ctypes.data, s, n, first.ctypes.data, labels.ctypes.data, labels.shape[1],
-                                                 int(permutations), int(seed), records.ctypes.data,
-                                                 stat.ctypes.data if with_stat else None, most.ctypes.data if with_max else None))
+    _call(lib, "edgetest_host", strata, s, mass.ctypes.data, s, n, first.ctypes.data, labels.ctypes.data, labels.shape[1],
+          int(permutations), int(seed), records.ctypes.data,
+          stat.ctypes.data if with_stat else None, most.ctypes.data if with_max else None)
     return Edgetest(records, stat, most)
 
 
@@ -861,52 +895,53 @@ class Cohort:
         return out
 
     def permanova_device(self, d_kr: int, labels, permutations: int, seed: int, pairwise: bool, d_out: int, d_ssw: int = 0,
-                         d_group_ss: int = 0, stream: int = 0) -> None:
+                         d_group_ss: int = 0, stream: int = 0, strata=None) -> None:
         """PERMANOVA of labels[S][M] (host; 0xffffffff: missing) over d_kr, float64 [S][S] in device memory as `kr_device`
         wrote it, into d_out, `capi.PERMANOVA` [M][1 + Q], and where given d_ssw, float64 [M][1 + Q][P + 1], and
         d_group_ss, float64 [M][256], every cell written; asynchronous on `stream` once the labels are copied, no readback
         (`epik_amd_cohort_permanova_device`)."""
         labels = _labels(labels, self.num_samples)
-        capi.check(self._lib.epik_amd_cohort_permanova_device(self._handle, d_kr or None, labels.ctypes.data, labels.shape[1],
-                                                              int(permutations), int(seed), int(bool(pairwise)), d_out or None,
-                                                              d_ssw or None, d_group_ss or None, stream or None))
+        _call(self._lib, "permanova_device", strata, self.num_samples, self._handle, d_kr or None, labels.ctypes.data, labels.shape[1],
+              int(permutations), int(seed), int(bool(pairwise)), d_out or None,
+              d_ssw or None, d_group_ss or None, stream or None)
 
     def permanova(self, tree, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
-                  with_ssw: bool = False, metric="kr") -> Permanova:
+                  with_ssw: bool = False, metric="kr", strata=None) -> Permanova:
         """PERMANOVA of the samples' groups in every column of labels[S][M] over their distances `metric`, KR by default
-        (`epik_amd_cohort_permanova_metric`)."""
+        (`epik_amd_cohort_permanova_metric`).  `strata`, one id per sample: the shuffles stay within the strata
+        (`epik_amd_cohort_permanova_strata`); likewise for `permdisp`, `edgetest`, `model` and the `_device` forms."""
         length = self._lengths(tree, branch_length)
         labels = _labels(labels, self.num_samples)
         records, ssw, group_ss = _permanova_buffers(labels.shape[1], permutations, pairwise, with_ssw)
-        capi.check(self._lib.epik_amd_cohort_permanova_metric(self._handle, tree._handle, length.ctypes.data, metric_id(metric),
-                                                              labels.ctypes.data, labels.shape[1], int(permutations), int(seed),
-                                                              int(bool(pairwise)), records.ctypes.data,
-                                                              ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data))
+        _call(self._lib, "permanova_metric", strata, self.num_samples, self._handle, tree._handle, length.ctypes.data,
+              metric_id(metric), labels.ctypes.data, labels.shape[1], int(permutations), int(seed),
+              int(bool(pairwise)), records.ctypes.data,
+              ssw.ctypes.data if with_ssw else None, group_ss.ctypes.data)
         return Permanova(records, ssw, group_ss)
 
     def permdisp_device(self, d_kr: int, labels, permutations: int, seed: int, pairwise: bool, d_out: int, d_group_mean: int,
-                        d_z: int, d_stat: int = 0, stream: int = 0) -> None:
+                        d_z: int, d_stat: int = 0, stream: int = 0, strata=None) -> None:
         """PERMDISP of labels[S][M] (host; 0xffffffff: missing) over d_kr, float64 [S][S] in device memory as `kr_device`
         wrote it, into d_out, `capi.PERMDISP` [M][1 + Q], d_group_mean, float64 [M][32], d_z, float64 [M][S], and where given
         d_stat, float64 [M][1 + Q][P + 1], every cell written; asynchronous on `stream` once the labels are copied, no
         readback (`epik_amd_cohort_permdisp_device`)."""
         labels = _labels(labels, self.num_samples)
-        capi.check(self._lib.epik_amd_cohort_permdisp_device(self._handle, d_kr or None, labels.ctypes.data, labels.shape[1],
-                                                             int(permutations), int(seed), int(bool(pairwise)), d_out or None,
-                                                             d_stat or None, d_group_mean or None, d_z or None, stream or None))
+        _call(self._lib, "permdisp_device", strata, self.num_samples, self._handle, d_kr or None, labels.ctypes.data, labels.shape[1],
+              int(permutations), int(seed), int(bool(pairwise)), d_out or None,
+              d_stat or None, d_group_mean or None, d_z or None, stream or None)
 
     def permdisp(self, tree, branch_length, labels, permutations: int = 999, seed: int = 1, pairwise: bool = False,
-                 with_stat: bool = False, metric="kr") -> Permdisp:
+                 with_stat: bool = False, metric="kr", strata=None) -> Permdisp:
         """PERMDISP of the samples' groups in every column of labels[S][M]: do they differ in their distances to the group
         centroids over the distances `metric`, KR by default (`epik_amd_cohort_permdisp_metric`)."""
         length = self._lengths(tree, branch_length)
         labels = _labels(labels, self.num_samples)
         out = _permdisp_buffers(labels.shape[1], self.num_samples, permutations, pairwise, with_stat)
-        capi.check(self._lib.epik_amd_cohort_permdisp_metric(self._handle, tree._handle, length.ctypes.data, metric_id(metric),
-                                                             labels.ctypes.data, labels.shape[1], int(permutations), int(seed),
-                                                             int(bool(pairwise)), out.records.ctypes.data,
-                                                             out.stat.ctypes.data if with_stat else None, out.group_mean.ctypes.data,
-                                                             out.z.ctypes.data))
+        _call(self._lib, "permdisp_metric", strata, self.num_samples, self._handle, tree._handle, length.ctypes.data,
+              metric_id(metric), labels.ctypes.data, labels.shape[1], int(permutations), int(seed),
+              int(bool(pairwise)), out.records.ctypes.data,
+              out.stat.ctypes.data if with_stat else None, out.group_mean.ctypes.data,
+              out.z.ctypes.data)
         return out
 
     def pcoa_device(self, d_kr: int, num_components: int, d_mu: int, d_coord: int, d_info: int, stream: int = 0) -> None:
@@ -929,51 +964,51 @@ class Cohort:
         return out
 
     def edgetest_device(self, tree, labels, permutations: int, seed: int, d_out: int, d_stat: int = 0, d_max: int = 0,
-                        stream: int = 0) -> None:
+                        stream: int = 0, strata=None) -> None:
         """The edge test of labels[S][M] (host; 0xffffffff: missing) into d_out, `capi.EDGETEST` [M][N], and where given
         d_stat, float64 [M][4][N][P + 1], and d_max, float64 [M][4][P + 1], all in device memory, every cell written;
         asynchronous on `stream` once the labels are copied, no readback (`epik_amd_cohort_edgetest_device`)."""
         labels = _labels(labels, self.num_samples)
-        capi.check(self._lib.epik_amd_cohort_edgetest_device(self._handle, self._tree_handle(tree, "edgetest_device"),
-                                                             labels.ctypes.data, labels.shape[1], int(permutations), int(seed),
-                                                             d_out or None, d_stat or None, d_max or None, stream or None))
+        _call(self._lib, "edgetest_device", strata, self.num_samples, self._handle, self._tree_handle(tree, "edgetest_device"),
+              labels.ctypes.data, labels.shape[1], int(permutations), int(seed),
+              d_out or None, d_stat or None, d_max or None, stream or None)
 
     def edgetest(self, tree, labels, permutations: int = 999, seed: int = 1, with_stat: bool = False,
-                 with_max: bool = False) -> Edgetest:
+                 with_max: bool = False, strata=None) -> Edgetest:
         """Which branches differ between the groups of every column of labels[S][M]: per branch the one-way ANOVA and
         Kruskal-Wallis of its mass and imbalance by permutation, with the max-statistic adjustment
         (`epik_amd_cohort_edgetest`)."""
         labels = _labels(labels, self.num_samples)
         records, stat, most = _edgetest_buffers(labels.shape[1], self.num_branches, permutations, with_stat, with_max)
-        capi.check(self._lib.epik_amd_cohort_edgetest(self._handle, self._tree_handle(tree, "edgetest"), labels.ctypes.data,
-                                                      labels.shape[1], int(permutations), int(seed), records.ctypes.data,
-                                                      stat.ctypes.data if with_stat else None,
-                                                      most.ctypes.data if with_max else None))
+        _call(self._lib, "edgetest", strata, self.num_samples, self._handle, self._tree_handle(tree, "edgetest"), labels.ctypes.data,
+              labels.shape[1], int(permutations), int(seed), records.ctypes.data,
+              stat.ctypes.data if with_stat else None,
+              most.ctypes.data if with_max else None)
         return Edgetest(records, stat, most)
 
     def model_device(self, d_kr: int, kind, labels, values, permutations: int, seed: int, d_out: int, d_info: int, d_aliased: int,
-                     d_stat: int = 0, stream: int = 0) -> None:
+                     d_stat: int = 0, stream: int = 0, strata=None) -> None:
         """The sequential model of the design kind[T], labels[S][T] and values[S][T] (host) over d_kr, float64 [S][S] in
         device memory as `kr_device` wrote it, into d_out, `capi.MODEL_TERM` [T + 1], d_info, one `capi.MODEL_INFO`, d_aliased,
         64 bytes, and where given d_stat, float64 [T + 1][P + 1], every cell written; asynchronous on `stream` once the design
         is copied, no readback (`epik_amd_cohort_model_device`)."""
         kind, labels, values = _design(kind, labels, values, self.num_samples)
-        capi.check(self._lib.epik_amd_cohort_model_device(self._handle, d_kr or None, kind.ctypes.data, labels.ctypes.data,
-                                                          values.ctypes.data, kind.shape[0], int(permutations), int(seed),
-                                                          d_out or None, d_info or None, d_stat or None, d_aliased or None,
-                                                          stream or None))
+        _call(self._lib, "model_device", strata, self.num_samples, self._handle, d_kr or None, kind.ctypes.data, labels.ctypes.data,
+              values.ctypes.data, kind.shape[0], int(permutations), int(seed),
+              d_out or None, d_info or None, d_stat or None, d_aliased or None,
+              stream or None)
 
     def model(self, tree, branch_length, kind, labels, values, permutations: int = 999, seed: int = 1, with_stat: bool = False,
-              metric="kr") -> Model:
+              metric="kr", strata=None) -> Model:
         """The sequential model of the samples over their distances `metric`, KR by default: every term of the design tested
         after the terms before it (`epik_amd_cohort_model_metric`)."""
         length = self._lengths(tree, branch_length)
         kind, labels, values = _design(kind, labels, values, self.num_samples)
         records, info, stat, aliased = _model_buffers(kind.shape[0], permutations, with_stat)
-        capi.check(self._lib.epik_amd_cohort_model_metric(self._handle, tree._handle, length.ctypes.data, metric_id(metric),
-                                                          kind.ctypes.data, labels.ctypes.data, values.ctypes.data, kind.shape[0],
-                                                          int(permutations), int(seed), records.ctypes.data, info.ctypes.data,
-                                                          stat.ctypes.data if with_stat else None, aliased.ctypes.data))
+        _call(self._lib, "model_metric", strata, self.num_samples, self._handle, tree._handle, length.ctypes.data, metric_id(metric),
+              kind.ctypes.data, labels.ctypes.data, values.ctypes.data, kind.shape[0],
+              int(permutations), int(seed), records.ctypes.data, info.ctypes.data,
+              stat.ctypes.data if with_stat else None, aliased.ctypes.data)
         return Model(records, info[0], stat, aliased)
 
     def reset(self) -> None:
@@ -1021,6 +1056,7 @@ def _distance_field(distance) -> str:
 
 
 _DISTANCE_FIELD = r"(?:\tdistance=(unweighted|weighted|generalized))?"
+_STRATA_FIELD = r"(?:\tstrata=(?P<strata>[^\t]+))?"  # the last field of the first line of the four permutation tests' files
 
 
 def _live_mask(names, live) -> np.ndarray:
@@ -1513,6 +1549,8 @@ def _read_used_head(fh, what: str, pattern: str, path: str):
     if not head:
         raise ValueError(f"{path}: not a cohort {what} file")
     info = {"samples": int(head.group(1)), "used": int(head.group(2)), "unused": []}
+    if head.groupdict().get("strata"):
+        info["strata"] = head.group("strata")
     line = fh.readline().rstrip("\n")
     while line.startswith("# unused\t"):
         info["unused"].append(line.split("\t", 1)[1])
@@ -1638,6 +1676,48 @@ def read_factors(path: str, names, pairwise: bool = False, most: int | None = No
     return columns, labels, label_names, skipped
 
 
+def read_strata(path: str, names, column: str | None = None):
+    """The strata of --cohort-strata FILE [--cohort-strata-column NAME] for the samples `names` of the list: (uint32 strata [S],
+    the column's name).  FILE is read by `read_factors` (its errors) without a cap on the labels; `column` may be None only if
+    FILE has one column.  ValueError too for a column that FILE lacks and, naming the line, for a sample without a value."""
+    columns, labels, _, _ = read_factors(path, names, most=1 << 32)
+    if column is None:
+        if len(columns) != 1:
+            raise ValueError(f"{path} has {len(columns)} columns: --cohort-strata-column must name one")
+        c = 0
+    elif column in columns:
+        c = columns.index(column)
+    else:
+        raise ValueError(f"--cohort-strata-column: {path} has no column '{column}'")
+    for s in np.flatnonzero(labels[:, c] == capi.PERMANOVA_MISSING):
+        with open(path, newline="") as fh:
+            number = next(n for n, line in enumerate(fh, 1) if line[:1] != "#" and line.rstrip("\r\n").split("\t")[0] == names[s])
+        raise ValueError(f"{path} line {number}, column {columns[c]}: the sample '{names[s]}' has no stratum")
+    return np.ascontiguousarray(labels[:, c]), columns[c]
+
+
+def with_strata_field(text: str, strata) -> str:
+    """A cohort_permanova, _permdisp, _edgetest or _model file's text with <TAB>strata=NAME at the end of its first line (after
+    distance=.. where that is there): what --cohort-strata makes of the four files.  None or "" leaves the text as it is."""
+    if not strata:
+        return text
+    at = text.find("\n")
+    at = len(text) if at < 0 else at
+    return text[:at] + f"\tstrata={strata}" + text[at:]
+
+
+def constant_within_strata(column_labels, totals, strata, missing=0xFFFFFFFF) -> bool:
+    """Whether a column's labels are constant inside every stratum among the samples with mass and a label: nothing can be
+    permuted there, and the drivers warn."""
+    seen = {}
+    for v, t, h in zip(column_labels, totals, strata):
+        if int(t) == 0 or int(v) == missing:
+            continue
+        if seen.setdefault(int(h), int(v)) != int(v):
+            return False
+    return True
+
+
 PERMANOVA_HEADER = "column\ta\tb\tused\tgroups\tss_total\tss_among\tss_within\tf\tr2\tat_most\tp"
 
 
@@ -1660,11 +1740,12 @@ def groups_of(labels, totals):
 
 
 def format_permanova_tsv(names, totals, columns, label_names, labels, permutations: int, seed: int, pairwise: bool, records,
-                         group_ss, distance="kr") -> str:
+                         group_ss, distance="kr", strata=None) -> str:
     """cohort_permanova_<list>.tsv: the first line, a `# unused` line per sample without mass, a `# column` line per column
     (its used samples and groups), a `# group` line per group (label, size, W_g / n_g of the observed labelling), the column
     names, then per column the whole test (a = b = *) and, with pairwise, its pairs in slot order; ss_among is
-    ss_total - ss_within; doubles as %.17g, NA as NA."""
+    ss_total - ss_within; doubles as %.17g, NA as NA.  `strata`: the name of the column of --cohort-strata, <TAB>strata=NAME at the
+    end of the first line."""
     records, labels = np.asarray(records), np.asarray(labels)
     slots = 1 + (capi.PERMANOVA_PAIR_SLOTS if pairwise else 0)
     if records.dtype != capi.PERMANOVA or records.shape != (len(columns), slots) or labels.shape != (len(names), len(columns)):
@@ -1690,19 +1771,20 @@ def format_permanova_tsv(names, totals, columns, label_names, labels, permutatio
             for h in range(1, len(order)):
                 for g in range(h):
                     lines.append(line(c, label_names[c][order[g]], label_names[c][order[h]], records[c, pair_slot(g, h)]))
-    return "\n".join(lines) + "\n"
+    return with_strata_field("\n".join(lines) + "\n", strata)
 
 
 PERMDISP_HEADER = "column\ta\tb\tused\tgroups\tclipped\teta2\tf\tat_least\tp"
 
 
 def format_permdisp_tsv(names, totals, columns, label_names, labels, permutations: int, seed: int, pairwise: bool, records,
-                        group_mean, z, distance="kr") -> str:
+                        group_mean, z, distance="kr", strata=None) -> str:
     """cohort_permdisp_<list>.tsv: the first line, the `# unused`, `# column` and `# group` lines as cohort_permanova's (a
     group's last field is its mean distance to centroid), the column names, per column the whole test (a = b = *) and, with
     pairwise, its pairs in slot order; then `# distances`, the column names column name label distance and, per column, a
     line per sample with mass and a label, in list order; doubles as %.17g, NA as NA.  Over a `distance` other than KR the
-    first line ends in <TAB>distance=NAME."""
+    first line ends in <TAB>distance=NAME.  `strata`: the name of the column of --cohort-strata, <TAB>strata=NAME at the
+    end of the first line."""
     records, labels = np.asarray(records), np.asarray(labels)
     slots = 1 + (capi.PERMDISP_PAIR_SLOTS if pairwise else 0)
     if records.dtype != capi.PERMDISP or records.shape != (len(columns), slots) or labels.shape != (len(names), len(columns)):
@@ -1732,7 +1814,7 @@ def format_permdisp_tsv(names, totals, columns, label_names, labels, permutation
             v = int(labels[s, c])
             if int(totals[s]) != 0 and v != capi.PERMDISP_MISSING:
                 lines.append(f"{column}\t{name}\t{label_names[c][v]}\t{_g17_or_na(z[c][s])}")
-    return "\n".join(lines) + "\n"
+    return with_strata_field("\n".join(lines) + "\n", strata)
 
 
 def read_permanova_tsv(path: str):
@@ -1741,7 +1823,7 @@ def read_permanova_tsv(path: str):
     name of `DISTANCES`, only where the first line has the field: a file over KR has none})"""
     with open(path, newline="") as fh:
         head, info, line = _read_used_head(fh, "permanova", r" columns=(\d+) permutations=(\d+) seed=(\d+) pairwise=([01])"
-                                           + _DISTANCE_FIELD, path)
+                                           + _DISTANCE_FIELD + _STRATA_FIELD, path)
         info.update(permutations=int(head.group(4)), seed=int(head.group(5)), pairwise=head.group(6) == "1", column_used=[],
                     column_groups=[])
         if head.group(7):                     # (a file over KR has no such field, and its info no such key)
@@ -1777,7 +1859,7 @@ def read_permdisp_tsv(path: str):
     name, label, distance)], info as `read_permanova_tsv`'s)"""
     with open(path, newline="") as fh:
         head, info, line = _read_used_head(fh, "permdisp", r" columns=(\d+) permutations=(\d+) seed=(\d+) pairwise=([01])"
-                                           + _DISTANCE_FIELD, path)
+                                           + _DISTANCE_FIELD + _STRATA_FIELD, path)
         info.update(permutations=int(head.group(4)), seed=int(head.group(5)), pairwise=head.group(6) == "1", column_used=[],
                     column_groups=[])
         if head.group(7):                     # (a file over KR has no such field, and its info no such key)
@@ -1819,11 +1901,12 @@ EDGETEST_HEADER = "edge_num\tcolumn" + "".join(f"\t{kind}_{field}" for kind in (
                                                for field in ("eta2", "f", "p", "p_adj", "top", "h", "kw_p", "kw_p_adj"))
 
 
-def format_edgetest_tsv(names, totals, columns, label_names, labels, permutations: int, seed: int, records) -> str:
+def format_edgetest_tsv(names, totals, columns, label_names, labels, permutations: int, seed: int, records, strata=None) -> str:
     """cohort_edgetest_<list>.tsv: the first line, a `# unused` line per sample without mass, a `# column` line per column
     (its used samples and groups), a `# group` line per group (label, size), the column names, then per column a line per
     branch with at least one defined family: eta2, F, p, p_adj, the label of the group with the largest mean, H and the
-    Kruskal-Wallis p and p_adj, of the mass and then of the imbalance; doubles as %.17g, NA as NA."""
+    Kruskal-Wallis p and p_adj, of the mass and then of the imbalance; doubles as %.17g, NA as NA.  `strata`: the name of the column of --cohort-strata, <TAB>strata=NAME at the
+    end of the first line."""
     records, labels = np.asarray(records), np.asarray(labels)
     if records.dtype != capi.EDGETEST or records.ndim != 2 or records.shape[0] != len(columns) or \
             labels.shape != (len(names), len(columns)):
@@ -1845,7 +1928,7 @@ def format_edgetest_tsv(names, totals, columns, label_names, labels, permutation
                            "NA" if top == capi.EDGETEST_MISSING else label_names[c][order[top]], _g17_or_na(ranks["stat"]),
                            _g17_or_na(ranks["p"]), _g17_or_na(ranks["p_adj"])]
             lines.append("\t".join(fields))
-    return "\n".join(lines) + "\n"
+    return with_strata_field("\n".join(lines) + "\n", strata)
 
 
 def read_edgetest_tsv(path: str):
@@ -1853,7 +1936,7 @@ def read_edgetest_tsv(path: str):
     `top` fields as labels (None for NA), groups [(c, g, label, n)], info {"samples", "used", "unused", "permutations",
     "seed", "column_used", "column_groups"})"""
     with open(path, newline="") as fh:
-        head, info, line = _read_used_head(fh, "edgetest", r" columns=(\d+) permutations=(\d+) seed=(\d+)", path)
+        head, info, line = _read_used_head(fh, "edgetest", r" columns=(\d+) permutations=(\d+) seed=(\d+)" + _STRATA_FIELD, path)
         info.update(permutations=int(head.group(4)), seed=int(head.group(5)), column_used=[], column_groups=[])
         columns, groups = [], []
         while line.startswith("# column\t"):
@@ -2004,12 +2087,13 @@ MODEL_HEADER = "term\tdf\tss\tr2\tf\tat_least\tp"
 
 
 def format_model_tsv(names, totals, terms, kind, label_names, labels, values, permutations: int, seed: int, model: Model,
-                     distance="kr") -> str:
+                     distance="kr", strata=None) -> str:
     """cohort_model_<list>.tsv: the first line (used = the complete cases with mass), a `# unused` line per sample without mass,
     a `# incomplete` line per sample with mass that lacks a value (with the first term it lacks), a `# term` line per term, a
     `# group` line per group of a factor term in the rule's order, a `# aliased` line per dropped column, the column names, a
     line per term, then `model`, `residual` (df_res, ss_res, 1 less every term's r2 in one chain) and `total`; doubles as
-    %.17g, NA as NA."""
+    %.17g, NA as NA.  `strata`: the name of the column of --cohort-strata, <TAB>strata=NAME at the
+    end of the first line."""
     kind, labels, values = np.asarray(kind), np.asarray(labels), np.asarray(values, dtype=np.float64)
     totals = [int(x) for x in totals]
     t_count, info, records = len(terms), model.info, model.records
@@ -2056,7 +2140,7 @@ def format_model_tsv(names, totals, terms, kind, label_names, labels, values, pe
     total = float(info["ss_total"]) > 0.0
     lines.append(f"residual\t{int(info['df_res'])}\t{_g17_or_na(info['ss_res'])}\t{_g17_or_na(rest) if total else 'NA'}\tNA\tNA\tNA")
     lines.append(f"total\t{int(info['used']) - 1}\t{_g17_or_na(info['ss_total'])}\t{'1' if total else 'NA'}\tNA\tNA\tNA")
-    return "\n".join(lines) + "\n"
+    return with_strata_field("\n".join(lines) + "\n", strata)
 
 
 def read_model_tsv(path: str):
@@ -2066,13 +2150,15 @@ def read_model_tsv(path: str):
     with open(path, newline="") as fh:
         first = fh.readline().rstrip("\n")
         head = re.fullmatch(r"# epik_amd model v1  samples=(\d+) used=(\d+) terms=(\d+) columns=(\d+) rank=(\d+) permutations=(\d+) "
-                            r"seed=(\d+)" + _DISTANCE_FIELD, first)
+                            r"seed=(\d+)" + _DISTANCE_FIELD + _STRATA_FIELD, first)
         if not head:
             raise ValueError(f"{path}: not a cohort model file")
         info = dict(samples=int(head.group(1)), used=int(head.group(2)), columns=int(head.group(4)), rank=int(head.group(5)),
                     permutations=int(head.group(6)), seed=int(head.group(7)), unused=[], incomplete=[], groups=[], aliased=[])
         if head.group(8):
             info["distance"] = head.group(8)
+        if head.group("strata"):
+            info["strata"] = head.group("strata")
         terms, rows = [], []
         line = fh.readline().rstrip("\n")
         while line.startswith("# "):

@@ -1,8 +1,8 @@
 // cohort_device.hpp -- what the cohort analyses share of a device cohort.  For the host: the object itself with its workspace
 // slots, and the enqueue calls that one analysis offers the others (the normalise and distance kernels, the mass plane, the
 // index of the used samples).  For the kernels (under __HIPCC__): NA, the Gower centring of a distance matrix, a branch's
-// vectors and midranks, the permutation key and rank, and a column's list and groups.  The host code around the kernels is
-// in cohort_entry.hpp.
+// vectors and midranks, the permutation key and rank, the strata rule's tables and arrangement, and a column's list and
+// groups.  The host code around the kernels is in cohort_entry.hpp.
 #ifndef EPIK_AMD_COHORT_DEVICE_HPP
 #define EPIK_AMD_COHORT_DEVICE_HPP
 
@@ -274,6 +274,56 @@ __device__ inline uint32_t permutation_rank(uint64_t seed, uint32_t p, uint32_t 
         }
     }
     return rank;
+}
+
+// The strata rule's tables of one list of n positions, which do not depend on p.  A workgroup of any size, every lane calling
+// it (it has barriers; n is uniform): hs[i] = the stratum of position i, from the strata by sample and sample_of(i), and
+// home[], the positions by (stratum, position): home[base_i + index rank of i in its stratum] = i, base_i the positions in
+// strata with a smaller id.  hs and home are the list's, in global memory or LDS.
+template <class SampleOf>
+__device__ inline void strata_tables(const uint32_t *__restrict__ strata, SampleOf sample_of, uint32_t n, uint32_t *hs, uint32_t *home)
+{
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) hs[i] = strata[sample_of(i)];
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+        const uint32_t mine = hs[i];
+        uint32_t slot = 0;
+#pragma unroll 4
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t other = hs[j];  // a broadcast
+            slot += other < mine || (other == mine && j < i);
+        }
+        home[slot] = i;  // (a bijection: slot < n)
+    }
+    __syncthreads();
+}
+
+// whether (stratum, key, position) of j comes before that of i: what places i among the positions of its own stratum, behind
+// every stratum with a smaller id.  Only equality of strata decides sigma_p: home[] is in the same order of the ids.
+__device__ inline bool strata_before(uint32_t hj, uint64_t kj, uint32_t j, uint32_t hi, uint64_t ki, uint32_t i)
+{
+    return hj < hi || (hj == hi && (kj < ki || (kj == ki && j < i)));
+}
+
+// permutation_rank's stratified sibling, called the same way: sigma_p(i) = home[base_i + w_p(i)] of the strata rule, with hs and
+// home from strata_tables.  The tile carries the strata beside the keys (htile[kCohortKeyTile], LDS), and the count runs on
+// over the tiles, so a stratum may straddle them.  Permutation 0 is the identity.
+__device__ inline uint32_t permutation_arrangement(uint64_t seed, uint32_t p, uint32_t i, uint32_t L, uint64_t *tile, uint32_t *htile,
+                                                   const uint32_t *__restrict__ hs, const uint32_t *__restrict__ home)
+{
+    if (p == 0) return i;  // (uniform)
+    const uint64_t mine = permutation_key(seed, p, i);
+    const uint32_t stratum = i < L ? hs[i] : 0;
+    uint32_t slot = 0;
+    for (uint32_t j0 = 0; j0 < L; j0 += kCohortKeyTile) {
+        const uint32_t nt = min(kCohortKeyTile, L - j0);
+        __syncthreads();  // (the tile is written again)
+        for (uint32_t j = threadIdx.x; j < nt; j += kBlock) tile[j] = permutation_key(seed, p, j0 + j), htile[j] = hs[j0 + j];
+        __syncthreads();
+#pragma unroll 4
+        for (uint32_t j = 0; j < nt; ++j) slot += strata_before(htile[j], tile[j], j0 + j, stratum, mine, i);  // broadcasts
+    }
+    return i < L ? home[slot] : 0;  // (slot < L)
 }
 
 // the lanes of a wave whose `flag` is set append (sample, group) to the list in the order of the lanes; returns how many did

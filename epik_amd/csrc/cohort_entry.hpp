@@ -161,6 +161,15 @@ inline int upload_labels_by_column(const uint32_t *labels, uint32_t S, uint32_t 
     return EPIK_AMD_OK;
 }
 
+// strata[S] (host; any uint32 is an id) into d_strata[padded] on the device, the padding 0: the strata rule's input by sample
+inline int upload_strata(const uint32_t *strata, uint32_t S, uint32_t padded, uint32_t *d_strata)
+{
+    std::vector<uint32_t> h(padded, 0);
+    std::copy(strata, strata + S, h.begin());
+    HIP_TRY(hipMemcpy(d_strata, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return EPIK_AMD_OK;
+}
+
 // the most distinct labels (each below 32, or `missing`) of a column of labels[S][M]: a bound of the column's G; *distinct: of
 // every column
 inline uint32_t most_distinct_labels(const uint32_t *labels, uint32_t S, uint32_t M, uint32_t missing,

@@ -32,6 +32,8 @@
 //                               one vector atomic add a wave; the maximum over a workgroup's branches in a register, then a
 //                               vector atomic max on the bit patterns.
 //   edgetest_finish_kernel      max_at_least, p and p_adj of every defined family; NA into stat where undefined; max.
+//   edgetest_strata_kernel      with strata only (the strata rule): the tables of every column's list, once a
+//                               call; edgetest_labellings_kernel<true> then takes sigma_p (permutation_arrangement) for the rank.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -80,9 +82,11 @@ struct EdgeSpace {
     uint32_t *active;  // [N] the branches to permute, then their number, then the defined branches of the four families
     EdgeColumn *cols;  // [M]
     uint8_t *lam;      // [M][Sp]: the groups of the positions
+    uint32_t *strata;  // with strata only: [Sp], the strata by sample
+    uint32_t *hs, *home;  // ... and [M][Sp]: the strata of the positions, and the positions by (stratum, position)
 };
 
-size_t edgetest_space(void *base, uint32_t N, uint32_t padded, uint32_t M, uint32_t P, EdgeSpace *sp)
+size_t edgetest_space(void *base, uint32_t N, uint32_t padded, uint32_t M, uint32_t P, bool strata, EdgeSpace *sp)
 {
     Carver c(base);
     const EdgeSpace parts{.D = c.take<double>((size_t)N * kFamilies * padded),
@@ -95,7 +99,10 @@ size_t edgetest_space(void *base, uint32_t N, uint32_t padded, uint32_t M, uint3
                           .defined = c.take<uint32_t>(N),
                           .active = c.take<uint32_t>((size_t)N + 1 + kFamilies),
                           .cols = c.take<EdgeColumn>(M),
-                          .lam = c.take<uint8_t>((size_t)M * padded)};
+                          .lam = c.take<uint8_t>((size_t)M * padded),
+                          .strata = c.take<uint32_t>(strata ? padded : 0),
+                          .hs = c.take<uint32_t>(strata ? (size_t)M * padded : 0),
+                          .home = c.take<uint32_t>(strata ? (size_t)M * padded : 0)};
     if (sp) *sp = parts;
     return c.bytes();
 }
@@ -208,6 +215,17 @@ __global__ __launch_bounds__(kBlock) void edgetest_observed_kernel(const EdgeArg
     }
 }
 
+// the strata rule's tables of every column's list: a workgroup a column
+__global__ __launch_bounds__(kBlock) void edgetest_strata_kernel(const EdgeSpace sp, uint32_t num_columns, uint32_t padded)
+{
+    for (uint32_t c = blockIdx.x; c < num_columns; c += gridDim.x) {  // (uniform)
+        const uint64_t at = (uint64_t)c * padded;
+        const uint32_t *idx = sp.idx + at;
+        strata_tables(sp.strata, [&](uint32_t i) { return idx[i]; }, sp.cols[c].used, sp.hs + at, sp.home + at);
+    }
+}
+
+template <bool kStrata>
 __global__ __launch_bounds__(kBlock) void edgetest_labellings_kernel(const EdgeArgs a)
 {
     __shared__ uint64_t tile[kKeyTile];
@@ -220,7 +238,13 @@ __global__ __launch_bounds__(kBlock) void edgetest_labellings_kernel(const EdgeA
         const uint32_t p = a.p0 + k;
         for (uint32_t base = 0; base < L; base += kBlock) {
             const uint32_t i = base + tid;
-            const uint32_t rank = permutation_rank(a.seed, p, i, L, tile);  // (permutation 0 is the identity)
+            uint32_t rank;  // (permutation 0 is the identity)
+            if constexpr (kStrata) {
+                __shared__ uint32_t htile[kKeyTile];
+                rank = permutation_arrangement(a.seed, p, i, L, tile, htile, a.sp.hs + (uint64_t)c * a.padded, a.sp.home + (uint64_t)c * a.padded);
+            } else {
+                rank = permutation_rank(a.seed, p, i, L, tile);
+            }
             if (i < L) mu8[((uint64_t)(i / 4) * kChunk + k) * 4 + i % 4] = lam[rank];  // (rank < L)
         }
     }
@@ -388,8 +412,8 @@ int check_arguments(const uint32_t *labels, uint32_t S, uint32_t M, uint32_t P)
     return rule_result(edgetest_arguments_valid(labels, S, M, P, err), err);
 }
 
-int edgetest_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels, uint32_t M, uint32_t P,
-                         uint64_t seed, void *d_out, void *d_stat, void *d_max, hipStream_t stream)
+int edgetest_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels, const uint32_t *strata, uint32_t M,
+                         uint32_t P, uint64_t seed, void *d_out, void *d_stat, void *d_max, hipStream_t stream)
 {
     COHORT_TRY(check_cohort(cohort));
     COHORT_TRY(check_columns(M));
@@ -402,12 +426,14 @@ int edgetest_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, con
     const double *d_X = nullptr;
     // (the checks of the tree; the device drained of every call before: nothing reads the workspace)
     COHORT_TRY(cohort_mass_plane_enqueue(cohort, tree, stream, &d_first, &d_X));
-    COHORT_TRY(cohort_space_ensure(cohort, kSpaceEdgetest, edgetest_space(nullptr, N, padded, M, P, nullptr)));
+    COHORT_TRY(cohort_space_ensure(cohort, kSpaceEdgetest, edgetest_space(nullptr, N, padded, M, P, strata != nullptr, nullptr)));
     EdgeSpace sp;
-    edgetest_space(cohort->space[kSpaceEdgetest].d, N, padded, M, P, &sp);
+    edgetest_space(cohort->space[kSpaceEdgetest].d, N, padded, M, P, strata != nullptr, &sp);
     COHORT_TRY(upload_labels_by_column(labels, S, M, padded, kMissing, sp.lab));
+    if (strata) COHORT_TRY(upload_strata(strata, S, padded, sp.strata));
     hipLaunchKernelGGL(edgetest_columns_kernel, cohort_grid(cohort, M, kColumns), dim3(kWave), 0, stream, cohort->d_total, sp.lab, S, padded, M,
                        sp.idx, sp.lam, sp.cols);
+    if (strata) hipLaunchKernelGGL(edgetest_strata_kernel, cohort_grid(cohort, M, kColumns), dim3(kBlock), 0, stream, sp, M, padded);
     const bool lds = lds_switch("EPIK_AMD_EDGETEST_LDS", S, kLdsPositions);  // (=0, tests: the general path whatever S)
     const uint32_t lanes = most_groups <= kRegisterGroups ? kBlock : kLdsLanes;
     const size_t dynamic = (lds ? (size_t)2 * padded * 8 : 0) + (most_groups <= kRegisterGroups ? 0 : (size_t)most_groups * lanes * 8);
@@ -424,7 +450,9 @@ int edgetest_device_impl(epik_amd_cohort *cohort, const epik_amd_tree *tree, con
             hipLaunchKernelGGL((edgetest_observed_kernel<false>), cohort_grid(cohort, N, kGeneralBlocks), dim3(kBlock), 0, stream, args);
         for (uint64_t p0 = 0; p0 < row; p0 += kChunk) {
             args.p0 = (uint32_t)p0, args.np = (uint32_t)std::min<uint64_t>(kChunk, row - p0);
-            hipLaunchKernelGGL(edgetest_labellings_kernel, cohort_grid(cohort, args.np, kManyBlocks), dim3(kBlock), 0, stream, args);
+            const dim3 labellings = cohort_grid(cohort, args.np, kManyBlocks);
+            if (strata) hipLaunchKernelGGL(edgetest_labellings_kernel<true>, labellings, dim3(kBlock), 0, stream, args);
+            else hipLaunchKernelGGL(edgetest_labellings_kernel<false>, labellings, dim3(kBlock), 0, stream, args);
             const uint64_t subs = (args.np + lanes - 1) / lanes;
             const dim3 grid = cohort_grid(cohort, (uint64_t)N * subs, kManyBlocks);
             if (most_groups <= 2)
@@ -448,14 +476,29 @@ extern "C" {
 int epik_amd_cohort_edgetest_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels, uint32_t num_columns,
                                     uint32_t num_permutations, uint64_t seed, void *d_out, void *d_stat, void *d_max, void *stream)
 {
+    return epik_amd_cohort_edgetest_strata_device(cohort, tree, labels, num_columns, num_permutations, seed, d_out, d_stat, d_max, stream,
+                                                  nullptr);
+}
+
+int epik_amd_cohort_edgetest_strata_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels,
+                                           uint32_t num_columns, uint32_t num_permutations, uint64_t seed, void *d_out, void *d_stat,
+                                           void *d_max, void *stream, const uint32_t *strata)
+{
     return guarded("cohort_edgetest_device", [&]() -> int {
-        return edgetest_device_impl(cohort, tree, labels, num_columns, num_permutations, seed, d_out, d_stat, d_max,
+        return edgetest_device_impl(cohort, tree, labels, strata, num_columns, num_permutations, seed, d_out, d_stat, d_max,
                                     static_cast<hipStream_t>(stream));
     });
 }
 
 int epik_amd_cohort_edgetest(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels, uint32_t num_columns,
                              uint32_t num_permutations, uint64_t seed, epik_amd_edgetest *out, double *stat, double *max)
+{
+    return epik_amd_cohort_edgetest_strata(cohort, tree, labels, num_columns, num_permutations, seed, out, stat, max, nullptr);
+}
+
+int epik_amd_cohort_edgetest_strata(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels, uint32_t num_columns,
+                                    uint32_t num_permutations, uint64_t seed, epik_amd_edgetest *out, double *stat, double *max,
+                                    const uint32_t *strata)
 {
     return guarded("cohort_edgetest", [&]() -> int {
         COHORT_TRY(check_cohort(cohort));
@@ -471,7 +514,7 @@ int epik_amd_cohort_edgetest(epik_amd_cohort *cohort, const epik_amd_tree *tree,
         COHORT_TRY(r.alloc(out_bytes));
         COHORT_TRY(s.alloc(stat_bytes, stat != nullptr));
         COHORT_TRY(m.alloc(max_bytes, max != nullptr));
-        COHORT_TRY(edgetest_device_impl(cohort, tree, labels, num_columns, num_permutations, seed, r.d, s.d, m.d, nullptr));
+        COHORT_TRY(edgetest_device_impl(cohort, tree, labels, strata, num_columns, num_permutations, seed, r.d, s.d, m.d, nullptr));
         COHORT_TRY(r.copy_to(out, out_bytes));
         COHORT_TRY(s.copy_to(stat, stat_bytes));
         return m.copy_to(max, max_bytes);
@@ -482,12 +525,20 @@ int epik_amd_cohort_edgetest_host(const uint64_t *mass, uint32_t num_samples, ui
                                   const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
                                   epik_amd_edgetest *out, double *stat, double *max)
 {
+    return epik_amd_cohort_edgetest_strata_host(mass, num_samples, num_branches, first, labels, num_columns, num_permutations, seed, out,
+                                                stat, max, nullptr);
+}
+
+int epik_amd_cohort_edgetest_strata_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                         const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
+                                         epik_amd_edgetest *out, double *stat, double *max, const uint32_t *strata)
+{
     return guarded("cohort_edgetest_host", [&]() -> int {
         COHORT_TRY(check_host_shape(num_samples, num_branches));
         COHORT_TRY(check_present(mass, first, labels, out));
         std::string err;
         return rule_result(edgetest_records(mass, num_samples, num_branches, first, labels, num_columns, num_permutations, seed, out, stat,
-                                            max, err),
+                                            max, err, strata),
                            err);
     });
 }

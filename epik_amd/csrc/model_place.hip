@@ -29,6 +29,8 @@
 //                        permutation_rank of cohort_device.hpp.  Launched twice: the identity alone, which writes the records,
 //                        the info block and F_0; then the permutations 1 .. P.
 //   model_finish_kernel  p = (1 + at_least) / (P + 1), and NA into the rows of stat whose test is undefined.
+//   model_strata_kernel  with strata only (the strata rule): the tables of the list of the complete cases; the
+//                        permutations' model_ss_kernel<.., kStrata = true> then takes sigma_p from permutation_arrangement.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -83,11 +85,13 @@ struct ModelSpace {
     uint32_t *lab;    // [T][Sp]: the labels by sample, `missing` for a sample that is no complete case
     uint32_t *idx;    // [T][Sp]: the samples of the positions (every term's list is the same)
     uint8_t *lam;     // [T][Sp]: the groups of the positions
+    uint32_t *strata;  // with strata only: [Sp], the strata by sample
+    uint32_t *hs, *home;  // ... and [Sp]: the strata of the positions, and the positions by (stratum, position)
 };
 
 constexpr size_t kSliceBytes = kPerms * kChunk * 8 + kPerms * 4;  // the bytes of a slice per padded sample
 
-size_t model_space(void *base, uint32_t S, uint32_t padded, uint32_t T, uint32_t slices, ModelSpace *sp)
+size_t model_space(void *base, uint32_t S, uint32_t padded, uint32_t T, uint32_t slices, bool strata, ModelSpace *sp)
 {
     Carver c(base);
     const ModelSpace parts{.B = c.take<double>((size_t)S * S),
@@ -99,7 +103,10 @@ size_t model_space(void *base, uint32_t S, uint32_t padded, uint32_t T, uint32_t
                            .meta = c.take<ModelMeta>(1),
                            .lab = c.take<uint32_t>((size_t)T * padded),
                            .idx = c.take<uint32_t>((size_t)T * padded),
-                           .lam = c.take<uint8_t>((size_t)T * padded)};
+                           .lam = c.take<uint8_t>((size_t)T * padded),
+                           .strata = c.take<uint32_t>(strata ? padded : 0),
+                           .hs = c.take<uint32_t>(strata ? padded : 0),
+                           .home = c.take<uint32_t>(strata ? padded : 0)};
     if (sp) *sp = parts;
     return c.bytes();
 }
@@ -233,7 +240,15 @@ struct SsArgs {
     double *stat;  // or null
     uint64_t seed;
     uint32_t num_terms, num_permutations, pitch;
+    const uint32_t *hs, *home;  // the strata rule's tables, or null
 };
+
+// the strata rule's tables of the list of the complete cases: one workgroup
+__global__ __launch_bounds__(kBlock) void model_strata_kernel(const uint32_t *__restrict__ strata, const uint32_t *__restrict__ idx,
+                                                              const ModelMeta *__restrict__ meta, uint32_t *hs, uint32_t *home)
+{
+    if (blockIdx.x == 0) strata_tables(strata, [&](uint32_t i) { return idx[i]; }, meta->L, hs, home);
+}
 
 // F of a term from its sums: the rule's three divisions, +infinity where the residual is not > 0
 __device__ inline double f_of(double ss, uint32_t df, double res, int64_t df_res)
@@ -244,7 +259,7 @@ __device__ inline double f_of(double ss, uint32_t df, double res, int64_t df_res
 
 // kObserved: the identity alone, and the records; else the permutations 1 .. P, kPerms a unit.  kCols: the chains of a
 // permutation that a lane keeps at a time.
-template <bool kLds, bool kObserved, uint32_t kCols>
+template <bool kLds, bool kObserved, uint32_t kCols, bool kStrata>
 __global__ __launch_bounds__(kBlock) void model_ss_kernel(const SsArgs a)
 {
     extern __shared__ __align__(16) unsigned char dynamic_lds[];
@@ -272,7 +287,14 @@ __global__ __launch_bounds__(kBlock) void model_ss_kernel(const SsArgs a)
         for (uint32_t k = 0; k < kPerms; ++k) {
             const uint32_t p = k < np ? p0 + k : 0;  // (beyond np: filling, the identity)
             for (uint32_t base = 0; base < L; base += kBlock) {  // (every lane calls: it has barriers)
-                const uint32_t i = base + tid, rank = permutation_rank(a.seed, p, i, L, tile);
+                const uint32_t i = base + tid;
+                uint32_t rank;
+                if constexpr (kStrata && !kObserved) {
+                    __shared__ uint32_t htile[kCohortKeyTile];
+                    rank = permutation_arrangement(a.seed, p, i, L, tile, htile, a.hs, a.home);
+                } else {
+                    rank = permutation_rank(a.seed, p, i, L, tile);
+                }
                 if (i < L) sigma[k * pitch + i] = rank;
             }
         }
@@ -386,12 +408,15 @@ template <bool kLds, uint32_t kCols>
 void launch_ss(const epik_amd_cohort *cohort, const SsArgs &args, size_t dynamic, hipStream_t stream)
 {
     const uint64_t units = (args.num_permutations + kPerms - 1) / kPerms, most = kLds ? kManyBlocks : kGeneralBlocks;
-    hipLaunchKernelGGL((model_ss_kernel<kLds, true, kCols>), dim3(1), dim3(kBlock), dynamic, stream, args);
-    hipLaunchKernelGGL((model_ss_kernel<kLds, false, kCols>), cohort_grid(cohort, units, most), dim3(kBlock), dynamic, stream, args);
+    const dim3 grid = cohort_grid(cohort, units, most);
+    hipLaunchKernelGGL((model_ss_kernel<kLds, true, kCols, false>), dim3(1), dim3(kBlock), dynamic, stream, args);  // (the identity)
+    if (args.hs) hipLaunchKernelGGL((model_ss_kernel<kLds, false, kCols, true>), grid, dim3(kBlock), dynamic, stream, args);
+    else hipLaunchKernelGGL((model_ss_kernel<kLds, false, kCols, false>), grid, dim3(kBlock), dynamic, stream, args);
 }
 
 int model_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *kind, const uint32_t *labels, const double *values,
-                      uint32_t T, uint32_t P, uint64_t seed, void *d_out, void *d_info, void *d_stat, void *d_aliased, hipStream_t stream)
+                      const uint32_t *strata, uint32_t T, uint32_t P, uint64_t seed, void *d_out, void *d_info, void *d_stat,
+                      void *d_aliased, hipStream_t stream)
 {
     COHORT_TRY(check_cohort(cohort));
     COHORT_TRY(terms_valid(T));
@@ -404,9 +429,10 @@ int model_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t 
     const bool lds = lds_switch("EPIK_AMD_MODEL_LDS", S, kLdsPositions);  // (=0, tests: the general path whatever S)
     // the general path's workgroups, each with a slice: the grid that launch_ss makes of the permutations' units
     const uint32_t slices = lds ? 0 : cohort_grid(cohort, (P + kPerms - 1) / kPerms, kGeneralBlocks).x;
-    COHORT_TRY(cohort_space_ensure(cohort, kSpaceModel, model_space(nullptr, S, padded, T, slices, nullptr)));
+    COHORT_TRY(cohort_space_ensure(cohort, kSpaceModel, model_space(nullptr, S, padded, T, slices, strata != nullptr, nullptr)));
     ModelSpace sp;
-    model_space(cohort->space[kSpaceModel].d, S, padded, T, slices, &sp);
+    model_space(cohort->space[kSpaceModel].d, S, padded, T, slices, strata != nullptr, &sp);
+    if (strata) COHORT_TRY(upload_strata(strata, S, padded, sp.strata));
     // the design by term; a sample that lacks any value is missing in every term, so every term lists the complete cases
     std::vector<uint32_t> lab((size_t)T * padded, kMissing);
     std::vector<double> val((size_t)T * padded, 0.0);
@@ -437,6 +463,7 @@ int model_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t 
     const uint64_t cells = (uint64_t)S * S;
     hipLaunchKernelGGL(model_terms_kernel, cohort_grid(cohort, T, kTerms), dim3(kWave), 0, stream, cohort->d_total, sp.lab, S, padded, T, sp.idx,
                        sp.lam, sp.meta);
+    if (strata) hipLaunchKernelGGL(model_strata_kernel, dim3(1), dim3(kBlock), 0, stream, sp.strata, sp.idx, sp.meta, sp.hs, sp.home);
     hipLaunchKernelGGL(model_rows_kernel, cohort_grid(cohort, (S + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream, kr, sp.idx, S,
                        sp.meta, sp.r);
     hipLaunchKernelGGL(model_total_kernel, dim3(1), dim3(kWave), 0, stream, kr, sp.idx, S, sp.meta, sp.r);
@@ -446,7 +473,8 @@ int model_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t 
                        static_cast<uint8_t *>(d_aliased));
     const uint32_t pitch = lds ? kLdsPositions : padded;
     const SsArgs args{sp.B, sp.Q, sp.meta, sp.scratch, static_cast<epik_amd_model_term *>(d_out),
-                      static_cast<epik_amd_model_info *>(d_info), static_cast<double *>(d_stat), seed, T, P, pitch};
+                      static_cast<epik_amd_model_info *>(d_info), static_cast<double *>(d_stat), seed, T, P, pitch,
+                      strata ? sp.hs : nullptr, strata ? sp.home : nullptr};
     const size_t dynamic = lds ? kSliceBytes * pitch : 0;
     const bool small = bound <= kSmallColumns;
     if (lds && small) launch_ss<true, kSmallColumns>(cohort, args, dynamic, stream);
@@ -468,9 +496,17 @@ int epik_amd_cohort_model_device(epik_amd_cohort *cohort, const void *d_kr, cons
                                  const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed, void *d_out,
                                  void *d_info, void *d_stat, void *d_aliased, void *stream)
 {
+    return epik_amd_cohort_model_strata_device(cohort, d_kr, kind, labels, values, num_terms, num_permutations, seed, d_out, d_info, d_stat,
+                                               d_aliased, stream, nullptr);
+}
+
+int epik_amd_cohort_model_strata_device(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *kind, const uint32_t *labels,
+                                        const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed, void *d_out,
+                                        void *d_info, void *d_stat, void *d_aliased, void *stream, const uint32_t *strata)
+{
     return guarded("cohort_model_device", [&]() -> int {
-        return model_device_impl(cohort, d_kr, kind, labels, values, num_terms, num_permutations, seed, d_out, d_info, d_stat, d_aliased,
-                                 static_cast<hipStream_t>(stream));
+        return model_device_impl(cohort, d_kr, kind, labels, values, strata, num_terms, num_permutations, seed, d_out, d_info, d_stat,
+                                 d_aliased, static_cast<hipStream_t>(stream));
     });
 }
 
@@ -487,6 +523,15 @@ int epik_amd_cohort_model_metric(epik_amd_cohort *cohort, const epik_amd_tree *t
                                  uint32_t num_permutations, uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info,
                                  double *stat, uint8_t *aliased)
 {
+    return epik_amd_cohort_model_strata(cohort, tree, branch_length, metric, kind, labels, values, num_terms, num_permutations, seed, out,
+                                        info, stat, aliased, nullptr);
+}
+
+int epik_amd_cohort_model_strata(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                                 const uint32_t *kind, const uint32_t *labels, const double *values, uint32_t num_terms,
+                                 uint32_t num_permutations, uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info,
+                                 double *stat, uint8_t *aliased, const uint32_t *strata)
+{
     return guarded("cohort_model", [&]() -> int {
         COHORT_TRY(check_cohort(cohort));
         COHORT_TRY(terms_valid(num_terms));
@@ -501,8 +546,8 @@ int epik_amd_cohort_model_metric(epik_amd_cohort *cohort, const epik_amd_tree *t
         COHORT_TRY(r.alloc(out_bytes + sizeof(epik_amd_model_info) + kColumns));  // the records | the info block | aliased
         COHORT_TRY(s.alloc(stat_bytes, stat != nullptr));
         COHORT_TRY(cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr));
-        COHORT_TRY(model_device_impl(cohort, kr.d, kind, labels, values, num_terms, num_permutations, seed, r.d, r.at(out_bytes), s.d,
-                                     r.at(out_bytes + sizeof(epik_amd_model_info)), nullptr));
+        COHORT_TRY(model_device_impl(cohort, kr.d, kind, labels, values, strata, num_terms, num_permutations, seed, r.d, r.at(out_bytes),
+                                     s.d, r.at(out_bytes + sizeof(epik_amd_model_info)), nullptr));
         COHORT_TRY(r.copy_to(out, out_bytes));
         COHORT_TRY(r.copy_to(info, sizeof *info, out_bytes));
         COHORT_TRY(r.copy_to(aliased, kColumns, out_bytes + sizeof *info));
@@ -524,13 +569,23 @@ int epik_amd_cohort_model_metric_host(const uint64_t *mass, uint32_t num_samples
                                       const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed,
                                       epik_amd_model_term *out, epik_amd_model_info *info, double *stat, uint8_t *aliased)
 {
+    return epik_amd_cohort_model_strata_host(mass, num_samples, num_branches, first, branch_length, metric, kind, labels, values, num_terms,
+                                             num_permutations, seed, out, info, stat, aliased, nullptr);
+}
+
+int epik_amd_cohort_model_strata_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                      const double *branch_length, uint32_t metric, const uint32_t *kind, const uint32_t *labels,
+                                      const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed,
+                                      epik_amd_model_term *out, epik_amd_model_info *info, double *stat, uint8_t *aliased,
+                                      const uint32_t *strata)
+{
     return guarded("cohort_model_host", [&]() -> int {
         COHORT_TRY(check_host_shape(num_samples, num_branches));
         COHORT_TRY(terms_valid(num_terms));
         COHORT_TRY(check_present(mass, first, branch_length, kind, labels, values, out, info, aliased));
         std::string err;
         return rule_result(model_records(mass, num_samples, num_branches, first, branch_length, kind, labels, values, num_terms,
-                                         num_permutations, seed, out, info, stat, aliased, err, metric),
+                                         num_permutations, seed, out, info, stat, aliased, err, metric, strata),
                            err);
     });
 }
@@ -539,13 +594,22 @@ int epik_amd_cohort_model_kr_host(const double *kr, const uint64_t *totals, uint
                                   const uint32_t *labels, const double *values, uint32_t num_terms, uint32_t num_permutations,
                                   uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info, double *stat, uint8_t *aliased)
 {
+    return epik_amd_cohort_model_strata_kr_host(kr, totals, num_samples, kind, labels, values, num_terms, num_permutations, seed, out, info,
+                                                stat, aliased, nullptr);
+}
+
+int epik_amd_cohort_model_strata_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *kind,
+                                         const uint32_t *labels, const double *values, uint32_t num_terms, uint32_t num_permutations,
+                                         uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info, double *stat,
+                                         uint8_t *aliased, const uint32_t *strata)
+{
     return guarded("cohort_model_kr_host", [&]() -> int {
         COHORT_TRY(check_host_samples(num_samples));
         COHORT_TRY(terms_valid(num_terms));
         COHORT_TRY(check_present(kr, totals, kind, labels, values, out, info, aliased));
         std::string err;
         return rule_result(model_records_of_kr(kr, totals, num_samples, kind, labels, values, num_terms, num_permutations, seed, out, info,
-                                               stat, aliased, err),
+                                               stat, aliased, err, strata),
                            err);
     });
 }

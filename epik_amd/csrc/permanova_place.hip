@@ -25,6 +25,9 @@
 //                             labelling with one group (whose W_0 is T) for SSW_0, ss_total, f, r2 and the groups' sums;
 //                             then the permutations 1 .. P, each unit adding its count to at_most with a vector atomic.
 //   permanova_finish_kernel   p = (1 + at_most) / (P + 1), and NA into the ssw of the tests that did not run.
+//   permanova_strata_kernel   with strata only (the strata rule of include/epik_amd.h): the tables of every
+//                             test's list, once a call; the permutations then run in permanova_ssw_kernel's kStrata
+//                             instantiation, whose LDS tier ends at kLdsStrataPositions.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -44,6 +47,7 @@ constexpr uint32_t kPairSlots = EPIK_AMD_PERMANOVA_PAIR_SLOTS;
 constexpr uint32_t kMissing = EPIK_AMD_PERMANOVA_MISSING;
 constexpr uint32_t kPerms = 4;              // the labellings a workgroup carries through one pass over A2: the bytes of a word
 constexpr uint32_t kLdsPositions = 1024;    // the most positions of a test whose vectors stay in LDS (62 KiB with the rest)
+constexpr uint32_t kLdsStrataPositions = 512;  // ... with strata: their two tables beside the rest would make 70 KiB at 1 024
 constexpr uint32_t kCountPositions = 256;   // up to here the LDS path ranks by counting; beyond, it sorts
 constexpr uint32_t kSmallSamples = 128;     // up to here a workgroup is one wave
 constexpr uint32_t kGeneralBlocks = 256;    // workgroups of the general path: each has a slice
@@ -74,11 +78,13 @@ struct PermSpace {
     PermColumn *cols;   // [M]
     PermTest *tests;    // [M][1 + Q]
     uint8_t *lam;       // as idx: the groups of the positions
+    uint32_t *strata;   // with strata only: [Sp], the strata by sample
+    uint32_t *hs, *home;  // ... and as idx: the strata of a test's positions, and its positions by (stratum, position)
 };
 
 constexpr size_t kSliceBytes = kPerms * 8 + 8 + 4;  // the bytes of a slice per padded sample
 
-size_t permanova_space(void *base, uint32_t S, uint32_t padded, uint32_t M, bool pairwise, PermSpace *sp)
+size_t permanova_space(void *base, uint32_t S, uint32_t padded, uint32_t M, bool pairwise, bool strata, PermSpace *sp)
 {
     const size_t slots = 1 + (pairwise ? kPairSlots : 0), lists = pairwise ? kPairGroups : 1, tests = M * slots;
     Carver c(base);
@@ -89,7 +95,10 @@ size_t permanova_space(void *base, uint32_t S, uint32_t padded, uint32_t M, bool
                           .active = c.take<uint32_t>(tests + 1),
                           .cols = c.take<PermColumn>(M),
                           .tests = c.take<PermTest>(tests),
-                          .lam = c.take<uint8_t>((size_t)M * lists * padded)};
+                          .lam = c.take<uint8_t>((size_t)M * lists * padded),
+                          .strata = c.take<uint32_t>(strata ? padded : 0),
+                          .hs = c.take<uint32_t>(strata ? (size_t)M * lists * padded : 0),
+                          .home = c.take<uint32_t>(strata ? (size_t)M * lists * padded : 0)};
     if (sp) *sp = parts;
     return c.bytes();
 }
@@ -189,7 +198,19 @@ struct SswArgs {
     double *ssw, *group_ss;  // or null
     uint64_t seed;
     uint32_t num_samples, padded, num_tests, slots, num_permutations, pitch;
+    const uint32_t *hs, *home;  // the strata rule's tables, as idx; or null
 };
+
+// the strata rule's tables of every test with a list: a workgroup a test
+__global__ __launch_bounds__(kBlock) void permanova_strata_kernel(const uint32_t *__restrict__ strata, const uint32_t *__restrict__ idx,
+                                                                  const PermTest *__restrict__ tests, uint32_t num_tests, uint32_t *hs,
+                                                                  uint32_t *home)
+{
+    for (uint32_t test = blockIdx.x; test < num_tests; test += gridDim.x) {  // (uniform)
+        const uint32_t *list = idx + tests[test].offset;
+        strata_tables(strata, [&](uint32_t i) { return list[i]; }, tests[test].n, hs + tests[test].offset, home + tests[test].offset);
+    }
+}
 
 // the row sums of the kPerms labellings for row i: t[k] = the chain over j > i, ascending, with the same byte k
 __device__ inline void row_sums(const double *__restrict__ A2, uint64_t S, const uint32_t *idx, const uint32_t *mu, uint32_t n,
@@ -210,8 +231,10 @@ __device__ inline void row_sums(const double *__restrict__ A2, uint64_t S, const
     t[i] = t0, t[pitch + i] = t1, t[2 * pitch + i] = t2, t[3 * pitch + i] = t3;
 }
 
-// kObserved: the labellings lambda and "one group" of every test to run; else its permutations 1 .. P, kPerms a unit
-template <bool kLds, bool kObserved>
+// kObserved: the labellings lambda and "one group" of every test to run; else its permutations 1 .. P, kPerms a unit.
+// kStrata: the arrangements of the strata rule: the ranking is by (stratum, key, position), and the slot's entry of home[] is
+// the position whose label is taken.
+template <bool kLds, bool kObserved, bool kStrata>
 __global__ __launch_bounds__(kBlock) void permanova_ssw_kernel(const SswArgs a)
 {
     extern __shared__ __align__(16) unsigned char dynamic_lds[];
@@ -245,9 +268,16 @@ __global__ __launch_bounds__(kBlock) void permanova_ssw_kernel(const SswArgs a)
         const bool whole = test % a.slots == 0;
         const uint32_t *idx = a.idx + info.offset;
         const uint8_t *lam = a.lam + info.offset;
+        const uint32_t *hs = nullptr, *home = nullptr;
+        if constexpr (kStrata) hs = a.hs + info.offset, home = a.home + info.offset;
         if (kLds) {
             for (uint32_t i = tid; i < n; i += threads) lds_idx[i] = idx[i], lds_lam[i] = lam[i];
             idx = lds_idx, lam = lds_lam;
+            if constexpr (kStrata) {  // (the two tables follow the groups: pitch % 64 == 0)
+                uint32_t *lds_hs = reinterpret_cast<uint32_t *>(lds_lam + pitch), *lds_home = lds_hs + pitch;
+                for (uint32_t i = tid; i < n; i += threads) lds_hs[i] = hs[i], lds_home[i] = home[i];
+                hs = lds_hs, home = lds_home;
+            }
         }
         for (uint32_t g = tid; g < G; g += threads) size[g] = whole ? a.cols[info.column].size[g] : g ? info.size[1] : info.size[0];
         __syncthreads();
@@ -277,12 +307,16 @@ __global__ __launch_bounds__(kBlock) void permanova_ssw_kernel(const SswArgs a)
                             const bool up = (lo & width) == 0;
                             const uint64_t ka = keys[lo], kc = keys[hi];
                             const uint32_t pa = pos[lo], pc = pos[hi];
-                            const bool above = ka > kc || (ka == kc && pa > pc);
+                            bool above;
+                            if constexpr (kStrata)  // (the padding's position is no index: its stratum is above every other)
+                                above = strata_before(pc < n ? hs[pc] : 0xffffffffu, kc, pc, pa < n ? hs[pa] : 0xffffffffu, ka, pa);
+                            else
+                                above = ka > kc || (ka == kc && pa > pc);
                             if (above == up) keys[lo] = kc, keys[hi] = ka, pos[lo] = pc, pos[hi] = pa;
                         }
                         __syncthreads();
                     }
-                for (uint32_t r = tid; r < n; r += threads) mu8[pos[r] * kPerms + k] = lam[r];
+                for (uint32_t r = tid; r < n; r += threads) mu8[pos[r] * kPerms + k] = lam[kStrata ? home[r] : r];
             } else {
                 for (uint32_t i = tid; i < n; i += threads) {
                     const uint64_t mine = keys[i];
@@ -290,9 +324,10 @@ __global__ __launch_bounds__(kBlock) void permanova_ssw_kernel(const SswArgs a)
 #pragma unroll 4
                     for (uint32_t j = 0; j < n; ++j) {
                         const uint64_t other = keys[j];  // a broadcast
-                        rank += other < mine || (other == mine && j < i);
+                        if constexpr (kStrata) rank += strata_before(hs[j], other, j, hs[i], mine, i);
+                        else rank += other < mine || (other == mine && j < i);
                     }
-                    mu8[i * kPerms + k] = lam[rank];
+                    mu8[i * kPerms + k] = lam[kStrata ? home[rank] : rank];
                 }
             }
             __syncthreads();  // (the keys are written again)
@@ -367,8 +402,8 @@ int check_arguments(const uint32_t *labels, uint32_t S, uint32_t M, uint32_t P, 
     return rule_result(permanova_arguments_valid(labels, S, M, P, pairwise, err), err);
 }
 
-int permanova_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, uint32_t M, uint32_t P, uint64_t seed,
-                          bool pairwise, void *d_out, void *d_ssw, void *d_group_ss, hipStream_t stream)
+int permanova_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, const uint32_t *strata, uint32_t M,
+                          uint32_t P, uint64_t seed, bool pairwise, void *d_out, void *d_ssw, void *d_group_ss, hipStream_t stream)
 {
     COHORT_TRY(check_cohort(cohort));
     COHORT_TRY(check_columns(M));
@@ -378,10 +413,11 @@ int permanova_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint3
     COHORT_TRY(check_has_distances(cohort));
     HIP_TRY(hipSetDevice(cohort->device));
     HIP_TRY(hipDeviceSynchronize());  // (the distances enqueued on whatever stream, and an earlier call that reads the workspace)
-    COHORT_TRY(cohort_space_ensure(cohort, kSpacePermanova, permanova_space(nullptr, S, padded, M, pairwise, nullptr)));
+    COHORT_TRY(cohort_space_ensure(cohort, kSpacePermanova, permanova_space(nullptr, S, padded, M, pairwise, strata != nullptr, nullptr)));
     PermSpace sp;
-    permanova_space(cohort->space[kSpacePermanova].d, S, padded, M, pairwise, &sp);
+    permanova_space(cohort->space[kSpacePermanova].d, S, padded, M, pairwise, strata != nullptr, &sp);
     COHORT_TRY(upload_labels_by_column(labels, S, M, padded, kMissing, sp.lab));
+    if (strata) COHORT_TRY(upload_strata(strata, S, padded, sp.strata));
     const uint32_t slots = 1 + (pairwise ? kPairSlots : 0), lists = pairwise ? kPairGroups : 1, tests = M * slots;
     HIP_TRY(hipMemsetAsync(sp.active + tests, 0, sizeof(uint32_t), stream));
     auto *out = static_cast<epik_amd_permanova *>(d_out);
@@ -393,21 +429,29 @@ int permanova_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint3
     if (pairwise)
         hipLaunchKernelGGL(permanova_pairs_kernel, cohort_grid(cohort, (uint64_t)M * kPairSlots, kManyBlocks), dim3(kWave), 0, stream, padded,
                            M, sp.idx, sp.lam, sp.cols, sp.tests, sp.active, out);
-    const bool lds = lds_switch("EPIK_AMD_PERMANOVA_LDS", S, kLdsPositions);  // (=0, tests: the general path whatever S)
+    if (strata)
+        hipLaunchKernelGGL(permanova_strata_kernel, cohort_grid(cohort, tests, kManyBlocks), dim3(kBlock), 0, stream, sp.strata, sp.idx,
+                           sp.tests, tests, sp.hs, sp.home);
+    // (=0, tests: the general path whatever S)
+    const bool lds = lds_switch("EPIK_AMD_PERMANOVA_LDS", S, strata ? kLdsStrataPositions : kLdsPositions);
     uint32_t pitch = padded;  // the general path's; the LDS path's: a power of two, for the sort
     if (lds)
         for (pitch = kWave; pitch < S; pitch <<= 1) {}
     const SswArgs args{sp.A2, sp.idx, sp.lam, sp.cols, sp.tests, sp.active, sp.scratch, out, static_cast<double *>(d_ssw),
-                       static_cast<double *>(d_group_ss), seed, S, padded, tests, slots, P, pitch};
-    const size_t dynamic = lds ? (size_t)pitch * (kPerms * 8 + 8 + 4 + 4 + 4 + 1) : 0;
+                       static_cast<double *>(d_group_ss), seed, S, padded, tests, slots, P, pitch, strata ? sp.hs : nullptr,
+                       strata ? sp.home : nullptr};
+    const size_t dynamic = lds ? (size_t)pitch * (kPerms * 8 + 8 + 4 + 4 + 4 + 1 + (strata ? 4 + 4 : 0)) : 0;
     const dim3 block(S <= kSmallSamples ? kWave : kBlock);
     const uint64_t chunks = (P + kPerms - 1) / kPerms, most = lds ? kManyBlocks : kGeneralBlocks;
+    const dim3 observed = cohort_grid(cohort, tests, most), permuted = cohort_grid(cohort, tests * chunks, most);
     if (lds) {
-        hipLaunchKernelGGL((permanova_ssw_kernel<true, true>), cohort_grid(cohort, tests, most), block, dynamic, stream, args);
-        hipLaunchKernelGGL((permanova_ssw_kernel<true, false>), cohort_grid(cohort, tests * chunks, most), block, dynamic, stream, args);
+        hipLaunchKernelGGL((permanova_ssw_kernel<true, true, false>), observed, block, dynamic, stream, args);
+        if (strata) hipLaunchKernelGGL((permanova_ssw_kernel<true, false, true>), permuted, block, dynamic, stream, args);
+        else hipLaunchKernelGGL((permanova_ssw_kernel<true, false, false>), permuted, block, dynamic, stream, args);
     } else {
-        hipLaunchKernelGGL((permanova_ssw_kernel<false, true>), cohort_grid(cohort, tests, most), block, 0, stream, args);
-        hipLaunchKernelGGL((permanova_ssw_kernel<false, false>), cohort_grid(cohort, tests * chunks, most), block, 0, stream, args);
+        hipLaunchKernelGGL((permanova_ssw_kernel<false, true, false>), observed, block, 0, stream, args);
+        if (strata) hipLaunchKernelGGL((permanova_ssw_kernel<false, false, true>), permuted, block, 0, stream, args);
+        else hipLaunchKernelGGL((permanova_ssw_kernel<false, false, false>), permuted, block, 0, stream, args);
     }
     const uint64_t finish = d_ssw ? (uint64_t)tests * (P + 1) : tests;
     hipLaunchKernelGGL(permanova_finish_kernel, cohort_grid(cohort, (finish + kBlock - 1) / kBlock, kManyBlocks), dim3(kBlock), 0, stream,
@@ -424,9 +468,17 @@ int epik_amd_cohort_permanova_device(epik_amd_cohort *cohort, const void *d_kr, 
                                      uint32_t num_permutations, uint64_t seed, int pairwise, void *d_out, void *d_ssw,
                                      void *d_group_ss, void *stream)
 {
+    return epik_amd_cohort_permanova_strata_device(cohort, d_kr, labels, num_columns, num_permutations, seed, pairwise, d_out, d_ssw,
+                                                   d_group_ss, stream, nullptr);
+}
+
+int epik_amd_cohort_permanova_strata_device(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, uint32_t num_columns,
+                                            uint32_t num_permutations, uint64_t seed, int pairwise, void *d_out, void *d_ssw,
+                                            void *d_group_ss, void *stream, const uint32_t *strata)
+{
     return guarded("cohort_permanova_device", [&]() -> int {
-        return permanova_device_impl(cohort, d_kr, labels, num_columns, num_permutations, seed, pairwise != 0, d_out, d_ssw, d_group_ss,
-                                     static_cast<hipStream_t>(stream));
+        return permanova_device_impl(cohort, d_kr, labels, strata, num_columns, num_permutations, seed, pairwise != 0, d_out, d_ssw,
+                                     d_group_ss, static_cast<hipStream_t>(stream));
     });
 }
 
@@ -441,6 +493,14 @@ int epik_amd_cohort_permanova(epik_amd_cohort *cohort, const epik_amd_tree *tree
 int epik_amd_cohort_permanova_metric(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
                                      const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                      epik_amd_permanova *out, double *ssw, double *group_ss)
+{
+    return epik_amd_cohort_permanova_strata(cohort, tree, branch_length, metric, labels, num_columns, num_permutations, seed, pairwise, out,
+                                            ssw, group_ss, nullptr);
+}
+
+int epik_amd_cohort_permanova_strata(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                                     const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
+                                     epik_amd_permanova *out, double *ssw, double *group_ss, const uint32_t *strata)
 {
     return guarded("cohort_permanova", [&]() -> int {
         COHORT_TRY(check_cohort(cohort));
@@ -458,7 +518,8 @@ int epik_amd_cohort_permanova_metric(epik_amd_cohort *cohort, const epik_amd_tre
         COHORT_TRY(s.alloc(ssw_bytes, ssw != nullptr));
         COHORT_TRY(g.alloc(group_bytes, group_ss != nullptr));
         COHORT_TRY(cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr));
-        COHORT_TRY(permanova_device_impl(cohort, kr.d, labels, num_columns, num_permutations, seed, pairwise != 0, r.d, s.d, g.d, nullptr));
+        COHORT_TRY(permanova_device_impl(cohort, kr.d, labels, strata, num_columns, num_permutations, seed, pairwise != 0, r.d, s.d, g.d,
+                                         nullptr));
         COHORT_TRY(r.copy_to(out, out_bytes));
         COHORT_TRY(s.copy_to(ssw, ssw_bytes));
         return g.copy_to(group_ss, group_bytes);
@@ -479,12 +540,21 @@ int epik_amd_cohort_permanova_metric_host(const uint64_t *mass, uint32_t num_sam
                                           uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permanova *out, double *ssw,
                                           double *group_ss)
 {
+    return epik_amd_cohort_permanova_strata_host(mass, num_samples, num_branches, first, branch_length, metric, labels, num_columns,
+                                                 num_permutations, seed, pairwise, out, ssw, group_ss, nullptr);
+}
+
+int epik_amd_cohort_permanova_strata_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                          const double *branch_length, uint32_t metric, const uint32_t *labels, uint32_t num_columns,
+                                          uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permanova *out, double *ssw,
+                                          double *group_ss, const uint32_t *strata)
+{
     return guarded("cohort_permanova_host", [&]() -> int {
         COHORT_TRY(check_host_shape(num_samples, num_branches));
         COHORT_TRY(check_present(mass, first, branch_length, labels, out));
         std::string err;
         return rule_result(permanova_records(mass, num_samples, num_branches, first, branch_length, labels, num_columns, num_permutations,
-                                             seed, pairwise != 0, out, ssw, group_ss, err, metric),
+                                             seed, pairwise != 0, out, ssw, group_ss, err, metric, strata),
                            err);
     });
 }
@@ -493,12 +563,20 @@ int epik_amd_cohort_permanova_kr_host(const double *kr, const uint64_t *totals, 
                                       uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                       epik_amd_permanova *out, double *ssw, double *group_ss)
 {
+    return epik_amd_cohort_permanova_strata_kr_host(kr, totals, num_samples, labels, num_columns, num_permutations, seed, pairwise, out, ssw,
+                                                    group_ss, nullptr);
+}
+
+int epik_amd_cohort_permanova_strata_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
+                                             uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
+                                             epik_amd_permanova *out, double *ssw, double *group_ss, const uint32_t *strata)
+{
     return guarded("cohort_permanova_kr_host", [&]() -> int {
         COHORT_TRY(check_host_samples(num_samples));
         COHORT_TRY(check_present(kr, totals, labels, out));
         std::string err;
         return rule_result(permanova_records_of_kr(kr, totals, num_samples, labels, num_columns, num_permutations, seed, pairwise != 0, out,
-                                                   ssw, group_ss, err),
+                                                   ssw, group_ss, err, strata),
                            err);
     });
 }

@@ -28,6 +28,8 @@
 //                               no branch); kG = 0: in LDS, [g][lane].  eta_r into stat; the count of eta_r >= eta2 by a ballot
 //                               and one vector atomic add a wave.
 //   permdisp_finish_kernel      p of every defined test; eta2 and NA into the stat of the tests that did not permute.
+//   permdisp_strata_kernel      with strata only (the strata rule): the tables of every test's list, once a call;
+//                               permdisp_labellings_kernel<true> then takes sigma_p (permutation_arrangement) for the rank.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -81,9 +83,11 @@ struct DispSpace {
     uint8_t *lam, *clip;    // [M][Sp]: the groups of the positions, and whether z2 < 0
     uint8_t *two;           // as pos: the groups of a test's positions
     uint8_t *MU;            // [lists * Sp][kChunk]: the chunk of labellings of the column at hand
+    uint32_t *strata;       // with strata only: [Sp], the strata by sample
+    uint32_t *hs, *home;    // ... and as pos: the strata of a test's positions, and its positions by (stratum, position)
 };
 
-size_t permdisp_space(void *base, uint32_t padded, uint32_t M, bool pairwise, DispSpace *sp)
+size_t permdisp_space(void *base, uint32_t padded, uint32_t M, bool pairwise, bool strata, DispSpace *sp)
 {
     const size_t slots = 1 + (pairwise ? kPairSlots : 0), lists = pairwise ? kGroups : 1;
     const size_t column = (size_t)M * padded, pool = (size_t)M * lists * padded;
@@ -103,7 +107,10 @@ size_t permdisp_space(void *base, uint32_t padded, uint32_t M, bool pairwise, Di
                           .lam = c.take<uint8_t>(column),
                           .clip = c.take<uint8_t>(column),
                           .two = c.take<uint8_t>(pool),
-                          .MU = c.take<uint8_t>(lists * padded * kChunk)};
+                          .MU = c.take<uint8_t>(lists * padded * kChunk),
+                          .strata = c.take<uint32_t>(strata ? padded : 0),
+                          .hs = c.take<uint32_t>(strata ? pool : 0),
+                          .home = c.take<uint32_t>(strata ? pool : 0)};
     if (sp) *sp = parts;
     return c.bytes();
 }
@@ -278,6 +285,17 @@ __global__ __launch_bounds__(kWave) void permdisp_tests_kernel(const DispArgs a)
     }
 }
 
+// the strata rule's tables of every test with a list: a workgroup a (column, slot)
+__global__ __launch_bounds__(kBlock) void permdisp_strata_kernel(const DispArgs a)
+{
+    for (uint32_t unit = blockIdx.x; unit < a.num_columns * a.slots; unit += gridDim.x) {  // (uniform)
+        const DispTest *test = a.sp.tests + unit;
+        const uint32_t *idx = a.sp.idx + (uint64_t)(unit / a.slots) * a.padded, *pos = a.sp.pos + test->offset;
+        strata_tables(a.sp.strata, [&](uint32_t i) { return idx[pos[i]]; }, test->n, a.sp.hs + test->offset, a.sp.home + test->offset);
+    }
+}
+
+template <bool kStrata>
 __global__ __launch_bounds__(kBlock) void permdisp_labellings_kernel(const DispArgs a)
 {
     __shared__ uint64_t tile[kCohortKeyTile];
@@ -291,7 +309,13 @@ __global__ __launch_bounds__(kBlock) void permdisp_labellings_kernel(const DispA
         uint8_t *mu = a.sp.MU + (test->offset - pool_at) * kChunk + k;  // (offset - pool_at + i < lists * Sp)
         for (uint32_t base = 0; base < n; base += kBlock) {
             const uint32_t i = base + threadIdx.x;
-            const uint32_t rank = permutation_rank(a.seed, a.p0 + k, i, n, tile);
+            uint32_t rank;
+            if constexpr (kStrata) {
+                __shared__ uint32_t htile[kCohortKeyTile];
+                rank = permutation_arrangement(a.seed, a.p0 + k, i, n, tile, htile, a.sp.hs + test->offset, a.sp.home + test->offset);
+            } else {
+                rank = permutation_rank(a.seed, a.p0 + k, i, n, tile);
+            }
             if (i < n) mu[(uint64_t)i * kChunk] = two[rank];  // (rank < n)
         }
     }
@@ -375,8 +399,9 @@ int check_arguments(const uint32_t *labels, uint32_t S, uint32_t M, uint32_t P)
     return rule_result(permdisp_arguments_valid(labels, S, M, P, err), err);
 }
 
-int permdisp_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, uint32_t M, uint32_t P, uint64_t seed,
-                         bool pairwise, void *d_out, void *d_stat, void *d_group_mean, void *d_z, hipStream_t stream)
+int permdisp_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, const uint32_t *strata, uint32_t M,
+                         uint32_t P, uint64_t seed, bool pairwise, void *d_out, void *d_stat, void *d_group_mean, void *d_z,
+                         hipStream_t stream)
 {
     COHORT_TRY(check_cohort(cohort));
     COHORT_TRY(check_columns(M));
@@ -391,10 +416,11 @@ int permdisp_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32
     for (uint32_t &n : most_tests) n = n >= 2 ? 1 + (pairwise ? n * (n - 1) / 2 : 0) : 0;
     HIP_TRY(hipSetDevice(cohort->device));
     HIP_TRY(hipDeviceSynchronize());  // (the distances enqueued on whatever stream, and an earlier call that reads the workspace)
-    COHORT_TRY(cohort_space_ensure(cohort, kSpacePermdisp, permdisp_space(nullptr, padded, M, pairwise, nullptr)));
+    COHORT_TRY(cohort_space_ensure(cohort, kSpacePermdisp, permdisp_space(nullptr, padded, M, pairwise, strata != nullptr, nullptr)));
     DispArgs args{};
-    permdisp_space(cohort->space[kSpacePermdisp].d, padded, M, pairwise, &args.sp);
+    permdisp_space(cohort->space[kSpacePermdisp].d, padded, M, pairwise, strata != nullptr, &args.sp);
     COHORT_TRY(upload_labels_by_column(labels, S, M, padded, kMissing, args.sp.lab));
+    if (strata) COHORT_TRY(upload_strata(strata, S, padded, args.sp.strata));
     const uint32_t slots = 1 + (pairwise ? kPairSlots : 0), lists = pairwise ? kGroups : 1;
     args.kr = static_cast<const double *>(d_kr), args.out = static_cast<epik_amd_permdisp *>(d_out);
     args.stat = static_cast<double *>(d_stat), args.group_mean = static_cast<double *>(d_group_mean), args.z = static_cast<double *>(d_z);
@@ -404,6 +430,7 @@ int permdisp_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32
     hipLaunchKernelGGL(permdisp_columns_kernel, cohort_grid(cohort, M, kColumns), dim3(kWave), 0, stream, cohort->d_total, args);
     hipLaunchKernelGGL(permdisp_distance_kernel, cohort_grid(cohort, M, kColumns), dim3(kBlock), 0, stream, args);
     hipLaunchKernelGGL(permdisp_tests_kernel, cohort_grid(cohort, tests, kManyBlocks), dim3(kWave), 0, stream, args);
+    if (strata) hipLaunchKernelGGL(permdisp_strata_kernel, cohort_grid(cohort, tests, kManyBlocks), dim3(kBlock), 0, stream, args);
     const bool registers = most_groups <= kRegisterGroups;
     const uint32_t lanes = registers ? kBlock : kLdsLanes;
     const size_t dynamic = registers ? 0 : (size_t)kGroups * lanes * sizeof(double);
@@ -414,7 +441,9 @@ int permdisp_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32
         for (uint32_t p0 = 1; p0 <= P; p0 += kChunk) {
             args.column = c, args.p0 = p0, args.np = std::min<uint32_t>(kChunk, P + 1 - p0);
             const uint64_t subs = (args.np + lanes - 1) / lanes, listed = most_tests[c];
-            hipLaunchKernelGGL(permdisp_labellings_kernel, cohort_grid(cohort, listed * args.np, kManyBlocks), dim3(kBlock), 0, stream, args);
+            const dim3 labellings = cohort_grid(cohort, listed * args.np, kManyBlocks);
+            if (strata) hipLaunchKernelGGL(permdisp_labellings_kernel<true>, labellings, dim3(kBlock), 0, stream, args);
+            else hipLaunchKernelGGL(permdisp_labellings_kernel<false>, labellings, dim3(kBlock), 0, stream, args);
             if (registers)
                 hipLaunchKernelGGL(permdisp_chains_kernel<kRegisterGroups>, cohort_grid(cohort, listed * subs, kManyBlocks), dim3(lanes), 0,
                                    stream, args);
@@ -437,9 +466,17 @@ int epik_amd_cohort_permdisp_device(epik_amd_cohort *cohort, const void *d_kr, c
                                     uint32_t num_permutations, uint64_t seed, int pairwise, void *d_out, void *d_stat,
                                     void *d_group_mean, void *d_z, void *stream)
 {
+    return epik_amd_cohort_permdisp_strata_device(cohort, d_kr, labels, num_columns, num_permutations, seed, pairwise, d_out, d_stat,
+                                                  d_group_mean, d_z, stream, nullptr);
+}
+
+int epik_amd_cohort_permdisp_strata_device(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, uint32_t num_columns,
+                                           uint32_t num_permutations, uint64_t seed, int pairwise, void *d_out, void *d_stat,
+                                           void *d_group_mean, void *d_z, void *stream, const uint32_t *strata)
+{
     return guarded("cohort_permdisp_device", [&]() -> int {
-        return permdisp_device_impl(cohort, d_kr, labels, num_columns, num_permutations, seed, pairwise != 0, d_out, d_stat, d_group_mean,
-                                    d_z, static_cast<hipStream_t>(stream));
+        return permdisp_device_impl(cohort, d_kr, labels, strata, num_columns, num_permutations, seed, pairwise != 0, d_out, d_stat,
+                                    d_group_mean, d_z, static_cast<hipStream_t>(stream));
     });
 }
 
@@ -454,6 +491,14 @@ int epik_amd_cohort_permdisp(epik_amd_cohort *cohort, const epik_amd_tree *tree,
 int epik_amd_cohort_permdisp_metric(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
                                     const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                     epik_amd_permdisp *out, double *stat, double *group_mean, double *z)
+{
+    return epik_amd_cohort_permdisp_strata(cohort, tree, branch_length, metric, labels, num_columns, num_permutations, seed, pairwise, out,
+                                           stat, group_mean, z, nullptr);
+}
+
+int epik_amd_cohort_permdisp_strata(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                                    const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
+                                    epik_amd_permdisp *out, double *stat, double *group_mean, double *z, const uint32_t *strata)
 {
     return guarded("cohort_permdisp", [&]() -> int {
         COHORT_TRY(check_cohort(cohort));
@@ -472,8 +517,8 @@ int epik_amd_cohort_permdisp_metric(epik_amd_cohort *cohort, const epik_amd_tree
         COHORT_TRY(g.alloc(mean_bytes));
         COHORT_TRY(zz.alloc(z_bytes));
         COHORT_TRY(cohort_distance_enqueue(cohort, tree, branch_length, metric, kr.d, nullptr));
-        COHORT_TRY(permdisp_device_impl(cohort, kr.d, labels, num_columns, num_permutations, seed, pairwise != 0, r.d, s.d, g.d, zz.d,
-                                        nullptr));
+        COHORT_TRY(permdisp_device_impl(cohort, kr.d, labels, strata, num_columns, num_permutations, seed, pairwise != 0, r.d, s.d, g.d,
+                                        zz.d, nullptr));
         COHORT_TRY(r.copy_to(out, out_bytes));
         COHORT_TRY(s.copy_to(stat, stat_bytes));
         COHORT_TRY(g.copy_to(group_mean, mean_bytes));
@@ -495,12 +540,21 @@ int epik_amd_cohort_permdisp_metric_host(const uint64_t *mass, uint32_t num_samp
                                          uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permdisp *out, double *stat,
                                          double *group_mean, double *z)
 {
+    return epik_amd_cohort_permdisp_strata_host(mass, num_samples, num_branches, first, branch_length, metric, labels, num_columns,
+                                                num_permutations, seed, pairwise, out, stat, group_mean, z, nullptr);
+}
+
+int epik_amd_cohort_permdisp_strata_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                         const double *branch_length, uint32_t metric, const uint32_t *labels, uint32_t num_columns,
+                                         uint32_t num_permutations, uint64_t seed, int pairwise, epik_amd_permdisp *out, double *stat,
+                                         double *group_mean, double *z, const uint32_t *strata)
+{
     return guarded("cohort_permdisp_host", [&]() -> int {
         COHORT_TRY(check_host_shape(num_samples, num_branches));
         COHORT_TRY(check_present(mass, first, branch_length, labels, out, group_mean, z));
         std::string err;
         return rule_result(permdisp_records(mass, num_samples, num_branches, first, branch_length, labels, num_columns, num_permutations,
-                                            seed, pairwise != 0, out, stat, group_mean, z, err, metric),
+                                            seed, pairwise != 0, out, stat, group_mean, z, err, metric, strata),
                            err);
     });
 }
@@ -509,12 +563,20 @@ int epik_amd_cohort_permdisp_kr_host(const double *kr, const uint64_t *totals, u
                                      uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                      epik_amd_permdisp *out, double *stat, double *group_mean, double *z)
 {
+    return epik_amd_cohort_permdisp_strata_kr_host(kr, totals, num_samples, labels, num_columns, num_permutations, seed, pairwise, out,
+                                                   stat, group_mean, z, nullptr);
+}
+
+int epik_amd_cohort_permdisp_strata_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
+                                            uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
+                                            epik_amd_permdisp *out, double *stat, double *group_mean, double *z, const uint32_t *strata)
+{
     return guarded("cohort_permdisp_kr_host", [&]() -> int {
         COHORT_TRY(check_host_samples(num_samples));
         COHORT_TRY(check_present(kr, totals, labels, out, group_mean, z));
         std::string err;
         return rule_result(permdisp_records_of_kr(kr, totals, num_samples, labels, num_columns, num_permutations, seed, pairwise != 0, out,
-                                                  stat, group_mean, z, err),
+                                                  stat, group_mean, z, err, strata),
                            err);
     });
 }

@@ -9,6 +9,7 @@
 #include <map>
 #include <set>
 #include <stdexcept>
+#include <tuple>
 
 namespace epik_amd {
 
@@ -920,6 +921,29 @@ inline uint64_t permanova_key(uint64_t seed, uint32_t p, uint32_t i)
     return z ^ (z >> 31);
 }
 
+// The arrangements sigma_p of the strata rule (include/epik_amd.h) over n positions: what the four permutation tests share.
+// `strata` is by sample, or null for one stratum, and sample[i] the sample of position i.  home[] lists the positions by
+// (stratum, position); the positions sorted by (stratum, key, position) take its entries slot by slot, so a position gets
+// the w-th member of its own stratum.  With one stratum sigma_p(i) = rank_p(i).
+struct arrangements {
+    std::vector<uint32_t> h, home, sigma;
+    std::vector<std::tuple<uint32_t, uint64_t, uint32_t>> keys;
+    template <class Sample>
+    arrangements(const uint32_t* strata, size_t n, Sample sample) : h(n, 0), home(n), sigma(n), keys(n)
+    {
+        for (size_t i = 0; i < n; ++i) home[i] = (uint32_t)i, h[i] = strata ? strata[sample(i)] : 0;
+        std::stable_sort(home.begin(), home.end(), [&](uint32_t a, uint32_t b) { return h[a] < h[b]; });
+    }
+    const std::vector<uint32_t>& of(uint64_t seed, uint32_t p)
+    {
+        const size_t n = h.size();
+        for (uint32_t i = 0; i < n; ++i) keys[i] = {h[i], permanova_key(seed, p, i), i};
+        std::sort(keys.begin(), keys.end());
+        for (size_t r = 0; r < n; ++r) sigma[std::get<2>(keys[r])] = home[r];
+        return sigma;
+    }
+};
+
 // SSW(mu) over the compact block A[n][n]: the rule's three chains; W_g / n_g into `terms` where asked for
 double permanova_ssw(const std::vector<double>& A, size_t n, const std::vector<uint32_t>& mu, const std::vector<uint32_t>& size,
                      std::vector<double>& t, double* terms)
@@ -944,7 +968,8 @@ double permanova_ssw(const std::vector<double>& A, size_t n, const std::vector<u
 
 // one test of the rule: the samples idx[n] with the groups lam[n] of sizes size[G]
 void permanova_test(const double* kr, size_t S, const std::vector<uint32_t>& idx, const std::vector<uint32_t>& lam,
-                    const std::vector<uint32_t>& size, uint32_t P, uint64_t seed, epik_amd_permanova& rec, double* ssw, double* terms)
+                    const std::vector<uint32_t>& size, uint32_t P, uint64_t seed, epik_amd_permanova& rec, double* ssw, double* terms,
+                    const uint32_t* strata)
 {
     const size_t n = idx.size(), G = size.size();
     rec.used = (uint32_t)n, rec.groups = (uint32_t)G;
@@ -964,13 +989,12 @@ void permanova_test(const double* kr, size_t S, const std::vector<uint32_t>& idx
         rec.r2 = among / rec.ss_total;
         if (ssw0 != 0.0) rec.f = (among / (double)(G - 1)) / (ssw0 / (double)(n - G));
     }
-    std::vector<std::pair<uint64_t, uint32_t>> keys(n);
+    arrangements arrange(strata, n, [&](size_t i) { return idx[i]; });
     std::vector<uint32_t> mu(n);
     uint64_t at_most = 0;
     for (uint32_t p = 1; p <= P; ++p) {
-        for (uint32_t i = 0; i < n; ++i) keys[i] = {permanova_key(seed, p, i), i};
-        std::sort(keys.begin(), keys.end());
-        for (size_t r = 0; r < n; ++r) mu[keys[r].second] = lam[r];  // (rank_p(keys[r].second) = r)
+        const std::vector<uint32_t>& sigma = arrange.of(seed, p);
+        for (size_t i = 0; i < n; ++i) mu[i] = lam[sigma[i]];
         const double v = permanova_ssw(A, n, mu, size, t, nullptr);
         if (ssw) ssw[p] = v;
         at_most += v <= ssw0;
@@ -1014,7 +1038,7 @@ int permanova_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint
 
 int permanova_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
                             uint32_t num_columns, uint32_t num_permutations, uint64_t seed, bool pairwise, epik_amd_permanova* out,
-                            double* ssw, double* group_ss, std::string& err)
+                            double* ssw, double* group_ss, std::string& err, const uint32_t* strata)
 {
     const size_t S = num_samples, M = num_columns, P = num_permutations;
     if (const int rc = permanova_arguments_valid(labels, num_samples, num_columns, num_permutations, pairwise, err); rc != EPIK_AMD_OK)
@@ -1033,7 +1057,7 @@ int permanova_records_of_kr(const double* kr, const uint64_t* totals, uint32_t n
             idx.push_back((uint32_t)s), lam.push_back(group_of[v]), ++size[group_of[v]];
         }
         permanova_test(kr, S, idx, lam, size, num_permutations, seed, out[c * slots], ssw ? ssw + c * slots * (P + 1) : nullptr,
-                       group_ss ? group_ss + c * EPIK_AMD_PERMANOVA_MAX_GROUPS : nullptr);
+                       group_ss ? group_ss + c * EPIK_AMD_PERMANOVA_MAX_GROUPS : nullptr, strata);
         if (!pairwise) continue;
         for (size_t h = 1; h < size.size(); ++h)
             for (size_t g = 0; g < h; ++g) {
@@ -1042,7 +1066,7 @@ int permanova_records_of_kr(const double* kr, const uint64_t* totals, uint32_t n
                     if (lam[i] == g || lam[i] == h) sub.push_back(idx[i]), two.push_back(lam[i] == h);
                 const size_t slot = c * slots + 1 + h * (h - 1) / 2 + g;
                 permanova_test(kr, S, sub, two, {size[g], size[h]}, num_permutations, seed, out[slot],
-                               ssw ? ssw + slot * (P + 1) : nullptr, nullptr);
+                               ssw ? ssw + slot * (P + 1) : nullptr, nullptr, strata);
             }
     }
     return EPIK_AMD_OK;
@@ -1051,7 +1075,7 @@ int permanova_records_of_kr(const double* kr, const uint64_t* totals, uint32_t n
 int permanova_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                       const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
                       uint64_t seed, bool pairwise, epik_amd_permanova* out, double* ssw, double* group_ss, std::string& err,
-                      uint32_t metric)
+                      uint32_t metric, const uint32_t* strata)
 {
     const size_t S = num_samples, N = num_branches;
     if (const int rc = permanova_arguments_valid(labels, num_samples, num_columns, num_permutations, pairwise, err); rc != EPIK_AMD_OK)
@@ -1063,7 +1087,7 @@ int permanova_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_b
     for (size_t s = 0; s < S; ++s)
         for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
     return permanova_records_of_kr(kr.data(), totals.data(), num_samples, labels, num_columns, num_permutations, seed, pairwise, out,
-                                   ssw, group_ss, err);
+                                   ssw, group_ss, err, strata);
 }
 
 int pcoa_components_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, uint32_t num_components, double* mu,
@@ -1205,7 +1229,7 @@ int edgetest_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint3
 
 int edgetest_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                      const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, epik_amd_edgetest* out,
-                     double* stat, double* max, std::string& err)
+                     double* stat, double* max, std::string& err, const uint32_t* strata)
 {
     constexpr size_t F = EPIK_AMD_EDGETEST_FAMILIES;
     const size_t S = num_samples, N = num_branches, M = num_columns, P = num_permutations, row = P + 1;
@@ -1235,7 +1259,7 @@ int edgetest_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_br
         // the labellings in chunks of permutations, a byte a position: the vectors of a branch are formed once a chunk
         const size_t chunk = std::max<size_t>(1, ((size_t)64 << 20) / L);
         std::vector<uint8_t> mu(std::min(chunk, row) * L);
-        std::vector<std::pair<uint64_t, uint32_t>> keys(L);
+        arrangements arrange(strata, L, [&](size_t i) { return list[i]; });
         std::vector<double> mmax(F * row, 0.0), sums(G), rank;
         std::vector<char> any(F, 0);
         std::vector<double> x[F];
@@ -1250,9 +1274,8 @@ int edgetest_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_br
                     for (size_t i = 0; i < L; ++i) m[i] = (uint8_t)lam[i];
                     continue;
                 }
-                for (uint32_t i = 0; i < L; ++i) keys[i] = {permanova_key(seed, p, i), i};
-                std::sort(keys.begin(), keys.end());
-                for (size_t q = 0; q < L; ++q) m[keys[q].second] = (uint8_t)lam[q];  // (rank_p(keys[q].second) = q)
+                const std::vector<uint32_t>& sigma = arrange.of(seed, p);
+                for (size_t i = 0; i < L; ++i) m[i] = (uint8_t)lam[sigma[i]];
             }
             for (size_t b = 0; b < N; ++b) {
                 epik_amd_edgetest& r = out[c * N + b];
@@ -1317,6 +1340,7 @@ namespace {
 struct permdisp_column {
     std::vector<double> z, r;
     std::vector<char> clip;
+    std::vector<uint32_t> strata;  // by position, or empty: one stratum
 };
 
 // one test of the PERMDISP rule: the column's positions pos[n] with the groups lam[n] of sizes size[G]
@@ -1343,12 +1367,11 @@ void permdisp_test(const permdisp_column& col, const std::vector<uint32_t>& pos,
         rec.at_least = P;
         if (stat) std::fill(stat + 1, stat + 1 + P, rec.eta2);
     } else {
-        std::vector<std::pair<uint64_t, uint32_t>> keys(n);
+        arrangements arrange(col.strata.empty() ? nullptr : col.strata.data(), n, [&](size_t i) { return pos[i]; });
         std::vector<uint8_t> mu(n);
         for (uint32_t p = 1; p <= P; ++p) {
-            for (uint32_t i = 0; i < n; ++i) keys[i] = {permanova_key(seed, p, i), i};
-            std::sort(keys.begin(), keys.end());
-            for (size_t q = 0; q < n; ++q) mu[keys[q].second] = lam[q];  // (rank_p(keys[q].second) = q)
+            const std::vector<uint32_t>& sigma = arrange.of(seed, p);
+            for (size_t i = 0; i < n; ++i) mu[i] = lam[sigma[i]];
             const double eta = edgetest_among(dr.d.data(), mu.data(), n, size, sums.data()) / dr.ss;
             if (stat) stat[p] = eta;
             rec.at_least += eta >= rec.eta2;
@@ -1367,7 +1390,7 @@ int permdisp_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint3
 
 int permdisp_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
                            uint32_t num_columns, uint32_t num_permutations, uint64_t seed, bool pairwise, epik_amd_permdisp* out,
-                           double* stat, double* group_mean, double* z, std::string& err)
+                           double* stat, double* group_mean, double* z, std::string& err, const uint32_t* strata)
 {
     const size_t S = num_samples, M = num_columns, P = num_permutations;
     if (const int rc = permdisp_arguments_valid(labels, num_samples, num_columns, num_permutations, err); rc != EPIK_AMD_OK) return rc;
@@ -1406,6 +1429,8 @@ int permdisp_records_of_kr(const double* kr, const uint64_t* totals, uint32_t nu
         }
         permdisp_column col;
         col.z.resize(L), col.r.resize(L), col.clip.resize(L);
+        if (strata)
+            for (size_t i = 0; i < L; ++i) col.strata.push_back(strata[idx[i]]);
         for (size_t i = 0; i < L; ++i) {
             const uint32_t g = lam[i];
             const double z2 = m[i] - (w[g] / (double)size[g]) / (double)size[g];
@@ -1437,7 +1462,7 @@ int permdisp_records_of_kr(const double* kr, const uint64_t* totals, uint32_t nu
 int permdisp_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                      const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
                      uint64_t seed, bool pairwise, epik_amd_permdisp* out, double* stat, double* group_mean, double* z, std::string& err,
-                     uint32_t metric)
+                     uint32_t metric, const uint32_t* strata)
 {
     const size_t S = num_samples, N = num_branches;
     if (const int rc = permdisp_arguments_valid(labels, num_samples, num_columns, num_permutations, err); rc != EPIK_AMD_OK) return rc;
@@ -1448,7 +1473,7 @@ int permdisp_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_br
     for (size_t s = 0; s < S; ++s)
         for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
     return permdisp_records_of_kr(kr.data(), totals.data(), num_samples, labels, num_columns, num_permutations, seed, pairwise, out,
-                                  stat, group_mean, z, err);
+                                  stat, group_mean, z, err, strata);
 }
 
 int model_arguments_valid(const uint32_t* kind, const uint32_t* labels, const double* values, uint32_t num_samples,
@@ -1498,7 +1523,7 @@ int model_arguments_valid(const uint32_t* kind, const uint32_t* labels, const do
 
 int model_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* kind, const uint32_t* labels,
                         const double* values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed, epik_amd_model_term* out,
-                        epik_amd_model_info* info, double* stat, uint8_t* aliased, std::string& err)
+                        epik_amd_model_info* info, double* stat, uint8_t* aliased, std::string& err, const uint32_t* strata)
 {
     const size_t S = num_samples, T = num_terms, P = num_permutations;
     if (const int rc = model_arguments_valid(kind, labels, values, num_samples, num_terms, num_permutations, err); rc != EPIK_AMD_OK)
@@ -1621,12 +1646,9 @@ int model_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_s
     }
     if (!testable || !R) return EPIK_AMD_OK;
     // 6 and 7: the permutations
-    std::vector<std::pair<uint64_t, uint32_t>> keys(L);
+    arrangements arrange(strata, L, [&](size_t i) { return used[i]; });
     for (uint32_t p = 1; p <= P; ++p) {
-        for (uint32_t i = 0; i < L; ++i) keys[i] = {permanova_key(seed, p, i), i};
-        std::sort(keys.begin(), keys.end());
-        for (size_t rank = 0; rank < L; ++rank) sigma[keys[rank].second] = (uint32_t)rank;
-        sums(sigma, ss);
+        sums(arrange.of(seed, p), ss);
         const double res = ss_total - ss[T];
         for (size_t k = 0; k <= T; ++k) {
             if (!df[k]) continue;
@@ -1643,7 +1665,7 @@ int model_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_s
 int model_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                   const double* branch_length, const uint32_t* kind, const uint32_t* labels, const double* values, uint32_t num_terms,
                   uint32_t num_permutations, uint64_t seed, epik_amd_model_term* out, epik_amd_model_info* info, double* stat,
-                  uint8_t* aliased, std::string& err, uint32_t metric)
+                  uint8_t* aliased, std::string& err, uint32_t metric, const uint32_t* strata)
 {
     const size_t S = num_samples, N = num_branches;
     if (const int rc = model_arguments_valid(kind, labels, values, num_samples, num_terms, num_permutations, err); rc != EPIK_AMD_OK)
@@ -1655,7 +1677,7 @@ int model_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branc
     for (size_t s = 0; s < S; ++s)
         for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
     return model_records_of_kr(kr.data(), totals.data(), num_samples, kind, labels, values, num_terms, num_permutations, seed, out, info,
-                               stat, aliased, err);
+                               stat, aliased, err, strata);
 }
 
 cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise, size_t most_labels,
@@ -2396,6 +2418,55 @@ std::string format_model_tsv(const std::vector<cohort_sample>& samples, const ui
            "\tNA\tNA\tNA\n";
     out += "total\t" + std::to_string((int64_t)info.used - 1) + "\t" + g17(info.ss_total) + "\t" + (total ? "1" : "NA") + "\tNA\tNA\tNA\n";
     return out;
+}
+
+std::vector<uint32_t> read_cohort_strata(const std::string& file, const std::string& column, const std::vector<cohort_sample>& samples,
+                                         std::string* name)
+{
+    const char* flag = "--cohort-strata";
+    const cohort_factors factors = read_cohort_factors(file, samples, false, (size_t)-1, flag);  // (no cap: a pair a label)
+    const size_t M = factors.columns.size();
+    size_t c = 0;
+    if (column.empty()) {
+        if (M != 1)
+            throw std::runtime_error(std::string(flag) + ": " + file + " has " + std::to_string(M) +
+                                     " columns: --cohort-strata-column must name one");
+    } else {
+        c = (size_t)(std::find(factors.columns.begin(), factors.columns.end(), column) - factors.columns.begin());
+        if (c == M) throw std::runtime_error("--cohort-strata-column: " + file + " has no column '" + column + "'");
+    }
+    std::vector<uint32_t> strata(samples.size());
+    for (size_t s = 0; s < samples.size(); ++s) {
+        strata[s] = factors.labels[s * M + c];
+        if (strata[s] != EPIK_AMD_PERMANOVA_MISSING) continue;
+        std::ifstream in(file);  // the sample's line, for the message: the reader has seen it
+        std::string line;
+        size_t number = 1;
+        for (; std::getline(in, line); ++number)
+            if (!line.empty() && line[0] != '#' && split_tabs(line)[0] == samples[s].name) break;
+        throw std::runtime_error(std::string(flag) + ": " + file + " line " + std::to_string(number) + ", column " + factors.columns[c] +
+                                 ": the sample '" + samples[s].name + "' has no stratum");
+    }
+    if (name) *name = factors.columns[c];
+    return strata;
+}
+
+std::string with_strata_field(std::string text, const std::string& name)
+{
+    if (!name.empty()) text.insert(std::min(text.find('\n'), text.size()), "\tstrata=" + name);
+    return text;
+}
+
+bool constant_within_strata(const uint32_t* labels, size_t S, size_t M, size_t c, uint32_t missing, const uint64_t* totals,
+                            const uint32_t* strata)
+{
+    std::map<uint32_t, uint32_t> label_of;
+    for (size_t s = 0; s < S; ++s) {
+        const uint32_t v = labels[s * M + c];
+        if (totals[s] == 0 || v == missing) continue;
+        if (!label_of.emplace(strata[s], v).second && label_of[strata[s]] != v) return false;
+    }
+    return true;
 }
 
 void write_through_part(const std::string& filename, const std::string& text)

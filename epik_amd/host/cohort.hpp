@@ -101,6 +101,9 @@ int correlation_records(const uint64_t* mass, uint32_t num_samples, uint32_t num
 int dispersion_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                        epik_amd_dispersion* out, std::string& err);
 
+/// The four permutation tests below take `strata` (strata[S] by sample, any uint32 an id; null: one stratum): the strata rule
+/// of include/epik_amd.h, sigma_p in place of rank_p.  Null gives the bits of the rule without strata.
+
 /// num_columns in [1, 64], num_permutations in [1, 999 999], every label below 256 or 0xffffffff (missing) and, with
 /// pairwise, at most 32 distinct labels a column: 0, or EPIK_AMD_ERR_INVALID with `err` naming the cause
 int permanova_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint32_t num_columns, uint32_t num_permutations,
@@ -111,13 +114,13 @@ int permanova_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint
 /// same bits.  0, or as permanova_arguments_valid.
 int permanova_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
                             uint32_t num_columns, uint32_t num_permutations, uint64_t seed, bool pairwise, epik_amd_permanova* out,
-                            double* ssw, double* group_ss, std::string& err);
+                            double* ssw, double* group_ss, std::string& err, const uint32_t* strata = nullptr);
 /// The same from the cells: distance_matrix, then permanova_records_of_kr.  The code behind epik_amd_cohort_permanova_host
 /// and _permanova_metric_host.
 int permanova_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                       const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
                       uint64_t seed, bool pairwise, epik_amd_permanova* out, double* ssw, double* group_ss, std::string& err,
-                      uint32_t metric = EPIK_AMD_DISTANCE_KR);
+                      uint32_t metric = EPIK_AMD_DISTANCE_KR, const uint32_t* strata = nullptr);
 
 /// Principal coordinates by the rule (include/epik_amd.h) from a KR matrix kr[S][S] and totals[S] (T_s): mu[S], coord[S][K]
 /// and *info, every cell written.  libepik_amd's kernels (pcoa_place.hip) give the same bits.  0, or EPIK_AMD_ERR_INVALID
@@ -139,7 +142,7 @@ int edgetest_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint3
 /// epik_amd_cohort_edgetest_host.  0, or as edgetest_arguments_valid; first[b] > b is refused.
 int edgetest_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                      const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed, epik_amd_edgetest* out,
-                     double* stat, double* max, std::string& err);
+                     double* stat, double* max, std::string& err, const uint32_t* strata = nullptr);
 
 /// num_columns in [1, 64], num_permutations in [1, 999 999], every label below 32 or 0xffffffff (missing): 0, or
 /// EPIK_AMD_ERR_INVALID with `err` naming the cause
@@ -150,13 +153,13 @@ int permdisp_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint3
 /// same bits.  The code behind epik_amd_cohort_permdisp_kr_host.  0, or as permdisp_arguments_valid.
 int permdisp_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
                            uint32_t num_columns, uint32_t num_permutations, uint64_t seed, bool pairwise, epik_amd_permdisp* out,
-                           double* stat, double* group_mean, double* z, std::string& err);
+                           double* stat, double* group_mean, double* z, std::string& err, const uint32_t* strata = nullptr);
 /// The same from mass[S][N]: the matrix by distance_matrix first.  The code behind epik_amd_cohort_permdisp_host and
 /// _permdisp_metric_host.
 int permdisp_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                      const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
                      uint64_t seed, bool pairwise, epik_amd_permdisp* out, double* stat, double* group_mean, double* z, std::string& err,
-                     uint32_t metric = EPIK_AMD_DISTANCE_KR);
+                     uint32_t metric = EPIK_AMD_DISTANCE_KR, const uint32_t* strata = nullptr);
 
 /// num_terms in [1, 16], every kind 0 or 1, num_permutations in [1, 999 999], every label of a factor term below 32 or
 /// 0xffffffff (missing), no infinite value of a numeric term, and at most 64 columns as the rule counts them: 0, or
@@ -168,13 +171,14 @@ int model_arguments_valid(const uint32_t* kind, const uint32_t* labels, const do
 /// same bits.  The code behind epik_amd_cohort_model_kr_host.  0, or as model_arguments_valid.
 int model_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* kind, const uint32_t* labels,
                         const double* values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed, epik_amd_model_term* out,
-                        epik_amd_model_info* info, double* stat, uint8_t* aliased, std::string& err);
+                        epik_amd_model_info* info, double* stat, uint8_t* aliased, std::string& err,
+                        const uint32_t* strata = nullptr);
 /// The same from mass[S][N]: the matrix by distance_matrix first.  The code behind epik_amd_cohort_model_host and
 /// _model_metric_host.
 int model_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
                   const double* branch_length, const uint32_t* kind, const uint32_t* labels, const double* values, uint32_t num_terms,
                   uint32_t num_permutations, uint64_t seed, epik_amd_model_term* out, epik_amd_model_info* info, double* stat,
-                  uint8_t* aliased, std::string& err, uint32_t metric = EPIK_AMD_DISTANCE_KR);
+                  uint8_t* aliased, std::string& err, uint32_t metric = EPIK_AMD_DISTANCE_KR, const uint32_t* strata = nullptr);
 
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
@@ -349,6 +353,19 @@ std::string format_permdisp_tsv(const std::vector<cohort_sample>& samples, const
 std::string format_model_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, const cohort_design& design,
                              uint32_t num_permutations, uint64_t seed, const epik_amd_model_term* records,
                              const epik_amd_model_info& info, const uint8_t* aliased, uint32_t distance = EPIK_AMD_DISTANCE_KR);
+/// The strata of --cohort-strata FILE [--cohort-strata-column NAME]: FILE is a TSV read by the factor reader (the same errors,
+/// naming line and column, under the flag's name) without a cap on the distinct labels; `column` picks the column and may be
+/// empty only if FILE has one.  strata[S]: the label ids of that column by first appearance; *name: the column's name.  Throws
+/// std::runtime_error too for a column that FILE lacks, and for a sample of the list without a value, naming its line.
+std::vector<uint32_t> read_cohort_strata(const std::string& file, const std::string& column, const std::vector<cohort_sample>& samples,
+                                         std::string* name);
+/// `text`, a cohort_permanova, _permdisp, _edgetest or _model file, with <TAB>strata=NAME at the end of its first line (after
+/// distance=.. where that is there): what --cohort-strata makes of the four files.  An empty name leaves the text as it is.
+std::string with_strata_field(std::string text, const std::string& name);
+/// whether the labels of column c of labels[S][M] (`missing`: none) are constant inside every stratum among the samples with
+/// mass and a label: nothing can be permuted there
+bool constant_within_strata(const uint32_t* labels, size_t S, size_t M, size_t c, uint32_t missing, const uint64_t* totals,
+                            const uint32_t* strata);
 /// `text` into `filename` through `filename`.part, renamed when all of it is written
 void write_through_part(const std::string& filename, const std::string& text);
 

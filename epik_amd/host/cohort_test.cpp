@@ -80,6 +80,16 @@ void write_array(std::ofstream& out, const T* data, size_t count)
     out.write(reinterpret_cast<const char*>(data), (std::streamsize)(count * sizeof(T)));
 }
 
+// the strata of the `*-strata` modes: uint32 [S], any value an id
+std::vector<uint32_t> read_strata(const char* path, uint64_t S)
+{
+    std::ifstream in(path, std::ios::binary | std::ios::ate);
+    if (!in) throw std::runtime_error(std::string("cannot open ") + path);
+    if ((uint64_t)in.tellg() != S * sizeof(uint32_t)) throw std::runtime_error("the strata file is not uint32 [S]");
+    in.seekg(0);
+    return read_array<uint32_t>(in, S);
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -328,8 +338,10 @@ int main(int argc, char** argv)
             return 0;
         }
         if ((argc == 8 && (std::strcmp(argv[1], "permanova") == 0 || std::strcmp(argv[1], "permdisp") == 0)) ||
-            (argc == 9 && (std::strcmp(argv[1], "permanova-tsv") == 0 || std::strcmp(argv[1], "permdisp-tsv") == 0))) {
-            const bool tsv = argc == 9, disp = std::strncmp(argv[1], "permdisp", 8) == 0;
+            (argc == 9 && (std::strcmp(argv[1], "permanova-tsv") == 0 || std::strcmp(argv[1], "permdisp-tsv") == 0)) ||
+            (argc == 9 && (std::strcmp(argv[1], "permanova-strata") == 0 || std::strcmp(argv[1], "permdisp-strata") == 0))) {
+            const bool stratified = std::strstr(argv[1], "-strata") != nullptr;
+            const bool tsv = argc == 9 && !stratified, disp = std::strncmp(argv[1], "permdisp", 8) == 0;
             std::ifstream in(argv[3], std::ios::binary);
             if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
             const auto head = read_array<uint64_t>(in, 2);
@@ -341,7 +353,9 @@ int main(int argc, char** argv)
             const uint32_t P = (uint32_t)std::strtoul(argv[argc - 3], nullptr, 10);
             const uint64_t seed = std::strtoull(argv[argc - 2], nullptr, 10);
             const bool pairwise = std::strcmp(argv[argc - 1], "0") != 0;
-            std::vector<uint32_t> labels;
+            std::vector<uint32_t> labels, strata;
+            if (stratified) strata = read_strata(argv[5], S);
+            const uint32_t* within = stratified ? strata.data() : nullptr;
             epik_amd::cohort_factors factors;
             std::vector<epik_amd::cohort_sample> samples;
             if (tsv) {
@@ -372,7 +386,7 @@ int main(int argc, char** argv)
                 std::string err;
                 if (epik_amd::permdisp_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), lengths.data(), labels.data(),
                                                (uint32_t)M, P, seed, pairwise, records.data(), tsv ? nullptr : stat.data(),
-                                               group_mean.data(), z.data(), err) != 0)
+                                               group_mean.data(), z.data(), err, EPIK_AMD_DISTANCE_KR, within) != 0)
                     throw std::runtime_error(err);
                 if (tsv) {
                     std::vector<uint64_t> totals(S, 0);
@@ -396,7 +410,7 @@ int main(int argc, char** argv)
             std::string err;
             if (epik_amd::permanova_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), lengths.data(), labels.data(),
                                             (uint32_t)M, P, seed, pairwise, records.data(), tsv ? nullptr : ssw.data(), group_ss.data(),
-                                            err) != 0)
+                                            err, EPIK_AMD_DISTANCE_KR, within) != 0)
                 throw std::runtime_error(err);
             if (tsv) {
                 std::vector<uint64_t> totals(S, 0);
@@ -414,8 +428,9 @@ int main(int argc, char** argv)
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }
-        if ((argc == 7 && std::strcmp(argv[1], "edgetest") == 0) || (argc == 8 && std::strcmp(argv[1], "edgetest-tsv") == 0)) {
-            const bool tsv = argc == 8;
+        if ((argc == 7 && std::strcmp(argv[1], "edgetest") == 0) || (argc == 8 && std::strcmp(argv[1], "edgetest-tsv") == 0) ||
+            (argc == 8 && std::strcmp(argv[1], "edgetest-strata") == 0)) {
+            const bool stratified = std::strcmp(argv[1], "edgetest-strata") == 0, tsv = argc == 8 && !stratified;
             std::ifstream in(argv[3], std::ios::binary);
             if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
             const auto head = read_array<uint64_t>(in, 2);
@@ -425,7 +440,8 @@ int main(int argc, char** argv)
             const auto first = read_array<uint32_t>(in, N);
             const uint32_t P = (uint32_t)std::strtoul(argv[argc - 2], nullptr, 10);
             const uint64_t seed = std::strtoull(argv[argc - 1], nullptr, 10);
-            std::vector<uint32_t> labels;
+            std::vector<uint32_t> labels, strata;
+            if (stratified) strata = read_strata(argv[5], S);
             epik_amd::cohort_factors factors;
             std::vector<epik_amd::cohort_sample> samples;
             if (tsv) {
@@ -452,7 +468,8 @@ int main(int argc, char** argv)
             std::vector<double> stat(tsv ? 0 : M * EPIK_AMD_EDGETEST_FAMILIES * N * row), max(tsv ? 0 : M * EPIK_AMD_EDGETEST_FAMILIES * row);
             std::string err;
             if (epik_amd::edgetest_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), labels.data(), (uint32_t)M, P, seed,
-                                           records.data(), tsv ? nullptr : stat.data(), tsv ? nullptr : max.data(), err) != 0)
+                                           records.data(), tsv ? nullptr : stat.data(), tsv ? nullptr : max.data(), err,
+                                           stratified ? strata.data() : nullptr) != 0)
                 throw std::runtime_error(err);
             if (tsv) {
                 std::vector<uint64_t> totals(S, 0);
@@ -504,7 +521,8 @@ int main(int argc, char** argv)
                                                                              aliased.data()));
             return 0;
         }
-        if (argc == 7 && std::strcmp(argv[1], "model") == 0) {
+        if ((argc == 7 && std::strcmp(argv[1], "model") == 0) || (argc == 8 && std::strcmp(argv[1], "model-strata") == 0)) {
+            const bool stratified = argc == 8;
             std::ifstream in(argv[3], std::ios::binary);
             if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
             const auto head = read_array<uint64_t>(in, 2);
@@ -513,8 +531,10 @@ int main(int argc, char** argv)
             const auto cells = read_array<uint64_t>(in, S * N);
             const auto first = read_array<uint32_t>(in, N);
             const auto lengths = read_array<double>(in, N);
-            const uint32_t P = (uint32_t)std::strtoul(argv[5], nullptr, 10);
-            const uint64_t seed = std::strtoull(argv[6], nullptr, 10);
+            const uint32_t P = (uint32_t)std::strtoul(argv[argc - 2], nullptr, 10);
+            const uint64_t seed = std::strtoull(argv[argc - 1], nullptr, 10);
+            std::vector<uint32_t> strata;
+            if (stratified) strata = read_strata(argv[5], S);
             std::ifstream design(argv[4], std::ios::binary);
             if (!design) throw std::runtime_error(std::string("cannot open ") + argv[4]);
             const uint64_t T = read_array<uint64_t>(design, 1)[0];
@@ -529,7 +549,8 @@ int main(int argc, char** argv)
             std::vector<uint8_t> aliased(EPIK_AMD_MODEL_MAX_COLUMNS);
             std::string err;
             if (epik_amd::model_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), lengths.data(), kind.data(), labels.data(),
-                                        values.data(), (uint32_t)T, P, seed, records.data(), &info, stat.data(), aliased.data(), err) != 0)
+                                        values.data(), (uint32_t)T, P, seed, records.data(), &info, stat.data(), aliased.data(), err,
+                                        EPIK_AMD_DISTANCE_KR, stratified ? strata.data() : nullptr) != 0)
                 throw std::runtime_error(err);
             std::ofstream out(argv[2], std::ios::binary);
             write_array(out, records.data(), records.size());
@@ -537,6 +558,28 @@ int main(int argc, char** argv)
             write_array(out, stat.data(), stat.size());
             write_array(out, aliased.data(), aliased.size());
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
+        // the drivers' strata reader and header field: strata-read <out.bin> <names.txt> <strata.tsv> <column or -> writes
+        // strata[S] and, after them, the column's name; strata-field <out.tsv> <in.tsv> <NAME> the file with the field
+        if (argc == 6 && std::strcmp(argv[1], "strata-read") == 0) {
+            std::vector<epik_amd::cohort_sample> samples;
+            std::ifstream names(argv[3]);
+            if (!names) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            for (std::string line; std::getline(names, line);) samples.push_back({line, ""});
+            std::string name;
+            const auto strata = epik_amd::read_cohort_strata(argv[4], std::strcmp(argv[5], "-") == 0 ? "" : argv[5], samples, &name);
+            std::ofstream out(argv[2], std::ios::binary);
+            write_array(out, strata.data(), strata.size());
+            out << name;
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
+        if (argc == 5 && std::strcmp(argv[1], "strata-field") == 0) {
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const std::string text((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            epik_amd::write_through_part(argv[2], epik_amd::with_strata_field(text, argv[4]));
             return 0;
         }
         std::cerr << "usage: cohort_test add <out.bin> <in.bin>... | kr <out.bin> <in.bin> | squash <out.bin> <in.bin> | "
@@ -549,7 +592,11 @@ int main(int argc, char** argv)
                      "edgetest <out.bin> <in.bin> <labels.bin> <P> <seed> | "
                      "edgetest-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed> | "
                      "model <out.bin> <in.bin> <design.bin> <P> <seed> | "
-                     "model-tsv <out.tsv> <in.bin> <names.txt> <design.tsv> <terms> <P> <seed>\n";
+                     "model-tsv <out.tsv> <in.bin> <names.txt> <design.tsv> <terms> <P> <seed> | "
+                     "permanova-strata | permdisp-strata <out.bin> <in.bin> <labels.bin> <strata.bin> <P> <seed> <pairwise> | "
+                     "edgetest-strata <out.bin> <in.bin> <labels.bin> <strata.bin> <P> <seed> | "
+                     "model-strata <out.bin> <in.bin> <design.bin> <strata.bin> <P> <seed> | "
+                     "strata-read <out.bin> <names.txt> <strata.tsv> <column or -> | strata-field <out.tsv> <in.tsv> <NAME>\n";
         return 2;
     } catch (const std::exception& error) {
         std::cerr << "Error: " << error.what() << std::endl;

@@ -35,6 +35,7 @@
 #include <limits>
 #include <map>
 #include <memory>
+#include <set>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -291,6 +292,11 @@ const char* kHelp =
     "                          adjustment (Westfall & Young 1993), on the device; writes cohort_edgetest_<list>.tsv\n"
     "      --cohort-edge-test-permutations arg  With --cohort-edge-test: the number of permutations in [1, 999999] (default: 999)\n"
     "      --cohort-edge-test-seed arg  With --cohort-edge-test: the seed of the permutations, a uint64 (default: 1)\n"
+    "      --cohort-strata arg  With --cohort-permanova, --cohort-permdisp, --cohort-edge-test or --cohort-model: permute within\n"
+    "                          strata only (a subject sampled several times, a batch): a column of the TSV file arg (as\n"
+    "                          --cohort-permanova's; any number of labels) gives every sample of the list its stratum; all of\n"
+    "                          those tests of the run use it, and their files' first line ends in <TAB>strata=NAME\n"
+    "      --cohort-strata-column arg  With --cohort-strata: the column of its file; required when the file has several\n"
     "  -h, --help              Print usage\n";
 
 struct options {
@@ -619,6 +625,12 @@ int main(int argc, char** argv)
                 throw std::runtime_error("--cohort-distance must be kr, unweighted, weighted or generalized, not '" + name + "'");
         }
         const bool with_edgetest = parsed.has("cohort-edge-test");
+        const bool with_strata = parsed.has("cohort-strata");
+        if (parsed.has("cohort-strata-column") && !with_strata)
+            throw std::runtime_error("--cohort-strata-column needs --cohort-strata (it names a column of that file)");
+        if (with_strata && !(with_permanova || with_permdisp || with_edgetest || with_model))
+            throw std::runtime_error("--cohort-strata needs --cohort-permanova, --cohort-permdisp, --cohort-edge-test or --cohort-model "
+                                     "(the tests that permute samples)");
         if (with_edgetest && !with_cohort)
             throw std::runtime_error("--cohort-edge-test needs --cohort (it tests the branches between the groups of the samples of the list)");
         for (const char* dependent : {"cohort-edge-test-permutations", "cohort-edge-test-seed"})
@@ -693,6 +705,15 @@ int main(int argc, char** argv)
             metadata = epik_amd::read_cohort_metadata(parsed.require("cohort-correlation"), cohort_samples);
             std::cout << "Cohort metadata: " << metadata.columns.size() << " columns, " << metadata.skipped
                       << " lines of samples that are not in the list skipped" << std::endl;
+        }
+        // --cohort-strata: the strata read by the factor reader, every error named by its line, before the database or a device is
+        std::vector<uint32_t> strata;
+        std::string strata_name;
+        if (with_strata) {
+            strata = epik_amd::read_cohort_strata(parsed.require("cohort-strata"), parsed.get("cohort-strata-column", ""), cohort_samples,
+                                                  &strata_name);
+            std::cout << "Cohort strata: column " << strata_name << ", " << std::set<uint32_t>(strata.begin(), strata.end()).size()
+                      << " strata of " << strata.size() << " samples" << std::endl;
         }
         // --cohort-permanova: the factors read, and every error of it named by its line, before the database or a device is
         epik_amd::cohort_factors factors;
@@ -1142,19 +1163,31 @@ int main(int argc, char** argv)
             epik_amd::placer::cohort_permanova permanova;
             permanova.labels = factors.labels.data(), permanova.num_columns = (uint32_t)factors.columns.size();
             permanova.num_permutations = permanova_permutations, permanova.seed = permanova_seed, permanova.pairwise = permanova_pairwise;
+            const uint32_t* within = with_strata ? strata.data() : nullptr;
+            permanova.strata = within;
             epik_amd::placer::cohort_edgetest edgetest;
             edgetest.labels = edge_factors.labels.data(), edgetest.num_columns = (uint32_t)edge_factors.columns.size();
-            edgetest.num_permutations = edgetest_permutations, edgetest.seed = edgetest_seed;
+            edgetest.num_permutations = edgetest_permutations, edgetest.seed = edgetest_seed, edgetest.strata = within;
             epik_amd::placer::cohort_pcoa pcoa;
             pcoa.num_components = pcoa_components;
             epik_amd::placer::cohort_permdisp permdisp;
             permdisp.labels = disp_factors.labels.data(), permdisp.num_columns = (uint32_t)disp_factors.columns.size();
             permdisp.num_permutations = permdisp_permutations, permdisp.seed = permdisp_seed, permdisp.pairwise = permdisp_pairwise;
+            permdisp.strata = within;
             epik_amd::placer::cohort_unifrac unifrac;
             unifrac.metrics = unifrac_metrics, unifrac.distance = cohort_distance;
             epik_amd::placer::cohort_model model;
             model.kind = design.kind.data(), model.labels = design.labels.data(), model.values = design.values.data();
             model.num_terms = (uint32_t)design.terms.size(), model.num_permutations = model_permutations, model.seed = model_seed;
+            model.strata = within;
+            // a factor that is constant inside every stratum of its used samples: no permutation changes anything, p = 1
+            const auto warn_nested = [&](const char* flag, const std::vector<std::string>& columns, const uint32_t* labels, uint32_t missing,
+                                         const std::vector<uint64_t>& mass_of) {
+                for (size_t c = 0; with_strata && c < columns.size(); ++c)
+                    if (epik_amd::constant_within_strata(labels, cohort_samples.size(), columns.size(), c, missing, mass_of.data(), within))
+                        std::cout << "Warning: " << flag << ": the column " << columns[c] << " is constant inside every stratum of "
+                                  << strata_name << ": no permutation can change it, p = 1" << std::endl;
+            };
             placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
                                with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr, with_kmeans ? &kmeans : nullptr,
                                with_alpha || with_rarefy ? &diversity : nullptr, with_correlation || with_dispersion ? &edges : nullptr,
@@ -1216,32 +1249,41 @@ int main(int argc, char** argv)
                 std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
                 for (size_t s = 0; s < mass_of.size(); ++s)
                     for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
-                epik_amd::write_through_part(cohort_permanova_filename,
-                                             epik_amd::format_permanova_tsv(cohort_samples, mass_of.data(), factors.columns, factors.names,
-                                                                            factors.labels.data(), permanova_permutations, permanova_seed,
-                                                                            permanova_pairwise, permanova.records.data(),
-                                                                            permanova.group_ss.data(), cohort_distance));
+                epik_amd::write_through_part(
+                    cohort_permanova_filename,
+                    epik_amd::with_strata_field(epik_amd::format_permanova_tsv(cohort_samples, mass_of.data(), factors.columns, factors.names,
+                                                                               factors.labels.data(), permanova_permutations, permanova_seed,
+                                                                               permanova_pairwise, permanova.records.data(),
+                                                                               permanova.group_ss.data(), cohort_distance),
+                                                strata_name));
+                warn_nested("--cohort-permanova", factors.columns, factors.labels.data(), EPIK_AMD_PERMANOVA_MISSING, mass_of);
             }
             if (with_edgetest) {
                 std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
                 for (size_t s = 0; s < mass_of.size(); ++s)
                     for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
-                epik_amd::write_through_part(cohort_edgetest_filename,
-                                             epik_amd::format_edgetest_tsv(cohort_samples, mass_of.data(), edge_factors.columns,
-                                                                           edge_factors.names, edge_factors.labels.data(),
-                                                                           (uint32_t)cohort.num_branches, edgetest_permutations,
-                                                                           edgetest_seed, edgetest.records.data()));
+                epik_amd::write_through_part(
+                    cohort_edgetest_filename,
+                    epik_amd::with_strata_field(epik_amd::format_edgetest_tsv(cohort_samples, mass_of.data(), edge_factors.columns,
+                                                                              edge_factors.names, edge_factors.labels.data(),
+                                                                              (uint32_t)cohort.num_branches, edgetest_permutations,
+                                                                              edgetest_seed, edgetest.records.data()),
+                                                strata_name));
+                warn_nested("--cohort-edge-test", edge_factors.columns, edge_factors.labels.data(), EPIK_AMD_EDGETEST_MISSING, mass_of);
             }
             if (with_permdisp) {
                 std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
                 for (size_t s = 0; s < mass_of.size(); ++s)
                     for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
-                epik_amd::write_through_part(cohort_permdisp_filename,
-                                             epik_amd::format_permdisp_tsv(cohort_samples, mass_of.data(), disp_factors.columns,
-                                                                           disp_factors.names, disp_factors.labels.data(),
-                                                                           permdisp_permutations, permdisp_seed, permdisp_pairwise,
-                                                                           permdisp.records.data(), permdisp.group_mean.data(),
-                                                                           permdisp.z.data(), cohort_distance));
+                epik_amd::write_through_part(
+                    cohort_permdisp_filename,
+                    epik_amd::with_strata_field(epik_amd::format_permdisp_tsv(cohort_samples, mass_of.data(), disp_factors.columns,
+                                                                              disp_factors.names, disp_factors.labels.data(),
+                                                                              permdisp_permutations, permdisp_seed, permdisp_pairwise,
+                                                                              permdisp.records.data(), permdisp.group_mean.data(),
+                                                                              permdisp.z.data(), cohort_distance),
+                                                strata_name));
+                warn_nested("--cohort-permdisp", disp_factors.columns, disp_factors.labels.data(), EPIK_AMD_PERMDISP_MISSING, mass_of);
                 const size_t slots = permdisp.records.size() / disp_factors.columns.size();
                 for (size_t c = 0; c < disp_factors.columns.size(); ++c) permdisp_clipped += permdisp.records[c * slots].clipped;
             }
@@ -1249,10 +1291,24 @@ int main(int argc, char** argv)
                 std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
                 for (size_t s = 0; s < mass_of.size(); ++s)
                     for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
-                epik_amd::write_through_part(cohort_model_filename,
-                                             epik_amd::format_model_tsv(cohort_samples, mass_of.data(), design, model_permutations, model_seed,
-                                                                        model.records.data(), model.info, model.aliased.data(),
-                                                                        cohort_distance));
+                epik_amd::write_through_part(
+                    cohort_model_filename,
+                    epik_amd::with_strata_field(epik_amd::format_model_tsv(cohort_samples, mass_of.data(), design, model_permutations,
+                                                                           model_seed, model.records.data(), model.info,
+                                                                           model.aliased.data(), cohort_distance),
+                                                strata_name));
+                // (the model's used samples are the complete cases)
+                const size_t T = design.terms.size();
+                std::vector<uint64_t> complete(mass_of);
+                for (size_t s = 0; s < complete.size(); ++s)
+                    for (size_t t = 0; t < T; ++t)
+                        if (design.kind[t] ? std::isnan(design.values[s * T + t]) : design.labels[s * T + t] == EPIK_AMD_MODEL_MISSING)
+                            complete[s] = 0;
+                for (size_t t = 0; with_strata && t < T; ++t)
+                    if (!design.kind[t] && epik_amd::constant_within_strata(design.labels.data(), complete.size(), T, t,
+                                                                            EPIK_AMD_MODEL_MISSING, complete.data(), within))
+                        std::cout << "Warning: --cohort-model: the term " << design.terms[t] << " is constant inside every stratum of "
+                                  << strata_name << ": no permutation changes its sum of squares" << std::endl;
                 for (const uint8_t byte : model.aliased) model_aliased += byte;
             }
             if (with_pcoa) {

@@ -47,6 +47,10 @@
 #pragma weak epik_amd_cohort_pcoa_metric
 #pragma weak epik_amd_cohort_permdisp_metric
 #pragma weak epik_amd_cohort_model_metric
+#pragma weak epik_amd_cohort_permanova_strata
+#pragma weak epik_amd_cohort_permdisp_strata
+#pragma weak epik_amd_cohort_edgetest_strata
+#pragma weak epik_amd_cohort_model_strata
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -306,6 +310,10 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
                          cohort_model* model)
 {
     if (model && !&epik_amd_cohort_model_metric) throw std::runtime_error("GPU placer: this libepik_amd has no sequential model");
+    if (((permanova && permanova->strata) || (permdisp && permdisp->strata) || (edgetest && edgetest->strata) || (model && model->strata)) &&
+        (!&epik_amd_cohort_permanova_strata || !&epik_amd_cohort_permdisp_strata || !&epik_amd_cohort_edgetest_strata ||
+         !&epik_amd_cohort_model_strata))
+        throw std::runtime_error("GPU placer: this libepik_amd has no permutations within strata");
     const uint32_t distance = unifrac ? unifrac->distance : EPIK_AMD_DISTANCE_KR;
     if (unifrac && (!&epik_amd_cohort_unifrac || !&epik_amd_cohort_permanova_metric || !&epik_amd_cohort_pcoa_metric ||
                     !&epik_amd_cohort_permdisp_metric))
@@ -390,7 +398,11 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
         const size_t slots = 1 + (permanova->pairwise ? EPIK_AMD_PERMANOVA_PAIR_SLOTS : 0);
         permanova->records.assign(permanova->num_columns * slots, epik_amd_permanova{});
         permanova->group_ss.assign((size_t)permanova->num_columns * EPIK_AMD_PERMANOVA_MAX_GROUPS, 0.0);
-        rc = distance != EPIK_AMD_DISTANCE_KR
+        rc = permanova->strata
+                 ? epik_amd_cohort_permanova_strata(_cohorts[0], tree, length.data(), distance, permanova->labels, permanova->num_columns,
+                                                    permanova->num_permutations, permanova->seed, permanova->pairwise ? 1 : 0,
+                                                    permanova->records.data(), nullptr, permanova->group_ss.data(), permanova->strata)
+             : distance != EPIK_AMD_DISTANCE_KR
                  ? epik_amd_cohort_permanova_metric(_cohorts[0], tree, length.data(), distance, permanova->labels, permanova->num_columns,
                                                     permanova->num_permutations, permanova->seed, permanova->pairwise ? 1 : 0,
                                                     permanova->records.data(), nullptr, permanova->group_ss.data())
@@ -400,8 +412,11 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
     }
     if (rc == EPIK_AMD_OK && edgetest) {
         edgetest->records.assign((size_t)edgetest->num_columns * parent.size(), epik_amd_edgetest{});
-        rc = epik_amd_cohort_edgetest(_cohorts[0], tree, edgetest->labels, edgetest->num_columns, edgetest->num_permutations,
-                                      edgetest->seed, edgetest->records.data(), nullptr, nullptr);
+        rc = edgetest->strata
+                 ? epik_amd_cohort_edgetest_strata(_cohorts[0], tree, edgetest->labels, edgetest->num_columns, edgetest->num_permutations,
+                                                   edgetest->seed, edgetest->records.data(), nullptr, nullptr, edgetest->strata)
+                 : epik_amd_cohort_edgetest(_cohorts[0], tree, edgetest->labels, edgetest->num_columns, edgetest->num_permutations,
+                                            edgetest->seed, edgetest->records.data(), nullptr, nullptr);
     }
     if (rc == EPIK_AMD_OK && pcoa) {
         pcoa->mu.assign(_cohort_samples, 0.0), pcoa->coord.assign((size_t)_cohort_samples * pcoa->num_components, 0.0);
@@ -416,7 +431,12 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
         permdisp->records.assign(permdisp->num_columns * slots, epik_amd_permdisp{});
         permdisp->group_mean.assign((size_t)permdisp->num_columns * EPIK_AMD_PERMDISP_MAX_GROUPS, 0.0);
         permdisp->z.assign((size_t)permdisp->num_columns * _cohort_samples, 0.0);
-        rc = distance != EPIK_AMD_DISTANCE_KR
+        rc = permdisp->strata
+                 ? epik_amd_cohort_permdisp_strata(_cohorts[0], tree, length.data(), distance, permdisp->labels, permdisp->num_columns,
+                                                   permdisp->num_permutations, permdisp->seed, permdisp->pairwise ? 1 : 0,
+                                                   permdisp->records.data(), nullptr, permdisp->group_mean.data(), permdisp->z.data(),
+                                                   permdisp->strata)
+             : distance != EPIK_AMD_DISTANCE_KR
                  ? epik_amd_cohort_permdisp_metric(_cohorts[0], tree, length.data(), distance, permdisp->labels, permdisp->num_columns,
                                                    permdisp->num_permutations, permdisp->seed, permdisp->pairwise ? 1 : 0,
                                                    permdisp->records.data(), nullptr, permdisp->group_mean.data(), permdisp->z.data())
@@ -427,9 +447,13 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
     if (rc == EPIK_AMD_OK && model) {
         model->records.assign((size_t)model->num_terms + 1, epik_amd_model_term{});
         model->aliased.assign(EPIK_AMD_MODEL_MAX_COLUMNS, 0);
-        rc = epik_amd_cohort_model_metric(_cohorts[0], tree, length.data(), distance, model->kind, model->labels, model->values,
-                                          model->num_terms, model->num_permutations, model->seed, model->records.data(), &model->info,
-                                          nullptr, model->aliased.data());
+        rc = model->strata
+                 ? epik_amd_cohort_model_strata(_cohorts[0], tree, length.data(), distance, model->kind, model->labels, model->values,
+                                                model->num_terms, model->num_permutations, model->seed, model->records.data(),
+                                                &model->info, nullptr, model->aliased.data(), model->strata)
+                 : epik_amd_cohort_model_metric(_cohorts[0], tree, length.data(), distance, model->kind, model->labels, model->values,
+                                                model->num_terms, model->num_permutations, model->seed, model->records.data(),
+                                                &model->info, nullptr, model->aliased.data());
     }
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);

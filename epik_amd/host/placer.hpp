@@ -212,6 +212,7 @@ public:
         uint32_t num_columns = 0, num_permutations = 999;
         uint64_t seed = 1;
         bool pairwise = false;
+        const uint32_t* strata = nullptr;  ///< --cohort-strata: strata[S], the permutations stay within them; or null
         std::vector<epik_amd_permanova> records;
         std::vector<double> group_ss;
     };
@@ -221,6 +222,7 @@ public:
         const uint32_t* labels = nullptr;
         uint32_t num_columns = 0, num_permutations = 999;
         uint64_t seed = 1;
+        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
         std::vector<epik_amd_edgetest> records;
     };
     /// With `pcoa` (--cohort-pcoa): the principal coordinates of the samples over the KR distances; num_components is K on
@@ -237,6 +239,7 @@ public:
         uint32_t num_columns = 0, num_permutations = 999;
         uint64_t seed = 1;
         bool pairwise = false;
+        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
         std::vector<epik_amd_permdisp> records;
         std::vector<double> group_mean, z;
     };
@@ -248,6 +251,7 @@ public:
         const double* values = nullptr;
         uint32_t num_terms = 0, num_permutations = 999;
         uint64_t seed = 1;
+        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
         std::vector<epik_amd_model_term> records;
         epik_amd_model_info info{};
         std::vector<uint8_t> aliased;

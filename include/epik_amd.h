@@ -896,6 +896,23 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *     undefined or a slot without a pair.  group_ss[M][256], where asked for: W_g / (double)n_g of lambda for g < G of a
  *     column whose test is defined, NA otherwise.  Every cell of every output is written.
  *
+ * Strata (blocked permutations; `strata =`, `how(blocks =)`): permute within strata only.  One rule for the four permutation
+ *   tests (PERMANOVA, PERMDISP, the edge test, the sequential model), for a cohort whose samples are not exchangeable as a
+ *   whole: a subject sampled several times, samples that come in batches.  strata[S], uint32, by sample: any value is a
+ *   stratum id, there is no "missing" one.  A test has the positions 0 .. n - 1, its used samples in list order, as without
+ *   strata; h_i is the stratum of the sample of position i, and key_p(i) is the PERMANOVA rule's.
+ *       w_p(i) = the number of positions j with h_j == h_i whose (key_p(j), j) is smaller than (key_p(i), i),
+ *       member(h, w) = the w-th position, ascending, among the positions of stratum h,
+ *       sigma_p(i) = member(h_i, w_p(i)),       sigma_0 = the identity.
+ *     Wherever a test uses rank_p(i) it uses sigma_p(i): mu^p_i = lambda_{sigma_p(i)} for PERMANOVA, PERMDISP and the edge
+ *     test (a pairwise sub-list has its own positions, and the strata of their samples), and the model's row of Q.  sigma_p is
+ *     a bijection that keeps every position in its stratum, so the sizes of the groups do not change and the labels of a
+ *     stratum are the same multiset under every p.  With one stratum sigma_p = rank_p: the entries without strata, and strata
+ *     == NULL, are this rule with h == 0 everywhere, and their bits are what they were.  Only the equality of ids enters:
+ *     renumbering the strata changes no bit.  A factor that is constant inside every stratum cannot be permuted: every
+ *     labelling is lambda, so every permuted statistic is the observed one and p = 1 (PERMDISP's permuted statistic is eta_r
+ *     of the residuals, not eta2 of z: there every eta_r(mu^p) is eta_r(lambda)).
+ *
  * Principal coordinates (Gower 1966; classical scaling, `cmdscale`, `pcoa`) of the cohort's samples over the KR distances:
  *   the ordination in which beta diversity is drawn.  From the matrix KR[S][S] of the KR rule, T_s and K in [1, 64].  The KR
  *   distance on a tree is not Euclidean, so the doubly centred matrix may be indefinite: the negative eigenvalues are
@@ -1317,6 +1334,24 @@ int epik_amd_cohort_permanova_metric_host(const uint64_t *mass, uint32_t num_sam
 int epik_amd_cohort_permanova_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
                                       uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                       epik_amd_permanova *out, double *ssw, double *group_ss);
+/* The same with the strata rule: the _device, _metric, _metric_host and _kr_host entries plus strata[S] (host memory; NULL: the
+ * bytes of the entry without it).  Refused as their siblings refuse.  Likewise for PERMDISP, the model and the edge test below. */
+int epik_amd_cohort_permanova_strata_device(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, uint32_t num_columns,
+                                            uint32_t num_permutations, uint64_t seed, int pairwise, void *d_out, void *d_ssw,
+                                            void *d_group_ss, void *stream, const uint32_t *strata);
+int epik_amd_cohort_permanova_strata(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                                     uint32_t metric, const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations,
+                                     uint64_t seed, int pairwise, epik_amd_permanova *out, double *ssw, double *group_ss,
+                                     const uint32_t *strata);
+int epik_amd_cohort_permanova_strata_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches,
+                                          const uint32_t *first, const double *branch_length, uint32_t metric,
+                                          const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
+                                          int pairwise, epik_amd_permanova *out, double *ssw, double *group_ss,
+                                          const uint32_t *strata);
+int epik_amd_cohort_permanova_strata_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples,
+                                             const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations,
+                                             uint64_t seed, int pairwise, epik_amd_permanova *out, double *ssw, double *group_ss,
+                                             const uint32_t *strata);
 typedef struct epik_amd_pcoa_info {
     uint32_t used, components; /* L, and K' = min(K, L) */
     uint32_t sweeps, converged;
@@ -1360,6 +1395,15 @@ int epik_amd_cohort_edgetest(epik_amd_cohort *cohort, const epik_amd_tree *tree,
 int epik_amd_cohort_edgetest_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
                                   const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
                                   epik_amd_edgetest *out, double *stat, double *max);
+int epik_amd_cohort_edgetest_strata_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels,
+                                           uint32_t num_columns, uint32_t num_permutations, uint64_t seed, void *d_out,
+                                           void *d_stat, void *d_max, void *stream, const uint32_t *strata);
+int epik_amd_cohort_edgetest_strata(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *labels,
+                                    uint32_t num_columns, uint32_t num_permutations, uint64_t seed, epik_amd_edgetest *out,
+                                    double *stat, double *max, const uint32_t *strata);
+int epik_amd_cohort_edgetest_strata_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                         const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
+                                         epik_amd_edgetest *out, double *stat, double *max, const uint32_t *strata);
 typedef struct epik_amd_permdisp {
     uint32_t used, groups; /* n and G of the test; 0, 0 for a slot without a pair */
     uint32_t clipped, pad; /* the positions of the test with z2 < 0; pad is 0 */
@@ -1392,6 +1436,22 @@ int epik_amd_cohort_permdisp_metric_host(const uint64_t *mass, uint32_t num_samp
 int epik_amd_cohort_permdisp_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
                                      uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
                                      epik_amd_permdisp *out, double *stat, double *group_mean, double *z);
+int epik_amd_cohort_permdisp_strata_device(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *labels, uint32_t num_columns,
+                                           uint32_t num_permutations, uint64_t seed, int pairwise, void *d_out, void *d_stat,
+                                           void *d_group_mean, void *d_z, void *stream, const uint32_t *strata);
+int epik_amd_cohort_permdisp_strata(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length,
+                                    uint32_t metric, const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations,
+                                    uint64_t seed, int pairwise, epik_amd_permdisp *out, double *stat, double *group_mean,
+                                    double *z, const uint32_t *strata);
+int epik_amd_cohort_permdisp_strata_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                         const double *branch_length, uint32_t metric, const uint32_t *labels,
+                                         uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
+                                         epik_amd_permdisp *out, double *stat, double *group_mean, double *z,
+                                         const uint32_t *strata);
+int epik_amd_cohort_permdisp_strata_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
+                                            uint32_t num_columns, uint32_t num_permutations, uint64_t seed, int pairwise,
+                                            epik_amd_permdisp *out, double *stat, double *group_mean, double *z,
+                                            const uint32_t *strata);
 typedef struct epik_amd_model_term {
     uint32_t df, columns; /* the accepted columns of the term and all of them; R and C for the whole model */
     uint64_t at_least;    /* #{p >= 1 : F(sigma_p) >= F(sigma_0)} */
@@ -1429,6 +1489,23 @@ int epik_amd_cohort_model_kr_host(const double *kr, const uint64_t *totals, uint
                                   const uint32_t *labels, const double *values, uint32_t num_terms, uint32_t num_permutations,
                                   uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info, double *stat,
                                   uint8_t *aliased);
+int epik_amd_cohort_model_strata_device(epik_amd_cohort *cohort, const void *d_kr, const uint32_t *kind, const uint32_t *labels,
+                                        const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed,
+                                        void *d_out, void *d_info, void *d_stat, void *d_aliased, void *stream,
+                                        const uint32_t *strata);
+int epik_amd_cohort_model_strata(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                                 const uint32_t *kind, const uint32_t *labels, const double *values, uint32_t num_terms,
+                                 uint32_t num_permutations, uint64_t seed, epik_amd_model_term *out, epik_amd_model_info *info,
+                                 double *stat, uint8_t *aliased, const uint32_t *strata);
+int epik_amd_cohort_model_strata_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                      const double *branch_length, uint32_t metric, const uint32_t *kind, const uint32_t *labels,
+                                      const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed,
+                                      epik_amd_model_term *out, epik_amd_model_info *info, double *stat, uint8_t *aliased,
+                                      const uint32_t *strata);
+int epik_amd_cohort_model_strata_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *kind,
+                                         const uint32_t *labels, const double *values, uint32_t num_terms,
+                                         uint32_t num_permutations, uint64_t seed, epik_amd_model_term *out,
+                                         epik_amd_model_info *info, double *stat, uint8_t *aliased, const uint32_t *strata);
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n);
 int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
