@@ -186,6 +186,29 @@ PLACE_OPTIONS = [
                                             help="With --cohort-model: the number of permutations [default: 999].")),
     (("--cohort-model-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
                                     help="With --cohort-model: the seed of the permutations, a uint64 [default: 1].")),
+    (("--cohort-mantel",), dict(type=click.Path(), default=None,
+                                help="With --cohort: a metadata TSV (as --cohort-correlation's): also test on the device, for every "
+                                     "column, whether the distance between samples grows with the difference in it (the Mantel "
+                                     "test), and write cohort_mantel_<list>.tsv.")),
+    (("--cohort-mantel-matrix",), dict(type=str, multiple=True,
+                                       help="With --cohort: NAME=FILE, a square TSV laid out as cohort_kr_<list>.tsv, as one more "
+                                            "side of the Mantel test; up to 8 times.")),
+    (("--cohort-mantel-method",), dict(type=click.Choice(("pearson", "spearman", "both")), default=None,
+                                       help="With the Mantel test: the correlation [default: pearson].")),
+    (("--cohort-mantel-partial",), dict(type=str, default=None,
+                                        help="With the Mantel test: the column or matrix NAME held fixed (the partial Mantel test).")),
+    (("--cohort-mantel-permutations",), dict(type=click.IntRange(1, 999999), default=None,
+                                             help="With the Mantel test: the number of permutations [default: 999].")),
+    (("--cohort-mantel-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
+                                     help="With the Mantel test: the seed of the permutations, a uint64 [default: 1].")),
+    (("--cohort-anosim",), dict(type=click.Path(), default=None,
+                                help="With --cohort: a TSV of factors (as --cohort-permanova's): also test on the device whether the "
+                                     "ranked distances between the groups of every column exceed those within (ANOSIM), and write "
+                                     "cohort_anosim_<list>.tsv.")),
+    (("--cohort-anosim-permutations",), dict(type=click.IntRange(1, 999999), default=None,
+                                             help="With --cohort-anosim: the number of permutations [default: 999].")),
+    (("--cohort-anosim-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
+                                     help="With --cohort-anosim: the seed of the permutations, a uint64 [default: 1].")),
     (("--cohort-strata",), dict(type=click.Path(), default=None,
                                 help="With --cohort-permanova, --cohort-permdisp, --cohort-edge-test or --cohort-model: a TSV (laid "
                                      "out as --cohort-permanova's, any number of labels) whose column gives every sample its "
@@ -238,7 +261,26 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                    cohort_pcoa=False, cohort_pcoa_components=None, cohort_permdisp=None, cohort_permdisp_permutations=None,
                    cohort_permdisp_seed=None, cohort_permdisp_pairwise=False, cohort_unifrac=None, cohort_distance=None,
                    cohort_model=None, cohort_model_terms=None, cohort_model_permutations=None, cohort_model_seed=None,
-                   cohort_strata=None, cohort_strata_column=None):
+                   cohort_strata=None, cohort_strata_column=None, cohort_mantel=None, cohort_mantel_matrix=(),
+                   cohort_mantel_method=None, cohort_mantel_partial=None, cohort_mantel_permutations=None, cohort_mantel_seed=None,
+                   cohort_anosim=None, cohort_anosim_permutations=None, cohort_anosim_seed=None):
+    with_mantel = cohort_mantel is not None or len(cohort_mantel_matrix) > 0
+    for flag, given in (("--cohort-mantel", cohort_mantel is not None), ("--cohort-mantel-matrix", len(cohort_mantel_matrix) > 0),
+                        ("--cohort-anosim", cohort_anosim is not None)):
+        if given and not cohort:
+            raise click.UsageError(f"{flag} needs --cohort")
+    for flag, given in (("--cohort-mantel-method", cohort_mantel_method is not None),
+                        ("--cohort-mantel-partial", cohort_mantel_partial is not None),
+                        ("--cohort-mantel-permutations", cohort_mantel_permutations is not None),
+                        ("--cohort-mantel-seed", cohort_mantel_seed is not None)):
+        if given and not with_mantel:
+            raise click.UsageError(f"{flag} needs --cohort-mantel or --cohort-mantel-matrix")
+    for flag, given in (("--cohort-anosim-permutations", cohort_anosim_permutations is not None),
+                        ("--cohort-anosim-seed", cohort_anosim_seed is not None)):
+        if given and cohort_anosim is None:
+            raise click.UsageError(f"{flag} needs --cohort-anosim")
+    if len(cohort_mantel_matrix) > 8:
+        raise click.UsageError("--cohort-mantel-matrix may be given 8 times at the most")
     if taxonomy_mass is not None and taxonomy is None:
         raise click.UsageError("--taxonomy-mass needs --taxonomy")
     if taxonomy_per_read and taxonomy is None:
@@ -310,7 +352,7 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
     if cohort_strata_column is not None and cohort_strata is None:
         raise click.UsageError("--cohort-strata-column needs --cohort-strata")
     if cohort_strata is not None and cohort_permanova is None and cohort_permdisp is None and cohort_edge_test is None \
-            and cohort_model is None:
+            and cohort_model is None and not with_mantel and cohort_anosim is None:
         raise click.UsageError("--cohort-strata needs --cohort-permanova, --cohort-permdisp, --cohort-edge-test or --cohort-model")
     if cohort_pcoa and not cohort:
         raise click.UsageError("--cohort-pcoa needs --cohort")
@@ -330,7 +372,8 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
     if cohort_distance is not None:
         if cohort_distance not in COHORT_DISTANCES:
             raise click.UsageError(f"--cohort-distance must be kr, unweighted, weighted or generalized, not '{cohort_distance}'")
-        if cohort_permanova is None and not cohort_pcoa and cohort_permdisp is None and cohort_model is None:
+        if cohort_permanova is None and not cohort_pcoa and cohort_permdisp is None and cohort_model is None and not with_mantel \
+                and cohort_anosim is None:
             raise click.UsageError("--cohort-distance needs --cohort-permanova, --cohort-pcoa or --cohort-permdisp")
     if cohort:
         for flag, given in (("--mates", mates is not None), ("--profile", profile), ("--profile-only", profile_only),
@@ -405,6 +448,19 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
             argv += ["--cohort-permdisp-seed", str(int(cohort_permdisp_seed))]
         if cohort_permdisp_pairwise:
             argv += ["--cohort-permdisp-pairwise"]
+    if cohort_mantel is not None:
+        argv += ["--cohort-mantel", str(cohort_mantel)]
+    for matrix in cohort_mantel_matrix:
+        argv += ["--cohort-mantel-matrix", str(matrix)]
+    for flag, value in (("--cohort-mantel-method", cohort_mantel_method), ("--cohort-mantel-partial", cohort_mantel_partial),
+                        ("--cohort-mantel-permutations", cohort_mantel_permutations), ("--cohort-mantel-seed", cohort_mantel_seed)):
+        if value is not None:
+            argv += [flag, str(value)]
+    if cohort_anosim is not None:
+        argv += ["--cohort-anosim", str(cohort_anosim)]
+        for flag, value in (("--cohort-anosim-permutations", cohort_anosim_permutations), ("--cohort-anosim-seed", cohort_anosim_seed)):
+            if value is not None:
+                argv += [flag, str(value)]
     if cohort_strata is not None:
         argv += ["--cohort-strata", str(cohort_strata)]
         if cohort_strata_column is not None:

@@ -74,6 +74,17 @@ PERMDISP_MAX_GROUPS = 32
 PERMDISP_PAIR_SLOTS = 496
 PERMDISP_MAX_PERMUTATIONS = 999999
 PERMDISP_MISSING = 0xFFFFFFFF
+#: epik_amd_mantel (64 bytes) and epik_amd_anosim (48 bytes): a test's record; the doubles of an undefined test are NA_BITS
+MANTEL = np.dtype([("used", np.uint32), ("side", np.uint32), ("method", np.uint32), ("partial", np.uint32),
+                   ("at_least", np.uint64), ("r", np.float64), ("r_xz", np.float64), ("r_yz", np.float64),
+                   ("stat", np.float64), ("p", np.float64)])
+ANOSIM = np.dtype([("used", np.uint32), ("groups", np.uint32), ("at_least", np.uint64), ("r", np.float64),
+                   ("mean_between", np.float64), ("mean_within", np.float64), ("p", np.float64)])
+MANTEL_MAX_SAMPLES = 8192
+MANTEL_MAX_COLUMNS = 64
+MANTEL_MAX_MATRICES = 8
+MANTEL_METHODS = {"pearson": 1, "spearman": 2}
+MANTEL_NO_CONTROL = 0xFFFFFFFF
 #: epik_amd_edgetest_family (48 bytes) and epik_amd_edgetest (208 bytes): a (column, branch)'s record of the edge test; the
 #: families are mass, rank(mass), imbalance, rank(imbalance); the doubles of an undefined family are NA_BITS
 EDGETEST_FAMILY = np.dtype([("eta2", np.float64), ("stat", np.float64), ("p", np.float64), ("p_adj", np.float64),
@@ -240,6 +251,14 @@ EXPORTS = (
     "epik_amd_cohort_edgetest_strata_device",
     "epik_amd_cohort_edgetest_strata",
     "epik_amd_cohort_edgetest_strata_host",
+    "epik_amd_cohort_mantel_device",
+    "epik_amd_cohort_mantel",
+    "epik_amd_cohort_mantel_host",
+    "epik_amd_cohort_mantel_kr_host",
+    "epik_amd_cohort_anosim_device",
+    "epik_amd_cohort_anosim",
+    "epik_amd_cohort_anosim_host",
+    "epik_amd_cohort_anosim_kr_host",
     "epik_amd_placer_cohort_reads",
     "epik_amd_placer_cohort_strands",
     "epik_amd_placer_cohort_frames",
@@ -679,6 +698,17 @@ def load() -> ctypes.CDLL:
             continue
         getattr(lib, "epik_amd_cohort_" + name).restype = i32
         getattr(lib, "epik_amd_cohort_" + name).argtypes = getattr(lib, "epik_amd_cohort_" + sibling).argtypes + [vp]
+    # (Mantel and ANOSIM: the sides or the labels, P, the seed, strata, the record and stat)
+    sides = [vp, u32, vp, vp, u32, u32, u32, u32, u64, vp, vp, vp]
+    labels = [vp, u32, u32, u64, vp, vp, vp]
+    for name, tail in (("mantel", sides), ("anosim", labels)):
+        for form, head in (("_device", [vp, vp]), ("", [vp, vp, vp, u32]), ("_host", [vp, u32, u32, vp, vp, u32]),
+                           ("_kr_host", [vp, vp, u32])):
+            if not hasattr(lib, "epik_amd_cohort_" + name + form):  # (an older library named by EPIK_AMD_LIB, as above)
+                continue
+            entry = getattr(lib, "epik_amd_cohort_" + name + form)
+            entry.restype = i32
+            entry.argtypes = head + tail + ([vp] if form == "_device" else [])
     lib.epik_amd_placer_cohort_reads.restype = i32
     lib.epik_amd_placer_cohort_reads.argtypes = [vp, vp, vp, vp, vp, vp, u64]
     for name in ("epik_amd_placer_cohort_strands", "epik_amd_placer_cohort_frames", "epik_amd_placer_cohort_mates"):

@@ -34,6 +34,10 @@ PERMANOVA of the samples' groups over the KR distances (the header's seventh rul
 PERMDISP, the test of the groups' dispersions that goes with it (the header's PERMDISP rule): `Cohort.permdisp` /
 `permdisp_device` on the device, `permdisp_host` and `permdisp_kr_host` on the host; `format_permdisp_tsv` is its output file.
 
+The Mantel and partial Mantel tests and ANOSIM (the header's Mantel rule): `Cohort.mantel` / `mantel_device` and `Cohort.anosim` /
+`anosim_device` on the device, `mantel_host`, `mantel_kr_host`, `anosim_host` and `anosim_kr_host` on the host, giving a `Mantel`
+or an `Anosim`; the sides are columns of per-sample numbers and square matrices, `strata=` an argument of every form.
+
 The edge test (the header's eighth rule): which branches differ between the groups of a factor column, by permutation with
 the max-statistic adjustment: `Cohort.edgetest` / `edgetest_device` on the device, `edgetest_host` on the host;
 `read_factors(..., most=32)` reads the file of --cohort-edge-test; `format_edgetest_tsv` and `read_edgetest_tsv` are its
@@ -540,6 +544,138 @@ def permdisp_host(mass, first, branch_length, labels, permutations: int = 999, s
 
 
 @dataclass
+class Mantel:
+    """What the Mantel tests give: `records` `capi.MANTEL` [tests], the tests in side-major order, pearson before spearman
+    (`side`, `method` and `partial` name each), and `stat` float64 [tests][P + 1] (the statistic of permutation 0 .. P; None
+    where not asked for)."""
+    records: np.ndarray
+    stat: np.ndarray | None
+
+
+@dataclass
+class Anosim:
+    """What ANOSIM gives: `records` `capi.ANOSIM` [M] and `stat` float64 [M][P + 1] (R of permutation 0 .. P; None where not
+    asked for)."""
+    records: np.ndarray
+    stat: np.ndarray | None
+
+
+def _strata(strata, num_samples: int):
+    if strata is None:
+        return None
+    strata = np.ascontiguousarray(strata, dtype=np.uint32)
+    if strata.shape != (num_samples,):
+        raise ValueError(f"strata must be [num_samples = {num_samples}]")
+    return strata
+
+
+def _pointer(array):
+    return array.ctypes.data if array is not None and array.size else None
+
+
+def _sides(values, matrices, matrix_present, methods, control, permutations, num_samples: int, with_stat: bool):
+    """The sides of a Mantel call as the C ABI takes them: (the arrays, which must outlive the call; the arguments from `values`
+    to `num_permutations`; an empty `Mantel`).  values [Mv][S] (NaN: missing), matrices [Mm][S][S], matrix_present [Mm][S]
+    (all present if None); `methods` names of `capi.MANTEL_METHODS` (or their bits), `control` a side index or None."""
+    s = num_samples
+    values = np.zeros((0, s)) if values is None else np.ascontiguousarray(values, dtype=np.float64)
+    matrices = np.zeros((0, s, s)) if matrices is None else np.ascontiguousarray(matrices, dtype=np.float64)
+    if values.ndim != 2 or values.shape[1] != s:
+        raise ValueError(f"values must be [num_columns][num_samples = {s}]")
+    if matrices.ndim != 3 or matrices.shape[1:] != (s, s):
+        raise ValueError(f"matrices must be [num_matrices][{s}][{s}]")
+    present = np.ones(matrices.shape[:2], np.uint8) if matrix_present is None else np.ascontiguousarray(matrix_present, dtype=np.uint8)
+    if present.shape != matrices.shape[:2]:
+        raise ValueError("matrix_present must be [num_matrices][num_samples]")
+    bits = int(methods) if isinstance(methods, (int, np.integer)) else 0
+    if not isinstance(methods, (int, np.integer)):
+        for name in ((methods,) if isinstance(methods, str) else methods):
+            if name not in capi.MANTEL_METHODS:
+                raise ValueError(f"unknown method {name!r} (pearson or spearman)")
+            bits |= capi.MANTEL_METHODS[name]
+    control = capi.MANTEL_NO_CONTROL if control is None else int(control)
+    if not 0 <= control <= 0xFFFFFFFF or not 0 <= bits <= 0xFFFFFFFF:
+        raise ValueError("control and methods are uint32")
+    tests = max((len(values) + len(matrices)) * bin(bits & 3).count("1"), 1)
+    rows = min(max(int(permutations), 0), capi.PERMANOVA_MAX_PERMUTATIONS) + 1
+    out = Mantel(np.zeros(tests, dtype=capi.MANTEL), np.full((tests, rows), np.nan) if with_stat else None)
+    args = (_pointer(values), len(values), _pointer(matrices), _pointer(present), len(matrices), bits, control, int(permutations))
+    return (values, matrices, present), args, out
+
+
+def _kr_and_totals(kr, totals):
+    kr = np.ascontiguousarray(kr, dtype=np.float64)
+    if kr.ndim != 2 or kr.shape[0] != kr.shape[1]:
+        raise ValueError("kr must be [num_samples][num_samples]")
+    totals = np.ascontiguousarray(totals, dtype=np.uint64)
+    if totals.shape != (kr.shape[0],):
+        raise ValueError("one total mass per sample")
+    return kr, totals
+
+
+def mantel_kr_host(kr, totals, values=None, matrices=None, matrix_present=None, methods=("pearson",), control=None,
+                   permutations: int = 999, seed: int = 1, strata=None, with_stat: bool = True) -> Mantel:
+    """The Mantel and partial Mantel tests of the rule from a matrix kr[S][S] and totals[S] (T_s) on the host
+    (`epik_amd_cohort_mantel_kr_host`): every side against the matrix, with `control` (a side) held fixed."""
+    lib = capi.load()
+    kr, totals = _kr_and_totals(kr, totals)
+    s = kr.shape[0]
+    keep, args, out = _sides(values, matrices, matrix_present, methods, control, permutations, s, with_stat)
+    strata = _strata(strata, s)
+    capi.check(lib.epik_amd_cohort_mantel_kr_host(kr.ctypes.data, totals.ctypes.data, s, *args, int(seed), _pointer(strata),
+                                                  out.records.ctypes.data, _pointer(out.stat)))
+    return out
+
+
+def mantel_host(mass, first, branch_length, values=None, matrices=None, matrix_present=None, methods=("pearson",), control=None,
+                permutations: int = 999, seed: int = 1, metric="kr", strata=None, with_stat: bool = True) -> Mantel:
+    """The same for mass[S][N] over the distance `metric` on the host (`epik_amd_cohort_mantel_host`)."""
+    lib = capi.load()
+    mass, first, length = _cells_and_tree(mass, first, branch_length)
+    s, n = mass.shape
+    keep, args, out = _sides(values, matrices, matrix_present, methods, control, permutations, s, with_stat)
+    strata = _strata(strata, s)
+    capi.check(lib.epik_amd_cohort_mantel_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, metric_id(metric), *args,
+                                               int(seed), _pointer(strata), out.records.ctypes.data, _pointer(out.stat)))
+    return out
+
+
+def _anosim_buffers(m: int, permutations: int, with_stat: bool) -> Anosim:
+    rows = min(max(int(permutations), 0), capi.PERMANOVA_MAX_PERMUTATIONS) + 1
+    return Anosim(np.zeros(max(m, 1), dtype=capi.ANOSIM), np.full((max(m, 1), rows), np.nan) if with_stat else None)
+
+
+def anosim_kr_host(kr, totals, labels, permutations: int = 999, seed: int = 1, strata=None, with_stat: bool = True) -> Anosim:
+    """ANOSIM of the rule from a matrix kr[S][S], totals[S] (T_s) and labels[S][M] (0xffffffff: missing) on the host
+    (`epik_amd_cohort_anosim_kr_host`)."""
+    lib = capi.load()
+    kr, totals = _kr_and_totals(kr, totals)
+    s = kr.shape[0]
+    labels = _labels(labels, s)
+    out = _anosim_buffers(labels.shape[1], permutations, with_stat)
+    strata = _strata(strata, s)
+    capi.check(lib.epik_amd_cohort_anosim_kr_host(kr.ctypes.data, totals.ctypes.data, s, labels.ctypes.data, labels.shape[1],
+                                                  int(permutations), int(seed), _pointer(strata), out.records.ctypes.data,
+                                                  _pointer(out.stat)))
+    return out
+
+
+def anosim_host(mass, first, branch_length, labels, permutations: int = 999, seed: int = 1, metric="kr", strata=None,
+                with_stat: bool = True) -> Anosim:
+    """The same for mass[S][N] over the distance `metric` on the host (`epik_amd_cohort_anosim_host`)."""
+    lib = capi.load()
+    mass, first, length = _cells_and_tree(mass, first, branch_length)
+    s, n = mass.shape
+    labels = _labels(labels, s)
+    out = _anosim_buffers(labels.shape[1], permutations, with_stat)
+    strata = _strata(strata, s)
+    capi.check(lib.epik_amd_cohort_anosim_host(mass.ctypes.data, s, n, first.ctypes.data, length.ctypes.data, metric_id(metric),
+                                               labels.ctypes.data, labels.shape[1], int(permutations), int(seed), _pointer(strata),
+                                               out.records.ctypes.data, _pointer(out.stat)))
+    return out
+
+
+@dataclass
 class Model:
     """What the sequential model gives: `records` `capi.MODEL_TERM` [T + 1] (the terms in test order, then the whole model),
     `info` one `capi.MODEL_INFO`, `stat` float64 [T + 1][P + 1] (F of permutation 0 .. P; None where not asked for) and
@@ -942,6 +1078,53 @@ class Cohort:
               int(bool(pairwise)), out.records.ctypes.data,
               out.stat.ctypes.data if with_stat else None, out.group_mean.ctypes.data,
               out.z.ctypes.data)
+        return out
+
+    def mantel_device(self, d_dist: int, values=None, matrices=None, matrix_present=None, methods=("pearson",), control=None,
+                      permutations: int = 999, seed: int = 1, d_out: int = 0, d_stat: int = 0, stream: int = 0, strata=None) -> None:
+        """The Mantel tests of the sides (host; `mantel`) over d_dist, float64 [S][S] in device memory as `kr_device` or
+        `unifrac_device` wrote it, into d_out, `capi.MANTEL` [tests], and where given d_stat, float64 [tests][P + 1], every cell
+        written; asynchronous on `stream` once the sides are copied, no readback (`epik_amd_cohort_mantel_device`)."""
+        keep, args, _ = _sides(values, matrices, matrix_present, methods, control, permutations, self.num_samples, False)
+        strata = _strata(strata, self.num_samples)
+        capi.check(self._lib.epik_amd_cohort_mantel_device(self._handle, d_dist or None, *args, int(seed), _pointer(strata),
+                                                           d_out or None, d_stat or None, stream or None))
+
+    def mantel(self, tree, branch_length, values=None, matrices=None, matrix_present=None, methods=("pearson",), control=None,
+               permutations: int = 999, seed: int = 1, metric="kr", strata=None, with_stat: bool = False) -> Mantel:
+        """The Mantel test of every side against the samples' distances `metric`, KR by default: values [Mv][S], a column of
+        numbers a side (NaN: missing; its distance is |v_s - v_t|), and matrices [Mm][S][S] with matrix_present [Mm][S].
+        `methods`: pearson, spearman or both; `control`: the side held fixed (the partial Mantel test of every other side);
+        `strata`, one id per sample: the shuffles stay within the strata (`epik_amd_cohort_mantel`)."""
+        length = self._lengths(tree, branch_length)
+        keep, args, out = _sides(values, matrices, matrix_present, methods, control, permutations, self.num_samples, with_stat)
+        strata = _strata(strata, self.num_samples)
+        capi.check(self._lib.epik_amd_cohort_mantel(self._handle, tree._handle, length.ctypes.data, metric_id(metric), *args, int(seed),
+                                                    _pointer(strata), out.records.ctypes.data, _pointer(out.stat)))
+        return out
+
+    def anosim_device(self, d_dist: int, labels, permutations: int, seed: int, d_out: int, d_stat: int = 0, stream: int = 0,
+                      strata=None) -> None:
+        """ANOSIM of labels[S][M] (host; 0xffffffff: missing) over d_dist as `mantel_device` takes it, into d_out, `capi.ANOSIM`
+        [M], and where given d_stat, float64 [M][P + 1], every cell written; asynchronous on `stream` once the labels are copied,
+        no readback (`epik_amd_cohort_anosim_device`)."""
+        labels = _labels(labels, self.num_samples)
+        strata = _strata(strata, self.num_samples)
+        capi.check(self._lib.epik_amd_cohort_anosim_device(self._handle, d_dist or None, labels.ctypes.data, labels.shape[1],
+                                                           int(permutations), int(seed), _pointer(strata), d_out or None,
+                                                           d_stat or None, stream or None))
+
+    def anosim(self, tree, branch_length, labels, permutations: int = 999, seed: int = 1, metric="kr", strata=None,
+               with_stat: bool = False) -> Anosim:
+        """ANOSIM of the samples' groups in every column of labels[S][M] over the ranks of their distances `metric`, KR by
+        default (`epik_amd_cohort_anosim`)."""
+        length = self._lengths(tree, branch_length)
+        labels = _labels(labels, self.num_samples)
+        out = _anosim_buffers(labels.shape[1], permutations, with_stat)
+        strata = _strata(strata, self.num_samples)
+        capi.check(self._lib.epik_amd_cohort_anosim(self._handle, tree._handle, length.ctypes.data, metric_id(metric),
+                                                    labels.ctypes.data, labels.shape[1], int(permutations), int(seed),
+                                                    _pointer(strata), out.records.ctypes.data, _pointer(out.stat)))
         return out
 
     def pcoa_device(self, d_kr: int, num_components: int, d_mu: int, d_coord: int, d_info: int, stream: int = 0) -> None:
@@ -2191,3 +2374,107 @@ def read_model_tsv(path: str):
     for name, r in (("residual", rows[-2]), ("total", rows[-1])):
         info[name] = (int(r[1]), _na_or_float(r[2]), _na_or_float(r[3]))
     return terms, records, info
+
+
+MANTEL_HEADER = "side\tmethod\tused\tr\tr_xz\tr_yz\tstat\tat_least\tp"
+ANOSIM_HEADER = "column\tused\tgroups\tmean_between\tmean_within\tr\tat_least\tp"
+_METHOD_NAMES = {1: "pearson", 2: "spearman", 3: "both"}
+
+
+def format_mantel_tsv(names, totals, side_names, num_columns: int, methods, control, permutations: int, seed: int, records,
+                      distance="kr", strata=None) -> str:
+    """cohort_mantel_<list>.tsv: the first line (sides, permutations, seed, method, partial=NAME or -), the `# unused` lines, a
+    `# side` line per side (the first `num_columns` are columns, the others matrices) with the samples of its first test, the
+    column names, then a line per test of records `capi.MANTEL` [tests]; doubles as %.17g, NA as NA.  `methods`: pearson,
+    spearman, both or the bits; `control`: a side index or None."""
+    bits = methods if isinstance(methods, int) else {v: k for k, v in _METHOD_NAMES.items()}[methods]
+    per_side = bin(bits).count("1")
+    records = np.asarray(records)
+    if records.dtype != capi.MANTEL or records.shape != (len(side_names) * per_side,):
+        raise ValueError("records must be capi.MANTEL [sides * methods]")
+    more = (f" sides={len(side_names)} permutations={int(permutations)} seed={int(seed)} method={_METHOD_NAMES[bits]}"
+            f" partial={'-' if control is None else side_names[control]}")
+    lines = _used_head("mantel", names, totals, more, distance)
+    lines += [f"# side\t{q}\t{'column' if q < num_columns else 'matrix'}\t{name}\t{int(records['used'][q * per_side])}"
+              for q, name in enumerate(side_names)]
+    lines.append(MANTEL_HEADER)
+    for r in records:
+        lines.append("\t".join([side_names[int(r["side"])], "spearman" if r["method"] else "pearson", str(int(r["used"])),
+                                _g17_or_na(r["r"]), _g17_or_na(r["r_xz"]), _g17_or_na(r["r_yz"]), _g17_or_na(r["stat"]),
+                                str(int(r["at_least"])), _g17_or_na(r["p"])]))
+    return with_strata_field("\n".join(lines) + "\n", strata)
+
+
+def format_anosim_tsv(names, totals, columns, label_names, labels, permutations: int, seed: int, records, distance="kr",
+                      strata=None) -> str:
+    """cohort_anosim_<list>.tsv: the first line, the `# unused`, `# column` and `# group` lines as cohort_permanova's (a group
+    line ends in its size), the column names, then a line per column of records `capi.ANOSIM` [M]."""
+    records = np.asarray(records)
+    if records.dtype != capi.ANOSIM or records.shape != (len(columns),):
+        raise ValueError("records must be capi.ANOSIM [num_columns]")
+    lines = _used_head("anosim", names, totals, f" columns={len(columns)} permutations={int(permutations)} seed={int(seed)}", distance)
+    lines += [f"# column\t{c}\t{name}\t{int(records['used'][c])}\t{int(records['groups'][c])}" for c, name in enumerate(columns)]
+    for c, (order, sizes) in enumerate(groups_of(labels, totals)):
+        lines += [f"# group\t{c}\t{g}\t{label_names[c][v]}\t{n}" for g, (v, n) in enumerate(zip(order, sizes))]
+    lines.append(ANOSIM_HEADER)
+    for name, r in zip(columns, records):
+        lines.append("\t".join([name, str(int(r["used"])), str(int(r["groups"])), _g17_or_na(r["mean_between"]),
+                                _g17_or_na(r["mean_within"]), _g17_or_na(r["r"]), str(int(r["at_least"])), _g17_or_na(r["p"])]))
+    return with_strata_field("\n".join(lines) + "\n", strata)
+
+
+_TAIL = r"(?:\tdistance=(?P<distance>\w+))?(?:\tstrata=(?P<strata>[^\t]+))?"
+
+
+def read_mantel_tsv(path: str):
+    """(side names, kinds "column" | "matrix", records `capi.MANTEL` [tests], info {"samples", "used", "unused", "permutations",
+    "seed", "method", "partial", "distance", "strata"})"""
+    with open(path, newline="") as fh:
+        head, info, line = _read_used_head(
+            fh, "mantel", r" sides=(\d+) permutations=(\d+) seed=(\d+) method=(pearson|spearman|both) partial=([^\t]+)" + _TAIL, path)
+        sides, kinds = [], []
+        while line.startswith("# side\t"):
+            _, q, kind, name, _used = line.split("\t")
+            if int(q) != len(sides) or kind not in ("column", "matrix"):
+                raise ValueError(f"{path}: the sides are not numbered in order")
+            sides.append(name), kinds.append(kind)
+            line = fh.readline().rstrip("\n")
+        if line != MANTEL_HEADER or len(sides) != int(head.group(3)):
+            raise ValueError(f"{path}: not a cohort mantel file")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    info.update(permutations=int(head.group(4)), seed=int(head.group(5)), method=head.group(6),
+                partial=None if head.group(7) == "-" else head.group(7), distance=head.group("distance") or "kr")
+    records = np.zeros(len(rows), dtype=capi.MANTEL)
+    for i, r in enumerate(rows):
+        if len(r) != 9 or r[0] not in sides or r[1] not in ("pearson", "spearman"):
+            raise ValueError(f"{path}: row {i} is no test")
+        side = sides.index(r[0])
+        records[i] = (int(r[2]), side, r[1] == "spearman", info["partial"] is not None and r[0] != info["partial"], int(r[7]),
+                      *(_na_or_float(x) for x in r[3:7]), _na_or_float(r[8]))
+    return sides, kinds, records, info
+
+
+def read_anosim_tsv(path: str):
+    """(columns, groups [(label, n)] per column, records `capi.ANOSIM` [M], info)"""
+    with open(path, newline="") as fh:
+        head, info, line = _read_used_head(fh, "anosim", r" columns=(\d+) permutations=(\d+) seed=(\d+)" + _TAIL, path)
+        columns, groups = [], []
+        while line.startswith("# column\t"):
+            columns.append(line.split("\t")[2]), groups.append([])
+            line = fh.readline().rstrip("\n")
+        while line.startswith("# group\t"):
+            _, c, g, label, n = line.split("\t")
+            if int(g) != len(groups[int(c)]):
+                raise ValueError(f"{path}: the groups are not numbered in order")
+            groups[int(c)].append((label, int(n)))
+            line = fh.readline().rstrip("\n")
+        if line != ANOSIM_HEADER or len(columns) != int(head.group(3)):
+            raise ValueError(f"{path}: not a cohort anosim file")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    info.update(permutations=int(head.group(4)), seed=int(head.group(5)), distance=head.group("distance") or "kr")
+    if [r[0] for r in rows] != columns or any(len(r) != 8 for r in rows):
+        raise ValueError(f"{path}: the rows do not follow the columns")
+    records = np.zeros(len(rows), dtype=capi.ANOSIM)
+    for i, r in enumerate(rows):
+        records[i] = (int(r[1]), int(r[2]), int(r[6]), _na_or_float(r[5]), _na_or_float(r[3]), _na_or_float(r[4]), _na_or_float(r[7]))
+    return columns, groups, records, info

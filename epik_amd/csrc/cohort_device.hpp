@@ -33,6 +33,7 @@ enum CohortSpaceId : uint32_t {
     kSpaceEdgetest,
     kSpacePermdisp,
     kSpaceModel,
+    kSpaceMantel,
     kCohortSpaces
 };
 

@@ -1680,6 +1680,298 @@ int model_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branc
                                stat, aliased, err, strata);
 }
 
+namespace {
+
+int too_many_samples(uint32_t num_samples, const char* what, std::string& err)
+{
+    if (num_samples <= EPIK_AMD_MANTEL_MAX_SAMPLES) return EPIK_AMD_OK;
+    err = std::string(what) + ": num_samples = " + std::to_string(num_samples) + " is above 8192, the most samples of this analysis";
+    return EPIK_AMD_ERR_INVALID;
+}
+
+int permutations_in_range(uint32_t num_permutations, std::string& err)
+{
+    if (num_permutations >= 1 && num_permutations <= EPIK_AMD_PERMANOVA_MAX_PERMUTATIONS) return EPIK_AMD_OK;
+    err = "num_permutations = " + std::to_string(num_permutations) + " is outside [1, 999999]";
+    return EPIK_AMD_ERR_INVALID;
+}
+
+// the rule's triangle chain of f(i, j) over the pairs of n positions: the rows' chains, then the chain of the rows
+template <class F>
+double triangle_chain(size_t n, F f)
+{
+    double total = 0.0;
+    for (size_t i = 0; i + 1 < n; ++i) {
+        double t = 0.0;
+        for (size_t j = i + 1; j < n; ++j) t = t + f(i, j);
+        total = total + t;
+    }
+    return total;
+}
+
+// one of x, y, z over a list of n positions as a symmetric table (the diagonal is never read): the values of cell(i, j), i < j,
+// or their midranks among the m of them; then the deviations from the chain's mean, and ss
+struct mantel_table {
+    std::vector<double> a;
+    double ss = 0.0;
+    template <class Cell>
+    void fill(size_t n, Cell cell, bool ranks)
+    {
+        a.assign(n * n, 0.0);
+        std::vector<double> v, r;
+        std::vector<uint32_t> order;
+        for (size_t i = 0; i < n; ++i)
+            for (size_t j = i + 1; j < n; ++j) v.push_back(cell(i, j));
+        if (ranks) midranks_sorted(v, order, r), v.swap(r);
+        size_t e = 0;
+        for (size_t i = 0; i < n; ++i)
+            for (size_t j = i + 1; j < n; ++j) a[i * n + j] = a[j * n + i] = v[e++];
+    }
+    void centre(size_t n)
+    {
+        const double mean = triangle_chain(n, [&](size_t i, size_t j) { return a[i * n + j]; }) / (double)(n * (n - 1) / 2);
+        for (size_t i = 0; i < n; ++i)
+            for (size_t j = 0; j < n; ++j)
+                if (i != j) a[i * n + j] = a[i * n + j] - mean;
+        ss = triangle_chain(n, [&](size_t i, size_t j) { return a[i * n + j] * a[i * n + j]; });
+    }
+};
+
+// the rule's partial statistic; false where the radicand that moves with the permutation is not > 0
+inline bool mantel_partial(double r_xy, double r_xz, double r_yz, double& stat)
+{
+    const double rad_x = 1.0 - r_xz * r_xz, rad_y = 1.0 - r_yz * r_yz;
+    if (!(rad_x > 0.0) || !(rad_y > 0.0)) return false;
+    stat = (r_xy - r_xz * r_yz) / (std::sqrt(rad_x) * std::sqrt(rad_y));
+    return true;
+}
+
+}  // namespace
+
+int mantel_arguments_valid(const mantel_sides& sides, uint32_t num_samples, uint32_t num_permutations, std::string& err)
+{
+    if (const int rc = too_many_samples(num_samples, "mantel", err); rc != EPIK_AMD_OK) return rc;
+    const size_t S = num_samples, Mv = sides.num_columns, Mm = sides.num_matrices;
+    if (Mv > EPIK_AMD_MANTEL_MAX_COLUMNS) {
+        err = "num_columns = " + std::to_string(Mv) + " is outside [0, 64]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if (Mm > EPIK_AMD_MANTEL_MAX_MATRICES) {
+        err = "num_matrices = " + std::to_string(Mm) + " is outside [0, 8]";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if (Mv + Mm == 0) {
+        err = "a Mantel test needs a side: num_columns and num_matrices are both 0";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if ((Mv && !sides.values) || (Mm && (!sides.matrices || !sides.matrix_present))) {
+        err = "null argument";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if (sides.methods < 1 || sides.methods > (EPIK_AMD_MANTEL_PEARSON | EPIK_AMD_MANTEL_SPEARMAN)) {
+        err = "methods = " + std::to_string(sides.methods) + " is outside [1, 3] (bit 0 pearson, bit 1 spearman)";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if (sides.control != EPIK_AMD_MANTEL_NO_CONTROL && sides.control >= Mv + Mm) {
+        err = "control = " + std::to_string(sides.control) + " names no side (there are " + std::to_string(Mv + Mm) + ")";
+        return EPIK_AMD_ERR_INVALID;
+    }
+    if (const int rc = permutations_in_range(num_permutations, err); rc != EPIK_AMD_OK) return rc;
+    for (size_t q = 0; q < Mv; ++q) {
+        double least = HUGE_VAL, most = -HUGE_VAL;
+        for (size_t s = 0; s < S; ++s) {
+            const double v = sides.values[q * S + s];
+            if (std::isinf(v)) {
+                err = "sample " + std::to_string(s) + ", column " + std::to_string(q) + ": the value is infinite";
+                return EPIK_AMD_ERR_INVALID;
+            }
+            if (v < least) least = v;
+            if (v > most) most = v;
+        }
+        if (most > least && std::isinf(most - least)) {  // (|v_s - v_t| would be the +inf that pads the sort of the pairs)
+            err = "column " + std::to_string(q) + ": the range of the values overflows a double";
+            return EPIK_AMD_ERR_INVALID;
+        }
+    }
+    for (size_t k = 0; k < Mm; ++k)
+        for (size_t s = 0; s < S; ++s)
+            for (size_t t = s + 1; t < S; ++t) {
+                const double v = sides.matrices[(k * S + s) * S + t];
+                if (!sides.matrix_present[k * S + s] || !sides.matrix_present[k * S + t] || (v >= 0.0 && std::isfinite(v))) continue;
+                err = "matrix " + std::to_string(k) + ", cell [" + std::to_string(s) + "][" + std::to_string(t) +
+                      "]: the distance is negative or not finite";
+                return EPIK_AMD_ERR_INVALID;
+            }
+    return EPIK_AMD_OK;
+}
+
+int anosim_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint32_t num_columns, uint32_t num_permutations, std::string& err)
+{
+    if (const int rc = too_many_samples(num_samples, "anosim", err); rc != EPIK_AMD_OK) return rc;
+    return permanova_arguments_valid(labels, num_samples, num_columns, num_permutations, false, err);
+}
+
+int mantel_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const mantel_sides& sides,
+                         uint32_t num_permutations, uint64_t seed, epik_amd_mantel* out, double* stat, std::string& err,
+                         const uint32_t* strata)
+{
+    if (const int rc = mantel_arguments_valid(sides, num_samples, num_permutations, err); rc != EPIK_AMD_OK) return rc;
+    const size_t S = num_samples, P = num_permutations, Mv = sides.num_columns, Q = sides.sides();
+    const double na = na_value();
+    if (stat) std::fill(stat, stat + (size_t)sides.tests() * (P + 1), na);
+    const auto present = [&](size_t q, size_t s) {
+        return q < Mv ? !std::isnan(sides.values[q * S + s]) : sides.matrix_present[(q - Mv) * S + s] != 0;
+    };
+    const auto distance = [&](size_t q, size_t s, size_t t) {  // (s < t)
+        return q < Mv ? std::fabs(sides.values[q * S + s] - sides.values[q * S + t]) : sides.matrices[((q - Mv) * S + s) * S + t];
+    };
+    size_t test = 0;
+    for (size_t q = 0; q < Q; ++q)
+        for (uint32_t method = 0; method < 2; ++method) {
+            if (!(sides.methods >> method & 1u)) continue;
+            const bool partial = sides.control != EPIK_AMD_MANTEL_NO_CONTROL && sides.control != q;
+            const size_t z_side = sides.control;
+            std::vector<uint32_t> u;
+            for (size_t s = 0; s < S; ++s)
+                if (totals[s] != 0 && present(q, s) && (!partial || present(z_side, s))) u.push_back((uint32_t)s);
+            const size_t n = u.size();
+            epik_amd_mantel& rec = out[test];
+            double* row = stat ? stat + test * (P + 1) : nullptr;
+            ++test;
+            rec = epik_amd_mantel{(uint32_t)n, (uint32_t)q, method, partial ? 1u : 0u, 0, na, na, na, na, na};
+            if (n < 3) continue;
+            mantel_table x, y, z;
+            x.fill(n, [&](size_t i, size_t j) { return kr[(size_t)u[i] * S + u[j]]; }, method == 1), x.centre(n);
+            y.fill(n, [&](size_t i, size_t j) { return distance(q, u[i], u[j]); }, method == 1), y.centre(n);
+            if (partial) z.fill(n, [&](size_t i, size_t j) { return distance(z_side, u[i], u[j]); }, method == 1), z.centre(n);
+            if (x.ss == 0.0 || y.ss == 0.0 || (partial && z.ss == 0.0)) continue;
+            const auto product = [&](const mantel_table& a, const mantel_table& b) {
+                return triangle_chain(n, [&](size_t i, size_t j) { return a.a[i * n + j] * b.a[i * n + j]; });
+            };
+            const double den_xy = std::sqrt(x.ss * y.ss), r_xy = product(x, y) / den_xy;
+            double den_xz = 0.0, r_xz = na, r_yz = na, stat0 = r_xy;
+            if (partial) {
+                den_xz = std::sqrt(x.ss * z.ss);
+                r_xz = product(x, z) / den_xz, r_yz = product(y, z) / std::sqrt(y.ss * z.ss);
+                if (!mantel_partial(r_xy, r_xz, r_yz, stat0)) continue;
+            }
+            rec.r = r_xy, rec.r_xz = r_xz, rec.r_yz = r_yz, rec.stat = stat0;
+            if (row) row[0] = stat0;
+            arrangements arrange(strata, n, [&](size_t i) { return u[i]; });
+            uint64_t at_least = 0;
+            for (uint32_t p = 1; p <= P; ++p) {
+                const std::vector<uint32_t>& sigma = arrange.of(seed, p);
+                const auto permuted = [&](const mantel_table& b) {
+                    return triangle_chain(n, [&](size_t i, size_t j) { return x.a[(size_t)sigma[i] * n + sigma[j]] * b.a[i * n + j]; });
+                };
+                double value = permuted(y) / den_xy;
+                if (partial && !mantel_partial(value, permuted(z) / den_xz, r_yz, value)) continue;  // (the row keeps its NA)
+                if (row) row[p] = value;
+                at_least += value >= stat0;
+            }
+            rec.at_least = at_least;
+            rec.p = (double)(1 + at_least) / (double)(P + 1);
+        }
+    return EPIK_AMD_OK;
+}
+
+namespace {
+
+// the matrix of `metric` and T_s from the cells: what the _host entries of the distance tests start from
+int matrix_and_totals(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                      const double* branch_length, uint32_t metric, std::vector<double>& kr, std::vector<uint64_t>& totals,
+                      std::string& err)
+{
+    const size_t S = num_samples, N = num_branches;
+    kr.resize(S * S), totals.assign(S, 0);
+    if (const int rc = distance_matrix(mass, num_samples, num_branches, first, branch_length, metric, kr.data(), err); rc != EPIK_AMD_OK)
+        return rc;
+    for (size_t s = 0; s < S; ++s)
+        for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
+    return EPIK_AMD_OK;
+}
+
+}  // namespace
+
+int mantel_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                   const double* branch_length, const mantel_sides& sides, uint32_t num_permutations, uint64_t seed,
+                   epik_amd_mantel* out, double* stat, std::string& err, uint32_t metric, const uint32_t* strata)
+{
+    if (const int rc = mantel_arguments_valid(sides, num_samples, num_permutations, err); rc != EPIK_AMD_OK) return rc;
+    std::vector<double> kr;
+    std::vector<uint64_t> totals;
+    if (const int rc = matrix_and_totals(mass, num_samples, num_branches, first, branch_length, metric, kr, totals, err); rc != EPIK_AMD_OK)
+        return rc;
+    return mantel_records_of_kr(kr.data(), totals.data(), num_samples, sides, num_permutations, seed, out, stat, err, strata);
+}
+
+int anosim_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
+                         uint32_t num_columns, uint32_t num_permutations, uint64_t seed, epik_amd_anosim* out, double* stat,
+                         std::string& err, const uint32_t* strata)
+{
+    if (const int rc = anosim_arguments_valid(labels, num_samples, num_columns, num_permutations, err); rc != EPIK_AMD_OK) return rc;
+    const size_t S = num_samples, M = num_columns, P = num_permutations;
+    const double na = na_value();
+    if (stat) std::fill(stat, stat + M * (P + 1), na);
+    for (size_t c = 0; c < M; ++c) {
+        std::vector<uint32_t> idx, lam, size, group_of(EPIK_AMD_PERMANOVA_MAX_GROUPS, EPIK_AMD_PERMANOVA_MISSING);
+        for (size_t s = 0; s < S; ++s) {
+            const uint32_t v = labels[s * M + c];
+            if (totals[s] == 0 || v == EPIK_AMD_PERMANOVA_MISSING) continue;
+            if (group_of[v] == EPIK_AMD_PERMANOVA_MISSING) group_of[v] = (uint32_t)size.size(), size.push_back(0);
+            idx.push_back((uint32_t)s), lam.push_back(group_of[v]), ++size[group_of[v]];
+        }
+        const size_t n = idx.size(), G = size.size();
+        out[c] = epik_amd_anosim{(uint32_t)n, (uint32_t)G, 0, na, na, na, na};
+        const uint64_t m = (uint64_t)n * (n ? n - 1 : 0) / 2;
+        uint64_t m_within = 0;
+        for (size_t g = 0; g < G; ++g) m_within += (uint64_t)size[g] * (size[g] - 1) / 2;
+        if (G < 2 || m_within < 1) continue;
+        mantel_table x;
+        x.fill(n, [&](size_t i, size_t j) { return kr[(size_t)idx[i] * S + idx[j]]; }, true);
+        const double all = (double)(m * (m + 1) / 2), half = (double)m / 2.0;
+        double between = 0.0, within = 0.0;
+        const auto statistic = [&](const std::vector<uint32_t>& mu) {
+            double w = 0.0;
+            for (size_t i = 0; i < n; ++i)
+                for (size_t j = i + 1; j < n; ++j)
+                    if (mu[i] == mu[j]) w = w + x.a[i * n + j];
+            within = w / (double)m_within, between = (all - w) / (double)(m - m_within);
+            return (between - within) / half;
+        };
+        const double r0 = statistic(lam);
+        out[c].r = r0, out[c].mean_between = between, out[c].mean_within = within;
+        double* row = stat ? stat + c * (P + 1) : nullptr;
+        if (row) row[0] = r0;
+        arrangements arrange(strata, n, [&](size_t i) { return idx[i]; });
+        std::vector<uint32_t> mu(n);
+        uint64_t at_least = 0;
+        for (uint32_t p = 1; p <= P; ++p) {
+            const std::vector<uint32_t>& sigma = arrange.of(seed, p);
+            for (size_t i = 0; i < n; ++i) mu[i] = lam[sigma[i]];
+            const double value = statistic(mu);
+            if (row) row[p] = value;
+            at_least += value >= r0;
+        }
+        out[c].at_least = at_least;
+        out[c].p = (double)(1 + at_least) / (double)(P + 1);
+    }
+    return EPIK_AMD_OK;
+}
+
+int anosim_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                   const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
+                   uint64_t seed, epik_amd_anosim* out, double* stat, std::string& err, uint32_t metric, const uint32_t* strata)
+{
+    if (const int rc = anosim_arguments_valid(labels, num_samples, num_columns, num_permutations, err); rc != EPIK_AMD_OK) return rc;
+    std::vector<double> kr;
+    std::vector<uint64_t> totals;
+    if (const int rc = matrix_and_totals(mass, num_samples, num_branches, first, branch_length, metric, kr, totals, err); rc != EPIK_AMD_OK)
+        return rc;
+    return anosim_records_of_kr(kr.data(), totals.data(), num_samples, labels, num_columns, num_permutations, seed, out, stat, err,
+                                strata);
+}
+
 cohort_factors read_cohort_factors(const std::string& file, const std::vector<cohort_sample>& samples, bool pairwise, size_t most_labels,
                                    const char* flag)
 {
@@ -2417,6 +2709,184 @@ std::string format_model_tsv(const std::vector<cohort_sample>& samples, const ui
     out += "residual\t" + std::to_string(info.df_res) + "\t" + g17(info.ss_res) + "\t" + (total ? g17(rest) : std::string("NA")) +
            "\tNA\tNA\tNA\n";
     out += "total\t" + std::to_string((int64_t)info.used - 1) + "\t" + g17(info.ss_total) + "\t" + (total ? "1" : "NA") + "\tNA\tNA\tNA\n";
+    return out;
+}
+
+cohort_matrix read_cohort_matrix(const std::string& file, const std::vector<cohort_sample>& samples, const char* flag)
+{
+    std::ifstream in(file);
+    if (!in) throw std::runtime_error(std::string(flag) + ": cannot open " + file);
+    const size_t S = samples.size();
+    std::map<std::string, size_t> index_of;
+    for (size_t s = 0; s < S; ++s) index_of[samples[s].name] = s;
+    cohort_matrix out;
+    out.matrix.assign(S * S, 0.0), out.present.assign(S, 0);
+    const auto fail = [&](size_t line_no, const std::string& what) {
+        throw std::runtime_error(std::string(flag) + ": " + file + ", line " + std::to_string(line_no) + ": " + what);
+    };
+    std::vector<std::string> header;        // the names of the first line
+    std::vector<size_t> target;             // their samples, or S for a name outside the list
+    std::map<std::string, size_t> column_of;
+    std::vector<size_t> row_line;           // the line of every name's row, 0: none yet
+    std::vector<std::vector<double>> rows;  // by the first line's order
+    size_t line_no = 0;
+    for (std::string line; std::getline(in, line);) {
+        ++line_no;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        const std::vector<std::string> fields = split_tabs(line);
+        if (header.empty()) {
+            if (fields.size() < 2 || fields[0] != "name") fail(line_no, "the first line must be name<TAB>name1<TAB>...");
+            for (size_t c = 1; c < fields.size(); ++c) {
+                if (fields[c].empty()) fail(line_no, "column " + std::to_string(c) + ": an empty name");
+                if (!column_of.emplace(fields[c], c - 1).second)
+                    fail(line_no, "column " + std::to_string(c) + ": the name '" + fields[c] + "' is given twice");
+                header.push_back(fields[c]);
+                const auto it = index_of.find(fields[c]);
+                target.push_back(it == index_of.end() ? S : it->second);
+            }
+            row_line.assign(header.size(), 0), rows.assign(header.size(), {});
+            continue;
+        }
+        if (fields.size() != header.size() + 1)
+            fail(line_no, std::to_string(fields.size()) + " fields, the first line has " + std::to_string(header.size() + 1));
+        const auto it = column_of.find(fields[0]);
+        if (it == column_of.end()) fail(line_no, "the name '" + fields[0] + "' is not in the first line");
+        const size_t r = it->second;
+        if (row_line[r]) fail(line_no, "the name '" + fields[0] + "' is given twice (line " + std::to_string(row_line[r]) + ")");
+        row_line[r] = line_no;
+        rows[r].resize(header.size());
+        for (size_t c = 0; c < header.size(); ++c) {
+            const std::string& cell = fields[c + 1];
+            const std::string where = "column " + std::to_string(c + 1) + " (" + header[c] + "): ";
+            if (!is_number(cell)) fail(line_no, where + "'" + cell + "' is not a number");
+            const double v = std::strtod(cell.c_str(), nullptr);
+            if (c != r && (!(v >= 0.0) || !std::isfinite(v))) fail(line_no, where + "the distance " + cell + " is negative or not finite");
+            rows[r][c] = v;
+            if (c != r && row_line[c] && rows[c][r] != v)
+                fail(line_no, where + "the distance " + cell + " differs from its mirror cell (line " + std::to_string(row_line[c]) + ")");
+        }
+    }
+    if (header.empty()) throw std::runtime_error(std::string(flag) + ": " + file + " has no first line of names");
+    for (size_t r = 0; r < header.size(); ++r)
+        if (!row_line[r]) throw std::runtime_error(std::string(flag) + ": " + file + " has no row for the name '" + header[r] + "'");
+    for (size_t r = 0; r < header.size(); ++r) {
+        if (target[r] == S) {
+            ++out.skipped;
+            continue;
+        }
+        out.present[target[r]] = 1;
+        for (size_t c = 0; c < header.size(); ++c)
+            if (target[c] != S && c != r) out.matrix[target[r] * S + target[c]] = rows[r][c];
+    }
+    return out;
+}
+
+cohort_mantel_sides read_cohort_mantel_sides(const std::string& metadata_file, const std::vector<std::string>& matrix_arguments,
+                                             const std::string& partial, const std::vector<cohort_sample>& samples)
+{
+    const size_t S = samples.size();
+    cohort_mantel_sides out;
+    if (!metadata_file.empty()) {
+        const cohort_metadata meta = read_cohort_metadata(metadata_file, samples);
+        const size_t M = meta.columns.size();
+        out.names = meta.columns, out.num_columns = (uint32_t)M, out.skipped = meta.skipped;
+        out.values.resize(M * S);
+        for (size_t s = 0; s < S; ++s)
+            for (size_t c = 0; c < M; ++c) out.values[c * S + s] = meta.values[s * M + c];
+    }
+    if (matrix_arguments.size() > EPIK_AMD_MANTEL_MAX_MATRICES)
+        throw std::runtime_error("--cohort-mantel-matrix is given " + std::to_string(matrix_arguments.size()) + " times, 8 at the most");
+    for (const std::string& argument : matrix_arguments) {
+        const size_t eq = argument.find('=');
+        if (eq == std::string::npos || eq == 0 || eq + 1 == argument.size())
+            throw std::runtime_error("--cohort-mantel-matrix " + argument + ": the argument must be NAME=FILE");
+        const std::string name = argument.substr(0, eq);
+        if (std::find(out.names.begin(), out.names.end(), name) != out.names.end())
+            throw std::runtime_error("--cohort-mantel-matrix " + argument + ": the name '" + name + "' is given twice");
+        const cohort_matrix m = read_cohort_matrix(argument.substr(eq + 1), samples);
+        out.names.push_back(name), ++out.num_matrices, out.skipped += m.skipped;
+        out.matrices.insert(out.matrices.end(), m.matrix.begin(), m.matrix.end());
+        out.present.insert(out.present.end(), m.present.begin(), m.present.end());
+    }
+    if (out.names.empty()) throw std::runtime_error("the Mantel test needs --cohort-mantel or --cohort-mantel-matrix (a side)");
+    if (!partial.empty()) {
+        const auto it = std::find(out.names.begin(), out.names.end(), partial);
+        if (it == out.names.end())
+            throw std::runtime_error("--cohort-mantel-partial: '" + partial + "' names no column of --cohort-mantel and no matrix");
+        out.control = (uint32_t)(it - out.names.begin());
+    }
+    return out;
+}
+
+const char* mantel_method_name(uint32_t methods)
+{
+    return methods == EPIK_AMD_MANTEL_PEARSON ? "pearson" : methods == EPIK_AMD_MANTEL_SPEARMAN ? "spearman" : "both";
+}
+
+uint32_t mantel_methods_of_name(const std::string& name)
+{
+    return name == "pearson" ? EPIK_AMD_MANTEL_PEARSON
+           : name == "spearman" ? EPIK_AMD_MANTEL_SPEARMAN
+           : name == "both"     ? (EPIK_AMD_MANTEL_PEARSON | EPIK_AMD_MANTEL_SPEARMAN)
+                                : 0u;
+}
+
+std::string format_mantel_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                              const std::vector<std::string>& side_names, uint32_t num_columns, uint32_t methods, uint32_t control,
+                              uint32_t num_permutations, uint64_t seed, const epik_amd_mantel* records, uint32_t distance)
+{
+    const size_t Q = side_names.size(), per_side = (methods & 1u) + (methods >> 1 & 1u);
+    std::string out = used_head(samples, totals, "mantel",
+                                " sides=" + std::to_string(Q) + " permutations=" + std::to_string(num_permutations) +
+                                    " seed=" + std::to_string(seed) + " method=" + mantel_method_name(methods) + " partial=" +
+                                    (control == EPIK_AMD_MANTEL_NO_CONTROL ? std::string("-") : side_names[control]) +
+                                    distance_field(distance));
+    for (size_t q = 0; q < Q; ++q)
+        out += "# side\t" + std::to_string(q) + '\t' + (q < num_columns ? "column" : "matrix") + '\t' + side_names[q] + '\t' +
+               std::to_string(records[q * per_side].used) + '\n';
+    out += "side\tmethod\tused\tr\tr_xz\tr_yz\tstat\tat_least\tp\n";
+    for (size_t e = 0; e < Q * per_side; ++e) {
+        const epik_amd_mantel& r = records[e];
+        out += side_names[r.side] + '\t' + (r.method ? "spearman" : "pearson") + '\t' + std::to_string(r.used) + '\t' + g17_or_na(r.r) +
+               '\t' + g17_or_na(r.r_xz) + '\t' + g17_or_na(r.r_yz) + '\t' + g17_or_na(r.stat) + '\t' + std::to_string(r.at_least) + '\t' +
+               g17_or_na(r.p) + '\n';
+    }
+    return out;
+}
+
+std::string format_anosim_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                              const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
+                              const uint32_t* labels, uint32_t num_permutations, uint64_t seed, const epik_amd_anosim* records,
+                              uint32_t distance)
+{
+    const size_t S = samples.size(), M = columns.size();
+    std::string out = used_head(samples, totals, "anosim",
+                                " columns=" + std::to_string(M) + " permutations=" + std::to_string(num_permutations) +
+                                    " seed=" + std::to_string(seed) + distance_field(distance));
+    for (size_t c = 0; c < M; ++c)
+        out += "# column\t" + std::to_string(c) + '\t' + columns[c] + '\t' + std::to_string(records[c].used) + '\t' +
+               std::to_string(records[c].groups) + '\n';
+    for (size_t c = 0; c < M; ++c) {  // the groups in the rule's order: by first appearance among the used samples
+        std::map<uint32_t, uint32_t> group_of;
+        std::vector<uint32_t> label_of, size_of;
+        for (size_t s = 0; s < S; ++s) {
+            const uint32_t v = labels[s * M + c];
+            if (totals[s] == 0 || v == EPIK_AMD_PERMANOVA_MISSING) continue;
+            const auto [it, fresh] = group_of.emplace(v, (uint32_t)label_of.size());
+            if (fresh) label_of.push_back(v), size_of.push_back(0);
+            ++size_of[it->second];
+        }
+        for (size_t g = 0; g < label_of.size(); ++g)
+            out += "# group\t" + std::to_string(c) + '\t' + std::to_string(g) + '\t' + names[c][label_of[g]] + '\t' +
+                   std::to_string(size_of[g]) + '\n';
+    }
+    out += "column\tused\tgroups\tmean_between\tmean_within\tr\tat_least\tp\n";
+    for (size_t c = 0; c < M; ++c) {
+        const epik_amd_anosim& r = records[c];
+        out += columns[c] + '\t' + std::to_string(r.used) + '\t' + std::to_string(r.groups) + '\t' + g17_or_na(r.mean_between) + '\t' +
+               g17_or_na(r.mean_within) + '\t' + g17_or_na(r.r) + '\t' + std::to_string(r.at_least) + '\t' + g17_or_na(r.p) + '\n';
+    }
     return out;
 }
 

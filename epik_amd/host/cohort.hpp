@@ -180,6 +180,47 @@ int model_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branc
                   uint32_t num_permutations, uint64_t seed, epik_amd_model_term* out, epik_amd_model_info* info, double* stat,
                   uint8_t* aliased, std::string& err, uint32_t metric = EPIK_AMD_DISTANCE_KR, const uint32_t* strata = nullptr);
 
+/// The sides of a Mantel call as the C ABI takes them: values[Mv][S] (NaN: missing), matrices[Mm][S][S] with
+/// matrix_present[Mm][S], the methods' bits and the control (a side, or EPIK_AMD_MANTEL_NO_CONTROL)
+struct mantel_sides {
+    const double* values;
+    uint32_t num_columns;
+    const double* matrices;
+    const uint8_t* matrix_present;
+    uint32_t num_matrices, methods, control;
+    uint32_t sides() const { return num_columns + num_matrices; }
+    uint32_t tests() const { return sides() * ((methods & 1u) + (methods >> 1 & 1u)); }
+};
+/// num_samples at most 8 192, Mv in [0, 64], Mm in [0, 8] and a side at least, their arrays present, methods in 1 .. 3, the
+/// control a side or none, num_permutations in [1, 999 999], no infinite value, and no cell [s][t], s < t, of a matrix between
+/// two present samples that is negative or not finite: 0, or EPIK_AMD_ERR_INVALID with `err` naming the cause.  Reads nothing of
+/// the arrays when a count is refused.
+int mantel_arguments_valid(const mantel_sides& sides, uint32_t num_samples, uint32_t num_permutations, std::string& err);
+/// num_samples at most 8 192, then as permanova_arguments_valid without pairwise
+int anosim_arguments_valid(const uint32_t* labels, uint32_t num_samples, uint32_t num_columns, uint32_t num_permutations,
+                           std::string& err);
+/// The Mantel and partial Mantel tests by the rule (include/epik_amd.h) from the matrix kr[S][S] and totals[S], one thread:
+/// out[sides.tests()] and, where not null, stat[tests][P + 1], every cell written.  libepik_amd's kernels (mantel_place.hip) give
+/// the same bits.  The code behind epik_amd_cohort_mantel_kr_host.  0, or as mantel_arguments_valid.
+int mantel_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const mantel_sides& sides,
+                         uint32_t num_permutations, uint64_t seed, epik_amd_mantel* out, double* stat, std::string& err,
+                         const uint32_t* strata = nullptr);
+/// The same from mass[S][N]: the matrix by distance_matrix first.  The code behind epik_amd_cohort_mantel_host.
+int mantel_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                   const double* branch_length, const mantel_sides& sides, uint32_t num_permutations, uint64_t seed,
+                   epik_amd_mantel* out, double* stat, std::string& err, uint32_t metric = EPIK_AMD_DISTANCE_KR,
+                   const uint32_t* strata = nullptr);
+/// ANOSIM by the rule from the matrix kr[S][S] and totals[S], one thread: out[M] and, where not null, stat[M][P + 1], every cell
+/// written.  The code behind epik_amd_cohort_anosim_kr_host; the kernels of mantel_place.hip give the same bits.
+int anosim_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* labels,
+                         uint32_t num_columns, uint32_t num_permutations, uint64_t seed, epik_amd_anosim* out, double* stat,
+                         std::string& err, const uint32_t* strata = nullptr);
+/// The same from mass[S][N].  The code behind epik_amd_cohort_anosim_host.
+int anosim_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first,
+                   const double* branch_length, const uint32_t* labels, uint32_t num_columns, uint32_t num_permutations,
+                   uint64_t seed, epik_amd_anosim* out, double* stat, std::string& err, uint32_t metric = EPIK_AMD_DISTANCE_KR,
+                   const uint32_t* strata = nullptr);
+
 /// The list of samples of --cohort: one name<TAB>path line each, paths relative to the list's directory; blank lines and
 /// lines that begin with '#' are skipped.  Throws std::runtime_error naming the line for a line without a tab, an empty
 /// name or path, a name given before, or a file that cannot be read; and for a list without any sample.
@@ -353,6 +394,59 @@ std::string format_permdisp_tsv(const std::vector<cohort_sample>& samples, const
 std::string format_model_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, const cohort_design& design,
                              uint32_t num_permutations, uint64_t seed, const epik_amd_model_term* records,
                              const epik_amd_model_info& info, const uint8_t* aliased, uint32_t distance = EPIK_AMD_DISTANCE_KR);
+/// A matrix of --cohort-mantel-matrix NAME=FILE: FILE is a square TSV in the layout of cohort_kr_<list>.tsv, a first line
+/// name<TAB>name1<TAB>..., then per line a name and one distance per name of the first line; blank lines and lines that begin with
+/// '#' are skipped.  The names are matched to the list: matrix[S][S] in the order of the list, present[s] = 1 for a sample of the
+/// list that the file has (a sample it lacks is missing on that side), names outside the list skipped and counted.  Throws
+/// std::runtime_error naming the line, and the column where there is one, for a name given twice (in the first line or as a row), a
+/// row whose name the first line lacks, a wrong field count, a cell that is no number, negative or not finite, a cell that differs
+/// from its mirror cell, and for a name of the first line without a row.  `flag` begins every message.
+struct cohort_matrix {
+    std::vector<double> matrix;    // [S][S]
+    std::vector<uint8_t> present;  // [S]
+    size_t skipped = 0;
+};
+cohort_matrix read_cohort_matrix(const std::string& file, const std::vector<cohort_sample>& samples,
+                                 const char* flag = "--cohort-mantel-matrix");
+/// The sides of --cohort-mantel FILE and --cohort-mantel-matrix NAME=FILE ... with --cohort-mantel-partial NAME: the metadata
+/// file (empty: none) read by read_cohort_metadata, every column a side, then the matrices in the order given (at most 8, each
+/// NAME=FILE with a NAME that no other side has), read by read_cohort_matrix.  names[Q]; values[Mv][S] (by side, as the C ABI
+/// takes them), matrices[Mm][S][S], present[Mm][S]; control: the side that `partial` names, or EPIK_AMD_MANTEL_NO_CONTROL for an
+/// empty one.  Throws std::runtime_error as the two readers do, and naming an argument without '=', an empty or repeated NAME,
+/// a ninth matrix, no side at all, or a `partial` that names no side.
+struct cohort_mantel_sides {
+    std::vector<std::string> names;
+    std::vector<double> values, matrices;
+    std::vector<uint8_t> present;
+    uint32_t num_columns = 0, num_matrices = 0, control = EPIK_AMD_MANTEL_NO_CONTROL;
+    size_t skipped = 0;
+    mantel_sides sides(uint32_t methods) const
+    {
+        return mantel_sides{values.data(), num_columns, matrices.data(), present.data(), num_matrices, methods, control};
+    }
+};
+cohort_mantel_sides read_cohort_mantel_sides(const std::string& metadata_file, const std::vector<std::string>& matrix_arguments,
+                                             const std::string& partial, const std::vector<cohort_sample>& samples);
+/// pearson | spearman | both of the methods' bits, and the bits of such a name (0 for any other)
+const char* mantel_method_name(uint32_t methods);
+uint32_t mantel_methods_of_name(const std::string& name);
+/// cohort_mantel .tsv: "# epik_amd mantel v1  samples=S used=L sides=Q permutations=P seed=X method=pearson|spearman|both
+/// partial=NAME|-", the "# unused" lines, a "# side<TAB>q<TAB>column|matrix<TAB>name<TAB>used_q" line per side (the first
+/// num_columns of side_names are columns; used_q of the side's first test), the column names side method used r r_xz r_yz stat
+/// at_least p, then a line per test of records[Q * popcount(methods)]; doubles %.17g, NA as NA.  Over a `distance` other than KR
+/// the first line ends in distance_field(distance).
+std::string format_mantel_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                              const std::vector<std::string>& side_names, uint32_t num_columns, uint32_t methods, uint32_t control,
+                              uint32_t num_permutations, uint64_t seed, const epik_amd_mantel* records,
+                              uint32_t distance = EPIK_AMD_DISTANCE_KR);
+/// cohort_anosim .tsv: "# epik_amd anosim v1  samples=S used=L columns=M permutations=P seed=X", the "# unused" lines, the
+/// "# column" lines as cohort_permanova's, a "# group<TAB>c<TAB>g<TAB>label<TAB>n" line per group (the groups in the rule's order),
+/// the column names column used groups mean_between mean_within r at_least p, then a line per column of records[M]; doubles
+/// %.17g, NA as NA.  Over a `distance` other than KR the first line ends in distance_field(distance).
+std::string format_anosim_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals,
+                              const std::vector<std::string>& columns, const std::vector<std::vector<std::string>>& names,
+                              const uint32_t* labels, uint32_t num_permutations, uint64_t seed, const epik_amd_anosim* records,
+                              uint32_t distance = EPIK_AMD_DISTANCE_KR);
 /// The strata of --cohort-strata FILE [--cohort-strata-column NAME]: FILE is a TSV read by the factor reader (the same errors,
 /// naming line and column, under the flag's name) without a cap on the distinct labels; `column` picks the column and may be
 /// empty only if FILE has one.  strata[S]: the label ids of that column by first appearance; *name: the column's name.  Throws

@@ -50,9 +50,17 @@
 //   cohort_test model-tsv <out.tsv> <in.bin> <names.txt> <design.tsv> <terms> <P> <seed>
 //                                           the file of --cohort-model for a `kr` input whose samples are named by the lines of
 //                                           names.txt, through the design file's reader and the formatter
+//   cohort_test mantel <out.bin> <in.bin> <sides.bin> <strata.bin or -> <P> <seed>
+//                                           the Mantel tests of a `kr` input with a `sides` file, uint64 Mv, Mm, methods, control
+//                                           (0xffffffff: none), float64 values[Mv][S], float64 matrices[Mm][S][S], uint8
+//                                           present[Mm][S]: epik_amd_mantel [tests], float64 stat[tests][P + 1]
+//   cohort_test anosim <out.bin> <in.bin> <labels.bin> <strata.bin or -> <P> <seed>
+//                                           ANOSIM of a `kr` input with a raw `labels` file, uint32 [S][M]: epik_amd_anosim [M],
+//                                           float64 stat[M][P + 1]
 // An `add` input holds, little endian: uint64 n, keep, num_branches, num_samples; epik_amd_placement rows[n][keep];
 // uint32 n_rows[n]; uint32 kmer_counts[n][keep]; uint32 weights[n]; uint32 samples[n].
 // A `kr` input: uint64 num_samples, num_branches; uint64 mass[S][N]; uint32 first[N]; float64 branch_length[N].
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -560,6 +568,118 @@ int main(int argc, char** argv)
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
         }
+        if (argc == 8 && (std::strcmp(argv[1], "mantel") == 0 || std::strcmp(argv[1], "anosim") == 0)) {
+            const bool ranked = std::strcmp(argv[1], "anosim") == 0;
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto cells = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const auto lengths = read_array<double>(in, N);
+            const uint32_t P = (uint32_t)std::strtoul(argv[6], nullptr, 10);
+            const uint64_t seed = std::strtoull(argv[7], nullptr, 10);
+            if (P < 1 || P > EPIK_AMD_PERMANOVA_MAX_PERMUTATIONS) throw std::runtime_error("P is outside [1, 999999]");
+            std::vector<uint32_t> strata;
+            const bool stratified = std::strcmp(argv[5], "-") != 0;
+            if (stratified) strata = read_strata(argv[5], S);
+            std::ifstream side(argv[4], std::ios::binary | std::ios::ate);
+            if (!side) throw std::runtime_error(std::string("cannot open ") + argv[4]);
+            const uint64_t bytes = (uint64_t)side.tellg();
+            side.seekg(0);
+            std::string err;
+            std::ofstream out(argv[2], std::ios::binary);
+            if (ranked) {
+                if (bytes == 0 || bytes % (S * sizeof(uint32_t)) != 0) throw std::runtime_error("the labels file is not uint32 [S][M]");
+                const uint64_t M = bytes / (S * sizeof(uint32_t));
+                if (M > EPIK_AMD_PERMANOVA_MAX_COLUMNS) throw std::runtime_error("the labels file has more than 64 columns");
+                const auto labels = read_array<uint32_t>(side, S * M);
+                std::vector<epik_amd_anosim> records(M);
+                std::vector<double> stat(M * ((uint64_t)P + 1));
+                if (epik_amd::anosim_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), lengths.data(), labels.data(), (uint32_t)M,
+                                             P, seed, records.data(), stat.data(), err, EPIK_AMD_DISTANCE_KR,
+                                             stratified ? strata.data() : nullptr) != 0)
+                    throw std::runtime_error(err);
+                write_array(out, records.data(), records.size());
+                write_array(out, stat.data(), stat.size());
+            } else {
+                const auto shape = read_array<uint64_t>(side, 4);  // Mv, Mm, methods, control
+                if (shape[0] > EPIK_AMD_MANTEL_MAX_COLUMNS || shape[1] > EPIK_AMD_MANTEL_MAX_MATRICES)
+                    throw std::runtime_error("the sides file has more than 64 columns or 8 matrices");
+                const auto values = read_array<double>(side, shape[0] * S);
+                const auto matrices = read_array<double>(side, shape[1] * S * S);
+                const auto present = read_array<uint8_t>(side, shape[1] * S);
+                const epik_amd::mantel_sides sides{values.data(), (uint32_t)shape[0], matrices.data(), present.data(), (uint32_t)shape[1],
+                                                   (uint32_t)shape[2], (uint32_t)shape[3]};
+                if (const int rc = epik_amd::mantel_arguments_valid(sides, (uint32_t)S, P, err); rc != 0) throw std::runtime_error(err);
+                std::vector<epik_amd_mantel> records(sides.tests());
+                std::vector<double> stat(records.size() * ((uint64_t)P + 1));
+                if (epik_amd::mantel_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), lengths.data(), sides, P, seed,
+                                             records.data(), stat.data(), err, EPIK_AMD_DISTANCE_KR,
+                                             stratified ? strata.data() : nullptr) != 0)
+                    throw std::runtime_error(err);
+                write_array(out, records.data(), records.size());
+                write_array(out, stat.data(), stat.size());
+            }
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
+        // the files of --cohort-mantel and --cohort-anosim for a `kr` input whose samples are named by the lines of names.txt, through
+        // the drivers' readers and formatters: mantel-tsv <out.tsv> <in.bin> <names.txt> <meta.tsv or -> <NAME=FILE,... or ->
+        // <pearson|spearman|both> <partial NAME or -> <P> <seed>; anosim-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed>
+        if ((argc == 11 && std::strcmp(argv[1], "mantel-tsv") == 0) || (argc == 8 && std::strcmp(argv[1], "anosim-tsv") == 0)) {
+            const bool ranked = argc == 8;
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            const auto cells = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const auto lengths = read_array<double>(in, N);
+            std::vector<epik_amd::cohort_sample> samples;
+            std::ifstream names(argv[4]);
+            if (!names) throw std::runtime_error(std::string("cannot open ") + argv[4]);
+            for (std::string line; std::getline(names, line);) samples.push_back({line, ""});
+            if (samples.size() != S) throw std::runtime_error("names.txt does not name the samples of the input");
+            const uint32_t P = (uint32_t)std::strtoul(argv[argc - 2], nullptr, 10);
+            const uint64_t seed = std::strtoull(argv[argc - 1], nullptr, 10);
+            std::vector<uint64_t> totals(S, 0);
+            for (size_t s = 0; s < S; ++s)
+                for (size_t b = 0; b < N; ++b) totals[s] += cells[s * N + b];
+            std::string err;
+            if (ranked) {
+                const auto factors = epik_amd::read_cohort_factors(argv[5], samples, false, 0, "--cohort-anosim");
+                std::vector<epik_amd_anosim> records(factors.columns.size());
+                if (epik_amd::anosim_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), lengths.data(), factors.labels.data(),
+                                             (uint32_t)factors.columns.size(), P, seed, records.data(), nullptr, err) != 0)
+                    throw std::runtime_error(err);
+                epik_amd::write_through_part(argv[2], epik_amd::format_anosim_tsv(samples, totals.data(), factors.columns, factors.names,
+                                                                                  factors.labels.data(), P, seed, records.data()));
+                return 0;
+            }
+            std::vector<std::string> matrices;
+            if (std::strcmp(argv[6], "-") != 0) {
+                std::string list = argv[6];
+                for (size_t at = 0; at <= list.size();) {
+                    const size_t comma = std::min(list.find(',', at), list.size());
+                    matrices.push_back(list.substr(at, comma - at));
+                    at = comma + 1;
+                }
+            }
+            const uint32_t methods = epik_amd::mantel_methods_of_name(argv[7]);
+            if (!methods) throw std::runtime_error("the method must be pearson, spearman or both");
+            const auto read = epik_amd::read_cohort_mantel_sides(std::strcmp(argv[5], "-") == 0 ? "" : argv[5], matrices,
+                                                                 std::strcmp(argv[8], "-") == 0 ? "" : argv[8], samples);
+            const epik_amd::mantel_sides sides = read.sides(methods);
+            std::vector<epik_amd_mantel> records(sides.tests());
+            if (epik_amd::mantel_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), lengths.data(), sides, P, seed,
+                                         records.data(), nullptr, err) != 0)
+                throw std::runtime_error(err);
+            epik_amd::write_through_part(argv[2], epik_amd::format_mantel_tsv(samples, totals.data(), read.names, read.num_columns, methods,
+                                                                              read.control, P, seed, records.data()));
+            return 0;
+        }
         // the drivers' strata reader and header field: strata-read <out.bin> <names.txt> <strata.tsv> <column or -> writes
         // strata[S] and, after them, the column's name; strata-field <out.tsv> <in.tsv> <NAME> the file with the field
         if (argc == 6 && std::strcmp(argv[1], "strata-read") == 0) {
@@ -596,6 +716,10 @@ int main(int argc, char** argv)
                      "permanova-strata | permdisp-strata <out.bin> <in.bin> <labels.bin> <strata.bin> <P> <seed> <pairwise> | "
                      "edgetest-strata <out.bin> <in.bin> <labels.bin> <strata.bin> <P> <seed> | "
                      "model-strata <out.bin> <in.bin> <design.bin> <strata.bin> <P> <seed> | "
+                     "mantel <out.bin> <in.bin> <sides.bin> <strata.bin or -> <P> <seed> | "
+                     "anosim <out.bin> <in.bin> <labels.bin> <strata.bin or -> <P> <seed> | "
+                     "mantel-tsv <out.tsv> <in.bin> <names.txt> <meta.tsv or -> <NAME=FILE,... or -> <method> <partial or -> <P> <seed> | "
+                     "anosim-tsv <out.tsv> <in.bin> <names.txt> <factors.tsv> <P> <seed> | "
                      "strata-read <out.bin> <names.txt> <strata.tsv> <column or -> | strata-field <out.tsv> <in.tsv> <NAME>\n";
         return 2;
     } catch (const std::exception& error) {

@@ -279,6 +279,21 @@ const char* kHelp =
     "      --cohort-permdisp-permutations arg  With --cohort-permdisp: the number of permutations in [1, 999999] (default: 999)\n"
     "      --cohort-permdisp-seed arg  With --cohort-permdisp: the seed of the permutations, a uint64 (default: 1)\n"
     "      --cohort-permdisp-pairwise  With --cohort-permdisp: also test every two groups of every column\n"
+    "      --cohort-mantel arg  With --cohort: also test, for every column of the metadata TSV file arg (as --cohort-correlation's),\n"
+    "                          whether the distance between samples grows with the difference in the column: the Mantel test\n"
+    "                          (Mantel 1967, one-sided) by permutation on the device; cohort_mantel_<list>.tsv\n"
+    "      --cohort-mantel-matrix arg  With --cohort: NAME=FILE, a square TSV in the layout of cohort_kr_<list>.tsv as one more side\n"
+    "                          of the Mantel test (a sample of the list that it lacks is missing on that side); up to 8 times\n"
+    "      --cohort-mantel-method arg  With the Mantel test: pearson (default), spearman or both\n"
+    "      --cohort-mantel-partial arg  With the Mantel test: the column or matrix NAME held fixed: the partial Mantel test (Smouse,\n"
+    "                          Long & Sokal 1986) of every other side\n"
+    "      --cohort-mantel-permutations arg  With the Mantel test: the number of permutations in [1, 999999] (default: 999)\n"
+    "      --cohort-mantel-seed arg  With the Mantel test: the seed of the permutations, a uint64 (default: 1)\n"
+    "      --cohort-anosim arg  With --cohort: also test, for every factor column of the TSV file arg (as --cohort-permanova's),\n"
+    "                          whether the ranked distances between its groups exceed those within: ANOSIM (Clarke 1993) on the\n"
+    "                          device; cohort_anosim_<list>.tsv\n"
+    "      --cohort-anosim-permutations arg  With --cohort-anosim: the number of permutations in [1, 999999] (default: 999)\n"
+    "      --cohort-anosim-seed arg  With --cohort-anosim: the seed of the permutations, a uint64 (default: 1)\n"
     "      --cohort-model arg     With --cohort: also fit, on the device, the sequential model adonis2(D ~ term1 + term2 + ...,\n"
     "                          by = \"terms\") over the columns of the TSV file arg (as --cohort-permanova's) that\n"
     "                          --cohort-model-terms names; cohort_model_<list>.tsv\n"
@@ -301,6 +316,7 @@ const char* kHelp =
 
 struct options {
     std::map<std::string, std::string> values;
+    std::vector<std::string> matrices;  // every --cohort-mantel-matrix, the one flag that may be repeated
     bool has(const std::string& k) const { return values.count(k) != 0; }
     std::string get(const std::string& k, const std::string& def) const
     {
@@ -345,6 +361,7 @@ options parse_args(int argc, char** argv)
             if (i + 1 >= argc) throw std::runtime_error("Option '" + name + "' is missing an argument");
             value = argv[++i];
         }
+        if (name == "cohort-mantel-matrix") opt.matrices.push_back(value);  // (may be repeated: every argument, in order)
         opt.values[name] = value;
     }
     return opt;
@@ -581,6 +598,43 @@ int main(int argc, char** argv)
             if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-permdisp-seed " + text + ": not a uint64");
             permdisp_seed = v;
         }
+        // the Mantel test and ANOSIM: checked before anything is opened or any device touched
+        const bool with_mantel = parsed.has("cohort-mantel") || parsed.has("cohort-mantel-matrix"), with_anosim = parsed.has("cohort-anosim");
+        for (const char* flag : {"cohort-mantel", "cohort-mantel-matrix", "cohort-anosim"})
+            if (parsed.has(flag) && !with_cohort)
+                throw std::runtime_error(std::string("--") + flag + " needs --cohort (it tests the distances between the samples of the list)");
+        for (const char* dependent : {"cohort-mantel-method", "cohort-mantel-partial", "cohort-mantel-permutations", "cohort-mantel-seed"})
+            if (parsed.has(dependent) && !with_mantel)
+                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-mantel or --cohort-mantel-matrix" +
+                                         (with_cohort ? "" : " (and they need --cohort )"));
+        for (const char* dependent : {"cohort-anosim-permutations", "cohort-anosim-seed"})
+            if (parsed.has(dependent) && !with_anosim)
+                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-anosim" +
+                                         (with_cohort ? "" : " (and that needs --cohort )"));
+        const auto permutations_of = [&](const char* flag) -> uint32_t {
+            if (!parsed.has(flag)) return 999;
+            const std::string text = parsed.require(flag);
+            char* end = nullptr;
+            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
+            if (!end || *end || v < 1 || v > EPIK_AMD_PERMANOVA_MAX_PERMUTATIONS)
+                throw std::runtime_error(std::string("--") + flag + " " + text + ": the number must lie in [1, 999999]");
+            return (uint32_t)v;
+        };
+        const auto seed_of = [&](const char* flag) -> uint64_t {
+            if (!parsed.has(flag)) return 1;
+            const std::string text = parsed.require(flag);
+            char* end = nullptr;
+            errno = 0;
+            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
+            if (!end || *end || errno == ERANGE) throw std::runtime_error(std::string("--") + flag + " " + text + ": not a uint64");
+            return v;
+        };
+        const uint32_t mantel_permutations = permutations_of("cohort-mantel-permutations");
+        const uint32_t anosim_permutations = permutations_of("cohort-anosim-permutations");
+        const uint64_t mantel_seed = seed_of("cohort-mantel-seed"), anosim_seed = seed_of("cohort-anosim-seed");
+        const uint32_t mantel_methods = epik_amd::mantel_methods_of_name(parsed.get("cohort-mantel-method", "pearson"));
+        if (!mantel_methods)
+            throw std::runtime_error("--cohort-mantel-method must be pearson, spearman or both, not '" + parsed.require("cohort-mantel-method") + "'");
         const bool with_model = parsed.has("cohort-model");
         if (with_model && !with_cohort)
             throw std::runtime_error("--cohort-model needs --cohort (it fits a model of the samples of the list)");
@@ -616,7 +670,7 @@ int main(int argc, char** argv)
             with_unifrac ? epik_amd::parse_unifrac_list(parsed.require("cohort-unifrac")) : std::vector<uint32_t>{};
         uint32_t cohort_distance = EPIK_AMD_DISTANCE_KR;
         if (parsed.has("cohort-distance")) {
-            if (!with_permanova && !with_pcoa && !with_permdisp && !with_model)
+            if (!with_permanova && !with_pcoa && !with_permdisp && !with_model && !with_mantel && !with_anosim)
                 throw std::runtime_error("--cohort-distance needs --cohort-permanova, --cohort-pcoa or --cohort-permdisp (the analyses that "
                                          "run over a distance; --cohort-model is one too)");
             const std::string name = parsed.require("cohort-distance");
@@ -628,7 +682,7 @@ int main(int argc, char** argv)
         const bool with_strata = parsed.has("cohort-strata");
         if (parsed.has("cohort-strata-column") && !with_strata)
             throw std::runtime_error("--cohort-strata-column needs --cohort-strata (it names a column of that file)");
-        if (with_strata && !(with_permanova || with_permdisp || with_edgetest || with_model))
+        if (with_strata && !(with_permanova || with_permdisp || with_edgetest || with_model || with_mantel || with_anosim))
             throw std::runtime_error("--cohort-strata needs --cohort-permanova, --cohort-permdisp, --cohort-edge-test or --cohort-model "
                                      "(the tests that permute samples)");
         if (with_edgetest && !with_cohort)
@@ -738,6 +792,22 @@ int main(int argc, char** argv)
             disp_factors = epik_amd::read_cohort_factors(parsed.require("cohort-permdisp"), cohort_samples, false,
                                                          EPIK_AMD_PERMDISP_MAX_GROUPS, "--cohort-permdisp");
             std::cout << "Cohort PERMDISP factors: " << disp_factors.columns.size() << " columns, " << disp_factors.skipped
+                      << " lines of samples that are not in the list skipped" << std::endl;
+        }
+
+        // --cohort-mantel / --cohort-mantel-matrix and --cohort-anosim: the sides and the factors read, every error named by its
+        // line, before the database or a device is
+        epik_amd::cohort_mantel_sides mantel_read;
+        if (with_mantel) {
+            mantel_read = epik_amd::read_cohort_mantel_sides(parsed.get("cohort-mantel", ""), parsed.matrices,
+                                                             parsed.get("cohort-mantel-partial", ""), cohort_samples);
+            std::cout << "Cohort Mantel sides: " << mantel_read.num_columns << " columns, " << mantel_read.num_matrices << " matrices, "
+                      << mantel_read.skipped << " lines of samples that are not in the list skipped" << std::endl;
+        }
+        epik_amd::cohort_factors anosim_factors;
+        if (with_anosim) {
+            anosim_factors = epik_amd::read_cohort_factors(parsed.require("cohort-anosim"), cohort_samples, false, 0, "--cohort-anosim");
+            std::cout << "Cohort ANOSIM factors: " << anosim_factors.columns.size() << " columns, " << anosim_factors.skipped
                       << " lines of samples that are not in the list skipped" << std::endl;
         }
 
@@ -1140,6 +1210,8 @@ int main(int argc, char** argv)
         const auto cohort_edgetest_filename = epik_amd::make_cohort_filename("edgetest", query_file, output_dir);
         const auto cohort_permdisp_filename = epik_amd::make_cohort_filename("permdisp", query_file, output_dir);
         const auto cohort_model_filename = epik_amd::make_cohort_filename("model", query_file, output_dir);
+        const auto cohort_mantel_filename = epik_amd::make_cohort_filename("mantel", query_file, output_dir);
+        const auto cohort_anosim_filename = epik_amd::make_cohort_filename("anosim", query_file, output_dir);
         size_t model_aliased = 0;
         const auto cohort_unifrac_filename = [&](uint32_t metric) {
             return epik_amd::make_cohort_filename(std::string("unifrac_") + epik_amd::distance_name(metric), query_file, output_dir);
@@ -1180,6 +1252,14 @@ int main(int argc, char** argv)
             model.kind = design.kind.data(), model.labels = design.labels.data(), model.values = design.values.data();
             model.num_terms = (uint32_t)design.terms.size(), model.num_permutations = model_permutations, model.seed = model_seed;
             model.strata = within;
+            epik_amd::placer::cohort_mantel mantel;
+            mantel.values = mantel_read.values.data(), mantel.matrices = mantel_read.matrices.data(), mantel.present = mantel_read.present.data();
+            mantel.num_columns = mantel_read.num_columns, mantel.num_matrices = mantel_read.num_matrices, mantel.methods = mantel_methods;
+            mantel.control = mantel_read.control, mantel.num_permutations = mantel_permutations, mantel.seed = mantel_seed;
+            mantel.strata = within;
+            epik_amd::placer::cohort_anosim anosim;
+            anosim.labels = anosim_factors.labels.data(), anosim.num_columns = (uint32_t)anosim_factors.columns.size();
+            anosim.num_permutations = anosim_permutations, anosim.seed = anosim_seed, anosim.strata = within;
             // a factor that is constant inside every stratum of its used samples: no permutation changes anything, p = 1
             const auto warn_nested = [&](const char* flag, const std::vector<std::string>& columns, const uint32_t* labels, uint32_t missing,
                                          const std::vector<uint64_t>& mass_of) {
@@ -1194,7 +1274,7 @@ int main(int argc, char** argv)
                                with_permanova ? &permanova : nullptr, with_edgetest ? &edgetest : nullptr, with_pcoa ? &pcoa : nullptr,
                                with_permdisp ? &permdisp : nullptr,
                                with_unifrac || cohort_distance != EPIK_AMD_DISTANCE_KR ? &unifrac : nullptr,
-                               with_model ? &model : nullptr);
+                               with_model ? &model : nullptr, with_mantel ? &mantel : nullptr, with_anosim ? &anosim : nullptr);
             for (size_t i = 0; i < unifrac_metrics.size(); ++i)
                 epik_amd::write_through_part(cohort_unifrac_filename(unifrac_metrics[i]),
                                              epik_amd::format_cohort_unifrac_tsv(cohort_samples, unifrac.matrix[i]));
@@ -1231,10 +1311,10 @@ int main(int argc, char** argv)
                 epik_amd::write_through_part(cohort_rarefy_filename, epik_amd::format_rarefy_tsv(cohort_samples, reads.data(), rarefy_step,
                                                                                                  rarefy_depths, diversity.curve.data()));
             }
+            std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's: what the files below take)
+            for (size_t s = 0; s < mass_of.size(); ++s)
+                for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
             if (with_correlation || with_dispersion) {
-                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
-                for (size_t s = 0; s < mass_of.size(); ++s)
-                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
                 if (with_correlation)
                     epik_amd::write_through_part(cohort_correlation_filename,
                                                  epik_amd::format_correlation_tsv(cohort_samples, mass_of.data(), metadata.columns,
@@ -1246,9 +1326,6 @@ int main(int argc, char** argv)
                                                                                  edges.dispersion.data()));
             }
             if (with_permanova) {
-                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
-                for (size_t s = 0; s < mass_of.size(); ++s)
-                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
                 epik_amd::write_through_part(
                     cohort_permanova_filename,
                     epik_amd::with_strata_field(epik_amd::format_permanova_tsv(cohort_samples, mass_of.data(), factors.columns, factors.names,
@@ -1259,9 +1336,6 @@ int main(int argc, char** argv)
                 warn_nested("--cohort-permanova", factors.columns, factors.labels.data(), EPIK_AMD_PERMANOVA_MISSING, mass_of);
             }
             if (with_edgetest) {
-                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
-                for (size_t s = 0; s < mass_of.size(); ++s)
-                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
                 epik_amd::write_through_part(
                     cohort_edgetest_filename,
                     epik_amd::with_strata_field(epik_amd::format_edgetest_tsv(cohort_samples, mass_of.data(), edge_factors.columns,
@@ -1272,9 +1346,6 @@ int main(int argc, char** argv)
                 warn_nested("--cohort-edge-test", edge_factors.columns, edge_factors.labels.data(), EPIK_AMD_EDGETEST_MISSING, mass_of);
             }
             if (with_permdisp) {
-                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
-                for (size_t s = 0; s < mass_of.size(); ++s)
-                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
                 epik_amd::write_through_part(
                     cohort_permdisp_filename,
                     epik_amd::with_strata_field(epik_amd::format_permdisp_tsv(cohort_samples, mass_of.data(), disp_factors.columns,
@@ -1287,10 +1358,27 @@ int main(int argc, char** argv)
                 const size_t slots = permdisp.records.size() / disp_factors.columns.size();
                 for (size_t c = 0; c < disp_factors.columns.size(); ++c) permdisp_clipped += permdisp.records[c * slots].clipped;
             }
+            if (with_mantel || with_anosim) {
+                if (with_mantel)
+                    epik_amd::write_through_part(
+                        cohort_mantel_filename,
+                        epik_amd::with_strata_field(epik_amd::format_mantel_tsv(cohort_samples, mass_of.data(), mantel_read.names,
+                                                                                mantel_read.num_columns, mantel_methods, mantel_read.control,
+                                                                                mantel_permutations, mantel_seed, mantel.records.data(),
+                                                                                cohort_distance),
+                                                    strata_name));
+                if (with_anosim) {
+                    epik_amd::write_through_part(
+                        cohort_anosim_filename,
+                        epik_amd::with_strata_field(epik_amd::format_anosim_tsv(cohort_samples, mass_of.data(), anosim_factors.columns,
+                                                                                anosim_factors.names, anosim_factors.labels.data(),
+                                                                                anosim_permutations, anosim_seed, anosim.records.data(),
+                                                                                cohort_distance),
+                                                    strata_name));
+                    warn_nested("--cohort-anosim", anosim_factors.columns, anosim_factors.labels.data(), EPIK_AMD_PERMANOVA_MISSING, mass_of);
+                }
+            }
             if (with_model) {
-                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
-                for (size_t s = 0; s < mass_of.size(); ++s)
-                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
                 epik_amd::write_through_part(
                     cohort_model_filename,
                     epik_amd::with_strata_field(epik_amd::format_model_tsv(cohort_samples, mass_of.data(), design, model_permutations,
@@ -1312,9 +1400,6 @@ int main(int argc, char** argv)
                 for (const uint8_t byte : model.aliased) model_aliased += byte;
             }
             if (with_pcoa) {
-                std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's)
-                for (size_t s = 0; s < mass_of.size(); ++s)
-                    for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
                 epik_amd::write_through_part(cohort_pcoa_filename, epik_amd::format_pcoa_tsv(cohort_samples, mass_of.data(), pcoa.num_components,
                                                                                              pcoa.mu.data(), pcoa.coord.data(), pcoa.info,
                                                                                              cohort_distance));
@@ -1400,6 +1485,8 @@ int main(int argc, char** argv)
         if (with_permanova) std::cout << "Cohort PERMANOVA: " << cohort_permanova_filename << std::endl;
         if (with_edgetest) std::cout << "Cohort edge test: " << cohort_edgetest_filename << std::endl;
         if (with_permdisp) std::cout << "Cohort PERMDISP: " << cohort_permdisp_filename << std::endl;
+        if (with_mantel) std::cout << "Cohort Mantel: " << cohort_mantel_filename << std::endl;
+        if (with_anosim) std::cout << "Cohort ANOSIM: " << cohort_anosim_filename << std::endl;
         if (with_model) std::cout << "Cohort model: " << cohort_model_filename << std::endl;
         if (model_aliased)
             std::cout << "Warning: " << model_aliased << " columns of the design are explained by the columns before them and were "

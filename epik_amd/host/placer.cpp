@@ -51,6 +51,8 @@
 #pragma weak epik_amd_cohort_permdisp_strata
 #pragma weak epik_amd_cohort_edgetest_strata
 #pragma weak epik_amd_cohort_model_strata
+#pragma weak epik_amd_cohort_mantel
+#pragma weak epik_amd_cohort_anosim
 #pragma weak epik_amd_placer_cohort_reads
 #pragma weak epik_amd_placer_cohort_strands
 #pragma weak epik_amd_placer_cohort_frames
@@ -307,8 +309,10 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
                          epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans,
                          cohort_diversity* diversity, cohort_edges* edges, cohort_permanova* permanova,
                          cohort_edgetest* edgetest, cohort_pcoa* pcoa, cohort_permdisp* permdisp, cohort_unifrac* unifrac,
-                         cohort_model* model)
+                         cohort_model* model, cohort_mantel* mantel, cohort_anosim* anosim)
 {
+    if ((mantel && !&epik_amd_cohort_mantel) || (anosim && !&epik_amd_cohort_anosim))
+        throw std::runtime_error("GPU placer: this libepik_amd has no Mantel test or no ANOSIM");
     if (model && !&epik_amd_cohort_model_metric) throw std::runtime_error("GPU placer: this libepik_amd has no sequential model");
     if (((permanova && permanova->strata) || (permdisp && permdisp->strata) || (edgetest && edgetest->strata) || (model && model->strata)) &&
         (!&epik_amd_cohort_permanova_strata || !&epik_amd_cohort_permdisp_strata || !&epik_amd_cohort_edgetest_strata ||
@@ -454,6 +458,18 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
                  : epik_amd_cohort_model_metric(_cohorts[0], tree, length.data(), distance, model->kind, model->labels, model->values,
                                                 model->num_terms, model->num_permutations, model->seed, model->records.data(),
                                                 &model->info, nullptr, model->aliased.data());
+    }
+    if (rc == EPIK_AMD_OK && mantel) {
+        const size_t per_side = (mantel->methods & 1u) + (mantel->methods >> 1 & 1u);
+        mantel->records.assign(((size_t)mantel->num_columns + mantel->num_matrices) * per_side, epik_amd_mantel{});
+        rc = epik_amd_cohort_mantel(_cohorts[0], tree, length.data(), distance, mantel->values, mantel->num_columns, mantel->matrices,
+                                    mantel->present, mantel->num_matrices, mantel->methods, mantel->control, mantel->num_permutations,
+                                    mantel->seed, mantel->strata, mantel->records.data(), nullptr);
+    }
+    if (rc == EPIK_AMD_OK && anosim) {
+        anosim->records.assign(anosim->num_columns, epik_amd_anosim{});
+        rc = epik_amd_cohort_anosim(_cohorts[0], tree, length.data(), distance, anosim->labels, anosim->num_columns,
+                                    anosim->num_permutations, anosim->seed, anosim->strata, anosim->records.data(), nullptr);
     }
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);

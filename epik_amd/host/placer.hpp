@@ -264,11 +264,33 @@ public:
         uint32_t distance = EPIK_AMD_DISTANCE_KR;
         std::vector<std::vector<double>> matrix;
     };
+    /// With `mantel` (--cohort-mantel, --cohort-mantel-matrix): the Mantel tests of the sides values[Mv][S], matrices[Mm][S][S] and
+    /// present[Mm][S] with the methods' bits and the control, num_permutations permutations from `seed`; records of
+    /// Q * popcount(methods) tests on return.  With `anosim` (--cohort-anosim): ANOSIM of labels[S][M]; records of M columns.  Both
+    /// run over the distance of `unifrac`, KR without one.
+    struct cohort_mantel {
+        const double* values = nullptr;
+        const double* matrices = nullptr;
+        const uint8_t* present = nullptr;
+        uint32_t num_columns = 0, num_matrices = 0, methods = EPIK_AMD_MANTEL_PEARSON, control = EPIK_AMD_MANTEL_NO_CONTROL;
+        uint32_t num_permutations = 999;
+        uint64_t seed = 1;
+        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
+        std::vector<epik_amd_mantel> records;
+    };
+    struct cohort_anosim {
+        const uint32_t* labels = nullptr;
+        uint32_t num_columns = 0, num_permutations = 999;
+        uint64_t seed = 1;
+        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
+        std::vector<epik_amd_anosim> records;
+    };
     void read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
                      epik_amd_squash_merge* merges = nullptr, uint32_t* num_merges = nullptr, cohort_epca* epca = nullptr,
                      cohort_kmeans* kmeans = nullptr, cohort_diversity* diversity = nullptr, cohort_edges* edges = nullptr,
                      cohort_permanova* permanova = nullptr, cohort_edgetest* edgetest = nullptr, cohort_pcoa* pcoa = nullptr,
-                     cohort_permdisp* permdisp = nullptr, cohort_unifrac* unifrac = nullptr, cohort_model* model = nullptr);
+                     cohort_permdisp* permdisp = nullptr, cohort_unifrac* unifrac = nullptr, cohort_model* model = nullptr,
+                     cohort_mantel* mantel = nullptr, cohort_anosim* anosim = nullptr);
     /// --taxonomy: one device taxonomy object per handle (epik_amd_taxonomy) from taxon_parent[T] and label[N], with one
     /// row of cells per sample of the cohort (call set_cohort first) or one row; from then on place_flat goes through
     /// the epik_amd_placer_taxa_* entries: every unique sequence is added with the number of its records as weight, a

@@ -913,6 +913,53 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *     labelling is lambda, so every permuted statistic is the observed one and p = 1 (PERMDISP's permuted statistic is eta_r
  *     of the residuals, not eta2 of z: there every eta_r(mu^p) is eta_r(lambda)).
  *
+ * Mantel, partial Mantel and ANOSIM (Mantel 1967, `mantel`; Smouse, Long & Sokal 1986, `mantel.partial`; Clarke 1993,
+ *   `anosim`): does the distance between samples grow with the difference in a variable or with another distance, with a
+ *   third held fixed; and are the ranked distances between groups larger than within them?  From the matrix D[S][S] of the
+ *   chosen distance, T_s, P = num_permutations in [1, 999 999], a uint64 seed and, optionally, strata[S].  S is at most
+ *   EPIK_AMD_MANTEL_MAX_SAMPLES = 8 192.  All arithmetic is IEEE double, every operation rounded on its own, nothing fused;
+ *   + - * / sqrt and comparisons only.  NA is EPIK_AMD_NA_BITS, written and never computed.
+ *   Sides.  values[Mv][S], Mv <= EPIK_AMD_MANTEL_MAX_COLUMNS = 64: side q < Mv is the column q of per-sample numbers, NaN
+ *     means missing (an infinity is refused, and so is a column whose largest value less its smallest overflows, so every
+ *     distance is finite); its distance is |v_s - v_t|, one subtraction and the absolute value.
+ *     matrices[Mm][S][S] with matrix_present[Mm][S] (a byte a sample, 0: missing), Mm <= EPIK_AMD_MANTEL_MAX_MATRICES = 8:
+ *     side Mv + k is matrix k, of which only the cells [s][t], s < t, are read (a cell between two present samples that is
+ *     negative or not finite is refused).  Q = Mv + Mm >= 1.  methods: bit 0 pearson, bit 1 spearman, at least one.  control: a
+ *     side, or EPIK_AMD_MANTEL_NO_CONTROL = 0xffffffff.  The tests are (side q, method) in side-major order, pearson before
+ *     spearman: Q * popcount(methods) records.  With a control z every side q != z is tested with z held fixed (partial = 1);
+ *     the control itself is tested plainly.
+ *   List.  A test uses the samples with T_s > 0 that are present on its side and, if partial, on the control, in ascending
+ *     s: the positions 0 .. n - 1, u_i the sample of position i.  The pairs are (i, j), i < j, i-major; m = n (n - 1) / 2.
+ *   Triangle chain.  Every sum over the pairs is taken in two steps: t_i = the sequential chain over j = i + 1 .. n - 1,
+ *     ascending, from +0.0; then the sequential chain of t_0 .. t_{n-2} from +0.0.  Rows may run in parallel; no chain is split.
+ *   Values.  x(i, j) = D[u_i][u_j], y(i, j) the side's distance of (u_i, u_j), z(i, j) the control's, each for i < j (so
+ *     s = u_i < t = u_j).  For spearman each of x, y, z is first replaced by its midranks among its own m values: less +
+ *     (equal + 1) / 2, the correlation rule's two counts.
+ *   Moments.  For a in x, y, z: mean_a = chain(a) / (double)m,  a' = a - mean_a,  ss_a = chain(a' * a').  For two of them
+ *     s_ab = chain(a' * b')  and  r_ab = s_ab / sqrt(ss_a * ss_b).
+ *   Statistic.  Plain: stat = r = r_xy; r_xz and r_yz are NA.  Partial: r = r_xy, r_xz, r_yz, and
+ *       stat = (r_xy - r_xz * r_yz) / (sqrt(1.0 - r_xz * r_xz) * sqrt(1.0 - r_yz * r_yz)).
+ *   Permutations.  For p = 1 .. P, sigma_p is the PERMANOVA rule's rank_p over the n positions, with strata the strata rule's
+ *     sigma_p: the same shuffles for the same seed.  x'_p(i, j) = x'(sigma_p(i), sigma_p(j)) (x' is symmetric), s_xy and, if
+ *     partial, s_xz are the chains over x'_p; the means, every ss and r_yz do not move.  stat_p is the statistic of these.  A
+ *     partial permutation whose 1.0 - r_xz * r_xz is not > 0.0 has stat_p = NA and is not counted.
+ *       at_least = #{p in 1 .. P : stat_p >= stat_0},     p = (double)(1 + at_least) / (double)(P + 1)     (one-sided).
+ *   Undefined.  Unless n >= 3, ss_x != 0.0, ss_y != 0.0 and, if partial, ss_z != 0.0 and both radicands > 0.0: every double
+ *     of the record is NA and at_least = 0 (used = n, side, method and partial are still written).
+ *   Results.  out[Q * popcount(methods)] of epik_amd_mantel; stat[tests][P + 1], where asked for: stat_p for p = 0 .. P, NA for
+ *     an undefined test.  Every cell of every output is written.
+ *   ANOSIM.  Per column c of labels[S][M] (the PERMANOVA rule's labels, U_c, positions, groups by first appearance, G, n_g and
+ *     lambda).  x is the midranks of D over the m pairs of the column's list.  lambda^p_i = lambda_{sigma_p(i)}, the PERMANOVA
+ *     rule's labellings (sigma_p the strata rule's with strata).  W_p = the sum of x(i, j) over the pairs with lambda^p_i ==
+ *     lambda^p_j; m_W = sum over g of n_g (n_g - 1) / 2, m_B = m - m_W.  Twice a midrank is an integer and every sum here is
+ *     exact in a double (m (m + 1) < 2^53), so its order is free.
+ *       mean_within_p = W_p / (double)m_W,   mean_between_p = ((double)(m (m + 1) / 2) - W_p) / (double)m_B,
+ *       R_p = (mean_between_p - mean_within_p) / ((double)m / 2.0),
+ *       at_least = #{p in 1 .. P : R_p >= R_0},     p = (double)(1 + at_least) / (double)(P + 1).
+ *     The record has r = R_0, mean_between and mean_within of p = 0.  Defined iff G >= 2 and m_W >= 1; otherwise every double is
+ *     NA and at_least = 0 (used = L and groups = G are still written).  out[M] of epik_amd_anosim; stat[M][P + 1], where asked
+ *     for: R_p, NA for an undefined column.
+ *
  * Principal coordinates (Gower 1966; classical scaling, `cmdscale`, `pcoa`) of the cohort's samples over the KR distances:
  *   the ordination in which beta diversity is drawn.  From the matrix KR[S][S] of the KR rule, T_s and K in [1, 64].  The KR
  *   distance on a tree is not Euclidean, so the doubly centred matrix may be indefinite: the negative eigenvalues are
@@ -1352,6 +1399,58 @@ int epik_amd_cohort_permanova_strata_kr_host(const double *kr, const uint64_t *t
                                              const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations,
                                              uint64_t seed, int pairwise, epik_amd_permanova *out, double *ssw, double *group_ss,
                                              const uint32_t *strata);
+/* Mantel, partial Mantel and ANOSIM (the rule above).  The sides, labels and strata are host memory (strata NULL: none; values
+ * or matrices NULL with a count of 0); stat may be NULL.  _device: over d_dist, float64 [S][S] in device memory as kr_device or
+ * unifrac_device wrote it for this cohort, into d_out and d_stat in device memory, asynchronous on `stream` once the sides are
+ * copied, no readback.  The entry with tree and lengths runs the distance `metric` itself, synchronous, into host memory.
+ * _host: the rule on the host from the cells; _kr_host: from a matrix and totals[S].  S > 8 192, a count outside its range, a
+ * control that names no side, or a null pointer: EPIK_AMD_ERR_INVALID, nothing written. */
+typedef struct epik_amd_mantel {
+    uint32_t used, side, method, partial; /* n; the side q; 0 pearson, 1 spearman; 1 with the control held fixed */
+    uint64_t at_least;                    /* #{p >= 1 : stat_p >= stat_0} */
+    double r, r_xz, r_yz, stat, p;
+} epik_amd_mantel; /* 64 bytes */
+typedef struct epik_amd_anosim {
+    uint32_t used, groups; /* L and G of the column */
+    uint64_t at_least;     /* #{p >= 1 : R_p >= R_0} */
+    double r, mean_between, mean_within, p;
+} epik_amd_anosim; /* 48 bytes */
+#define EPIK_AMD_MANTEL_MAX_SAMPLES 8192u
+#define EPIK_AMD_MANTEL_MAX_COLUMNS 64u
+#define EPIK_AMD_MANTEL_MAX_MATRICES 8u
+#define EPIK_AMD_MANTEL_PEARSON 1u
+#define EPIK_AMD_MANTEL_SPEARMAN 2u
+#define EPIK_AMD_MANTEL_NO_CONTROL 0xffffffffu
+int epik_amd_cohort_mantel_device(epik_amd_cohort *cohort, const void *d_dist, const double *values, uint32_t num_columns,
+                                  const double *matrices, const uint8_t *matrix_present, uint32_t num_matrices, uint32_t methods,
+                                  uint32_t control, uint32_t num_permutations, uint64_t seed, const uint32_t *strata, void *d_out,
+                                  void *d_stat, void *stream);
+int epik_amd_cohort_mantel(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                           const double *values, uint32_t num_columns, const double *matrices, const uint8_t *matrix_present,
+                           uint32_t num_matrices, uint32_t methods, uint32_t control, uint32_t num_permutations, uint64_t seed,
+                           const uint32_t *strata, epik_amd_mantel *out, double *stat);
+int epik_amd_cohort_mantel_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                const double *branch_length, uint32_t metric, const double *values, uint32_t num_columns,
+                                const double *matrices, const uint8_t *matrix_present, uint32_t num_matrices, uint32_t methods,
+                                uint32_t control, uint32_t num_permutations, uint64_t seed, const uint32_t *strata,
+                                epik_amd_mantel *out, double *stat);
+int epik_amd_cohort_mantel_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const double *values,
+                                   uint32_t num_columns, const double *matrices, const uint8_t *matrix_present,
+                                   uint32_t num_matrices, uint32_t methods, uint32_t control, uint32_t num_permutations,
+                                   uint64_t seed, const uint32_t *strata, epik_amd_mantel *out, double *stat);
+int epik_amd_cohort_anosim_device(epik_amd_cohort *cohort, const void *d_dist, const uint32_t *labels, uint32_t num_columns,
+                                  uint32_t num_permutations, uint64_t seed, const uint32_t *strata, void *d_out, void *d_stat,
+                                  void *stream);
+int epik_amd_cohort_anosim(epik_amd_cohort *cohort, const epik_amd_tree *tree, const double *branch_length, uint32_t metric,
+                           const uint32_t *labels, uint32_t num_columns, uint32_t num_permutations, uint64_t seed,
+                           const uint32_t *strata, epik_amd_anosim *out, double *stat);
+int epik_amd_cohort_anosim_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                const double *branch_length, uint32_t metric, const uint32_t *labels, uint32_t num_columns,
+                                uint32_t num_permutations, uint64_t seed, const uint32_t *strata, epik_amd_anosim *out,
+                                double *stat);
+int epik_amd_cohort_anosim_kr_host(const double *kr, const uint64_t *totals, uint32_t num_samples, const uint32_t *labels,
+                                   uint32_t num_columns, uint32_t num_permutations, uint64_t seed, const uint32_t *strata,
+                                   epik_amd_anosim *out, double *stat);
 typedef struct epik_amd_pcoa_info {
     uint32_t used, components; /* L, and K' = min(K, L) */
     uint32_t sweeps, converged;
