@@ -35,6 +35,9 @@ branch ANOVA and Kruskal-Wallis of mass and imbalance by permutation, max-statis
 most 32 labels a column) differ in spread (PERMDISP: distances to group centroids, permutation of residuals),
 cohort_permdisp_<list>.tsv; --cohort-permdisp-permutations P (default 999), --cohort-permdisp-seed X (default 1),
 --cohort-permdisp-pairwise.
+--cohort-edge-model FILE --cohort-edge-model-terms LIST, with --cohort: the same design fitted to every branch's mass share and
+imbalance by permutation, with the max-statistic adjustment over the branches, cohort_edgemodel_<list>.tsv;
+--cohort-edge-model-permutations P (default 999), --cohort-edge-model-seed X (default 1).
 --cohort-model FILE --cohort-model-terms LIST, with --cohort: the sequential model adonis2(D ~ term1 + term2 + ..., by = "terms")
 over the columns of FILE (a TSV, as --cohort-permanova's) that LIST names, comma-separated f:NAME (a factor) or n:NAME (a
 numeric covariate) in test order, cohort_model_<list>.tsv; --cohort-model-permutations P (default 999), --cohort-model-seed X
@@ -175,6 +178,16 @@ PLACE_OPTIONS = [
     (("--cohort-permdisp-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
                                        help="With --cohort-permdisp: the seed of the permutations, a uint64 [default: 1].")),
     (("--cohort-permdisp-pairwise",), dict(is_flag=True, help="With --cohort-permdisp: also test every two groups of every column.")),
+    (("--cohort-edge-model",), dict(type=click.Path(), default=None,
+                                    help="With --cohort: a TSV as --cohort-model's; also fit on the device the sequential linear model "
+                                         "of --cohort-edge-model-terms to every branch's mass share and imbalance, by permutation, "
+                                         "and write cohort_edgemodel_<list>.tsv.")),
+    (("--cohort-edge-model-terms",), dict(type=str, default=None,
+                                          help="With --cohort-edge-model (required): the terms in test order, as --cohort-model-terms.")),
+    (("--cohort-edge-model-permutations",), dict(type=click.IntRange(1, 999999), default=None,
+                                                 help="With --cohort-edge-model: the number of permutations [default: 999].")),
+    (("--cohort-edge-model-seed",), dict(type=click.IntRange(0, (1 << 64) - 1), default=None,
+                                         help="With --cohort-edge-model: the seed of the permutations, a uint64 [default: 1].")),
     (("--cohort-model",), dict(type=click.Path(), default=None,
                                help="With --cohort: a TSV of factors and covariates (laid out as --cohort-permanova's): also fit on "
                                     "the device the sequential model of the terms of --cohort-model-terms, each tested after the "
@@ -261,6 +274,7 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                    cohort_pcoa=False, cohort_pcoa_components=None, cohort_permdisp=None, cohort_permdisp_permutations=None,
                    cohort_permdisp_seed=None, cohort_permdisp_pairwise=False, cohort_unifrac=None, cohort_distance=None,
                    cohort_model=None, cohort_model_terms=None, cohort_model_permutations=None, cohort_model_seed=None,
+                   cohort_edge_model=None, cohort_edge_model_terms=None, cohort_edge_model_permutations=None, cohort_edge_model_seed=None,
                    cohort_strata=None, cohort_strata_column=None, cohort_mantel=None, cohort_mantel_matrix=(),
                    cohort_mantel_method=None, cohort_mantel_partial=None, cohort_mantel_permutations=None, cohort_mantel_seed=None,
                    cohort_anosim=None, cohort_anosim_permutations=None, cohort_anosim_seed=None):
@@ -349,10 +363,19 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
             raise click.UsageError(f"{flag} needs --cohort-model")
     if cohort_model is not None and cohort_model_terms is None:
         raise click.UsageError("--cohort-model needs --cohort-model-terms")
+    if cohort_edge_model is not None and not cohort:
+        raise click.UsageError("--cohort-edge-model needs --cohort")
+    for flag, given in (("--cohort-edge-model-terms", cohort_edge_model_terms is not None),
+                        ("--cohort-edge-model-permutations", cohort_edge_model_permutations is not None),
+                        ("--cohort-edge-model-seed", cohort_edge_model_seed is not None)):
+        if given and cohort_edge_model is None:
+            raise click.UsageError(f"{flag} needs --cohort-edge-model")
+    if cohort_edge_model is not None and cohort_edge_model_terms is None:
+        raise click.UsageError("--cohort-edge-model needs --cohort-edge-model-terms")
     if cohort_strata_column is not None and cohort_strata is None:
         raise click.UsageError("--cohort-strata-column needs --cohort-strata")
     if cohort_strata is not None and cohort_permanova is None and cohort_permdisp is None and cohort_edge_test is None \
-            and cohort_model is None and not with_mantel and cohort_anosim is None:
+            and cohort_model is None and not with_mantel and cohort_anosim is None and cohort_edge_model is None:
         raise click.UsageError("--cohort-strata needs --cohort-permanova, --cohort-permdisp, --cohort-edge-test or --cohort-model")
     if cohort_pcoa and not cohort:
         raise click.UsageError("--cohort-pcoa needs --cohort")
@@ -465,6 +488,12 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
         argv += ["--cohort-strata", str(cohort_strata)]
         if cohort_strata_column is not None:
             argv += ["--cohort-strata-column", str(cohort_strata_column)]
+    if cohort_edge_model is not None:
+        argv += ["--cohort-edge-model", str(cohort_edge_model), "--cohort-edge-model-terms", str(cohort_edge_model_terms)]
+        if cohort_edge_model_permutations is not None:
+            argv += ["--cohort-edge-model-permutations", str(int(cohort_edge_model_permutations))]
+        if cohort_edge_model_seed is not None:
+            argv += ["--cohort-edge-model-seed", str(int(cohort_edge_model_seed))]
     if cohort_model is not None:
         argv += ["--cohort-model", str(cohort_model), "--cohort-model-terms", str(cohort_model_terms)]
         if cohort_model_permutations is not None:

@@ -107,6 +107,16 @@ MODEL_MAX_COLUMNS = 64
 MODEL_MAX_GROUPS = 32
 MODEL_MAX_PERMUTATIONS = 999999
 MODEL_MISSING = 0xFFFFFFFF
+#: epik_amd_edgemodel_family (72 bytes), epik_amd_edgemodel (144 bytes) and epik_amd_edgemodel_info (152 bytes): a (term,
+#: branch)'s record of the edge model, the families mass and imbalance, and the info block; the doubles of an undefined family
+#: are NA_BITS
+EDGEMODEL_FAMILY = np.dtype([("ss", np.float64), ("r2", np.float64), ("partial_r2", np.float64), ("f", np.float64),
+                             ("p", np.float64), ("p_adj", np.float64), ("at_least", np.uint64), ("max_at_least", np.uint64),
+                             ("sign", np.int32), ("pad", np.uint32)])
+EDGEMODEL = np.dtype([("family", EDGEMODEL_FAMILY, (2,))])
+EDGEMODEL_INFO = np.dtype([("used", np.uint32), ("terms", np.uint32), ("columns", np.uint32), ("rank", np.uint32),
+                           ("df_res", np.int64), ("df", np.uint32, (16,)), ("term_columns", np.uint32, (16,))])
+EDGEMODEL_FAMILIES = 2
 NA_BITS = 0x7FF8000000000000
 RAREFY_MAX_DEPTHS = 256
 RAREFY_MAX_DEPTH = 1 << 20
@@ -248,6 +258,12 @@ EXPORTS = (
     "epik_amd_cohort_model_strata",
     "epik_amd_cohort_model_strata_host",
     "epik_amd_cohort_model_strata_kr_host",
+    "epik_amd_cohort_edgemodel_device",
+    "epik_amd_cohort_edgemodel",
+    "epik_amd_cohort_edgemodel_host",
+    "epik_amd_cohort_edgemodel_strata_device",
+    "epik_amd_cohort_edgemodel_strata",
+    "epik_amd_cohort_edgemodel_strata_host",
     "epik_amd_cohort_edgetest_strata_device",
     "epik_amd_cohort_edgetest_strata",
     "epik_amd_cohort_edgetest_strata_host",
@@ -685,6 +701,14 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_cohort_edgetest.argtypes = [vp, vp, vp, u32, u32, u64, vp, vp, vp]
     lib.epik_amd_cohort_edgetest_host.restype = i32
     lib.epik_amd_cohort_edgetest_host.argtypes = [vp, u32, u32, vp, vp, u32, u32, u64, vp, vp, vp]
+    # (the edge model: the tree or the cells, the design, P, the seed, the records, the info block, stat, max, aliased)
+    design = [vp, vp, vp, u32, u32, u64, vp, vp, vp, vp, vp]
+    for form, head, tail in (("_device", [vp, vp], [vp]), ("", [vp, vp], []), ("_host", [vp, u32, u32, vp], [])):
+        if not hasattr(lib, "epik_amd_cohort_edgemodel" + form):  # (an older library named by EPIK_AMD_LIB, as below)
+            continue
+        entry = getattr(lib, "epik_amd_cohort_edgemodel" + form)
+        entry.restype = i32
+        entry.argtypes = head + design + tail
     # (the strata rule's entries: a sibling's arguments, then strata)
     for name, sibling in (("permanova_strata_device", "permanova_device"), ("permanova_strata", "permanova_metric"),
                           ("permanova_strata_host", "permanova_metric_host"), ("permanova_strata_kr_host", "permanova_kr_host"),
@@ -693,7 +717,9 @@ def load() -> ctypes.CDLL:
                           ("model_strata_device", "model_device"), ("model_strata", "model_metric"),
                           ("model_strata_host", "model_metric_host"), ("model_strata_kr_host", "model_kr_host"),
                           ("edgetest_strata_device", "edgetest_device"), ("edgetest_strata", "edgetest"),
-                          ("edgetest_strata_host", "edgetest_host")):
+                          ("edgetest_strata_host", "edgetest_host"),
+                          ("edgemodel_strata_device", "edgemodel_device"), ("edgemodel_strata", "edgemodel"),
+                          ("edgemodel_strata_host", "edgemodel_host")):
         if not hasattr(lib, "epik_amd_cohort_" + name):  # (an older library named by EPIK_AMD_LIB: tools/strata_rate.py's yardstick)
             continue
         getattr(lib, "epik_amd_cohort_" + name).restype = i32

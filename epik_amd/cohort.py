@@ -429,6 +429,9 @@ _STRATA_ENTRY = {
     "edgetest_device": "edgetest_strata_device",
     "edgetest": "edgetest_strata",
     "edgetest_host": "edgetest_strata_host",
+    "edgemodel_device": "edgemodel_strata_device",
+    "edgemodel": "edgemodel_strata",
+    "edgemodel_host": "edgemodel_strata_host",
 }
 
 
@@ -771,6 +774,43 @@ def edgetest_host(mass, first, labels, permutations: int = 999, seed: int = 1, w
           int(permutations), int(seed), records.ctypes.data,
           stat.ctypes.data if with_stat else None, most.ctypes.data if with_max else None)
     return Edgetest(records, stat, most)
+
+
+@dataclass
+class Edgemodel:
+    """What the edge model gives: `records` `capi.EDGEMODEL` [T][N] (a term a row, the families mass and imbalance), `info` one
+    `capi.EDGEMODEL_INFO`, `stat` float64 [T][2][N][P + 1] (the partial R2 of the permutations 0 .. P; None where not asked
+    for), `max` float64 [T][2][P + 1] (the maxima over the defined branches) and `aliased` uint8 [64] as the model's."""
+    records: np.ndarray
+    info: np.void
+    stat: np.ndarray | None
+    max: np.ndarray | None
+    aliased: np.ndarray
+
+
+def _edgemodel_buffers(t: int, n: int, permutations: int, with_stat: bool, with_max: bool):
+    row = min(max(int(permutations), 0), capi.MODEL_MAX_PERMUTATIONS) + 1
+    t = min(max(t, 1), capi.MODEL_MAX_TERMS)
+    records = np.zeros((t, n), dtype=capi.EDGEMODEL)
+    info = np.zeros(1, dtype=capi.EDGEMODEL_INFO)
+    stat = np.full((t, capi.EDGEMODEL_FAMILIES, n, row), np.nan) if with_stat else None
+    most = np.full((t, capi.EDGEMODEL_FAMILIES, row), np.nan) if with_max else None
+    return records, info, stat, most, np.zeros(capi.MODEL_MAX_COLUMNS, dtype=np.uint8)
+
+
+def edgemodel_host(mass, first, kind, labels, values, permutations: int = 999, seed: int = 1, with_stat: bool = True,
+                   with_max: bool = True, strata=None) -> Edgemodel:
+    """The edge model of the rule for mass[S][N] and the design kind[T], labels[S][T] (0xffffffff: missing) and values[S][T]
+    (NaN: missing) on the host, one thread (`epik_amd_cohort_edgemodel_host`)."""
+    lib = capi.load()
+    mass, first = _mass_and_first(mass, first)
+    s, n = mass.shape
+    kind, labels, values = _design(kind, labels, values, s)
+    records, info, stat, most, aliased = _edgemodel_buffers(kind.shape[0], n, permutations, with_stat, with_max)
+    _call(lib, "edgemodel_host", strata, s, mass.ctypes.data, s, n, first.ctypes.data, kind.ctypes.data, labels.ctypes.data,
+          values.ctypes.data, kind.shape[0], int(permutations), int(seed), records.ctypes.data, info.ctypes.data,
+          stat.ctypes.data if with_stat else None, most.ctypes.data if with_max else None, aliased.ctypes.data)
+    return Edgemodel(records, info[0], stat, most, aliased)
 
 
 @dataclass
@@ -1193,6 +1233,29 @@ class Cohort:
               int(permutations), int(seed), records.ctypes.data, info.ctypes.data,
               stat.ctypes.data if with_stat else None, aliased.ctypes.data)
         return Model(records, info[0], stat, aliased)
+
+    def edgemodel_device(self, tree, kind, labels, values, permutations: int, seed: int, d_out: int, d_info: int, d_aliased: int,
+                         d_stat: int = 0, d_max: int = 0, stream: int = 0, strata=None) -> None:
+        """The edge model of the design kind[T], labels[S][T] and values[S][T] (host) into d_out, `capi.EDGEMODEL` [T][N],
+        d_info, one `capi.EDGEMODEL_INFO`, d_aliased, 64 bytes, and where given d_stat, float64 [T][2][N][P + 1], and d_max,
+        float64 [T][2][P + 1], all in device memory, every cell written; asynchronous on `stream` once the design is copied,
+        no readback (`epik_amd_cohort_edgemodel_device`)."""
+        kind, labels, values = _design(kind, labels, values, self.num_samples)
+        _call(self._lib, "edgemodel_device", strata, self.num_samples, self._handle, self._tree_handle(tree, "edgemodel_device"),
+              kind.ctypes.data, labels.ctypes.data, values.ctypes.data, kind.shape[0], int(permutations), int(seed),
+              d_out or None, d_info or None, d_stat or None, d_max or None, d_aliased or None, stream or None)
+
+    def edgemodel(self, tree, kind, labels, values, permutations: int = 999, seed: int = 1, with_stat: bool = False,
+                  with_max: bool = False, strata=None) -> Edgemodel:
+        """On which branches a term of the design still matters after the terms before it: per branch the sequential linear
+        model of its mass and imbalance by permutation, with the max-statistic adjustment (`epik_amd_cohort_edgemodel`)."""
+        kind, labels, values = _design(kind, labels, values, self.num_samples)
+        records, info, stat, most, aliased = _edgemodel_buffers(kind.shape[0], self.num_branches, permutations, with_stat, with_max)
+        _call(self._lib, "edgemodel", strata, self.num_samples, self._handle, self._tree_handle(tree, "edgemodel"), kind.ctypes.data,
+              labels.ctypes.data, values.ctypes.data, kind.shape[0], int(permutations), int(seed), records.ctypes.data,
+              info.ctypes.data, stat.ctypes.data if with_stat else None, most.ctypes.data if with_max else None,
+              aliased.ctypes.data)
+        return Edgemodel(records, info[0], stat, most, aliased)
 
     def reset(self) -> None:
         capi.check(self._lib.epik_amd_cohort_reset(self._handle))
@@ -2269,22 +2332,10 @@ def read_design(path: str, terms: str, names):
 MODEL_HEADER = "term\tdf\tss\tr2\tf\tat_least\tp"
 
 
-def format_model_tsv(names, totals, terms, kind, label_names, labels, values, permutations: int, seed: int, model: Model,
-                     distance="kr", strata=None) -> str:
-    """cohort_model_<list>.tsv: the first line (used = the complete cases with mass), a `# unused` line per sample without mass,
-    a `# incomplete` line per sample with mass that lacks a value (with the first term it lacks), a `# term` line per term, a
-    `# group` line per group of a factor term in the rule's order, a `# aliased` line per dropped column, the column names, a
-    line per term, then `model`, `residual` (df_res, ss_res, 1 less every term's r2 in one chain) and `total`; doubles as
-    %.17g, NA as NA.  `strata`: the name of the column of --cohort-strata, <TAB>strata=NAME at the
-    end of the first line."""
-    kind, labels, values = np.asarray(kind), np.asarray(labels), np.asarray(values, dtype=np.float64)
-    totals = [int(x) for x in totals]
-    t_count, info, records = len(terms), model.info, model.records
-    if labels.shape != (len(names), t_count) or values.shape != labels.shape or len(records) != t_count + 1 or len(totals) != len(names):
-        raise ValueError("labels and values must be [num_samples][num_terms], the records [num_terms + 1]")
-    lines = [f"# epik_amd model v1  samples={len(names)} used={int(info['used'])} terms={t_count} columns={int(info['columns'])} "
-             f"rank={int(info['rank'])} permutations={int(permutations)} seed={int(seed)}" + _distance_field(distance)]
-    lines += [f"# unused\t{name}" for name, t in zip(names, totals) if t == 0]
+def _design_lines(names, totals, terms, kind, label_names, labels, values, term_columns, term_df, aliased):
+    """The lines that cohort_model and cohort_edgemodel .tsv share: `# unused`, `# incomplete`, `# term`, `# group`, `# aliased`."""
+    t_count = len(terms)
+    lines = [f"# unused\t{name}" for name, t in zip(names, totals) if t == 0]
     lacks = np.where(kind[None, :] != 0, np.isnan(values), labels == capi.MODEL_MISSING)
     used = []
     for s, name in enumerate(names):
@@ -2294,7 +2345,7 @@ def format_model_tsv(names, totals, terms, kind, label_names, labels, values, pe
             lines.append(f"# incomplete\t{name}\t{terms[int(np.argmax(lacks[s]))]}")
         else:
             used.append(s)
-    lines += [f"# term\t{t}\t{'n' if kind[t] else 'f'}\t{terms[t]}\t{int(records['columns'][t])}\t{int(records['df'][t])}"
+    lines += [f"# term\t{t}\t{'n' if kind[t] else 'f'}\t{terms[t]}\t{int(term_columns[t])}\t{int(term_df[t])}"
               for t in range(t_count)]
     column_of, groups = [], []
     for t in range(t_count):
@@ -2310,7 +2361,26 @@ def format_model_tsv(names, totals, terms, kind, label_names, labels, values, pe
         groups += [f"# group\t{t}\t{g}\t{label_names[t][v]}\t{sizes[v]}" for g, v in enumerate(order)]
         column_of += [(t, label_names[t][v]) for v in order[1:]]
     lines += groups
-    lines += [f"# aliased\t{t}\t{label}" for c, (t, label) in enumerate(column_of[:capi.MODEL_MAX_COLUMNS]) if model.aliased[c]]
+    lines += [f"# aliased\t{t}\t{label}" for c, (t, label) in enumerate(column_of[:capi.MODEL_MAX_COLUMNS]) if aliased[c]]
+    return lines
+
+
+def format_model_tsv(names, totals, terms, kind, label_names, labels, values, permutations: int, seed: int, model: Model,
+                     distance="kr", strata=None) -> str:
+    """cohort_model_<list>.tsv: the first line (used = the complete cases with mass), a `# unused` line per sample without mass,
+    a `# incomplete` line per sample with mass that lacks a value (with the first term it lacks), a `# term` line per term, a
+    `# group` line per group of a factor term in the rule's order, a `# aliased` line per dropped column, the column names, a
+    line per term, then `model`, `residual` (df_res, ss_res, 1 less every term's r2 in one chain) and `total`; doubles as
+    %.17g, NA as NA.  `strata`: the name of the column of --cohort-strata, <TAB>strata=NAME at the
+    end of the first line."""
+    kind, labels, values = np.asarray(kind), np.asarray(labels), np.asarray(values, dtype=np.float64)
+    totals = [int(x) for x in totals]
+    t_count, info, records = len(terms), model.info, model.records
+    if labels.shape != (len(names), t_count) or values.shape != labels.shape or len(records) != t_count + 1 or len(totals) != len(names):
+        raise ValueError("labels and values must be [num_samples][num_terms], the records [num_terms + 1]")
+    lines = [f"# epik_amd model v1  samples={len(names)} used={int(info['used'])} terms={t_count} columns={int(info['columns'])} "
+             f"rank={int(info['rank'])} permutations={int(permutations)} seed={int(seed)}" + _distance_field(distance)]
+    lines += _design_lines(names, totals, terms, kind, label_names, labels, values, records['columns'], records['df'], model.aliased)
     lines.append(MODEL_HEADER)
     rest = np.float64(1.0)
     for k in range(t_count + 1):
@@ -2373,6 +2443,85 @@ def read_model_tsv(path: str):
             records[f][k] = _na_or_float(text)
     for name, r in (("residual", rows[-2]), ("total", rows[-1])):
         info[name] = (int(r[1]), _na_or_float(r[2]), _na_or_float(r[3]))
+    return terms, records, info
+
+
+EDGEMODEL_FIELDS = ("ss", "r2", "partial_r2", "f", "sign", "p", "p_adj")
+EDGEMODEL_HEADER = "term\tedge_num\t" + "\t".join(f"{k}_{f}" for k in ("mass", "imbalance") for f in EDGEMODEL_FIELDS)
+
+
+def format_edgemodel_tsv(names, totals, terms, kind, label_names, labels, values, permutations: int, seed: int, result: Edgemodel,
+                         strata=None) -> str:
+    """cohort_edgemodel_<list>.tsv: the first line, the `# unused`, `# incomplete`, `# term`, `# group` and `# aliased` lines of
+    cohort_model_<list>.tsv, the column names, then per term a line per branch with a defined family: the term, the branch and,
+    for mass and imbalance, ss r2 partial_r2 f sign p p_adj; doubles as %.17g, NA as NA.  `strata`: as format_model_tsv's."""
+    kind, labels, values = np.asarray(kind), np.asarray(labels), np.asarray(values, dtype=np.float64)
+    totals = [int(x) for x in totals]
+    t_count, info, records = len(terms), result.info, result.records
+    if labels.shape != (len(names), t_count) or values.shape != labels.shape or records.shape[0] != t_count or len(totals) != len(names):
+        raise ValueError("labels and values must be [num_samples][num_terms], the records [num_terms][num_branches]")
+    lines = [f"# epik_amd edgemodel v1  samples={len(names)} used={int(info['used'])} terms={t_count} columns={int(info['columns'])} "
+             f"rank={int(info['rank'])} permutations={int(permutations)} seed={int(seed)}"]
+    lines += _design_lines(names, totals, terms, kind, label_names, labels, values, info["term_columns"], info["df"], result.aliased)
+    lines.append(EDGEMODEL_HEADER)
+    for t in range(t_count):
+        for b in range(records.shape[1]):
+            fams = records["family"][t, b]
+            if np.isnan(fams["ss"]).all():
+                continue
+            cells = [terms[t], str(b)]
+            for fam in fams:
+                cells += [_g17_or_na(fam["ss"]), _g17_or_na(fam["r2"]), _g17_or_na(fam["partial_r2"]), _g17_or_na(fam["f"]),
+                          "NA" if np.isnan(fam["ss"]) else str(int(fam["sign"])), _g17_or_na(fam["p"]), _g17_or_na(fam["p_adj"])]
+            lines.append("\t".join(cells))
+    return with_strata_field("\n".join(lines) + "\n", strata)
+
+
+def read_edgemodel_tsv(path: str, num_branches: int):
+    """(terms [(name, 'f' | 'n', columns, df)], records `capi.EDGEMODEL` [T][N] with ss, r2, partial_r2, f, sign, p and p_adj (NA
+    for a branch without a line; the counts are not in the file), info: samples, used, columns, rank, permutations, seed, unused,
+    incomplete, groups, aliased and, with strata, strata)."""
+    with open(path, newline="") as fh:
+        first = fh.readline().rstrip("\n")
+        head = re.fullmatch(r"# epik_amd edgemodel v1  samples=(\d+) used=(\d+) terms=(\d+) columns=(\d+) rank=(\d+) permutations=(\d+) "
+                            r"seed=(\d+)" + _STRATA_FIELD, first)
+        if not head:
+            raise ValueError(f"{path}: not a cohort edgemodel file")
+        info = dict(samples=int(head.group(1)), used=int(head.group(2)), columns=int(head.group(4)), rank=int(head.group(5)),
+                    permutations=int(head.group(6)), seed=int(head.group(7)), unused=[], incomplete=[], groups=[], aliased=[])
+        if head.group("strata"):
+            info["strata"] = head.group("strata")
+        terms = []
+        line = fh.readline().rstrip("\n")
+        while line.startswith("# "):
+            r = line.split("\t")
+            if r[0] == "# unused" and len(r) == 2:
+                info["unused"].append(r[1])
+            elif r[0] == "# incomplete" and len(r) == 3:
+                info["incomplete"].append((r[1], r[2]))
+            elif r[0] == "# term" and len(r) == 6 and int(r[1]) == len(terms):
+                terms.append((r[3], r[2], int(r[4]), int(r[5])))
+            elif r[0] == "# group" and len(r) == 5:
+                info["groups"].append((int(r[1]), int(r[2]), r[3], int(r[4])))
+            elif r[0] == "# aliased" and len(r) == 3:
+                info["aliased"].append((int(r[1]), r[2]))
+            else:
+                raise ValueError(f"{path}: not a line of a cohort edgemodel file: {line!r}")
+            line = fh.readline().rstrip("\n")
+        if line != EDGEMODEL_HEADER or len(terms) != int(head.group(3)):
+            raise ValueError(f"{path}: not a cohort edgemodel file")
+        rows = [ln.rstrip("\n").split("\t") for ln in fh]
+    records = np.zeros((len(terms), num_branches), dtype=capi.EDGEMODEL)
+    for f in EDGEMODEL_FIELDS:
+        if f != "sign":
+            records["family"][f] = _na_or_float("NA")
+    index = {name: t for t, (name, _, _, _) in enumerate(terms)}
+    for r in rows:
+        if len(r) != 16 or r[0] not in index or not 0 <= int(r[1]) < num_branches:
+            raise ValueError(f"{path}: not a line of a cohort edgemodel file: {r!r}")
+        for k in range(2):
+            for f, text in zip(EDGEMODEL_FIELDS, r[2 + 7 * k:9 + 7 * k]):
+                records["family"][f][index[r[0]], int(r[1]), k] = (0 if text == "NA" else int(text)) if f == "sign" else _na_or_float(text)
     return terms, records, info
 
 

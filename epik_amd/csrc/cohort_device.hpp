@@ -34,6 +34,7 @@ enum CohortSpaceId : uint32_t {
     kSpacePermdisp,
     kSpaceModel,
     kSpaceMantel,
+    kSpaceEdgemodel,
     kCohortSpaces
 };
 

@@ -8,6 +8,7 @@
 // one lane (__dadd_rn / __dsub_rn / __dmul_rn / __ddiv_rn / __dsqrt_rn; the file is built with -ffp-contract=off as well).  No
 // MFMA: the chains have a fixed order.  NA is stored as its bit pattern and never computed.
 //
+//   (model_terms_kernel, model_basis_kernel and model_strata_kernel are in model_basis.hpp, which the edge model shares)
 //   model_terms_kernel   a wave a term: the complete cases with mass in list order (the host has set the label of every term
 //                        to `missing` for a sample that lacks any value, so every term sees the same list) and the groups of
 //                        a factor by first appearance: column_list of cohort_device.hpp, PERMANOVA's.
@@ -34,46 +35,28 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <set>
 #include <string>
 #include <vector>
 
 #include "../host/cohort.hpp"
 #include "cohort_entry.hpp"
+#include "model_basis.hpp"
 
 namespace {
 
 using namespace epik_amd;
 
-constexpr uint32_t kTerms = EPIK_AMD_MODEL_MAX_TERMS;
-constexpr uint32_t kColumns = EPIK_AMD_MODEL_MAX_COLUMNS;
-constexpr uint32_t kGroups = EPIK_AMD_MODEL_MAX_GROUPS;
-constexpr uint32_t kMissing = EPIK_AMD_MODEL_MISSING;
+constexpr uint32_t kTerms = kModelTerms, kColumns = kModelColumns, kPitch = kModelPitch;
 constexpr uint32_t kPerms = 4;             // the permutations a workgroup carries through one pass over B
 constexpr uint32_t kChunk = 8;             // the columns a lane accumulates at a time: kPerms * kChunk chains in registers
 constexpr uint32_t kSmallColumns = 4;      // a design of up to here columns accumulates kSmallColumns at a time instead
 constexpr uint32_t kLdsPositions = 128;    // the most samples whose row sums and arrangements stay in LDS (34 KiB)
 constexpr uint32_t kGeneralBlocks = 256;   // workgroups of the general path: each has a slice
 constexpr uint64_t kManyBlocks = 65536;
-constexpr uint32_t kPitch = kColumns;      // doubles a row of Q
 
 static_assert(sizeof(epik_amd_model_term) == 48 && sizeof(epik_amd_model_info) == 40, "the records are 48 and 40 bytes");
 static_assert(kBlock == 256 && kWave == 64 && kColumns % kChunk == 0 && kChunk % kSmallColumns == 0);
 static_assert(kPerms * (kTerms + 1) <= kBlock && kPerms * kChunk <= kBlock && kColumns <= kBlock);
-
-// what the kernels hand on to one another, in the workspace
-struct ModelMeta {
-    uint32_t L, C, R, testable;
-    int64_t df_res;
-    double g, ss_total, ss_res;
-    uint32_t groups[kTerms];
-    uint32_t df[kTerms + 1], columns[kTerms + 1], first[kTerms + 1];  // of a term, and of the whole model; first: its first accepted column
-    double f0[kTerms + 1];
-};
-
-struct ModelKinds {
-    uint32_t kind[kTerms];
-};
 
 struct ModelSpace {
     double *B;        // [S][S]: the Gower matrix, L x L compact
@@ -111,24 +94,6 @@ size_t model_space(void *base, uint32_t S, uint32_t padded, uint32_t T, uint32_t
     return c.bytes();
 }
 
-__global__ __launch_bounds__(kWave) void model_terms_kernel(const uint64_t *__restrict__ total, const uint32_t *__restrict__ lab,
-                                                            uint32_t num_samples, uint32_t padded, uint32_t num_terms,
-                                                            uint32_t *__restrict__ idx, uint8_t *__restrict__ lam,
-                                                            ModelMeta *__restrict__ meta)
-{
-    __shared__ uint32_t group_of[kGroups], size[kGroups];
-    for (uint32_t t = blockIdx.x; t < num_terms; t += gridDim.x) {
-        const uint64_t offset = (uint64_t)t * padded;
-        uint32_t L, G;  // (uniform)
-        column_list<kGroups>(total, lab + offset, num_samples, kMissing, group_of, size, idx + offset, lam + offset, L, G);
-        if (threadIdx.x == 0) {
-            meta->groups[t] = G;
-            if (t == 0) meta->L = L;
-        }
-        __syncthreads();  // (the tables are written again)
-    }
-}
-
 __global__ __launch_bounds__(kBlock) void model_rows_kernel(const double *__restrict__ kr, const uint32_t *__restrict__ used,
                                                             uint32_t num_samples, const ModelMeta *__restrict__ meta,
                                                             double *__restrict__ r)
@@ -159,78 +124,6 @@ __global__ __launch_bounds__(kBlock) void model_centre_kernel(const double *__re
     gower_centre_cells(kr, used, num_samples, meta->L, r, meta->g, B);
 }
 
-// one workgroup; every condition around a barrier is uniform (L, G, R and the acceptance come from shared memory)
-__global__ __launch_bounds__(kBlock) void model_basis_kernel(const ModelKinds kinds, uint32_t num_terms, uint32_t padded,
-                                                             const double *__restrict__ val, const uint32_t *__restrict__ idx,
-                                                             const uint8_t *__restrict__ lam, double *v, double *Q,
-                                                             ModelMeta *meta, uint8_t *__restrict__ aliased)
-{
-    __shared__ double h[kColumns];
-    __shared__ double mean_of, root_of;
-    __shared__ uint32_t accepted;
-    const uint32_t tid = threadIdx.x, L = meta->L;
-    uint32_t C = 0, R = 0;
-    for (uint32_t t = 0; t < num_terms; ++t) {
-        const bool numeric = kinds.kind[t] != 0;
-        const uint32_t G = meta->groups[t], width = numeric ? 1 : G ? G - 1 : 0, first = R;
-        const uint64_t offset = (uint64_t)t * padded;
-        for (uint32_t w = 0; w < width; ++w, ++C) {
-            for (uint32_t i = tid; i < L; i += kBlock) v[i] = numeric ? val[offset + idx[i]] : lam[offset + i] == w + 1 ? 1.0 : 0.0;
-            __syncthreads();
-            if (tid == 0 && L) {
-                double acc = 0.0;
-#pragma unroll 4
-                for (uint32_t i = 0; i < L; ++i) acc = __dadd_rn(acc, v[i]);
-                mean_of = __ddiv_rn(acc, (double)L);
-            }
-            __syncthreads();
-            for (uint32_t i = tid; i < L; i += kBlock) v[i] = __dsub_rn(v[i], mean_of);
-            __syncthreads();
-            double n0 = 0.0;  // (lane 0's)
-            if (tid == 0) {
-#pragma unroll 4
-                for (uint32_t i = 0; i < L; ++i) n0 = __dadd_rn(n0, __dmul_rn(v[i], v[i]));
-            }
-            for (uint32_t pass = 0; pass < 2; ++pass) {
-                for (uint32_t k = tid; k < R; k += kBlock) {
-                    double acc = 0.0;
-#pragma unroll 4
-                    for (uint32_t i = 0; i < L; ++i) acc = __dadd_rn(acc, __dmul_rn(Q[(uint64_t)i * kPitch + k], v[i]));
-                    h[k] = acc;
-                }
-                __syncthreads();
-                for (uint32_t i = tid; i < L; i += kBlock) {
-                    const double *row = Q + (uint64_t)i * kPitch;
-                    double x = v[i];
-                    for (uint32_t k = 0; k < R; ++k) x = __dsub_rn(x, __dmul_rn(h[k], row[k]));
-                    v[i] = x;
-                }
-                __syncthreads();
-            }
-            if (tid == 0) {
-                double n1 = 0.0;
-#pragma unroll 4
-                for (uint32_t i = 0; i < L; ++i) n1 = __dadd_rn(n1, __dmul_rn(v[i], v[i]));
-                const bool accept = n0 > 0.0 && n1 > __dmul_rn(0x1p-40, n0);
-                accepted = accept, root_of = accept ? __dsqrt_rn(n1) : 0.0;
-                aliased[C] = accept ? 0 : 1;
-            }
-            __syncthreads();
-            if (accepted) {
-                for (uint32_t i = tid; i < L; i += kBlock) Q[(uint64_t)i * kPitch + R] = __ddiv_rn(v[i], root_of);
-                ++R;
-            }
-            __syncthreads();  // (v, the acceptance and Q are complete before the next column)
-        }
-        if (tid == 0) meta->df[t] = R - first, meta->columns[t] = width, meta->first[t] = first;
-    }
-    for (uint32_t c = C + tid; c < kColumns; c += kBlock) aliased[c] = 0;
-    if (tid == 0) {
-        meta->C = C, meta->R = R, meta->df[num_terms] = R, meta->columns[num_terms] = C, meta->first[num_terms] = 0;
-        meta->df_res = (int64_t)L - 1 - (int64_t)R;
-    }
-}
-
 struct SsArgs {
     const double *B, *Q;
     ModelMeta *meta;
@@ -242,13 +135,6 @@ struct SsArgs {
     uint32_t num_terms, num_permutations, pitch;
     const uint32_t *hs, *home;  // the strata rule's tables, or null
 };
-
-// the strata rule's tables of the list of the complete cases: one workgroup
-__global__ __launch_bounds__(kBlock) void model_strata_kernel(const uint32_t *__restrict__ strata, const uint32_t *__restrict__ idx,
-                                                              const ModelMeta *__restrict__ meta, uint32_t *hs, uint32_t *home)
-{
-    if (blockIdx.x == 0) strata_tables(strata, [&](uint32_t i) { return idx[i]; }, meta->L, hs, home);
-}
 
 // F of a term from its sums: the rule's three divisions, +infinity where the residual is not > 0
 __device__ inline double f_of(double ss, uint32_t df, double res, int64_t df_res)
@@ -433,30 +319,10 @@ int model_device_impl(epik_amd_cohort *cohort, const void *d_kr, const uint32_t 
     ModelSpace sp;
     model_space(cohort->space[kSpaceModel].d, S, padded, T, slices, strata != nullptr, &sp);
     if (strata) COHORT_TRY(upload_strata(strata, S, padded, sp.strata));
-    // the design by term; a sample that lacks any value is missing in every term, so every term lists the complete cases
-    std::vector<uint32_t> lab((size_t)T * padded, kMissing);
-    std::vector<double> val((size_t)T * padded, 0.0);
+    // the design by term, every term listing the complete cases (model_basis.hpp)
     ModelKinds kinds{};
     size_t bound = 0;  // the columns as the rule counts them: at least those of the used samples
-    for (uint32_t t = 0; t < T; ++t) {
-        kinds.kind[t] = kind[t];
-        std::set<uint32_t> distinct;
-        for (uint32_t s = 0; s < S; ++s)
-            if (!kind[t] && labels[(size_t)s * T + t] != kMissing) distinct.insert(labels[(size_t)s * T + t]);
-        bound += kind[t] ? 1 : distinct.empty() ? 0 : distinct.size() - 1;
-    }
-    for (uint32_t s = 0; s < S; ++s) {
-        bool complete = true;
-        for (uint32_t t = 0; t < T; ++t)
-            complete = complete && (kind[t] ? !std::isnan(values[(size_t)s * T + t]) : labels[(size_t)s * T + t] != kMissing);
-        if (!complete) continue;
-        for (uint32_t t = 0; t < T; ++t) {
-            lab[(size_t)t * padded + s] = kind[t] ? 0 : labels[(size_t)s * T + t];
-            val[(size_t)t * padded + s] = kind[t] ? values[(size_t)s * T + t] : 0.0;
-        }
-    }
-    HIP_TRY(hipMemcpy(sp.lab, lab.data(), lab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sp.val, val.data(), val.size() * sizeof(double), hipMemcpyHostToDevice));
+    COHORT_TRY(model_design_upload(kind, labels, values, S, T, padded, sp.lab, sp.val, kinds, bound));
     HIP_TRY(hipMemsetAsync(sp.meta, 0, sizeof(ModelMeta), stream));
     HIP_TRY(hipMemsetAsync(sp.Q, 0, (size_t)padded * kPitch * sizeof(double), stream));  // (a lane reads whole chunks of a row)
     const auto *kr = static_cast<const double *>(d_kr);

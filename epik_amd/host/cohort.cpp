@@ -1521,6 +1521,78 @@ int model_arguments_valid(const uint32_t* kind, const uint32_t* labels, const do
     return EPIK_AMD_OK;
 }
 
+namespace {
+
+// Steps 1, 3 and 4 of the sequential model's rule, which the edge model shares word for word: the complete cases with mass, the
+// centred columns in term order and the basis by classical Gram-Schmidt twice.  Nothing here depends on the response.
+struct design_basis {
+    std::vector<size_t> used;            // U, in list order
+    std::vector<std::vector<double>> Q;  // the accepted columns, in order
+    std::vector<uint32_t> df, columns;   // [T + 1]: of a term, and of the whole model
+    size_t C = 0;
+    int64_t df_res = 0;
+    design_basis(const uint64_t* totals, size_t S, const uint32_t* kind, const uint32_t* labels, const double* values, size_t T,
+                 uint8_t* aliased)
+        : df(T + 1, 0), columns(T + 1, 0)
+    {
+        // 1: the complete cases with mass
+        for (size_t s = 0; s < S; ++s) {
+            bool complete = totals[s] != 0;
+            for (size_t t = 0; t < T && complete; ++t)
+                complete = kind[t] ? !std::isnan(values[s * T + t]) : labels[s * T + t] != EPIK_AMD_MODEL_MISSING;
+            if (complete) used.push_back(s);
+        }
+        const size_t L = used.size();
+        // 3 and 4: the columns in term order, centred, and the basis by classical Gram-Schmidt twice
+        std::fill(aliased, aliased + EPIK_AMD_MODEL_MAX_COLUMNS, (uint8_t)0);
+        std::vector<double> v(L), h;
+        for (size_t t = 0; t < T; ++t) {
+            std::vector<uint32_t> lam(L, 0), group_of(EPIK_AMD_MODEL_MAX_GROUPS, EPIK_AMD_MODEL_MISSING);
+            uint32_t G = 0;
+            if (!kind[t])
+                for (size_t i = 0; i < L; ++i) {
+                    const uint32_t label = labels[used[i] * T + t];
+                    if (group_of[label] == EPIK_AMD_MODEL_MISSING) group_of[label] = G++;
+                    lam[i] = group_of[label];
+                }
+            const uint32_t width = kind[t] ? 1 : G ? G - 1 : 0;
+            for (uint32_t w = 0; w < width; ++w, ++C) {
+                ++columns[t];
+                for (size_t i = 0; i < L; ++i) v[i] = kind[t] ? values[used[i] * T + t] : lam[i] == w + 1 ? 1.0 : 0.0;
+                double n0 = 0.0;
+                if (L) {
+                    double acc = 0.0;
+                    for (size_t i = 0; i < L; ++i) acc = acc + v[i];
+                    const double mean = acc / (double)L;
+                    for (size_t i = 0; i < L; ++i) v[i] = v[i] - mean, n0 = n0 + v[i] * v[i];
+                }
+                for (int pass = 0; pass < 2; ++pass) {
+                    h.assign(Q.size(), 0.0);
+                    for (size_t k = 0; k < Q.size(); ++k)
+                        for (size_t i = 0; i < L; ++i) h[k] = h[k] + Q[k][i] * v[i];
+                    for (size_t i = 0; i < L; ++i)
+                        for (size_t k = 0; k < Q.size(); ++k) v[i] = v[i] - h[k] * Q[k][i];
+                }
+                double n1 = 0.0;
+                for (size_t i = 0; i < L; ++i) n1 = n1 + v[i] * v[i];
+                if (n0 > 0.0 && n1 > std::ldexp(1.0, -40) * n0) {
+                    const double root = std::sqrt(n1);
+                    Q.emplace_back(L);
+                    for (size_t i = 0; i < L; ++i) Q.back()[i] = v[i] / root;
+                    ++df[t];
+                } else {
+                    aliased[C] = 1;
+                }
+            }
+        }
+        const size_t R = Q.size();
+        df[T] = (uint32_t)R, columns[T] = (uint32_t)C;
+        df_res = (int64_t)L - 1 - (int64_t)R;
+    }
+};
+
+}  // namespace
+
 int model_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_samples, const uint32_t* kind, const uint32_t* labels,
                         const double* values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed, epik_amd_model_term* out,
                         epik_amd_model_info* info, double* stat, uint8_t* aliased, std::string& err, const uint32_t* strata)
@@ -1529,15 +1601,13 @@ int model_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_s
     if (const int rc = model_arguments_valid(kind, labels, values, num_samples, num_terms, num_permutations, err); rc != EPIK_AMD_OK)
         return rc;
     const double na = na_value();
-    // 1: the complete cases with mass
-    std::vector<size_t> used;
-    for (size_t s = 0; s < S; ++s) {
-        bool complete = totals[s] != 0;
-        for (size_t t = 0; t < T && complete; ++t)
-            complete = kind[t] ? !std::isnan(values[s * T + t]) : labels[s * T + t] != EPIK_AMD_MODEL_MISSING;
-        if (complete) used.push_back(s);
-    }
-    const size_t L = used.size();
+    // 1, 3 and 4: the complete cases with mass, the columns and the basis
+    const design_basis basis(totals, S, kind, labels, values, T, aliased);
+    const std::vector<size_t>& used = basis.used;
+    const std::vector<std::vector<double>>& Q = basis.Q;
+    const std::vector<uint32_t>&df = basis.df, &columns = basis.columns;
+    const size_t L = used.size(), C = basis.C, R = Q.size();
+    const int64_t df_res = basis.df_res;
     // 2: the Gower matrix, as pcoa_components_of_kr forms it
     std::vector<double> B(L * L, 0.0), r(L);
     for (size_t i = 0; i < L; ++i)
@@ -1557,54 +1627,6 @@ int model_records_of_kr(const double* kr, const uint64_t* totals, uint32_t num_s
         for (size_t j = i; j < L; ++j) B[i * L + j] = B[j * L + i] = -0.5 * (((B[i * L + j] - r[i]) - r[j]) + g);
     double ss_total = 0.0;
     for (size_t i = 0; i < L; ++i) ss_total = ss_total + B[i * L + i];
-    // 3 and 4: the columns in term order, centred, and the basis by classical Gram-Schmidt twice
-    std::vector<std::vector<double>> Q;
-    std::vector<uint32_t> df(T + 1, 0), columns(T + 1, 0);
-    std::fill(aliased, aliased + EPIK_AMD_MODEL_MAX_COLUMNS, (uint8_t)0);
-    size_t C = 0;
-    std::vector<double> v(L), h;
-    for (size_t t = 0; t < T; ++t) {
-        std::vector<uint32_t> lam(L, 0), group_of(EPIK_AMD_MODEL_MAX_GROUPS, EPIK_AMD_MODEL_MISSING);
-        uint32_t G = 0;
-        if (!kind[t])
-            for (size_t i = 0; i < L; ++i) {
-                const uint32_t label = labels[used[i] * T + t];
-                if (group_of[label] == EPIK_AMD_MODEL_MISSING) group_of[label] = G++;
-                lam[i] = group_of[label];
-            }
-        const uint32_t width = kind[t] ? 1 : G ? G - 1 : 0;
-        for (uint32_t w = 0; w < width; ++w, ++C) {
-            ++columns[t];
-            for (size_t i = 0; i < L; ++i) v[i] = kind[t] ? values[used[i] * T + t] : lam[i] == w + 1 ? 1.0 : 0.0;
-            double n0 = 0.0;
-            if (L) {
-                double acc = 0.0;
-                for (size_t i = 0; i < L; ++i) acc = acc + v[i];
-                const double mean = acc / (double)L;
-                for (size_t i = 0; i < L; ++i) v[i] = v[i] - mean, n0 = n0 + v[i] * v[i];
-            }
-            for (int pass = 0; pass < 2; ++pass) {
-                h.assign(Q.size(), 0.0);
-                for (size_t k = 0; k < Q.size(); ++k)
-                    for (size_t i = 0; i < L; ++i) h[k] = h[k] + Q[k][i] * v[i];
-                for (size_t i = 0; i < L; ++i)
-                    for (size_t k = 0; k < Q.size(); ++k) v[i] = v[i] - h[k] * Q[k][i];
-            }
-            double n1 = 0.0;
-            for (size_t i = 0; i < L; ++i) n1 = n1 + v[i] * v[i];
-            if (n0 > 0.0 && n1 > std::ldexp(1.0, -40) * n0) {
-                const double root = std::sqrt(n1);
-                Q.emplace_back(L);
-                for (size_t i = 0; i < L; ++i) Q.back()[i] = v[i] / root;
-                ++df[t];
-            } else {
-                aliased[C] = 1;
-            }
-        }
-    }
-    const size_t R = Q.size();
-    df[T] = (uint32_t)R, columns[T] = (uint32_t)C;
-    const int64_t df_res = (int64_t)L - 1 - (int64_t)R;
     // 5: SS_k of an arrangement into ss[T + 1], the model's last
     std::vector<double> tc(L);
     const auto sums = [&](const std::vector<uint32_t>& sigma, std::vector<double>& ss) {
@@ -1678,6 +1700,118 @@ int model_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branc
         for (size_t b = 0; b < N; ++b) totals[s] += mass[s * N + b];
     return model_records_of_kr(kr.data(), totals.data(), num_samples, kind, labels, values, num_terms, num_permutations, seed, out, info,
                                stat, aliased, err, strata);
+}
+
+int edgemodel_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first, const uint32_t* kind,
+                      const uint32_t* labels, const double* values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed,
+                      epik_amd_edgemodel* out, epik_amd_edgemodel_info* info, double* stat, double* max, uint8_t* aliased,
+                      std::string& err, const uint32_t* strata)
+{
+    constexpr size_t F = EPIK_AMD_EDGEMODEL_FAMILIES;
+    const size_t S = num_samples, N = num_branches, T = num_terms, P = num_permutations, row = P + 1;
+    if (const int rc = model_arguments_valid(kind, labels, values, num_samples, num_terms, num_permutations, err); rc != EPIK_AMD_OK)
+        return rc;
+    kr_planes planes;
+    if (const int rc = make_planes(mass, S, N, first, nullptr, planes, err); rc != EPIK_AMD_OK) return rc;
+    const double na = na_value();
+    const design_basis basis(planes.total.data(), S, kind, labels, values, T, aliased);
+    const std::vector<size_t>& used = basis.used;
+    const std::vector<uint32_t>& df = basis.df;
+    const size_t L = used.size(), R = basis.Q.size();
+    const int64_t df_res = basis.df_res;
+    *info = epik_amd_edgemodel_info{(uint32_t)L, (uint32_t)T, (uint32_t)basis.C, (uint32_t)R, df_res, {}, {}};
+    for (size_t k = 0; k < T; ++k) info->df[k] = df[k], info->term_columns[k] = basis.columns[k];
+    const epik_amd_edgemodel_family none{na, na, na, na, na, na, 0, 0, 0, 0};
+    for (size_t e = 0; e < T * N; ++e) out[e].family[0] = out[e].family[1] = none;
+    if (stat) std::fill(stat, stat + T * F * N * row, na);
+    if (max) std::fill(max, max + T * F * row, na);
+    if (df_res < 1 || R == 0) return EPIK_AMD_OK;
+    // the basis by position, a row a position: Qrow[i][c]; and the arranged rows of a chunk of permutations
+    std::vector<double> Qrow(L * R);
+    for (size_t c = 0; c < R; ++c)
+        for (size_t i = 0; i < L; ++i) Qrow[i * R + c] = basis.Q[c][i];
+    const size_t chunk = std::max<size_t>(1, ((size_t)8 << 20) / (L * R));
+    std::vector<double> Qs(std::min(chunk, row) * L * R);
+    arrangements arrange(strata, L, [&](size_t i) { return used[i]; });
+    std::vector<double> mmax(T * F * row, 0.0), s(R), x[F];
+    std::vector<char> any(F, 0);
+    centred dev[F];
+    // SS_k and phi_k of the sums s_c of one arrangement into ss[T] and phi[T] (phi means something where df_k >= 1); returns SS_res
+    std::vector<double> phi(T), ss(T);
+    const auto statistic = [&](double sxx) {
+        size_t c = 0;
+        double model = 0.0;
+        for (size_t k = 0; k < T; ++k) {
+            double term = 0.0;
+            for (uint32_t w = 0; w < df[k]; ++w, ++c) term = term + s[c] * s[c];
+            ss[k] = term;
+            model = model + term;
+        }
+        const double res = sxx - model;
+        for (size_t k = 0; k < T; ++k) phi[k] = res > 0.0 ? ss[k] / (ss[k] + res) : ss[k] > 0.0 ? 1.0 : 0.0;
+        return res;
+    };
+    for (size_t p0 = 0; p0 < row; p0 += chunk) {
+        const size_t np = std::min(chunk, row - p0);
+        for (size_t k = 0; k < np; ++k) {
+            double* q = Qs.data() + k * L * R;
+            if (p0 + k == 0) {
+                std::copy(Qrow.begin(), Qrow.end(), q);
+                continue;
+            }
+            const std::vector<uint32_t>& sigma = arrange.of(seed, (uint32_t)(p0 + k));
+            for (size_t i = 0; i < L; ++i) std::copy(Qrow.begin() + sigma[i] * R, Qrow.begin() + (sigma[i] + 1) * R, q + i * R);
+        }
+        for (size_t b = 0; b < N; ++b) {
+            const bool inner = first[b] < b;
+            branch_vectors(mass, planes, N, b, used, x[0], x[1]);
+            for (size_t f = 0; f < (inner ? F : 1); ++f) {
+                dev[f].of(x[f]);
+                const double sxx = dev[f].ss;
+                if (!(sxx > 0.0)) continue;
+                const double* d = dev[f].d.data();
+                for (size_t k = 0; k < np; ++k) {
+                    const double* q = Qs.data() + k * L * R;
+                    std::fill(s.begin(), s.end(), 0.0);
+                    for (size_t i = 0; i < L; ++i)
+                        for (size_t c = 0; c < R; ++c) s[c] = s[c] + q[i * R + c] * d[i];
+                    const double res = statistic(sxx);
+                    const size_t p = p0 + k;
+                    for (size_t t = 0, c = 0; t < T; c += df[t], ++t) {
+                        if (!df[t]) continue;
+                        epik_amd_edgemodel_family& fam = out[t * N + b].family[f];
+                        if (p == 0) {
+                            fam = epik_amd_edgemodel_family{ss[t], ss[t] / sxx, phi[t], na, na, na, 0, 0, 0, 0};
+                            if (res > 0.0) fam.f = (ss[t] / (double)df[t]) / (res / (double)df_res);
+                            if (df[t] == 1) fam.sign = s[c] > 0.0 ? 1 : s[c] < 0.0 ? -1 : 0;
+                            any[f] = 1;
+                        }
+                        const size_t cell = (t * F + f) * row + p;
+                        if (stat) stat[((t * F + f) * N + b) * row + p] = phi[t];
+                        if (phi[t] > mmax[cell]) mmax[cell] = phi[t];
+                        fam.at_least += p >= 1 && phi[t] >= fam.partial_r2;
+                    }
+                }
+            }
+        }
+    }
+    // max_at_least by a search in the sorted maxima: a count, exact however it is found
+    for (size_t t = 0; t < T; ++t)
+        for (size_t f = 0; f < F; ++f) {
+            if (!df[t] || !any[f]) continue;
+            const double* m = mmax.data() + (t * F + f) * row;
+            if (max) std::copy(m, m + row, max + (t * F + f) * row);
+            std::vector<double> sorted(m + 1, m + row);
+            std::sort(sorted.begin(), sorted.end());
+            for (size_t b = 0; b < N; ++b) {
+                epik_amd_edgemodel_family& fam = out[t * N + b].family[f];
+                if (std::isnan(fam.partial_r2)) continue;
+                fam.max_at_least = (uint64_t)(sorted.end() - std::lower_bound(sorted.begin(), sorted.end(), fam.partial_r2));
+                fam.p = (double)(1 + fam.at_least) / (double)(P + 1);
+                fam.p_adj = (double)(1 + fam.max_at_least) / (double)(P + 1);
+            }
+        }
+    return EPIK_AMD_OK;
 }
 
 namespace {
@@ -2645,14 +2779,15 @@ std::string format_permdisp_tsv(const std::vector<cohort_sample>& samples, const
     return out;
 }
 
-std::string format_model_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, const cohort_design& design,
-                             uint32_t num_permutations, uint64_t seed, const epik_amd_model_term* records,
-                             const epik_amd_model_info& info, const uint8_t* aliased, uint32_t distance)
+namespace {
+
+// the lines of a design that cohort_model and cohort_edgemodel .tsv share: "# unused", "# incomplete", "# term", "# group" and
+// "# aliased", from the columns and the accepted columns of every term and the aliased bytes
+std::string design_lines(const std::vector<cohort_sample>& samples, const uint64_t* totals, const cohort_design& design,
+                         const std::vector<uint32_t>& columns_of, const std::vector<uint32_t>& df_of, const uint8_t* aliased)
 {
     const size_t S = samples.size(), T = design.terms.size();
-    std::string out = "# epik_amd model v1  samples=" + std::to_string(S) + " used=" + std::to_string(info.used) +
-                      " terms=" + std::to_string(T) + " columns=" + std::to_string(info.columns) + " rank=" + std::to_string(info.rank) +
-                      " permutations=" + std::to_string(num_permutations) + " seed=" + std::to_string(seed) + distance_field(distance) + "\n";
+    std::string out;
     for (size_t s = 0; s < S; ++s)
         if (totals[s] == 0) out += "# unused\t" + samples[s].name + "\n";
     const auto lacks = [&](size_t s, size_t t) {
@@ -2670,7 +2805,7 @@ std::string format_model_tsv(const std::vector<cohort_sample>& samples, const ui
     }
     for (size_t t = 0; t < T; ++t)
         out += "# term\t" + std::to_string(t) + (design.kind[t] ? "\tn\t" : "\tf\t") + design.terms[t] + "\t" +
-               std::to_string(records[t].columns) + "\t" + std::to_string(records[t].df) + "\n";
+               std::to_string(columns_of[t]) + "\t" + std::to_string(df_of[t]) + "\n";
     // the groups of the factor terms in the rule's order, and the label of every column
     std::vector<std::string> column_label;
     std::vector<size_t> column_term;
@@ -2696,6 +2831,22 @@ std::string format_model_tsv(const std::vector<cohort_sample>& samples, const ui
     out += groups;
     for (size_t c = 0; c < column_label.size() && c < EPIK_AMD_MODEL_MAX_COLUMNS; ++c)
         if (aliased[c]) out += "# aliased\t" + std::to_string(column_term[c]) + "\t" + column_label[c] + "\n";
+    return out;
+}
+
+}  // namespace
+
+std::string format_model_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, const cohort_design& design,
+                             uint32_t num_permutations, uint64_t seed, const epik_amd_model_term* records,
+                             const epik_amd_model_info& info, const uint8_t* aliased, uint32_t distance)
+{
+    const size_t S = samples.size(), T = design.terms.size();
+    std::string out = "# epik_amd model v1  samples=" + std::to_string(S) + " used=" + std::to_string(info.used) +
+                      " terms=" + std::to_string(T) + " columns=" + std::to_string(info.columns) + " rank=" + std::to_string(info.rank) +
+                      " permutations=" + std::to_string(num_permutations) + " seed=" + std::to_string(seed) + distance_field(distance) + "\n";
+    std::vector<uint32_t> columns_of(T), df_of(T);
+    for (size_t t = 0; t < T; ++t) columns_of[t] = records[t].columns, df_of[t] = records[t].df;
+    out += design_lines(samples, totals, design, columns_of, df_of, aliased);
     out += "term\tdf\tss\tr2\tf\tat_least\tp\n";
     double rest = 1.0;
     for (size_t k = 0; k <= T; ++k) {
@@ -2709,6 +2860,34 @@ std::string format_model_tsv(const std::vector<cohort_sample>& samples, const ui
     out += "residual\t" + std::to_string(info.df_res) + "\t" + g17(info.ss_res) + "\t" + (total ? g17(rest) : std::string("NA")) +
            "\tNA\tNA\tNA\n";
     out += "total\t" + std::to_string((int64_t)info.used - 1) + "\t" + g17(info.ss_total) + "\t" + (total ? "1" : "NA") + "\tNA\tNA\tNA\n";
+    return out;
+}
+
+std::string format_edgemodel_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, const cohort_design& design,
+                                 uint32_t num_branches, uint32_t num_permutations, uint64_t seed, const epik_amd_edgemodel* records,
+                                 const epik_amd_edgemodel_info& info, const uint8_t* aliased)
+{
+    const size_t S = samples.size(), T = design.terms.size(), N = num_branches;
+    std::string out = "# epik_amd edgemodel v1  samples=" + std::to_string(S) + " used=" + std::to_string(info.used) +
+                      " terms=" + std::to_string(T) + " columns=" + std::to_string(info.columns) + " rank=" + std::to_string(info.rank) +
+                      " permutations=" + std::to_string(num_permutations) + " seed=" + std::to_string(seed) + "\n";
+    out += design_lines(samples, totals, design, std::vector<uint32_t>(info.term_columns, info.term_columns + T),
+                        std::vector<uint32_t>(info.df, info.df + T), aliased);
+    out += "term\tedge_num";
+    for (const char* kind : {"mass", "imbalance"})
+        for (const char* field : {"ss", "r2", "partial_r2", "f", "sign", "p", "p_adj"}) out += std::string("\t") + kind + '_' + field;
+    out += '\n';
+    for (size_t t = 0; t < T; ++t)
+        for (size_t b = 0; b < N; ++b) {
+            const epik_amd_edgemodel& r = records[t * N + b];
+            if (std::isnan(r.family[0].ss) && std::isnan(r.family[1].ss)) continue;
+            out += design.terms[t] + '\t' + std::to_string(b);
+            for (const auto& fam : r.family)
+                out += '\t' + g17_or_na(fam.ss) + '\t' + g17_or_na(fam.r2) + '\t' + g17_or_na(fam.partial_r2) + '\t' + g17_or_na(fam.f) +
+                       '\t' + (std::isnan(fam.ss) ? std::string("NA") : std::to_string(fam.sign)) + '\t' + g17_or_na(fam.p) + '\t' +
+                       g17_or_na(fam.p_adj);
+            out += '\n';
+        }
     return out;
 }
 

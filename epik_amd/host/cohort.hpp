@@ -180,6 +180,14 @@ int model_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branc
                   uint32_t num_permutations, uint64_t seed, epik_amd_model_term* out, epik_amd_model_info* info, double* stat,
                   uint8_t* aliased, std::string& err, uint32_t metric = EPIK_AMD_DISTANCE_KR, const uint32_t* strata = nullptr);
 
+/// The edge model by the rule (include/epik_amd.h) from mass[S][N], one thread: out[T][N], *info, aliased[64] and, where not
+/// null, stat[T][2][N][P + 1] and max[T][2][P + 1], every cell written.  libepik_amd's kernels (edgemodel_place.hip) give the
+/// same bits.  The code behind epik_amd_cohort_edgemodel_host.  0, as model_arguments_valid, or first[b] > b.
+int edgemodel_records(const uint64_t* mass, uint32_t num_samples, uint32_t num_branches, const uint32_t* first, const uint32_t* kind,
+                      const uint32_t* labels, const double* values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed,
+                      epik_amd_edgemodel* out, epik_amd_edgemodel_info* info, double* stat, double* max, uint8_t* aliased,
+                      std::string& err, const uint32_t* strata = nullptr);
+
 /// The sides of a Mantel call as the C ABI takes them: values[Mv][S] (NaN: missing), matrices[Mm][S][S] with
 /// matrix_present[Mm][S], the methods' bits and the control (a side, or EPIK_AMD_MANTEL_NO_CONTROL)
 struct mantel_sides {
@@ -394,6 +402,13 @@ std::string format_permdisp_tsv(const std::vector<cohort_sample>& samples, const
 std::string format_model_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, const cohort_design& design,
                              uint32_t num_permutations, uint64_t seed, const epik_amd_model_term* records,
                              const epik_amd_model_info& info, const uint8_t* aliased, uint32_t distance = EPIK_AMD_DISTANCE_KR);
+/// cohort_edgemodel .tsv: "# epik_amd edgemodel v1  samples=S used=L terms=T columns=C rank=R permutations=P seed=X", the
+/// "# unused", "# incomplete", "# term", "# group" and "# aliased" lines of cohort_model .tsv, the column names term edge_num and,
+/// for mass and imbalance, _ss _r2 _partial_r2 _f _sign _p _p_adj, then per term a line per branch with a defined family, from
+/// records[T][N]; doubles %.17g, NA where undefined.
+std::string format_edgemodel_tsv(const std::vector<cohort_sample>& samples, const uint64_t* totals, const cohort_design& design,
+                                 uint32_t num_branches, uint32_t num_permutations, uint64_t seed, const epik_amd_edgemodel* records,
+                                 const epik_amd_edgemodel_info& info, const uint8_t* aliased);
 /// A matrix of --cohort-mantel-matrix NAME=FILE: FILE is a square TSV in the layout of cohort_kr_<list>.tsv, a first line
 /// name<TAB>name1<TAB>..., then per line a name and one distance per name of the first line; blank lines and lines that begin with
 /// '#' are skipped.  The names are matched to the list: matrix[S][S] in the order of the list, present[s] = 1 for a sample of the

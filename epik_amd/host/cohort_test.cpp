@@ -50,6 +50,13 @@
 //   cohort_test model-tsv <out.tsv> <in.bin> <names.txt> <design.tsv> <terms> <P> <seed>
 //                                           the file of --cohort-model for a `kr` input whose samples are named by the lines of
 //                                           names.txt, through the design file's reader and the formatter
+//   cohort_test edgemodel <out.bin> <in.bin> <design.bin> <P> <seed>
+//                                           the edge model of a `kr` input (its lengths are not read) with a `design` file as for
+//                                           `model`: epik_amd_edgemodel [T][N], epik_amd_edgemodel_info, float64
+//                                           stat[T][2][N][P + 1], float64 max[T][2][P + 1], uint8 aliased[64];
+//                                           edgemodel-strata: with <strata.bin> after the design
+//   cohort_test edgemodel-tsv <out.tsv> <in.bin> <names.txt> <design.tsv> <terms> <P> <seed>
+//                                           the file of --cohort-edge-model, as model-tsv
 //   cohort_test mantel <out.bin> <in.bin> <sides.bin> <strata.bin or -> <P> <seed>
 //                                           the Mantel tests of a `kr` input with a `sides` file, uint64 Mv, Mm, methods, control
 //                                           (0xffffffff: none), float64 values[Mv][S], float64 matrices[Mm][S][S], uint8
@@ -529,6 +536,40 @@ int main(int argc, char** argv)
                                                                              aliased.data()));
             return 0;
         }
+        if (argc == 9 && std::strcmp(argv[1], "edgemodel-tsv") == 0) {
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto cells = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const uint32_t P = (uint32_t)std::strtoul(argv[7], nullptr, 10);
+            const uint64_t seed = std::strtoull(argv[8], nullptr, 10);
+            std::vector<epik_amd::cohort_sample> samples;
+            std::ifstream names(argv[4]);
+            if (!names) throw std::runtime_error(std::string("cannot open ") + argv[4]);
+            for (std::string line; std::getline(names, line);) samples.push_back({line, ""});
+            if (samples.size() != S) throw std::runtime_error("the names file does not name every sample");
+            const epik_amd::cohort_design design = epik_amd::read_cohort_design(argv[5], argv[6], samples);
+            std::cout << "Cohort edge model design: " << design.terms.size() << " terms, " << design.skipped
+                      << " lines of samples that are not in the list skipped" << std::endl;
+            const size_t T = design.terms.size();
+            std::vector<epik_amd_edgemodel> records(T * N);
+            epik_amd_edgemodel_info info{};
+            std::vector<uint8_t> aliased(EPIK_AMD_MODEL_MAX_COLUMNS);
+            std::string err;
+            if (epik_amd::edgemodel_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), design.kind.data(), design.labels.data(),
+                                            design.values.data(), (uint32_t)T, P, seed, records.data(), &info, nullptr, nullptr,
+                                            aliased.data(), err) != 0)
+                throw std::runtime_error(err);
+            std::vector<uint64_t> totals(S, 0);
+            for (uint64_t s = 0; s < S; ++s)
+                for (uint64_t b = 0; b < N; ++b) totals[s] += cells[s * N + b];
+            epik_amd::write_through_part(argv[2], epik_amd::format_edgemodel_tsv(samples, totals.data(), design, (uint32_t)N, P, seed,
+                                                                                 records.data(), info, aliased.data()));
+            return 0;
+        }
         if ((argc == 7 && std::strcmp(argv[1], "model") == 0) || (argc == 8 && std::strcmp(argv[1], "model-strata") == 0)) {
             const bool stratified = argc == 8;
             std::ifstream in(argv[3], std::ios::binary);
@@ -564,6 +605,46 @@ int main(int argc, char** argv)
             write_array(out, records.data(), records.size());
             write_array(out, &info, 1);
             write_array(out, stat.data(), stat.size());
+            write_array(out, aliased.data(), aliased.size());
+            if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
+            return 0;
+        }
+        if ((argc == 7 && std::strcmp(argv[1], "edgemodel") == 0) || (argc == 8 && std::strcmp(argv[1], "edgemodel-strata") == 0)) {
+            const bool stratified = argc == 8;
+            std::ifstream in(argv[3], std::ios::binary);
+            if (!in) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+            const auto head = read_array<uint64_t>(in, 2);
+            const uint64_t S = head[0], N = head[1];
+            if (S == 0) throw std::runtime_error("no sample");
+            const auto cells = read_array<uint64_t>(in, S * N);
+            const auto first = read_array<uint32_t>(in, N);
+            const uint32_t P = (uint32_t)std::strtoul(argv[argc - 2], nullptr, 10);
+            const uint64_t seed = std::strtoull(argv[argc - 1], nullptr, 10);
+            std::vector<uint32_t> strata;
+            if (stratified) strata = read_strata(argv[5], S);
+            std::ifstream design(argv[4], std::ios::binary);
+            if (!design) throw std::runtime_error(std::string("cannot open ") + argv[4]);
+            const uint64_t T = read_array<uint64_t>(design, 1)[0];
+            if (T < 1 || T > EPIK_AMD_MODEL_MAX_TERMS) throw std::runtime_error("the design file has a number of terms outside [1, 16]");
+            if (P < 1 || P > EPIK_AMD_MODEL_MAX_PERMUTATIONS) throw std::runtime_error("P is outside [1, 999999]");
+            const auto kind = read_array<uint32_t>(design, T);
+            const auto labels = read_array<uint32_t>(design, S * T);
+            const auto values = read_array<double>(design, S * T);
+            const uint64_t row = (uint64_t)P + 1;
+            std::vector<epik_amd_edgemodel> records(T * N);
+            epik_amd_edgemodel_info info{};
+            std::vector<double> stat(T * EPIK_AMD_EDGEMODEL_FAMILIES * N * row), most(T * EPIK_AMD_EDGEMODEL_FAMILIES * row);
+            std::vector<uint8_t> aliased(EPIK_AMD_MODEL_MAX_COLUMNS);
+            std::string err;
+            if (epik_amd::edgemodel_records(cells.data(), (uint32_t)S, (uint32_t)N, first.data(), kind.data(), labels.data(), values.data(),
+                                            (uint32_t)T, P, seed, records.data(), &info, stat.data(), most.data(), aliased.data(), err,
+                                            stratified ? strata.data() : nullptr) != 0)
+                throw std::runtime_error(err);
+            std::ofstream out(argv[2], std::ios::binary);
+            write_array(out, records.data(), records.size());
+            write_array(out, &info, 1);
+            write_array(out, stat.data(), stat.size());
+            write_array(out, most.data(), most.size());
             write_array(out, aliased.data(), aliased.size());
             if (!out) throw std::runtime_error(std::string("cannot write ") + argv[2]);
             return 0;
@@ -716,6 +797,9 @@ int main(int argc, char** argv)
                      "permanova-strata | permdisp-strata <out.bin> <in.bin> <labels.bin> <strata.bin> <P> <seed> <pairwise> | "
                      "edgetest-strata <out.bin> <in.bin> <labels.bin> <strata.bin> <P> <seed> | "
                      "model-strata <out.bin> <in.bin> <design.bin> <strata.bin> <P> <seed> | "
+                     "edgemodel <out.bin> <in.bin> <design.bin> <P> <seed> | "
+                     "edgemodel-strata <out.bin> <in.bin> <design.bin> <strata.bin> <P> <seed> | "
+                     "edgemodel-tsv <out.tsv> <in.bin> <names.txt> <design.tsv> <terms> <P> <seed> | "
                      "mantel <out.bin> <in.bin> <sides.bin> <strata.bin or -> <P> <seed> | "
                      "anosim <out.bin> <in.bin> <labels.bin> <strata.bin or -> <P> <seed> | "
                      "mantel-tsv <out.tsv> <in.bin> <names.txt> <meta.tsv or -> <NAME=FILE,... or -> <method> <partial or -> <P> <seed> | "

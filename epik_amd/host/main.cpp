@@ -301,6 +301,12 @@ const char* kHelp =
     "                          or n:NAME (a numeric covariate); at most 16 terms and 64 design columns\n"
     "      --cohort-model-permutations arg  With --cohort-model: the number of permutations in [1, 999999] (default: 999)\n"
     "      --cohort-model-seed arg  With --cohort-model: the seed of the permutations, a uint64 (default: 1)\n"
+    "      --cohort-edge-model arg  With --cohort: also fit, on the device, the sequential linear model of --cohort-edge-model-terms to\n"
+    "                          every branch's mass share and imbalance, by permutation, with the max-statistic adjustment over the\n"
+    "                          branches; arg is a TSV file as --cohort-model's; cohort_edgemodel_<list>.tsv\n"
+    "      --cohort-edge-model-terms arg  With --cohort-edge-model (required): the terms in test order, as --cohort-model-terms\n"
+    "      --cohort-edge-model-permutations arg  With --cohort-edge-model: the number of permutations in [1, 999999] (default: 999)\n"
+    "      --cohort-edge-model-seed arg  With --cohort-edge-model: the seed of the permutations, a uint64 (default: 1)\n"
     "      --cohort-edge-test arg  With --cohort: also test, for every factor column of the TSV file arg (as --cohort-permanova's,\n"
     "                          at most 32 labels a column), on which branches its groups of samples differ: the one-way ANOVA and\n"
     "                          Kruskal-Wallis of every branch's mass and imbalance by permutation, with the max-statistic\n"
@@ -662,6 +668,18 @@ int main(int argc, char** argv)
             if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-model-seed " + text + ": not a uint64");
             model_seed = v;
         }
+        const bool with_edgemodel = parsed.has("cohort-edge-model");
+        if (with_edgemodel && !with_cohort)
+            throw std::runtime_error("--cohort-edge-model needs --cohort (it fits a model to the branches of the samples of the list)");
+        for (const char* dependent : {"cohort-edge-model-terms", "cohort-edge-model-permutations", "cohort-edge-model-seed"})
+            if (parsed.has(dependent) && !with_edgemodel)
+                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-edge-model" +
+                                         (with_cohort ? "" : " (and that needs --cohort )"));
+        if (with_edgemodel && !parsed.has("cohort-edge-model-terms"))
+            throw std::runtime_error("--cohort-edge-model needs --cohort-edge-model-terms (the terms of the model, f:NAME or n:NAME, in test "
+                                     "order)");
+        const uint32_t edgemodel_permutations = permutations_of("cohort-edge-model-permutations");
+        const uint64_t edgemodel_seed = seed_of("cohort-edge-model-seed");
         // --cohort-unifrac / --cohort-distance: checked before anything is opened or any device touched
         const bool with_unifrac = parsed.has("cohort-unifrac");
         if (with_unifrac && !with_cohort)
@@ -682,7 +700,7 @@ int main(int argc, char** argv)
         const bool with_strata = parsed.has("cohort-strata");
         if (parsed.has("cohort-strata-column") && !with_strata)
             throw std::runtime_error("--cohort-strata-column needs --cohort-strata (it names a column of that file)");
-        if (with_strata && !(with_permanova || with_permdisp || with_edgetest || with_model || with_mantel || with_anosim))
+        if (with_strata && !(with_permanova || with_permdisp || with_edgetest || with_model || with_mantel || with_anosim || with_edgemodel))
             throw std::runtime_error("--cohort-strata needs --cohort-permanova, --cohort-permdisp, --cohort-edge-test or --cohort-model "
                                      "(the tests that permute samples)");
         if (with_edgetest && !with_cohort)
@@ -816,6 +834,15 @@ int main(int argc, char** argv)
         if (with_model) {
             design = epik_amd::read_cohort_design(parsed.require("cohort-model"), parsed.require("cohort-model-terms"), cohort_samples);
             std::cout << "Cohort model design: " << design.terms.size() << " terms, " << design.skipped
+                      << " lines of samples that are not in the list skipped" << std::endl;
+        }
+
+        // --cohort-edge-model: its design likewise (the same file may serve --cohort-model)
+        epik_amd::cohort_design edge_design;
+        if (with_edgemodel) {
+            edge_design = epik_amd::read_cohort_design(parsed.require("cohort-edge-model"), parsed.require("cohort-edge-model-terms"),
+                                                       cohort_samples);
+            std::cout << "Cohort edge model design: " << edge_design.terms.size() << " terms, " << edge_design.skipped
                       << " lines of samples that are not in the list skipped" << std::endl;
         }
 
@@ -1212,7 +1239,8 @@ int main(int argc, char** argv)
         const auto cohort_model_filename = epik_amd::make_cohort_filename("model", query_file, output_dir);
         const auto cohort_mantel_filename = epik_amd::make_cohort_filename("mantel", query_file, output_dir);
         const auto cohort_anosim_filename = epik_amd::make_cohort_filename("anosim", query_file, output_dir);
-        size_t model_aliased = 0;
+        const auto cohort_edgemodel_filename = epik_amd::make_cohort_filename("edgemodel", query_file, output_dir);
+        size_t model_aliased = 0, edgemodel_aliased = 0;
         const auto cohort_unifrac_filename = [&](uint32_t metric) {
             return epik_amd::make_cohort_filename(std::string("unifrac_") + epik_amd::distance_name(metric), query_file, output_dir);
         };
@@ -1252,6 +1280,10 @@ int main(int argc, char** argv)
             model.kind = design.kind.data(), model.labels = design.labels.data(), model.values = design.values.data();
             model.num_terms = (uint32_t)design.terms.size(), model.num_permutations = model_permutations, model.seed = model_seed;
             model.strata = within;
+            epik_amd::placer::cohort_edgemodel edgemodel;
+            edgemodel.kind = edge_design.kind.data(), edgemodel.labels = edge_design.labels.data(), edgemodel.values = edge_design.values.data();
+            edgemodel.num_terms = (uint32_t)edge_design.terms.size(), edgemodel.num_permutations = edgemodel_permutations;
+            edgemodel.seed = edgemodel_seed, edgemodel.strata = within;
             epik_amd::placer::cohort_mantel mantel;
             mantel.values = mantel_read.values.data(), mantel.matrices = mantel_read.matrices.data(), mantel.present = mantel_read.present.data();
             mantel.num_columns = mantel_read.num_columns, mantel.num_matrices = mantel_read.num_matrices, mantel.methods = mantel_methods;
@@ -1274,7 +1306,8 @@ int main(int argc, char** argv)
                                with_permanova ? &permanova : nullptr, with_edgetest ? &edgetest : nullptr, with_pcoa ? &pcoa : nullptr,
                                with_permdisp ? &permdisp : nullptr,
                                with_unifrac || cohort_distance != EPIK_AMD_DISTANCE_KR ? &unifrac : nullptr,
-                               with_model ? &model : nullptr, with_mantel ? &mantel : nullptr, with_anosim ? &anosim : nullptr);
+                               with_model ? &model : nullptr, with_mantel ? &mantel : nullptr, with_anosim ? &anosim : nullptr,
+                               with_edgemodel ? &edgemodel : nullptr);
             for (size_t i = 0; i < unifrac_metrics.size(); ++i)
                 epik_amd::write_through_part(cohort_unifrac_filename(unifrac_metrics[i]),
                                              epik_amd::format_cohort_unifrac_tsv(cohort_samples, unifrac.matrix[i]));
@@ -1399,6 +1432,16 @@ int main(int argc, char** argv)
                                   << strata_name << ": no permutation changes its sum of squares" << std::endl;
                 for (const uint8_t byte : model.aliased) model_aliased += byte;
             }
+            if (with_edgemodel) {
+                epik_amd::write_through_part(
+                    cohort_edgemodel_filename,
+                    epik_amd::with_strata_field(epik_amd::format_edgemodel_tsv(cohort_samples, mass_of.data(), edge_design,
+                                                                               (uint32_t)cohort.num_branches, edgemodel_permutations,
+                                                                               edgemodel_seed, edgemodel.records.data(), edgemodel.info,
+                                                                               edgemodel.aliased.data()),
+                                                strata_name));
+                for (const uint8_t byte : edgemodel.aliased) edgemodel_aliased += byte;
+            }
             if (with_pcoa) {
                 epik_amd::write_through_part(cohort_pcoa_filename, epik_amd::format_pcoa_tsv(cohort_samples, mass_of.data(), pcoa.num_components,
                                                                                              pcoa.mu.data(), pcoa.coord.data(), pcoa.info,
@@ -1491,6 +1534,10 @@ int main(int argc, char** argv)
         if (model_aliased)
             std::cout << "Warning: " << model_aliased << " columns of the design are explained by the columns before them and were "
                       << "dropped (the # aliased lines of " << cohort_model_filename << ")" << std::endl;
+        if (with_edgemodel) std::cout << "Cohort edge model: " << cohort_edgemodel_filename << std::endl;
+        if (edgemodel_aliased)
+            std::cout << "Warning: " << edgemodel_aliased << " columns of the edge model's design are explained by the columns before "
+                      << "them and were dropped (the # aliased lines of " << cohort_edgemodel_filename << ")" << std::endl;
         if (permdisp_clipped)
             std::cout << "Warning: " << permdisp_clipped << " squared distances to a group centroid are negative (the "
                       << (cohort_distance == EPIK_AMD_DISTANCE_KR ? "KR" : epik_amd::distance_name(cohort_distance)) << " distance is not "

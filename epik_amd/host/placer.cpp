@@ -51,6 +51,7 @@
 #pragma weak epik_amd_cohort_permdisp_strata
 #pragma weak epik_amd_cohort_edgetest_strata
 #pragma weak epik_amd_cohort_model_strata
+#pragma weak epik_amd_cohort_edgemodel_strata
 #pragma weak epik_amd_cohort_mantel
 #pragma weak epik_amd_cohort_anosim
 #pragma weak epik_amd_placer_cohort_reads
@@ -309,8 +310,9 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
                          epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans,
                          cohort_diversity* diversity, cohort_edges* edges, cohort_permanova* permanova,
                          cohort_edgetest* edgetest, cohort_pcoa* pcoa, cohort_permdisp* permdisp, cohort_unifrac* unifrac,
-                         cohort_model* model, cohort_mantel* mantel, cohort_anosim* anosim)
+                         cohort_model* model, cohort_mantel* mantel, cohort_anosim* anosim, cohort_edgemodel* edgemodel)
 {
+    if (edgemodel && !&epik_amd_cohort_edgemodel_strata) throw std::runtime_error("GPU placer: this libepik_amd has no edge model");
     if ((mantel && !&epik_amd_cohort_mantel) || (anosim && !&epik_amd_cohort_anosim))
         throw std::runtime_error("GPU placer: this libepik_amd has no Mantel test or no ANOSIM");
     if (model && !&epik_amd_cohort_model_metric) throw std::runtime_error("GPU placer: this libepik_amd has no sequential model");
@@ -458,6 +460,13 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
                  : epik_amd_cohort_model_metric(_cohorts[0], tree, length.data(), distance, model->kind, model->labels, model->values,
                                                 model->num_terms, model->num_permutations, model->seed, model->records.data(),
                                                 &model->info, nullptr, model->aliased.data());
+    }
+    if (rc == EPIK_AMD_OK && edgemodel) {
+        edgemodel->records.assign((size_t)edgemodel->num_terms * parent.size(), epik_amd_edgemodel{});
+        edgemodel->aliased.assign(EPIK_AMD_MODEL_MAX_COLUMNS, 0);
+        rc = epik_amd_cohort_edgemodel_strata(_cohorts[0], tree, edgemodel->kind, edgemodel->labels, edgemodel->values, edgemodel->num_terms,
+                                              edgemodel->num_permutations, edgemodel->seed, edgemodel->records.data(), &edgemodel->info,
+                                              nullptr, nullptr, edgemodel->aliased.data(), edgemodel->strata);
     }
     if (rc == EPIK_AMD_OK && mantel) {
         const size_t per_side = (mantel->methods & 1u) + (mantel->methods >> 1 & 1u);

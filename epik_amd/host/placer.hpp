@@ -256,6 +256,19 @@ public:
         epik_amd_model_info info{};
         std::vector<uint8_t> aliased;
     };
+    /// With `edgemodel` (--cohort-edge-model): the edge model of the design kind[T], labels[S][T], values[S][T] with
+    /// num_permutations permutations from `seed`; records of T * N (term, branch) pairs, info and 64 aliased bytes on return.
+    struct cohort_edgemodel {
+        const uint32_t* kind = nullptr;
+        const uint32_t* labels = nullptr;
+        const double* values = nullptr;
+        uint32_t num_terms = 0, num_permutations = 999;
+        uint64_t seed = 1;
+        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
+        std::vector<epik_amd_edgemodel> records;
+        epik_amd_edgemodel_info info{};
+        std::vector<uint8_t> aliased;
+    };
     /// With `unifrac` (--cohort-unifrac, --cohort-distance): the UniFrac distances `metrics` (EPIK_AMD_DISTANCE_UNWEIGHTED ..
     /// _GENERALIZED, each at most once), matrix[i] of num_samples * num_samples values for metrics[i] on return; and `distance`
     /// (EPIK_AMD_DISTANCE_*), the distance that `permanova`, `pcoa`, `permdisp` and `model` run over instead of KR.
@@ -290,7 +303,7 @@ public:
                      cohort_kmeans* kmeans = nullptr, cohort_diversity* diversity = nullptr, cohort_edges* edges = nullptr,
                      cohort_permanova* permanova = nullptr, cohort_edgetest* edgetest = nullptr, cohort_pcoa* pcoa = nullptr,
                      cohort_permdisp* permdisp = nullptr, cohort_unifrac* unifrac = nullptr, cohort_model* model = nullptr,
-                     cohort_mantel* mantel = nullptr, cohort_anosim* anosim = nullptr);
+                     cohort_mantel* mantel = nullptr, cohort_anosim* anosim = nullptr, cohort_edgemodel* edgemodel = nullptr);
     /// --taxonomy: one device taxonomy object per handle (epik_amd_taxonomy) from taxon_parent[T] and label[N], with one
     /// row of cells per sample of the cohort (call set_cohort first) or one row; from then on place_flat goes through
     /// the epik_amd_placer_taxa_* entries: every unique sequence is added with the number of its records as weight, a

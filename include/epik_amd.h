@@ -960,6 +960,42 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *     NA and at_least = 0 (used = L and groups = G are still written).  out[M] of epik_amd_anosim; stat[M][P + 1], where asked
  *     for: R_p, NA for an undefined column.
  *
+ * Edge model (a sequential linear model per branch by permutation, with the edge test's single-step max-statistic adjustment):
+ *   on which branches does a term still matter once the terms before it are accounted for?  From mass[S][N], first[N] and the
+ *   design exactly as the sequential model takes it (kind[T], labels[S][T], values[S][T], at most 16 terms and 64 columns),
+ *   P = num_permutations in [1, 999 999], a uint64 seed and, optionally, strata[S].  All arithmetic is IEEE double, every
+ *   operation rounded on its own, nothing fused; + - * / and comparisons only (the basis takes the model's sqrt).  NA is
+ *   EPIK_AMD_NA_BITS, written and never computed.
+ *   Samples, columns and basis.  U, L, the centred columns, the accepted columns q_c, df_k, R, `aliased` and df_res = L - 1 - R
+ *     are the steps 1, 3 and 4 of the sequential model's rule, word for word: none depends on the response, so for the same
+ *     design used, columns, rank, df and the aliased bytes equal the model's.
+ *   Families.  Two vectors x over the positions of a branch b: f = 0 is xm[b], the mass of the correlation rule; f = 1 is
+ *     xi[b], the imbalance (inner branches only).  mx, d_i and sxx are the edge test's chains.  There are no rank families.
+ *   The sums of an arrangement sigma.  sigma_p is the PERMANOVA rule's rank_p among the L positions, with strata the strata
+ *     rule's sigma_p; sigma_0 is the identity.  The response stays and whole rows of Q move, as in the model.
+ *       s_c = the sequential sum from +0.0 over i ascending of q_c[sigma(i)] * d_i       (a product, then an addition),
+ *       SS_k = the chain from +0.0 of s_c * s_c over the accepted columns of term k in order,
+ *       SS_model = the chain from +0.0 of SS_k over the terms in order,       SS_res = sxx - SS_model.
+ *     An implementation may share out terms, branches, families, permutations and columns; it may never split one chain.
+ *   Statistic.  phi_k(sigma) = SS_k / (SS_k + SS_res) where SS_res > 0.0; otherwise 1.0 if SS_k > 0.0 and +0.0 if not (the
+ *     conservative side).  phi is the partial R2, which increases with F_k at fixed degrees of freedom; it is bounded, so a
+ *     maximum over branches compares like with like, and never below +0.0, so that maximum is one of bit patterns.
+ *   Defined.  (b, f, k) is defined iff df_k >= 1, df_res >= 1, sxx > 0.0 and, for f = 1, b is inner.
+ *   Observed (sigma_0).  ss = SS_k,  r2 = SS_k / sxx,  partial_r2 = phi_k,  f = (SS_k / (double)df_k) / (SS_res / (double)df_res),
+ *     NA unless SS_res > 0.0;  sign = +1, -1 or 0, the sign of s_c, for a term with exactly one accepted column, 0 otherwise.
+ *   p-values.  at_least = #{p in 1 .. P : phi_k(sigma_p) >= phi_k(sigma_0)},   p = (double)(1 + at_least) / (double)(P + 1);
+ *       Mmax_p[k][f] = the maximum of phi_k(sigma_p) over the branches on which (b, f, k) is defined,
+ *       max_at_least = #{p in 1 .. P : Mmax_p >= phi_k(sigma_0)},   p_adj = (double)(1 + max_at_least) / (double)(P + 1).
+ *   Results.  out[T][N] of epik_amd_edgemodel, two families each: an undefined family has NA doubles, counts 0, sign 0.
+ *     info: used = L, terms = T, columns = C, rank = R, df_res, df[k] and term_columns[k] for k < T, 0 beyond.  aliased[64] as
+ *     the model's.  stat[T][2][N][P + 1], where asked for: phi_k(sigma_p), NA where undefined.  max[T][2][P + 1], where asked
+ *     for: Mmax_p with p = 0 as well, NA where no branch is defined.  Every cell is written.
+ *   By hand: four samples, the factor (a, a, b, b) and then the covariate (0, 1, 2, 3): q_0 = (-1/2, -1/2, 1/2, 1/2) and
+ *     q_1 = (-1/2, 1/2, -1/2, 1/2).  A branch with d = q_0: sxx = 1, SS_1 = 1, SS_2 = 0, SS_res = 0: r2 = 1 and 0, partial_r2 = 1
+ *     and +0.0, f NA, sign +1 and 0.  A branch with d = q_1: the same with the terms exchanged.  (The shares of a sample sum to one, so
+ *     two branches of one cohort cannot both hold these deviations: the tests' case has d = q_0 / 2 on one branch and q_1 / 2 on
+ *     another, sxx = 1/4, SS = 1/4 and 0, and r2, partial_r2 and the signs as here.)
+ *
  * Principal coordinates (Gower 1966; classical scaling, `cmdscale`, `pcoa`) of the cohort's samples over the KR distances:
  *   the ordination in which beta diversity is drawn.  From the matrix KR[S][S] of the KR rule, T_s and K in [1, 64].  The KR
  *   distance on a tree is not Euclidean, so the doubly centred matrix may be indefinite: the negative eigenvalues are
@@ -1230,6 +1266,20 @@ int epik_amd_placer_confidence_mates(epik_amd_placer *p, const char *seqs, const
  *               `metric` as permanova_metric.
  *   model_host  the rule on the host from mass[S][N], first[N], branch_length[N] and the design, no device; model_metric_host
  *               with `metric`.  model_kr_host: the same from a matrix kr[S][S] and totals[S] (T_s; only > 0 matters).
+ *   edgemodel_device  checks the tree as edgetest_device and the design as model_device (HOST, read before the call returns):
+ *               refused are a null cohort, tree, kind, labels, values, d_out, d_info or d_aliased, and what model_device
+ *               refuses of a design.  It shares the workspace of correlation_device (the masses) and keeps one of its own until
+ *               destroy(), grown where a call needs more: with Sp = S rounded up to 32, 16 * N * Sp bytes (the two centred
+ *               vectors of every branch), up to 49 152 * Sp bytes (the arranged basis and the arrangements of a chunk of
+ *               permutations: 12 bytes a chain, min(P + 1, a chunk's permutations) times the design's columns of them, 4 096 at the most), 528 Sp bytes (the basis), 16 * T * (N + P + 1) bytes (the observed phi and Mmax),
+ *               16 Sp bytes for each of 256 workgroups of the general path, 17 Sp bytes a term and 28 * N bytes of tables.
+ *               d_out is epik_amd_edgemodel [T][N], d_info one epik_amd_edgemodel_info, d_aliased 64 bytes; d_stat (may be null)
+ *               float64 [T][2][N][P + 1]; d_max (may be null) float64 [T][2][P + 1]; all in device memory.  Once enqueued on
+ *               `stream` it needs no readback.  The cells are not changed.  A cohort of up to 1 024 samples keeps a branch's
+ *               vectors in LDS in the observed pass; beyond, or with EPIK_AMD_EDGEMODEL_LDS=0 (read at the call), in global
+ *               memory: the same bits.   edgemodel: the same into host memory, synchronous; stat and max may be null.
+ *               _strata forms: with strata[S] (host; NULL: the bytes of the entry without it).
+ *   edgemodel_host  the rule on the host from mass[S][N], first[N] and the design, no device; first[b] > b is refused.
  * cohort_reads / _strands / _frames / _mates: the profile_* twins with samples[n] (HOST uint32) beside the weights.
  */
 typedef struct epik_amd_cohort epik_amd_cohort;
@@ -1605,6 +1655,45 @@ int epik_amd_cohort_model_strata_kr_host(const double *kr, const uint64_t *total
                                          const uint32_t *labels, const double *values, uint32_t num_terms,
                                          uint32_t num_permutations, uint64_t seed, epik_amd_model_term *out,
                                          epik_amd_model_info *info, double *stat, uint8_t *aliased, const uint32_t *strata);
+typedef struct epik_amd_edgemodel_family {
+    double ss, r2, partial_r2, f, p, p_adj;
+    uint64_t at_least, max_at_least; /* #{p >= 1 : phi(sigma_p) >= partial_r2}, #{p >= 1 : Mmax_p >= partial_r2} */
+    int32_t sign;                    /* of s_c for a term with one accepted column; 0 otherwise */
+    uint32_t pad;                    /* 0 */
+} epik_amd_edgemodel_family; /* 72 bytes */
+typedef struct epik_amd_edgemodel {
+    epik_amd_edgemodel_family family[2]; /* mass, imbalance */
+} epik_amd_edgemodel; /* 144 bytes */
+typedef struct epik_amd_edgemodel_info {
+    uint32_t used, terms, columns, rank; /* L, T, C, R: the model's */
+    int64_t df_res;                      /* L - 1 - R */
+    uint32_t df[16], term_columns[16];   /* the accepted columns of a term and all of them; 0 beyond T */
+} epik_amd_edgemodel_info; /* 152 bytes */
+#define EPIK_AMD_EDGEMODEL_FAMILIES 2u
+int epik_amd_cohort_edgemodel_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *kind,
+                                     const uint32_t *labels, const double *values, uint32_t num_terms, uint32_t num_permutations,
+                                     uint64_t seed, void *d_out, void *d_info, void *d_stat, void *d_max, void *d_aliased,
+                                     void *stream);
+int epik_amd_cohort_edgemodel(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *kind, const uint32_t *labels,
+                              const double *values, uint32_t num_terms, uint32_t num_permutations, uint64_t seed,
+                              epik_amd_edgemodel *out, epik_amd_edgemodel_info *info, double *stat, double *max, uint8_t *aliased);
+int epik_amd_cohort_edgemodel_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                   const uint32_t *kind, const uint32_t *labels, const double *values, uint32_t num_terms,
+                                   uint32_t num_permutations, uint64_t seed, epik_amd_edgemodel *out,
+                                   epik_amd_edgemodel_info *info, double *stat, double *max, uint8_t *aliased);
+int epik_amd_cohort_edgemodel_strata_device(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *kind,
+                                            const uint32_t *labels, const double *values, uint32_t num_terms,
+                                            uint32_t num_permutations, uint64_t seed, void *d_out, void *d_info, void *d_stat,
+                                            void *d_max, void *d_aliased, void *stream, const uint32_t *strata);
+int epik_amd_cohort_edgemodel_strata(epik_amd_cohort *cohort, const epik_amd_tree *tree, const uint32_t *kind,
+                                     const uint32_t *labels, const double *values, uint32_t num_terms, uint32_t num_permutations,
+                                     uint64_t seed, epik_amd_edgemodel *out, epik_amd_edgemodel_info *info, double *stat,
+                                     double *max, uint8_t *aliased, const uint32_t *strata);
+int epik_amd_cohort_edgemodel_strata_host(const uint64_t *mass, uint32_t num_samples, uint32_t num_branches, const uint32_t *first,
+                                          const uint32_t *kind, const uint32_t *labels, const double *values, uint32_t num_terms,
+                                          uint32_t num_permutations, uint64_t seed, epik_amd_edgemodel *out,
+                                          epik_amd_edgemodel_info *info, double *stat, double *max, uint8_t *aliased,
+                                          const uint32_t *strata);
 int epik_amd_placer_cohort_reads(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
                                  const uint32_t *weights, const uint32_t *samples, uint64_t n);
 int epik_amd_placer_cohort_strands(epik_amd_placer *p, epik_amd_cohort *cohort, const char *seqs, const uint64_t *seq_offsets,
