@@ -18,9 +18,7 @@
 // accepts DNA databases, epik-aa protein ones.
 #include <algorithm>
 #include <cctype>
-#include <cerrno>
 #include <chrono>
-#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <exception>
@@ -35,13 +33,13 @@
 #include <limits>
 #include <map>
 #include <memory>
-#include <set>
 #include <sstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "cohort.hpp"
+#include "cohort_run.hpp"
 #include "confidence.hpp"
 #include "taxonomy.hpp"
 #include "jplace.hpp"
@@ -320,22 +318,7 @@ const char* kHelp =
     "      --cohort-strata-column arg  With --cohort-strata: the column of its file; required when the file has several\n"
     "  -h, --help              Print usage\n";
 
-struct options {
-    std::map<std::string, std::string> values;
-    std::vector<std::string> matrices;  // every --cohort-mantel-matrix, the one flag that may be repeated
-    bool has(const std::string& k) const { return values.count(k) != 0; }
-    std::string get(const std::string& k, const std::string& def) const
-    {
-        const auto it = values.find(k);
-        return it == values.end() ? def : it->second;
-    }
-    std::string require(const std::string& k) const
-    {
-        const auto it = values.find(k);
-        if (it == values.end()) throw std::runtime_error("Option '" + k + "' has no value");
-        return it->second;
-    }
-};
+using epik_amd::options;
 
 options parse_args(int argc, char** argv)
 {
@@ -371,6 +354,23 @@ options parse_args(int argc, char** argv)
         opt.values[name] = value;
     }
     return opt;
+}
+
+/// The lines of a per-record file went into `filename`.part, because the header counts the records and only the end of the
+/// input tells how many: the file proper is the header and then the part, which goes
+void finish_part_file(std::ofstream& part_out, const std::string& filename, const std::string& header, uint64_t records)
+{
+    part_out.close();
+    if (!part_out) throw std::runtime_error("Could not write " + filename + ".part");
+    {
+        std::ifstream part(filename + ".part", std::ios::binary);
+        std::ofstream whole(filename, std::ios::binary);
+        whole << header;
+        if (records) whole << part.rdbuf();
+        whole.close();
+        if (!part || !whole) throw std::runtime_error("Could not write " + filename);
+    }
+    std::remove((filename + ".part").c_str());
 }
 
 }  // namespace
@@ -458,282 +458,9 @@ int main(int argc, char** argv)
             if (used != text.size() || used == 0) throw std::runtime_error("--assign-mass must be a number in [0, 1], not '" + text + "'");
             assign_tau_q = epik_amd::assign_tau_q(tau);
         }
-        // --cohort: checked before anything is opened or any device touched
-        const bool with_cohort = parsed.has("cohort"), with_squash = parsed.has("cohort-squash");
-        if (with_squash && !with_cohort) throw std::runtime_error("--cohort-squash needs --cohort (it clusters the samples of the list)");
-        const bool with_epca = parsed.has("cohort-epca");
-        if (with_epca && !with_cohort)
-            throw std::runtime_error("--cohort-epca needs --cohort (it takes the principal components of the samples of the list)");
-        if (parsed.has("cohort-epca-components") && !with_epca)
-            throw std::runtime_error("--cohort-epca-components needs --cohort-epca (the flag that computes the components)");
-        uint32_t epca_components = 5;
-        if (with_epca) {
-            const auto text = parsed.get("cohort-epca-components", "5");
-            size_t used = 0;
-            unsigned long k = 0;
-            try {
-                k = std::stoul(text, &used);
-            } catch (const std::exception&) {
-                used = 0;
-            }
-            if (used != text.size() || used == 0 || text[0] == '-' || k < 1 || k > EPIK_AMD_EPCA_MAX_COMPONENTS)
-                throw std::runtime_error("--cohort-epca-components must be a whole number in [1, 64], not '" + text + "'");
-            epca_components = (uint32_t)k;
-        }
-        const bool with_pcoa = parsed.has("cohort-pcoa");
-        if (with_pcoa && !with_cohort)
-            throw std::runtime_error("--cohort-pcoa needs --cohort (it takes the principal coordinates of the samples of the list)");
-        if (parsed.has("cohort-pcoa-components") && !with_pcoa)
-            throw std::runtime_error("--cohort-pcoa-components needs --cohort-pcoa (the flag that computes the coordinates)");
-        uint32_t pcoa_components = 5;
-        if (with_pcoa) {
-            const auto text = parsed.get("cohort-pcoa-components", "5");
-            size_t used = 0;
-            unsigned long k = 0;
-            try {
-                k = std::stoul(text, &used);
-            } catch (const std::exception&) {
-                used = 0;
-            }
-            if (used != text.size() || used == 0 || text[0] == '-' || k < 1 || k > EPIK_AMD_PCOA_MAX_COMPONENTS)
-                throw std::runtime_error("--cohort-pcoa-components must be a whole number in [1, 64], not '" + text + "'");
-            pcoa_components = (uint32_t)k;
-        }
-        const bool with_kmeans = parsed.has("cohort-kmeans");
-        if (with_kmeans && !with_cohort) throw std::runtime_error("--cohort-kmeans needs --cohort (it clusters the samples of the list)");
-        if (parsed.has("cohort-kmeans-iterations") && !with_kmeans)
-            throw std::runtime_error("--cohort-kmeans-iterations needs --cohort-kmeans (the flag that clusters the samples)");
-        uint32_t kmeans_clusters = 0, kmeans_iterations = 100;
-        if (with_kmeans) {
-            const auto whole_number = [&](const std::string& flag, const std::string& fallback, unsigned long most) {
-                const auto text = parsed.get(flag, fallback);
-                size_t used = 0;
-                unsigned long v = 0;
-                try {
-                    v = std::stoul(text, &used);
-                } catch (const std::exception&) {
-                    used = 0;
-                }
-                if (used != text.size() || used == 0 || text[0] == '-' || v < 1 || v > most)
-                    throw std::runtime_error("--" + flag + " must be a whole number in [1, " + std::to_string(most) + "], not '" + text + "'");
-                return (uint32_t)v;
-            };
-            kmeans_clusters = whole_number("cohort-kmeans", "", EPIK_AMD_KMEANS_MAX_CLUSTERS);
-            kmeans_iterations = whole_number("cohort-kmeans-iterations", "100", EPIK_AMD_KMEANS_MAX_ITERATIONS);
-        }
-        const bool with_alpha = parsed.has("cohort-alpha"), with_rarefy = parsed.has("cohort-rarefy");
-        if (with_alpha && !with_cohort) throw std::runtime_error("--cohort-alpha needs --cohort (it measures the samples of the list)");
-        if (with_rarefy && !with_cohort) throw std::runtime_error("--cohort-rarefy needs --cohort (it rarefies the samples of the list)");
-        if (parsed.has("cohort-rarefy-step") && !with_rarefy)
-            throw std::runtime_error("--cohort-rarefy-step needs --cohort-rarefy (the flag that computes the curves)");
-        uint32_t rarefy_step = 0, rarefy_depths = 0;
-        if (with_rarefy) {
-            const auto whole_number = [&](const std::string& flag, const std::string& text) {
-                size_t used = 0;
-                unsigned long v = 0;
-                try {
-                    v = std::stoul(text, &used);
-                } catch (const std::exception&) {
-                    used = 0;
-                }
-                if (used != text.size() || used == 0 || text[0] == '-' || v < 1 || v > EPIK_AMD_RAREFY_MAX_DEPTH)
-                    throw std::runtime_error("--" + flag + " must be a whole number in [1, 1048576], not '" + text + "'");
-                return (uint32_t)v;
-            };
-            const uint32_t deepest = whole_number("cohort-rarefy", parsed.get("cohort-rarefy", ""));
-            rarefy_step = std::max(1u, (deepest + 63) / 64);
-            if (parsed.has("cohort-rarefy-step")) rarefy_step = whole_number("cohort-rarefy-step", parsed.get("cohort-rarefy-step", ""));
-            rarefy_depths = deepest / rarefy_step;
-            if (rarefy_depths < 1 || rarefy_depths > EPIK_AMD_RAREFY_MAX_DEPTHS)
-                throw std::runtime_error("--cohort-rarefy-step " + std::to_string(rarefy_step) + " gives floor(" + std::to_string(deepest) +
-                                         " / " + std::to_string(rarefy_step) + ") = " + std::to_string(rarefy_depths) +
-                                         " depths of --cohort-rarefy: the number must lie in [1, 256]");
-        }
-        const bool with_correlation = parsed.has("cohort-correlation"), with_dispersion = parsed.has("cohort-dispersion");
-        if (with_correlation && !with_cohort)
-            throw std::runtime_error("--cohort-correlation needs --cohort (it correlates the samples of the list with their metadata)");
-        if (with_dispersion && !with_cohort)
-            throw std::runtime_error("--cohort-dispersion needs --cohort (it measures the branches across the samples of the list)");
-        const bool with_permanova = parsed.has("cohort-permanova"), permanova_pairwise = parsed.has("cohort-permanova-pairwise");
-        if (with_permanova && !with_cohort)
-            throw std::runtime_error("--cohort-permanova needs --cohort (it tests the groups of the samples of the list)");
-        for (const char* dependent : {"cohort-permanova-permutations", "cohort-permanova-seed", "cohort-permanova-pairwise"})
-            if (parsed.has(dependent) && !with_permanova)
-                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-permanova" +
-                                         (with_cohort ? "" : " (and that needs --cohort )"));
-        uint32_t permanova_permutations = 999;
-        uint64_t permanova_seed = 1;
-        if (parsed.has("cohort-permanova-permutations")) {
-            const std::string text = parsed.require("cohort-permanova-permutations");
-            char* end = nullptr;
-            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
-            if (!end || *end || v < 1 || v > EPIK_AMD_PERMANOVA_MAX_PERMUTATIONS)
-                throw std::runtime_error("--cohort-permanova-permutations " + text + ": the number must lie in [1, 999999]");
-            permanova_permutations = (uint32_t)v;
-        }
-        if (parsed.has("cohort-permanova-seed")) {
-            const std::string text = parsed.require("cohort-permanova-seed");
-            char* end = nullptr;
-            errno = 0;
-            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
-            if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-permanova-seed " + text + ": not a uint64");
-            permanova_seed = v;
-        }
-        const bool with_permdisp = parsed.has("cohort-permdisp"), permdisp_pairwise = parsed.has("cohort-permdisp-pairwise");
-        if (with_permdisp && !with_cohort)
-            throw std::runtime_error("--cohort-permdisp needs --cohort (it tests the dispersions of the groups of the samples of the list)");
-        for (const char* dependent : {"cohort-permdisp-permutations", "cohort-permdisp-seed", "cohort-permdisp-pairwise"})
-            if (parsed.has(dependent) && !with_permdisp)
-                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-permdisp" +
-                                         (with_cohort ? "" : " (and that needs --cohort )"));
-        uint32_t permdisp_permutations = 999;
-        uint64_t permdisp_seed = 1;
-        if (parsed.has("cohort-permdisp-permutations")) {
-            const std::string text = parsed.require("cohort-permdisp-permutations");
-            char* end = nullptr;
-            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
-            if (!end || *end || v < 1 || v > EPIK_AMD_PERMDISP_MAX_PERMUTATIONS)
-                throw std::runtime_error("--cohort-permdisp-permutations " + text + ": the number must lie in [1, 999999]");
-            permdisp_permutations = (uint32_t)v;
-        }
-        if (parsed.has("cohort-permdisp-seed")) {
-            const std::string text = parsed.require("cohort-permdisp-seed");
-            char* end = nullptr;
-            errno = 0;
-            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
-            if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-permdisp-seed " + text + ": not a uint64");
-            permdisp_seed = v;
-        }
-        // the Mantel test and ANOSIM: checked before anything is opened or any device touched
-        const bool with_mantel = parsed.has("cohort-mantel") || parsed.has("cohort-mantel-matrix"), with_anosim = parsed.has("cohort-anosim");
-        for (const char* flag : {"cohort-mantel", "cohort-mantel-matrix", "cohort-anosim"})
-            if (parsed.has(flag) && !with_cohort)
-                throw std::runtime_error(std::string("--") + flag + " needs --cohort (it tests the distances between the samples of the list)");
-        for (const char* dependent : {"cohort-mantel-method", "cohort-mantel-partial", "cohort-mantel-permutations", "cohort-mantel-seed"})
-            if (parsed.has(dependent) && !with_mantel)
-                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-mantel or --cohort-mantel-matrix" +
-                                         (with_cohort ? "" : " (and they need --cohort )"));
-        for (const char* dependent : {"cohort-anosim-permutations", "cohort-anosim-seed"})
-            if (parsed.has(dependent) && !with_anosim)
-                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-anosim" +
-                                         (with_cohort ? "" : " (and that needs --cohort )"));
-        const auto permutations_of = [&](const char* flag) -> uint32_t {
-            if (!parsed.has(flag)) return 999;
-            const std::string text = parsed.require(flag);
-            char* end = nullptr;
-            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
-            if (!end || *end || v < 1 || v > EPIK_AMD_PERMANOVA_MAX_PERMUTATIONS)
-                throw std::runtime_error(std::string("--") + flag + " " + text + ": the number must lie in [1, 999999]");
-            return (uint32_t)v;
-        };
-        const auto seed_of = [&](const char* flag) -> uint64_t {
-            if (!parsed.has(flag)) return 1;
-            const std::string text = parsed.require(flag);
-            char* end = nullptr;
-            errno = 0;
-            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
-            if (!end || *end || errno == ERANGE) throw std::runtime_error(std::string("--") + flag + " " + text + ": not a uint64");
-            return v;
-        };
-        const uint32_t mantel_permutations = permutations_of("cohort-mantel-permutations");
-        const uint32_t anosim_permutations = permutations_of("cohort-anosim-permutations");
-        const uint64_t mantel_seed = seed_of("cohort-mantel-seed"), anosim_seed = seed_of("cohort-anosim-seed");
-        const uint32_t mantel_methods = epik_amd::mantel_methods_of_name(parsed.get("cohort-mantel-method", "pearson"));
-        if (!mantel_methods)
-            throw std::runtime_error("--cohort-mantel-method must be pearson, spearman or both, not '" + parsed.require("cohort-mantel-method") + "'");
-        const bool with_model = parsed.has("cohort-model");
-        if (with_model && !with_cohort)
-            throw std::runtime_error("--cohort-model needs --cohort (it fits a model of the samples of the list)");
-        for (const char* dependent : {"cohort-model-terms", "cohort-model-permutations", "cohort-model-seed"})
-            if (parsed.has(dependent) && !with_model)
-                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-model" +
-                                         (with_cohort ? "" : " (and that needs --cohort )"));
-        if (with_model && !parsed.has("cohort-model-terms"))
-            throw std::runtime_error("--cohort-model needs --cohort-model-terms (the terms of the model, f:NAME or n:NAME, in test order)");
-        uint32_t model_permutations = 999;
-        uint64_t model_seed = 1;
-        if (parsed.has("cohort-model-permutations")) {
-            const std::string text = parsed.require("cohort-model-permutations");
-            char* end = nullptr;
-            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
-            if (!end || *end || v < 1 || v > EPIK_AMD_MODEL_MAX_PERMUTATIONS)
-                throw std::runtime_error("--cohort-model-permutations " + text + ": the number must lie in [1, 999999]");
-            model_permutations = (uint32_t)v;
-        }
-        if (parsed.has("cohort-model-seed")) {
-            const std::string text = parsed.require("cohort-model-seed");
-            char* end = nullptr;
-            errno = 0;
-            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
-            if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-model-seed " + text + ": not a uint64");
-            model_seed = v;
-        }
-        const bool with_edgemodel = parsed.has("cohort-edge-model");
-        if (with_edgemodel && !with_cohort)
-            throw std::runtime_error("--cohort-edge-model needs --cohort (it fits a model to the branches of the samples of the list)");
-        for (const char* dependent : {"cohort-edge-model-terms", "cohort-edge-model-permutations", "cohort-edge-model-seed"})
-            if (parsed.has(dependent) && !with_edgemodel)
-                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-edge-model" +
-                                         (with_cohort ? "" : " (and that needs --cohort )"));
-        if (with_edgemodel && !parsed.has("cohort-edge-model-terms"))
-            throw std::runtime_error("--cohort-edge-model needs --cohort-edge-model-terms (the terms of the model, f:NAME or n:NAME, in test "
-                                     "order)");
-        const uint32_t edgemodel_permutations = permutations_of("cohort-edge-model-permutations");
-        const uint64_t edgemodel_seed = seed_of("cohort-edge-model-seed");
-        // --cohort-unifrac / --cohort-distance: checked before anything is opened or any device touched
-        const bool with_unifrac = parsed.has("cohort-unifrac");
-        if (with_unifrac && !with_cohort)
-            throw std::runtime_error("--cohort-unifrac needs --cohort (it takes the UniFrac distances between the samples of the list)");
-        const std::vector<uint32_t> unifrac_metrics =
-            with_unifrac ? epik_amd::parse_unifrac_list(parsed.require("cohort-unifrac")) : std::vector<uint32_t>{};
-        uint32_t cohort_distance = EPIK_AMD_DISTANCE_KR;
-        if (parsed.has("cohort-distance")) {
-            if (!with_permanova && !with_pcoa && !with_permdisp && !with_model && !with_mantel && !with_anosim)
-                throw std::runtime_error("--cohort-distance needs --cohort-permanova, --cohort-pcoa or --cohort-permdisp (the analyses that "
-                                         "run over a distance; --cohort-model is one too)");
-            const std::string name = parsed.require("cohort-distance");
-            cohort_distance = epik_amd::distance_of_name(name, true);
-            if (cohort_distance == 0xffffffffu)
-                throw std::runtime_error("--cohort-distance must be kr, unweighted, weighted or generalized, not '" + name + "'");
-        }
-        const bool with_edgetest = parsed.has("cohort-edge-test");
-        const bool with_strata = parsed.has("cohort-strata");
-        if (parsed.has("cohort-strata-column") && !with_strata)
-            throw std::runtime_error("--cohort-strata-column needs --cohort-strata (it names a column of that file)");
-        if (with_strata && !(with_permanova || with_permdisp || with_edgetest || with_model || with_mantel || with_anosim || with_edgemodel))
-            throw std::runtime_error("--cohort-strata needs --cohort-permanova, --cohort-permdisp, --cohort-edge-test or --cohort-model "
-                                     "(the tests that permute samples)");
-        if (with_edgetest && !with_cohort)
-            throw std::runtime_error("--cohort-edge-test needs --cohort (it tests the branches between the groups of the samples of the list)");
-        for (const char* dependent : {"cohort-edge-test-permutations", "cohort-edge-test-seed"})
-            if (parsed.has(dependent) && !with_edgetest)
-                throw std::runtime_error(std::string("--") + dependent + " needs --cohort-edge-test" +
-                                         (with_cohort ? "" : " (and that needs --cohort )"));
-        uint32_t edgetest_permutations = 999;
-        uint64_t edgetest_seed = 1;
-        if (parsed.has("cohort-edge-test-permutations")) {
-            const std::string text = parsed.require("cohort-edge-test-permutations");
-            char* end = nullptr;
-            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
-            if (!end || *end || v < 1 || v > EPIK_AMD_EDGETEST_MAX_PERMUTATIONS)
-                throw std::runtime_error("--cohort-edge-test-permutations " + text + ": the number must lie in [1, 999999]");
-            edgetest_permutations = (uint32_t)v;
-        }
-        if (parsed.has("cohort-edge-test-seed")) {
-            const std::string text = parsed.require("cohort-edge-test-seed");
-            char* end = nullptr;
-            errno = 0;
-            const unsigned long long v = text.empty() || text[0] < '0' || text[0] > '9' ? 0 : std::strtoull(text.c_str(), &end, 10);
-            if (!end || *end || errno == ERANGE) throw std::runtime_error("--cohort-edge-test-seed " + text + ": not a uint64");
-            edgetest_seed = v;
-        }
-        if (with_cohort) {
-            for (const char* other : {"mates", "profile-only", "profile", "assign"})
-                if (parsed.has(other)) throw std::runtime_error(std::string("--cohort does not work with --") + other);
-            if (std::stoul(parsed.get("db-shard", "1")) > 1)
-                throw std::runtime_error("--cohort does not work with --db-shard > 1 (the rows of a sharded placement are finished "
-                                         "on several devices)");
-        }
+        // --cohort and its analyses: checked before anything is opened or any device touched
+        epik_amd::cohort_plan cohort_plan = epik_amd::parse_cohort_options(parsed);
+        const bool with_cohort = cohort_plan.with_cohort;
         // --taxonomy / --taxonomy-mass / --taxonomy-per-read: checked before anything is opened or any device touched
         const bool with_taxonomy = parsed.has("taxonomy"), taxonomy_per_read = parsed.has("taxonomy-per-read");
         if (parsed.has("taxonomy-mass") && !with_taxonomy) throw std::runtime_error("--taxonomy-mass needs --taxonomy");
@@ -768,83 +495,9 @@ int main(int argc, char** argv)
         const auto keep_factor = std::stod(parsed.get("keep-factor", "0.01"));
         const auto output_dir = parsed.require("output-dir");
         epik_amd::check_mu(user_mu);
-        // --cohort: the list of samples, every file of it looked at before the database or a device is
-        std::vector<epik_amd::cohort_sample> cohort_samples;
-        if (with_cohort) cohort_samples = epik_amd::read_cohort_list(query_file);
-        // --cohort-correlation: the metadata read, and every error of it named by its line, before the database or a device is
-        epik_amd::cohort_metadata metadata;
-        if (with_correlation) {
-            metadata = epik_amd::read_cohort_metadata(parsed.require("cohort-correlation"), cohort_samples);
-            std::cout << "Cohort metadata: " << metadata.columns.size() << " columns, " << metadata.skipped
-                      << " lines of samples that are not in the list skipped" << std::endl;
-        }
-        // --cohort-strata: the strata read by the factor reader, every error named by its line, before the database or a device is
-        std::vector<uint32_t> strata;
-        std::string strata_name;
-        if (with_strata) {
-            strata = epik_amd::read_cohort_strata(parsed.require("cohort-strata"), parsed.get("cohort-strata-column", ""), cohort_samples,
-                                                  &strata_name);
-            std::cout << "Cohort strata: column " << strata_name << ", " << std::set<uint32_t>(strata.begin(), strata.end()).size()
-                      << " strata of " << strata.size() << " samples" << std::endl;
-        }
-        // --cohort-permanova: the factors read, and every error of it named by its line, before the database or a device is
-        epik_amd::cohort_factors factors;
-        if (with_permanova) {
-            factors = epik_amd::read_cohort_factors(parsed.require("cohort-permanova"), cohort_samples, permanova_pairwise);
-            std::cout << "Cohort factors: " << factors.columns.size() << " columns, " << factors.skipped
-                      << " lines of samples that are not in the list skipped" << std::endl;
-        }
-
-        // --cohort-edge-test: the same reader with the edge test's cap, before the database or a device is
-        epik_amd::cohort_factors edge_factors;
-        if (with_edgetest) {
-            edge_factors = epik_amd::read_cohort_factors(parsed.require("cohort-edge-test"), cohort_samples, false,
-                                                         EPIK_AMD_EDGETEST_MAX_GROUPS, "--cohort-edge-test");
-            std::cout << "Cohort edge-test factors: " << edge_factors.columns.size() << " columns, " << edge_factors.skipped
-                      << " lines of samples that are not in the list skipped" << std::endl;
-        }
-
-        // --cohort-permdisp: the same reader with the cap of 32 labels, before the database or a device is
-        epik_amd::cohort_factors disp_factors;
-        if (with_permdisp) {
-            disp_factors = epik_amd::read_cohort_factors(parsed.require("cohort-permdisp"), cohort_samples, false,
-                                                         EPIK_AMD_PERMDISP_MAX_GROUPS, "--cohort-permdisp");
-            std::cout << "Cohort PERMDISP factors: " << disp_factors.columns.size() << " columns, " << disp_factors.skipped
-                      << " lines of samples that are not in the list skipped" << std::endl;
-        }
-
-        // --cohort-mantel / --cohort-mantel-matrix and --cohort-anosim: the sides and the factors read, every error named by its
-        // line, before the database or a device is
-        epik_amd::cohort_mantel_sides mantel_read;
-        if (with_mantel) {
-            mantel_read = epik_amd::read_cohort_mantel_sides(parsed.get("cohort-mantel", ""), parsed.matrices,
-                                                             parsed.get("cohort-mantel-partial", ""), cohort_samples);
-            std::cout << "Cohort Mantel sides: " << mantel_read.num_columns << " columns, " << mantel_read.num_matrices << " matrices, "
-                      << mantel_read.skipped << " lines of samples that are not in the list skipped" << std::endl;
-        }
-        epik_amd::cohort_factors anosim_factors;
-        if (with_anosim) {
-            anosim_factors = epik_amd::read_cohort_factors(parsed.require("cohort-anosim"), cohort_samples, false, 0, "--cohort-anosim");
-            std::cout << "Cohort ANOSIM factors: " << anosim_factors.columns.size() << " columns, " << anosim_factors.skipped
-                      << " lines of samples that are not in the list skipped" << std::endl;
-        }
-
-        // --cohort-model: the design read, and every error of it named by its line and column, before the database or a device is
-        epik_amd::cohort_design design;
-        if (with_model) {
-            design = epik_amd::read_cohort_design(parsed.require("cohort-model"), parsed.require("cohort-model-terms"), cohort_samples);
-            std::cout << "Cohort model design: " << design.terms.size() << " terms, " << design.skipped
-                      << " lines of samples that are not in the list skipped" << std::endl;
-        }
-
-        // --cohort-edge-model: its design likewise (the same file may serve --cohort-model)
-        epik_amd::cohort_design edge_design;
-        if (with_edgemodel) {
-            edge_design = epik_amd::read_cohort_design(parsed.require("cohort-edge-model"), parsed.require("cohort-edge-model-terms"),
-                                                       cohort_samples);
-            std::cout << "Cohort edge model design: " << edge_design.terms.size() << " terms, " << edge_design.skipped
-                      << " lines of samples that are not in the list skipped" << std::endl;
-        }
+        // --cohort: the list of samples and the analyses' side files, every file looked at before the database or a device is
+        cohort_plan.read_inputs(query_file);
+        const std::vector<epik_amd::cohort_sample>& cohort_samples = cohort_plan.samples;
 
         // --taxonomy: the file read, and every error of it named by its line, before the database or a device is
         epik_amd::taxonomy taxa;
@@ -1219,254 +872,9 @@ int main(int argc, char** argv)
             for (const auto& entry : db.tree_index()) subtree_num_nodes.push_back(entry.subtree_num_nodes);
             epik_amd::write_profile_tsv(profile_filename, profile, subtree_num_nodes);
         }
-        const auto cohort_samples_filename = epik_amd::make_cohort_filename("samples", query_file, output_dir);
-        const auto cohort_profile_filename = epik_amd::make_cohort_filename("profile", query_file, output_dir);
-        const auto cohort_kr_filename = epik_amd::make_cohort_filename("kr", query_file, output_dir);
-        const auto cohort_squash_filename = epik_amd::make_cohort_filename("squash", query_file, output_dir);
-        const auto cohort_squash_tree_filename = epik_amd::make_cohort_filename("squash", query_file, output_dir, ".nwk");
-        const auto cohort_epca_filename = epik_amd::make_cohort_filename("epca", query_file, output_dir);
-        const auto cohort_epca_edges_filename = epik_amd::make_cohort_filename("epca_edges", query_file, output_dir);
-        const auto cohort_pcoa_filename = epik_amd::make_cohort_filename("pcoa", query_file, output_dir);
-        const auto cohort_kmeans_filename = epik_amd::make_cohort_filename("kmeans", query_file, output_dir);
-        const auto cohort_kmeans_centroids_filename = epik_amd::make_cohort_filename("kmeans_centroids", query_file, output_dir);
-        const auto cohort_alpha_filename = epik_amd::make_cohort_filename("alpha", query_file, output_dir);
-        const auto cohort_rarefy_filename = epik_amd::make_cohort_filename("rarefy", query_file, output_dir);
-        const auto cohort_correlation_filename = epik_amd::make_cohort_filename("correlation", query_file, output_dir);
-        const auto cohort_dispersion_filename = epik_amd::make_cohort_filename("dispersion", query_file, output_dir);
-        const auto cohort_permanova_filename = epik_amd::make_cohort_filename("permanova", query_file, output_dir);
-        const auto cohort_edgetest_filename = epik_amd::make_cohort_filename("edgetest", query_file, output_dir);
-        const auto cohort_permdisp_filename = epik_amd::make_cohort_filename("permdisp", query_file, output_dir);
-        const auto cohort_model_filename = epik_amd::make_cohort_filename("model", query_file, output_dir);
-        const auto cohort_mantel_filename = epik_amd::make_cohort_filename("mantel", query_file, output_dir);
-        const auto cohort_anosim_filename = epik_amd::make_cohort_filename("anosim", query_file, output_dir);
-        const auto cohort_edgemodel_filename = epik_amd::make_cohort_filename("edgemodel", query_file, output_dir);
-        size_t model_aliased = 0, edgemodel_aliased = 0;
-        const auto cohort_unifrac_filename = [&](uint32_t metric) {
-            return epik_amd::make_cohort_filename(std::string("unifrac_") + epik_amd::distance_name(metric), query_file, output_dir);
-        };
-        uint64_t permdisp_clipped = 0;
-        bool epca_converged = true, kmeans_converged = true, pcoa_converged = true;
-        if (with_cohort) {
-            // the handles' cohorts summed on the first device, read once, and the distances computed there
-            epik_amd::sample_cohort cohort((uint32_t)cohort_samples.size(), (uint32_t)tree.get_node_count());
-            std::vector<double> kr(cohort_samples.size() * cohort_samples.size());
-            std::vector<epik_amd_squash_merge> merges(with_squash ? cohort_samples.size() - 1 : 0);
-            uint32_t num_merges = 0;
-            epik_amd::placer::cohort_epca epca;
-            epca.num_components = epca_components;
-            epik_amd::placer::cohort_kmeans kmeans;
-            kmeans.num_clusters = kmeans_clusters, kmeans.max_iterations = kmeans_iterations;
-            epik_amd::placer::cohort_diversity diversity;
-            diversity.with_alpha = with_alpha, diversity.depth_step = rarefy_step, diversity.num_depths = rarefy_depths;
-            epik_amd::placer::cohort_edges edges;
-            edges.meta = metadata.values.data(), edges.num_columns = (uint32_t)metadata.columns.size(), edges.with_dispersion = with_dispersion;
-            epik_amd::placer::cohort_permanova permanova;
-            permanova.labels = factors.labels.data(), permanova.num_columns = (uint32_t)factors.columns.size();
-            permanova.num_permutations = permanova_permutations, permanova.seed = permanova_seed, permanova.pairwise = permanova_pairwise;
-            const uint32_t* within = with_strata ? strata.data() : nullptr;
-            permanova.strata = within;
-            epik_amd::placer::cohort_edgetest edgetest;
-            edgetest.labels = edge_factors.labels.data(), edgetest.num_columns = (uint32_t)edge_factors.columns.size();
-            edgetest.num_permutations = edgetest_permutations, edgetest.seed = edgetest_seed, edgetest.strata = within;
-            epik_amd::placer::cohort_pcoa pcoa;
-            pcoa.num_components = pcoa_components;
-            epik_amd::placer::cohort_permdisp permdisp;
-            permdisp.labels = disp_factors.labels.data(), permdisp.num_columns = (uint32_t)disp_factors.columns.size();
-            permdisp.num_permutations = permdisp_permutations, permdisp.seed = permdisp_seed, permdisp.pairwise = permdisp_pairwise;
-            permdisp.strata = within;
-            epik_amd::placer::cohort_unifrac unifrac;
-            unifrac.metrics = unifrac_metrics, unifrac.distance = cohort_distance;
-            epik_amd::placer::cohort_model model;
-            model.kind = design.kind.data(), model.labels = design.labels.data(), model.values = design.values.data();
-            model.num_terms = (uint32_t)design.terms.size(), model.num_permutations = model_permutations, model.seed = model_seed;
-            model.strata = within;
-            epik_amd::placer::cohort_edgemodel edgemodel;
-            edgemodel.kind = edge_design.kind.data(), edgemodel.labels = edge_design.labels.data(), edgemodel.values = edge_design.values.data();
-            edgemodel.num_terms = (uint32_t)edge_design.terms.size(), edgemodel.num_permutations = edgemodel_permutations;
-            edgemodel.seed = edgemodel_seed, edgemodel.strata = within;
-            epik_amd::placer::cohort_mantel mantel;
-            mantel.values = mantel_read.values.data(), mantel.matrices = mantel_read.matrices.data(), mantel.present = mantel_read.present.data();
-            mantel.num_columns = mantel_read.num_columns, mantel.num_matrices = mantel_read.num_matrices, mantel.methods = mantel_methods;
-            mantel.control = mantel_read.control, mantel.num_permutations = mantel_permutations, mantel.seed = mantel_seed;
-            mantel.strata = within;
-            epik_amd::placer::cohort_anosim anosim;
-            anosim.labels = anosim_factors.labels.data(), anosim.num_columns = (uint32_t)anosim_factors.columns.size();
-            anosim.num_permutations = anosim_permutations, anosim.seed = anosim_seed, anosim.strata = within;
-            // a factor that is constant inside every stratum of its used samples: no permutation changes anything, p = 1
-            const auto warn_nested = [&](const char* flag, const std::vector<std::string>& columns, const uint32_t* labels, uint32_t missing,
-                                         const std::vector<uint64_t>& mass_of) {
-                for (size_t c = 0; with_strata && c < columns.size(); ++c)
-                    if (epik_amd::constant_within_strata(labels, cohort_samples.size(), columns.size(), c, missing, mass_of.data(), within))
-                        std::cout << "Warning: " << flag << ": the column " << columns[c] << " is constant inside every stratum of "
-                                  << strata_name << ": no permutation can change it, p = 1" << std::endl;
-            };
-            placer.read_cohort(cohort.mass.data(), cohort.best.data(), cohort.totals.data(), kr.data(), merges.data(),
-                               with_squash ? &num_merges : nullptr, with_epca ? &epca : nullptr, with_kmeans ? &kmeans : nullptr,
-                               with_alpha || with_rarefy ? &diversity : nullptr, with_correlation || with_dispersion ? &edges : nullptr,
-                               with_permanova ? &permanova : nullptr, with_edgetest ? &edgetest : nullptr, with_pcoa ? &pcoa : nullptr,
-                               with_permdisp ? &permdisp : nullptr,
-                               with_unifrac || cohort_distance != EPIK_AMD_DISTANCE_KR ? &unifrac : nullptr,
-                               with_model ? &model : nullptr, with_mantel ? &mantel : nullptr, with_anosim ? &anosim : nullptr,
-                               with_edgemodel ? &edgemodel : nullptr);
-            for (size_t i = 0; i < unifrac_metrics.size(); ++i)
-                epik_amd::write_through_part(cohort_unifrac_filename(unifrac_metrics[i]),
-                                             epik_amd::format_cohort_unifrac_tsv(cohort_samples, unifrac.matrix[i]));
-            epik_amd::write_through_part(cohort_samples_filename, epik_amd::format_cohort_samples_tsv(cohort_samples, cohort));
-            epik_amd::write_through_part(cohort_profile_filename, epik_amd::format_cohort_profile_tsv(cohort_samples, cohort));
-            epik_amd::write_through_part(cohort_kr_filename, epik_amd::format_cohort_kr_tsv(cohort_samples, kr));
-            std::vector<char> live(cohort_samples.size());  // (T_s > 0, the sum wrapping as the rule's)
-            for (size_t s = 0; s < live.size(); ++s) {
-                uint64_t total = 0;
-                for (size_t b = 0; b < cohort.num_branches; ++b) total += cohort.mass[s * cohort.num_branches + b];
-                live[s] = total != 0;
-            }
-            if (with_epca) {
-                epik_amd::write_through_part(cohort_epca_filename, epik_amd::format_epca_tsv(cohort_samples, live, epca.num_components,
-                                                                                             epca.mu.data(), epca.proj.data(), epca.info));
-                epik_amd::write_through_part(cohort_epca_edges_filename,
-                                             epik_amd::format_epca_edges_tsv(epca.first, epca.edge.data(), epca.info));
-                epca_converged = epca.info.converged != 0;
-            }
-            if (with_kmeans) {
-                epik_amd::write_through_part(cohort_kmeans_filename, epik_amd::format_kmeans_tsv(cohort_samples, kmeans.samples.data(),
-                                                                                                 kmeans.clusters.data(), kmeans.info));
-                epik_amd::write_through_part(cohort_kmeans_centroids_filename,
-                                             epik_amd::format_kmeans_centroids_tsv(kmeans.centroids.data(), (uint32_t)cohort.num_branches,
-                                                                                   kmeans.info));
-                kmeans_converged = kmeans.info.converged != 0;
-            }
-            if (with_alpha)
-                epik_amd::write_through_part(cohort_alpha_filename, epik_amd::format_alpha_tsv(cohort_samples, diversity.alpha.data()));
-            if (with_rarefy) {
-                std::vector<uint64_t> reads(cohort_samples.size(), 0);  // (n_s, the sum wrapping as the rule's)
-                for (size_t s = 0; s < reads.size(); ++s)
-                    for (size_t b = 0; b < cohort.num_branches; ++b) reads[s] += cohort.best[s * cohort.num_branches + b];
-                epik_amd::write_through_part(cohort_rarefy_filename, epik_amd::format_rarefy_tsv(cohort_samples, reads.data(), rarefy_step,
-                                                                                                 rarefy_depths, diversity.curve.data()));
-            }
-            std::vector<uint64_t> mass_of(cohort_samples.size(), 0);  // (T_s, the sum wrapping as the rule's: what the files below take)
-            for (size_t s = 0; s < mass_of.size(); ++s)
-                for (size_t b = 0; b < cohort.num_branches; ++b) mass_of[s] += cohort.mass[s * cohort.num_branches + b];
-            if (with_correlation || with_dispersion) {
-                if (with_correlation)
-                    epik_amd::write_through_part(cohort_correlation_filename,
-                                                 epik_amd::format_correlation_tsv(cohort_samples, mass_of.data(), metadata.columns,
-                                                                                  (uint32_t)cohort.num_branches, edges.correlation.data(),
-                                                                                  edges.used.data()));
-                if (with_dispersion)
-                    epik_amd::write_through_part(cohort_dispersion_filename,
-                                                 epik_amd::format_dispersion_tsv(cohort_samples, mass_of.data(), (uint32_t)cohort.num_branches,
-                                                                                 edges.dispersion.data()));
-            }
-            if (with_permanova) {
-                epik_amd::write_through_part(
-                    cohort_permanova_filename,
-                    epik_amd::with_strata_field(epik_amd::format_permanova_tsv(cohort_samples, mass_of.data(), factors.columns, factors.names,
-                                                                               factors.labels.data(), permanova_permutations, permanova_seed,
-                                                                               permanova_pairwise, permanova.records.data(),
-                                                                               permanova.group_ss.data(), cohort_distance),
-                                                strata_name));
-                warn_nested("--cohort-permanova", factors.columns, factors.labels.data(), EPIK_AMD_PERMANOVA_MISSING, mass_of);
-            }
-            if (with_edgetest) {
-                epik_amd::write_through_part(
-                    cohort_edgetest_filename,
-                    epik_amd::with_strata_field(epik_amd::format_edgetest_tsv(cohort_samples, mass_of.data(), edge_factors.columns,
-                                                                              edge_factors.names, edge_factors.labels.data(),
-                                                                              (uint32_t)cohort.num_branches, edgetest_permutations,
-                                                                              edgetest_seed, edgetest.records.data()),
-                                                strata_name));
-                warn_nested("--cohort-edge-test", edge_factors.columns, edge_factors.labels.data(), EPIK_AMD_EDGETEST_MISSING, mass_of);
-            }
-            if (with_permdisp) {
-                epik_amd::write_through_part(
-                    cohort_permdisp_filename,
-                    epik_amd::with_strata_field(epik_amd::format_permdisp_tsv(cohort_samples, mass_of.data(), disp_factors.columns,
-                                                                              disp_factors.names, disp_factors.labels.data(),
-                                                                              permdisp_permutations, permdisp_seed, permdisp_pairwise,
-                                                                              permdisp.records.data(), permdisp.group_mean.data(),
-                                                                              permdisp.z.data(), cohort_distance),
-                                                strata_name));
-                warn_nested("--cohort-permdisp", disp_factors.columns, disp_factors.labels.data(), EPIK_AMD_PERMDISP_MISSING, mass_of);
-                const size_t slots = permdisp.records.size() / disp_factors.columns.size();
-                for (size_t c = 0; c < disp_factors.columns.size(); ++c) permdisp_clipped += permdisp.records[c * slots].clipped;
-            }
-            if (with_mantel || with_anosim) {
-                if (with_mantel)
-                    epik_amd::write_through_part(
-                        cohort_mantel_filename,
-                        epik_amd::with_strata_field(epik_amd::format_mantel_tsv(cohort_samples, mass_of.data(), mantel_read.names,
-                                                                                mantel_read.num_columns, mantel_methods, mantel_read.control,
-                                                                                mantel_permutations, mantel_seed, mantel.records.data(),
-                                                                                cohort_distance),
-                                                    strata_name));
-                if (with_anosim) {
-                    epik_amd::write_through_part(
-                        cohort_anosim_filename,
-                        epik_amd::with_strata_field(epik_amd::format_anosim_tsv(cohort_samples, mass_of.data(), anosim_factors.columns,
-                                                                                anosim_factors.names, anosim_factors.labels.data(),
-                                                                                anosim_permutations, anosim_seed, anosim.records.data(),
-                                                                                cohort_distance),
-                                                    strata_name));
-                    warn_nested("--cohort-anosim", anosim_factors.columns, anosim_factors.labels.data(), EPIK_AMD_PERMANOVA_MISSING, mass_of);
-                }
-            }
-            if (with_model) {
-                epik_amd::write_through_part(
-                    cohort_model_filename,
-                    epik_amd::with_strata_field(epik_amd::format_model_tsv(cohort_samples, mass_of.data(), design, model_permutations,
-                                                                           model_seed, model.records.data(), model.info,
-                                                                           model.aliased.data(), cohort_distance),
-                                                strata_name));
-                // (the model's used samples are the complete cases)
-                const size_t T = design.terms.size();
-                std::vector<uint64_t> complete(mass_of);
-                for (size_t s = 0; s < complete.size(); ++s)
-                    for (size_t t = 0; t < T; ++t)
-                        if (design.kind[t] ? std::isnan(design.values[s * T + t]) : design.labels[s * T + t] == EPIK_AMD_MODEL_MISSING)
-                            complete[s] = 0;
-                for (size_t t = 0; with_strata && t < T; ++t)
-                    if (!design.kind[t] && epik_amd::constant_within_strata(design.labels.data(), complete.size(), T, t,
-                                                                            EPIK_AMD_MODEL_MISSING, complete.data(), within))
-                        std::cout << "Warning: --cohort-model: the term " << design.terms[t] << " is constant inside every stratum of "
-                                  << strata_name << ": no permutation changes its sum of squares" << std::endl;
-                for (const uint8_t byte : model.aliased) model_aliased += byte;
-            }
-            if (with_edgemodel) {
-                epik_amd::write_through_part(
-                    cohort_edgemodel_filename,
-                    epik_amd::with_strata_field(epik_amd::format_edgemodel_tsv(cohort_samples, mass_of.data(), edge_design,
-                                                                               (uint32_t)cohort.num_branches, edgemodel_permutations,
-                                                                               edgemodel_seed, edgemodel.records.data(), edgemodel.info,
-                                                                               edgemodel.aliased.data()),
-                                                strata_name));
-                for (const uint8_t byte : edgemodel.aliased) edgemodel_aliased += byte;
-            }
-            if (with_pcoa) {
-                epik_amd::write_through_part(cohort_pcoa_filename, epik_amd::format_pcoa_tsv(cohort_samples, mass_of.data(), pcoa.num_components,
-                                                                                             pcoa.mu.data(), pcoa.coord.data(), pcoa.info,
-                                                                                             cohort_distance));
-                pcoa_converged = pcoa.info.converged != 0;
-            }
-            if (with_squash) {
-                epik_amd::write_through_part(cohort_squash_filename,
-                                             epik_amd::format_squash_tsv(cohort_samples, live, merges.data(), num_merges));
-                epik_amd::write_through_part(cohort_squash_tree_filename,
-                                             epik_amd::format_squash_newick(cohort_samples, live, merges.data(), num_merges));
-            }
-        }
+        cohort_plan.run_and_write(placer, query_file, output_dir);
         if (with_assign) {
-            assign_out.close();
-            if (!assign_out) throw std::runtime_error("Could not write " + assign_filename + ".part");
-            {
-                std::ifstream part(assign_filename + ".part", std::ios::binary);
-                std::ofstream whole(assign_filename, std::ios::binary);
-                whole << epik_amd::format_assign_header(assign_tau_q, assign_records);
-                if (assign_records) whole << part.rdbuf();
-                whole.close();
-                if (!part || !whole) throw std::runtime_error("Could not write " + assign_filename);
-            }
-            std::remove((assign_filename + ".part").c_str());
+            finish_part_file(assign_out, assign_filename, epik_amd::format_assign_header(assign_tau_q, assign_records), assign_records);
             epik_amd::write_text_file(assign_clades_filename, epik_amd::format_assign_clades_tsv(assign_sums, *assign_tree, assign_tau_q));
         }
         if (with_taxonomy) {
@@ -1481,19 +889,9 @@ int main(int argc, char** argv)
             } else {
                 epik_amd::write_through_part(taxa_filename, epik_amd::format_taxa_tsv(cells, 0, taxa, taxonomy_tau_q));
             }
-            if (taxonomy_per_read) {
-                taxa_reads_out.close();
-                if (!taxa_reads_out) throw std::runtime_error("Could not write " + taxa_reads_filename + ".part");
-                {
-                    std::ifstream part(taxa_reads_filename + ".part", std::ios::binary);
-                    std::ofstream whole(taxa_reads_filename, std::ios::binary);
-                    whole << epik_amd::format_taxa_reads_header(taxonomy_tau_q, taxa_reads_records);
-                    if (taxa_reads_records) whole << part.rdbuf();
-                    whole.close();
-                    if (!part || !whole) throw std::runtime_error("Could not write " + taxa_reads_filename);
-                }
-                std::remove((taxa_reads_filename + ".part").c_str());
-            }
+            if (taxonomy_per_read)
+                finish_part_file(taxa_reads_out, taxa_reads_filename, epik_amd::format_taxa_reads_header(taxonomy_tau_q, taxa_reads_records),
+                                 taxa_reads_records);
         }
         if (num_iterations) average_speed /= (double)num_iterations;
         std::cout << std::endl
@@ -1501,51 +899,7 @@ int main(int argc, char** argv)
                   << " seq/s.\n";
         if (jplace) std::cout << "Output: " << jplace_filename << std::endl;
         if (with_profile) std::cout << "Profile: " << profile_filename << std::endl;
-        if (with_cohort)
-            std::cout << "Cohort samples: " << cohort_samples_filename << "\nCohort profile: " << cohort_profile_filename
-                      << "\nCohort distances: " << cohort_kr_filename << std::endl;
-        for (const uint32_t metric : unifrac_metrics)
-            std::cout << "Cohort UniFrac distances (" << epik_amd::distance_name(metric) << "): " << cohort_unifrac_filename(metric) << std::endl;
-        if (with_squash)
-            std::cout << "Cohort clustering: " << cohort_squash_filename << "\nCohort cluster tree: " << cohort_squash_tree_filename
-                      << std::endl;
-        if (with_epca)
-            std::cout << "Cohort principal components: " << cohort_epca_filename << "\nCohort component edges: " << cohort_epca_edges_filename
-                      << std::endl;
-        if (!epca_converged)
-            std::cout << "Warning: the edge principal components did not converge in " << EPIK_AMD_EPCA_MAX_SWEEPS
-                      << " sweeps (converged=0 in " << cohort_epca_filename << ")" << std::endl;
-        if (with_kmeans)
-            std::cout << "Cohort k-means: " << cohort_kmeans_filename << "\nCohort k-means centroids: " << cohort_kmeans_centroids_filename
-                      << std::endl;
-        if (!kmeans_converged)
-            std::cout << "Warning: the phylogenetic k-means did not converge in " << kmeans_iterations
-                      << " iterations (converged=0 in " << cohort_kmeans_filename << ")" << std::endl;
-        if (with_alpha) std::cout << "Cohort alpha diversity: " << cohort_alpha_filename << std::endl;
-        if (with_rarefy) std::cout << "Cohort rarefaction curves: " << cohort_rarefy_filename << std::endl;
-        if (with_correlation) std::cout << "Cohort edge correlation: " << cohort_correlation_filename << std::endl;
-        if (with_dispersion) std::cout << "Cohort edge dispersion: " << cohort_dispersion_filename << std::endl;
-        if (with_permanova) std::cout << "Cohort PERMANOVA: " << cohort_permanova_filename << std::endl;
-        if (with_edgetest) std::cout << "Cohort edge test: " << cohort_edgetest_filename << std::endl;
-        if (with_permdisp) std::cout << "Cohort PERMDISP: " << cohort_permdisp_filename << std::endl;
-        if (with_mantel) std::cout << "Cohort Mantel: " << cohort_mantel_filename << std::endl;
-        if (with_anosim) std::cout << "Cohort ANOSIM: " << cohort_anosim_filename << std::endl;
-        if (with_model) std::cout << "Cohort model: " << cohort_model_filename << std::endl;
-        if (model_aliased)
-            std::cout << "Warning: " << model_aliased << " columns of the design are explained by the columns before them and were "
-                      << "dropped (the # aliased lines of " << cohort_model_filename << ")" << std::endl;
-        if (with_edgemodel) std::cout << "Cohort edge model: " << cohort_edgemodel_filename << std::endl;
-        if (edgemodel_aliased)
-            std::cout << "Warning: " << edgemodel_aliased << " columns of the edge model's design are explained by the columns before "
-                      << "them and were dropped (the # aliased lines of " << cohort_edgemodel_filename << ")" << std::endl;
-        if (permdisp_clipped)
-            std::cout << "Warning: " << permdisp_clipped << " squared distances to a group centroid are negative (the "
-                      << (cohort_distance == EPIK_AMD_DISTANCE_KR ? "KR" : epik_amd::distance_name(cohort_distance)) << " distance is not "
-                      << "Euclidean) and count as zero (the clipped column of " << cohort_permdisp_filename << ")" << std::endl;
-        if (with_pcoa) std::cout << "Cohort principal coordinates: " << cohort_pcoa_filename << std::endl;
-        if (!pcoa_converged)
-            std::cout << "Warning: the principal coordinates did not converge in " << EPIK_AMD_PCOA_MAX_SWEEPS
-                      << " sweeps (converged=0 in " << cohort_pcoa_filename << ")" << std::endl;
+        cohort_plan.print_summary();
         if (with_taxonomy) std::cout << "Taxa: " << taxa_filename << std::endl;
         if (taxonomy_per_read) std::cout << "Taxa of the reads: " << taxa_reads_filename << std::endl;
         if (with_assign) std::cout << "Assignments: " << assign_filename << "\nAssigned clades: " << assign_clades_filename << std::endl;

@@ -306,49 +306,49 @@ void placer::read_taxonomy(uint64_t* direct, uint64_t* assigned, epik_amd_taxa_t
     if (bad_samples) throw std::runtime_error("GPU placer: " + std::to_string(bad_samples) + " reads of no sample of the taxonomy object");
 }
 
-void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
-                         epik_amd_squash_merge* merges, uint32_t* num_merges, cohort_epca* epca, cohort_kmeans* kmeans,
-                         cohort_diversity* diversity, cohort_edges* edges, cohort_permanova* permanova,
-                         cohort_edgetest* edgetest, cohort_pcoa* pcoa, cohort_permdisp* permdisp, cohort_unifrac* unifrac,
-                         cohort_model* model, cohort_mantel* mantel, cohort_anosim* anosim, cohort_edgemodel* edgemodel)
+void placer::read_cohort(cohort_request& request)
 {
-    if (edgemodel && !&epik_amd_cohort_edgemodel_strata) throw std::runtime_error("GPU placer: this libepik_amd has no edge model");
-    if ((mantel && !&epik_amd_cohort_mantel) || (anosim && !&epik_amd_cohort_anosim))
+    const uint32_t* const strata = request.strata;
+    const uint32_t distance = request.distance;
+    if (request.edgemodel && !&epik_amd_cohort_edgemodel_strata) throw std::runtime_error("GPU placer: this libepik_amd has no edge model");
+    if ((request.mantel && !&epik_amd_cohort_mantel) || (request.anosim && !&epik_amd_cohort_anosim))
         throw std::runtime_error("GPU placer: this libepik_amd has no Mantel test or no ANOSIM");
-    if (model && !&epik_amd_cohort_model_metric) throw std::runtime_error("GPU placer: this libepik_amd has no sequential model");
-    if (((permanova && permanova->strata) || (permdisp && permdisp->strata) || (edgetest && edgetest->strata) || (model && model->strata)) &&
+    if (request.model && !&epik_amd_cohort_model_metric) throw std::runtime_error("GPU placer: this libepik_amd has no sequential model");
+    if (strata && (request.permanova || request.permdisp || request.edgetest || request.model) &&
         (!&epik_amd_cohort_permanova_strata || !&epik_amd_cohort_permdisp_strata || !&epik_amd_cohort_edgetest_strata ||
          !&epik_amd_cohort_model_strata))
         throw std::runtime_error("GPU placer: this libepik_amd has no permutations within strata");
-    const uint32_t distance = unifrac ? unifrac->distance : EPIK_AMD_DISTANCE_KR;
-    if (unifrac && (!&epik_amd_cohort_unifrac || !&epik_amd_cohort_permanova_metric || !&epik_amd_cohort_pcoa_metric ||
-                    !&epik_amd_cohort_permdisp_metric))
+    if ((request.unifrac || distance != EPIK_AMD_DISTANCE_KR) && (!&epik_amd_cohort_unifrac || !&epik_amd_cohort_permanova_metric ||
+                                                          !&epik_amd_cohort_pcoa_metric || !&epik_amd_cohort_permdisp_metric))
         throw std::runtime_error("GPU placer: this libepik_amd has no UniFrac distances");
-    if (permdisp && !&epik_amd_cohort_permdisp) throw std::runtime_error("GPU placer: this libepik_amd has no PERMDISP");
-    if (pcoa && !&epik_amd_cohort_pcoa) throw std::runtime_error("GPU placer: this libepik_amd has no principal coordinates");
-    if (edgetest && !&epik_amd_cohort_edgetest) throw std::runtime_error("GPU placer: this libepik_amd has no edge test");
-    if (permanova && !&epik_amd_cohort_permanova) throw std::runtime_error("GPU placer: this libepik_amd has no PERMANOVA");
-    if (edges && (!&epik_amd_cohort_correlation || !&epik_amd_cohort_dispersion))
+    if (request.permdisp && !&epik_amd_cohort_permdisp) throw std::runtime_error("GPU placer: this libepik_amd has no PERMDISP");
+    if (request.pcoa && !&epik_amd_cohort_pcoa) throw std::runtime_error("GPU placer: this libepik_amd has no principal coordinates");
+    if (request.edgetest && !&epik_amd_cohort_edgetest) throw std::runtime_error("GPU placer: this libepik_amd has no edge test");
+    if (request.permanova && !&epik_amd_cohort_permanova) throw std::runtime_error("GPU placer: this libepik_amd has no PERMANOVA");
+    if ((request.correlation || request.dispersion) && (!&epik_amd_cohort_correlation || !&epik_amd_cohort_dispersion))
         throw std::runtime_error("GPU placer: this libepik_amd has no edge correlation and dispersion");
-    if (diversity && (!&epik_amd_cohort_alpha || !&epik_amd_cohort_rarefy))
+    if ((request.alpha || request.rarefy) && (!&epik_amd_cohort_alpha || !&epik_amd_cohort_rarefy))
         throw std::runtime_error("GPU placer: this libepik_amd has no alpha diversity and rarefaction");
-    if (kmeans && !&epik_amd_cohort_kmeans) throw std::runtime_error("GPU placer: this libepik_amd has no phylogenetic k-means");
-    if (num_merges && !&epik_amd_cohort_squash) throw std::runtime_error("GPU placer: this libepik_amd has no squash clustering");
-    if (epca && !&epik_amd_cohort_epca) throw std::runtime_error("GPU placer: this libepik_amd has no edge principal components");
+    if (request.kmeans && !&epik_amd_cohort_kmeans) throw std::runtime_error("GPU placer: this libepik_amd has no phylogenetic k-means");
+    if (request.squash && !&epik_amd_cohort_squash) throw std::runtime_error("GPU placer: this libepik_amd has no squash clustering");
+    if (request.epca && !&epik_amd_cohort_epca) throw std::runtime_error("GPU placer: this libepik_amd has no edge principal components");
     const auto check = [](int rc) {
         if (rc != EPIK_AMD_OK) throw std::runtime_error(std::string("GPU placer: ") + epik_amd_last_error());
     };
     if (_cohorts.empty()) throw std::runtime_error("GPU placer: no cohort (set_cohort)");
+    const size_t S = _cohort_samples, N = _original_tree.get_node_count();
+    request.cells = sample_cohort((uint32_t)S, (uint32_t)N);
+    request.kr.assign(S * S, 0.0);
     // integer adds: the sum is the same bits whichever handle placed which batch
     for (size_t g = 1; g < _cohorts.size(); ++g) {
-        check(epik_amd_cohort_read(_cohorts[g], mass, best, totals, nullptr));
-        check(epik_amd_cohort_add_cells(_cohorts[0], mass, best, totals));
+        check(epik_amd_cohort_read(_cohorts[g], request.cells.mass.data(), request.cells.best.data(), request.cells.totals.data(), nullptr));
+        check(epik_amd_cohort_add_cells(_cohorts[0], request.cells.mass.data(), request.cells.best.data(), request.cells.totals.data()));
         epik_amd_cohort_destroy(_cohorts[g]);  // (summed once: a second read_cohort finds it all in the first)
         _cohorts[g] = nullptr;
     }
     _cohorts.resize(1);
     uint64_t bad_samples = 0;
-    check(epik_amd_cohort_read(_cohorts[0], mass, best, totals, &bad_samples));
+    check(epik_amd_cohort_read(_cohorts[0], request.cells.mass.data(), request.cells.best.data(), request.cells.totals.data(), &bad_samples));
     if (bad_samples) throw std::runtime_error("GPU placer: " + std::to_string(bad_samples) + " reads of no sample of the cohort");
     std::vector<uint32_t> parent;
     std::vector<double> length;
@@ -358,128 +358,128 @@ void placer::read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals
     }
     epik_amd_tree* tree = nullptr;
     check(epik_amd_tree_create(_devices[0], parent.data(), length.data(), (uint32_t)parent.size(), &tree));
-    int rc = epik_amd_cohort_kr(_cohorts[0], tree, length.data(), kr);
-    if (unifrac) unifrac->matrix.assign(unifrac->metrics.size(), std::vector<double>((size_t)_cohort_samples * _cohort_samples, 0.0));
-    for (size_t i = 0; rc == EPIK_AMD_OK && unifrac && i < unifrac->metrics.size(); ++i)
-        rc = epik_amd_cohort_unifrac(_cohorts[0], tree, length.data(), unifrac->metrics[i], unifrac->matrix[i].data());
-    if (rc == EPIK_AMD_OK && num_merges) rc = epik_amd_cohort_squash(_cohorts[0], tree, length.data(), merges, num_merges);
-    if (rc == EPIK_AMD_OK && epca) {
-        const size_t N = parent.size(), K = epca->num_components;
-        epca->mu.assign(K, 0.0), epca->proj.assign((size_t)_cohort_samples * K, 0.0), epca->edge.assign(K * N, 0.0);
-        epca->first.resize(N);
-        for (size_t b = 0; b < N; ++b) epca->first[b] = (uint32_t)b;  // (post-order ids: a parent comes after its children)
+    epik_amd_cohort* const cohort = _cohorts[0];
+    const double* const len = length.data();
+    // the analyses in their fixed order; after the first that fails none runs.  Which entry serves a test -- the plain
+    // one, _metric or _strata -- is part of what an older libepik_amd can still run: the newer ones only where needed
+    int rc = epik_amd_cohort_kr(cohort, tree, len, request.kr.data());
+    const auto run = [&](bool engaged, auto&& call) {
+        if (rc == EPIK_AMD_OK && engaged) rc = call();
+    };
+    if (request.unifrac) request.unifrac->matrix.assign(request.unifrac->metrics.size(), std::vector<double>(S * S, 0.0));
+    for (size_t i = 0; request.unifrac && i < request.unifrac->metrics.size(); ++i)
+        run(true, [&] { return epik_amd_cohort_unifrac(cohort, tree, len, request.unifrac->metrics[i], request.unifrac->matrix[i].data()); });
+    run(request.squash.has_value(), [&] {
+        auto& t = *request.squash;
+        t.merges.assign(S ? S - 1 : 0, epik_amd_squash_merge{});
+        return epik_amd_cohort_squash(cohort, tree, len, t.merges.data(), &t.num_merges);
+    });
+    run(request.epca.has_value(), [&] {
+        auto& t = *request.epca;
+        const size_t K = t.num_components;
+        t.mu.assign(K, 0.0), t.proj.assign(S * K, 0.0), t.edge.assign(K * N, 0.0);
+        t.first.resize(N);
+        for (size_t b = 0; b < N; ++b) t.first[b] = (uint32_t)b;  // (post-order ids: a parent comes after its children)
         for (size_t b = 0; b < N; ++b)
-            if (parent[b] != EPIK_AMD_TREE_NO_PARENT && parent[b] < N)
-                epca->first[parent[b]] = std::min(epca->first[parent[b]], epca->first[b]);
-        rc = epik_amd_cohort_epca(_cohorts[0], tree, epca->num_components, epca->mu.data(), epca->proj.data(), epca->edge.data(),
-                                  &epca->info);
-    }
-    if (rc == EPIK_AMD_OK && kmeans) {
-        const size_t N = parent.size(), K = kmeans->num_clusters;
-        kmeans->samples.assign(_cohort_samples, epik_amd_kmeans_sample{}), kmeans->clusters.assign(K, epik_amd_kmeans_cluster{});
-        kmeans->centroids.assign(K * N, 0.0);
-        rc = epik_amd_cohort_kmeans(_cohorts[0], tree, length.data(), kmeans->num_clusters, kmeans->max_iterations,
-                                    kmeans->samples.data(), kmeans->clusters.data(), kmeans->centroids.data(), &kmeans->info);
-    }
-    if (rc == EPIK_AMD_OK && diversity && diversity->with_alpha) {
-        diversity->alpha.assign(_cohort_samples, epik_amd_alpha{});
-        rc = epik_amd_cohort_alpha(_cohorts[0], tree, length.data(), diversity->alpha.data());
-    }
-    if (rc == EPIK_AMD_OK && diversity && diversity->num_depths) {
-        diversity->curve.assign((size_t)_cohort_samples * diversity->num_depths * 2, 0.0);
-        rc = epik_amd_cohort_rarefy(_cohorts[0], tree, length.data(), diversity->depth_step, diversity->num_depths,
-                                    diversity->curve.data());
-    }
-    if (rc == EPIK_AMD_OK && edges && edges->num_columns) {
-        edges->correlation.assign((size_t)edges->num_columns * parent.size(), epik_amd_correlation{});
-        edges->used.assign(edges->num_columns, 0);
-        rc = epik_amd_cohort_correlation(_cohorts[0], tree, edges->meta, edges->num_columns, edges->correlation.data(),
-                                         edges->used.data());
-    }
-    if (rc == EPIK_AMD_OK && edges && edges->with_dispersion) {
-        edges->dispersion.assign(parent.size(), epik_amd_dispersion{});
-        rc = epik_amd_cohort_dispersion(_cohorts[0], tree, edges->dispersion.data());
-    }
-    if (rc == EPIK_AMD_OK && permanova) {
-        const size_t slots = 1 + (permanova->pairwise ? EPIK_AMD_PERMANOVA_PAIR_SLOTS : 0);
-        permanova->records.assign(permanova->num_columns * slots, epik_amd_permanova{});
-        permanova->group_ss.assign((size_t)permanova->num_columns * EPIK_AMD_PERMANOVA_MAX_GROUPS, 0.0);
-        rc = permanova->strata
-                 ? epik_amd_cohort_permanova_strata(_cohorts[0], tree, length.data(), distance, permanova->labels, permanova->num_columns,
-                                                    permanova->num_permutations, permanova->seed, permanova->pairwise ? 1 : 0,
-                                                    permanova->records.data(), nullptr, permanova->group_ss.data(), permanova->strata)
-             : distance != EPIK_AMD_DISTANCE_KR
-                 ? epik_amd_cohort_permanova_metric(_cohorts[0], tree, length.data(), distance, permanova->labels, permanova->num_columns,
-                                                    permanova->num_permutations, permanova->seed, permanova->pairwise ? 1 : 0,
-                                                    permanova->records.data(), nullptr, permanova->group_ss.data())
-                 : epik_amd_cohort_permanova(_cohorts[0], tree, length.data(), permanova->labels, permanova->num_columns,
-                                             permanova->num_permutations, permanova->seed, permanova->pairwise ? 1 : 0,
-                                             permanova->records.data(), nullptr, permanova->group_ss.data());
-    }
-    if (rc == EPIK_AMD_OK && edgetest) {
-        edgetest->records.assign((size_t)edgetest->num_columns * parent.size(), epik_amd_edgetest{});
-        rc = edgetest->strata
-                 ? epik_amd_cohort_edgetest_strata(_cohorts[0], tree, edgetest->labels, edgetest->num_columns, edgetest->num_permutations,
-                                                   edgetest->seed, edgetest->records.data(), nullptr, nullptr, edgetest->strata)
-                 : epik_amd_cohort_edgetest(_cohorts[0], tree, edgetest->labels, edgetest->num_columns, edgetest->num_permutations,
-                                            edgetest->seed, edgetest->records.data(), nullptr, nullptr);
-    }
-    if (rc == EPIK_AMD_OK && pcoa) {
-        pcoa->mu.assign(_cohort_samples, 0.0), pcoa->coord.assign((size_t)_cohort_samples * pcoa->num_components, 0.0);
-        rc = distance != EPIK_AMD_DISTANCE_KR
-                 ? epik_amd_cohort_pcoa_metric(_cohorts[0], tree, length.data(), distance, pcoa->num_components, pcoa->mu.data(),
-                                               pcoa->coord.data(), &pcoa->info)
-                 : epik_amd_cohort_pcoa(_cohorts[0], tree, length.data(), pcoa->num_components, pcoa->mu.data(), pcoa->coord.data(),
-                                        &pcoa->info);
-    }
-    if (rc == EPIK_AMD_OK && permdisp) {
-        const size_t slots = 1 + (permdisp->pairwise ? EPIK_AMD_PERMDISP_PAIR_SLOTS : 0);
-        permdisp->records.assign(permdisp->num_columns * slots, epik_amd_permdisp{});
-        permdisp->group_mean.assign((size_t)permdisp->num_columns * EPIK_AMD_PERMDISP_MAX_GROUPS, 0.0);
-        permdisp->z.assign((size_t)permdisp->num_columns * _cohort_samples, 0.0);
-        rc = permdisp->strata
-                 ? epik_amd_cohort_permdisp_strata(_cohorts[0], tree, length.data(), distance, permdisp->labels, permdisp->num_columns,
-                                                   permdisp->num_permutations, permdisp->seed, permdisp->pairwise ? 1 : 0,
-                                                   permdisp->records.data(), nullptr, permdisp->group_mean.data(), permdisp->z.data(),
-                                                   permdisp->strata)
-             : distance != EPIK_AMD_DISTANCE_KR
-                 ? epik_amd_cohort_permdisp_metric(_cohorts[0], tree, length.data(), distance, permdisp->labels, permdisp->num_columns,
-                                                   permdisp->num_permutations, permdisp->seed, permdisp->pairwise ? 1 : 0,
-                                                   permdisp->records.data(), nullptr, permdisp->group_mean.data(), permdisp->z.data())
-                 : epik_amd_cohort_permdisp(_cohorts[0], tree, length.data(), permdisp->labels, permdisp->num_columns,
-                                            permdisp->num_permutations, permdisp->seed, permdisp->pairwise ? 1 : 0,
-                                            permdisp->records.data(), nullptr, permdisp->group_mean.data(), permdisp->z.data());
-    }
-    if (rc == EPIK_AMD_OK && model) {
-        model->records.assign((size_t)model->num_terms + 1, epik_amd_model_term{});
-        model->aliased.assign(EPIK_AMD_MODEL_MAX_COLUMNS, 0);
-        rc = model->strata
-                 ? epik_amd_cohort_model_strata(_cohorts[0], tree, length.data(), distance, model->kind, model->labels, model->values,
-                                                model->num_terms, model->num_permutations, model->seed, model->records.data(),
-                                                &model->info, nullptr, model->aliased.data(), model->strata)
-                 : epik_amd_cohort_model_metric(_cohorts[0], tree, length.data(), distance, model->kind, model->labels, model->values,
-                                                model->num_terms, model->num_permutations, model->seed, model->records.data(),
-                                                &model->info, nullptr, model->aliased.data());
-    }
-    if (rc == EPIK_AMD_OK && edgemodel) {
-        edgemodel->records.assign((size_t)edgemodel->num_terms * parent.size(), epik_amd_edgemodel{});
-        edgemodel->aliased.assign(EPIK_AMD_MODEL_MAX_COLUMNS, 0);
-        rc = epik_amd_cohort_edgemodel_strata(_cohorts[0], tree, edgemodel->kind, edgemodel->labels, edgemodel->values, edgemodel->num_terms,
-                                              edgemodel->num_permutations, edgemodel->seed, edgemodel->records.data(), &edgemodel->info,
-                                              nullptr, nullptr, edgemodel->aliased.data(), edgemodel->strata);
-    }
-    if (rc == EPIK_AMD_OK && mantel) {
-        const size_t per_side = (mantel->methods & 1u) + (mantel->methods >> 1 & 1u);
-        mantel->records.assign(((size_t)mantel->num_columns + mantel->num_matrices) * per_side, epik_amd_mantel{});
-        rc = epik_amd_cohort_mantel(_cohorts[0], tree, length.data(), distance, mantel->values, mantel->num_columns, mantel->matrices,
-                                    mantel->present, mantel->num_matrices, mantel->methods, mantel->control, mantel->num_permutations,
-                                    mantel->seed, mantel->strata, mantel->records.data(), nullptr);
-    }
-    if (rc == EPIK_AMD_OK && anosim) {
-        anosim->records.assign(anosim->num_columns, epik_amd_anosim{});
-        rc = epik_amd_cohort_anosim(_cohorts[0], tree, length.data(), distance, anosim->labels, anosim->num_columns,
-                                    anosim->num_permutations, anosim->seed, anosim->strata, anosim->records.data(), nullptr);
-    }
+            if (parent[b] != EPIK_AMD_TREE_NO_PARENT && parent[b] < N) t.first[parent[b]] = std::min(t.first[parent[b]], t.first[b]);
+        return epik_amd_cohort_epca(cohort, tree, t.num_components, t.mu.data(), t.proj.data(), t.edge.data(), &t.info);
+    });
+    run(request.kmeans.has_value(), [&] {
+        auto& t = *request.kmeans;
+        const size_t K = t.num_clusters;
+        t.samples.assign(S, epik_amd_kmeans_sample{}), t.clusters.assign(K, epik_amd_kmeans_cluster{}), t.centroids.assign(K * N, 0.0);
+        return epik_amd_cohort_kmeans(cohort, tree, len, t.num_clusters, t.max_iterations, t.samples.data(), t.clusters.data(),
+                                      t.centroids.data(), &t.info);
+    });
+    run(request.alpha.has_value(), [&] {
+        request.alpha->alpha.assign(S, epik_amd_alpha{});
+        return epik_amd_cohort_alpha(cohort, tree, len, request.alpha->alpha.data());
+    });
+    run(request.rarefy.has_value(), [&] {
+        auto& t = *request.rarefy;
+        t.curve.assign(S * t.num_depths * 2, 0.0);
+        return epik_amd_cohort_rarefy(cohort, tree, len, t.depth_step, t.num_depths, t.curve.data());
+    });
+    run(request.correlation.has_value(), [&] {
+        auto& t = *request.correlation;
+        t.correlation.assign((size_t)t.num_columns * N, epik_amd_correlation{});
+        t.used.assign(t.num_columns, 0);
+        return epik_amd_cohort_correlation(cohort, tree, t.meta, t.num_columns, t.correlation.data(), t.used.data());
+    });
+    run(request.dispersion.has_value(), [&] {
+        request.dispersion->dispersion.assign(N, epik_amd_dispersion{});
+        return epik_amd_cohort_dispersion(cohort, tree, request.dispersion->dispersion.data());
+    });
+    run(request.permanova.has_value(), [&] {
+        auto& t = *request.permanova;
+        t.records.assign(t.num_columns * (1 + (t.pairwise ? (size_t)EPIK_AMD_PERMANOVA_PAIR_SLOTS : 0)), epik_amd_permanova{});
+        t.group_ss.assign((size_t)t.num_columns * EPIK_AMD_PERMANOVA_MAX_GROUPS, 0.0);
+        return strata ? epik_amd_cohort_permanova_strata(cohort, tree, len, distance, t.labels, t.num_columns, t.num_permutations, t.seed,
+                                                         t.pairwise ? 1 : 0, t.records.data(), nullptr, t.group_ss.data(), strata)
+               : distance != EPIK_AMD_DISTANCE_KR
+                   ? epik_amd_cohort_permanova_metric(cohort, tree, len, distance, t.labels, t.num_columns, t.num_permutations, t.seed,
+                                                      t.pairwise ? 1 : 0, t.records.data(), nullptr, t.group_ss.data())
+                   : epik_amd_cohort_permanova(cohort, tree, len, t.labels, t.num_columns, t.num_permutations, t.seed, t.pairwise ? 1 : 0,
+                                               t.records.data(), nullptr, t.group_ss.data());
+    });
+    run(request.edgetest.has_value(), [&] {
+        auto& t = *request.edgetest;
+        t.records.assign((size_t)t.num_columns * N, epik_amd_edgetest{});
+        return strata ? epik_amd_cohort_edgetest_strata(cohort, tree, t.labels, t.num_columns, t.num_permutations, t.seed, t.records.data(),
+                                                        nullptr, nullptr, strata)
+                      : epik_amd_cohort_edgetest(cohort, tree, t.labels, t.num_columns, t.num_permutations, t.seed, t.records.data(),
+                                                 nullptr, nullptr);
+    });
+    run(request.pcoa.has_value(), [&] {
+        auto& t = *request.pcoa;
+        t.mu.assign(S, 0.0), t.coord.assign(S * t.num_components, 0.0);
+        return distance != EPIK_AMD_DISTANCE_KR
+                   ? epik_amd_cohort_pcoa_metric(cohort, tree, len, distance, t.num_components, t.mu.data(), t.coord.data(), &t.info)
+                   : epik_amd_cohort_pcoa(cohort, tree, len, t.num_components, t.mu.data(), t.coord.data(), &t.info);
+    });
+    run(request.permdisp.has_value(), [&] {
+        auto& t = *request.permdisp;
+        t.records.assign(t.num_columns * (1 + (t.pairwise ? (size_t)EPIK_AMD_PERMDISP_PAIR_SLOTS : 0)), epik_amd_permdisp{});
+        t.group_mean.assign((size_t)t.num_columns * EPIK_AMD_PERMDISP_MAX_GROUPS, 0.0);
+        t.z.assign((size_t)t.num_columns * S, 0.0);
+        return strata ? epik_amd_cohort_permdisp_strata(cohort, tree, len, distance, t.labels, t.num_columns, t.num_permutations, t.seed,
+                                                        t.pairwise ? 1 : 0, t.records.data(), nullptr, t.group_mean.data(), t.z.data(),
+                                                        strata)
+               : distance != EPIK_AMD_DISTANCE_KR
+                   ? epik_amd_cohort_permdisp_metric(cohort, tree, len, distance, t.labels, t.num_columns, t.num_permutations, t.seed,
+                                                     t.pairwise ? 1 : 0, t.records.data(), nullptr, t.group_mean.data(), t.z.data())
+                   : epik_amd_cohort_permdisp(cohort, tree, len, t.labels, t.num_columns, t.num_permutations, t.seed, t.pairwise ? 1 : 0,
+                                              t.records.data(), nullptr, t.group_mean.data(), t.z.data());
+    });
+    run(request.model.has_value(), [&] {
+        auto& t = *request.model;
+        t.records.assign((size_t)t.num_terms + 1, epik_amd_model_term{});
+        t.aliased.assign(EPIK_AMD_MODEL_MAX_COLUMNS, 0);
+        return strata ? epik_amd_cohort_model_strata(cohort, tree, len, distance, t.kind, t.labels, t.values, t.num_terms, t.num_permutations,
+                                                     t.seed, t.records.data(), &t.info, nullptr, t.aliased.data(), strata)
+                      : epik_amd_cohort_model_metric(cohort, tree, len, distance, t.kind, t.labels, t.values, t.num_terms, t.num_permutations,
+                                                     t.seed, t.records.data(), &t.info, nullptr, t.aliased.data());
+    });
+    run(request.edgemodel.has_value(), [&] {
+        auto& t = *request.edgemodel;
+        t.records.assign((size_t)t.num_terms * N, epik_amd_edgemodel{});
+        t.aliased.assign(EPIK_AMD_MODEL_MAX_COLUMNS, 0);
+        return epik_amd_cohort_edgemodel_strata(cohort, tree, t.kind, t.labels, t.values, t.num_terms, t.num_permutations, t.seed,
+                                                t.records.data(), &t.info, nullptr, nullptr, t.aliased.data(), strata);
+    });
+    run(request.mantel.has_value(), [&] {
+        auto& t = *request.mantel;
+        const size_t per_side = (t.methods & 1u) + (t.methods >> 1 & 1u);
+        t.records.assign(((size_t)t.num_columns + t.num_matrices) * per_side, epik_amd_mantel{});
+        return epik_amd_cohort_mantel(cohort, tree, len, distance, t.values, t.num_columns, t.matrices, t.present, t.num_matrices, t.methods,
+                                      t.control, t.num_permutations, t.seed, strata, t.records.data(), nullptr);
+    });
+    run(request.anosim.has_value(), [&] {
+        auto& t = *request.anosim;
+        t.records.assign(t.num_columns, epik_amd_anosim{});
+        return epik_amd_cohort_anosim(cohort, tree, len, distance, t.labels, t.num_columns, t.num_permutations, t.seed, strata,
+                                      t.records.data(), nullptr);
+    });
     const std::string message = rc != EPIK_AMD_OK ? epik_amd_last_error() : "";
     epik_amd_tree_destroy(tree);
     if (rc != EPIK_AMD_OK) throw std::runtime_error("GPU placer: " + message);

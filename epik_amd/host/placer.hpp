@@ -11,10 +11,12 @@
 #define EPIK_AMD_HOST_PLACER_HPP
 
 #include <functional>
+#include <optional>
 #include <string_view>
 #include <unordered_map>
 #include <vector>
 
+#include "cohort.hpp"
 #include "epik_amd.h"
 #include "phylo_kmer_db.hpp"
 #include "phylo_tree.hpp"
@@ -164,146 +166,138 @@ public:
     /// weight; it returns batches without rows and without strand / frame bytes.  Replicated databases only.
     void set_cohort(uint32_t num_samples);
     bool cohort_mode() const noexcept { return !_cohorts.empty(); }
-    /// The cohorts of all handles summed into the first one's (epik_amd_cohort_add_cells), read back -- `mass` and `best`
-    /// of num_samples * num_branches cells each, `totals` of num_samples --, and the KR distance between every two
-    /// samples computed on that device: `kr` of num_samples * num_samples values.  Once, at the end.  With `num_merges`
-    /// (--cohort-squash) the squash clustering of the samples too, there: `merges` of num_samples - 1 records.  With
-    /// `epca` (--cohort-epca) their edge principal components too: `epca->num_components` is K on entry; mu of K, proj
-    /// of num_samples * K, edge of K * num_branches values, the info block and the tree's first[] on return.
-    struct cohort_epca {
-        uint32_t num_components = 0;
+    /// What read_cohort computes: `cells` (mass, best and totals, sized here) and `kr` of num_samples * num_samples values
+    /// in every run, and each analysis whose member is engaged: its fields above the blank line are set on entry, those
+    /// below are sized and filled here.  `strata` (--cohort-strata: strata[num_samples], or null) is what every test that
+    /// permutes samples stays within; `distance` (EPIK_AMD_DISTANCE_*) is what permanova, pcoa, permdisp, model, mantel
+    /// and anosim run over.
+    struct cohort_squash {  ///< --cohort-squash: merges of num_samples - 1 records, num_merges of them used
+        std::vector<epik_amd_squash_merge> merges;
+        uint32_t num_merges = 0;
+    };
+    struct cohort_epca {  ///< --cohort-epca: mu of K, proj of num_samples * K, edge of K * num_branches, the tree's first[]
+        uint32_t num_components = 5;
+
         std::vector<double> mu, proj, edge;
         epik_amd_epca_info info{};
         std::vector<uint32_t> first;
     };
-    /// With `kmeans` (--cohort-kmeans) their phylogenetic k-means too: num_clusters (K) and max_iterations on entry;
-    /// samples of num_samples records, clusters of K, centroids of K * num_branches values and the info block on return.
-    struct cohort_kmeans {
-        uint32_t num_clusters = 0, max_iterations = 0;
+    struct cohort_kmeans {  ///< --cohort-kmeans: samples of num_samples, clusters of K, centroids of K * num_branches
+        uint32_t num_clusters = 0, max_iterations = 100;
+
         std::vector<epik_amd_kmeans_sample> samples;
         std::vector<epik_amd_kmeans_cluster> clusters;
         std::vector<double> centroids;
         epik_amd_kmeans_info info{};
     };
-    /// With `diversity` (--cohort-alpha, --cohort-rarefy): with_alpha asks for the alpha indices, alpha of num_samples
-    /// records on return; num_depths > 0 asks for the rarefaction curves at the depths j * depth_step, curve of
-    /// num_samples * num_depths * 2 values on return.
-    struct cohort_diversity {
-        bool with_alpha = false;
-        uint32_t depth_step = 0, num_depths = 0;
+    struct cohort_alpha {  ///< --cohort-alpha: alpha of num_samples records
         std::vector<epik_amd_alpha> alpha;
+    };
+    struct cohort_rarefy {  ///< --cohort-rarefy: the curves at the depths j * depth_step, curve of num_samples * num_depths * 2
+        uint32_t depth_step = 0, num_depths = 0;
+
         std::vector<double> curve;
     };
-    /// With `edges` (--cohort-correlation, --cohort-dispersion): num_columns > 0 asks for the edge correlation with
-    /// meta[S][M], correlation of M * num_branches records and used of M counts on return; with_dispersion asks for the edge
-    /// dispersion, dispersion of num_branches records on return.
-    struct cohort_edges {
+    struct cohort_correlation {  ///< --cohort-correlation with meta[S][M]: correlation of M * num_branches, used of M counts
         const double* meta = nullptr;
         uint32_t num_columns = 0;
-        bool with_dispersion = false;
+
         std::vector<epik_amd_correlation> correlation;
         std::vector<uint32_t> used;
+    };
+    struct cohort_dispersion {  ///< --cohort-dispersion: dispersion of num_branches records
         std::vector<epik_amd_dispersion> dispersion;
     };
-    /// With `permanova` (--cohort-permanova): PERMANOVA of labels[S][M] with num_permutations permutations from `seed`,
-    /// records of M * (1 + Q) tests (Q = 496 with pairwise, else 0) and group_ss of M * 256 sums on return.
-    struct cohort_permanova {
-        const uint32_t* labels = nullptr;
-        uint32_t num_columns = 0, num_permutations = 999;
-        uint64_t seed = 1;
-        bool pairwise = false;
-        const uint32_t* strata = nullptr;  ///< --cohort-strata: strata[S], the permutations stay within them; or null
-        std::vector<epik_amd_permanova> records;
-        std::vector<double> group_ss;
-    };
-    /// With `edgetest` (--cohort-edge-test): the edge test of labels[S][M] with num_permutations permutations from `seed`,
-    /// records of M * N (column, branch) pairs on return.
-    struct cohort_edgetest {
-        const uint32_t* labels = nullptr;
-        uint32_t num_columns = 0, num_permutations = 999;
-        uint64_t seed = 1;
-        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
-        std::vector<epik_amd_edgetest> records;
-    };
-    /// With `pcoa` (--cohort-pcoa): the principal coordinates of the samples over the KR distances; num_components is K on
-    /// entry; mu of num_samples eigenvalues, coord of num_samples * K values and the info block on return.
-    struct cohort_pcoa {
-        uint32_t num_components = 0;
+    struct cohort_pcoa {  ///< --cohort-pcoa: mu of num_samples eigenvalues, coord of num_samples * K
+        uint32_t num_components = 5;
+
         std::vector<double> mu, coord;
         epik_amd_pcoa_info info{};
     };
-    /// With `permdisp` (--cohort-permdisp): PERMDISP of labels[S][M] with num_permutations permutations from `seed`, with the
-    /// pairs of groups too where `pairwise`; records of M * (1 + Q) tests, group_mean of M * 32 and z of M * S values on return.
-    struct cohort_permdisp {
-        const uint32_t* labels = nullptr;
-        uint32_t num_columns = 0, num_permutations = 999;
+    struct cohort_unifrac {  ///< --cohort-unifrac: metrics (each at most once), matrix[i] of num_samples^2 for metrics[i]
+        std::vector<uint32_t> metrics;
+
+        std::vector<std::vector<double>> matrix;
+    };
+    /// What the tests that permute samples share; those over the factor columns labels[S][M] share these too
+    struct cohort_permutation_test {
+        uint32_t num_permutations = 999;
         uint64_t seed = 1;
+    };
+    struct cohort_factor_test : cohort_permutation_test {
+        const uint32_t* labels = nullptr;
+        uint32_t num_columns = 0;
+    };
+    struct cohort_permanova : cohort_factor_test {  ///< records of M * (1 + Q) tests (Q = 496 with pairwise), group_ss of M * 256
         bool pairwise = false;
-        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
+
+        std::vector<epik_amd_permanova> records;
+        std::vector<double> group_ss;
+    };
+    struct cohort_edgetest : cohort_factor_test {  ///< records of M * num_branches (column, branch) pairs
+        std::vector<epik_amd_edgetest> records;
+    };
+    struct cohort_permdisp : cohort_factor_test {  ///< records of M * (1 + Q) tests, group_mean of M * 32, z of M * S
+        bool pairwise = false;
+
         std::vector<epik_amd_permdisp> records;
         std::vector<double> group_mean, z;
     };
-    /// With `model` (--cohort-model): the sequential model of the design kind[T], labels[S][T], values[S][T] with
-    /// num_permutations permutations from `seed`; records of T + 1 terms, info and 64 aliased bytes on return.
-    struct cohort_model {
+    struct cohort_anosim : cohort_factor_test {  ///< records of M columns
+        std::vector<epik_amd_anosim> records;
+    };
+    /// The design kind[T], labels[S][T], values[S][T] of --cohort-model and --cohort-edge-model
+    struct cohort_design_test : cohort_permutation_test {
         const uint32_t* kind = nullptr;
         const uint32_t* labels = nullptr;
         const double* values = nullptr;
-        uint32_t num_terms = 0, num_permutations = 999;
-        uint64_t seed = 1;
-        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
+        uint32_t num_terms = 0;
+    };
+    struct cohort_model : cohort_design_test {  ///< records of T + 1 terms, info and 64 aliased bytes
         std::vector<epik_amd_model_term> records;
         epik_amd_model_info info{};
         std::vector<uint8_t> aliased;
     };
-    /// With `edgemodel` (--cohort-edge-model): the edge model of the design kind[T], labels[S][T], values[S][T] with
-    /// num_permutations permutations from `seed`; records of T * N (term, branch) pairs, info and 64 aliased bytes on return.
-    struct cohort_edgemodel {
-        const uint32_t* kind = nullptr;
-        const uint32_t* labels = nullptr;
-        const double* values = nullptr;
-        uint32_t num_terms = 0, num_permutations = 999;
-        uint64_t seed = 1;
-        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
+    struct cohort_edgemodel : cohort_design_test {  ///< records of T * num_branches (term, branch) pairs, info, 64 aliased bytes
         std::vector<epik_amd_edgemodel> records;
         epik_amd_edgemodel_info info{};
         std::vector<uint8_t> aliased;
     };
-    /// With `unifrac` (--cohort-unifrac, --cohort-distance): the UniFrac distances `metrics` (EPIK_AMD_DISTANCE_UNWEIGHTED ..
-    /// _GENERALIZED, each at most once), matrix[i] of num_samples * num_samples values for metrics[i] on return; and `distance`
-    /// (EPIK_AMD_DISTANCE_*), the distance that `permanova`, `pcoa`, `permdisp` and `model` run over instead of KR.
-    struct cohort_unifrac {
-        std::vector<uint32_t> metrics;
-        uint32_t distance = EPIK_AMD_DISTANCE_KR;
-        std::vector<std::vector<double>> matrix;
-    };
-    /// With `mantel` (--cohort-mantel, --cohort-mantel-matrix): the Mantel tests of the sides values[Mv][S], matrices[Mm][S][S] and
-    /// present[Mm][S] with the methods' bits and the control, num_permutations permutations from `seed`; records of
-    /// Q * popcount(methods) tests on return.  With `anosim` (--cohort-anosim): ANOSIM of labels[S][M]; records of M columns.  Both
-    /// run over the distance of `unifrac`, KR without one.
-    struct cohort_mantel {
+    /// The sides values[Mv][S], matrices[Mm][S][S] and present[Mm][S] with the methods' bits and the control; records of
+    /// Q * popcount(methods) tests
+    struct cohort_mantel : cohort_permutation_test {
         const double* values = nullptr;
         const double* matrices = nullptr;
         const uint8_t* present = nullptr;
         uint32_t num_columns = 0, num_matrices = 0, methods = EPIK_AMD_MANTEL_PEARSON, control = EPIK_AMD_MANTEL_NO_CONTROL;
-        uint32_t num_permutations = 999;
-        uint64_t seed = 1;
-        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
+
         std::vector<epik_amd_mantel> records;
     };
-    struct cohort_anosim {
-        const uint32_t* labels = nullptr;
-        uint32_t num_columns = 0, num_permutations = 999;
-        uint64_t seed = 1;
-        const uint32_t* strata = nullptr;  ///< as cohort_permanova's
-        std::vector<epik_amd_anosim> records;
+    struct cohort_request {
+        sample_cohort cells;
+        std::vector<double> kr;
+        const uint32_t* strata = nullptr;
+        uint32_t distance = EPIK_AMD_DISTANCE_KR;
+        std::optional<cohort_unifrac> unifrac;
+        std::optional<cohort_squash> squash;
+        std::optional<cohort_epca> epca;
+        std::optional<cohort_kmeans> kmeans;
+        std::optional<cohort_alpha> alpha;
+        std::optional<cohort_rarefy> rarefy;
+        std::optional<cohort_correlation> correlation;
+        std::optional<cohort_dispersion> dispersion;
+        std::optional<cohort_permanova> permanova;
+        std::optional<cohort_edgetest> edgetest;
+        std::optional<cohort_pcoa> pcoa;
+        std::optional<cohort_permdisp> permdisp;
+        std::optional<cohort_model> model;
+        std::optional<cohort_edgemodel> edgemodel;
+        std::optional<cohort_mantel> mantel;
+        std::optional<cohort_anosim> anosim;
     };
-    void read_cohort(uint64_t* mass, uint64_t* best, epik_amd_profile_totals* totals, double* kr,
-                     epik_amd_squash_merge* merges = nullptr, uint32_t* num_merges = nullptr, cohort_epca* epca = nullptr,
-                     cohort_kmeans* kmeans = nullptr, cohort_diversity* diversity = nullptr, cohort_edges* edges = nullptr,
-                     cohort_permanova* permanova = nullptr, cohort_edgetest* edgetest = nullptr, cohort_pcoa* pcoa = nullptr,
-                     cohort_permdisp* permdisp = nullptr, cohort_unifrac* unifrac = nullptr, cohort_model* model = nullptr,
-                     cohort_mantel* mantel = nullptr, cohort_anosim* anosim = nullptr, cohort_edgemodel* edgemodel = nullptr);
+    /// The cohorts of all handles summed into the first one's (epik_amd_cohort_add_cells) and read back, and the KR
+    /// distances and every engaged analysis of `request` computed on that device.  Once, at the end.
+    void read_cohort(cohort_request& request);
     /// --taxonomy: one device taxonomy object per handle (epik_amd_taxonomy) from taxon_parent[T] and label[N], with one
     /// row of cells per sample of the cohort (call set_cohort first) or one row; from then on place_flat goes through
     /// the epik_amd_placer_taxa_* entries: every unique sequence is added with the number of its records as weight, a
