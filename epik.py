@@ -50,6 +50,9 @@ negative ones of a distance that is not Euclidean, cohort_pcoa_<list>.tsv; --coh
 --cohort-unifrac LIST, with --cohort: the UniFrac distances between every two samples, LIST a comma-separated subset of
 unweighted, weighted, generalized, or all; cohort_unifrac_<metric>_<list>.tsv each.  --cohort-distance NAME (kr, unweighted,
 weighted, generalized): the distance --cohort-permanova, --cohort-pcoa and --cohort-permdisp run over (default kr).
+--windows W --window-groups FILE: long sequences painted by windows of W characters, every window placed by itself and called
+for a group of FILE (a taxonomy file); windows_<input>.tsv (segments) and windows_breakpoints_<input>.tsv, no jplace;
+--window-step S (default max(1, W / 4)), --window-mass (default 0.8), --window-rank D (default 1), --windows-per-window.
 """
 from __future__ import annotations
 
@@ -250,6 +253,21 @@ PLACE_OPTIONS = [
                                      "[default: 0.95].")),
     (("--taxonomy-per-read",), dict(is_flag=True, help="With --taxonomy: also write taxa_reads_<input>.tsv, per read its taxon, "
                                                        "that taxon's share of the mass and the taxon of its best row.")),
+    (("--windows",), dict(type=click.IntRange(1, (1 << 31) - 1), default=None,
+                          help="Paint long sequences by windows of this many characters: every window is placed by itself and "
+                               "called for a group of --window-groups; writes windows_<input>.tsv (segments) and "
+                               "windows_breakpoints_<input>.tsv and no jplace (not with --mates, --translate, --profile, "
+                               "--profile-only, --assign, --taxonomy, --cohort or --db-shard > 1).")),
+    (("--window-step",), dict(type=click.IntRange(1, (1 << 31) - 1), default=None,
+                              help="With --windows: the distance between two windows, in [1, window] [default: max(1, window / 4)].")),
+    (("--window-mass",), dict(type=float, default=None,
+                              help="With --windows: the share of a window's placement mass its group must hold, in (0.5, 1] "
+                                   "[default: 0.8].")),
+    (("--window-groups",), dict(type=click.Path(), default=None,
+                                help="With --windows (required): a taxonomy file, one leaf_label<TAB>A;B;C line per reference leaf.")),
+    (("--window-rank",), dict(type=click.IntRange(1, (1 << 32) - 1), default=None,
+                              help="With --windows: the groups are the taxa of this many elements of the taxopath [default: 1].")),
+    (("--windows-per-window",), dict(is_flag=True, help="With --windows: also write windows_all_<input>.tsv, a line per window.")),
 ]
 
 
@@ -277,7 +295,25 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
                    cohort_edge_model=None, cohort_edge_model_terms=None, cohort_edge_model_permutations=None, cohort_edge_model_seed=None,
                    cohort_strata=None, cohort_strata_column=None, cohort_mantel=None, cohort_mantel_matrix=(),
                    cohort_mantel_method=None, cohort_mantel_partial=None, cohort_mantel_permutations=None, cohort_mantel_seed=None,
-                   cohort_anosim=None, cohort_anosim_permutations=None, cohort_anosim_seed=None):
+                   cohort_anosim=None, cohort_anosim_permutations=None, cohort_anosim_seed=None, windows=None, window_step=None,
+                   window_mass=None, window_groups=None, window_rank=None, windows_per_window=False):
+    for flag, given in (("--window-step", window_step is not None), ("--window-mass", window_mass is not None),
+                        ("--window-groups", window_groups is not None), ("--window-rank", window_rank is not None),
+                        ("--windows-per-window", windows_per_window)):
+        if given and windows is None:
+            raise click.UsageError(f"{flag} needs --windows")
+    if windows is not None:
+        if window_groups is None:
+            raise click.UsageError("--windows needs --window-groups")
+        for flag, given in (("--mates", mates is not None), ("--translate", translate is not None), ("--profile", profile),
+                            ("--profile-only", profile_only), ("--assign", assign), ("--taxonomy", taxonomy is not None),
+                            ("--cohort", cohort), ("--db-shard > 1", db_shard != 1)):
+            if given:
+                raise click.UsageError(f"--windows does not work with {flag}")
+        if window_step is not None and int(window_step) > int(windows):
+            raise click.UsageError(f"--window-step must be a whole number in [1, {int(windows)}], not '{int(window_step)}'")
+        if window_mass is not None and not 0.5 < float(window_mass) <= 1.0:
+            raise click.UsageError("--window-mass must lie in (0.5, 1]")
     with_mantel = cohort_mantel is not None or len(cohort_mantel_matrix) > 0
     for flag, given in (("--cohort-mantel", cohort_mantel is not None), ("--cohort-mantel-matrix", len(cohort_mantel_matrix) > 0),
                         ("--cohort-anosim", cohort_anosim is not None)):
@@ -514,6 +550,16 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
             argv += ["--taxonomy-mass", repr(float(taxonomy_mass))]
         if taxonomy_per_read:
             argv += ["--taxonomy-per-read"]
+    if windows is not None:
+        argv += ["--windows", str(int(windows)), "--window-groups", str(window_groups)]
+        if window_step is not None:
+            argv += ["--window-step", str(int(window_step))]
+        if window_mass is not None:
+            argv += ["--window-mass", repr(float(window_mass))]
+        if window_rank is not None:
+            argv += ["--window-rank", str(int(window_rank))]
+        if windows_per_window:
+            argv += ["--windows-per-window"]
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 

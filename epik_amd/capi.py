@@ -25,6 +25,10 @@ PLACEMENT = np.dtype([("branch", np.uint32), ("score", np.float32), ("lwr", np.f
 CONFIDENCE = np.dtype([("clade", np.uint32), ("clade_mass_q", np.uint32), ("edpl", np.float64)])
 #: numpy mirror of `epik_amd_taxon_record` {taxon, taxon_mass_q, first_taxon, total_q} (16 bytes)
 TAXON_RECORD = np.dtype([("taxon", np.uint32), ("taxon_mass_q", np.uint32), ("first_taxon", np.uint32), ("total_q", np.uint32)])
+#: numpy mirrors of `epik_amd_window_record` (16 bytes) and `epik_amd_window_segment` (32 bytes)
+WINDOW_RECORD = np.dtype([("call", np.uint32), ("call_mass_q", np.uint32), ("first_group", np.uint32), ("total_q", np.uint32)])
+WINDOW_SEGMENT = np.dtype([("call", np.uint32), ("first_window", np.uint32), ("num_windows", np.uint32), ("reserved", np.uint32),
+                           ("call_mass", np.uint64), ("total", np.uint64)])
 #: numpy mirror of `epik_amd_taxa_totals` (48 bytes)
 TAXA_TOTALS = np.dtype([(name, np.uint64) for name in ("placed", "no_hit", "too_short", "too_narrow", "no_mass", "bad_reads")])
 #: epik_amd_squash_merge (32 bytes)
@@ -291,6 +295,13 @@ EXPORTS = (
     "epik_amd_placer_taxa_strands",
     "epik_amd_placer_taxa_frames",
     "epik_amd_placer_taxa_mates",
+    "epik_amd_window_span",
+    "epik_amd_placer_window_workspace_bytes",
+    "epik_amd_placer_place_windows_device",
+    "epik_amd_placer_place_windows",
+    "epik_amd_placer_paint_windows",
+    "epik_amd_windows_paint_device",
+    "epik_amd_windows_paint_host",
 )
 
 
@@ -382,6 +393,14 @@ TAXON_TOO_NARROW, TAXON_TOO_SHORT, TAXON_NO_HIT, TAXON_BAD_ROW, TAXON_NO_MASS = 
                                                                                  0xFFFFFFFB)
 TAXON_CLASSES = {TAXON_TOO_NARROW: "too_narrow", TAXON_TOO_SHORT: "too_short", TAXON_NO_HIT: "no_hit", TAXON_BAD_ROW: "bad_row",
                  TAXON_NO_MASS: "no_mass"}
+
+#: painting by windows (EPIK_AMD_WINDOW_*): the group of a branch above the groups, the most windows a read may have, and
+#: the calls of the windows that get no group
+WINDOW_NO_GROUP, WINDOW_MAX_PER_READ = 0xFFFFFFFF, 1 << 24
+WINDOW_TOO_NARROW, WINDOW_TOO_SHORT, WINDOW_NO_HIT, WINDOW_BAD_ROW, WINDOW_NO_MASS, WINDOW_AMBIGUOUS = (
+    0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC, 0xFFFFFFFB, 0xFFFFFFFA)
+WINDOW_CLASSES = {WINDOW_TOO_NARROW: "too_narrow", WINDOW_TOO_SHORT: "too_short", WINDOW_NO_HIT: "no_hit",
+                  WINDOW_BAD_ROW: "bad_row", WINDOW_NO_MASS: "no_mass", WINDOW_AMBIGUOUS: "ambiguous"}
 
 #: strand modes of epik_amd_placer_place_strands[_device], and their names in Placer / epik.py / epik-dna --strand
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
@@ -764,6 +783,21 @@ def load() -> ctypes.CDLL:
     for name in ("epik_amd_placer_taxa_strands", "epik_amd_placer_taxa_frames", "epik_amd_placer_taxa_mates"):
         getattr(lib, name).restype = i32
         getattr(lib, name).argtypes = [vp, vp, vp, u64, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    # (painting by windows)
+    lib.epik_amd_window_span.restype = u64
+    lib.epik_amd_window_span.argtypes = [u64, u32, u32, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.epik_amd_placer_window_workspace_bytes.restype = i32
+    lib.epik_amd_placer_window_workspace_bytes.argtypes = [vp, u64, u64, u64, u32, ctypes.POINTER(u64)]
+    lib.epik_amd_placer_place_windows_device.restype = i32
+    lib.epik_amd_placer_place_windows_device.argtypes = [vp, vp, vp, u64, u32, u32, u32, u64, u64, vp, u64, vp, vp, vp, vp, vp, vp]
+    lib.epik_amd_placer_place_windows.restype = i32
+    lib.epik_amd_placer_place_windows.argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp, vp]
+    lib.epik_amd_placer_paint_windows.restype = i32
+    lib.epik_amd_placer_paint_windows.argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.epik_amd_windows_paint_device.restype = i32
+    lib.epik_amd_windows_paint_device.argtypes = [i32, vp, vp, vp, vp, u64, u64, u32, vp, u32, u32, vp, vp, vp, vp]
+    lib.epik_amd_windows_paint_host.restype = i32
+    lib.epik_amd_windows_paint_host.argtypes = [vp, vp, vp, vp, u64, u32, vp, u32, u32, vp, vp, vp]
     _lib = lib
     return lib
 

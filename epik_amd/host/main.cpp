@@ -13,7 +13,8 @@
 // devices); --mates FILE (paired-end reads: the second mates, one placement per pair); --assign [--assign-mass T] (per
 // record the LCA clade that holds T of its placement mass and the EDPL, confidence.hpp, computed on the devices);
 // --cohort (the query is a list of samples: their profiles and the KR distance between every two of them, cohort.hpp,
-// summed and computed on the devices, no jplace).
+// summed and computed on the devices, no jplace); --windows W (long sequences painted by windows, windows.hpp: every
+// window placed by itself and called for a group of --window-groups, segments and breakpoints, no jplace).
 // The two binaries differ as the reference's do (epik/CMakeLists.txt:72,124): epik-dna
 // accepts DNA databases, epik-aa protein ones.
 #include <algorithm>
@@ -49,6 +50,7 @@
 #include "profile.hpp"
 #include "report.hpp"
 #include "seq_record.hpp"
+#include "windows.hpp"
 
 #ifndef EPIK_AMD_NO_MAIN
 namespace {
@@ -316,6 +318,18 @@ const char* kHelp =
     "                          --cohort-permanova's; any number of labels) gives every sample of the list its stratum; all of\n"
     "                          those tests of the run use it, and their files' first line ends in <TAB>strata=NAME\n"
     "      --cohort-strata-column arg  With --cohort-strata: the column of its file; required when the file has several\n"
+    "      --windows arg       Paint long sequences by windows of arg characters: every window is placed by itself and called\n"
+    "                          for the group of --window-groups that holds --window-mass of its placement mass.  Writes no\n"
+    "                          jplace but windows_<query>.tsv (per record its segments: runs of windows with one call) and\n"
+    "                          windows_breakpoints_<query>.tsv (where the call changes from one group to another); with\n"
+    "                          --strand both every window picks its own strand; not with --mates, --translate, --profile,\n"
+    "                          --profile-only, --assign, --taxonomy, --cohort or --db-shard > 1\n"
+    "      --window-step arg   With --windows: the distance between two windows, in [1, window] (default: max(1, window / 4))\n"
+    "      --window-mass arg   With --windows: the share of a window's placement mass its group must hold, in (0.5, 1]\n"
+    "                          (default: 0.8)\n"
+    "      --window-groups arg With --windows (required): a taxonomy file, one leaf_label<TAB>A;B;C line per reference leaf\n"
+    "      --window-rank arg   With --windows: the groups are the taxa of so many elements of the taxopath (default: 1)\n"
+    "      --windows-per-window  With --windows: also write windows_all_<query>.tsv, a line per window\n"
     "  -h, --help              Print usage\n";
 
 using epik_amd::options;
@@ -342,7 +356,7 @@ options parse_args(int argc, char** argv)
         } else {
             continue;  // positional arguments are ignored (epik.py passes the query twice, epik.py:88,96)
         }
-        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca" || name == "cohort-pcoa" || name == "cohort-alpha" || name == "cohort-dispersion" || name == "cohort-permanova-pairwise" || name == "cohort-permdisp-pairwise" || name == "taxonomy-per-read") && !have_value)) {  // flags
+        if (name == "help" || ((name == "profile" || name == "profile-only" || name == "assign" || name == "cohort" || name == "cohort-squash" || name == "cohort-epca" || name == "cohort-pcoa" || name == "cohort-alpha" || name == "cohort-dispersion" || name == "cohort-permanova-pairwise" || name == "cohort-permdisp-pairwise" || name == "taxonomy-per-read" || name == "windows-per-window") && !have_value)) {  // flags
             opt.values[name] = "1";
             continue;
         }
@@ -485,6 +499,8 @@ int main(int argc, char** argv)
             if (taxonomy_tau_q <= (1u << 29) || taxonomy_tau_q > (1u << 30))
                 throw std::runtime_error("--taxonomy-mass must be a number in (0.5, 1], not '" + text + "'");
         }
+        // --windows and the flags that depend on it: checked before anything is opened or any device touched
+        epik_amd::windows_plan windows_plan = epik_amd::parse_windows_options(parsed);
         const auto db_file = parsed.require("database");
         const auto query_file = parsed.require("query");
         const auto num_threads = (size_t)std::stoul(parsed.get("jobs", "1"));
@@ -499,6 +515,7 @@ int main(int argc, char** argv)
         cohort_plan.read_inputs(query_file);
         const std::vector<epik_amd::cohort_sample>& cohort_samples = cohort_plan.samples;
 
+        windows_plan.read_inputs();  // (--window-groups: the same reader, the same errors)
         // --taxonomy: the file read, and every error of it named by its line, before the database or a device is
         epik_amd::taxonomy taxa;
         if (with_taxonomy) {
@@ -592,6 +609,30 @@ int main(int argc, char** argv)
             placer.set_taxonomy(taxa.parent, label, taxonomy_tau_q, taxonomy_per_read);
         }
         db.drop_lists();  // the lists are on the devices now; tree, k and omega stay for the output
+        // --windows: a run of its own, no jplace
+        if (windows_plan.with_windows) {
+            std::vector<uint32_t> parent;
+            std::vector<std::string> names;
+            for (const auto& node : tree.nodes()) {
+                parent.push_back(node.parent < 0 ? EPIK_AMD_TREE_NO_PARENT : (uint32_t)node.parent);
+                names.push_back(node.get_label());
+            }
+            windows_plan.label(parent.data(), names, (uint32_t)parent.size());
+            std::cout << "Instruction set: gfx950 (" << placer.handle_count() << " device(s))" << std::endl;
+            std::cout << "Painting " << query_file << " by windows of " << windows_plan.window << " every " << windows_plan.step << " ("
+                      << windows_plan.group_paths.size() << " groups)..." << std::endl;
+            const auto begin = std::chrono::steady_clock::now();
+            const auto report = epik_amd::run_windows(placer, windows_plan, (uint32_t)strand, query_file, output_dir, batch_size, num_threads);
+            const auto ms = (size_t)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - begin).count();
+            std::cout << std::endl
+                      << "Painted " << report.records << " sequences: " << report.windows << " windows, " << report.segments
+                      << " segments, " << report.breakpoints << " breakpoints.\nWindows: " << report.windows_file
+                      << "\nBreakpoints: " << report.breakpoints_file << std::endl;
+            if (windows_plan.per_window) std::cout << "Windows, one by one: " << report.all_file << std::endl;
+            std::cout << "Placement time: " << epik_amd::human_duration(ms) << " (" << ms << " ms)" << std::endl;
+            std::cout << "Done." << '\n' << std::flush;
+            return 0;
+        }
         const auto tree_as_newick = epik_amd::io::to_newick(tree, true);
         const auto jplace_filename = make_output_filename(query_file, output_dir);
         const auto invocation = make_invocation(argc, argv);

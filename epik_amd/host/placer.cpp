@@ -65,6 +65,7 @@
 #pragma weak epik_amd_placer_taxa_strands
 #pragma weak epik_amd_placer_taxa_frames
 #pragma weak epik_amd_placer_taxa_mates
+#pragma weak epik_amd_placer_paint_windows
 
 namespace epik_amd {
 
@@ -285,6 +286,45 @@ void placer::set_taxonomy(const std::vector<uint32_t>& taxon_parent, const std::
         }
         _taxa.push_back(taxa);
     }
+}
+
+placer::window_batch placer::paint_windows(const std::vector<seq_record>& records, size_t device_index, uint32_t window,
+                                           uint32_t step, uint32_t strand_mode, const std::vector<uint32_t>& group, uint32_t tau_q,
+                                           bool per_window)
+{
+    if (_sharded) throw std::runtime_error("GPU placer: --windows does not work with --db-shard > 1");
+    if (!&epik_amd_placer_paint_windows) throw std::runtime_error("GPU placer: this libepik_amd has no windowed placement");
+    if (group.size() != _original_tree.get_node_count()) throw std::runtime_error("GPU placer: the groups do not fit the tree");
+    const uint64_t n = records.size();
+    window_batch out;
+    out.win_offsets.assign(n + 1, 0);
+    std::vector<uint64_t> offsets(n + 1, 0);
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t len = records[i].sequence().size();
+        const uint64_t nw = epik_amd_window_span(len, window, step, 0, nullptr, nullptr);
+        if (nw == 0) throw std::runtime_error("GPU placer: the window or its step is out of range");
+        offsets[i + 1] = offsets[i] + len;
+        out.win_offsets[i + 1] = out.win_offsets[i] + nw;
+    }
+    std::string bytes;
+    bytes.reserve(offsets[n]);
+    for (const auto& record : records) bytes.append(record.sequence());
+    const uint64_t total = out.win_offsets[n];
+    out.records.resize(total), out.segments.resize(total), out.n_segments.resize(n), out.strand.resize(total);
+    std::vector<epik_amd_placement> rows;
+    if (per_window) rows.resize(total * _keep_at_most), out.n_rows.resize(total);
+    std::vector<uint64_t> counted(n + 1, 0);
+    if (epik_amd_placer_paint_windows(_handles.at(device_index), bytes.data(), offsets.data(), n, window, step, strand_mode, group.data(),
+                                      tau_q, per_window ? rows.data() : nullptr, per_window ? out.n_rows.data() : nullptr, nullptr,
+                                      out.strand.data(), counted.data(), out.records.data(), out.segments.data(),
+                                      out.n_segments.data()) != EPIK_AMD_OK)
+        throw std::runtime_error(std::string("GPU placer: ") + epik_amd_last_error());
+    if (n && counted != out.win_offsets) throw std::runtime_error("GPU placer: the library counted other windows than the driver");
+    if (per_window) {
+        out.best.resize(total);
+        for (uint64_t v = 0; v < total; ++v) out.best[v] = rows[v * _keep_at_most];
+    }
+    return out;
 }
 
 void placer::read_taxonomy(uint64_t* direct, uint64_t* assigned, epik_amd_taxa_totals* totals)

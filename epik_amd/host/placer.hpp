@@ -309,6 +309,21 @@ public:
     /// The objects of all handles summed into the first one's (epik_amd_taxonomy_add_cells) and read back: direct and
     /// assigned of num_samples * num_taxa cells each, totals of num_samples.  Once, at the end.
     void read_taxonomy(uint64_t* direct, uint64_t* assigned, epik_amd_taxa_totals* totals);
+    /// --windows: what one batch of records gives (epik_amd_placer_paint_windows): record i owns the windows
+    /// win_offsets[i] .. win_offsets[i + 1] - 1 and the segments at win_offsets[i] + s, s < n_segments[i]
+    struct window_batch {
+        std::vector<uint64_t> win_offsets;
+        std::vector<epik_amd_window_record> records;
+        std::vector<epik_amd_window_segment> segments;
+        std::vector<uint32_t> n_segments;
+        std::vector<uint8_t> strand;
+        std::vector<uint32_t> n_rows;           ///< per_window only: the rows of every window ...
+        std::vector<epik_amd_placement> best;   ///< ... and the first of them
+    };
+    /// Every record of `records` cut into windows, placed and painted on device `device_index`: no de-duplication, the
+    /// records are independent.  Replicated databases only (not --db-shard).  One call a device at a time.
+    window_batch paint_windows(const std::vector<seq_record>& records, size_t device_index, uint32_t window, uint32_t step,
+                               uint32_t strand_mode, const std::vector<uint32_t>& group, uint32_t tau_q, bool per_window);
     /// The profiles of all devices read back and summed; `mass` and `best` of num_branches cells each.
     void read_profiles(uint64_t* mass, uint64_t* best, epik_amd_profile_totals& totals) const;
     /// distal_length / pendant_length of a placement on branch b (place.cpp:110-123, 435-437)

@@ -5,6 +5,8 @@
 //                                                          out.bin: uint64 T; uint32 taxon_parent[T]; uint32 first[T];
 //                                                          uint32 label[N]; T taxopaths, each uint32 length + bytes.
 //                                                          An error goes to stdout, exit status 1.
+//   taxa_test groups <taxonomy.tsv> <tree.bin> <depth> <out.bin>  the groups painting by windows calls at that depth
+//                                                          (groups_at_rank): uint64 G; uint32 group[N]; uint32 group_taxa[G]
 //   taxa_test records <tau_q> <in.bin> <out.bin>           epik_amd_taxon_record [n]
 //   taxa_test cells <tau_q> <in.bin> <out.bin>             uint64 direct[S][T], assigned[S][T], totals[S][6], bad_samples
 //   taxa_test files <tau_q> <in.bin> <taxonomy.tsv> <prefix>  the three files of that batch, every read named read_<i> and
@@ -38,7 +40,7 @@ void write_array(std::ofstream& out, const T* data, size_t count)
     out.write(reinterpret_cast<const char*>(data), (std::streamsize)(count * sizeof(T)));
 }
 
-int labels(const char* taxonomy_path, const char* tree_path, const char* out_path)
+int labels(const char* taxonomy_path, const char* tree_path, const char* out_path, const char* depth = nullptr)
 {
     std::ifstream text(taxonomy_path);
     if (!text) throw std::runtime_error(std::string("cannot open ") + taxonomy_path);
@@ -67,6 +69,16 @@ int labels(const char* taxonomy_path, const char* tree_path, const char* out_pat
     if (epik_amd::taxonomy_first(taxa.parent.data(), taxa.num_taxa(), "taxon", first, err) != 0 || first != taxa.first)
         throw std::runtime_error("the parser's taxonomy does not validate: " + err);
     std::ofstream out(out_path, std::ios::binary);
+    if (depth) {
+        std::vector<uint32_t> group, group_taxa;
+        epik_amd::groups_at_rank(taxa, label, (uint32_t)std::stoul(depth), group, group_taxa);
+        const uint64_t G = group_taxa.size();
+        write_array(out, &G, 1);
+        write_array(out, group.data(), group.size());
+        write_array(out, group_taxa.data(), group_taxa.size());
+        if (!out) throw std::runtime_error(std::string("cannot write ") + out_path);
+        return 0;
+    }
     const uint64_t T = taxa.num_taxa();
     write_array(out, &T, 1);
     write_array(out, taxa.parent.data(), T);
@@ -160,10 +172,12 @@ int main(int argc, char** argv)
 {
     try {
         if (argc == 5 && std::strcmp(argv[1], "labels") == 0) return labels(argv[2], argv[3], argv[4]);
+        if (argc == 6 && std::strcmp(argv[1], "groups") == 0) return labels(argv[2], argv[3], argv[5], argv[4]);
         if (argc == 5 && std::strcmp(argv[1], "records") == 0) return assign(true, argv[2], argv[3], argv[4]);
         if (argc == 5 && std::strcmp(argv[1], "cells") == 0) return assign(false, argv[2], argv[3], argv[4]);
         if (argc == 6 && std::strcmp(argv[1], "files") == 0) return files(argv[2], argv[3], argv[4], argv[5]);
         std::cerr << "usage: taxa_test labels <taxonomy.tsv> <tree.bin> <out.bin> | records|cells <tau_q> <in.bin> <out.bin> |\n"
+                     "       taxa_test groups <taxonomy.tsv> <tree.bin> <depth> <out.bin> |\n"
                      "       taxa_test files <tau_q> <in.bin> <taxonomy.tsv> <prefix>\n";
         return 2;
     } catch (const std::exception& e) {

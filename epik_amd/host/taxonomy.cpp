@@ -179,6 +179,22 @@ int label_branches(const taxonomy& taxa, const uint32_t* parent, const std::vect
     return EPIK_AMD_OK;
 }
 
+void groups_at_rank(const taxonomy& taxa, const std::vector<uint32_t>& label, uint32_t depth, std::vector<uint32_t>& group,
+                    std::vector<uint32_t>& group_taxa)
+{
+    const uint32_t T = taxa.num_taxa();
+    std::vector<uint32_t> deep(T, 0), at_depth(T, EPIK_AMD_WINDOW_NO_GROUP);  // at_depth[t]: the GROUP of t's ancestor there
+    for (uint32_t t = T - 1; t-- > 0;) deep[t] = deep[taxa.parent[t]] + 1;
+    group_taxa.clear();
+    for (uint32_t t = 0; t < T; ++t)
+        if (depth >= 1 && deep[t] == depth) at_depth[t] = (uint32_t)group_taxa.size(), group_taxa.push_back(t);
+    for (uint32_t t = T - 1; t-- > 0;)  // (a parent has the larger id: it is done before its children)
+        if (deep[t] > depth) at_depth[t] = at_depth[taxa.parent[t]];
+    group.assign(label.size(), EPIK_AMD_WINDOW_NO_GROUP);
+    for (size_t b = 0; b < label.size(); ++b)
+        if (label[b] < T && depth >= 1 && deep[label[b]] >= depth) group[b] = at_depth[label[b]];
+}
+
 void taxa_assign(const uint32_t* taxon_parent, uint32_t num_taxa, const uint32_t* label,
                  uint32_t num_branches, uint32_t keep, const epik_amd_placement* rows, const uint32_t* n_rows,
                  const uint32_t* kmer_counts, const uint32_t* weights, const uint32_t* samples, uint64_t n, uint32_t tau_q,

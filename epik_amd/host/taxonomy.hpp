@@ -40,6 +40,12 @@ int taxonomy_first(const uint32_t* parent, uint32_t n, const char* what, std::ve
 int label_branches(const taxonomy& taxa, const uint32_t* parent, const std::vector<std::string>& names, uint32_t n,
                    std::vector<uint32_t>& label, std::string& err);
 
+/// The groups painting by windows calls (include/epik_amd.h), cut at `depth` >= 1 elements of the taxopath: group[b] is
+/// the depth-`depth` ancestor of label[b] when that label is at least so deep, else EPIK_AMD_WINDOW_NO_GROUP; group ids
+/// number the taxa of that depth in ascending taxon id, group_taxa[g] the taxon of group g.
+void groups_at_rank(const taxonomy& taxa, const std::vector<uint32_t>& label, uint32_t depth, std::vector<uint32_t>& group,
+                    std::vector<uint32_t>& group_taxa);
+
 /// The cells of `num_samples` samples over `num_taxa` taxa, and the rule that fills them
 struct taxa_cells {
     taxa_cells() = default;

@@ -340,6 +340,125 @@ class Placer:
                                     self._strand_mode(mode), d_workspace, workspace_bytes, d_rows, d_n_rows,
                                     d_kmer_counts, d_strand, stream)
 
+    # -- long sequences painted by windows (epik_amd/windows.py) ---------------------------------
+    def window_workspace_bytes(self, n: int, num_windows: int, window_bytes: int, mode="forward") -> int:
+        """Device workspace `place_windows_device` needs for n reads of num_windows windows and window_bytes window
+        characters in total (`epik_amd_placer_window_workspace_bytes`)."""
+        out = ctypes.c_uint64(0)
+        capi.check(self._lib.epik_amd_placer_window_workspace_bytes(self._handle, int(n), int(num_windows), int(window_bytes),
+                                                                    self._strand_mode(mode), ctypes.byref(out)))
+        return int(out.value)
+
+    def place_windows(self, seqs: np.ndarray, seq_offsets: np.ndarray, window: int, step: int, mode="forward"):
+        """Every window of every read placed as a read of its own, on the strand(s) `mode` asks for -- with "both" each
+        window picks its strand (`epik_amd_placer_place_windows`).  Returns (rows [V, keep], n_rows [V], kmer_counts
+        [V, keep], strand [V] uint8, win_offsets [n + 1] uint64): read i owns the windows win_offsets[i] ..
+        win_offsets[i + 1] - 1, V = win_offsets[n]."""
+        from . import windows
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+        n = int(seq_offsets.shape[0] - 1)
+        try:
+            total = int(windows.win_offsets(np.diff(seq_offsets.astype(np.int64)), int(window), int(step))[-1])
+        except ValueError:
+            total = 0   # (the library refuses such a window or step, in its own words, before it looks at a buffer)
+        rows = np.zeros((total, self.keep_at_most), dtype=capi.PLACEMENT)
+        n_rows = np.zeros(total, dtype=np.uint32)
+        counts = np.zeros((total, self.keep_at_most), dtype=np.uint32)
+        strand = np.zeros(total, dtype=np.uint8)
+        win_offs = np.zeros(n + 1, dtype=np.uint64)
+        capi.check(self._lib.epik_amd_placer_place_windows(
+            self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n, int(window), int(step), self._strand_mode(mode),
+            rows.ctypes.data, n_rows.ctypes.data, counts.ctypes.data, strand.ctypes.data, win_offs.ctypes.data))
+        return rows, n_rows, counts, strand, win_offs
+
+    def place_and_paint_windows(self, seqs: np.ndarray, seq_offsets: np.ndarray, window: int, step: int, group, tau_q: int,
+                                mode="forward", rows_out: bool = True):
+        """`place_windows` with every chunk's windows painted on the device from the rows the placement left there
+        (`epik_amd_placer_paint_windows`): `group` uint32 [num_branches].  `rows_out=False`: rows, row counts and k-mer
+        counts stay on the device (None in the result).  Returns (rows, n_rows, kmer_counts, strand, win_offsets,
+        records, segments, n_segments)."""
+        from . import windows
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+        group = np.ascontiguousarray(group, dtype=np.uint32)
+        if group.shape != (self.num_branches,):
+            raise ValueError(f"group must hold one value per branch ({self.num_branches}), not {group.shape}")
+        n = int(seq_offsets.shape[0] - 1)
+        try:
+            total = int(windows.win_offsets(np.diff(seq_offsets.astype(np.int64)), int(window), int(step))[-1])
+        except ValueError:
+            total = 0
+        rows = np.zeros((total, self.keep_at_most), dtype=capi.PLACEMENT) if rows_out else None
+        n_rows = np.zeros(total, dtype=np.uint32) if rows_out else None
+        counts = np.zeros((total, self.keep_at_most), dtype=np.uint32) if rows_out else None
+        strand, win_offs = np.zeros(total, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64)
+        records, segments = np.zeros(total, dtype=capi.WINDOW_RECORD), np.zeros(total, dtype=capi.WINDOW_SEGMENT)
+        n_segments = np.zeros(n, dtype=np.uint32)
+        ptr = (lambda a: None if a is None else a.ctypes.data)
+        capi.check(self._lib.epik_amd_placer_paint_windows(
+            self._handle, seqs.ctypes.data, seq_offsets.ctypes.data, n, int(window), int(step), self._strand_mode(mode),
+            group.ctypes.data, int(tau_q), ptr(rows), ptr(n_rows), ptr(counts), strand.ctypes.data, win_offs.ctypes.data,
+            records.ctypes.data, segments.ctypes.data, n_segments.ctypes.data))
+        return rows, n_rows, counts, strand, win_offs, records, segments, n_segments
+
+    def place_windows_device(self, d_seqs: int, d_seq_offsets: int, n: int, window: int, step: int, mode, num_windows: int,
+                             window_bytes: int, d_workspace: int, workspace_bytes: int, d_rows: int, d_n_rows: int,
+                             d_kmer_counts: int = 0, d_strand: int = 0, d_win_offsets: int = 0, stream: int = 0) -> None:
+        """`place_windows` on device buffers, asynchronous on `stream`; the caller's totals (epik_amd/windows.py), count
+        width (`choose_counts` with min(longest read, window)) and workspace of `window_workspace_bytes`
+        (`epik_amd_placer_place_windows_device`)."""
+        capi.check(self._lib.epik_amd_placer_place_windows_device(
+            self._handle, d_seqs, d_seq_offsets, int(n), int(window), int(step), self._strand_mode(mode), int(num_windows),
+            int(window_bytes), d_workspace or None, int(workspace_bytes), d_rows, d_n_rows, d_kmer_counts or None,
+            d_strand or None, d_win_offsets or None, stream or None))
+
+    def paint_windows_device(self, d_rows: int, d_n_rows: int, d_kmer_counts: int, d_win_offsets: int, n: int,
+                             num_windows: int, d_group: int, tau_q: int, d_records: int = 0, d_segments: int = 0,
+                             d_n_segments: int = 0, stream: int = 0, keep: int = None, num_branches: int = None) -> None:
+        """The window records, segments and segment counts of the windows whose rows a placement left in device memory,
+        asynchronous on `stream` (`epik_amd_windows_paint_device`); `d_group`: uint32 [num_branches].  `keep` and
+        `num_branches` default to the placer's (forged rows may have others)."""
+        capi.check(self._lib.epik_amd_windows_paint_device(
+            self.device, d_rows, d_n_rows, d_kmer_counts, d_win_offsets, int(n), int(num_windows),
+            self.keep_at_most if keep is None else int(keep), d_group, self.num_branches if num_branches is None else int(num_branches),
+            int(tau_q), d_records or None, d_segments or None, d_n_segments or None, stream or None))
+
+    def paint_windows(self, rows: np.ndarray, n_rows: np.ndarray, kmer_counts: np.ndarray, win_offsets: np.ndarray, group,
+                      tau_q: int):
+        """`paint_windows_device` for rows that are in host memory (`place_windows`'): copied to the placer's device
+        (through torch), painted there and copied back.  Returns (records capi.WINDOW_RECORD [V], segments
+        capi.WINDOW_SEGMENT [V] -- read i's at win_offsets[i] + s, the slots beyond n_segments[i] zero --, n_segments [n])."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        rows = np.ascontiguousarray(rows, dtype=capi.PLACEMENT)
+        total, keep = rows.shape
+        win_offsets = np.ascontiguousarray(win_offsets, dtype=np.uint64)
+        group = np.ascontiguousarray(group, dtype=np.uint32)
+        n = len(win_offsets) - 1
+        if int(win_offsets[-1]) > total or len(n_rows) != total:
+            raise ValueError(f"win_offsets name {int(win_offsets[-1])} windows, the rows hold {total}")
+        records, segments = np.zeros(total, dtype=capi.WINDOW_RECORD), np.zeros(total, dtype=capi.WINDOW_SEGMENT)
+        n_segments = np.zeros(n, dtype=np.uint32)
+        if n == 0 or total == 0:
+            return records, segments, n_segments
+        up = (lambda a, view: torch.from_numpy(np.ascontiguousarray(a).view(view).reshape(-1)).to(dev))
+        d_rows, d_n = up(rows, np.float64), up(np.ascontiguousarray(n_rows, dtype=np.uint32), np.int32)
+        d_counts = up(np.ascontiguousarray(kmer_counts, dtype=np.uint32), np.int32)
+        d_wo, d_group = up(win_offsets, np.int64), up(group, np.int32)
+        d_rec = torch.zeros(total * 4, dtype=torch.int32, device=dev)
+        d_seg = torch.zeros(total * 4, dtype=torch.int64, device=dev)
+        d_ns = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.paint_windows_device(d_rows.data_ptr(), d_n.data_ptr(), d_counts.data_ptr(), d_wo.data_ptr(), n, int(win_offsets[-1]),
+                                  d_group.data_ptr(), tau_q, d_rec.data_ptr(), d_seg.data_ptr(), d_ns.data_ptr(), keep=keep,
+                                  num_branches=len(group))
+        torch.cuda.synchronize(dev)
+        records[:] = d_rec.cpu().numpy().view(capi.WINDOW_RECORD)
+        segments[:] = d_seg.cpu().numpy().view(capi.WINDOW_SEGMENT)
+        n_segments[:] = d_ns.cpu().numpy().view(np.uint32)
+        return records, segments, n_segments
+
     # -- paired-end reads, one placement per fragment ---------------------------------------------
     @staticmethod
     def _mates_mode(strand, orientation) -> int:

@@ -156,6 +156,30 @@ def label_branches(taxa: Taxonomy, tree_parent, names) -> np.ndarray:
     return np.array(label, dtype=np.uint32)
 
 
+def groups_at_rank(taxa: Taxonomy, label, depth: int):
+    """The groups painting by windows calls (epik_amd/windows.py), cut at `depth` >= 1 elements of the taxopath: the
+    group of a branch is the depth-`depth` ancestor of its label when the label is at least that deep, else
+    capi.WINDOW_NO_GROUP; group ids number the taxa of that depth in ascending taxon id.  Returns (group uint32 [N],
+    the taxon of every group)."""
+    depth = int(depth)
+    if depth < 1:
+        raise ValueError(f"the window rank must be at least 1, not {depth}")
+    T = taxa.num_taxa
+    deep = np.zeros(T, np.int64)
+    for t in range(T - 2, -1, -1):
+        deep[t] = deep[taxa.parent[t]] + 1
+    anc = np.arange(T)                    # the ancestor of t at `depth`, for the taxa at least that deep
+    for t in range(T - 2, -1, -1):
+        if deep[t] > depth:
+            anc[t] = anc[taxa.parent[t]]
+    group_taxa = np.flatnonzero(deep == depth)
+    id_of = np.full(T, capi.WINDOW_NO_GROUP, np.int64)
+    id_of[group_taxa] = np.arange(len(group_taxa))
+    label = np.asarray(label).astype(np.int64)
+    group = np.where(deep[label] >= depth, id_of[anc[label]], capi.WINDOW_NO_GROUP)
+    return group.astype(np.uint32), [int(t) for t in group_taxa]
+
+
 def taxonomy_first(parent) -> np.ndarray:
     """first[] of parent[] (-1 or capi.TREE_NO_PARENT for the root), by subtree sizes."""
     parent = np.asarray(parent).astype(np.int64)

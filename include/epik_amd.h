@@ -1843,6 +1843,132 @@ int epik_amd_placer_taxa_mates(epik_amd_placer *p, const char *seqs, const uint6
                                epik_amd_taxon_record *records, const uint32_t *weights, const uint32_t *samples,
                                epik_amd_profile *profile, epik_amd_cohort *cohort);
 
+/*
+ * Long sequences painted by windows.  No reference counterpart (SHERPAS, a sibling of the reference, does it with
+ * phylo-k-mers on the CPU): a query longer than one evolutionary history -- a recombinant genome, a chimeric amplicon,
+ * a contig -- is cut into windows, every window is placed by itself, called for the group of branches that holds its
+ * mass, and the runs of windows that agree are reported with the places where the call changes.
+ *
+ * The windows of a read of L characters, window W and step S, k <= W < 2^31, 1 <= S <= W (epik_amd_window_span):
+ *   L <= W   one window [0, L) -- for L = 0 too: such a window comes back with n_rows 0 like any read shorter than k;
+ *   L >  W   nw = 1 + ceil((L - W) / S) windows; window w < nw - 1 is [w S, w S + W), the last one [L - W, L): the
+ *            tail is always covered.
+ *   win_offsets[n + 1] is the exclusive sum of nw over the batch: read i owns the windows win_offsets[i] ..
+ *   win_offsets[i + 1] - 1 of every per-window array.  A read of more than EPIK_AMD_WINDOW_MAX_PER_READ windows is
+ *   EPIK_AMD_ERR_INVALID in the host entry; to the device entry the caller answers for it.
+ *
+ * Placement.  Every window is a read of its own to the placement: rows [num_windows][keep], n_rows [num_windows],
+ * k-mer counts [num_windows][keep] and a strand byte [num_windows] are those place_strands gives for the windows' bytes
+ * with the same `mode`; with BOTH every window picks its own strand by that rule.  Amino-acid handles take FORWARD only
+ * (the strand placement's own check refuses the rest); whole databases only.
+ *   place_windows_device  asynchronous on `stream`, never allocates, count width as the caller chose it (the longest
+ *       window is min(longest read, W)).  num_windows and window_bytes are the batch's totals as epik_amd_window_span
+ *       gives them (window_bytes: the sum of the windows' lengths); the output buffers hold num_windows items and
+ *       d_workspace at least window_workspace_bytes(n, num_windows, window_bytes, mode).  The kernels count and cut by
+ *       themselves and clamp every write to those totals: totals that do not fit the batch give wrong windows, never a
+ *       write outside.  d_kmer_counts, d_strand and d_win_offsets (uint64 [n + 1]) may be NULL.
+ *   place_windows         synchronous, host buffers sized by the caller from epik_amd_window_span.  Chunks are cut on
+ *       READ boundaries by a budget of windows and window bytes (EPIK_AMD_WINDOW_CHUNK_WINDOWS overrides the former:
+ *       tests).  A read is never split across chunks in this version: one whose windows do not fit the device fails
+ *       with the allocation's error (EPIK_AMD_ERR_HIP).  The count width is chosen for min(longest read, W): no window
+ *       comes back EPIK_AMD_ROWS_COUNTS_TOO_NARROW.  kmer_counts, strand and win_offsets may be NULL.
+ *
+ * Painting.  group[b], b < N, is the group id of branch b or EPIK_AMD_WINDOW_NO_GROUP for a branch above the groups
+ * (ids at or above EPIK_AMD_WINDOW_AMBIGUOUS are refused by the host entry).  q(), keep and nr = min(n_rows, keep) are
+ * the taxa rule's; the record of window v, the tests in this order:
+ *     n_rows[v] == EPIK_AMD_ROWS_COUNTS_TOO_NARROW    call = EPIK_AMD_WINDOW_TOO_NARROW
+ *     n_rows[v] == 0                                  call = EPIK_AMD_WINDOW_TOO_SHORT
+ *     kmer_counts[v * keep] == 0                      call = EPIK_AMD_WINDOW_NO_HIT
+ *     a row j < nr with branch >= N                   call = EPIK_AMD_WINDOW_BAD_ROW
+ *     S = the sum over j < nr of q(lwr_j) is 0        call = EPIK_AMD_WINDOW_NO_MASS
+ *   otherwise mass(g) = the sum of q(lwr_j) over j < nr with group[b_j] == g (NO_GROUP is in no mass: those rows count
+ *   in S only) and call = the group g with mass(g) * 2^30 >= tau_q * S, compared as exact integers.  tau_q lies in
+ *   (2^29, 2^30], anything else is EPIK_AMD_ERR_INVALID: at most one group then qualifies.  None does:
+ *   call = EPIK_AMD_WINDOW_AMBIGUOUS.  A record with a status call has its other fields 0; else call_mass_q =
+ *   mass(call) and total_q = S, both saturating at 2^32 - 1, and first_group = group[b_0].
+ *   A segment of a read is a maximal run of consecutive windows with equal call; status calls count as values.  Its
+ *   record: the call, its first window (counted inside the read), its number of windows, and the sums over its windows
+ *   of the unsaturated mass(call) and S (both 0 for a status call).  Read i has n_segments[i] of them, written to the
+ *   slots win_offsets[i] + s, s < n_segments[i]; slots beyond are left alone by the device entry and zeroed by the
+ *   host entry.  Records and segments are a pure function of the rows: the same bits whatever the grid or the stream.
+ *   windows_paint_device  asynchronous on `stream` of `device`, allocates nothing; all pointers are device memory,
+ *       num_windows = win_offsets[n] as the caller knows it (windows beyond it are not looked at).
+ *   windows_paint_host    the same rule with no device.
+ *   paint_windows         place_windows with every chunk's windows painted on the device from the rows the placement
+ *       left there: group[num_branches of the placer] (HOST) is uploaded once; records [num_windows], segments
+ *       [num_windows] and n_segments [n] are host arrays.  rows, n_rows, kmer_counts, strand, win_offsets, records,
+ *       segments and n_segments may be NULL, each by itself: that part stays on the device.  Synchronous.
+ */
+#define EPIK_AMD_WINDOW_MAX_PER_READ (1u << 24)
+#define EPIK_AMD_WINDOW_NO_GROUP 0xffffffffu
+#define EPIK_AMD_WINDOW_TOO_NARROW 0xffffffffu
+#define EPIK_AMD_WINDOW_TOO_SHORT 0xfffffffeu
+#define EPIK_AMD_WINDOW_NO_HIT 0xfffffffdu
+#define EPIK_AMD_WINDOW_BAD_ROW 0xfffffffcu
+#define EPIK_AMD_WINDOW_NO_MASS 0xfffffffbu
+#define EPIK_AMD_WINDOW_AMBIGUOUS 0xfffffffau
+typedef struct {
+    uint32_t call;
+    uint32_t call_mass_q;
+    uint32_t first_group;
+    uint32_t total_q;
+} epik_amd_window_record; /* 16 bytes */
+typedef struct {
+    uint32_t call;
+    uint32_t first_window;
+    uint32_t num_windows;
+    uint32_t reserved; /* 0 */
+    uint64_t call_mass;
+    uint64_t total;
+} epik_amd_window_segment; /* 32 bytes */
+
+/* The number of windows of a read of `len` characters (0: window or step out of range); for w below it *begin and
+ * *end (either may be NULL) get window w, 0-based half-open in the read.  Defined here, so that a caller sizes its buffers
+ * without a call into the library and a kernel can use it; libepik_amd exports it as well (a binding without a C compiler). */
+#if defined(__HIP__)
+#define EPIK_AMD_INLINE inline __attribute__((host)) __attribute__((device))
+#elif defined(__cplusplus)
+#define EPIK_AMD_INLINE inline
+#else
+#define EPIK_AMD_INLINE static inline
+#endif
+EPIK_AMD_INLINE uint64_t epik_amd_window_span(uint64_t len, uint32_t window, uint32_t step, uint64_t w,
+                                              uint64_t *begin, uint64_t *end)
+{
+    if (window == 0 || window >= 0x80000000u || step == 0 || step > window) return 0;
+    const uint64_t nw = len <= window ? 1 : 1 + (len - window + step - 1) / step;
+    if (w < nw) {
+        const uint64_t b = len <= window ? 0 : w + 1 < nw ? w * step : len - window;
+        if (begin) *begin = b;
+        if (end) *end = len <= window ? len : b + window;
+    }
+    return nw;
+}
+
+int epik_amd_placer_window_workspace_bytes(const epik_amd_placer *p, uint64_t n, uint64_t num_windows,
+                                           uint64_t window_bytes, uint32_t mode, uint64_t *bytes);
+int epik_amd_placer_place_windows_device(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offsets, uint64_t n,
+                                         uint32_t window, uint32_t step, uint32_t mode, uint64_t num_windows,
+                                         uint64_t window_bytes, void *d_workspace, uint64_t workspace_bytes,
+                                         void *d_rows, void *d_n_rows, void *d_kmer_counts, void *d_strand,
+                                         void *d_win_offsets, void *stream);
+int epik_amd_placer_place_windows(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                                  uint32_t window, uint32_t step, uint32_t mode, epik_amd_placement *rows,
+                                  uint32_t *n_rows, uint32_t *kmer_counts, uint8_t *strand, uint64_t *win_offsets);
+int epik_amd_placer_paint_windows(epik_amd_placer *p, const char *seqs, const uint64_t *seq_offsets, uint64_t n,
+                                  uint32_t window, uint32_t step, uint32_t mode, const uint32_t *group, uint32_t tau_q,
+                                  epik_amd_placement *rows, uint32_t *n_rows, uint32_t *kmer_counts, uint8_t *strand,
+                                  uint64_t *win_offsets, epik_amd_window_record *records,
+                                  epik_amd_window_segment *segments, uint32_t *n_segments);
+int epik_amd_windows_paint_device(int device, const void *d_rows, const void *d_n_rows, const void *d_kmer_counts,
+                                  const void *d_win_offsets, uint64_t n, uint64_t num_windows, uint32_t keep,
+                                  const void *d_group, uint32_t num_branches, uint32_t tau_q, void *d_records,
+                                  void *d_segments, void *d_n_segments, void *stream);
+int epik_amd_windows_paint_host(const epik_amd_placement *rows, const uint32_t *n_rows, const uint32_t *kmer_counts,
+                                const uint64_t *win_offsets, uint64_t n, uint32_t keep, const uint32_t *group,
+                                uint32_t num_branches, uint32_t tau_q, epik_amd_window_record *records,
+                                epik_amd_window_segment *segments, uint32_t *n_segments);
+
 /* Which kernels the last launch of this handle ran (reports; a large-tree handle falls back from the three-kernel
  * placement to the one-kernel one when the device has no room for the scratch of a launch). */
 #define EPIK_AMD_PATH_WAVE 0u            /* place_reads_kernel: one wavefront per read */
