@@ -53,6 +53,11 @@ weighted, generalized): the distance --cohort-permanova, --cohort-pcoa and --coh
 --windows W --window-groups FILE: long sequences painted by windows of W characters, every window placed by itself and called
 for a group of FILE (a taxonomy file); windows_<input>.tsv (segments) and windows_breakpoints_<input>.tsv, no jplace;
 --window-step S (default max(1, W / 4)), --window-mass (default 0.8), --window-rank D (default 1), --windows-per-window.
+
+Two more commands, not in the reference's launcher (its databases come from another program, IPK), make the database `place`
+starts from: `extend -t TREE -r ALIGNMENT -o DIR [--reduction R]` writes the tree and alignment with ghost nodes that an ancestral
+reconstruction is run on, and `build -t TREE --ar-probs FILE --ar-tree FILE -s nucl|amino -k K --omega W [--ghosts inner|outer|both]
+[--chunk G] -o DB` builds the database on the GPU from that run's posteriors (epik_amd/dbbuild.py, epik_amd/build.py).
 """
 from __future__ import annotations
 
@@ -580,6 +585,63 @@ place = click.argument("input_file", type=click.Path(exists=True))(_place)
 for flags, kwargs in reversed(PLACE_OPTIONS):
     place = click.option(*flags, **kwargs)(place)
 place = epik.command(name="place")(place)
+
+
+def _fail_usage(err):
+    raise click.UsageError(str(err))
+
+
+@epik.command(name="extend")
+@click.option("-t", "--tree", "tree", required=True, type=click.Path(exists=True, dir_okay=False),
+              help="The reference tree (Newick, rooted and binary).")
+@click.option("-r", "--refalign", "refalign", required=True, type=click.Path(exists=True, dir_okay=False),
+              help="The reference alignment (FASTA), a sequence per leaf of the tree.")
+@click.option("-o", "--outputdir", required=True, type=click.Path(file_okay=False),
+              help="Directory that receives extended.nwk, extended.fasta and columns.tsv.")
+@click.option("--reduction", type=float, default=None,
+              help="First remove the columns whose share of gaps is at least this [default: keep every column].")
+def extend(tree, refalign, outputdir, reduction):
+    """Adds the ghost nodes to a reference tree and alignment: what the ancestral reconstruction is run on."""
+    from epik_amd import dbbuild
+    try:
+        paths = dbbuild.extend_files(tree, refalign, outputdir, reduction)
+    except dbbuild.BuildInputError as err:
+        _fail_usage(err)
+    for path in paths.values():
+        print(path)
+
+
+@epik.command(name="build")
+@click.option("-t", "--tree", "tree", required=True, type=click.Path(dir_okay=False), help="The reference tree `extend` was given.")
+@click.option("--ar-probs", required=True, type=click.Path(dir_okay=False),
+              help="The reconstruction's posteriors: a tab-separated table with Node, Site and p_<state> columns "
+                   "(RAxML-NG --ancestral: *.ancestralProbs).")
+@click.option("--ar-tree", required=True, type=click.Path(dir_okay=False),
+              help="The extended tree as the reconstruction wrote it back, inner nodes labelled (*.ancestralTree).")
+@click.option("-s", "--states", type=click.Choice(sorted(DRIVERS, reverse=True)), default="nucl", show_default=True,
+              help="nucl for DNA, amino for proteins.")
+@click.option("-k", "--kmer-size", "kmer_size", required=True, type=int, help="k: 2 to 15 for nucl, 2 to 7 for amino.")
+@click.option("--omega", type=float, default=1.5, show_default=True, help="Score-threshold parameter: (omega / sigma)^k.")
+@click.option("--ghosts", type=click.Choice(["inner", "outer", "both"]), default="both", show_default=True,
+              help="Which ghost nodes of every branch to use: its midpoint (inner), the pendant node (outer), or both.")
+@click.option("--chunk", type=int, default=256, show_default=True, help="Ghost nodes handed to the device at a time.")
+@click.option("-o", "--output", "output", required=True, type=click.Path(dir_okay=False), help="The database to write (.ekdb).")
+def build_db(tree, ar_probs, ar_tree, states, kmer_size, omega, ghosts, chunk, output):
+    """Builds a phylo-k-mer database on the GPU from the posteriors of an extended tree's ghost nodes."""
+    from epik_amd import dbbuild
+    try:
+        dbbuild.check_build_options(states, kmer_size, omega, chunk)  # (before anything is opened)
+    except dbbuild.BuildInputError as err:
+        _fail_usage(err)
+    for flag, path in (("-t", tree), ("--ar-probs", ar_probs), ("--ar-tree", ar_tree)):
+        if not os.path.isfile(path):
+            raise click.UsageError(f"{flag}: the file '{path}' does not exist")
+    try:
+        info = dbbuild.build_from_files(tree, ar_probs, ar_tree, states, kmer_size, omega, output, ghosts=ghosts, chunk=chunk)
+    except dbbuild.BuildInputError as err:
+        _fail_usage(err)
+    print(f"{output}: {info['num_keys']} k-mers, {info['num_entries']} phylo-k-mers from {info['ghost_nodes']} ghost nodes "
+          f"of {info['num_branches'] - 1} branches")
 
 
 if __name__ == "__main__":

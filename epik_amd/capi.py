@@ -302,6 +302,13 @@ EXPORTS = (
     "epik_amd_placer_paint_windows",
     "epik_amd_windows_paint_device",
     "epik_amd_windows_paint_host",
+    "epik_amd_builder_create",
+    "epik_amd_builder_add",
+    "epik_amd_builder_add_device",
+    "epik_amd_builder_finish",
+    "epik_amd_builder_copy",
+    "epik_amd_builder_destroy",
+    "epik_amd_build_host",
 )
 
 
@@ -798,6 +805,21 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_windows_paint_device.argtypes = [i32, vp, vp, vp, vp, u64, u64, u32, vp, u32, u32, vp, vp, vp, vp]
     lib.epik_amd_windows_paint_host.restype = i32
     lib.epik_amd_windows_paint_host.argtypes = [vp, vp, vp, vp, u64, u32, vp, u32, u32, vp, vp, vp]
+    # (the database builder)
+    lib.epik_amd_builder_create.restype = i32
+    lib.epik_amd_builder_create.argtypes = [i32, u32, u32, u32, ctypes.c_float, u64, ctypes.POINTER(vp)]
+    lib.epik_amd_builder_add.restype = i32
+    lib.epik_amd_builder_add.argtypes = [vp, vp, vp, u64, u64]
+    lib.epik_amd_builder_add_device.restype = i32
+    lib.epik_amd_builder_add_device.argtypes = [vp, vp, vp, u64, u64]
+    lib.epik_amd_builder_finish.restype = i32
+    lib.epik_amd_builder_finish.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.epik_amd_builder_copy.restype = i32
+    lib.epik_amd_builder_copy.argtypes = [vp, vp, vp, vp]
+    lib.epik_amd_builder_destroy.restype = None
+    lib.epik_amd_builder_destroy.argtypes = [vp]
+    lib.epik_amd_build_host.restype = i32
+    lib.epik_amd_build_host.argtypes = [u32, u32, u32, ctypes.c_float, vp, vp, u64, u64, u32, ctypes.POINTER(vp)]
     _lib = lib
     return lib
 

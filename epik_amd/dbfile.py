@@ -53,9 +53,10 @@ def write_db(path: str, db: SynthDB, newick: str) -> None:
         fh.write(tree)
         offs = db.offsets.astype(np.int64)
         crc = 0
+        codes = getattr(db, "keys", None)  # the sparse form: list i belongs to code keys[i] (ascending, as the lists are)
         for key in order:
             b, e = int(offs[key]), int(offs[key + 1])
-            record = struct.pack("<II", int(key), e - b) + db.values[b:e].tobytes()
+            record = struct.pack("<II", int(key) if codes is None else int(codes[key]), e - b) + db.values[b:e].tobytes()
             crc = zlib.crc32(record, crc)
             fh.write(record)
         fh.write(END_MAGIC + struct.pack("<QQII", len(order), db.num_entries, crc & 0xFFFFFFFF, 0))

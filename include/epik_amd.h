@@ -1969,6 +1969,72 @@ int epik_amd_windows_paint_host(const epik_amd_placement *rows, const uint32_t *
                                 uint32_t num_branches, uint32_t tau_q, epik_amd_window_record *records,
                                 epik_amd_window_segment *segments, uint32_t *n_segments);
 
+/*
+ * Building a phylo-k-mer database from ancestral posteriors.  The reference's world does this in a second product
+ * (IPK, after RAPPAS: PAPERS.md) on CPU threads; the rule below is this project's own, worded so that the device, the
+ * host mirror and a numpy restatement give the same bytes.
+ *
+ * Inputs.  sigma is 4 or 20; k lies in [2, 15] for sigma = 4 and in [2, 7] for sigma = 20 (keys stay inside uint32);
+ * num_branches is N >= 1; log_thr is a float32, at most 0 and no NaN (the caller passes log10f((omega / sigma)^k) as
+ * the placement computes it).  Ghost nodes arrive in chunks: logp float32 [G][L][sigma], log10 of the posterior of
+ * every state at every site (every value at most 0, -inf for p = 0; NaN and values above 0 are refused), and branch_of
+ * uint32 [G], every value below N, repeats and any order allowed.  L >= k is the same for every chunk of one build.
+ * The logarithm is the caller's (log10f on the host); the device never evaluates one.
+ *
+ * The rule.  For ghost node g, window start w in [0, L - k] and letters c_0 .. c_{k-1}:
+ *     s = ((((+0.0f + logp[g][w][c_0]) + logp[g][w+1][c_1]) + ...) + logp[g][w+k-1][c_{k-1}])
+ * in float32, left to right, every addition rounded to nearest (no contraction).  The k-mer survives iff
+ * s >= log_thr (the loader's comparison), and its key is the sum of c_j sigma^(k-1-j): first letter most significant.
+ * The value of (key, b) is the maximum of s over every surviving (g, w) with branch_of[g] = b.
+ *   Zeros.  The chain starts from +0.0f, and in round-to-nearest (+0) + (-0) = +0 and x + y of two values <= 0 is
+ *   -0 only when both are -0: a sum that starts from +0.0 never produces -0.0, even over logp values given as -0.0.
+ *   +0.0 and -0.0 therefore never both occur as a score, and "maximum" needs no rule for them.
+ *   Pruning cannot change the result.  Rounded addition is monotone in each operand, so the left-to-right sum of a
+ *   prefix completed with the best remaining letter of every position is the maximum over its completions, and a
+ *   prefix whose completed sum is below log_thr has no survivor.  The kernels and the host mirror cut a prefix of
+ *   depth d when fl(s_d + R_d) < log_thr (1 + 16 k 2^-24) (rounded away from 0), R_d the float32 right-to-left sum
+ *   of the best remaining letters: both fl(s_d + R_d) and the completed sum are sums of at most k + 1 values of one
+ *   sign and lie within (1 +- 2^-24)^(k+1) of the exact sum, so the cut is never taken for a prefix with a survivor;
+ *   what it lets through is tested exactly at depth k.
+ *   Chunking cannot change the result either: maximum is associative and commutative and the survivors of a ghost
+ *   node depend on nothing but that node, so any split of the ghost nodes into chunks, and any split of a chunk
+ *   inside the library, gives the same bytes.
+ *
+ * The result has the sparse CSR form of the placer's descriptor: keys uint32 [K] ascending, one per key with at least
+ * one value; offsets uint64 [K + 1]; values [E] {branch, score}, branch ascending within a key.  K = 0 is valid.
+ *
+ *   builder_create   a builder on `device`; workspace_bytes is what the enumeration of one chunk may use on the
+ *       device (its per-window counts and its (key, branch, score) tuples at 40 bytes each; 0: 1 GiB).  A chunk
+ *       whose tuples do not fit is split by ghost nodes inside `add`, as often as needed; only a single ghost node
+ *       that does not fit is EPIK_AMD_ERR_INVALID (the message says how many bytes it needs; the ghost nodes of the
+ *       chunk before it have been added by then, the others have not).  Beside the workspace
+ *       the builder holds its running store (12 bytes an entry, sorted and deduplicated; twice while a chunk is
+ *       merged in) and the scratch of hipCUB's scans and sorts.
+ *   builder_add          logp and branch_of are HOST arrays; synchronous.
+ *   builder_add_device   the same with DEVICE arrays on the builder's device; synchronous as well (the counts of a
+ *       chunk size its tuples).
+ *       Both refuse, with EPIK_AMD_ERR_INVALID and nothing added to the store: a NaN or a value above 0 (the message
+ *       names the first one's ghost node, site and state), branch_of[g] >= N (names g), L < k, L other than the
+ *       first chunk's.  G = 0 is a valid no-op.
+ *   builder_finish   the sizes of the result; *num_splits (may be NULL) gets how many times `add` has split a chunk
+ *       so far.  More chunks may be added afterwards; finish then has to be called again before copy.
+ *   builder_copy     the result into HOST arrays of those sizes.
+ *   build_host       the same rule in plain C++ on `num_threads` threads (0: one), no device: pruned depth-first
+ *       enumeration and a std::sort merge.  *result is a finished builder that finish, copy and destroy take.
+ */
+typedef struct epik_amd_builder epik_amd_builder;
+int epik_amd_builder_create(int device, uint32_t sigma, uint32_t k, uint32_t num_branches, float log_thr,
+                            uint64_t workspace_bytes, epik_amd_builder **builder);
+int epik_amd_builder_add(epik_amd_builder *builder, const float *logp, const uint32_t *branch_of, uint64_t G, uint64_t L);
+int epik_amd_builder_add_device(epik_amd_builder *builder, const void *d_logp, const void *d_branch_of, uint64_t G,
+                                uint64_t L);
+int epik_amd_builder_finish(epik_amd_builder *builder, uint64_t *num_keys, uint64_t *num_entries, uint64_t *num_splits);
+int epik_amd_builder_copy(epik_amd_builder *builder, uint32_t *keys, uint64_t *offsets, epik_amd_pkdb_value *values);
+void epik_amd_builder_destroy(epik_amd_builder *builder);
+int epik_amd_build_host(uint32_t sigma, uint32_t k, uint32_t num_branches, float log_thr, const float *logp,
+                        const uint32_t *branch_of, uint64_t G, uint64_t L, uint32_t num_threads,
+                        epik_amd_builder **result);
+
 /* Which kernels the last launch of this handle ran (reports; a large-tree handle falls back from the three-kernel
  * placement to the one-kernel one when the device has no room for the scratch of a launch). */
 #define EPIK_AMD_PATH_WAVE 0u            /* place_reads_kernel: one wavefront per read */
