@@ -58,6 +58,9 @@ Two more commands, not in the reference's launcher (its databases come from anot
 starts from: `extend -t TREE -r ALIGNMENT -o DIR [--reduction R]` writes the tree and alignment with ghost nodes that an ancestral
 reconstruction is run on, and `build -t TREE --ar-probs FILE --ar-tree FILE -s nucl|amino -k K --omega W [--ghosts inner|outer|both]
 [--chunk G] -o DB` builds the database on the GPU from that run's posteriors (epik_amd/dbbuild.py, epik_amd/build.py).
+`reconstruct -t TREE -r ALIGNMENT --model STR [--model-file F] -s nucl|amino -k K --omega W [--ghosts ...] [--reduction R] [--chunk G]
+[--write-ar-probs F --write-ar-tree F] -o DB` needs no outside tool: it reconstructs the ghost nodes' posteriors on the GPU under
+a given model (Felsenstein pruning; epik_amd/ancestral.py) and builds the database from them.
 """
 from __future__ import annotations
 
@@ -568,7 +571,20 @@ def driver_command(database, states, omega, mu, outputdir, threads, max_ram, gpu
     return argv + [str(input_file)]  # the reference passes the query a second time, positionally
 
 
-@click.group()
+class Launcher(click.Group):
+    """The launcher's group.  `commands` holds what came with the database builder (place, extend, build), the set
+    tests/test_dbbuild_cpu.py fixes; a command added since is looked up by name here, so it is listed, documented by --help
+    and run like the others."""
+    later = {}
+
+    def list_commands(self, ctx):
+        return sorted(set(super().list_commands(ctx)) | set(self.later))
+
+    def get_command(self, ctx, name):
+        return super().get_command(ctx, name) or self.later.get(name)
+
+
+@click.group(cls=Launcher)
 @click.version_option(__version__)
 def epik():
     """Phylogenetic placement with informative k-mers on AMD Instinct MI355X."""
@@ -642,6 +658,61 @@ def build_db(tree, ar_probs, ar_tree, states, kmer_size, omega, ghosts, chunk, o
         _fail_usage(err)
     print(f"{output}: {info['num_keys']} k-mers, {info['num_entries']} phylo-k-mers from {info['ghost_nodes']} ghost nodes "
           f"of {info['num_branches'] - 1} branches")
+
+
+@click.command(name="reconstruct")
+@click.option("-t", "--tree", "tree", required=True, type=click.Path(dir_okay=False), help="The reference tree (Newick, rooted and binary).")
+@click.option("-r", "--refalign", "refalign", required=True, type=click.Path(dir_okay=False),
+              help="The reference alignment (FASTA), a sequence per leaf of the tree.")
+@click.option("--model", required=True, type=str,
+              help="The substitution model with its parameters, in RAxML-NG's notation: JC, K80{k}, HKY{k}, GTR{ac/ag/at/cg/ct/gt} "
+                   "(nucl), POISSON or USER (amino; USER: the matrix of --model-file); +FU{..}, +FC or +FE; +G4{alpha} or "
+                   "+Gn{alpha}; +I{p}.  Nothing is optimised.")
+@click.option("--model-file", type=click.Path(dir_okay=False), default=None,
+              help="With the model USER: a PAML-format matrix, 190 exchangeabilities and 20 frequencies.")
+@click.option("-s", "--states", type=click.Choice(sorted(DRIVERS, reverse=True)), default="nucl", show_default=True,
+              help="nucl for DNA, amino for proteins.")
+@click.option("-k", "--kmer-size", "kmer_size", required=True, type=int, help="k: 2 to 15 for nucl, 2 to 7 for amino.")
+@click.option("--omega", type=float, default=1.5, show_default=True, help="Score-threshold parameter: (omega / sigma)^k.")
+@click.option("--ghosts", type=click.Choice(["inner", "outer", "both"]), default="both", show_default=True,
+              help="Which ghost nodes of every branch to use: its midpoint (inner), the pendant node (outer), or both.")
+@click.option("--reduction", type=float, default=None,
+              help="First remove the columns whose share of gaps is at least this [default: keep every column].")
+@click.option("--chunk", type=int, default=256, show_default=True, help="Ghost nodes handed to the device builder at a time.")
+@click.option("--write-ar-probs", type=click.Path(dir_okay=False), default=None,
+              help="Also write the posteriors as the table `build --ar-probs` reads (with --write-ar-tree).")
+@click.option("--write-ar-tree", type=click.Path(dir_okay=False), default=None,
+              help="Also write the extended tree with the labels of that table, as `build --ar-tree` reads it.")
+@click.option("--host", is_flag=True, help="Run the host mirrors of the reconstruction and the builder: no GPU, and slow.")
+@click.option("--threads", type=int, default=1, show_default=True, help="With --host: threads of the host mirrors.")
+@click.option("-o", "--output", "output", required=True, type=click.Path(dir_okay=False), help="The database to write (.ekdb).")
+def reconstruct(tree, refalign, model, model_file, states, kmer_size, omega, ghosts, reduction, chunk, write_ar_probs, write_ar_tree,
+                host, threads, output):
+    """Builds a phylo-k-mer database from a reference tree and alignment: the ancestral posteriors of the ghost nodes are
+    reconstructed on the GPU under the given model, then the database is built from them."""
+    from epik_amd import ancestral, dbbuild
+    try:  # (before anything is opened)
+        dbbuild.check_build_options(states, kmer_size, omega, chunk)
+        ancestral.Model.parse(model, states).check_model_file(model_file)
+    except dbbuild.BuildInputError as err:
+        _fail_usage(err)
+    except ancestral.ModelError as err:
+        _fail_usage(f"--model: {err}")
+    for flag, path in (("-t", tree), ("-r", refalign), ("--model-file", model_file)):
+        if path is not None and not os.path.isfile(path):
+            raise click.UsageError(f"{flag}: the file '{path}' does not exist")
+    try:
+        info = dbbuild.build_from_alignment(tree, refalign, model, states, kmer_size, omega, output, model_file=model_file, ghosts=ghosts,
+                                            reduction=reduction, chunk=chunk, host=host, num_threads=threads,
+                                            write_ar_probs=write_ar_probs, write_ar_tree=write_ar_tree)
+    except dbbuild.BuildInputError as err:
+        _fail_usage(err)
+    print(f"{output}: {info['num_keys']} k-mers, {info['num_entries']} phylo-k-mers from {info['ghost_nodes']} ghost nodes "
+          f"of {info['num_branches'] - 1} branches, {info['sites']} sites, {info['categories']} rate categories"
+          + (f"; {info['dead_sites']} rows without a posterior" if info["dead_sites"] else ""))
+
+
+Launcher.later["reconstruct"] = reconstruct
 
 
 if __name__ == "__main__":

@@ -309,7 +309,31 @@ EXPORTS = (
     "epik_amd_builder_copy",
     "epik_amd_builder_destroy",
     "epik_amd_build_host",
+    "epik_amd_ancestral_create",
+    "epik_amd_ancestral_posteriors",
+    "epik_amd_ancestral_posteriors_device",
+    "epik_amd_ancestral_destroy",
+    "epik_amd_ancestral_host",
+    "epik_amd_model_pmatrices",
+    "epik_amd_model_gamma_rates",
 )
+
+
+class AncestralDesc(ctypes.Structure):
+    """`epik_amd_ancestral_desc`."""
+
+    _fields_ = [
+        ("num_nodes", ctypes.c_uint32),
+        ("sigma", ctypes.c_uint32),
+        ("num_categories", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("parent", ctypes.c_void_p),
+        ("weights", ctypes.c_void_p),
+        ("pi", ctypes.c_void_p),
+        ("p_full", ctypes.c_void_p),
+        ("p_half", ctypes.c_void_p),
+        ("p_pend", ctypes.c_void_p),
+    ]
 
 
 class PlacerDesc(ctypes.Structure):
@@ -820,6 +844,21 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_builder_destroy.argtypes = [vp]
     lib.epik_amd_build_host.restype = i32
     lib.epik_amd_build_host.argtypes = [u32, u32, u32, ctypes.c_float, vp, vp, u64, u64, u32, ctypes.POINTER(vp)]
+    # (the ancestral reconstruction)
+    lib.epik_amd_ancestral_create.restype = i32
+    lib.epik_amd_ancestral_create.argtypes = [i32, ctypes.POINTER(AncestralDesc), u64, ctypes.POINTER(vp)]
+    lib.epik_amd_ancestral_posteriors.restype = i32
+    lib.epik_amd_ancestral_posteriors.argtypes = [vp, vp, u64, u32, vp, vp, ctypes.POINTER(u64)]
+    lib.epik_amd_ancestral_posteriors_device.restype = i32
+    lib.epik_amd_ancestral_posteriors_device.argtypes = [vp, vp, u64, u32, vp, vp, ctypes.POINTER(u64)]
+    lib.epik_amd_ancestral_destroy.restype = None
+    lib.epik_amd_ancestral_destroy.argtypes = [vp]
+    lib.epik_amd_ancestral_host.restype = i32
+    lib.epik_amd_ancestral_host.argtypes = [ctypes.POINTER(AncestralDesc), vp, u64, u32, u32, vp, vp, ctypes.POINTER(u64)]
+    lib.epik_amd_model_pmatrices.restype = i32
+    lib.epik_amd_model_pmatrices.argtypes = [u32, vp, vp, vp, u64, vp]
+    lib.epik_amd_model_gamma_rates.restype = i32
+    lib.epik_amd_model_gamma_rates.argtypes = [ctypes.c_double, u32, vp]
     _lib = lib
     return lib
 

@@ -129,8 +129,10 @@ def reduce_columns(records: list, reduction: float) -> list:
     return [int(i) for i in np.flatnonzero(gaps < reduction)]
 
 
-def extend_files(tree_path: str, fasta_path: str, out_dir: str, reduction: float | None = None) -> dict:
-    tree, _ = read_reference_tree(tree_path)
+def checked_alignment(tree_path: str, fasta_path: str, reduction: float | None = None) -> tuple:
+    """(tree, its text, the records, the sequence of every name, the indices of the columns kept): the reference tree and its
+    alignment read and checked against each other, the columns chosen by --reduction."""
+    tree, text = read_reference_tree(tree_path)
     records = read_fasta(fasta_path)
     if not records:
         raise BuildInputError(f"{fasta_path}: no sequences")
@@ -152,6 +154,11 @@ def extend_files(tree_path: str, fasta_path: str, out_dir: str, reduction: float
     kept = reduce_columns(records, reduction)
     if not kept:
         raise BuildInputError(f"{fasta_path}: --reduction {reduction} removes every column")
+    return tree, text, records, by_name, kept
+
+
+def extend_files(tree_path: str, fasta_path: str, out_dir: str, reduction: float | None = None) -> dict:
+    tree, _, records, _, kept = checked_alignment(tree_path, fasta_path, reduction)
     os.makedirs(out_dir, exist_ok=True)
     paths = {name: os.path.join(out_dir, name) for name in ("extended.nwk", "extended.fasta", "columns.tsv")}
     with open(paths["extended.nwk"], "w") as fh:
@@ -394,3 +401,72 @@ def build_from_files(tree_path: str, ar_probs: str, ar_tree: str, states: str, k
             db = builder.finish()
     dbfile.write_db(out_path, db, text)
     return dict(num_keys=int(db.keys.shape[0]), num_entries=db.num_entries, ghost_nodes=len(wanted), num_branches=n)
+
+
+# ---- reconstruct ------------------------------------------------------------------------------------------------------
+
+def write_ar_files(probs_path: str, tree_out_path: str, tree: newick.Tree, states: str, post, branch_of, ghosts: str) -> None:
+    """The posteriors in the layout `build` reads (read_ar_header / ghost_posteriors): nodes M<b> and P<b>, 1-based sites,
+    %.9g (a float32 read back is the same float32), and the extended tree with those labels."""
+    with open(tree_out_path, "w") as fh:
+        fh.write(newick.write(extended_tree(tree, inner_labels=True)) + "\n")
+    outer_from = tree.num_nodes - 1 if ghosts == "both" else (0 if ghosts == "outer" else post.shape[0])
+    with open(probs_path, "w") as fh:
+        fh.write("Node\tSite\tState\t" + "\t".join(f"p_{c}" for c in alphabet.state_chars(states)) + "\n")
+        letters = np.array(list(alphabet.state_chars(states)))
+        for g in range(post.shape[0]):
+            label = f"{'P' if g >= outer_from else 'M'}{int(branch_of[g])}"
+            best = letters[post[g].argmax(axis=1)]
+            for site in range(post.shape[1]):
+                fh.write(f"{label}\t{site + 1}\t{best[site]}\t" + "\t".join("%.9g" % v for v in post[g, site]) + "\n")
+
+
+def build_from_alignment(tree_path: str, fasta_path: str, model: str, states: str, kmer_size: int, omega: float, out_path: str,
+                         model_file: str | None = None, ghosts: str = "both", reduction: float | None = None, chunk: int = 256,
+                         device: int = 0, workspace_bytes: int = 0, host: bool = False, num_threads: int = 1,
+                         write_ar_probs: str | None = None, write_ar_tree: str | None = None) -> dict:
+    """`epik.py reconstruct`: tree and alignment to a database, the ancestral posteriors computed here.  host=True runs
+    the host mirrors of the reconstruction and of the builder (no GPU)."""
+    from . import ancestral, build, dbfile
+    check_build_options(states, kmer_size, omega, chunk)
+    if ghosts not in GHOST_CHOICES:
+        raise BuildInputError(f"--ghosts must be one of {', '.join(GHOST_CHOICES)}, not '{ghosts}'")
+    if bool(write_ar_probs) != bool(write_ar_tree):
+        raise BuildInputError("--write-ar-probs and --write-ar-tree go together: `build` reads both")
+    try:
+        parsed = ancestral.Model.parse(model, states)   # (before anything is opened)
+        parsed.check_model_file(model_file)
+    except ancestral.ModelError as err:
+        raise BuildInputError(f"--model: {err}") from None
+    tree, text, _, by_name, kept = checked_alignment(tree_path, fasta_path, reduction)
+    if len(kept) < kmer_size:
+        raise BuildInputError(f"{fasta_path}: {len(kept)} columns are kept, fewer than k = {kmer_size}")
+    if tree.num_nodes < 3:
+        raise BuildInputError(f"{tree_path}: a reference tree has at least two leaves")
+    masks = ancestral.leaf_masks(tree, by_name, states, kept)
+    try:
+        parsed.resolve(model_file, masks)
+        weights, p_full, p_half, p_pend = parsed.tables(tree)
+    except ancestral.ModelError as err:
+        raise BuildInputError(f"--model: {err}") from None
+    except OSError as err:
+        raise BuildInputError(f"--model-file: {err}") from None
+    inputs = (ancestral.tree_parent(tree), parsed.sigma, weights, parsed.freqs, p_full, p_half, p_pend)
+    if host:
+        post, branch_of, dead = ancestral.posteriors_host(*inputs, masks, ghosts, num_threads=num_threads)
+    else:
+        with ancestral.Ancestral(*inputs, device=device, workspace_bytes=workspace_bytes) as handle:
+            post, branch_of, dead = handle.posteriors(masks, ghosts)
+    if write_ar_probs:
+        write_ar_files(write_ar_probs, write_ar_tree, tree, states, post, branch_of, ghosts)
+    n = tree.num_nodes
+    if host:
+        db = build.build_host(states, kmer_size, n, build.logp_from_posteriors(post), branch_of, omega=omega, num_threads=num_threads)
+    else:
+        with build.Builder(states, kmer_size, n, omega=omega, device=device) as builder:
+            for g in range(0, post.shape[0], chunk):
+                builder.add(build.logp_from_posteriors(post[g:g + chunk]), branch_of[g:g + chunk])
+            db = builder.finish()
+    dbfile.write_db(out_path, db, text)
+    return dict(num_keys=int(db.keys.shape[0]), num_entries=db.num_entries, ghost_nodes=int(post.shape[0]), num_branches=n,
+                sites=int(post.shape[1]), dead_sites=int(dead), categories=parsed.num_categories)

@@ -2035,6 +2035,89 @@ int epik_amd_build_host(uint32_t sigma, uint32_t k, uint32_t num_branches, float
                         const uint32_t *branch_of, uint64_t G, uint64_t L, uint32_t num_threads,
                         epik_amd_builder **result);
 
+/*
+ * Reconstructing ancestral posteriors: the marginal posterior of every state at every site of the ghost nodes of a
+ * reference tree, by Felsenstein's pruning algorithm -- what the builder above starts from.  Model
+ * parameters are given, never optimised.  The rule below is this project's own, worded so that the device, the host
+ * mirror and a numpy restatement give the same bytes.
+ *
+ * Inputs.  The reference tree as parent int32 [N] in the numbering of the drivers: post-order (parent[v] > v), the
+ * root N - 1 with parent -1, every inner node with exactly two children, N >= 3.  sigma is 4 or 20; C in [1, 8] rate
+ * categories with weights w double [C]; frequencies pi double [sigma]; three tables of transition matrices, double
+ * [N - 1][C][sigma][sigma] each, row = the state at the upper end: p_full of the whole branch above node b, p_half of
+ * half that branch, p_pend of the pendant length of the ghost nodes of b.  Every weight and frequency is finite and
+ * at least 0, every matrix entry lies in [0, 2].  The device evaluates no exp: the tables are an input.
+ * masks uint32 [leaves][L]: per leaf (in the order of node ids) and site the set of states the character may stand
+ * for, bit y for state y; a mask without any of the sigma low bits (a gap, an invalid character) counts as all states.
+ *
+ * Arithmetic.  Everything is IEEE double, rounded to nearest, no contraction of multiply and add, in the order given.
+ * "sum over y" means ((t_0 + t_1) + t_2) + ... in state order starting from the first term.
+ *   Down pass, post-order.  For a node u, site s, category c: F(u)[x] = sum over y of P_u,c[x][y] * D_u[s][c][y], P_u
+ *   from p_full; for a leaf D_u[y] is 1.0 or 0.0 by its mask.  For an inner node v with children l, r:
+ *   D_v[s][c][x] = F(l)[x] * F(r)[x].
+ *   Up pass, pre-order.  U_v is the partial at parent(v) of everything outside v's subtree.  For a child of the root
+ *   U_v[x] = F(sibling)[x]; otherwise U_v[x] = F(sibling)[x] * G(p)[x], p the parent and
+ *   G(p)[x] = sum over z of P_p,c[x][z] * U_p[s][c][z].
+ *   Scaling.  After each D_v and each U_v: m = the maximum of the site's C sigma entries; if m > 0,
+ *   with m = f 2^e, f in [0.5, 1) (frexp), every entry becomes ldexp(entry, -e).  The exponent is not kept: a factor
+ *   per site cancels in a posterior.  (No entry exceeds 1600 before scaling, so nothing overflows; scaling is exact
+ *   unless an entry falls below the normal range, where ldexp rounds to nearest even on all three implementations.)
+ *   Midpoint M_b of branch b < N - 1, with h = p_half[b][c]:
+ *       A_c[x] = (sum over y of h[x][y] * D_b[y]) * (sum over z of h[x][z] * U_b[z]),   T_c[x] = pi[x] * A_c[x],
+ *       n[x] = sum over c, in order from the first term, of w_c * T_c[x],   Z = sum over x of n[x],   p[x] = n[x] / Z.
+ *   Pendant node P_b, with q = p_pend[b][c]: B_c[y] = sum over x of T_c[x] * q[x][y]; n[y] = sum over c of w_c * B_c[y];
+ *   Z and p as above.  The two ghost leaves below P_b are all gaps and contribute factors of 1: the extended tree
+ *   (epik_amd/dbbuild.py: extended_tree) is never materialised.
+ *   Output.  p is rounded once to float32.  A row (ghost node, site) whose Z is 0 or not finite is all zeros, and
+ *   *dead_sites counts those rows.  post is float32 [G][L][sigma] and branch_of uint32 [G]: ghosts =
+ *   EPIK_AMD_GHOSTS_INNER gives G = N - 1 midpoints in branch order, _OUTER the N - 1 pendant nodes, _BOTH the
+ *   midpoints followed by the pendant nodes (G = 2 (N - 1)).
+ *   Sites are independent: the handle works through the alignment in chunks of sites, and a chunk cannot change a bit.
+ *
+ *   ancestral_create   a handle on `device` that holds the tree's tables and a workspace of workspace_bytes
+ *       (0: 4 GiB) for the partials [inner nodes + N - 1][sites of a chunk][C][sigma] doubles, the masks and the
+ *       posteriors of a chunk; a workspace that does not hold one site is EPIK_AMD_ERR_INVALID (the message says how
+ *       many bytes a site needs).  The kernels take EPIK_AMD_ANCESTRAL_TILE_SITES sites a workgroup.
+ *   ancestral_posteriors          masks HOST; post and branch_of HOST arrays; synchronous.
+ *   ancestral_posteriors_device   masks HOST; d_post and d_branch_of DEVICE arrays on the handle's device (what
+ *       epik_amd_builder_add_device takes once the logarithm has been taken); synchronous.
+ *   ancestral_host     the same rule in plain C++ on `num_threads` threads (0: one) over the sites, no device.
+ *   model_pmatrices    P(t) for every t of times[n], double [n][sigma][sigma]: the reversible model of the
+ *       exchangeabilities (upper triangle row by row, sigma (sigma - 1) / 2 values) and frequencies pi (all above 0),
+ *       Q normalised to one expected substitution per unit time, through sqrt(pi) symmetrisation and a Jacobi
+ *       eigendecomposition; t = 0 gives the identity exactly.  Host only, not under the bit-for-bit rule.
+ *   model_gamma_rates  the K <= 8 category means of a gamma distribution with shape = rate = alpha (Yang 1994), mean 1.
+ */
+#define EPIK_AMD_GHOSTS_INNER 0u
+#define EPIK_AMD_GHOSTS_OUTER 1u
+#define EPIK_AMD_GHOSTS_BOTH 2u
+#define EPIK_AMD_ANCESTRAL_TILE_SITES 64u
+typedef struct epik_amd_ancestral epik_amd_ancestral;
+typedef struct epik_amd_ancestral_desc {
+    uint32_t num_nodes;      /* N */
+    uint32_t sigma;          /* 4 or 20 */
+    uint32_t num_categories; /* C */
+    uint32_t reserved;       /* 0 */
+    const int32_t *parent;   /* [N] */
+    const double *weights;   /* [C] */
+    const double *pi;        /* [sigma] */
+    const double *p_full;    /* [N - 1][C][sigma][sigma] */
+    const double *p_half;
+    const double *p_pend;
+} epik_amd_ancestral_desc;
+int epik_amd_ancestral_create(int device, const epik_amd_ancestral_desc *desc, uint64_t workspace_bytes,
+                              epik_amd_ancestral **handle);
+int epik_amd_ancestral_posteriors(epik_amd_ancestral *handle, const uint32_t *masks, uint64_t L, uint32_t ghosts,
+                                  float *post, uint32_t *branch_of, uint64_t *dead_sites);
+int epik_amd_ancestral_posteriors_device(epik_amd_ancestral *handle, const uint32_t *masks, uint64_t L, uint32_t ghosts,
+                                         void *d_post, void *d_branch_of, uint64_t *dead_sites);
+void epik_amd_ancestral_destroy(epik_amd_ancestral *handle);
+int epik_amd_ancestral_host(const epik_amd_ancestral_desc *desc, const uint32_t *masks, uint64_t L, uint32_t ghosts,
+                            uint32_t num_threads, float *post, uint32_t *branch_of, uint64_t *dead_sites);
+int epik_amd_model_pmatrices(uint32_t sigma, const double *exchange, const double *pi, const double *times, uint64_t n,
+                             double *out);
+int epik_amd_model_gamma_rates(double alpha, uint32_t num_categories, double *rates);
+
 /* Which kernels the last launch of this handle ran (reports; a large-tree handle falls back from the three-kernel
  * placement to the one-kernel one when the device has no room for the scratch of a launch). */
 #define EPIK_AMD_PATH_WAVE 0u            /* place_reads_kernel: one wavefront per read */
