@@ -139,6 +139,7 @@ EXPORTS = (
     "epik_amd_placer_run_counts",
     "epik_amd_placer_ring_form",
     "epik_amd_placer_table_form",
+    "epik_amd_placer_tail_form",
     "epik_amd_placer_destroy",
     "epik_amd_placer_place",
     "epik_amd_placer_place_device",
@@ -450,6 +451,7 @@ FRAME_NAMES = ("+1", "+2", "+3", "-1", "-2", "-3")
 
 #: n_rows of a read with more k-mers than the counts of a device-pointer launch hold
 ROWS_COUNTS_TOO_NARROW = 0xFFFFFFFF
+TAIL_WAVE, TAIL_KERNEL = 0, 1   # epik_amd_placer_tail_form
 
 
 class EpikAmdError(RuntimeError):
@@ -548,6 +550,9 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_placer_ring_form.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     lib.epik_amd_placer_table_form.restype = i32
     lib.epik_amd_placer_table_form.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
+    if hasattr(lib, "epik_amd_placer_tail_form"):  # (an older library named by EPIK_AMD_LIB)
+        lib.epik_amd_placer_tail_form.restype = i32
+        lib.epik_amd_placer_tail_form.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     lib.epik_amd_placer_destroy.restype = None
     lib.epik_amd_placer_destroy.argtypes = [vp]
     lib.epik_amd_placer_place.restype = i32

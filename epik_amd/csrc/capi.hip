@@ -146,6 +146,7 @@ void epik_amd_placer_destroy(epik_amd_placer *p)
     (void)hipFree(p->d_total);
     (void)hipFree(p->d_front_hdr);
     (void)hipFree(p->d_finish_hdr);
+    (void)hipFree(p->d_tail_ws);
     (void)hipFree(p->d_slow_list);
     (void)hipFree(p->d_slice_rows);
     (void)hipFree(p->d_slice_sums);
@@ -328,6 +329,11 @@ int create_impl(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t sh
         // the run-list ring's descriptors: near wherever the posting region allows it, unless "far" is asked for
         const char *form = std::getenv("EPIK_AMD_RING_FORM");
         p->ring_near = p->runs != 0 && plan.posting_bytes < epik_amd::kNearRegionBytes && !(form && std::strcmp(form, "far") == 0);
+        // the tail of a read in a kernel of its own wherever that form exists (the kernels with list counts), unless
+        // "wave" is asked for
+        const char *tail = std::getenv("EPIK_AMD_TAIL");
+        p->tail_kernel = !p->team && p->runs == epik_amd::kRunLists && d->keep_at_most >= 1 &&
+                         d->keep_at_most <= epik_amd::kTailMaxKeep && !(tail && std::strcmp(tail, "wave") == 0);
     }
     p->db_bytes = plan.posting_bytes;
     CREATE_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
@@ -383,6 +389,7 @@ int create_impl(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t sh
     pp.log_threshold = d->log_threshold;
 #ifdef EPIK_AMD_ABLATION
     if (const char *ab = std::getenv("EPIK_AMD_ABLATE")) pp.ablate = (uint32_t)std::atoi(ab);
+    if (pp.ablate) p->tail_kernel = false;  // (an epilogue that stops early leaves no header for the finishing kernel)
     if (const char *e = std::getenv("EPIK_AMD_GRID_PERCENT")) p->grid_percent = std::strtoull(e, nullptr, 10);
     if (const char *st = std::getenv("EPIK_AMD_STAMPS"); st && st[0] == '1') {
         CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&pp.dbg), kDbgWords * sizeof(unsigned long long)));
@@ -513,6 +520,11 @@ int create_impl(const epik_amd_placer_desc *d, uint32_t shard_index, uint32_t sh
                 CREATE_TRY(epik_amd::set_place_reads_lds_limit(p->layout, runs, counts, block_bytes));
                 int per_cu = 0;
                 CREATE_TRY(epik_amd::place_reads_occupancy(p->layout, runs, counts, (int)(wpb * 64u), block_bytes, &per_cu));
+                if (p->tail_kernel && counts != epik_amd::kCounts8) {  // (one geometry for both forms of the kernel)
+                    int deferred = 0;
+                    CREATE_TRY(epik_amd::place_reads_occupancy(p->layout, runs, counts, (int)(wpb * 64u), block_bytes, &deferred, true));
+                    per_cu = std::min(per_cu, deferred);
+                }
                 const uint32_t lds_units = (block_bytes + epik_amd::kLdsGranule - 1u) / epik_amd::kLdsGranule;
                 per_cu = std::min<int>(per_cu, (int)(128u / std::max(lds_units, 1u)));
                 if (per_cu < 1) per_cu = 1;
@@ -831,6 +843,23 @@ static int reserve_front(epik_amd_placer *p, uint64_t n, uint64_t total_chars, b
     return EPIK_AMD_OK;
 }
 
+// The headers and candidates between a placement kernel that defers its tail and finish_rows_kernel for a launch of n reads
+// (place_kernel.h: tail_ws_bytes).  Grown, never shrunk, with a quarter of head room as the staging buffers have (batches
+// that grow slowly do not reallocate every call); growing frees the old buffer, which waits for the device -- for the
+// launches before this one that still use it.  One workspace per handle: its launches are enqueued on one
+// stream or ordered (include/epik_amd.h), as with the scratch of the large trees.
+static int reserve_tail(epik_amd_placer *p, uint64_t n)
+{
+    if (epik_amd::tail_ws_bytes(n, p->params.keep_at_most) > p->tail_ws_bytes) {
+        const size_t bytes = epik_amd::tail_ws_bytes(n + n / 4 + 64, p->params.keep_at_most);
+        (void)hipFree(p->d_tail_ws);
+        p->d_tail_ws = nullptr, p->tail_ws_bytes = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p->d_tail_ws), bytes));
+        p->tail_ws_bytes = bytes;
+    }
+    return EPIK_AMD_OK;
+}
+
 static int launch(epik_amd_placer *p, launch_mode mode, const void *d_seqs, const void *d_seq_offsets, uint64_t n,
                   void *d_rows, void *d_n_rows, void *d_counts, hipStream_t stream, const shard_buffers &shard = {},
                   uint64_t total_chars = 0)
@@ -988,8 +1017,18 @@ static int launch(epik_amd_placer *p, launch_mode mode, const void *d_seqs, cons
         HIP_TRY(epik_amd::launch_finish_reads(pp, p->counts, dim3((unsigned)blocks), dim3(g.waves_per_block * 64u),
                                               g.lds_block_bytes, stream));
     } else {
-        HIP_TRY(epik_amd::launch_place_reads(pp, p->layout, p->runs | p->geo[p->counts].ring, p->counts, dim3((unsigned)blocks),
-                                             dim3(g.waves_per_block * 64u), g.lds_block_bytes, stream));
+        // placing with list counts: the waves stop behind the rank, finish_rows_kernel follows on the same stream (an
+        // accumulate-only launch has no tail)
+        const bool deferred = mode == kPlace && p->tail_kernel && p->counts != epik_amd::kCounts8;
+        if (deferred) {
+            if (const int rc = reserve_tail(p, n); rc != EPIK_AMD_OK) return rc;
+            HIP_TRY(epik_amd::launch_place_reads_deferred(pp, p->d_tail_ws, p->layout, p->runs | p->geo[p->counts].ring, p->counts,
+                                                          dim3((unsigned)blocks), dim3(g.waves_per_block * 64u), g.lds_block_bytes, stream));
+            HIP_TRY(epik_amd::launch_finish_rows(pp, p->d_tail_ws, stream));
+        } else {
+            HIP_TRY(epik_amd::launch_place_reads(pp, p->layout, p->runs | p->geo[p->counts].ring, p->counts, dim3((unsigned)blocks),
+                                                 dim3(g.waves_per_block * 64u), g.lds_block_bytes, stream));
+        }
     }
     if (timed) {
         HIP_TRY(hipEventRecord(p->ev_stop, stream));
@@ -1141,6 +1180,14 @@ int epik_amd_placer_ring_form(const epik_amd_placer *p, uint32_t counts, uint32_
     if (counts > (uint32_t)epik_amd::kCounts32) return fail(EPIK_AMD_ERR_INVALID, "counts must be 0, 1 or 2");
     const int ring = p->team ? 0 : p->geo[counts].ring;
     *form = ((ring & epik_amd::kRingNear) ? EPIK_AMD_RING_NEAR : 0u) | ((ring & epik_amd::kRingSlack) ? EPIK_AMD_RING_SLACK : 0u);
+    return EPIK_AMD_OK;
+}
+
+int epik_amd_placer_tail_form(const epik_amd_placer *p, uint32_t counts, uint32_t *form)
+{
+    if (!p || !form) return fail(EPIK_AMD_ERR_INVALID, "null argument");
+    if (counts > (uint32_t)epik_amd::kCounts32) return fail(EPIK_AMD_ERR_INVALID, "counts must be 0, 1 or 2");
+    *form = p->tail_kernel && counts != (uint32_t)epik_amd::kCounts8 ? EPIK_AMD_TAIL_KERNEL : EPIK_AMD_TAIL_WAVE;
     return EPIK_AMD_OK;
 }
 
@@ -1397,13 +1444,14 @@ int epik_amd_placer_release_scratch(epik_amd_placer *p)
                      &p->d_slice_sums, reinterpret_cast<void **>(&p->d_front_pool), reinterpret_cast<void **>(&p->d_sparse_cap),
                      reinterpret_cast<void **>(&p->d_scan_tiles), reinterpret_cast<void **>(&p->d_seqs),
                      reinterpret_cast<void **>(&p->d_seq_offsets), reinterpret_cast<void **>(&p->d_rows),
-                     reinterpret_cast<void **>(&p->d_n_rows), reinterpret_cast<void **>(&p->d_counts)};
+                     reinterpret_cast<void **>(&p->d_n_rows), reinterpret_cast<void **>(&p->d_counts),
+                     reinterpret_cast<void **>(&p->d_tail_ws)};
     for (void **b : bufs) {
         if (*b) (void)hipFree(*b);
         *b = nullptr;
     }
     p->front_hdr_bytes = 0, p->finish_hdr_bytes = 0, p->slow_list_reads = 0, p->slice_out_reads = 0, p->front_pool_cap = 0, p->sparse_cap_items = 0;
-    p->d_seqs_cap = 0, p->d_reads_cap = 0, p->front_failed_reads = 0;
+    p->d_seqs_cap = 0, p->d_reads_cap = 0, p->front_failed_reads = 0, p->tail_ws_bytes = 0;
     return EPIK_AMD_OK;
 }
 

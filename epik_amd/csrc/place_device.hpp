@@ -614,6 +614,17 @@ template <typename Layout, typename = void>
 struct ListCounts : std::false_type {};
 template <typename Layout>
 struct ListCounts<Layout, std::void_t<decltype(Layout::kListCounts)>> : std::bool_constant<Layout::kListCounts> {};
+// A layout whose reads leave the double-precision tail of their epilogue to finish_rows_kernel (tail_kernel.hip): the
+// layout it wraps in everything else.  A type of its own, so that the instantiations of the kernels over the plain
+// layouts stay the kernels they are.
+template <typename Layout>
+struct DeferredTail : Layout {
+    static constexpr bool kDeferTail = true;
+};
+template <typename Layout, typename = void>
+struct DefersTail : std::false_type {};
+template <typename Layout>
+struct DefersTail<Layout, std::void_t<decltype(Layout::kDeferTail)>> : std::bool_constant<Layout::kDeferTail> {};
 
 // absolute address of chunk c (64 postings each) of the list at byte offset `addr`
 template <typename Layout>
@@ -1115,8 +1126,12 @@ __device__ __forceinline__ void materialize_counts(WaveLds<CountT> lds, uint32_t
 // read by itself (place_kernel.hip); everything comes from the kernel arguments, the context is
 // empty and costs nothing.  team_kernel.hip has a context of its own: one slice of the branch
 // range, the rest of the read's workgroup owning the other slices.
-struct WaveCtx {
+// kDeferTailT: the epilogue stops behind the rank and leaves the double-precision tail of the read to finish_rows_kernel
+// (tail_kernel.hip; TailHeader below).
+template <bool kDeferTailT>
+struct WaveCtxT {
     static constexpr bool kTeam = false;
+    static constexpr bool kDeferTail = kDeferTailT;
     static constexpr uint32_t kCandCap = kChunkCap;  // top-k candidates: as many as chunk descriptors fit
     __device__ __forceinline__ bool untouched() const { return false; }  // (a team context may know that no row holds a count)
     template <typename Params>
@@ -1134,6 +1149,9 @@ struct WaveCtx {
         Layout::lookup(p, key, 0u, addr, len);
     }
 };
+typedef WaveCtxT<false> WaveCtx;
+template <typename Ctx>
+constexpr bool kDefersTail = requires { requires Ctx::kDeferTail; };  // (a team context has no such member)
 
 // amb_slot >= 0 (accumulate-only launches of a k-mer-space shard): the read's ambiguous k-mers
 // are not added to the sums but recorded, per branch, as {order of the first ambiguous key of
@@ -1241,6 +1259,27 @@ struct TeamPartial {
     uint32_t reserved;
     double sum;
 };
+
+// What a wave of the one-wavefront kernel hands to finish_rows_kernel (tail_kernel.hip) when its context defers the
+// tail (WaveCtxT<true>): per read one header, and the read's ranked candidates as {branch, score bits, k-mer count, 0},
+// the row of rank r in entry read * keep_at_most + r, r < n_sel.  Both lie in the launch's workspace
+// (PlaceParams::tail_ws): [n_reads] headers, then [n_reads * keep_at_most] candidates.  The caller's rows are not
+// touched before the filter has decided: a slot past n_rows keeps what it held, as with the tail in the wave.
+struct alignas(16) TailHeader {
+    double sum;        // relative regime: sum_i 10^(score_i - ref_score) + the not-placed term, finished in the wave;
+                       // else the term-by-term double sum over the placed branches (0 when everything underflows)
+    float ref_score;   // max(best score, threshold score)
+    float thr_score;
+    float not_placed;  // (float)N - (float)touched
+    uint32_t bits;     // n_sel (kTailSelMask) | flags
+    uint32_t reserved[2];
+};
+static_assert(sizeof(TailHeader) == kTailHeaderBytes && sizeof(v4u) == kTailRowBytes, "the workspace the host sizes (place_kernel.h)");
+constexpr uint32_t kTailSelMask = 0xffu;
+constexpr uint32_t kTailRelative = 0x100u;      // the sum is relative to 10^ref_score
+constexpr uint32_t kTailUnderflow = 0x200u;     // ref_score < -325: every power is 0
+constexpr uint32_t kTailUntouched = 0x400u;     // no list found: the rows are the first branches at the threshold score
+constexpr uint32_t kTailNone = 0x800u;          // n_rows is final (too short, counts too narrow): the read has no tail
 
 // With Ctx = WaveCtx this is the whole epilogue of a read.  With a team context (Ctx::kTeam) it
 // works on one slice of the branches: correction, the slice's own top rows and its share of
@@ -1651,6 +1690,52 @@ __device__ __forceinline__ void place_epilogue_body(const PlaceParams *__restric
         if (!untouched) lds.clear(n_rows_pad);
         EPI_STAMP(7)  // clear
         (void)read;
+        return;
+    }
+    if constexpr (kDefersTail<Ctx>) {
+        // ---- the tail in a kernel of its own: ranked candidates and the read's header to the workspace ----------
+        // (the sum exactly as below: the same operands in the same order)
+        const float not_placed = (float)N - (float)touched;  // :174
+        double sum;
+        if (relative_sum) {
+            sum = wave_sum_f64((double)rel_sum);
+            if (not_placed != 0.0f)
+                sum += (double)(not_placed *
+                                __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(thr_score, ref_score), kLog2Of10)));
+        } else {
+            sum = 0.0;
+            if (!all_underflow) {
+                for (uint32_t i = lane; i < N; i += kWave) {
+                    const uint2 cv = lds.load(i);
+                    if (cv.y != 0) sum += pow10_f64((double)__uint_as_float(cv.x));
+                }
+                sum = wave_sum_f64(sum);
+            }
+        }
+        TailHeader *headers = static_cast<TailHeader *>(p.tail_ws);
+        TailHeader *hdr = headers + read;
+        v4u *rows_out = reinterpret_cast<v4u *>(headers + p.n_reads) + read * keep;
+#pragma unroll
+        for (int q = 0; q < kQ; ++q) {
+            if ((uint32_t)q < n_q && my_key[q] != 0 && my_rank[q] < n_sel) {
+                const uint32_t branch = ~(uint32_t)my_key[q];
+                uint32_t count = 0u;
+                if (p.kmer_counts) count = (touched && branch < N) ? ((uint32_t)lds.count[branch] & ~(uint32_t)lds.kSeen) : 0u;
+                rows_out[my_rank[q]] = v4u{branch, __float_as_uint(unord_f32((uint32_t)(my_key[q] >> 32))), count, 0u};
+            }
+        }
+        if (lane == 0) {
+            TailHeader h;
+            h.sum = sum;
+            h.ref_score = ref_score;
+            h.thr_score = thr_score;
+            h.not_placed = not_placed;
+            h.bits = n_sel | (relative_sum ? kTailRelative : 0u) | (all_underflow ? kTailUnderflow : 0u) |
+                     (touched == 0 ? kTailUntouched : 0u);
+            h.reserved[0] = h.reserved[1] = 0u;
+            *hdr = h;
+        }
+        lds.clear(n_rows_pad);
         return;
     }
     // ---- 10^score of every row that will be reported (:254), the lanes side by side.  The row of

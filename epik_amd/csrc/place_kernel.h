@@ -32,7 +32,15 @@ struct PlaceParams {
     // k-mer-space shard: raw per-branch sums, [n_reads][num_branches].  Non-null in
     // place_reads_kernel = accumulate only (no epilogue); the input of finish_reads_kernel.
     float *partial_scores;
-    uint16_t *partial_counts;        // (a read of a k-mer-space shard has at most 65535 k-mers)
+    union {
+        uint16_t *partial_counts;    // (a read of a k-mer-space shard has at most 65535 k-mers)
+        // In the place of the partial counts, which only an accumulate-only launch has: the workspace of a launch
+        // whose reads leave their double-precision tail to finish_rows_kernel (the DeferredTail instantiations of
+        // place_reads_kernel, and that kernel) -- [n_reads] headers of kTailHeaderBytes, then [n_reads * keep_at_most]
+        // candidates of kTailRowBytes (place_device.hpp: TailHeader).  The argument block of every other kernel is
+        // what it was.
+        void *tail_ws;
+    };
     // ... and how its ambiguous k-mers cross the shards (place.cpp:385-388 holds over the whole
     // database): amb_slot[read] >= 0 names the read's row in amb_order / amb_avg,
     // [slots][num_branches]: accumulate records there, per branch, the order of the first ambiguous
@@ -58,6 +66,9 @@ struct PlaceParams {
     uint32_t ablate;                 // timing experiments only (-DEPIK_AMD_ABLATION builds)
     unsigned long long *dbg;         // phase cycle sums (-DEPIK_AMD_ABLATION builds, EPIK_AMD_STAMPS=1)
 };
+constexpr size_t kTailHeaderBytes = 32, kTailRowBytes = 16;
+constexpr size_t tail_ws_bytes(uint64_t n_reads, uint32_t keep) { return (size_t)n_reads * (kTailHeaderBytes + (size_t)keep * kTailRowBytes); }
+constexpr uint32_t kTailMaxKeep = 64;  // a group of lanes per read, a lane per row: handles that keep more finish in the wave
 
 // n_rows of a read with more k-mers than the launch's count width holds (EPIK_AMD_ROWS_COUNTS_TOO_NARROW)
 constexpr uint32_t kCountsTooNarrow = 0xffffffffu;
@@ -182,7 +193,14 @@ hipError_t launch_place_reads(const PlaceParams &p, DbLayout layout, int runs, i
                               size_t lds_bytes, hipStream_t stream);
 hipError_t set_place_reads_lds_limit(DbLayout layout, int runs, int counts, size_t lds_bytes);
 hipError_t place_reads_occupancy(DbLayout layout, int runs, int counts, int block_threads, size_t lds_bytes,
-                                 int *blocks_per_cu);
+                                 int *blocks_per_cu, bool deferred_tail = false);
+// tail_ws != null: the launch defers the tail of its reads to finish_rows_kernel (tail_kernel.hip), which the caller
+// enqueues behind it with the same arguments -- a lane per reported row turns the headers and candidates of the
+// workspace into rows, n_rows and k-mer counts.  Only the kernels with list counts come in that form (runs has
+// kRunLists, 16- or 32-bit counts), for keep_at_most <= kTailMaxKeep.
+hipError_t launch_place_reads_deferred(const PlaceParams &p, void *tail_ws, DbLayout layout, int runs, int counts, dim3 grid,
+                                       dim3 block, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_finish_rows(const PlaceParams &p, void *tail_ws, hipStream_t stream);
 hipError_t launch_finish_reads(const PlaceParams &p, int counts, dim3 grid, dim3 block, size_t lds_bytes,
                                hipStream_t stream);
 hipError_t set_finish_reads_lds_limit(int counts, size_t lds_bytes);

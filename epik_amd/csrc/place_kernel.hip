@@ -88,6 +88,9 @@ __global__ __launch_bounds__(256, 5) void place_reads_kernel(PlaceParams p)
                 }
             } else if (lane == 0) {
                 p.n_rows[read] = len < k ? 0u : kCountsTooNarrow;
+                // (n_rows is final: the finishing kernel must neither write it nor look for rows)
+                // (of such a header only `bits` is written, and only `bits` is read)
+                if constexpr (DefersTail<Layout>::value) static_cast<TailHeader *>(p.tail_ws)[read].bits = kTailNone;
             }
             continue;
         }
@@ -256,7 +259,8 @@ __global__ __launch_bounds__(256, 5) void place_reads_kernel(PlaceParams p)
         }
         // ---- correction, sum_scores, top-k, LWR, rows out, reset of the wave's vectors ----------
         if (lane == 0) lds.store(p.n_pad - 1u, 0u, 0u);  // the dummy row of the out-of-range lanes
-        place_epilogue<Layout, CountT>(kp, lds, read, n_kmers, WaveCtx{});
+        // (a DeferredTail layout: the epilogue ends behind the rank, finish_rows_kernel -- tail_kernel.hip -- does the rest)
+        place_epilogue<Layout, CountT>(kp, lds, read, n_kmers, WaveCtxT<DefersTail<Layout>::value>{});
         EPIK_STAMP(4)  // top-k, LWR, rows out, reset
     }
 #ifdef EPIK_AMD_ABLATION
@@ -400,21 +404,47 @@ hipError_t launch_place_reads(const PlaceParams &p, DbLayout layout, int runs, i
     });
 }
 
+hipError_t launch_place_reads_deferred(const PlaceParams &p, void *tail_ws, DbLayout layout, int runs, int counts, dim3 grid,
+                                       dim3 block, size_t lds_bytes, hipStream_t stream)
+{
+    if (!tail_ws || p.partial_scores) return hipErrorInvalidValue;  // (an accumulate-only launch has no tail)
+    PlaceParams q = p;
+    q.tail_ws = tail_ws;
+    return dispatch(layout, runs, counts, [&]<typename L, typename C>() {
+        if constexpr (ListCounts<L>::value) {
+            hipLaunchKernelGGL((place_reads_kernel<DeferredTail<L>, C>), grid, block, lds_bytes, stream, q);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
+    });
+}
+
 // The attribute is a cap per kernel and process, not a reservation (what a launch occupies is what it
 // asks for): it is always raised to the whole LDS of a CU, so that placers of different trees alive in
 // one process can never lower it under each other's launches.
 hipError_t set_place_reads_lds_limit(DbLayout layout, int runs, int counts, size_t /*lds_bytes*/)
 {
     return dispatch(layout, runs, counts, [&]<typename L, typename C>() {
+        if constexpr (ListCounts<L>::value) {  // ... and its form with the tail deferred
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&place_reads_kernel<DeferredTail<L>, C>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu);
+            if (e != hipSuccess) return e;
+        }
         return hipFuncSetAttribute(reinterpret_cast<const void *>(&place_reads_kernel<L, C>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu);
     });
 }
 
 hipError_t place_reads_occupancy(DbLayout layout, int runs, int counts, int block_threads, size_t lds_bytes,
-                                 int *blocks_per_cu)
+                                 int *blocks_per_cu, bool deferred_tail)
 {
     return dispatch(layout, runs, counts, [&]<typename L, typename C>() {
+        if constexpr (ListCounts<L>::value) {
+            if (deferred_tail)
+                return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, place_reads_kernel<DeferredTail<L>, C>,
+                                                                    block_threads, lds_bytes);
+        }
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, place_reads_kernel<L, C>,
                                                             block_threads, lds_bytes);
     });

@@ -37,7 +37,14 @@ struct epik_amd_placer {
     // ... and the form of the run-list ring's chunk descriptors (RunListLayout), latched beside it: near where the posting
     // region is shorter than epik_amd::kNearRegionBytes (EPIK_AMD_RING_FORM=near|far forces it where legal)
     bool ring_near = false;
-    bool team = false;               // the team kernel (one workgroup per read) places; else one wavefront per read
+    // ... and where the kernels with list counts finish a read (EPIK_AMD_TAIL=wave|kernel, latched beside them): in
+    // finish_rows_kernel (tail_kernel.hip), whose headers and candidates are this workspace, grown on demand.  Placing
+    // launches only: a finish launch of this path (finish_reads_kernel) keeps the tail in its wave and has no workspace
+    // to share with a place launch beside it.
+    bool tail_kernel = false;
+    uint8_t *d_tail_ws = nullptr;
+    size_t tail_ws_bytes = 0;
+    bool team = false;              // the team kernel (one workgroup per read) places; else one wavefront per read
     int team_waves = 0;
     const uint8_t *team_table = nullptr;
     uint32_t team_passes = 0, team_slice_rows = 0, team_rows_pad = 0;

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # sizes their grids; shard_place.hip -- the host side of place_sharded and its one element-wise kernel -- is not among
 # them: no counter pass runs it)
 KERNEL_SOURCES = ("place_kernel.hip", "place_device.hpp", "team_kernel.hip", "team_stream.hip", "team_device.hpp",
-                  "team_epilogue.hpp", "place_kernel.h", "db_layout.h", "db_image.cpp", "capi.hip", "placer_impl.hpp")
+                  "team_epilogue.hpp", "tail_kernel.hip", "tail_device.hpp", "place_kernel.h", "db_layout.h", "db_image.cpp", "capi.hip", "placer_impl.hpp")
 
 
 def kernel_source_hash() -> str:

@@ -187,6 +187,16 @@ int epik_amd_placer_ring_form(const epik_amd_placer *p, uint32_t counts, uint32_
 #define EPIK_AMD_TABLE_PAIRED 2u
 #define EPIK_AMD_TABLE_TRIPLED 3u
 int epik_amd_placer_table_form(const epik_amd_placer *p, uint32_t *form);
+/* Where the one-wavefront kernel of this handle finishes a read, for that count width: EPIK_AMD_TAIL_WAVE -- in the wave
+ * that placed it; EPIK_AMD_TAIL_KERNEL -- the wave stops behind the ranking of its candidates, and a second kernel,
+ * enqueued behind the first on the same stream, computes 10^score, the LWRs and the filter with a lane per reported row
+ * and writes rows, n_rows and k-mer counts (the kernels with list counts -- epik_amd_placer_run_counts -- of handles
+ * with keep_at_most <= 64; placing launches only).  The output is the same bytes in either form, the slots past n_rows
+ * included: nothing writes them.  EPIK_AMD_TAIL (read at create()): `wave` keeps the tail in the wave; `kernel` is the
+ * default wherever that form exists. */
+#define EPIK_AMD_TAIL_WAVE 0u
+#define EPIK_AMD_TAIL_KERNEL 1u
+int epik_amd_placer_tail_form(const epik_amd_placer *p, uint32_t counts, uint32_t *form);
 /* The image create() uploads for that plan, written front to back into host buffers of
  * plan->table_bytes / filter_bytes / posting_bytes (NULL = that part is produced and dropped).
  * Host only; create() streams the same bytes to the device without holding them. */
@@ -214,7 +224,12 @@ int epik_amd_placer_place(epik_amd_placer *p, const char *seqs, const uint64_t *
  * Same computation with every buffer already resident in device memory, enqueued
  * on `stream` (a hipStream_t passed as void*; NULL = the default stream) without
  * synchronising.  d_kmer_counts may be NULL.  The launches of one handle share its scratch
- * memory (large trees): enqueue them on one stream, or order them.
+ * memory (large trees; the headers and candidates of EPIK_AMD_TAIL_KERNEL): enqueue them on one stream, or order them.
+ * A call that has to allocate or grow that scratch (the first one, and one with more reads than any before it by more
+ * than the head room) frees the old buffer first, which waits for the device; every other call only enqueues.
+ * The call may enqueue more than one kernel: rows, n_rows and k-mer counts are final when `stream` reaches the end of
+ * the last of them (with EPIK_AMD_TAIL_KERNEL, of the kernel that finishes the rows) -- for whoever reads them on the
+ * same stream, behind an event recorded on it after the call, or after a synchronise.
  */
 int epik_amd_placer_place_device(epik_amd_placer *p, const void *d_seqs, const void *d_seq_offsets,
                                  uint64_t n, void *d_rows, void *d_n_rows, void *d_kmer_counts,

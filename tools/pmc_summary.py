@@ -13,7 +13,7 @@ for f in sorted(glob.glob(os.path.join(root, "*", "*", "*_counter_collection.csv
     run = f.split(os.sep)[-3]
     for r in csv.DictReader(open(f)):
         name = r["Kernel_Name"]
-        for key in ("place_reads_kernel", "team_place_kernel", "team_front_kernel", "team_stream_kernel",
+        for key in ("place_reads_kernel", "finish_rows_kernel", "team_place_kernel", "team_front_kernel", "team_stream_kernel",
                     "team_merge", "stream_seq", "stream_rnd"):
             if key in name:
                 # (team_merge_kernel, or since round 5 team_merge_packed_kernel<16 | 32>: one line either way)
