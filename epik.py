@@ -61,6 +61,9 @@ reconstruction is run on, and `build -t TREE --ar-probs FILE --ar-tree FILE -s n
 `reconstruct -t TREE -r ALIGNMENT --model STR [--model-file F] -s nucl|amino -k K --omega W [--ghosts ...] [--reduction R] [--chunk G]
 [--write-ar-probs F --write-ar-tree F] -o DB` needs no outside tool: it reconstructs the ghost nodes' posteriors on the GPU under
 a given model (Felsenstein pruning; epik_amd/ancestral.py) and builds the database from them.
+`build` and `reconstruct` take `--filter best|mif0|random [--filter-seed X]`: the order the k-mers are stored in, which --mu and
+--max-ram cut a prefix of (epik_amd/filters.py; best is the default and the order written so far); `rank -i DB --filter F
+[--filter-seed X] [--host] -o OUT` re-ranks a database that exists.
 """
 from __future__ import annotations
 
@@ -641,19 +644,27 @@ def extend(tree, refalign, outputdir, reduction):
 @click.option("--ghosts", type=click.Choice(["inner", "outer", "both"]), default="both", show_default=True,
               help="Which ghost nodes of every branch to use: its midpoint (inner), the pendant node (outer), or both.")
 @click.option("--chunk", type=int, default=256, show_default=True, help="Ghost nodes handed to the device at a time.")
+@click.option("--filter", "filter_name", type=str, default="best", show_default=True,
+              help="The order the k-mers are stored in, most informative first (--mu and --max-ram load a prefix of it): best (the "
+                   "best score of a k-mer's list), mif0 (the entropy of the branch given the k-mer) or random.")
+@click.option("--filter-seed", type=click.IntRange(0, (1 << 64) - 1), default=None,
+              help="With --filter random: the seed, a uint64 [default: 0].")
+@click.option("--host", is_flag=True, help="Run the host mirrors of the builder and the ranking: no GPU, and slow.")
 @click.option("-o", "--output", "output", required=True, type=click.Path(dir_okay=False), help="The database to write (.ekdb).")
-def build_db(tree, ar_probs, ar_tree, states, kmer_size, omega, ghosts, chunk, output):
+def build_db(tree, ar_probs, ar_tree, states, kmer_size, omega, ghosts, chunk, filter_name, filter_seed, host, output):
     """Builds a phylo-k-mer database on the GPU from the posteriors of an extended tree's ghost nodes."""
     from epik_amd import dbbuild
     try:
         dbbuild.check_build_options(states, kmer_size, omega, chunk)  # (before anything is opened)
+        dbbuild.check_filter_options(filter_name, filter_seed)
     except dbbuild.BuildInputError as err:
         _fail_usage(err)
     for flag, path in (("-t", tree), ("--ar-probs", ar_probs), ("--ar-tree", ar_tree)):
         if not os.path.isfile(path):
             raise click.UsageError(f"{flag}: the file '{path}' does not exist")
     try:
-        info = dbbuild.build_from_files(tree, ar_probs, ar_tree, states, kmer_size, omega, output, ghosts=ghosts, chunk=chunk)
+        info = dbbuild.build_from_files(tree, ar_probs, ar_tree, states, kmer_size, omega, output, ghosts=ghosts, chunk=chunk,
+                                        host=host, filter=filter_name, filter_seed=filter_seed)
     except dbbuild.BuildInputError as err:
         _fail_usage(err)
     print(f"{output}: {info['num_keys']} k-mers, {info['num_entries']} phylo-k-mers from {info['ghost_nodes']} ghost nodes "
@@ -683,16 +694,22 @@ def build_db(tree, ar_probs, ar_tree, states, kmer_size, omega, ghosts, chunk, o
               help="Also write the posteriors as the table `build --ar-probs` reads (with --write-ar-tree).")
 @click.option("--write-ar-tree", type=click.Path(dir_okay=False), default=None,
               help="Also write the extended tree with the labels of that table, as `build --ar-tree` reads it.")
-@click.option("--host", is_flag=True, help="Run the host mirrors of the reconstruction and the builder: no GPU, and slow.")
+@click.option("--filter", "filter_name", type=str, default="best", show_default=True,
+              help="The order the k-mers are stored in, most informative first (--mu and --max-ram load a prefix of it): best (the "
+                   "best score of a k-mer's list), mif0 (the entropy of the branch given the k-mer) or random.")
+@click.option("--filter-seed", type=click.IntRange(0, (1 << 64) - 1), default=None,
+              help="With --filter random: the seed, a uint64 [default: 0].")
+@click.option("--host", is_flag=True, help="Run the host mirrors of the reconstruction, the builder and the ranking: no GPU, and slow.")
 @click.option("--threads", type=int, default=1, show_default=True, help="With --host: threads of the host mirrors.")
 @click.option("-o", "--output", "output", required=True, type=click.Path(dir_okay=False), help="The database to write (.ekdb).")
 def reconstruct(tree, refalign, model, model_file, states, kmer_size, omega, ghosts, reduction, chunk, write_ar_probs, write_ar_tree,
-                host, threads, output):
+                filter_name, filter_seed, host, threads, output):
     """Builds a phylo-k-mer database from a reference tree and alignment: the ancestral posteriors of the ghost nodes are
     reconstructed on the GPU under the given model, then the database is built from them."""
     from epik_amd import ancestral, dbbuild
     try:  # (before anything is opened)
         dbbuild.check_build_options(states, kmer_size, omega, chunk)
+        dbbuild.check_filter_options(filter_name, filter_seed)
         ancestral.Model.parse(model, states).check_model_file(model_file)
     except dbbuild.BuildInputError as err:
         _fail_usage(err)
@@ -704,7 +721,8 @@ def reconstruct(tree, refalign, model, model_file, states, kmer_size, omega, gho
     try:
         info = dbbuild.build_from_alignment(tree, refalign, model, states, kmer_size, omega, output, model_file=model_file, ghosts=ghosts,
                                             reduction=reduction, chunk=chunk, host=host, num_threads=threads,
-                                            write_ar_probs=write_ar_probs, write_ar_tree=write_ar_tree)
+                                            write_ar_probs=write_ar_probs, write_ar_tree=write_ar_tree, filter=filter_name,
+                                            filter_seed=filter_seed)
     except dbbuild.BuildInputError as err:
         _fail_usage(err)
     print(f"{output}: {info['num_keys']} k-mers, {info['num_entries']} phylo-k-mers from {info['ghost_nodes']} ghost nodes "
@@ -713,6 +731,33 @@ def reconstruct(tree, refalign, model, model_file, states, kmer_size, omega, gho
 
 
 Launcher.later["reconstruct"] = reconstruct
+
+
+@click.command(name="rank")
+@click.option("-i", "--database", "database", required=True, type=click.Path(dir_okay=False), help="The database to re-rank (.ekdb).")
+@click.option("--filter", "filter_name", required=True, type=str, help="best, mif0 or random: as `build --filter`.")
+@click.option("--filter-seed", type=click.IntRange(0, (1 << 64) - 1), default=None,
+              help="With --filter random: the seed, a uint64 [default: 0].")
+@click.option("--host", is_flag=True, help="Rank on the host mirror: no GPU.")
+@click.option("--threads", type=int, default=1, show_default=True, help="With --host: threads of the host mirror.")
+@click.option("-o", "--output", "output", required=True, type=click.Path(dir_okay=False), help="The database to write (.ekdb).")
+def rank_db(database, filter_name, filter_seed, host, threads, output):
+    """Re-ranks the k-mers of a database that exists: read whole at its own omega, ranked on the GPU, written in the new order."""
+    from epik_amd import dbbuild
+    try:
+        dbbuild.check_filter_options(filter_name, filter_seed)  # (before anything is opened)
+    except dbbuild.BuildInputError as err:
+        _fail_usage(err)
+    if not os.path.isfile(database):
+        raise click.UsageError(f"-i: the file '{database}' does not exist")
+    try:
+        info = dbbuild.rerank_file(database, output, filter_name, filter_seed, host=host, num_threads=threads)
+    except dbbuild.BuildInputError as err:
+        _fail_usage(err)
+    print(f"{output}: {info['num_keys']} k-mers, {info['num_entries']} phylo-k-mers ranked by {filter_name}")
+
+
+Launcher.later["rank"] = rank_db
 
 
 if __name__ == "__main__":

@@ -98,6 +98,17 @@ class Builder:
         keys, offsets, values, self.num_splits = _copy_out(self._lib, self._handle)
         return _as_db(self.states, self.kmer_size, self.omega, self.num_branches, self.log_thr, keys, offsets, values)
 
+    def rank(self, filter="best", seed: int = 0):
+        """(value float64 [K], order uint32 [K]) of the finished database by informativeness (epik_amd/filters.py), on the
+        builder's own device arrays: after `finish`, nothing is uploaded.  `order` is what dbfile.write_db takes."""
+        from . import filters
+        nk, ne = ctypes.c_uint64(), ctypes.c_uint64()
+        capi.check(self._lib.epik_amd_builder_finish(self._handle, ctypes.byref(nk), ctypes.byref(ne), None))
+        value, order = np.zeros(nk.value, np.float64), np.zeros(nk.value, np.uint32)
+        fid = filters.filter_id(filter) if isinstance(filter, str) else int(filter)
+        capi.check(self._lib.epik_amd_builder_rank(self._handle, fid, int(seed) & (2 ** 64 - 1), value.ctypes.data, order.ctypes.data))
+        return value, order
+
     def close(self) -> None:
         if self._handle:
             self._lib.epik_amd_builder_destroy(self._handle)

@@ -317,6 +317,11 @@ EXPORTS = (
     "epik_amd_ancestral_host",
     "epik_amd_model_pmatrices",
     "epik_amd_model_gamma_rates",
+    "epik_amd_filter_rank_device",
+    "epik_amd_filter_rank",
+    "epik_amd_builder_rank",
+    "epik_amd_filter_rank_host",
+    "epik_amd_filter_math_host",
 )
 
 
@@ -864,6 +869,17 @@ def load() -> ctypes.CDLL:
     lib.epik_amd_model_pmatrices.argtypes = [u32, vp, vp, vp, u64, vp]
     lib.epik_amd_model_gamma_rates.restype = i32
     lib.epik_amd_model_gamma_rates.argtypes = [ctypes.c_double, u32, vp]
+    # (the informativeness ranking)
+    lib.epik_amd_filter_rank_device.restype = i32
+    lib.epik_amd_filter_rank_device.argtypes = [i32, u32, ctypes.c_float, vp, vp, vp, u64, u32, u64, vp, vp, vp]
+    lib.epik_amd_filter_rank.restype = i32
+    lib.epik_amd_filter_rank.argtypes = [i32, u32, ctypes.c_float, vp, vp, vp, u64, u32, u64, vp, vp]
+    lib.epik_amd_builder_rank.restype = i32
+    lib.epik_amd_builder_rank.argtypes = [vp, u32, u64, vp, vp]
+    lib.epik_amd_filter_rank_host.restype = i32
+    lib.epik_amd_filter_rank_host.argtypes = [u32, ctypes.c_float, vp, vp, vp, u64, u32, u64, u32, vp, vp]
+    lib.epik_amd_filter_math_host.restype = i32
+    lib.epik_amd_filter_math_host.argtypes = [vp, u64, vp, vp]
     _lib = lib
     return lib
 

@@ -1,5 +1,6 @@
 // build_place.hip -- phylo-k-mer databases built from ancestral posteriors: epik_amd_builder_create, _add,
-// _add_device, _finish, _copy, _destroy and epik_amd_build_host (include/epik_amd.h, where the rule is stated once).
+// _add_device, _finish, _copy, _rank, _destroy and epik_amd_build_host (include/epik_amd.h, where the rule is stated once;
+// _rank hands the finished arrays to filter_place.hip).
 //
 // The reference's world builds its databases in another product on CPU threads (IPK); nothing of it is restated here.
 //
@@ -32,6 +33,8 @@
 #include <vector>
 
 #include "../host/build.hpp"
+#include "../host/filter.hpp"
+#include "filter_entry.hpp"
 #include "host_entry.hpp"
 
 struct epik_amd_builder {
@@ -56,6 +59,8 @@ struct epik_amd_builder {
     uint64_t *d_offsets = nullptr;
     epik_amd_pkdb_value *d_values = nullptr;
     epik_amd::build_result host;
+    // what builder_rank keeps between calls: the ranking's scratch, and value | order of the last call
+    epik_amd::FilterScratch rank_scratch, rank_out;
 };
 
 namespace {
@@ -626,6 +631,38 @@ int epik_amd_builder_copy(epik_amd_builder *builder, uint32_t *keys, uint64_t *o
     return EPIK_AMD_OK;
 }
 
+int epik_amd_builder_rank(epik_amd_builder *builder, uint32_t filter, uint64_t seed, double *value, uint32_t *order)
+{
+    if (!builder) return fail_with(EPIK_AMD_ERR_INVALID, "null builder");
+    if (!builder->finished) return fail_with(EPIK_AMD_ERR_INVALID, "builder_rank before builder_finish");
+    const uint64_t K = builder->num_keys;
+    if (K && (!value || !order)) return fail_with(EPIK_AMD_ERR_INVALID, "null host buffer");
+    try {
+        std::string err;
+        if (builder->device < 0) {
+            const int rc = filter_rank_host(builder->num_branches, builder->log_thr, builder->host.keys.data(), builder->host.offsets.data(),
+                                            builder->host.values.data(), K, filter, seed, 1, value, order, err);
+            return rc == EPIK_AMD_OK ? rc : fail_with(rc, err);
+        }
+        if (const int rc = filter_check_params(builder->num_branches, builder->log_thr, filter, err); rc != EPIK_AMD_OK) return fail_with(rc, err);
+        if (K == 0) return EPIK_AMD_OK;
+        HIP_TRY(hipSetDevice(builder->device));
+        const uint64_t o_order = align_up(K * sizeof(double));  // value | order on the device, kept by the handle
+        if (const int rc = filter_scratch_reserve(builder->rank_out, o_order + K * sizeof(uint32_t), builder->stream); rc != EPIK_AMD_OK) return rc;
+        uint8_t *base = static_cast<uint8_t *>(builder->rank_out.base);
+        if (const int rc = filter_rank_on_device(builder->device, builder->num_branches, builder->log_thr, builder->d_keys, builder->d_offsets,
+                                                 builder->d_values, K, filter, seed, reinterpret_cast<double *>(base),
+                                                 reinterpret_cast<uint32_t *>(base + o_order), builder->stream, &builder->rank_scratch);
+            rc != EPIK_AMD_OK)
+            return rc;
+        HIP_TRY(hipMemcpy(value, base, K * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(order, base + o_order, K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return EPIK_AMD_OK;
+    } catch (const std::exception &e) {
+        return fail_with(EPIK_AMD_ERR_INVALID, std::string("builder_rank: ") + e.what());
+    }
+}
+
 void epik_amd_builder_destroy(epik_amd_builder *builder)
 {
     if (!builder) return;
@@ -633,6 +670,7 @@ void epik_amd_builder_destroy(epik_amd_builder *builder)
         (void)hipSetDevice(builder->device);
         if (builder->stream) (void)hipStreamSynchronize(builder->stream);
         free_finished(builder);
+        filter_scratch_free(builder->rank_scratch), filter_scratch_free(builder->rank_out);
         if (builder->store_packed) (void)hipFree(builder->store_packed);
         if (builder->store_score) (void)hipFree(builder->store_score);
         if (builder->ws) (void)hipFree(builder->ws);

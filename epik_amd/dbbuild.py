@@ -336,12 +336,62 @@ def check_build_options(states: str, kmer_size: int, omega: float, chunk: int) -
         raise BuildInputError(f"--chunk must be at least 1, not {chunk}")
 
 
+def check_filter_options(filter: str, filter_seed) -> None:
+    """--filter and --filter-seed: what can be refused before a file is opened."""
+    from . import filters
+    if filter not in filters.FILTERS:
+        raise BuildInputError(f"--filter: '{filter}' is no filter (one of {', '.join(filters.FILTERS)})")
+    if filter_seed is not None and filter != "random":
+        raise BuildInputError("--filter-seed needs --filter random")
+    if filter_seed is not None and not 0 <= int(filter_seed) < 2 ** 64:
+        raise BuildInputError(f"--filter-seed must be a uint64, not {filter_seed}")
+
+
+def ranked_order(db, filter: str, filter_seed, host: bool = False, num_threads: int = 1, device: int = 0):
+    """The order dbfile.write_db is given for `filter`: None for "best" (its own, unchanged), else the ranking's."""
+    from . import filters
+    if filter == "best":
+        return None
+    return filters.rank_db(db, filter, filter_seed or 0, host=host, num_threads=num_threads, device=device)[1]
+
+
+def rerank_file(in_path: str, out_path: str, filter: str, filter_seed=None, host: bool = False, num_threads: int = 1,
+                device: int = 0) -> dict:
+    """`epik.py rank`: a database file read whole (mu = 1, its own omega), ranked by `filter`, written to out_path."""
+    import struct
+
+    from . import dbfile, filters
+    check_filter_options(filter, filter_seed)
+    try:
+        with open(in_path, "rb") as fh:
+            head = fh.read(24)
+        if len(head) < 24 or head[:8] != dbfile.MAGIC:
+            raise RuntimeError(f"{in_path} is not an EPIKAMD1 file")
+        built_omega = struct.unpack("<f", head[20:24])[0]
+        dense, text = dbfile.read_db(in_path, mu=1.0, omega=built_omega)
+    except (RuntimeError, OSError, struct.error) as err:
+        raise BuildInputError(str(err)) from None
+    lens = np.diff(dense.offsets.astype(np.int64))
+    keys = np.flatnonzero(lens)
+    offsets = np.zeros(len(keys) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum(lens[keys])
+    db = dense
+    db.keys, db.offsets = keys.astype(np.uint32), offsets      # the sparse form of the same lists: values stay as they lie
+    db.omega = built_omega                                     # (the header's own float32, written back bit for bit)
+    order = filters.rank_db(db, filter, filter_seed or 0, host=host, num_threads=num_threads, device=device)[1]
+    dbfile.write_db(out_path, db, text, order=order)
+    return dict(num_keys=len(keys), num_entries=int(db.values.shape[0]), num_branches=db.num_branches)
+
+
 def build_from_files(tree_path: str, ar_probs: str, ar_tree: str, states: str, kmer_size: int, omega: float, out_path: str,
-                     ghosts: str = "both", chunk: int = 256, device: int = 0, workspace_bytes: int = 0, host: bool = False) -> dict:
+                     ghosts: str = "both", chunk: int = 256, device: int = 0, workspace_bytes: int = 0, host: bool = False,
+                     filter: str = "best", filter_seed: int | None = None) -> dict:
     """`epik.py build`.  host=True runs the host mirror over all ghost nodes at once instead of the device builder
-    (no GPU: tests of the file side)."""
+    (no GPU: tests of the file side).  `filter` ranks the k-mers of the file (epik_amd/filters.py); "best" is the order
+    dbfile.write_db has always written."""
     from . import build, dbfile
     check_build_options(states, kmer_size, omega, chunk)
+    check_filter_options(filter, filter_seed)
     if ghosts not in GHOST_CHOICES:
         raise BuildInputError(f"--ghosts must be one of {', '.join(GHOST_CHOICES)}, not '{ghosts}'")
     tree, text = read_reference_tree(tree_path)
@@ -395,11 +445,13 @@ def build_from_files(tree_path: str, ar_probs: str, ar_tree: str, states: str, k
         logp = np.concatenate([c[0] for c in chunks]) if chunks else np.zeros((0, kmer_size, sigma), np.float32)
         branch_of = np.concatenate([c[1] for c in chunks]) if chunks else np.zeros(0, np.uint32)
         db = build.build_host(states, kmer_size, n, logp, branch_of, omega=omega)
+        order = ranked_order(db, filter, filter_seed, host=True)
     else:
         with build.Builder(states, kmer_size, n, omega=omega, device=device, workspace_bytes=workspace_bytes) as builder:
             stream(builder)
             db = builder.finish()
-    dbfile.write_db(out_path, db, text)
+            order = None if filter == "best" else builder.rank(filter, filter_seed or 0)[1]
+    dbfile.write_db(out_path, db, text, order=order)
     return dict(num_keys=int(db.keys.shape[0]), num_entries=db.num_entries, ghost_nodes=len(wanted), num_branches=n)
 
 
@@ -424,11 +476,13 @@ def write_ar_files(probs_path: str, tree_out_path: str, tree: newick.Tree, state
 def build_from_alignment(tree_path: str, fasta_path: str, model: str, states: str, kmer_size: int, omega: float, out_path: str,
                          model_file: str | None = None, ghosts: str = "both", reduction: float | None = None, chunk: int = 256,
                          device: int = 0, workspace_bytes: int = 0, host: bool = False, num_threads: int = 1,
-                         write_ar_probs: str | None = None, write_ar_tree: str | None = None) -> dict:
+                         write_ar_probs: str | None = None, write_ar_tree: str | None = None, filter: str = "best",
+                         filter_seed: int | None = None) -> dict:
     """`epik.py reconstruct`: tree and alignment to a database, the ancestral posteriors computed here.  host=True runs
-    the host mirrors of the reconstruction and of the builder (no GPU)."""
+    the host mirrors of the reconstruction, of the builder and of the ranking (no GPU)."""
     from . import ancestral, build, dbfile
     check_build_options(states, kmer_size, omega, chunk)
+    check_filter_options(filter, filter_seed)
     if ghosts not in GHOST_CHOICES:
         raise BuildInputError(f"--ghosts must be one of {', '.join(GHOST_CHOICES)}, not '{ghosts}'")
     if bool(write_ar_probs) != bool(write_ar_tree):
@@ -462,11 +516,13 @@ def build_from_alignment(tree_path: str, fasta_path: str, model: str, states: st
     n = tree.num_nodes
     if host:
         db = build.build_host(states, kmer_size, n, build.logp_from_posteriors(post), branch_of, omega=omega, num_threads=num_threads)
+        order = ranked_order(db, filter, filter_seed, host=True, num_threads=num_threads)
     else:
         with build.Builder(states, kmer_size, n, omega=omega, device=device) as builder:
             for g in range(0, post.shape[0], chunk):
                 builder.add(build.logp_from_posteriors(post[g:g + chunk]), branch_of[g:g + chunk])
             db = builder.finish()
-    dbfile.write_db(out_path, db, text)
+            order = None if filter == "best" else builder.rank(filter, filter_seed or 0)[1]
+    dbfile.write_db(out_path, db, text, order=order)
     return dict(num_keys=int(db.keys.shape[0]), num_entries=db.num_entries, ghost_nodes=int(post.shape[0]), num_branches=n,
                 sites=int(post.shape[1]), dead_sites=int(dead), categories=parsed.num_categories)

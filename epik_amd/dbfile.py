@@ -42,8 +42,37 @@ def informativeness_order(offsets: np.ndarray, values: np.ndarray) -> np.ndarray
     return keys[np.lexsort((keys, -best.astype(np.float64)))]
 
 
-def write_db(path: str, db: SynthDB, newick: str) -> None:
-    order = informativeness_order(db.offsets, db.values)
+#: keys whose records write_db assembles at a time
+WRITE_BLOCK_KEYS = 1 << 16
+
+
+def _records(keys, codes, offs, pairs) -> bytes:
+    """The records of the lists `keys`, in that order: { u32 code | u32 n | n x { u32 branch, f32 score } } each."""
+    begin = offs[keys]
+    n = offs[keys + 1] - begin
+    start = np.zeros(len(keys), dtype=np.int64)          # of every record, in 32-bit words
+    np.cumsum(2 + 2 * n[:-1], out=start[1:])
+    words = np.empty(int(2 * len(keys) + 2 * n.sum()), dtype="<u4")
+    words[start] = keys if codes is None else codes[keys]
+    words[start + 1] = n
+    within = np.arange(int(n.sum()), dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)
+    source = np.repeat(begin, n) + within
+    dest = np.repeat(start + 2, n) + 2 * within
+    words[dest] = pairs[source, 0]
+    words[dest + 1] = pairs[source, 1]
+    return words.tobytes()
+
+
+def write_db(path: str, db: SynthDB, newick: str, order=None) -> None:
+    """Writes `db` with its k-mers in `order` (indices of its lists, most informative first: epik_amd/filters.py);
+    None: informativeness_order, the order this function has always written."""
+    if order is None:
+        order = informativeness_order(db.offsets, db.values)
+    else:
+        order = np.ascontiguousarray(order).astype(np.int64)
+        lists = int(db.offsets.shape[0] - 1)
+        if order.ndim != 1 or (len(order) and (order.min() < 0 or order.max() >= lists)) or len(np.unique(order)) != len(order):
+            raise ValueError(f"order must hold different indices of the {lists} lists")
     with open(path, "wb") as fh:
         fh.write(MAGIC)
         fh.write(struct.pack("<IIIf", VERSION, 0 if db.states == "nucl" else 1, db.kmer_size,
@@ -54,11 +83,12 @@ def write_db(path: str, db: SynthDB, newick: str) -> None:
         offs = db.offsets.astype(np.int64)
         crc = 0
         codes = getattr(db, "keys", None)  # the sparse form: list i belongs to code keys[i] (ascending, as the lists are)
-        for key in order:
-            b, e = int(offs[key]), int(offs[key + 1])
-            record = struct.pack("<II", int(key) if codes is None else int(codes[key]), e - b) + db.values[b:e].tobytes()
-            crc = zlib.crc32(record, crc)
-            fh.write(record)
+        pairs = np.ascontiguousarray(db.values, dtype=PKDB_VALUE).view("<u4").reshape(-1, 2)
+        order = np.asarray(order, dtype=np.int64)
+        for at in range(0, len(order), WRITE_BLOCK_KEYS):
+            block = _records(order[at:at + WRITE_BLOCK_KEYS], codes, offs, pairs)
+            crc = zlib.crc32(block, crc)
+            fh.write(block)
         fh.write(END_MAGIC + struct.pack("<QQII", len(order), db.num_entries, crc & 0xFFFFFFFF, 0))
 
 

@@ -31,14 +31,15 @@ int main(int argc, char** argv)
     using namespace epik_amd;
     // host_test load <file>: epik_amd::load by itself (tests/test_host_cpu.py hands it damaged containers; the driver
     // asks for its devices first)
-    // ... host_test load <file> <max_entries> <shard_index> <shard_count>: the k-mer codes that shard keeps
-    if ((argc == 3 || argc == 6) && std::string(argv[1]) == "load") {
+    // ... host_test load <file> <max_entries> <shard_index> <shard_count> [mu]: the k-mer codes that shard keeps (of the
+    // first mu of the file: tests/test_filter_cpu.py)
+    if ((argc == 3 || argc == 6 || argc == 7) && std::string(argv[1]) == "load") {
         try {
-            const size_t limit = argc == 6 ? (size_t)std::stoull(argv[3]) : std::numeric_limits<size_t>::max();
-            const auto db = load(argv[2], 1.0f, 1.5f, limit, argc == 6 ? (uint32_t)std::stoul(argv[4]) : 0u,
-                                 argc == 6 ? (uint32_t)std::stoul(argv[5]) : 1u);
+            const size_t limit = argc >= 6 ? (size_t)std::stoull(argv[3]) : std::numeric_limits<size_t>::max();
+            const auto db = load(argv[2], argc == 7 ? std::stof(argv[6]) : 1.0f, 1.5f, limit, argc >= 6 ? (uint32_t)std::stoul(argv[4]) : 0u,
+                                 argc >= 6 ? (uint32_t)std::stoul(argv[5]) : 1u);
             std::cout << "loaded " << db.get_num_entries_loaded() << " phylo-k-mers, version " << db.version() << std::endl;
-            if (argc == 6) {
+            if (argc >= 6) {
                 std::cout << "keys";
                 for (const auto key : db.keys()) std::cout << ' ' << key;
                 std::cout << std::endl;

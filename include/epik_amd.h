@@ -2133,6 +2133,86 @@ int epik_amd_model_pmatrices(uint32_t sigma, const double *exchange, const doubl
                              double *out);
 int epik_amd_model_gamma_rates(double alpha, uint32_t num_categories, double *rates);
 
+/*
+ * Ranking phylo-k-mers by informativeness: the order in which a database file stores its k-mers, which --mu and
+ * --max-ram cut a prefix of.  The rule below is this project's own reading of "informative k-mers" (EPIK;
+ * neither i2l nor IPK is available, so it is not IPK's formula: DESIGN.md, assumption register), worded so that the
+ * device, the host mirror and a numpy restatement give the same bytes.
+ *
+ * Inputs.  A database in the sparse CSR form that builder_copy returns: keys uint32 [K] ascending, offsets uint64
+ * [K + 1], values {branch, score}, branch ascending within a list, score a float32 log10 (at most 0, -inf allowed, no
+ * NaN); N = num_branches >= 1; log_thr a float32, at most 0 (-inf allowed); a filter id; a uint64 seed.
+ * Outputs.  value double [K], smaller = more informative, and order uint32 [K]: the permutation of 0 .. K - 1 sorted by
+ * (value ascending, key ascending), -0.0 counted as +0.0 (value[] holds +0.0 then).  A value is never a NaN (below).
+ *
+ * Arithmetic.  IEEE double, rounded to nearest, no contraction of multiply and add, every parenthesis as written.
+ *   LOG2_10 = 3.321928094887362, LN2 = 0.6931471805599453, TWO_OVER_LN2 = 2.8853900817779268,
+ *   SQRT_HALF = 0.7071067811865476 (the doubles nearest to those constants).
+ *   ek_exp2(x), x <= 1023:  +0.0 if x < -1022 (so -inf gives +0.0 and no result is subnormal); else n = rint(x) (ties to
+ *     even), r = x - n (exact), y = r * LN2, q = c_13, then q = q * y + c_j for j = 12 .. 0 with c_j the double nearest
+ *     to 1 / j!, and the result is ldexp(q, n) (exact: q lies in [0.70, 1.42] and x >= -1022 puts n = -1022 with r >= 0).
+ *   ek_log2(z), z > 0 finite:  z = m 2^e, m in [0.5, 1) (frexp); if m < SQRT_HALF then m = m * 2 and e = e - 1;
+ *     t = (m - 1.0) / (m + 1.0), u = t * t, q = d_11, then q = q * u + d_j for j = 10 .. 0 with d_j the double nearest to
+ *     1 / (2 j + 1), and the result is (double)e + (t * q) * TWO_OVER_LN2.  (ek_log2(0) = -inf, ek_log2(+inf) = +inf and
+ *     a NaN below 0: the rule never gets there.)
+ *   The literal coefficients stand in epik_amd/host/filter.hpp, which the kernels and the host mirror both compile.
+ *
+ * EPIK_AMD_FILTER_MIF0: the conditional entropy H(B | w), in bits, of the branch given the k-mer, a branch without an
+ * entry standing at the threshold probability.  For a list (b_i, s_i), i = 0 .. n - 1:
+ *     x_i = (double)s_i * LOG2_10,   p_i = ek_exp2(x_i),   q_i = +0.0 if p_i == 0.0, else p_i * x_i
+ *     A = SUM p_i,   B = SUM q_i                                               (SUM: below)
+ *     x_t = (double)log_thr * LOG2_10,   t = ek_exp2(x_t),   M = (double)(N - n) (0.0 if n >= N)
+ *     R = M * t,   C = +0.0 if R == 0.0, else R * x_t,   Z = A + R
+ *     value = +inf if Z == 0.0, else ek_log2(Z) - ((B + C) / Z)
+ *   SUM over the entries does not depend on the grid or on how many lanes serve a key: 64 interleaved chains, entry i
+ *   to chain i mod 64, each chain ((+0.0 + u_c) + u_{c+64}) + ... in ascending i, and the 64 chain sums combined by the
+ *   butterfly a[c] = a[c] + a[c + h] for c < h, for h = 32, 16, 8, 4, 2, 1; SUM is a[0].  Addition is commutative, so a
+ *   butterfly of lane exchanges (a[c] + a[c xor h] in every lane) gives the same bits.  Every p_i is >= +0.0 and every
+ *   q_i <= 0, a chain starts from +0.0, and x + (+0.0) is x for every x but -0.0, which it turns into +0.0: no chain
+ *   holds -0.0, the empty chains hold +0.0, and adding them changes nothing -- a list of n <= 64 entries may be summed
+ *   in closed form, n <= 4: ((+0.0 + u_0) + (+0.0 + u_2)) + ((+0.0 + u_1) + (+0.0 + u_3)) with +0.0 for an absent entry.
+ *   No NaN.  s_i = -inf or p_i = 0 contributes +0.0 to both sums (0 * -inf is never formed); log_thr = -inf gives
+ *   t = 0, R = 0 and C = +0.0; every p_i that is not 0 is at least 2^-1022 and at most 1, so A, B, R and C are finite,
+ *   Z is 0 or a normal number, and (B + C) / Z is finite (|x| <= 1022, so |B + C| <= 1022 Z).  Z == 0 (every entry at
+ *   p = 0 and t = 0) gives +inf: such a key is ranked last.  n = N gives M = 0; N = 1 with its one entry at s = 0 gives
+ *   ek_log2(1) - 0 / 1 = 0.  An empty list (builder_copy has none) follows the same formulas with A = B = +0.0.
+ * EPIK_AMD_FILTER_BEST: value = -(double)max_i s_i (+inf for an empty list): the order dbfile.informativeness_order
+ *   has always written.
+ * EPIK_AMD_FILTER_RANDOM: in uint64 arithmetic mod 2^64 (the splitmix64 finaliser, as the permutation tests' key),
+ *     z = seed + (uint64)key * 0x9E3779B97F4A7C15,  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9,
+ *     z = (z ^ z >> 27) * 0x94D049BB133111EB,  z = z ^ z >> 31,   value = (double)(z >> 11)   (exact: 53 bits).
+ *   The mix is a bijection; two keys whose z differ only in the low 11 bits tie and are ordered by key.
+ * Order.  value with -0.0 folded into +0.0 has the monotone image  u = bits ^ 0xFFFF.. if the sign bit is set, else
+ * bits | 2^63; order is the stable sort of 0 .. K - 1 by u.
+ *
+ *   filter_rank_device  keys, offsets, values, value and order are DEVICE arrays on `device`; the work is enqueued on
+ *       `stream` and the call returns after it has finished (the checks' findings and the bits in use of the images are
+ *       read back; the sort's scratch, 20 bytes a key and hipCUB's own, is allocated once per call).  K < 2^31.
+ *   filter_rank         the same with HOST arrays: uploaded, ranked on `device`, copied back.
+ *   builder_rank        after builder_finish: a device builder's own device arrays, nothing uploaded; the finished
+ *       result of epik_amd_build_host runs the host mirror on one thread.  value and order are HOST arrays [num_keys].
+ *       The builder keeps the scratch of the call (32 bytes a key and hipCUB's own) until it is destroyed.
+ *   filter_rank_host    the same rule in plain C++ on `num_threads` threads (0: one), no device.
+ *   filter_math_host    exp2_out[i] = ek_exp2(x[i]) and log2_out[i] = ek_log2(x[i]) (either may be NULL): tests.
+ * All refuse with EPIK_AMD_ERR_INVALID and a message that names the first offender: an unknown filter; offsets that
+ * are not ascending (offsets[k + 1] below offsets[k] or above offsets[K]); a score that is a NaN or above 0; a branch
+ * that is not below N -- in that order when several apply.  K = 0 is valid and touches no array.
+ */
+#define EPIK_AMD_FILTER_BEST 0u
+#define EPIK_AMD_FILTER_MIF0 1u
+#define EPIK_AMD_FILTER_RANDOM 2u
+int epik_amd_filter_rank_device(int device, uint32_t num_branches, float log_thr, const void *d_keys, const void *d_offsets,
+                                const void *d_values, uint64_t K, uint32_t filter, uint64_t seed, void *d_value,
+                                void *d_order, void *stream);
+int epik_amd_filter_rank(int device, uint32_t num_branches, float log_thr, const uint32_t *keys, const uint64_t *offsets,
+                         const epik_amd_pkdb_value *values, uint64_t K, uint32_t filter, uint64_t seed, double *value,
+                         uint32_t *order);
+int epik_amd_builder_rank(epik_amd_builder *builder, uint32_t filter, uint64_t seed, double *value, uint32_t *order);
+int epik_amd_filter_rank_host(uint32_t num_branches, float log_thr, const uint32_t *keys, const uint64_t *offsets,
+                              const epik_amd_pkdb_value *values, uint64_t K, uint32_t filter, uint64_t seed,
+                              uint32_t num_threads, double *value, uint32_t *order);
+int epik_amd_filter_math_host(const double *x, uint64_t n, double *exp2_out, double *log2_out);
+
 /* Which kernels the last launch of this handle ran (reports; a large-tree handle falls back from the three-kernel
  * placement to the one-kernel one when the device has no room for the scratch of a launch). */
 #define EPIK_AMD_PATH_WAVE 0u            /* place_reads_kernel: one wavefront per read */
