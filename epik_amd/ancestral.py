@@ -349,12 +349,16 @@ class Ancestral:
         self.dead_sites = int(dead.value)
         return post, branch_of, self.dead_sites
 
-    def posteriors_device(self, masks, ghosts="both") -> tuple:
-        """The same, left on the handle's device: torch tensors float32 [G][L][sigma] and int32 [G] (the bits of uint32)."""
+    def posteriors_device(self, masks, ghosts="both", out=None) -> tuple:
+        """The same, left on the handle's device: torch tensors float32 [G][L][sigma] and int32 [G] (the bits of uint32).
+        `out`: a contiguous float32 tensor of that shape on the device to write into (made when None)."""
         import torch
         ghosts, masks = _ghosts(ghosts), self._in.masks(masks)
         G = self._in.ghost_count(ghosts) if ghosts in GHOSTS.values() else 1
-        d_post = torch.zeros((G, masks.shape[1], self._in.sigma), dtype=torch.float32, device="cuda")
+        shape = (G, masks.shape[1], self._in.sigma)
+        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor of {shape} on the device")
+        d_post = torch.zeros(shape, dtype=torch.float32, device="cuda") if out is None else out
         d_branch_of = torch.zeros(G, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
         dead = ctypes.c_uint64()

@@ -62,8 +62,9 @@ def test_key_counts_around_the_tile_and_the_workgroup(num_keys):
 
 
 def test_tiles_that_mix_short_and_long_lists_under_the_grid_stride():
-    """About 70 000 keys, more tiles than the grid has waves: most keys have one entry, every tile a few lists longer than
-    64 x 4, and scores with many ties."""
+    """About 70 000 keys in 1 094 tiles on 274 workgroups, one tile a wave: most keys have one entry, every tile a few lists
+    longer than 64 x 4, and scores with many ties.  (The grid's own stride begins above 32 768 tiles; the second sweep is
+    test_build_seams_gpu.py's.)"""
     rng = np.random.default_rng(17)
     K, N = 70001, 400
     lengths = np.ones(K, dtype=np.int64)
